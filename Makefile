@@ -78,13 +78,14 @@ tests/emu/libsasa_emu.so: tests/emu/emu.cpp $(CSRC)/sasa_kernels.h $(CSRC)/sr_ca
 
 # Sanitizer build of the HOST sources (the reference's CI runs its C under sanitizers): the parsers,
 # the selection language, the C API shims and the test-point generator with AddressSanitizer + UBSan, linked with
-# the ordinary (uninstrumented) engine object.  `make asan-test` runs the CPU suites that exercise them.
+# the ordinary (uninstrumented) engine object; its objects stay in the tree (tests/emu/asan_*.o), so that builds by
+# different users of one machine do not share them.  `make asan-test` runs the CPU suites that exercise them.
 ASAN_SO = tests/emu/libfreesasa_amd_asan.so
 SANFLAGS = -O1 -g -std=gnu99 -fPIC -ffp-contract=off -Wall -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined
 asan: $(ASAN_SO)
 $(ASAN_SO): $(CSRC)/api.c $(CSRC)/seam.c $(CSRC)/testpoints.c $(CSRC)/ingest.c $(CSRC)/select.c $(CSRC)/ingest_cache.c $(CSRC)/hostfault.c $(CSRC)/hostfault.h $(CSRC)/protor_table.h $(GPU_OBJS) include/freesasa_amd.h include/freesasa_gpu.h include/freesasa_ingest.h
-	for f in api seam testpoints ingest select ingest_cache hostfault; do $(CC) $(SANFLAGS) -Iinclude -pthread -c $(CSRC)/$$f.c -o /tmp/asan_$$f.o || exit 1; done
-	$(CXX) -shared -fPIC -o $@ /tmp/asan_api.o /tmp/asan_seam.o /tmp/asan_testpoints.o /tmp/asan_ingest.o /tmp/asan_select.o /tmp/asan_ingest_cache.o /tmp/asan_hostfault.o $(GPU_OBJS) \
+	for f in api seam testpoints ingest select ingest_cache hostfault; do $(CC) $(SANFLAGS) -Iinclude -pthread -c $(CSRC)/$$f.c -o tests/emu/asan_$$f.o || exit 1; done
+	$(CXX) -shared -fPIC -o $@ $(foreach f,api seam testpoints ingest select ingest_cache hostfault,tests/emu/asan_$(f).o) $(GPU_OBJS) \
 	    -fsanitize=address,undefined -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib -lamdhip64 -lpthread -lm
 asan-test: $(ASAN_SO)
 	LD_PRELOAD="$$($(CC) -print-file-name=libasan.so) $$($(CC) -print-file-name=libubsan.so)" ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 \

@@ -9,16 +9,23 @@ slices, probe 1.4 A, fp64).  Multi-GPU: every rank owns its own 1000 structures 
 scaling, independent structures, no collective on the data path); the timed region is
 bracketed by barrier + synchronize and the MAX over ranks is reported.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--structs S] [--atoms A]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--structs S] [--atoms A] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs
+is given, and prints the headline line.  Everything else the benchmark measures or checks runs only
+with --full (the --no-* options then leave parts of it out).
+
+Rank 0 prints ONE JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...) with extra objects:
   roofline     — achieved = ALGORITHMIC bytes (40 B/atom: x,y,z,R in, SASA out) of the dominant
                  kernel (k_lr2_tile) / its HIP-event duration measured live on the launch stream;
+                 traffic from the committed profile, or (--full) from rocprofv3 passes of this run;
+--full only:
   end_to_end   — SURVEY 8(d)(i): the same batch from host arrays to host per-atom areas, PCIe included;
   cpu_baseline — the real reference (oracle/_ref, kind "reference") or the oracle port, timed on
                  this box's host cores on a bounded sample of the same batch (own process: one worker
-                 process per core, plus the reference's own n_threads 1 / 2 / 16 on one structure).
+                 process per core, plus the reference's own n_threads 1 / 2 / 16 on one structure);
+  and the sustained loop, the synchronous entry, the other configurations, the drivers' keys.
 """
 import argparse
 import json
@@ -607,8 +614,10 @@ def bench_trajectory(args, rank, world, local_rank):
     frames = np.stack([tools.jitter(base, 100 + f, 0.5) for f in range(n_frames)])
     fa.trajectory(frames[:16], r, per_atom=True, device=local_rank)            # warm-up
     t0 = time.perf_counter()
-    totals, _ = fa.trajectory(frames, r, per_atom=True, device=local_rank)
+    totals, sasa = fa.trajectory(frames, r, per_atom=True, device=local_rank)
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"totals": totals, "sasa": sasa})
     if rank == 0:
         print(json.dumps({"metric": "atom-frames/sec SASA (L&R 20 slices), host-resident trajectory",
                           "value": world * n_atoms * n_frames / dt, "unit": "atoms/s", "n_gpus": world,
@@ -686,6 +695,19 @@ def rank_driver_workloads(fa, tools, torch, dist, dev, rank, world, local_rank, 
     return out
 
 
+def dump_outputs(out_dir, arrays, limit_bytes=48 << 20):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64.  An array larger than its even share of
+    limit_bytes is replaced by a fixed sample of its elements (indices drawn with seed 0, in ascending order), so two
+    runs with the same arguments write the same elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = limit_bytes // len(arrays)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64).reshape(-1)
+        if a.nbytes > share:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, share // 8, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -707,11 +729,23 @@ def main():
     ap.add_argument("--no-neighbors", action="store_true", help="skip the neighbor count (one launch of the kernel's neighbor phase): the counter passes of tools/gpu_round.sh want the tile kernel's own launches only")
     ap.add_argument("--no-secondary", action="store_true", help="skip the short measurements of the other single-GPU configurations")
     ap.add_argument("--no-drivers", action="store_true", help="skip the file sweep / cache sweep / trajectory-file / latency keys (they write ~4 GB of scratch files under /tmp)")
-    ap.add_argument("--sustain-seconds", type=float, default=2.0, help="length of the sustained run reported next to the headline (0: none)")
+    ap.add_argument("--sustain-seconds", type=float, default=2.0, help="with --full: length of the sustained run reported next to the headline (0: none)")
     ap.add_argument("--dry-run", action="store_true",
                     help="TEST ONLY (tests/test_distributed.py): the rank / argument / JSON plumbing on CPU under gloo, "
                          "with a stand-in for the engine that computes nothing; prints \"dry_run\": true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64, at most 48 MiB in all: "
+                         "a fixed sample of the per-atom areas of a large batch)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: sustained loop, synchronous entry, neighbor count, rocprofv3 "
+                         "counter passes, other configurations, drivers, end-to-end, CPU baseline (the --no-* options leave parts out)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.sustain_seconds = 0
+        args.no_live_counters = args.no_cpu_baseline = args.no_end_to_end = True
+        args.no_neighbors = args.no_secondary = args.no_drivers = True
 
     import torch
     import torch.distributed as dist
@@ -839,6 +873,11 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        outputs = {"sasa": d_sasa.cpu().numpy(), "totals": d_tot.cpu().numpy()}
+        if sr:
+            outputs["counts"] = d_cnt.cpu().numpy()
+        dump_outputs(args.dump_outputs, outputs)
     if use_async:
         st = ctx.stats()
         k_ms = k_ms[2:] + [st["ms_kernel"]] if len(k_ms) > 2 else [st["ms_kernel"]]
@@ -947,7 +986,7 @@ def main():
             return
         if not sr and not args.no_neighbors:
             out["config"]["avg_neighbors_per_atom"] = neighbors_per_atom(fa, torch, d_xyz, d_r, offs, dev, local_rank)
-        if use_async and world == 1:
+        if use_async and world == 1 and args.full:
             # the synchronous entry on the same context: the same bits, and its rate for comparison
             got_async = d_sasa.clone()
             n_sync = max(5, args.steps // 2)

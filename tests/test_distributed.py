@@ -150,7 +150,7 @@ def test_bench_py_two_ranks_dry_run():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--structs", "5", "--atoms", "400", "--dry-run"]
+           "--structs", "5", "--atoms", "400", "--dry-run", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -217,6 +217,38 @@ def test_bench_py_one_rank_dry_run_with_the_process_group_forced():
     assert res["dry_run"] is True and res["config"]["process_group"].startswith("gloo world 1")
 
 
+def test_bench_py_dump_outputs_dry_run(tmp_path):
+    """--dump-outputs on CPU with --dry-run: after the timed steps the arrays a caller of the timed path receives (per-atom
+    areas, per-structure totals) are written as float64 .npy files; --steps is the number of timed steps."""
+    import json
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--structs", "4", "--atoms", "300", "--dry-run", "--dump-outputs", str(tmp_path / "out")]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    res = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+    assert res["steps"] == 3 and res["ms_per_step"] >= 2.0
+    assert sorted(os.listdir(tmp_path / "out")) == ["sasa.npy", "totals.npy"]
+    sasa, totals = np.load(tmp_path / "out" / "sasa.npy"), np.load(tmp_path / "out" / "totals.npy")
+    assert sasa.dtype == np.float64 and sasa.shape == (4 * 300,) and totals.dtype == np.float64 and totals.shape == (4,)
+
+
+def test_bench_py_dump_outputs_samples_a_large_output(tmp_path):
+    """An output larger than its share of the dump's limit is written as the same fixed sample on every run."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big = np.arange(10_000, dtype=np.float64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"sasa": big, "totals": big[:10]}, limit_bytes=2 * 8 * 1000)
+    a, b = np.load(tmp_path / "a" / "sasa.npy"), np.load(tmp_path / "b" / "sasa.npy")
+    assert a.shape == (1000,) and np.array_equal(a, b) and np.all(np.diff(a) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "totals.npy"), big[:10])
+
+
 @pytest.mark.gpu
 def test_bench_py_one_rank_initialises_rccl_on_the_gpu():
     """Round-4 review, item 6: bench.py's multi-rank plumbing ran only for world > 1, i.e. never on hardware before the
@@ -231,7 +263,7 @@ def test_bench_py_one_rank_initialises_rccl_on_the_gpu():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), FREESASA_AMD_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--structs", "60", "--atoms", "5000", "--sustain-seconds", "0.5", "--no-live-counters", "--no-cpu-baseline",
+           "--structs", "60", "--atoms", "5000", "--full", "--sustain-seconds", "0.5", "--no-live-counters", "--no-cpu-baseline",
            "--no-end-to-end", "--no-secondary", "--no-neighbors", "--no-drivers"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -240,3 +272,29 @@ def test_bench_py_one_rank_initialises_rccl_on_the_gpu():
     res = json.loads(lines[0])
     assert res["config"]["process_group"].startswith("nccl world 1")
     assert res["n_gpus"] == 1 and res["value"] > 1e7 and res["sustained"]["seconds"] >= 0.5 and res["sustained"]["value"] > 1e7
+
+
+@pytest.mark.gpu
+def test_bench_py_plain_run_dumps_what_the_timed_path_computed(tmp_path):
+    """A plain bench.py run on the MI355X: the headline line without the --full keys, and --dump-outputs writes the
+    per-atom areas and per-structure totals of the last timed step - the engine's areas for the same seeded batch."""
+    import json
+    import numpy as np
+    import freesasa_amd as fa
+    import tools
+    structs, atoms = 20, 2000
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--structs", str(structs), "--atoms", str(atoms), "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    assert res["steps"] == 2 and res["ms_per_step"] > 0 and res["value"] > 0
+    for key in ("sustained", "synchronous_entry", "contained_caps_off", "end_to_end", "cpu_baseline"):
+        assert key not in res
+    xyz, r, offs = tools.coil_batch(structs, atoms, seed0=1000)
+    want, _, want_tot = fa.calc_batch(xyz, r, offs, fa.LEE_RICHARDS, 1.4, 20)
+    sasa, totals = np.load(tmp_path / "sasa.npy"), np.load(tmp_path / "totals.npy")
+    assert sasa.shape == (structs * atoms,) and totals.shape == (structs,)
+    assert np.max(np.abs(sasa - want)) < 1e-8 and np.max(np.abs(totals - want_tot)) < 1e-6

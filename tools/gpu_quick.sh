@@ -11,7 +11,7 @@ else
 fi
 tail -25 $O/${TAG}_pytest_gpu.log
 if [ "${BENCH:-1}" = "1" ]; then
-  (timeout 900 python bench.py ${BENCH_ARGS}) > $O/${TAG}_bench.out 2> $O/${TAG}_bench.err; echo "bench rc=$?" >> $O/${TAG}_bench.err
+  (timeout 900 python bench.py --full ${BENCH_ARGS}) > $O/${TAG}_bench.out 2> $O/${TAG}_bench.err; echo "bench rc=$?" >> $O/${TAG}_bench.err
   grep '^{' $O/${TAG}_bench.out | tail -1 > $O/${TAG}_bench.json
   tail -3 $O/${TAG}_bench.err
   python - $O/${TAG}_bench.json <<'PY'

@@ -11,7 +11,7 @@ O=$REPO/gpurun_out
 (timeout 300 python -c "import __graft_entry__ as g; g.smoke()") > $O/${TAG}_smoke.log 2>&1; echo "smoke rc=$?" >> $O/${TAG}_smoke.log
 (timeout 900 python -m pytest tests -m gpu -q -s --durations=5) > $O/${TAG}_pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $O/${TAG}_pytest_gpu.log
 grep "adversarial" $O/${TAG}_pytest_gpu.log > $O/${TAG}_adversarial.txt
-(timeout 900 python bench.py) > $O/${TAG}_bench.out 2> $O/${TAG}_bench.err; echo "bench rc=$?" >> $O/${TAG}_bench.err
+(timeout 900 python bench.py --full) > $O/${TAG}_bench.out 2> $O/${TAG}_bench.err; echo "bench rc=$?" >> $O/${TAG}_bench.err
 grep '^{' $O/${TAG}_bench.out | tail -1 > $O/${TAG}_bench.json
 export TMPDIR=/tmp
 cd /tmp
