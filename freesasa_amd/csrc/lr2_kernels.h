@@ -14,7 +14,8 @@
  *                  hits keep (xd, yd, zd, Rj) in LDS — no second fetch of a neighbor
  *   P2 offsets     the atoms' lists in the pool; whether the tile fits the launch
  *   (caps)         round 6, "P1.5" in the tables: hits whose cap on the atom's sphere lies inside another hit's cap are
- *                  dropped - their arcs lie inside the other's on every slice (lr2_prune_contained); offsets again
+ *                  dropped - their arcs lie inside the other's on every slice (lr2_prune_contained); the kept hits
+ *                  closed up (P3 makes fewer rounds of records); offsets again
  *   P3 pairs       per (atom, neighbor): beta = atan2(yd, xd) + pi and the two coefficients of
  *                  2 Ri' cos(alpha) = b' + a' t, LINEAR in the slice height t (see lr2_record);
  *                  lists sorted by beta
@@ -729,7 +730,6 @@ SASA_D double lr2_acos_lower(double c)
 #ifndef LR2_PRUNE_LIST
 #define LR2_PRUNE_LIST 4   /* caps in one of an atom's two lists.  MI355X, final form, kernel ms on coils at 20 / 100 slices (mean of three runs): 2: 2.86 / 2.71, 3: 2.78 / 2.59, 4: 2.78 / 2.56, 6: 2.77 / 2.54 */
 #endif
-#define LR2_DEAD_TAG 0xff  /* tag of a dropped hit (atoms of a tile: < 8) */
 struct __attribute__((aligned(16))) Lr2Cap { float x, y, z, c; };
 SASA_HD int lr2_prune_arg(int want, int TA, int pool) /* Lr2Args::prune: > 0 on (the chooser's figure, at most what a list holds), 0: off */
 {
@@ -748,11 +748,36 @@ SASA_HD int lr2_prune_arg(int want, int TA, int pool) /* Lr2Args::prune: > 0 on 
    atom, filled in order of arrival - lost 2 - 5 % there). */
 static inline int lr2_prune_want(int ns, bool dense) { return ns >= 32 ? 4 : (dense ? 0 : 3); }
 SASA_D int lr2_cap_bin(float c) { const int b = (int)fmaf(c, 10.0f, -2.0f); return b < 0 ? 0 : (b > 7 ? 7 : b); } /* the cover filter's bins: 0.1 wide from 0.2 */
+/* The list: ALL hits of the leading bins that together hold no more than the list does - a set that depends on the
+   atom's neighbors alone, not on the order in which a tile of some shape found them: what is dropped, and with it
+   every path a tile takes from here on (an arc stack that is too short sends it to another launch), is the same
+   for every tile shape.  The bins' running sums byte-parallel (x 0x01010101 adds every byte to the ones above it),
+   then the first byte that exceeds the list (its bit 7 after adding 127 - LK); the bins before it are listed (-1:
+   none, the first bin alone is too many).  Every bin's count is first saturated at LK + 1 - enough to exceed the
+   list, and eight of them sum to less than 128 - so no running sum reaches bit 7 by itself or carries into the
+   next byte, whatever the counts (a side with 133 hits or more wrapped the sums until round 7, and which caps were
+   listed then followed their order of arrival).  (A byte itself does not wrap: the phase runs on tiles of at most
+   64 x LR2_PRUNE_ROUNDS hits.) */
+SASA_HD int lr2_prune_last_bin(unsigned long long h) /* h: the (atom, side)'s histogram, a byte per bin */
+{
+    constexpr int LK = LR2_PRUNE_LIST;
+    constexpr unsigned long long ones = 0x0101010101010101ull;
+    /* per byte min(count, LK + 1): a count >= 8 (bits 3..7, shifted down so that no byte carries into the next), or one of
+       the low three bits above LK + 1, sets the byte's bit 7 */
+    const unsigned long long big = (((h & (0xf8ull * ones)) >> 1) + 0x7cull * ones) & (0x80ull * ones);
+    const unsigned long long gt = (((h & (0x07ull * ones)) + (0x7full - (LK + 1)) * ones) & (0x80ull * ones)) | big;
+    const unsigned long long m8 = (gt >> 7) * 0xffull;
+    h = (h & ~m8) | ((unsigned long long)(LK + 1) * ones & m8);
+    const unsigned lo = (unsigned)h * 0x01010101u, hi = (unsigned)(h >> 32) * 0x01010101u + (lo >> 24) * 0x01010101u;
+    const unsigned add = (unsigned)(127 - LK) * 0x01010101u;
+    const unsigned mlo = (lo + add) & 0x80808080u, mhi = (hi + add) & 0x80808080u;
+    return (mlo ? __builtin_ctz(mlo) >> 3 : (mhi ? 4 + (__builtin_ctz(mhi) >> 3) : 8)) - 1;
+}
 /* Two lists per atom, one for either side of the x axis (the same-side rule above): a hit is tested against the largest caps
    of ITS side only - half the trips of one list for the same caps, and no side test inside the loop (per side the 4 largest
    caps drop 38 % of all records on coils, 35 % on 1a0q; all pairs: 43 / 44 %). */
 template <int RMAX>
-SASA_D void lr2_prune_contained(const Lr2Mem &m, int nh, int TA, int want, int lane)
+SASA_D int lr2_prune_contained(const Lr2Mem &m, int nh, int TA, int want, int lane)
 {
     constexpr int LK = LR2_PRUNE_LIST;
     (void)want; /* (on / off since the lists are chosen by the bins alone) */
@@ -786,21 +811,7 @@ SASA_D void lr2_prune_contained(const Lr2Mem &m, int nh, int TA, int want, int l
         }
     }
     LR2_SYNC();
-    if (lane < 2 * TA) {
-        /* The list: ALL hits of the leading bins that together hold no more than the list does - a set that depends on the
-           atom's neighbors alone, not on the order in which a tile of some shape found them: what is dropped, and with it
-           every path a tile takes from here on (an arc stack that is too short sends it to another launch), is the same
-           for every tile shape.  The bins' running sums byte-parallel (x 0x01010101 adds every byte to the ones above it;
-           sums beyond 255 carry into the next byte and at worst list nothing - an atom with that many hits on one side has
-           left this launch long before), then the first byte that exceeds the list (its bit 7 after adding 127 - LK); the
-           bins before it are listed (-1: none, the first bin alone is too many). */
-        const unsigned long long h = chist[lane];
-        const unsigned lo = (unsigned)h * 0x01010101u, hi = (unsigned)(h >> 32) * 0x01010101u + (lo >> 24) * 0x01010101u;
-        const unsigned add = (unsigned)(127 - LK) * 0x01010101u;
-        const unsigned mlo = (lo + add) & 0x80808080u, mhi = (hi + add) & 0x80808080u;
-        const int tb = (mlo ? __builtin_ctz(mlo) >> 3 : (mhi ? 4 + (__builtin_ctz(mhi) >> 3) : 8)) - 1;
-        chist[lane] = (unsigned long long)(long long)tb;
-    }
+    if (lane < 2 * TA) chist[lane] = (unsigned long long)(long long)lr2_prune_last_bin(chist[lane]);
     LR2_SYNC();
     for (int r = 0; r < RMAX; ++r) {
         const int li = lis[r];
@@ -815,30 +826,50 @@ SASA_D void lr2_prune_contained(const Lr2Mem &m, int nh, int TA, int want, int l
         }
     }
     LR2_SYNC();
+    /* The test, and the hits that stay closed up in place (order kept): P3 makes records for hits [0, return value) only, and a
+       round of records costs the wave the same whether it holds 64 hits or 6.  Random coils at 20 slices (emulation, tiles of
+       six atoms): 58 % of the tiles with two rounds of hits and 96 % of those with three keep one round less. */
+    unsigned kept = 0; /* bit r: the lane's hit of round r stays */
+#pragma unroll
     for (int r = 0; r < RMAX; ++r) {
         const int gp = lane + LR2_LANES * r;
         const int li = lis[r];
-        if (li < 0) continue;
-        const Lr2Cap *const L = bigc + LK * li;
-        const float *const S = (const float *)bigs + LK * li;
-        const float clim = cc[r] - 4e-6f, sj = LR2_CAP_SIN(cc[r]);
         bool inside = false;
-        int nb = fill[li];
-        nb = nb < LK ? nb : LK;
-        for (int k = 0; k < nb; ++k) { /* (the wave runs as many trips as its longest list) */
-            const Lr2Cap q = L[k];
-            const float dot = fmaf(nz[r], q.z, fmaf(ny[r], q.y, nx[r] * q.x));
-            const float rhs = fmaf(sj, S[k], fmaf(cc[r], q.c, 8e-6f));
-            inside = inside || (q.c <= clim && dot >= rhs); /* (a direction that is not a number compares false) */
+        if (li >= 0) {
+            const Lr2Cap *const L = bigc + LK * li;
+            const float *const S = (const float *)bigs + LK * li;
+            const float clim = cc[r] - 4e-6f, sj = LR2_CAP_SIN(cc[r]);
+            int nb = fill[li];
+            nb = nb < LK ? nb : LK;
+            for (int k = 0; k < nb; ++k) { /* (the wave runs as many trips as its longest list) */
+                const Lr2Cap q = L[k];
+                const float dot = fmaf(nz[r], q.z, fmaf(ny[r], q.y, nx[r] * q.x));
+                const float rhs = fmaf(sj, S[k], fmaf(cc[r], q.c, 8e-6f));
+                inside = inside || (q.c <= clim && dot >= rhs); /* (a direction that is not a number compares false) */
+            }
+            if (inside) SASA_ATOMIC_ADD_LDS(&m.acnt[li >> 1], -1);
         }
-        if (inside) {
-            m.tag[gp] = (unsigned char)LR2_DEAD_TAG;
-            SASA_ATOMIC_ADD_LDS(&m.acnt[li >> 1], -1);
-        }
+        if (gp < nh && !inside) kept |= 1u << r;
+    }
+    int nk = 0; /* hits kept in the rounds so far (wave-uniform) */
+#pragma unroll
+    for (int r = 0; r < RMAX; ++r) {
+        const int gp = lane + LR2_LANES * r;
+        const bool keep = (kept >> r) & 1u;
+        const unsigned long long km = LR2_BALLOT(keep);
+        const int dst = nk + LR2_RANK(km, lane);
+        const bool move = keep && dst != gp; /* (dst <= gp: a hit moves down into a place that is read already) */
+        double hx = 0, hy = 0, hz = 0, hw = 0; /* (the hit as four numbers: a Quad here was kept in scratch) */
+        int tg = 0;
+        if (move) { const Quad q = m.hits[gp]; hx = q.x; hy = q.y; hz = q.z; hw = q.w; tg = m.tag[gp]; }
+        LR2_SYNC(); /* (every lane has read its hit before any writes over it) */
+        if (move) { Quad q; q.x = hx; q.y = hy; q.z = hz; q.w = hw; m.hits[dst] = q; m.tag[dst] = (unsigned char)tg; }
+        nk += LR2_POPC64(km);
     }
 #undef LR2_CAP_LIST
 #undef LR2_CAP_SIN
     LR2_SYNC();
+    return nk;
 }
 
 /* ---------------------------------------------------------------- P0's global loads, one tile ahead
@@ -1127,12 +1158,13 @@ SASA_D int lr2_tile(const Lr2Args &a, const Lr2Mem &m, int p0, int na, bool samp
        whatever could be dropped from them, so the same atoms go through the same launches with the phase on and off (the
        last launch, for atoms with lists beyond any tile's, has the first-generation kernel's arithmetic: equal to 1e-11,
        not to the bit), and the pool's demand statistics are those of the lists as found. */
+    int nr = nh; /* hits P3 makes records of: [0, nr) */
     if (LR2_PRUNE && !HOOKS) {
         const int pk = LR2_COLD(a, prune);
         /* (uniform; a tile with more rounds of hits than the build holds in registers is not pruned) */
         constexpr int PR = RMAX < LR2_PRUNE_ROUNDS(PAIRS) ? RMAX : LR2_PRUNE_ROUNDS(PAIRS);
         if (pk > 0 && nh > 0 && nh <= LR2_LANES * PR) {
-            lr2_prune_contained<PR>(m, nh, TA, pk, lane);
+            nr = lr2_prune_contained<PR>(m, nh, TA, pk, lane);
             const int c = lane < TA ? m.acnt[lane] : 0, pc = (c + 1) & ~1; /* the offsets again, of the lists that are left */
             const int incl = lr2_scan_add(pc, lane), cmax = lr2_scan_max16(c, lane);
             if (lane < TA) m.aoff[lane] = incl - pc;
@@ -1169,10 +1201,9 @@ SASA_D int lr2_tile(const Lr2Args &a, const Lr2Mem &m, int p0, int na, bool samp
             const int gp = lane + LR2_LANES * r;
             r_pos[r] = -1;
             r_cb[r] = 0;
-            if (gp < nh) {
+            if (gp < nr) {
                 const Quad hq = m.hits[gp];
                 const int la = (int)m.tag[gp];
-                if (la == LR2_DEAD_TAG) continue; /* a cap inside another (P1.5) */
                 const int sa = SASA_ATOMIC_ADD_LDS(&m.gsz[la], 1); /* place in the atom's list, in order of discovery (gsz: zero since P0) */
                 const int o = m.aoff[la];
                 const double ri = m.atom[la].w;
