@@ -117,6 +117,11 @@ def lib():
         L.freesasa_gpu_class_sums_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _lp, C.c_int, C.c_void_p]
         L.freesasa_gpu_residue_areas_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _lp, C.c_int,
                                                      C.POINTER(C.c_short), _dp, C.c_int, C.c_void_p, C.c_void_p]
+        _i32p = C.POINTER(C.c_int32)
+        L.freesasa_gpu_groups_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _lp, C.c_int, C.c_void_p, _i32p,
+                                              C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.freesasa_gpu_calc_groups.argtypes = [_dp, _dp, _lp, C.c_int, _i32p, _i32p, C.c_int, C.c_double, C.c_int,
+                                               _dp, _dp, _dp, _dp, C.c_int, C.c_char_p, C.c_int]
         L.freesasa_gpu_test_points.argtypes = [C.c_int, _dp]
         L.freesasa_gpu_test_points.restype = None
         L.freesasa_gpu_calc_batch.argtypes = [_dp, _dp, _lp, C.c_int, C.c_int, C.c_double, C.c_int,
@@ -201,6 +206,30 @@ def calc_batch(xyz, radii, offsets, alg=LEE_RICHARDS, probe=1.4, resolution=20, 
     if ret:
         raise RuntimeError("freesasa_gpu_calc_batch: " + err.value.decode())
     return sasa, counts, totals
+
+
+def calc_groups(xyz, radii, offsets, group, n_groups, alg=LEE_RICHARDS, probe=1.4, resolution=20, device=-1):
+    """freesasa_gpu_calc_groups() on host arrays: (sasa, iso, totals, group_totals[G, 3]).  group: an int32 id per atom,
+    local to its structure (-1: in no group); n_groups: groups per structure.  iso - sasa is each atom's buried area;
+    group_totals rows are (isolated, complex, buried) per group, structure-major."""
+    xyz, radii = _f64(xyz).reshape(-1), _f64(radii)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    group = np.ascontiguousarray(group, dtype=np.int32)
+    n_groups = np.ascontiguousarray(n_groups, dtype=np.int32)
+    n, ns = radii.size, offsets.size - 1
+    if group.size != n or n_groups.size != ns:
+        raise ValueError("group needs one id per atom and n_groups one count per structure")
+    G = int(n_groups.astype(np.int64).sum())
+    sasa, iso, totals, gt = np.empty(n), np.empty(n), np.empty(ns), np.empty((max(G, 0), 3))
+    err = C.create_string_buffer(512)
+    i32 = C.POINTER(C.c_int32)
+    ret = lib().freesasa_gpu_calc_groups(xyz.ctypes.data_as(_dp), radii.ctypes.data_as(_dp), offsets.ctypes.data_as(_lp), ns,
+                                         group.ctypes.data_as(i32), n_groups.ctypes.data_as(i32), alg, probe, resolution,
+                                         sasa.ctypes.data_as(_dp), iso.ctypes.data_as(_dp), totals.ctypes.data_as(_dp),
+                                         gt.ctypes.data_as(_dp), device, err, 512)
+    if ret:
+        raise RuntimeError("freesasa_gpu_calc_groups: " + err.value.decode())
+    return sasa, iso, totals, gt
 
 
 def calc_batch_devices(xyz, radii, offsets, devices, alg=LEE_RICHARDS, probe=1.4, resolution=20):
@@ -512,6 +541,19 @@ class GpuContext:
             rt.ctypes.data_as(_dp) if rt is not None else None, (rt.size // 5) if rt is not None else 0, d_abs, d_rel)
         if ret:
             raise RuntimeError("freesasa_gpu_residue_areas_dev: " + self.error())
+
+    def groups(self, d_xyz, d_radii, offsets, d_group, n_groups, d_sasa, d_iso, d_totals=0, d_group_totals=0,
+               alg=LEE_RICHARDS, probe=1.4, resolution=20):
+        """freesasa_gpu_groups_dev(): complex areas (d_sasa), areas of every atom in its isolated group (d_iso), totals
+        and per-group (isolated, complex, buried) totals (d_group_totals [3 G]); d_group is a device int32 array,
+        n_groups a host array of groups per structure."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        ng = np.ascontiguousarray(n_groups, dtype=np.int32)
+        ret = lib().freesasa_gpu_groups_dev(self._h, alg, d_xyz, d_radii, offsets.ctypes.data_as(_lp), offsets.size - 1,
+                                            d_group, ng.ctypes.data_as(C.POINTER(C.c_int32)), probe, resolution, d_sasa,
+                                            d_iso, d_totals or None, d_group_totals or None)
+        if ret:
+            raise RuntimeError("freesasa_gpu_groups_dev: " + self.error())
 
     def shrake_rupley(self, d_xyz, d_radii, offsets, d_sasa, d_counts=0, d_totals=0, probe=1.4,
                       n_points=100):

@@ -9,6 +9,7 @@
  *   gpu_ops.hip        device-side aggregates (segments, classes, residues) and the kernel test hooks
  *   gpu_hostbatch.hip  host-pointer batches: the context pool, one device, several devices, the pipelined form
  *   gpu_drivers.hip    file sweep and trajectory drivers (one device or a list of devices), done-lists
+ *   gpu_groups.hip     chain groups: a batch and every group of it cut out as a structure of its own, in one batch
  */
 #ifndef FREESASA_AMD_ENGINE_INTERNAL_H
 #define FREESASA_AMD_ENGINE_INTERNAL_H
@@ -24,6 +25,7 @@
 #include "../../include/freesasa_ingest.h"
 #include "sasa_kernels.h"
 #include "lr2_kernels.h"
+#include "group_kernels.h"
 
 /* ------------------------------------------------------------------ kernel launchers (gpu_kernels.hip) */
 
@@ -56,6 +58,12 @@ hipError_t kl_arc_kat(const double *d_arcs, const int *d_first, int n_sets, doub
 hipError_t kl_widen_f32(const float *d_in, double *d_out, long long n, hipStream_t st);
 hipError_t kl_narrow_f64(const double *d_in, float *d_out, long long n, hipStream_t st);
 void kl_dump_phase_clocks(void); /* (dev builds with -DSASA_PHASE_TIMING; else nothing) */
+/* chain groups (group_kernels.h): count and validate (one thread per atom), the stable cut into the combined batch (one
+   wave per structure), the finish (one thread per combined atom), totals (one thread per group / structure) */
+hipError_t kl_grp_count(const sasa::GrpArgs &a, hipStream_t st);
+hipError_t kl_grp_rank(const sasa::GrpArgs &a, hipStream_t st);
+hipError_t kl_grp_finish(const sasa::GrpArgs &a, hipStream_t st);
+hipError_t kl_grp_totals(const sasa::GrpArgs &a, hipStream_t st);
 
 /* ------------------------------------------------------------------ context (gpu_engine.hip) */
 
@@ -103,8 +111,10 @@ struct freesasa_gpu_ctx {
     DevBuf captab;
     std::vector<sasa::SrCapEntry> captab_host;
     int captab_n = 0, captab_l = 0;    /* its resolution; 0: no table for these points (more than 128, not unit vectors, switched off) */
-    /* host staging for freesasa_gpu_calc_batch */
-    DevBuf h_xyz, h_radii, h_sasa, h_counts, h_totals;
+    /* host staging for freesasa_gpu_calc_batch (and freesasa_gpu_calc_groups: h_group, h_iso, h_gtot) */
+    DevBuf h_xyz, h_radii, h_sasa, h_counts, h_totals, h_group, h_iso, h_gtot;
+    /* chain groups (gpu_groups.hip): offsets and group bases, keys, counts, cursors, the combined batch, its results */
+    DevBuf g_meta, g_key, g_count, g_cursor, g_xyz, g_radii, g_src, g_sasa, g_gath, g_tot, g_tot2;
     void *stage_in = nullptr, *stage_out = nullptr; /* page-locked host staging of freesasa_gpu_calc_batch_pipelined */
     size_t stage_in_cap = 0, stage_out_cap = 0;
     int *pinned = nullptr; /* page-locked host words for the small device->host readbacks: two sets of ST_WORDS + 4 */

@@ -127,7 +127,9 @@ extern "C" void freesasa_gpu_ctx_destroy(freesasa_gpu_ctx *c)
     DevBuf *all[] = {&c->chunk_struct, &c->chunk_begin, &c->chunk_len, &c->struct_chunk0, &c->bpart, &c->offsets, &c->grid, &c->ncells, &c->sid, &c->cell_of, &c->rank, &c->cell_start,
                      &c->blk_sums, &c->cell_tbl, &c->cell_first, &c->sq, &c->s_idx,
                      &c->status, &c->ovf_tiles, &c->ovf_tiles2, &c->ovf_atoms, &c->unit_pts, &c->captab, &c->slab, &c->seg,
-                     &c->h_xyz, &c->h_radii, &c->h_sasa, &c->h_counts, &c->h_totals};
+                     &c->h_xyz, &c->h_radii, &c->h_sasa, &c->h_counts, &c->h_totals, &c->h_group, &c->h_iso, &c->h_gtot,
+                     &c->g_meta, &c->g_key, &c->g_count, &c->g_cursor, &c->g_xyz, &c->g_radii, &c->g_src, &c->g_sasa,
+                     &c->g_gath, &c->g_tot, &c->g_tot2};
     for (DevBuf *b : all)
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : c->parse)

@@ -1,0 +1,211 @@
+/*
+ * gpu_groups.hip — chain groups (include/freesasa_gpu.h, freesasa_gpu_groups_dev / freesasa_gpu_calc_groups): the area
+ * of every atom in its complex and in its group cut out as a structure of its own (ref: freesasa_structure_get_chains_lcl,
+ * src/structure.c:1026-1080, without the re-classification), in ONE batch.  Host code; the kernels are in
+ * gpu_kernels.hip (phase functions: group_kernels.h).
+ *
+ *   1. count and validate   k_grp_count: atoms per group, bad ids into the status words; the counts come back to the
+ *                           host (the batch's offsets are a host array)
+ *   2. stable cut           k_grp_rank: every group's atoms, in input order, behind the complex structures: one
+ *                           combined batch (32 bytes per atom: xyz and radius) and the source index of each atom
+ *   3. one run_batch        the complex and all its groups share one cell sort and one sequence of tile launches
+ *   4. finish               k_grp_finish (areas back to input order), the totals kernels over the groups' complex
+ *                           areas, k_grp_totals
+ */
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+#include <vector>
+
+#include "engine_internal.h"
+
+using namespace sasa;
+
+#define GRP_MAX_PER_STRUCT 65535
+
+static int groups_impl(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets,
+                       int n_structs, const int32_t *d_group, const int32_t *n_groups, double probe, int resolution,
+                       double *d_sasa, double *d_iso, double *d_totals, double *d_group_totals)
+{
+    c->err[0] = 0;
+    if (!d_xyz || !d_radii || !offsets || !d_group || !n_groups || !d_sasa || !d_iso) return ctx_fail(c, "null argument");
+    if (alg != 0 && alg != 1) return ctx_fail(c, "unknown algorithm %d", alg);
+    if (n_structs <= 0) return ctx_fail(c, "n_structs must be > 0");
+    if (resolution <= 0) return ctx_fail(c, "resolution must be > 0");
+    if (offsets[0] != 0) return ctx_fail(c, "offsets[0] must be 0");
+    for (int s = 0; s < n_structs; ++s)
+        if (offsets[s + 1] < offsets[s]) return ctx_fail(c, "offsets must be non-decreasing");
+    const int64_t n64 = offsets[n_structs];
+    if (n64 <= 0) return ctx_fail(c, "empty batch");
+    if (n64 > (int64_t)1 << 30) return ctx_fail(c, "batch too large (max 2^30 atoms per call)");
+    const int n = (int)n64;
+    /* offsets and the group bases, one upload */
+    std::vector<int64_t> meta(2 * ((size_t)n_structs + 1));
+    int64_t G64 = 0;
+    for (int s = 0; s < n_structs; ++s) {
+        if (n_groups[s] < 0 || n_groups[s] > GRP_MAX_PER_STRUCT)
+            return ctx_fail(c, "n_groups[%d] = %d is outside 0 .. %d", s, n_groups[s], GRP_MAX_PER_STRUCT);
+        meta[s] = offsets[s];
+        meta[(size_t)n_structs + 1 + s] = G64;
+        G64 += n_groups[s];
+    }
+    meta[n_structs] = offsets[n_structs];
+    meta[2 * (size_t)n_structs + 1] = G64;
+    if (G64 + n_structs > (int64_t)1 << 30) return ctx_fail(c, "too many groups (max 2^30 structures and groups per call)");
+    const int G = (int)G64;
+
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    if (ensure(c, c->g_meta, meta.size() * sizeof(int64_t)) || ensure(c, c->g_key, 4 * (size_t)n) ||
+        ensure(c, c->g_count, 4 * ((size_t)G + 2)))
+        return -1;
+    GrpArgs ga;
+    memset(&ga, 0, sizeof ga);
+    ga.xyz = d_xyz; ga.radii = d_radii; ga.group = d_group;
+    ga.offsets = (const int64_t *)c->g_meta.p; ga.gbase = ga.offsets + n_structs + 1;
+    ga.n_structs = n_structs; ga.n_atoms = n; ga.n_groups = G;
+    ga.key = (int *)c->g_key.p; ga.count = (int *)c->g_count.p;
+
+    /* 1. count and validate; the counts and the two status words back (stream sync 1 of 2 beyond run_batch's) */
+    HIP_TRY(c, hipMemcpyAsync(c->g_meta.p, meta.data(), meta.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(c->g_count.p, 0, 4 * ((size_t)G + 2), st));
+    HIP_TRY(c, kl_grp_count(ga, st));
+    std::vector<int> cnt((size_t)G + 2);
+    HIP_TRY(c, hipMemcpyAsync(cnt.data(), c->g_count.p, 4 * ((size_t)G + 2), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (cnt[G]) {
+        const int64_t i = (int64_t)cnt[(size_t)G + 1] - 1;
+        int32_t g = 0;
+        HIP_TRY(c, hipMemcpy(&g, d_group + i, sizeof g, hipMemcpyDeviceToHost));
+        int s = 0;
+        while (s + 1 < n_structs && offsets[s + 1] <= i) ++s;
+        return ctx_fail(c, "atom %lld (structure %d) has group id %d: ids are -1 .. n_groups[s] - 1 = %d", (long long)i, s, g,
+                        n_groups[s] - 1);
+    }
+
+    /* the combined batch: the complex structures, then every group as a structure */
+    std::vector<int64_t> comb((size_t)n_structs + G + 1);
+    std::vector<int> cursor((size_t)G + 1);
+    for (int s = 0; s <= n_structs; ++s) comb[s] = offsets[s];
+    int64_t pos = n;
+    for (int k = 0; k < G; ++k) {
+        cursor[k] = (int)pos;
+        pos += cnt[k];
+        comb[(size_t)n_structs + 1 + k] = pos;
+    }
+    const int64_t n_iso = pos - n;
+    if (pos > (int64_t)1 << 30) return ctx_fail(c, "batch and groups too large (max 2^30 atoms per call together)");
+    const size_t N = (size_t)pos, NS = (size_t)n_structs + G;
+    if (ensure(c, c->g_cursor, 4 * ((size_t)G + 1)) || ensure(c, c->g_xyz, 24 * N) || ensure(c, c->g_radii, 8 * N) ||
+        ensure(c, c->g_src, 4 * ((size_t)n_iso + 1)) || ensure(c, c->g_sasa, 8 * N) || ensure(c, c->g_gath, 8 * N) ||
+        ensure(c, c->g_tot, 8 * NS) || ensure(c, c->g_tot2, 8 * NS))
+        return -1;
+    ga.cursor = (int *)c->g_cursor.p; ga.cxyz = (double *)c->g_xyz.p; ga.cradii = (double *)c->g_radii.p;
+    ga.src = (int *)c->g_src.p; ga.n_iso = (int)n_iso;
+
+    /* 2. the stable cut */
+    HIP_TRY(c, hipMemcpyAsync(c->g_xyz.p, d_xyz, 24 * (size_t)n, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->g_radii.p, d_radii, 8 * (size_t)n, hipMemcpyDeviceToDevice, st));
+    if (G > 0) {
+        HIP_TRY(c, hipMemcpyAsync(c->g_cursor.p, cursor.data(), 4 * (size_t)G, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, kl_grp_rank(ga, st));
+    }
+
+    /* 3. one batch over the complex and its groups */
+    std::vector<double> tp;
+    if (alg == 1) {
+        tp.resize(3 * (size_t)resolution);
+        freesasa_gpu_test_points(resolution, tp.data());
+    }
+    if (run_batch(c, alg == 0, (const double *)c->g_xyz.p, (const double *)c->g_radii.p, comb.data(), (int)NS, probe, resolution,
+                  alg == 1 ? tp.data() : nullptr, (double *)c->g_sasa.p, nullptr, (double *)c->g_tot.p))
+        return -1;
+
+    /* 4. finish: areas to the caller, each group's complex area reduced like its isolated total (the chunk tables of
+          the combined batch, which run_batch left on the device) */
+    ga.csasa = (const double *)c->g_sasa.p; ga.ctot = (const double *)c->g_tot.p; ga.ctot2 = (const double *)c->g_tot2.p;
+    ga.cgath = (double *)c->g_gath.p; ga.sasa = d_sasa; ga.iso = d_iso; ga.totals = d_totals; ga.gtot = d_group_totals;
+    HIP_TRY(c, kl_grp_finish(ga, st));
+    if (G > 0 && d_group_totals) {
+        PipeArgs pa;
+        memset(&pa, 0, sizeof pa);
+        pa.n_structs = (int)NS; pa.n_atoms = (int)N; pa.offsets = (const int64_t *)c->offsets.p;
+        pa.n_chunks = c->n_chunks; pa.chunk_struct = (const int *)c->chunk_struct.p; pa.chunk_begin = (const int64_t *)c->chunk_begin.p;
+        pa.chunk_len = (const int *)c->chunk_len.p; pa.struct_chunk0 = (const int *)c->struct_chunk0.p;
+        HIP_TRY(c, kl_totals(pa, c->n_chunks, (int)NS, (const double *)c->g_gath.p, (double *)c->bpart.p, (double *)c->g_tot2.p, st));
+    }
+    if (d_totals || (G > 0 && d_group_totals)) HIP_TRY(c, kl_grp_totals(ga, st));
+    HIP_TRY(c, hipStreamSynchronize(st)); /* (stream sync 2 of 2 beyond run_batch's: the call is synchronous) */
+    return 0;
+}
+
+extern "C" int freesasa_gpu_groups_dev(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii,
+                                       const int64_t *offsets, int n_structs, const int32_t *d_group, const int32_t *n_groups,
+                                       double probe_radius, int resolution, double *d_sasa, double *d_iso, double *d_totals,
+                                       double *d_group_totals)
+{
+    if (!c) return -1;
+    if (freesasa_gpu_wait(c)) return -1; /* (batches submitted asynchronously come first) */
+    return guarded_ctx(c, [&]() -> int {
+        const int rc = groups_impl(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe_radius, resolution,
+                                   d_sasa, d_iso, d_totals, d_group_totals);
+        if (rc) (void)hipStreamSynchronize(c->stream);
+        return rc;
+    });
+}
+
+extern "C" int freesasa_gpu_calc_groups(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
+                                        const int32_t *group, const int32_t *n_groups, int alg, double probe_radius,
+                                        int resolution, double *sasa_out, double *iso_out, double *totals_out,
+                                        double *group_totals_out, int device, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (!xyz || !radii || !offsets || !group || !n_groups || !sasa_out || !iso_out) return set_err(err_out, err_len, "null argument");
+    if (n_structs <= 0 || offsets[n_structs] <= 0) return set_err(err_out, err_len, "empty batch");
+    if (freesasa_gpu_device_count() <= 0)
+        return set_err(err_out, err_len, "no HIP device available: libfreesasa_amd has no CPU path");
+    return guarded(err_out, err_len, [&]() -> int {
+    PoolLease lease(device);
+    freesasa_gpu_ctx *c = lease.c;
+    if (!c) return set_err(err_out, err_len, "could not create a GPU context");
+    int ret = -1;
+    do {
+        const size_t n = (size_t)offsets[n_structs];
+        int64_t G = 0; /* (bad counts are refused by freesasa_gpu_groups_dev, with its message: staged for none here) */
+        for (int s = 0; s < n_structs; ++s) G += n_groups[s] > 0 && n_groups[s] <= GRP_MAX_PER_STRUCT ? n_groups[s] : 0;
+        if (hipSetDevice(c->device) != hipSuccess) { ctx_fail(c, "hipSetDevice failed"); break; }
+        if (ensure(c, c->h_xyz, 24 * n) || ensure(c, c->h_radii, 8 * n) || ensure(c, c->h_group, 4 * n) ||
+            ensure(c, c->h_sasa, 8 * n) || ensure(c, c->h_iso, 8 * n) || ensure(c, c->h_totals, 8 * (size_t)n_structs) ||
+            ensure(c, c->h_gtot, 24 * (size_t)G + 8))
+            break;
+        if (hipMemcpyAsync(c->h_xyz.p, xyz, 24 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            hipMemcpyAsync(c->h_radii.p, radii, 8 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            hipMemcpyAsync(c->h_group.p, group, 4 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+            ctx_fail(c, "host-to-device copy failed");
+            break;
+        }
+        if (freesasa_gpu_groups_dev(c, alg, (const double *)c->h_xyz.p, (const double *)c->h_radii.p, offsets, n_structs,
+                                    (const int32_t *)c->h_group.p, n_groups, probe_radius, resolution, (double *)c->h_sasa.p,
+                                    (double *)c->h_iso.p, totals_out ? (double *)c->h_totals.p : nullptr,
+                                    group_totals_out ? (double *)c->h_gtot.p : nullptr))
+            break;
+        if (hipMemcpyAsync(sasa_out, c->h_sasa.p, 8 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipMemcpyAsync(iso_out, c->h_iso.p, 8 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            (totals_out && hipMemcpyAsync(totals_out, c->h_totals.p, 8 * (size_t)n_structs, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+            (group_totals_out && G > 0 &&
+             hipMemcpyAsync(group_totals_out, c->h_gtot.p, 24 * (size_t)G, hipMemcpyDeviceToHost, c->stream) != hipSuccess)) {
+            ctx_fail(c, "device-to-host copy failed");
+            break;
+        }
+        if (hipStreamSynchronize(c->stream) != hipSuccess) { ctx_fail(c, "stream synchronize failed"); break; }
+        ret = 0;
+    } while (0);
+    if (ret) {
+        (void)hipStreamSynchronize(c->stream);
+        set_err(err_out, err_len, c->err[0] ? c->err : "GPU batch failed");
+    }
+    return ret;
+    });
+}

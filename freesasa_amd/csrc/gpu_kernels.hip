@@ -783,6 +783,46 @@ hipError_t kl_narrow_f64(const double *d_in, float *d_out, long long n, hipStrea
     return hipGetLastError();
 }
 
+/* chain groups (group_kernels.h, gpu_groups.hip): count and validate, stable cut into the combined batch, finish */
+__global__ __launch_bounds__(GRP_B) void k_grp_count(GrpArgs a)
+{
+    grp_count_atom(a, blockIdx.x * GRP_B + threadIdx.x, threadIdx.x & 63);
+}
+__global__ __launch_bounds__(64) void k_grp_rank(GrpArgs a)
+{
+    grp_rank_struct(a, blockIdx.x, threadIdx.x);
+}
+__global__ __launch_bounds__(GRP_B) void k_grp_finish(GrpArgs a)
+{
+    grp_finish_atom(a, (int64_t)blockIdx.x * GRP_B + threadIdx.x);
+}
+__global__ __launch_bounds__(GRP_B) void k_grp_totals(GrpArgs a)
+{
+    grp_totals_item(a, blockIdx.x * GRP_B + threadIdx.x);
+}
+hipError_t kl_grp_count(const GrpArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_grp_count, dim3((unsigned)((a.n_atoms + GRP_B - 1) / GRP_B)), dim3(GRP_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_grp_rank(const GrpArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_grp_rank, dim3((unsigned)a.n_structs), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_grp_finish(const GrpArgs &a, hipStream_t st)
+{
+    const int64_t t = (int64_t)a.n_atoms + a.n_iso;
+    hipLaunchKernelGGL(k_grp_finish, dim3((unsigned)((t + GRP_B - 1) / GRP_B)), dim3(GRP_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_grp_totals(const GrpArgs &a, hipStream_t st)
+{
+    const int m = a.n_groups > a.n_structs ? a.n_groups : a.n_structs;
+    hipLaunchKernelGGL(k_grp_totals, dim3((unsigned)((m + GRP_B - 1) / GRP_B)), dim3(GRP_B), 0, st, a);
+    return hipGetLastError();
+}
+
 void kl_dump_phase_clocks(void)
 {
 #ifdef SASA_PHASE_TIMING

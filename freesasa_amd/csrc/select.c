@@ -390,3 +390,152 @@ int freesasa_ingest_select(const freesasa_ingest_batch *b, int structure, const 
     snprintf(name_out, FREESASA_INGEST_MAX_SELECTION_NAME + 1, "%.50s", name);
     return c.warn ? FREESASA_INGEST_SELECT_WARN : (int)c.n;
 }
+
+/* ------------------------------------------------------------------ chain groups (include/freesasa_ingest.h) */
+
+#define CG_MAX_LABELS 4096
+typedef struct { char label[4]; int group; } cg_label_t;
+
+static int cg_fail(char *err, int err_len, const char *msg)
+{
+    if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", msg);
+    return -1;
+}
+
+/* The tokens of the reference's split() (src/main.cc:380-386: std::sregex_token_iterator with -1): text between the
+ * separators, an empty one between two adjacent separators or before a leading one, none after a trailing one. */
+static int cg_next_token(const char *s, size_t len, size_t *pos, char sep, size_t *b, size_t *e)
+{
+    if (*pos >= len) return 0;
+    *b = *pos;
+    size_t k = *pos;
+    while (k < len && s[k] != sep) ++k;
+    *e = k;
+    *pos = k < len ? k + 1 : k;
+    return 1;
+}
+
+/* spec -> labels with their group; returns the number of groups or -1 (err set) */
+static int cg_parse(const char *spec, int is_long, cg_label_t *lab, int *n_lab, char *err, int err_len)
+{
+    const size_t len = strlen(spec);
+    if (!is_long) /* ref: src/main.cc:396-408 */
+        for (size_t i = 0; i < len; ++i) {
+            const char a = spec[i];
+            if (a != '+' && !(a >= 'a' && a <= 'z') && !(a >= 'A' && a <= 'Z') && !(a >= '0' && a <= '9')) {
+                char msg[160];
+                snprintf(msg, sizeof msg, "character '%c' not valid chain ID in chain groups, valid characters are [A-z0-9] and '+' as separator", a);
+                return cg_fail(err, err_len, msg);
+            }
+        }
+    int n_groups = 0;
+    *n_lab = 0;
+    size_t pos = 0, gb, ge;
+    while (cg_next_token(spec, len, &pos, '+', &gb, &ge)) {
+        int in_group = 0;
+        if (!is_long) { /* one character per chain (ref: src/main.cc:411-420) */
+            for (size_t i = gb; i < ge; ++i) {
+                if (*n_lab >= CG_MAX_LABELS) return cg_fail(err, err_len, "too many chain labels");
+                memset(lab[*n_lab].label, 0, 4);
+                lab[*n_lab].label[0] = spec[i];
+                lab[(*n_lab)++].group = n_groups;
+                ++in_group;
+            }
+        } else { /* labels of at most 3 characters between '/' (ref: src/main.cc:427-443) */
+            size_t p2 = gb, lb, le;
+            while (cg_next_token(spec, ge, &p2, '/', &lb, &le)) {
+                if (le - lb > 3) return cg_fail(err, err_len, "Chain labels can not have more than 3 characters");
+                /* an empty label names no chain of any structure: the reference refuses every structure */
+                if (le == lb) return cg_fail(err, err_len, "empty chain label");
+                if (*n_lab >= CG_MAX_LABELS) return cg_fail(err, err_len, "too many chain labels");
+                memset(lab[*n_lab].label, 0, 4);
+                memcpy(lab[*n_lab].label, spec + lb, le - lb);
+                lab[(*n_lab)++].group = n_groups;
+                ++in_group;
+            }
+        }
+        /* (an empty group - "A++B", "+A" - is refused for every structure by the reference, src/structure.c:1038) */
+        if (in_group == 0) return cg_fail(err, err_len, "empty chain group");
+        ++n_groups;
+        if (n_groups > 65535) return cg_fail(err, err_len, "too many chain groups");
+    }
+    for (int i = 0; i < *n_lab; ++i)
+        for (int j = 0; j < i; ++j)
+            if (memcmp(lab[i].label, lab[j].label, 4) == 0)
+                /* (within one group the reference refuses every structure, src/structure.c:1070: the group can never
+                   hold as many distinct chains as it names) */
+                return cg_fail(err, err_len, lab[i].group == lab[j].group ? "a chain is named twice in one group"
+                                                                          : "overlapping groups are not supported");
+    return n_groups;
+}
+
+int freesasa_ingest_chain_groups(const freesasa_ingest_batch *b, const char *spec, int flags, int32_t *group_out,
+                                 int32_t *n_groups_out, int32_t *status_out, char *err, int err_len)
+{
+    if (err && err_len > 0) err[0] = 0;
+    if (!b || !group_out || !n_groups_out || !status_out) return cg_fail(err, err_len, "null argument");
+    if (flags & ~(FREESASA_INGEST_GROUPS_LONG | FREESASA_INGEST_SEPARATE_CHAINS)) return cg_fail(err, err_len, "unknown flags");
+    const int separate = (flags & FREESASA_INGEST_SEPARATE_CHAINS) != 0;
+    if (separate && spec) return cg_fail(err, err_len, "chain groups and separate chains can't be combined");
+    if (!separate && !spec) return cg_fail(err, err_len, "no chain groups given");
+    cg_label_t *lab = NULL;
+    int n_lab = 0, G = 0;
+    if (!separate) {
+        lab = (cg_label_t *)hf_malloc(sizeof(cg_label_t) * CG_MAX_LABELS);
+        if (!lab) return cg_fail(err, err_len, "out of memory");
+        G = cg_parse(spec, (flags & FREESASA_INGEST_GROUPS_LONG) != 0, lab, &n_lab, err, err_len);
+        if (G < 0) { free(lab); return -1; }
+    }
+    int *present = NULL;
+    if (!separate && n_lab > 0) {
+        present = (int *)hf_malloc(sizeof(int) * (size_t)n_lab);
+        if (!present) { free(lab); return cg_fail(err, err_len, "out of memory"); }
+    }
+    for (int s = 0; s < b->n_structs; ++s) {
+        const int64_t a0 = b->offsets[s], a1 = b->offsets[s + 1];
+        const int64_t r0 = b->res_offsets[s], r1 = b->res_offsets[s + 1];
+        for (int64_t i = a0; i < a1; ++i) group_out[i] = -1;
+        status_out[s] = b->status ? b->status[s] : FREESASA_INGEST_OK;
+        n_groups_out[s] = separate ? 0 : G;
+        if (status_out[s] != FREESASA_INGEST_OK) continue;
+        if (separate) {
+            /* a new structure wherever the chain label changes from one atom to the next, a recurring label included
+               (ref: freesasa_pdb_get_chains, src/pdb.c:96-140) */
+            int g = -1;
+            const char *last = NULL;
+            for (int64_t r = r0; r < r1; ++r) {
+                const char *lbl = b->res_chain + 4 * r;
+                if (b->res_first[r + 1] > b->res_first[r] && (!last || memcmp(lbl, last, 4) != 0)) { ++g; last = lbl; }
+                for (int64_t i = b->res_first[r]; i < b->res_first[r + 1]; ++i) group_out[i] = g;
+            }
+            if (g + 1 > 65535) {
+                for (int64_t i = a0; i < a1; ++i) group_out[i] = -1;
+                status_out[s] = FREESASA_INGEST_EGROUP;
+                continue;
+            }
+            n_groups_out[s] = g + 1;
+            continue;
+        }
+        for (int i = 0; i < n_lab; ++i) present[i] = 0;
+        for (int64_t r = r0; r < r1; ++r) {
+            if (b->res_first[r + 1] <= b->res_first[r]) continue;
+            const char *lbl = b->res_chain + 4 * r;
+            int hit = -1;
+            for (int i = 0; i < n_lab; ++i) /* (ref: chain_group_has_chain, strncmp over the 4 bytes of a label) */
+                if (strncmp(lab[i].label, lbl, 4) == 0) { hit = i; break; }
+            if (hit < 0) continue;
+            present[hit] = 1;
+            for (int64_t i = b->res_first[r]; i < b->res_first[r + 1]; ++i) group_out[i] = lab[hit].group;
+        }
+        /* every named chain has to be there (ref: src/structure.c:1066-1075) */
+        int ok = 1;
+        for (int i = 0; i < n_lab; ++i) ok &= present[i];
+        if (!ok) {
+            for (int64_t i = a0; i < a1; ++i) group_out[i] = -1;
+            status_out[s] = FREESASA_INGEST_EGROUP;
+        }
+    }
+    free(lab);
+    free(present);
+    return 0;
+}

@@ -15,7 +15,8 @@ from . import lib
 INCLUDE_HETATM, INCLUDE_HYDROGEN, JOIN_MODELS = 1, 1 << 2, 1 << 5     # ref: src/freesasa.h:182-191
 HALT_AT_UNKNOWN, SKIP_UNKNOWN, RADIUS_FROM_OCCUPANCY = 1 << 6, 1 << 7, 1 << 8
 PARSE_ON_DEVICE = 1 << 16       # sweep drivers only: the files' text is parsed by kernels (csrc/gpu_parse.hip)
-OK, EIO, EFORMAT, EEMPTY, EUNKNOWN, EOPTION, ENOMEM, EVERSION = range(8)
+OK, EIO, EFORMAT, EEMPTY, EUNKNOWN, EOPTION, ENOMEM, EVERSION, EGROUP = range(9)
+GROUPS_LONG, SEPARATE_CHAINS = 1, 1 << 4   # flags of freesasa_ingest_chain_groups
 APOLAR, POLAR, UNKNOWN = 0, 1, 2
 
 
@@ -107,6 +108,26 @@ class Batch:
             raise ValueError(f"cannot parse selection {command!r}")
         return name.value.decode(), mask, ret == -2
 
+    def chain_groups(self, spec=None, long=False, separate_chains=False):
+        """freesasa_ingest_chain_groups(): (group[n_atoms] int32, n_groups[n_structs], status[n_structs]) for
+        freesasa_amd.calc_groups / GpuContext.groups.  spec: the reference's --chain-groups ("AB+C"; long=True: its
+        --chain-groups-long, "A/B+C"), or separate_chains=True for one group per chain.  A structure without a
+        requested chain gets status EGROUP and ids -1.  Raises ValueError on a bad spec or overlapping groups."""
+        L = _proto()
+        group = np.empty(self.n_atoms, dtype=np.int32)
+        n_groups = np.empty(self.n_structs, dtype=np.int32)
+        status = np.empty(self.n_structs, dtype=np.int32)
+        err = C.create_string_buffer(256)
+        flags = (GROUPS_LONG if long else 0) | (SEPARATE_CHAINS if separate_chains else 0)
+        cb = self._as_c()
+        i32 = C.POINTER(C.c_int32)
+        ret = L.freesasa_ingest_chain_groups(C.byref(cb), spec.encode() if spec is not None else None, flags,
+                                             group.ctypes.data_as(i32), n_groups.ctypes.data_as(i32),
+                                             status.ctypes.data_as(i32), err, 256)
+        if ret:
+            raise ValueError(f"chain groups {spec!r}: {err.value.decode()}")
+        return group, n_groups, status
+
     def residue_sums(self, per_atom):
         """Host-side segmented sum over the residues (the device-side one is GpuContext.segment_sums)."""
         per_atom = np.asarray(per_atom, dtype=np.float64)
@@ -129,6 +150,8 @@ def _proto():
         L.freesasa_ingest_guess_radius.restype = C.c_double
         L.freesasa_ingest_residue_reference_table.argtypes = [C.POINTER(C.c_double)]
         L.freesasa_ingest_is_backbone.argtypes = [C.c_char_p]
+        L.freesasa_ingest_chain_groups.argtypes = [C.POINTER(_CBatch), C.c_char_p, C.c_int, C.POINTER(C.c_int32),
+                                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_char_p, C.c_int]
         L.freesasa_ingest_select.argtypes = [C.POINTER(_CBatch), C.c_int, C.c_char_p, C.c_char_p, C.POINTER(C.c_ubyte)]
         L.freesasa_ingest_save.argtypes = [C.POINTER(_CBatch), C.c_char_p]
         L.freesasa_ingest_load.argtypes = [C.c_char_p, C.POINTER(_CBatch)]

@@ -299,6 +299,35 @@ int freesasa_gpu_trajectory(const double *xyz_frames, const double *radii, int n
                             double *totals_out, double *sasa_out, int device,
                             char *err_out, int err_len);
 
+/* Chain groups: the area of every atom in its complex AND in its group taken on its own (the reference's
+   --chain-groups / --separate-chains: freesasa_structure_get_chains_lcl, src/structure.c:1026-1080, minus the
+   re-classification), so that iso - sasa is the area an atom buries in the complex.
+   d_group [n_atoms] (DEVICE): an int32 group id per atom, local to its structure, -1 = in no group; n_groups
+   [n_structs] (HOST): structure s has groups 0 .. n_groups[s] - 1 (0 <= n_groups[s] <= 65535).  Groups are a partition:
+   the isolated structure of group (s, g) is the atoms of s with id g, in their order, with the caller's coordinates and
+   radii.  An empty group is allowed (totals 0).  alg, probe_radius and resolution as in freesasa_gpu_calc_batch (S&R:
+   the points of freesasa_gpu_test_points(resolution)).
+   Results (device): d_sasa [n_atoms] the complex areas, bit-identical to freesasa_gpu_lr_batch_dev / _sr_batch_dev on
+   the same batch; d_iso [n_atoms] each atom's area in its isolated group, bit-identical to the engine's result for that
+   group given as a structure of its own (= d_sasa for atoms with id -1); d_totals [n_structs] (may be NULL) as there;
+   d_group_totals [3 G] (may be NULL; G = sum of n_groups, groups k in structure-major order): [3k] the isolated total,
+   bit-identical to the engine's d_totals for the isolated structure, [3k + 1] the complex area of the group's atoms,
+   summed the same way over them in order, [3k + 2] = [3k] - [3k + 1], the buried area.
+   The groups and the complex go through ONE batch (gpu_groups.hip).  Synchronous; batches in flight on the context
+   are collected first.  It makes TWO stream synchronizations more than freesasa_gpu_lr_batch_dev: one to read the
+   per-group atom counts (they size the combined batch), one at the end.  A group id < -1 or >= n_groups[s] (found on
+   the device), a bad n_groups or a NULL argument: -1 with the context's error text, the context stays usable. */
+int freesasa_gpu_groups_dev(freesasa_gpu_ctx *ctx, int alg, const double *d_xyz, const double *d_radii,
+                            const int64_t *offsets, int n_structs, const int32_t *d_group, const int32_t *n_groups,
+                            double probe_radius, int resolution,
+                            double *d_sasa, double *d_iso, double *d_totals, double *d_group_totals);
+/* The same on host arrays (group in host memory too), on a pooled per-thread context like freesasa_gpu_calc_batch.
+   totals_out, group_totals_out may be NULL.  Returns 0 / -1 with err_out. */
+int freesasa_gpu_calc_groups(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
+                             const int32_t *group, const int32_t *n_groups, int alg, double probe_radius,
+                             int resolution, double *sasa_out, double *iso_out, double *totals_out,
+                             double *group_totals_out, int device, char *err_out, int err_len);
+
 #ifdef __cplusplus
 }
 #endif

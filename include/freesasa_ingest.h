@@ -47,8 +47,9 @@ enum {
     FREESASA_INGEST_EUNKNOWN = 4, /* HALT_AT_UNKNOWN and an atom the classifier does not know */
     FREESASA_INGEST_EOPTION = 5,  /* unsupported option bits */
     FREESASA_INGEST_ENOMEM = 6,
-    FREESASA_INGEST_EVERSION = 7  /* a cache file written by an earlier format version (1: rounds 2-4): not damaged, but
+    FREESASA_INGEST_EVERSION = 7, /* a cache file written by an earlier format version (1: rounds 2-4): not damaged, but
                                      this build reads version 2 only - save the batch again (freesasa_ingest_save) */
+    FREESASA_INGEST_EGROUP = 8    /* freesasa_ingest_chain_groups: a requested chain is not in the structure */
 };
 
 /* atom classes (ref: src/freesasa.h:163-167) */
@@ -158,6 +159,27 @@ int freesasa_ingest_cache_read_atoms(const freesasa_ingest_cache *cache, int64_t
 #define FREESASA_INGEST_SELECT_WARN (-2)
 int freesasa_ingest_select(const freesasa_ingest_batch *batch, int structure, const char *command,
                            char name_out[FREESASA_INGEST_MAX_SELECTION_NAME + 1], unsigned char *mask_out);
+
+/* Chain groups of every structure of a batch, as group ids for freesasa_gpu_groups_dev (include/freesasa_gpu.h): the
+ * reference CLI's --chain-groups / --separate-chains (src/main.cc:261-312).  An atom's chain is its residue's res_chain.
+ *   spec, flags 0: the short syntax "AB+C" (ref: src/main.cc:389-424): characters [A-Za-z0-9] and '+', one character per
+ *     chain, '+' between groups ("" : no groups; a trailing '+' is dropped, as the reference's split() drops it).
+ *   spec, FREESASA_INGEST_GROUPS_LONG: the long syntax "A/B+C" (ref: src/main.cc:427-443): labels of at most 3
+ *     characters, '/' between the chains of a group.
+ *   spec NULL, FREESASA_INGEST_SEPARATE_CHAINS: one group per chain, cut where the chain label changes from one atom to
+ *     the next (ref: freesasa_pdb_get_chains, src/pdb.c:96-140): a label that recurs after another one starts a group of
+ *     its own.  (The reference cuts on the lines of the file; lines this batch left out - hydrogens, alternate
+ *     locations - cannot start a group here.)
+ * group_out [n_atoms] receives the ids (-1: in no group), n_groups_out [n_structs] the groups of each structure (the
+ * number of groups of the spec for every structure; 0 for a failed input), status_out [n_structs] the input's status or
+ * FREESASA_INGEST_EGROUP when a chain the spec names is missing (all atoms of that structure get -1; the reference
+ * refuses such a structure, src/structure.c:1068-1075).  Groups are a partition: a chain named in two groups is a call
+ * error ("overlapping groups are not supported"), and so are a chain named twice in one group, an empty group or label
+ * (the reference refuses every structure for those) and a syntax error.  Returns 0, or -1 with the message in err. */
+#define FREESASA_INGEST_GROUPS_LONG 1
+#define FREESASA_INGEST_SEPARATE_CHAINS (1 << 4) /* (the reference's FREESASA_SEPARATE_CHAINS; the loaders refuse it) */
+int freesasa_ingest_chain_groups(const freesasa_ingest_batch *b, const char *spec, int flags, int32_t *group_out,
+                                 int32_t *n_groups_out, int32_t *status_out, char *err, int err_len);
 
 /* The classifier on its own (ref: freesasa_classifier_radius / _class with the ProtOr classifier,
  * src/classifier.c:781-813): radius in A or -1.0 if unknown; *cls (may be NULL) receives the class. */
