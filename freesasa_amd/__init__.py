@@ -151,6 +151,9 @@ def lib():
                                                    C.POINTER(C.c_longlong), C.c_char_p, C.c_int]
         L.freesasa_gpu_sweep_files_devices.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                                        C.c_longlong, _dp, _dp, _lp, _ip, C.c_char_p, C.c_longlong, _ip, C.c_int, C.c_char_p, C.c_int]
+        L.freesasa_gpu_sweep_files_classified.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                                          C.c_longlong, _dp, _dp, _lp, _ip, C.c_char_p, C.c_longlong, _ip, C.c_int,
+                                                          C.c_void_p, C.c_char_p, C.c_int]
         L.freesasa_gpu_sweep_cache_devices.argtypes = [C.c_char_p, C.c_int, C.c_double, C.c_int, C.c_longlong, _dp, _dp, _lp, _ip, C.c_int,
                                                        _ip, C.c_int, C.c_int, C.c_char_p, C.c_int]
         L.freesasa_gpu_trajectory_devices.argtypes = [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
@@ -284,16 +287,24 @@ def shard_cuts(offsets, n_parts):
 
 
 def sweep_files(paths, alg=LEE_RICHARDS, probe=1.4, resolution=20, ingest_options=0, n_threads=0, batch_atoms=0,
-                class_sums=True, device=-1, devices=None):
+                class_sums=True, device=-1, devices=None, classifier=None):
     """freesasa_gpu_sweep_files[_devices](): PDB / mmCIF files -> (totals[n], class_sums[n,3] or None, n_atoms[n],
     status[n]); loading of the next batch overlaps the GPU work on the current one.  devices: a list of devices
-    (entries may repeat) that share the batches, largest first."""
+    (entries may repeat) that share the batches, largest first.  classifier: an ingest.Classifier in place of ProtOr
+    (freesasa_gpu_sweep_files_classified), for the host and the device parser alike."""
     n = len(paths)
     arr = (C.c_char_p * n)(*[str(p).encode() for p in paths])
     totals, atoms, status = np.zeros(n), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
     cls = np.zeros((n, 3)) if class_sums else None
     err = C.create_string_buffer(512)
-    if devices is None:
+    if classifier is not None:
+        from . import ingest
+        keep, dp_, nd = _devs(devices, device)
+        ret = lib().freesasa_gpu_sweep_files_classified(arr, n, ingest_options, n_threads, alg, probe, resolution, batch_atoms,
+                                                        totals.ctypes.data_as(_dp), cls.ctypes.data_as(_dp) if cls is not None else None,
+                                                        atoms.ctypes.data_as(_lp), status.ctypes.data_as(_ip), None, 0, dp_, nd,
+                                                        ingest._handle(classifier), err, 512)
+    elif devices is None:
         ret = lib().freesasa_gpu_sweep_files(arr, n, ingest_options, n_threads, alg, probe, resolution, batch_atoms,
                                              totals.ctypes.data_as(_dp), cls.ctypes.data_as(_dp) if cls is not None else None,
                                              atoms.ctypes.data_as(_lp), status.ctypes.data_as(_ip), device, err, 512)
@@ -308,15 +319,23 @@ def sweep_files(paths, alg=LEE_RICHARDS, probe=1.4, resolution=20, ingest_option
 
 
 def sweep_files_resumable(paths, done_path, alg=LEE_RICHARDS, probe=1.4, resolution=20, ingest_options=0, n_threads=0,
-                          batch_atoms=0, max_new_batches=0, device=-1, devices=None):
+                          batch_atoms=0, max_new_batches=0, device=-1, devices=None, classifier=None):
     """freesasa_gpu_sweep_files_resumable(): like sweep_files with a done-list at done_path (+ done_path.bin):
-    returns (complete, totals, class_sums, n_atoms, status); batches listed there are not computed again."""
+    returns (complete, totals, class_sums, n_atoms, status); batches listed there are not computed again.  A done-list
+    written under one classifier (or none) is refused by a call with another."""
     n = len(paths)
     arr = (C.c_char_p * n)(*[str(p).encode() for p in paths])
     totals, atoms, status = np.zeros(n), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
     cls = np.zeros((n, 3))
     err = C.create_string_buffer(512)
-    if devices is None:
+    if classifier is not None:
+        from . import ingest
+        keep, dp_, nd = _devs(devices, device)
+        ret = lib().freesasa_gpu_sweep_files_classified(arr, n, ingest_options, n_threads, alg, probe, resolution, batch_atoms,
+                                                        totals.ctypes.data_as(_dp), cls.ctypes.data_as(_dp), atoms.ctypes.data_as(_lp),
+                                                        status.ctypes.data_as(_ip), str(done_path).encode(), max_new_batches, dp_, nd,
+                                                        ingest._handle(classifier), err, 512)
+    elif devices is None:
         ret = lib().freesasa_gpu_sweep_files_resumable(arr, n, ingest_options, n_threads, alg, probe, resolution, batch_atoms,
                                                        totals.ctypes.data_as(_dp), cls.ctypes.data_as(_dp), atoms.ctypes.data_as(_lp),
                                                        status.ctypes.data_as(_ip), str(done_path).encode(), max_new_batches, device, err, 512)
@@ -403,13 +422,19 @@ def trajectory_file(frames_path, radii, totals_path, sasa_path=None, done_path=N
     return ret == 0, int(total.value)
 
 
-def parse_files_dev(paths, ingest_options=0, n_threads=0, device=0):
+def parse_files_dev(paths, ingest_options=0, n_threads=0, device=0, classifier=None):
     """freesasa_gpu_parse_files(): the device-side PDB / mmCIF parser on its own -> (xyz [atoms, 3], radii, classes,
-    offsets [n + 1], status [n], refused [n]); a refused file (the sweep hands it to the host parser) contributes no atoms."""
+    offsets [n + 1], status [n], refused [n]); a refused file (the sweep hands it to the host parser) contributes no atoms.
+    classifier: an ingest.Classifier in place of ProtOr (freesasa_gpu_parse_files_classified)."""
     L = lib()
     L.freesasa_gpu_parse_files.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(C.c_ubyte),
                                            C.c_longlong, _lp, _ip, _ip, C.c_char_p, C.c_int]
     L.freesasa_gpu_parse_files.restype = C.c_longlong
+    L.freesasa_gpu_parse_files_classified.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp,
+                                                      C.POINTER(C.c_ubyte), C.c_longlong, _lp, _ip, _ip, C.c_void_p, C.c_char_p, C.c_int]
+    L.freesasa_gpu_parse_files_classified.restype = C.c_longlong
+    from . import ingest
+    handle = ingest._handle(classifier)
     n = len(paths)
     arr = (C.c_char_p * n)(*[str(p).encode() for p in paths])
     offs, status, host = np.zeros(n + 1, dtype=np.int64), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
@@ -417,9 +442,12 @@ def parse_files_dev(paths, ingest_options=0, n_threads=0, device=0):
     cap = 1 << 16
     while True:
         xyz, r, cls = np.empty(3 * cap), np.empty(cap), np.empty(cap, dtype=np.uint8)
-        got = L.freesasa_gpu_parse_files(arr, n, ingest_options, n_threads, device, xyz.ctypes.data_as(_dp), r.ctypes.data_as(_dp),
-                                         cls.ctypes.data_as(C.POINTER(C.c_ubyte)), cap, offs.ctypes.data_as(_lp), status.ctypes.data_as(_ip),
-                                         host.ctypes.data_as(_ip), err, 512)
+        args = (arr, n, ingest_options, n_threads, device, xyz.ctypes.data_as(_dp), r.ctypes.data_as(_dp),
+                cls.ctypes.data_as(C.POINTER(C.c_ubyte)), cap, offs.ctypes.data_as(_lp), status.ctypes.data_as(_ip), host.ctypes.data_as(_ip))
+        if classifier is None:
+            got = L.freesasa_gpu_parse_files(*args, err, 512)
+        else:
+            got = L.freesasa_gpu_parse_files_classified(*args, handle, err, 512)
         if got == -2:
             cap = int(offs[-1]) + 16
             continue

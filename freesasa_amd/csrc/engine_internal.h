@@ -132,8 +132,9 @@ struct freesasa_gpu_ctx {
     bool hint_far = false;    /* ... a quarter or more of its tiles had an atom beyond LR2_WALK_Z: the next batch gets the walking build of the main launch */
     int hint_pool2 = 0, hint_ta2 = 0, hint_mw2 = 0; /* ... and the pool the last batch's demand histogram asks for, for tiles of that shape */
     /* the device-side parser's workspace and what its two phases hand each other (gpu_parse.hip) */
-    DevBuf parse[11];
+    DevBuf parse[12]; /* gpu_parse.hip: [0..10] text, files, lines; [11] a user classifier's table */
     std::vector<long long> parse_off;
+    std::vector<unsigned char> parse_table; /* host copy of a user classifier's table being uploaded (gpu_parse.hip) */
     long long parse_atoms = 0;
     int parse_lines = 0, parse_files = 0, parse_options = 0;
     unsigned parse_T = 0;

@@ -233,7 +233,8 @@ static_assert(sizeof(SweepRec) == 48, "result record");
 int sweep_impl(const char *const *paths, int n_paths, int ingest_options, int n_threads,
                int alg, double probe, int resolution, long long batch_atoms,
                double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out,
-               const char *done_path, long long max_new_batches, const int *devices, int n_devices, char *err_out, int err_len)
+               const char *done_path, long long max_new_batches, const int *devices, int n_devices,
+               const freesasa_ingest_classifier *classifier, char *err_out, int err_len)
 {
     if (err_out && err_len > 0) err_out[0] = 0;
     if (!paths || n_paths < 0 || !totals_out || !status_out) return set_err(err_out, err_len, "null argument");
@@ -280,6 +281,10 @@ int sweep_impl(const char *const *paths, int n_paths, int ingest_options, int n_
         char head[256];
         snprintf(head, sizeof head, "freesasa_amd sweep done-list v2 n_files=%d batches=%d files=%016llx options=%d alg=%d resolution=%d probe=%.17g\n",
                  n_paths, n_batches, h, ingest_options & ~FREESASA_INGEST_PARSE_ON_DEVICE, alg, resolution, probe); /* (who parses does not change a result: not part of the run's name) */
+        if (classifier) { /* (without one the line is what it always was: earlier done-lists resume) */
+            const size_t hl = strlen(head);
+            snprintf(head + hl - 1, sizeof head - (hl - 1), " classifier=%016llx\n", (unsigned long long)freesasa_ingest_classifier_digest(classifier));
+        }
         const std::string res_path = std::string(done_path) + ".bin";
         bool resume = false;
         if (FILE *fp = fopen(done_path, "r")) {
@@ -391,7 +396,7 @@ int sweep_impl(const char *const *paths, int n_paths, int ingest_options, int n_
                 if (hipSetDevice(c->device) != hipSuccess) { ctx_fail(c, "hipSetDevice failed"); break; }
                 long long total = 0;
                 long long tq = sprof ? now_ns() : 0;
-                if (parse_batch_dev_begin(c, cur_s.text, cur_s.T, cur_s.files.data(), ns, ingest_options, atoms.data(), status.data(), host.data(), &total)) break;
+                if (parse_batch_dev_begin(c, cur_s.text, cur_s.T, cur_s.files.data(), ns, ingest_options, classifier, atoms.data(), status.data(), host.data(), &total)) break;
                 if (sprof) { const long long t1 = now_ns(); tp_parse += t1 - tq; tq = t1; }
                 /* the files the device left to the host parser: read now, appended behind the device's atoms */
                 for (int k = 0; k < ns; ++k) if (host[(size_t)k]) fb.push_back(k);
@@ -399,7 +404,7 @@ int sweep_impl(const char *const *paths, int n_paths, int ingest_options, int n_
                 if (!fb.empty()) {
                     std::vector<const char *> fp;
                     for (int k : fb) fp.push_back(paths[first + k]);
-                    const int lrc = freesasa_ingest_pdb_files(fp.data(), (int)fp.size(), ingest_options, loader_threads, &hb.b);
+                    const int lrc = freesasa_ingest_pdb_files_ex(fp.data(), (int)fp.size(), ingest_options, loader_threads, classifier, &hb.b);
                     if (lrc) { ctx_fail(c, "loader failed with code %d", lrc); break; }
                 }
                 const long long extra = hb.b.n_atoms, n_all = total + extra;
@@ -476,7 +481,7 @@ int sweep_impl(const char *const *paths, int n_paths, int ingest_options, int n_
         freesasa_gpu_ctx *c = lease.c;
         if (!c) { fe.set("could not create a GPU context"); return; }
         auto load = [&](int b, freesasa_ingest_batch *out, int *rc) noexcept { /* (C code: nothing to catch) */
-            *rc = freesasa_ingest_pdb_files(paths + cut[b], cut[b + 1] - cut[b], ingest_options, loader_threads, out);
+            *rc = freesasa_ingest_pdb_files_ex(paths + cut[b], cut[b + 1] - cut[b], ingest_options, loader_threads, classifier, out);
         };
         size_t ti = next.fetch_add(1);
         if (ti < todo.size()) load(todo[ti], &cur, &cur_rc);
@@ -866,9 +871,10 @@ int traj_run(TrajIO &io, const double *radii, int n_atoms, long long n_frames, i
    arrays of `cap` atoms), offsets_out [n + 1], status_out [n] (the loader's codes), host_out [n] (1: the device refuses the
    file - the sweep would hand it to the host parser - and it contributes nothing here).  Returns the atoms written, -1 on
    error, -2 if cap is too small (offsets_out[n] says how many are needed). */
-extern "C" long long freesasa_gpu_parse_files(const char *const *paths, int n_paths, int ingest_options, int n_threads, int device,
-                                              double *xyz_out, double *radii_out, unsigned char *class_out, long long cap,
-                                              long long *offsets_out, int *status_out, int *host_out, char *err_out, int err_len)
+extern "C" long long freesasa_gpu_parse_files_classified(const char *const *paths, int n_paths, int ingest_options, int n_threads, int device,
+                                                         double *xyz_out, double *radii_out, unsigned char *class_out, long long cap,
+                                                         long long *offsets_out, int *status_out, int *host_out,
+                                                         const freesasa_ingest_classifier *classifier, char *err_out, int err_len)
 {
     if (err_out && err_len > 0) err_out[0] = 0;
     if (!paths || n_paths <= 0 || !offsets_out || !status_out || !host_out) return set_err(err_out, err_len, "bad argument");
@@ -884,7 +890,7 @@ extern "C" long long freesasa_gpu_parse_files(const char *const *paths, int n_pa
         if (s.rc) return set_err(err_out, err_len, "could not stage the files");
         std::vector<int> atoms((size_t)n_paths);
         long long total = 0;
-        if (parse_batch_dev_begin(c, s.text, s.T, s.files.data(), n_paths, ingest_options & ~FREESASA_INGEST_PARSE_ON_DEVICE, atoms.data(), status_out, host_out, &total) ||
+        if (parse_batch_dev_begin(c, s.text, s.T, s.files.data(), n_paths, ingest_options & ~FREESASA_INGEST_PARSE_ON_DEVICE, classifier, atoms.data(), status_out, host_out, &total) ||
             parse_batch_dev_finish(c, 0))
             return set_err(err_out, err_len, c->err);
         offsets_out[0] = 0;
@@ -902,6 +908,14 @@ extern "C" long long freesasa_gpu_parse_files(const char *const *paths, int n_pa
     return rc ? -1 : written;
 }
 
+extern "C" long long freesasa_gpu_parse_files(const char *const *paths, int n_paths, int ingest_options, int n_threads, int device,
+                                              double *xyz_out, double *radii_out, unsigned char *class_out, long long cap,
+                                              long long *offsets_out, int *status_out, int *host_out, char *err_out, int err_len)
+{
+    return freesasa_gpu_parse_files_classified(paths, n_paths, ingest_options, n_threads, device, xyz_out, radii_out, class_out, cap,
+                                               offsets_out, status_out, host_out, nullptr, err_out, err_len);
+}
+
 /* files the sweeps of this process parsed on the device / left to the host parser since the last call (FREESASA_INGEST_PARSE_ON_DEVICE) */
 extern "C" void freesasa_gpu_sweep_parse_stats(long long *device_files, long long *host_files)
 {
@@ -915,7 +929,7 @@ extern "C" int freesasa_gpu_sweep_files(const char *const *paths, int n_paths, i
                                         int device, char *err_out, int err_len)
 {
     return sweep_impl(paths, n_paths, ingest_options, n_threads, alg, probe, resolution, batch_atoms, totals_out, class_sums_out,
-                      atoms_out, status_out, nullptr, 0, &device, 1, err_out, err_len);
+                      atoms_out, status_out, nullptr, 0, &device, 1, nullptr, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_sweep_files_resumable(const char *const *paths, int n_paths, int ingest_options, int n_threads,
@@ -924,7 +938,7 @@ extern "C" int freesasa_gpu_sweep_files_resumable(const char *const *paths, int 
                                                   const char *done_path, long long max_new_batches, int device, char *err_out, int err_len)
 {
     return sweep_impl(paths, n_paths, ingest_options, n_threads, alg, probe, resolution, batch_atoms, totals_out, class_sums_out,
-                      atoms_out, status_out, done_path, max_new_batches, &device, 1, err_out, err_len);
+                      atoms_out, status_out, done_path, max_new_batches, &device, 1, nullptr, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_sweep_files_devices(const char *const *paths, int n_paths, int ingest_options, int n_threads,
@@ -934,7 +948,17 @@ extern "C" int freesasa_gpu_sweep_files_devices(const char *const *paths, int n_
                                                 char *err_out, int err_len)
 {
     return sweep_impl(paths, n_paths, ingest_options, n_threads, alg, probe, resolution, batch_atoms, totals_out, class_sums_out,
-                      atoms_out, status_out, done_path, max_new_batches, devices, n_devices, err_out, err_len);
+                      atoms_out, status_out, done_path, max_new_batches, devices, n_devices, nullptr, err_out, err_len);
+}
+
+extern "C" int freesasa_gpu_sweep_files_classified(const char *const *paths, int n_paths, int ingest_options, int n_threads,
+                                                   int alg, double probe, int resolution, long long batch_atoms,
+                                                   double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out,
+                                                   const char *done_path, long long max_new_batches, const int *devices, int n_devices,
+                                                   const freesasa_ingest_classifier *classifier, char *err_out, int err_len)
+{
+    return sweep_impl(paths, n_paths, ingest_options, n_threads, alg, probe, resolution, batch_atoms, totals_out, class_sums_out,
+                      atoms_out, status_out, done_path, max_new_batches, devices, n_devices, classifier, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_sweep_cache_devices(const char *cache_path, int alg, double probe, int resolution, long long batch_atoms,

@@ -5,6 +5,10 @@
 #include <stddef.h>
 
 struct freesasa_gpu_ctx;
+struct freesasa_ingest_classifier;
+
+/* rows of a user classifier the device parser takes (a larger table: the batch's files go to the host parser) */
+#define PARSE_MAX_CLASSIFIER_ROWS 16384
 
 enum { PARSE_PDB = 0, PARSE_CIF = 1, PARSE_HOST = 2 };
 
@@ -20,11 +24,12 @@ struct ParseFile {
     unsigned char pad[3];
 };
 
-/* Phase 1: text -> per-file atoms / status / refused (host arrays [F]) and the total of kept atoms.  Phase 2: the kept atoms
+/* Phase 1: text -> per-file atoms / status / refused (host arrays [F]) and the total of kept atoms; cls: a user classifier
+ * (NULL: ProtOr), its table uploaded with the batch.  Phase 2: the kept atoms
  * into c->h_xyz / c->h_radii / c->h_counts (classes), which are sized for total + extra_atoms first (the caller appends what
  * the host parser read of the refused files behind them).  0 / -1 (message in the context). */
 int parse_batch_dev_begin(freesasa_gpu_ctx *c, unsigned char *h_text, size_t T, const ParseFile *files, int F, int options,
-                          int *atoms_out, int *status_out, int *host_out, long long *total_atoms_out);
+                          const struct freesasa_ingest_classifier *cls, int *atoms_out, int *status_out, int *host_out, long long *total_atoms_out);
 int parse_batch_dev_finish(freesasa_gpu_ctx *c, long long extra_atoms);
 
 #endif

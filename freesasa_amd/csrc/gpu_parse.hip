@@ -10,7 +10,8 @@
  *
  *   kp_count_nl / kp_scan_blocks / kp_line_starts   where the lines are (a line = up to a '\n'; every file ends with one)
  *   kp_parse_lines   one thread per line: record type, hydrogen test, alt-loc label, coordinates, ProtOr radius and
- *                    class (binary search in the table of protor_table.h), element fallback; mmCIF: the row's tokens
+ *                    class (binary search in the table of protor_table.h) - or, kp_parse_lines<true>, a user classifier's
+ *                    (its table uploaded with the batch; (ANY, atom) on a miss) -, element fallback; mmCIF: the row's tokens
  *   kp_resolve       one wave per file, its lines in order: first ENDMDL / lowest model, the alt-loc rule (a scan: wave
  *                    ballots), the first error, which atoms are kept and where they land
  *   kp_scatter       kept atoms to the batch arrays the tile kernels read
@@ -32,6 +33,7 @@
 #include <vector>
 
 #include "engine_internal.h"
+#include "classifier.h"
 #include "gpu_parse.h"
 #include "protor_table.h"
 
@@ -73,6 +75,9 @@ struct ParseArgs {
     const unsigned short *esym; const double *erad;                                /* [ELEMENT_N] */
     /* output */
     double *xyz, *radii; unsigned char *cls;
+    /* a user classifier (kp_parse_lines<true>; classifier.h): its rows sorted by key, whether one is an ANY row */
+    const unsigned long long *ckey; const double *crad; const unsigned char *ccls;
+    int cn, cany;
 };
 
 #define PB 256
@@ -159,6 +164,43 @@ __device__ double protor_radius(const ParseArgs &a, const unsigned char *rt, int
     }
     return -1.0;
 }
+/* A user classifier (ingest.c's lookup through ingest_classifier_lookup__): the exact (residue, atom) key, then - only if
+   the table has ANY rows - (ANY, atom).  A residue token of more than 3 characters cannot be a listed residue: straight to ANY. */
+__device__ int classifier_find(const ParseArgs &a, unsigned long long k)
+{
+    int lo = 0, hi = a.cn - 1;
+    while (lo <= hi) {
+        const int mid = (lo + hi) >> 1;
+        const unsigned long long v = a.ckey[mid];
+        if (v == k) return mid;
+        if (v < k) lo = mid + 1; else hi = mid - 1;
+    }
+    return -1;
+}
+__device__ double classifier_radius(const ParseArgs &a, const unsigned char *rt, int rl, const unsigned char *at, int al, int *cls)
+{
+    *cls = 2; /* FREESASA_INGEST_UNKNOWN */
+    if (al < 1 || al > 4) return -1.0;
+    unsigned long long ka = 0;
+    for (int i = 0; i < 4; ++i) ka = (ka << 8) | (i < al ? at[i] : (unsigned char)' ');
+    int i = -1;
+    if (rl >= 1 && rl <= 3) {
+        unsigned long long kr = 0;
+        for (int q = 0; q < 3; ++q) kr = (kr << 8) | (q < rl ? rt[q] : (unsigned char)' ');
+        i = classifier_find(a, (kr << 32) | ka);
+    }
+    if (i < 0 && a.cany) i = classifier_find(a, (((unsigned long long)'A' << 48) | ((unsigned long long)'N' << 40) | ((unsigned long long)'Y' << 32)) | ka);
+    if (i < 0) return -1.0;
+    *cls = a.ccls[i];
+    return a.crad[i];
+}
+/* the ProtOr build (CUSTOM = false) is the parser as it was before user classifiers: the same code, the same registers */
+template <bool CUSTOM>
+__device__ __forceinline__ double atom_radius(const ParseArgs &a, const unsigned char *rt, int rl, const unsigned char *at, int al, int *cls)
+{
+    if (CUSTOM) return classifier_radius(a, rt, rl, at, al, cls);
+    return protor_radius(a, rt, rl, at, al, cls);
+}
 /* sym: the symbol's characters (n of them, at most 2 are looked at): right-justified to two, compared as they are */
 __device__ double element_radius(const ParseArgs &a, const unsigned char *sym, int n)
 {
@@ -233,6 +275,7 @@ __device__ bool ieq(const unsigned char *p, const char *kw, int n)
     return true;
 }
 
+template <bool CUSTOM>
 __device__ void parse_pdb_line(const ParseArgs &a, const unsigned char *line, int n, unsigned &flag, double v[3], double &r, int &cls)
 {
     /* ingest.c parse_pdb, the body of its line loop; n counts the newline like the reference's fgets buffer */
@@ -274,7 +317,7 @@ __device__ void parse_pdb_line(const ParseArgs &a, const unsigned char *line, in
         }
         int as_, rs_;
         const int al = field_token(line + 12, has_name ? 4 : 0, &as_), rl = field_token(line + 17, n >= 20 ? 3 : 0, &rs_);
-        const double rc = protor_radius(a, line + 17 + rs_, rl, line + 12 + as_, al, &cls);
+        const double rc = atom_radius<CUSTOM>(a, line + 17 + rs_, rl, line + 12 + as_, al, &cls);
         if (rc >= 0) {
             r = rc;
         } else {
@@ -287,6 +330,7 @@ __device__ void parse_pdb_line(const ParseArgs &a, const unsigned char *line, in
     if (n >= 6 && line[0] == 'E' && line[1] == 'N' && line[2] == 'D' && line[3] == 'M' && line[4] == 'D' && line[5] == 'L') flag = PL_ENDMDL;
 }
 
+template <bool CUSTOM>
 __device__ void parse_cif_line(const ParseArgs &a, const ParseFile &pf, const unsigned char *line, int n, unsigned &flag, int &model,
                                double v[3], double &r, int &cls)
 {
@@ -347,7 +391,7 @@ __device__ void parse_cif_line(const ParseArgs &a, const ParseFile &pf, const un
     for (int k = 0; k < sl; ++k) if (is_sp(sy[k]) || sy[k] == 0) { flag |= PL_HOST; return; }
     for (int k = 0; k < 3; ++k)
         if (!plain_double(line + tp[8 + k], tn[8 + k], &v[k])) { flag |= PL_HOST; return; } /* (the host's strtod path) */
-    const double rc = protor_radius(a, rn, rl, an, al, &cls);
+    const double rc = atom_radius<CUSTOM>(a, rn, rl, an, al, &cls);
     if (rc >= 0) {
         r = rc;
     } else {
@@ -357,6 +401,7 @@ __device__ void parse_cif_line(const ParseArgs &a, const ParseFile &pf, const un
     }
 }
 
+template <bool CUSTOM>
 __global__ __launch_bounds__(PB) void kp_parse_lines(ParseArgs a)
 {
     const int l = blockIdx.x * PB + threadIdx.x;
@@ -373,9 +418,9 @@ __global__ __launch_bounds__(PB) void kp_parse_lines(ParseArgs a)
     if (pf.kind == PARSE_PDB) {
         /* (n counts the newline, as the reference's buffer does - except behind a last line that had none) */
         const bool last = a.lstart[l + 1] == a.files[lo + 1].beg;
-        parse_pdb_line(a, line, len + ((last && pf.no_final_nl) ? 0 : 1), flag, v, r, cls);
+        parse_pdb_line<CUSTOM>(a, line, len + ((last && pf.no_final_nl) ? 0 : 1), flag, v, r, cls);
     } else if (pf.kind == PARSE_CIF) {
-        if (s >= pf.row0) parse_cif_line(a, pf, line, len, flag, model, v, r, cls);
+        if (s >= pf.row0) parse_cif_line<CUSTOM>(a, pf, line, len, flag, model, v, r, cls);
     }
     a.lflag[l] = flag;
     a.lmodel[l] = model;
@@ -536,9 +581,30 @@ static int tables_for(freesasa_gpu_ctx *c, ParseArgs &pa)
     return 0;
 }
 
+/* A user classifier's table into the context's buffer next to the files' (c->parse[11]), on the stream, with every batch: a
+   few KB against the batch's text, and no classifier's lifetime is tied to device-global state.  (The host copy lives in the
+   context too: the upload may run after this returns.)  1: the table is larger than PARSE_MAX_CLASSIFIER_ROWS. */
+static int classifier_for(freesasa_gpu_ctx *c, const freesasa_ingest_classifier *cls, ParseArgs &pa)
+{
+    const uint64_t *k; const double *r; const uint8_t *cl;
+    int any = 0;
+    const int n = ingest_classifier_table__(cls, &k, &r, &cl, &any);
+    if (n > PARSE_MAX_CLASSIFIER_ROWS) return 1;
+    const size_t b_key = 8 * (size_t)n, b_rad = 8 * (size_t)n, bytes = b_key + b_rad + (size_t)n + 8;
+    c->parse_table.resize(bytes);
+    unsigned char *h = c->parse_table.data();
+    if (n) { memcpy(h, k, b_key); memcpy(h + b_key, r, b_rad); memcpy(h + b_key + b_rad, cl, (size_t)n); }
+    if (ensure(c, c->parse[11], bytes)) return -1;
+    HIP_TRY(c, hipMemcpyAsync(c->parse[11].p, h, bytes, hipMemcpyHostToDevice, c->stream));
+    char *p = (char *)c->parse[11].p;
+    pa.ckey = (const unsigned long long *)p; pa.crad = (const double *)(p + b_key); pa.ccls = (const unsigned char *)(p + b_key + b_rad);
+    pa.cn = n; pa.cany = any;
+    return 0;
+}
+
 /* (gpu_parse.h) */
 int parse_batch_dev_begin(freesasa_gpu_ctx *c, unsigned char *h_text, size_t T, const ParseFile *files, int F, int options,
-                          int *atoms_out, int *status_out, int *host_out, long long *total_atoms_out)
+                          const freesasa_ingest_classifier *cls, int *atoms_out, int *status_out, int *host_out, long long *total_atoms_out)
 {
     if (T >= (1ULL << 31)) return ctx_fail(c, "batch text too large for the device parser");
     hipStream_t st = c->stream;
@@ -546,6 +612,17 @@ int parse_batch_dev_begin(freesasa_gpu_ctx *c, unsigned char *h_text, size_t T, 
     memset(&a, 0, sizeof a);
     c->parse_lines = 0; c->parse_atoms = 0;
     if (tables_for(c, a)) return -1;
+    if (cls) {
+        const int rc = classifier_for(c, cls, a);
+        if (rc < 0) return -1;
+        if (rc > 0) { /* a table beyond the limit: every file of the batch to the host parser */
+            for (int f = 0; f < F; ++f) { atoms_out[f] = 0; status_out[f] = 0; host_out[f] = 1; }
+            *total_atoms_out = 0;
+            c->parse_off.assign((size_t)F + 1, 0);
+            c->parse_files = F; c->parse_options = options; c->parse_T = (unsigned)T;
+            return 0;
+        }
+    }
     const size_t Tp = (T + 15) & ~(size_t)15;
     for (size_t k = T; k < Tp; ++k) h_text[k] = ' ';
     a.T = (unsigned)T; a.F = F; a.options = options;
@@ -577,7 +654,8 @@ int parse_batch_dev_begin(freesasa_gpu_ctx *c, unsigned char *h_text, size_t T, 
     a.lx = (double *)B[9].p; a.ly = a.lx + L; a.lz = a.ly + L; a.lr = a.lz + L; a.lcls = (unsigned char *)B[10].p;
     const int lblocks = (int)((L + PB - 1) / PB);
     hipLaunchKernelGGL(kp_line_starts, dim3(a.n_blocks), dim3(PB), 0, st, a);
-    hipLaunchKernelGGL(kp_parse_lines, dim3(lblocks), dim3(PB), 0, st, a);
+    if (cls) hipLaunchKernelGGL(kp_parse_lines<true>, dim3(lblocks), dim3(PB), 0, st, a);
+    else hipLaunchKernelGGL(kp_parse_lines<false>, dim3(lblocks), dim3(PB), 0, st, a);
     hipLaunchKernelGGL(kp_resolve, dim3(F), dim3(64), 0, st, a);
     HIP_TRY(c, hipGetLastError());
     /* atoms / status / refused per file -> host */

@@ -27,6 +27,7 @@
 #include <unistd.h>
 
 #include "protor_table.h"
+#include "classifier.h"
 #include "hostfault.h"
 
 #define CHUNK 119 /* fgets(line, PDB_MAX_LINE_STRL = 120) */
@@ -354,7 +355,7 @@ static inline int coords_8_3(const char *sec, double v[3])
  * the reference's strlen on its fgets buffer, by a memchr), its name fields are trimmed once and serve the radius
  * lookup, the backbone test and the stored names alike, and no character test is a library call - 157 -> ~95 ns per
  * atom on 1a0q, one thread. */
-static void parse_pdb(const char *text, size_t len, int options, parsed *p)
+static void parse_pdb(const char *text, size_t len, int options, const freesasa_ingest_classifier *classifier, parsed *p)
 {
     p->n = p->n0; p->nres = p->nres0; p->status = 0;
     if ((options & FREESASA_INGEST_SKIP_UNKNOWN) && (options & FREESASA_INGEST_HALT_AT_UNKNOWN))
@@ -423,7 +424,7 @@ static void parse_pdb(const char *text, size_t len, int options, parsed *p)
             const int al = field_token(aname, has_name ? 4 : 0, &at), rl = field_token(rname, n >= 20 ? 3 : 0, &rt);
             double r;
             int cls;
-            const double rc = protor_lookup(rt, rl, at, al, &cls);
+            const double rc = classifier ? ingest_classifier_lookup__(classifier, rt, rl, at, al, &cls) : protor_lookup(rt, rl, at, al, &cls);
             if (options & FREESASA_INGEST_RADIUS_FROM_OCCUPANCY) {
                 r = 1;
             } else if (rc >= 0) {
@@ -453,7 +454,7 @@ static void parse_pdb(const char *text, size_t len, int options, parsed *p)
             if (p->n == p->n0 || memcmp(rnumber, prev_number, 6) != 0 || chain != prev_chain) {
                 if (grow_res(p)) { p->status = FREESASA_INGEST_ENOMEM; return; }
                 p->res_first[p->nres] = p->n - p->n0;
-                p->res_ref[p->nres] = (int16_t)residue_ref_index(rname);
+                p->res_ref[p->nres] = classifier ? (int16_t)-1 : (int16_t)residue_ref_index(rname); /* (a config file has no reference areas) */
                 memset(p->res_name + 4 * p->nres, 0, 4);
                 memcpy(p->res_name + 4 * p->nres, rname, 3);
                 memcpy(p->res_number + 6 * p->nres, rnumber, 6);
@@ -906,6 +907,7 @@ static int tok_plain_double(const cif_tok *t, double *out)
 typedef struct {
     parsed *p;
     int options;
+    const freesasa_ingest_classifier *classifier; /* NULL: ProtOr */
     int have_model, model, min_model; /* model being read (the first one met) and the lowest seen */
     char prev_alt;
     char prev_number[6], prev_chain[4];
@@ -958,7 +960,10 @@ static int cif_visit_atom(const cif_tok *row, void *ctx)
     plain = plain && (size_t)al == (row[5].n >= 2 && row[5].p[0] == '"' ? (row[5].n - 2 < 4 ? row[5].n - 2 : 4) : (row[5].n < 4 ? row[5].n : 4)) &&
             (size_t)rl == (row[4].n < 3 ? row[4].n : 3) && (size_t)sl == (row[7].n < 2 ? row[7].n : 2);
     int cls;
-    double r = plain ? protor_lookup(rname, rl, aname, al, &cls) : freesasa_ingest_protor_radius(rname, aname, &cls);
+    double r;
+    if (c->classifier) r = plain ? ingest_classifier_lookup__(c->classifier, rname, rl, aname, al, &cls)
+                                 : freesasa_ingest_classifier_radius(c->classifier, rname, aname, &cls);
+    else r = plain ? protor_lookup(rname, rl, aname, al, &cls) : freesasa_ingest_protor_radius(rname, aname, &cls);
     if (r < 0) {
         if (c->options & (FREESASA_INGEST_HALT_AT_UNKNOWN | FREESASA_INGEST_SKIP_UNKNOWN)) return 0;
         r = freesasa_ingest_guess_radius(symbol);
@@ -972,7 +977,7 @@ static int cif_visit_atom(const cif_tok *row, void *ctx)
     if (p->n == p->n0 || memcmp(znum, c->prev_number, 6) != 0 || memcmp(zchain, c->prev_chain, 4) != 0) {
         if (grow_res(p)) { p->status = FREESASA_INGEST_ENOMEM; return -1; }
         p->res_first[p->nres] = p->n - p->n0;
-        p->res_ref[p->nres] = (int16_t)residue_ref_index(rname);
+        p->res_ref[p->nres] = c->classifier ? (int16_t)-1 : (int16_t)residue_ref_index(rname);
         char zname[4] = {0};
         for (int i = 0; i < 3 && rname[i]; ++i) zname[i] = rname[i];
         memcpy(p->res_name + 4 * p->nres, zname, 4);
@@ -999,7 +1004,7 @@ static int cif_visit_atom(const cif_tok *row, void *ctx)
     return 0;
 }
 
-static void parse_cif(const char *text, size_t len, int options, parsed *p)
+static void parse_cif(const char *text, size_t len, int options, const freesasa_ingest_classifier *classifier, parsed *p)
 {
     /* The reference collects the model numbers first and keeps the lowest (src/cif.cc:78-87,
        225-234).  Files list their models in ascending order, so one pass suffices: read the atoms
@@ -1009,7 +1014,7 @@ static void parse_cif(const char *text, size_t len, int options, parsed *p)
     for (int pass = 0; pass < 2; ++pass) {
         p->n = p->n0; p->nres = p->nres0; p->status = 0;
         memset(&c, 0, sizeof c);
-        c.p = p; c.options = options; c.prev_alt = '.';
+        c.p = p; c.options = options; c.classifier = classifier; c.prev_alt = '.';
         if (pass == 1) { c.have_model = 1; c.model = c.min_model = p->scratch_model; }
         cif_walk(text, len, cif_visit_atom, &c);
         if (!c.have_model || c.min_model == c.model || p->status) break;
@@ -1107,10 +1112,10 @@ int freesasa_ingest_cif_locate(const char *text, size_t len, int *ncol_out, sign
     return 2;
 }
 
-static void parse_any(const char *text, size_t len, int options, parsed *p)
+static void parse_any(const char *text, size_t len, int options, const freesasa_ingest_classifier *classifier, parsed *p)
 {
-    if (looks_like_cif(text, len)) parse_cif(text, len, options, p);
-    else parse_pdb(text, len, options, p);
+    if (looks_like_cif(text, len)) parse_cif(text, len, options, classifier, p);
+    else parse_pdb(text, len, options, classifier, p);
 }
 
 /* Whole file into a buffer that is reused from call to call.  0 on success, else the input's status
@@ -1151,6 +1156,7 @@ typedef struct {
     const char *const *texts;
     const size_t *lens;
     int n, options, n_workers;
+    const freesasa_ingest_classifier *classifier; /* NULL: ProtOr */
     slot *slots;
     parsed *arena; /* [n_workers] */
     int64_t *a_off, *r_off; /* [n + 1] output offsets of every input */
@@ -1235,11 +1241,11 @@ static void *worker(void *arg)
         if (k >= j->n) break;
         A->n0 = A->n; A->nres0 = A->nres;
         if (j->texts) {
-            parse_any(j->texts[k], j->lens[k], j->options, A);
+            parse_any(j->texts[k], j->lens[k], j->options, j->classifier, A);
         } else {
             size_t len = 0;
             if ((A->status = read_file(j->paths[k], &text, &cap, &len)) != 0) { /* (EIO or ENOMEM) */ }
-            else parse_any(text, len, j->options, A);
+            else parse_any(text, len, j->options, j->classifier, A);
         }
         slot *s = &j->slots[k];
         s->worker = w;
@@ -1494,5 +1500,25 @@ int freesasa_ingest_pdb_texts(const char *const *texts, const size_t *lens, int 
     job j;
     memset(&j, 0, sizeof j);
     j.texts = texts; j.lens = lens; j.n = n_texts; j.options = options;
+    return run(&j, n_threads, out);
+}
+
+int freesasa_ingest_pdb_files_ex(const char *const *paths, int n_paths, int options, int n_threads,
+                                 const freesasa_ingest_classifier *classifier, freesasa_ingest_batch *out)
+{
+    if (!out) return FREESASA_INGEST_EOPTION;
+    job j;
+    memset(&j, 0, sizeof j);
+    j.paths = paths; j.n = n_paths; j.options = options; j.classifier = classifier;
+    return run(&j, n_threads, out);
+}
+
+int freesasa_ingest_pdb_texts_ex(const char *const *texts, const size_t *lens, int n_texts, int options, int n_threads,
+                                 const freesasa_ingest_classifier *classifier, freesasa_ingest_batch *out)
+{
+    if (!out) return FREESASA_INGEST_EOPTION;
+    job j;
+    memset(&j, 0, sizeof j);
+    j.texts = texts; j.lens = lens; j.n = n_texts; j.options = options; j.classifier = classifier;
     return run(&j, n_threads, out);
 }

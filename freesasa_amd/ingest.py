@@ -166,6 +166,21 @@ def _proto():
         L.freesasa_ingest_cache_offsets.argtypes = [C.c_void_p]; L.freesasa_ingest_cache_offsets.restype = C.POINTER(C.c_int64)
         L.freesasa_ingest_cache_status.argtypes = [C.c_void_p]; L.freesasa_ingest_cache_status.restype = C.POINTER(C.c_int32)
         L.freesasa_ingest_cache_read_atoms.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_ubyte)]
+        L.freesasa_ingest_pdb_files_ex.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(_CBatch)]
+        L.freesasa_ingest_pdb_texts_ex.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_int,
+                                                   C.c_void_p, C.POINTER(_CBatch)]
+        L.freesasa_ingest_classifier_from_file.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
+        L.freesasa_ingest_classifier_from_file.restype = C.c_void_p
+        L.freesasa_ingest_classifier_from_text.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_int]
+        L.freesasa_ingest_classifier_from_text.restype = C.c_void_p
+        L.freesasa_ingest_classifier_free.argtypes = [C.c_void_p]
+        L.freesasa_ingest_classifier_free.restype = None
+        L.freesasa_ingest_classifier_name.argtypes = [C.c_void_p]
+        L.freesasa_ingest_classifier_name.restype = C.c_char_p
+        L.freesasa_ingest_classifier_radius.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_int)]
+        L.freesasa_ingest_classifier_radius.restype = C.c_double
+        L.freesasa_ingest_classifier_digest.argtypes = [C.c_void_p]
+        L.freesasa_ingest_classifier_digest.restype = C.c_uint64
         L._ingest_ready = True
     return L
 
@@ -179,12 +194,70 @@ def _finish(L, rc, cb):
         L.freesasa_ingest_free(C.byref(cb))
 
 
-def load_pdb_files(paths, options=0, n_threads=0):
-    """Read PDB files into one Batch; per-file failures are in batch.status (empty structures)."""
+class Classifier:
+    """A user classifier (freesasa_ingest_classifier_*): radii and classes from a configuration file in the reference's
+    format (its -c option), given as a path or as text.  Raises ValueError with the reason for a file the reference would
+    reject.  .name ("no-name-given" without a name: entry), .digest (of the resolved table), .radius(res, atom) ->
+    (radius, class), radius -1.0 and class UNKNOWN for an atom it does not know.  Batches loaded with one have
+    res_ref = -1 throughout: a configuration file carries no reference areas."""
+
+    def __init__(self, path=None, text=None):
+        if (path is None) == (text is None):
+            raise ValueError("Classifier takes exactly one of path= and text=")
+        L = _proto()
+        err = C.create_string_buffer(512)
+        if path is not None:
+            h = L.freesasa_ingest_classifier_from_file(str(path).encode(), err, len(err))
+        else:
+            raw = text.encode() if isinstance(text, str) else bytes(text)
+            h = L.freesasa_ingest_classifier_from_text(raw, len(raw), err, len(err))
+        if not h:
+            raise ValueError(err.value.decode(errors="replace") or "classifier rejected")
+        self._h = C.c_void_p(h)
+        self.name = L.freesasa_ingest_classifier_name(self._h).decode(errors="replace")
+        self.digest = int(L.freesasa_ingest_classifier_digest(self._h))
+
+    def radius(self, res_name, atom_name):
+        cls = C.c_int()
+        r = _proto().freesasa_ingest_classifier_radius(self._h, _b(res_name), _b(atom_name), C.byref(cls))
+        return r, cls.value
+
+    @property
+    def handle(self):
+        """the freesasa_ingest_classifier * (valid while this object lives)"""
+        return self._h
+
+    def __del__(self):
+        try:
+            if self._h:
+                _proto().freesasa_ingest_classifier_free(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+def _b(s):
+    return s.encode() if isinstance(s, str) else bytes(s)
+
+
+def _handle(classifier):
+    """None -> NULL; a Classifier -> its handle"""
+    if classifier is None:
+        return None
+    if not isinstance(classifier, Classifier):
+        raise TypeError("classifier= takes an ingest.Classifier")
+    return classifier.handle
+
+
+def load_pdb_files(paths, options=0, n_threads=0, classifier=None):
+    """Read PDB files into one Batch; per-file failures are in batch.status (empty structures).  classifier: an
+    ingest.Classifier in place of ProtOr (res_ref is then -1 throughout)."""
     L = _proto()
     arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
     cb = _CBatch()
-    return _finish(L, L.freesasa_ingest_pdb_files(arr, len(paths), options, n_threads, C.byref(cb)), cb)
+    if classifier is None:
+        return _finish(L, L.freesasa_ingest_pdb_files(arr, len(paths), options, n_threads, C.byref(cb)), cb)
+    return _finish(L, L.freesasa_ingest_pdb_files_ex(arr, len(paths), options, n_threads, _handle(classifier), C.byref(cb)), cb)
 
 
 def load_cache(path, n_threads=0):
@@ -244,14 +317,16 @@ class Cache:
             pass
 
 
-def load_pdb_texts(texts, options=0, n_threads=0):
+def load_pdb_texts(texts, options=0, n_threads=0, classifier=None):
     """Same for PDB texts in memory (bytes or str)."""
     L = _proto()
     raw = [t.encode() if isinstance(t, str) else bytes(t) for t in texts]
     arr = (C.c_char_p * len(raw))(*raw)
     lens = (C.c_size_t * len(raw))(*[len(t) for t in raw])
     cb = _CBatch()
-    return _finish(L, L.freesasa_ingest_pdb_texts(arr, lens, len(raw), options, n_threads, C.byref(cb)), cb)
+    if classifier is None:
+        return _finish(L, L.freesasa_ingest_pdb_texts(arr, lens, len(raw), options, n_threads, C.byref(cb)), cb)
+    return _finish(L, L.freesasa_ingest_pdb_texts_ex(arr, lens, len(raw), options, n_threads, _handle(classifier), C.byref(cb)), cb)
 
 
 def residue_reference_table():

@@ -32,6 +32,7 @@ extern "C" {
 #endif
 
 typedef struct freesasa_gpu_ctx freesasa_gpu_ctx;
+struct freesasa_ingest_classifier; /* include/freesasa_ingest.h */
 
 /* Per-call statistics of the last batch run on a context. */
 typedef struct freesasa_gpu_stats {
@@ -252,6 +253,24 @@ int freesasa_gpu_sweep_files_devices(const char *const *paths, int n_paths, int 
                                      double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out,
                                      const char *done_path, long long max_new_batches, const int *devices, int n_devices,
                                      char *err, int err_len);
+/* The file sweep and the device-side parser with a user classifier (include/freesasa_ingest.h,
+   freesasa_ingest_classifier_from_file: the reference's -c configuration files) in place of ProtOr: the arguments of
+   freesasa_gpu_sweep_files_devices / freesasa_gpu_parse_files and the classifier; classifier NULL: exactly those entries.
+   The host parser (the loader threads, and the files the device refuses) and the device parser (its table uploaded with
+   every batch into the context's own buffer; a table of more than 16384 rows is not taken: the batch's files then go to
+   the host parser and count as such in freesasa_gpu_sweep_parse_stats) both classify with it.  Radii and classes - and
+   so totals and class sums - are those of the reference under that classifier; the done-list's first line names it
+   (" classifier=<digest>", freesasa_ingest_classifier_digest): a done-list written under another classifier, or under
+   none, belongs to other parameters and is refused, and one written without a classifier keeps its old first line. */
+int freesasa_gpu_sweep_files_classified(const char *const *paths, int n_paths, int ingest_options, int n_threads,
+                                        int alg, double probe_radius, int resolution, long long batch_atoms,
+                                        double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out,
+                                        const char *done_path, long long max_new_batches, const int *devices, int n_devices,
+                                        const struct freesasa_ingest_classifier *classifier, char *err, int err_len);
+long long freesasa_gpu_parse_files_classified(const char *const *paths, int n_paths, int ingest_options, int n_threads, int device,
+                                              double *xyz_out, double *radii_out, unsigned char *class_out, long long cap,
+                                              long long *offsets_out, int *status_out, int *host_out,
+                                              const struct freesasa_ingest_classifier *classifier, char *err, int err_len);
 int freesasa_gpu_sweep_cache_devices(const char *cache_path, int alg, double probe_radius, int resolution, long long batch_atoms,
                                      double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out, int n_out,
                                      const int *devices, int n_devices, int lanes_per_device, char *err, int err_len);

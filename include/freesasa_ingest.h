@@ -73,7 +73,8 @@ typedef struct freesasa_ingest_batch {
     int64_t *res_first;   /* [n_residues + 1] batch-wide atom index of each residue's first atom */
     int64_t *res_offsets; /* [n_structs + 1] */
     int16_t *res_ref;     /* [n_residues] row of the reference-area table for relative SASA, -1: the classifier
-                             does not know the residue (ref: src/classifier.c:853-861) */
+                             does not know the residue (ref: src/classifier.c:853-861); -1 throughout for a batch
+                             loaded with a user classifier (freesasa_ingest_pdb_files_ex): no relative SASA there */
     char *res_name;       /* [4 * n_residues] residue names, NUL padded ("ALA\0") */
     char *res_number;     /* [6 * n_residues] residue number incl. insertion code (" 123A\0") */
     char *res_chain;      /* [4 * n_residues] chain label, NUL padded (one character from PDB files, up to
@@ -107,6 +108,36 @@ int freesasa_ingest_pdb_files(const char *const *paths, int n_paths, int options
 /* Same for PDB / mmCIF texts already in memory (texts[k] has lens[k] bytes, no terminator needed). */
 int freesasa_ingest_pdb_texts(const char *const *texts, const size_t *lens, int n_texts, int options,
                               int n_threads, freesasa_ingest_batch *out);
+
+/* User classifiers: radii and polar / apolar classes from a configuration file in the reference's format (its -c option;
+ * ref: freesasa_classifier_from_file, src/classifier.c:703-850; the reference ships NACCESS, OONS and DSSP files as
+ * share/<name>.config).  What a file means follows the reference's reader, its rejections included (classifier.c names them).
+ * _from_file / _from_text return NULL, with the reason in err, for a file that cannot be read or that the reference would
+ * reject.  The object is immutable: the loader threads and the sweeps' workers share it.
+ *   _name: the file's name: entry, "no-name-given" without one.
+ *   _radius: radius of (res_name, atom_name), both trimmed to their first token - the (residue, atom) row, else the
+ *     (ANY, atom) row (a residue the file lists without that atom, or does not list at all) - or -1.0; *cls (may be NULL)
+ *     receives the row's class, FREESASA_INGEST_UNKNOWN for an unknown atom.
+ *   _digest: a digest of the resolved table (its rows, radii and classes; not of the text): the sweeps' done-lists name
+ *     the classifier by it. */
+typedef struct freesasa_ingest_classifier freesasa_ingest_classifier;
+freesasa_ingest_classifier *freesasa_ingest_classifier_from_file(const char *path, char *err, int err_len);
+freesasa_ingest_classifier *freesasa_ingest_classifier_from_text(const char *text, size_t len, char *err, int err_len);
+void freesasa_ingest_classifier_free(freesasa_ingest_classifier *classifier);
+const char *freesasa_ingest_classifier_name(const freesasa_ingest_classifier *classifier);
+double freesasa_ingest_classifier_radius(const freesasa_ingest_classifier *classifier, const char *res_name, const char *atom_name,
+                                         int *cls);
+uint64_t freesasa_ingest_classifier_digest(const freesasa_ingest_classifier *classifier);
+
+/* freesasa_ingest_pdb_files / _pdb_texts with a user classifier in place of ProtOr (classifier NULL: exactly those
+ * entries).  Radii and classes come from the classifier, an atom it does not know is treated as the reference treats it
+ * under the options (element radius, HALT_AT_UNKNOWN, SKIP_UNKNOWN), and res_ref is -1 for every residue: a
+ * configuration file carries no reference areas, so relative SASA is not available for such a batch (the reference's
+ * CLI drops its REL columns under -c as well, src/main.cc:729-730). */
+int freesasa_ingest_pdb_files_ex(const char *const *paths, int n_paths, int options, int n_threads,
+                                 const freesasa_ingest_classifier *classifier, freesasa_ingest_batch *out);
+int freesasa_ingest_pdb_texts_ex(const char *const *texts, const size_t *lens, int n_texts, int options, int n_threads,
+                                 const freesasa_ingest_classifier *classifier, freesasa_ingest_batch *out);
 
 /* Releases a batch THIS LIBRARY built (freesasa_ingest_pdb_files / _pdb_texts / _load / _load_mt) and zeroes the
  * struct.  The arrays of such a batch lie in one block whose header sits 16 bytes before `xyz`; a struct filled in by
