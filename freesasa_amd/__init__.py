@@ -318,6 +318,89 @@ def sweep_files(paths, alg=LEE_RICHARDS, probe=1.4, resolution=20, ingest_option
     return totals, cls, atoms, status
 
 
+class ResidueTableC(C.Structure):
+    """freesasa_gpu_residue_table (include/freesasa_gpu.h)."""
+    _fields_ = [("n_files", C.c_int32), ("n_residues", C.c_int64), ("res_offsets", _lp), ("res_atoms", C.POINTER(C.c_int32)),
+                ("res_ref", C.POINTER(C.c_int16)), ("abs", _dp), ("rel", _dp), ("res_name", C.POINTER(C.c_char)),
+                ("res_number", C.POINTER(C.c_char)), ("res_chain", C.POINTER(C.c_char))]
+
+
+class ResidueTable:
+    """numpy copy of a freesasa_gpu_residue_table: file k owns residues [res_offsets[k], res_offsets[k + 1]); abs columns are
+    total, main chain, side chain, polar, apolar, unknown, rel columns the first five over the reference areas (NaN: none);
+    the labels are decoded like ingest.Batch decodes them."""
+
+    def __init__(self, ct):
+        n, nr = int(ct.n_files), int(ct.n_residues)
+
+        def arr(ptr, count, dtype):
+            if count == 0:
+                return np.zeros(0, dtype=dtype)
+            nbytes = count * np.dtype(dtype).itemsize    # (one copy: a view of the C block, copied before the block is freed)
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_ubyte)), (nbytes,)).view(dtype).copy()
+        self.n_files, self.n_residues = n, nr
+        self.res_offsets = arr(ct.res_offsets, n + 1, np.int64)
+        self.res_atoms = arr(ct.res_atoms, nr, np.int32)
+        self.res_ref = arr(ct.res_ref, nr, np.int16)
+        self.abs = arr(ct.abs, 6 * nr, np.float64).reshape(nr, 6)
+        self.rel = arr(ct.rel, 5 * nr, np.float64).reshape(nr, 5)
+        self.res_name_raw = arr(ct.res_name, nr, "S4")
+        self.res_number_raw = arr(ct.res_number, nr, "S6")
+        self.res_chain_raw = arr(ct.res_chain, nr, "S4")
+
+    @property
+    def res_name(self):
+        return [v.decode() for v in self.res_name_raw.tolist()]
+
+    @property
+    def res_number(self):
+        return [v.decode() for v in self.res_number_raw.tolist()]
+
+    @property
+    def res_chain(self):
+        return [v.decode() for v in self.res_chain_raw.tolist()]
+
+    def file(self, k):
+        """the slice of file k's residues"""
+        return slice(int(self.res_offsets[k]), int(self.res_offsets[k + 1]))
+
+
+def _residue_proto(L):
+    L.freesasa_gpu_sweep_files_residues.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                                    C.c_longlong, _dp, _dp, _lp, _ip, _ip, C.c_int, C.c_void_p,
+                                                    C.POINTER(ResidueTableC), C.c_char_p, C.c_int]
+    L.freesasa_gpu_residue_table_free.argtypes = [C.POINTER(ResidueTableC)]
+    L.freesasa_gpu_residue_table_free.restype = None
+    return L
+
+
+def sweep_files_residues(paths, alg=LEE_RICHARDS, probe=1.4, resolution=20, ingest_options=0, n_threads=0, batch_atoms=0,
+                         device=-1, devices=None, classifier=None):
+    """freesasa_gpu_sweep_files_residues(): sweep_files plus the per-residue table of all files -> (totals[n],
+    class_sums[n,3], n_atoms[n], status[n], table: a ResidueTable).  The per-atom areas stay on the device; with
+    ingest.PARSE_ON_DEVICE the residues are built there too.  classifier: an ingest.Classifier in place of ProtOr (the
+    relative areas are then NaN throughout)."""
+    from . import ingest
+    L = _residue_proto(lib())
+    n = len(paths)
+    arr = (C.c_char_p * n)(*[str(p).encode() for p in paths])
+    totals, atoms, status = np.zeros(n), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+    cls = np.zeros((n, 3))
+    err = C.create_string_buffer(512)
+    keep, dp_, nd = _devs(devices, device)
+    ct = ResidueTableC()
+    ret = L.freesasa_gpu_sweep_files_residues(arr, n, ingest_options, n_threads, alg, probe, resolution, batch_atoms,
+                                              totals.ctypes.data_as(_dp), cls.ctypes.data_as(_dp), atoms.ctypes.data_as(_lp),
+                                              status.ctypes.data_as(_ip), dp_, nd, ingest._handle(classifier), C.byref(ct), err, 512)
+    if ret:
+        raise RuntimeError("freesasa_gpu_sweep_files_residues: " + err.value.decode())
+    try:
+        table = ResidueTable(ct)
+    finally:
+        L.freesasa_gpu_residue_table_free(C.byref(ct))
+    return totals, cls, atoms, status, table
+
+
 def sweep_files_resumable(paths, done_path, alg=LEE_RICHARDS, probe=1.4, resolution=20, ingest_options=0, n_threads=0,
                           batch_atoms=0, max_new_batches=0, device=-1, devices=None, classifier=None):
     """freesasa_gpu_sweep_files_resumable(): like sweep_files with a done-list at done_path (+ done_path.bin):

@@ -105,6 +105,8 @@ struct freesasa_gpu_ctx {
     int n_chunks = 0;
     DevBuf sq, s_idx;
     DevBuf status, ovf_tiles, ovf_tiles2, ovf_atoms, unit_pts, slab, seg;
+    DevBuf res_table;                  /* the reference areas of relative SASA, uploaded once (residue_areas_resident) */
+    std::vector<double> res_table_host;
     std::vector<int64_t> offsets_host; /* last uploaded offsets */
     std::vector<double> unit_host;     /* last uploaded S&R unit points */
     /* S&R, third arrangement (sr_caps.h): the table of cap masks of unit_host, rebuilt when the points change */
@@ -117,6 +119,8 @@ struct freesasa_gpu_ctx {
     DevBuf g_meta, g_key, g_count, g_cursor, g_xyz, g_radii, g_src, g_sasa, g_gath, g_tot, g_tot2;
     void *stage_in = nullptr, *stage_out = nullptr; /* page-locked host staging of freesasa_gpu_calc_batch_pipelined */
     size_t stage_in_cap = 0, stage_out_cap = 0;
+    void *res_stage = nullptr; /* page-locked: a batch's per-residue areas and arrays on their way to the host (gpu_drivers.hip) */
+    size_t res_stage_cap = 0;
     int *pinned = nullptr; /* page-locked host words for the small device->host readbacks: two sets of ST_WORDS + 4 */
     long long max_cells = 1LL << 30;
     long long cells_hint = 0; /* cells the last batch needed, with a margin: the table is never sized below it */
@@ -132,7 +136,7 @@ struct freesasa_gpu_ctx {
     bool hint_far = false;    /* ... a quarter or more of its tiles had an atom beyond LR2_WALK_Z: the next batch gets the walking build of the main launch */
     int hint_pool2 = 0, hint_ta2 = 0, hint_mw2 = 0; /* ... and the pool the last batch's demand histogram asks for, for tiles of that shape */
     /* the device-side parser's workspace and what its two phases hand each other (gpu_parse.hip) */
-    DevBuf parse[12]; /* gpu_parse.hip: [0..10] text, files, lines; [11] a user classifier's table */
+    DevBuf parse[20]; /* gpu_parse.hip: [0..10] text, files, lines; [11] a user classifier's table; [12..18] residues (gpu_parse.h); [19] per-residue areas (gpu_drivers.hip) */
     std::vector<long long> parse_off;
     std::vector<unsigned char> parse_table; /* host copy of a user classifier's table being uploaded (gpu_parse.hip) */
     long long parse_atoms = 0;
@@ -162,6 +166,13 @@ int ensure(freesasa_gpu_ctx *c, DevBuf &b, size_t bytes);
    (resolution = test points, unit_points on the host). */
 int run_batch(freesasa_gpu_ctx *c, bool lr, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
               double probe, int resolution, const double *unit_points, double *d_sasa, int *d_counts, double *d_totals);
+
+/* Per-residue areas (freesasa_gpu_residue_areas_dev's kernel) on arrays that are ALL on the device already - residue
+   offsets [n_res + 1], reference rows [n_res] (NULL: no relative areas wanted, d_rel ignored), backbone flags, classes -
+   enqueued on the context's stream, no synchronisation; the reference-area table goes up with the context's first call.
+   (gpu_ops.hip) */
+int residue_areas_resident(freesasa_gpu_ctx *c, const double *d_sasa, const unsigned char *d_class, const unsigned char *d_backbone,
+                           const int64_t *d_res_first, const short *d_ref_row, int n_res, double *d_abs, double *d_rel);
 
 /* ------------------------------------------------------------------ host-side helpers (gpu_hostbatch.hip) */
 

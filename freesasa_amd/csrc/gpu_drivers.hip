@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <atomic>
 #include <fcntl.h>
+#include <memory>
 #include <mutex>
 #include <stdint.h>
 #include <stdio.h>
@@ -34,6 +35,7 @@
 
 #include "engine_internal.h"
 #include "gpu_parse.h"
+#include "hostfault.h"
 
 namespace {
 
@@ -222,6 +224,31 @@ struct FirstError {
 struct SweepRec { double total, cls[3]; long long atoms; int status, pad; };
 static_assert(sizeof(SweepRec) == 48, "result record");
 
+/* The per-residue table of freesasa_gpu_sweep_files_residues.  Workers finish batches in any order and a file's place in
+   the table depends on the residues of every file before it: each batch leaves a block of its own, and the table is
+   assembled from them once all are done.  A batch's residues are in ITS order: the files the device parsed one after the
+   other, behind them those of the files the host parser read (fstart says where a file's run begins). */
+struct ResBatch {
+    int first = 0, ns = 0;                  /* files [first, first + ns) */
+    long long n_res = 0;
+    std::vector<long long> fstart, fcount;  /* [ns] */
+    std::vector<int64_t> res_first;         /* [n_res + 1] atoms, batch-wide */
+    std::vector<double> areas;              /* abs [6 n_res] | rel [5 n_res] */
+    std::vector<int16_t> ref;               /* [n_res] */
+    std::vector<char> name, number, chain;  /* [4 | 6 | 4 per residue] */
+    void size(long long R)
+    {
+        n_res = R;
+        res_first.assign((size_t)R + 1, 0); areas.resize(11 * (size_t)R); ref.resize((size_t)R);
+        name.resize(4 * (size_t)R); number.resize(6 * (size_t)R); chain.resize(4 * (size_t)R);
+    }
+};
+struct ResCollector {
+    std::mutex mu;
+    std::vector<std::unique_ptr<ResBatch>> done;
+    void add(std::unique_ptr<ResBatch> &rb) { std::lock_guard<std::mutex> lk(mu); done.push_back(std::move(rb)); }
+};
+
 /* Files -> per-structure totals.  Every worker owns a pooled context of its device and a loader: while batch k is on
  * the GPU the loader's threads (include/freesasa_ingest.h) read the batch the worker took next.  Inputs that fail to
  * load get total 0 and their loader status; the call only fails for GPU errors.
@@ -234,7 +261,7 @@ int sweep_impl(const char *const *paths, int n_paths, int ingest_options, int n_
                int alg, double probe, int resolution, long long batch_atoms,
                double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out,
                const char *done_path, long long max_new_batches, const int *devices, int n_devices,
-               const freesasa_ingest_classifier *classifier, char *err_out, int err_len)
+               const freesasa_ingest_classifier *classifier, ResCollector *rcol, char *err_out, int err_len)
 {
     if (err_out && err_len > 0) err_out[0] = 0;
     if (!paths || n_paths < 0 || !totals_out || !status_out) return set_err(err_out, err_len, "null argument");
@@ -365,6 +392,7 @@ int sweep_impl(const char *const *paths, int n_paths, int ingest_options, int n_
     auto now_ns = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (long long)ts.tv_sec * 1000000000LL + ts.tv_nsec; };
     auto worker_dev = [&](int w) noexcept {
       try {
+        std::vector<int64_t> hrf; /* residues: the host parser's res_first, shifted (declared before the context: a copy may still read it) */
         DeviceNodeScope node(devices[w]);
         PoolLease lease(devices[w]);
         freesasa_gpu_ctx *c = lease.c;
@@ -390,6 +418,8 @@ int sweep_impl(const char *const *paths, int n_paths, int ingest_options, int n_
             std::vector<double> tot, cls;
             std::vector<int> fb;  /* the files the device left to the host parser ... */
             Batch hb;             /* ... as the host read them (alive until the stream is idle: its arrays are copied from) */
+            std::unique_ptr<ResBatch> rb;
+            if (rcol) { rb.reset(new ResBatch); rb->first = first; rb->ns = ns; rb->fstart.assign((size_t)ns, 0); rb->fcount.assign((size_t)ns, 0); rb->size(0); }
             int ret = -1;
             do {
                 if (cur_s.rc) { ctx_fail(c, cur_s.rc == -1 ? "out of page-locked host memory (file staging)" : (cur_s.rc == -2 ? "a batch of files larger than 2 GB: use a smaller batch_atoms" : "out of host memory (file staging)")); break; }
@@ -410,6 +440,7 @@ int sweep_impl(const char *const *paths, int n_paths, int ingest_options, int n_
                 const long long extra = hb.b.n_atoms, n_all = total + extra;
                 if (sprof) { const long long t1 = now_ns(); tp_host += t1 - tq; tq = t1; }
                 if (parse_batch_dev_finish(c, extra)) break;
+                if (rcol && parse_batch_dev_residues_count(c, extra)) break;
                 const int nst = ns + (int)fb.size();
                 std::vector<int64_t> off((size_t)nst + 1);
                 off[0] = 0;
@@ -427,7 +458,8 @@ int sweep_impl(const char *const *paths, int n_paths, int ingest_options, int n_
                 if (extra > 0 &&
                     (hipMemcpyAsync((double *)c->h_xyz.p + 3 * total, hb.b.xyz, 24 * (size_t)extra, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
                      hipMemcpyAsync((double *)c->h_radii.p + total, hb.b.radii, 8 * (size_t)extra, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-                     hipMemcpyAsync((unsigned char *)c->h_counts.p + total, hb.b.atom_class, (size_t)extra, hipMemcpyHostToDevice, c->stream) != hipSuccess)) {
+                     hipMemcpyAsync((unsigned char *)c->h_counts.p + total, hb.b.atom_class, (size_t)extra, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+                     (rcol && hipMemcpyAsync((unsigned char *)c->parse[15].p + total, hb.b.atom_backbone, (size_t)extra, hipMemcpyHostToDevice, c->stream) != hipSuccess))) {
                     ctx_fail(c, "host-to-device copy failed");
                     break;
                 }
@@ -436,6 +468,39 @@ int sweep_impl(const char *const *paths, int n_paths, int ingest_options, int n_
                 if (run_batch(c, alg == 0, (double *)c->h_xyz.p, (double *)c->h_radii.p, off.data(), nst, probe, resolution,
                               alg == 1 ? tp.data() : nullptr, (double *)c->h_sasa.p, nullptr, d_tot))
                     break;
+                /* residues: the device's count came back under run_batch's wait; the host parser's go behind them */
+                const long long Rd = rcol ? parse_batch_dev_residues_found(c) : 0, Rh = rcol ? hb.b.n_residues : 0, R = Rd + Rh;
+                unsigned char *r_stage = nullptr;
+                if (rcol && R > 0) {
+                    if (Rd < 0 || R >= (1LL << 31)) { ctx_fail(c, "bad residue count from the device parser"); break; }
+                    if (parse_batch_dev_residues_build(c, (int)Rd, Rh, classifier != nullptr) || ensure(c, c->parse[19], 88 * (size_t)R) ||
+                        ensure_pinned(c, &c->res_stage, &c->res_stage_cap, 88 * (size_t)R + 24 * (size_t)Rd + 8 + 4 * (size_t)ns))
+                        break;
+                    if (Rh > 0) {
+                        hrf.resize((size_t)Rh + 1);
+                        for (long long j = 0; j <= Rh; ++j) hrf[(size_t)j] = total + hb.b.res_first[j];
+                        if (hipMemcpyAsync((int64_t *)c->parse[16].p + Rd, hrf.data(), 8 * ((size_t)Rh + 1), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+                            hipMemcpyAsync((int16_t *)c->parse[17].p + Rd, hb.b.res_ref, 2 * (size_t)Rh, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+                            ctx_fail(c, "host-to-device copy failed");
+                            break;
+                        }
+                    }
+                    double *d_abs = (double *)c->parse[19].p;
+                    if (residue_areas_resident(c, (double *)c->h_sasa.p, (const unsigned char *)c->h_counts.p, (const unsigned char *)c->parse[15].p,
+                                               (const int64_t *)c->parse[16].p, (const short *)c->parse[17].p, (int)R, d_abs, d_abs + 6 * R))
+                        break;
+                    /* page-locked: areas | the device's res_first, reference rows, labels, first residue per file */
+                    r_stage = (unsigned char *)c->res_stage;
+                    unsigned char *q = r_stage + 88 * (size_t)R;
+                    bool ok = hipMemcpyAsync(r_stage, d_abs, 88 * (size_t)R, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+                    if (Rd > 0)
+                        ok = ok && hipMemcpyAsync(q, c->parse[16].p, 8 * ((size_t)Rd + 1), hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+                             hipMemcpyAsync(q + 8 * ((size_t)Rd + 1), c->parse[17].p, 2 * (size_t)Rd, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+                             hipMemcpyAsync(q + 8 + 10 * (size_t)Rd, c->parse[18].p, 14 * (size_t)Rd, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+                             hipMemcpyAsync(q + 8 + 24 * (size_t)Rd, c->parse[14].p, 4 * (size_t)ns, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+                    if (!ok) { ctx_fail(c, "device-to-host copy failed"); break; }
+                    rb->size(R);
+                }
                 tot.resize((size_t)nst);
                 if (want_cls) {
                     cls.resize(3 * (size_t)nst);
@@ -451,12 +516,48 @@ int sweep_impl(const char *const *paths, int n_paths, int ingest_options, int n_
                     for (size_t j = 0; j < fb.size(); ++j) for (int q = 0; q < 3; ++q) cls[3 * (size_t)fb[j] + q] = cls[3 * ((size_t)ns + j) + q];
                     if (class_sums_out) memcpy(class_sums_out + 3 * (size_t)first, cls.data(), 8 * 3 * (size_t)ns);
                 }
+                if (r_stage) {
+                    const unsigned char *q = r_stage + 88 * (size_t)R;
+                    memcpy(rb->areas.data(), r_stage, 88 * (size_t)R);
+                    if (Rd > 0) {
+                        memcpy(rb->res_first.data(), q, 8 * ((size_t)Rd + 1));
+                        memcpy(rb->ref.data(), q + 8 * ((size_t)Rd + 1), 2 * (size_t)Rd);
+                        const unsigned char *lab = q + 8 + 10 * (size_t)Rd;
+                        memcpy(rb->name.data(), lab, 4 * (size_t)Rd);
+                        memcpy(rb->chain.data(), lab + 4 * (size_t)Rd, 4 * (size_t)Rd);
+                        memcpy(rb->number.data(), lab + 8 * (size_t)Rd, 6 * (size_t)Rd);
+                        /* a file's run ends where the next file that kept atoms begins */
+                        const int *frf = (const int *)(q + 8 + 24 * (size_t)Rd);
+                        long long end = Rd;
+                        bool sane = true;
+                        for (int k = ns - 1; k >= 0; --k) {
+                            if (host[(size_t)k] || atoms[(size_t)k] == 0) continue;
+                            if (frf[k] < 0 || frf[k] >= end) { sane = false; break; }
+                            rb->fstart[(size_t)k] = frf[k]; rb->fcount[(size_t)k] = end - frf[k];
+                            end = frf[k];
+                        }
+                        if (!sane || end != 0) { ctx_fail(c, "the device parser's residue table does not match its atoms"); ret = -1; break; }
+                    }
+                    for (long long j = 0; j < Rh; ++j) rb->res_first[(size_t)(Rd + j)] = total + hb.b.res_first[j];
+                    rb->res_first[(size_t)R] = n_all;
+                    if (Rh > 0) {
+                        memcpy(rb->ref.data() + Rd, hb.b.res_ref, 2 * (size_t)Rh);
+                        memcpy(rb->name.data() + 4 * Rd, hb.b.res_name, 4 * (size_t)Rh);
+                        memcpy(rb->number.data() + 6 * Rd, hb.b.res_number, 6 * (size_t)Rh);
+                        memcpy(rb->chain.data() + 4 * Rd, hb.b.res_chain, 4 * (size_t)Rh);
+                    }
+                    for (size_t j = 0; j < fb.size(); ++j) {
+                        rb->fstart[(size_t)fb[j]] = Rd + hb.b.res_offsets[j];
+                        rb->fcount[(size_t)fb[j]] = hb.b.res_offsets[j + 1] - hb.b.res_offsets[j];
+                    }
+                }
                 if (sprof) tp_run += now_ns() - tq;
                 ret = 0;
             } while (0);
             if (ret) (void)hipStreamSynchronize(c->stream);
             long long tr = sprof ? now_ns() : 0;
             if (!ret && fd_done >= 0 && record(c, b, first, ns, atoms64.data(), cls.empty() ? nullptr : cls.data())) ret = -1;
+            if (!ret && rcol) rcol->add(rb);
             if (ret) fe.set(c->err[0] ? c->err : "GPU sweep failed");
             if (sprof) { const long long t1 = now_ns(); tp_rec += t1 - tr; tr = t1; }
             loader.join();
@@ -491,6 +592,8 @@ int sweep_impl(const char *const *paths, int n_paths, int ingest_options, int n_
             ThreadGroup loader; /* (joined before nxt can go away, whatever happens below) */
             if (tn < todo.size() && !loader.spawn(load, todo[tn], &nxt, &nxt_rc)) { fe.set("could not start a loader thread"); break; }
             const int first = cut[b], ns = cut[b + 1] - cut[b];
+            std::unique_ptr<ResBatch> rb;
+            if (rcol) { rb.reset(new ResBatch); rb->first = first; rb->ns = ns; rb->fstart.assign((size_t)ns, 0); rb->fcount.assign((size_t)ns, 0); rb->size(0); }
             int ret = 0;
             do {
                 if (cur_rc) { ctx_fail(c, "loader failed with code %d", cur_rc); ret = -1; break; }
@@ -517,14 +620,45 @@ int sweep_impl(const char *const *paths, int n_paths, int ingest_options, int n_
                               alg == 1 ? tp.data() : nullptr, (double *)c->h_sasa.p, nullptr, d_tot))
                     break;
                 double *cls_dst = class_sums_out ? class_sums_out + 3 * (size_t)first : nullptr;
+                if (want_cls || rcol) {
+                    if (hipMemcpyAsync(c->h_counts.p, cur.atom_class, n, hipMemcpyHostToDevice, c->stream) != hipSuccess) { ctx_fail(c, "host-to-device copy failed"); break; }
+                }
+                /* residues: the loader's boundaries, reference rows and backbone flags go up, the areas come back page-locked */
+                const long long R = rcol ? cur.n_residues : 0;
+                if (R > 0) {
+                    if (R >= (1LL << 31)) { ctx_fail(c, "too many residues in one batch"); break; }
+                    if (ensure(c, c->parse[15], n) || ensure(c, c->parse[16], 8 * ((size_t)R + 1)) || ensure(c, c->parse[17], 2 * (size_t)R) ||
+                        ensure(c, c->parse[19], 88 * (size_t)R) || ensure_pinned(c, &c->res_stage, &c->res_stage_cap, 88 * (size_t)R))
+                        break;
+                    if (hipMemcpyAsync(c->parse[15].p, cur.atom_backbone, n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+                        hipMemcpyAsync(c->parse[16].p, cur.res_first, 8 * ((size_t)R + 1), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+                        hipMemcpyAsync(c->parse[17].p, cur.res_ref, 2 * (size_t)R, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+                        ctx_fail(c, "host-to-device copy failed");
+                        break;
+                    }
+                    double *d_abs = (double *)c->parse[19].p;
+                    if (residue_areas_resident(c, (double *)c->h_sasa.p, (const unsigned char *)c->h_counts.p, (const unsigned char *)c->parse[15].p,
+                                               (const int64_t *)c->parse[16].p, (const short *)c->parse[17].p, (int)R, d_abs, d_abs + 6 * R))
+                        break;
+                    if (hipMemcpyAsync(c->res_stage, d_abs, 88 * (size_t)R, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { ctx_fail(c, "device-to-host copy failed"); break; }
+                    rb->size(R);
+                }
                 if (want_cls) {
                     if (!cls_dst) { cls_tmp.resize(3 * (size_t)ns); cls_dst = cls_tmp.data(); }
-                    if (hipMemcpyAsync(c->h_counts.p, cur.atom_class, n, hipMemcpyHostToDevice, c->stream) != hipSuccess) { ctx_fail(c, "host-to-device copy failed"); break; }
                     if (freesasa_gpu_class_sums_dev(c, (double *)c->h_sasa.p, (const unsigned char *)c->h_counts.p, cur.offsets, ns, d_cls)) break;
                     if (hipMemcpyAsync(cls_dst, d_cls, 8 * 3 * (size_t)ns, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { ctx_fail(c, "device-to-host copy failed"); break; }
                 }
                 if (hipMemcpyAsync(totals_out + first, d_tot, 8 * (size_t)ns, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { ctx_fail(c, "device-to-host copy failed"); break; }
                 if (hipStreamSynchronize(c->stream) != hipSuccess) { ctx_fail(c, "stream synchronize failed"); break; }
+                if (R > 0) {
+                    memcpy(rb->areas.data(), c->res_stage, 88 * (size_t)R);
+                    memcpy(rb->res_first.data(), cur.res_first, 8 * ((size_t)R + 1));
+                    memcpy(rb->ref.data(), cur.res_ref, 2 * (size_t)R);
+                    memcpy(rb->name.data(), cur.res_name, 4 * (size_t)R);
+                    memcpy(rb->number.data(), cur.res_number, 6 * (size_t)R);
+                    memcpy(rb->chain.data(), cur.res_chain, 4 * (size_t)R);
+                    for (int k = 0; k < ns; ++k) { rb->fstart[(size_t)k] = cur.res_offsets[k]; rb->fcount[(size_t)k] = cur.res_offsets[k + 1] - cur.res_offsets[k]; }
+                }
                 ret = 0;
             } while (0);
             if (ret) (void)hipStreamSynchronize(c->stream); /* no copy may still read the batch when it is freed */
@@ -534,6 +668,7 @@ int sweep_impl(const char *const *paths, int n_paths, int ingest_options, int n_
                 const double *cls_src = class_sums_out ? class_sums_out + 3 * (size_t)first : (cur.n_atoms > 0 ? cls_tmp.data() : nullptr);
                 if (record(c, b, first, ns, at.data(), cls_src)) ret = -1;
             }
+            if (!ret && rcol) rcol->add(rb);
             if (ret) fe.set(c->err[0] ? c->err : "GPU sweep failed");
             loader.join();
             cur_b.take(nxt_b);
@@ -929,7 +1064,7 @@ extern "C" int freesasa_gpu_sweep_files(const char *const *paths, int n_paths, i
                                         int device, char *err_out, int err_len)
 {
     return sweep_impl(paths, n_paths, ingest_options, n_threads, alg, probe, resolution, batch_atoms, totals_out, class_sums_out,
-                      atoms_out, status_out, nullptr, 0, &device, 1, nullptr, err_out, err_len);
+                      atoms_out, status_out, nullptr, 0, &device, 1, nullptr, nullptr, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_sweep_files_resumable(const char *const *paths, int n_paths, int ingest_options, int n_threads,
@@ -938,7 +1073,7 @@ extern "C" int freesasa_gpu_sweep_files_resumable(const char *const *paths, int 
                                                   const char *done_path, long long max_new_batches, int device, char *err_out, int err_len)
 {
     return sweep_impl(paths, n_paths, ingest_options, n_threads, alg, probe, resolution, batch_atoms, totals_out, class_sums_out,
-                      atoms_out, status_out, done_path, max_new_batches, &device, 1, nullptr, err_out, err_len);
+                      atoms_out, status_out, done_path, max_new_batches, &device, 1, nullptr, nullptr, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_sweep_files_devices(const char *const *paths, int n_paths, int ingest_options, int n_threads,
@@ -948,7 +1083,7 @@ extern "C" int freesasa_gpu_sweep_files_devices(const char *const *paths, int n_
                                                 char *err_out, int err_len)
 {
     return sweep_impl(paths, n_paths, ingest_options, n_threads, alg, probe, resolution, batch_atoms, totals_out, class_sums_out,
-                      atoms_out, status_out, done_path, max_new_batches, devices, n_devices, nullptr, err_out, err_len);
+                      atoms_out, status_out, done_path, max_new_batches, devices, n_devices, nullptr, nullptr, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_sweep_files_classified(const char *const *paths, int n_paths, int ingest_options, int n_threads,
@@ -958,7 +1093,75 @@ extern "C" int freesasa_gpu_sweep_files_classified(const char *const *paths, int
                                                    const freesasa_ingest_classifier *classifier, char *err_out, int err_len)
 {
     return sweep_impl(paths, n_paths, ingest_options, n_threads, alg, probe, resolution, batch_atoms, totals_out, class_sums_out,
-                      atoms_out, status_out, done_path, max_new_batches, devices, n_devices, classifier, err_out, err_len);
+                      atoms_out, status_out, done_path, max_new_batches, devices, n_devices, classifier, nullptr, err_out, err_len);
+}
+
+/* The sweep with the per-residue table (include/freesasa_gpu.h): the batches' blocks (ResBatch) into ONE block behind
+   res_offsets, files in the caller's order, each file's residues in the file's order. */
+static int assemble_residue_table(int n_paths, std::vector<std::unique_ptr<ResBatch>> &done, freesasa_gpu_residue_table *t, char *err_out, int err_len)
+{
+    std::vector<long long> count((size_t)n_paths, 0);
+    std::vector<char> seen((size_t)n_paths, 0);
+    for (auto &rb : done)
+        for (int k = 0; k < rb->ns; ++k) { count[(size_t)(rb->first + k)] = rb->fcount[(size_t)k]; seen[(size_t)(rb->first + k)] = 1; }
+    long long R = 0;
+    for (int f = 0; f < n_paths; ++f) {
+        if (!seen[(size_t)f]) return set_err(err_out, err_len, "a batch of the sweep left no residue block");
+        R += count[(size_t)f];
+    }
+    const size_t n = (size_t)n_paths, r = (size_t)R;
+    const size_t o_abs = 8 * (n + 1), o_rel = o_abs + 48 * r, o_atoms = o_rel + 40 * r, o_ref = o_atoms + 4 * r, o_name = o_ref + 2 * r,
+                 o_number = o_name + 4 * r, o_chain = o_number + 6 * r, bytes = o_chain + 4 * r;
+    char *blk = (char *)hf_malloc(bytes + 8);
+    if (!blk) return set_err(err_out, err_len, "out of host memory (residue table)");
+    t->n_files = n_paths; t->n_residues = R;
+    t->res_offsets = (int64_t *)blk; t->abs = (double *)(blk + o_abs); t->rel = (double *)(blk + o_rel);
+    t->res_atoms = (int32_t *)(blk + o_atoms); t->res_ref = (int16_t *)(blk + o_ref);
+    t->res_name = blk + o_name; t->res_number = blk + o_number; t->res_chain = blk + o_chain;
+    t->res_offsets[0] = 0;
+    for (int f = 0; f < n_paths; ++f) t->res_offsets[f + 1] = t->res_offsets[f] + count[(size_t)f];
+    for (auto &rb : done) {
+        const double *b_abs = rb->areas.data(), *b_rel = b_abs + 6 * rb->n_res;
+        for (int k = 0; k < rb->ns; ++k) {
+            const size_t m = (size_t)rb->fcount[(size_t)k], src = (size_t)rb->fstart[(size_t)k], dst = (size_t)t->res_offsets[rb->first + k];
+            if (!m) continue;
+            memcpy(t->abs + 6 * dst, b_abs + 6 * src, 48 * m);
+            memcpy(t->rel + 5 * dst, b_rel + 5 * src, 40 * m);
+            memcpy(t->res_ref + dst, rb->ref.data() + src, 2 * m);
+            memcpy(t->res_name + 4 * dst, rb->name.data() + 4 * src, 4 * m);
+            memcpy(t->res_number + 6 * dst, rb->number.data() + 6 * src, 6 * m);
+            memcpy(t->res_chain + 4 * dst, rb->chain.data() + 4 * src, 4 * m);
+            for (size_t q = 0; q < m; ++q) t->res_atoms[dst + q] = (int32_t)(rb->res_first[src + q + 1] - rb->res_first[src + q]);
+        }
+    }
+    return 0;
+}
+
+extern "C" void freesasa_gpu_residue_table_free(freesasa_gpu_residue_table *table)
+{
+    if (!table) return;
+    free(table->res_offsets); /* (the one block: assemble_residue_table) */
+    memset(table, 0, sizeof *table);
+}
+
+extern "C" int freesasa_gpu_sweep_files_residues(const char *const *paths, int n_paths, int ingest_options, int n_threads,
+                                                 int alg, double probe, int resolution, long long batch_atoms,
+                                                 double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out,
+                                                 const int *devices, int n_devices, const freesasa_ingest_classifier *classifier,
+                                                 freesasa_gpu_residue_table *table_out, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (table_out) memset(table_out, 0, sizeof *table_out);
+    if (!table_out) return set_err(err_out, err_len, "null argument");
+    const int rc = guarded(err_out, err_len, [&]() -> int {
+        ResCollector col;
+        if (sweep_impl(paths, n_paths, ingest_options, n_threads, alg, probe, resolution, batch_atoms, totals_out, class_sums_out,
+                       atoms_out, status_out, nullptr, 0, devices, n_devices, classifier, &col, err_out, err_len))
+            return -1;
+        return assemble_residue_table(n_paths, col.done, table_out, err_out, err_len);
+    });
+    if (rc) freesasa_gpu_residue_table_free(table_out);
+    return rc ? -1 : 0;
 }
 
 extern "C" int freesasa_gpu_sweep_cache_devices(const char *cache_path, int alg, double probe, int resolution, long long batch_atoms,

@@ -126,7 +126,7 @@ extern "C" void freesasa_gpu_ctx_destroy(freesasa_gpu_ctx *c)
     (void)hipStreamSynchronize(c->stream);
     DevBuf *all[] = {&c->chunk_struct, &c->chunk_begin, &c->chunk_len, &c->struct_chunk0, &c->bpart, &c->offsets, &c->grid, &c->ncells, &c->sid, &c->cell_of, &c->rank, &c->cell_start,
                      &c->blk_sums, &c->cell_tbl, &c->cell_first, &c->sq, &c->s_idx,
-                     &c->status, &c->ovf_tiles, &c->ovf_tiles2, &c->ovf_atoms, &c->unit_pts, &c->captab, &c->slab, &c->seg,
+                     &c->status, &c->ovf_tiles, &c->ovf_tiles2, &c->ovf_atoms, &c->unit_pts, &c->captab, &c->slab, &c->seg, &c->res_table,
                      &c->h_xyz, &c->h_radii, &c->h_sasa, &c->h_counts, &c->h_totals, &c->h_group, &c->h_iso, &c->h_gtot,
                      &c->g_meta, &c->g_key, &c->g_count, &c->g_cursor, &c->g_xyz, &c->g_radii, &c->g_src, &c->g_sasa,
                      &c->g_gath, &c->g_tot, &c->g_tot2};
@@ -142,6 +142,7 @@ extern "C" void freesasa_gpu_ctx_destroy(freesasa_gpu_ctx *c)
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->stage_in) (void)hipHostFree(c->stage_in);
     if (c->stage_out) (void)hipHostFree(c->stage_out);
+    if (c->res_stage) (void)hipHostFree(c->res_stage);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }

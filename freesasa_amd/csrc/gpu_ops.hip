@@ -82,6 +82,30 @@ extern "C" int freesasa_gpu_residue_areas_dev(freesasa_gpu_ctx *c, const double 
     });
 }
 
+/* (engine_internal.h) the same kernel for callers whose residue arrays are on the device already: the file sweep's table */
+int residue_areas_resident(freesasa_gpu_ctx *c, const double *d_sasa, const unsigned char *d_class, const unsigned char *d_backbone,
+                           const int64_t *d_res_first, const short *d_ref_row, int n_res, double *d_abs, double *d_rel)
+{
+    if (!d_sasa || !d_class || !d_backbone || !d_res_first || !d_abs || n_res <= 0) return ctx_fail(c, "bad argument");
+    const double *d_table = nullptr;
+    if (d_ref_row) {
+        if (!c->res_table.p) {
+            const int rows = freesasa_ingest_residue_reference_table(nullptr);
+            c->res_table_host.resize(5 * (size_t)rows); /* (lives in the context: the copy may run later) */
+            freesasa_ingest_residue_reference_table(c->res_table_host.data());
+            if (ensure(c, c->res_table, 8 * c->res_table_host.size())) return -1;
+            if (hipMemcpyAsync(c->res_table.p, c->res_table_host.data(), 8 * c->res_table_host.size(), hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+                (void)hipFree(c->res_table.p);
+                c->res_table = DevBuf();
+                return ctx_fail(c, "upload of the reference areas failed");
+            }
+        }
+        d_table = (const double *)c->res_table.p;
+    }
+    HIP_TRY(c, kl_residue_areas(d_sasa, d_class, d_backbone, d_res_first, d_ref_row, d_table, d_abs, d_ref_row ? d_rel : nullptr, n_res, c->stream));
+    return 0;
+}
+
 /* ------------------------------------------------------------------ test hooks of the L&R kernel's integer parts */
 
 /* The neighbor sets the Lee-Richards kernel finds (ref: freesasa_nb_new with radii + probe, src/nb.c:524-557, what

@@ -32,4 +32,17 @@ int parse_batch_dev_begin(freesasa_gpu_ctx *c, unsigned char *h_text, size_t T, 
                           const struct freesasa_ingest_classifier *cls, int *atoms_out, int *status_out, int *host_out, long long *total_atoms_out);
 int parse_batch_dev_finish(freesasa_gpu_ctx *c, long long extra_atoms);
 
+/* Residues of the atoms the device kept (freesasa_gpu_sweep_files_residues), behind parse_batch_dev_finish on the same stream,
+ * by the host loader's rules (ingest.c parse_pdb / cif_visit_atom): nothing here synchronises.
+ * _count: key and backbone flag of every kept atom in atom order (flags into c->parse[15], sized for the atoms + extra_atoms),
+ *   the number of residue starts; the count is on its way into a page-locked word and is read with _found once the stream
+ *   has been waited for (run_batch does).
+ * _build: first atom (c->parse[16], int64 [n_res + 1], batch-wide; sized for n_res + extra_res + 1 so that the caller can
+ *   append the host parser's), reference row (c->parse[17], int16; -1 throughout when custom), labels (c->parse[18]: n_res
+ *   names of 4 bytes | n_res chains of 4 | n_res numbers of 6) and, per file that kept atoms, its first residue
+ *   (c->parse[14], int32 [F], others -1). */
+int parse_batch_dev_residues_count(freesasa_gpu_ctx *c, long long extra_atoms);
+int parse_batch_dev_residues_found(freesasa_gpu_ctx *c);
+int parse_batch_dev_residues_build(freesasa_gpu_ctx *c, int n_res, long long extra_res, int custom);
+
 #endif

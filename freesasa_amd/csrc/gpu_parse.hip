@@ -15,13 +15,17 @@
  *   kp_resolve       one wave per file, its lines in order: first ENDMDL / lowest model, the alt-loc rule (a scan: wave
  *                    ballots), the first error, which atoms are kept and where they land
  *   kp_scatter       kept atoms to the batch arrays the tile kernels read
+ *   kp_res_keys / kp_res_count / kp_res_build   ONLY for a sweep that asks for the per-residue table: residue key and
+ *                    backbone flag of every kept atom in atom order, a flag where the key changes, its prefix sum over the
+ *                    batch's atoms (kp_scan_blocks again), first atom / labels / reference row per residue
  *
  * What the device REFUSES goes to the host parser, file by file, and is counted: coordinates not of the "%8.3f" form
  * (PDB) or not plain decimals of <= 15 digits (mmCIF) - the host's strtod path -, lines longer than the reference's
  * 119-byte fgets chunk, RADIUS_FROM_OCCUPANCY, mmCIF that is not ONE data block with its _atom_site category in one
  * loop with one row per line (pair form, several blocks, text fields or names with blanks inside the rows).
- * Output: coordinates, radii, classes, atoms per file, status per file - what a sweep needs.  Residue boundaries and
- * labels are not built here (the sweep's totals and class sums do not use them; freesasa_ingest_* builds them).
+ * Output: coordinates, radii, classes, atoms per file, status per file - what a sweep's totals and class sums need - and,
+ * for freesasa_gpu_sweep_files_residues, residue boundaries, labels, reference rows and backbone flags by the host loader's
+ * rules (parse_batch_dev_residues_*; kernels of their own, so the plain sweep runs exactly the kernels it ran before).
  */
 #include <hip/hip_runtime.h>
 
@@ -549,6 +553,177 @@ __global__ __launch_bounds__(PB) void kp_scatter(ParseArgs a)
     a.cls[o] = a.lcls[l];
 }
 
+/* ---- residues (freesasa_gpu_sweep_files_residues): what ingest.c parse_pdb / cif_visit_atom build next to the atoms.
+   Kernels of their own behind kp_scatter: the sweep without residues launches none of them.
+   The key of a kept atom, 16 bytes in ATOM order: [0..5] res_number, [6..9] res_chain, [10..13] res_name as
+   freesasa_ingest_batch stores them, [14] backbone flag, [15] 1 for the first kept atom of its file. */
+struct ResArgs {
+    ParseArgs p;              /* text, files, lines, lpos, fatoms, foff */
+    uint4 *akey;              /* [A] */
+    unsigned char *bb;        /* [A] backbone flags, the array k_residue_areas reads */
+    long long A;              /* atoms the device kept in this batch */
+    int R, custom;            /* kp_res_build: residues (the count kp_res_count found); a user classifier: no reference rows */
+    long long *res_first;     /* [R + 1] */
+    short *res_ref;           /* [R] */
+    unsigned *res_name, *res_chain; /* [R] four bytes each */
+    unsigned short *res_number;     /* [3 R] six bytes each */
+    int *frfirst;             /* [F] first residue of every file that kept atoms (others untouched) */
+    unsigned bbkey[BACKBONE_N];     /* backbone names, residue names of the reference-area table: up to 3 characters, byte k = character k */
+    unsigned refkey[RESIDUE_REF_N];
+};
+
+__host__ __device__ __forceinline__ unsigned tok3_key(const unsigned char *t, int n)
+{
+    return (unsigned)t[0] | (n > 1 ? (unsigned)t[1] << 8 : 0u) | (n > 2 ? (unsigned)t[2] << 16 : 0u);
+}
+
+/* one thread per line; a kept line's fields to its atom's place */
+__global__ __launch_bounds__(PB) void kp_res_keys(ResArgs ra)
+{
+    const ParseArgs &a = ra.p;
+    const int l = blockIdx.x * PB + threadIdx.x;
+    if (l >= a.L) return;
+    const int p = a.lpos[l];
+    if (p < 0) return;
+    const unsigned s = a.lstart[l], e = a.lstart[l + 1] - 1;
+    int lo = 0, hi = a.F;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (a.files[mid].beg <= s) lo = mid; else hi = mid; }
+    if (a.fatoms[lo] == 0) return;
+    const long long o = a.foff[lo] + p;
+    if (o >= ra.A) return;
+    const ParseFile pf = a.files[lo];
+    const unsigned char *line = a.text + s;
+    unsigned char k[16];
+    for (int i = 0; i < 16; ++i) k[i] = 0;
+    const unsigned char *an;
+    int al;
+    if (pf.kind == PARSE_PDB) {
+        /* (a kept atom line has its 54 columns and no NUL before them: ingest.c parse_pdb) */
+        for (int i = 0; i < 5; ++i) k[i] = line[22 + i];
+        k[6] = line[21];
+        for (int i = 0; i < 3; ++i) k[10 + i] = line[17 + i];
+        int as_;
+        al = field_token(line + 12, 4, &as_);
+        an = line + 12 + as_;
+    } else {
+        /* the row's tokens again (parse_cif_line took this line as a row: same cuts) */
+        const int n = (int)(e - s);
+        int tp[6], tn[6];
+        for (int q = 0; q < 6; ++q) { tp[q] = 0; tn[q] = 0; }
+        int i = 0, col = 0;
+        while (i < n) {
+            while (i < n && cif_ws(line[i])) ++i;
+            if (i >= n || line[i] == '#') break;
+            const int t0 = i;
+            if (line[i] == '\'' || line[i] == '"') {
+                const unsigned q = line[i++];
+                while (i < n) {
+                    if (line[i] == q && (i + 1 >= n || cif_ws(line[i + 1]))) { ++i; break; }
+                    ++i;
+                }
+            } else {
+                while (i < n && !cif_ws(line[i])) ++i;
+            }
+            for (int q = 1; q < 6; ++q)
+                if (pf.slot[q] == col) { tp[q] = t0; tn[q] = i - t0; }
+            ++col;
+        }
+        /* number: auth_seq_id (15 characters at most, up to a NUL) + the insertion code unless '?', cut to 5 (ingest.c cif_visit_atom) */
+        int nn = 0;
+        const int w = tn[2] < 15 ? tn[2] : 15;
+        while (nn < w && line[tp[2] + nn] != 0) ++nn;
+        const unsigned ins = line[tp[3]];
+        for (int q = 0; q < 5; ++q) {
+            const unsigned ch = q < nn ? line[tp[2] + q] : (q == nn && ins != '?' ? ins : 0u);
+            if (ch == 0) break;
+            k[q] = (unsigned char)ch;
+        }
+        for (int q = 0; q < 3 && q < tn[1] && line[tp[1] + q] != 0; ++q) k[6 + q] = line[tp[1] + q];
+        for (int q = 0; q < 3 && q < tn[4] && line[tp[4] + q] != 0; ++q) k[10 + q] = line[tp[4] + q];
+        an = line + tp[5];
+        al = tn[5];
+        if (al >= 2 && an[0] == '"') { ++an; al -= 2; }
+        if (al > 4) al = 4;
+    }
+    /* ingest.c backbone_tok: names of 1 to 3 characters */
+    unsigned bb = 0;
+    if (al >= 1 && al <= 3) {
+        const unsigned key = tok3_key(an, al);
+        for (int i = 0; i < BACKBONE_N; ++i) bb |= ra.bbkey[i] == key ? 1u : 0u;
+    }
+    k[14] = (unsigned char)bb;
+    k[15] = p == 0 ? 1 : 0;
+    uint4 v;
+    v.x = k[0] | (k[1] << 8) | (k[2] << 16) | ((unsigned)k[3] << 24);
+    v.y = k[4] | (k[5] << 8) | (k[6] << 16) | ((unsigned)k[7] << 24);
+    v.z = k[8] | (k[9] << 8) | (k[10] << 16) | ((unsigned)k[11] << 24);
+    v.w = k[12] | (k[13] << 8) | (k[14] << 16) | ((unsigned)k[15] << 24);
+    ra.akey[o] = v;
+    ra.bb[o] = (unsigned char)bb;
+}
+
+/* a residue starts at a file's first kept atom and where number or chain differ from the previous kept atom's */
+__device__ __forceinline__ bool res_starts(const ResArgs &ra, long long i, uint4 &v)
+{
+    if (i >= ra.A) return false;
+    v = ra.akey[i];
+    if ((v.w >> 24) || i == 0) return true;
+    const uint4 u = ra.akey[i - 1];
+    return u.x != v.x || u.y != v.y || ((u.z ^ v.z) & 0xffffu) != 0;
+}
+
+__global__ __launch_bounds__(PB) void kp_res_count(ResArgs ra)
+{
+    __shared__ unsigned part[PB / 64];
+    uint4 v;
+    unsigned c = res_starts(ra, (long long)blockIdx.x * PB + threadIdx.x, v) ? 1u : 0u;
+    for (int d = 1; d < 64; d <<= 1) c += __shfl_xor(c, d, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) ra.p.blk_cnt[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+
+/* behind kp_scan_blocks: the residue an atom starts is the number of starts before it - the same in every run, for any batch cut */
+__global__ __launch_bounds__(PB) void kp_res_build(ResArgs ra)
+{
+    __shared__ unsigned wsum[PB / 64];
+    const long long i = (long long)blockIdx.x * PB + threadIdx.x;
+    uint4 v;
+    const bool st = res_starts(ra, i, v);
+    unsigned incl = st ? 1u : 0u;
+    for (int d = 1; d < 64; d <<= 1) { const unsigned o = __shfl_up(incl, d, 64); if ((int)(threadIdx.x & 63) >= d) incl += o; }
+    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
+    __syncthreads();
+    unsigned r = ra.p.blk_cnt[blockIdx.x] + incl - (st ? 1u : 0u);
+    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) r += wsum[w];
+    if (i == 0) ra.res_first[ra.R] = ra.A;
+    if (!st || r >= (unsigned)ra.R) return;
+    ra.res_first[r] = i;
+    ra.res_number[3 * (size_t)r] = (unsigned short)(v.x & 0xffffu);
+    ra.res_number[3 * (size_t)r + 1] = (unsigned short)(v.x >> 16);
+    ra.res_number[3 * (size_t)r + 2] = (unsigned short)(v.y & 0xffffu);
+    ra.res_chain[r] = (v.y >> 16) | (v.z << 16);
+    const unsigned name = (v.z >> 16) | (v.w << 16);
+    ra.res_name[r] = name;
+    /* ingest.c residue_ref_index: the name's first token, 1 to 3 characters, in the table of reference areas */
+    int row = -1;
+    if (!ra.custom) {
+        unsigned t = name;
+        while ((t & 0xffu) != 0 && is_sp(t & 0xffu)) t >>= 8;
+        unsigned key = 0;
+        int n = 0;
+        for (; n < 4 && ((t >> (8 * n)) & 0xffu) != 0 && !is_sp((t >> (8 * n)) & 0xffu); ++n) key |= t & (0xffu << (8 * n));
+        if (n >= 1 && n <= 3)
+            for (int q = RESIDUE_REF_N - 1; q >= 0; --q) row = ra.refkey[q] == key ? q : row;
+    }
+    ra.res_ref[r] = (short)row;
+    if (v.w >> 24) {
+        int lo = 0, hi = ra.p.F;
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (ra.p.foff[mid] <= i) lo = mid; else hi = mid; }
+        ra.frfirst[lo] = (int)r;
+    }
+}
+
 /* the classifier's tables on the device, once per device */
 struct Tables { void *p = nullptr; };
 Tables g_tables[64];
@@ -694,6 +869,74 @@ int parse_batch_dev_finish(freesasa_gpu_ctx *c, long long extra_atoms)
     a.xyz = (double *)c->h_xyz.p; a.radii = (double *)c->h_radii.p; a.cls = (unsigned char *)c->h_counts.p;
     HIP_TRY(c, hipMemcpyAsync(B[4].p, c->parse_off.data(), 8 * ((size_t)F + 1), hipMemcpyHostToDevice, st)); /* (parse_off lives in the context: the copy may run later) */
     hipLaunchKernelGGL(kp_scatter, dim3((unsigned)((L + PB - 1) / PB)), dim3(PB), 0, st, a);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+/* ---- residues (gpu_parse.h).  Buffers: c->parse[12] atom keys, [13] block counts of residue starts, [14] first residue per
+   file, [15] backbone flags, [16] res_first, [17] reference rows, [18] labels (names | chains | numbers). */
+static void res_args(freesasa_gpu_ctx *c, ResArgs &ra)
+{
+    memset(&ra, 0, sizeof ra);
+    DevBuf *B = c->parse;
+    ParseArgs &a = ra.p;
+    const int F = c->parse_files;
+    a.T = c->parse_T; a.F = F; a.options = c->parse_options; a.L = c->parse_lines;
+    a.text = (const unsigned char *)B[0].p; a.files = (const ParseFile *)B[1].p;
+    a.fatoms = (int *)B[3].p; a.fstatus = a.fatoms + F; a.fhost = a.fstatus + F; a.foff = (long long *)B[4].p;
+    a.lstart = (unsigned *)B[5].p; a.lpos = (int *)B[8].p;
+    ra.A = c->parse_atoms;
+    a.n_blocks = (int)((ra.A + PB - 1) / PB);
+    a.blk_cnt = (unsigned *)B[13].p;
+    ra.akey = (uint4 *)B[12].p; ra.bb = (unsigned char *)B[15].p;
+    for (int i = 0; i < BACKBONE_N; ++i) { const char *b = backbone_names[i]; ra.bbkey[i] = tok3_key((const unsigned char *)b, (int)strlen(b)); }
+    for (int i = 0; i < RESIDUE_REF_N; ++i) { const char *r = residue_ref_table[i].res; ra.refkey[i] = tok3_key((const unsigned char *)r, (int)strlen(r)); }
+}
+
+int parse_batch_dev_residues_count(freesasa_gpu_ctx *c, long long extra_atoms)
+{
+    int *words = c->pinned + 2 * (sasa::ST_WORDS + 4);
+    words[1] = 0;
+    const long long A = c->parse_atoms, cap = A + (extra_atoms > 0 ? extra_atoms : 0);
+    if (cap <= 0) return 0;
+    DevBuf *B = c->parse;
+    if (ensure(c, B[15], (size_t)cap)) return -1;
+    if (A == 0) return 0;
+    const int rblocks = (int)((A + PB - 1) / PB);
+    if (ensure(c, B[12], 16 * (size_t)A) || ensure(c, B[13], 4 * ((size_t)rblocks + 2))) return -1;
+    ResArgs ra;
+    res_args(c, ra);
+    hipStream_t st = c->stream;
+    hipLaunchKernelGGL(kp_res_keys, dim3((unsigned)((c->parse_lines + PB - 1) / PB)), dim3(PB), 0, st, ra);
+    hipLaunchKernelGGL(kp_res_count, dim3(rblocks), dim3(PB), 0, st, ra);
+    hipLaunchKernelGGL(kp_scan_blocks, dim3(1), dim3(1024), 0, st, ra.p);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(words + 1, ra.p.blk_cnt + rblocks, 4, hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+int parse_batch_dev_residues_found(freesasa_gpu_ctx *c)
+{
+    return (c->pinned + 2 * (sasa::ST_WORDS + 4))[1];
+}
+
+int parse_batch_dev_residues_build(freesasa_gpu_ctx *c, int n_res, long long extra_res, int custom)
+{
+    const size_t cap = (size_t)n_res + (size_t)(extra_res > 0 ? extra_res : 0);
+    DevBuf *B = c->parse;
+    if (cap == 0) return 0;
+    if (ensure(c, B[16], 8 * (cap + 1)) || ensure(c, B[17], 2 * cap)) return -1;
+    if (n_res <= 0) return 0;
+    const int F = c->parse_files;
+    if (ensure(c, B[18], 14 * (size_t)n_res) || ensure(c, B[14], 4 * (size_t)F)) return -1;
+    ResArgs ra;
+    res_args(c, ra);
+    ra.R = n_res; ra.custom = custom;
+    ra.res_first = (long long *)B[16].p; ra.res_ref = (short *)B[17].p;
+    ra.res_name = (unsigned *)B[18].p; ra.res_chain = ra.res_name + n_res; ra.res_number = (unsigned short *)(ra.res_chain + n_res);
+    ra.frfirst = (int *)B[14].p;
+    HIP_TRY(c, hipMemsetAsync(B[14].p, 0xff, 4 * (size_t)F, c->stream));
+    hipLaunchKernelGGL(kp_res_build, dim3((unsigned)ra.p.n_blocks), dim3(PB), 0, c->stream, ra);
     HIP_TRY(c, hipGetLastError());
     return 0;
 }

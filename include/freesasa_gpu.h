@@ -271,6 +271,38 @@ long long freesasa_gpu_parse_files_classified(const char *const *paths, int n_pa
                                               double *xyz_out, double *radii_out, unsigned char *class_out, long long cap,
                                               long long *offsets_out, int *status_out, int *host_out,
                                               const struct freesasa_ingest_classifier *classifier, char *err, int err_len);
+/* The file sweep with a PER-RESIDUE table: what the reference prints with --format=rsa / --format=seq (src/rsa.c:14-25,
+   src/node.c:717-764), for all files of a sweep in one call.  The arguments of freesasa_gpu_sweep_files_classified without
+   done_path and max_new_batches; totals, class sums, atom counts and status come back exactly as that entry gives them, and
+   table_out receives one table for all files: file k owns residues [res_offsets[k], res_offsets[k + 1]) - none if it failed -
+   in the file's order, whatever the devices, workers or the batch cut.  Per residue: its atoms, the row of the reference-area
+   table (freesasa_ingest_residue_reference_table; -1: none), abs[6 r + ..] = total, main chain, side chain, polar, apolar,
+   unknown and rel[5 r + ..] = 100 * abs / reference (NaN where res_ref < 0) as freesasa_gpu_residue_areas_dev computes them,
+   and the labels in the byte layout of freesasa_ingest_batch.  classifier NULL: ProtOr; a user classifier: res_ref -1 and rel
+   NaN throughout (a configuration file has no reference areas; the reference's CLI drops its REL columns under -c,
+   src/main.cc:729-730).  The per-atom areas never leave the device: the residue sums are taken there, and with
+   FREESASA_INGEST_PARSE_ON_DEVICE the residues themselves - boundaries, labels, reference rows, backbone flags - are built on
+   the device by the host loader's rules (csrc/gpu_parse.hip); files the device refuses are read by the host parser as in
+   every sweep.  The table's arrays are ONE block, released by freesasa_gpu_residue_table_free only (which zeroes the struct;
+   a zeroed struct is a no-op); on any failure (-1, message in err) the struct is zeroed and nothing is kept.
+   Not offered: a done-list / resumable form (records of variable length need a file format of their own), the cache sweep
+   (a cache read brings coordinates, radii and classes, no residue arrays), per-residue output of the trajectory drivers. */
+typedef struct freesasa_gpu_residue_table {
+    int32_t n_files;
+    int64_t n_residues;
+    int64_t *res_offsets;  /* [n_files + 1] */
+    int32_t *res_atoms;    /* [n_residues] atoms of the residue */
+    int16_t *res_ref;      /* [n_residues] row of the reference-area table, -1: none */
+    double *abs;           /* [6 * n_residues] */
+    double *rel;           /* [5 * n_residues] */
+    char *res_name, *res_number, *res_chain; /* [4 | 6 | 4 bytes per residue], as in freesasa_ingest_batch */
+} freesasa_gpu_residue_table;
+int freesasa_gpu_sweep_files_residues(const char *const *paths, int n_paths, int ingest_options, int n_threads,
+                                      int alg, double probe_radius, int resolution, long long batch_atoms,
+                                      double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out,
+                                      const int *devices, int n_devices, const struct freesasa_ingest_classifier *classifier,
+                                      freesasa_gpu_residue_table *table_out, char *err, int err_len);
+void freesasa_gpu_residue_table_free(freesasa_gpu_residue_table *table);
 int freesasa_gpu_sweep_cache_devices(const char *cache_path, int alg, double probe_radius, int resolution, long long batch_atoms,
                                      double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out, int n_out,
                                      const int *devices, int n_devices, int lanes_per_device, char *err, int err_len);

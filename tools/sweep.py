@@ -2,14 +2,17 @@
 """Whole-directory sweep: PDB files -> batched ingestion on host threads -> SASA on the GPU ->
 per-structure totals (BASELINE configs[3] in miniature; SURVEY §8f N1 + the batch entry point).
 
-    python tools/sweep.py [--replicate N] [--threads T] [--batch-atoms A] [--devices 0,1,...] [--done FILE] [--cache FILE] [paths ...]
+    python tools/sweep.py [--replicate N] [--threads T] [--batch-atoms A] [--devices 0,1,...] [--done FILE] [--cache FILE]
+                          [--residues OUT.tsv] [paths ...]
 
 Without paths it sweeps the PDB fixtures under tests/golden/pdb, replicated N times.  Loading of
 batch k+1 runs on host threads while the GPU computes batch k.  Prints one JSON line with the
 end-to-end rate, the loader-only rate and (if oracle/_ref is present) the reference reader's
 single-thread rate on the same files.  --devices: the GPUs that share the batches (freesasa_gpu_sweep_files_devices;
 default: every visible device; entries may repeat); --done: a done-list, so that an interrupted sweep resumes — on any
-device list; --cache FILE: sweep the binary cache FILE instead (written first from the files if it does not exist)."""
+device list; --cache FILE: sweep the binary cache FILE instead (written first from the files if it does not exist);
+--residues OUT.tsv: the per-residue table of all files (freesasa_gpu_sweep_files_residues): file, chain, number, name, the
+five absolute areas (total, main chain, side chain, polar, apolar) and the five relative ones, N/A where there is none."""
 import argparse
 import glob
 import json
@@ -24,6 +27,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def write_residues(path, paths, table):
+    """one line per residue; NaN (no reference areas for the residue) is written N/A, as the reference's RSA files do"""
+    name, number, chain = table.res_name, table.res_number, table.res_chain
+    with open(path, "w") as fh:
+        fh.write("file\tchain\tnumber\tname\tabs_total\tabs_main\tabs_side\tabs_polar\tabs_apolar\trel_total\trel_main\trel_side\trel_polar\trel_apolar\n")
+        for k, p in enumerate(paths):
+            for r in range(int(table.res_offsets[k]), int(table.res_offsets[k + 1])):
+                cols = [p, chain[r], number[r].strip(), name[r].strip()] + [f"{v:.2f}" for v in table.abs[r, :5]] + \
+                       ["N/A" if np.isnan(v) else f"{v:.1f}" for v in table.rel[r]]
+                fh.write("\t".join(cols) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("paths", nargs="*")
@@ -36,10 +51,13 @@ def main():
     ap.add_argument("--devices", default="", help="comma-separated device list (default: all visible devices)")
     ap.add_argument("--done", default=None, help="done-list file: resume an interrupted sweep")
     ap.add_argument("--cache", default=None, help="binary cache file to sweep (created from the files when missing)")
+    ap.add_argument("--residues", default=None, metavar="OUT.tsv", help="write the per-residue table of all files (not with --done or --cache)")
     ap.add_argument("--engine", choices=["python", "c"], default="c",
                     help="c: freesasa_gpu_sweep_files (loader thread || GPU inside the library); "
                          "python: the same pipeline written with the two-step Python API")
     args = ap.parse_args()
+    if args.residues and (args.done or args.cache or args.no_gpu or args.engine != "c"):
+        ap.error("--residues goes with the C engine's plain file sweep only (no --done, --cache, --no-gpu, --engine python)")
     import freesasa_amd as fa
     from freesasa_amd import ingest
 
@@ -80,6 +98,11 @@ def main():
             complete, totals, _, atoms, status = fa.sweep_files_resumable(paths, args.done, fa.LEE_RICHARDS, resolution=args.slices, n_threads=args.threads,
                                                                          batch_atoms=args.batch_atoms, devices=devices, ingest_options=popt)
             out["complete"] = bool(complete)
+        elif args.residues:
+            totals, _, atoms, status, table = fa.sweep_files_residues(paths, fa.LEE_RICHARDS, resolution=args.slices, n_threads=args.threads,
+                                                                      batch_atoms=args.batch_atoms, devices=devices, ingest_options=popt)
+            write_residues(args.residues, paths, table)
+            out["residues"] = int(table.n_residues)
         else:
             totals, _, atoms, status = fa.sweep_files(paths, fa.LEE_RICHARDS, resolution=args.slices, n_threads=args.threads,
                                                       batch_atoms=args.batch_atoms, class_sums=True, devices=devices, ingest_options=popt)
