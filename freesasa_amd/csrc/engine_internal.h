@@ -8,7 +8,10 @@
  *                      asynchronous batches, the device-pointer entry points
  *   gpu_ops.hip        device-side aggregates (segments, classes, residues) and the kernel test hooks
  *   gpu_hostbatch.hip  host-pointer batches: the context pool, one device, several devices, the pipelined form
- *   gpu_drivers.hip    file sweep and trajectory drivers (one device or a list of devices), done-lists
+ *   gpu_drivers.hip    cache sweep and trajectory drivers (one device or a list of devices); what the drivers share
+ *                      (device lists, the host budget, DoneList)
+ *   gpu_sweep.hip      the file sweep (host or device parser, done-list, per-residue table) and the device parser's entries
+ *   gpu_parse.hip      the device-side PDB / mmCIF parser: its kernels and their host driver (gpu_parse.h)
  *   gpu_groups.hip     chain groups: a batch and every group of it cut out as a structure of its own, in one batch
  */
 #ifndef FREESASA_AMD_ENGINE_INTERNAL_H
@@ -16,9 +19,15 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+#include <functional>
+#include <mutex>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdio.h>
+#include <string>
 #include <thread>
+#include <unistd.h>
 #include <vector>
 
 #include "../../include/freesasa_gpu.h"
@@ -26,6 +35,7 @@
 #include "sasa_kernels.h"
 #include "lr2_kernels.h"
 #include "group_kernels.h"
+#include "gpu_parse.h"
 
 /* ------------------------------------------------------------------ kernel launchers (gpu_kernels.hip) */
 
@@ -119,7 +129,7 @@ struct freesasa_gpu_ctx {
     DevBuf g_meta, g_key, g_count, g_cursor, g_xyz, g_radii, g_src, g_sasa, g_gath, g_tot, g_tot2;
     void *stage_in = nullptr, *stage_out = nullptr; /* page-locked host staging of freesasa_gpu_calc_batch_pipelined */
     size_t stage_in_cap = 0, stage_out_cap = 0;
-    void *res_stage = nullptr; /* page-locked: a batch's per-residue areas and arrays on their way to the host (gpu_drivers.hip) */
+    void *res_stage = nullptr; /* page-locked: a batch's per-residue areas and arrays on their way to the host (gpu_sweep.hip) */
     size_t res_stage_cap = 0;
     int *pinned = nullptr; /* page-locked host words for the small device->host readbacks: two sets of ST_WORDS + 4 */
     long long max_cells = 1LL << 30;
@@ -136,7 +146,7 @@ struct freesasa_gpu_ctx {
     bool hint_far = false;    /* ... a quarter or more of its tiles had an atom beyond LR2_WALK_Z: the next batch gets the walking build of the main launch */
     int hint_pool2 = 0, hint_ta2 = 0, hint_mw2 = 0; /* ... and the pool the last batch's demand histogram asks for, for tiles of that shape */
     /* the device-side parser's workspace and what its two phases hand each other (gpu_parse.hip) */
-    DevBuf parse[20]; /* gpu_parse.hip: [0..10] text, files, lines; [11] a user classifier's table; [12..18] residues (gpu_parse.h); [19] per-residue areas (gpu_drivers.hip) */
+    DevBuf parse[PBUF_COUNT]; /* (enum ParseBuf, gpu_parse.h, says what each holds) */
     std::vector<long long> parse_off;
     std::vector<unsigned char> parse_table; /* host copy of a user classifier's table being uploaded (gpu_parse.hip) */
     long long parse_atoms = 0;
@@ -270,6 +280,66 @@ struct PoolLease {
         pool_put(c);
     }
 };
+/* ------------------------------------------------------------------ what the drivers share (gpu_drivers.hip) */
+
+bool pread_all(int fd, void *buf, size_t bytes, long long off);
+bool pwrite_all(int fd, const void *buf, size_t bytes, long long off);
+/* the device list of a call: every entry an existing device (entries may repeat); -1 with a message */
+int check_devices(const int *devices, int n_devices, char *err_out, int err_len);
+/* CPUs this process may count on (the cgroup's grant divided among the ranks of the node), and the host threads of one of
+   n_workers loaders: the caller's total (or, <= 0, this process's CPUs) divided among them */
+int process_cpus();
+int threads_per_worker(int n_threads, int n_workers);
+
+/* a descriptor of a driver's scope: closed on every way out of it */
+struct Fd {
+    int fd = -1;
+    Fd() = default;
+    Fd(const Fd &) = delete;
+    Fd &operator=(const Fd &) = delete;
+    ~Fd() { if (fd >= 0) close(fd); }
+};
+
+/* first failure of a set of workers wins; the others stop taking work */
+struct FirstError {
+    std::mutex mu;
+    std::atomic<int> failed{0};
+    char text[256] = {0};
+    void set(const char *msg)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!failed.load()) snprintf(text, sizeof text, "%s", msg && msg[0] ? msg : "GPU driver failed");
+        failed = 1;
+    }
+    void set_exception() noexcept /* inside a catch block */
+    {
+        char msg[200];
+        try { set(exception_text(msg, sizeof msg)); } catch (...) { failed = 1; }
+    }
+};
+
+/* The done-list of a resumable run: a first line that names the run (built by its driver), then "shard <unit> <a> <b>" per
+   finished unit (a batch of files, a shard of frames), appended by one worker at a time once the unit's results are on disk.
+   read: FRESH (no list, or an empty one), RESUMED (the list of this run: its complete lines that valid() accepts are done
+   - a line cut short by a crash does not count) or REFUSED (another run's list; nothing is touched).  open: for appending -
+   a fresh list is truncated and gets its first line; 0, -1 cannot open, -2 cannot write.  A driver opens its result files
+   between the two, truncated unless resumed(). */
+struct DoneList {
+    enum { FRESH = 0, RESUMED = 1, REFUSED = 2 };
+    int read(const char *path, const char *head, long long n_units, const std::function<bool(long long, long long, long long)> &valid);
+    int open();
+    bool active() const { return f.fd >= 0; }
+    bool resumed() const { return resumed_; }
+    bool done(long long k) const { return (size_t)k < done_.size() && done_[(size_t)k]; }
+    int append(long long k, long long a, long long b); /* the line, flushed to disk; 0 / -1 */
+private:
+    Fd f;
+    std::mutex mu;
+    std::string path_, head_;
+    bool resumed_ = false;
+    std::vector<char> done_;
+};
+
 bool host_pinned(const void *p); /* page-locked already (hipHostMalloc / hipHostRegister, e.g. a pinned tensor)? */
 int ensure_pinned(freesasa_gpu_ctx *c, void **p, size_t *cap, size_t bytes); /* grow a context's page-locked staging buffer */
 

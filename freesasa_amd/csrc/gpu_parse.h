@@ -24,23 +24,50 @@ struct ParseFile {
     unsigned char pad[3];
 };
 
+/* The parser's device buffers, c->parse[] (engine_internal.h): one name per slot.  [F]: per file of the batch, [L]: per line,
+   [A]: per kept atom, [R]: per residue. */
+enum ParseBuf {
+    PBUF_TEXT,        /* unsigned char: the batch's text, padded to 16 bytes */
+    PBUF_FILES,       /* ParseFile [F + 1] */
+    PBUF_BLK_CNT,     /* unsigned [text blocks + 2]: newlines per block, scanned; the last word: lines */
+    PBUF_FILE_WORDS,  /* int: atoms [F] | status [F] | refused [F] */
+    PBUF_FILE_OFF,    /* long long [F + 1]: a file's first kept atom */
+    PBUF_LSTART,      /* unsigned [L + 2]: a line's first byte */
+    PBUF_LFLAG,       /* unsigned [L] */
+    PBUF_LMODEL,      /* int [L] */
+    PBUF_LPOS,        /* int [L]: a kept line's place among its file's atoms */
+    PBUF_LXYZR,       /* double: x [L] | y [L] | z [L] | radius [L] */
+    PBUF_LCLS,        /* unsigned char [L]: class */
+    PBUF_CLASSIFIER,  /* a user classifier's table: keys (uint64) | radii (double) | classes (unsigned char) */
+    PBUF_AKEY,        /* uint4 [A]: residue key of every kept atom */
+    PBUF_RES_BLK_CNT, /* unsigned [atom blocks + 2]: residue starts per block, scanned; the last word: residues */
+    PBUF_FILE_RES0,   /* int [F]: first residue of a file that kept atoms, others -1 */
+    PBUF_BACKBONE,    /* unsigned char [A + extra atoms]: backbone flags */
+    PBUF_RES_FIRST,   /* int64 [R + extra residues + 1]: first atom, batch-wide */
+    PBUF_RES_REF,     /* int16 [R + extra residues]: reference row (-1 throughout with a user classifier) */
+    PBUF_RES_LABELS,  /* names, 4 bytes [R] | chains, 4 bytes [R] | numbers, 6 bytes [R] */
+    PBUF_RES_AREAS,   /* double: abs [6 R] | rel [5 R], R with the host parser's residues (owned by the sweep, gpu_sweep.hip) */
+    PBUF_COUNT
+};
+
 /* Phase 1: text -> per-file atoms / status / refused (host arrays [F]) and the total of kept atoms; cls: a user classifier
  * (NULL: ProtOr), its table uploaded with the batch.  Phase 2: the kept atoms
  * into c->h_xyz / c->h_radii / c->h_counts (classes), which are sized for total + extra_atoms first (the caller appends what
- * the host parser read of the refused files behind them).  0 / -1 (message in the context). */
+ * the host parser read of the refused files behind them).  0 / -1 (message in the context).
+ * _none instead of _begin: this batch has no device-parsed part (contexts are pooled: without it _finish and the residue
+ * calls would see the counts of the context's previous batch); they then only size the buffers for the extra atoms / residues. */
 int parse_batch_dev_begin(freesasa_gpu_ctx *c, unsigned char *h_text, size_t T, const ParseFile *files, int F, int options,
                           const struct freesasa_ingest_classifier *cls, int *atoms_out, int *status_out, int *host_out, long long *total_atoms_out);
+void parse_batch_dev_none(freesasa_gpu_ctx *c);
 int parse_batch_dev_finish(freesasa_gpu_ctx *c, long long extra_atoms);
 
 /* Residues of the atoms the device kept (freesasa_gpu_sweep_files_residues), behind parse_batch_dev_finish on the same stream,
  * by the host loader's rules (ingest.c parse_pdb / cif_visit_atom): nothing here synchronises.
- * _count: key and backbone flag of every kept atom in atom order (flags into c->parse[15], sized for the atoms + extra_atoms),
- *   the number of residue starts; the count is on its way into a page-locked word and is read with _found once the stream
- *   has been waited for (run_batch does).
- * _build: first atom (c->parse[16], int64 [n_res + 1], batch-wide; sized for n_res + extra_res + 1 so that the caller can
- *   append the host parser's), reference row (c->parse[17], int16; -1 throughout when custom), labels (c->parse[18]: n_res
- *   names of 4 bytes | n_res chains of 4 | n_res numbers of 6) and, per file that kept atoms, its first residue
- *   (c->parse[14], int32 [F], others -1). */
+ * _count: key and backbone flag of every kept atom in atom order (PBUF_BACKBONE, sized for the atoms + extra_atoms), the number
+ *   of residue starts; the count is on its way into a page-locked word and is read with _found once the stream has been waited
+ *   for (run_batch does).
+ * _build: PBUF_RES_FIRST and PBUF_RES_REF (sized for n_res + extra_res so that the caller can append the host parser's),
+ *   PBUF_RES_LABELS and PBUF_FILE_RES0. */
 int parse_batch_dev_residues_count(freesasa_gpu_ctx *c, long long extra_atoms);
 int parse_batch_dev_residues_found(freesasa_gpu_ctx *c);
 int parse_batch_dev_residues_build(freesasa_gpu_ctx *c, int n_res, long long extra_res, int custom);

@@ -756,7 +756,7 @@ static int tables_for(freesasa_gpu_ctx *c, ParseArgs &pa)
     return 0;
 }
 
-/* A user classifier's table into the context's buffer next to the files' (c->parse[11]), on the stream, with every batch: a
+/* A user classifier's table into the context's buffer next to the files' (c->parse[PBUF_CLASSIFIER]), on the stream, with every batch: a
    few KB against the batch's text, and no classifier's lifetime is tied to device-global state.  (The host copy lives in the
    context too: the upload may run after this returns.)  1: the table is larger than PARSE_MAX_CLASSIFIER_ROWS. */
 static int classifier_for(freesasa_gpu_ctx *c, const freesasa_ingest_classifier *cls, ParseArgs &pa)
@@ -769,9 +769,9 @@ static int classifier_for(freesasa_gpu_ctx *c, const freesasa_ingest_classifier 
     c->parse_table.resize(bytes);
     unsigned char *h = c->parse_table.data();
     if (n) { memcpy(h, k, b_key); memcpy(h + b_key, r, b_rad); memcpy(h + b_key + b_rad, cl, (size_t)n); }
-    if (ensure(c, c->parse[11], bytes)) return -1;
-    HIP_TRY(c, hipMemcpyAsync(c->parse[11].p, h, bytes, hipMemcpyHostToDevice, c->stream));
-    char *p = (char *)c->parse[11].p;
+    if (ensure(c, c->parse[PBUF_CLASSIFIER], bytes)) return -1;
+    HIP_TRY(c, hipMemcpyAsync(c->parse[PBUF_CLASSIFIER].p, h, bytes, hipMemcpyHostToDevice, c->stream));
+    char *p = (char *)c->parse[PBUF_CLASSIFIER].p;
     pa.ckey = (const unsigned long long *)p; pa.crad = (const double *)(p + b_key); pa.ccls = (const unsigned char *)(p + b_key + b_rad);
     pa.cn = n; pa.cany = any;
     return 0;
@@ -803,13 +803,13 @@ int parse_batch_dev_begin(freesasa_gpu_ctx *c, unsigned char *h_text, size_t T, 
     a.T = (unsigned)T; a.F = F; a.options = options;
     a.n_blocks = (int)((Tp + PBLK - 1) / PBLK);
     DevBuf *B = c->parse;
-    if (ensure(c, B[0], Tp + 16) || ensure(c, B[1], sizeof(ParseFile) * ((size_t)F + 1)) || ensure(c, B[2], 4 * ((size_t)a.n_blocks + 2)) ||
-        ensure(c, B[3], 4 * 3 * (size_t)F + 16) || ensure(c, B[4], 8 * ((size_t)F + 1)))
+    if (ensure(c, B[PBUF_TEXT], Tp + 16) || ensure(c, B[PBUF_FILES], sizeof(ParseFile) * ((size_t)F + 1)) || ensure(c, B[PBUF_BLK_CNT], 4 * ((size_t)a.n_blocks + 2)) ||
+        ensure(c, B[PBUF_FILE_WORDS], 4 * 3 * (size_t)F + 16) || ensure(c, B[PBUF_FILE_OFF], 8 * ((size_t)F + 1)))
         return -1;
-    a.text = (const unsigned char *)B[0].p; a.files = (const ParseFile *)B[1].p; a.blk_cnt = (unsigned *)B[2].p;
-    a.fatoms = (int *)B[3].p; a.fstatus = a.fatoms + F; a.fhost = a.fstatus + F; a.foff = (long long *)B[4].p;
-    HIP_TRY(c, hipMemcpyAsync(B[0].p, h_text, Tp, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(B[1].p, files, sizeof(ParseFile) * ((size_t)F + 1), hipMemcpyHostToDevice, st));
+    a.text = (const unsigned char *)B[PBUF_TEXT].p; a.files = (const ParseFile *)B[PBUF_FILES].p; a.blk_cnt = (unsigned *)B[PBUF_BLK_CNT].p;
+    a.fatoms = (int *)B[PBUF_FILE_WORDS].p; a.fstatus = a.fatoms + F; a.fhost = a.fstatus + F; a.foff = (long long *)B[PBUF_FILE_OFF].p;
+    HIP_TRY(c, hipMemcpyAsync(B[PBUF_TEXT].p, h_text, Tp, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(B[PBUF_FILES].p, files, sizeof(ParseFile) * ((size_t)F + 1), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(kp_count_nl, dim3(a.n_blocks), dim3(PB), 0, st, a);
     hipLaunchKernelGGL(kp_scan_blocks, dim3(1), dim3(1024), 0, st, a);
     int *words = c->pinned + 2 * (sasa::ST_WORDS + 4); /* (four ints behind the two status sets: gpu_engine.hip) */
@@ -822,11 +822,11 @@ int parse_batch_dev_begin(freesasa_gpu_ctx *c, unsigned char *h_text, size_t T, 
         return 0;
     }
     const size_t L = (size_t)a.L;
-    if (ensure(c, B[5], 4 * (L + 2)) || ensure(c, B[6], 4 * L) || ensure(c, B[7], 4 * L) || ensure(c, B[8], 4 * L) ||
-        ensure(c, B[9], 8 * 4 * L) || ensure(c, B[10], L))
+    if (ensure(c, B[PBUF_LSTART], 4 * (L + 2)) || ensure(c, B[PBUF_LFLAG], 4 * L) || ensure(c, B[PBUF_LMODEL], 4 * L) || ensure(c, B[PBUF_LPOS], 4 * L) ||
+        ensure(c, B[PBUF_LXYZR], 8 * 4 * L) || ensure(c, B[PBUF_LCLS], L))
         return -1;
-    a.lstart = (unsigned *)B[5].p; a.lflag = (unsigned *)B[6].p; a.lmodel = (int *)B[7].p; a.lpos = (int *)B[8].p;
-    a.lx = (double *)B[9].p; a.ly = a.lx + L; a.lz = a.ly + L; a.lr = a.lz + L; a.lcls = (unsigned char *)B[10].p;
+    a.lstart = (unsigned *)B[PBUF_LSTART].p; a.lflag = (unsigned *)B[PBUF_LFLAG].p; a.lmodel = (int *)B[PBUF_LMODEL].p; a.lpos = (int *)B[PBUF_LPOS].p;
+    a.lx = (double *)B[PBUF_LXYZR].p; a.ly = a.lx + L; a.lz = a.ly + L; a.lr = a.lz + L; a.lcls = (unsigned char *)B[PBUF_LCLS].p;
     const int lblocks = (int)((L + PB - 1) / PB);
     hipLaunchKernelGGL(kp_line_starts, dim3(a.n_blocks), dim3(PB), 0, st, a);
     if (cls) hipLaunchKernelGGL(kp_parse_lines<true>, dim3(lblocks), dim3(PB), 0, st, a);
@@ -849,6 +849,12 @@ int parse_batch_dev_begin(freesasa_gpu_ctx *c, unsigned char *h_text, size_t T, 
     return 0;
 }
 
+/* (gpu_parse.h) */
+void parse_batch_dev_none(freesasa_gpu_ctx *c)
+{
+    c->parse_lines = 0; c->parse_atoms = 0; c->parse_files = 0;
+}
+
 int parse_batch_dev_finish(freesasa_gpu_ctx *c, long long extra_atoms)
 {
     const long long run = c->parse_atoms, cap = run + (extra_atoms > 0 ? extra_atoms : 0);
@@ -862,19 +868,18 @@ int parse_batch_dev_finish(freesasa_gpu_ctx *c, long long extra_atoms)
     const size_t L = (size_t)c->parse_lines;
     const int F = c->parse_files;
     a.T = c->parse_T; a.F = F; a.options = c->parse_options; a.L = (int)L;
-    a.text = (const unsigned char *)B[0].p; a.files = (const ParseFile *)B[1].p;
-    a.fatoms = (int *)B[3].p; a.fstatus = a.fatoms + F; a.fhost = a.fstatus + F; a.foff = (long long *)B[4].p;
-    a.lstart = (unsigned *)B[5].p; a.lflag = (unsigned *)B[6].p; a.lmodel = (int *)B[7].p; a.lpos = (int *)B[8].p;
-    a.lx = (double *)B[9].p; a.ly = a.lx + L; a.lz = a.ly + L; a.lr = a.lz + L; a.lcls = (unsigned char *)B[10].p;
+    a.text = (const unsigned char *)B[PBUF_TEXT].p; a.files = (const ParseFile *)B[PBUF_FILES].p;
+    a.fatoms = (int *)B[PBUF_FILE_WORDS].p; a.fstatus = a.fatoms + F; a.fhost = a.fstatus + F; a.foff = (long long *)B[PBUF_FILE_OFF].p;
+    a.lstart = (unsigned *)B[PBUF_LSTART].p; a.lflag = (unsigned *)B[PBUF_LFLAG].p; a.lmodel = (int *)B[PBUF_LMODEL].p; a.lpos = (int *)B[PBUF_LPOS].p;
+    a.lx = (double *)B[PBUF_LXYZR].p; a.ly = a.lx + L; a.lz = a.ly + L; a.lr = a.lz + L; a.lcls = (unsigned char *)B[PBUF_LCLS].p;
     a.xyz = (double *)c->h_xyz.p; a.radii = (double *)c->h_radii.p; a.cls = (unsigned char *)c->h_counts.p;
-    HIP_TRY(c, hipMemcpyAsync(B[4].p, c->parse_off.data(), 8 * ((size_t)F + 1), hipMemcpyHostToDevice, st)); /* (parse_off lives in the context: the copy may run later) */
+    HIP_TRY(c, hipMemcpyAsync(B[PBUF_FILE_OFF].p, c->parse_off.data(), 8 * ((size_t)F + 1), hipMemcpyHostToDevice, st)); /* (parse_off lives in the context: the copy may run later) */
     hipLaunchKernelGGL(kp_scatter, dim3((unsigned)((L + PB - 1) / PB)), dim3(PB), 0, st, a);
     HIP_TRY(c, hipGetLastError());
     return 0;
 }
 
-/* ---- residues (gpu_parse.h).  Buffers: c->parse[12] atom keys, [13] block counts of residue starts, [14] first residue per
-   file, [15] backbone flags, [16] res_first, [17] reference rows, [18] labels (names | chains | numbers). */
+/* ---- residues (gpu_parse.h; the buffers: PBUF_AKEY .. PBUF_RES_LABELS) */
 static void res_args(freesasa_gpu_ctx *c, ResArgs &ra)
 {
     memset(&ra, 0, sizeof ra);
@@ -882,13 +887,13 @@ static void res_args(freesasa_gpu_ctx *c, ResArgs &ra)
     ParseArgs &a = ra.p;
     const int F = c->parse_files;
     a.T = c->parse_T; a.F = F; a.options = c->parse_options; a.L = c->parse_lines;
-    a.text = (const unsigned char *)B[0].p; a.files = (const ParseFile *)B[1].p;
-    a.fatoms = (int *)B[3].p; a.fstatus = a.fatoms + F; a.fhost = a.fstatus + F; a.foff = (long long *)B[4].p;
-    a.lstart = (unsigned *)B[5].p; a.lpos = (int *)B[8].p;
+    a.text = (const unsigned char *)B[PBUF_TEXT].p; a.files = (const ParseFile *)B[PBUF_FILES].p;
+    a.fatoms = (int *)B[PBUF_FILE_WORDS].p; a.fstatus = a.fatoms + F; a.fhost = a.fstatus + F; a.foff = (long long *)B[PBUF_FILE_OFF].p;
+    a.lstart = (unsigned *)B[PBUF_LSTART].p; a.lpos = (int *)B[PBUF_LPOS].p;
     ra.A = c->parse_atoms;
     a.n_blocks = (int)((ra.A + PB - 1) / PB);
-    a.blk_cnt = (unsigned *)B[13].p;
-    ra.akey = (uint4 *)B[12].p; ra.bb = (unsigned char *)B[15].p;
+    a.blk_cnt = (unsigned *)B[PBUF_RES_BLK_CNT].p;
+    ra.akey = (uint4 *)B[PBUF_AKEY].p; ra.bb = (unsigned char *)B[PBUF_BACKBONE].p;
     for (int i = 0; i < BACKBONE_N; ++i) { const char *b = backbone_names[i]; ra.bbkey[i] = tok3_key((const unsigned char *)b, (int)strlen(b)); }
     for (int i = 0; i < RESIDUE_REF_N; ++i) { const char *r = residue_ref_table[i].res; ra.refkey[i] = tok3_key((const unsigned char *)r, (int)strlen(r)); }
 }
@@ -900,10 +905,10 @@ int parse_batch_dev_residues_count(freesasa_gpu_ctx *c, long long extra_atoms)
     const long long A = c->parse_atoms, cap = A + (extra_atoms > 0 ? extra_atoms : 0);
     if (cap <= 0) return 0;
     DevBuf *B = c->parse;
-    if (ensure(c, B[15], (size_t)cap)) return -1;
+    if (ensure(c, B[PBUF_BACKBONE], (size_t)cap)) return -1;
     if (A == 0) return 0;
     const int rblocks = (int)((A + PB - 1) / PB);
-    if (ensure(c, B[12], 16 * (size_t)A) || ensure(c, B[13], 4 * ((size_t)rblocks + 2))) return -1;
+    if (ensure(c, B[PBUF_AKEY], 16 * (size_t)A) || ensure(c, B[PBUF_RES_BLK_CNT], 4 * ((size_t)rblocks + 2))) return -1;
     ResArgs ra;
     res_args(c, ra);
     hipStream_t st = c->stream;
@@ -925,17 +930,17 @@ int parse_batch_dev_residues_build(freesasa_gpu_ctx *c, int n_res, long long ext
     const size_t cap = (size_t)n_res + (size_t)(extra_res > 0 ? extra_res : 0);
     DevBuf *B = c->parse;
     if (cap == 0) return 0;
-    if (ensure(c, B[16], 8 * (cap + 1)) || ensure(c, B[17], 2 * cap)) return -1;
+    if (ensure(c, B[PBUF_RES_FIRST], 8 * (cap + 1)) || ensure(c, B[PBUF_RES_REF], 2 * cap)) return -1;
     if (n_res <= 0) return 0;
     const int F = c->parse_files;
-    if (ensure(c, B[18], 14 * (size_t)n_res) || ensure(c, B[14], 4 * (size_t)F)) return -1;
+    if (ensure(c, B[PBUF_RES_LABELS], 14 * (size_t)n_res) || ensure(c, B[PBUF_FILE_RES0], 4 * (size_t)F)) return -1;
     ResArgs ra;
     res_args(c, ra);
     ra.R = n_res; ra.custom = custom;
-    ra.res_first = (long long *)B[16].p; ra.res_ref = (short *)B[17].p;
-    ra.res_name = (unsigned *)B[18].p; ra.res_chain = ra.res_name + n_res; ra.res_number = (unsigned short *)(ra.res_chain + n_res);
-    ra.frfirst = (int *)B[14].p;
-    HIP_TRY(c, hipMemsetAsync(B[14].p, 0xff, 4 * (size_t)F, c->stream));
+    ra.res_first = (long long *)B[PBUF_RES_FIRST].p; ra.res_ref = (short *)B[PBUF_RES_REF].p;
+    ra.res_name = (unsigned *)B[PBUF_RES_LABELS].p; ra.res_chain = ra.res_name + n_res; ra.res_number = (unsigned short *)(ra.res_chain + n_res);
+    ra.frfirst = (int *)B[PBUF_FILE_RES0].p;
+    HIP_TRY(c, hipMemsetAsync(B[PBUF_FILE_RES0].p, 0xff, 4 * (size_t)F, c->stream));
     hipLaunchKernelGGL(kp_res_build, dim3((unsigned)ra.p.n_blocks), dim3(PB), 0, c->stream, ra);
     HIP_TRY(c, hipGetLastError());
     return 0;

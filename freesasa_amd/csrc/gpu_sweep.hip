@@ -1,0 +1,722 @@
+/*
+ * gpu_sweep.hip — the structure sweep over PDB / mmCIF files (BASELINE configs[3], include/freesasa_gpu.h) over ONE
+ * device or a LIST of devices, and the device-side parser's own entries.  Host code; gpu_drivers.hip says how the
+ * drivers divide work among devices and what they share (engine_internal.h).
+ *
+ * A worker per entry of the device list takes batches of whole files from a shared counter, largest first.  Who parses is
+ * an option (FREESASA_INGEST_PARSE_ON_DEVICE) and only decides how a batch BEGINS: its text staged and parsed on the device
+ * (gpu_parse.hip), the files the device refuses read by the host parser - or every file read by the host parser.  From
+ * there on a batch is "the atoms the device parsed, and behind them what the host parser read": ONE tail computes,
+ * aggregates, copies back and records it, and sees the second case as the first with nothing parsed on the device.
+ */
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <fcntl.h>
+#include <memory>
+#include <stdlib.h>
+#include <string.h>
+#include <sys/stat.h>
+#include <time.h>
+
+#include "engine_internal.h"
+#include "hostfault.h"
+
+namespace {
+
+struct Batch { /* a loader batch (freesasa_ingest.h) */
+    freesasa_ingest_batch b;
+    Batch() { memset(&b, 0, sizeof b); }
+    Batch(const Batch &) = delete;
+    Batch &operator=(const Batch &) = delete;
+    ~Batch() { freesasa_ingest_free(&b); }
+    void clear() { freesasa_ingest_free(&b); } /* (leaves it zeroed) */
+    void take(Batch &o) { clear(); b = o.b; memset(&o.b, 0, sizeof o.b); }
+};
+
+/* ---- the device-side parser's input (gpu_parse.hip): a batch's files read - not parsed - into page-locked memory */
+/* The text lives in one of the worker's CONTEXT's two page-locked staging buffers (stage_in / stage_out: they stay with the
+   pooled context from call to call).  Until round 6's last session every sweep allocated and freed its own: hipHostMalloc
+   and hipHostFree of 50 MB take 5 - 7 ms each and hold the runtime's lock while they do - in the kernel trace of a 70 ms
+   sweep (tools/dev/sweep_trace.sh) the first 24 ms saw five batches where the steady state does twenty-two, and the last
+   batch's tile kernel waited 11 ms for the OTHER worker to free its buffers. */
+struct Staged {
+    unsigned char *text = nullptr; /* page-locked: the files one after the other, each in a slot of its size + 1 and ending with '\n' */
+    size_t T = 0;
+    void **slot = nullptr;         /* the context's buffer and its capacity */
+    size_t *slot_cap = nullptr;
+    std::vector<ParseFile> files;  /* [n + 1] */
+    int rc = 0;                    /* -1: no page-locked memory */
+    Staged(void **slot_, size_t *cap_) : slot(slot_), slot_cap(cap_) {}
+    Staged(const Staged &) = delete;
+    Staged &operator=(const Staged &) = delete;
+    void swap(Staged &o) { std::swap(text, o.text); std::swap(T, o.T); std::swap(slot, o.slot); std::swap(slot_cap, o.slot_cap); files.swap(o.files); std::swap(rc, o.rc); }
+};
+/* n files -> out, with `threads` readers (each file: one pread loop, then the one-line-at-a-time look at an mmCIF file's text
+   before its _atom_site loop: freesasa_ingest_cif_locate); a file that cannot be read is left to the host parser, which
+   reports it */
+void stage_files(const char *const *paths, int n, int options, int threads, Staged *out)
+{
+    out->rc = 0;
+    out->files.assign((size_t)n + 1, ParseFile());
+    std::vector<long long> size((size_t)n, 0);
+    size_t T = 0;
+    for (int f = 0; f < n; ++f) {
+        struct stat st;
+        size[f] = (paths[f] && stat(paths[f], &st) == 0 && st.st_size > 0) ? (long long)st.st_size : 0;
+        out->files[f].beg = (unsigned)T;
+        T += (size_t)size[f] + 1;
+    }
+    if (T >= (1ULL << 31)) { out->rc = -2; return; }
+    out->files[n].beg = (unsigned)T;
+    out->T = T;
+    if (T + 64 > *out->slot_cap) {
+        if (*out->slot) (void)hipHostFree(*out->slot);
+        *out->slot = nullptr; *out->slot_cap = 0;
+        const size_t want = T + T / 8 + 4096;
+        if (host_malloc(out->slot, want) != hipSuccess) { out->rc = -1; out->text = nullptr; return; }
+        *out->slot_cap = want;
+    }
+    out->text = (unsigned char *)*out->slot;
+    std::atomic<int> next(0);
+    auto reader = [&]() noexcept {
+        for (;;) {
+            const int f = next.fetch_add(1);
+            if (f >= n) break;
+            ParseFile &pf = out->files[f];
+            unsigned char *dst = out->text + pf.beg;
+            const size_t slot = (size_t)size[f] + 1;
+            size_t got = 0;
+            bool ok = false;
+            if (paths[f]) {
+                const int fd = open(paths[f], O_RDONLY);
+                if (fd >= 0) {
+                    ok = true;
+                    while (got < (size_t)size[f]) {
+                        const ssize_t r = pread(fd, dst + got, (size_t)size[f] - got, (off_t)got);
+                        if (r < 0) { ok = false; break; }
+                        if (r == 0) break;
+                        got += (size_t)r;
+                    }
+                    close(fd);
+                }
+            }
+            pf.no_final_nl = (got > 0 && dst[got - 1] != '\n') ? 1 : 0;
+            memset(dst + got, '\n', slot - got); /* (the slot's spare byte, and whatever a file that shrank left) */
+            pf.kind = PARSE_HOST; pf.ncol = 0; pf.row0 = 0;
+            if (!ok || (long long)got != size[f] || (options & FREESASA_INGEST_RADIUS_FROM_OCCUPANCY)) continue;
+            int ncol = 0;
+            size_t row0 = 0;
+            const int kind = freesasa_ingest_cif_locate((const char *)dst, got, &ncol, pf.slot, &row0);
+            if (kind == 0) pf.kind = PARSE_PDB;
+            else if (kind == 1) { pf.kind = PARSE_CIF; pf.ncol = (short)ncol; pf.row0 = pf.beg + (unsigned)row0; }
+        }
+    };
+    ThreadGroup tg;
+    for (int t = 1; t < threads && t < n; ++t)
+        if (!tg.spawn(reader)) break; /* (fewer readers then) */
+    reader();
+}
+std::atomic<long long> g_parse_dev_files(0), g_parse_host_files(0);
+
+/* ------------------------------------------------------------------ structure sweep: files */
+
+struct SweepRec { double total, cls[3]; long long atoms; int status, pad; };
+static_assert(sizeof(SweepRec) == 48, "result record");
+
+/* The per-residue table of freesasa_gpu_sweep_files_residues.  Workers finish batches in any order and a file's place in
+   the table depends on the residues of every file before it: each batch leaves a block of its own, and the table is
+   assembled from them once all are done.  A batch's residues are in ITS order: the files the device parsed one after the
+   other, behind them those of the files the host parser read (fstart says where a file's run begins). */
+struct ResBatch {
+    int first = 0, ns = 0;                  /* files [first, first + ns) */
+    long long n_res = 0;
+    std::vector<long long> fstart, fcount;  /* [ns] */
+    std::vector<int64_t> res_first;         /* [n_res + 1] atoms, batch-wide */
+    std::vector<double> areas;              /* abs [6 n_res] | rel [5 n_res] */
+    std::vector<int16_t> ref;               /* [n_res] */
+    std::vector<char> name, number, chain;  /* [4 | 6 | 4 per residue] */
+    void size(long long R)
+    {
+        n_res = R;
+        res_first.assign((size_t)R + 1, 0); areas.resize(11 * (size_t)R); ref.resize((size_t)R);
+        name.resize(4 * (size_t)R); number.resize(6 * (size_t)R); chain.resize(4 * (size_t)R);
+    }
+};
+struct ResCollector {
+    std::mutex mu;
+    std::vector<std::unique_ptr<ResBatch>> done;
+    void add(std::unique_ptr<ResBatch> &rb) { std::lock_guard<std::mutex> lk(mu); done.push_back(std::move(rb)); }
+};
+
+/* what a sweep entry was called with (read-only) */
+struct SweepArgs {
+    const char *const *paths; int n_paths, ingest_options, n_threads;
+    int alg; double probe; int resolution; long long batch_atoms;
+    double *totals_out, *class_sums_out; long long *atoms_out; int *status_out;
+    const char *done_path; long long max_new_batches; /* (may be NULL / 0) */
+    const int *devices; int n_devices;
+    const freesasa_ingest_classifier *classifier;     /* (may be NULL) */
+    ResCollector *rcol;                               /* (may be NULL) */
+};
+/* what the workers of one sweep share */
+struct Sweep {
+    const SweepArgs &a;
+    bool dev_parse = false, want_cls = false;
+    int options = 0;               /* the loader's (without FREESASA_INGEST_PARSE_ON_DEVICE) */
+    int loader_threads = 1;
+    std::vector<int> cut, todo;    /* batch b: files [cut[b], cut[b + 1]); the batches to compute, largest first */
+    std::vector<double> tp;        /* S&R test points */
+    std::atomic<size_t> next{0};
+    FirstError fe;
+    DoneList list;
+    Fd res;                        /* <done_path>.bin */
+    /* dev aid (FREESASA_AMD_SWEEP_PROFILE): where a worker's wall clock goes - staging of its first batch, parse (upload, line
+       and atom counts back), the files left to the host parser, the tile kernels up to the totals, the done-list, waiting for
+       the loader of the next batch */
+    bool sprof = false;
+    std::atomic<long long> tp_first{0}, tp_parse{0}, tp_host{0}, tp_run{0}, tp_rec{0}, tp_join{0}, tp_stage{0};
+    explicit Sweep(const SweepArgs &a_) : a(a_) {}
+};
+long long now_ns() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (long long)ts.tv_sec * 1000000000LL + ts.tv_nsec; }
+
+/* what a worker's loader thread prepares of the NEXT batch while this one is on the GPU: with the parser on the device the
+   files' text in page-locked memory, else the batch as the host parser read it (nothing is ever copied to the device from
+   `b` itself: the worker takes it over first) */
+struct Ahead {
+    Staged s;
+    Batch b;
+    int rc = 0; /* the loader's code */
+    Ahead(void **slot, size_t *cap) : s(slot, cap) {}
+    void swap(Ahead &o) { s.swap(o.s); std::swap(b.b, o.b.b); std::swap(rc, o.rc); }
+};
+void look_ahead(Sweep &S, int b, Ahead *out) noexcept
+{
+    const long long t0 = S.sprof ? now_ns() : 0;
+    const char *const *paths = S.a.paths + S.cut[b];
+    const int n = S.cut[b + 1] - S.cut[b];
+    if (S.dev_parse) {
+        try { stage_files(paths, n, S.options, S.loader_threads, &out->s); } catch (...) { out->s.rc = -3; }
+    } else {
+        out->rc = freesasa_ingest_pdb_files_ex(paths, n, S.options, S.loader_threads, S.a.classifier, &out->b.b); /* (C code: nothing to catch) */
+    }
+    if (S.sprof) S.tp_stage += now_ns() - t0;
+}
+
+/* one batch in its worker's hands */
+struct Work {
+    int b, first, ns;                     /* batch, its files [first, first + ns) */
+    int nd = 0;                           /* structures the device parser made: one per file (a refused file an empty one) or none */
+    long long total = 0;                  /* ... and their atoms */
+    std::vector<int> atoms, status, host; /* [ns] the device parser's: atoms kept, loader status, 1 = left to the host parser */
+    std::vector<int> fb;                  /* the files the host parser read, in its batch's order: structure nd + j is file fb[j] */
+    std::vector<long long> atoms64;       /* [ns] results for the done-list's records */
+    std::vector<double> cls;              /* [3 ns], empty: none computed */
+    std::unique_ptr<ResBatch> rb;
+    long long R = 0, Rd = 0;              /* residues of the batch, and how many of them are the device's */
+    Work(const Sweep &S, int b_) : b(b_), first(S.cut[b_]), ns(S.cut[b_ + 1] - S.cut[b_]), atoms((size_t)ns), status((size_t)ns), host((size_t)ns), atoms64((size_t)ns, 0)
+    {
+        if (!S.a.rcol) return;
+        rb.reset(new ResBatch);
+        rb->first = first; rb->ns = ns; rb->fstart.assign((size_t)ns, 0); rb->fcount.assign((size_t)ns, 0); rb->size(0);
+    }
+};
+
+/* How a batch begins with the parser ON THE DEVICE (gpu_parse.hip): the text the loader staged is uploaded and parsed; the
+   files the device refuses are read by the host parser now (hb) and go behind the device's atoms as further structures. */
+int front_device(Sweep &S, freesasa_gpu_ctx *c, Ahead &cur, Work &w, Batch &hb)
+{
+    if (cur.s.rc)
+        return ctx_fail(c, "%s", cur.s.rc == -1 ? "out of page-locked host memory (file staging)" : (cur.s.rc == -2 ? "a batch of files larger than 2 GB: use a smaller batch_atoms" : "out of host memory (file staging)"));
+    long long tq = S.sprof ? now_ns() : 0;
+    if (parse_batch_dev_begin(c, cur.s.text, cur.s.T, cur.s.files.data(), w.ns, S.options, S.a.classifier, w.atoms.data(), w.status.data(), w.host.data(), &w.total)) return -1;
+    w.nd = w.ns;
+    if (S.sprof) { const long long t1 = now_ns(); S.tp_parse += t1 - tq; tq = t1; }
+    for (int k = 0; k < w.ns; ++k) if (w.host[(size_t)k]) w.fb.push_back(k);
+    g_parse_dev_files += w.ns - (long long)w.fb.size(); g_parse_host_files += (long long)w.fb.size();
+    hb.clear();
+    if (!w.fb.empty()) {
+        std::vector<const char *> fp;
+        for (int k : w.fb) fp.push_back(S.a.paths[w.first + k]);
+        const int lrc = freesasa_ingest_pdb_files_ex(fp.data(), (int)fp.size(), S.options, S.loader_threads, S.a.classifier, &hb.b);
+        if (lrc) return ctx_fail(c, "loader failed with code %d", lrc);
+    }
+    if (S.sprof) S.tp_host += now_ns() - tq;
+    return 0;
+}
+/* ... and with the host parser: the loader read every file; the device parsed nothing */
+int front_host(freesasa_gpu_ctx *c, Ahead &cur, Work &w, Batch &hb)
+{
+    if (cur.rc) return ctx_fail(c, "loader failed with code %d", cur.rc);
+    parse_batch_dev_none(c);
+    hb.take(cur.b);
+    w.host.assign((size_t)w.ns, 1);
+    for (int k = 0; k < w.ns; ++k) w.fb.push_back(k);
+    return 0;
+}
+
+/* residues, behind run_batch: the device's count came back under its wait; the host parser's go behind them.  Enqueues the
+   areas (PBUF_RES_AREAS) and their way back into page-locked c->res_stage: areas | the device's res_first, reference rows,
+   labels, first residue per file.  Sets w.R, w.Rd. */
+int residues_enqueue(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, std::vector<int64_t> &hrf)
+{
+    const long long Rd = parse_batch_dev_residues_found(c), Rh = hb.b.n_residues, R = Rd + Rh;
+    if (R <= 0) return 0;
+    if (Rd < 0 || R >= (1LL << 31)) return ctx_fail(c, "bad residue count from the device parser");
+    DevBuf *B = c->parse;
+    if (parse_batch_dev_residues_build(c, (int)Rd, Rh, S.a.classifier != nullptr) || ensure(c, B[PBUF_RES_AREAS], 88 * (size_t)R) ||
+        ensure_pinned(c, &c->res_stage, &c->res_stage_cap, 88 * (size_t)R + 24 * (size_t)Rd + 8 + 4 * (size_t)w.ns))
+        return -1;
+    if (Rh > 0) {
+        hrf.resize((size_t)Rh + 1);
+        for (long long j = 0; j <= Rh; ++j) hrf[(size_t)j] = w.total + hb.b.res_first[j];
+        if (hipMemcpyAsync((int64_t *)B[PBUF_RES_FIRST].p + Rd, hrf.data(), 8 * ((size_t)Rh + 1), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            hipMemcpyAsync((int16_t *)B[PBUF_RES_REF].p + Rd, hb.b.res_ref, 2 * (size_t)Rh, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+            return ctx_fail(c, "host-to-device copy failed");
+    }
+    double *d_abs = (double *)B[PBUF_RES_AREAS].p;
+    if (residue_areas_resident(c, (double *)c->h_sasa.p, (const unsigned char *)c->h_counts.p, (const unsigned char *)B[PBUF_BACKBONE].p,
+                               (const int64_t *)B[PBUF_RES_FIRST].p, (const short *)B[PBUF_RES_REF].p, (int)R, d_abs, d_abs + 6 * R))
+        return -1;
+    unsigned char *r_stage = (unsigned char *)c->res_stage, *q = r_stage + 88 * (size_t)R;
+    bool ok = hipMemcpyAsync(r_stage, d_abs, 88 * (size_t)R, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+    if (Rd > 0)
+        ok = ok && hipMemcpyAsync(q, B[PBUF_RES_FIRST].p, 8 * ((size_t)Rd + 1), hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+             hipMemcpyAsync(q + 8 * ((size_t)Rd + 1), B[PBUF_RES_REF].p, 2 * (size_t)Rd, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+             hipMemcpyAsync(q + 8 + 10 * (size_t)Rd, B[PBUF_RES_LABELS].p, 14 * (size_t)Rd, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+             hipMemcpyAsync(q + 8 + 24 * (size_t)Rd, B[PBUF_FILE_RES0].p, 4 * (size_t)w.ns, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+    if (!ok) return ctx_fail(c, "device-to-host copy failed");
+    w.rb->size(R);
+    w.R = R; w.Rd = Rd;
+    return 0;
+}
+/* ... and, the stream waited for, from the page-locked block and the host parser's batch into the batch's ResBatch */
+int residues_collect(freesasa_gpu_ctx *c, Work &w, const Batch &hb)
+{
+    ResBatch *rb = w.rb.get();
+    const long long R = w.R, Rd = w.Rd, Rh = R - Rd;
+    const unsigned char *r_stage = (const unsigned char *)c->res_stage, *q = r_stage + 88 * (size_t)R;
+    memcpy(rb->areas.data(), r_stage, 88 * (size_t)R);
+    if (Rd > 0) {
+        memcpy(rb->res_first.data(), q, 8 * ((size_t)Rd + 1));
+        memcpy(rb->ref.data(), q + 8 * ((size_t)Rd + 1), 2 * (size_t)Rd);
+        const unsigned char *lab = q + 8 + 10 * (size_t)Rd;
+        memcpy(rb->name.data(), lab, 4 * (size_t)Rd);
+        memcpy(rb->chain.data(), lab + 4 * (size_t)Rd, 4 * (size_t)Rd);
+        memcpy(rb->number.data(), lab + 8 * (size_t)Rd, 6 * (size_t)Rd);
+        /* a file's run ends where the next file that kept atoms begins */
+        const int *frf = (const int *)(q + 8 + 24 * (size_t)Rd);
+        long long end = Rd;
+        bool sane = true;
+        for (int k = w.ns - 1; k >= 0; --k) {
+            if (w.host[(size_t)k] || w.atoms[(size_t)k] == 0) continue;
+            if (frf[k] < 0 || frf[k] >= end) { sane = false; break; }
+            rb->fstart[(size_t)k] = frf[k]; rb->fcount[(size_t)k] = end - frf[k];
+            end = frf[k];
+        }
+        if (!sane || end != 0) return ctx_fail(c, "the device parser's residue table does not match its atoms");
+    }
+    for (long long j = 0; j < Rh; ++j) rb->res_first[(size_t)(Rd + j)] = w.total + hb.b.res_first[j];
+    rb->res_first[(size_t)R] = w.total + hb.b.n_atoms;
+    if (Rh > 0) {
+        memcpy(rb->ref.data() + Rd, hb.b.res_ref, 2 * (size_t)Rh);
+        memcpy(rb->name.data() + 4 * Rd, hb.b.res_name, 4 * (size_t)Rh);
+        memcpy(rb->number.data() + 6 * Rd, hb.b.res_number, 6 * (size_t)Rh);
+        memcpy(rb->chain.data() + 4 * Rd, hb.b.res_chain, 4 * (size_t)Rh);
+    }
+    for (size_t j = 0; j < w.fb.size(); ++j) {
+        rb->fstart[(size_t)w.fb[j]] = Rd + hb.b.res_offsets[j];
+        rb->fcount[(size_t)w.fb[j]] = hb.b.res_offsets[j + 1] - hb.b.res_offsets[j];
+    }
+    return 0;
+}
+
+/* The rest of a batch, whoever parsed: w.nd structures of w.total atoms are on the device (c->h_xyz, h_radii, h_counts;
+   backbone flags and residue keys in c->parse[]), hb holds the files w.fb as the host parser read them and goes up behind
+   them.  Results into the caller's arrays, w.atoms64 / w.cls and w.rb; on success the stream has been waited for. */
+int tail(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, std::vector<int64_t> &hrf)
+{
+    const SweepArgs &a = S.a;
+    const int ns = w.ns, first = w.first, nd = w.nd, nst = nd + (int)w.fb.size();
+    const long long total = w.total, extra = hb.b.n_atoms, n_all = total + extra;
+    if (parse_batch_dev_finish(c, extra)) return -1;
+    if (a.rcol && parse_batch_dev_residues_count(c, extra)) return -1;
+    std::vector<int64_t> off((size_t)nst + 1);
+    off[0] = 0;
+    for (int k = 0; k < nd; ++k) off[(size_t)k + 1] = off[(size_t)k] + w.atoms[(size_t)k];
+    for (size_t j = 0; j < w.fb.size(); ++j) off[(size_t)nd + j + 1] = total + hb.b.offsets[j + 1];
+    for (int k = 0; k < ns; ++k) {
+        a.status_out[first + k] = w.status[(size_t)k];
+        a.totals_out[first + k] = 0;
+        w.atoms64[(size_t)k] = w.atoms[(size_t)k];
+        if (a.class_sums_out) a.class_sums_out[3 * (first + k)] = a.class_sums_out[3 * (first + k) + 1] = a.class_sums_out[3 * (first + k) + 2] = 0;
+    }
+    for (size_t j = 0; j < w.fb.size(); ++j) { a.status_out[first + w.fb[j]] = hb.b.status[j]; w.atoms64[(size_t)w.fb[j]] = hb.b.offsets[j + 1] - hb.b.offsets[j]; }
+    if (a.atoms_out) for (int k = 0; k < ns; ++k) a.atoms_out[first + k] = w.atoms64[(size_t)k];
+    if (n_all == 0) return 0;
+    if (extra > 0 &&
+        (hipMemcpyAsync((double *)c->h_xyz.p + 3 * total, hb.b.xyz, 24 * (size_t)extra, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+         hipMemcpyAsync((double *)c->h_radii.p + total, hb.b.radii, 8 * (size_t)extra, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+         hipMemcpyAsync((unsigned char *)c->h_counts.p + total, hb.b.atom_class, (size_t)extra, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+         (a.rcol && hipMemcpyAsync((unsigned char *)c->parse[PBUF_BACKBONE].p + total, hb.b.atom_backbone, (size_t)extra, hipMemcpyHostToDevice, c->stream) != hipSuccess)))
+        return ctx_fail(c, "host-to-device copy failed");
+    if (ensure(c, c->h_sasa, 8 * (size_t)n_all) || ensure(c, c->h_totals, 8 * 4 * (size_t)nst)) return -1;
+    double *d_tot = (double *)c->h_totals.p, *d_cls = d_tot + nst;
+    if (run_batch(c, a.alg == 0, (double *)c->h_xyz.p, (double *)c->h_radii.p, off.data(), nst, a.probe, a.resolution,
+                  a.alg == 1 ? S.tp.data() : nullptr, (double *)c->h_sasa.p, nullptr, d_tot))
+        return -1;
+    if (a.rcol && residues_enqueue(S, c, w, hb, hrf)) return -1;
+    std::vector<double> tot((size_t)nst), cls;
+    if (S.want_cls) {
+        cls.resize(3 * (size_t)nst);
+        if (freesasa_gpu_class_sums_dev(c, (double *)c->h_sasa.p, (const unsigned char *)c->h_counts.p, off.data(), nst, d_cls)) return -1;
+        if (hipMemcpyAsync(cls.data(), d_cls, 8 * 3 * (size_t)nst, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return ctx_fail(c, "device-to-host copy failed");
+    }
+    if (hipMemcpyAsync(tot.data(), d_tot, 8 * (size_t)nst, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return ctx_fail(c, "device-to-host copy failed");
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return ctx_fail(c, "stream synchronize failed");
+    /* structure k < nd of the batch is file k; structure nd + j is the j-th file the host read */
+    for (int k = 0; k < nd; ++k) a.totals_out[first + k] = tot[(size_t)k];
+    for (size_t j = 0; j < w.fb.size(); ++j) a.totals_out[first + w.fb[j]] = tot[(size_t)nd + j];
+    if (S.want_cls) {
+        w.cls.assign(3 * (size_t)ns, 0);
+        if (nd) memcpy(w.cls.data(), cls.data(), 8 * 3 * (size_t)nd);
+        for (size_t j = 0; j < w.fb.size(); ++j) memcpy(&w.cls[3 * (size_t)w.fb[j]], &cls[3 * ((size_t)nd + j)], 8 * 3);
+        if (a.class_sums_out) memcpy(a.class_sums_out + 3 * (size_t)first, w.cls.data(), 8 * 3 * (size_t)ns);
+    }
+    return w.R > 0 ? residues_collect(c, w, hb) : 0;
+}
+
+/* the results of a finished batch into the result file, then its line in the done-list */
+int record(Sweep &S, freesasa_gpu_ctx *c, const Work &w)
+{
+    std::vector<SweepRec> recs((size_t)w.ns);
+    for (int k = 0; k < w.ns; ++k) {
+        SweepRec &r = recs[(size_t)k];
+        memset(&r, 0, sizeof r);
+        r.total = S.a.totals_out[w.first + k]; r.status = S.a.status_out[w.first + k];
+        r.atoms = w.atoms64[(size_t)k];
+        if (!w.cls.empty()) for (int q = 0; q < 3; ++q) r.cls[q] = w.cls[3 * (size_t)k + q];
+    }
+    /* (the records of a batch lie at their own offset: no lock; the list itself is appended to by one worker at a time) */
+    if (!pwrite_all(S.res.fd, recs.data(), sizeof(SweepRec) * recs.size(), (long long)sizeof(SweepRec) * w.first) || fdatasync(S.res.fd) != 0 ||
+        S.list.append(w.b, w.first, w.ns))
+        return ctx_fail(c, "could not record the finished batch in the done-list");
+    return 0;
+}
+
+/* A worker owns a pooled context of its device and a loader: while batch k is on the GPU the loader thread prepares the
+   batch the worker took next (Ahead).  A batch is a chain on the context's stream: text or arrays over PCIe, parse, cell
+   sort, tile kernels, aggregates, results back. */
+void worker(Sweep &S, int wi) noexcept
+{
+  try {
+    /* declared before the context, so freed after its stream is idle (PoolLease), whatever ends the worker: the host parser's
+       part of the batch in hand and its res_first, shifted - copies to the device read both */
+    Batch hb;
+    std::vector<int64_t> hrf;
+    DeviceNodeScope node(S.a.devices[wi]); /* this worker - its context's page-locked memory, its loader threads - on the device's NUMA node */
+    PoolLease lease(S.a.devices[wi]);
+    freesasa_gpu_ctx *c = lease.c;
+    if (!c) { S.fe.set("could not create a GPU context"); return; }
+    Ahead cur(&c->stage_in, &c->stage_in_cap), nxt(&c->stage_out, &c->stage_out_cap);
+    size_t ti = S.next.fetch_add(1);
+    { const long long t0 = S.sprof ? now_ns() : 0;
+      if (ti < S.todo.size()) look_ahead(S, S.todo[ti], &cur);
+      if (S.sprof) S.tp_first += now_ns() - t0; }
+    while (ti < S.todo.size() && !S.fe.failed.load()) {
+        const size_t tn = S.next.fetch_add(1); /* the batch this worker does next: prepared while this one computes */
+        ThreadGroup loader; /* (joined before nxt can go away, whatever happens below) */
+        if (tn < S.todo.size() && !loader.spawn(look_ahead, std::ref(S), S.todo[tn], &nxt)) { S.fe.set("could not start a loader thread"); break; }
+        Work w(S, S.todo[ti]);
+        int ret = hipSetDevice(c->device) == hipSuccess ? 0 : ctx_fail(c, "hipSetDevice failed");
+        if (!ret) ret = S.dev_parse ? front_device(S, c, cur, w, hb) : front_host(c, cur, w, hb);
+        long long tr = S.sprof ? now_ns() : 0;
+        if (!ret) ret = tail(S, c, w, hb, hrf);
+        if (ret) (void)hipStreamSynchronize(c->stream); /* no copy may still read the batch when it is freed */
+        if (S.sprof) { const long long t1 = now_ns(); S.tp_run += t1 - tr; tr = t1; }
+        if (!ret && S.list.active()) ret = record(S, c, w);
+        if (!ret && S.a.rcol) S.a.rcol->add(w.rb);
+        if (ret) S.fe.set(c->err[0] ? c->err : "GPU sweep failed");
+        if (S.sprof) { const long long t1 = now_ns(); S.tp_rec += t1 - tr; tr = t1; }
+        loader.join();
+        if (S.sprof) S.tp_join += now_ns() - tr;
+        cur.swap(nxt);
+        ti = tn;
+    }
+  } catch (...) { /* (an exception that leaves a thread's function ends the process: it ends the sweep instead) */
+    S.fe.set_exception();
+  }
+}
+
+/* The done-list of this sweep (gpu_drivers.hip says what a done-list is) and its result file <done_path>.bin: per file total
+   | class sums (3) | atoms | status (SweepRec), written before the batch is listed.  -1: another run's list, or files that
+   cannot be opened. */
+int open_done_list(Sweep &S, int n_batches, char *err_out, int err_len)
+{
+    const SweepArgs &a = S.a;
+    unsigned long long h = 1469598103934665603ULL; /* FNV-1a over the files' names, sizes and modification times: the done-list belongs to THESE files as they are now */
+    for (int k = 0; k < a.n_paths; ++k) {
+        for (const char *q = a.paths[k] ? a.paths[k] : ""; ; ++q) { h = (h ^ (unsigned char)*q) * 1099511628211ULL; if (!*q) break; }
+        struct stat st;
+        long long id[3] = {-1, -1, -1};
+        if (a.paths[k] && stat(a.paths[k], &st) == 0) { id[0] = (long long)st.st_size; id[1] = (long long)st.st_mtim.tv_sec; id[2] = (long long)st.st_mtim.tv_nsec; }
+        for (size_t q = 0; q < sizeof id; ++q) h = (h ^ ((const unsigned char *)id)[q]) * 1099511628211ULL;
+    }
+    char head[256];
+    snprintf(head, sizeof head, "freesasa_amd sweep done-list v2 n_files=%d batches=%d files=%016llx options=%d alg=%d resolution=%d probe=%.17g\n",
+             a.n_paths, n_batches, h, S.options, a.alg, a.resolution, a.probe); /* (who parses does not change a result: not part of the run's name) */
+    if (a.classifier) { /* (without one the line is what it always was: earlier done-lists resume) */
+        const size_t hl = strlen(head);
+        snprintf(head + hl - 1, sizeof head - (hl - 1), " classifier=%016llx\n", (unsigned long long)freesasa_ingest_classifier_digest(a.classifier));
+    }
+    const std::vector<int> &cut = S.cut;
+    if (S.list.read(a.done_path, head, n_batches, [&cut](long long b, long long first, long long count) { return first == cut[(size_t)b] && count == cut[(size_t)b + 1] - cut[(size_t)b]; }) == DoneList::REFUSED)
+        return set_err(err_out, err_len, "the done-list belongs to a sweep with other parameters or other (changed) input files");
+    const std::string res_path = std::string(a.done_path) + ".bin";
+    S.res.fd = open(res_path.c_str(), S.list.resumed() ? O_RDWR | O_CREAT : O_RDWR | O_CREAT | O_TRUNC, 0644);
+    if (S.res.fd < 0 || S.list.open()) return set_err(err_out, err_len, "cannot open the done-list or its result file");
+    return 0;
+}
+/* the results of a batch the done-list names, from the result file (false: unreadable - the batch is computed again) */
+bool load_recorded(Sweep &S, int b)
+{
+    const SweepArgs &a = S.a;
+    std::vector<SweepRec> recs((size_t)(S.cut[b + 1] - S.cut[b]));
+    if (!pread_all(S.res.fd, recs.data(), sizeof(SweepRec) * recs.size(), (long long)sizeof(SweepRec) * S.cut[b])) return false;
+    for (size_t k = 0; k < recs.size(); ++k) {
+        const int f = S.cut[b] + (int)k;
+        a.totals_out[f] = recs[k].total; a.status_out[f] = recs[k].status;
+        if (a.atoms_out) a.atoms_out[f] = recs[k].atoms;
+        if (a.class_sums_out) for (int q = 0; q < 3; ++q) a.class_sums_out[3 * f + q] = recs[k].cls[q];
+    }
+    return true;
+}
+
+/* Files -> per-structure totals.  Inputs that fail to load get total 0 and their loader status; the call only fails for GPU
+ * errors.  With a done-list (a.done_path) a call that finds the list of the same run takes the listed batches' results from
+ * the result file and only computes the others.
+ * Returns 0 done, 1 stopped after max_new_batches, -1 error. */
+int sweep_impl(SweepArgs a, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (!a.paths || a.n_paths < 0 || !a.totals_out || !a.status_out) return set_err(err_out, err_len, "null argument");
+    if (a.alg != 0 && a.alg != 1) return set_err(err_out, err_len, "unknown algorithm");
+    if (check_devices(a.devices, a.n_devices, err_out, err_len)) return -1;
+    if (a.n_paths == 0) return 0;
+    /* (round 6, MI355X box, 1.2e7 protein atoms in 7172 files, 16 CPUs, two workers on the device, parser on the device,
+       batches of 5e5 / 1e6 / 1.5e6 / 2e6 atoms: 2.2 / 2.5 / 2.4 / 2.3e8 atoms/s once the workers' page-locked staging stays
+       with their contexts - tools/dev/sweep_profile.py; with a staging buffer allocated and freed per call, as until the
+       round's last session: 1.7 / 1.5 / - / 1.1e8; host parser 1.25 / 1.34 / - / 1.31e8) */
+    if (a.batch_atoms <= 0) a.batch_atoms = 1000000;
+    /* ONE device in the list: two workers on it, so that the upload of one batch runs under the kernels of the other */
+    const int two[2] = {a.devices[0], a.devices[0]};
+    if (a.n_devices == 1 && !getenv("FREESASA_AMD_SWEEP_ONE_WORKER")) { a.devices = two; a.n_devices = 2; }
+    return guarded(err_out, err_len, [&]() -> int {
+    Sweep S(a);
+    S.dev_parse = (a.ingest_options & FREESASA_INGEST_PARSE_ON_DEVICE) != 0;
+    S.options = a.ingest_options & ~FREESASA_INGEST_PARSE_ON_DEVICE;
+    S.want_cls = a.class_sums_out != nullptr || a.done_path != nullptr;
+    S.sprof = getenv("FREESASA_AMD_SWEEP_PROFILE") != nullptr;
+    /* batches of roughly batch_atoms atoms, estimated from the file sizes (~81 bytes per ATOM line) */
+    S.cut.assign(1, 0);
+    std::vector<long long> batch_bytes;
+    long long bytes = 0;
+    for (int k = 0; k < a.n_paths; ++k) {
+        struct stat st;
+        bytes += (a.paths[k] && stat(a.paths[k], &st) == 0) ? (long long)st.st_size : 0;
+        if (bytes >= a.batch_atoms * 81 && k + 1 < a.n_paths) { S.cut.push_back(k + 1); batch_bytes.push_back(bytes); bytes = 0; }
+    }
+    S.cut.push_back(a.n_paths);
+    batch_bytes.push_back(bytes);
+    const int n_batches = (int)S.cut.size() - 1;
+    if (a.done_path && open_done_list(S, n_batches, err_out, err_len)) return -1;
+    for (int b = 0; b < n_batches; ++b)
+        if (!S.list.done(b) || !load_recorded(S, b)) S.todo.push_back(b);
+    bool stopped = false;
+    if (a.max_new_batches > 0 && (long long)S.todo.size() > a.max_new_batches) { S.todo.resize((size_t)a.max_new_batches); stopped = true; }
+    if (S.todo.empty()) return stopped ? 1 : 0;
+    /* largest first (LPT): whoever is free takes the largest batch left */
+    std::stable_sort(S.todo.begin(), S.todo.end(), [&](int x, int y) { return batch_bytes[(size_t)x] > batch_bytes[(size_t)y]; });
+    const int n_workers = a.n_devices < (int)S.todo.size() ? a.n_devices : (int)S.todo.size();
+    S.loader_threads = threads_per_worker(a.n_threads, n_workers);
+    if (a.alg == 1) { S.tp.resize(3 * (size_t)(a.resolution > 0 ? a.resolution : 1)); if (a.resolution > 0) freesasa_gpu_test_points(a.resolution, S.tp.data()); }
+    {
+        ThreadGroup tg;
+        for (int w = 1; w < n_workers; ++w)
+            if (!tg.spawn(worker, std::ref(S), w)) { S.fe.set("could not start a worker thread"); break; }
+        if (!S.fe.failed.load()) worker(S, 0);
+    }
+    if (S.sprof && S.dev_parse)
+        fprintf(stderr, "sweep profile (%d workers, %zu batches, %d loader threads each; ms summed over the workers): first batch staged %.1f | parse %.1f | host parser %.1f | "
+                        "kernels to totals %.1f | done-list %.1f | waiting for the loader %.1f || staging itself (loader threads) %.1f\n",
+                n_workers, S.todo.size(), S.loader_threads, S.tp_first / 1e6, S.tp_parse / 1e6, S.tp_host / 1e6, S.tp_run / 1e6, S.tp_rec / 1e6, S.tp_join / 1e6, S.tp_stage / 1e6);
+    if (S.fe.failed.load()) return set_err(err_out, err_len, S.fe.text);
+    return stopped ? 1 : 0;
+    });
+}
+
+} /* namespace */
+
+/* ------------------------------------------------------------------ entry points */
+
+/* The device-side parser on its own (tests, tools): n files -> coordinates, radii and classes of the atoms it keeps (host
+   arrays of `cap` atoms), offsets_out [n + 1], status_out [n] (the loader's codes), host_out [n] (1: the device refuses the
+   file - the sweep would hand it to the host parser - and it contributes nothing here).  Returns the atoms written, -1 on
+   error, -2 if cap is too small (offsets_out[n] says how many are needed). */
+extern "C" long long freesasa_gpu_parse_files_classified(const char *const *paths, int n_paths, int ingest_options, int n_threads, int device,
+                                                         double *xyz_out, double *radii_out, unsigned char *class_out, long long cap,
+                                                         long long *offsets_out, int *status_out, int *host_out,
+                                                         const freesasa_ingest_classifier *classifier, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (!paths || n_paths <= 0 || !offsets_out || !status_out || !host_out) return set_err(err_out, err_len, "bad argument");
+    if (check_devices(&device, 1, err_out, err_len)) return -1;
+    long long written = -1;
+    const int rc = guarded(err_out, err_len, [&]() -> int {
+        PoolLease lease(device);
+        freesasa_gpu_ctx *c = lease.c;
+        if (!c) return set_err(err_out, err_len, "could not create a GPU context");
+        Staged s(&c->stage_in, &c->stage_in_cap);
+        if (hipSetDevice(c->device) != hipSuccess) return set_err(err_out, err_len, "hipSetDevice failed");
+        stage_files(paths, n_paths, ingest_options & ~FREESASA_INGEST_PARSE_ON_DEVICE, threads_per_worker(n_threads, 1), &s);
+        if (s.rc) return set_err(err_out, err_len, "could not stage the files");
+        std::vector<int> atoms((size_t)n_paths);
+        long long total = 0;
+        if (parse_batch_dev_begin(c, s.text, s.T, s.files.data(), n_paths, ingest_options & ~FREESASA_INGEST_PARSE_ON_DEVICE, classifier, atoms.data(), status_out, host_out, &total) ||
+            parse_batch_dev_finish(c, 0))
+            return set_err(err_out, err_len, c->err);
+        offsets_out[0] = 0;
+        for (int k = 0; k < n_paths; ++k) offsets_out[k + 1] = offsets_out[k] + atoms[(size_t)k];
+        if (total > cap) { written = -2; return 0; }
+        if (total > 0 &&
+            ((xyz_out && hipMemcpyAsync(xyz_out, c->h_xyz.p, 24 * (size_t)total, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+             (radii_out && hipMemcpyAsync(radii_out, c->h_radii.p, 8 * (size_t)total, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+             (class_out && hipMemcpyAsync(class_out, c->h_counts.p, (size_t)total, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+             hipStreamSynchronize(c->stream) != hipSuccess))
+            return set_err(err_out, err_len, "device-to-host copy failed");
+        written = total;
+        return 0;
+    });
+    return rc ? -1 : written;
+}
+
+extern "C" long long freesasa_gpu_parse_files(const char *const *paths, int n_paths, int ingest_options, int n_threads, int device,
+                                              double *xyz_out, double *radii_out, unsigned char *class_out, long long cap,
+                                              long long *offsets_out, int *status_out, int *host_out, char *err_out, int err_len)
+{
+    return freesasa_gpu_parse_files_classified(paths, n_paths, ingest_options, n_threads, device, xyz_out, radii_out, class_out, cap,
+                                               offsets_out, status_out, host_out, nullptr, err_out, err_len);
+}
+
+/* files the sweeps of this process parsed on the device / left to the host parser since the last call (FREESASA_INGEST_PARSE_ON_DEVICE) */
+extern "C" void freesasa_gpu_sweep_parse_stats(long long *device_files, long long *host_files)
+{
+    if (device_files) *device_files = g_parse_dev_files.exchange(0);
+    if (host_files) *host_files = g_parse_host_files.exchange(0);
+}
+
+extern "C" int freesasa_gpu_sweep_files_classified(const char *const *paths, int n_paths, int ingest_options, int n_threads,
+                                                   int alg, double probe, int resolution, long long batch_atoms,
+                                                   double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out,
+                                                   const char *done_path, long long max_new_batches, const int *devices, int n_devices,
+                                                   const freesasa_ingest_classifier *classifier, char *err_out, int err_len)
+{
+    return sweep_impl({paths, n_paths, ingest_options, n_threads, alg, probe, resolution, batch_atoms, totals_out, class_sums_out, atoms_out, status_out,
+                       done_path, max_new_batches, devices, n_devices, classifier, nullptr}, err_out, err_len);
+}
+
+extern "C" int freesasa_gpu_sweep_files_devices(const char *const *paths, int n_paths, int ingest_options, int n_threads,
+                                                int alg, double probe, int resolution, long long batch_atoms,
+                                                double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out,
+                                                const char *done_path, long long max_new_batches, const int *devices, int n_devices,
+                                                char *err_out, int err_len)
+{
+    return freesasa_gpu_sweep_files_classified(paths, n_paths, ingest_options, n_threads, alg, probe, resolution, batch_atoms, totals_out, class_sums_out,
+                                               atoms_out, status_out, done_path, max_new_batches, devices, n_devices, nullptr, err_out, err_len);
+}
+
+extern "C" int freesasa_gpu_sweep_files_resumable(const char *const *paths, int n_paths, int ingest_options, int n_threads,
+                                                  int alg, double probe, int resolution, long long batch_atoms,
+                                                  double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out,
+                                                  const char *done_path, long long max_new_batches, int device, char *err_out, int err_len)
+{
+    return freesasa_gpu_sweep_files_devices(paths, n_paths, ingest_options, n_threads, alg, probe, resolution, batch_atoms, totals_out, class_sums_out,
+                                            atoms_out, status_out, done_path, max_new_batches, &device, 1, err_out, err_len);
+}
+
+extern "C" int freesasa_gpu_sweep_files(const char *const *paths, int n_paths, int ingest_options, int n_threads,
+                                        int alg, double probe, int resolution, long long batch_atoms,
+                                        double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out,
+                                        int device, char *err_out, int err_len)
+{
+    return freesasa_gpu_sweep_files_resumable(paths, n_paths, ingest_options, n_threads, alg, probe, resolution, batch_atoms, totals_out, class_sums_out,
+                                              atoms_out, status_out, nullptr, 0, device, err_out, err_len);
+}
+
+/* The sweep with the per-residue table (include/freesasa_gpu.h): the batches' blocks (ResBatch) into ONE block behind
+   res_offsets, files in the caller's order, each file's residues in the file's order. */
+static int assemble_residue_table(int n_paths, std::vector<std::unique_ptr<ResBatch>> &done, freesasa_gpu_residue_table *t, char *err_out, int err_len)
+{
+    std::vector<long long> count((size_t)n_paths, 0);
+    std::vector<char> seen((size_t)n_paths, 0);
+    for (auto &rb : done)
+        for (int k = 0; k < rb->ns; ++k) { count[(size_t)(rb->first + k)] = rb->fcount[(size_t)k]; seen[(size_t)(rb->first + k)] = 1; }
+    long long R = 0;
+    for (int f = 0; f < n_paths; ++f) {
+        if (!seen[(size_t)f]) return set_err(err_out, err_len, "a batch of the sweep left no residue block");
+        R += count[(size_t)f];
+    }
+    const size_t n = (size_t)n_paths, r = (size_t)R;
+    const size_t o_abs = 8 * (n + 1), o_rel = o_abs + 48 * r, o_atoms = o_rel + 40 * r, o_ref = o_atoms + 4 * r, o_name = o_ref + 2 * r,
+                 o_number = o_name + 4 * r, o_chain = o_number + 6 * r, bytes = o_chain + 4 * r;
+    char *blk = (char *)hf_malloc(bytes + 8);
+    if (!blk) return set_err(err_out, err_len, "out of host memory (residue table)");
+    t->n_files = n_paths; t->n_residues = R;
+    t->res_offsets = (int64_t *)blk; t->abs = (double *)(blk + o_abs); t->rel = (double *)(blk + o_rel);
+    t->res_atoms = (int32_t *)(blk + o_atoms); t->res_ref = (int16_t *)(blk + o_ref);
+    t->res_name = blk + o_name; t->res_number = blk + o_number; t->res_chain = blk + o_chain;
+    t->res_offsets[0] = 0;
+    for (int f = 0; f < n_paths; ++f) t->res_offsets[f + 1] = t->res_offsets[f] + count[(size_t)f];
+    for (auto &rb : done) {
+        const double *b_abs = rb->areas.data(), *b_rel = b_abs + 6 * rb->n_res;
+        for (int k = 0; k < rb->ns; ++k) {
+            const size_t m = (size_t)rb->fcount[(size_t)k], src = (size_t)rb->fstart[(size_t)k], dst = (size_t)t->res_offsets[rb->first + k];
+            if (!m) continue;
+            memcpy(t->abs + 6 * dst, b_abs + 6 * src, 48 * m);
+            memcpy(t->rel + 5 * dst, b_rel + 5 * src, 40 * m);
+            memcpy(t->res_ref + dst, rb->ref.data() + src, 2 * m);
+            memcpy(t->res_name + 4 * dst, rb->name.data() + 4 * src, 4 * m);
+            memcpy(t->res_number + 6 * dst, rb->number.data() + 6 * src, 6 * m);
+            memcpy(t->res_chain + 4 * dst, rb->chain.data() + 4 * src, 4 * m);
+            for (size_t q = 0; q < m; ++q) t->res_atoms[dst + q] = (int32_t)(rb->res_first[src + q + 1] - rb->res_first[src + q]);
+        }
+    }
+    return 0;
+}
+
+extern "C" void freesasa_gpu_residue_table_free(freesasa_gpu_residue_table *table)
+{
+    if (!table) return;
+    free(table->res_offsets); /* (the one block: assemble_residue_table) */
+    memset(table, 0, sizeof *table);
+}
+
+extern "C" int freesasa_gpu_sweep_files_residues(const char *const *paths, int n_paths, int ingest_options, int n_threads,
+                                                 int alg, double probe, int resolution, long long batch_atoms,
+                                                 double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out,
+                                                 const int *devices, int n_devices, const freesasa_ingest_classifier *classifier,
+                                                 freesasa_gpu_residue_table *table_out, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (table_out) memset(table_out, 0, sizeof *table_out);
+    if (!table_out) return set_err(err_out, err_len, "null argument");
+    const int rc = guarded(err_out, err_len, [&]() -> int {
+        ResCollector col;
+        if (sweep_impl({paths, n_paths, ingest_options, n_threads, alg, probe, resolution, batch_atoms, totals_out, class_sums_out, atoms_out, status_out,
+                        nullptr, 0, devices, n_devices, classifier, &col}, err_out, err_len))
+            return -1;
+        return assemble_residue_table(n_paths, col.done, table_out, err_out, err_len);
+    });
+    if (rc) freesasa_gpu_residue_table_free(table_out);
+    return rc ? -1 : 0;
+}
