@@ -2,8 +2,8 @@
 #   make            -> freesasa_amd/lib/libfreesasa_amd.so (stand-alone drop-in library)
 #                      freesasa_amd/lib/libfreesasa_amd_seam.a (seam objects for a drop-in
 #                      build of the reference)
-#   make emu        -> tests/emu/libsasa_emu.so  (TESTS ONLY: the kernel phase functions
-#                      driven on the CPU; never linked into the product)
+#   make emu        -> tests/emu/libsasa_emu.so, libselect_emu.so  (TESTS ONLY: the kernel phase
+#                      functions driven on the CPU; never linked into the product)
 #   make oracle     -> oracle/ (TESTS ONLY) ; make tools -> tools/libsasa_synth.so
 HIPCC   ?= /opt/rocm/bin/hipcc
 CC      ?= gcc
@@ -19,7 +19,7 @@ all: $(LIBDIR)/libfreesasa_amd.so $(LIBDIR)/libfreesasa_amd_seam.a
 # Device code lives in ONE translation unit (gpu_kernels.hip); the compiler's per-kernel resource report (registers,
 # scratch, LDS) is kept next to its object: tests/test_capi.py checks that the hot kernels do not spill.  The other
 # .hip files are host code over the HIP runtime (engine_internal.h says who holds what).
-ENGINE_HDRS = $(CSRC)/classifier.h $(CSRC)/engine_internal.h $(CSRC)/sasa_kernels.h $(CSRC)/group_kernels.h $(CSRC)/sr_caps.h $(CSRC)/lr2_kernels.h $(CSRC)/gpu_parse.h $(CSRC)/protor_table.h include/freesasa_gpu.h include/freesasa_ingest.h
+ENGINE_HDRS = $(CSRC)/classifier.h $(CSRC)/engine_internal.h $(CSRC)/sasa_kernels.h $(CSRC)/group_kernels.h $(CSRC)/select_kernels.h $(CSRC)/select_program.h $(CSRC)/sr_caps.h $(CSRC)/lr2_kernels.h $(CSRC)/gpu_parse.h $(CSRC)/protor_table.h include/freesasa_gpu.h include/freesasa_ingest.h
 $(LIBDIR)/gpu_kernels.o: $(CSRC)/gpu_kernels.hip $(ENGINE_HDRS)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(LIBDIR)/kernel_resources.txt; rc=$$?; \
@@ -59,7 +59,7 @@ $(LIBDIR)/classifier.o: $(CSRC)/classifier.c $(CSRC)/classifier.h include/freesa
 	@mkdir -p $(LIBDIR)
 	$(CC) $(CFLAGS) -Iinclude -c $< -o $@
 
-$(LIBDIR)/select.o: $(CSRC)/select.c include/freesasa_ingest.h $(CSRC)/hostfault.h
+$(LIBDIR)/select.o: $(CSRC)/select.c $(CSRC)/select_program.h include/freesasa_ingest.h $(CSRC)/hostfault.h
 	@mkdir -p $(LIBDIR)
 	$(CC) $(CFLAGS) -Iinclude -c $< -o $@
 
@@ -70,15 +70,19 @@ $(LIBDIR)/ingest_cache.o: $(CSRC)/ingest_cache.c include/freesasa_ingest.h $(CSR
 $(LIBDIR)/libfreesasa_amd.so: $(GPU_OBJS) $(LIBDIR)/seam.o $(LIBDIR)/testpoints.o $(LIBDIR)/api.o $(LIBDIR)/ingest.o $(LIBDIR)/classifier.o $(LIBDIR)/select.o $(LIBDIR)/ingest_cache.o $(LIBDIR)/hostfault.o $(LIBDIR)/hostfault_new.o $(CSRC)/exports.map
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--version-script=$(CSRC)/exports.map -o $@ $(filter %.o,$^)
 
-$(LIBDIR)/libfreesasa_amd_seam.a: $(GPU_OBJS) $(LIBDIR)/seam.o $(LIBDIR)/testpoints.o $(LIBDIR)/ingest.o $(LIBDIR)/classifier.o $(LIBDIR)/ingest_cache.o $(LIBDIR)/hostfault.o
+$(LIBDIR)/libfreesasa_amd_seam.a: $(GPU_OBJS) $(LIBDIR)/seam.o $(LIBDIR)/testpoints.o $(LIBDIR)/ingest.o $(LIBDIR)/classifier.o $(LIBDIR)/select.o $(LIBDIR)/ingest_cache.o $(LIBDIR)/hostfault.o
 	rm -f $@; ar rcs $@ $^
 
-emu: tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so
+emu: tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so
 # the loader with its byte-at-a-time mmCIF tokenizer only: the differential twin of the SSE2 row scanner
 tests/emu/libingest_scalar.so: $(CSRC)/ingest.c $(CSRC)/classifier.c $(CSRC)/classifier.h $(CSRC)/hostfault.c $(CSRC)/hostfault.h $(CSRC)/protor_table.h include/freesasa_ingest.h
 	$(CC) $(CFLAGS) -DFREESASA_INGEST_NO_SIMD -Iinclude -pthread -shared -o $@ $(CSRC)/ingest.c $(CSRC)/classifier.c $(CSRC)/hostfault.c -lm
 tests/emu/libsasa_emu.so: tests/emu/emu.cpp $(CSRC)/sasa_kernels.h $(CSRC)/sr_caps.h $(CSRC)/lr2_kernels.h
 	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -DSASA_EMU -shared -o $@ tests/emu/emu.cpp -lm
+
+# the selection kernels' phase functions (select_kernels.h) driven over a loaded batch
+tests/emu/libselect_emu.so: tests/emu/emu_select.cpp $(CSRC)/select_kernels.h $(CSRC)/select_program.h $(CSRC)/sasa_kernels.h include/freesasa_ingest.h
+	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -DSASA_EMU -Iinclude -shared -o $@ tests/emu/emu_select.cpp -lm
 
 # Sanitizer build of the HOST sources (the reference's CI runs its C under sanitizers): the parsers,
 # the selection language, the C API shims and the test-point generator with AddressSanitizer + UBSan, linked with
@@ -95,13 +99,15 @@ asan-test: $(ASAN_SO)
 	LD_PRELOAD="$$($(CC) -print-file-name=libasan.so) $$($(CC) -print-file-name=libubsan.so)" ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 \
 	    FREESASA_AMD_LIB=$(CURDIR)/$(ASAN_SO) python -m pytest tests/test_ingest.py tests/test_select.py tests/test_capi.py tests/test_hostfault.py tests/test_classifier.py tests/test_classifier_hostfault.py -q -m "not gpu" -p no:cacheprovider
 
+# (-r: no built-in rules.  The reference's generated lexer.c / parser.c are compiled where they lie; make's built-in .l.c / .y.c
+# rules would try to regenerate them INSIDE the reference tree whenever lexer.l / parser.y carry a later time stamp.)
 oracle: $(LIBDIR)/libfreesasa_amd_seam.a
-	$(MAKE) -C oracle all dropin
+	$(MAKE) -r -C oracle all dropin
 tools:
 	$(MAKE) -C tools
 
 clean:
-	rm -rf $(LIBDIR) tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so
+	rm -rf $(LIBDIR) tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so
 	$(MAKE) -C oracle clean
 	$(MAKE) -C tools clean
 .PHONY: all emu oracle tools clean asan asan-test

@@ -401,6 +401,60 @@ def sweep_files_residues(paths, alg=LEE_RICHARDS, probe=1.4, resolution=20, inge
     return totals, cls, atoms, status, table
 
 
+def _select_proto(L):
+    L.freesasa_gpu_select_batch.argtypes = [C.c_void_p, C.c_void_p, _dp, _dp, C.POINTER(C.c_longlong), C.POINTER(C.c_ulonglong),
+                                            C.c_int, C.c_char_p, C.c_int]
+    L.freesasa_gpu_sweep_files_select.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                                  C.c_longlong, _dp, _dp, _lp, _ip, _ip, C.c_int, C.c_void_p, C.c_void_p,
+                                                  _dp, C.POINTER(C.c_longlong), C.c_char_p, C.c_int]
+    return L
+
+
+def select_batch(batch, selection, sasa, device=-1, bits=False):
+    """freesasa_gpu_select_batch(): the areas of an ingest.Selection set on a loaded ingest.Batch, from per-atom areas on
+    the host (e.g. calc_batch's) -> (areas[n_structs, S], counts[n_structs, S]) or, bits=True, (areas, counts,
+    bits[n_atoms] uint64: bit k = selection k holds the atom).  The masks and the sums are made on the device."""
+    L = _select_proto(lib())
+    S, ns = len(selection), batch.n_structs
+    sasa = _f64(sasa)
+    if sasa.size != batch.n_atoms:
+        raise ValueError("sasa needs one area per atom of the batch")
+    areas, counts = np.zeros((ns, S)), np.zeros((ns, S), dtype=np.int64)
+    words = np.zeros(batch.n_atoms, dtype=np.uint64) if bits else None
+    err = C.create_string_buffer(512)
+    cb = batch._as_c()
+    ret = L.freesasa_gpu_select_batch(C.byref(cb), selection.handle, sasa.ctypes.data_as(_dp), areas.ctypes.data_as(_dp),
+                                      counts.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                      words.ctypes.data_as(C.POINTER(C.c_ulonglong)) if bits else None, device, err, 512)
+    if ret:
+        raise RuntimeError("freesasa_gpu_select_batch: " + err.value.decode())
+    return (areas, counts, words) if bits else (areas, counts)
+
+
+def sweep_files_select(paths, selection, alg=LEE_RICHARDS, probe=1.4, resolution=20, ingest_options=0, n_threads=0, batch_atoms=0,
+                       device=-1, devices=None, classifier=None):
+    """freesasa_gpu_sweep_files_select(): sweep_files plus the areas of an ingest.Selection set for every file ->
+    (totals[n], class_sums[n,3], n_atoms[n], status[n], areas[n, S], counts[n, S]); a file that failed to load has zeros.
+    The per-atom areas stay on the device; with ingest.PARSE_ON_DEVICE the atoms' names, symbols and residues are built
+    there too.  classifier: an ingest.Classifier in place of ProtOr."""
+    from . import ingest
+    L = _select_proto(lib())
+    n, S = len(paths), len(selection)
+    arr = (C.c_char_p * n)(*[str(p).encode() for p in paths])
+    totals, atoms, status = np.zeros(n), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+    cls = np.zeros((n, 3))
+    areas, counts = np.zeros((n, S)), np.zeros((n, S), dtype=np.int64)
+    err = C.create_string_buffer(512)
+    keep, dp_, nd = _devs(devices, device)
+    ret = L.freesasa_gpu_sweep_files_select(arr, n, ingest_options, n_threads, alg, probe, resolution, batch_atoms,
+                                            totals.ctypes.data_as(_dp), cls.ctypes.data_as(_dp), atoms.ctypes.data_as(_lp),
+                                            status.ctypes.data_as(_ip), dp_, nd, ingest._handle(classifier), selection.handle,
+                                            areas.ctypes.data_as(_dp), counts.ctypes.data_as(C.POINTER(C.c_longlong)), err, 512)
+    if ret:
+        raise RuntimeError("freesasa_gpu_sweep_files_select: " + err.value.decode())
+    return totals, cls, atoms, status, areas, counts
+
+
 def sweep_files_resumable(paths, done_path, alg=LEE_RICHARDS, probe=1.4, resolution=20, ingest_options=0, n_threads=0,
                           batch_atoms=0, max_new_batches=0, device=-1, devices=None, classifier=None):
     """freesasa_gpu_sweep_files_resumable(): like sweep_files with a done-list at done_path (+ done_path.bin):

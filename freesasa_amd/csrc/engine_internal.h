@@ -6,11 +6,11 @@
  *                      kl_* launchers below (the only file that holds device code)
  *   gpu_engine.hip     the per-device context (workspace, status words, events), the launch sequence of one batch,
  *                      asynchronous batches, the device-pointer entry points
- *   gpu_ops.hip        device-side aggregates (segments, classes, residues) and the kernel test hooks
+ *   gpu_ops.hip        device-side aggregates (segments, classes, residues, selections) and the kernel test hooks
  *   gpu_hostbatch.hip  host-pointer batches: the context pool, one device, several devices, the pipelined form
  *   gpu_drivers.hip    cache sweep and trajectory drivers (one device or a list of devices); what the drivers share
  *                      (device lists, the host budget, DoneList)
- *   gpu_sweep.hip      the file sweep (host or device parser, done-list, per-residue table) and the device parser's entries
+ *   gpu_sweep.hip      the file sweep (host or device parser, done-list, per-residue table, selections) and the device parser's entries
  *   gpu_parse.hip      the device-side PDB / mmCIF parser: its kernels and their host driver (gpu_parse.h)
  *   gpu_groups.hip     chain groups: a batch and every group of it cut out as a structure of its own, in one batch
  */
@@ -35,6 +35,7 @@
 #include "sasa_kernels.h"
 #include "lr2_kernels.h"
 #include "group_kernels.h"
+#include "select_kernels.h"
 #include "gpu_parse.h"
 
 /* ------------------------------------------------------------------ kernel launchers (gpu_kernels.hip) */
@@ -74,6 +75,11 @@ hipError_t kl_grp_count(const sasa::GrpArgs &a, hipStream_t st);
 hipError_t kl_grp_rank(const sasa::GrpArgs &a, hipStream_t st);
 hipError_t kl_grp_finish(const sasa::GrpArgs &a, hipStream_t st);
 hipError_t kl_grp_totals(const sasa::GrpArgs &a, hipStream_t st);
+
+/* selection areas (select_kernels.h): the mask word of every atom (one thread per atom), the masked sums (one workgroup per
+   structure and SEL_G selections) */
+hipError_t kl_sel_mask(const sasa::SelArgs &a, hipStream_t st);
+hipError_t kl_sel_sums(const sasa::SelArgs &a, hipStream_t st);
 
 /* ------------------------------------------------------------------ context (gpu_engine.hip) */
 
@@ -183,6 +189,12 @@ int run_batch(freesasa_gpu_ctx *c, bool lr, const double *d_xyz, const double *d
    (gpu_ops.hip) */
 int residue_areas_resident(freesasa_gpu_ctx *c, const double *d_sasa, const unsigned char *d_class, const unsigned char *d_backbone,
                            const int64_t *d_res_first, const short *d_ref_row, int n_res, double *d_abs, double *d_rel);
+
+/* Selection areas (freesasa_gpu_select_batch's kernels) for callers whose arrays are on the device already: the caller fills
+   the atoms' keys, offsets, residue boundaries and labels, n_* and sasa of `sa`; this uploads the set's program, sizes the
+   mask words and the results (c->parse[PBUF_SEL_*]; sa.bits / sa.area / sa.count say where) and enqueues sel_mask and
+   sel_sums on the context's stream.  No synchronisation.  (gpu_ops.hip) */
+int select_resident(freesasa_gpu_ctx *c, const struct freesasa_ingest_selection *sel, sasa::SelArgs &sa);
 
 /* ------------------------------------------------------------------ host-side helpers (gpu_hostbatch.hip) */
 

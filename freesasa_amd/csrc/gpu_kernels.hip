@@ -823,6 +823,30 @@ hipError_t kl_grp_totals(const GrpArgs &a, hipStream_t st)
     return hipGetLastError();
 }
 
+/* selection areas (select_kernels.h): the compiled set per atom, then the masked sums per (structure, SEL_G selections) */
+__global__ __launch_bounds__(SEL_B) void k_sel_mask(SelArgs a)
+{
+    sel_mask_atom(a, (int64_t)blockIdx.x * SEL_B + threadIdx.x);
+}
+__global__ __launch_bounds__(SASA_TOT_B) void k_sel_sums(SelArgs a)
+{
+    __shared__ double part[SEL_G * SASA_TOT_B];
+    __shared__ int cnt[SEL_G * SASA_TOT_B];
+    sel_sums_phase0(a, part, cnt, blockIdx.x, blockIdx.y * SEL_G, threadIdx.x);
+    __syncthreads();
+    sel_sums_phase1(a, part, cnt, blockIdx.x, blockIdx.y * SEL_G, threadIdx.x);
+}
+hipError_t kl_sel_mask(const SelArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_sel_mask, dim3((unsigned)((a.n_atoms + SEL_B - 1) / SEL_B)), dim3(SEL_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_sel_sums(const SelArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_sel_sums, dim3((unsigned)a.n_structs, (unsigned)((a.n_sel + SEL_G - 1) / SEL_G)), dim3(SASA_TOT_B), 0, st, a);
+    return hipGetLastError();
+}
+
 void kl_dump_phase_clocks(void)
 {
 #ifdef SASA_PHASE_TIMING

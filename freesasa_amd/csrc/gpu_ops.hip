@@ -1,5 +1,5 @@
 /*
- * gpu_ops.hip — device-side aggregates over per-atom areas (segments, atom classes, residues: what the reference's
+ * gpu_ops.hip — device-side aggregates over per-atom areas (segments, atom classes, residues, selections: what the reference's
  * result tree adds up on the host, src/node.c:717-764, src/classifier.c:830-866, src/rsa.c:14-25) and the test hooks
  * that run the integer / exact parts of the Lee-Richards kernel on their own.  Host code; kernels in gpu_kernels.hip.
  */
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "engine_internal.h"
+#include "select_program.h"
 
 extern "C" int freesasa_gpu_segment_sums_dev(freesasa_gpu_ctx *c, const double *d_sasa, const int64_t *seg,
                                              int n_segs, double *d_out)
@@ -104,6 +105,91 @@ int residue_areas_resident(freesasa_gpu_ctx *c, const double *d_sasa, const unsi
     }
     HIP_TRY(c, kl_residue_areas(d_sasa, d_class, d_backbone, d_res_first, d_ref_row, d_table, d_abs, d_ref_row ? d_rel : nullptr, n_res, c->stream));
     return 0;
+}
+
+/* ------------------------------------------------------------------ selection areas (select_kernels.h) */
+
+/* (engine_internal.h) */
+int select_resident(freesasa_gpu_ctx *c, const freesasa_ingest_selection *sel, sasa::SelArgs &sa)
+{
+    int n_words = 0, flags = 0;
+    const freesasa_sel_word *prog = (const freesasa_sel_word *)freesasa_ingest_selection_program(sel, &n_words, &flags);
+    const int S = freesasa_ingest_selection_count(sel);
+    if (S < 1 || n_words < 1 || sa.n_atoms <= 0 || sa.n_structs <= 0 || sa.n_res <= 0) return ctx_fail(c, "bad argument");
+    DevBuf *B = c->parse;
+    const size_t cells = (size_t)sa.n_structs * (size_t)S;
+    if (ensure(c, B[PBUF_SEL_PROG], sizeof(freesasa_sel_word) * (size_t)n_words) || ensure(c, B[PBUF_SEL_BITS], 8 * (size_t)sa.n_atoms) ||
+        ensure(c, B[PBUF_SEL_OUT], 16 * cells))
+        return -1;
+    /* (the program lives in the set, which outlives the call: the copy may run later) */
+    HIP_TRY(c, hipMemcpyAsync(B[PBUF_SEL_PROG].p, prog, sizeof(freesasa_sel_word) * (size_t)n_words, hipMemcpyHostToDevice, c->stream));
+    sa.prog = (const freesasa_sel_word *)B[PBUF_SEL_PROG].p; sa.n_words = n_words; sa.flags = flags; sa.n_sel = S;
+    sa.bits = (uint64_t *)B[PBUF_SEL_BITS].p;
+    sa.area = (double *)B[PBUF_SEL_OUT].p; sa.count = (long long *)(sa.area + cells);
+    HIP_TRY(c, kl_sel_mask(sa, c->stream));
+    HIP_TRY(c, kl_sel_sums(sa, c->stream));
+    return 0;
+}
+
+extern "C" int freesasa_gpu_select_batch(const freesasa_ingest_batch *b, const freesasa_ingest_selection *sel, const double *sasa,
+                                         double *area_out, long long *atoms_out, unsigned long long *bits_out, int device,
+                                         char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (!b || !sel || !sasa || !area_out || !atoms_out) return set_err(err_out, err_len, "null argument");
+    const int S = freesasa_ingest_selection_count(sel), ns = b->n_structs;
+    const int64_t n = b->n_atoms, R = b->n_residues;
+    if (ns < 0 || n < 0 || R < 0 || (n > 0 && (R == 0 || ns == 0))) return set_err(err_out, err_len, "inconsistent batch");
+    for (int k = 0; k < ns; ++k)
+        if (b->offsets[k + 1] < b->offsets[k]) return set_err(err_out, err_len, "structure offsets must be non-decreasing");
+    for (int64_t r = 0; r < R; ++r)
+        if (b->res_first[r + 1] < b->res_first[r]) return set_err(err_out, err_len, "residue offsets must be non-decreasing");
+    if (ns > 0 && (b->offsets[0] != 0 || b->offsets[ns] != n || (R > 0 && (b->res_first[0] != 0 || b->res_first[R] != n))))
+        return set_err(err_out, err_len, "inconsistent batch");
+    for (size_t k = 0; k < (size_t)ns * (size_t)S; ++k) { area_out[k] = 0; atoms_out[k] = 0; }
+    if (n == 0) return 0; /* (nothing to select from: freesasa_ingest_select gives 0 as well) */
+    if (freesasa_gpu_device_count() <= 0) return set_err(err_out, err_len, "no HIP device available: libfreesasa_amd has no CPU path");
+    return guarded(err_out, err_len, [&]() -> int {
+        std::vector<uint64_t> keys((size_t)n); /* (declared before the lease: freed after its stream is idle) */
+        sel_pack_atom_keys(b->atom_name, b->atom_symbol, n, keys.data());
+        PoolLease lease(device);
+        freesasa_gpu_ctx *c = lease.c;
+        if (!c) return set_err(err_out, err_len, "could not create a GPU context");
+        c->err[0] = 0;
+        const int rc = [&]() -> int {
+            HIP_TRY(c, hipSetDevice(c->device));
+            DevBuf *B = c->parse;
+            const size_t b_off = 8 * ((size_t)ns + 1), b_first = 8 * ((size_t)R + 1);
+            if (ensure(c, c->h_sasa, 8 * (size_t)n) || ensure(c, c->seg, b_off + b_first) || ensure(c, B[PBUF_ATOM_KEYS], 8 * (size_t)n) ||
+                ensure(c, B[PBUF_SEL_LABELS], 14 * (size_t)R))
+                return -1;
+            char *seg = (char *)c->seg.p, *lab = (char *)B[PBUF_SEL_LABELS].p;
+            hipStream_t st = c->stream;
+            HIP_TRY(c, hipMemcpyAsync(c->h_sasa.p, sasa, 8 * (size_t)n, hipMemcpyHostToDevice, st));
+            HIP_TRY(c, hipMemcpyAsync(seg, b->offsets, b_off, hipMemcpyHostToDevice, st));
+            HIP_TRY(c, hipMemcpyAsync(seg + b_off, b->res_first, b_first, hipMemcpyHostToDevice, st));
+            HIP_TRY(c, hipMemcpyAsync(B[PBUF_ATOM_KEYS].p, keys.data(), 8 * (size_t)n, hipMemcpyHostToDevice, st));
+            HIP_TRY(c, hipMemcpyAsync(lab, b->res_name, 4 * (size_t)R, hipMemcpyHostToDevice, st));
+            HIP_TRY(c, hipMemcpyAsync(lab + 4 * (size_t)R, b->res_chain, 4 * (size_t)R, hipMemcpyHostToDevice, st));
+            HIP_TRY(c, hipMemcpyAsync(lab + 8 * (size_t)R, b->res_number, 6 * (size_t)R, hipMemcpyHostToDevice, st));
+            sasa::SelArgs sa;
+            memset(&sa, 0, sizeof sa);
+            sa.akey = (const uint64_t *)B[PBUF_ATOM_KEYS].p;
+            sa.offsets = (const int64_t *)seg; sa.n_structs = ns; sa.n_atoms = n;
+            sa.res_first = (const int64_t *)(seg + b_off); sa.n_res = R; sa.n_res_dev = 0;
+            sa.name_h = (const uint32_t *)lab; sa.chain_h = (const uint32_t *)(lab + 4 * (size_t)R); sa.number_h = (const uint16_t *)(lab + 8 * (size_t)R);
+            sa.sasa = (const double *)c->h_sasa.p;
+            if (select_resident(c, sel, sa)) return -1;
+            const size_t cells = (size_t)ns * (size_t)S;
+            HIP_TRY(c, hipMemcpyAsync(area_out, sa.area, 8 * cells, hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipMemcpyAsync(atoms_out, sa.count, 8 * cells, hipMemcpyDeviceToHost, st));
+            if (bits_out) HIP_TRY(c, hipMemcpyAsync(bits_out, sa.bits, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipStreamSynchronize(st));
+            return 0;
+        }();
+        if (rc) { (void)hipStreamSynchronize(c->stream); return set_err(err_out, err_len, c->err[0] ? c->err : "selection areas failed"); }
+        return 0;
+    });
 }
 
 /* ------------------------------------------------------------------ test hooks of the L&R kernel's integer parts */

@@ -47,6 +47,11 @@ enum ParseBuf {
     PBUF_RES_REF,     /* int16 [R + extra residues]: reference row (-1 throughout with a user classifier) */
     PBUF_RES_LABELS,  /* names, 4 bytes [R] | chains, 4 bytes [R] | numbers, 6 bytes [R] */
     PBUF_RES_AREAS,   /* double: abs [6 R] | rel [5 R], R with the host parser's residues (owned by the sweep, gpu_sweep.hip) */
+    PBUF_ATOM_KEYS,   /* uint64 [A + extra atoms]: name (4 bytes) | symbol (2 bytes) | 0 0 of every atom, ONLY for a sweep with selections */
+    PBUF_SEL_LABELS,  /* the HOST parser's residues of a selection sweep (or a loaded batch's): names, 4 bytes | chains, 4 bytes | numbers, 6 bytes */
+    PBUF_SEL_PROG,    /* freesasa_sel_word: the selection set's program */
+    PBUF_SEL_BITS,    /* uint64 [atoms]: bit k = selection k holds the atom */
+    PBUF_SEL_OUT,     /* double [structures * selections] areas | long long [structures * selections] selected atoms */
     PBUF_COUNT
 };
 
@@ -71,5 +76,10 @@ int parse_batch_dev_finish(freesasa_gpu_ctx *c, long long extra_atoms);
 int parse_batch_dev_residues_count(freesasa_gpu_ctx *c, long long extra_atoms);
 int parse_batch_dev_residues_found(freesasa_gpu_ctx *c);
 int parse_batch_dev_residues_build(freesasa_gpu_ctx *c, int n_res, long long extra_res, int custom);
+
+/* Atom keys of the atoms the device kept (freesasa_gpu_sweep_files_select), behind parse_batch_dev_finish on the same stream:
+ * name and element symbol of every kept atom at its place in PBUF_ATOM_KEYS (sized for the atoms + extra_atoms), as the host
+ * loader stores them in atom_name / atom_symbol (ingest.c parse_pdb / cif_visit_atom).  Nothing here synchronises. */
+int parse_batch_dev_atom_keys(freesasa_gpu_ctx *c, long long extra_atoms);
 
 #endif

@@ -18,6 +18,8 @@
  *   kp_res_keys / kp_res_count / kp_res_build   ONLY for a sweep that asks for the per-residue table: residue key and
  *                    backbone flag of every kept atom in atom order, a flag where the key changes, its prefix sum over the
  *                    batch's atoms (kp_scan_blocks again), first atom / labels / reference row per residue
+ *   kp_atom_keys     ONLY for a sweep with selections (freesasa_gpu_sweep_files_select): name and element symbol of every
+ *                    kept atom in atom order, as the host loader stores them
  *
  * What the device REFUSES goes to the host parser, file by file, and is counted: coordinates not of the "%8.3f" form
  * (PDB) or not plain decimals of <= 15 digits (mmCIF) - the host's strtod path -, lines longer than the reference's
@@ -724,6 +726,94 @@ __global__ __launch_bounds__(PB) void kp_res_build(ResArgs ra)
     }
 }
 
+/* ---- atom keys (freesasa_gpu_sweep_files_select): what ingest.c parse_pdb / cif_visit_atom store in atom_name / atom_symbol.
+   A kernel of its own behind kp_scatter, next to kp_res_keys: only a sweep with selections launches it.  One thread per
+   line; a kept line's name (trimmed token, 4 bytes) and element symbol (2 bytes), NUL padded, to its atom's place. */
+/* ingest.c guess_symbol: the element from the four name columns.  (parse_pdb_line holds the same three lines in place: calling
+   this from there was tried and changes the schedule of kp_parse_lines - the plain sweep's kernels stay the parent's,
+   instruction for instruction, so the lines are restated here rather than shared.) */
+__device__ __forceinline__ void guess_symbol(unsigned char symbol[2], const unsigned char *nm)
+{
+    if (nm[0] == ' ' || (nm[0] >= '1' && nm[0] <= '9')) { symbol[0] = ' '; symbol[1] = nm[1]; }
+    else if (nm[3] == ' ') { symbol[0] = nm[0]; symbol[1] = nm[1]; }
+    else { symbol[0] = ' '; symbol[1] = nm[0]; }
+}
+
+struct KeyArgs {
+    ParseArgs p;               /* text, files, lines, lpos, fatoms, foff */
+    unsigned long long *key;   /* [A] */
+    long long A;
+};
+
+__global__ __launch_bounds__(PB) void kp_atom_keys(KeyArgs ka)
+{
+    const ParseArgs &a = ka.p;
+    const int l = blockIdx.x * PB + threadIdx.x;
+    if (l >= a.L) return;
+    const int p = a.lpos[l];
+    if (p < 0) return;
+    const unsigned s = a.lstart[l], e = a.lstart[l + 1] - 1;
+    int lo = 0, hi = a.F;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (a.files[mid].beg <= s) lo = mid; else hi = mid; }
+    if (a.fatoms[lo] == 0) return;
+    const long long o = a.foff[lo] + p;
+    if (o >= ka.A) return;
+    const ParseFile pf = a.files[lo];
+    const unsigned char *line = a.text + s;
+    const unsigned char *an;
+    int al;
+    unsigned sym0 = 0, sym1 = 0; /* the stored symbol's two bytes (held as values: an array indexed by the token's start would live in scratch) */
+    if (pf.kind == PARSE_PDB) {
+        /* n as parse_pdb_line counts it (the newline, an embedded NUL ends the line); a kept line has its 54 columns */
+        const bool last = a.lstart[l + 1] == a.files[lo + 1].beg;
+        int n = (int)(e - s) + ((last && pf.no_final_nl) ? 0 : 1);
+        for (int i = 54; i < n; ++i)
+            if (line[i] == 0) { n = i; break; }
+        int as_;
+        al = field_token(line + 12, 4, &as_);
+        an = line + 12 + as_;
+        /* columns 77-78 when present and not blank, else guessed from the name; then the field's first token */
+        const bool has_sym = n >= 78;
+        unsigned char symbol[2] = {0, 0};
+        if (has_sym) { symbol[0] = line[76]; symbol[1] = line[77]; }
+        if (!has_sym || (symbol[0] == ' ' && symbol[1] == ' ')) guess_symbol(symbol, line + 12);
+        const unsigned c0 = symbol[0], c1 = symbol[1];
+        if (!is_sp(c0)) { sym0 = c0; sym1 = is_sp(c1) ? 0u : c1; }
+        else if (!is_sp(c1)) sym0 = c1;
+    } else {
+        /* the row's tokens again (parse_cif_line took this line as a row with plain names: same cuts) */
+        const int n = (int)(e - s);
+        int tp5 = 0, tn5 = 0, tp7 = 0, tn7 = 0;
+        int i = 0, col = 0;
+        while (i < n) {
+            while (i < n && cif_ws(line[i])) ++i;
+            if (i >= n || line[i] == '#') break;
+            const int t0 = i;
+            if (line[i] == '\'' || line[i] == '"') {
+                const unsigned q = line[i++];
+                while (i < n) {
+                    if (line[i] == q && (i + 1 >= n || cif_ws(line[i + 1]))) { ++i; break; }
+                    ++i;
+                }
+            } else {
+                while (i < n && !cif_ws(line[i])) ++i;
+            }
+            if (pf.slot[5] == col) { tp5 = t0; tn5 = i - t0; }
+            if (pf.slot[7] == col) { tp7 = t0; tn7 = i - t0; }
+            ++col;
+        }
+        an = line + tp5;
+        al = tn5;
+        if (al >= 2 && an[0] == '"') { ++an; al -= 2; }
+        if (al > 4) al = 4;
+        if (tn7 > 0) sym0 = line[tp7];
+        if (tn7 > 1) sym1 = line[tp7 + 1];
+    }
+    unsigned long long k = ((unsigned long long)sym0 << 32) | ((unsigned long long)sym1 << 40);
+    for (int i = 0; i < al && i < 4; ++i) k |= (unsigned long long)an[i] << (8 * i);
+    ka.key[o] = k;
+}
+
 /* the classifier's tables on the device, once per device */
 struct Tables { void *p = nullptr; };
 Tables g_tables[64];
@@ -942,6 +1032,28 @@ int parse_batch_dev_residues_build(freesasa_gpu_ctx *c, int n_res, long long ext
     ra.frfirst = (int *)B[PBUF_FILE_RES0].p;
     HIP_TRY(c, hipMemsetAsync(B[PBUF_FILE_RES0].p, 0xff, 4 * (size_t)F, c->stream));
     hipLaunchKernelGGL(kp_res_build, dim3((unsigned)ra.p.n_blocks), dim3(PB), 0, c->stream, ra);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+/* ---- atom keys (gpu_parse.h; the buffer: PBUF_ATOM_KEYS) */
+int parse_batch_dev_atom_keys(freesasa_gpu_ctx *c, long long extra_atoms)
+{
+    const long long A = c->parse_atoms, cap = A + (extra_atoms > 0 ? extra_atoms : 0);
+    if (cap <= 0) return 0;
+    DevBuf *B = c->parse;
+    if (ensure(c, B[PBUF_ATOM_KEYS], 8 * (size_t)cap)) return -1;
+    if (A == 0) return 0;
+    KeyArgs ka;
+    memset(&ka, 0, sizeof ka);
+    ParseArgs &a = ka.p;
+    const int F = c->parse_files;
+    a.T = c->parse_T; a.F = F; a.options = c->parse_options; a.L = c->parse_lines;
+    a.text = (const unsigned char *)B[PBUF_TEXT].p; a.files = (const ParseFile *)B[PBUF_FILES].p;
+    a.fatoms = (int *)B[PBUF_FILE_WORDS].p; a.fstatus = a.fatoms + F; a.fhost = a.fstatus + F; a.foff = (long long *)B[PBUF_FILE_OFF].p;
+    a.lstart = (unsigned *)B[PBUF_LSTART].p; a.lpos = (int *)B[PBUF_LPOS].p;
+    ka.key = (unsigned long long *)B[PBUF_ATOM_KEYS].p; ka.A = A;
+    hipLaunchKernelGGL(kp_atom_keys, dim3((unsigned)((c->parse_lines + PB - 1) / PB)), dim3(PB), 0, c->stream, ka);
     HIP_TRY(c, hipGetLastError());
     return 0;
 }

@@ -21,6 +21,7 @@
 
 #include "engine_internal.h"
 #include "hostfault.h"
+#include "select_program.h"
 
 namespace {
 
@@ -158,6 +159,8 @@ struct SweepArgs {
     const int *devices; int n_devices;
     const freesasa_ingest_classifier *classifier;     /* (may be NULL) */
     ResCollector *rcol;                               /* (may be NULL) */
+    const freesasa_ingest_selection *sel;             /* (may be NULL; never together with rcol) */
+    double *sel_area_out; long long *sel_atoms_out;   /* [n_paths * selections] */
 };
 /* what the workers of one sweep share */
 struct Sweep {
@@ -214,6 +217,8 @@ struct Work {
     std::vector<double> cls;              /* [3 ns], empty: none computed */
     std::unique_ptr<ResBatch> rb;
     long long R = 0, Rd = 0;              /* residues of the batch, and how many of them are the device's */
+    std::vector<double> sel_area;         /* [structures of the batch * selections] on their way back: areas, selected atoms */
+    std::vector<long long> sel_count;
     Work(const Sweep &S, int b_) : b(b_), first(S.cut[b_]), ns(S.cut[b_ + 1] - S.cut[b_]), atoms((size_t)ns), status((size_t)ns), host((size_t)ns), atoms64((size_t)ns, 0)
     {
         if (!S.a.rcol) return;
@@ -331,16 +336,62 @@ int residues_collect(freesasa_gpu_ctx *c, Work &w, const Batch &hb)
     return 0;
 }
 
+/* selections, behind run_batch (the device's residue count came back under its wait): residue boundaries and labels as for
+   the residue table; the host parser's residue labels and atom keys go up behind the device's; sel_mask and sel_sums
+   (select_kernels.h) are enqueued and their results start their way back into w.sel_area / w.sel_count. */
+int select_enqueue(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, int nst, std::vector<int64_t> &hrf, std::vector<uint64_t> &hkeys)
+{
+    const SweepArgs &a = S.a;
+    const long long total = w.total, extra = hb.b.n_atoms;
+    const long long Rd = parse_batch_dev_residues_found(c), Rh = hb.b.n_residues, R = Rd + Rh;
+    if (Rd < 0 || R <= 0 || R >= (1LL << 31)) return ctx_fail(c, "bad residue count from the device parser");
+    DevBuf *B = c->parse;
+    if (parse_batch_dev_residues_build(c, (int)Rd, Rh, a.classifier != nullptr)) return -1;
+    if (Rh > 0) {
+        if (ensure(c, B[PBUF_SEL_LABELS], 14 * (size_t)Rh)) return -1;
+        hrf.resize((size_t)Rh + 1);
+        for (long long j = 0; j <= Rh; ++j) hrf[(size_t)j] = total + hb.b.res_first[j];
+        hkeys.resize((size_t)extra);
+        sel_pack_atom_keys(hb.b.atom_name, hb.b.atom_symbol, extra, hkeys.data());
+        char *lab = (char *)B[PBUF_SEL_LABELS].p;
+        if (hipMemcpyAsync((int64_t *)B[PBUF_RES_FIRST].p + Rd, hrf.data(), 8 * ((size_t)Rh + 1), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            hipMemcpyAsync((uint64_t *)B[PBUF_ATOM_KEYS].p + total, hkeys.data(), 8 * (size_t)extra, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            hipMemcpyAsync(lab, hb.b.res_name, 4 * (size_t)Rh, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            hipMemcpyAsync(lab + 4 * (size_t)Rh, hb.b.res_chain, 4 * (size_t)Rh, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            hipMemcpyAsync(lab + 8 * (size_t)Rh, hb.b.res_number, 6 * (size_t)Rh, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+            return ctx_fail(c, "host-to-device copy failed");
+    }
+    sasa::SelArgs sa;
+    memset(&sa, 0, sizeof sa);
+    sa.akey = (const uint64_t *)B[PBUF_ATOM_KEYS].p;
+    sa.offsets = (const int64_t *)c->offsets.p; /* (run_batch left the batch's offsets there) */
+    sa.n_structs = nst; sa.n_atoms = total + extra;
+    sa.res_first = (const int64_t *)B[PBUF_RES_FIRST].p; sa.n_res = R; sa.n_res_dev = Rd;
+    sa.name_d = (const uint32_t *)B[PBUF_RES_LABELS].p; sa.chain_d = sa.name_d + Rd; sa.number_d = (const uint16_t *)(sa.chain_d + Rd);
+    const char *lab = (const char *)B[PBUF_SEL_LABELS].p;
+    sa.name_h = (const uint32_t *)lab; sa.chain_h = (const uint32_t *)(lab + 4 * (size_t)Rh); sa.number_h = (const uint16_t *)(lab + 8 * (size_t)Rh);
+    sa.sasa = (const double *)c->h_sasa.p;
+    if (select_resident(c, a.sel, sa)) return -1;
+    const size_t cells = (size_t)nst * (size_t)sa.n_sel;
+    w.sel_area.resize(cells); w.sel_count.resize(cells);
+    if (hipMemcpyAsync(w.sel_area.data(), sa.area, 8 * cells, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipMemcpyAsync(w.sel_count.data(), sa.count, 8 * cells, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+        return ctx_fail(c, "device-to-host copy failed");
+    return 0;
+}
+
 /* The rest of a batch, whoever parsed: w.nd structures of w.total atoms are on the device (c->h_xyz, h_radii, h_counts;
    backbone flags and residue keys in c->parse[]), hb holds the files w.fb as the host parser read them and goes up behind
    them.  Results into the caller's arrays, w.atoms64 / w.cls and w.rb; on success the stream has been waited for. */
-int tail(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, std::vector<int64_t> &hrf)
+int tail(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, std::vector<int64_t> &hrf, std::vector<uint64_t> &hkeys)
 {
     const SweepArgs &a = S.a;
     const int ns = w.ns, first = w.first, nd = w.nd, nst = nd + (int)w.fb.size();
     const long long total = w.total, extra = hb.b.n_atoms, n_all = total + extra;
     if (parse_batch_dev_finish(c, extra)) return -1;
-    if (a.rcol && parse_batch_dev_residues_count(c, extra)) return -1;
+    if ((a.rcol || a.sel) && parse_batch_dev_residues_count(c, extra)) return -1;
+    if (a.sel && parse_batch_dev_atom_keys(c, extra)) return -1;
+    const int n_sel = a.sel ? freesasa_ingest_selection_count(a.sel) : 0;
     std::vector<int64_t> off((size_t)nst + 1);
     off[0] = 0;
     for (int k = 0; k < nd; ++k) off[(size_t)k + 1] = off[(size_t)k] + w.atoms[(size_t)k];
@@ -350,6 +401,7 @@ int tail(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, std::vector<in
         a.totals_out[first + k] = 0;
         w.atoms64[(size_t)k] = w.atoms[(size_t)k];
         if (a.class_sums_out) a.class_sums_out[3 * (first + k)] = a.class_sums_out[3 * (first + k) + 1] = a.class_sums_out[3 * (first + k) + 2] = 0;
+        for (int q = 0; q < n_sel; ++q) { a.sel_area_out[(size_t)(first + k) * n_sel + q] = 0; a.sel_atoms_out[(size_t)(first + k) * n_sel + q] = 0; }
     }
     for (size_t j = 0; j < w.fb.size(); ++j) { a.status_out[first + w.fb[j]] = hb.b.status[j]; w.atoms64[(size_t)w.fb[j]] = hb.b.offsets[j + 1] - hb.b.offsets[j]; }
     if (a.atoms_out) for (int k = 0; k < ns; ++k) a.atoms_out[first + k] = w.atoms64[(size_t)k];
@@ -366,6 +418,7 @@ int tail(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, std::vector<in
                   a.alg == 1 ? S.tp.data() : nullptr, (double *)c->h_sasa.p, nullptr, d_tot))
         return -1;
     if (a.rcol && residues_enqueue(S, c, w, hb, hrf)) return -1;
+    if (a.sel && select_enqueue(S, c, w, hb, nst, hrf, hkeys)) return -1;
     std::vector<double> tot((size_t)nst), cls;
     if (S.want_cls) {
         cls.resize(3 * (size_t)nst);
@@ -382,6 +435,11 @@ int tail(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, std::vector<in
         if (nd) memcpy(w.cls.data(), cls.data(), 8 * 3 * (size_t)nd);
         for (size_t j = 0; j < w.fb.size(); ++j) memcpy(&w.cls[3 * (size_t)w.fb[j]], &cls[3 * ((size_t)nd + j)], 8 * 3);
         if (a.class_sums_out) memcpy(a.class_sums_out + 3 * (size_t)first, w.cls.data(), 8 * 3 * (size_t)ns);
+    }
+    for (int k = 0; k < nst && n_sel; ++k) { /* (a structure without atoms has sums of nothing: the zeros are there already) */
+        const size_t f = (size_t)first + (k < nd ? (size_t)k : (size_t)w.fb[(size_t)(k - nd)]);
+        memcpy(a.sel_area_out + f * n_sel, &w.sel_area[(size_t)k * n_sel], 8 * (size_t)n_sel);
+        memcpy(a.sel_atoms_out + f * n_sel, &w.sel_count[(size_t)k * n_sel], 8 * (size_t)n_sel);
     }
     return w.R > 0 ? residues_collect(c, w, hb) : 0;
 }
@@ -414,6 +472,7 @@ void worker(Sweep &S, int wi) noexcept
        part of the batch in hand and its res_first, shifted - copies to the device read both */
     Batch hb;
     std::vector<int64_t> hrf;
+    std::vector<uint64_t> hkeys; /* (the host parser's atom keys, packed: selections) */
     DeviceNodeScope node(S.a.devices[wi]); /* this worker - its context's page-locked memory, its loader threads - on the device's NUMA node */
     PoolLease lease(S.a.devices[wi]);
     freesasa_gpu_ctx *c = lease.c;
@@ -431,7 +490,7 @@ void worker(Sweep &S, int wi) noexcept
         int ret = hipSetDevice(c->device) == hipSuccess ? 0 : ctx_fail(c, "hipSetDevice failed");
         if (!ret) ret = S.dev_parse ? front_device(S, c, cur, w, hb) : front_host(c, cur, w, hb);
         long long tr = S.sprof ? now_ns() : 0;
-        if (!ret) ret = tail(S, c, w, hb, hrf);
+        if (!ret) ret = tail(S, c, w, hb, hrf, hkeys);
         if (ret) (void)hipStreamSynchronize(c->stream); /* no copy may still read the batch when it is freed */
         if (S.sprof) { const long long t1 = now_ns(); S.tp_run += t1 - tr; tr = t1; }
         if (!ret && S.list.active()) ret = record(S, c, w);
@@ -622,7 +681,7 @@ extern "C" int freesasa_gpu_sweep_files_classified(const char *const *paths, int
                                                    const freesasa_ingest_classifier *classifier, char *err_out, int err_len)
 {
     return sweep_impl({paths, n_paths, ingest_options, n_threads, alg, probe, resolution, batch_atoms, totals_out, class_sums_out, atoms_out, status_out,
-                       done_path, max_new_batches, devices, n_devices, classifier, nullptr}, err_out, err_len);
+                       done_path, max_new_batches, devices, n_devices, classifier, nullptr, nullptr, nullptr, nullptr}, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_sweep_files_devices(const char *const *paths, int n_paths, int ingest_options, int n_threads,
@@ -713,10 +772,26 @@ extern "C" int freesasa_gpu_sweep_files_residues(const char *const *paths, int n
     const int rc = guarded(err_out, err_len, [&]() -> int {
         ResCollector col;
         if (sweep_impl({paths, n_paths, ingest_options, n_threads, alg, probe, resolution, batch_atoms, totals_out, class_sums_out, atoms_out, status_out,
-                        nullptr, 0, devices, n_devices, classifier, &col}, err_out, err_len))
+                        nullptr, 0, devices, n_devices, classifier, &col, nullptr, nullptr, nullptr}, err_out, err_len))
             return -1;
         return assemble_residue_table(n_paths, col.done, table_out, err_out, err_len);
     });
     if (rc) freesasa_gpu_residue_table_free(table_out);
+    return rc ? -1 : 0;
+}
+
+/* The sweep with selections (include/freesasa_gpu.h): a SweepArgs member away from the residue sweep. */
+extern "C" int freesasa_gpu_sweep_files_select(const char *const *paths, int n_paths, int ingest_options, int n_threads,
+                                               int alg, double probe, int resolution, long long batch_atoms,
+                                               double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out,
+                                               const int *devices, int n_devices, const freesasa_ingest_classifier *classifier,
+                                               const freesasa_ingest_selection *sel, double *sel_area_out, long long *sel_atoms_out,
+                                               char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (!sel || !sel_area_out || !sel_atoms_out) return set_err(err_out, err_len, "null argument");
+    if (freesasa_ingest_selection_count(sel) < 1) return set_err(err_out, err_len, "empty selection set");
+    const int rc = sweep_impl({paths, n_paths, ingest_options, n_threads, alg, probe, resolution, batch_atoms, totals_out, class_sums_out, atoms_out, status_out,
+                               nullptr, 0, devices, n_devices, classifier, nullptr, sel, sel_area_out, sel_atoms_out}, err_out, err_len);
     return rc ? -1 : 0;
 }

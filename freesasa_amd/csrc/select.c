@@ -11,7 +11,7 @@
  * chain character, invalid identifiers are ignored with a warning).  The result is a byte mask over
  * the atoms of one structure of a freesasa_ingest_batch; the area of a selection is the masked sum
  * of per-atom SASA (freesasa_gpu_class_sums_dev with the mask as class gives it on the device).
- * Host code only.
+ * Host code only; freesasa_ingest_selection_compile (below) turns a set of commands into a program that kernels run.
  */
 #include "freesasa_ingest.h"
 
@@ -20,6 +20,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "hostfault.h"
+#include "select_program.h"
 
 /* ------------------------------------------------------------------ lexer */
 
@@ -389,6 +390,142 @@ int freesasa_ingest_select(const freesasa_ingest_batch *b, int structure, const 
     if (rc) return FREESASA_INGEST_SELECT_FAIL;
     snprintf(name_out, FREESASA_INGEST_MAX_SELECTION_NAME + 1, "%.50s", name);
     return c.warn ? FREESASA_INGEST_SELECT_WARN : (int)c.n;
+}
+
+/* ------------------------------------------------------------------ compiled selection sets (select_program.h)
+ * The same lexer, parser and rules; the tree of every command flattened into one postfix program that a kernel runs per
+ * atom (select_kernels.h).  freesasa_ingest_select above is what the program is held against. */
+
+struct freesasa_ingest_selection {
+    int n, n_words, flags, depth;
+    char name[SEL_MAX_SELECTIONS][FREESASA_INGEST_MAX_SELECTION_NAME + 1];
+    freesasa_sel_word words[SEL_MAX_WORDS];
+};
+
+typedef struct { freesasa_ingest_selection *s; int warn, too_long, depth; } comp_t;
+
+static void emit(comp_t *c, uint32_t op, uint32_t a, uint32_t b)
+{
+    freesasa_ingest_selection *s = c->s;
+    if (s->n_words >= SEL_MAX_WORDS) { c->too_long = 1; return; }
+    freesasa_sel_word *w = &s->words[s->n_words++];
+    w->op = op; w->a = a; w->b = b; w->c = 0;
+    if (op == SEL_OP_AND || op == SEL_OP_OR || op == SEL_OP_END) --c->depth;
+    else if (op != SEL_OP_NOT && ++c->depth > s->depth) s->depth = c->depth;
+}
+
+/* select_id: an id that valid_id refuses is skipped with a warning; the others compare with a trimmed field */
+static void comp_id(comp_t *c, int parent, const expr *e)
+{
+    if (!valid_id(parent, e)) { c->warn = 1; emit(c, SEL_OP_FALSE, 0, 0); return; }
+    if (parent == E_CHAIN) { emit(c, SEL_OP_CHAIN, (unsigned char)e->value[0], 0); return; }
+    const size_t n = strlen(e->value);
+    if (n > 6) { emit(c, SEL_OP_FALSE, 0, 0); return; } /* (a number longer than the number field: equals no field) */
+    uint64_t key = 0;
+    for (size_t i = 0; i < n; ++i) key |= (uint64_t)(unsigned char)e->value[i] << (8 * i);
+    const uint32_t op = parent == E_NAME ? SEL_OP_NAME : parent == E_SYMBOL ? SEL_OP_SYMBOL : parent == E_RESN ? SEL_OP_RESN : SEL_OP_RESI;
+    emit(c, op, (uint32_t)key, (uint32_t)(key >> 32));
+}
+
+/* select_range: its type checks, its bounds */
+static void comp_range(comp_t *c, int type, int parent, const expr *l, const expr *r)
+{
+    int bad;
+    if (parent == E_RESI) bad = (l && l->type != E_NUMBER) || (r && r->type != E_NUMBER);
+    else bad = l->type != r->type || (l->type == E_ID && (strlen(l->value) > 1 || strlen(r->value) > 1));
+    if (bad) { c->warn = 1; emit(c, SEL_OP_FALSE, 0, 0); return; }
+    if (parent == E_RESI) {
+        c->s->flags |= SEL_FLAG_RESI_RANGE;
+        if (type == E_RANGE_OPEN_L) { c->s->flags |= SEL_FLAG_OPEN; emit(c, SEL_OP_RESI_OPEN_L, 0, (uint32_t)atoi(r->value)); }
+        else if (type == E_RANGE_OPEN_R) { c->s->flags |= SEL_FLAG_OPEN; emit(c, SEL_OP_RESI_OPEN_R, (uint32_t)atoi(l->value), 0); }
+        else emit(c, SEL_OP_RESI_RANGE, (uint32_t)atoi(l->value), (uint32_t)atoi(r->value));
+    } else if (l->type == E_NUMBER) {
+        emit(c, SEL_OP_CHAIN_RANGE, (uint32_t)atoi(l->value), (uint32_t)atoi(r->value)); /* ("chain 1-5": the character's code in 1..5) */
+    } else {
+        emit(c, SEL_OP_CHAIN_RANGE, (uint32_t)(int)l->value[0], (uint32_t)(int)r->value[0]);
+    }
+}
+
+/* select_list: the items in its order, joined by or (*count: items so far) */
+static void comp_list(comp_t *c, int parent, const expr *e, int *count)
+{
+    if (e->type == E_PLUS) { comp_list(c, parent, e->l, count); comp_list(c, parent, e->r, count); return; }
+    if (e->type == E_RANGE || e->type == E_RANGE_OPEN_L || e->type == E_RANGE_OPEN_R) comp_range(c, e->type, parent, e->l, e->r);
+    else comp_id(c, parent, e);
+    if ((*count)++) emit(c, SEL_OP_OR, 0, 0);
+}
+
+static void comp_expr(comp_t *c, const expr *e)
+{
+    switch (e->type) {
+    case E_RESN: case E_RESI: case E_SYMBOL: case E_NAME: case E_CHAIN: {
+        int count = 0;
+        comp_list(c, e->type, e->l, &count);
+        break;
+    }
+    case E_NOT: comp_expr(c, e->r); emit(c, SEL_OP_NOT, 0, 0); break;
+    default: comp_expr(c, e->l); comp_expr(c, e->r); emit(c, e->type == E_AND ? SEL_OP_AND : SEL_OP_OR, 0, 0); break;
+    }
+}
+
+static freesasa_ingest_selection *sel_fail(freesasa_ingest_selection *s, char *err, int err_len, const char *fmt, const char *arg)
+{
+    if (err && err_len > 0) snprintf(err, (size_t)err_len, fmt, arg);
+    free(s);
+    return NULL;
+}
+
+freesasa_ingest_selection *freesasa_ingest_selection_compile(const char *const *commands, int n_commands, int *rc_out, char *err, int err_len)
+{
+    if (err && err_len > 0) err[0] = '\0';
+    if (!commands || n_commands < 1) return sel_fail(NULL, err, err_len, "%s", "no selection commands given");
+    for (int k = 0; rc_out && k < n_commands; ++k) rc_out[k] = 0;
+    if (n_commands > SEL_MAX_SELECTIONS) return sel_fail(NULL, err, err_len, "%s", "more than 64 selections in one set");
+    freesasa_ingest_selection *s = hf_calloc(1, sizeof *s);
+    if (!s) return sel_fail(NULL, err, err_len, "%s", "out of memory (selection set)");
+    for (int k = 0; k < n_commands; ++k) {
+        const char *command = commands[k];
+        parser ps; /* (the head of a command as freesasa_ingest_select reads it) */
+        memset(&ps, 0, sizeof ps);
+        expr *e = NULL;
+        char name[64] = "";
+        if (command) {
+            ps.lx.s = command; ps.lx.len = strlen(command);
+            advance(&ps);
+            if (ps.cur.type == K_SELID) {
+                snprintf(name, sizeof name, "%s", ps.cur.text);
+                advance(&ps);
+                if (ps.cur.type == K_COMMA) { advance(&ps); e = parse_or(&ps); }
+            }
+        }
+        if (!e || ps.err || ps.cur.type != K_END) {
+            free_expr(e);
+            if (rc_out) rc_out[k] = FREESASA_INGEST_SELECT_FAIL;
+            return sel_fail(s, err, err_len, "cannot parse selection '%.200s'", command ? command : "(null)");
+        }
+        comp_t c;
+        c.s = s; c.warn = 0; c.too_long = 0; c.depth = 0;
+        comp_expr(&c, e);
+        emit(&c, SEL_OP_END, (uint32_t)k, 0);
+        free_expr(e);
+        if (c.too_long) return sel_fail(s, err, err_len, "the selection set is longer than a program of 4096 words (at '%.200s')", command);
+        if (s->depth > SEL_MAX_DEPTH) return sel_fail(s, err, err_len, "selection '%.200s' is nested deeper than 64 levels", command);
+        if (c.warn && rc_out) rc_out[k] = FREESASA_INGEST_SELECT_WARN;
+        snprintf(s->name[k], sizeof s->name[k], "%.50s", name);
+        s->n = k + 1;
+    }
+    return s;
+}
+
+int freesasa_ingest_selection_count(const freesasa_ingest_selection *s) { return s ? s->n : 0; }
+const char *freesasa_ingest_selection_name(const freesasa_ingest_selection *s, int k) { return s && k >= 0 && k < s->n ? s->name[k] : NULL; }
+void freesasa_ingest_selection_free(freesasa_ingest_selection *s) { free(s); }
+const void *freesasa_ingest_selection_program(const freesasa_ingest_selection *s, int *n_words, int *flags)
+{
+    if (!s) return NULL;
+    if (n_words) *n_words = s->n_words;
+    if (flags) *flags = s->flags;
+    return s->words;
 }
 
 /* ------------------------------------------------------------------ chain groups (include/freesasa_ingest.h) */

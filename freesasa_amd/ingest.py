@@ -185,6 +185,23 @@ def _proto():
     return L
 
 
+def _selection_proto():
+    """the freesasa_ingest_selection_* entries (bound on first use: a library built before them still loads)"""
+    L = _proto()
+    if not getattr(L, "_selection_ready", False):
+        L.freesasa_ingest_selection_compile.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_int]
+        L.freesasa_ingest_selection_compile.restype = C.c_void_p
+        L.freesasa_ingest_selection_count.argtypes = [C.c_void_p]
+        L.freesasa_ingest_selection_name.argtypes = [C.c_void_p, C.c_int]
+        L.freesasa_ingest_selection_name.restype = C.c_char_p
+        L.freesasa_ingest_selection_free.argtypes = [C.c_void_p]
+        L.freesasa_ingest_selection_free.restype = None
+        L.freesasa_ingest_selection_program.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.freesasa_ingest_selection_program.restype = C.c_void_p
+        L._selection_ready = True
+    return L
+
+
 def _finish(L, rc, cb):
     if rc:
         raise RuntimeError(f"freesasa_ingest failed with code {rc}")
@@ -232,6 +249,55 @@ class Classifier:
             if self._h:
                 _proto().freesasa_ingest_classifier_free(self._h)
                 self._h = None
+        except Exception:
+            pass
+
+
+class Selection:
+    """A compiled set of 1 .. 64 selections (freesasa_ingest_selection_*): the commands of the reference's --select
+    ("name, resn ala+arg and not chain B") as one program that kernels run per atom (freesasa_amd.select_batch,
+    freesasa_amd.sweep_files_select).  .names (cut to 50 characters), .warned (per command: parts of it are ignored, as
+    Batch.select reports).  Raises ValueError naming the command that does not parse, or the limit a set exceeds (64
+    selections, 4096 program words, 64 levels of nesting); MemoryError when the library is out of memory."""
+
+    def __init__(self, commands):
+        if isinstance(commands, (str, bytes)):
+            commands = [commands]
+        self.commands = [c.decode() if isinstance(c, bytes) else str(c) for c in commands]
+        L = _selection_proto()
+        n = len(self.commands)
+        arr = (C.c_char_p * max(n, 1))(*[c.encode() for c in self.commands])
+        rc = (C.c_int * max(n, 1))()
+        err = C.create_string_buffer(512)
+        self._h = None
+        h = L.freesasa_ingest_selection_compile(arr, n, rc, err, len(err))
+        if not h:
+            msg = err.value.decode(errors="replace") or "selection set rejected"
+            if msg.startswith("out of memory"):
+                raise MemoryError(msg)
+            raise ValueError(msg)
+        self._h = C.c_void_p(h)
+        self.names = [L.freesasa_ingest_selection_name(self._h, k).decode(errors="replace") for k in range(n)]
+        self.warned = [rc[k] == -2 for k in range(n)]
+
+    def __len__(self):
+        return len(self.names)
+
+    @property
+    def handle(self):
+        """the freesasa_ingest_selection * (valid until close())"""
+        if not self._h:
+            raise ValueError("the selection set is closed")
+        return self._h
+
+    def close(self):
+        if self._h:
+            _selection_proto().freesasa_ingest_selection_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass
 

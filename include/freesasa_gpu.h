@@ -303,6 +303,38 @@ int freesasa_gpu_sweep_files_residues(const char *const *paths, int n_paths, int
                                       const int *devices, int n_devices, const struct freesasa_ingest_classifier *classifier,
                                       freesasa_gpu_residue_table *table_out, char *err, int err_len);
 void freesasa_gpu_residue_table_free(freesasa_gpu_residue_table *table);
+/* SELECTION AREAS on the device: the reference's --select (src/selection.c:683-742) for a set of up to 64 selections compiled
+   once (freesasa_ingest_selection_compile, include/freesasa_ingest.h).  A kernel runs the set's program for every atom - its
+   name and element symbol, the number, chain and name labels of its residue (the residue's first atom's, as
+   freesasa_ingest_select reads them), its structure's first and last residue number for the open ranges - and leaves one
+   64-bit word per atom, bit k = selection k holds it; a second kernel sums the per-atom areas under every mask per
+   structure, in the order of the class sums: an area equals element [1] of freesasa_gpu_class_sums_dev with the
+   selection's 0/1 mask as class, bit for bit.
+   _select_batch: a LOADED batch and per-atom areas the caller holds on the host (e.g. from freesasa_gpu_calc_batch) ->
+   area_out / atoms_out [n_structs * n_sel] (structure-major: the area and the number of selected atoms; 0 for a structure
+   without atoms, as freesasa_ingest_select returns 0 for it) and, unless NULL, bits_out [n_atoms], the mask words.
+   Labels, keys and areas go up, the kernels run, the results come back; on a pooled context of `device` (-1: any).
+   _sweep_files_select: the file sweep with selections - the arguments of freesasa_gpu_sweep_files_residues with a selection
+   set in place of the table.  Totals, class sums, atom counts and status are exactly freesasa_gpu_sweep_files_classified's;
+   sel_area_out / sel_atoms_out [n_paths * n_sel] are file-major, 0 for a file that failed to load or kept no atoms.  The
+   per-atom areas never leave the device: the two kernels run behind the batch's tile kernels on its stream and their
+   results ride in front of the batch's one synchronisation.  With FREESASA_INGEST_PARSE_ON_DEVICE the atoms' keys and the
+   residues are built on the device (csrc/gpu_parse.hip: kp_atom_keys, kp_res_*); files the host parser read - all of them
+   without that option, the refused ones with it - have theirs uploaded (8 bytes per atom, 22 per residue).
+   Both return 0 / -1 with the message in err.
+   Not offered: a done-list / resumable form, the cache sweep (a cache read brings no names or residue arrays), selections
+   in the trajectory drivers. */
+struct freesasa_ingest_selection;
+struct freesasa_ingest_batch;
+int freesasa_gpu_select_batch(const struct freesasa_ingest_batch *batch, const struct freesasa_ingest_selection *sel,
+                              const double *sasa, double *area_out, long long *atoms_out, unsigned long long *bits_out,
+                              int device, char *err, int err_len);
+int freesasa_gpu_sweep_files_select(const char *const *paths, int n_paths, int ingest_options, int n_threads,
+                                    int alg, double probe_radius, int resolution, long long batch_atoms,
+                                    double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out,
+                                    const int *devices, int n_devices, const struct freesasa_ingest_classifier *classifier,
+                                    const struct freesasa_ingest_selection *sel,
+                                    double *sel_area_out, long long *sel_atoms_out, char *err, int err_len);
 int freesasa_gpu_sweep_cache_devices(const char *cache_path, int alg, double probe_radius, int resolution, long long batch_atoms,
                                      double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out, int n_out,
                                      const int *devices, int n_devices, int lanes_per_device, char *err, int err_len);

@@ -191,6 +191,29 @@ int freesasa_ingest_cache_read_atoms(const freesasa_ingest_cache *cache, int64_t
 int freesasa_ingest_select(const freesasa_ingest_batch *batch, int structure, const char *command,
                            char name_out[FREESASA_INGEST_MAX_SELECTION_NAME + 1], unsigned char *mask_out);
 
+/* A COMPILED set of selections, for the device (include/freesasa_gpu.h: freesasa_gpu_select_batch,
+ * freesasa_gpu_sweep_files_select): the same lexer, grammar and rules, every command's tree flattened into one postfix
+ * program of fixed-size words that a kernel runs per atom.  What the command alone decides - upper-casing, the ids and
+ * ranges freesasa_ingest_select ignores with a warning, atoi of the bounds, the packing of an id into an integer key - is
+ * decided here; the open ends of "resi -N" / "resi N-" stay operands the structure fills in.
+ *   _compile: n_commands (1 .. 64) commands -> the set, or NULL with the reason in err.  rc_out [n_commands] (may be
+ *     NULL): 0, FREESASA_INGEST_SELECT_WARN (parts of the command are ignored, as freesasa_ingest_select ignores them)
+ *     or, for the command that does not parse (err quotes it; the whole compile fails), FREESASA_INGEST_SELECT_FAIL.
+ *     Limits, refused with a message and never truncated: 64 selections per set (one 64-bit mask word per atom), 4096
+ *     program words per set (a word per id, range and operator), 64 levels of operand nesting (the evaluation stack).
+ *   _name: selection k's name, cut to FREESASA_INGEST_MAX_SELECTION_NAME characters (owned by the set).
+ * The set is immutable: threads and sweeps share it.  _free(NULL) is a no-op. */
+typedef struct freesasa_ingest_selection freesasa_ingest_selection;
+freesasa_ingest_selection *freesasa_ingest_selection_compile(const char *const *commands, int n_commands, int *rc_out,
+                                                             char *err, int err_len);
+int freesasa_ingest_selection_count(const freesasa_ingest_selection *selection);
+const char *freesasa_ingest_selection_name(const freesasa_ingest_selection *selection, int k);
+void freesasa_ingest_selection_free(freesasa_ingest_selection *selection);
+/* The set's program, for the engine and for tests: n_words words of 16 bytes (four uint32: opcode and operands; the
+ * format is csrc/select_program.h's and may change between versions), *flags what the kernel has to prepare per atom.
+ * Owned by the set. */
+const void *freesasa_ingest_selection_program(const freesasa_ingest_selection *selection, int *n_words, int *flags);
+
 /* Chain groups of every structure of a batch, as group ids for freesasa_gpu_groups_dev (include/freesasa_gpu.h): the
  * reference CLI's --chain-groups / --separate-chains (src/main.cc:261-312).  An atom's chain is its residue's res_chain.
  *   spec, flags 0: the short syntax "AB+C" (ref: src/main.cc:389-424): characters [A-Za-z0-9] and '+', one character per

@@ -3,7 +3,7 @@
 per-structure totals (BASELINE configs[3] in miniature; SURVEY §8f N1 + the batch entry point).
 
     python tools/sweep.py [--replicate N] [--threads T] [--batch-atoms A] [--devices 0,1,...] [--done FILE] [--cache FILE]
-                          [--residues OUT.tsv] [paths ...]
+                          [--residues OUT.tsv] [--select CMD ... --select-out OUT.tsv] [paths ...]
 
 Without paths it sweeps the PDB fixtures under tests/golden/pdb, replicated N times.  Loading of
 batch k+1 runs on host threads while the GPU computes batch k.  Prints one JSON line with the
@@ -12,7 +12,9 @@ single-thread rate on the same files.  --devices: the GPUs that share the batche
 default: every visible device; entries may repeat); --done: a done-list, so that an interrupted sweep resumes — on any
 device list; --cache FILE: sweep the binary cache FILE instead (written first from the files if it does not exist);
 --residues OUT.tsv: the per-residue table of all files (freesasa_gpu_sweep_files_residues): file, chain, number, name, the
-five absolute areas (total, main chain, side chain, polar, apolar) and the five relative ones, N/A where there is none."""
+five absolute areas (total, main chain, side chain, polar, apolar) and the five relative ones, N/A where there is none;
+--select CMD (repeatable, up to 64) with --select-out OUT.tsv: the reference's --select for all files
+(freesasa_gpu_sweep_files_select): file, then one area column per selection name."""
 import argparse
 import glob
 import json
@@ -39,6 +41,14 @@ def write_residues(path, paths, table):
                 fh.write("\t".join(cols) + "\n")
 
 
+def write_selections(path, paths, names, areas):
+    """one line per file: its path, then the area of every selection"""
+    with open(path, "w") as fh:
+        fh.write("\t".join(["file"] + list(names)) + "\n")
+        for k, p in enumerate(paths):
+            fh.write("\t".join([p] + [f"{v:.2f}" for v in areas[k]]) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("paths", nargs="*")
@@ -52,14 +62,26 @@ def main():
     ap.add_argument("--done", default=None, help="done-list file: resume an interrupted sweep")
     ap.add_argument("--cache", default=None, help="binary cache file to sweep (created from the files when missing)")
     ap.add_argument("--residues", default=None, metavar="OUT.tsv", help="write the per-residue table of all files (not with --done or --cache)")
+    ap.add_argument("--select", action="append", default=[], metavar="CMD", help='a selection in the reference\'s language ("name, resn ala+arg and not chain B"); repeatable, up to 64')
+    ap.add_argument("--select-out", default=None, metavar="OUT.tsv", help="write the selections' areas of all files (not with --done, --cache or --no-gpu)")
     ap.add_argument("--engine", choices=["python", "c"], default="c",
                     help="c: freesasa_gpu_sweep_files (loader thread || GPU inside the library); "
                          "python: the same pipeline written with the two-step Python API")
     args = ap.parse_args()
     if args.residues and (args.done or args.cache or args.no_gpu or args.engine != "c"):
         ap.error("--residues goes with the C engine's plain file sweep only (no --done, --cache, --no-gpu, --engine python)")
+    if bool(args.select) != bool(args.select_out):
+        ap.error("--select and --select-out go together")
+    if args.select and (args.done or args.cache or args.no_gpu or args.residues or args.engine != "c"):
+        ap.error("--select goes with the C engine's plain file sweep only (no --done, --cache, --no-gpu, --residues, --engine python)")
     import freesasa_amd as fa
     from freesasa_amd import ingest
+    selection = None
+    if args.select:
+        try:
+            selection = ingest.Selection(args.select)
+        except ValueError as e:
+            ap.error(str(e))
 
     paths = args.paths or [p for p in sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "pdb", "*.pdb")))
                            if os.path.getsize(p) > 10_000]
@@ -103,6 +125,12 @@ def main():
                                                                       batch_atoms=args.batch_atoms, devices=devices, ingest_options=popt)
             write_residues(args.residues, paths, table)
             out["residues"] = int(table.n_residues)
+        elif selection is not None:
+            totals, _, atoms, status, areas, counts = fa.sweep_files_select(paths, selection, fa.LEE_RICHARDS, resolution=args.slices, n_threads=args.threads,
+                                                                            batch_atoms=args.batch_atoms, devices=devices, ingest_options=popt)
+            write_selections(args.select_out, paths, selection.names, areas)
+            out["selections"] = len(selection)
+            out["selected_atoms"] = int(counts.sum())
         else:
             totals, _, atoms, status = fa.sweep_files(paths, fa.LEE_RICHARDS, resolution=args.slices, n_threads=args.threads,
                                                       batch_atoms=args.batch_atoms, class_sums=True, devices=devices, ingest_options=popt)
