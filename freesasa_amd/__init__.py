@@ -455,6 +455,102 @@ def sweep_files_select(paths, selection, alg=LEE_RICHARDS, probe=1.4, resolution
     return totals, cls, atoms, status, areas, counts
 
 
+class GroupTableC(C.Structure):
+    """freesasa_gpu_group_table (include/freesasa_gpu.h)."""
+    _fields_ = [("n_files", C.c_int32), ("n_groups", C.c_int64), ("group_offsets", _lp), ("group_atoms", C.POINTER(C.c_int32)),
+                ("areas", _dp), ("chain", C.POINTER(C.c_char))]
+
+
+class GroupTable:
+    """numpy copy of a freesasa_gpu_group_table: file k owns groups [group_offsets[k], group_offsets[k + 1]); areas columns are
+    isolated, complex, buried; chain: the group's label (separate chains: the run's; a spec: the first the spec names)."""
+
+    def __init__(self, ct):
+        n, ng = int(ct.n_files), int(ct.n_groups)
+
+        def arr(ptr, count, dtype):
+            if count == 0:
+                return np.zeros(0, dtype=dtype)
+            nbytes = count * np.dtype(dtype).itemsize    # (one copy: a view of the C block, copied before the block is freed)
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_ubyte)), (nbytes,)).view(dtype).copy()
+        self.n_files, self.n_groups = n, ng
+        self.group_offsets = arr(ct.group_offsets, n + 1, np.int64)
+        self.group_atoms = arr(ct.group_atoms, ng, np.int32)
+        self.areas = arr(ct.areas, 3 * ng, np.float64).reshape(ng, 3)
+        self.chain_raw = arr(ct.chain, ng, "S4")
+
+    @property
+    def chain(self):
+        return [v.decode() for v in self.chain_raw.tolist()]
+
+    def file(self, k):
+        """the slice of file k's groups"""
+        return slice(int(self.group_offsets[k]), int(self.group_offsets[k + 1]))
+
+
+def _groups_proto(L):
+    i32 = C.POINTER(C.c_int32)
+    L.freesasa_gpu_sweep_files_groups.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                                  C.c_longlong, _dp, _dp, _lp, _ip, _ip, C.c_int, C.c_void_p, C.c_char_p, C.c_int,
+                                                  _ip, C.POINTER(GroupTableC), C.c_char_p, C.c_int]
+    L.freesasa_gpu_group_table_free.argtypes = [C.POINTER(GroupTableC)]
+    L.freesasa_gpu_group_table_free.restype = None
+    L.freesasa_gpu_chain_group_ids.argtypes = [C.c_void_p, C.c_char_p, C.c_int, i32, i32, i32, C.c_int, C.c_char_p, C.c_int]
+    return L
+
+
+def _group_flags(long_syntax, separate_chains):
+    from . import ingest
+    return (ingest.GROUPS_LONG if long_syntax else 0) | (ingest.SEPARATE_CHAINS if separate_chains else 0)
+
+
+def chain_group_ids(batch, spec=None, separate_chains=False, long_syntax=False, device=0):
+    """freesasa_gpu_chain_group_ids(): Batch.chain_groups made by the device's kernel -> (group[n_atoms] int32,
+    n_groups[n_structs], status[n_structs]).  A bad spec raises RuntimeError with freesasa_ingest_chain_groups's message."""
+    L = _groups_proto(lib())
+    group = np.empty(batch.n_atoms, dtype=np.int32)
+    n_groups = np.empty(batch.n_structs, dtype=np.int32)
+    status = np.empty(batch.n_structs, dtype=np.int32)
+    err = C.create_string_buffer(512)
+    i32 = C.POINTER(C.c_int32)
+    cb = batch._as_c()
+    ret = L.freesasa_gpu_chain_group_ids(C.byref(cb), spec.encode() if spec is not None else None, _group_flags(long_syntax, separate_chains),
+                                         group.ctypes.data_as(i32), n_groups.ctypes.data_as(i32), status.ctypes.data_as(i32), device, err, 512)
+    if ret:
+        raise RuntimeError("freesasa_gpu_chain_group_ids: " + err.value.decode())
+    return group, n_groups, status
+
+
+def sweep_files_groups(paths, spec=None, separate_chains=False, long_syntax=False, alg=LEE_RICHARDS, probe=1.4, resolution=20,
+                       ingest_options=0, n_threads=0, batch_atoms=0, device=-1, devices=None, classifier=None):
+    """freesasa_gpu_sweep_files_groups(): sweep_files plus the chain groups of every file (the reference's --chain-groups SPEC,
+    long_syntax=True: --chain-groups-long, or --separate-chains) -> (totals[n], class_sums[n,3], n_atoms[n], status[n],
+    group_status[n], table: a GroupTable).  The group ids are made on the device and stay there with the per-atom areas; a
+    file whose group_status is not 0 (its load failed, or ingest.EGROUP: a chain the spec names is missing) owns no rows."""
+    from . import ingest
+    L = _groups_proto(lib())
+    n = len(paths)
+    arr = (C.c_char_p * n)(*[str(p).encode() for p in paths])
+    totals, atoms, status = np.zeros(n), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+    gstatus = np.zeros(n, dtype=np.int32)
+    cls = np.zeros((n, 3))
+    err = C.create_string_buffer(512)
+    keep, dp_, nd = _devs(devices, device)
+    ct = GroupTableC()
+    ret = L.freesasa_gpu_sweep_files_groups(arr, n, ingest_options, n_threads, alg, probe, resolution, batch_atoms,
+                                            totals.ctypes.data_as(_dp), cls.ctypes.data_as(_dp), atoms.ctypes.data_as(_lp),
+                                            status.ctypes.data_as(_ip), dp_, nd, ingest._handle(classifier),
+                                            spec.encode() if spec is not None else None, _group_flags(long_syntax, separate_chains),
+                                            gstatus.ctypes.data_as(_ip), C.byref(ct), err, 512)
+    if ret:
+        raise RuntimeError("freesasa_gpu_sweep_files_groups: " + err.value.decode())
+    try:
+        table = GroupTable(ct)
+    finally:
+        L.freesasa_gpu_group_table_free(C.byref(ct))
+    return totals, cls, atoms, status, gstatus, table
+
+
 def sweep_files_resumable(paths, done_path, alg=LEE_RICHARDS, probe=1.4, resolution=20, ingest_options=0, n_threads=0,
                           batch_atoms=0, max_new_batches=0, device=-1, devices=None, classifier=None):
     """freesasa_gpu_sweep_files_resumable(): like sweep_files with a done-list at done_path (+ done_path.bin):

@@ -12,7 +12,8 @@
  *                      (device lists, the host budget, DoneList)
  *   gpu_sweep.hip      the file sweep (host or device parser, done-list, per-residue table, selections) and the device parser's entries
  *   gpu_parse.hip      the device-side PDB / mmCIF parser: its kernels and their host driver (gpu_parse.h)
- *   gpu_groups.hip     chain groups: a batch and every group of it cut out as a structure of its own, in one batch
+ *   gpu_groups.hip     chain groups: a batch and every group of it cut out as a structure of its own, in one batch; the
+ *                      group ids made on the device
  */
 #ifndef FREESASA_AMD_ENGINE_INTERNAL_H
 #define FREESASA_AMD_ENGINE_INTERNAL_H
@@ -75,6 +76,9 @@ hipError_t kl_grp_count(const sasa::GrpArgs &a, hipStream_t st);
 hipError_t kl_grp_rank(const sasa::GrpArgs &a, hipStream_t st);
 hipError_t kl_grp_finish(const sasa::GrpArgs &a, hipStream_t st);
 hipError_t kl_grp_totals(const sasa::GrpArgs &a, hipStream_t st);
+/* group ids made on the device (group_kernels.h): one wave per structure; the label of every group of separate chains */
+hipError_t kl_gid_struct(const sasa::GidArgs &a, hipStream_t st);
+hipError_t kl_gid_label(const sasa::GidLabelArgs &a, hipStream_t st);
 
 /* selection areas (select_kernels.h): the mask word of every atom (one thread per atom), the masked sums (one workgroup per
    structure and SEL_G selections) */
@@ -133,6 +137,9 @@ struct freesasa_gpu_ctx {
     DevBuf h_xyz, h_radii, h_sasa, h_counts, h_totals, h_group, h_iso, h_gtot;
     /* chain groups (gpu_groups.hip): offsets and group bases, keys, counts, cursors, the combined batch, its results */
     DevBuf g_meta, g_key, g_count, g_cursor, g_xyz, g_radii, g_src, g_sasa, g_gath, g_tot, g_tot2;
+    /* group ids made on the device: the spec's label table, the per-structure words (offsets, status in, n_groups and group
+       status out), the groups' labels */
+    DevBuf gi_tab, gi_words, gi_label;
     void *stage_in = nullptr, *stage_out = nullptr; /* page-locked host staging of freesasa_gpu_calc_batch_pipelined */
     size_t stage_in_cap = 0, stage_out_cap = 0;
     void *res_stage = nullptr; /* page-locked: a batch's per-residue areas and arrays on their way to the host (gpu_sweep.hip) */
@@ -195,6 +202,29 @@ int residue_areas_resident(freesasa_gpu_ctx *c, const double *d_sasa, const unsi
    mask words and the results (c->parse[PBUF_SEL_*]; sa.bits / sa.area / sa.count say where) and enqueues sel_mask and
    sel_sums on the context's stream.  No synchronisation.  (gpu_ops.hip) */
 int select_resident(freesasa_gpu_ctx *c, const struct freesasa_ingest_selection *sel, sasa::SelArgs &sa);
+
+/* ------------------------------------------------------------------ chain groups for the file sweep (gpu_groups.hip) */
+
+/* a chain-group request as the device takes it: freesasa_ingest_chain_groups_parse's labels sorted by their value as a word */
+struct GroupSpec {
+    bool separate = false;
+    int n_groups = 0;                 /* the spec's (0: separate chains) */
+    std::vector<uint32_t> lab;        /* ascending */
+    std::vector<int32_t> lab_group;
+    std::vector<uint32_t> first_label; /* [n_groups] the first label the spec names for the group */
+};
+int group_spec_parse(const char *spec, int flags, GroupSpec *out, char *err_out, int err_len); /* 0 / -1 with select.c's message */
+/* The ids kernel on arrays that are on the device: the caller fills offsets, residues, labels, status and the outputs of
+   `ga`; this uploads the spec's table (c->gi_tab; `gs` outlives the stream's work) and enqueues the kernel.  No synchronisation. */
+int group_ids_resident(freesasa_gpu_ctx *c, const GroupSpec &gs, sasa::GidArgs &ga);
+/* freesasa_gpu_groups_dev's pipeline on arrays that are on the context's stream already, nothing waited for at its end
+   (inside, the counts come back and run_batch waits as ever).  d_sasa / d_iso / d_totals / d_group_totals may be null;
+   unit_points: the S&R test points (null: made here); counts_out (may be null) receives the atoms of every group.  The
+   combined batch's areas stay in c->g_sasa (the complex's first), its totals in c->g_tot, its offsets in c->offsets, the
+   source atoms in c->g_src. */
+int groups_resident(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
+                    const int32_t *d_group, const int32_t *n_groups, double probe, int resolution, const double *unit_points,
+                    double *d_sasa, double *d_iso, double *d_totals, double *d_group_totals, std::vector<int> *counts_out);
 
 /* ------------------------------------------------------------------ host-side helpers (gpu_hostbatch.hip) */
 

@@ -11,12 +11,17 @@
  *   3. one run_batch        the complex and all its groups share one cell sort and one sequence of tile launches
  *   4. finish               k_grp_finish (areas back to input order), the totals kernels over the groups' complex
  *                           areas, k_grp_totals
+ *
+ * groups_resident is that pipeline for callers whose arrays are on the context's stream (the file sweep, gpu_sweep.hip);
+ * below it, the group ids themselves made on the device from residues and chain labels (k_gid_struct).
  */
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <algorithm>
+#include <utility>
 #include <vector>
 
 #include "engine_internal.h"
@@ -25,18 +30,13 @@ using namespace sasa;
 
 #define GRP_MAX_PER_STRUCT 65535
 
-static int groups_impl(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets,
-                       int n_structs, const int32_t *d_group, const int32_t *n_groups, double probe, int resolution,
-                       double *d_sasa, double *d_iso, double *d_totals, double *d_group_totals)
+static_assert(GID_EGROUP == FREESASA_INGEST_EGROUP && GID_MAX_PER_STRUCT == GRP_MAX_PER_STRUCT && GID_MAX_LABELS == FREESASA_INGEST_MAX_GROUP_LABELS, "group_kernels.h");
+
+/* (engine_internal.h) */
+int groups_resident(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
+                    const int32_t *d_group, const int32_t *n_groups, double probe, int resolution, const double *unit_points,
+                    double *d_sasa, double *d_iso, double *d_totals, double *d_group_totals, std::vector<int> *counts_out)
 {
-    c->err[0] = 0;
-    if (!d_xyz || !d_radii || !offsets || !d_group || !n_groups || !d_sasa || !d_iso) return ctx_fail(c, "null argument");
-    if (alg != 0 && alg != 1) return ctx_fail(c, "unknown algorithm %d", alg);
-    if (n_structs <= 0) return ctx_fail(c, "n_structs must be > 0");
-    if (resolution <= 0) return ctx_fail(c, "resolution must be > 0");
-    if (offsets[0] != 0) return ctx_fail(c, "offsets[0] must be 0");
-    for (int s = 0; s < n_structs; ++s)
-        if (offsets[s + 1] < offsets[s]) return ctx_fail(c, "offsets must be non-decreasing");
     const int64_t n64 = offsets[n_structs];
     if (n64 <= 0) return ctx_fail(c, "empty batch");
     if (n64 > (int64_t)1 << 30) return ctx_fail(c, "batch too large (max 2^30 atoms per call)");
@@ -115,12 +115,13 @@ static int groups_impl(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const 
 
     /* 3. one batch over the complex and its groups */
     std::vector<double> tp;
-    if (alg == 1) {
+    if (alg == 1 && !unit_points) {
         tp.resize(3 * (size_t)resolution);
         freesasa_gpu_test_points(resolution, tp.data());
+        unit_points = tp.data();
     }
     if (run_batch(c, alg == 0, (const double *)c->g_xyz.p, (const double *)c->g_radii.p, comb.data(), (int)NS, probe, resolution,
-                  alg == 1 ? tp.data() : nullptr, (double *)c->g_sasa.p, nullptr, (double *)c->g_tot.p))
+                  alg == 1 ? unit_points : nullptr, (double *)c->g_sasa.p, nullptr, (double *)c->g_tot.p))
         return -1;
 
     /* 4. finish: areas to the caller, each group's complex area reduced like its isolated total (the chunk tables of
@@ -137,7 +138,26 @@ static int groups_impl(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const 
         HIP_TRY(c, kl_totals(pa, c->n_chunks, (int)NS, (const double *)c->g_gath.p, (double *)c->bpart.p, (double *)c->g_tot2.p, st));
     }
     if (d_totals || (G > 0 && d_group_totals)) HIP_TRY(c, kl_grp_totals(ga, st));
-    HIP_TRY(c, hipStreamSynchronize(st)); /* (stream sync 2 of 2 beyond run_batch's: the call is synchronous) */
+    if (counts_out) { cnt.resize((size_t)G); counts_out->swap(cnt); }
+    return 0;
+}
+
+static int groups_impl(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets,
+                       int n_structs, const int32_t *d_group, const int32_t *n_groups, double probe, int resolution,
+                       double *d_sasa, double *d_iso, double *d_totals, double *d_group_totals)
+{
+    c->err[0] = 0;
+    if (!d_xyz || !d_radii || !offsets || !d_group || !n_groups || !d_sasa || !d_iso) return ctx_fail(c, "null argument");
+    if (alg != 0 && alg != 1) return ctx_fail(c, "unknown algorithm %d", alg);
+    if (n_structs <= 0) return ctx_fail(c, "n_structs must be > 0");
+    if (resolution <= 0) return ctx_fail(c, "resolution must be > 0");
+    if (offsets[0] != 0) return ctx_fail(c, "offsets[0] must be 0");
+    for (int s = 0; s < n_structs; ++s)
+        if (offsets[s + 1] < offsets[s]) return ctx_fail(c, "offsets must be non-decreasing");
+    if (groups_resident(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe, resolution, nullptr, d_sasa, d_iso,
+                        d_totals, d_group_totals, nullptr))
+        return -1;
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); /* (stream sync 2 of 2 beyond run_batch's: the call is synchronous) */
     return 0;
 }
 
@@ -207,5 +227,107 @@ extern "C" int freesasa_gpu_calc_groups(const double *xyz, const double *radii, 
         set_err(err_out, err_len, c->err[0] ? c->err : "GPU batch failed");
     }
     return ret;
+    });
+}
+
+/* ------------------------------------------------------------------ group ids made on the device (group_kernels.h) */
+
+/* (engine_internal.h) */
+int group_spec_parse(const char *spec, int flags, GroupSpec *out, char *err_out, int err_len)
+{
+    std::vector<char> labels(4 * (size_t)FREESASA_INGEST_MAX_GROUP_LABELS);
+    std::vector<int32_t> groups((size_t)FREESASA_INGEST_MAX_GROUP_LABELS);
+    int n_lab = 0;
+    const int G = freesasa_ingest_chain_groups_parse(spec, flags, labels.data(), groups.data(), &n_lab, err_out, err_len);
+    if (G < 0) return -1;
+    out->separate = (flags & FREESASA_INGEST_SEPARATE_CHAINS) != 0;
+    out->n_groups = G;
+    out->first_label.assign((size_t)G, 0);
+    std::vector<char> named((size_t)G, 0);
+    std::vector<std::pair<uint32_t, int32_t>> tab((size_t)n_lab);
+    for (int i = 0; i < n_lab; ++i) {
+        uint32_t w;
+        memcpy(&w, labels.data() + 4 * (size_t)i, 4);
+        tab[(size_t)i] = {w, groups[(size_t)i]};
+        if (!named[(size_t)groups[(size_t)i]]) { named[(size_t)groups[(size_t)i]] = 1; out->first_label[(size_t)groups[(size_t)i]] = w; }
+    }
+    std::sort(tab.begin(), tab.end());
+    out->lab.resize((size_t)n_lab); out->lab_group.resize((size_t)n_lab);
+    for (int i = 0; i < n_lab; ++i) { out->lab[(size_t)i] = tab[(size_t)i].first; out->lab_group[(size_t)i] = tab[(size_t)i].second; }
+    return 0;
+}
+
+/* (engine_internal.h) */
+int group_ids_resident(freesasa_gpu_ctx *c, const GroupSpec &gs, GidArgs &ga)
+{
+    const size_t n_lab = gs.lab.size();
+    if (ga.n_structs <= 0 || (!gs.separate && n_lab == 0)) return ctx_fail(c, "bad argument");
+    ga.n_lab = (int)n_lab; ga.n_spec_groups = gs.n_groups;
+    if (n_lab > 0) {
+        if (ensure(c, c->gi_tab, 8 * n_lab)) return -1;
+        ga.lab = (const uint32_t *)c->gi_tab.p; ga.lab_group = (const int32_t *)(ga.lab + n_lab);
+        HIP_TRY(c, hipMemcpyAsync(c->gi_tab.p, gs.lab.data(), 4 * n_lab, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync((char *)c->gi_tab.p + 4 * n_lab, gs.lab_group.data(), 4 * n_lab, hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(c, kl_gid_struct(ga, c->stream));
+    return 0;
+}
+
+extern "C" int freesasa_gpu_chain_group_ids(const freesasa_ingest_batch *b, const char *spec, int flags, int32_t *group_out,
+                                            int32_t *n_groups_out, int32_t *status_out, int device, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (!b || !group_out || !n_groups_out || !status_out) return set_err(err_out, err_len, "null argument");
+    return guarded(err_out, err_len, [&]() -> int {
+        GroupSpec gs; /* (declared before the lease: freed after its stream is idle) */
+        if (group_spec_parse(spec, flags, &gs, err_out, err_len)) return -1;
+        const int ns = b->n_structs;
+        const int64_t n = b->n_atoms, R = b->n_residues;
+        if (ns < 0 || n < 0 || R < 0 || n > (int64_t)1 << 30 || (n > 0 && (R == 0 || ns == 0))) return set_err(err_out, err_len, "inconsistent batch");
+        for (int k = 0; k < ns; ++k)
+            if (b->offsets[k + 1] < b->offsets[k]) return set_err(err_out, err_len, "structure offsets must be non-decreasing");
+        for (int64_t r = 0; r < R; ++r)
+            if (b->res_first[r + 1] < b->res_first[r]) return set_err(err_out, err_len, "residue offsets must be non-decreasing");
+        if (ns > 0 && (b->offsets[0] != 0 || b->offsets[ns] != n || (R > 0 && (b->res_first[0] != 0 || b->res_first[R] != n))))
+            return set_err(err_out, err_len, "inconsistent batch");
+        if (ns == 0) return 0;
+        if (freesasa_gpu_device_count() <= 0) return set_err(err_out, err_len, "no HIP device available: libfreesasa_amd has no CPU path");
+        std::vector<int32_t> st_in((size_t)ns, 0);
+        if (b->status) memcpy(st_in.data(), b->status, 4 * (size_t)ns);
+        const int64_t zero = 0;
+        PoolLease lease(device);
+        freesasa_gpu_ctx *c = lease.c;
+        if (!c) return set_err(err_out, err_len, "could not create a GPU context");
+        c->err[0] = 0;
+        const int rc = [&]() -> int {
+            HIP_TRY(c, hipSetDevice(c->device));
+            DevBuf *B = c->parse;
+            const size_t b_off = 8 * ((size_t)ns + 1), b_first = 8 * ((size_t)R + 1);
+            if (ensure(c, c->seg, b_off + b_first) || ensure(c, B[PBUF_SEL_LABELS], 4 * (size_t)R + 4) || ensure(c, c->h_group, 4 * (size_t)n + 4) ||
+                ensure(c, c->gi_words, 12 * (size_t)ns))
+                return -1;
+            char *seg = (char *)c->seg.p;
+            int32_t *words = (int32_t *)c->gi_words.p;
+            hipStream_t st = c->stream;
+            HIP_TRY(c, hipMemcpyAsync(seg, b->offsets, b_off, hipMemcpyHostToDevice, st));
+            HIP_TRY(c, hipMemcpyAsync(seg + b_off, R > 0 ? b->res_first : &zero, b_first, hipMemcpyHostToDevice, st));
+            if (R > 0) HIP_TRY(c, hipMemcpyAsync(B[PBUF_SEL_LABELS].p, b->res_chain, 4 * (size_t)R, hipMemcpyHostToDevice, st));
+            HIP_TRY(c, hipMemcpyAsync(words, st_in.data(), 4 * (size_t)ns, hipMemcpyHostToDevice, st));
+            GidArgs ga;
+            memset(&ga, 0, sizeof ga);
+            ga.offsets = (const int64_t *)seg; ga.n_structs = ns;
+            ga.res_first = (const int64_t *)(seg + b_off); ga.n_res = R; ga.n_res_dev = 0;
+            ga.chain_h = (const uint32_t *)B[PBUF_SEL_LABELS].p;
+            ga.status = words; ga.n_groups = words + ns; ga.group_status = words + 2 * (size_t)ns;
+            ga.group = (int32_t *)c->h_group.p;
+            if (group_ids_resident(c, gs, ga)) return -1;
+            if (n > 0) HIP_TRY(c, hipMemcpyAsync(group_out, ga.group, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipMemcpyAsync(n_groups_out, ga.n_groups, 4 * (size_t)ns, hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipMemcpyAsync(status_out, ga.group_status, 4 * (size_t)ns, hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipStreamSynchronize(st));
+            return 0;
+        }();
+        if (rc) { (void)hipStreamSynchronize(c->stream); return set_err(err_out, err_len, c->err[0] ? c->err : "group ids failed"); }
+        return 0;
     });
 }

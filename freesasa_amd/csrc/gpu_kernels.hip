@@ -823,6 +823,27 @@ hipError_t kl_grp_totals(const GrpArgs &a, hipStream_t st)
     return hipGetLastError();
 }
 
+/* group ids made on the device (group_kernels.h): one wave per structure; the labels of separate chains' groups */
+__global__ __launch_bounds__(64) void k_gid_struct(GidArgs a)
+{
+    __shared__ unsigned present[GID_MAX_LABELS / 32];
+    gid_struct(a, present, blockIdx.x, threadIdx.x);
+}
+__global__ __launch_bounds__(GRP_B) void k_gid_label(GidLabelArgs a)
+{
+    gid_label_item(a, blockIdx.x * GRP_B + threadIdx.x);
+}
+hipError_t kl_gid_struct(const GidArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_gid_struct, dim3((unsigned)a.n_structs), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_gid_label(const GidLabelArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_gid_label, dim3((unsigned)((a.n_groups + GRP_B - 1) / GRP_B)), dim3(GRP_B), 0, st, a);
+    return hipGetLastError();
+}
+
 /* selection areas (select_kernels.h): the compiled set per atom, then the masked sums per (structure, SEL_G selections) */
 __global__ __launch_bounds__(SEL_B) void k_sel_mask(SelArgs a)
 {

@@ -150,6 +150,21 @@ struct ResCollector {
     void add(std::unique_ptr<ResBatch> &rb) { std::lock_guard<std::mutex> lk(mu); done.push_back(std::move(rb)); }
 };
 
+/* The group table of freesasa_gpu_sweep_files_groups, collected like the residue table: a block per batch, its groups in the
+   batch's structure order (fstart says where a file's run begins; a file whose group status is not 0 owns none). */
+struct GrpBatch {
+    int first = 0, ns = 0;
+    std::vector<long long> fstart, fcount;  /* [ns] */
+    std::vector<int32_t> atoms;             /* [groups] */
+    std::vector<double> areas;              /* [3 groups] */
+    std::vector<uint32_t> chain;            /* [groups] */
+};
+struct GrpCollector {
+    std::mutex mu;
+    std::vector<std::unique_ptr<GrpBatch>> done;
+    void add(std::unique_ptr<GrpBatch> &gb) { std::lock_guard<std::mutex> lk(mu); done.push_back(std::move(gb)); }
+};
+
 /* what a sweep entry was called with (read-only) */
 struct SweepArgs {
     const char *const *paths; int n_paths, ingest_options, n_threads;
@@ -161,6 +176,8 @@ struct SweepArgs {
     ResCollector *rcol;                               /* (may be NULL) */
     const freesasa_ingest_selection *sel;             /* (may be NULL; never together with rcol) */
     double *sel_area_out; long long *sel_atoms_out;   /* [n_paths * selections] */
+    const GroupSpec *grp;                             /* (may be NULL; never together with rcol or sel) */
+    GrpCollector *gcol; int *group_status_out;        /* [n_paths] */
 };
 /* what the workers of one sweep share */
 struct Sweep {
@@ -219,8 +236,14 @@ struct Work {
     long long R = 0, Rd = 0;              /* residues of the batch, and how many of them are the device's */
     std::vector<double> sel_area;         /* [structures of the batch * selections] on their way back: areas, selected atoms */
     std::vector<long long> sel_count;
+    std::unique_ptr<GrpBatch> gb;         /* chain groups: the batch's block, the words of its structures (status in | n_groups | group status) */
+    std::vector<int32_t> gwords;
     Work(const Sweep &S, int b_) : b(b_), first(S.cut[b_]), ns(S.cut[b_ + 1] - S.cut[b_]), atoms((size_t)ns), status((size_t)ns), host((size_t)ns), atoms64((size_t)ns, 0)
     {
+        if (S.a.gcol) {
+            gb.reset(new GrpBatch);
+            gb->first = first; gb->ns = ns; gb->fstart.assign((size_t)ns, 0); gb->fcount.assign((size_t)ns, 0);
+        }
         if (!S.a.rcol) return;
         rb.reset(new ResBatch);
         rb->first = first; rb->ns = ns; rb->fstart.assign((size_t)ns, 0); rb->fcount.assign((size_t)ns, 0); rb->size(0);
@@ -380,6 +403,87 @@ int select_enqueue(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, int 
     return 0;
 }
 
+/* chain groups, IN PLACE of run_batch: the device's residue count is waited for (it sizes the residue arrays; nothing to wait
+   for when the device parsed nothing), residue boundaries and labels as for the selections, the host parser's chain labels
+   and the structures' status behind them; the ids kernel (group_kernels.h); n_groups and the group status of every structure
+   back (they size the combined batch); then the complex and its groups as ONE batch (groups_resident, gpu_groups.hip).  The
+   groups' atoms, and on the stream their three areas and - separate chains - their labels on the way into w.gb.  Leaves the
+   complex's areas in c->g_sasa and its totals in d_tot. */
+int groups_run(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, int nst, const std::vector<int64_t> &off, std::vector<int64_t> &hrf, double *d_tot)
+{
+    const SweepArgs &a = S.a;
+    const GroupSpec &gs = *a.grp;
+    const long long total = w.total, n_all = off[(size_t)nst];
+    if (c->parse_atoms > 0 && hipStreamSynchronize(c->stream) != hipSuccess) return ctx_fail(c, "stream synchronize failed");
+    const long long Rd = parse_batch_dev_residues_found(c), Rh = hb.b.n_residues, R = Rd + Rh;
+    if (Rd < 0 || R <= 0 || R >= (1LL << 31)) return ctx_fail(c, "bad residue count from the device parser");
+    DevBuf *B = c->parse;
+    if (parse_batch_dev_residues_build(c, (int)Rd, Rh, a.classifier != nullptr)) return -1;
+    const size_t b_off = 8 * ((size_t)nst + 1);
+    if (ensure(c, B[PBUF_SEL_LABELS], 4 * (size_t)Rh + 4) || ensure(c, c->h_group, 4 * (size_t)n_all) || ensure(c, c->gi_words, b_off + 12 * (size_t)nst)) return -1;
+    if (Rh > 0) {
+        hrf.resize((size_t)Rh + 1);
+        for (long long j = 0; j <= Rh; ++j) hrf[(size_t)j] = total + hb.b.res_first[j];
+        if (hipMemcpyAsync((int64_t *)B[PBUF_RES_FIRST].p + Rd, hrf.data(), 8 * ((size_t)Rh + 1), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            hipMemcpyAsync(B[PBUF_SEL_LABELS].p, hb.b.res_chain, 4 * (size_t)Rh, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+            return ctx_fail(c, "host-to-device copy failed");
+    }
+    /* structure k < nd is file k (one the device refused: an empty structure that failed), structure nd + j the j-th file the host read */
+    w.gwords.assign(3 * (size_t)nst, 0);
+    for (int k = 0; k < w.nd; ++k) w.gwords[(size_t)k] = w.host[(size_t)k] ? FREESASA_INGEST_EIO : w.status[(size_t)k];
+    for (size_t j = 0; j < w.fb.size(); ++j) w.gwords[(size_t)w.nd + j] = hb.b.status[j];
+    char *words = (char *)c->gi_words.p;
+    if (hipMemcpyAsync(words, off.data(), b_off, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(words + b_off, w.gwords.data(), 4 * (size_t)nst, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        return ctx_fail(c, "host-to-device copy failed");
+    sasa::GidArgs ga;
+    memset(&ga, 0, sizeof ga);
+    ga.offsets = (const int64_t *)words; ga.n_structs = nst;
+    ga.res_first = (const int64_t *)B[PBUF_RES_FIRST].p; ga.n_res = R; ga.n_res_dev = Rd;
+    ga.chain_d = (const uint32_t *)B[PBUF_RES_LABELS].p + Rd; ga.chain_h = (const uint32_t *)B[PBUF_SEL_LABELS].p;
+    ga.status = (const int32_t *)(words + b_off); ga.n_groups = (int32_t *)(words + b_off) + nst; ga.group_status = ga.n_groups + nst;
+    ga.group = (int32_t *)c->h_group.p;
+    if (group_ids_resident(c, gs, ga)) return -1;
+    if (hipMemcpyAsync(w.gwords.data() + nst, ga.n_groups, 8 * (size_t)nst, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return ctx_fail(c, "device-to-host copy failed");
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return ctx_fail(c, "stream synchronize failed");
+    /* a structure whose group status is not 0 owns no groups */
+    int32_t *ng = w.gwords.data() + nst;
+    const int32_t *gst = ng + nst;
+    long long G = 0;
+    for (int k = 0; k < nst; ++k) { if (gst[k] != 0) ng[k] = 0; G += ng[k]; }
+    if (ensure(c, c->h_gtot, 24 * (size_t)G + 8)) return -1;
+    std::vector<int> cnt;
+    if (groups_resident(c, a.alg, (const double *)c->h_xyz.p, (const double *)c->h_radii.p, off.data(), nst, ga.group, ng, a.probe, a.resolution,
+                        a.alg == 1 ? S.tp.data() : nullptr, nullptr, nullptr, d_tot, (double *)c->h_gtot.p, &cnt))
+        return -1;
+    GrpBatch *gb = w.gb.get();
+    gb->atoms.assign(cnt.begin(), cnt.end());
+    gb->areas.resize(3 * (size_t)G); gb->chain.assign((size_t)G, 0);
+    long long at = 0;
+    for (int k = 0; k < nst; ++k) {
+        const size_t f = k < w.nd ? (size_t)k : (size_t)w.fb[(size_t)(k - w.nd)];
+        if (k < w.nd && w.host[(size_t)k]) continue;
+        gb->fstart[f] = at; gb->fcount[f] = ng[k];
+        a.group_status_out[w.first + (int)f] = gst[k];
+        if (!gs.separate) for (int g = 0; g < ng[k]; ++g) gb->chain[(size_t)(at + g)] = gs.first_label[(size_t)g];
+        at += ng[k];
+    }
+    if (G == 0) return 0;
+    if (gs.separate) {
+        if (ensure(c, c->gi_label, 4 * (size_t)G)) return -1;
+        sasa::GidLabelArgs la;
+        memset(&la, 0, sizeof la);
+        la.coffsets = (const int64_t *)c->offsets.p; la.src = (const int *)c->g_src.p;
+        la.n_structs = nst; la.n_groups = (int)G; la.n_atoms = n_all;
+        la.res_first = ga.res_first; la.n_res = R; la.n_res_dev = Rd; la.chain_d = ga.chain_d; la.chain_h = ga.chain_h;
+        la.label = (uint32_t *)c->gi_label.p;
+        if (kl_gid_label(la, c->stream) != hipSuccess) return ctx_fail(c, "kernel launch failed");
+        if (hipMemcpyAsync(gb->chain.data(), la.label, 4 * (size_t)G, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return ctx_fail(c, "device-to-host copy failed");
+    }
+    if (hipMemcpyAsync(gb->areas.data(), c->h_gtot.p, 24 * (size_t)G, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return ctx_fail(c, "device-to-host copy failed");
+    return 0;
+}
+
 /* The rest of a batch, whoever parsed: w.nd structures of w.total atoms are on the device (c->h_xyz, h_radii, h_counts;
    backbone flags and residue keys in c->parse[]), hb holds the files w.fb as the host parser read them and goes up behind
    them.  Results into the caller's arrays, w.atoms64 / w.cls and w.rb; on success the stream has been waited for. */
@@ -389,7 +493,7 @@ int tail(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, std::vector<in
     const int ns = w.ns, first = w.first, nd = w.nd, nst = nd + (int)w.fb.size();
     const long long total = w.total, extra = hb.b.n_atoms, n_all = total + extra;
     if (parse_batch_dev_finish(c, extra)) return -1;
-    if ((a.rcol || a.sel) && parse_batch_dev_residues_count(c, extra)) return -1;
+    if ((a.rcol || a.sel || a.grp) && parse_batch_dev_residues_count(c, extra)) return -1;
     if (a.sel && parse_batch_dev_atom_keys(c, extra)) return -1;
     const int n_sel = a.sel ? freesasa_ingest_selection_count(a.sel) : 0;
     std::vector<int64_t> off((size_t)nst + 1);
@@ -404,6 +508,7 @@ int tail(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, std::vector<in
         for (int q = 0; q < n_sel; ++q) { a.sel_area_out[(size_t)(first + k) * n_sel + q] = 0; a.sel_atoms_out[(size_t)(first + k) * n_sel + q] = 0; }
     }
     for (size_t j = 0; j < w.fb.size(); ++j) { a.status_out[first + w.fb[j]] = hb.b.status[j]; w.atoms64[(size_t)w.fb[j]] = hb.b.offsets[j + 1] - hb.b.offsets[j]; }
+    if (a.grp) for (int k = 0; k < ns; ++k) a.group_status_out[first + k] = a.status_out[first + k]; /* (a batch without atoms: nobody loaded) */
     if (a.atoms_out) for (int k = 0; k < ns; ++k) a.atoms_out[first + k] = w.atoms64[(size_t)k];
     if (n_all == 0) return 0;
     if (extra > 0 &&
@@ -414,15 +519,19 @@ int tail(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, std::vector<in
         return ctx_fail(c, "host-to-device copy failed");
     if (ensure(c, c->h_sasa, 8 * (size_t)n_all) || ensure(c, c->h_totals, 8 * 4 * (size_t)nst)) return -1;
     double *d_tot = (double *)c->h_totals.p, *d_cls = d_tot + nst;
-    if (run_batch(c, a.alg == 0, (double *)c->h_xyz.p, (double *)c->h_radii.p, off.data(), nst, a.probe, a.resolution,
-                  a.alg == 1 ? S.tp.data() : nullptr, (double *)c->h_sasa.p, nullptr, d_tot))
+    const double *d_areas = (const double *)c->h_sasa.p;
+    if (a.grp) {
+        if (groups_run(S, c, w, hb, nst, off, hrf, d_tot)) return -1;
+        d_areas = (const double *)c->g_sasa.p;
+    } else if (run_batch(c, a.alg == 0, (double *)c->h_xyz.p, (double *)c->h_radii.p, off.data(), nst, a.probe, a.resolution,
+                         a.alg == 1 ? S.tp.data() : nullptr, (double *)c->h_sasa.p, nullptr, d_tot))
         return -1;
     if (a.rcol && residues_enqueue(S, c, w, hb, hrf)) return -1;
     if (a.sel && select_enqueue(S, c, w, hb, nst, hrf, hkeys)) return -1;
     std::vector<double> tot((size_t)nst), cls;
     if (S.want_cls) {
         cls.resize(3 * (size_t)nst);
-        if (freesasa_gpu_class_sums_dev(c, (double *)c->h_sasa.p, (const unsigned char *)c->h_counts.p, off.data(), nst, d_cls)) return -1;
+        if (freesasa_gpu_class_sums_dev(c, d_areas, (const unsigned char *)c->h_counts.p, off.data(), nst, d_cls)) return -1;
         if (hipMemcpyAsync(cls.data(), d_cls, 8 * 3 * (size_t)nst, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return ctx_fail(c, "device-to-host copy failed");
     }
     if (hipMemcpyAsync(tot.data(), d_tot, 8 * (size_t)nst, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return ctx_fail(c, "device-to-host copy failed");
@@ -495,6 +604,7 @@ void worker(Sweep &S, int wi) noexcept
         if (S.sprof) { const long long t1 = now_ns(); S.tp_run += t1 - tr; tr = t1; }
         if (!ret && S.list.active()) ret = record(S, c, w);
         if (!ret && S.a.rcol) S.a.rcol->add(w.rb);
+        if (!ret && S.a.gcol) S.a.gcol->add(w.gb);
         if (ret) S.fe.set(c->err[0] ? c->err : "GPU sweep failed");
         if (S.sprof) { const long long t1 = now_ns(); S.tp_rec += t1 - tr; tr = t1; }
         loader.join();
@@ -793,5 +903,67 @@ extern "C" int freesasa_gpu_sweep_files_select(const char *const *paths, int n_p
     if (freesasa_ingest_selection_count(sel) < 1) return set_err(err_out, err_len, "empty selection set");
     const int rc = sweep_impl({paths, n_paths, ingest_options, n_threads, alg, probe, resolution, batch_atoms, totals_out, class_sums_out, atoms_out, status_out,
                                nullptr, 0, devices, n_devices, classifier, nullptr, sel, sel_area_out, sel_atoms_out}, err_out, err_len);
+    return rc ? -1 : 0;
+}
+
+/* The sweep with chain groups (include/freesasa_gpu.h): the batches' blocks (GrpBatch) into ONE block behind group_offsets,
+   files in the caller's order, each file's groups in their order. */
+static int assemble_group_table(int n_paths, std::vector<std::unique_ptr<GrpBatch>> &done, freesasa_gpu_group_table *t, char *err_out, int err_len)
+{
+    std::vector<long long> count((size_t)n_paths, 0);
+    std::vector<char> seen((size_t)n_paths, 0);
+    for (auto &gb : done)
+        for (int k = 0; k < gb->ns; ++k) { count[(size_t)(gb->first + k)] = gb->fcount[(size_t)k]; seen[(size_t)(gb->first + k)] = 1; }
+    long long G = 0;
+    for (int f = 0; f < n_paths; ++f) {
+        if (!seen[(size_t)f]) return set_err(err_out, err_len, "a batch of the sweep left no group block");
+        G += count[(size_t)f];
+    }
+    const size_t n = (size_t)n_paths, g = (size_t)G;
+    const size_t o_areas = 8 * (n + 1), o_atoms = o_areas + 24 * g, o_chain = o_atoms + 4 * g, bytes = o_chain + 4 * g;
+    char *blk = (char *)hf_malloc(bytes + 8);
+    if (!blk) return set_err(err_out, err_len, "out of host memory (group table)");
+    t->n_files = n_paths; t->n_groups = G;
+    t->group_offsets = (int64_t *)blk; t->areas = (double *)(blk + o_areas); t->group_atoms = (int32_t *)(blk + o_atoms); t->chain = blk + o_chain;
+    t->group_offsets[0] = 0;
+    for (int f = 0; f < n_paths; ++f) t->group_offsets[f + 1] = t->group_offsets[f] + count[(size_t)f];
+    for (auto &gb : done)
+        for (int k = 0; k < gb->ns; ++k) {
+            const size_t m = (size_t)gb->fcount[(size_t)k], src = (size_t)gb->fstart[(size_t)k], dst = (size_t)t->group_offsets[gb->first + k];
+            if (!m) continue;
+            memcpy(t->areas + 3 * dst, gb->areas.data() + 3 * src, 24 * m);
+            memcpy(t->group_atoms + dst, gb->atoms.data() + src, 4 * m);
+            memcpy(t->chain + 4 * dst, gb->chain.data() + src, 4 * m);
+        }
+    return 0;
+}
+
+extern "C" void freesasa_gpu_group_table_free(freesasa_gpu_group_table *table)
+{
+    if (!table) return;
+    free(table->group_offsets); /* (the one block: assemble_group_table) */
+    memset(table, 0, sizeof *table);
+}
+
+extern "C" int freesasa_gpu_sweep_files_groups(const char *const *paths, int n_paths, int ingest_options, int n_threads,
+                                               int alg, double probe, int resolution, long long batch_atoms,
+                                               double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out,
+                                               const int *devices, int n_devices, const freesasa_ingest_classifier *classifier,
+                                               const char *spec, int group_flags, int *group_status_out,
+                                               freesasa_gpu_group_table *table_out, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (table_out) memset(table_out, 0, sizeof *table_out);
+    if (!table_out || !group_status_out) return set_err(err_out, err_len, "null argument");
+    const int rc = guarded(err_out, err_len, [&]() -> int {
+        GroupSpec gs; /* (outlives the workers and their contexts' streams) */
+        if (group_spec_parse(spec, group_flags, &gs, err_out, err_len)) return -1;
+        GrpCollector col;
+        SweepArgs a = {paths, n_paths, ingest_options, n_threads, alg, probe, resolution, batch_atoms, totals_out, class_sums_out, atoms_out, status_out,
+                       nullptr, 0, devices, n_devices, classifier, nullptr, nullptr, nullptr, nullptr, &gs, &col, group_status_out};
+        if (sweep_impl(a, err_out, err_len)) return -1;
+        return assemble_group_table(n_paths, col.done, table_out, err_out, err_len);
+    });
+    if (rc) freesasa_gpu_group_table_free(table_out);
     return rc ? -1 : 0;
 }

@@ -43,7 +43,7 @@ struct GrpArgs {
     const double *ctot;   /* [n_structs + G] per combined structure */
     const double *ctot2;  /* [n_structs + G] per combined structure, over cgath */
     double *cgath;        /* [N] complex area of every combined atom (j < n: its own; j >= n: its source atom's) */
-    double *sasa, *iso;   /* [n] caller's outputs */
+    double *sasa, *iso;   /* [n] caller's outputs (either may be null: the file sweep wants neither, gpu_sweep.hip) */
     double *totals;       /* [n_structs] or null */
     double *gtot;         /* [3 G] or null */
 };
@@ -133,12 +133,12 @@ SASA_D void grp_finish_atom(const GrpArgs &a, int64_t t)
     const int64_t n = a.n_atoms;
     if (t < n) {
         const double v = a.csasa[t];
-        a.sasa[t] = v;
+        if (a.sasa) a.sasa[t] = v;
         a.cgath[t] = v;
-        if (a.key[t] < 0) a.iso[t] = v;
+        if (a.iso && a.key[t] < 0) a.iso[t] = v;
     } else if (t < n + a.n_iso) {
         const int i = a.src[t - n];
-        a.iso[i] = a.csasa[t];
+        if (a.iso) a.iso[i] = a.csasa[t];
         a.cgath[t] = a.csasa[i];
     }
 }
@@ -153,6 +153,162 @@ SASA_D void grp_totals_item(const GrpArgs &a, int k)
         a.gtot[3 * (int64_t)k + 1] = t1;
         a.gtot[3 * (int64_t)k + 2] = t0 - t1;
     }
+}
+
+/* ------------------------------------------------------------------ group ids made on the device
+ * (freesasa_gpu_chain_group_ids, freesasa_gpu_sweep_files_groups): what freesasa_ingest_chain_groups (select.c) makes of a
+ * loaded batch's chain labels, made of residue boundaries and labels that are on the device - the device parser's residues
+ * first, a loaded batch's behind them, as SelArgs has them.  The spec is parsed on the host by select.c's own code
+ * (freesasa_ingest_chain_groups_parse); its labels come sorted by their value as a word so that a residue finds its own in
+ * log2(n_lab) steps. */
+
+#define GID_MAX_PER_STRUCT 65535
+#define GID_MAX_LABELS 4096
+#define GID_EGROUP 8 /* FREESASA_INGEST_EGROUP (gpu_groups.hip asserts it) */
+#ifdef SASA_EMU
+#define GID_FENCE() ((void)0)
+#else
+#define GID_FENCE() __threadfence()
+#endif
+
+struct GidArgs {
+    const int64_t *offsets;      /* [n_structs + 1] atoms */
+    int n_structs;
+    const int64_t *res_first;    /* [n_res + 1] first atom of every residue, batch-wide (n_res 0: one entry) */
+    int64_t n_res, n_res_dev;    /* residues < n_res_dev have their label in chain_d, the others, counted from n_res_dev, in chain_h */
+    const uint32_t *chain_d, *chain_h;
+    const int32_t *status;       /* [n_structs] the loader's status */
+    const uint32_t *lab;         /* [n_lab] the spec's labels, ascending; n_lab 0: separate chains */
+    const int32_t *lab_group;    /* [n_lab] */
+    int n_lab, n_spec_groups;
+    int32_t *group;              /* [n_atoms] */
+    int32_t *n_groups, *group_status; /* [n_structs] */
+};
+
+/* the first k in [0, n] with first[k] >= v (first has n + 1 entries, ascending): a structure's residues are those between
+   the bounds of its first atom and of its end; a residue without atoms on the border belongs to nobody it matters to */
+SASA_D int64_t gid_lower(const int64_t *first, int64_t n, int64_t v)
+{
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (first[mid] < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+/* strncmp over 4 bytes as equality of words: nothing behind a label's first NUL counts */
+SASA_D uint32_t gid_canon(uint32_t l)
+{
+    if (!(l & 0xffu)) return 0;
+    if (!(l & 0xff00u)) return l & 0xffu;
+    if (!(l & 0xff0000u)) return l & 0xffffu;
+    return l;
+}
+
+/* ONE WAVE PER STRUCTURE, its residues 64 at a time in order.  Separate chains: a residue that holds atoms starts a group
+ * when its 4 label bytes differ from those of the residue with atoms before it - the lane below it, or, for the step's first
+ * one, the label carried over from the step before; a lane's group is the running number plus the starts up to its own.
+ * Spec: every lane looks its label up, marks it present (present [GID_MAX_LABELS / 32], the wave's own: LDS) and takes its
+ * group; a structure that misses one of the labels has all its ids put back to -1.  A lane writes the ids of its residue's
+ * atoms itself. */
+SASA_D void gid_struct(const GidArgs &a, unsigned *present, int s, int lane)
+{
+    const int64_t b = a.offsets[s], e = a.offsets[s + 1];
+    const int st = a.status[s];
+    const bool separate = a.n_lab == 0;
+    int ng = separate ? 0 : a.n_spec_groups, gs = st;
+    bool bad = st != 0;
+    if (st == 0) {
+        const int words = (a.n_lab + 31) >> 5;
+        for (int w = lane; w < words; w += 64) present[w] = 0;
+        LR2_SYNC();
+        const int64_t r0 = gid_lower(a.res_first, a.n_res, b), r1 = gid_lower(a.res_first, a.n_res, e);
+        int run = 0;          /* groups so far, the label of the last residue with atoms (alike in every lane) */
+        bool have = false;
+        uint32_t carry = 0;
+        for (int64_t rb = r0; rb < r1; rb += 64) {
+            const int64_t r = rb + lane;
+            int64_t a0 = 0, a1 = 0;
+            if (r < r1) { a0 = a.res_first[r]; a1 = a.res_first[r + 1]; }
+            const bool has = a1 > a0;
+            uint32_t lbl = 0;
+            if (has) lbl = r < a.n_res_dev ? a.chain_d[r] : a.chain_h[r - a.n_res_dev];
+            int g = -1;
+            if (separate) {
+                const unsigned long long hm = LR2_BALLOT(has);
+                const unsigned long long below = hm & ((1ull << lane) - 1ull);
+                const uint32_t pl = (uint32_t)LR2_SHFL((int)lbl, below ? 63 - __builtin_clzll(below) : 0);
+                const bool start = has && (below ? lbl != pl : (!have || lbl != carry));
+                const unsigned long long sm = LR2_BALLOT(start);
+                g = run + (int)LR2_POPC64(sm & ((2ull << lane) - 1ull)) - 1;
+                run += (int)LR2_POPC64(sm);
+                const uint32_t last = (uint32_t)LR2_SHFL((int)lbl, hm ? 63 - __builtin_clzll(hm) : 0);
+                if (hm) { carry = last; have = true; }
+            } else if (has) {
+                const uint32_t key = gid_canon(lbl);
+                int lo = 0, hi = a.n_lab - 1;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (a.lab[mid] < key) lo = mid + 1;
+                    else hi = mid;
+                }
+                if (a.lab[lo] == key) {
+                    SASA_ATOMIC_OR_LDS(&present[lo >> 5], 1u << (lo & 31));
+                    g = a.lab_group[lo];
+                }
+            }
+            for (int64_t i = a0; i < a1; ++i) a.group[i] = g;
+        }
+        if (separate) {
+            bad = run > GID_MAX_PER_STRUCT;
+            ng = bad ? 0 : run;
+        } else {
+            LR2_SYNC();
+            bool miss = false;
+            for (int w = lane; w < words; w += 64) {
+                const int nb = a.n_lab - 32 * w;
+                miss = miss || present[w] != (nb >= 32 ? 0xffffffffu : (1u << nb) - 1u);
+            }
+            bad = LR2_BALLOT(miss) != 0;
+        }
+        if (bad) gs = GID_EGROUP;
+    }
+    if (bad) {
+        GID_FENCE(); /* (the ids written above, by other lanes, are in memory before these go over them) */
+        for (int64_t i = b + lane; i < e; i += 64) a.group[i] = -1;
+    }
+    if (lane == 0) { a.n_groups[s] = ng; a.group_status[s] = gs; }
+}
+
+/* The label of every group of a batch cut by separate chains, one thread per group: that of the residue of the group's first
+ * atom in the combined batch (coffsets: the combined batch's offsets, [n_structs + n_groups + 1]; src as in GrpArgs). */
+struct GidLabelArgs {
+    const int64_t *coffsets;
+    const int *src;
+    int n_structs, n_groups;
+    int64_t n_atoms;
+    const int64_t *res_first;
+    int64_t n_res, n_res_dev;
+    const uint32_t *chain_d, *chain_h;
+    uint32_t *label;             /* [n_groups] */
+};
+SASA_D void gid_label_item(const GidLabelArgs &a, int k)
+{
+    if (k >= a.n_groups) return;
+    const int64_t p0 = a.coffsets[a.n_structs + k], p1 = a.coffsets[a.n_structs + k + 1];
+    uint32_t l = 0;
+    if (p1 > p0 && a.n_res > 0) {
+        const int64_t i = a.src[p0 - a.n_atoms];
+        int64_t lo = 0, hi = a.n_res - 1; /* the last residue that begins at or before atom i */
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) >> 1;
+            if (a.res_first[mid] <= i) lo = mid;
+            else hi = mid - 1;
+        }
+        l = lo < a.n_res_dev ? a.chain_d[lo] : a.chain_h[lo - a.n_res_dev];
+    }
+    a.label[k] = l;
 }
 
 } /* namespace sasa */

@@ -606,15 +606,41 @@ static int cg_parse(const char *spec, int is_long, cg_label_t *lab, int *n_lab, 
     return n_groups;
 }
 
+/* the call errors of a spec and its flags that need no parse; 0 or -1 (err set) */
+static int cg_check(const char *spec, int flags, char *err, int err_len)
+{
+    if (flags & ~(FREESASA_INGEST_GROUPS_LONG | FREESASA_INGEST_SEPARATE_CHAINS)) return cg_fail(err, err_len, "unknown flags");
+    const int separate = (flags & FREESASA_INGEST_SEPARATE_CHAINS) != 0;
+    if (separate && spec) return cg_fail(err, err_len, "chain groups and separate chains can't be combined");
+    if (!separate && !spec) return cg_fail(err, err_len, "no chain groups given");
+    return 0;
+}
+
+int freesasa_ingest_chain_groups_parse(const char *spec, int flags, char *labels_out, int32_t *label_group_out, int *n_labels_out,
+                                       char *err, int err_len)
+{
+    if (err && err_len > 0) err[0] = 0;
+    if (!labels_out || !label_group_out || !n_labels_out) return cg_fail(err, err_len, "null argument");
+    *n_labels_out = 0;
+    if (cg_check(spec, flags, err, err_len)) return -1;
+    if (flags & FREESASA_INGEST_SEPARATE_CHAINS) return 0;
+    cg_label_t *lab = (cg_label_t *)hf_malloc(sizeof(cg_label_t) * CG_MAX_LABELS);
+    if (!lab) return cg_fail(err, err_len, "out of memory");
+    int n_lab = 0;
+    const int G = cg_parse(spec, (flags & FREESASA_INGEST_GROUPS_LONG) != 0, lab, &n_lab, err, err_len);
+    for (int i = 0; G >= 0 && i < n_lab; ++i) { memcpy(labels_out + 4 * i, lab[i].label, 4); label_group_out[i] = lab[i].group; }
+    if (G >= 0) *n_labels_out = n_lab;
+    free(lab);
+    return G;
+}
+
 int freesasa_ingest_chain_groups(const freesasa_ingest_batch *b, const char *spec, int flags, int32_t *group_out,
                                  int32_t *n_groups_out, int32_t *status_out, char *err, int err_len)
 {
     if (err && err_len > 0) err[0] = 0;
     if (!b || !group_out || !n_groups_out || !status_out) return cg_fail(err, err_len, "null argument");
-    if (flags & ~(FREESASA_INGEST_GROUPS_LONG | FREESASA_INGEST_SEPARATE_CHAINS)) return cg_fail(err, err_len, "unknown flags");
+    if (cg_check(spec, flags, err, err_len)) return -1;
     const int separate = (flags & FREESASA_INGEST_SEPARATE_CHAINS) != 0;
-    if (separate && spec) return cg_fail(err, err_len, "chain groups and separate chains can't be combined");
-    if (!separate && !spec) return cg_fail(err, err_len, "no chain groups given");
     cg_label_t *lab = NULL;
     int n_lab = 0, G = 0;
     if (!separate) {

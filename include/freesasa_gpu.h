@@ -335,6 +335,48 @@ int freesasa_gpu_sweep_files_select(const char *const *paths, int n_paths, int i
                                     const int *devices, int n_devices, const struct freesasa_ingest_classifier *classifier,
                                     const struct freesasa_ingest_selection *sel,
                                     double *sel_area_out, long long *sel_atoms_out, char *err, int err_len);
+/* CHAIN GROUPS in the file sweep: the reference's --chain-groups / --separate-chains (src/main.cc:261-312) for all files of a
+   sweep in one call - how much area every group of chains of every file exposes on its own, in its complex, and buries.
+   _sweep_files_groups: the arguments of freesasa_gpu_sweep_files_select up to `classifier`, then spec and group_flags as
+   freesasa_ingest_chain_groups takes them (include/freesasa_ingest.h: the short or the long syntax, or spec NULL with
+   FREESASA_INGEST_SEPARATE_CHAINS).  A bad character, an empty group, overlapping groups, both or neither of spec and
+   separate chains, unknown flags are call errors with that function's messages (its own code parses the spec), reported
+   before a device is touched or a file read.  Totals, class sums, atom counts and status are exactly
+   freesasa_gpu_sweep_files_classified's.  group_status_out [n_paths]: the loader's status, or FREESASA_INGEST_EGROUP (a chain
+   the spec names is missing, or more than 65535 separate chains); a file whose group status is not 0 owns no rows of the
+   table - an EGROUP file keeps its total, class sums and atom count.  table_out: file k owns groups [group_offsets[k],
+   group_offsets[k + 1]) in the spec's order (separate chains: in the file's); per group its atoms, areas[3 g + ..] = isolated,
+   complex, buried (the columns of freesasa_gpu_groups_dev's d_group_totals) and chain[4 g ..], 4 bytes as res_chain holds
+   them: the run's label with separate chains, else the first label the spec names for the group.
+   The per-atom group ids are made ON THE DEVICE (csrc/group_kernels.h, k_gid_struct: one wave per structure over its
+   residues) from residue boundaries and chain labels that are there - with FREESASA_INGEST_PARSE_ON_DEVICE the device
+   parser's, the host parser's files' uploaded behind them (12 bytes per residue) - and neither they nor any per-atom area
+   leave it: per batch the structures' group counts and status and the groups' atom counts come back (they size the combined
+   batch of freesasa_gpu_groups_dev's pipeline), then 24 bytes per group and, with separate chains, its label.
+   The table's arrays are ONE block, released by freesasa_gpu_group_table_free only (which zeroes the struct; a zeroed struct
+   is a no-op); on any failure (-1, message in err) the struct is zeroed and nothing is kept.
+   _chain_group_ids: the ids kernel alone on a LOADED batch, the twin of freesasa_ingest_chain_groups with the same outputs
+   (group_out [n_atoms], n_groups_out and status_out [n_structs]): offsets, residue boundaries, chain labels and status go up,
+   the three arrays come back; on a pooled context of `device` (-1: any).  0 / -1 with the message in err.
+   Not offered: a done-list / resumable form (records of variable length), the cache sweep (a cache read brings no residue
+   arrays), chain groups in the trajectory drivers. */
+typedef struct freesasa_gpu_group_table {
+    int32_t n_files;
+    int64_t n_groups;
+    int64_t *group_offsets; /* [n_files + 1]: file k owns groups [group_offsets[k], group_offsets[k + 1]) */
+    int32_t *group_atoms;   /* [n_groups] */
+    double *areas;          /* [3 * n_groups]: isolated, complex, buried */
+    char *chain;            /* [4 * n_groups] */
+} freesasa_gpu_group_table;
+int freesasa_gpu_sweep_files_groups(const char *const *paths, int n_paths, int ingest_options, int n_threads,
+                                    int alg, double probe_radius, int resolution, long long batch_atoms,
+                                    double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out,
+                                    const int *devices, int n_devices, const struct freesasa_ingest_classifier *classifier,
+                                    const char *spec, int group_flags, int *group_status_out,
+                                    freesasa_gpu_group_table *table_out, char *err, int err_len);
+void freesasa_gpu_group_table_free(freesasa_gpu_group_table *table);
+int freesasa_gpu_chain_group_ids(const struct freesasa_ingest_batch *batch, const char *spec, int flags, int32_t *group_out,
+                                 int32_t *n_groups_out, int32_t *status_out, int device, char *err, int err_len);
 int freesasa_gpu_sweep_cache_devices(const char *cache_path, int alg, double probe_radius, int resolution, long long batch_atoms,
                                      double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out, int n_out,
                                      const int *devices, int n_devices, int lanes_per_device, char *err, int err_len);

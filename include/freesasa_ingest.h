@@ -234,6 +234,14 @@ const void *freesasa_ingest_selection_program(const freesasa_ingest_selection *s
 #define FREESASA_INGEST_SEPARATE_CHAINS (1 << 4) /* (the reference's FREESASA_SEPARATE_CHAINS; the loaders refuse it) */
 int freesasa_ingest_chain_groups(const freesasa_ingest_batch *b, const char *spec, int flags, int32_t *group_out,
                                  int32_t *n_groups_out, int32_t *status_out, char *err, int err_len);
+/* The spec and flags of freesasa_ingest_chain_groups on their own, for callers that make the ids elsewhere (the device:
+ * freesasa_gpu_chain_group_ids, freesasa_gpu_sweep_files_groups): the same checks in the same order with the same messages.
+ * labels_out [4 * FREESASA_INGEST_MAX_GROUP_LABELS] receives the labels in the spec's order, NUL-padded to 4 bytes,
+ * label_group_out [FREESASA_INGEST_MAX_GROUP_LABELS] the group of each, *n_labels_out their number (0 with
+ * FREESASA_INGEST_SEPARATE_CHAINS).  Returns the number of groups of the spec (0: separate chains), or -1 with the message. */
+#define FREESASA_INGEST_MAX_GROUP_LABELS 4096
+int freesasa_ingest_chain_groups_parse(const char *spec, int flags, char *labels_out, int32_t *label_group_out, int *n_labels_out,
+                                       char *err, int err_len);
 
 /* The classifier on its own (ref: freesasa_classifier_radius / _class with the ProtOr classifier,
  * src/classifier.c:781-813): radius in A or -1.0 if unknown; *cls (may be NULL) receives the class. */

@@ -3,7 +3,8 @@
 per-structure totals (BASELINE configs[3] in miniature; SURVEY §8f N1 + the batch entry point).
 
     python tools/sweep.py [--replicate N] [--threads T] [--batch-atoms A] [--devices 0,1,...] [--done FILE] [--cache FILE]
-                          [--residues OUT.tsv] [--select CMD ... --select-out OUT.tsv] [paths ...]
+                          [--residues OUT.tsv] [--select CMD ... --select-out OUT.tsv]
+                          [--chain-groups SPEC | --separate-chains, --groups-out OUT.tsv] [paths ...]
 
 Without paths it sweeps the PDB fixtures under tests/golden/pdb, replicated N times.  Loading of
 batch k+1 runs on host threads while the GPU computes batch k.  Prints one JSON line with the
@@ -14,7 +15,9 @@ device list; --cache FILE: sweep the binary cache FILE instead (written first fr
 --residues OUT.tsv: the per-residue table of all files (freesasa_gpu_sweep_files_residues): file, chain, number, name, the
 five absolute areas (total, main chain, side chain, polar, apolar) and the five relative ones, N/A where there is none;
 --select CMD (repeatable, up to 64) with --select-out OUT.tsv: the reference's --select for all files
-(freesasa_gpu_sweep_files_select): file, then one area column per selection name."""
+(freesasa_gpu_sweep_files_select): file, then one area column per selection name;
+--chain-groups SPEC ("AB+C") or --separate-chains with --groups-out OUT.tsv: the reference's chain groups for all files
+(freesasa_gpu_sweep_files_groups): file, group index, label, atoms, isolated, complex and buried area per line."""
 import argparse
 import glob
 import json
@@ -49,6 +52,17 @@ def write_selections(path, paths, names, areas):
             fh.write("\t".join([p] + [f"{v:.2f}" for v in areas[k]]) + "\n")
 
 
+def write_groups(path, paths, table):
+    """one line per group: its file, its index in the file, label, atoms, isolated, complex and buried area"""
+    chain = table.chain
+    with open(path, "w") as fh:
+        fh.write("file\tgroup\tlabel\tatoms\tisolated\tcomplex\tburied\n")
+        for k, p in enumerate(paths):
+            s = table.file(k)
+            for g in range(s.start, s.stop):
+                fh.write("\t".join([p, str(g - s.start), chain[g], str(int(table.group_atoms[g]))] + [f"{v:.2f}" for v in table.areas[g]]) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("paths", nargs="*")
@@ -64,6 +78,9 @@ def main():
     ap.add_argument("--residues", default=None, metavar="OUT.tsv", help="write the per-residue table of all files (not with --done or --cache)")
     ap.add_argument("--select", action="append", default=[], metavar="CMD", help='a selection in the reference\'s language ("name, resn ala+arg and not chain B"); repeatable, up to 64')
     ap.add_argument("--select-out", default=None, metavar="OUT.tsv", help="write the selections' areas of all files (not with --done, --cache or --no-gpu)")
+    ap.add_argument("--chain-groups", default=None, metavar="SPEC", help='the reference\'s --chain-groups for every file ("AB+C": chains A and B as one group, C as another)')
+    ap.add_argument("--separate-chains", action="store_true", help="the reference's --separate-chains for every file: one group per chain")
+    ap.add_argument("--groups-out", default=None, metavar="OUT.tsv", help="write the groups' areas of all files (not with --select, --residues, --done, --cache or --no-gpu)")
     ap.add_argument("--engine", choices=["python", "c"], default="c",
                     help="c: freesasa_gpu_sweep_files (loader thread || GPU inside the library); "
                          "python: the same pipeline written with the two-step Python API")
@@ -74,6 +91,13 @@ def main():
         ap.error("--select and --select-out go together")
     if args.select and (args.done or args.cache or args.no_gpu or args.residues or args.engine != "c"):
         ap.error("--select goes with the C engine's plain file sweep only (no --done, --cache, --no-gpu, --residues, --engine python)")
+    want_groups = args.chain_groups is not None or args.separate_chains
+    if args.chain_groups is not None and args.separate_chains:
+        ap.error("--chain-groups and --separate-chains can't be combined")
+    if want_groups != bool(args.groups_out):
+        ap.error("--chain-groups / --separate-chains and --groups-out go together")
+    if want_groups and (args.select or args.done or args.cache or args.no_gpu or args.residues or args.engine != "c"):
+        ap.error("chain groups go with the C engine's plain file sweep only (no --select, --residues, --done, --cache, --no-gpu, --engine python)")
     import freesasa_amd as fa
     from freesasa_amd import ingest
     selection = None
@@ -131,6 +155,13 @@ def main():
             write_selections(args.select_out, paths, selection.names, areas)
             out["selections"] = len(selection)
             out["selected_atoms"] = int(counts.sum())
+        elif want_groups:
+            totals, _, atoms, status, gstatus, gtable = fa.sweep_files_groups(paths, args.chain_groups, separate_chains=args.separate_chains, alg=fa.LEE_RICHARDS,
+                                                                              resolution=args.slices, n_threads=args.threads, batch_atoms=args.batch_atoms,
+                                                                              devices=devices, ingest_options=popt)
+            write_groups(args.groups_out, paths, gtable)
+            out["groups"] = int(gtable.n_groups)
+            out["files_without_their_groups"] = int(((gstatus != 0) & (status == 0)).sum())
         else:
             totals, _, atoms, status = fa.sweep_files(paths, fa.LEE_RICHARDS, resolution=args.slices, n_threads=args.threads,
                                                       batch_atoms=args.batch_atoms, class_sums=True, devices=devices, ingest_options=popt)
