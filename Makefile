@@ -2,7 +2,7 @@
 #   make            -> freesasa_amd/lib/libfreesasa_amd.so (stand-alone drop-in library)
 #                      freesasa_amd/lib/libfreesasa_amd_seam.a (seam objects for a drop-in
 #                      build of the reference)
-#   make emu        -> tests/emu/libsasa_emu.so, libselect_emu.so, libgroups_emu.so  (TESTS ONLY: the kernel phase
+#   make emu        -> tests/emu/libsasa_emu.so, libselect_emu.so, libgroups_emu.so, libtraj_emu.so  (TESTS ONLY: the kernel phase
 #                      functions driven on the CPU; never linked into the product)
 #   make oracle     -> oracle/ (TESTS ONLY) ; make tools -> tools/libsasa_synth.so
 HIPCC   ?= /opt/rocm/bin/hipcc
@@ -19,7 +19,7 @@ all: $(LIBDIR)/libfreesasa_amd.so $(LIBDIR)/libfreesasa_amd_seam.a
 # Device code lives in ONE translation unit (gpu_kernels.hip); the compiler's per-kernel resource report (registers,
 # scratch, LDS) is kept next to its object: tests/test_capi.py checks that the hot kernels do not spill.  The other
 # .hip files are host code over the HIP runtime (engine_internal.h says who holds what).
-ENGINE_HDRS = $(CSRC)/classifier.h $(CSRC)/engine_internal.h $(CSRC)/sasa_kernels.h $(CSRC)/group_kernels.h $(CSRC)/select_kernels.h $(CSRC)/select_program.h $(CSRC)/sr_caps.h $(CSRC)/lr2_kernels.h $(CSRC)/gpu_parse.h $(CSRC)/protor_table.h include/freesasa_gpu.h include/freesasa_ingest.h
+ENGINE_HDRS = $(CSRC)/classifier.h $(CSRC)/engine_internal.h $(CSRC)/sasa_kernels.h $(CSRC)/group_kernels.h $(CSRC)/select_kernels.h $(CSRC)/traj_kernels.h $(CSRC)/select_program.h $(CSRC)/sr_caps.h $(CSRC)/lr2_kernels.h $(CSRC)/gpu_parse.h $(CSRC)/protor_table.h include/freesasa_gpu.h include/freesasa_ingest.h
 $(LIBDIR)/gpu_kernels.o: $(CSRC)/gpu_kernels.hip $(ENGINE_HDRS)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(LIBDIR)/kernel_resources.txt; rc=$$?; \
@@ -73,7 +73,7 @@ $(LIBDIR)/libfreesasa_amd.so: $(GPU_OBJS) $(LIBDIR)/seam.o $(LIBDIR)/testpoints.
 $(LIBDIR)/libfreesasa_amd_seam.a: $(GPU_OBJS) $(LIBDIR)/seam.o $(LIBDIR)/testpoints.o $(LIBDIR)/ingest.o $(LIBDIR)/classifier.o $(LIBDIR)/select.o $(LIBDIR)/ingest_cache.o $(LIBDIR)/hostfault.o
 	rm -f $@; ar rcs $@ $^
 
-emu: tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so
+emu: tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so
 # the loader with its byte-at-a-time mmCIF tokenizer only: the differential twin of the SSE2 row scanner
 tests/emu/libingest_scalar.so: $(CSRC)/ingest.c $(CSRC)/classifier.c $(CSRC)/classifier.h $(CSRC)/hostfault.c $(CSRC)/hostfault.h $(CSRC)/protor_table.h include/freesasa_ingest.h
 	$(CC) $(CFLAGS) -DFREESASA_INGEST_NO_SIMD -Iinclude -pthread -shared -o $@ $(CSRC)/ingest.c $(CSRC)/classifier.c $(CSRC)/hostfault.c -lm
@@ -83,6 +83,10 @@ tests/emu/libsasa_emu.so: tests/emu/emu.cpp $(CSRC)/sasa_kernels.h $(CSRC)/sr_ca
 # the selection kernels' phase functions (select_kernels.h) driven over a loaded batch
 tests/emu/libselect_emu.so: tests/emu/emu_select.cpp $(CSRC)/select_kernels.h $(CSRC)/select_program.h $(CSRC)/sasa_kernels.h include/freesasa_ingest.h
 	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -DSASA_EMU -Iinclude -shared -o $@ tests/emu/emu_select.cpp -lm
+
+# the trajectory topology's phase functions (traj_kernels.h): the gather and the per-frame sums over one structure of a loaded batch
+tests/emu/libtraj_emu.so: tests/emu/emu_traj.cpp $(CSRC)/traj_kernels.h $(CSRC)/select_kernels.h $(CSRC)/select_program.h $(CSRC)/sasa_kernels.h include/freesasa_ingest.h
+	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -DSASA_EMU -Iinclude -shared -o $@ tests/emu/emu_traj.cpp -lm
 
 # the group-ids kernel's phase function (group_kernels.h, gid_struct) driven over a loaded batch, one wave per structure
 tests/emu/libgroups_emu.so: tests/emu/emu_groups.cpp $(CSRC)/group_kernels.h $(CSRC)/lr2_kernels.h $(CSRC)/sasa_kernels.h $(CSRC)/sr_caps.h include/freesasa_ingest.h
@@ -111,7 +115,7 @@ tools:
 	$(MAKE) -C tools
 
 clean:
-	rm -rf $(LIBDIR) tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so
+	rm -rf $(LIBDIR) tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so
 	$(MAKE) -C oracle clean
 	$(MAKE) -C tools clean
 .PHONY: all emu oracle tools clean asan asan-test

@@ -655,6 +655,100 @@ def trajectory_file(frames_path, radii, totals_path, sasa_path=None, done_path=N
     return ret == 0, int(total.value)
 
 
+def _topology_proto(L):
+    _i32p, _llp = C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
+    L.freesasa_gpu_trajectory_topology.argtypes = [_dp, C.c_int, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_void_p,
+                                                   C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _llp,
+                                                   _ip, C.c_int, C.c_char_p, C.c_int]
+    L.freesasa_gpu_trajectory_file_topology.argtypes = [C.c_char_p, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, C.c_int, _i32p,
+                                                        C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
+                                                        C.c_char_p, C.c_char_p, C.c_char_p, _llp, C.c_char_p, C.c_longlong, _ip, C.c_int,
+                                                        _llp, C.c_char_p, C.c_int]
+    return L
+
+
+class TopologyResult:
+    """What trajectory_topology() returns: totals [F], class_sums [F, 3] (apolar, polar, unknown), residues [F, R, 6] (total,
+    main chain, side chain, polar, apolar, unknown), selection_areas [F, S] and selection_atoms [S] (None without a
+    selection set), sasa [F, n] or None, and res_ref [R]: rows of ingest.residue_reference_table() - the relative areas are
+    100 * residues[..., :5] / table[res_ref] where res_ref >= 0."""
+
+    def __init__(self, totals, class_sums, residues, selection_areas, selection_atoms, sasa, res_ref):
+        self.totals, self.class_sums, self.residues = totals, class_sums, residues
+        self.selection_areas, self.selection_atoms, self.sasa, self.res_ref = selection_areas, selection_atoms, sasa, res_ref
+
+
+def _topology_args(batch, structure, atom_index, frame_atoms):
+    """(n, R, res_ref, index array or None, frame_atoms) of a topology; the library checks them"""
+    ok = 0 <= structure < batch.n_structs
+    n = int(batch.offsets[structure + 1] - batch.offsets[structure]) if ok else 0
+    r0, r1 = (int(batch.res_offsets[structure]), int(batch.res_offsets[structure + 1])) if ok else (0, 0)
+    idx = None if atom_index is None else np.ascontiguousarray(atom_index, dtype=np.int32)
+    if idx is not None and idx.size != n and ok:
+        raise ValueError("atom_index needs one entry per atom of the structure")
+    return n, r1 - r0, batch.res_ref[r0:r1].copy(), idx, int(n if frame_atoms is None else frame_atoms)
+
+
+def trajectory_topology(frames, batch, structure=0, atom_index=None, selection=None, per_atom=False, alg=LEE_RICHARDS, probe=1.4,
+                        resolution=20, frames_per_batch=0, device=-1, devices=None):
+    """freesasa_gpu_trajectory_topology(): frames [F, frame_atoms, 3] of a (solvated) system whose solute is structure
+    `structure` of the ingest.Batch - topology atom i is frame atom atom_index[i] (None: the frames hold exactly the
+    structure's atoms) - -> a TopologyResult.  The gather, the per-residue, per-class and per-selection sums run on the
+    device; the per-atom areas come back only with per_atom=True."""
+    L = _topology_proto(lib())
+    frames = np.ascontiguousarray(frames, dtype=np.float64)
+    if frames.ndim != 3 or frames.shape[2] != 3:
+        raise ValueError("frames must be [n_frames, frame_atoms, 3]")
+    F = frames.shape[0]
+    n, R, res_ref, idx, fa_ = _topology_args(batch, structure, atom_index, frames.shape[1])
+    S = len(selection) if selection is not None else 0
+    totals, cls, res = np.zeros(F), np.zeros((F, 3)), np.zeros((F, R, 6))
+    sel_area = np.zeros((F, S)) if selection is not None else None
+    sel_atoms = np.zeros(S, dtype=np.int64) if selection is not None else None
+    sasa = np.zeros((F, n)) if per_atom else None
+    err = C.create_string_buffer(512)
+    keep, dp_, nd = _devs(devices, device)
+    cb = batch._as_c()
+    opt = lambda a, t=_dp: None if a is None else a.ctypes.data_as(t)
+    ret = L.freesasa_gpu_trajectory_topology(frames.ctypes.data_as(_dp), F, C.byref(cb), structure, fa_, opt(idx, C.POINTER(C.c_int32)),
+                                             selection.handle if selection is not None else None, alg, probe, resolution,
+                                             frames_per_batch, totals.ctypes.data_as(_dp), opt(sasa), cls.ctypes.data_as(_dp),
+                                             res.ctypes.data_as(_dp), opt(sel_area), opt(sel_atoms, C.POINTER(C.c_longlong)),
+                                             dp_, nd, err, 512)
+    if ret:
+        raise RuntimeError("freesasa_gpu_trajectory_topology: " + err.value.decode())
+    return TopologyResult(totals, cls, res, sel_area, sel_atoms, sasa, res_ref)
+
+
+def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_index=None, frame_atoms=None, selection=None,
+                             sasa_path=None, class_sums_path=None, residues_path=None, selections_path=None, done_path=None,
+                             f32=False, header_bytes=0, n_frames=0, alg=LEE_RICHARDS, probe=1.4, resolution=20, frames_per_batch=0,
+                             max_new_shards=0, device=-1, devices=None, out_f32=False):
+    """freesasa_gpu_trajectory_file_topology(): trajectory_file() with a topology (see trajectory_topology; frame_atoms:
+    atoms per frame of the file, None: the structure's) and one raw fp64 result file per output asked for: class sums
+    [F, 3], residues [F, R, 6], selection areas [F, S].  Returns (complete, n_frames, selection_atoms [S] or None)."""
+    L = _topology_proto(lib())
+    n, R, res_ref, idx, fa_ = _topology_args(batch, structure, atom_index, frame_atoms)
+    S = len(selection) if selection is not None else 0
+    sel_atoms = np.zeros(S, dtype=np.int64) if selection is not None else None
+    bits = (1 if f32 else 0) | (2 if out_f32 else 0)
+    err = C.create_string_buffer(512)
+    total = C.c_longlong(0)
+    enc = lambda p: None if p is None else str(p).encode()
+    keep, dp_, nd = _devs(devices, device)
+    cb = batch._as_c()
+    ret = L.freesasa_gpu_trajectory_file_topology(enc(frames_path), bits, header_bytes, n_frames, C.byref(cb), structure, fa_,
+                                                  None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  selection.handle if selection is not None else None, alg, probe, resolution,
+                                                  frames_per_batch, enc(totals_path), enc(sasa_path), enc(class_sums_path),
+                                                  enc(residues_path), enc(selections_path),
+                                                  None if sel_atoms is None else sel_atoms.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                                  enc(done_path), max_new_shards, dp_, nd, C.byref(total), err, 512)
+    if ret < 0:
+        raise RuntimeError("freesasa_gpu_trajectory_file_topology: " + err.value.decode())
+    return ret == 0, int(total.value), sel_atoms
+
+
 def parse_files_dev(paths, ingest_options=0, n_threads=0, device=0, classifier=None):
     """freesasa_gpu_parse_files(): the device-side PDB / mmCIF parser on its own -> (xyz [atoms, 3], radii, classes,
     offsets [n + 1], status [n], refused [n]); a refused file (the sweep hands it to the host parser) contributes no atoms.

@@ -37,6 +37,7 @@
 #include "lr2_kernels.h"
 #include "group_kernels.h"
 #include "select_kernels.h"
+#include "traj_kernels.h"
 #include "gpu_parse.h"
 
 /* ------------------------------------------------------------------ kernel launchers (gpu_kernels.hip) */
@@ -84,6 +85,14 @@ hipError_t kl_gid_label(const sasa::GidLabelArgs &a, hipStream_t st);
    structure and SEL_G selections) */
 hipError_t kl_sel_mask(const sasa::SelArgs &a, hipStream_t st);
 hipError_t kl_sel_sums(const sasa::SelArgs &a, hipStream_t st);
+
+/* the trajectory drivers' topology (traj_kernels.h): full frames (fp64, or fp32 widened on the way) -> the compact frames the
+   engine reads; per-frame residue areas (one thread per frame and residue), class sums (one workgroup per frame) and
+   selection areas (one workgroup per frame and SEL_G selections) */
+hipError_t kl_traj_gather(const sasa::TrajArgs &a, const void *d_in, bool in_f32, double *d_out, hipStream_t st);
+hipError_t kl_traj_residues(const sasa::TrajArgs &a, hipStream_t st);
+hipError_t kl_traj_class(const sasa::TrajArgs &a, hipStream_t st);
+hipError_t kl_traj_sel(const sasa::TrajArgs &a, hipStream_t st);
 
 /* ------------------------------------------------------------------ context (gpu_engine.hip) */
 

@@ -868,6 +868,54 @@ hipError_t kl_sel_sums(const SelArgs &a, hipStream_t st)
     return hipGetLastError();
 }
 
+/* the trajectory drivers' topology (traj_kernels.h): the gather in front of the engine, the per-frame sums behind it */
+template <class T>
+__global__ __launch_bounds__(TRAJ_B) void k_traj_gather(TrajArgs a, const T *in, double *out)
+{
+    traj_gather(a, in, out, (int64_t)blockIdx.x * TRAJ_B + threadIdx.x);
+}
+__global__ __launch_bounds__(TRAJ_B) void k_traj_residues(TrajArgs a)
+{
+    traj_residue(a, (int64_t)blockIdx.x * TRAJ_B + threadIdx.x);
+}
+__global__ __launch_bounds__(SASA_TOT_B) void k_traj_class(TrajArgs a)
+{
+    __shared__ double part[3 * SASA_TOT_B];
+    traj_class_phase0(a, part, blockIdx.x, threadIdx.x);
+    __syncthreads();
+    class_phase1(part, a.cls_out, blockIdx.x, threadIdx.x);
+}
+__global__ __launch_bounds__(SASA_TOT_B) void k_traj_sel(TrajArgs a)
+{
+    __shared__ double part[SEL_G * SASA_TOT_B];
+    __shared__ int cnt[SEL_G * SASA_TOT_B];
+    traj_sel_phase0(a, part, cnt, blockIdx.x, blockIdx.y * SEL_G, threadIdx.x);
+    __syncthreads();
+    traj_sel_phase1(a, part, cnt, blockIdx.x, blockIdx.y * SEL_G, threadIdx.x);
+}
+hipError_t kl_traj_gather(const TrajArgs &a, const void *d_in, bool in_f32, double *d_out, hipStream_t st)
+{
+    const unsigned grid = (unsigned)((3 * (int64_t)a.n_frames * a.n + TRAJ_B - 1) / TRAJ_B);
+    if (in_f32) hipLaunchKernelGGL(k_traj_gather<float>, dim3(grid), dim3(TRAJ_B), 0, st, a, (const float *)d_in, d_out);
+    else hipLaunchKernelGGL(k_traj_gather<double>, dim3(grid), dim3(TRAJ_B), 0, st, a, (const double *)d_in, d_out);
+    return hipGetLastError();
+}
+hipError_t kl_traj_residues(const TrajArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_traj_residues, dim3((unsigned)(((int64_t)a.n_frames * a.n_res + TRAJ_B - 1) / TRAJ_B)), dim3(TRAJ_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_traj_class(const TrajArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_traj_class, dim3((unsigned)a.n_frames), dim3(SASA_TOT_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_traj_sel(const TrajArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_traj_sel, dim3((unsigned)a.n_frames, (unsigned)((a.n_sel + SEL_G - 1) / SEL_G)), dim3(SASA_TOT_B), 0, st, a);
+    return hipGetLastError();
+}
+
 void kl_dump_phase_clocks(void)
 {
 #ifdef SASA_PHASE_TIMING

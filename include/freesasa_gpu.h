@@ -286,7 +286,8 @@ long long freesasa_gpu_parse_files_classified(const char *const *paths, int n_pa
    every sweep.  The table's arrays are ONE block, released by freesasa_gpu_residue_table_free only (which zeroes the struct;
    a zeroed struct is a no-op); on any failure (-1, message in err) the struct is zeroed and nothing is kept.
    Not offered: a done-list / resumable form (records of variable length need a file format of their own), the cache sweep
-   (a cache read brings coordinates, radii and classes, no residue arrays), per-residue output of the trajectory drivers. */
+   (a cache read brings coordinates, radii and classes, no residue arrays).  (Per-residue output of the trajectory drivers:
+   freesasa_gpu_trajectory_topology below.) */
 typedef struct freesasa_gpu_residue_table {
     int32_t n_files;
     int64_t n_residues;
@@ -322,8 +323,8 @@ void freesasa_gpu_residue_table_free(freesasa_gpu_residue_table *table);
    residues are built on the device (csrc/gpu_parse.hip: kp_atom_keys, kp_res_*); files the host parser read - all of them
    without that option, the refused ones with it - have theirs uploaded (8 bytes per atom, 22 per residue).
    Both return 0 / -1 with the message in err.
-   Not offered: a done-list / resumable form, the cache sweep (a cache read brings no names or residue arrays), selections
-   in the trajectory drivers. */
+   Not offered: a done-list / resumable form, the cache sweep (a cache read brings no names or residue arrays).  (Selections
+   in the trajectory drivers: freesasa_gpu_trajectory_topology below.) */
 struct freesasa_ingest_selection;
 struct freesasa_ingest_batch;
 int freesasa_gpu_select_batch(const struct freesasa_ingest_batch *batch, const struct freesasa_ingest_selection *sel,
@@ -423,6 +424,58 @@ int freesasa_gpu_trajectory(const double *xyz_frames, const double *radii, int n
                             int alg, double probe_radius, int resolution, int frames_per_batch,
                             double *totals_out, double *sasa_out, int device,
                             char *err_out, int err_len);
+
+/* Trajectory drivers with a TOPOLOGY: the solute of a solvated system, its residues, its classes and a set of selections,
+   per frame.  The arguments of freesasa_gpu_trajectory_devices / freesasa_gpu_trajectory_file_devices with the pair
+   (radii, n_atoms) replaced by
+     batch, structure   structure `structure` of a loaded batch (include/freesasa_ingest.h) supplies what the kernels read:
+                        its n atoms with their radii, classes, backbone flags, names and symbols, and its residues
+                        (boundaries rebased to the structure, labels).  Its coordinates are not used.
+     frame_atoms, atom_index   every input frame holds frame_atoms >= n atoms (3 * frame_atoms numbers); topology atom i
+                        is frame atom atom_index[i] - any order, every index in [0, frame_atoms), none twice (two atoms
+                        at one place give NaN).  atom_index NULL: the identity, and frame_atoms must be n.  The other
+                        atoms of a frame - the solvent - go up with it and are dropped on the device by one gather
+                        kernel (fp32 frames are widened by the same kernel); no index: the plain drivers' path.
+     sel                a compiled set of up to 64 selections (freesasa_ingest_selection_compile) or NULL.
+   Outputs, all fp64 and in frame order; each may be NULL (not wanted) except the totals.  Memory form: arrays; file form:
+   paths of files whose offsets the frame number fixes, written by pwrite per shard like the totals file:
+     totals      1 per frame          (8 f)            what the plain drivers give for the topology's atoms
+     per-atom    n per frame          (8 n f)          likewise (file form: fp32 when bit 1 of frames_f32 is set)
+     class sums  3 per frame          (8 * 3 f)        apolar, polar, unknown: freesasa_gpu_class_sums_dev on the frame
+     residues    6 R per frame        (8 * 6 R f)      total, main chain, side chain, polar, apolar, unknown of the
+                                                       structure's R residues: d_abs of freesasa_gpu_residue_areas_dev
+     selections  S per frame          (8 S f)          area_out of freesasa_gpu_select_batch
+   each bit for bit what the named entry gives on the frame taken as a structure of its own.  sel_atoms_out [S] (may be
+   NULL): the atoms every selection holds - they do not depend on the frame and come back once, with the first shard a
+   call computes (a resumed call that finds every shard done leaves the array as it is).  RELATIVE areas are not written:
+   they are the residue columns divided by constants - 100 * column / freesasa_ingest_residue_reference_table()[5 *
+   res_ref[r] + column] for the first five columns, where the structure's res_ref[r] >= 0.
+   The residue boundaries, classes, backbone flags, the index and the selections' mask words (the set's program run once
+   over the topology; open ranges take the structure's first and last residue) are made once per lane and stay on the
+   device; per shard a gather and three kinds of ordered sums run on the lane's stream behind the tile kernels, and their
+   results ride in front of the shard's one stream synchronisation.  Per-atom areas leave the device only when asked for.
+   frames_per_batch <= 0: 1250000 / frame_atoms + 1.
+   The done-list's first line also names the index, frame_atoms, the structure's residue boundaries, classes and backbone
+   flags, the selection set's program and which outputs are written: a done-list that differs in any of these - or one
+   of the plain drivers - is refused; every result file is flushed before its shard is listed.
+   Argument errors - NULL batch, structure out of range, a structure that failed to load or has no atoms, a bad index,
+   frame_atoms < n - return -1 with a message before a device is touched or a file opened.
+   Returns as the plain drivers: 0 / -1, the file form 1 when max_new_shards stopped it.
+   Not offered: chain groups in the trajectory drivers, relative areas in files, trajectory container formats. */
+int freesasa_gpu_trajectory_topology(const double *xyz_frames, int n_frames, const struct freesasa_ingest_batch *batch, int structure,
+                                     int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
+                                     int alg, double probe_radius, int resolution, int frames_per_batch,
+                                     double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
+                                     double *sel_area_out, long long *sel_atoms_out,
+                                     const int *devices, int n_devices, char *err, int err_len);
+int freesasa_gpu_trajectory_file_topology(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
+                                          const struct freesasa_ingest_batch *batch, int structure,
+                                          int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
+                                          int alg, double probe_radius, int resolution, int frames_per_batch,
+                                          const char *totals_path, const char *sasa_path, const char *class_sums_path,
+                                          const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
+                                          const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                          long long *frames_total_out, char *err, int err_len);
 
 /* Chain groups: the area of every atom in its complex AND in its group taken on its own (the reference's
    --chain-groups / --separate-chains: freesasa_structure_get_chains_lcl, src/structure.c:1026-1080, minus the

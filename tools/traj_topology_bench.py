@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""What a topology costs the trajectory file driver (freesasa_gpu_trajectory_file_topology): frames of a 100 000-atom solvated
+system (fp32, page cache warm) whose solute is a 10 000-atom poly-alanine globule at the front of every frame, the other
+90 000 atoms solvent that the gather drops on the device.  Arms, alternating, each run after one warm-up pass:
+
+    plain     trajectory_file on frames of the 10 000 solute atoms alone, totals only (what a caller who strips the
+              solvent on the host would run; the stripping itself is not timed)
+    totals    trajectory_file_topology on the full frames, totals only
+    all       ... with class sums, per-residue areas (2000 residues) and 8 selections
+
+One JSON line per arm: atom-frames/s counted in SOLUTE atoms and in frame atoms, the median and the spread of --reps runs.
+
+    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--scratch DIR] [--out FILE]
+
+For the kernel times: `rocprofv3 --kernel-trace --stats -- python tools/traj_topology_bench.py --reps 1 --arms all`
+(k_traj_gather / k_traj_residues / k_traj_class / k_traj_sel are the topology's kernels)."""
+import argparse
+import json
+import os
+import shutil
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import freesasa_amd as fa          # noqa: E402
+import tools                       # noqa: E402
+from freesasa_amd import ingest    # noqa: E402
+
+N_SOLUTE, N_FRAME = 10_000, 100_000
+EIGHT = ["bb, name n+ca+c+o", "cb, name cb", "r, resi 10-200 and not symbol c", "open, resi -50 or resi 1900-", "ch, chain A",
+         "o, symbol o", "n, symbol n and resi 500-1500", "none, resn gly"]
+
+
+def solute():
+    """a poly-alanine of 2000 residues on the positions of tools.globule: (batch of one structure, xyz [n, 3])"""
+    xyz, _ = tools.globule(N_SOLUTE, 11)
+    xyz = xyz - xyz.mean(0)
+    names = [(" N  ", "N"), (" CA ", "C"), (" C  ", "C"), (" O  ", "O"), (" CB ", "C")]
+    lines = []
+    for i, (x, y, z) in enumerate(xyz):
+        nm, el = names[i % 5]
+        lines.append("ATOM  %5d %s ALA A%4d    %8.3f%8.3f%8.3f  1.00  0.00          %2s" % ((i + 1) % 100000, nm, i // 5 + 1, x, y, z, el))
+    b = ingest.load_pdb_texts(["\n".join(lines) + "\nEND\n"])
+    assert b.status[0] == 0 and b.n_atoms == N_SOLUTE and b.n_residues == N_SOLUTE // 5
+    return b, b.xyz.copy()
+
+
+def make_frames(scratch, xyz, n_frames):
+    full, bare = os.path.join(scratch, "solvated.f32"), os.path.join(scratch, "solute.f32")
+    rng = np.random.default_rng(5)
+    half = 1.3 * np.abs(xyz).max()
+    with open(full, "wb") as f_full, open(bare, "wb") as f_bare:
+        for f in range(n_frames):
+            s = (xyz + rng.uniform(-0.25, 0.25, xyz.shape)).astype(np.float32)
+            w = rng.uniform(-half, half, (N_FRAME - N_SOLUTE, 3)).astype(np.float32)
+            s.tofile(f_bare)
+            np.concatenate([s, w]).tofile(f_full)
+    return full, bare
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=240)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--arms", default="plain,totals,all")
+    ap.add_argument("--scratch", default=None)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    scratch = args.scratch or tempfile.mkdtemp(prefix="traj_topology_bench_")
+    try:
+        b, xyz = solute()
+        full, bare = make_frames(scratch, xyz, args.frames)
+        sel = ingest.Selection(EIGHT)
+        index = np.arange(N_SOLUTE, dtype=np.int32)
+        p = lambda k: os.path.join(scratch, k)
+        arms = {
+            "plain": lambda: fa.trajectory_file(bare, b.radii, p("t0"), f32=True),
+            "totals": lambda: fa.trajectory_file_topology(full, b, p("t1"), atom_index=index, frame_atoms=N_FRAME, f32=True),
+            "all": lambda: fa.trajectory_file_topology(full, b, p("t2"), atom_index=index, frame_atoms=N_FRAME, f32=True, selection=sel,
+                                                       class_sums_path=p("c2"), residues_path=p("r2"), selections_path=p("s2")),
+        }
+        names = [a for a in args.arms.split(",") if a in arms]
+        runs = {a: [] for a in names}
+        for a in names:
+            arms[a]()                                                    # warm-up: contexts, staging, page cache
+        for _ in range(args.reps):
+            for a in names:
+                t0 = time.perf_counter()
+                res = arms[a]()
+                runs[a].append(time.perf_counter() - t0)
+                assert res[0] and res[1] == args.frames
+        assert not names or np.array_equal(np.fromfile(p("t0" if "plain" in names else "t1")), np.fromfile(p({"plain": "t0", "totals": "t1", "all": "t2"}[names[-1]])))
+        lines = []
+        for a in names:
+            v = sorted(runs[a])
+            med = v[len(v) // 2]
+            lines.append(json.dumps({"arm": a, "frames": args.frames, "frame_atoms": N_SOLUTE if a == "plain" else N_FRAME, "solute_atoms": N_SOLUTE,
+                                     "median_seconds": med, "min_seconds": v[0], "max_seconds": v[-1],
+                                     "solute_atom_frames_per_s": N_SOLUTE * args.frames / med,
+                                     "frame_atom_frames_per_s": (N_SOLUTE if a == "plain" else N_FRAME) * args.frames / med, "runs": len(v)}))
+        print("\n".join(lines))
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+    finally:
+        if not args.scratch:
+            shutil.rmtree(scratch, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    main()
