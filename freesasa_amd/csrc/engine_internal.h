@@ -369,6 +369,16 @@ struct FirstError {
     }
 };
 
+/* The lanes (workers) of a driver: bodies 1 .. n-1 on threads of their own, started in that order, body 0 on the calling
+   thread unless something has failed by then; all joined on the way out.  The bodies report through `fe` themselves. */
+template <class F> void run_lanes(int n, FirstError &fe, F &&body)
+{
+    ThreadGroup tg;
+    for (int k = 1; k < n; ++k)
+        if (!tg.spawn(body, k)) { fe.set("could not start a worker thread"); break; }
+    if (n > 0 && !fe.failed.load()) body(0);
+}
+
 /* The done-list of a resumable run: a first line that names the run (built by its driver), then "shard <unit> <a> <b>" per
    finished unit (a batch of files, a shard of frames), appended by one worker at a time once the unit's results are on disk.
    read: FRESH (no list, or an empty one), RESUMED (the list of this run: its complete lines that valid() accepts are done

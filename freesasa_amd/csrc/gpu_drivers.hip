@@ -15,6 +15,7 @@
  * and grants 16) are divided among the devices' loaders.  A device may appear in the list more than once (its units
  * then overlap their copies and kernels; the tests run device lists [0, 0, 0] and [0] * 8 on a one-GPU box).
  * Results are bit-identical to the single-device drivers': a unit's numbers do not depend on who computed it.
+ * The lanes of every driver are started by run_lanes (engine_internal.h): lane 0 is the calling thread.
  */
 #include <hip/hip_runtime.h>
 
@@ -240,12 +241,7 @@ int sweep_cache_impl(const char *cache_path, int alg, double probe, int resoluti
         fe.set_exception();
       }
     };
-    {
-        ThreadGroup tg;
-        for (int k = 1; k < n_lanes; ++k)
-            if (!tg.spawn(lane, k)) { fe.set("could not start a worker thread"); break; }
-        if (n_lanes > 0 && !fe.failed.load()) lane(0);
-    }
+    run_lanes(n_lanes, fe, lane);
     if (fe.failed.load()) return set_err(err_out, err_len, fe.text);
     return 0;
     });
@@ -260,20 +256,37 @@ int sweep_cache_impl(const char *cache_path, int alg, double probe, int resoluti
  *     the arithmetic stays fp64] -> cell sort + tile kernels -> device-to-host -> write (memory or files)
  * while the other lanes are in another stage.  The radii live once per device context (shared by every frame of
  * a batch).  With a done-list file every finished shard is recorded after its results are on disk; a later call
- * with the same parameters skips the recorded shards: an interrupted run resumes — on any list of devices. */
+ * with the same parameters skips the recorded shards: an interrupted run resumes — on any list of devices.
+ *
+ * The shape is the file sweep's (gpu_sweep.hip): TrajSpec is what an entry was called with, TrajIO where the frames come
+ * from and ONE TABLE of the per-frame outputs (TrajOut), TrajRun what the lanes of a run share, TrajLane a lane's context,
+ * TrajShard the shard in its hands.  A shard goes through shard_size -> _read -> _upload -> _compute -> _download -> _write
+ * -> _record (shard_run), each 0 or -1 with the context's message; traj_lane takes shards until none is left and on a
+ * failure drains its stream and sets the run's first error. */
+
+/* One per-frame OUTPUT of a run: a row of TrajIO's table.  An entry point says where it goes - the caller's array or a
+   result file - and everything else that is per output (opening the files, is it wanted, its place in a shard's blocks, the
+   copy or the pwrite at the frame's offset, the flush, the done-list's outputs= word) is a loop over the table. */
+enum { OUT_TOTALS, OUT_SASA, OUT_CLS, OUT_RES, OUT_SEL, N_OUT };
+struct TrajOut {
+    const char *name;           /* in messages: "cannot open the %s file", "could not write the %s file" */
+    int bit;                    /* in the outputs= word of a done-list's first line */
+    void *mem = nullptr;        /* the caller's array [n_frames * per_frame] ... */
+    const char *path = nullptr; /* ... or a result file, */
+    Fd f;                       /* open for the length of the run */
+    size_t esz = 8, per_frame = 0; /* bytes per value (4: per-atom areas asked for as fp32); (TrajRun) values per frame, 0: not computed */
+    bool wanted() const { return mem || path; }
+};
 struct TrajIO {
     const double *mem_in = nullptr; /* frames in host memory (fp64) ... */
-    int fd_in = -1;                 /* ... or in a file of raw frames */
-    int in_f32 = 0;
+    Fd in;                          /* ... or in a file of raw frames */
     long long in_header = 0;
-    double *totals_mem = nullptr, *sasa_mem = nullptr;
-    int fd_totals = -1, fd_sasa = -1;
-    DoneList *list = nullptr;       /* (file runs with a done-list) */
-    int out_f32 = 0;                /* per-atom areas written as fp32 (narrowed on the device; an output format) */
-    /* runs with a topology: class sums [3], residue areas [6 R], selection areas [S] per frame; the selections' atoms once */
-    double *cls_mem = nullptr, *res_mem = nullptr, *sel_mem = nullptr;
-    long long *sel_atoms = nullptr;
-    int fd_cls = -1, fd_res = -1, fd_sel = -1;
+    int in_f32 = 0;
+    /* per frame: total [1], per-atom areas [n]; runs with a topology: class sums [3], residue areas [6 R], selection areas [S] */
+    TrajOut out[N_OUT] = {{"totals", 0}, {"per-atom", 1}, {"class-sums", 2}, {"residues", 4}, {"selections", 8}};
+    long long *sel_atoms = nullptr; /* the selections' atoms [S]: frame-independent, delivered once */
+    bool out_f32() const { return out[OUT_SASA].esz == 4; } /* per-atom areas written as fp32 (narrowed on the device; an output format) */
+    DoneList list;                  /* (active: a file run with a done-list) */
 };
 
 /* The TOPOLOGY of a trajectory (include/freesasa_gpu.h, freesasa_gpu_trajectory_topology): one structure of a loaded batch
@@ -388,198 +401,266 @@ int topo_upload(freesasa_gpu_ctx *c, const TrajTopo &tp, sasa::TrajArgs &ta)
     return 0;
 }
 
-/* returns 0: all shards done, 1: stopped after max_new shards (more left), -1: error */
-int traj_run(TrajIO &io, const double *radii, int n_atoms, long long n_frames, int alg, double probe, int resolution,
-             int frames_per_batch, int lanes_per_device, long long max_new, const int *devices, int n_devices, char *err_out, int err_len,
-             const TrajTopo *topo = nullptr)
+/* what a trajectory entry was called with */
+struct TrajSpec {
+    const double *radii; int n_atoms; long long n_frames; int alg; double probe; int resolution, frames_per_batch;
+    const int *devices; int n_devices;
+    const TrajTopo *topo = nullptr;
+    long long max_new = 0; /* (file runs) stop after this many new shards */
+};
+
+/* The checks every entry makes of its arguments, in every entry's order.  sizes_msg: the entry's wording for "no atoms or no
+   frames" (NULL: it has made that check in its own terms). */
+int traj_check_args(const TrajSpec &s, const char *sizes_msg, char *err_out, int err_len)
 {
-    return guarded(err_out, err_len, [&]() -> int {
-    const size_t n = (size_t)n_atoms, FB = (size_t)frames_per_batch;
-    const long long n_shards = (n_frames + frames_per_batch - 1) / frames_per_batch;
-    if (lanes_per_device <= 0) {
-        /* three lanes keep one device's PCIe in, kernels and PCIe out busy (measured, round 2; round 6, from and to files on the
-           MI355X box, 600 frames x 100 000 atoms: 3 lanes 2.97e8, 6 lanes 3.10e8 atom-frames/s with two of the three contexts
-           cold - the kernel trace shows the tile kernels of the lanes back to back, 2.9 ms per shard of 1.2e6 atoms: the
-           driver runs at the rate of the kernels); with several devices the lanes also share the granted
-           CPUs (a lane reads, copies and writes on the host): two each at least */
-        const int per = process_cpus() / n_devices;
-        lanes_per_device = per >= 3 ? 3 : 2;
-        if (const char *e = getenv("FREESASA_AMD_TRAJ_LANES")) lanes_per_device = atoi(e) > 0 ? atoi(e) : lanes_per_device; /* tuning aid */
-    }
-    if (lanes_per_device > 8) lanes_per_device = 8;
-    int n_lanes = lanes_per_device * n_devices;
-    if (n_lanes > n_shards) n_lanes = (int)n_shards;
-    std::vector<double> tp;
-    if (alg == 1) { tp.resize(3 * (size_t)resolution); freesasa_gpu_test_points(resolution, tp.data()); }
-    std::vector<int64_t> offs(FB + 1);
-    for (size_t k = 0; k <= FB; ++k) offs[k] = (int64_t)(k * n);
-    const bool in_pinned = io.mem_in && host_pinned(io.mem_in);
-    const bool out_pinned = io.totals_mem && host_pinned(io.totals_mem) && (!io.sasa_mem || host_pinned(io.sasa_mem));
-    const bool want_sasa = io.sasa_mem || io.fd_sasa >= 0;
-    /* a topology: frames of fa atoms come in (the gather makes the engine's n of them), and per frame xw more numbers go out */
+    if (sizes_msg && (s.n_atoms <= 0 || s.n_frames <= 0)) return set_err(err_out, err_len, sizes_msg);
+    if (s.alg != 0 && s.alg != 1) return set_err(err_out, err_len, "unknown algorithm");
+    if (s.resolution <= 0) return set_err(err_out, err_len, "resolution must be > 0");
+    return check_devices(s.devices, s.n_devices, err_out, err_len);
+}
+/* ... and the size of a shard, once the number of frames is known (a file run asks the file).  The default goes by the atoms
+   that come IN: with a topology the staging of a mostly-solvent frame stays what the plain drivers' is (not measured whether
+   sizing by the kept atoms, i.e. longer shards for the engine, would be faster). */
+int traj_shard_size(TrajSpec &s, long long frame_atoms, char *err_out, int err_len)
+{
+    if (s.frames_per_batch <= 0) s.frames_per_batch = (int)(1250000 / frame_atoms) + 1;
+    if (s.frames_per_batch > s.n_frames) s.frames_per_batch = (int)s.n_frames;
+    return (long long)s.frames_per_batch * frame_atoms > (1LL << 30) ? set_err(err_out, err_len, "batch too large") : 0;
+}
+
+/* what the lanes of one run share */
+struct TrajRun {
+    const TrajSpec &s;
+    TrajIO &io;
+    const TrajTopo *const topo = s.topo;
+    const size_t n = (size_t)s.n_atoms, FB = (size_t)s.frames_per_batch; /* atoms the engine sees, frames of a full shard */
+    const long long n_shards = (s.n_frames + s.frames_per_batch - 1) / s.frames_per_batch;
+    /* a topology: frames of fa atoms come in (with an index the gather makes the engine's n of them); esz bytes per atom */
     const bool gather = topo && topo->index;
     const size_t fa = topo ? (size_t)topo->frame_atoms : n, esz = io.in_f32 ? 12 : 24;
     const size_t widen_bytes = io.in_f32 && !gather ? 12 * n * FB : 0; /* (fp32 frames without an index: kl_widen_f32's input) */
-    const bool want_cls = topo && (io.cls_mem || io.fd_cls >= 0), want_res = topo && (io.res_mem || io.fd_res >= 0);
-    const bool want_sel = topo && topo->sel && (io.sel_mem || io.fd_sel >= 0 || io.sel_atoms);
-    const size_t R = topo ? (size_t)topo->n_res : 0, S = want_sel ? (size_t)topo->n_sel : 0;
-    const size_t xw = (want_cls ? 3 : 0) + (want_res ? 6 * R : 0) + 2 * S;
-    std::atomic<long long> next(0), fresh(0);
-    std::atomic<int> stopped(0), counts_out(0);
+    /* the caller's arrays are page-locked: no staging */
+    const bool in_pinned = io.mem_in && host_pinned(io.mem_in);
+    const bool direct_out = io.out[OUT_TOTALS].mem && host_pinned(io.out[OUT_TOTALS].mem) && (!io.out[OUT_SASA].mem || host_pinned(io.out[OUT_SASA].mem));
+    const size_t S = topo && topo->sel && (io.out[OUT_SEL].wanted() || io.sel_atoms) ? (size_t)topo->n_sel : 0; /* selections computed */
+    /* A shard's sums lie one behind the other in ONE block, cut to its nf frames: classes | residues | selection areas |
+       selected atoms.  Output k's begin at x0[k] * nf doubles (k = N_OUT: the atom counts); xw doubles per frame hold it all. */
+    size_t x0[N_OUT + 1] = {0, 0, 0}, xw;
+    std::vector<double> tp;    /* S&R test points */
+    std::vector<int64_t> offs; /* a full shard as a batch: k n */
+    std::atomic<long long> next{0}, fresh{0};
+    std::atomic<int> stopped{0}, counts_out{0};
     FirstError fe;
     /* dev aid (FREESASA_AMD_TRAJ_PROFILE): where the lanes' host time goes - read, waiting for the device, write, flush */
     const bool prof = getenv("FREESASA_AMD_TRAJ_PROFILE") != nullptr;
-    std::atomic<long long> t_read(0), t_dev(0), t_write(0), t_flush(0);
-    auto now_ns = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (long long)ts.tv_sec * 1000000000LL + ts.tv_nsec; };
-    auto lane = [&](int id) noexcept {
-      try {
-        DeviceNodeScope node(devices[id % n_devices]); /* the lane and its page-locked staging on the device's NUMA node */
-        PoolLease lease(devices[id % n_devices]); /* lanes 0 .. n_devices-1 open one device each, the next n_devices the second lane of each, ... */
-        freesasa_gpu_ctx *c = lease.c;
-        if (!c) { fe.set("could not create a GPU context"); return; }
-        bool radii_up = false, topo_up = false;
-        sasa::TrajArgs ta;
-        for (;;) {
-            const long long k = next.fetch_add(1);
-            if (k >= n_shards || fe.failed.load()) break;
-            if (io.list && io.list->done(k)) continue;
-            if (max_new > 0 && fresh.fetch_add(1) >= max_new) { stopped = 1; break; }
-            const long long f0 = k * frames_per_batch;
-            const int nf = (int)(n_frames - f0 < frames_per_batch ? n_frames - f0 : frames_per_batch);
-            const size_t na = n * (size_t)nf;
-            const size_t in_bytes = esz * fa * (size_t)nf;
-            int rc = -1;
-            do {
-                if (hipSetDevice(c->device) != hipSuccess) { ctx_fail(c, "hipSetDevice failed"); break; }
-                if (ensure(c, c->h_xyz, 24 * n * FB) || ensure(c, c->h_radii, 8 * n) || ensure(c, c->h_sasa, 8 * n * FB) ||
-                    ensure(c, c->h_totals, 8 * FB) || ((widen_bytes || io.out_f32) && ensure(c, c->h_counts, widen_bytes + (io.out_f32 ? 4 * n * FB : 0))) ||
-                    (gather && ensure(c, c->g_xyz, esz * fa * FB)) || (xw && ensure(c, c->h_gtot, 8 * xw * FB)))
-                    break;
-                if (!radii_up) { /* once per lane: the radii of the system */
-                    if (hipMemcpyAsync(c->h_radii.p, radii, 8 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) { ctx_fail(c, "radii upload failed"); break; }
-                    radii_up = true;
-                }
-                if (topo && !topo_up) { /* ... and its topology */
-                    if (topo_upload(c, *topo, ta)) break;
-                    topo_up = true;
-                }
-                const void *src;
-                long long tp0 = prof ? now_ns() : 0;
-                if (io.mem_in && in_pinned) {
-                    src = io.mem_in + 3 * fa * (size_t)f0;
-                } else {
-                    if (ensure_pinned(c, &c->stage_in, &c->stage_in_cap, in_bytes)) break;
-                    if (io.mem_in) memcpy(c->stage_in, io.mem_in + 3 * fa * (size_t)f0, in_bytes);
-                    else if (!pread_all(io.fd_in, c->stage_in, in_bytes, io.in_header + (long long)esz * (long long)fa * f0)) {
-                        ctx_fail(c, "could not read frames %lld..%lld of the frame file", f0, f0 + nf - 1);
-                        break;
-                    }
-                    src = c->stage_in;
-                }
-                if (prof) { const long long t = now_ns(); t_read += t - tp0; tp0 = t; }
-                if (gather) { /* full frames up as they were read; one kernel drops the solvent and widens fp32 */
-                    if (hipMemcpyAsync(c->g_xyz.p, src, in_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) { ctx_fail(c, "host-to-device copy failed"); break; }
-                    ta.n_frames = nf;
-                    if (kl_traj_gather(ta, c->g_xyz.p, io.in_f32 != 0, (double *)c->h_xyz.p, c->stream) != hipSuccess) { ctx_fail(c, "gather launch failed"); break; }
-                } else if (io.in_f32) {
-                    if (hipMemcpyAsync(c->h_counts.p, src, in_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) { ctx_fail(c, "host-to-device copy failed"); break; }
-                    if (kl_widen_f32((const float *)c->h_counts.p, (double *)c->h_xyz.p, (long long)(3 * na), c->stream) != hipSuccess) { ctx_fail(c, "widening launch failed"); break; }
-                } else if (hipMemcpyAsync(c->h_xyz.p, src, in_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
-                    ctx_fail(c, "host-to-device copy failed");
-                    break;
-                }
-                c->shared_radii = true;
-                const int rb = run_batch(c, alg == 0, (double *)c->h_xyz.p, (double *)c->h_radii.p, offs.data(), nf, probe, resolution,
-                                         alg == 1 ? tp.data() : nullptr, (double *)c->h_sasa.p, nullptr, (double *)c->h_totals.p);
-                c->shared_radii = false;
-                if (rb) break;
-                double *dst_tot = io.totals_mem ? io.totals_mem + f0 : nullptr, *dst_sasa = io.sasa_mem ? io.sasa_mem + n * (size_t)f0 : nullptr;
-                const bool staged = !(io.totals_mem && out_pinned);
-                const size_t eb = io.out_f32 ? 4 : 8; /* bytes per per-atom area in the result file */
-                if (staged) {
-                    if (ensure_pinned(c, &c->stage_out, &c->stage_out_cap, 8 * (size_t)nf + (want_sasa ? 8 * na : 0))) break;
-                    dst_tot = (double *)c->stage_out;
-                    dst_sasa = want_sasa ? (double *)c->stage_out + nf : nullptr;
-                }
-                const void *d_areas = c->h_sasa.p;
-                if (want_sasa && io.out_f32) { /* (file output only) narrowed on the device: half the bytes over PCIe and into the file */
-                    if (ensure(c, c->h_counts, 4 * n * FB + widen_bytes)) break;
-                    float *d32 = (float *)((char *)c->h_counts.p + widen_bytes);
-                    if (kl_narrow_f64((const double *)c->h_sasa.p, d32, (long long)na, c->stream) != hipSuccess) { ctx_fail(c, "narrowing launch failed"); break; }
-                    d_areas = d32;
-                }
-                bool ok = hipMemcpyAsync(dst_tot, c->h_totals.p, 8 * (size_t)nf, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
-                if (ok && want_sasa) ok = hipMemcpyAsync(dst_sasa, d_areas, eb * na, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
-                /* the topology's per-frame sums, behind the tile kernels on this stream; cut to this shard's nf frames they lie
-                   one behind the other in c->h_gtot - classes | residues | selection areas | selected atoms - and come back
-                   in ONE copy, in front of the shard's one synchronisation */
-                double *x_out = nullptr;
-                const size_t o_res = want_cls ? 3 * (size_t)nf : 0, o_sel = o_res + (want_res ? 6 * R * (size_t)nf : 0), o_cnt = o_sel + S * (size_t)nf;
-                if (ok && xw) {
-                    if (ensure_pinned(c, &c->res_stage, &c->res_stage_cap, 8 * xw * (size_t)nf)) break;
-                    x_out = (double *)c->res_stage;
-                    double *d_x = (double *)c->h_gtot.p;
-                    ta.n_frames = nf; ta.sasa = (const double *)c->h_sasa.p;
-                    ta.cls_out = d_x; ta.res_out = d_x + o_res; ta.sel_out = d_x + o_sel; ta.sel_count = (long long *)(d_x + o_cnt);
-                    if ((want_res && kl_traj_residues(ta, c->stream) != hipSuccess) || (want_cls && kl_traj_class(ta, c->stream) != hipSuccess) ||
-                        (want_sel && kl_traj_sel(ta, c->stream) != hipSuccess)) {
-                        ctx_fail(c, "launch of the per-frame sums failed"); break;
-                    }
-                    ok = hipMemcpyAsync(x_out, d_x, 8 * (o_cnt + S), hipMemcpyDeviceToHost, c->stream) == hipSuccess;
-                }
-                if (!ok) { ctx_fail(c, "device-to-host copy failed"); break; }
-                if (hipStreamSynchronize(c->stream) != hipSuccess) { ctx_fail(c, "stream synchronize failed"); break; }
-                if (prof) { const long long t = now_ns(); t_dev += t - tp0; tp0 = t; }
-                const long long sasa_off = (long long)eb * (long long)n * f0;
-                if (staged) {
-                    if (io.totals_mem) memcpy(io.totals_mem + f0, dst_tot, 8 * (size_t)nf);
-                    if (io.sasa_mem) memcpy(io.sasa_mem + n * (size_t)f0, dst_sasa, 8 * na);
-                    if (io.fd_totals >= 0 && !pwrite_all(io.fd_totals, dst_tot, 8 * (size_t)nf, 8 * f0)) { ctx_fail(c, "could not write the totals file"); break; }
-                    if (io.fd_sasa >= 0 && !pwrite_all(io.fd_sasa, dst_sasa, eb * na, sasa_off)) { ctx_fail(c, "could not write the per-atom file"); break; }
-                }
-                if (xw) {
-                    if (io.cls_mem) memcpy(io.cls_mem + 3 * (size_t)f0, x_out, 8 * 3 * (size_t)nf);
-                    if (io.res_mem) memcpy(io.res_mem + 6 * R * (size_t)f0, x_out + o_res, 8 * 6 * R * (size_t)nf);
-                    if (io.sel_mem) memcpy(io.sel_mem + S * (size_t)f0, x_out + o_sel, 8 * S * (size_t)nf);
-                    if (io.sel_atoms && S && !counts_out.exchange(1)) memcpy(io.sel_atoms, x_out + o_cnt, 8 * S); /* (frame-independent: once) */
-                    if (io.fd_cls >= 0 && !pwrite_all(io.fd_cls, x_out, 8 * 3 * (size_t)nf, 8 * 3 * f0)) { ctx_fail(c, "could not write the class-sums file"); break; }
-                    if (io.fd_res >= 0 && !pwrite_all(io.fd_res, x_out + o_res, 8 * 6 * R * (size_t)nf, 8 * 6 * (long long)R * f0)) { ctx_fail(c, "could not write the residues file"); break; }
-                    if (io.fd_sel >= 0 && !pwrite_all(io.fd_sel, x_out + o_sel, 8 * S * (size_t)nf, 8 * (long long)S * f0)) { ctx_fail(c, "could not write the selections file"); break; }
-                }
-                if (prof) { const long long t = now_ns(); t_write += t - tp0; tp0 = t; }
-                if (io.list) { /* results first, then the record: a shard is listed only when its numbers are on disk */
-                    const bool flushed = (io.fd_totals < 0 || fdatasync(io.fd_totals) == 0) && (io.fd_sasa < 0 || fdatasync(io.fd_sasa) == 0) &&
-                                         (io.fd_cls < 0 || fdatasync(io.fd_cls) == 0) && (io.fd_res < 0 || fdatasync(io.fd_res) == 0) &&
-                                         (io.fd_sel < 0 || fdatasync(io.fd_sel) == 0);
-                    if (!flushed) {
-                        ctx_fail(c, "could not flush the result files: the shard is not listed as done"); break;
-                    }
-                    if (io.list->append(k, f0, nf)) { ctx_fail(c, "could not append to the done-list"); break; }
-                }
-                if (prof) t_flush += now_ns() - tp0;
-                rc = 0;
-            } while (0);
-            if (rc) {
-                c->shared_radii = false;
-                (void)hipStreamSynchronize(c->stream);
-                fe.set(c->err[0] ? c->err : "trajectory shard failed");
-                break;
-            }
-        }
-      } catch (...) {
-        fe.set_exception();
-      }
-    };
+    std::atomic<long long> t_read{0}, t_dev{0}, t_write{0}, t_flush{0};
+
+    TrajRun(const TrajSpec &s_, TrajIO &io_) : s(s_), io(io_), offs(FB + 1)
     {
-        ThreadGroup tg;
-        for (int k = 1; k < n_lanes; ++k)
-            if (!tg.spawn(lane, k)) { fe.set("could not start a worker thread"); break; }
-        if (!fe.failed.load()) lane(0);
+        if (s.alg == 1) { tp.resize(3 * (size_t)s.resolution); freesasa_gpu_test_points(s.resolution, tp.data()); }
+        for (size_t k = 0; k <= FB; ++k) offs[k] = (int64_t)(k * n);
+        const size_t per[N_OUT] = {1, n, topo ? (size_t)3 : 0, topo ? 6 * (size_t)topo->n_res : 0, S};
+        for (int k = 0; k < N_OUT; ++k) {
+            io.out[k].per_frame = io.out[k].wanted() || k == OUT_SEL ? per[k] : 0;
+            if (k >= OUT_CLS) x0[k + 1] = x0[k] + io.out[k].per_frame;
+        }
+        xw = x0[N_OUT] + S;
     }
-    if (prof) fprintf(stderr, "trajectory lanes %d: per lane, ms: read %.1f  device (copies + kernels) %.1f  write %.1f  flush + done-list %.1f\n", n_lanes,
-                      1e-6 * t_read.load() / n_lanes, 1e-6 * t_dev.load() / n_lanes, 1e-6 * t_write.load() / n_lanes, 1e-6 * t_flush.load() / n_lanes);
-    if (fe.failed.load()) return set_err(err_out, err_len, fe.text);
-    return stopped.load() ? 1 : 0;
+};
+/* a lane: its pooled context and what it has put there once */
+struct TrajLane {
+    freesasa_gpu_ctx *c;
+    bool radii_up = false, topo_up = false;
+    sasa::TrajArgs ta;
+};
+/* a shard in its lane's hands: frames [f0, f0 + nf) */
+struct TrajShard {
+    long long k, f0; int nf;
+    size_t na, in_bytes; /* its atoms as the engine sees them, the bytes that come in */
+    const void *src;     /* its frames on the host (page-locked) */
+    const void *d_areas; /* its per-atom areas on the device, as they go out */
+    char *host[N_OUT];   /* where every output's values are after the download (page-locked) */
+};
+long long now_ns() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (long long)ts.tv_sec * 1000000000LL + ts.tv_nsec; }
+
+/* the device buffers, for a FULL shard (a short last one fits); once per lane the radii of the system and its topology */
+int shard_size(TrajRun &T, TrajLane &L)
+{
+    freesasa_gpu_ctx *c = L.c;
+    const size_t n = T.n, FB = T.FB, narrow_bytes = T.io.out_f32() ? 4 * n * FB : 0;
+    if (hipSetDevice(c->device) != hipSuccess) return ctx_fail(c, "hipSetDevice failed");
+    if (ensure(c, c->h_xyz, 24 * n * FB) || ensure(c, c->h_radii, 8 * n) || ensure(c, c->h_sasa, 8 * n * FB) || ensure(c, c->h_totals, 8 * FB) ||
+        (T.widen_bytes + narrow_bytes && ensure(c, c->h_counts, T.widen_bytes + narrow_bytes)) ||
+        (T.gather && ensure(c, c->g_xyz, T.esz * T.fa * FB)) || (T.xw && ensure(c, c->h_gtot, 8 * T.xw * FB)))
+        return -1;
+    if (!L.radii_up && hipMemcpyAsync(c->h_radii.p, T.s.radii, 8 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "radii upload failed");
+    if (T.topo && !L.topo_up && topo_upload(c, *T.topo, L.ta)) return -1;
+    L.radii_up = L.topo_up = true;
+    return 0;
+}
+
+/* the shard's frames in page-locked memory: the caller's own, or the lane's staging filled from memory or from the file */
+int shard_read(TrajRun &T, freesasa_gpu_ctx *c, TrajShard &h)
+{
+    h.src = T.io.mem_in ? T.io.mem_in + 3 * T.fa * (size_t)h.f0 : nullptr;
+    if (h.src && T.in_pinned) return 0;
+    if (ensure_pinned(c, &c->stage_in, &c->stage_in_cap, h.in_bytes)) return -1;
+    if (h.src) memcpy(c->stage_in, h.src, h.in_bytes);
+    else if (!pread_all(T.io.in.fd, c->stage_in, h.in_bytes, T.io.in_header + (long long)T.esz * (long long)T.fa * h.f0))
+        return ctx_fail(c, "could not read frames %lld..%lld of the frame file", h.f0, h.f0 + h.nf - 1);
+    h.src = c->stage_in;
+    return 0;
+}
+
+/* ... to the device, into the compact fp64 frames the engine reads (c->h_xyz): as they are, widened, or gathered */
+int shard_upload(TrajRun &T, TrajLane &L, const TrajShard &h)
+{
+    freesasa_gpu_ctx *c = L.c;
+    const bool f32 = T.io.in_f32 != 0;
+    void *d_in = T.gather ? c->g_xyz.p : (f32 ? c->h_counts.p : c->h_xyz.p);
+    if (hipMemcpyAsync(d_in, h.src, h.in_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "host-to-device copy failed");
+    L.ta.n_frames = h.nf;
+    /* full frames up as they were read: one kernel drops the solvent and widens fp32 */
+    if (T.gather && kl_traj_gather(L.ta, d_in, f32, (double *)c->h_xyz.p, c->stream) != hipSuccess) return ctx_fail(c, "gather launch failed");
+    if (!T.gather && f32 && kl_widen_f32((const float *)d_in, (double *)c->h_xyz.p, (long long)(3 * h.na), c->stream) != hipSuccess) return ctx_fail(c, "widening launch failed");
+    return 0;
+}
+
+/* the engine on the shard as a batch of nf structures that share their radii; behind it on the stream what is made of the
+   areas on the device: fp32 per-atom areas, the topology's per-frame sums into their block (c->h_gtot, TrajRun::x0) */
+int shard_compute(TrajRun &T, TrajLane &L, TrajShard &h)
+{
+    freesasa_gpu_ctx *c = L.c;
+    const TrajOut *out = T.io.out;
+    c->shared_radii = true;
+    const int rb = run_batch(c, T.s.alg == 0, (double *)c->h_xyz.p, (double *)c->h_radii.p, T.offs.data(), h.nf, T.s.probe, T.s.resolution,
+                             T.s.alg == 1 ? T.tp.data() : nullptr, (double *)c->h_sasa.p, nullptr, (double *)c->h_totals.p);
+    c->shared_radii = false;
+    if (rb) return -1;
+    /* (file output only) per-atom areas narrowed on the device: half the bytes over PCIe and into the file */
+    const bool narrow = out[OUT_SASA].per_frame && T.io.out_f32();
+    h.d_areas = narrow ? (char *)c->h_counts.p + T.widen_bytes : c->h_sasa.p;
+    if (narrow && kl_narrow_f64((const double *)c->h_sasa.p, (float *)h.d_areas, (long long)h.na, c->stream) != hipSuccess) return ctx_fail(c, "narrowing launch failed");
+    if (!T.xw) return 0;
+    sasa::TrajArgs &ta = L.ta; /* (n_frames: shard_upload's) */
+    double *const d_x = (double *)c->h_gtot.p;
+    const size_t nf = (size_t)h.nf;
+    ta.sasa = (const double *)c->h_sasa.p;
+    ta.cls_out = d_x; ta.res_out = d_x + T.x0[OUT_RES] * nf; ta.sel_out = d_x + T.x0[OUT_SEL] * nf; ta.sel_count = (long long *)(d_x + T.x0[N_OUT] * nf);
+    if ((out[OUT_RES].per_frame && kl_traj_residues(ta, c->stream) != hipSuccess) || (out[OUT_CLS].per_frame && kl_traj_class(ta, c->stream) != hipSuccess) ||
+        (T.S && kl_traj_sel(ta, c->stream) != hipSuccess))
+        return ctx_fail(c, "launch of the per-frame sums failed");
+    return 0;
+}
+
+/* The results to the host: totals and per-atom areas straight into the caller's arrays when those are page-locked, else into
+   c->stage_out one behind the other; the block of sums in ONE copy into c->res_stage; then the shard's one synchronisation. */
+int shard_download(TrajRun &T, freesasa_gpu_ctx *c, TrajShard &h)
+{
+    const TrajOut *out = T.io.out;
+    const size_t nf = (size_t)h.nf, sasa_bytes = out[OUT_SASA].esz * out[OUT_SASA].per_frame * nf;
+    if (!T.direct_out && ensure_pinned(c, &c->stage_out, &c->stage_out_cap, 8 * nf + 8 * out[OUT_SASA].per_frame * nf)) return -1;
+    if (T.xw && ensure_pinned(c, &c->res_stage, &c->res_stage_cap, 8 * T.xw * nf)) return -1;
+    for (int k = 0; k < N_OUT; ++k)
+        h.host[k] = k >= OUT_CLS ? (char *)c->res_stage + 8 * T.x0[k] * nf
+                  : T.direct_out ? (char *)out[k].mem + 8 * out[k].per_frame * (size_t)h.f0 : (char *)c->stage_out + (k == OUT_SASA ? 8 * nf : 0);
+    if (hipMemcpyAsync(h.host[OUT_TOTALS], c->h_totals.p, 8 * nf, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        (sasa_bytes && hipMemcpyAsync(h.host[OUT_SASA], h.d_areas, sasa_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+        (T.xw && hipMemcpyAsync(c->res_stage, c->h_gtot.p, 8 * (T.x0[N_OUT] * nf + T.S), hipMemcpyDeviceToHost, c->stream) != hipSuccess))
+        return ctx_fail(c, "device-to-host copy failed");
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return ctx_fail(c, "stream synchronize failed");
+    return 0;
+}
+
+/* every output to its place, at the frame's offset: the caller's array (unless it came straight there) or the result file */
+int shard_write(TrajRun &T, freesasa_gpu_ctx *c, const TrajShard &h)
+{
+    for (int k = 0; k < N_OUT; ++k) {
+        const TrajOut &o = T.io.out[k];
+        const size_t bytes = o.esz * o.per_frame * (size_t)h.nf;
+        const long long at = (long long)(o.esz * o.per_frame) * h.f0;
+        if (o.mem && bytes && (char *)o.mem + at != h.host[k]) memcpy((char *)o.mem + at, h.host[k], bytes);
+        if (o.f.fd >= 0 && bytes && !pwrite_all(o.f.fd, h.host[k], bytes, at)) return ctx_fail(c, "could not write the %s file", o.name);
+    }
+    if (T.io.sel_atoms && T.S && !T.counts_out.exchange(1)) memcpy(T.io.sel_atoms, (char *)c->res_stage + 8 * T.x0[N_OUT] * (size_t)h.nf, 8 * T.S); /* (frame-independent: once) */
+    return 0;
+}
+
+/* results first, then the record: a shard is listed only when its numbers are on disk */
+int shard_record(TrajRun &T, freesasa_gpu_ctx *c, const TrajShard &h)
+{
+    if (!T.io.list.active()) return 0;
+    for (const TrajOut &o : T.io.out)
+        if (o.f.fd >= 0 && fdatasync(o.f.fd) != 0) return ctx_fail(c, "could not flush the result files: the shard is not listed as done");
+    return T.io.list.append(h.k, h.f0, h.nf) ? ctx_fail(c, "could not append to the done-list") : 0;
+}
+
+/* the stages of one shard, the profile's clocks between them */
+int shard_run(TrajRun &T, TrajLane &L, TrajShard &h)
+{
+    if (shard_size(T, L)) return -1;
+    long long t0 = T.prof ? now_ns() : 0;
+    auto lap = [&](std::atomic<long long> &sum) { if (T.prof) { const long long t = now_ns(); sum += t - t0; t0 = t; } };
+    if (shard_read(T, L.c, h)) return -1;
+    lap(T.t_read);
+    if (shard_upload(T, L, h) || shard_compute(T, L, h) || shard_download(T, L.c, h)) return -1;
+    lap(T.t_dev);
+    if (shard_write(T, L.c, h)) return -1;
+    lap(T.t_write);
+    if (shard_record(T, L.c, h)) return -1;
+    lap(T.t_flush);
+    return 0;
+}
+
+/* A lane owns a pooled context of its device: lanes 0 .. n_devices-1 open one device each, the next n_devices the second
+   lane of each, ...  It takes shards from the shared counter until none is left, max_new were begun or a lane has failed. */
+void traj_lane(TrajRun &T, int id) noexcept
+{
+  try {
+    const TrajSpec &s = T.s;
+    DeviceNodeScope node(s.devices[id % s.n_devices]); /* the lane and its page-locked staging on the device's NUMA node */
+    PoolLease lease(s.devices[id % s.n_devices]);
+    TrajLane L = {lease.c};
+    if (!L.c) { T.fe.set("could not create a GPU context"); return; }
+    for (;;) {
+        TrajShard h;
+        h.k = T.next.fetch_add(1);
+        if (h.k >= T.n_shards || T.fe.failed.load()) break;
+        if (T.io.list.done(h.k)) continue;
+        if (s.max_new > 0 && T.fresh.fetch_add(1) >= s.max_new) { T.stopped = 1; break; }
+        h.f0 = h.k * s.frames_per_batch;
+        h.nf = (int)(s.n_frames - h.f0 < s.frames_per_batch ? s.n_frames - h.f0 : s.frames_per_batch);
+        h.na = T.n * (size_t)h.nf; h.in_bytes = T.esz * T.fa * (size_t)h.nf;
+        if (shard_run(T, L, h)) {
+            (void)hipStreamSynchronize(L.c->stream); /* nothing of the shard may still run when the lane lets go */
+            T.fe.set(L.c->err[0] ? L.c->err : "trajectory shard failed");
+            break;
+        }
+    }
+  } catch (...) {
+    T.fe.set_exception();
+  }
+}
+
+/* returns 0: all shards done, 1: stopped after max_new shards (more left), -1: error */
+int traj_run(TrajIO &io, const TrajSpec &s, char *err_out, int err_len)
+{
+    return guarded(err_out, err_len, [&]() -> int {
+    TrajRun T(s, io);
+    /* three lanes keep one device's PCIe in, kernels and PCIe out busy (measured, round 2; round 6, from and to files on the
+       MI355X box, 600 frames x 100 000 atoms: 3 lanes 2.97e8, 6 lanes 3.10e8 atom-frames/s with two of the three contexts
+       cold - the kernel trace shows the tile kernels of the lanes back to back, 2.9 ms per shard of 1.2e6 atoms: the
+       driver runs at the rate of the kernels); with several devices the lanes also share the granted
+       CPUs (a lane reads, copies and writes on the host): two each at least */
+    int per_device = process_cpus() / s.n_devices >= 3 ? 3 : 2;
+    if (const char *e = getenv("FREESASA_AMD_TRAJ_LANES")) per_device = atoi(e) > 0 ? atoi(e) : per_device; /* tuning aid */
+    int n_lanes = (per_device > 8 ? 8 : per_device) * s.n_devices;
+    if (n_lanes > T.n_shards) n_lanes = (int)T.n_shards;
+    run_lanes(n_lanes, T.fe, [&T](int id) noexcept { traj_lane(T, id); });
+    if (T.prof) fprintf(stderr, "trajectory lanes %d: per lane, ms: read %.1f  device (copies + kernels) %.1f  write %.1f  flush + done-list %.1f\n", n_lanes,
+                        1e-6 * T.t_read.load() / n_lanes, 1e-6 * T.t_dev.load() / n_lanes, 1e-6 * T.t_write.load() / n_lanes, 1e-6 * T.t_flush.load() / n_lanes);
+    if (T.fe.failed.load()) return set_err(err_out, err_len, T.fe.text);
+    return T.stopped.load() ? 1 : 0;
     });
 }
 
@@ -597,22 +678,18 @@ extern "C" int freesasa_gpu_sweep_cache_devices(const char *cache_path, int alg,
 
 /* ------------------------------------------------------------------ entry points: trajectories */
 
-static int trajectory_mem(const double *xyz_frames, const double *radii, int n_atoms, int n_frames, int alg, double probe, int resolution,
-                          int frames_per_batch, double *totals_out, double *sasa_out, const int *devices, int n_devices, char *err_out, int err_len)
+extern "C" int freesasa_gpu_trajectory_devices(const double *xyz_frames, const double *radii, int n_atoms, int n_frames,
+                                               int alg, double probe, int resolution, int frames_per_batch,
+                                               double *totals_out, double *sasa_out, const int *devices, int n_devices, char *err_out, int err_len)
 {
     if (err_out && err_len > 0) err_out[0] = 0;
     if (!xyz_frames || !radii || !totals_out) return set_err(err_out, err_len, "null argument");
-    if (n_atoms <= 0 || n_frames <= 0) return set_err(err_out, err_len, "n_atoms and n_frames must be > 0");
-    if (alg != 0 && alg != 1) return set_err(err_out, err_len, "unknown algorithm");
-    if (resolution <= 0) return set_err(err_out, err_len, "resolution must be > 0");
-    if (check_devices(devices, n_devices, err_out, err_len)) return -1;
-    if (frames_per_batch <= 0) frames_per_batch = (int)(1250000 / n_atoms) + 1;
-    if (frames_per_batch > n_frames) frames_per_batch = n_frames;
-    if ((long long)frames_per_batch * n_atoms > (1LL << 30)) return set_err(err_out, err_len, "batch too large");
+    TrajSpec s = {radii, n_atoms, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices};
+    if (traj_check_args(s, "n_atoms and n_frames must be > 0", err_out, err_len) || traj_shard_size(s, n_atoms, err_out, err_len)) return -1;
     return guarded(err_out, err_len, [&]() -> int {
         TrajIO io;
-        io.mem_in = xyz_frames; io.totals_mem = totals_out; io.sasa_mem = sasa_out;
-        return traj_run(io, radii, n_atoms, n_frames, alg, probe, resolution, frames_per_batch, 0, 0, devices, n_devices, err_out, err_len) < 0 ? -1 : 0;
+        io.mem_in = xyz_frames; io.out[OUT_TOTALS].mem = totals_out; io.out[OUT_SASA].mem = sasa_out;
+        return traj_run(io, s, err_out, err_len) < 0 ? -1 : 0;
     });
 }
 
@@ -620,14 +697,7 @@ extern "C" int freesasa_gpu_trajectory(const double *xyz_frames, const double *r
                                        int alg, double probe, int resolution, int frames_per_batch,
                                        double *totals_out, double *sasa_out, int device, char *err_out, int err_len)
 {
-    return trajectory_mem(xyz_frames, radii, n_atoms, n_frames, alg, probe, resolution, frames_per_batch, totals_out, sasa_out, &device, 1, err_out, err_len);
-}
-
-extern "C" int freesasa_gpu_trajectory_devices(const double *xyz_frames, const double *radii, int n_atoms, int n_frames,
-                                               int alg, double probe, int resolution, int frames_per_batch,
-                                               double *totals_out, double *sasa_out, const int *devices, int n_devices, char *err_out, int err_len)
-{
-    return trajectory_mem(xyz_frames, radii, n_atoms, n_frames, alg, probe, resolution, frames_per_batch, totals_out, sasa_out, devices, n_devices, err_out, err_len);
+    return freesasa_gpu_trajectory_devices(xyz_frames, radii, n_atoms, n_frames, alg, probe, resolution, frames_per_batch, totals_out, sasa_out, &device, 1, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_trajectory_topology(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
@@ -643,115 +713,83 @@ extern "C" int freesasa_gpu_trajectory_topology(const double *xyz_frames, int n_
         if (topo_make(batch, structure, frame_atoms, atom_index, sel, &tp, err_out, err_len)) return -1;
         if (!xyz_frames || !totals_out) return set_err(err_out, err_len, "null argument");
         if ((sel_area_out || sel_atoms_out) && !sel) return set_err(err_out, err_len, "selection outputs need a selection set");
-        if (n_frames <= 0) return set_err(err_out, err_len, "n_frames must be > 0");
-        if (alg != 0 && alg != 1) return set_err(err_out, err_len, "unknown algorithm");
-        if (resolution <= 0) return set_err(err_out, err_len, "resolution must be > 0");
-        if (check_devices(devices, n_devices, err_out, err_len)) return -1;
-        /* by the atoms that come IN: the staging of a mostly-solvent frame stays what the plain drivers' is (not measured
-           whether sizing by the kept atoms, i.e. longer shards for the engine, would be faster) */
-        if (frames_per_batch <= 0) frames_per_batch = (int)(1250000 / frame_atoms) + 1;
-        if (frames_per_batch > n_frames) frames_per_batch = n_frames;
-        if ((long long)frames_per_batch * frame_atoms > (1LL << 30)) return set_err(err_out, err_len, "batch too large");
+        TrajSpec s = {tp.radii, tp.n, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, &tp};
+        if (traj_check_args(s, "n_frames must be > 0", err_out, err_len) || traj_shard_size(s, frame_atoms, err_out, err_len)) return -1;
         TrajIO io;
-        io.mem_in = xyz_frames; io.totals_mem = totals_out; io.sasa_mem = sasa_out;
-        io.cls_mem = class_sums_out; io.res_mem = residues_out; io.sel_mem = sel_area_out; io.sel_atoms = sel_atoms_out;
-        return traj_run(io, tp.radii, tp.n, n_frames, alg, probe, resolution, frames_per_batch, 0, 0, devices, n_devices, err_out, err_len, &tp) < 0 ? -1 : 0;
+        io.mem_in = xyz_frames; io.sel_atoms = sel_atoms_out;
+        double *const mem[N_OUT] = {totals_out, sasa_out, class_sums_out, residues_out, sel_area_out};
+        for (int k = 0; k < N_OUT; ++k) io.out[k].mem = mem[k];
+        return traj_run(io, s, err_out, err_len) < 0 ? -1 : 0;
     });
 }
 
-/* Frame file -> result files, resumable (include/freesasa_gpu.h has the formats).  The done-list names its run: the
- * parameters, the frame file's size and modification time and a checksum of the radii — NOT the devices: a run
- * interrupted on eight GPUs may be finished on one, with the same files byte for byte. */
-/* (tp: a run with a topology - frames of tp->frame_atoms atoms, three more result files, a longer first line) */
-static int trajectory_file_run(const char *frames_path, int frames_f32, long long header_bytes, const double *radii,
-                               int n_atoms, long long n_frames, int alg, double probe, int resolution,
-                               int frames_per_batch, const char *totals_path, const char *sasa_path,
-                               const char *done_path, long long max_new_shards, const int *devices, int n_devices,
-                               long long *frames_total_out, char *err_out, int err_len,
-                               const TrajTopo *tp = nullptr, const char *cls_path = nullptr, const char *res_path = nullptr,
-                               const char *sel_path = nullptr, long long *sel_atoms_out = nullptr)
+/* The first line of a trajectory file run's done-list names the run: the parameters, the frame file's size and modification
+   time and a checksum of the radii - NOT the devices: a run interrupted on eight GPUs may be finished on one, with the same
+   files byte for byte.  With a topology, in front of the line's end, what its outputs depend on: digests of the index, of
+   residue boundaries + classes + backbone flags, of the selection set's program, and which result files the run writes. */
+static int traj_done_head(char *head, size_t cap, const TrajSpec &s, const TrajIO &io, const struct stat &st)
 {
-    if (!frames_path || !radii || !totals_path) return set_err(err_out, err_len, "null argument");
-    if (n_atoms <= 0 || header_bytes < 0) return set_err(err_out, err_len, "bad argument");
-    if (alg != 0 && alg != 1) return set_err(err_out, err_len, "unknown algorithm");
-    if (resolution <= 0) return set_err(err_out, err_len, "resolution must be > 0");
-    if (check_devices(devices, n_devices, err_out, err_len)) return -1;
-    return guarded(err_out, err_len, [&]() -> int {
-    TrajIO io;
-    Fd f_in, f_totals, f_sasa, f_cls, f_res, f_sel; /* (closed on every way out) */
-    const long long frame_atoms = tp ? tp->frame_atoms : n_atoms;
-    DoneList list;
-    f_in.fd = io.fd_in = open(frames_path, O_RDONLY);
-    if (io.fd_in < 0) return set_err(err_out, err_len, "cannot open the frame file");
-    struct stat st;
-    if (fstat(io.fd_in, &st) != 0) return set_err(err_out, err_len, "cannot stat the frame file");
-    const long long frame_bytes = ((frames_f32 & 1) ? 12LL : 24LL) * frame_atoms;
-    const long long in_file = ((long long)st.st_size - header_bytes) / frame_bytes;
-    if (n_frames <= 0) n_frames = in_file;
-    if (n_frames <= 0 || n_frames > in_file) return set_err(err_out, err_len, "the frame file holds fewer frames than asked for");
-    if (frames_total_out) *frames_total_out = n_frames;
-    /* (a topology: by the atoms that come IN, so that the staging of a mostly-solvent frame stays what it is without one; not
-       measured whether sizing by the kept atoms, i.e. longer shards for the engine, would be faster) */
-    if (frames_per_batch <= 0) frames_per_batch = (int)(1250000 / frame_atoms) + 1;
-    if (frames_per_batch > n_frames) frames_per_batch = (int)n_frames;
-    if ((long long)frames_per_batch * frame_atoms > (1LL << 30)) return set_err(err_out, err_len, "batch too large");
-    io.in_f32 = (frames_f32 & 1) ? 1 : 0; io.in_header = header_bytes;
-    io.out_f32 = (frames_f32 & 2) ? 1 : 0;
-    const long long n_shards = (n_frames + frames_per_batch - 1) / frames_per_batch;
-    if (done_path) {
-        unsigned long long hr = 1469598103934665603ULL; /* FNV-1a over the radii */
-        for (size_t q = 0; q < 8 * (size_t)n_atoms; ++q) hr = (hr ^ ((const unsigned char *)radii)[q]) * 1099511628211ULL;
-        char head[500];
-        int len = snprintf(head, sizeof head, "freesasa_amd trajectory done-list v2 n_atoms=%d n_frames=%lld frames_per_batch=%d alg=%d resolution=%d probe=%.17g f32=%d "
-                 "header_bytes=%lld frames_size=%lld frames_mtime=%lld.%09ld radii=%016llx\n",
-                 n_atoms, n_frames, frames_per_batch, alg, resolution, probe, io.in_f32 | (io.out_f32 << 1), header_bytes, (long long)st.st_size,
-                 (long long)st.st_mtim.tv_sec, (long)st.st_mtim.tv_nsec, hr);
-        if (tp && len > 0 && len < (int)sizeof head) { /* ... and what the topology's outputs depend on, in front of the line's end */
-            unsigned long long h_res = fnv1a(tp->seg.data(), 8 * ((size_t)tp->n_res + 1));
-            h_res = fnv1a(tp->bb, (size_t)tp->n, fnv1a(tp->cls, (size_t)tp->n, h_res));
-            unsigned long long h_sel = 0;
-            if (tp->sel) {
-                int n_words = 0, flags = 0;
-                const void *prog = freesasa_ingest_selection_program(tp->sel, &n_words, &flags);
-                const int key[3] = {tp->n_sel, n_words, flags};
-                h_sel = fnv1a(prog, sizeof(freesasa_sel_word) * (size_t)n_words, fnv1a(key, sizeof key));
-            }
-            len += snprintf(head + len - 1, sizeof head - (size_t)len + 1, " topology frame_atoms=%d index=%016llx residues=%016llx selection=%016llx outputs=%d\n",
-                            tp->frame_atoms, tp->index ? fnv1a(tp->index, 4 * (size_t)tp->n) : 0ULL, h_res, h_sel,
-                            (sasa_path ? 1 : 0) | (cls_path ? 2 : 0) | (res_path ? 4 : 0) | (sel_path ? 8 : 0)) - 1;
+    int len = snprintf(head, cap, "freesasa_amd trajectory done-list v2 n_atoms=%d n_frames=%lld frames_per_batch=%d alg=%d resolution=%d probe=%.17g f32=%d "
+                       "header_bytes=%lld frames_size=%lld frames_mtime=%lld.%09ld radii=%016llx\n",
+                       s.n_atoms, s.n_frames, s.frames_per_batch, s.alg, s.resolution, s.probe, io.in_f32 | (io.out_f32() << 1), io.in_header, (long long)st.st_size,
+                       (long long)st.st_mtim.tv_sec, (long)st.st_mtim.tv_nsec, fnv1a(s.radii, 8 * (size_t)s.n_atoms));
+    const TrajTopo *tp = s.topo;
+    if (tp && len > 0 && len < (int)cap) {
+        unsigned long long h_res = fnv1a(tp->seg.data(), 8 * ((size_t)tp->n_res + 1));
+        h_res = fnv1a(tp->bb, (size_t)tp->n, fnv1a(tp->cls, (size_t)tp->n, h_res));
+        unsigned long long h_sel = 0;
+        if (tp->sel) {
+            int n_words = 0, flags = 0;
+            const void *prog = freesasa_ingest_selection_program(tp->sel, &n_words, &flags);
+            const int key[3] = {tp->n_sel, n_words, flags};
+            h_sel = fnv1a(prog, sizeof(freesasa_sel_word) * (size_t)n_words, fnv1a(key, sizeof key));
         }
-        if (len <= 0 || len >= (int)sizeof head) return set_err(err_out, err_len, "cannot write the done-list");
-        const int fpb = frames_per_batch;
-        if (list.read(done_path, head, n_shards, [fpb](long long k, long long f0, long long) { return f0 == k * fpb; }) == DoneList::REFUSED)
-            return set_err(err_out, err_len, tp ? "the done-list belongs to a run with other parameters, radii, topology, selections, outputs or frame file"
-                                                : "the done-list belongs to a run with other parameters, radii or frame file");
+        int outputs = 0;
+        for (const TrajOut &o : io.out) outputs |= o.path ? o.bit : 0;
+        len += snprintf(head + len - 1, cap - (size_t)len + 1, " topology frame_atoms=%d index=%016llx residues=%016llx selection=%016llx outputs=%d\n",
+                        tp->frame_atoms, tp->index ? fnv1a(tp->index, 4 * (size_t)tp->n) : 0ULL, h_res, h_sel, outputs) - 1;
     }
-    const int flags = list.resumed() ? O_WRONLY | O_CREAT : O_WRONLY | O_CREAT | O_TRUNC;
-    f_totals.fd = io.fd_totals = open(totals_path, flags, 0644);
-    if (io.fd_totals < 0) return set_err(err_out, err_len, "cannot open the totals file");
-    if (sasa_path) {
-        f_sasa.fd = io.fd_sasa = open(sasa_path, flags, 0644);
-        if (io.fd_sasa < 0) return set_err(err_out, err_len, "cannot open the per-atom file");
-    }
-    if (cls_path) {
-        f_cls.fd = io.fd_cls = open(cls_path, flags, 0644);
-        if (io.fd_cls < 0) return set_err(err_out, err_len, "cannot open the class-sums file");
-    }
-    if (res_path) {
-        f_res.fd = io.fd_res = open(res_path, flags, 0644);
-        if (io.fd_res < 0) return set_err(err_out, err_len, "cannot open the residues file");
-    }
-    if (sel_path) {
-        f_sel.fd = io.fd_sel = open(sel_path, flags, 0644);
-        if (io.fd_sel < 0) return set_err(err_out, err_len, "cannot open the selections file");
-    }
-    io.sel_atoms = sel_atoms_out;
+    return len > 0 && len < (int)cap ? 0 : -1;
+}
+
+/* Frame file -> result files, resumable (include/freesasa_gpu.h has the formats).  The caller has put the result files'
+   paths into io.out[]; s.topo: a run with a topology - frames of its frame_atoms atoms, a longer first line of the done-list. */
+static int trajectory_file_run(const char *frames_path, int frames_f32, long long header_bytes, TrajSpec s, TrajIO &io,
+                               const char *done_path, long long *frames_total_out, char *err_out, int err_len)
+{
+    if (!frames_path || !s.radii || !io.out[OUT_TOTALS].path) return set_err(err_out, err_len, "null argument");
+    if (s.n_atoms <= 0 || header_bytes < 0) return set_err(err_out, err_len, "bad argument");
+    if (traj_check_args(s, nullptr, err_out, err_len)) return -1;
+    return guarded(err_out, err_len, [&]() -> int {
+    const long long frame_atoms = s.topo ? s.topo->frame_atoms : s.n_atoms;
+    io.in.fd = open(frames_path, O_RDONLY);
+    if (io.in.fd < 0) return set_err(err_out, err_len, "cannot open the frame file");
+    struct stat st;
+    if (fstat(io.in.fd, &st) != 0) return set_err(err_out, err_len, "cannot stat the frame file");
+    io.in_header = header_bytes; io.in_f32 = (frames_f32 & 1) ? 1 : 0; io.out[OUT_SASA].esz = (frames_f32 & 2) ? 4 : 8;
+    const long long in_file = ((long long)st.st_size - header_bytes) / ((io.in_f32 ? 12LL : 24LL) * frame_atoms);
+    if (s.n_frames <= 0) s.n_frames = in_file;
+    if (s.n_frames <= 0 || s.n_frames > in_file) return set_err(err_out, err_len, "the frame file holds fewer frames than asked for");
+    if (frames_total_out) *frames_total_out = s.n_frames;
+    if (traj_shard_size(s, frame_atoms, err_out, err_len)) return -1;
     if (done_path) {
-        const int orc = list.open();
-        if (orc) return set_err(err_out, err_len, orc == -1 ? "cannot open the done-list" : "cannot write the done-list");
-        io.list = &list;
+        char head[500];
+        if (traj_done_head(head, sizeof head, s, io, st)) return set_err(err_out, err_len, "cannot write the done-list");
+        const int fpb = s.frames_per_batch;
+        if (io.list.read(done_path, head, (s.n_frames + fpb - 1) / fpb, [fpb](long long k, long long f0, long long) { return f0 == k * fpb; }) == DoneList::REFUSED)
+            return set_err(err_out, err_len, s.topo ? "the done-list belongs to a run with other parameters, radii, topology, selections, outputs or frame file"
+                                                    : "the done-list belongs to a run with other parameters, radii or frame file");
     }
-    return traj_run(io, radii, n_atoms, n_frames, alg, probe, resolution, frames_per_batch, 0, max_new_shards, devices, n_devices, err_out, err_len, tp);
+    for (TrajOut &o : io.out) { /* (a resumed run's files keep what the listed shards wrote) */
+        if (!o.path) continue;
+        o.f.fd = open(o.path, io.list.resumed() ? O_WRONLY | O_CREAT : O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (o.f.fd < 0) return set_err(err_out, err_len, ("cannot open the " + std::string(o.name) + " file").c_str());
+    }
+    if (done_path) {
+        const int orc = io.list.open();
+        if (orc) return set_err(err_out, err_len, orc == -1 ? "cannot open the done-list" : "cannot write the done-list");
+    }
+    return traj_run(io, s, err_out, err_len);
     });
 }
 
@@ -762,8 +800,10 @@ extern "C" int freesasa_gpu_trajectory_file_devices(const char *frames_path, int
                                                     long long *frames_total_out, char *err_out, int err_len)
 {
     if (err_out && err_len > 0) err_out[0] = 0;
-    return trajectory_file_run(frames_path, frames_f32, header_bytes, radii, n_atoms, n_frames, alg, probe, resolution, frames_per_batch,
-                               totals_path, sasa_path, done_path, max_new_shards, devices, n_devices, frames_total_out, err_out, err_len);
+    TrajSpec s = {radii, n_atoms, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, nullptr, max_new_shards};
+    TrajIO io;
+    io.out[OUT_TOTALS].path = totals_path; io.out[OUT_SASA].path = sasa_path;
+    return trajectory_file_run(frames_path, frames_f32, header_bytes, s, io, done_path, frames_total_out, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_trajectory_file_topology(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
@@ -780,9 +820,12 @@ extern "C" int freesasa_gpu_trajectory_file_topology(const char *frames_path, in
         TrajTopo tp; /* (outlives the run: the lanes upload from it) */
         if (topo_make(batch, structure, frame_atoms, atom_index, sel, &tp, err_out, err_len)) return -1;
         if ((sel_area_path || sel_atoms_out) && !sel) return set_err(err_out, err_len, "selection outputs need a selection set");
-        return trajectory_file_run(frames_path, frames_f32, header_bytes, tp.radii, tp.n, n_frames, alg, probe, resolution, frames_per_batch,
-                                   totals_path, sasa_path, done_path, max_new_shards, devices, n_devices, frames_total_out, err_out, err_len,
-                                   &tp, class_sums_path, residues_path, sel_area_path, sel_atoms_out);
+        TrajSpec s = {tp.radii, tp.n, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, &tp, max_new_shards};
+        TrajIO io;
+        io.sel_atoms = sel_atoms_out;
+        const char *const path[N_OUT] = {totals_path, sasa_path, class_sums_path, residues_path, sel_area_path};
+        for (int k = 0; k < N_OUT; ++k) io.out[k].path = path[k];
+        return trajectory_file_run(frames_path, frames_f32, header_bytes, s, io, done_path, frames_total_out, err_out, err_len);
     });
 }
 

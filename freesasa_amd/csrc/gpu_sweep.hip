@@ -709,12 +709,7 @@ int sweep_impl(SweepArgs a, char *err_out, int err_len)
     const int n_workers = a.n_devices < (int)S.todo.size() ? a.n_devices : (int)S.todo.size();
     S.loader_threads = threads_per_worker(a.n_threads, n_workers);
     if (a.alg == 1) { S.tp.resize(3 * (size_t)(a.resolution > 0 ? a.resolution : 1)); if (a.resolution > 0) freesasa_gpu_test_points(a.resolution, S.tp.data()); }
-    {
-        ThreadGroup tg;
-        for (int w = 1; w < n_workers; ++w)
-            if (!tg.spawn(worker, std::ref(S), w)) { S.fe.set("could not start a worker thread"); break; }
-        if (!S.fe.failed.load()) worker(S, 0);
-    }
+    run_lanes(n_workers, S.fe, [&S](int w) noexcept { worker(S, w); });
     if (S.sprof && S.dev_parse)
         fprintf(stderr, "sweep profile (%d workers, %zu batches, %d loader threads each; ms summed over the workers): first batch staged %.1f | parse %.1f | host parser %.1f | "
                         "kernels to totals %.1f | done-list %.1f | waiting for the loader %.1f || staging itself (loader threads) %.1f\n",

@@ -295,3 +295,134 @@ def test_every_allocation_failure_is_an_error_and_the_next_call_works(system, se
         fa.host_test_fail_after(0)
     assert failures >= 5, (hook, failures)
     L.freesasa_gpu_release_pool()
+
+
+# ------------------------------------------------------------------------------------------------ the table of outputs
+
+KINDS = ("totals", "sasa", "cls", "res", "sel")
+PATH_ARG = dict(sasa="sasa_path", cls="class_sums_path", res="residues_path", sel="selections_path")
+
+
+@pytest.fixture(scope="module")
+def all_outputs(system, sel, tmp_path_factory):
+    """the spliced 752-atom frames in a file and the run that writes every output: (frame file, its result files)"""
+    one, _, big = system
+    tmp = tmp_path_factory.mktemp("outputs")
+    full, index = big["spliced"]
+    path = tmp / "frames.f64"
+    full.tofile(path)
+    paths, done, n_frames, _ = file_run(tmp, "all", path, one, sel, atom_index=index, frame_atoms=752)
+    assert done and n_frames == F
+    return path, paths
+
+
+@pytest.mark.parametrize("asked, with_sel, word", [(("cls",), True, 2), (("res",), False, 4), (("sel",), True, 8), (("res", "sel"), True, 12),
+                                                   (("sasa", "cls"), False, 3), ((), False, 0)])
+def test_every_subset_of_outputs_lays_its_block_out_correctly(system, sel, all_outputs, tmp_path, asked, with_sel, word):
+    """The sums of a shard lie one behind the other in one block - classes | residues | selection areas | atom counts - so where
+    an output begins depends on which of the others are computed: every subset's files equal the all-outputs run's, nothing
+    else is written, and the done-list names the outputs."""
+    one, _, big = system
+    path, ref = all_outputs
+    mine = {k: str(tmp_path / k) for k in KINDS + ("done",)}
+    kw = {PATH_ARG[k]: mine[k] for k in asked}
+    done, n_frames, atoms = fa.trajectory_file_topology(path, one, mine["totals"], atom_index=big["spliced"][1], frame_atoms=752,
+                                                        selection=sel if with_sel else None, done_path=mine["done"],
+                                                        frames_per_batch=FPB, devices=DEVS, **kw)
+    assert done and n_frames == F
+    for k in KINDS:
+        if k == "totals" or k in asked:
+            assert open(mine[k], "rb").read() == open(ref[k], "rb").read(), k
+        else:
+            assert not os.path.exists(mine[k]), k
+    if with_sel:
+        assert np.array_equal(atoms, reference(system, sel, "lr20")["atoms"])
+    else:
+        assert atoms is None
+    assert open(mine["done"]).readline().endswith(" outputs=%d\n" % word)
+
+
+def test_fp32_per_atom_file_with_a_topology_and_a_gather(system, sel, tmp_path):
+    one, _, big = system
+    full, index = big["scattered"]
+    want = reference(system, sel, "lr20")
+    path = tmp_path / "frames.f64"
+    full.tofile(path)
+    kw = dict(atom_index=index, frame_atoms=752)
+    p64, done, _, _ = file_run(tmp_path, "f64", path, one, sel, **kw)
+    assert done
+    p32, done, _, atoms = file_run(tmp_path, "f32", path, one, sel, out_f32=True, **kw)
+    assert done and np.array_equal(atoms, want["atoms"])
+    got = np.fromfile(p32["sasa"], dtype=np.float32)
+    assert got.tobytes() == want["sasa"].astype(np.float32).tobytes()
+    for k in ("totals", "cls", "res", "sel"):
+        assert open(p32[k], "rb").read() == open(p64[k], "rb").read(), k
+    before = {k: open(p32[k], "rb").read() for k in p32}
+    with pytest.raises(RuntimeError, match="other parameters"):
+        file_run(tmp_path, "f32", path, one, sel, **kw)
+    assert before == {k: open(p32[k], "rb").read() for k in p32}
+
+
+def test_page_locked_caller_arrays(system, sel):
+    """Frames in page-locked memory are uploaded from where they are, and page-locked result arrays are written by the device:
+    the paths without staging give the bytes of the staged ones."""
+    import torch
+    one, frames, _ = system
+    want = reference(system, sel, "lr20")
+    radii = np.ascontiguousarray(one.radii, dtype=np.float64)
+    totals, sasa = fa.trajectory(frames, radii, frames_per_batch=FPB, device=0)
+    assert totals.tobytes() == want["totals"].tobytes() and sasa.tobytes() == np.ascontiguousarray(want["sasa"]).tobytes()
+    pinned = torch.from_numpy(frames).pin_memory()
+    view = pinned.numpy()
+    assert pinned.is_pinned() and np.ascontiguousarray(view, dtype=np.float64) is view
+    t2, s2 = fa.trajectory(view, radii, frames_per_batch=FPB, device=0)
+    assert t2.tobytes() == totals.tobytes() and s2.tobytes() == sasa.tobytes()
+    # the output arrays page-locked too: the entry itself
+    L = fa.lib()
+    dp = C.POINTER(C.c_double)
+    devs = (C.c_int * len(DEVS))(*DEVS)
+    for per_atom in (True, False):
+        t_out = torch.zeros(F, dtype=torch.float64).pin_memory()
+        s_out = torch.zeros(F, N, dtype=torch.float64).pin_memory()
+        err = C.create_string_buffer(512)
+        rc = L.freesasa_gpu_trajectory_devices(C.cast(pinned.data_ptr(), dp), radii.ctypes.data_as(dp), N, F, fa.LEE_RICHARDS, 1.4, 20, FPB,
+                                               C.cast(t_out.data_ptr(), dp), C.cast(s_out.data_ptr(), dp) if per_atom else None,
+                                               devs, len(DEVS), err, 512)
+        assert rc == 0, err.value
+        assert t_out.numpy().tobytes() == totals.tobytes()
+        assert s_out.numpy().tobytes() == (sasa.tobytes() if per_atom else bytes(8 * F * N))
+
+
+def fnv1a(data, h=1469598103934665603):
+    for b in bytes(data):
+        h = ((h ^ b) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def plain_head(path, radii, n_frames, fpb, alg=0, resolution=20, probe=1.4, flags=0, header_bytes=0):
+    """the first line of a trajectory done-list as freesasa_amd/csrc/gpu_drivers.hip documents it"""
+    st = os.stat(path)
+    return ("freesasa_amd trajectory done-list v2 n_atoms=%d n_frames=%d frames_per_batch=%d alg=%d resolution=%d probe=%s f32=%d "
+            "header_bytes=%d frames_size=%d frames_mtime=%d.%09d radii=%016x\n"
+            % (radii.size, n_frames, fpb, alg, resolution, "%.17g" % probe, flags, header_bytes, st.st_size,
+               st.st_mtime_ns // 10**9, st.st_mtime_ns % 10**9, fnv1a(np.ascontiguousarray(radii, dtype=np.float64).tobytes())))
+
+
+def test_the_done_lists_first_line_is_the_documented_one(system, sel, all_outputs, tmp_path):
+    """The first line names the run, and a list written by one build must be resumed by the next: the whole line of a plain
+    run, and of a run with a topology everything but the digest of the selection set's program (its words are the library's)."""
+    import re
+    one, frames, big = system
+    path = tmp_path / "frames.f32"
+    frames.astype(np.float32).tofile(path)
+    p = lambda k: str(tmp_path / k)
+    assert fa.trajectory_file(path, one.radii, p("t"), p("s"), p("d"), f32=True, out_f32=True, frames_per_batch=FPB, devices=DEVS) == (True, F)
+    assert open(p("d")).readline() == plain_head(path, one.radii, F, FPB, flags=3)
+    full_path, ref = all_outputs
+    index = big["spliced"][1]
+    res_first = np.ascontiguousarray(one.res_first[:R + 1] - one.offsets[0], dtype=np.int64)
+    h_res = fnv1a(one.atom_backbone[:N].tobytes(), fnv1a(one.atom_class[:N].tobytes(), fnv1a(res_first.tobytes())))
+    head = open(ref["done"]).readline()
+    lead = plain_head(full_path, one.radii, F, FPB)[:-1] + " topology frame_atoms=752 index=%016x residues=%016x " % (fnv1a(index.tobytes()), h_res)
+    assert head.startswith(lead)
+    assert re.fullmatch(r"selection=[0-9a-f]{16} outputs=15\n", head[len(lead):])
