@@ -2,7 +2,7 @@
 #   make            -> freesasa_amd/lib/libfreesasa_amd.so (stand-alone drop-in library)
 #                      freesasa_amd/lib/libfreesasa_amd_seam.a (seam objects for a drop-in
 #                      build of the reference)
-#   make emu        -> tests/emu/libsasa_emu.so, libselect_emu.so, libgroups_emu.so, libtraj_emu.so  (TESTS ONLY: the kernel phase
+#   make emu        -> tests/emu/libsasa_emu.so, libselect_emu.so, libgroups_emu.so, libtraj_emu.so, libtraj_groups_emu.so  (TESTS ONLY: the kernel phase
 #                      functions driven on the CPU; never linked into the product)
 #   make oracle     -> oracle/ (TESTS ONLY) ; make tools -> tools/libsasa_synth.so
 HIPCC   ?= /opt/rocm/bin/hipcc
@@ -73,7 +73,7 @@ $(LIBDIR)/libfreesasa_amd.so: $(GPU_OBJS) $(LIBDIR)/seam.o $(LIBDIR)/testpoints.
 $(LIBDIR)/libfreesasa_amd_seam.a: $(GPU_OBJS) $(LIBDIR)/seam.o $(LIBDIR)/testpoints.o $(LIBDIR)/ingest.o $(LIBDIR)/classifier.o $(LIBDIR)/select.o $(LIBDIR)/ingest_cache.o $(LIBDIR)/hostfault.o
 	rm -f $@; ar rcs $@ $^
 
-emu: tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so
+emu: tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so tests/emu/libtraj_groups_emu.so
 # the loader with its byte-at-a-time mmCIF tokenizer only: the differential twin of the SSE2 row scanner
 tests/emu/libingest_scalar.so: $(CSRC)/ingest.c $(CSRC)/classifier.c $(CSRC)/classifier.h $(CSRC)/hostfault.c $(CSRC)/hostfault.h $(CSRC)/protor_table.h include/freesasa_ingest.h
 	$(CC) $(CFLAGS) -DFREESASA_INGEST_NO_SIMD -Iinclude -pthread -shared -o $@ $(CSRC)/ingest.c $(CSRC)/classifier.c $(CSRC)/hostfault.c -lm
@@ -87,6 +87,11 @@ tests/emu/libselect_emu.so: tests/emu/emu_select.cpp $(CSRC)/select_kernels.h $(
 # the trajectory topology's phase functions (traj_kernels.h): the gather and the per-frame sums over one structure of a loaded batch
 tests/emu/libtraj_emu.so: tests/emu/emu_traj.cpp $(CSRC)/traj_kernels.h $(CSRC)/select_kernels.h $(CSRC)/select_program.h $(CSRC)/sasa_kernels.h include/freesasa_ingest.h
 	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -DSASA_EMU -Iinclude -shared -o $@ tests/emu/emu_traj.cpp -lm
+
+# chain groups per frame (traj_kernels.h, traj_group_*) and, as their yardstick, the chain-group entry's phase functions
+# (group_kernels.h) on one frame as a batch of one structure
+tests/emu/libtraj_groups_emu.so: tests/emu/emu_traj_groups.cpp $(CSRC)/traj_kernels.h $(CSRC)/group_kernels.h $(CSRC)/select_kernels.h $(CSRC)/select_program.h $(CSRC)/lr2_kernels.h $(CSRC)/sasa_kernels.h $(CSRC)/sr_caps.h include/freesasa_ingest.h
+	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -DSASA_EMU -Iinclude -shared -o $@ tests/emu/emu_traj_groups.cpp -lm
 
 # the group-ids kernel's phase function (group_kernels.h, gid_struct) driven over a loaded batch, one wave per structure
 tests/emu/libgroups_emu.so: tests/emu/emu_groups.cpp $(CSRC)/group_kernels.h $(CSRC)/lr2_kernels.h $(CSRC)/sasa_kernels.h $(CSRC)/sr_caps.h include/freesasa_ingest.h
@@ -115,7 +120,7 @@ tools:
 	$(MAKE) -C tools
 
 clean:
-	rm -rf $(LIBDIR) tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so
+	rm -rf $(LIBDIR) tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so tests/emu/libtraj_groups_emu.so
 	$(MAKE) -C oracle clean
 	$(MAKE) -C tools clean
 .PHONY: all emu oracle tools clean asan asan-test

@@ -664,6 +664,14 @@ def _topology_proto(L):
                                                         C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
                                                         C.c_char_p, C.c_char_p, C.c_char_p, _llp, C.c_char_p, C.c_longlong, _ip, C.c_int,
                                                         _llp, C.c_char_p, C.c_int]
+    # the same with chain groups: (group, n_groups) behind the selection set, the two group outputs behind sel_atoms_out
+    L.freesasa_gpu_trajectory_groups.argtypes = [_dp, C.c_int, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_void_p, _i32p, C.c_int,
+                                                 C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _llp, _dp, _dp,
+                                                 _ip, C.c_int, C.c_char_p, C.c_int]
+    L.freesasa_gpu_trajectory_file_groups.argtypes = [C.c_char_p, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, C.c_int, _i32p,
+                                                      C.c_void_p, _i32p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_char_p,
+                                                      C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, _llp, C.c_char_p, C.c_char_p,
+                                                      C.c_char_p, C.c_longlong, _ip, C.c_int, _llp, C.c_char_p, C.c_int]
     return L
 
 
@@ -671,11 +679,15 @@ class TopologyResult:
     """What trajectory_topology() returns: totals [F], class_sums [F, 3] (apolar, polar, unknown), residues [F, R, 6] (total,
     main chain, side chain, polar, apolar, unknown), selection_areas [F, S] and selection_atoms [S] (None without a
     selection set), sasa [F, n] or None, and res_ref [R]: rows of ingest.residue_reference_table() - the relative areas are
-    100 * residues[..., :5] / table[res_ref] where res_ref >= 0."""
+    100 * residues[..., :5] / table[res_ref] where res_ref >= 0.  With chain groups (None without): group_areas [F, G, 3]
+    (isolated, complex, buried per frame and group), group_atoms [G], and with per_atom isolated [F, n], every atom's area in
+    its group taken on its own (isolated - sasa: what the atom buries in the complex)."""
 
-    def __init__(self, totals, class_sums, residues, selection_areas, selection_atoms, sasa, res_ref):
+    def __init__(self, totals, class_sums, residues, selection_areas, selection_atoms, sasa, res_ref, group_areas=None,
+                 group_atoms=None, isolated=None):
         self.totals, self.class_sums, self.residues = totals, class_sums, residues
         self.selection_areas, self.selection_atoms, self.sasa, self.res_ref = selection_areas, selection_atoms, sasa, res_ref
+        self.group_areas, self.group_atoms, self.isolated = group_areas, group_atoms, isolated
 
 
 def _topology_args(batch, structure, atom_index, frame_atoms):
@@ -689,12 +701,43 @@ def _topology_args(batch, structure, atom_index, frame_atoms):
     return n, r1 - r0, batch.res_ref[r0:r1].copy(), idx, int(n if frame_atoms is None else frame_atoms)
 
 
+def _topology_groups(batch, structure, n, chain_groups, separate_chains, long, group, n_groups):
+    """(ids [n] int32, G, atoms per group [G]) of the topology's structure, or (None, 0, None): from a spec / separate chains
+    through Batch.chain_groups (the structure's slice of the batch's ids), or from ids given directly; the library checks
+    the ids"""
+    if chain_groups is not None or separate_chains:
+        if group is not None:
+            raise ValueError("give chain_groups / separate_chains or group, not both")
+        from . import ingest
+        ids, ng, status = batch.chain_groups(chain_groups, long=long, separate_chains=separate_chains)
+        if not 0 <= structure < batch.n_structs:
+            raise ValueError("structure out of range")
+        if status[structure] == ingest.EGROUP:
+            raise ValueError("the topology's structure lacks a chain the groups name (EGROUP)")
+        group, n_groups = ids[batch.offsets[structure]:batch.offsets[structure + 1]], int(ng[structure])
+    if group is None:
+        if n_groups is not None:
+            raise ValueError("n_groups needs group")
+        return None, 0, None
+    group = np.ascontiguousarray(group, dtype=np.int32)
+    if n_groups is None:
+        raise ValueError("group needs n_groups")
+    if group.size != n:
+        raise ValueError("group needs one id per atom of the structure")
+    G = int(n_groups)
+    return group, G, np.bincount(group[(group >= 0) & (group < G)], minlength=max(G, 0)).astype(np.int64)
+
+
 def trajectory_topology(frames, batch, structure=0, atom_index=None, selection=None, per_atom=False, alg=LEE_RICHARDS, probe=1.4,
-                        resolution=20, frames_per_batch=0, device=-1, devices=None):
+                        resolution=20, frames_per_batch=0, device=-1, devices=None, chain_groups=None, separate_chains=False,
+                        long=False, group=None, n_groups=None):
     """freesasa_gpu_trajectory_topology(): frames [F, frame_atoms, 3] of a (solvated) system whose solute is structure
     `structure` of the ingest.Batch - topology atom i is frame atom atom_index[i] (None: the frames hold exactly the
     structure's atoms) - -> a TopologyResult.  The gather, the per-residue, per-class and per-selection sums run on the
-    device; the per-atom areas come back only with per_atom=True."""
+    device; the per-atom areas come back only with per_atom=True.
+    Chain groups (freesasa_gpu_trajectory_groups): chain_groups="AB+C" (long=True: the long syntax) or separate_chains=True
+    as Batch.chain_groups takes them, or group=ids [n] (-1: in no group) with n_groups=G - the result then has group_areas,
+    group_atoms and, with per_atom, isolated."""
     L = _topology_proto(lib())
     frames = np.ascontiguousarray(frames, dtype=np.float64)
     if frames.ndim != 3 or frames.shape[2] != 3:
@@ -710,23 +753,39 @@ def trajectory_topology(frames, batch, structure=0, atom_index=None, selection=N
     keep, dp_, nd = _devs(devices, device)
     cb = batch._as_c()
     opt = lambda a, t=_dp: None if a is None else a.ctypes.data_as(t)
-    ret = L.freesasa_gpu_trajectory_topology(frames.ctypes.data_as(_dp), F, C.byref(cb), structure, fa_, opt(idx, C.POINTER(C.c_int32)),
-                                             selection.handle if selection is not None else None, alg, probe, resolution,
-                                             frames_per_batch, totals.ctypes.data_as(_dp), opt(sasa), cls.ctypes.data_as(_dp),
-                                             res.ctypes.data_as(_dp), opt(sel_area), opt(sel_atoms, C.POINTER(C.c_longlong)),
-                                             dp_, nd, err, 512)
+    ids, G, g_atoms = _topology_groups(batch, structure, n, chain_groups, separate_chains, long, group, n_groups)
+    if ids is None:
+        ret = L.freesasa_gpu_trajectory_topology(frames.ctypes.data_as(_dp), F, C.byref(cb), structure, fa_, opt(idx, C.POINTER(C.c_int32)),
+                                                 selection.handle if selection is not None else None, alg, probe, resolution,
+                                                 frames_per_batch, totals.ctypes.data_as(_dp), opt(sasa), cls.ctypes.data_as(_dp),
+                                                 res.ctypes.data_as(_dp), opt(sel_area), opt(sel_atoms, C.POINTER(C.c_longlong)),
+                                                 dp_, nd, err, 512)
+        if ret:
+            raise RuntimeError("freesasa_gpu_trajectory_topology: " + err.value.decode())
+        return TopologyResult(totals, cls, res, sel_area, sel_atoms, sasa, res_ref)
+    g_areas = np.zeros((F, max(G, 0), 3))
+    iso = np.zeros((F, n)) if per_atom else None
+    ret = L.freesasa_gpu_trajectory_groups(frames.ctypes.data_as(_dp), F, C.byref(cb), structure, fa_, opt(idx, C.POINTER(C.c_int32)),
+                                           selection.handle if selection is not None else None, opt(ids, C.POINTER(C.c_int32)), G,
+                                           alg, probe, resolution, frames_per_batch, totals.ctypes.data_as(_dp), opt(sasa),
+                                           cls.ctypes.data_as(_dp), res.ctypes.data_as(_dp), opt(sel_area),
+                                           opt(sel_atoms, C.POINTER(C.c_longlong)), g_areas.ctypes.data_as(_dp), opt(iso),
+                                           dp_, nd, err, 512)
     if ret:
-        raise RuntimeError("freesasa_gpu_trajectory_topology: " + err.value.decode())
-    return TopologyResult(totals, cls, res, sel_area, sel_atoms, sasa, res_ref)
+        raise RuntimeError("freesasa_gpu_trajectory_groups: " + err.value.decode())
+    return TopologyResult(totals, cls, res, sel_area, sel_atoms, sasa, res_ref, g_areas, g_atoms, iso)
 
 
 def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_index=None, frame_atoms=None, selection=None,
                              sasa_path=None, class_sums_path=None, residues_path=None, selections_path=None, done_path=None,
                              f32=False, header_bytes=0, n_frames=0, alg=LEE_RICHARDS, probe=1.4, resolution=20, frames_per_batch=0,
-                             max_new_shards=0, device=-1, devices=None, out_f32=False):
+                             max_new_shards=0, device=-1, devices=None, out_f32=False, chain_groups=None, separate_chains=False,
+                             long=False, group=None, n_groups=None, group_areas_path=None, isolated_path=None):
     """freesasa_gpu_trajectory_file_topology(): trajectory_file() with a topology (see trajectory_topology; frame_atoms:
     atoms per frame of the file, None: the structure's) and one raw fp64 result file per output asked for: class sums
-    [F, 3], residues [F, R, 6], selection areas [F, S].  Returns (complete, n_frames, selection_atoms [S] or None)."""
+    [F, 3], residues [F, R, 6], selection areas [F, S].  Returns (complete, n_frames, selection_atoms [S] or None).
+    Chain groups (the keywords of trajectory_topology; freesasa_gpu_trajectory_file_groups): group_areas_path receives
+    [F, G, 3] fp64, isolated_path [F, n] fp64 (fp32 with out_f32)."""
     L = _topology_proto(lib())
     n, R, res_ref, idx, fa_ = _topology_args(batch, structure, atom_index, frame_atoms)
     S = len(selection) if selection is not None else 0
@@ -737,6 +796,20 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
     enc = lambda p: None if p is None else str(p).encode()
     keep, dp_, nd = _devs(devices, device)
     cb = batch._as_c()
+    ids, G, _ = _topology_groups(batch, structure, n, chain_groups, separate_chains, long, group, n_groups)
+    if ids is not None or group_areas_path is not None or isolated_path is not None:
+        ret = L.freesasa_gpu_trajectory_file_groups(enc(frames_path), bits, header_bytes, n_frames, C.byref(cb), structure, fa_,
+                                                    None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    selection.handle if selection is not None else None,
+                                                    None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), G,
+                                                    alg, probe, resolution, frames_per_batch, enc(totals_path), enc(sasa_path),
+                                                    enc(class_sums_path), enc(residues_path), enc(selections_path),
+                                                    None if sel_atoms is None else sel_atoms.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                                    enc(group_areas_path), enc(isolated_path),
+                                                    enc(done_path), max_new_shards, dp_, nd, C.byref(total), err, 512)
+        if ret < 0:
+            raise RuntimeError("freesasa_gpu_trajectory_file_groups: " + err.value.decode())
+        return ret == 0, int(total.value), sel_atoms
     ret = L.freesasa_gpu_trajectory_file_topology(enc(frames_path), bits, header_bytes, n_frames, C.byref(cb), structure, fa_,
                                                   None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
                                                   selection.handle if selection is not None else None, alg, probe, resolution,

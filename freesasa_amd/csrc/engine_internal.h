@@ -93,6 +93,12 @@ hipError_t kl_traj_gather(const sasa::TrajArgs &a, const void *d_in, bool in_f32
 hipError_t kl_traj_residues(const sasa::TrajArgs &a, hipStream_t st);
 hipError_t kl_traj_class(const sasa::TrajArgs &a, hipStream_t st);
 hipError_t kl_traj_sel(const sasa::TrajArgs &a, hipStream_t st);
+/* ... chain groups per frame: the combined batch's radii, the isolated structures' coordinates behind the compact frames (both
+   one thread per element), the finish (one thread per combined atom), three columns per (frame, group) */
+hipError_t kl_traj_group_radii(const sasa::TrajGroupArgs &a, hipStream_t st);
+hipError_t kl_traj_group_gather(const sasa::TrajGroupArgs &a, hipStream_t st);
+hipError_t kl_traj_group_finish(const sasa::TrajGroupArgs &a, hipStream_t st);
+hipError_t kl_traj_group_totals(const sasa::TrajGroupArgs &a, hipStream_t st);
 
 /* ------------------------------------------------------------------ context (gpu_engine.hip) */
 

@@ -86,7 +86,7 @@ int DoneList::read(const char *path, const char *head, long long n_units, const 
     done_.assign((size_t)n_units, 0);
     FILE *fp = fopen(path, "r");
     if (!fp) return FRESH;
-    char line[512];
+    char line[1024];
     if (fgets(line, sizeof line, fp)) {
         if (head_ != line) { fclose(fp); return REFUSED; }
         resumed_ = true;
@@ -267,7 +267,7 @@ int sweep_cache_impl(const char *cache_path, int alg, double probe, int resoluti
 /* One per-frame OUTPUT of a run: a row of TrajIO's table.  An entry point says where it goes - the caller's array or a
    result file - and everything else that is per output (opening the files, is it wanted, its place in a shard's blocks, the
    copy or the pwrite at the frame's offset, the flush, the done-list's outputs= word) is a loop over the table. */
-enum { OUT_TOTALS, OUT_SASA, OUT_CLS, OUT_RES, OUT_SEL, N_OUT };
+enum { OUT_TOTALS, OUT_SASA, OUT_ISO, OUT_CLS, OUT_RES, OUT_SEL, OUT_GRP, N_OUT }; /* (per atom | from OUT_CLS on: the block of sums) */
 struct TrajOut {
     const char *name;           /* in messages: "cannot open the %s file", "could not write the %s file" */
     int bit;                    /* in the outputs= word of a done-list's first line */
@@ -282,10 +282,11 @@ struct TrajIO {
     Fd in;                          /* ... or in a file of raw frames */
     long long in_header = 0;
     int in_f32 = 0;
-    /* per frame: total [1], per-atom areas [n]; runs with a topology: class sums [3], residue areas [6 R], selection areas [S] */
-    TrajOut out[N_OUT] = {{"totals", 0}, {"per-atom", 1}, {"class-sums", 2}, {"residues", 4}, {"selections", 8}};
+    /* per frame: total [1], per-atom areas [n]; runs with a topology: class sums [3], residue areas [6 R], selection areas [S];
+       with chain groups: every atom's area in its isolated group [n], and isolated, complex, buried per group [3 G] */
+    TrajOut out[N_OUT] = {{"totals", 0}, {"per-atom", 1}, {"isolated", 32}, {"class-sums", 2}, {"residues", 4}, {"selections", 8}, {"groups", 16}};
     long long *sel_atoms = nullptr; /* the selections' atoms [S]: frame-independent, delivered once */
-    bool out_f32() const { return out[OUT_SASA].esz == 4; } /* per-atom areas written as fp32 (narrowed on the device; an output format) */
+    bool out_f32() const { return out[OUT_SASA].esz == 4; } /* per-atom and isolated areas written as fp32 (narrowed on the device; an output format) */
     DoneList list;                  /* (active: a file run with a done-list) */
 };
 
@@ -302,6 +303,11 @@ struct TrajTopo {
     const freesasa_ingest_selection *sel = nullptr;
     std::vector<uint64_t> keys;      /* (selections) name | symbol of every atom */
     const char *res_name = nullptr, *res_chain = nullptr, *res_number = nullptr; /* the structure's first residue's */
+    /* chain groups (group_make): the ids, and the cut of the structure into its groups (traj_kernels.h, traj_group_cut) */
+    const int32_t *group = nullptr;  /* [n], -1: in no group; NULL: a run without groups */
+    int n_groups = 0, n_iso = 0;     /* G; atoms with an id >= 0 */
+    std::vector<int64_t> gfirst;     /* [G + 1] */
+    std::vector<int32_t> src;        /* [n_iso] */
 };
 
 unsigned long long fnv1a(const void *p, size_t bytes, unsigned long long h = 1469598103934665603ULL)
@@ -354,17 +360,49 @@ int topo_make(const freesasa_ingest_batch *b, int structure, int frame_atoms, co
     return 0;
 }
 
+/* the argument checks of chain groups and the cut, on the host: 0 (tp->group stays NULL when no groups are asked for), or -1
+   with the message.  areas / iso: is that output asked for? */
+int group_make(const int32_t *group, int n_groups, bool areas, bool iso, TrajTopo *tp, char *err_out, int err_len)
+{
+    if (!group && !areas && !iso) return 0;
+    if (!group) return set_err(err_out, err_len, "group areas and isolated areas need group ids (group is NULL)");
+    if (!areas) return set_err(err_out, err_len, "group ids are given but the group areas have nowhere to go (NULL)");
+    if (n_groups < 1 || n_groups > 65535) return set_err(err_out, err_len, "n_groups must be 1 .. 65535");
+    tp->gfirst.resize((size_t)n_groups + 1);
+    tp->src.resize((size_t)tp->n);
+    int64_t bad = 0;
+    const int64_t n_iso = sasa::traj_group_cut(group, tp->n, n_groups, tp->gfirst.data(), tp->src.data(), &bad);
+    if (n_iso < 0) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "atom %lld has group id %d: ids are -1 .. n_groups - 1 = %d", (long long)bad, group[bad], n_groups - 1);
+        return set_err(err_out, err_len, msg);
+    }
+    tp->group = group; tp->n_groups = n_groups; tp->n_iso = (int)n_iso;
+    return 0;
+}
+
 /* Once per lane: the topology onto the lane's context - c->seg: residue boundaries | the one structure's offsets | index |
-   classes | backbone flags; with selections the keys, labels and program where freesasa_gpu_select_batch puts them, and
+   classes | backbone flags [| radii | group ids | src: the constant part of `ga`]; with selections the keys, labels and program where freesasa_gpu_select_batch puts them, and
    sel_mask_atom over the topology: the mask words stay in c->parse[PBUF_SEL_BITS].  (run_batch touches none of these.)
    Fills the constant part of `ta`.  Enqueued on the context's stream, nothing waited for. */
-int topo_upload(freesasa_gpu_ctx *c, const TrajTopo &tp, sasa::TrajArgs &ta)
+int topo_upload(freesasa_gpu_ctx *c, const TrajTopo &tp, sasa::TrajArgs &ta, sasa::TrajGroupArgs &ga)
 {
     const size_t n = (size_t)tp.n, R = (size_t)tp.n_res;
     const size_t b_seg = 8 * (R + 3), b_idx = tp.index ? (4 * n + 7) & ~(size_t)7 : 0;
-    if (ensure(c, c->seg, b_seg + b_idx + 2 * n)) return -1;
+    /* chain groups, behind the flags: the structure's radii (the combined batch's are made of them on the device) | ids | src */
+    const size_t b_flags = (2 * n + 7) & ~(size_t)7, b_grp = tp.group ? 8 * n + 4 * n + 4 * (size_t)tp.n_iso : 0;
+    if (ensure(c, c->seg, b_seg + b_idx + (tp.group ? b_flags : 2 * n) + b_grp)) return -1;
     char *base = (char *)c->seg.p;
     hipStream_t st = c->stream;
+    memset(&ga, 0, sizeof ga);
+    if (tp.group) {
+        char *g = base + b_seg + b_idx + b_flags;
+        HIP_TRY(c, hipMemcpyAsync(g, tp.radii, 8 * n, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(g + 8 * n, tp.group, 4 * n, hipMemcpyHostToDevice, st));
+        if (tp.n_iso) HIP_TRY(c, hipMemcpyAsync(g + 12 * n, tp.src.data(), 4 * (size_t)tp.n_iso, hipMemcpyHostToDevice, st));
+        ga.n = tp.n; ga.n_iso = tp.n_iso; ga.n_groups = tp.n_groups;
+        ga.radii = (const double *)g; ga.group = (const int32_t *)(g + 8 * n); ga.src = (const int32_t *)(g + 12 * n);
+    }
     HIP_TRY(c, hipMemcpyAsync(base, tp.seg.data(), b_seg, hipMemcpyHostToDevice, st));
     if (tp.index) HIP_TRY(c, hipMemcpyAsync(base + b_seg, tp.index, 4 * n, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(base + b_seg + b_idx, tp.cls, n, hipMemcpyHostToDevice, st));
@@ -425,7 +463,13 @@ int traj_shard_size(TrajSpec &s, long long frame_atoms, char *err_out, int err_l
 {
     if (s.frames_per_batch <= 0) s.frames_per_batch = (int)(1250000 / frame_atoms) + 1;
     if (s.frames_per_batch > s.n_frames) s.frames_per_batch = (int)s.n_frames;
-    return (long long)s.frames_per_batch * frame_atoms > (1LL << 30) ? set_err(err_out, err_len, "batch too large") : 0;
+    if ((long long)s.frames_per_batch * frame_atoms > (1LL << 30)) return set_err(err_out, err_len, "batch too large");
+    /* chain groups: the engine sees a shard's frames AND their isolated groups as one batch - up to twice the atoms */
+    if (s.topo && s.topo->group && ((long long)s.frames_per_batch * ((long long)s.topo->n + s.topo->n_iso) > (1LL << 30) ||
+                                    (long long)s.frames_per_batch * (1 + s.topo->n_groups) > (1LL << 30)))
+        return set_err(err_out, err_len, "batch too large with chain groups: frames_per_batch x (atoms + atoms in groups) and frames_per_batch x (1 + groups) "
+                                         "must not exceed 2^30");
+    return 0;
 }
 
 /* what the lanes of one run share */
@@ -433,7 +477,10 @@ struct TrajRun {
     const TrajSpec &s;
     TrajIO &io;
     const TrajTopo *const topo = s.topo;
-    const size_t n = (size_t)s.n_atoms, FB = (size_t)s.frames_per_batch; /* atoms the engine sees, frames of a full shard */
+    const size_t n = (size_t)s.n_atoms, FB = (size_t)s.frames_per_batch; /* atoms of a frame as the engine sees it, frames of a full shard */
+    /* chain groups: behind a shard's frames every group of every frame as a structure of its own (traj_kernels.h) */
+    const bool groups = topo && topo->group;
+    const size_t G = groups ? (size_t)topo->n_groups : 0, n_iso = groups ? (size_t)topo->n_iso : 0, nc = n + n_iso; /* nc: combined atoms per frame */
     const long long n_shards = (s.n_frames + s.frames_per_batch - 1) / s.frames_per_batch;
     /* a topology: frames of fa atoms come in (with an index the gather makes the engine's n of them); esz bytes per atom */
     const bool gather = topo && topo->index;
@@ -441,13 +488,16 @@ struct TrajRun {
     const size_t widen_bytes = io.in_f32 && !gather ? 12 * n * FB : 0; /* (fp32 frames without an index: kl_widen_f32's input) */
     /* the caller's arrays are page-locked: no staging */
     const bool in_pinned = io.mem_in && host_pinned(io.mem_in);
-    const bool direct_out = io.out[OUT_TOTALS].mem && host_pinned(io.out[OUT_TOTALS].mem) && (!io.out[OUT_SASA].mem || host_pinned(io.out[OUT_SASA].mem));
+    const bool direct_out = io.out[OUT_TOTALS].mem && host_pinned(io.out[OUT_TOTALS].mem) && (!io.out[OUT_SASA].mem || host_pinned(io.out[OUT_SASA].mem)) &&
+                            (!io.out[OUT_ISO].mem || host_pinned(io.out[OUT_ISO].mem));
     const size_t S = topo && topo->sel && (io.out[OUT_SEL].wanted() || io.sel_atoms) ? (size_t)topo->n_sel : 0; /* selections computed */
     /* A shard's sums lie one behind the other in ONE block, cut to its nf frames: classes | residues | selection areas |
-       selected atoms.  Output k's begin at x0[k] * nf doubles (k = N_OUT: the atom counts); xw doubles per frame hold it all. */
+       groups | selected atoms.  Output k's begin at x0[k] * nf doubles (k = N_OUT: the atom counts); xw doubles per frame hold it all. */
     size_t x0[N_OUT + 1] = {0, 0, 0}, xw;
     std::vector<double> tp;    /* S&R test points */
-    std::vector<int64_t> offs; /* a full shard as a batch: k n */
+    /* a full shard as a batch: k n; with chain groups behind them FB n + f n_iso + gfirst[g] - and the same for the run's short
+       last shard, whose isolated structures begin earlier (without groups a short shard is a prefix of the full one) */
+    std::vector<int64_t> offs, offs_last;
     std::atomic<long long> next{0}, fresh{0};
     std::atomic<int> stopped{0}, counts_out{0};
     FirstError fe;
@@ -455,11 +505,19 @@ struct TrajRun {
     const bool prof = getenv("FREESASA_AMD_TRAJ_PROFILE") != nullptr;
     std::atomic<long long> t_read{0}, t_dev{0}, t_write{0}, t_flush{0};
 
-    TrajRun(const TrajSpec &s_, TrajIO &io_) : s(s_), io(io_), offs(FB + 1)
+    void batch_offsets(size_t nf, std::vector<int64_t> &o) const
+    {
+        o.resize(nf * (1 + G) + 1);
+        for (size_t k = 0; k <= nf; ++k) o[k] = (int64_t)(k * n);
+        for (size_t f = 0; f < nf && G; ++f)
+            for (size_t g = 1; g <= G; ++g) o[nf + f * G + g] = (int64_t)(nf * n + f * n_iso) + topo->gfirst[g];
+    }
+    TrajRun(const TrajSpec &s_, TrajIO &io_) : s(s_), io(io_)
     {
         if (s.alg == 1) { tp.resize(3 * (size_t)s.resolution); freesasa_gpu_test_points(s.resolution, tp.data()); }
-        for (size_t k = 0; k <= FB; ++k) offs[k] = (int64_t)(k * n);
-        const size_t per[N_OUT] = {1, n, topo ? (size_t)3 : 0, topo ? 6 * (size_t)topo->n_res : 0, S};
+        batch_offsets(FB, offs);
+        if (groups && (size_t)(s.n_frames % s.frames_per_batch)) batch_offsets((size_t)(s.n_frames % s.frames_per_batch), offs_last);
+        const size_t per[N_OUT] = {1, n, groups ? n : 0, topo ? (size_t)3 : 0, topo ? 6 * (size_t)topo->n_res : 0, S, 3 * G};
         for (int k = 0; k < N_OUT; ++k) {
             io.out[k].per_frame = io.out[k].wanted() || k == OUT_SEL ? per[k] : 0;
             if (k >= OUT_CLS) x0[k + 1] = x0[k] + io.out[k].per_frame;
@@ -472,13 +530,15 @@ struct TrajLane {
     freesasa_gpu_ctx *c;
     bool radii_up = false, topo_up = false;
     sasa::TrajArgs ta;
+    sasa::TrajGroupArgs ga; /* (chain groups) */
+    int radii_nf = 0;       /* ... the shard length the combined batch's radii are laid out for */
 };
 /* a shard in its lane's hands: frames [f0, f0 + nf) */
 struct TrajShard {
     long long k, f0; int nf;
     size_t na, in_bytes; /* its atoms as the engine sees them, the bytes that come in */
     const void *src;     /* its frames on the host (page-locked) */
-    const void *d_areas; /* its per-atom areas on the device, as they go out */
+    const void *d_areas, *d_iso; /* its per-atom (and isolated) areas on the device, as they go out */
     char *host[N_OUT];   /* where every output's values are after the download (page-locked) */
 };
 long long now_ns() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (long long)ts.tv_sec * 1000000000LL + ts.tv_nsec; }
@@ -487,14 +547,18 @@ long long now_ns() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (l
 int shard_size(TrajRun &T, TrajLane &L)
 {
     freesasa_gpu_ctx *c = L.c;
-    const size_t n = T.n, FB = T.FB, narrow_bytes = T.io.out_f32() ? 4 * n * FB : 0;
+    const size_t n = T.n, FB = T.FB, nc = T.nc, iso = T.io.out[OUT_ISO].per_frame;
+    const size_t narrow_bytes = T.io.out_f32() ? 4 * (n + iso) * FB : 0; /* (the isolated areas' behind the per-atom areas') */
     if (hipSetDevice(c->device) != hipSuccess) return ctx_fail(c, "hipSetDevice failed");
-    if (ensure(c, c->h_xyz, 24 * n * FB) || ensure(c, c->h_radii, 8 * n) || ensure(c, c->h_sasa, 8 * n * FB) || ensure(c, c->h_totals, 8 * FB) ||
+    /* (with chain groups nc = n + n_iso atoms and 1 + G structures per frame, and radii per atom: the isolated structures are not n atoms long) */
+    if (ensure(c, c->h_xyz, 24 * nc * FB) || ensure(c, c->h_radii, T.groups ? 8 * nc * FB : 8 * n) || ensure(c, c->h_sasa, 8 * nc * FB) ||
+        ensure(c, c->h_totals, 8 * (1 + T.G) * FB) ||
         (T.widen_bytes + narrow_bytes && ensure(c, c->h_counts, T.widen_bytes + narrow_bytes)) ||
-        (T.gather && ensure(c, c->g_xyz, T.esz * T.fa * FB)) || (T.xw && ensure(c, c->h_gtot, 8 * T.xw * FB)))
+        (T.gather && ensure(c, c->g_xyz, T.esz * T.fa * FB)) || (T.xw && ensure(c, c->h_gtot, 8 * T.xw * FB)) ||
+        (T.groups && (ensure(c, c->g_gath, 8 * nc * FB) || ensure(c, c->g_tot2, 8 * (1 + T.G) * FB))) || (iso && ensure(c, c->h_iso, 8 * n * FB)))
         return -1;
-    if (!L.radii_up && hipMemcpyAsync(c->h_radii.p, T.s.radii, 8 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "radii upload failed");
-    if (T.topo && !L.topo_up && topo_upload(c, *T.topo, L.ta)) return -1;
+    if (!T.groups && !L.radii_up && hipMemcpyAsync(c->h_radii.p, T.s.radii, 8 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "radii upload failed");
+    if (T.topo && !L.topo_up && topo_upload(c, *T.topo, L.ta, L.ga)) return -1;
     L.radii_up = L.topo_up = true;
     return 0;
 }
@@ -523,6 +587,14 @@ int shard_upload(TrajRun &T, TrajLane &L, const TrajShard &h)
     /* full frames up as they were read: one kernel drops the solvent and widens fp32 */
     if (T.gather && kl_traj_gather(L.ta, d_in, f32, (double *)c->h_xyz.p, c->stream) != hipSuccess) return ctx_fail(c, "gather launch failed");
     if (!T.gather && f32 && kl_widen_f32((const float *)d_in, (double *)c->h_xyz.p, (long long)(3 * h.na), c->stream) != hipSuccess) return ctx_fail(c, "widening launch failed");
+    if (!T.groups) return 0;
+    /* chain groups: behind the compact frames, whoever made them, every group's atoms of every frame; the radii of the
+       combined batch once per shard length (the isolated structures begin at nf n) */
+    sasa::TrajGroupArgs &ga = L.ga;
+    ga.n_frames = h.nf; ga.xyz = (double *)c->h_xyz.p; ga.cradii = (double *)c->h_radii.p;
+    if (L.radii_nf != h.nf && kl_traj_group_radii(ga, c->stream) != hipSuccess) return ctx_fail(c, "launch of the groups' radii failed");
+    L.radii_nf = h.nf;
+    if (kl_traj_group_gather(ga, c->stream) != hipSuccess) return ctx_fail(c, "launch of the groups' gather failed");
     return 0;
 }
 
@@ -532,19 +604,43 @@ int shard_compute(TrajRun &T, TrajLane &L, TrajShard &h)
 {
     freesasa_gpu_ctx *c = L.c;
     const TrajOut *out = T.io.out;
-    c->shared_radii = true;
-    const int rb = run_batch(c, T.s.alg == 0, (double *)c->h_xyz.p, (double *)c->h_radii.p, T.offs.data(), h.nf, T.s.probe, T.s.resolution,
-                             T.s.alg == 1 ? T.tp.data() : nullptr, (double *)c->h_sasa.p, nullptr, (double *)c->h_totals.p);
+    const size_t nf = (size_t)h.nf;
+    /* (chain groups: ONE batch of the nf frames and their nf G isolated groups, radii per atom) */
+    c->shared_radii = !T.groups;
+    const int rb = run_batch(c, T.s.alg == 0, (double *)c->h_xyz.p, (double *)c->h_radii.p, (T.groups && nf != T.FB ? T.offs_last : T.offs).data(),
+                             (int)(nf * (1 + T.G)), T.s.probe, T.s.resolution, T.s.alg == 1 ? T.tp.data() : nullptr, (double *)c->h_sasa.p, nullptr,
+                             (double *)c->h_totals.p);
     c->shared_radii = false;
     if (rb) return -1;
+    h.d_iso = nullptr;
+    if (T.groups) {
+        /* grp_finish_atom per frame, each group's complex area reduced like its isolated total (the combined batch's chunk
+           tables, which run_batch left on the device: gpu_groups.hip does the same), the three columns into the block of sums */
+        sasa::TrajGroupArgs &ga = L.ga; /* (n_frames: shard_upload's) */
+        ga.csasa = (const double *)c->h_sasa.p; ga.cgath = (double *)c->g_gath.p; ga.iso = out[OUT_ISO].per_frame ? (double *)c->h_iso.p : nullptr;
+        ga.ctot = (const double *)c->h_totals.p; ga.ctot2 = (const double *)c->g_tot2.p; ga.out = (double *)c->h_gtot.p + T.x0[OUT_GRP] * nf;
+        sasa::PipeArgs pa;
+        memset(&pa, 0, sizeof pa);
+        pa.n_structs = (int)(nf * (1 + T.G)); pa.n_atoms = (int)(nf * T.nc); pa.offsets = (const int64_t *)c->offsets.p;
+        pa.n_chunks = c->n_chunks; pa.chunk_struct = (const int *)c->chunk_struct.p; pa.chunk_begin = (const int64_t *)c->chunk_begin.p;
+        pa.chunk_len = (const int *)c->chunk_len.p; pa.struct_chunk0 = (const int *)c->struct_chunk0.p;
+        if (kl_traj_group_finish(ga, c->stream) != hipSuccess ||
+            kl_totals(pa, c->n_chunks, pa.n_structs, (const double *)c->g_gath.p, (double *)c->bpart.p, (double *)c->g_tot2.p, c->stream) != hipSuccess ||
+            kl_traj_group_totals(ga, c->stream) != hipSuccess)
+            return ctx_fail(c, "launch of the groups' sums failed");
+        h.d_iso = ga.iso;
+    }
     /* (file output only) per-atom areas narrowed on the device: half the bytes over PCIe and into the file */
     const bool narrow = out[OUT_SASA].per_frame && T.io.out_f32();
     h.d_areas = narrow ? (char *)c->h_counts.p + T.widen_bytes : c->h_sasa.p;
     if (narrow && kl_narrow_f64((const double *)c->h_sasa.p, (float *)h.d_areas, (long long)h.na, c->stream) != hipSuccess) return ctx_fail(c, "narrowing launch failed");
+    if (h.d_iso && T.io.out_f32()) {
+        h.d_iso = (char *)c->h_counts.p + T.widen_bytes + 4 * T.n * T.FB;
+        if (kl_narrow_f64((const double *)c->h_iso.p, (float *)h.d_iso, (long long)h.na, c->stream) != hipSuccess) return ctx_fail(c, "narrowing launch failed");
+    }
     if (!T.xw) return 0;
     sasa::TrajArgs &ta = L.ta; /* (n_frames: shard_upload's) */
     double *const d_x = (double *)c->h_gtot.p;
-    const size_t nf = (size_t)h.nf;
     ta.sasa = (const double *)c->h_sasa.p;
     ta.cls_out = d_x; ta.res_out = d_x + T.x0[OUT_RES] * nf; ta.sel_out = d_x + T.x0[OUT_SEL] * nf; ta.sel_count = (long long *)(d_x + T.x0[N_OUT] * nf);
     if ((out[OUT_RES].per_frame && kl_traj_residues(ta, c->stream) != hipSuccess) || (out[OUT_CLS].per_frame && kl_traj_class(ta, c->stream) != hipSuccess) ||
@@ -553,19 +649,21 @@ int shard_compute(TrajRun &T, TrajLane &L, TrajShard &h)
     return 0;
 }
 
-/* The results to the host: totals and per-atom areas straight into the caller's arrays when those are page-locked, else into
+/* The results to the host: totals and per-atom (and isolated) areas straight into the caller's arrays when those are page-locked, else into
    c->stage_out one behind the other; the block of sums in ONE copy into c->res_stage; then the shard's one synchronisation. */
 int shard_download(TrajRun &T, freesasa_gpu_ctx *c, TrajShard &h)
 {
     const TrajOut *out = T.io.out;
-    const size_t nf = (size_t)h.nf, sasa_bytes = out[OUT_SASA].esz * out[OUT_SASA].per_frame * nf;
-    if (!T.direct_out && ensure_pinned(c, &c->stage_out, &c->stage_out_cap, 8 * nf + 8 * out[OUT_SASA].per_frame * nf)) return -1;
+    const size_t nf = (size_t)h.nf, sasa_bytes = out[OUT_SASA].esz * out[OUT_SASA].per_frame * nf, iso_bytes = out[OUT_ISO].esz * out[OUT_ISO].per_frame * nf;
+    if (!T.direct_out && ensure_pinned(c, &c->stage_out, &c->stage_out_cap, 8 * nf + 8 * (out[OUT_SASA].per_frame + out[OUT_ISO].per_frame) * nf)) return -1;
     if (T.xw && ensure_pinned(c, &c->res_stage, &c->res_stage_cap, 8 * T.xw * nf)) return -1;
     for (int k = 0; k < N_OUT; ++k)
         h.host[k] = k >= OUT_CLS ? (char *)c->res_stage + 8 * T.x0[k] * nf
-                  : T.direct_out ? (char *)out[k].mem + 8 * out[k].per_frame * (size_t)h.f0 : (char *)c->stage_out + (k == OUT_SASA ? 8 * nf : 0);
+                  : T.direct_out ? (char *)out[k].mem + 8 * out[k].per_frame * (size_t)h.f0
+                  : (char *)c->stage_out + (k == OUT_SASA ? 8 * nf : k == OUT_ISO ? 8 * nf + 8 * out[OUT_SASA].per_frame * nf : 0);
     if (hipMemcpyAsync(h.host[OUT_TOTALS], c->h_totals.p, 8 * nf, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         (sasa_bytes && hipMemcpyAsync(h.host[OUT_SASA], h.d_areas, sasa_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+        (iso_bytes && hipMemcpyAsync(h.host[OUT_ISO], h.d_iso, iso_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
         (T.xw && hipMemcpyAsync(c->res_stage, c->h_gtot.p, 8 * (T.x0[N_OUT] * nf + T.S), hipMemcpyDeviceToHost, c->stream) != hipSuccess))
         return ctx_fail(c, "device-to-host copy failed");
     if (hipStreamSynchronize(c->stream) != hipSuccess) return ctx_fail(c, "stream synchronize failed");
@@ -700,6 +798,31 @@ extern "C" int freesasa_gpu_trajectory(const double *xyz_frames, const double *r
     return freesasa_gpu_trajectory_devices(xyz_frames, radii, n_atoms, n_frames, alg, probe, resolution, frames_per_batch, totals_out, sasa_out, &device, 1, err_out, err_len);
 }
 
+extern "C" int freesasa_gpu_trajectory_groups(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
+                                              int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
+                                              const int32_t *group, int n_groups,
+                                              int alg, double probe, int resolution, int frames_per_batch,
+                                              double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
+                                              double *sel_area_out, long long *sel_atoms_out, double *group_areas_out, double *iso_out,
+                                              const int *devices, int n_devices, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    return guarded(err_out, err_len, [&]() -> int {
+        TrajTopo tp;
+        if (topo_make(batch, structure, frame_atoms, atom_index, sel, &tp, err_out, err_len)) return -1;
+        if (group_make(group, n_groups, group_areas_out != nullptr, iso_out != nullptr, &tp, err_out, err_len)) return -1;
+        if (!xyz_frames || !totals_out) return set_err(err_out, err_len, "null argument");
+        if ((sel_area_out || sel_atoms_out) && !sel) return set_err(err_out, err_len, "selection outputs need a selection set");
+        TrajSpec s = {tp.radii, tp.n, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, &tp};
+        if (traj_check_args(s, "n_frames must be > 0", err_out, err_len) || traj_shard_size(s, frame_atoms, err_out, err_len)) return -1;
+        TrajIO io;
+        io.mem_in = xyz_frames; io.sel_atoms = sel_atoms_out;
+        double *const mem[N_OUT] = {totals_out, sasa_out, iso_out, class_sums_out, residues_out, sel_area_out, group_areas_out};
+        for (int k = 0; k < N_OUT; ++k) io.out[k].mem = mem[k];
+        return traj_run(io, s, err_out, err_len) < 0 ? -1 : 0;
+    });
+}
+
 extern "C" int freesasa_gpu_trajectory_topology(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
                                                 int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
                                                 int alg, double probe, int resolution, int frames_per_batch,
@@ -707,26 +830,16 @@ extern "C" int freesasa_gpu_trajectory_topology(const double *xyz_frames, int n_
                                                 double *sel_area_out, long long *sel_atoms_out,
                                                 const int *devices, int n_devices, char *err_out, int err_len)
 {
-    if (err_out && err_len > 0) err_out[0] = 0;
-    return guarded(err_out, err_len, [&]() -> int {
-        TrajTopo tp;
-        if (topo_make(batch, structure, frame_atoms, atom_index, sel, &tp, err_out, err_len)) return -1;
-        if (!xyz_frames || !totals_out) return set_err(err_out, err_len, "null argument");
-        if ((sel_area_out || sel_atoms_out) && !sel) return set_err(err_out, err_len, "selection outputs need a selection set");
-        TrajSpec s = {tp.radii, tp.n, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, &tp};
-        if (traj_check_args(s, "n_frames must be > 0", err_out, err_len) || traj_shard_size(s, frame_atoms, err_out, err_len)) return -1;
-        TrajIO io;
-        io.mem_in = xyz_frames; io.sel_atoms = sel_atoms_out;
-        double *const mem[N_OUT] = {totals_out, sasa_out, class_sums_out, residues_out, sel_area_out};
-        for (int k = 0; k < N_OUT; ++k) io.out[k].mem = mem[k];
-        return traj_run(io, s, err_out, err_len) < 0 ? -1 : 0;
-    });
+    return freesasa_gpu_trajectory_groups(xyz_frames, n_frames, batch, structure, frame_atoms, atom_index, sel, nullptr, 0, alg, probe, resolution,
+                                          frames_per_batch, totals_out, sasa_out, class_sums_out, residues_out, sel_area_out, sel_atoms_out, nullptr, nullptr,
+                                          devices, n_devices, err_out, err_len);
 }
 
 /* The first line of a trajectory file run's done-list names the run: the parameters, the frame file's size and modification
    time and a checksum of the radii - NOT the devices: a run interrupted on eight GPUs may be finished on one, with the same
    files byte for byte.  With a topology, in front of the line's end, what its outputs depend on: digests of the index, of
-   residue boundaries + classes + backbone flags, of the selection set's program, and which result files the run writes. */
+   residue boundaries + classes + backbone flags, of the selection set's program, and which result files the run writes; with
+   chain groups, behind that, a digest of the group count and the ids. */
 static int traj_done_head(char *head, size_t cap, const TrajSpec &s, const TrajIO &io, const struct stat &st)
 {
     int len = snprintf(head, cap, "freesasa_amd trajectory done-list v2 n_atoms=%d n_frames=%lld frames_per_batch=%d alg=%d resolution=%d probe=%.17g f32=%d "
@@ -748,6 +861,9 @@ static int traj_done_head(char *head, size_t cap, const TrajSpec &s, const TrajI
         for (const TrajOut &o : io.out) outputs |= o.path ? o.bit : 0;
         len += snprintf(head + len - 1, cap - (size_t)len + 1, " topology frame_atoms=%d index=%016llx residues=%016llx selection=%016llx outputs=%d\n",
                         tp->frame_atoms, tp->index ? fnv1a(tp->index, 4 * (size_t)tp->n) : 0ULL, h_res, h_sel, outputs) - 1;
+        /* ... and with chain groups a digest of G and the ids (a run without groups keeps the line it had) */
+        if (tp->group && len > 0 && len < (int)cap)
+            len += snprintf(head + len - 1, cap - (size_t)len + 1, " groups=%016llx\n", fnv1a(tp->group, 4 * (size_t)tp->n, fnv1a(&tp->n_groups, sizeof tp->n_groups))) - 1;
     }
     return len > 0 && len < (int)cap ? 0 : -1;
 }
@@ -766,18 +882,19 @@ static int trajectory_file_run(const char *frames_path, int frames_f32, long lon
     if (io.in.fd < 0) return set_err(err_out, err_len, "cannot open the frame file");
     struct stat st;
     if (fstat(io.in.fd, &st) != 0) return set_err(err_out, err_len, "cannot stat the frame file");
-    io.in_header = header_bytes; io.in_f32 = (frames_f32 & 1) ? 1 : 0; io.out[OUT_SASA].esz = (frames_f32 & 2) ? 4 : 8;
+    io.in_header = header_bytes; io.in_f32 = (frames_f32 & 1) ? 1 : 0; io.out[OUT_SASA].esz = io.out[OUT_ISO].esz = (frames_f32 & 2) ? 4 : 8;
     const long long in_file = ((long long)st.st_size - header_bytes) / ((io.in_f32 ? 12LL : 24LL) * frame_atoms);
     if (s.n_frames <= 0) s.n_frames = in_file;
     if (s.n_frames <= 0 || s.n_frames > in_file) return set_err(err_out, err_len, "the frame file holds fewer frames than asked for");
     if (frames_total_out) *frames_total_out = s.n_frames;
     if (traj_shard_size(s, frame_atoms, err_out, err_len)) return -1;
     if (done_path) {
-        char head[500];
+        char head[640];
         if (traj_done_head(head, sizeof head, s, io, st)) return set_err(err_out, err_len, "cannot write the done-list");
         const int fpb = s.frames_per_batch;
         if (io.list.read(done_path, head, (s.n_frames + fpb - 1) / fpb, [fpb](long long k, long long f0, long long) { return f0 == k * fpb; }) == DoneList::REFUSED)
-            return set_err(err_out, err_len, s.topo ? "the done-list belongs to a run with other parameters, radii, topology, selections, outputs or frame file"
+            return set_err(err_out, err_len, s.topo && s.topo->group ? "the done-list belongs to a run with other parameters, radii, topology, selections, chain groups, outputs or frame file"
+                                           : s.topo ? "the done-list belongs to a run with other parameters, radii, topology, selections, outputs or frame file"
                                                     : "the done-list belongs to a run with other parameters, radii or frame file");
     }
     for (TrajOut &o : io.out) { /* (a resumed run's files keep what the listed shards wrote) */
@@ -806,6 +923,32 @@ extern "C" int freesasa_gpu_trajectory_file_devices(const char *frames_path, int
     return trajectory_file_run(frames_path, frames_f32, header_bytes, s, io, done_path, frames_total_out, err_out, err_len);
 }
 
+extern "C" int freesasa_gpu_trajectory_file_groups(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
+                                                   const freesasa_ingest_batch *batch, int structure,
+                                                   int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
+                                                   const int32_t *group, int n_groups,
+                                                   int alg, double probe, int resolution, int frames_per_batch,
+                                                   const char *totals_path, const char *sasa_path, const char *class_sums_path,
+                                                   const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
+                                                   const char *group_areas_path, const char *iso_path,
+                                                   const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                                   long long *frames_total_out, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    return guarded(err_out, err_len, [&]() -> int {
+        TrajTopo tp; /* (outlives the run: the lanes upload from it) */
+        if (topo_make(batch, structure, frame_atoms, atom_index, sel, &tp, err_out, err_len)) return -1;
+        if (group_make(group, n_groups, group_areas_path != nullptr, iso_path != nullptr, &tp, err_out, err_len)) return -1;
+        if ((sel_area_path || sel_atoms_out) && !sel) return set_err(err_out, err_len, "selection outputs need a selection set");
+        TrajSpec s = {tp.radii, tp.n, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, &tp, max_new_shards};
+        TrajIO io;
+        io.sel_atoms = sel_atoms_out;
+        const char *const path[N_OUT] = {totals_path, sasa_path, iso_path, class_sums_path, residues_path, sel_area_path, group_areas_path};
+        for (int k = 0; k < N_OUT; ++k) io.out[k].path = path[k];
+        return trajectory_file_run(frames_path, frames_f32, header_bytes, s, io, done_path, frames_total_out, err_out, err_len);
+    });
+}
+
 extern "C" int freesasa_gpu_trajectory_file_topology(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
                                                      const freesasa_ingest_batch *batch, int structure,
                                                      int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
@@ -815,18 +958,10 @@ extern "C" int freesasa_gpu_trajectory_file_topology(const char *frames_path, in
                                                      const char *done_path, long long max_new_shards, const int *devices, int n_devices,
                                                      long long *frames_total_out, char *err_out, int err_len)
 {
-    if (err_out && err_len > 0) err_out[0] = 0;
-    return guarded(err_out, err_len, [&]() -> int {
-        TrajTopo tp; /* (outlives the run: the lanes upload from it) */
-        if (topo_make(batch, structure, frame_atoms, atom_index, sel, &tp, err_out, err_len)) return -1;
-        if ((sel_area_path || sel_atoms_out) && !sel) return set_err(err_out, err_len, "selection outputs need a selection set");
-        TrajSpec s = {tp.radii, tp.n, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, &tp, max_new_shards};
-        TrajIO io;
-        io.sel_atoms = sel_atoms_out;
-        const char *const path[N_OUT] = {totals_path, sasa_path, class_sums_path, residues_path, sel_area_path};
-        for (int k = 0; k < N_OUT; ++k) io.out[k].path = path[k];
-        return trajectory_file_run(frames_path, frames_f32, header_bytes, s, io, done_path, frames_total_out, err_out, err_len);
-    });
+    return freesasa_gpu_trajectory_file_groups(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, nullptr, 0,
+                                               alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
+                                               sel_area_path, sel_atoms_out, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
+                                               frames_total_out, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_trajectory_file(const char *frames_path, int frames_f32, long long header_bytes, const double *radii,

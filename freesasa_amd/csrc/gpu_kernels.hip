@@ -916,6 +916,47 @@ hipError_t kl_traj_sel(const TrajArgs &a, hipStream_t st)
     return hipGetLastError();
 }
 
+/* ... chain groups per frame (traj_kernels.h): the combined batch's radii (once per lane and shard length), the isolated
+   structures' coordinates in front of the engine; the finish and the three columns per (frame, group) behind it */
+__global__ __launch_bounds__(TRAJ_B) void k_traj_group_radii(TrajGroupArgs a)
+{
+    traj_group_radii(a, (int64_t)blockIdx.x * TRAJ_B + threadIdx.x);
+}
+__global__ __launch_bounds__(TRAJ_B) void k_traj_group_gather(TrajGroupArgs a)
+{
+    traj_group_gather(a, (int64_t)blockIdx.x * TRAJ_B + threadIdx.x);
+}
+__global__ __launch_bounds__(TRAJ_B) void k_traj_group_finish(TrajGroupArgs a)
+{
+    traj_group_finish(a, (int64_t)blockIdx.x * TRAJ_B + threadIdx.x);
+}
+__global__ __launch_bounds__(TRAJ_B) void k_traj_group_totals(TrajGroupArgs a)
+{
+    traj_group_totals(a, (int64_t)blockIdx.x * TRAJ_B + threadIdx.x);
+}
+static unsigned traj_group_grid(int64_t threads) { return (unsigned)((threads + TRAJ_B - 1) / TRAJ_B); }
+hipError_t kl_traj_group_radii(const TrajGroupArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_traj_group_radii, dim3(traj_group_grid((int64_t)a.n_frames * ((int64_t)a.n + a.n_iso))), dim3(TRAJ_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_traj_group_gather(const TrajGroupArgs &a, hipStream_t st)
+{
+    if (a.n_iso == 0) return hipSuccess; /* (every group empty: nothing behind the frames) */
+    hipLaunchKernelGGL(k_traj_group_gather, dim3(traj_group_grid(3 * (int64_t)a.n_frames * a.n_iso)), dim3(TRAJ_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_traj_group_finish(const TrajGroupArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_traj_group_finish, dim3(traj_group_grid((int64_t)a.n_frames * ((int64_t)a.n + a.n_iso))), dim3(TRAJ_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_traj_group_totals(const TrajGroupArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_traj_group_totals, dim3(traj_group_grid((int64_t)a.n_frames * a.n_groups)), dim3(TRAJ_B), 0, st, a);
+    return hipGetLastError();
+}
+
 void kl_dump_phase_clocks(void)
 {
 #ifdef SASA_PHASE_TIMING

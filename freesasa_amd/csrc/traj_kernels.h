@@ -8,6 +8,7 @@
  *   traj_residue       the six per-residue areas of every (frame, residue), as residue_areas (sasa_kernels.h)
  *   traj_class_phase0  the three class sums of every frame, as class_phase0 / class_phase1
  *   traj_sel_phase0/1  the selection areas of every frame, as sel_sums_phase0 / sel_sums_phase1 (select_kernels.h)
+ *   traj_group_*       chain groups per frame: the isolated structures behind the frames, as group_kernels.h (at the end)
  *
  * Atom i of frame f is element f * n + i of the shard's per-atom areas and reads the per-topology arrays at i.  Every sum
  * takes its atoms in the order of the function it is named after - the same chunks of SASA_TOT_B, left to right, the
@@ -121,6 +122,100 @@ SASA_D void traj_sel_phase1(const TrajArgs &a, const double *part, const int *cn
     for (int k = 0; k < SASA_TOT_B; ++k) { t += part[tid * SASA_TOT_B + k]; c += cnt[tid * SASA_TOT_B + k]; }
     a.sel_out[(int64_t)f * a.n_sel + g0 + tid] = t;
     a.sel_count[(int64_t)f * a.n_sel + g0 + tid] = c;
+}
+
+/* ------------------------------------------------------------------ chain groups per frame
+ * (freesasa_gpu_trajectory_groups / _trajectory_file_groups): every frame in its complex and every group of it cut out as a
+ * structure of its own, in ONE batch per shard.  The topology's cut into its groups is the same for every frame: the host
+ * makes it once per run (traj_group_cut: src, gfirst), a lane uploads src once.  The combined batch of a shard of nf frames:
+ *
+ *     atoms  [0, nf n)                          the nf complex frames, where the plain path has them
+ *            nf n + f n_iso + gfirst[g] ...     the isolated structure of group g of frame f: its atoms in input order
+ *     structures  f < nf: frame f;  nf + f G + g: group g of frame f
+ *
+ * which is, structure for structure and atom for atom, the combined batch freesasa_gpu_groups_dev (group_kernels.h) makes of
+ * the nf frames given as a batch of nf structures with the ids repeated - so the engine's areas and totals, the totals
+ * kernels over cgath (the same chunk tables) and the columns below are that entry's, bit for bit.  No float atomics. */
+
+struct TrajGroupArgs {
+    int n, n_iso, n_groups;   /* atoms of the topology, those of them with an id >= 0, groups */
+    int n_frames;             /* frames of this shard */
+    const int32_t *group;     /* [n] group id of every atom of the topology, -1: in no group */
+    const int32_t *src;       /* [n_iso] topology atom of every isolated atom: group-major, input order within a group */
+    const double *radii;      /* [n] the topology's radii */
+    double *xyz;              /* [3 n_frames (n + n_iso)] the combined batch: the compact frames first (gather: in and out) */
+    double *cradii;           /* [n_frames (n + n_iso)] its per-atom radii */
+    const double *csasa;      /* [n_frames (n + n_iso)] its areas */
+    double *cgath;            /* [n_frames (n + n_iso)] the complex area of every combined atom */
+    double *iso;              /* [n_frames n] every atom's area in its isolated group, frame-major input order; or null */
+    const double *ctot, *ctot2; /* [n_frames (1 + n_groups)] per combined structure: over csasa (the engine's), over cgath */
+    double *out;              /* [n_frames n_groups 3] isolated, complex, buried */
+};
+
+/* The cut, on the host, once per run: gfirst [n_groups + 1] (prefix of the groups' atom counts) and src [atoms with an id
+   >= 0] - the order grp_rank_struct (group_kernels.h) produces for a one-structure batch.  Returns n_iso, or -1 with the first
+   atom whose id is < -1 or >= n_groups in *bad_atom. */
+inline int64_t traj_group_cut(const int32_t *group, int64_t n, int n_groups, int64_t *gfirst, int32_t *src, int64_t *bad_atom)
+{
+    for (int g = 0; g <= n_groups; ++g) gfirst[g] = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (group[i] < -1 || group[i] >= n_groups) { *bad_atom = i; return -1; }
+        if (group[i] >= 0) ++gfirst[group[i] + 1];
+    }
+    for (int g = 0; g < n_groups; ++g) gfirst[g + 1] += gfirst[g];
+    for (int64_t i = 0; i < n; ++i)
+        if (group[i] >= 0) src[gfirst[group[i]]++] = (int32_t)i; /* (gfirst[g] runs up to gfirst[g + 1] ...) */
+    for (int g = n_groups; g > 0; --g) gfirst[g] = gfirst[g - 1]; /* (... and is put back) */
+    gfirst[0] = 0;
+    return gfirst[n_groups];
+}
+
+/* traj_group_radii, one thread per combined atom: n_frames copies of the n radii, then n_frames copies of the n_iso permuted
+   ones.  Once per lane and shard length: the radii do not change over the run. */
+SASA_D void traj_group_radii(const TrajGroupArgs &a, int64_t t)
+{
+    const int64_t nc = (int64_t)a.n_frames * a.n;
+    if (t < nc) a.cradii[t] = a.radii[t % a.n];
+    else if (t < nc + (int64_t)a.n_frames * a.n_iso) a.cradii[t] = a.radii[a.src[(t - nc) % a.n_iso]];
+}
+
+/* traj_group_gather, one thread per COORDINATE of the isolated part (3 n_frames n_iso): consecutive lanes write consecutive
+   doubles behind the compact frames and read them through src (three lanes share an atom). */
+SASA_D void traj_group_gather(const TrajGroupArgs &a, int64_t t)
+{
+    if (t >= 3 * (int64_t)a.n_frames * a.n_iso) return;
+    const int64_t atom = t / 3;
+    const int comp = (int)(t - 3 * atom);
+    const int64_t f = atom / a.n_iso;
+    const int j = (int)(atom - f * a.n_iso);
+    a.xyz[3 * (int64_t)a.n_frames * a.n + t] = a.xyz[3 * (f * a.n + a.src[j]) + comp];
+}
+
+/* traj_group_finish, one thread per combined atom: grp_finish_atom with the frame arithmetic (the complex areas stay where the
+   engine wrote them: the driver reads csasa[f n + i]). */
+SASA_D void traj_group_finish(const TrajGroupArgs &a, int64_t t)
+{
+    const int64_t nc = (int64_t)a.n_frames * a.n;
+    if (t < nc) {
+        const double v = a.csasa[t];
+        a.cgath[t] = v;
+        if (a.iso && a.group[t % a.n] < 0) a.iso[t] = v;
+    } else if (t < nc + (int64_t)a.n_frames * a.n_iso) {
+        const int64_t q = t - nc, f = q / a.n_iso;
+        const int64_t i = f * a.n + a.src[q - f * a.n_iso];
+        if (a.iso) a.iso[i] = a.csasa[t];
+        a.cgath[t] = a.csasa[i];
+    }
+}
+
+/* traj_group_totals, one thread per (frame, group): grp_totals_item's three columns */
+SASA_D void traj_group_totals(const TrajGroupArgs &a, int64_t t)
+{
+    if (t >= (int64_t)a.n_frames * a.n_groups) return;
+    const double t0 = a.ctot[a.n_frames + t], t1 = a.ctot2[a.n_frames + t];
+    a.out[3 * t] = t0;
+    a.out[3 * t + 1] = t1;
+    a.out[3 * t + 2] = t0 - t1;
 }
 
 } /* namespace sasa */

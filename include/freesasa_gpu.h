@@ -360,7 +360,7 @@ int freesasa_gpu_sweep_files_select(const char *const *paths, int n_paths, int i
    (group_out [n_atoms], n_groups_out and status_out [n_structs]): offsets, residue boundaries, chain labels and status go up,
    the three arrays come back; on a pooled context of `device` (-1: any).  0 / -1 with the message in err.
    Not offered: a done-list / resumable form (records of variable length), the cache sweep (a cache read brings no residue
-   arrays), chain groups in the trajectory drivers. */
+   arrays).  (Chain groups in the trajectory drivers: freesasa_gpu_trajectory_groups below.) */
 typedef struct freesasa_gpu_group_table {
     int32_t n_files;
     int64_t n_groups;
@@ -461,7 +461,7 @@ int freesasa_gpu_trajectory(const double *xyz_frames, const double *radii, int n
    Argument errors - NULL batch, structure out of range, a structure that failed to load or has no atoms, a bad index,
    frame_atoms < n - return -1 with a message before a device is touched or a file opened.
    Returns as the plain drivers: 0 / -1, the file form 1 when max_new_shards stopped it.
-   Not offered: chain groups in the trajectory drivers, relative areas in files, trajectory container formats. */
+   Not offered: relative areas in files, trajectory container formats.  (Chain groups: freesasa_gpu_trajectory_groups below.) */
 int freesasa_gpu_trajectory_topology(const double *xyz_frames, int n_frames, const struct freesasa_ingest_batch *batch, int structure,
                                      int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
                                      int alg, double probe_radius, int resolution, int frames_per_batch,
@@ -476,6 +476,52 @@ int freesasa_gpu_trajectory_file_topology(const char *frames_path, int frames_f3
                                           const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
                                           const char *done_path, long long max_new_shards, const int *devices, int n_devices,
                                           long long *frames_total_out, char *err, int err_len);
+
+/* CHAIN GROUPS in the trajectory drivers: the reference's --chain-groups / --separate-chains as a time series of an interface
+   - per frame the area every group of chains has on its own, the area it has in the complex, and the area it buries.  The two
+   entries above are these with group = NULL; the arguments are theirs, with behind `sel`
+     group, n_groups    group [n]: one int32 id per atom of the topology's structure, -1 = in no group - the slice
+                        [offsets[structure], offsets[structure + 1]) of what freesasa_ingest_chain_groups or
+                        freesasa_gpu_chain_group_ids gives for the batch; 1 <= n_groups <= 65535.  An empty group is allowed
+                        (its totals are 0).  group NULL: no groups, and both outputs below must be NULL.
+   and behind sel_atoms_out the outputs (memory form: arrays; file form: paths, offsets fixed by the frame number)
+     group areas  3 G per frame       (8 * 3 G f)      isolated, complex, buried of every group: required with group
+     isolated     n per frame         (8 n f)          every atom's area in its group taken on its own (= its complex area
+                                                       for an atom in no group); may be NULL (file form: fp32, 4 n f, when
+                                                       bit 1 of frames_f32 is set)
+   group_areas_out[f] is bit for bit d_group_totals, and iso_out[f] d_iso, of freesasa_gpu_groups_dev (below) on frame f taken
+   as a structure of its own; every other output is bit for bit what the entries above give without groups.
+   The topology does not change over the run, so neither does its cut into groups: the host makes it once (the atoms of every
+   group in input order), a lane uploads it once and writes the radii of its shards once; per shard ONE batch goes through
+   the engine - the frames where they are without groups, behind them every group of every frame as a structure of its own
+   (one gather kernel) - and behind the tile kernels the groups' complex areas are summed with the chunks of their isolated
+   totals (csrc/traj_kernels.h).  The engine therefore sees up to TWICE the atoms of a shard: n + (atoms with an id >= 0)
+   per frame; frames_per_batch <= 0 is still 1250000 / frame_atoms + 1, and frames_per_batch times that sum, and times
+   1 + n_groups, must not exceed 2^30 (-1 with a message).  A run without groups takes exactly the copies and kernels it took.
+   The done-list's first line names the outputs (groups 16, isolated 32) and ends in groups=<digest of n_groups and the ids>;
+   a list that differs is refused; both files are flushed before their shard is listed.
+   Argument errors, -1 with a message before a device is touched or a file opened: an id < -1 or >= n_groups (the message
+   names the atom and the id), n_groups out of range, group given without group areas or either output without group.
+   Not offered: a buried area per residue, group ids made on the device for a trajectory (make them once with
+   freesasa_gpu_chain_group_ids), trajectory container formats. */
+int freesasa_gpu_trajectory_groups(const double *xyz_frames, int n_frames, const struct freesasa_ingest_batch *batch, int structure,
+                                   int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
+                                   const int32_t *group, int n_groups,
+                                   int alg, double probe_radius, int resolution, int frames_per_batch,
+                                   double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
+                                   double *sel_area_out, long long *sel_atoms_out,
+                                   double *group_areas_out /* [F, G, 3] */, double *iso_out /* [F, n] or NULL */,
+                                   const int *devices, int n_devices, char *err, int err_len);
+int freesasa_gpu_trajectory_file_groups(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
+                                        const struct freesasa_ingest_batch *batch, int structure,
+                                        int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
+                                        const int32_t *group, int n_groups,
+                                        int alg, double probe_radius, int resolution, int frames_per_batch,
+                                        const char *totals_path, const char *sasa_path, const char *class_sums_path,
+                                        const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
+                                        const char *group_areas_path, const char *iso_path,
+                                        const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                        long long *frames_total_out, char *err, int err_len);
 
 /* Chain groups: the area of every atom in its complex AND in its group taken on its own (the reference's
    --chain-groups / --separate-chains: freesasa_structure_get_chains_lcl, src/structure.c:1026-1080, minus the

@@ -7,13 +7,17 @@ system (fp32, page cache warm) whose solute is a 10 000-atom poly-alanine globul
               solvent on the host would run; the stripping itself is not timed)
     totals    trajectory_file_topology on the full frames, totals only
     all       ... with class sums, per-residue areas (2000 residues) and 8 selections
+    groups    ... totals and the chain groups' areas (isolated, complex, buried per frame): the solute cut into two groups of
+              5 000 atoms, group areas only - against `totals` this is what the groups cost
+    longway   the same numbers without the driver's groups: per shard-sized run of frames the host reads the full frames,
+              strips the solvent, widens to fp64 and calls calc_groups with the ids repeated per frame (per-atom areas come back)
 
 One JSON line per arm: atom-frames/s counted in SOLUTE atoms and in frame atoms, the median and the spread of --reps runs.
 
-    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--scratch DIR] [--out FILE]
+    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE]
 
 For the kernel times: `rocprofv3 --kernel-trace --stats -- python tools/traj_topology_bench.py --reps 1 --arms all`
-(k_traj_gather / k_traj_residues / k_traj_class / k_traj_sel are the topology's kernels)."""
+(k_traj_gather / k_traj_residues / k_traj_class / k_traj_sel are the topology's kernels, k_traj_group_* the groups')."""
 import argparse
 import json
 import os
@@ -63,11 +67,26 @@ def make_frames(scratch, xyz, n_frames):
     return full, bare
 
 
+def long_way(full, b, ids, n_frames, out_path):
+    """group areas of every frame through calc_groups on host-tiled batches of the driver's default shard length"""
+    fpb = 1250000 // N_FRAME + 1
+    areas = np.empty((n_frames, 2, 3))
+    frames = np.memmap(full, dtype=np.float32, mode="r", shape=(n_frames, N_FRAME, 3))
+    for f0 in range(0, n_frames, fpb):
+        nf = min(fpb, n_frames - f0)
+        xyz = np.ascontiguousarray(frames[f0:f0 + nf, :N_SOLUTE], dtype=np.float64).reshape(-1, 3)
+        offs = np.arange(nf + 1, dtype=np.int64) * N_SOLUTE
+        _, _, _, gt = fa.calc_groups(xyz, np.tile(b.radii, nf), offs, np.tile(ids, nf), np.full(nf, 2, np.int32))
+        areas[f0:f0 + nf] = gt.reshape(nf, 2, 3)
+    areas.tofile(out_path)
+    return True, n_frames
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=240)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--arms", default="plain,totals,all")
+    ap.add_argument("--arms", default="plain,totals,all,groups,longway")
     ap.add_argument("--scratch", default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -77,12 +96,16 @@ def main():
         full, bare = make_frames(scratch, xyz, args.frames)
         sel = ingest.Selection(EIGHT)
         index = np.arange(N_SOLUTE, dtype=np.int32)
+        ids = (np.arange(N_SOLUTE) >= N_SOLUTE // 2).astype(np.int32)
         p = lambda k: os.path.join(scratch, k)
         arms = {
             "plain": lambda: fa.trajectory_file(bare, b.radii, p("t0"), f32=True),
             "totals": lambda: fa.trajectory_file_topology(full, b, p("t1"), atom_index=index, frame_atoms=N_FRAME, f32=True),
             "all": lambda: fa.trajectory_file_topology(full, b, p("t2"), atom_index=index, frame_atoms=N_FRAME, f32=True, selection=sel,
                                                        class_sums_path=p("c2"), residues_path=p("r2"), selections_path=p("s2")),
+            "groups": lambda: fa.trajectory_file_topology(full, b, p("t3"), atom_index=index, frame_atoms=N_FRAME, f32=True, group=ids, n_groups=2,
+                                                          group_areas_path=p("g3")),
+            "longway": lambda: long_way(full, b, ids, args.frames, p("g4")),
         }
         names = [a for a in args.arms.split(",") if a in arms]
         runs = {a: [] for a in names}
@@ -94,7 +117,9 @@ def main():
                 res = arms[a]()
                 runs[a].append(time.perf_counter() - t0)
                 assert res[0] and res[1] == args.frames
-        assert not names or np.array_equal(np.fromfile(p("t0" if "plain" in names else "t1")), np.fromfile(p({"plain": "t0", "totals": "t1", "all": "t2"}[names[-1]])))
+        totals = [np.fromfile(p(k)) for a, k in (("plain", "t0"), ("totals", "t1"), ("all", "t2"), ("groups", "t3")) if a in names]
+        assert all(np.array_equal(t, totals[0]) for t in totals)
+        assert not ("groups" in names and "longway" in names) or np.array_equal(np.fromfile(p("g3")), np.fromfile(p("g4")))
         lines = []
         for a in names:
             v = sorted(runs[a])
