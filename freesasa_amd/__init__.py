@@ -630,14 +630,56 @@ def trajectory(xyz_frames, radii, alg=LEE_RICHARDS, probe=1.4, resolution=20, fr
     return totals, sasa
 
 
+FRAMES_F32, FRAMES_OUT_F32, FRAMES_DCD = 1, 2, 4   # the bits of frames_f32 (include/freesasa_gpu.h)
+
+
+class DcdInfoC(C.Structure):
+    _fields_ = [("n_atoms", C.c_int32), ("n_frames", C.c_int64), ("n_frames_header", C.c_int64), ("first_frame", C.c_int64),
+                ("frame_bytes", C.c_int64), ("x_off", C.c_int32), ("plane_bytes", C.c_int32), ("big_endian", C.c_int32),
+                ("has_cell", C.c_int32), ("has_4d", C.c_int32), ("charmm_version", C.c_int32)]
+
+
+class DcdInfo:
+    """What dcd_info() returns: the fields of freesasa_gpu_dcd_info (include/freesasa_gpu.h) - n_atoms, n_frames (whole
+    frames by file size), n_frames_header (as the header claims), first_frame, frame_bytes, x_off, plane_bytes (bytes), and
+    the flags big_endian, has_cell, has_4d as bools, charmm_version."""
+
+    def __init__(self, c):
+        for name, _ in DcdInfoC._fields_:
+            v = int(getattr(c, name))
+            setattr(self, name, bool(v) if name in ("big_endian", "has_cell", "has_4d") else v)
+
+    def __repr__(self):
+        return "DcdInfo(" + ", ".join(f"{name}={getattr(self, name)}" for name, _ in DcdInfoC._fields_) + ")"
+
+
+def dcd_info(path):
+    """freesasa_gpu_dcd_info_read(): the header of a DCD trajectory -> DcdInfo; ValueError with the library's message for
+    a file that is no DCD, is damaged, or is a DCD the drivers do not read (fixed atoms, 64-bit record markers)."""
+    L = lib()
+    L.freesasa_gpu_dcd_info_read.argtypes = [C.c_char_p, C.POINTER(DcdInfoC), C.c_char_p, C.c_int]
+    c = DcdInfoC()
+    err = C.create_string_buffer(512)
+    if L.freesasa_gpu_dcd_info_read(str(path).encode(), C.byref(c), err, 512):
+        raise ValueError("freesasa_gpu_dcd_info_read: " + err.value.decode())
+    return DcdInfo(c)
+
+
+def _frames_bits(f32, out_f32, dcd, header_bytes):
+    if dcd and (f32 or header_bytes):
+        raise ValueError("dcd=True excludes f32=True and a non-zero header_bytes: a DCD file says for itself where its frames are")
+    return (FRAMES_F32 if f32 else 0) | (FRAMES_OUT_F32 if out_f32 else 0) | (FRAMES_DCD if dcd else 0)
+
+
 def trajectory_file(frames_path, radii, totals_path, sasa_path=None, done_path=None, f32=False, header_bytes=0,
                     n_frames=0, alg=LEE_RICHARDS, probe=1.4, resolution=20, frames_per_batch=0, max_new_shards=0, device=-1,
-                    devices=None, out_f32=False):
+                    devices=None, out_f32=False, dcd=False):
     """freesasa_gpu_trajectory_file(): raw frame file -> totals file (+ per-atom file), resumable through the
     done-list at done_path.  Returns (complete, n_frames): complete is False when max_new_shards stopped the run.
-    f32: the frames are floats (an input format); out_f32: the per-atom file holds floats (an output format)."""
+    f32: the frames are floats (an input format); out_f32: the per-atom file holds floats (an output format);
+    dcd: frames_path is a DCD trajectory whose NATOM is len(radii) (no f32, no header_bytes with it)."""
     radii = _f64(radii)
-    f32 = (1 if f32 else 0) | (2 if out_f32 else 0)
+    f32 = _frames_bits(f32, out_f32, dcd, header_bytes)
     err = C.create_string_buffer(512)
     total = C.c_longlong(0)
     enc = lambda p: None if p is None else str(p).encode()
@@ -780,17 +822,20 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
                              sasa_path=None, class_sums_path=None, residues_path=None, selections_path=None, done_path=None,
                              f32=False, header_bytes=0, n_frames=0, alg=LEE_RICHARDS, probe=1.4, resolution=20, frames_per_batch=0,
                              max_new_shards=0, device=-1, devices=None, out_f32=False, chain_groups=None, separate_chains=False,
-                             long=False, group=None, n_groups=None, group_areas_path=None, isolated_path=None):
+                             long=False, group=None, n_groups=None, group_areas_path=None, isolated_path=None, dcd=False):
     """freesasa_gpu_trajectory_file_topology(): trajectory_file() with a topology (see trajectory_topology; frame_atoms:
     atoms per frame of the file, None: the structure's) and one raw fp64 result file per output asked for: class sums
     [F, 3], residues [F, R, 6], selection areas [F, S].  Returns (complete, n_frames, selection_atoms [S] or None).
     Chain groups (the keywords of trajectory_topology; freesasa_gpu_trajectory_file_groups): group_areas_path receives
-    [F, G, 3] fp64, isolated_path [F, n] fp64 (fp32 with out_f32)."""
+    [F, G, 3] fp64, isolated_path [F, n] fp64 (fp32 with out_f32).
+    dcd: frames_path is a DCD trajectory; frame_atoms None is then the file's NATOM."""
     L = _topology_proto(lib())
+    if dcd and frame_atoms is None:
+        frame_atoms = dcd_info(frames_path).n_atoms
     n, R, res_ref, idx, fa_ = _topology_args(batch, structure, atom_index, frame_atoms)
     S = len(selection) if selection is not None else 0
     sel_atoms = np.zeros(S, dtype=np.int64) if selection is not None else None
-    bits = (1 if f32 else 0) | (2 if out_f32 else 0)
+    bits = _frames_bits(f32, out_f32, dcd, header_bytes)
     err = C.create_string_buffer(512)
     total = C.c_longlong(0)
     enc = lambda p: None if p is None else str(p).encode()

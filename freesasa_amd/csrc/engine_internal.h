@@ -90,6 +90,8 @@ hipError_t kl_sel_sums(const sasa::SelArgs &a, hipStream_t st);
    engine reads; per-frame residue areas (one thread per frame and residue), class sums (one workgroup per frame) and
    selection areas (one workgroup per frame and SEL_G selections) */
 hipError_t kl_traj_gather(const sasa::TrajArgs &a, const void *d_in, bool in_f32, double *d_out, hipStream_t st);
+/* ... the same from the bytes of DCD frames (planar fp32 records, byte-swapped when big_endian): the gather and the widening in one */
+hipError_t kl_traj_gather_dcd(const sasa::TrajDcdArgs &a, const void *d_in, bool big_endian, double *d_out, hipStream_t st);
 hipError_t kl_traj_residues(const sasa::TrajArgs &a, hipStream_t st);
 hipError_t kl_traj_class(const sasa::TrajArgs &a, hipStream_t st);
 hipError_t kl_traj_sel(const sasa::TrajArgs &a, hipStream_t st);

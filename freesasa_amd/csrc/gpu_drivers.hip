@@ -253,7 +253,8 @@ int sweep_cache_impl(const char *cache_path, int alg, double probe, int resoluti
  * frames that goes through the engine as one batch.  A few host lanes PER DEVICE take shards from a shared counter; a
  * lane owns a pooled context (stream, workspace, page-locked staging) of its device and does, for its shard,
  *     read (memory or frame file) -> host-to-device -> [fp32 frames widened to fp64 on the device: an INPUT format,
- *     the arithmetic stays fp64] -> cell sort + tile kernels -> device-to-host -> write (memory or files)
+ *     the arithmetic stays fp64; the planar fp32 records of a DCD file made into compact fp64 frames by one kernel]
+ *     -> cell sort + tile kernels -> device-to-host -> write (memory or files)
  * while the other lanes are in another stage.  The radii live once per device context (shared by every frame of
  * a batch).  With a done-list file every finished shard is recorded after its results are on disk; a later call
  * with the same parameters skips the recorded shards: an interrupted run resumes — on any list of devices.
@@ -280,8 +281,10 @@ struct TrajOut {
 struct TrajIO {
     const double *mem_in = nullptr; /* frames in host memory (fp64) ... */
     Fd in;                          /* ... or in a file of raw frames */
-    long long in_header = 0;
+    long long in_header = 0;        /* (a DCD file: the byte of frame 0) */
     int in_f32 = 0;
+    bool in_dcd = false;            /* the file is a DCD trajectory: its frames go up as they lie in the file ... */
+    freesasa_gpu_dcd_info dcd = {}; /* ... and this says where their planes are (dcd.c) */
     /* per frame: total [1], per-atom areas [n]; runs with a topology: class sums [3], residue areas [6 R], selection areas [S];
        with chain groups: every atom's area in its isolated group [n], and isolated, complex, buried per group [3 G] */
     TrajOut out[N_OUT] = {{"totals", 0}, {"per-atom", 1}, {"isolated", 32}, {"class-sums", 2}, {"residues", 4}, {"selections", 8}, {"groups", 16}};
@@ -486,6 +489,10 @@ struct TrajRun {
     const bool gather = topo && topo->index;
     const size_t fa = topo ? (size_t)topo->frame_atoms : n, esz = io.in_f32 ? 12 : 24;
     const size_t widen_bytes = io.in_f32 && !gather ? 12 * n * FB : 0; /* (fp32 frames without an index: kl_widen_f32's input) */
+    /* bytes from one input frame to the next: raw frames, or a DCD file's stride (kl_traj_gather_dcd then does the gather's
+       and the widening's work, with or without an index) */
+    const bool dcd = io.in_dcd;
+    const size_t stride = dcd ? (size_t)io.dcd.frame_bytes : esz * fa;
     /* the caller's arrays are page-locked: no staging */
     const bool in_pinned = io.mem_in && host_pinned(io.mem_in);
     const bool direct_out = io.out[OUT_TOTALS].mem && host_pinned(io.out[OUT_TOTALS].mem) && (!io.out[OUT_SASA].mem || host_pinned(io.out[OUT_SASA].mem)) &&
@@ -554,7 +561,7 @@ int shard_size(TrajRun &T, TrajLane &L)
     if (ensure(c, c->h_xyz, 24 * nc * FB) || ensure(c, c->h_radii, T.groups ? 8 * nc * FB : 8 * n) || ensure(c, c->h_sasa, 8 * nc * FB) ||
         ensure(c, c->h_totals, 8 * (1 + T.G) * FB) ||
         (T.widen_bytes + narrow_bytes && ensure(c, c->h_counts, T.widen_bytes + narrow_bytes)) ||
-        (T.gather && ensure(c, c->g_xyz, T.esz * T.fa * FB)) || (T.xw && ensure(c, c->h_gtot, 8 * T.xw * FB)) ||
+        ((T.gather || T.dcd) && ensure(c, c->g_xyz, T.stride * FB)) || (T.xw && ensure(c, c->h_gtot, 8 * T.xw * FB)) ||
         (T.groups && (ensure(c, c->g_gath, 8 * nc * FB) || ensure(c, c->g_tot2, 8 * (1 + T.G) * FB))) || (iso && ensure(c, c->h_iso, 8 * n * FB)))
         return -1;
     if (!T.groups && !L.radii_up && hipMemcpyAsync(c->h_radii.p, T.s.radii, 8 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "radii upload failed");
@@ -563,29 +570,62 @@ int shard_size(TrajRun &T, TrajLane &L)
     return 0;
 }
 
-/* the shard's frames in page-locked memory: the caller's own, or the lane's staging filled from memory or from the file */
+/* every record marker of the DCD frames [0, nf) at `bytes`: 6 per frame, 2 more with a cell record, 2 more with a 4th dimension.
+   Returns the first frame with a wrong one, or -1. */
+long long dcd_damaged_frame(const freesasa_gpu_dcd_info &d, const char *bytes, long long nf)
+{
+    auto word = [&](uint32_t v) { return d.big_endian ? __builtin_bswap32(v) : v; };
+    const uint32_t cell = word(48), plane = word(4u * (uint32_t)d.n_atoms);
+    for (long long f = 0; f < nf; ++f) {
+        const char *p = bytes + f * d.frame_bytes;
+        uint32_t w[2];
+        if (d.has_cell) {
+            memcpy(&w[0], p, 4); memcpy(&w[1], p + 52, 4);
+            if (w[0] != cell || w[1] != cell) return f;
+            p += 56;
+        }
+        for (int k = 0; k < 3 + d.has_4d; ++k, p += d.plane_bytes) {
+            memcpy(&w[0], p, 4); memcpy(&w[1], p + d.plane_bytes - 4, 4);
+            if (w[0] != plane || w[1] != plane) return f;
+        }
+    }
+    return -1;
+}
+
+/* the shard's frames in page-locked memory: the caller's own, or the lane's staging filled from memory or from the file
+   (a DCD file: the bytes as they lie there, every record marker checked) */
 int shard_read(TrajRun &T, freesasa_gpu_ctx *c, TrajShard &h)
 {
     h.src = T.io.mem_in ? T.io.mem_in + 3 * T.fa * (size_t)h.f0 : nullptr;
     if (h.src && T.in_pinned) return 0;
     if (ensure_pinned(c, &c->stage_in, &c->stage_in_cap, h.in_bytes)) return -1;
     if (h.src) memcpy(c->stage_in, h.src, h.in_bytes);
-    else if (!pread_all(T.io.in.fd, c->stage_in, h.in_bytes, T.io.in_header + (long long)T.esz * (long long)T.fa * h.f0))
+    else if (!pread_all(T.io.in.fd, c->stage_in, h.in_bytes, T.io.in_header + (long long)T.stride * h.f0))
         return ctx_fail(c, "could not read frames %lld..%lld of the frame file", h.f0, h.f0 + h.nf - 1);
+    if (T.dcd) {
+        const long long bad = dcd_damaged_frame(T.io.dcd, (const char *)c->stage_in, h.nf);
+        if (bad >= 0) return ctx_fail(c, "frame %lld of the DCD file is damaged: a record marker is not what the header implies", h.f0 + bad);
+    }
     h.src = c->stage_in;
     return 0;
 }
 
-/* ... to the device, into the compact fp64 frames the engine reads (c->h_xyz): as they are, widened, or gathered */
+/* ... to the device, into the compact fp64 frames the engine reads (c->h_xyz): as they are, widened, or gathered; a DCD file's
+   bytes as they are, de-planarized (and gathered, widened, byte-swapped) by one kernel */
 int shard_upload(TrajRun &T, TrajLane &L, const TrajShard &h)
 {
     freesasa_gpu_ctx *c = L.c;
     const bool f32 = T.io.in_f32 != 0;
-    void *d_in = T.gather ? c->g_xyz.p : (f32 ? c->h_counts.p : c->h_xyz.p);
+    void *d_in = T.gather || T.dcd ? c->g_xyz.p : (f32 ? c->h_counts.p : c->h_xyz.p);
     if (hipMemcpyAsync(d_in, h.src, h.in_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "host-to-device copy failed");
     L.ta.n_frames = h.nf;
+    if (T.dcd) {
+        const freesasa_gpu_dcd_info &d = T.io.dcd;
+        const sasa::TrajDcdArgs da = {(int)T.n, h.nf, T.gather ? L.ta.index : nullptr, d.frame_bytes, d.x_off, d.plane_bytes};
+        if (kl_traj_gather_dcd(da, d_in, d.big_endian != 0, (double *)c->h_xyz.p, c->stream) != hipSuccess) return ctx_fail(c, "DCD gather launch failed");
+    }
     /* full frames up as they were read: one kernel drops the solvent and widens fp32 */
-    if (T.gather && kl_traj_gather(L.ta, d_in, f32, (double *)c->h_xyz.p, c->stream) != hipSuccess) return ctx_fail(c, "gather launch failed");
+    if (T.gather && !T.dcd && kl_traj_gather(L.ta, d_in, f32, (double *)c->h_xyz.p, c->stream) != hipSuccess) return ctx_fail(c, "gather launch failed");
     if (!T.gather && f32 && kl_widen_f32((const float *)d_in, (double *)c->h_xyz.p, (long long)(3 * h.na), c->stream) != hipSuccess) return ctx_fail(c, "widening launch failed");
     if (!T.groups) return 0;
     /* chain groups: behind the compact frames, whoever made them, every group's atoms of every frame; the radii of the
@@ -728,7 +768,7 @@ void traj_lane(TrajRun &T, int id) noexcept
         if (s.max_new > 0 && T.fresh.fetch_add(1) >= s.max_new) { T.stopped = 1; break; }
         h.f0 = h.k * s.frames_per_batch;
         h.nf = (int)(s.n_frames - h.f0 < s.frames_per_batch ? s.n_frames - h.f0 : s.frames_per_batch);
-        h.na = T.n * (size_t)h.nf; h.in_bytes = T.esz * T.fa * (size_t)h.nf;
+        h.na = T.n * (size_t)h.nf; h.in_bytes = T.stride * (size_t)h.nf;
         if (shard_run(T, L, h)) {
             (void)hipStreamSynchronize(L.c->stream); /* nothing of the shard may still run when the lane lets go */
             T.fe.set(L.c->err[0] ? L.c->err : "trajectory shard failed");
@@ -839,12 +879,13 @@ extern "C" int freesasa_gpu_trajectory_topology(const double *xyz_frames, int n_
    time and a checksum of the radii - NOT the devices: a run interrupted on eight GPUs may be finished on one, with the same
    files byte for byte.  With a topology, in front of the line's end, what its outputs depend on: digests of the index, of
    residue boundaries + classes + backbone flags, of the selection set's program, and which result files the run writes; with
-   chain groups, behind that, a digest of the group count and the ids. */
+   chain groups, behind that, a digest of the group count and the ids.  A DCD run: bit 2 in the f32= word and the byte of
+   frame 0 as header_bytes=; a raw run's line is what it was. */
 static int traj_done_head(char *head, size_t cap, const TrajSpec &s, const TrajIO &io, const struct stat &st)
 {
     int len = snprintf(head, cap, "freesasa_amd trajectory done-list v2 n_atoms=%d n_frames=%lld frames_per_batch=%d alg=%d resolution=%d probe=%.17g f32=%d "
                        "header_bytes=%lld frames_size=%lld frames_mtime=%lld.%09ld radii=%016llx\n",
-                       s.n_atoms, s.n_frames, s.frames_per_batch, s.alg, s.resolution, s.probe, io.in_f32 | (io.out_f32() << 1), io.in_header, (long long)st.st_size,
+                       s.n_atoms, s.n_frames, s.frames_per_batch, s.alg, s.resolution, s.probe, io.in_f32 | (io.out_f32() << 1) | (io.in_dcd ? FREESASA_GPU_FRAMES_DCD : 0), io.in_header, (long long)st.st_size,
                        (long long)st.st_mtim.tv_sec, (long)st.st_mtim.tv_nsec, fnv1a(s.radii, 8 * (size_t)s.n_atoms));
     const TrajTopo *tp = s.topo;
     if (tp && len > 0 && len < (int)cap) {
@@ -868,22 +909,36 @@ static int traj_done_head(char *head, size_t cap, const TrajSpec &s, const TrajI
     return len > 0 && len < (int)cap ? 0 : -1;
 }
 
-/* Frame file -> result files, resumable (include/freesasa_gpu.h has the formats).  The caller has put the result files'
+/* Frame file (raw frames, or with FREESASA_GPU_FRAMES_DCD a DCD trajectory) -> result files, resumable (include/freesasa_gpu.h has the formats).  The caller has put the result files'
    paths into io.out[]; s.topo: a run with a topology - frames of its frame_atoms atoms, a longer first line of the done-list. */
 static int trajectory_file_run(const char *frames_path, int frames_f32, long long header_bytes, TrajSpec s, TrajIO &io,
                                const char *done_path, long long *frames_total_out, char *err_out, int err_len)
 {
     if (!frames_path || !s.radii || !io.out[OUT_TOTALS].path) return set_err(err_out, err_len, "null argument");
     if (s.n_atoms <= 0 || header_bytes < 0) return set_err(err_out, err_len, "bad argument");
+    const long long frame_atoms = s.topo ? s.topo->frame_atoms : s.n_atoms;
+    if (frames_f32 & FREESASA_GPU_FRAMES_DCD) {
+        /* a DCD file says for itself where its frames are and what they are: before a device is touched or an output file opened */
+        if (header_bytes != 0) return set_err(err_out, err_len, "header_bytes must be 0 with a DCD file: the byte of its first frame comes from its header");
+        if (frames_f32 & FREESASA_GPU_FRAMES_F32) return set_err(err_out, err_len, "bit 0 of frames_f32 (raw fp32 frames) and bit 2 (a DCD file) exclude each other");
+        if (freesasa_gpu_dcd_info_read(frames_path, &io.dcd, err_out, err_len)) return -1;
+        if (io.dcd.n_atoms != frame_atoms) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "the DCD file holds %d atoms per frame, the run expects %lld", (int)io.dcd.n_atoms, frame_atoms);
+            return set_err(err_out, err_len, msg);
+        }
+        io.in_dcd = true;
+    }
     if (traj_check_args(s, nullptr, err_out, err_len)) return -1;
     return guarded(err_out, err_len, [&]() -> int {
-    const long long frame_atoms = s.topo ? s.topo->frame_atoms : s.n_atoms;
     io.in.fd = open(frames_path, O_RDONLY);
     if (io.in.fd < 0) return set_err(err_out, err_len, "cannot open the frame file");
     struct stat st;
     if (fstat(io.in.fd, &st) != 0) return set_err(err_out, err_len, "cannot stat the frame file");
-    io.in_header = header_bytes; io.in_f32 = (frames_f32 & 1) ? 1 : 0; io.out[OUT_SASA].esz = io.out[OUT_ISO].esz = (frames_f32 & 2) ? 4 : 8;
-    const long long in_file = ((long long)st.st_size - header_bytes) / ((io.in_f32 ? 12LL : 24LL) * frame_atoms);
+    io.in_header = io.in_dcd ? io.dcd.first_frame : header_bytes;
+    io.in_f32 = (frames_f32 & 1) ? 1 : 0; io.out[OUT_SASA].esz = io.out[OUT_ISO].esz = (frames_f32 & 2) ? 4 : 8;
+    const long long in_file = io.in_dcd ? ((long long)st.st_size - io.dcd.first_frame) / io.dcd.frame_bytes
+                                        : ((long long)st.st_size - header_bytes) / ((io.in_f32 ? 12LL : 24LL) * frame_atoms);
     if (s.n_frames <= 0) s.n_frames = in_file;
     if (s.n_frames <= 0 || s.n_frames > in_file) return set_err(err_out, err_len, "the frame file holds fewer frames than asked for");
     if (frames_total_out) *frames_total_out = s.n_frames;

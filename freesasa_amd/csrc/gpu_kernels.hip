@@ -874,6 +874,11 @@ __global__ __launch_bounds__(TRAJ_B) void k_traj_gather(TrajArgs a, const T *in,
 {
     traj_gather(a, in, out, (int64_t)blockIdx.x * TRAJ_B + threadIdx.x);
 }
+template <bool SWAP>
+__global__ __launch_bounds__(TRAJ_B) void k_traj_gather_dcd(TrajDcdArgs a, const uint32_t *in, double *out)
+{
+    traj_gather_dcd<SWAP>(a, in, out, (int64_t)blockIdx.x * TRAJ_B + threadIdx.x);
+}
 __global__ __launch_bounds__(TRAJ_B) void k_traj_residues(TrajArgs a)
 {
     traj_residue(a, (int64_t)blockIdx.x * TRAJ_B + threadIdx.x);
@@ -898,6 +903,13 @@ hipError_t kl_traj_gather(const TrajArgs &a, const void *d_in, bool in_f32, doub
     const unsigned grid = (unsigned)((3 * (int64_t)a.n_frames * a.n + TRAJ_B - 1) / TRAJ_B);
     if (in_f32) hipLaunchKernelGGL(k_traj_gather<float>, dim3(grid), dim3(TRAJ_B), 0, st, a, (const float *)d_in, d_out);
     else hipLaunchKernelGGL(k_traj_gather<double>, dim3(grid), dim3(TRAJ_B), 0, st, a, (const double *)d_in, d_out);
+    return hipGetLastError();
+}
+hipError_t kl_traj_gather_dcd(const TrajDcdArgs &a, const void *d_in, bool big_endian, double *d_out, hipStream_t st)
+{
+    const unsigned grid = (unsigned)((3 * (int64_t)a.n_frames * a.n + TRAJ_B - 1) / TRAJ_B);
+    if (big_endian) hipLaunchKernelGGL(k_traj_gather_dcd<true>, dim3(grid), dim3(TRAJ_B), 0, st, a, (const uint32_t *)d_in, d_out);
+    else hipLaunchKernelGGL(k_traj_gather_dcd<false>, dim3(grid), dim3(TRAJ_B), 0, st, a, (const uint32_t *)d_in, d_out);
     return hipGetLastError();
 }
 hipError_t kl_traj_residues(const TrajArgs &a, hipStream_t st)

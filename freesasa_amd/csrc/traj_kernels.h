@@ -5,6 +5,7 @@
  * selections hold it is the same for every frame and lives once per lane on the device.  Per shard, behind the tile kernels:
  *
  *   traj_gather        out[f][i] = in[f][index[i]], fp32 input widened on the way (before the engine sees the frames)
+ *   traj_gather_dcd    the same from the bytes of DCD frames: planar x[] | y[] | z[] records of fp32, either byte order
  *   traj_residue       the six per-residue areas of every (frame, residue), as residue_areas (sasa_kernels.h)
  *   traj_class_phase0  the three class sums of every frame, as class_phase0 / class_phase1
  *   traj_sel_phase0/1  the selection areas of every frame, as sel_sums_phase0 / sel_sums_phase1 (select_kernels.h)
@@ -57,6 +58,39 @@ SASA_D void traj_gather(const TrajArgs &a, const T *in, double *out, int64_t t)
     const int64_t f = atom / a.n;
     const int i = (int)(atom - f * a.n);
     out[t] = (double)in[3 * (f * a.frame_atoms + a.index[i]) + comp];
+}
+
+/* traj_gather_dcd: the frames of a shard as they lie in a DCD file (dcd.c has the layout) -> the compact fp64 frames.  Each
+   frame is frame_bytes long and holds, from byte x_off on, three planes plane_bytes apart: x[], y[], z[] of ALL its atoms as
+   fp32, with record markers (and, in front or behind, a unit cell and a 4th dimension) between them that no thread reads.
+   One thread per output coordinate, t -> (f, i, comp) as in traj_gather: consecutive lanes write consecutive doubles; lanes
+   t, t + 3, t + 6, ... read consecutive floats of one plane when the index is monotonic.  index NULL: the identity (the
+   plain drivers, or a topology that is the whole frame).  Every offset is a multiple of 4 and in general not of 8 (an odd
+   atom count makes plane_bytes an odd multiple of 4): 4-byte loads only, `in` is the shard's bytes as 32-bit words.  SWAP: the
+   file is big-endian - a build of its own, not a branch per lane.  This is traj_gather AND the widening for DCD input. */
+struct TrajDcdArgs {
+    int n;                /* atoms of a frame as the engine sees it */
+    int n_frames;         /* frames of this shard */
+    const int32_t *index; /* [n] output atom i is the file's atom index[i]; NULL: i */
+    int64_t frame_bytes;  /* the file's stride from frame to frame */
+    int x_off;            /* byte of x[0] within a frame */
+    int plane_bytes;      /* from x[k] to y[k] to z[k] */
+};
+template <bool SWAP>
+SASA_D void traj_gather_dcd(const TrajDcdArgs &a, const uint32_t *in, double *out, int64_t t)
+{
+    const int64_t total = 3 * (int64_t)a.n_frames * a.n;
+    if (t >= total) return;
+    const int64_t atom = t / 3;
+    const int comp = (int)(t - 3 * atom);
+    const int64_t f = atom / a.n;
+    const int i = (int)(atom - f * a.n);
+    const int64_t byte = f * a.frame_bytes + a.x_off + (int64_t)comp * a.plane_bytes + 4 * (int64_t)(a.index ? a.index[i] : i);
+    uint32_t w = in[byte >> 2];
+    if (SWAP) w = (w >> 24) | ((w >> 8) & 0xff00u) | ((w << 8) & 0xff0000u) | (w << 24);
+    float v;
+    memcpy(&v, &w, 4);
+    out[t] = (double)v;
 }
 
 /* traj_residue, one thread per (frame, residue): residue_areas' loop with the areas of frame f and the flags of the topology */

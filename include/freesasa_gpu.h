@@ -419,7 +419,49 @@ int freesasa_gpu_calc_batch(const double *xyz, const double *radii, const int64_
    shards listed there, so an interrupted run (crash, kill, max_new_shards) resumes where it stopped and ends
    with the same files, bit for bit, as an uninterrupted one; a done-list with other parameters is an error.
    n_frames <= 0: all whole frames of the file; *frames_total_out (may be NULL) receives the count.
-   max_new_shards > 0: stop after that many shards.  Returns 0 all done, 1 stopped early, -1 error. */
+   max_new_shards > 0: stop after that many shards.  Returns 0 all done, 1 stopped early, -1 error.
+
+   DCD input (all four file entries: freesasa_gpu_trajectory_file, _file_devices, _file_topology, _file_groups): with bit 2
+   of frames_f32 set (FREESASA_GPU_FRAMES_DCD) frames_path is a DCD trajectory as CHARMM, NAMD, OpenMM and LAMMPS write it -
+   uncompressed fp32, either byte order, with or without a unit-cell record and a 4th-dimension record per frame, every
+   frame at the same byte stride (freesasa_gpu_dcd_info_read below has the layout).  header_bytes must be 0 and bit 0
+   clear; bit 1 (fp32 output) keeps its meaning.  The frame count, the byte of frame 0 and the stride come from the file's
+   header and its SIZE (never from the header's frame count); the file's NATOM must equal n_atoms (with a topology:
+   frame_atoms) - a mismatch, a non-zero header_bytes or bit 0 is -1 with a message before a device is touched or an output
+   file opened.  A shard is still one read and one host-to-device copy of contiguous bytes, exactly as they lie in the
+   file; ONE kernel (traj_kernels.h, traj_gather_dcd) makes of the planar x[] | y[] | z[] records the compact fp64 frames
+   the engine reads - byte-swapped when the file is big-endian, through the atom index when there is a topology - which
+   is the work the gather and the widening do for raw frames.  The unit cell and the 4th dimension are never read.  On the
+   host every record marker of every frame of a shard is checked before the shard goes up: a mismatch ends the run like a
+   failed read ("frame K of the DCD file is damaged"; the shard is not listed).  The done-list's f32= word carries bit 2
+   and its header_bytes= the byte of frame 0: a raw run's list is refused by a DCD run and the other way round; a raw run's
+   line is what it was.  SASA is computed WITHOUT periodic images: a solute that the writer wrapped across the box must be
+   made whole beforehand.  Not offered: DCD files with fixed atoms or 64-bit record markers, other container formats (XTC,
+   TRR, NetCDF), any use of the unit cell, a memory form. */
+#define FREESASA_GPU_FRAMES_F32 1     /* frames_f32 bit 0: raw fp32 frames (input format) */
+#define FREESASA_GPU_FRAMES_OUT_F32 2 /* bit 1: per-atom (and isolated) areas written as fp32 (output format) */
+#define FREESASA_GPU_FRAMES_DCD 4     /* bit 2: frames_path is a DCD trajectory */
+
+/* The header of a DCD file.  Every integer of the file is an int32 in the file's byte order; records lie between two equal
+   byte counts:  [84 | "CORD" | 20 control words | 84]  [m | NTITLE | 80 NTITLE bytes | m]  [4 | NATOM | 4], then per frame
+   [48 | 6 doubles | 48] when there is a unit cell, [4N | N floats | 4N] for x, for y and for z, and once more when there is a
+   4th dimension.  Control words: 0 the frame count as the writer claims it, 8 fixed atoms, 10 / 11 non-zero: a unit-cell /
+   4th-dimension record per frame, 19 the CHARMM version (0: X-PLOR, which has neither record - words 10 and 11 are ignored).
+   Returns 0, or -1 with a message in err that says which check failed: the first word is neither 84 nor 84 byte-swapped,
+   "CORD" is missing, 64-bit record markers, fixed atoms, NATOM <= 0, a header marker that does not match, a file shorter
+   than the header, a file that holds no whole frame.  A tail that is not a whole frame is ignored.  Allocates nothing. */
+typedef struct freesasa_gpu_dcd_info {
+    int32_t n_atoms;          /* NATOM */
+    int64_t n_frames;         /* whole frames by FILE SIZE */
+    int64_t n_frames_header;  /* NSET as the header claims (often 0 or stale: reported, never trusted) */
+    int64_t first_frame;      /* byte of frame 0 */
+    int64_t frame_bytes;      /* constant stride */
+    int32_t x_off;            /* byte of x[0] within a frame (4, or 60 with a cell record) */
+    int32_t plane_bytes;      /* 4 * n_atoms + 8: x -> y -> z */
+    int32_t big_endian, has_cell, has_4d, charmm_version;
+} freesasa_gpu_dcd_info;
+int freesasa_gpu_dcd_info_read(const char *path, freesasa_gpu_dcd_info *out, char *err, int err_len); /* 0 / -1 */
+
 int freesasa_gpu_trajectory(const double *xyz_frames, const double *radii, int n_atoms, int n_frames,
                             int alg, double probe_radius, int resolution, int frames_per_batch,
                             double *totals_out, double *sasa_out, int device,
@@ -461,7 +503,7 @@ int freesasa_gpu_trajectory(const double *xyz_frames, const double *radii, int n
    Argument errors - NULL batch, structure out of range, a structure that failed to load or has no atoms, a bad index,
    frame_atoms < n - return -1 with a message before a device is touched or a file opened.
    Returns as the plain drivers: 0 / -1, the file form 1 when max_new_shards stopped it.
-   Not offered: relative areas in files, trajectory container formats.  (Chain groups: freesasa_gpu_trajectory_groups below.) */
+   Not offered: relative areas in files, trajectory container formats other than DCD.  (Chain groups: freesasa_gpu_trajectory_groups below.) */
 int freesasa_gpu_trajectory_topology(const double *xyz_frames, int n_frames, const struct freesasa_ingest_batch *batch, int structure,
                                      int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
                                      int alg, double probe_radius, int resolution, int frames_per_batch,
@@ -503,7 +545,7 @@ int freesasa_gpu_trajectory_file_topology(const char *frames_path, int frames_f3
    Argument errors, -1 with a message before a device is touched or a file opened: an id < -1 or >= n_groups (the message
    names the atom and the id), n_groups out of range, group given without group areas or either output without group.
    Not offered: a buried area per residue, group ids made on the device for a trajectory (make them once with
-   freesasa_gpu_chain_group_ids), trajectory container formats. */
+   freesasa_gpu_chain_group_ids), trajectory container formats other than DCD. */
 int freesasa_gpu_trajectory_groups(const double *xyz_frames, int n_frames, const struct freesasa_ingest_batch *batch, int structure,
                                    int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
                                    const int32_t *group, int n_groups,

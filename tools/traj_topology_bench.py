@@ -12,9 +12,15 @@ system (fp32, page cache warm) whose solute is a 10 000-atom poly-alanine globul
     longway   the same numbers without the driver's groups: per shard-sized run of frames the host reads the full frames,
               strips the solvent, widens to fp64 and calls calc_groups with the ids repeated per frame (per-atom areas come back)
 
+With --dcd the arms are instead
+    raw       `totals` above: the raw fp32 file
+    dcd       the same call on a little-endian DCD file with a unit-cell record that holds the same fp32 values (12 N + 80 bytes
+              per frame against 12 N; de-planarized, gathered and widened by one kernel on the device)
+timed in one process, interleaved; the totals files must be identical.
+
 One JSON line per arm: atom-frames/s counted in SOLUTE atoms and in frame atoms, the median and the spread of --reps runs.
 
-    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE]
+    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd]
 
 For the kernel times: `rocprofv3 --kernel-trace --stats -- python tools/traj_topology_bench.py --reps 1 --arms all`
 (k_traj_gather / k_traj_residues / k_traj_class / k_traj_sel are the topology's kernels, k_traj_group_* the groups')."""
@@ -22,6 +28,7 @@ import argparse
 import json
 import os
 import shutil
+import struct
 import sys
 import tempfile
 import time
@@ -54,17 +61,31 @@ def solute():
     return b, b.xyz.copy()
 
 
-def make_frames(scratch, xyz, n_frames):
-    full, bare = os.path.join(scratch, "solvated.f32"), os.path.join(scratch, "solute.f32")
+def dcd_header(n_atoms, n_frames):
+    """a little-endian CHARMM-style DCD header: a unit cell per frame, no 4th dimension, one title line"""
+    rec = lambda body: struct.pack("<i", len(body)) + body + struct.pack("<i", len(body))
+    icntrl = [0] * 20
+    icntrl[0], icntrl[1], icntrl[2], icntrl[3], icntrl[10], icntrl[19] = n_frames, 1, 1, n_frames, 1, 24
+    return rec(b"CORD" + struct.pack("<20i", *icntrl)) + rec(struct.pack("<i", 1) + b"REMARKS traj_topology_bench".ljust(80)) + rec(struct.pack("<i", n_atoms))
+
+
+def make_frames(scratch, xyz, n_frames, dcd=False):
+    full, bare, as_dcd = os.path.join(scratch, "solvated.f32"), os.path.join(scratch, "solute.f32"), os.path.join(scratch, "solvated.dcd")
     rng = np.random.default_rng(5)
     half = 1.3 * np.abs(xyz).max()
-    with open(full, "wb") as f_full, open(bare, "wb") as f_bare:
+    plane = struct.pack("<i", 4 * N_FRAME)
+    cell = struct.pack("<i", 48) + np.array([2 * half, 0, 2 * half, 0, 0, 2 * half]).astype("<f8").tobytes() + struct.pack("<i", 48)
+    with open(full, "wb") as f_full, open(bare, "wb") as f_bare, open(as_dcd if dcd else os.devnull, "wb") as f_dcd:
+        f_dcd.write(dcd_header(N_FRAME, n_frames))
         for f in range(n_frames):
             s = (xyz + rng.uniform(-0.25, 0.25, xyz.shape)).astype(np.float32)
             w = rng.uniform(-half, half, (N_FRAME - N_SOLUTE, 3)).astype(np.float32)
             s.tofile(f_bare)
-            np.concatenate([s, w]).tofile(f_full)
-    return full, bare
+            frame = np.concatenate([s, w])
+            frame.tofile(f_full)
+            if dcd:
+                f_dcd.write(cell + b"".join(plane + np.ascontiguousarray(frame[:, k]).tobytes() + plane for k in range(3)))
+    return full, bare, as_dcd
 
 
 def long_way(full, b, ids, n_frames, out_path):
@@ -89,11 +110,12 @@ def main():
     ap.add_argument("--arms", default="plain,totals,all,groups,longway")
     ap.add_argument("--scratch", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--dcd", action="store_true", help="time the raw fp32 file against a DCD file of the same frames")
     args = ap.parse_args()
     scratch = args.scratch or tempfile.mkdtemp(prefix="traj_topology_bench_")
     try:
         b, xyz = solute()
-        full, bare = make_frames(scratch, xyz, args.frames)
+        full, bare, as_dcd = make_frames(scratch, xyz, args.frames, args.dcd)
         sel = ingest.Selection(EIGHT)
         index = np.arange(N_SOLUTE, dtype=np.int32)
         ids = (np.arange(N_SOLUTE) >= N_SOLUTE // 2).astype(np.int32)
@@ -107,7 +129,11 @@ def main():
                                                           group_areas_path=p("g3")),
             "longway": lambda: long_way(full, b, ids, args.frames, p("g4")),
         }
-        names = [a for a in args.arms.split(",") if a in arms]
+        if args.dcd:
+            arms = {"raw": arms["totals"],
+                    "dcd": lambda: fa.trajectory_file_topology(as_dcd, b, p("t5"), atom_index=index, dcd=True)}
+            assert fa.dcd_info(as_dcd).n_frames == args.frames and os.path.getsize(as_dcd) - os.path.getsize(full) == 80 * args.frames + 196
+        names = list(arms) if args.dcd else [a for a in args.arms.split(",") if a in arms]
         runs = {a: [] for a in names}
         for a in names:
             arms[a]()                                                    # warm-up: contexts, staging, page cache
@@ -117,7 +143,7 @@ def main():
                 res = arms[a]()
                 runs[a].append(time.perf_counter() - t0)
                 assert res[0] and res[1] == args.frames
-        totals = [np.fromfile(p(k)) for a, k in (("plain", "t0"), ("totals", "t1"), ("all", "t2"), ("groups", "t3")) if a in names]
+        totals = [np.fromfile(p(k)) for a, k in (("plain", "t0"), ("totals", "t1"), ("all", "t2"), ("groups", "t3"), ("raw", "t1"), ("dcd", "t5")) if a in names]
         assert all(np.array_equal(t, totals[0]) for t in totals)
         assert not ("groups" in names and "longway" in names) or np.array_equal(np.fromfile(p("g3")), np.fromfile(p("g4")))
         lines = []
