@@ -7,9 +7,10 @@
  *   gpu_engine.hip     the per-device context (workspace, status words, events), the launch sequence of one batch,
  *                      asynchronous batches, the device-pointer entry points
  *   gpu_ops.hip        device-side aggregates (segments, classes, residues, selections) and the kernel test hooks
- *   gpu_hostbatch.hip  host-pointer batches: the context pool, one device, several devices, the pipelined form
- *   gpu_drivers.hip    cache sweep and trajectory drivers (one device or a list of devices); what the drivers share
- *                      (device lists, the host budget, DoneList)
+ *   gpu_hostbatch.hip  host-pointer batches: the context pool; the chunk path and its entries - one device, several devices,
+ *                      the pipelined form, the cache sweep
+ *   gpu_drivers.hip    trajectory drivers (one device or a list of devices); what the drivers share (device lists, the
+ *                      host budget, DoneList)
  *   gpu_sweep.hip      the file sweep (host or device parser, done-list, per-residue table, selections) and the device parser's entries
  *   gpu_parse.hip      the device-side PDB / mmCIF parser: its kernels and their host driver (gpu_parse.h)
  *   gpu_groups.hip     chain groups: a batch and every group of it cut out as a structure of its own, in one batch; the
@@ -411,5 +412,49 @@ private:
 
 bool host_pinned(const void *p); /* page-locked already (hipHostMalloc / hipHostRegister, e.g. a pinned tensor)? */
 int ensure_pinned(freesasa_gpu_ctx *c, void **p, size_t *cap, size_t bytes); /* grow a context's page-locked staging buffer */
+
+/* ------------------------------------------------------------------ host batches: the chunk path (gpu_hostbatch.hip)
+ * freesasa_gpu_calc_batch, _calc_batch_devices, _calc_batch_pipelined and the cache sweep are ONE path: a BatchCall is what
+ * the entry was called with, a Chunk a run of its structures in the hands of one pooled context, and a chunk goes through
+ * chunk_size -> _fill -> _upload -> _compute -> _download -> _deliver (chunk_run), each 0 or -1 with the context's message.
+ * Declared here: what freesasa_gpu_calc_groups (gpu_groups.hip) shares with them. */
+
+/* the Shrake-Rupley test points of a call (none for Lee-Richards; a resolution <= 0 is run_batch's to refuse) */
+std::vector<double> call_test_points(int alg, int resolution);
+
+struct BatchCall {
+    const double *xyz = nullptr, *radii = nullptr; /* the caller's arrays ... */
+    freesasa_ingest_cache *cache = nullptr;        /* ... or a cache file that holds them */
+    const int64_t *offsets = nullptr;              /* of all its structures */
+    int alg = 0, resolution = 0;
+    double probe = 0;
+    std::vector<double> tp;                        /* call_test_points */
+    /* the outputs that are wanted: per atom, S&R's counts per atom, per structure, three class sums per structure (cache) */
+    double *sasa_out = nullptr;
+    int *counts_out = nullptr;
+    double *totals_out = nullptr, *class_sums_out = nullptr;
+    /* inputs / outputs pass through the context's page-locked stage_in / stage_out (else: copied in place) */
+    bool stage_in = false, stage_out = false;
+    const char *fallback = "GPU batch failed"; /* the entry's error text when the context has none */
+    bool want_counts() const { return counts_out && alg == 1; }
+    size_t cols() const { return class_sums_out ? 4 : 1; } /* doubles per structure in c->h_totals: total | class sums */
+};
+struct Chunk {
+    int s0 = 0, ns = 0;           /* structures [s0, s0 + ns) of the call, */
+    int64_t a0 = 0;               /* their atoms [a0, a0 + n) */
+    size_t n = 0;
+    const int64_t *off = nullptr; /* their offsets [ns + 1], rebased to a0 */
+    const double *xyz = nullptr, *radii = nullptr; /* (chunk_fill) its inputs where the device copies them from */
+    const unsigned char *cls = nullptr;
+    double *sasa = nullptr, *totals = nullptr;     /* (chunk_download) its outputs where the device copies them to */
+    int *counts = nullptr;
+};
+/* the device buffers of a chunk - c->h_xyz, h_radii, h_sasa, h_totals; h_counts for what rides beside the atoms (S&R's counts
+   out, the cache's classes in) - and the staging the call asks for; the inputs enqueued on the context's stream */
+int chunk_size(const BatchCall &b, freesasa_gpu_ctx *c, const Chunk &h);
+int chunk_upload(freesasa_gpu_ctx *c, const Chunk &h);
+/* The one failure epilogue: nothing is left running on the stream (the caller's arrays are not touched after the entry
+   returns); the text is the context's message or the entry's fallback. */
+const char *chunk_failed(const BatchCall &b, freesasa_gpu_ctx *c);
 
 #endif

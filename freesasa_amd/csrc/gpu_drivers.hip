@@ -1,8 +1,8 @@
 /*
  * gpu_drivers.hip — the drivers for BASELINE configs[3] and configs[4] (include/freesasa_gpu.h): the structure sweep
- * over PDB / mmCIF files (gpu_sweep.hip), the same sweep from a binary cache, and the trajectory drivers (both here, with
- * what all three share: engine_internal.h) — each over ONE device or a LIST of devices of the node.  Host code; kernels
- * in gpu_kernels.hip.
+ * over PDB / mmCIF files (gpu_sweep.hip), the same sweep from a binary cache (gpu_hostbatch.hip: chunks of the host-batch
+ * path whose source is the file) and the trajectory drivers (here, with what all three share: engine_internal.h) — each
+ * over ONE device or a LIST of devices of the node.  Host code; kernels in gpu_kernels.hip.
  *
  * What replaces what: the reference reads one file per run of its CLI (src/main.cc:763-779) and spreads ONE structure
  * over <= 16 pthreads (src/sasa_lr.c:219-253).  Here the unit of parallel work is a batch of whole structures (a
@@ -115,137 +115,6 @@ int DoneList::append(long long k, long long a, long long b)
 }
 
 namespace {
-
-struct Cache {
-    freesasa_ingest_cache *c = nullptr;
-    Cache() = default;
-    Cache(const Cache &) = delete;
-    Cache &operator=(const Cache &) = delete;
-    ~Cache() { if (c) freesasa_ingest_cache_close(c); }
-};
-
-/* ------------------------------------------------------------------ structure sweep: from a binary cache */
-
-/* The sweep of a cache file (freesasa_ingest_save): no parsing, no classification — what is left on the host is to get
- * 33 bytes per atom (coordinates, radius, class) from the file into page-locked memory, which one thread does at
- * ~1e8 atoms/s (pread from the page cache + checksum) against 4.5e8 atoms/s of one GPU at protein density.  So every
- * device gets several lanes (threads), each with its own pooled context and page-locked staging: a lane takes the
- * next batch of structures from the shared counter, reads and verifies exactly its run of atoms
- * (freesasa_ingest_cache_read_atoms: piece checksums) into its staging buffer, copies it to the device and computes,
- * while the other lanes are in another stage. */
-int sweep_cache_impl(const char *cache_path, int alg, double probe, int resolution, long long batch_atoms,
-                     double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out, int n_out,
-                     const int *devices, int n_devices, int lanes_per_device, char *err_out, int err_len)
-{
-    if (err_out && err_len > 0) err_out[0] = 0;
-    if (!cache_path || !totals_out) return set_err(err_out, err_len, "null argument");
-    if (alg != 0 && alg != 1) return set_err(err_out, err_len, "unknown algorithm");
-    if (resolution <= 0) return set_err(err_out, err_len, "resolution must be > 0");
-    if (check_devices(devices, n_devices, err_out, err_len)) return -1;
-    return guarded(err_out, err_len, [&]() -> int {
-    Cache cache_h; /* (closed on every way out) */
-    const int orc = freesasa_ingest_cache_open(cache_path, &cache_h.c);
-    if (orc) {
-        char msg[96];
-        snprintf(msg, sizeof msg, "cannot open the cache file (freesasa_ingest code %d)", orc);
-        return set_err(err_out, err_len, msg);
-    }
-    freesasa_ingest_cache *const cache = cache_h.c;
-    const int S = freesasa_ingest_cache_n_structs(cache);
-    const int64_t *offs = freesasa_ingest_cache_offsets(cache);
-    const int32_t *stat = freesasa_ingest_cache_status(cache);
-    if (n_out < S) return set_err(err_out, err_len, "the output arrays are shorter than the cache's structure count");
-    if (batch_atoms <= 0) batch_atoms = 1000000; /* (measured, round 5, 1.2e7 protein atoms on one MI355X with 16 CPUs: 8 lanes x 1e6 atoms 3.5e8 atoms/s, 4 x 2e6 3.1e8, 2 x 2e6 2.6e8; the kernels alone run 4.5e8 at this density) */
-    if (batch_atoms > (1LL << 30)) batch_atoms = 1LL << 30;
-    std::vector<int> cut(1, 0);
-    for (int s = 0; s < S; ++s) {
-        if (offs[s + 1] - offs[s] > (1LL << 30)) return set_err(err_out, err_len, "a structure of the cache is too large for one batch");
-        if (offs[s + 1] - offs[cut.back()] > batch_atoms && s > cut.back()) cut.push_back(s); /* (a batch never exceeds batch_atoms unless one structure does) */
-    }
-    cut.push_back(S);
-    const int n_batches = (int)cut.size() - 1;
-    for (int s = 0; s < S; ++s) {
-        totals_out[s] = 0;
-        if (status_out) status_out[s] = stat[s];
-        if (atoms_out) atoms_out[s] = offs[s + 1] - offs[s];
-        if (class_sums_out) class_sums_out[3 * s] = class_sums_out[3 * s + 1] = class_sums_out[3 * s + 2] = 0;
-    }
-    if (lanes_per_device <= 0) {
-        /* the granted CPUs divided among the devices, 8 at most; two where they allow (one lane reads while the other
-           computes) - but never more lanes in all than twice the CPUs: eight devices on four CPUs get one lane each, not
-           sixteen threads that read and checksum in turns (round-5 advisor) */
-        const int cpus = process_cpus();
-        lanes_per_device = cpus / n_devices;
-        if (lanes_per_device > 8) lanes_per_device = 8;
-        if (lanes_per_device < 2) lanes_per_device = 2 * cpus >= 2 * n_devices ? 2 : 1;
-    }
-    if (lanes_per_device > 8) lanes_per_device = 8;
-    int n_lanes = lanes_per_device * n_devices;
-    if (n_lanes > n_batches) n_lanes = n_batches;
-    std::vector<double> tp;
-    if (alg == 1) { tp.resize(3 * (size_t)resolution); freesasa_gpu_test_points(resolution, tp.data()); }
-    std::atomic<int> next(0);
-    FirstError fe;
-    auto lane = [&](int id) noexcept {
-      try {
-        DeviceNodeScope node(devices[id % n_devices]); /* the lane and its page-locked staging on the device's NUMA node */
-        PoolLease lease(devices[id % n_devices]);
-        freesasa_gpu_ctx *c = lease.c;
-        if (!c) { fe.set("could not create a GPU context"); return; }
-        std::vector<int64_t> off;
-        for (;;) {
-            const int b = next.fetch_add(1);
-            if (b >= n_batches || fe.failed.load()) break;
-            const int s0 = cut[b], ns = cut[b + 1] - cut[b];
-            const int64_t a0 = offs[s0];
-            const size_t n = (size_t)(offs[s0 + ns] - a0);
-            if (n == 0) continue;
-            off.resize((size_t)ns + 1);
-            for (int i = 0; i <= ns; ++i) off[i] = offs[s0 + i] - a0;
-            int rc = -1;
-            do {
-                if (hipSetDevice(c->device) != hipSuccess) { ctx_fail(c, "hipSetDevice failed"); break; }
-                if (ensure(c, c->h_xyz, 24 * n) || ensure(c, c->h_radii, 8 * n) || ensure(c, c->h_sasa, 8 * n) ||
-                    ensure(c, c->h_counts, n) || ensure(c, c->h_totals, 8 * 4 * (size_t)ns))
-                    break;
-                if (ensure_pinned(c, &c->stage_in, &c->stage_in_cap, 33 * n + 64) || ensure_pinned(c, &c->stage_out, &c->stage_out_cap, 8 * 4 * (size_t)ns)) break;
-                double *h_xyz = (double *)c->stage_in, *h_r = h_xyz + 3 * n;
-                uint8_t *h_cls = (uint8_t *)(h_r + n);
-                const int rrc = freesasa_ingest_cache_read_atoms(cache, a0, a0 + (int64_t)n, h_xyz, h_r, class_sums_out ? h_cls : nullptr);
-                if (rrc) { ctx_fail(c, "the cache file failed its checksum or could not be read (freesasa_ingest code %d)", rrc); break; }
-                if (hipMemcpyAsync(c->h_xyz.p, h_xyz, 24 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-                    hipMemcpyAsync(c->h_radii.p, h_r, 8 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-                    (class_sums_out && hipMemcpyAsync(c->h_counts.p, h_cls, n, hipMemcpyHostToDevice, c->stream) != hipSuccess)) {
-                    ctx_fail(c, "host-to-device copy failed");
-                    break;
-                }
-                double *d_tot = (double *)c->h_totals.p, *d_cls = d_tot + ns;
-                if (run_batch(c, alg == 0, (double *)c->h_xyz.p, (double *)c->h_radii.p, off.data(), ns, probe, resolution,
-                              alg == 1 ? tp.data() : nullptr, (double *)c->h_sasa.p, nullptr, d_tot))
-                    break;
-                if (class_sums_out && freesasa_gpu_class_sums_dev(c, (double *)c->h_sasa.p, (const unsigned char *)c->h_counts.p, off.data(), ns, d_cls)) break;
-                double *h_out = (double *)c->stage_out;
-                if (hipMemcpyAsync(h_out, d_tot, 8 * (size_t)(class_sums_out ? 4 * ns : ns), hipMemcpyDeviceToHost, c->stream) != hipSuccess) { ctx_fail(c, "device-to-host copy failed"); break; }
-                if (hipStreamSynchronize(c->stream) != hipSuccess) { ctx_fail(c, "stream synchronize failed"); break; }
-                memcpy(totals_out + s0, h_out, 8 * (size_t)ns);
-                if (class_sums_out) memcpy(class_sums_out + 3 * (size_t)s0, h_out + ns, 8 * 3 * (size_t)ns);
-                rc = 0;
-            } while (0);
-            if (rc) {
-                (void)hipStreamSynchronize(c->stream);
-                fe.set(c->err[0] ? c->err : "GPU cache sweep failed");
-                break;
-            }
-        }
-      } catch (...) {
-        fe.set_exception();
-      }
-    };
-    run_lanes(n_lanes, fe, lane);
-    if (fe.failed.load()) return set_err(err_out, err_len, fe.text);
-    return 0;
-    });
-}
 
 /* ------------------------------------------------------------------ trajectory driver */
 
@@ -501,7 +370,7 @@ struct TrajRun {
     /* A shard's sums lie one behind the other in ONE block, cut to its nf frames: classes | residues | selection areas |
        groups | selected atoms.  Output k's begin at x0[k] * nf doubles (k = N_OUT: the atom counts); xw doubles per frame hold it all. */
     size_t x0[N_OUT + 1] = {0, 0, 0}, xw;
-    std::vector<double> tp;    /* S&R test points */
+    const std::vector<double> tp = call_test_points(s.alg, s.resolution);
     /* a full shard as a batch: k n; with chain groups behind them FB n + f n_iso + gfirst[g] - and the same for the run's short
        last shard, whose isolated structures begin earlier (without groups a short shard is a prefix of the full one) */
     std::vector<int64_t> offs, offs_last;
@@ -521,7 +390,6 @@ struct TrajRun {
     }
     TrajRun(const TrajSpec &s_, TrajIO &io_) : s(s_), io(io_)
     {
-        if (s.alg == 1) { tp.resize(3 * (size_t)s.resolution); freesasa_gpu_test_points(s.resolution, tp.data()); }
         batch_offsets(FB, offs);
         if (groups && (size_t)(s.n_frames % s.frames_per_batch)) batch_offsets((size_t)(s.n_frames % s.frames_per_batch), offs_last);
         const size_t per[N_OUT] = {1, n, groups ? n : 0, topo ? (size_t)3 : 0, topo ? 6 * (size_t)topo->n_res : 0, S, 3 * G};
@@ -803,16 +671,6 @@ int traj_run(TrajIO &io, const TrajSpec &s, char *err_out, int err_len)
 }
 
 } /* namespace */
-
-/* ------------------------------------------------------------------ entry points */
-
-extern "C" int freesasa_gpu_sweep_cache_devices(const char *cache_path, int alg, double probe, int resolution, long long batch_atoms,
-                                                double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out, int n_out,
-                                                const int *devices, int n_devices, int lanes_per_device, char *err_out, int err_len)
-{
-    return sweep_cache_impl(cache_path, alg, probe, resolution, batch_atoms, totals_out, class_sums_out, atoms_out, status_out, n_out,
-                            devices, n_devices, lanes_per_device, err_out, err_len);
-}
 
 /* ------------------------------------------------------------------ entry points: trajectories */
 

@@ -13,7 +13,9 @@
  *                           areas, k_grp_totals
  *
  * groups_resident is that pipeline for callers whose arrays are on the context's stream (the file sweep, gpu_sweep.hip);
- * below it, the group ids themselves made on the device from residues and chain labels (k_gid_struct).
+ * freesasa_gpu_calc_groups brings host arrays to it with the host-batch path's sizing, upload and failure epilogue
+ * (chunk_size, chunk_upload, chunk_failed: gpu_hostbatch.hip) and its own extras; below it, the group ids themselves made
+ * on the device from residues and chain labels (k_gid_struct).
  */
 #include <hip/hip_runtime.h>
 
@@ -115,11 +117,7 @@ int groups_resident(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const dou
 
     /* 3. one batch over the complex and its groups */
     std::vector<double> tp;
-    if (alg == 1 && !unit_points) {
-        tp.resize(3 * (size_t)resolution);
-        freesasa_gpu_test_points(resolution, tp.data());
-        unit_points = tp.data();
-    }
+    if (alg == 1 && !unit_points) { tp = call_test_points(alg, resolution); unit_points = tp.data(); }
     if (run_batch(c, alg == 0, (const double *)c->g_xyz.p, (const double *)c->g_radii.p, comb.data(), (int)NS, probe, resolution,
                   alg == 1 ? unit_points : nullptr, (double *)c->g_sasa.p, nullptr, (double *)c->g_tot.p))
         return -1;
@@ -190,43 +188,32 @@ extern "C" int freesasa_gpu_calc_groups(const double *xyz, const double *radii, 
     PoolLease lease(device);
     freesasa_gpu_ctx *c = lease.c;
     if (!c) return set_err(err_out, err_len, "could not create a GPU context");
-    int ret = -1;
-    do {
-        const size_t n = (size_t)offsets[n_structs];
-        int64_t G = 0; /* (bad counts are refused by freesasa_gpu_groups_dev, with its message: staged for none here) */
-        for (int s = 0; s < n_structs; ++s) G += n_groups[s] > 0 && n_groups[s] <= GRP_MAX_PER_STRUCT ? n_groups[s] : 0;
-        if (hipSetDevice(c->device) != hipSuccess) { ctx_fail(c, "hipSetDevice failed"); break; }
-        if (ensure(c, c->h_xyz, 24 * n) || ensure(c, c->h_radii, 8 * n) || ensure(c, c->h_group, 4 * n) ||
-            ensure(c, c->h_sasa, 8 * n) || ensure(c, c->h_iso, 8 * n) || ensure(c, c->h_totals, 8 * (size_t)n_structs) ||
-            ensure(c, c->h_gtot, 24 * (size_t)G + 8))
-            break;
-        if (hipMemcpyAsync(c->h_xyz.p, xyz, 24 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-            hipMemcpyAsync(c->h_radii.p, radii, 8 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-            hipMemcpyAsync(c->h_group.p, group, 4 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
-            ctx_fail(c, "host-to-device copy failed");
-            break;
-        }
+    const size_t n = (size_t)offsets[n_structs];
+    int64_t G = 0; /* (bad counts are refused by freesasa_gpu_groups_dev, with its message: staged for none here) */
+    for (int s = 0; s < n_structs; ++s) G += n_groups[s] > 0 && n_groups[s] <= GRP_MAX_PER_STRUCT ? n_groups[s] : 0;
+    /* the batch as one chunk of the host-batch path, in place: its sizing, upload and failure epilogue; the groups' extras here */
+    const BatchCall b; /* (nothing staged, no counts, the fallback text of the batches) */
+    Chunk h;
+    h.ns = n_structs; h.n = n; h.off = offsets; h.xyz = xyz; h.radii = radii;
+    const int rc = [&]() -> int {
+        if (chunk_size(b, c, h) || ensure(c, c->h_group, 4 * n) || ensure(c, c->h_iso, 8 * n) || ensure(c, c->h_gtot, 24 * (size_t)G + 8)) return -1;
+        if (chunk_upload(c, h)) return -1;
+        if (hipMemcpyAsync(c->h_group.p, group, 4 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "host-to-device copy failed");
         if (freesasa_gpu_groups_dev(c, alg, (const double *)c->h_xyz.p, (const double *)c->h_radii.p, offsets, n_structs,
                                     (const int32_t *)c->h_group.p, n_groups, probe_radius, resolution, (double *)c->h_sasa.p,
                                     (double *)c->h_iso.p, totals_out ? (double *)c->h_totals.p : nullptr,
                                     group_totals_out ? (double *)c->h_gtot.p : nullptr))
-            break;
+            return -1;
         if (hipMemcpyAsync(sasa_out, c->h_sasa.p, 8 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             hipMemcpyAsync(iso_out, c->h_iso.p, 8 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             (totals_out && hipMemcpyAsync(totals_out, c->h_totals.p, 8 * (size_t)n_structs, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
             (group_totals_out && G > 0 &&
-             hipMemcpyAsync(group_totals_out, c->h_gtot.p, 24 * (size_t)G, hipMemcpyDeviceToHost, c->stream) != hipSuccess)) {
-            ctx_fail(c, "device-to-host copy failed");
-            break;
-        }
-        if (hipStreamSynchronize(c->stream) != hipSuccess) { ctx_fail(c, "stream synchronize failed"); break; }
-        ret = 0;
-    } while (0);
-    if (ret) {
-        (void)hipStreamSynchronize(c->stream);
-        set_err(err_out, err_len, c->err[0] ? c->err : "GPU batch failed");
-    }
-    return ret;
+             hipMemcpyAsync(group_totals_out, c->h_gtot.p, 24 * (size_t)G, hipMemcpyDeviceToHost, c->stream) != hipSuccess))
+            return ctx_fail(c, "device-to-host copy failed");
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return ctx_fail(c, "stream synchronize failed");
+        return 0;
+    }();
+    return rc ? set_err(err_out, err_len, chunk_failed(b, c)) : 0;
     });
 }
 

@@ -1,7 +1,8 @@
 /*
  * gpu_hostbatch.hip — host-pointer batches (include/freesasa_gpu.h): the pool of contexts behind the re-entrant
- * entry points, one batch on one device, a batch cut over a list of devices, and the pipelined form whose PCIe copies
- * run under the kernels of other chunks.  Host code; kernels in gpu_kernels.hip.
+ * entry points; the chunk path (BatchCall, Chunk and the chunk_* stages, engine_internal.h) and the entries on top of it:
+ * one batch on one device, a batch cut over a list of devices, the pipelined form whose PCIe copies run under the kernels
+ * of other chunks, and the sweep of a binary cache.  Host code; kernels in gpu_kernels.hip.
  */
 #include <hip/hip_runtime.h>
 
@@ -157,6 +158,167 @@ DeviceNodeScope::~DeviceNodeScope()
     (void)sched_setaffinity(0, sizeof old, &old);
 }
 
+/* ------------------------------------------------------------------ the chunk path (engine_internal.h) */
+
+std::vector<double> call_test_points(int alg, int resolution)
+{
+    std::vector<double> tp;
+    if (alg != 1) return tp;
+    tp.resize(3 * (size_t)(resolution > 0 ? resolution : 1));
+    if (resolution > 0) freesasa_gpu_test_points(resolution, tp.data());
+    return tp;
+}
+
+/* the arguments every entry has, as a call */
+static BatchCall batch_call(const double *xyz, const double *radii, const int64_t *offsets, int alg, double probe, int resolution,
+                            double *sasa_out, int *counts_out, double *totals_out)
+{
+    BatchCall b;
+    b.xyz = xyz; b.radii = radii; b.offsets = offsets;
+    b.alg = alg; b.probe = probe; b.resolution = resolution; b.tp = call_test_points(alg, resolution);
+    b.sasa_out = sasa_out; b.counts_out = counts_out; b.totals_out = totals_out;
+    return b;
+}
+
+/* structures [s0, s0 + ns) of a call as a chunk; `store` (a lane's, reused from chunk to chunk) holds its offsets */
+static Chunk chunk_of(const BatchCall &b, int s0, int ns, std::vector<int64_t> &store)
+{
+    Chunk h;
+    h.s0 = s0; h.ns = ns; h.a0 = b.offsets[s0]; h.n = (size_t)(b.offsets[s0 + ns] - h.a0);
+    store.resize((size_t)ns + 1);
+    for (int i = 0; i <= ns; ++i) store[(size_t)i] = b.offsets[s0 + i] - h.a0;
+    h.off = store.data();
+    return h;
+}
+
+/* a chunk without atoms never sees a device: its structures' totals are 0 */
+static bool chunk_empty(const BatchCall &b, const Chunk &h)
+{
+    if (h.n) return false;
+    for (int i = 0; i < h.ns && b.totals_out; ++i) b.totals_out[h.s0 + i] = 0;
+    return true;
+}
+
+int chunk_size(const BatchCall &b, freesasa_gpu_ctx *c, const Chunk &h)
+{
+    const size_t n = h.n, aux = b.want_counts() ? 4 : b.class_sums_out ? 1 : 0, tot_bytes = 8 * b.cols() * (size_t)h.ns;
+    if (hipSetDevice(c->device) != hipSuccess) return ctx_fail(c, "hipSetDevice failed");
+    if (ensure(c, c->h_xyz, 24 * n) || ensure(c, c->h_radii, 8 * n) || ensure(c, c->h_sasa, 8 * n) ||
+        (aux && ensure(c, c->h_counts, aux * n)) || ensure(c, c->h_totals, tot_bytes))
+        return -1;
+    /* coordinates | radii [| the cache's classes] in, per-atom areas | counts | totals and class sums out */
+    if (b.stage_in && ensure_pinned(c, &c->stage_in, &c->stage_in_cap, b.cache ? 33 * n + 64 : 32 * n)) return -1;
+    if (b.stage_out && ensure_pinned(c, &c->stage_out, &c->stage_out_cap, (b.sasa_out ? 8 * n : 0) + (b.want_counts() ? 4 * n : 0) + (b.totals_out ? tot_bytes : 0)))
+        return -1;
+    return 0;
+}
+
+/* The chunk's inputs where the device can copy them from - the only stage that knows the source: the caller's arrays in
+   place, the caller's arrays through the context's staging, or the cache file read (and verified: piece checksums) into it. */
+static int chunk_fill(const BatchCall &b, freesasa_gpu_ctx *c, Chunk &h)
+{
+    if (!b.stage_in) { h.xyz = b.xyz + 3 * h.a0; h.radii = b.radii + h.a0; return 0; }
+    double *xyz = (double *)c->stage_in, *radii = xyz + 3 * h.n;
+    unsigned char *cls = b.class_sums_out ? (unsigned char *)(radii + h.n) : nullptr;
+    h.xyz = xyz; h.radii = radii; h.cls = cls;
+    if (b.cache) {
+        const int rc = freesasa_ingest_cache_read_atoms(b.cache, h.a0, h.a0 + (int64_t)h.n, xyz, radii, cls);
+        return rc ? ctx_fail(c, "the cache file failed its checksum or could not be read (freesasa_ingest code %d)", rc) : 0;
+    }
+    memcpy(xyz, b.xyz + 3 * h.a0, 24 * h.n);
+    memcpy(radii, b.radii + h.a0, 8 * h.n);
+    return 0;
+}
+
+int chunk_upload(freesasa_gpu_ctx *c, const Chunk &h)
+{
+    if (hipMemcpyAsync(c->h_xyz.p, h.xyz, 24 * h.n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(c->h_radii.p, h.radii, 8 * h.n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        (h.cls && hipMemcpyAsync(c->h_counts.p, h.cls, h.n, hipMemcpyHostToDevice, c->stream) != hipSuccess))
+        return ctx_fail(c, "host-to-device copy failed");
+    return 0;
+}
+
+const char *chunk_failed(const BatchCall &b, freesasa_gpu_ctx *c)
+{
+    (void)hipStreamSynchronize(c->stream);
+    return c->err[0] ? c->err : b.fallback;
+}
+
+/* the engine on the chunk as a batch of its own; behind it the class sums of a cache sweep, beside the totals in c->h_totals */
+static int chunk_compute(const BatchCall &b, freesasa_gpu_ctx *c, const Chunk &h)
+{
+    if (b.alg != 0 && b.alg != 1) return ctx_fail(c, "unknown algorithm %d", b.alg); /* (freesasa_gpu_calc_batch's check: the other entries refuse it before they begin) */
+    double *d_sasa = (double *)c->h_sasa.p, *d_tot = b.totals_out ? (double *)c->h_totals.p : nullptr;
+    if (run_batch(c, b.alg == 0, (double *)c->h_xyz.p, (double *)c->h_radii.p, h.off, h.ns, b.probe, b.resolution, b.alg == 1 ? b.tp.data() : nullptr,
+                  d_sasa, b.want_counts() ? (int *)c->h_counts.p : nullptr, d_tot))
+        return -1;
+    if (b.class_sums_out && freesasa_gpu_class_sums_dev(c, d_sasa, (const unsigned char *)c->h_counts.p, h.off, h.ns, d_tot + h.ns)) return -1;
+    return 0;
+}
+
+/* The results to the host - into the caller's arrays in place, or one behind the other into the context's staging - and
+   the chunk's one synchronisation. */
+static int chunk_download(const BatchCall &b, freesasa_gpu_ctx *c, Chunk &h)
+{
+    const size_t n = h.n, tot_bytes = 8 * b.cols() * (size_t)h.ns;
+    h.sasa = b.sasa_out ? b.sasa_out + h.a0 : nullptr;
+    h.counts = b.want_counts() ? b.counts_out + h.a0 : nullptr;
+    h.totals = b.totals_out ? b.totals_out + h.s0 : nullptr;
+    if (b.stage_out) {
+        char *p = (char *)c->stage_out;
+        if (h.sasa) { h.sasa = (double *)p; p += 8 * n; }
+        if (h.counts) { h.counts = (int *)p; p += 4 * n; }
+        if (h.totals) h.totals = (double *)p;
+    }
+    if ((h.sasa && hipMemcpyAsync(h.sasa, c->h_sasa.p, 8 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+        (h.counts && hipMemcpyAsync(h.counts, c->h_counts.p, 4 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+        (h.totals && hipMemcpyAsync(h.totals, c->h_totals.p, tot_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess))
+        return ctx_fail(c, "device-to-host copy failed");
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return ctx_fail(c, "stream synchronize failed");
+    return 0;
+}
+
+/* ... and from the staging to the caller's arrays */
+static void chunk_deliver(const BatchCall &b, const Chunk &h)
+{
+    if (!b.stage_out) return;
+    if (h.sasa) memcpy(b.sasa_out + h.a0, h.sasa, 8 * h.n);
+    if (h.counts) memcpy(b.counts_out + h.a0, h.counts, 4 * h.n);
+    if (h.totals) memcpy(b.totals_out + h.s0, h.totals, 8 * (size_t)h.ns);
+    if (b.class_sums_out) memcpy(b.class_sums_out + 3 * (size_t)h.s0, h.totals + h.ns, 8 * 3 * (size_t)h.ns);
+}
+
+/* the stages of one chunk on a context; -1: the caller owes chunk_failed */
+static int chunk_run(const BatchCall &b, freesasa_gpu_ctx *c, Chunk &h)
+{
+    if (chunk_size(b, c, h) || chunk_fill(b, c, h) || chunk_upload(c, h) || chunk_compute(b, c, h) || chunk_download(b, c, h)) return -1;
+    chunk_deliver(b, h);
+    return 0;
+}
+
+/* A lane owns a pooled context of its device and takes the chunks [cut[k], cut[k + 1]) from the shared counter until none is
+   left or a lane has failed. */
+static void chunk_lane(const BatchCall &b, const std::vector<int> &cut, std::atomic<int> &next, FirstError &fe, int device) noexcept
+{
+  try {
+    PoolLease lease(device);
+    if (!lease.c) { fe.set("could not create a GPU context"); return; }
+    std::vector<int64_t> off;
+    for (;;) {
+        const int k = next.fetch_add(1);
+        if (k + 1 >= (int)cut.size() || fe.failed.load()) break;
+        Chunk h = chunk_of(b, cut[k], cut[k + 1] - cut[k], off);
+        if (chunk_empty(b, h)) continue;
+        if (chunk_run(b, lease.c, h)) { fe.set(chunk_failed(b, lease.c)); break; }
+    }
+  } catch (...) { /* (the lease has left the stream idle and returned the context) */
+    fe.set_exception();
+  }
+}
+
+/* ------------------------------------------------------------------ one batch, one device: the batch as it is, in place */
+
 extern "C" int freesasa_gpu_calc_batch(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
                                        int alg, double probe, int resolution, double *sasa_out, int *counts_out,
                                        double *totals_out, int device, char *err_out, int err_len)
@@ -167,56 +329,20 @@ extern "C" int freesasa_gpu_calc_batch(const double *xyz, const double *radii, c
         return set_err(err_out, err_len, "no HIP device available: libfreesasa_amd has no CPU path");
     return guarded(err_out, err_len, [&]() -> int {
     PoolLease lease(device); /* (returned to the pool, its stream idle, on every way out - an exception included) */
-    freesasa_gpu_ctx *c = lease.c;
-    if (!c) return set_err(err_out, err_len, "could not create a GPU context");
-    int ret = -1;
-    do {
-        if (n_structs <= 0 || offsets[n_structs] <= 0) { ctx_fail(c, "empty batch"); break; }
-        const size_t n = (size_t)offsets[n_structs];
-        if (hipSetDevice(c->device) != hipSuccess) { ctx_fail(c, "hipSetDevice failed"); break; }
-        if (ensure(c, c->h_xyz, 24 * n) || ensure(c, c->h_radii, 8 * n) || ensure(c, c->h_sasa, 8 * n) ||
-            ensure(c, c->h_counts, 4 * n) || ensure(c, c->h_totals, 8 * (size_t)n_structs))
-            break;
-        if (hipMemcpyAsync(c->h_xyz.p, xyz, 24 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-            hipMemcpyAsync(c->h_radii.p, radii, 8 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
-            ctx_fail(c, "host-to-device copy failed");
-            break;
-        }
-        if (alg == 0) {
-            ret = run_batch(c, true, (double *)c->h_xyz.p, (double *)c->h_radii.p, offsets, n_structs, probe, resolution,
-                            nullptr, (double *)c->h_sasa.p, nullptr, totals_out ? (double *)c->h_totals.p : nullptr);
-        } else if (alg == 1) {
-            std::vector<double> tp(3 * (size_t)(resolution > 0 ? resolution : 1));
-            if (resolution > 0) freesasa_gpu_test_points(resolution, tp.data());
-            ret = run_batch(c, false, (double *)c->h_xyz.p, (double *)c->h_radii.p, offsets, n_structs, probe, resolution,
-                            tp.data(), (double *)c->h_sasa.p, counts_out ? (int *)c->h_counts.p : nullptr,
-                            totals_out ? (double *)c->h_totals.p : nullptr);
-        } else {
-            ctx_fail(c, "unknown algorithm %d", alg);
-        }
-        if (ret) break;
-        ret = -1;
-        if (hipMemcpyAsync(sasa_out, c->h_sasa.p, 8 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { ctx_fail(c, "device-to-host copy failed"); break; }
-        if (counts_out && alg == 1 &&
-            hipMemcpyAsync(counts_out, c->h_counts.p, 4 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { ctx_fail(c, "device-to-host copy failed"); break; }
-        if (totals_out &&
-            hipMemcpyAsync(totals_out, c->h_totals.p, 8 * (size_t)n_structs, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { ctx_fail(c, "device-to-host copy failed"); break; }
-        if (hipStreamSynchronize(c->stream) != hipSuccess) { ctx_fail(c, "stream synchronize failed"); break; }
-        ret = 0;
-    } while (0);
-    if (ret) {
-        (void)hipStreamSynchronize(c->stream); /* the caller's arrays must not be read after we return */
-        set_err(err_out, err_len, c->err[0] ? c->err : "GPU batch failed");
-    }
-    return ret;
+    if (!lease.c) return set_err(err_out, err_len, "could not create a GPU context");
+    if (n_structs <= 0 || offsets[n_structs] <= 0) return set_err(err_out, err_len, "empty batch");
+    const BatchCall b = batch_call(xyz, radii, offsets, alg, probe, resolution, sasa_out, counts_out, totals_out);
+    Chunk h;
+    h.ns = n_structs; h.n = (size_t)offsets[n_structs]; h.off = offsets;
+    return chunk_run(b, lease.c, h) ? set_err(err_out, err_len, chunk_failed(b, lease.c)) : 0;
     });
 }
 
 /* ------------------------------------------------------------------ several GPUs, one process */
 
 /* Independent structures shard with no exchange: the batch is cut into contiguous runs of
- * structures with about equal atom counts, one run per device of the mask, each run handled by its
- * own host thread through freesasa_gpu_calc_batch (its own pooled context, stream and workspace).
+ * structures with about equal atom counts, one run per entry of the device list, each run one chunk on its
+ * own host thread (its own pooled context, stream and workspace).
  * Contiguous runs need no gather: every device reads and writes its slice of the caller's arrays. */
 /* cuts[k] = first structure of shard k (cuts[n_parts] = n_structs): where the running atom count passes
  * k/n_parts of the total; shards may be empty when there are fewer structures than parts */
@@ -244,36 +370,24 @@ extern "C" int freesasa_gpu_calc_batch_devices(const double *xyz, const double *
     for (int k = 0; k < n_devices; ++k)
         if (devices[k] < 0 || devices[k] >= n_dev) return set_err(err_out, err_len, "device index out of range");
     return guarded(err_out, err_len, [&]() -> int {
-    const int nd = n_devices;
-    std::vector<int> cut(nd + 1);
-    freesasa_gpu_shard_cuts(offsets, n_structs, nd, cut.data());
-    std::vector<int> rc(nd, 0);
-    std::vector<std::vector<char>> errs(nd, std::vector<char>(256, 0));
-    auto run = [&](int k) noexcept {
-        try {
-            const int s0 = cut[k], ns = cut[k + 1] - cut[k];
-            if (ns <= 0 || offsets[s0 + ns] == offsets[s0]) return;
-            std::vector<int64_t> off(ns + 1); /* the shard's own CSR offsets start at 0 */
-            for (int i = 0; i <= ns; ++i) off[i] = offsets[s0 + i] - offsets[s0];
-            const int64_t a0 = offsets[s0];
-            rc[k] = freesasa_gpu_calc_batch(xyz + 3 * a0, radii + a0, off.data(), ns, alg, probe, resolution, sasa_out + a0,
-                                            counts_out ? counts_out + a0 : nullptr, totals_out ? totals_out + s0 : nullptr,
-                                            devices[k], errs[k].data(), (int)errs[k].size());
-        } catch (...) { /* (an exception that leaves a thread's function ends the process) */
-            exception_text(errs[k].data(), errs[k].size());
-            rc[k] = -1;
-        }
-    };
-    bool started = true;
-    {
-        ThreadGroup tg; /* joined on every way out */
-        for (int k = 1; k < nd && started; ++k) started = tg.spawn(run, k);
-        if (started) run(0);
-    }
-    if (!started) return set_err(err_out, err_len, "could not start a worker thread");
-    for (int k = 0; k < nd; ++k)
-        if (rc[k]) return set_err(err_out, err_len, errs[k].data()[0] ? errs[k].data() : "a device shard failed");
-    return 0;
+    BatchCall b = batch_call(xyz, radii, offsets, alg, probe, resolution, sasa_out, counts_out, totals_out);
+    b.fallback = "a device shard failed";
+    std::vector<int> cut((size_t)n_devices + 1);
+    freesasa_gpu_shard_cuts(offsets, n_structs, n_devices, cut.data());
+    FirstError fe;
+    run_lanes(n_devices, fe, [&](int k) noexcept { /* shard k on devices[k]; a shard without atoms opens no context */
+      try {
+        std::vector<int64_t> off;
+        Chunk h = chunk_of(b, cut[k], cut[k + 1] - cut[k], off);
+        if (chunk_empty(b, h)) return;
+        PoolLease lease(devices[k]);
+        if (!lease.c) fe.set("could not create a GPU context");
+        else if (chunk_run(b, lease.c, h)) fe.set(chunk_failed(b, lease.c));
+      } catch (...) {
+        fe.set_exception();
+      }
+    });
+    return fe.failed.load() ? set_err(err_out, err_len, fe.text) : 0;
     });
 }
 
@@ -341,98 +455,97 @@ extern "C" int freesasa_gpu_calc_batch_pipelined(const double *xyz, const double
     if (n_lanes > 8) n_lanes = 8;
     if (chunk_atoms <= 0) chunk_atoms = 1250000;
     return guarded(err_out, err_len, [&]() -> int {
+    BatchCall b = batch_call(xyz, radii, offsets, alg, probe, resolution, sasa_out, counts_out, totals_out);
+    b.stage_in = !pin_in; b.stage_out = !pin_out;
     std::vector<int> cut(1, 0);
     for (int s = 0; s < n_structs; ++s)
         if (offsets[s + 1] - offsets[cut.back()] >= chunk_atoms && s + 1 < n_structs) cut.push_back(s + 1);
     cut.push_back(n_structs);
     const int n_chunks = (int)cut.size() - 1;
-    if (n_lanes > n_chunks) n_lanes = n_chunks;
-    std::vector<double> tp;
-    if (alg == 1) { tp.resize(3 * (size_t)(resolution > 0 ? resolution : 1)); if (resolution > 0) freesasa_gpu_test_points(resolution, tp.data()); }
-    std::atomic<int> next(0), failed(0);
-    std::vector<std::vector<char>> errs(n_lanes, std::vector<char>(256, 0));
-    auto lane = [&](int id) noexcept {
-      try {
-        PoolLease lease(device);
-        freesasa_gpu_ctx *c = lease.c;
-        if (!c) { snprintf(errs[id].data(), 256, "could not create a GPU context"); failed = 1; return; }
-        std::vector<int64_t> off;
-        for (;;) {
-            const int k = next.fetch_add(1);
-            if (k >= n_chunks || failed.load()) break;
-            const int s0 = cut[k], ns = cut[k + 1] - cut[k];
-            const int64_t a0 = offsets[s0];
-            const size_t n = (size_t)(offsets[s0 + ns] - a0);
-            if (n == 0) { if (totals_out) for (int i = 0; i < ns; ++i) totals_out[s0 + i] = 0; continue; }
-            off.resize((size_t)ns + 1);
-            for (int i = 0; i <= ns; ++i) off[i] = offsets[s0 + i] - a0;
-            int rc = -1;
-            do {
-                if (hipSetDevice(c->device) != hipSuccess) { ctx_fail(c, "hipSetDevice failed"); break; }
-                if (ensure(c, c->h_xyz, 24 * n) || ensure(c, c->h_radii, 8 * n) || ensure(c, c->h_sasa, 8 * n) ||
-                    ensure(c, c->h_counts, 4 * n) || ensure(c, c->h_totals, 8 * (size_t)ns))
-                    break;
-                const double *src_xyz = xyz + 3 * a0, *src_r = radii + a0;
-                if (!pin_in) {
-                    if (ensure_pinned(c, &c->stage_in, &c->stage_in_cap, 32 * n)) break;
-                    memcpy(c->stage_in, src_xyz, 24 * n);
-                    memcpy((char *)c->stage_in + 24 * n, src_r, 8 * n);
-                    src_xyz = (const double *)c->stage_in;
-                    src_r = (const double *)((char *)c->stage_in + 24 * n);
-                }
-                if (hipMemcpyAsync(c->h_xyz.p, src_xyz, 24 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-                    hipMemcpyAsync(c->h_radii.p, src_r, 8 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
-                    ctx_fail(c, "host-to-device copy failed");
-                    break;
-                }
-                if (run_batch(c, alg == 0, (double *)c->h_xyz.p, (double *)c->h_radii.p, off.data(), ns, probe, resolution,
-                              alg == 1 ? tp.data() : nullptr, (double *)c->h_sasa.p, counts_out && alg == 1 ? (int *)c->h_counts.p : nullptr,
-                              totals_out ? (double *)c->h_totals.p : nullptr))
-                    break;
-                const bool want_counts = counts_out && alg == 1;
-                double *dst_sasa = sasa_out + a0, *dst_tot = totals_out ? totals_out + s0 : nullptr;
-                int *dst_cnt = want_counts ? counts_out + a0 : nullptr;
-                const size_t out_bytes = 8 * n + (want_counts ? 4 * n : 0) + (dst_tot ? 8 * (size_t)ns : 0);
-                if (!pin_out) {
-                    if (ensure_pinned(c, &c->stage_out, &c->stage_out_cap, out_bytes)) break;
-                    dst_sasa = (double *)c->stage_out;
-                    dst_cnt = want_counts ? (int *)((char *)c->stage_out + 8 * n) : nullptr;
-                    dst_tot = totals_out ? (double *)((char *)c->stage_out + 8 * n + (want_counts ? 4 * n : 0)) : nullptr;
-                }
-                bool ok = hipMemcpyAsync(dst_sasa, c->h_sasa.p, 8 * n, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
-                if (ok && want_counts) ok = hipMemcpyAsync(dst_cnt, c->h_counts.p, 4 * n, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
-                if (ok && dst_tot) ok = hipMemcpyAsync(dst_tot, c->h_totals.p, 8 * (size_t)ns, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
-                if (!ok) { ctx_fail(c, "device-to-host copy failed"); break; }
-                if (hipStreamSynchronize(c->stream) != hipSuccess) { ctx_fail(c, "stream synchronize failed"); break; }
-                if (!pin_out) {
-                    memcpy(sasa_out + a0, dst_sasa, 8 * n);
-                    if (want_counts) memcpy(counts_out + a0, dst_cnt, 4 * n);
-                    if (totals_out) memcpy(totals_out + s0, dst_tot, 8 * (size_t)ns);
-                }
-                rc = 0;
-            } while (0);
-            if (rc) {
-                (void)hipStreamSynchronize(c->stream); /* nothing may still read the caller's arrays when we return */
-                snprintf(errs[id].data(), 256, "%s", c->err[0] ? c->err : "GPU batch failed");
-                failed = 1;
-                break;
-            }
-        }
-      } catch (...) { /* (the lease has left the stream idle and returned the context) */
-        exception_text(errs[id].data(), errs[id].size());
-        failed = 1;
-      }
-    };
-    {
-        ThreadGroup tg;
-        for (int k = 1; k < n_lanes; ++k)
-            if (!tg.spawn(lane, k)) { snprintf(errs[0].data(), 256, "could not start a worker thread"); failed = 1; break; }
-        if (!failed.load()) lane(0);
-    }
-    if (failed.load())
-        for (int k = 0; k < n_lanes; ++k)
-            if (errs[k][0]) return set_err(err_out, err_len, errs[k].data());
-    return failed.load() ? set_err(err_out, err_len, "GPU batch failed") : 0;
+    std::atomic<int> next(0);
+    FirstError fe;
+    run_lanes(n_lanes > n_chunks ? n_chunks : n_lanes, fe, [&](int) noexcept { chunk_lane(b, cut, next, fe, device); });
+    return fe.failed.load() ? set_err(err_out, err_len, fe.text) : 0;
     });
 }
 
+/* ------------------------------------------------------------------ structure sweep: from a binary cache */
+
+namespace {
+struct Cache {
+    freesasa_ingest_cache *c = nullptr;
+    Cache() = default;
+    Cache(const Cache &) = delete;
+    Cache &operator=(const Cache &) = delete;
+    ~Cache() { if (c) freesasa_ingest_cache_close(c); }
+};
+} /* namespace */
+
+/* The sweep of a cache file (freesasa_ingest_save): no parsing, no classification — what is left on the host is to get
+ * 33 bytes per atom (coordinates, radius, class) from the file into page-locked memory, which one thread does at
+ * ~1e8 atoms/s (pread from the page cache + checksum) against 4.5e8 atoms/s of one GPU at protein density.  So every
+ * device gets several lanes (threads), each with its own pooled context and page-locked staging: a lane takes the
+ * next batch of structures from the shared counter, reads and verifies exactly its run of atoms
+ * (freesasa_ingest_cache_read_atoms: piece checksums) into its staging buffer, copies it to the device and computes,
+ * while the other lanes are in another stage: the pipelined entry's lanes over chunks whose source is the file. */
+extern "C" int freesasa_gpu_sweep_cache_devices(const char *cache_path, int alg, double probe, int resolution, long long batch_atoms,
+                                                double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out, int n_out,
+                                                const int *devices, int n_devices, int lanes_per_device, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (!cache_path || !totals_out) return set_err(err_out, err_len, "null argument");
+    if (alg != 0 && alg != 1) return set_err(err_out, err_len, "unknown algorithm");
+    if (resolution <= 0) return set_err(err_out, err_len, "resolution must be > 0");
+    if (check_devices(devices, n_devices, err_out, err_len)) return -1;
+    return guarded(err_out, err_len, [&]() -> int {
+    Cache cache_h; /* (closed on every way out) */
+    const int orc = freesasa_ingest_cache_open(cache_path, &cache_h.c);
+    if (orc) {
+        char msg[96];
+        snprintf(msg, sizeof msg, "cannot open the cache file (freesasa_ingest code %d)", orc);
+        return set_err(err_out, err_len, msg);
+    }
+    const int S = freesasa_ingest_cache_n_structs(cache_h.c);
+    const int64_t *offs = freesasa_ingest_cache_offsets(cache_h.c);
+    const int32_t *stat = freesasa_ingest_cache_status(cache_h.c);
+    if (n_out < S) return set_err(err_out, err_len, "the output arrays are shorter than the cache's structure count");
+    if (batch_atoms <= 0) batch_atoms = 1000000; /* (measured, round 5, 1.2e7 protein atoms on one MI355X with 16 CPUs: 8 lanes x 1e6 atoms 3.5e8 atoms/s, 4 x 2e6 3.1e8, 2 x 2e6 2.6e8; the kernels alone run 4.5e8 at this density) */
+    if (batch_atoms > (1LL << 30)) batch_atoms = 1LL << 30;
+    std::vector<int> cut(1, 0);
+    for (int s = 0; s < S; ++s) {
+        if (offs[s + 1] - offs[s] > (1LL << 30)) return set_err(err_out, err_len, "a structure of the cache is too large for one batch");
+        if (offs[s + 1] - offs[cut.back()] > batch_atoms && s > cut.back()) cut.push_back(s); /* (a batch never exceeds batch_atoms unless one structure does) */
+    }
+    cut.push_back(S);
+    const int n_batches = (int)cut.size() - 1;
+    for (int s = 0; s < S; ++s) {
+        totals_out[s] = 0;
+        if (status_out) status_out[s] = stat[s];
+        if (atoms_out) atoms_out[s] = offs[s + 1] - offs[s];
+        if (class_sums_out) class_sums_out[3 * s] = class_sums_out[3 * s + 1] = class_sums_out[3 * s + 2] = 0;
+    }
+    if (lanes_per_device <= 0) {
+        /* the granted CPUs divided among the devices, 8 at most; two where they allow (one lane reads while the other
+           computes) - but never more lanes in all than twice the CPUs: eight devices on four CPUs get one lane each, not
+           sixteen threads that read and checksum in turns (round-5 advisor) */
+        const int cpus = process_cpus();
+        lanes_per_device = cpus / n_devices;
+        if (lanes_per_device > 8) lanes_per_device = 8;
+        if (lanes_per_device < 2) lanes_per_device = 2 * cpus >= 2 * n_devices ? 2 : 1;
+    }
+    if (lanes_per_device > 8) lanes_per_device = 8;
+    const int n_lanes = lanes_per_device * n_devices;
+    /* the cache as a call: every chunk read into the lane's staging, its totals (and class sums) through stage_out */
+    BatchCall b = batch_call(nullptr, nullptr, offs, alg, probe, resolution, nullptr, nullptr, totals_out);
+    b.cache = cache_h.c; b.class_sums_out = class_sums_out;
+    b.stage_in = b.stage_out = true;
+    b.fallback = "GPU cache sweep failed";
+    std::atomic<int> next(0);
+    FirstError fe;
+    run_lanes(n_lanes > n_batches ? n_batches : n_lanes, fe, [&](int id) noexcept {
+        DeviceNodeScope node(devices[id % n_devices]); /* the lane and its page-locked staging on the device's NUMA node */
+        chunk_lane(b, cut, next, fe, devices[id % n_devices]);
+    });
+    return fe.failed.load() ? set_err(err_out, err_len, fe.text) : 0;
+    });
+}

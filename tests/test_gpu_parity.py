@@ -681,6 +681,42 @@ def test_single_process_multi_device_entry_matches_one_batch(fa, oracle_lib):
         fa.calc_batch_devices(xyz, r, offs, [0, 99])
 
 
+def test_structures_without_atoms_get_a_total_of_zero_from_every_in_memory_entry(fa):
+    """Two 40-atom coils followed by two structures without atoms, totals and areas prefilled with NaN, straight through
+    the library: freesasa_gpu_calc_batch (one chunk), _calc_batch_devices on [0, 0, 0, 0] (cuts [0, 1, 1, 2, 4]: a shard
+    without structures and one of two empty ones) and _calc_batch_pipelined with 2 lanes and chunks of 40 atoms (cuts
+    [0, 1, 2, 4]).  A chunk or shard without atoms is never computed; its structures' totals are written as 0.0 all the same
+    (freesasa_gpu_calc_batch_devices used to leave them as they were)."""
+    import ctypes as C
+    L = fa.lib()
+    dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int64)
+    parts = [tools.coil(40, 61), tools.coil(40, 62)]
+    xyz = np.ascontiguousarray(np.concatenate([p[0] for p in parts]), dtype=np.float64).reshape(-1)
+    r = np.ascontiguousarray(np.concatenate([p[1] for p in parts]), dtype=np.float64)
+    offs = np.array([0, 40, 80, 80, 80], dtype=np.int64)
+    assert fa.shard_cuts(offs, 4).tolist() == [0, 1, 1, 2, 4]
+    devs = np.zeros(4, dtype=np.int32)
+    for alg, res in ((fa.LEE_RICHARDS, 20), (fa.SHRAKE_RUPLEY, 100)):
+        want, _, want_t = fa.calc_batch(xyz, r, offs[:3], alg, resolution=res)
+
+        def run(entry, *tail):
+            sasa, totals = np.full(80, np.nan), np.full(4, np.nan)
+            err = C.create_string_buffer(512)
+            ret = entry(xyz.ctypes.data_as(dp), r.ctypes.data_as(dp), offs.ctypes.data_as(lp), 4, alg, 1.4, res,
+                        sasa.ctypes.data_as(dp), None, totals.ctypes.data_as(dp), *tail, err, 512)
+            assert ret == 0, err.value.decode()
+            return sasa, totals
+
+        got = {"calc_batch": run(L.freesasa_gpu_calc_batch, 0),
+               "calc_batch_devices": run(L.freesasa_gpu_calc_batch_devices, devs.ctypes.data_as(ip), 4),
+               "calc_batch_pipelined": run(L.freesasa_gpu_calc_batch_pipelined, 0, 2, 40)}
+        for name, (sasa, totals) in got.items():
+            assert not np.isnan(sasa).any() and not np.isnan(totals).any(), (name, alg, totals)
+            assert np.array_equal(totals[2:], [0.0, 0.0]), (name, alg, totals)
+            assert np.array_equal(totals[:2], want_t) and np.array_equal(sasa, want), (name, alg)
+            assert sasa.tobytes() == got["calc_batch"][0].tobytes() and totals.tobytes() == got["calc_batch"][1].tobytes(), (name, alg)
+
+
 def test_neighbor_sets_of_the_lr_kernel_are_the_reference_ones(fa, oracle_lib):
     """Hot loop #1 on the HIP path, integers only: per-atom neighbor COUNTS (and, for the reference's own 6-atom
     case, tests/test_nb.c:7-27, the neighbor SETS) found by the Lee-Richards kernel's discovery phase equal the
