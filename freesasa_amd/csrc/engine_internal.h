@@ -15,6 +15,8 @@
  *   gpu_parse.hip      the device-side PDB / mmCIF parser: its kernels and their host driver (gpu_parse.h)
  *   gpu_groups.hip     chain groups: a batch and every group of it cut out as a structure of its own, in one batch; the
  *                      group ids made on the device
+ *   gpu_periodic.hip   periodic images: a batch and its orthorhombic cells expanded into a batch with the images that
+ *                      matter, the areas of the real atoms collected; the stage the trajectory file drivers share
  */
 #ifndef FREESASA_AMD_ENGINE_INTERNAL_H
 #define FREESASA_AMD_ENGINE_INTERNAL_H
@@ -39,6 +41,7 @@
 #include "group_kernels.h"
 #include "select_kernels.h"
 #include "traj_kernels.h"
+#include "pbc_kernels.h"
 #include "gpu_parse.h"
 
 /* ------------------------------------------------------------------ kernel launchers (gpu_kernels.hip) */
@@ -103,6 +106,12 @@ hipError_t kl_traj_group_gather(const sasa::TrajGroupArgs &a, hipStream_t st);
 hipError_t kl_traj_group_finish(const sasa::TrajGroupArgs &a, hipStream_t st);
 hipError_t kl_traj_group_totals(const sasa::TrajGroupArgs &a, hipStream_t st);
 
+/* periodic images (pbc_kernels.h): image counts and bases (one workgroup per structure); the expanded batch, the real atoms'
+   areas out of its areas (both one thread per atom of the caller's batch) */
+hipError_t kl_pbc_count(const sasa::PbcArgs &a, hipStream_t st);
+hipError_t kl_pbc_emit(const sasa::PbcArgs &a, hipStream_t st);
+hipError_t kl_pbc_collect(const sasa::PbcArgs &a, hipStream_t st);
+
 /* ------------------------------------------------------------------ context (gpu_engine.hip) */
 
 struct DevBuf {
@@ -158,6 +167,11 @@ struct freesasa_gpu_ctx {
     /* group ids made on the device: the spec's label table, the per-structure words (offsets, status in, n_groups and group
        status out), the groups' labels */
     DevBuf gi_tab, gi_words, gi_label;
+    /* periodic images (gpu_periodic.hip): offsets | expanded offsets | cells | image counts | max radii; the atoms' image bases;
+       the expanded batch and its areas; the chunk tables of the CALLER's batch (its totals are summed like any batch's) */
+    DevBuf p_meta, p_ibase, p_xyz, p_radii, p_sasa, p_chunks, p_part;
+    std::vector<int64_t> p_offsets_host; /* the offsets p_chunks was made for */
+    int p_n_chunks = 0;
     void *stage_in = nullptr, *stage_out = nullptr; /* page-locked host staging of freesasa_gpu_calc_batch_pipelined */
     size_t stage_in_cap = 0, stage_out_cap = 0;
     void *res_stage = nullptr; /* page-locked: a batch's per-residue areas and arrays on their way to the host (gpu_sweep.hip) */
@@ -243,6 +257,24 @@ int group_ids_resident(freesasa_gpu_ctx *c, const GroupSpec &gs, sasa::GidArgs &
 int groups_resident(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
                     const int32_t *d_group, const int32_t *n_groups, double probe, int resolution, const double *unit_points,
                     double *d_sasa, double *d_iso, double *d_totals, double *d_group_totals, std::vector<int> *counts_out);
+
+/* ------------------------------------------------------------------ periodic images (gpu_periodic.hip) */
+
+/* The cutoff of a structure, c = 2 (max radius + probe), and the check of one cell against it on the host: 0, or the 1-based
+   axis of the first edge that is not finite (negative) or shorter than c (positive). */
+double periodic_cutoff(const double *radii, int64_t n, double probe);
+int periodic_cell_bad(const double *cell, double c);
+/* freesasa_gpu_periodic_dev's pipeline on arrays that are on the context's stream already: count, the image counts back to
+   the host (one synchronisation; run_batch takes host offsets), emit, run_batch on the expanded batch with per-atom radii,
+   collect into d_sasa [offsets[n_structs]], totals over the real atoms into d_totals (may be null).  Nothing is waited for
+   at its end.  n_fixed > 0: every structure holds n_fixed atoms and d_radii their n_fixed radii (the frames of a shard;
+   offsets then is k n_fixed).  cells: host, [3 n_structs], checked by the caller to be finite; an edge shorter than a
+   structure's c is refused here, after the count and before the engine runs; d_cells: the same on the device already
+   (null: uploaded here).  unit_points: the S&R test points (null: made
+   here).  images_out (host, may be null) receives the image count of every structure. */
+int periodic_resident(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
+                      int n_fixed, const double *cells, const double *d_cells, double probe, int resolution, const double *unit_points,
+                      double *d_sasa, double *d_totals, int64_t *images_out);
 
 /* ------------------------------------------------------------------ host-side helpers (gpu_hostbatch.hip) */
 

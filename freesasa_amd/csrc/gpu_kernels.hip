@@ -969,6 +969,40 @@ hipError_t kl_traj_group_totals(const TrajGroupArgs &a, hipStream_t st)
     return hipGetLastError();
 }
 
+/* periodic images (pbc_kernels.h): the image counts and their bases (one workgroup per structure), the expanded batch in
+   front of the engine and the real atoms' areas behind it (one thread per atom of the caller's batch) */
+__global__ __launch_bounds__(PBC_B) void k_pbc_count(PbcArgs a)
+{
+    __shared__ double lds_d[PBC_B];
+    __shared__ int lds_w[PBC_WAVES];
+    pbc_count_struct(a, lds_d, lds_w, blockIdx.x, threadIdx.x);
+}
+__global__ __launch_bounds__(PBC_B) void k_pbc_emit(PbcArgs a)
+{
+    pbc_emit_atom(a, (int64_t)blockIdx.x * PBC_B + threadIdx.x);
+}
+__global__ __launch_bounds__(PBC_B) void k_pbc_collect(PbcArgs a)
+{
+    pbc_collect_atom(a, (int64_t)blockIdx.x * PBC_B + threadIdx.x);
+}
+hipError_t kl_pbc_count(const PbcArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_pbc_count, dim3((unsigned)a.n_structs), dim3(PBC_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_pbc_emit(const PbcArgs &a, hipStream_t st)
+{
+    if (a.n_atoms == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_pbc_emit, dim3((unsigned)((a.n_atoms + PBC_B - 1) / PBC_B)), dim3(PBC_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_pbc_collect(const PbcArgs &a, hipStream_t st)
+{
+    if (a.n_atoms == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_pbc_collect, dim3((unsigned)((a.n_atoms + PBC_B - 1) / PBC_B)), dim3(PBC_B), 0, st, a);
+    return hipGetLastError();
+}
+
 void kl_dump_phase_clocks(void)
 {
 #ifdef SASA_PHASE_TIMING

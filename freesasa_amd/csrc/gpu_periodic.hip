@@ -1,0 +1,260 @@
+/*
+ * gpu_periodic.hip — periodic images (include/freesasa_gpu.h, freesasa_gpu_periodic_dev / freesasa_gpu_calc_periodic; the
+ * FREESASA_GPU_FRAMES_PBC bit of the trajectory file drivers): every structure with an orthorhombic cell of its own, the
+ * SASA of its atoms among their periodic images.  Host code; the kernels are in gpu_kernels.hip (phase functions and the
+ * definition: pbc_kernels.h).
+ *
+ *   1. count      k_pbc_count: per atom the base of its images, per structure the image count and the max radius; those
+ *                 come back to the host (the engine takes host offsets): the call's one synchronisation beyond run_batch's
+ *   2. check      every edge against the structure's c = 2 (max radius + probe); the expanded batch against the engine's
+ *                 2^30 atoms - before the engine runs
+ *   3. emit       k_pbc_emit: the wrapped atoms, then their images, at each structure's expanded offset, radii per atom
+ *   4. run_batch  the expanded batch: the tile kernels know nothing of cells
+ *   5. collect    k_pbc_collect: the first n areas of every expanded structure into the caller's compact array
+ *   6. totals     the totals kernels over the compact areas with the chunk table of the CALLER's offsets: the sum over the
+ *                 real atoms in the order every batch's totals are formed in (a cell that makes no image gives the plain
+ *                 run's totals bit for bit)
+ *
+ * periodic_resident is that pipeline for callers whose arrays are on the context's stream (the trajectory lanes,
+ * gpu_drivers.hip); freesasa_gpu_calc_periodic brings host arrays to it with the host-batch path's sizing, upload and
+ * failure epilogue (gpu_hostbatch.hip), as freesasa_gpu_calc_groups does.
+ */
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+#include <vector>
+
+#include "engine_internal.h"
+
+using namespace sasa;
+
+/* (engine_internal.h) */
+double periodic_cutoff(const double *radii, int64_t n, double probe)
+{
+    double m = 0;
+    for (int64_t i = 0; i < n; ++i)
+        if (radii[i] > m) m = radii[i];
+    return 2.0 * (m + probe);
+}
+int periodic_cell_bad(const double *cell, double c)
+{
+    for (int a = 0; a < 3; ++a) {
+        if (!isfinite(cell[a])) return -(a + 1);
+        if (!(cell[a] >= c)) return a + 1;
+    }
+    return 0;
+}
+
+static int cell_fail(freesasa_gpu_ctx *c, int s, const double *cell, int bad, double cut)
+{
+    const int a = bad < 0 ? -bad - 1 : bad - 1;
+    if (bad < 0) return ctx_fail(c, "structure %d: edge %c of its cell is not finite", s, "xyz"[a]);
+    return ctx_fail(c, "structure %d: edge %c of its cell is %.17g, shorter than c = 2 (max radius + probe) = %.17g: "
+                       "first-shell images do not suffice", s, "xyz"[a], cell[a], cut);
+}
+
+/* the chunk table of the caller's offsets (run_batch_once makes the same of the offsets it is given), kept until they change:
+   chunk_begin [nc] | chunk_len [nc] | chunk_struct [nc] | struct_chunk0 [ns + 1] in c->p_chunks */
+static int compact_chunks(freesasa_gpu_ctx *c, const int64_t *offsets, int n_structs, PipeArgs &pa)
+{
+    const size_t ns1 = (size_t)n_structs + 1;
+    if (c->p_offsets_host.size() != ns1 || memcmp(c->p_offsets_host.data(), offsets, 8 * ns1) != 0) {
+        c->p_offsets_host.clear();
+        std::vector<int> cs, cl, sc0(ns1);
+        std::vector<int64_t> cb;
+        for (int s = 0; s < n_structs; ++s) {
+            sc0[s] = (int)cs.size();
+            for (int64_t b = offsets[s]; b < offsets[s + 1]; b += SASA_BOUNDS_CHUNK) {
+                const int64_t e = b + SASA_BOUNDS_CHUNK < offsets[s + 1] ? b + SASA_BOUNDS_CHUNK : offsets[s + 1];
+                cs.push_back(s); cb.push_back(b); cl.push_back((int)(e - b));
+            }
+        }
+        sc0[n_structs] = (int)cs.size();
+        const size_t nc = cs.size();
+        if (ensure(c, c->p_chunks, 16 * nc + 4 * ns1) || ensure(c, c->p_part, 8 * nc)) return -1;
+        char *p = (char *)c->p_chunks.p;
+        /* (synchronous copies out of vectors that end with this scope; the stream's earlier work does not read the table) */
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipMemcpy(p, cb.data(), 8 * nc, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(p + 8 * nc, cl.data(), 4 * nc, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(p + 12 * nc, cs.data(), 4 * nc, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(p + 16 * nc, sc0.data(), 4 * ns1, hipMemcpyHostToDevice));
+        c->p_n_chunks = (int)nc;
+        c->p_offsets_host.assign(offsets, offsets + ns1);
+    }
+    const size_t nc = (size_t)c->p_n_chunks;
+    const char *p = (const char *)c->p_chunks.p;
+    memset(&pa, 0, sizeof pa);
+    pa.n_structs = n_structs; pa.n_atoms = (int)offsets[n_structs]; pa.n_chunks = (int)nc;
+    pa.chunk_begin = (const int64_t *)p; pa.chunk_len = (const int *)(p + 8 * nc); pa.chunk_struct = (const int *)(p + 12 * nc);
+    pa.struct_chunk0 = (const int *)(p + 16 * nc);
+    return 0;
+}
+
+/* (engine_internal.h) */
+int periodic_resident(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
+                      int n_fixed, const double *cells, const double *d_cells, double probe, int resolution, const double *unit_points,
+                      double *d_sasa, double *d_totals, int64_t *images_out)
+{
+    const int64_t n = offsets[n_structs];
+    if (n <= 0) return ctx_fail(c, "empty batch");
+    if (n > (int64_t)1 << 30) return ctx_fail(c, "the expanded batch is too large (max 2^30 atoms and images per call)");
+    const size_t ns = (size_t)n_structs;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    /* offsets [ns + 1] | expanded offsets [ns + 1] | cells [3 ns] | image counts [ns] | max radii [ns] */
+    const size_t o_eoff = 8 * (ns + 1), o_cell = 2 * o_eoff, o_img = o_cell + 24 * ns, o_rmax = o_img + 8 * ns, meta_bytes = o_rmax + 8 * ns;
+    if (ensure(c, c->p_meta, meta_bytes) || ensure(c, c->p_ibase, 4 * (size_t)n)) return -1;
+    char *meta = (char *)c->p_meta.p;
+    PipeArgs ta; /* (the totals' chunk table first: it goes up with copies that wait for the stream when the offsets are new) */
+    if (d_totals && compact_chunks(c, offsets, n_structs, ta)) return -1;
+    PbcArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.xyz = d_xyz; pa.radii = d_radii; pa.n_structs = n_structs; pa.n_atoms = n; pa.probe = probe;
+    pa.n_fixed = n_fixed > 0 ? n_fixed : 0; pa.shared_radii = n_fixed > 0;
+    pa.offsets = n_fixed > 0 ? nullptr : (const int64_t *)meta;
+    pa.cells = d_cells ? d_cells : (const double *)(meta + o_cell);
+    pa.ibase = (int *)c->p_ibase.p; pa.n_img = (int64_t *)(meta + o_img); pa.rmax = (double *)(meta + o_rmax);
+
+    /* 1. count; the image counts and max radii back (the one synchronisation beyond run_batch's) */
+    std::vector<int64_t> back(2 * ns), eoff(ns + 1); /* (declared before the copies that use them: they outlive the stream's reads) */
+    if (n_fixed <= 0) HIP_TRY(c, hipMemcpyAsync(meta, offsets, 8 * (ns + 1), hipMemcpyHostToDevice, st));
+    if (!d_cells) HIP_TRY(c, hipMemcpyAsync(meta + o_cell, cells, 24 * ns, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, kl_pbc_count(pa, st));
+    HIP_TRY(c, hipMemcpyAsync(back.data(), meta + o_img, 16 * ns, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+
+    /* 2. the checks that need the device's numbers, before the engine runs */
+    eoff[0] = 0;
+    for (size_t s = 0; s < ns; ++s) {
+        const int64_t ns_atoms = offsets[s + 1] - offsets[s];
+        if (ns_atoms > 0) {
+            double rmax;
+            memcpy(&rmax, &back[ns + s], 8);
+            const double cut = 2.0 * (rmax + probe);
+            const int bad = periodic_cell_bad(cells + 3 * s, cut);
+            if (bad) return cell_fail(c, (int)s, cells + 3 * s, bad, cut);
+        }
+        if (back[s] < 0 || back[s] > 26 * ns_atoms) return ctx_fail(c, "structure %d: bad image count from the device", (int)s);
+        eoff[s + 1] = eoff[s] + ns_atoms + back[s];
+        if (images_out) images_out[s] = back[s];
+    }
+    const int64_t N = eoff[ns];
+    if (N > (int64_t)1 << 30)
+        return ctx_fail(c, "the expanded batch is too large: %lld atoms and %lld images (max 2^30 together per call)", (long long)n, (long long)(N - n));
+
+    /* 3. emit */
+    if (ensure(c, c->p_xyz, 24 * (size_t)N) || ensure(c, c->p_radii, 8 * (size_t)N) || ensure(c, c->p_sasa, 8 * (size_t)N)) return -1;
+    pa.eoff = (const int64_t *)(meta + o_eoff); pa.exyz = (double *)c->p_xyz.p; pa.eradii = (double *)c->p_radii.p;
+    HIP_TRY(c, hipMemcpyAsync(meta + o_eoff, eoff.data(), 8 * (ns + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, kl_pbc_emit(pa, st));
+
+    /* 4. the engine on the expanded batch (synchronous: eoff is no longer read when it returns) */
+    std::vector<double> tp;
+    if (alg == 1 && !unit_points) { tp = call_test_points(alg, resolution); unit_points = tp.data(); }
+    const bool shared = c->shared_radii;
+    c->shared_radii = false;
+    const int rb = run_batch(c, alg == 0, (const double *)c->p_xyz.p, (const double *)c->p_radii.p, eoff.data(), n_structs, probe, resolution,
+                             alg == 1 ? unit_points : nullptr, (double *)c->p_sasa.p, nullptr, nullptr);
+    c->shared_radii = shared;
+    if (rb) return -1;
+
+    /* 5. collect, 6. totals over the real atoms */
+    pa.esasa = (const double *)c->p_sasa.p; pa.sasa = d_sasa;
+    HIP_TRY(c, kl_pbc_collect(pa, st));
+    if (d_totals) HIP_TRY(c, kl_totals(ta, ta.n_chunks, n_structs, d_sasa, (double *)c->p_part.p, d_totals, st));
+    return 0;
+}
+
+static int periodic_impl(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets,
+                         int n_structs, const double *cells, double probe, int resolution, double *d_sasa, double *d_totals,
+                         int64_t *images_out)
+{
+    c->err[0] = 0;
+    if (!d_xyz || !d_radii || !offsets || !cells || !d_sasa) return ctx_fail(c, "null argument");
+    if (alg != 0 && alg != 1) return ctx_fail(c, "unknown algorithm %d", alg);
+    if (n_structs <= 0) return ctx_fail(c, "n_structs must be > 0");
+    if (resolution <= 0) return ctx_fail(c, "resolution must be > 0");
+    if (offsets[0] != 0) return ctx_fail(c, "offsets[0] must be 0");
+    for (int s = 0; s < n_structs; ++s)
+        if (offsets[s + 1] < offsets[s]) return ctx_fail(c, "offsets must be non-decreasing");
+    for (int s = 0; s < n_structs; ++s) {
+        const int bad = offsets[s + 1] > offsets[s] ? periodic_cell_bad(cells + 3 * (size_t)s, 0.0) : 0;
+        if (bad < 0) return cell_fail(c, s, cells + 3 * (size_t)s, bad, 0.0);
+    }
+    if (periodic_resident(c, alg, d_xyz, d_radii, offsets, n_structs, 0, cells, nullptr, probe, resolution, nullptr, d_sasa, d_totals, images_out))
+        return -1;
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); /* (the call is synchronous) */
+    return 0;
+}
+
+extern "C" int freesasa_gpu_periodic_dev(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii,
+                                         const int64_t *offsets, int n_structs, const double *cells, double probe_radius,
+                                         int resolution, double *d_sasa, double *d_totals, int64_t *images_out)
+{
+    if (!c) return -1;
+    if (freesasa_gpu_wait(c)) return -1; /* (batches submitted asynchronously come first) */
+    return guarded_ctx(c, [&]() -> int {
+        const int rc = periodic_impl(c, alg, d_xyz, d_radii, offsets, n_structs, cells, probe_radius, resolution, d_sasa, d_totals, images_out);
+        if (rc) (void)hipStreamSynchronize(c->stream);
+        return rc;
+    });
+}
+
+extern "C" int freesasa_gpu_calc_periodic(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
+                                          const double *cells, int alg, double probe_radius, int resolution,
+                                          double *sasa_out, double *totals_out, int64_t *images_out,
+                                          int device, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (!xyz || !radii || !offsets || !cells || !sasa_out) return set_err(err_out, err_len, "null argument");
+    if (n_structs <= 0 || offsets[n_structs] <= 0) return set_err(err_out, err_len, "empty batch");
+    /* before an array is read or a device touched: the sizes, then every structure's cell against its own radii */
+    if (offsets[0] != 0) return set_err(err_out, err_len, "offsets[0] must be 0");
+    for (int s = 0; s < n_structs; ++s)
+        if (offsets[s + 1] < offsets[s]) return set_err(err_out, err_len, "offsets must be non-decreasing");
+    if (offsets[n_structs] > (int64_t)1 << 30)
+        return set_err(err_out, err_len, "the expanded batch is too large (max 2^30 atoms and images per call)");
+    for (int s = 0; s < n_structs; ++s) {
+        const int64_t ns_atoms = offsets[s + 1] - offsets[s];
+        if (ns_atoms == 0) continue;
+        const double *cell = cells + 3 * (size_t)s;
+        const double cut = periodic_cutoff(radii + offsets[s], ns_atoms, probe_radius);
+        const int bad = periodic_cell_bad(cell, cut);
+        if (bad) {
+            char msg[240];
+            const int a = bad < 0 ? -bad - 1 : bad - 1;
+            if (bad < 0) snprintf(msg, sizeof msg, "structure %d: edge %c of its cell is not finite", s, "xyz"[a]);
+            else snprintf(msg, sizeof msg, "structure %d: edge %c of its cell is %.17g, shorter than c = 2 (max radius + probe) = %.17g: "
+                                           "first-shell images do not suffice", s, "xyz"[a], cell[a], cut);
+            return set_err(err_out, err_len, msg);
+        }
+    }
+    if (freesasa_gpu_device_count() <= 0)
+        return set_err(err_out, err_len, "no HIP device available: libfreesasa_amd has no CPU path");
+    return guarded(err_out, err_len, [&]() -> int {
+    PoolLease lease(device);
+    freesasa_gpu_ctx *c = lease.c;
+    if (!c) return set_err(err_out, err_len, "could not create a GPU context");
+    const size_t n = (size_t)offsets[n_structs];
+    /* the batch as one chunk of the host-batch path, in place: its sizing, upload and failure epilogue */
+    const BatchCall b;
+    Chunk h;
+    h.ns = n_structs; h.n = n; h.off = offsets; h.xyz = xyz; h.radii = radii;
+    const int rc = [&]() -> int {
+        if (chunk_size(b, c, h) || chunk_upload(c, h)) return -1;
+        if (freesasa_gpu_periodic_dev(c, alg, (const double *)c->h_xyz.p, (const double *)c->h_radii.p, offsets, n_structs, cells,
+                                      probe_radius, resolution, (double *)c->h_sasa.p, totals_out ? (double *)c->h_totals.p : nullptr, images_out))
+            return -1;
+        if (hipMemcpyAsync(sasa_out, c->h_sasa.p, 8 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            (totals_out && hipMemcpyAsync(totals_out, c->h_totals.p, 8 * (size_t)n_structs, hipMemcpyDeviceToHost, c->stream) != hipSuccess))
+            return ctx_fail(c, "device-to-host copy failed");
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return ctx_fail(c, "stream synchronize failed");
+        return 0;
+    }();
+    return rc ? set_err(err_out, err_len, chunk_failed(b, c)) : 0;
+    });
+}

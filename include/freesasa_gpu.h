@@ -399,6 +399,35 @@ int freesasa_gpu_calc_batch(const double *xyz, const double *radii, const int64_
                             double *sasa_out, int *counts_out, double *totals_out,
                             int device, char *err_out, int err_len);
 
+/* Periodic images: every structure s has an orthorhombic cell L = cells[3 s .. 3 s + 2] of its own.  With
+   c = 2 (max radius of the structure + probe_radius), the largest distance at which two of its atoms can be neighbours:
+     requirement   L finite and L[a] >= c on every axis (first-shell images then suffice); anything else is refused (-1 with a
+                   message that names the structure and the edge), never approximated
+     wrap          w[i][a] = x[i][a] - L[a] * floor(x[i][a] / L[a]), fp64
+     images        on axis a atom i admits shift 0 always, +1 when w[i][a] < c, -1 when w[i][a] > L[a] - c; its images are the
+                   admitted (sx, sy, sz) != (0, 0, 0) at w[i] + s L with radius r[i]: 0 to 26 per atom
+     expanded      the wrapped atoms in input order, then the images by atom and, within an atom, by 9 (sx+1) + 3 (sy+1) + (sz+1)
+     result        atom i's area is the engine's area of atom i of the expanded structure; a structure's total is the sum over
+                   its real atoms, formed like every total of the engine (fixed order, no float atomics)
+   Coordinates in [0, L) further than c from every face give the areas and totals of the batch entries bit for bit.  A
+   structure without atoms passes (total 0).  The expansion is made on the device (pbc_kernels.h) and the expanded batch
+   goes through the engine as any batch: its 2^30-atom limit applies to atoms and images together.  images_out (host,
+   [n_structs], may be NULL) receives the image count of every structure.
+   freesasa_gpu_periodic_dev: d_xyz, d_radii, d_sasa [offsets[n_structs]], d_totals [n_structs] (may be NULL) on the device,
+   offsets and cells on the host; synchronous.  freesasa_gpu_calc_periodic: host arrays, pooled context (device -1: the
+   current one); the cells are checked against the radii before a device is touched.  Returns 0 / -1.
+   Not offered: triclinic cells, cells smaller than c, skipping the area computation of the image atoms (their areas are
+   computed and dropped), periodic images in the file or cache sweeps (a PDB CRYST1 record is a crystallographic cell with
+   symmetry).  Trajectories: FREESASA_GPU_FRAMES_PBC below. */
+int freesasa_gpu_periodic_dev(freesasa_gpu_ctx *ctx, int alg, const double *d_xyz, const double *d_radii,
+                              const int64_t *offsets, int n_structs, const double *cells /* host, [3 n_structs] */,
+                              double probe_radius, int resolution, double *d_sasa, double *d_totals,
+                              int64_t *images_out /* host, [n_structs], may be NULL */);
+int freesasa_gpu_calc_periodic(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
+                               const double *cells, int alg, double probe_radius, int resolution,
+                               double *sasa_out, double *totals_out, int64_t *images_out,
+                               int device, char *err_out, int err_len);
+
 /* Trajectory drivers (BASELINE configs[4]): frames of the SAME n_atoms atoms, radii constant.
    Frames are independent structures; a SHARD = frames_per_batch frames (<= 0: about 1.25e6 atoms) goes through the
    engine as one batch.  A few host lanes take shards from a shared counter, each on its own pooled context and
@@ -435,12 +464,29 @@ int freesasa_gpu_calc_batch(const double *xyz, const double *radii, const int64_
    host every record marker of every frame of a shard is checked before the shard goes up: a mismatch ends the run like a
    failed read ("frame K of the DCD file is damaged"; the shard is not listed).  The done-list's f32= word carries bit 2
    and its header_bytes= the byte of frame 0: a raw run's list is refused by a DCD run and the other way round; a raw run's
-   line is what it was.  SASA is computed WITHOUT periodic images: a solute that the writer wrapped across the box must be
-   made whole beforehand.  Not offered: DCD files with fixed atoms or 64-bit record markers, other container formats (XTC,
-   TRR, NetCDF), any use of the unit cell, a memory form. */
+   line is what it was.  Without bit 3 SASA is computed WITHOUT periodic images: a solute that the writer wrapped across the
+   box must be made whole beforehand.  Not offered: DCD files with fixed atoms or 64-bit record markers, other container
+   formats (XTC, TRR, NetCDF), a memory form.
+
+   Periodic images (freesasa_gpu_trajectory_file, _file_devices, _file_topology): with bit 3 (FREESASA_GPU_FRAMES_PBC) beside
+   bit 2 every frame is computed among the periodic images its own unit-cell record implies, as freesasa_gpu_calc_periodic
+   below defines them - the atoms the engine sees (with a topology: the atoms the index keeps) wrapped into the cell, the
+   first-shell images that can touch them added on the device in front of the engine, the areas and the total of the real
+   atoms collected behind it; residues, class sums, selections, fp32 output and the files are what they are without the bit.
+   On the host every frame's cell record is decoded beside the marker check (6 doubles in the file's byte order, CHARMM's A,
+   gamma, B, beta, alpha, C: the angles as cosines or as degrees): an angle field v with neither |v| <= 1e-6 nor
+   |v - 90| <= 1e-4, or an edge that is not finite or shorter than c = 2 (max radius + probe), ends the run like a damaged
+   frame ("frame K of the DCD file: ..." with the reason; the shard is not listed).  A shard's edges go up behind its bytes,
+   24 bytes per frame.  Refused with a message before a device is touched or an output file opened: bit 3 without bit 2, a
+   DCD file without a cell record, freesasa_gpu_trajectory_file_groups (an isolated group among periodic images is not
+   defined).  The done-list's f32= word carries bit 3: a periodic run's list is refused by a run without the bit and the other
+   way round.  A cell no atom comes within c of changes nothing: such a run's files are those of the run without the bit,
+   byte for byte.  Not offered: triclinic cells, cells smaller than c, a cell for raw frame files or the memory entries,
+   chain groups with periodic images. */
 #define FREESASA_GPU_FRAMES_F32 1     /* frames_f32 bit 0: raw fp32 frames (input format) */
 #define FREESASA_GPU_FRAMES_OUT_F32 2 /* bit 1: per-atom (and isolated) areas written as fp32 (output format) */
 #define FREESASA_GPU_FRAMES_DCD 4     /* bit 2: frames_path is a DCD trajectory */
+#define FREESASA_GPU_FRAMES_PBC 8     /* bit 3: with bit 2, every frame among the periodic images of its cell record */
 
 /* The header of a DCD file.  Every integer of the file is an int32 in the file's byte order; records lie between two equal
    byte counts:  [84 | "CORD" | 20 control words | 84]  [m | NTITLE | 80 NTITLE bytes | m]  [4 | NATOM | 4], then per frame

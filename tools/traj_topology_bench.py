@@ -18,9 +18,20 @@ With --dcd the arms are instead
               per frame against 12 N; de-planarized, gathered and widened by one kernel on the device)
 timed in one process, interleaved; the totals files must be identical.
 
+With --pbc the arms are the periodic images of the DCD drivers (FREESASA_GPU_FRAMES_PBC) against the same call without the bit,
+on two DCD files with a unit-cell record:
+    solvated      the 100 000-atom frames above moved into the cell [0, 2 half)^3, the solute mid-box and further than c from
+                  every face (almost no images: the cost of the stage itself), trajectory_file_topology, totals only
+    solvated-pbc  the same call with pbc=True
+    filled        frames of the 10 000 solute atoms alone in a cell one lattice spacing wider than their extent: the kept atoms
+                  fill the box (the expansion factor decides the cost, about ((L + 2 c) / L)^3), trajectory_file, totals only
+    filled-pbc    the same call with pbc=True
+each line with images_per_atom (calc_periodic on frame 0; null where the library has no periodic entry).  --pbc-arms off runs the
+two arms without the bit alone and passes no pbc keyword: the form an older library's wrapper takes, for a baseline.
+
 One JSON line per arm: atom-frames/s counted in SOLUTE atoms and in frame atoms, the median and the spread of --reps runs.
 
-    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd]
+    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd] [--pbc [--pbc-arms all|off]]
 
 For the kernel times: `rocprofv3 --kernel-trace --stats -- python tools/traj_topology_bench.py --reps 1 --arms all`
 (k_traj_gather / k_traj_residues / k_traj_class / k_traj_sel are the topology's kernels, k_traj_group_* the groups')."""
@@ -88,6 +99,36 @@ def make_frames(scratch, xyz, n_frames, dcd=False):
     return full, bare, as_dcd
 
 
+def make_pbc_frames(scratch, xyz, n_frames):
+    """the two DCD files of --pbc -> (solvated path, its cell, filled path, its cell); coordinates as make_frames draws them,
+    moved so that the cell begins at 0"""
+    rng = np.random.default_rng(5)
+    half = 1.3 * np.abs(xyz).max()
+    lo = xyz.min(0) - 0.5 * 2.6 - 0.25
+    edge = (xyz.max(0) - xyz.min(0)) + 2.6 + 0.5
+    out = []
+    for name, n, shift, cell in (("solvated_pbc.dcd", N_FRAME, half, np.full(3, 2 * half)), ("filled_pbc.dcd", N_SOLUTE, -lo, edge)):
+        path = os.path.join(scratch, name)
+        plane = struct.pack("<i", 4 * n)
+        rec = struct.pack("<i", 48) + np.array([cell[0], 0, cell[1], 0, 0, cell[2]]).astype("<f8").tobytes() + struct.pack("<i", 48)
+        with open(path, "wb") as fh:
+            fh.write(dcd_header(n, n_frames))
+            for f in range(n_frames):
+                frame = (xyz + rng.uniform(-0.25, 0.25, xyz.shape) + shift).astype(np.float32)
+                if n > N_SOLUTE:
+                    frame = np.concatenate([frame, rng.uniform(0, 2 * half, (n - N_SOLUTE, 3)).astype(np.float32)])
+                fh.write(rec + b"".join(plane + np.ascontiguousarray(frame[:, k]).tobytes() + plane for k in range(3)))
+        out += [path, cell]
+    return out
+
+
+def first_frame(path, n):
+    """the first n atoms of frame 0 of a little-endian DCD file with a cell record, widened"""
+    info = fa.dcd_info(path)
+    raw = np.fromfile(path, dtype=np.uint8, count=info.frame_bytes, offset=info.first_frame)
+    return np.stack([raw[info.x_off + k * info.plane_bytes:][:4 * n].view("<f4") for k in range(3)], axis=1).astype(np.float64)
+
+
 def long_way(full, b, ids, n_frames, out_path):
     """group areas of every frame through calc_groups on host-tiled batches of the driver's default shard length"""
     fpb = 1250000 // N_FRAME + 1
@@ -111,11 +152,13 @@ def main():
     ap.add_argument("--scratch", default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--dcd", action="store_true", help="time the raw fp32 file against a DCD file of the same frames")
+    ap.add_argument("--pbc", action="store_true", help="time the DCD drivers with and without periodic images")
+    ap.add_argument("--pbc-arms", default="all", choices=["all", "off"])
     args = ap.parse_args()
     scratch = args.scratch or tempfile.mkdtemp(prefix="traj_topology_bench_")
     try:
         b, xyz = solute()
-        full, bare, as_dcd = make_frames(scratch, xyz, args.frames, args.dcd)
+        full, bare, as_dcd = make_frames(scratch, xyz, args.frames, args.dcd) if not args.pbc else (None, None, None)
         sel = ingest.Selection(EIGHT)
         index = np.arange(N_SOLUTE, dtype=np.int32)
         ids = (np.arange(N_SOLUTE) >= N_SOLUTE // 2).astype(np.int32)
@@ -133,7 +176,17 @@ def main():
             arms = {"raw": arms["totals"],
                     "dcd": lambda: fa.trajectory_file_topology(as_dcd, b, p("t5"), atom_index=index, dcd=True)}
             assert fa.dcd_info(as_dcd).n_frames == args.frames and os.path.getsize(as_dcd) - os.path.getsize(full) == 80 * args.frames + 196
-        names = list(arms) if args.dcd else [a for a in args.arms.split(",") if a in arms]
+        images = {}
+        if args.pbc:
+            solv, solv_cell, fill, fill_cell = make_pbc_frames(scratch, xyz, args.frames)
+            arms = {"solvated": lambda: fa.trajectory_file_topology(solv, b, p("t6"), atom_index=index, dcd=True),
+                    "filled": lambda: fa.trajectory_file(fill, b.radii, p("t8"), dcd=True)}
+            if args.pbc_arms == "all":
+                arms = {"solvated": arms["solvated"],
+                        "solvated-pbc": lambda: fa.trajectory_file_topology(solv, b, p("t7"), atom_index=index, dcd=True, pbc=True),
+                        "filled": arms["filled"],
+                        "filled-pbc": lambda: fa.trajectory_file(fill, b.radii, p("t9"), dcd=True, pbc=True)}
+        names = list(arms) if args.dcd or args.pbc else [a for a in args.arms.split(",") if a in arms]
         runs = {a: [] for a in names}
         for a in names:
             arms[a]()                                                    # warm-up: contexts, staging, page cache
@@ -143,17 +196,28 @@ def main():
                 res = arms[a]()
                 runs[a].append(time.perf_counter() - t0)
                 assert res[0] and res[1] == args.frames
+        if args.pbc and hasattr(fa, "calc_periodic"):    # (behind the timed runs: a batch of another shape leaves its launch history in a pooled context)
+            for a, path, cell in (("solvated", solv, solv_cell), ("filled", fill, fill_cell)):
+                k = fa.calc_periodic(first_frame(path, N_SOLUTE), b.radii, [0, N_SOLUTE], [cell])[2]
+                images[a] = images[a + "-pbc"] = float(k[0]) / N_SOLUTE
         totals = [np.fromfile(p(k)) for a, k in (("plain", "t0"), ("totals", "t1"), ("all", "t2"), ("groups", "t3"), ("raw", "t1"), ("dcd", "t5")) if a in names]
         assert all(np.array_equal(t, totals[0]) for t in totals)
+        if "solvated-pbc" in names:      # no atom of the solute within c of a face: the bit changes nothing; a filled box: it must
+            assert images["solvated"] > 0 or np.array_equal(np.fromfile(p("t6")), np.fromfile(p("t7")))
+            assert np.all(np.fromfile(p("t9")) < np.fromfile(p("t8")))
         assert not ("groups" in names and "longway" in names) or np.array_equal(np.fromfile(p("g3")), np.fromfile(p("g4")))
         lines = []
         for a in names:
             v = sorted(runs[a])
             med = v[len(v) // 2]
-            lines.append(json.dumps({"arm": a, "frames": args.frames, "frame_atoms": N_SOLUTE if a == "plain" else N_FRAME, "solute_atoms": N_SOLUTE,
-                                     "median_seconds": med, "min_seconds": v[0], "max_seconds": v[-1],
-                                     "solute_atom_frames_per_s": N_SOLUTE * args.frames / med,
-                                     "frame_atom_frames_per_s": (N_SOLUTE if a == "plain" else N_FRAME) * args.frames / med, "runs": len(v)}))
+            frame_atoms = N_SOLUTE if a == "plain" or a.startswith("filled") else N_FRAME
+            line = {"arm": a, "frames": args.frames, "frame_atoms": frame_atoms, "solute_atoms": N_SOLUTE,
+                    "median_seconds": med, "min_seconds": v[0], "max_seconds": v[-1],
+                    "solute_atom_frames_per_s": N_SOLUTE * args.frames / med,
+                    "frame_atom_frames_per_s": frame_atoms * args.frames / med, "runs": len(v)}
+            if args.pbc:
+                line["images_per_atom"] = images.get(a)
+            lines.append(json.dumps(line))
         print("\n".join(lines))
         if args.out:
             with open(args.out, "w") as fh:
