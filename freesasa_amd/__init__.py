@@ -126,6 +126,10 @@ def lib():
                                                 C.c_void_p, C.c_void_p, _lp]
         L.freesasa_gpu_calc_periodic.argtypes = [_dp, _dp, _lp, C.c_int, _dp, C.c_int, C.c_double, C.c_int, _dp, _dp, _lp,
                                                  C.c_int, C.c_char_p, C.c_int]
+        L.freesasa_gpu_periodic_triclinic_dev.argtypes = L.freesasa_gpu_periodic_dev.argtypes
+        L.freesasa_gpu_calc_periodic_triclinic.argtypes = L.freesasa_gpu_calc_periodic.argtypes
+        L.freesasa_gpu_cell_widths.argtypes = [_dp, _dp]
+        L.freesasa_gpu_cell_from_dcd.argtypes = [_dp, _dp, C.c_char_p, C.c_int]
         L.freesasa_gpu_test_points.argtypes = [C.c_int, _dp]
         L.freesasa_gpu_test_points.restype = None
         L.freesasa_gpu_calc_batch.argtypes = [_dp, _dp, _lp, C.c_int, C.c_int, C.c_double, C.c_int,
@@ -258,6 +262,49 @@ def calc_periodic(xyz, radii, offsets, cells, alg=LEE_RICHARDS, probe=1.4, resol
     if ret:
         raise RuntimeError("freesasa_gpu_calc_periodic: " + err.value.decode())
     return sasa, totals, images
+
+
+def calc_periodic_triclinic(xyz, radii, offsets, cells6, alg=LEE_RICHARDS, probe=1.4, resolution=20, device=-1):
+    """freesasa_gpu_calc_periodic_triclinic() on host arrays: (sasa, totals, images) as calc_periodic.  cells6 [n_structs, 6]:
+    every structure's cell as (ax, bx, by, cx, cy, cz), the lower-triangular box matrix with rows a, b, c; all finite, ax, by,
+    cz > 0 and every width (cell_widths) at least 2 (max radius of the structure + probe)."""
+    xyz, radii = _f64(xyz).reshape(-1), _f64(radii)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    cells6 = _f64(cells6).reshape(-1)
+    n, ns = radii.size, offsets.size - 1
+    if cells6.size != 6 * ns:
+        raise ValueError("cells6 needs six numbers per structure")
+    sasa, totals, images = np.empty(n), np.empty(ns), np.zeros(ns, dtype=np.int64)
+    err = C.create_string_buffer(512)
+    ret = lib().freesasa_gpu_calc_periodic_triclinic(xyz.ctypes.data_as(_dp), radii.ctypes.data_as(_dp), offsets.ctypes.data_as(_lp), ns,
+                                                     cells6.ctypes.data_as(_dp), alg, probe, resolution, sasa.ctypes.data_as(_dp),
+                                                     totals.ctypes.data_as(_dp), images.ctypes.data_as(_lp), device, err, 512)
+    if ret:
+        raise RuntimeError("freesasa_gpu_calc_periodic_triclinic: " + err.value.decode())
+    return sasa, totals, images
+
+
+def cell_widths(cell6):
+    """freesasa_gpu_cell_widths(): the distances (d_a, d_b, d_c) between the opposite faces of the cell (ax, bx, by, cx, cy, cz);
+    ValueError for an entry that is not finite or a diagonal entry that is not positive."""
+    cell6, out = _f64(cell6).reshape(-1), np.empty(3)
+    if cell6.size != 6:
+        raise ValueError("a cell is six numbers")
+    if lib().freesasa_gpu_cell_widths(cell6.ctypes.data_as(_dp), out.ctypes.data_as(_dp)):
+        raise ValueError("freesasa_gpu_cell_widths: the entries must be finite and ax, by, cz > 0")
+    return out
+
+
+def cell_from_dcd(rec):
+    """freesasa_gpu_cell_from_dcd(): a DCD unit-cell record (A, gamma, B, beta, alpha, C; the angles as cosines or degrees) ->
+    the cell (ax, bx, by, cx, cy, cz); ValueError with the library's reason for a record that spans no cell."""
+    rec, out = _f64(rec).reshape(-1), np.empty(6)
+    if rec.size != 6:
+        raise ValueError("a cell record is six numbers")
+    why = C.create_string_buffer(256)
+    if lib().freesasa_gpu_cell_from_dcd(rec.ctypes.data_as(_dp), out.ctypes.data_as(_dp), why, 256):
+        raise ValueError("freesasa_gpu_cell_from_dcd: " + why.value.decode())
+    return out
 
 
 def calc_batch_devices(xyz, radii, offsets, devices, alg=LEE_RICHARDS, probe=1.4, resolution=20):
@@ -655,7 +702,7 @@ def trajectory(xyz_frames, radii, alg=LEE_RICHARDS, probe=1.4, resolution=20, fr
     return totals, sasa
 
 
-FRAMES_F32, FRAMES_OUT_F32, FRAMES_DCD, FRAMES_PBC = 1, 2, 4, 8   # the bits of frames_f32 (include/freesasa_gpu.h)
+FRAMES_F32, FRAMES_OUT_F32, FRAMES_DCD, FRAMES_PBC, FRAMES_TRICLINIC = 1, 2, 4, 8, 16   # the bits of frames_f32 (include/freesasa_gpu.h)
 
 
 class DcdInfoC(C.Structure):
@@ -690,22 +737,24 @@ def dcd_info(path):
     return DcdInfo(c)
 
 
-def _frames_bits(f32, out_f32, dcd, header_bytes, pbc=False):
+def _frames_bits(f32, out_f32, dcd, header_bytes, pbc=False, triclinic=False):
     if dcd and (f32 or header_bytes):
         raise ValueError("dcd=True excludes f32=True and a non-zero header_bytes: a DCD file says for itself where its frames are")
-    return (FRAMES_F32 if f32 else 0) | (FRAMES_OUT_F32 if out_f32 else 0) | (FRAMES_DCD if dcd else 0) | (FRAMES_PBC if pbc else 0)
+    return (FRAMES_F32 if f32 else 0) | (FRAMES_OUT_F32 if out_f32 else 0) | (FRAMES_DCD if dcd else 0) | (FRAMES_PBC if pbc else 0) | \
+        (FRAMES_TRICLINIC if triclinic else 0)
 
 
 def trajectory_file(frames_path, radii, totals_path, sasa_path=None, done_path=None, f32=False, header_bytes=0,
                     n_frames=0, alg=LEE_RICHARDS, probe=1.4, resolution=20, frames_per_batch=0, max_new_shards=0, device=-1,
-                    devices=None, out_f32=False, dcd=False, pbc=False):
+                    devices=None, out_f32=False, dcd=False, pbc=False, triclinic=False):
     """freesasa_gpu_trajectory_file(): raw frame file -> totals file (+ per-atom file), resumable through the
     done-list at done_path.  Returns (complete, n_frames): complete is False when max_new_shards stopped the run.
     f32: the frames are floats (an input format); out_f32: the per-atom file holds floats (an output format);
     dcd: frames_path is a DCD trajectory whose NATOM is len(radii) (no f32, no header_bytes with it);
-    pbc: (with dcd) every frame among the periodic images its unit-cell record implies, as calc_periodic defines them."""
+    pbc: (with dcd) every frame among the periodic images its unit-cell record implies, as calc_periodic defines them;
+    triclinic: (with dcd and pbc) the record decoded by cell_from_dcd, the frame as calc_periodic_triclinic defines it."""
     radii = _f64(radii)
-    f32 = _frames_bits(f32, out_f32, dcd, header_bytes, pbc)
+    f32 = _frames_bits(f32, out_f32, dcd, header_bytes, pbc, triclinic)
     err = C.create_string_buffer(512)
     total = C.c_longlong(0)
     enc = lambda p: None if p is None else str(p).encode()
@@ -848,21 +897,23 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
                              sasa_path=None, class_sums_path=None, residues_path=None, selections_path=None, done_path=None,
                              f32=False, header_bytes=0, n_frames=0, alg=LEE_RICHARDS, probe=1.4, resolution=20, frames_per_batch=0,
                              max_new_shards=0, device=-1, devices=None, out_f32=False, chain_groups=None, separate_chains=False,
-                             long=False, group=None, n_groups=None, group_areas_path=None, isolated_path=None, dcd=False, pbc=False):
+                             long=False, group=None, n_groups=None, group_areas_path=None, isolated_path=None, dcd=False, pbc=False,
+                             triclinic=False):
     """freesasa_gpu_trajectory_file_topology(): trajectory_file() with a topology (see trajectory_topology; frame_atoms:
     atoms per frame of the file, None: the structure's) and one raw fp64 result file per output asked for: class sums
     [F, 3], residues [F, R, 6], selection areas [F, S].  Returns (complete, n_frames, selection_atoms [S] or None).
     Chain groups (the keywords of trajectory_topology; freesasa_gpu_trajectory_file_groups): group_areas_path receives
     [F, G, 3] fp64, isolated_path [F, n] fp64 (fp32 with out_f32).
     dcd: frames_path is a DCD trajectory; frame_atoms None is then the file's NATOM.
-    pbc: (with dcd) the atoms the index keeps among their periodic images, frame by frame (not offered with chain groups)."""
+    pbc: (with dcd) the atoms the index keeps among their periodic images, frame by frame (not offered with chain groups);
+    triclinic: (with dcd and pbc) the cell records decoded as triclinic cells, see trajectory_file."""
     L = _topology_proto(lib())
     if dcd and frame_atoms is None:
         frame_atoms = dcd_info(frames_path).n_atoms
     n, R, res_ref, idx, fa_ = _topology_args(batch, structure, atom_index, frame_atoms)
     S = len(selection) if selection is not None else 0
     sel_atoms = np.zeros(S, dtype=np.int64) if selection is not None else None
-    bits = _frames_bits(f32, out_f32, dcd, header_bytes, pbc)
+    bits = _frames_bits(f32, out_f32, dcd, header_bytes, pbc, triclinic)
     err = C.create_string_buffer(512)
     total = C.c_longlong(0)
     enc = lambda p: None if p is None else str(p).encode()
@@ -1069,6 +1120,21 @@ class GpuContext:
                                               images.ctypes.data_as(_lp))
         if ret:
             raise RuntimeError("freesasa_gpu_periodic_dev: " + self.error())
+        return images
+
+    def periodic_triclinic(self, d_xyz, d_radii, offsets, cells6, d_sasa, d_totals=0, alg=LEE_RICHARDS, probe=1.4, resolution=20):
+        """freesasa_gpu_periodic_triclinic_dev(): periodic() for triclinic cells (cells6: a host array [n_structs, 6], see
+        calc_periodic_triclinic)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        cells6 = _f64(cells6).reshape(-1)
+        if cells6.size != 6 * (offsets.size - 1):
+            raise ValueError("cells6 needs six numbers per structure")
+        images = np.zeros(offsets.size - 1, dtype=np.int64)
+        ret = lib().freesasa_gpu_periodic_triclinic_dev(self._h, alg, d_xyz, d_radii, offsets.ctypes.data_as(_lp), offsets.size - 1,
+                                                        cells6.ctypes.data_as(_dp), probe, resolution, d_sasa, d_totals or None,
+                                                        images.ctypes.data_as(_lp))
+        if ret:
+            raise RuntimeError("freesasa_gpu_periodic_triclinic_dev: " + self.error())
         return images
 
     def shrake_rupley(self, d_xyz, d_radii, offsets, d_sasa, d_counts=0, d_totals=0, probe=1.4,

@@ -15,8 +15,8 @@
  *   gpu_parse.hip      the device-side PDB / mmCIF parser: its kernels and their host driver (gpu_parse.h)
  *   gpu_groups.hip     chain groups: a batch and every group of it cut out as a structure of its own, in one batch; the
  *                      group ids made on the device
- *   gpu_periodic.hip   periodic images: a batch and its orthorhombic cells expanded into a batch with the images that
- *                      matter, the areas of the real atoms collected; the stage the trajectory file drivers share
+ *   gpu_periodic.hip   periodic images: a batch and its cells (orthorhombic or triclinic) expanded into a batch with the
+ *                      images that matter, the areas of the real atoms collected; the stage the trajectory file drivers share
  */
 #ifndef FREESASA_AMD_ENGINE_INTERNAL_H
 #define FREESASA_AMD_ENGINE_INTERNAL_H
@@ -42,6 +42,7 @@
 #include "select_kernels.h"
 #include "traj_kernels.h"
 #include "pbc_kernels.h"
+#include "pbc_tri_kernels.h"
 #include "gpu_parse.h"
 
 /* ------------------------------------------------------------------ kernel launchers (gpu_kernels.hip) */
@@ -111,6 +112,9 @@ hipError_t kl_traj_group_totals(const sasa::TrajGroupArgs &a, hipStream_t st);
 hipError_t kl_pbc_count(const sasa::PbcArgs &a, hipStream_t st);
 hipError_t kl_pbc_emit(const sasa::PbcArgs &a, hipStream_t st);
 hipError_t kl_pbc_collect(const sasa::PbcArgs &a, hipStream_t st);
+/* ... in a triclinic cell (pbc_tri_kernels.h): the same two phases with the general geometry; the collect is kl_pbc_collect */
+hipError_t kl_pbc_tri_count(const sasa::PbcTriArgs &a, hipStream_t st);
+hipError_t kl_pbc_tri_emit(const sasa::PbcTriArgs &a, hipStream_t st);
 
 /* ------------------------------------------------------------------ context (gpu_engine.hip) */
 
@@ -275,6 +279,16 @@ int periodic_cell_bad(const double *cell, double c);
 int periodic_resident(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
                       int n_fixed, const double *cells, const double *d_cells, double probe, int resolution, const double *unit_points,
                       double *d_sasa, double *d_totals, int64_t *images_out);
+/* Triclinic cells (pbc_tri_kernels.h).  periodic_cell6_bad (cell.c): the shape check of six numbers ax, bx, by, cx, cy, cz on the host: 0,
+   -(k + 1) when entry k is not finite, k + 1 when the diagonal entry k (0, 2, 5) is not positive.  periodic_widths_bad: 0, or
+   the 1-based axis (a, b, c) of the first width below c.  periodic_resident_tri is periodic_resident for cells9 [9 n_structs] =
+   per structure the six numbers and their three widths (freesasa_gpu_cell_widths), shape-checked by the caller; d_cells9: the
+   same on the device already (null: uploaded here). */
+extern "C" int periodic_cell6_bad(const double *cell6); /* (cell.c) */
+int periodic_widths_bad(const double *widths, double c);
+int periodic_resident_tri(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
+                          int n_fixed, const double *cells9, const double *d_cells9, double probe, int resolution, const double *unit_points,
+                          double *d_sasa, double *d_totals, int64_t *images_out);
 
 /* ------------------------------------------------------------------ host-side helpers (gpu_hostbatch.hip) */
 

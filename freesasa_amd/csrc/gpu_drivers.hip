@@ -156,6 +156,7 @@ struct TrajIO {
     bool in_dcd = false;            /* the file is a DCD trajectory: its frames go up as they lie in the file ... */
     freesasa_gpu_dcd_info dcd = {}; /* ... and this says where their planes are (dcd.c) */
     bool pbc = false;               /* FREESASA_GPU_FRAMES_PBC: every frame among the images its cell record implies (gpu_periodic.hip) */
+    bool tri = false;               /* ... FREESASA_GPU_FRAMES_TRICLINIC beside it: the record decoded as a triclinic cell */
     /* per frame: total [1], per-atom areas [n]; runs with a topology: class sums [3], residue areas [6 R], selection areas [S];
        with chain groups: every atom's area in its isolated group [n], and isolated, complex, buried per group [3 G] */
     TrajOut out[N_OUT] = {{"totals", 0}, {"per-atom", 1}, {"isolated", 32}, {"class-sums", 2}, {"residues", 4}, {"selections", 8}, {"groups", 16}};
@@ -369,6 +370,8 @@ struct TrajRun {
     const bool pbc = io.pbc;
     const double pbc_cut = pbc ? periodic_cutoff(s.radii, s.n_atoms, s.probe) : 0;
     static size_t cells_at(size_t in_bytes) { return (in_bytes + 7) & ~(size_t)7; }
+    /* (a triclinic run: per frame the six numbers of the cell and its three widths) */
+    const size_t cell_bytes = io.tri ? 8 * PBC_TRI_CELL : 24;
     /* the caller's arrays are page-locked: no staging */
     const bool in_pinned = io.mem_in && host_pinned(io.mem_in);
     const bool direct_out = io.out[OUT_TOTALS].mem && host_pinned(io.out[OUT_TOTALS].mem) && (!io.out[OUT_SASA].mem || host_pinned(io.out[OUT_SASA].mem)) &&
@@ -436,7 +439,7 @@ int shard_size(TrajRun &T, TrajLane &L)
     if (ensure(c, c->h_xyz, 24 * nc * FB) || ensure(c, c->h_radii, T.groups ? 8 * nc * FB : 8 * n) || ensure(c, c->h_sasa, 8 * nc * FB) ||
         ensure(c, c->h_totals, 8 * (1 + T.G) * FB) ||
         (T.widen_bytes + narrow_bytes && ensure(c, c->h_counts, T.widen_bytes + narrow_bytes)) ||
-        ((T.gather || T.dcd) && ensure(c, c->g_xyz, T.pbc ? TrajRun::cells_at(T.stride * FB) + 24 * FB : T.stride * FB)) || (T.xw && ensure(c, c->h_gtot, 8 * T.xw * FB)) ||
+        ((T.gather || T.dcd) && ensure(c, c->g_xyz, T.pbc ? TrajRun::cells_at(T.stride * FB) + T.cell_bytes * FB : T.stride * FB)) || (T.xw && ensure(c, c->h_gtot, 8 * T.xw * FB)) ||
         (T.groups && (ensure(c, c->g_gath, 8 * nc * FB) || ensure(c, c->g_tot2, 8 * (1 + T.G) * FB))) || (iso && ensure(c, c->h_iso, 8 * n * FB)))
         return -1;
     if (!T.groups && !L.radii_up && hipMemcpyAsync(c->h_radii.p, T.s.radii, 8 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "radii upload failed");
@@ -467,6 +470,17 @@ long long dcd_damaged_frame(const freesasa_gpu_dcd_info &d, const char *bytes, l
     return -1;
 }
 
+/* the six doubles of frame f's cell record, in the host's byte order */
+static void dcd_cell_record(const freesasa_gpu_dcd_info &d, const char *bytes, long long f, double *v)
+{
+    for (int k = 0; k < 6; ++k) {
+        uint64_t w;
+        memcpy(&w, bytes + f * d.frame_bytes + 4 + 8 * k, 8);
+        if (d.big_endian) w = __builtin_bswap64(w);
+        memcpy(&v[k], &w, 8);
+    }
+}
+
 /* The cell records of the DCD frames [0, nf) at `bytes` (their markers are checked): 6 doubles in the file's byte order, CHARMM's
    A, gamma, B, beta, alpha, C - the angles as cosines or as degrees.  The edges into edges[nf][3]; returns -1, or the first frame
    whose cell periodic images are not offered for, the reason in why: an angle that is not a right one, an edge that is not
@@ -475,12 +489,7 @@ long long dcd_cells(const freesasa_gpu_dcd_info &d, const char *bytes, long long
 {
     for (long long f = 0; f < nf; ++f) {
         double v[6];
-        for (int k = 0; k < 6; ++k) {
-            uint64_t w;
-            memcpy(&w, bytes + f * d.frame_bytes + 4 + 8 * k, 8);
-            if (d.big_endian) w = __builtin_bswap64(w);
-            memcpy(&v[k], &w, 8);
-        }
+        dcd_cell_record(d, bytes, f, v);
         const int ang[3] = {1, 3, 4}, edge[3] = {0, 2, 5};
         for (int k = 0; k < 3; ++k)
             if (!(fabs(v[ang[k]]) <= 1e-6 || fabs(v[ang[k]] - 90.0) <= 1e-4)) {
@@ -500,6 +509,30 @@ long long dcd_cells(const freesasa_gpu_dcd_info &d, const char *bytes, long long
     return -1;
 }
 
+/* The same records decoded as triclinic cells (freesasa_gpu_cell_from_dcd): cell9[nf][9] receives the six numbers of every
+   frame's cell and, behind them, its three widths; returns -1, or the first frame whose record spans no cell or whose cell has
+   a width below cut, the reason in why. */
+long long dcd_cells_tri(const freesasa_gpu_dcd_info &d, const char *bytes, long long nf, double cut, double *cell9, char *why, size_t why_len)
+{
+    for (long long f = 0; f < nf; ++f) {
+        double v[6], *h = cell9 + PBC_TRI_CELL * f;
+        dcd_cell_record(d, bytes, f, v);
+        if (freesasa_gpu_cell_from_dcd(v, h, why, (int)why_len)) return f;
+        const int shape = periodic_cell6_bad(h);
+        if (shape) { /* (an edge that is not positive: everything else the decoder has refused) */
+            snprintf(why, why_len, "edge %c of its cell is %.9g: not positive", shape == 1 ? 'A' : shape == 3 ? 'B' : 'C', v[shape == 1 ? 0 : shape == 3 ? 2 : 5]);
+            return f;
+        }
+        (void)freesasa_gpu_cell_widths(h, h + 6);
+        const int bad = periodic_widths_bad(h + 6, cut);
+        if (bad) {
+            snprintf(why, why_len, "width %c of its cell is %.9g, smaller than c = 2 (max radius + probe) = %.9g", "abc"[bad - 1], h[6 + bad - 1], cut);
+            return f;
+        }
+    }
+    return -1;
+}
+
 /* the shard's frames in page-locked memory: the caller's own, or the lane's staging filled from memory or from the file
    (a DCD file: the bytes as they lie there, every record marker checked; with periodic images every cell record decoded and
    checked, the edges behind the bytes) */
@@ -507,7 +540,7 @@ int shard_read(TrajRun &T, freesasa_gpu_ctx *c, TrajShard &h)
 {
     h.src = T.io.mem_in ? T.io.mem_in + 3 * T.fa * (size_t)h.f0 : nullptr;
     if (h.src && T.in_pinned) return 0;
-    if (ensure_pinned(c, &c->stage_in, &c->stage_in_cap, T.pbc ? TrajRun::cells_at(h.in_bytes) + 24 * (size_t)h.nf : h.in_bytes)) return -1;
+    if (ensure_pinned(c, &c->stage_in, &c->stage_in_cap, T.pbc ? TrajRun::cells_at(h.in_bytes) + T.cell_bytes * (size_t)h.nf : h.in_bytes)) return -1;
     if (h.src) memcpy(c->stage_in, h.src, h.in_bytes);
     else if (!pread_all(T.io.in.fd, c->stage_in, h.in_bytes, T.io.in_header + (long long)T.stride * h.f0))
         return ctx_fail(c, "could not read frames %lld..%lld of the frame file", h.f0, h.f0 + h.nf - 1);
@@ -516,8 +549,9 @@ int shard_read(TrajRun &T, freesasa_gpu_ctx *c, TrajShard &h)
         if (bad >= 0) return ctx_fail(c, "frame %lld of the DCD file is damaged: a record marker is not what the header implies", h.f0 + bad);
         if (T.pbc) {
             char why[160];
-            const long long odd = dcd_cells(T.io.dcd, (const char *)c->stage_in, h.nf, T.pbc_cut,
-                                            (double *)((char *)c->stage_in + TrajRun::cells_at(h.in_bytes)), why, sizeof why);
+            double *cells = (double *)((char *)c->stage_in + TrajRun::cells_at(h.in_bytes));
+            const long long odd = T.io.tri ? dcd_cells_tri(T.io.dcd, (const char *)c->stage_in, h.nf, T.pbc_cut, cells, why, sizeof why)
+                                           : dcd_cells(T.io.dcd, (const char *)c->stage_in, h.nf, T.pbc_cut, cells, why, sizeof why);
             if (odd >= 0) return ctx_fail(c, "frame %lld of the DCD file: %s", h.f0 + odd, why);
         }
     }
@@ -533,7 +567,7 @@ int shard_upload(TrajRun &T, TrajLane &L, const TrajShard &h)
     const bool f32 = T.io.in_f32 != 0;
     void *d_in = T.gather || T.dcd ? c->g_xyz.p : (f32 ? c->h_counts.p : c->h_xyz.p);
     /* (periodic images: the shard's cell edges behind its bytes, in the same copy) */
-    const size_t up_bytes = T.pbc ? TrajRun::cells_at(h.in_bytes) + 24 * (size_t)h.nf : h.in_bytes;
+    const size_t up_bytes = T.pbc ? TrajRun::cells_at(h.in_bytes) + T.cell_bytes * (size_t)h.nf : h.in_bytes;
     if (hipMemcpyAsync(d_in, h.src, up_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "host-to-device copy failed");
     L.ta.n_frames = h.nf;
     if (T.dcd) {
@@ -567,7 +601,7 @@ int shard_compute(TrajRun &T, TrajLane &L, TrajShard &h)
     /* periodic images: the compact frames expanded by their cells, the engine on the expanded shard (radii per atom, offsets
        that vary), the real atoms' areas and totals collected where the plain path puts them (gpu_periodic.hip) */
     const size_t at = TrajRun::cells_at(h.in_bytes);
-    const int rb = T.pbc ? periodic_resident(c, T.s.alg, (double *)c->h_xyz.p, (double *)c->h_radii.p, T.offs.data(), h.nf, (int)T.n,
+    const int rb = T.pbc ? (T.io.tri ? periodic_resident_tri : periodic_resident)(c, T.s.alg, (double *)c->h_xyz.p, (double *)c->h_radii.p, T.offs.data(), h.nf, (int)T.n,
                                              (const double *)((const char *)h.src + at), (const double *)((const char *)c->g_xyz.p + at),
                                              T.s.probe, T.s.resolution, T.s.alg == 1 ? T.tp.data() : nullptr, (double *)c->h_sasa.p,
                                              (double *)c->h_totals.p, nullptr)
@@ -794,12 +828,12 @@ extern "C" int freesasa_gpu_trajectory_topology(const double *xyz_frames, int n_
    files byte for byte.  With a topology, in front of the line's end, what its outputs depend on: digests of the index, of
    residue boundaries + classes + backbone flags, of the selection set's program, and which result files the run writes; with
    chain groups, behind that, a digest of the group count and the ids.  A DCD run: bit 2 in the f32= word and the byte of
-   frame 0 as header_bytes=; a raw run's line is what it was.  Periodic images: bit 3 in the f32= word. */
+   frame 0 as header_bytes=; a raw run's line is what it was.  Periodic images: bit 3 in the f32= word, triclinic cells: bit 4. */
 static int traj_done_head(char *head, size_t cap, const TrajSpec &s, const TrajIO &io, const struct stat &st)
 {
     int len = snprintf(head, cap, "freesasa_amd trajectory done-list v2 n_atoms=%d n_frames=%lld frames_per_batch=%d alg=%d resolution=%d probe=%.17g f32=%d "
                        "header_bytes=%lld frames_size=%lld frames_mtime=%lld.%09ld radii=%016llx\n",
-                       s.n_atoms, s.n_frames, s.frames_per_batch, s.alg, s.resolution, s.probe, io.in_f32 | (io.out_f32() << 1) | (io.in_dcd ? FREESASA_GPU_FRAMES_DCD : 0) | (io.pbc ? FREESASA_GPU_FRAMES_PBC : 0), io.in_header, (long long)st.st_size,
+                       s.n_atoms, s.n_frames, s.frames_per_batch, s.alg, s.resolution, s.probe, io.in_f32 | (io.out_f32() << 1) | (io.in_dcd ? FREESASA_GPU_FRAMES_DCD : 0) | (io.pbc ? FREESASA_GPU_FRAMES_PBC : 0) | (io.tri ? FREESASA_GPU_FRAMES_TRICLINIC : 0), io.in_header, (long long)st.st_size,
                        (long long)st.st_mtim.tv_sec, (long)st.st_mtim.tv_nsec, fnv1a(s.radii, 8 * (size_t)s.n_atoms));
     const TrajTopo *tp = s.topo;
     if (tp && len > 0 && len < (int)cap) {
@@ -833,6 +867,8 @@ static int trajectory_file_run(const char *frames_path, int frames_f32, long lon
     const long long frame_atoms = s.topo ? s.topo->frame_atoms : s.n_atoms;
     if ((frames_f32 & FREESASA_GPU_FRAMES_PBC) && !(frames_f32 & FREESASA_GPU_FRAMES_DCD))
         return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) needs bit 2 (a DCD file): raw frame files carry no cell");
+    if ((frames_f32 & FREESASA_GPU_FRAMES_TRICLINIC) && !(frames_f32 & FREESASA_GPU_FRAMES_PBC))
+        return set_err(err_out, err_len, "bit 4 of frames_f32 (triclinic cells) needs bit 3 (periodic images) and bit 2 (a DCD file)");
     if (frames_f32 & FREESASA_GPU_FRAMES_DCD) {
         /* a DCD file says for itself where its frames are and what they are: before a device is touched or an output file opened */
         if (header_bytes != 0) return set_err(err_out, err_len, "header_bytes must be 0 with a DCD file: the byte of its first frame comes from its header");
@@ -847,6 +883,7 @@ static int trajectory_file_run(const char *frames_path, int frames_f32, long lon
         if (frames_f32 & FREESASA_GPU_FRAMES_PBC) {
             if (!io.dcd.has_cell) return set_err(err_out, err_len, "periodic images need a DCD file with a unit-cell record per frame: this one has none");
             io.pbc = true;
+            io.tri = (frames_f32 & FREESASA_GPU_FRAMES_TRICLINIC) != 0;
         }
     }
     if (traj_check_args(s, nullptr, err_out, err_len)) return -1;
@@ -937,6 +974,8 @@ extern "C" int freesasa_gpu_trajectory_file_groups(const char *frames_path, int 
                                                    long long *frames_total_out, char *err_out, int err_len)
 {
     if (err_out && err_len > 0) err_out[0] = 0;
+    if (frames_f32 & FREESASA_GPU_FRAMES_TRICLINIC)
+        return set_err(err_out, err_len, "bit 4 of frames_f32 (triclinic cells) is not offered with chain groups: an isolated group among periodic images is not defined");
     if (frames_f32 & FREESASA_GPU_FRAMES_PBC)
         return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) is not offered with chain groups: an isolated group among periodic images is not defined");
     return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,

@@ -985,6 +985,28 @@ __global__ __launch_bounds__(PBC_B) void k_pbc_collect(PbcArgs a)
 {
     pbc_collect_atom(a, (int64_t)blockIdx.x * PBC_B + threadIdx.x);
 }
+/* ... in a triclinic cell (pbc_tri_kernels.h) */
+__global__ __launch_bounds__(PBC_B) void k_pbc_tri_count(PbcTriArgs a)
+{
+    __shared__ double lds_d[PBC_B];
+    __shared__ int lds_w[PBC_WAVES];
+    pbc_tri_count_struct(a, lds_d, lds_w, blockIdx.x, threadIdx.x);
+}
+__global__ __launch_bounds__(PBC_B) void k_pbc_tri_emit(PbcTriArgs a)
+{
+    pbc_tri_emit_atom(a, (int64_t)blockIdx.x * PBC_B + threadIdx.x);
+}
+hipError_t kl_pbc_tri_count(const PbcTriArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_pbc_tri_count, dim3((unsigned)a.b.n_structs), dim3(PBC_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_pbc_tri_emit(const PbcTriArgs &a, hipStream_t st)
+{
+    if (a.b.n_atoms == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_pbc_tri_emit, dim3((unsigned)((a.b.n_atoms + PBC_B - 1) / PBC_B)), dim3(PBC_B), 0, st, a);
+    return hipGetLastError();
+}
 hipError_t kl_pbc_count(const PbcArgs &a, hipStream_t st)
 {
     hipLaunchKernelGGL(k_pbc_count, dim3((unsigned)a.n_structs), dim3(PBC_B), 0, st, a);

@@ -2,7 +2,10 @@
  * gpu_periodic.hip — periodic images (include/freesasa_gpu.h, freesasa_gpu_periodic_dev / freesasa_gpu_calc_periodic; the
  * FREESASA_GPU_FRAMES_PBC bit of the trajectory file drivers): every structure with an orthorhombic cell of its own, the
  * SASA of its atoms among their periodic images.  Host code; the kernels are in gpu_kernels.hip (phase functions and the
- * definition: pbc_kernels.h).
+ * definition: pbc_kernels.h).  The same pipeline serves triclinic cells (freesasa_gpu_periodic_triclinic_dev /
+ * freesasa_gpu_calc_periodic_triclinic, FREESASA_GPU_FRAMES_TRICLINIC; pbc_tri_kernels.h): a cell is then nine doubles on the
+ * device - its six numbers and the three widths the host made of them (cell.c) -, count and emit are the triclinic kernels
+ * and the check is of the widths; everything else, the orthorhombic path included, is what it was.
  *
  *   1. count      k_pbc_count: per atom the base of its images, per structure the image count and the max radius; those
  *                 come back to the host (the engine takes host offsets): the call's one synchronisation beyond run_batch's
@@ -46,6 +49,28 @@ int periodic_cell_bad(const double *cell, double c)
         if (!(cell[a] >= c)) return a + 1;
     }
     return 0;
+}
+
+/* (engine_internal.h; periodic_cell6_bad is in cell.c) */
+int periodic_widths_bad(const double *widths, double c)
+{
+    for (int a = 0; a < 3; ++a)
+        if (!(widths[a] >= c)) return a + 1;
+    return 0;
+}
+static const char *const CELL6_NAME[6] = {"ax", "bx", "by", "cx", "cy", "cz"};
+/* the messages of a refused triclinic cell: its shape (bad: periodic_cell6_bad's) ... */
+static void cell6_msg(char *msg, size_t len, int s, const double *h, int bad)
+{
+    const int k = bad < 0 ? -bad - 1 : bad - 1;
+    if (bad < 0) snprintf(msg, len, "structure %d: entry %s of its cell is not finite", s, CELL6_NAME[k]);
+    else snprintf(msg, len, "structure %d: entry %s of its cell is %.17g: ax, by and cz must be > 0", s, CELL6_NAME[k], h[k]);
+}
+/* ... and a width (bad: periodic_widths_bad's) */
+static void width_msg(char *msg, size_t len, int s, const double *widths, int bad, double cut)
+{
+    snprintf(msg, len, "structure %d: width %c of its cell is %.17g, smaller than c = 2 (max radius + probe) = %.17g: "
+                       "first-shell images do not suffice", s, "abc"[bad - 1], widths[bad - 1], cut);
 }
 
 static int cell_fail(freesasa_gpu_ctx *c, int s, const double *cell, int bad, double cut)
@@ -94,36 +119,38 @@ static int compact_chunks(freesasa_gpu_ctx *c, const int64_t *offsets, int n_str
     return 0;
 }
 
-/* (engine_internal.h) */
-int periodic_resident(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
-                      int n_fixed, const double *cells, const double *d_cells, double probe, int resolution, const double *unit_points,
-                      double *d_sasa, double *d_totals, int64_t *images_out)
+/* periodic_resident (tri false: cells [3 n_structs]) and periodic_resident_tri (tri: cells [9 n_structs]) */
+static int resident(freesasa_gpu_ctx *c, bool tri, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
+                    int n_fixed, const double *cells, const double *d_cells, double probe, int resolution, const double *unit_points,
+                    double *d_sasa, double *d_totals, int64_t *images_out)
 {
+    const size_t W = tri ? PBC_TRI_CELL : 3; /* doubles per cell */
     const int64_t n = offsets[n_structs];
     if (n <= 0) return ctx_fail(c, "empty batch");
     if (n > (int64_t)1 << 30) return ctx_fail(c, "the expanded batch is too large (max 2^30 atoms and images per call)");
     const size_t ns = (size_t)n_structs;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    /* offsets [ns + 1] | expanded offsets [ns + 1] | cells [3 ns] | image counts [ns] | max radii [ns] */
-    const size_t o_eoff = 8 * (ns + 1), o_cell = 2 * o_eoff, o_img = o_cell + 24 * ns, o_rmax = o_img + 8 * ns, meta_bytes = o_rmax + 8 * ns;
+    /* offsets [ns + 1] | expanded offsets [ns + 1] | cells [W ns] | image counts [ns] | max radii [ns] */
+    const size_t o_eoff = 8 * (ns + 1), o_cell = 2 * o_eoff, o_img = o_cell + 8 * W * ns, o_rmax = o_img + 8 * ns, meta_bytes = o_rmax + 8 * ns;
     if (ensure(c, c->p_meta, meta_bytes) || ensure(c, c->p_ibase, 4 * (size_t)n)) return -1;
     char *meta = (char *)c->p_meta.p;
     PipeArgs ta; /* (the totals' chunk table first: it goes up with copies that wait for the stream when the offsets are new) */
     if (d_totals && compact_chunks(c, offsets, n_structs, ta)) return -1;
-    PbcArgs pa;
-    memset(&pa, 0, sizeof pa);
+    PbcTriArgs pt;
+    memset(&pt, 0, sizeof pt);
+    PbcArgs &pa = pt.b;
     pa.xyz = d_xyz; pa.radii = d_radii; pa.n_structs = n_structs; pa.n_atoms = n; pa.probe = probe;
     pa.n_fixed = n_fixed > 0 ? n_fixed : 0; pa.shared_radii = n_fixed > 0;
     pa.offsets = n_fixed > 0 ? nullptr : (const int64_t *)meta;
-    pa.cells = d_cells ? d_cells : (const double *)(meta + o_cell);
+    (tri ? pt.cell9 : pa.cells) = d_cells ? d_cells : (const double *)(meta + o_cell);
     pa.ibase = (int *)c->p_ibase.p; pa.n_img = (int64_t *)(meta + o_img); pa.rmax = (double *)(meta + o_rmax);
 
     /* 1. count; the image counts and max radii back (the one synchronisation beyond run_batch's) */
     std::vector<int64_t> back(2 * ns), eoff(ns + 1); /* (declared before the copies that use them: they outlive the stream's reads) */
     if (n_fixed <= 0) HIP_TRY(c, hipMemcpyAsync(meta, offsets, 8 * (ns + 1), hipMemcpyHostToDevice, st));
-    if (!d_cells) HIP_TRY(c, hipMemcpyAsync(meta + o_cell, cells, 24 * ns, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, kl_pbc_count(pa, st));
+    if (!d_cells) HIP_TRY(c, hipMemcpyAsync(meta + o_cell, cells, 8 * W * ns, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, tri ? kl_pbc_tri_count(pt, st) : kl_pbc_count(pa, st));
     HIP_TRY(c, hipMemcpyAsync(back.data(), meta + o_img, 16 * ns, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
 
@@ -135,7 +162,12 @@ int periodic_resident(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const d
             double rmax;
             memcpy(&rmax, &back[ns + s], 8);
             const double cut = 2.0 * (rmax + probe);
-            const int bad = periodic_cell_bad(cells + 3 * s, cut);
+            const int bad = tri ? periodic_widths_bad(cells + W * s + 6, cut) : periodic_cell_bad(cells + 3 * s, cut);
+            if (bad && tri) {
+                char msg[240];
+                width_msg(msg, sizeof msg, (int)s, cells + W * s + 6, bad, cut);
+                return ctx_fail(c, "%s", msg);
+            }
             if (bad) return cell_fail(c, (int)s, cells + 3 * s, bad, cut);
         }
         if (back[s] < 0 || back[s] > 26 * ns_atoms) return ctx_fail(c, "structure %d: bad image count from the device", (int)s);
@@ -150,7 +182,7 @@ int periodic_resident(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const d
     if (ensure(c, c->p_xyz, 24 * (size_t)N) || ensure(c, c->p_radii, 8 * (size_t)N) || ensure(c, c->p_sasa, 8 * (size_t)N)) return -1;
     pa.eoff = (const int64_t *)(meta + o_eoff); pa.exyz = (double *)c->p_xyz.p; pa.eradii = (double *)c->p_radii.p;
     HIP_TRY(c, hipMemcpyAsync(meta + o_eoff, eoff.data(), 8 * (ns + 1), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, kl_pbc_emit(pa, st));
+    HIP_TRY(c, tri ? kl_pbc_tri_emit(pt, st) : kl_pbc_emit(pa, st));
 
     /* 4. the engine on the expanded batch (synchronous: eoff is no longer read when it returns) */
     std::vector<double> tp;
@@ -169,7 +201,33 @@ int periodic_resident(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const d
     return 0;
 }
 
-static int periodic_impl(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets,
+/* (engine_internal.h) */
+int periodic_resident(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
+                      int n_fixed, const double *cells, const double *d_cells, double probe, int resolution, const double *unit_points,
+                      double *d_sasa, double *d_totals, int64_t *images_out)
+{
+    return resident(c, false, alg, d_xyz, d_radii, offsets, n_structs, n_fixed, cells, d_cells, probe, resolution, unit_points, d_sasa, d_totals, images_out);
+}
+int periodic_resident_tri(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
+                          int n_fixed, const double *cells9, const double *d_cells9, double probe, int resolution, const double *unit_points,
+                          double *d_sasa, double *d_totals, int64_t *images_out)
+{
+    return resident(c, true, alg, d_xyz, d_radii, offsets, n_structs, n_fixed, cells9, d_cells9, probe, resolution, unit_points, d_sasa, d_totals, images_out);
+}
+
+/* the six numbers of every structure's cell with their widths behind them: cells9 [9 n_structs] (a structure without atoms,
+   whose cell is not checked, may get widths that are not numbers: no thread reads them for an atom) */
+static void cells9_make(const double *cells6, int n_structs, std::vector<double> &cells9)
+{
+    cells9.resize((size_t)PBC_TRI_CELL * (size_t)n_structs);
+    for (size_t s = 0; s < (size_t)n_structs; ++s) {
+        memcpy(&cells9[PBC_TRI_CELL * s], cells6 + 6 * s, 48);
+        (void)freesasa_gpu_cell_widths(cells6 + 6 * s, &cells9[PBC_TRI_CELL * s + 6]);
+    }
+}
+
+/* tri: cells is [6 n_structs] */
+static int periodic_impl(freesasa_gpu_ctx *c, bool tri, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets,
                          int n_structs, const double *cells, double probe, int resolution, double *d_sasa, double *d_totals,
                          int64_t *images_out)
 {
@@ -181,33 +239,60 @@ static int periodic_impl(freesasa_gpu_ctx *c, int alg, const double *d_xyz, cons
     if (offsets[0] != 0) return ctx_fail(c, "offsets[0] must be 0");
     for (int s = 0; s < n_structs; ++s)
         if (offsets[s + 1] < offsets[s]) return ctx_fail(c, "offsets must be non-decreasing");
+    /* the shape of every cell that has atoms, before the device is touched */
+    std::vector<double> cells9;
     for (int s = 0; s < n_structs; ++s) {
-        const int bad = offsets[s + 1] > offsets[s] ? periodic_cell_bad(cells + 3 * (size_t)s, 0.0) : 0;
-        if (bad < 0) return cell_fail(c, s, cells + 3 * (size_t)s, bad, 0.0);
+        if (offsets[s + 1] == offsets[s]) continue;
+        if (tri) {
+            const int bad = periodic_cell6_bad(cells + 6 * (size_t)s);
+            if (bad) {
+                char msg[240];
+                cell6_msg(msg, sizeof msg, s, cells + 6 * (size_t)s, bad);
+                return ctx_fail(c, "%s", msg);
+            }
+        } else {
+            const int bad = periodic_cell_bad(cells + 3 * (size_t)s, 0.0);
+            if (bad < 0) return cell_fail(c, s, cells + 3 * (size_t)s, bad, 0.0);
+        }
     }
-    if (periodic_resident(c, alg, d_xyz, d_radii, offsets, n_structs, 0, cells, nullptr, probe, resolution, nullptr, d_sasa, d_totals, images_out))
+    if (tri) cells9_make(cells, n_structs, cells9);
+    if (resident(c, tri, alg, d_xyz, d_radii, offsets, n_structs, 0, tri ? cells9.data() : cells, nullptr, probe, resolution, nullptr, d_sasa, d_totals, images_out))
         return -1;
     HIP_TRY(c, hipStreamSynchronize(c->stream)); /* (the call is synchronous) */
     return 0;
+}
+
+static int periodic_dev(freesasa_gpu_ctx *c, bool tri, int alg, const double *d_xyz, const double *d_radii,
+                        const int64_t *offsets, int n_structs, const double *cells, double probe_radius,
+                        int resolution, double *d_sasa, double *d_totals, int64_t *images_out)
+{
+    if (!c) return -1;
+    if (freesasa_gpu_wait(c)) return -1; /* (batches submitted asynchronously come first) */
+    return guarded_ctx(c, [&]() -> int {
+        const int rc = periodic_impl(c, tri, alg, d_xyz, d_radii, offsets, n_structs, cells, probe_radius, resolution, d_sasa, d_totals, images_out);
+        if (rc) (void)hipStreamSynchronize(c->stream);
+        return rc;
+    });
 }
 
 extern "C" int freesasa_gpu_periodic_dev(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii,
                                          const int64_t *offsets, int n_structs, const double *cells, double probe_radius,
                                          int resolution, double *d_sasa, double *d_totals, int64_t *images_out)
 {
-    if (!c) return -1;
-    if (freesasa_gpu_wait(c)) return -1; /* (batches submitted asynchronously come first) */
-    return guarded_ctx(c, [&]() -> int {
-        const int rc = periodic_impl(c, alg, d_xyz, d_radii, offsets, n_structs, cells, probe_radius, resolution, d_sasa, d_totals, images_out);
-        if (rc) (void)hipStreamSynchronize(c->stream);
-        return rc;
-    });
+    return periodic_dev(c, false, alg, d_xyz, d_radii, offsets, n_structs, cells, probe_radius, resolution, d_sasa, d_totals, images_out);
+}
+extern "C" int freesasa_gpu_periodic_triclinic_dev(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii,
+                                                   const int64_t *offsets, int n_structs, const double *cells6, double probe_radius,
+                                                   int resolution, double *d_sasa, double *d_totals, int64_t *images_out)
+{
+    return periodic_dev(c, true, alg, d_xyz, d_radii, offsets, n_structs, cells6, probe_radius, resolution, d_sasa, d_totals, images_out);
 }
 
-extern "C" int freesasa_gpu_calc_periodic(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
-                                          const double *cells, int alg, double probe_radius, int resolution,
-                                          double *sasa_out, double *totals_out, int64_t *images_out,
-                                          int device, char *err_out, int err_len)
+/* tri: cells is [6 n_structs] */
+static int calc_periodic(bool tri, const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
+                         const double *cells, int alg, double probe_radius, int resolution,
+                         double *sasa_out, double *totals_out, int64_t *images_out,
+                         int device, char *err_out, int err_len)
 {
     if (err_out && err_len > 0) err_out[0] = 0;
     if (!xyz || !radii || !offsets || !cells || !sasa_out) return set_err(err_out, err_len, "null argument");
@@ -221,8 +306,24 @@ extern "C" int freesasa_gpu_calc_periodic(const double *xyz, const double *radii
     for (int s = 0; s < n_structs; ++s) {
         const int64_t ns_atoms = offsets[s + 1] - offsets[s];
         if (ns_atoms == 0) continue;
-        const double *cell = cells + 3 * (size_t)s;
         const double cut = periodic_cutoff(radii + offsets[s], ns_atoms, probe_radius);
+        if (tri) {
+            const double *h = cells + 6 * (size_t)s;
+            char msg[240];
+            double widths[3];
+            int bad = periodic_cell6_bad(h);
+            if (bad) {
+                cell6_msg(msg, sizeof msg, s, h, bad);
+                return set_err(err_out, err_len, msg);
+            }
+            (void)freesasa_gpu_cell_widths(h, widths);
+            if ((bad = periodic_widths_bad(widths, cut)) != 0) {
+                width_msg(msg, sizeof msg, s, widths, bad, cut);
+                return set_err(err_out, err_len, msg);
+            }
+            continue;
+        }
+        const double *cell = cells + 3 * (size_t)s;
         const int bad = periodic_cell_bad(cell, cut);
         if (bad) {
             char msg[240];
@@ -246,8 +347,8 @@ extern "C" int freesasa_gpu_calc_periodic(const double *xyz, const double *radii
     h.ns = n_structs; h.n = n; h.off = offsets; h.xyz = xyz; h.radii = radii;
     const int rc = [&]() -> int {
         if (chunk_size(b, c, h) || chunk_upload(c, h)) return -1;
-        if (freesasa_gpu_periodic_dev(c, alg, (const double *)c->h_xyz.p, (const double *)c->h_radii.p, offsets, n_structs, cells,
-                                      probe_radius, resolution, (double *)c->h_sasa.p, totals_out ? (double *)c->h_totals.p : nullptr, images_out))
+        if (periodic_dev(c, tri, alg, (const double *)c->h_xyz.p, (const double *)c->h_radii.p, offsets, n_structs, cells,
+                         probe_radius, resolution, (double *)c->h_sasa.p, totals_out ? (double *)c->h_totals.p : nullptr, images_out))
             return -1;
         if (hipMemcpyAsync(sasa_out, c->h_sasa.p, 8 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             (totals_out && hipMemcpyAsync(totals_out, c->h_totals.p, 8 * (size_t)n_structs, hipMemcpyDeviceToHost, c->stream) != hipSuccess))
@@ -257,4 +358,19 @@ extern "C" int freesasa_gpu_calc_periodic(const double *xyz, const double *radii
     }();
     return rc ? set_err(err_out, err_len, chunk_failed(b, c)) : 0;
     });
+}
+
+extern "C" int freesasa_gpu_calc_periodic(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
+                                          const double *cells, int alg, double probe_radius, int resolution,
+                                          double *sasa_out, double *totals_out, int64_t *images_out,
+                                          int device, char *err_out, int err_len)
+{
+    return calc_periodic(false, xyz, radii, offsets, n_structs, cells, alg, probe_radius, resolution, sasa_out, totals_out, images_out, device, err_out, err_len);
+}
+extern "C" int freesasa_gpu_calc_periodic_triclinic(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
+                                                    const double *cells6, int alg, double probe_radius, int resolution,
+                                                    double *sasa_out, double *totals_out, int64_t *images_out,
+                                                    int device, char *err_out, int err_len)
+{
+    return calc_periodic(true, xyz, radii, offsets, n_structs, cells6, alg, probe_radius, resolution, sasa_out, totals_out, images_out, device, err_out, err_len);
 }

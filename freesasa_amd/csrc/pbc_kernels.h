@@ -33,7 +33,8 @@
  * One workgroup per structure suits trajectory shards of hundreds of frames and batches of many structures; for ONE
  * structure of 1e6 atoms it is slow (a single CU walks it).  That is accepted: there is no multi-workgroup scan here.
  *
- * Not offered: triclinic cells; cells smaller than c; a cell for raw fp32 / fp64 frame files or the memory trajectory
+ * Triclinic cells: pbc_tri_kernels.h, beside this file (nothing here changes for them).
+ * Not offered: cells smaller than c; a cell for raw fp32 / fp64 frame files or the memory trajectory
  * entries (callers pass frames as a batch to freesasa_gpu_calc_periodic); chain groups with periodic images; skipping the
  * area computation of the image atoms (their areas are computed and dropped); file or cache sweeps (a PDB CRYST1 record is a
  * crystallographic cell with symmetry: another feature).

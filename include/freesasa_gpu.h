@@ -416,9 +416,9 @@ int freesasa_gpu_calc_batch(const double *xyz, const double *radii, const int64_
    freesasa_gpu_periodic_dev: d_xyz, d_radii, d_sasa [offsets[n_structs]], d_totals [n_structs] (may be NULL) on the device,
    offsets and cells on the host; synchronous.  freesasa_gpu_calc_periodic: host arrays, pooled context (device -1: the
    current one); the cells are checked against the radii before a device is touched.  Returns 0 / -1.
-   Not offered: triclinic cells, cells smaller than c, skipping the area computation of the image atoms (their areas are
+   Not offered: cells smaller than c, skipping the area computation of the image atoms (their areas are
    computed and dropped), periodic images in the file or cache sweeps (a PDB CRYST1 record is a crystallographic cell with
-   symmetry).  Trajectories: FREESASA_GPU_FRAMES_PBC below. */
+   symmetry).  Triclinic cells: the two entries below these.  Trajectories: FREESASA_GPU_FRAMES_PBC below. */
 int freesasa_gpu_periodic_dev(freesasa_gpu_ctx *ctx, int alg, const double *d_xyz, const double *d_radii,
                               const int64_t *offsets, int n_structs, const double *cells /* host, [3 n_structs] */,
                               double probe_radius, int resolution, double *d_sasa, double *d_totals,
@@ -427,6 +427,54 @@ int freesasa_gpu_calc_periodic(const double *xyz, const double *radii, const int
                                const double *cells, int alg, double probe_radius, int resolution,
                                double *sasa_out, double *totals_out, int64_t *images_out,
                                int device, char *err_out, int err_len);
+
+/* Periodic images in a TRICLINIC cell: every structure s has a cell of six numbers h = cells6[6 s .. 6 s + 5] =
+   (ax, bx, by, cx, cy, cz), the lower-triangular box matrix with rows a = (ax, 0, 0), b = (bx, by, 0), c = (cx, cy, cz) - the
+   form GROMACS, LAMMPS and OpenMM hold (truncated octahedra, rhombic dodecahedra, hexagonal prisms, crystals).  Everything is
+   fp64, every operation rounded on its own, in exactly the order written.  With c = 2 (max radius of the structure +
+   probe_radius):
+     widths        d_c = cz;  d_b = by * (cz / sqrt(cy*cy + cz*cz));  t = bx*cy - by*cx;
+                   d_a = ax * ((by*cz) / sqrt(((by*cz)*(by*cz) + (bx*cz)*(bx*cz)) + t*t))
+                   (the distances between opposite faces; made once per structure on the host, freesasa_gpu_cell_widths; for a
+                   right-angled cell the edges exactly)
+     requirement   all six numbers finite, ax, by, cz > 0 and every width >= c.  Shifts in {-1, 0, 1}^3 then suffice: two points
+                   whose k-th fractional coordinates differ by D are at least |D| d_k apart, and the neighbour predicate is
+                   strict.  Anything else is refused (-1 with a message that names the structure and the entry or width), never
+                   approximated.  The cell need not be reduced.
+     fractional    of a point p:  fc = p_z / cz;  fb = (p_y - fc*cy) / by;  fa = ((p_x - fc*cx) - fb*bx) / ax
+     wrap          with n = floor(f) of the input atom:
+                   w_x = ((x - nc*cx) - nb*bx) - na*ax;  w_y = (y - nc*cy) - nb*by;  w_z = z - nc*cz
+     images        g = the fractional coordinates of w, recomputed with the same formulas (not f - n).  Axis k admits shift 0
+                   always, +1 when g_k * d_k < c, -1 when (1.0 - g_k) * d_k < c; an atom's images are the admitted
+                   (sa, sb, sc) != (0, 0, 0), 0 to 26 per atom, with the atom's radius, at
+                   x = ((w_x + sc*cx) + sb*bx) + sa*ax;  y = (w_y + sc*cy) + sb*by;  z = w_z + sc*cz
+     expanded      the wrapped atoms in input order, then the images by atom and, within an atom, by 9 (sa+1) + 3 (sb+1) + (sc+1)
+     result        as for orthorhombic cells: atom i's area is the engine's area of atom i of the expanded structure, totals over
+                   the real atoms formed like every total of the engine
+   On cells (Lx, 0, Ly, 0, 0, Lz) this is the definition above (the tests hold both entries to the same bytes).  Arguments,
+   limits, images_out and return values are those of freesasa_gpu_periodic_dev / freesasa_gpu_calc_periodic, whose behaviour,
+   messages and refusals do not change; the expansion is made on the device (pbc_tri_kernels.h).
+   Not offered: cells with a width below c, skipping the area computation of the image atoms, chain groups with images, a
+   PDB CRYST1 record. */
+int freesasa_gpu_periodic_triclinic_dev(freesasa_gpu_ctx *ctx, int alg, const double *d_xyz, const double *d_radii,
+                                        const int64_t *offsets, int n_structs, const double *cells6 /* host, [6 n_structs] */,
+                                        double probe_radius, int resolution, double *d_sasa, double *d_totals,
+                                        int64_t *images_out /* host, [n_structs], may be NULL */);
+int freesasa_gpu_calc_periodic_triclinic(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
+                                         const double *cells6, int alg, double probe_radius, int resolution,
+                                         double *sasa_out, double *totals_out, int64_t *images_out,
+                                         int device, char *err_out, int err_len);
+/* The three widths (d_a, d_b, d_c) of a cell as defined above.  Returns 0, or -1 (widths_out then holds NaN) when an entry is
+   not finite or ax, by or cz is not positive.  Touches no device. */
+int freesasa_gpu_cell_widths(const double cell6[6], double widths_out[3]);
+/* A CHARMM / NAMD / OpenMM unit-cell record as DCD files hold it - rec = A, gamma, B, beta, alpha, C - to the six numbers.
+   An angle field v with |v| <= 1 is a cosine; otherwise it is degrees and must lie in (0, 180).  |v| <= 1e-6 and
+   |v - 90| <= 1e-4 give cosine 0 EXACTLY (the two cases the orthorhombic decoder of FREESASA_GPU_FRAMES_PBC accepts); any other
+   degree value gives cos(v pi / 180).  Then ax = A, bx = B cosg, by = B sqrt(1 - cosg cosg), cx = C cosb,
+   cy = C ((cosa - cosb cosg) / sqrt(1 - cosg cosg)), cz = sqrt((C*C - cx*cx) - cy*cy); right angles give (A, 0, B, 0, 0, C)
+   exactly.  Returns 0, or -1 with the reason in why (may be NULL): an edge that is not finite, an angle field that is neither,
+   angles that span no cell (cz^2 <= 0 or not a number).  Touches no device. */
+int freesasa_gpu_cell_from_dcd(const double rec[6], double cell6_out[6], char *why, int why_len);
 
 /* Trajectory drivers (BASELINE configs[4]): frames of the SAME n_atoms atoms, radii constant.
    Frames are independent structures; a SHARD = frames_per_batch frames (<= 0: about 1.25e6 atoms) goes through the
@@ -481,12 +529,21 @@ int freesasa_gpu_calc_periodic(const double *xyz, const double *radii, const int
    DCD file without a cell record, freesasa_gpu_trajectory_file_groups (an isolated group among periodic images is not
    defined).  The done-list's f32= word carries bit 3: a periodic run's list is refused by a run without the bit and the other
    way round.  A cell no atom comes within c of changes nothing: such a run's files are those of the run without the bit,
-   byte for byte.  Not offered: triclinic cells, cells smaller than c, a cell for raw frame files or the memory entries,
-   chain groups with periodic images. */
+   byte for byte.  Without bit 4 a cell that is not orthorhombic is refused as said above.
+
+   Triclinic cells: with bit 4 (FREESASA_GPU_FRAMES_TRICLINIC) beside bits 2 and 3 every frame's record is decoded by
+   freesasa_gpu_cell_from_dcd and the frame computed as freesasa_gpu_calc_periodic_triclinic defines it.  A record that
+   decodes to no cell, an edge that is not positive or a width below the run's c ends the run like a damaged frame
+   ("frame K of the DCD file: ..."; the shard is not listed).  A shard's cells and widths go up behind its bytes, 72 bytes
+   per frame instead of 24, still one copy.  Bit 4 without bits 2 and 3, and freesasa_gpu_trajectory_file_groups with it,
+   are refused before a device is touched or an output file opened.  The done-list's f32= word carries bit 4: runs with and
+   without it refuse each other's lists.  A right-angled file gives the files of the run without bit 4, byte for byte.
+   Not offered: cells smaller than c, a cell for raw frame files or the memory entries, chain groups with periodic images. */
 #define FREESASA_GPU_FRAMES_F32 1     /* frames_f32 bit 0: raw fp32 frames (input format) */
 #define FREESASA_GPU_FRAMES_OUT_F32 2 /* bit 1: per-atom (and isolated) areas written as fp32 (output format) */
 #define FREESASA_GPU_FRAMES_DCD 4     /* bit 2: frames_path is a DCD trajectory */
 #define FREESASA_GPU_FRAMES_PBC 8     /* bit 3: with bit 2, every frame among the periodic images of its cell record */
+#define FREESASA_GPU_FRAMES_TRICLINIC 16 /* bit 4: with bits 2 and 3, the cell record decoded as a triclinic cell */
 
 /* The header of a DCD file.  Every integer of the file is an int32 in the file's byte order; records lie between two equal
    byte counts:  [84 | "CORD" | 20 control words | 84]  [m | NTITLE | 80 NTITLE bytes | m]  [4 | NATOM | 4], then per frame

@@ -28,10 +28,17 @@ on two DCD files with a unit-cell record:
     filled-pbc    the same call with pbc=True
 each line with images_per_atom (calc_periodic on frame 0; null where the library has no periodic entry).  --pbc-arms off runs the
 two arms without the bit alone and passes no pbc keyword: the form an older library's wrapper takes, for a baseline.
+With --triclinic beside --pbc (FREESASA_GPU_FRAMES_TRICLINIC) three arms more, interleaved with the others:
+    solvated-tri  solvated-pbc with triclinic=True: the same right-angled records through the general geometry (the totals file
+    filled-tri    must be that of the arm without the bit, byte for byte) - its price at an equal image count
+    octa-tri      the frames of `filled` in a truncated octahedron of the same volume as filled's cell (box vectors of length d
+                  at GROMACS's angles, the record's angles as cosines 1/3, -1/3, 1/3), pbc=True, triclinic=True; images_per_atom
+                  from calc_periodic_triclinic on frame 0.  The globule was not built for that cell: where its corners wrap onto
+                  its faces atoms overlap, which a cost measurement can live with.
 
 One JSON line per arm: atom-frames/s counted in SOLUTE atoms and in frame atoms, the median and the spread of --reps runs.
 
-    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd] [--pbc [--pbc-arms all|off]]
+    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd] [--pbc [--pbc-arms all|off] [--triclinic]]
 
 For the kernel times: `rocprofv3 --kernel-trace --stats -- python tools/traj_topology_bench.py --reps 1 --arms all`
 (k_traj_gather / k_traj_residues / k_traj_class / k_traj_sel are the topology's kernels, k_traj_group_* the groups')."""
@@ -99,9 +106,10 @@ def make_frames(scratch, xyz, n_frames, dcd=False):
     return full, bare, as_dcd
 
 
-def make_pbc_frames(scratch, xyz, n_frames):
+def make_pbc_frames(scratch, xyz, n_frames, octa=False):
     """the two DCD files of --pbc -> (solvated path, its cell, filled path, its cell); coordinates as make_frames draws them,
-    moved so that the cell begins at 0"""
+    moved so that the cell begins at 0.  octa: behind them the path of a third file - filled's frames with the record of a
+    truncated octahedron of filled's volume - and that record"""
     rng = np.random.default_rng(5)
     half = 1.3 * np.abs(xyz).max()
     lo = xyz.min(0) - 0.5 * 2.6 - 0.25
@@ -119,6 +127,17 @@ def make_pbc_frames(scratch, xyz, n_frames):
                     frame = np.concatenate([frame, rng.uniform(0, 2 * half, (n - N_SOLUTE, 3)).astype(np.float32)])
                 fh.write(rec + b"".join(plane + np.ascontiguousarray(frame[:, k]).tobytes() + plane for k in range(3)))
         out += [path, cell]
+    if octa:
+        d = float(np.prod(out[3]) / (4.0 * np.sqrt(3.0) / 9.0)) ** (1.0 / 3.0)     # the volume of GROMACS's cell of vector length d is 4 sqrt(3) / 9 d^3
+        record = np.array([d, 1.0 / 3.0, d, -1.0 / 3.0, 1.0 / 3.0, d])
+        data = bytearray(open(out[2], "rb").read())
+        info = fa.dcd_info(out[2])
+        for f in range(n_frames):
+            struct.pack_into("<6d", data, info.first_frame + f * info.frame_bytes + 4, *record)
+        path = os.path.join(scratch, "octa_pbc.dcd")
+        with open(path, "wb") as fh:
+            fh.write(bytes(data))
+        out += [path, record]
     return out
 
 
@@ -154,6 +173,7 @@ def main():
     ap.add_argument("--dcd", action="store_true", help="time the raw fp32 file against a DCD file of the same frames")
     ap.add_argument("--pbc", action="store_true", help="time the DCD drivers with and without periodic images")
     ap.add_argument("--pbc-arms", default="all", choices=["all", "off"])
+    ap.add_argument("--triclinic", action="store_true", help="with --pbc: the arms of the triclinic bit beside the others")
     args = ap.parse_args()
     scratch = args.scratch or tempfile.mkdtemp(prefix="traj_topology_bench_")
     try:
@@ -178,7 +198,8 @@ def main():
             assert fa.dcd_info(as_dcd).n_frames == args.frames and os.path.getsize(as_dcd) - os.path.getsize(full) == 80 * args.frames + 196
         images = {}
         if args.pbc:
-            solv, solv_cell, fill, fill_cell = make_pbc_frames(scratch, xyz, args.frames)
+            tri = args.triclinic and args.pbc_arms == "all"
+            solv, solv_cell, fill, fill_cell, *octa = make_pbc_frames(scratch, xyz, args.frames, tri)
             arms = {"solvated": lambda: fa.trajectory_file_topology(solv, b, p("t6"), atom_index=index, dcd=True),
                     "filled": lambda: fa.trajectory_file(fill, b.radii, p("t8"), dcd=True)}
             if args.pbc_arms == "all":
@@ -186,6 +207,10 @@ def main():
                         "solvated-pbc": lambda: fa.trajectory_file_topology(solv, b, p("t7"), atom_index=index, dcd=True, pbc=True),
                         "filled": arms["filled"],
                         "filled-pbc": lambda: fa.trajectory_file(fill, b.radii, p("t9"), dcd=True, pbc=True)}
+            if tri:
+                arms.update({"solvated-tri": lambda: fa.trajectory_file_topology(solv, b, p("t10"), atom_index=index, dcd=True, pbc=True, triclinic=True),
+                             "filled-tri": lambda: fa.trajectory_file(fill, b.radii, p("t11"), dcd=True, pbc=True, triclinic=True),
+                             "octa-tri": lambda: fa.trajectory_file(octa[0], b.radii, p("t12"), dcd=True, pbc=True, triclinic=True)})
         names = list(arms) if args.dcd or args.pbc else [a for a in args.arms.split(",") if a in arms]
         runs = {a: [] for a in names}
         for a in names:
@@ -199,18 +224,23 @@ def main():
         if args.pbc and hasattr(fa, "calc_periodic"):    # (behind the timed runs: a batch of another shape leaves its launch history in a pooled context)
             for a, path, cell in (("solvated", solv, solv_cell), ("filled", fill, fill_cell)):
                 k = fa.calc_periodic(first_frame(path, N_SOLUTE), b.radii, [0, N_SOLUTE], [cell])[2]
-                images[a] = images[a + "-pbc"] = float(k[0]) / N_SOLUTE
+                images[a] = images[a + "-pbc"] = images[a + "-tri"] = float(k[0]) / N_SOLUTE
+            if tri:
+                k = fa.calc_periodic_triclinic(first_frame(octa[0], N_SOLUTE), b.radii, [0, N_SOLUTE], [fa.cell_from_dcd(octa[1])])[2]
+                images["octa-tri"] = float(k[0]) / N_SOLUTE
         totals = [np.fromfile(p(k)) for a, k in (("plain", "t0"), ("totals", "t1"), ("all", "t2"), ("groups", "t3"), ("raw", "t1"), ("dcd", "t5")) if a in names]
         assert all(np.array_equal(t, totals[0]) for t in totals)
         if "solvated-pbc" in names:      # no atom of the solute within c of a face: the bit changes nothing; a filled box: it must
             assert images["solvated"] > 0 or np.array_equal(np.fromfile(p("t6")), np.fromfile(p("t7")))
             assert np.all(np.fromfile(p("t9")) < np.fromfile(p("t8")))
+        if "filled-tri" in names:        # right-angled records through the general geometry: the files of the arms without bit 4
+            assert np.array_equal(np.fromfile(p("t10")), np.fromfile(p("t7"))) and np.array_equal(np.fromfile(p("t11")), np.fromfile(p("t9")))
         assert not ("groups" in names and "longway" in names) or np.array_equal(np.fromfile(p("g3")), np.fromfile(p("g4")))
         lines = []
         for a in names:
             v = sorted(runs[a])
             med = v[len(v) // 2]
-            frame_atoms = N_SOLUTE if a == "plain" or a.startswith("filled") else N_FRAME
+            frame_atoms = N_SOLUTE if a == "plain" or a.startswith("filled") or a.startswith("octa") else N_FRAME
             line = {"arm": a, "frames": args.frames, "frame_atoms": frame_atoms, "solute_atoms": N_SOLUTE,
                     "median_seconds": med, "min_seconds": v[0], "max_seconds": v[-1],
                     "solute_atom_frames_per_s": N_SOLUTE * args.frames / med,
