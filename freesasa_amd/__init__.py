@@ -130,6 +130,7 @@ def lib():
         L.freesasa_gpu_calc_periodic_triclinic.argtypes = L.freesasa_gpu_calc_periodic.argtypes
         L.freesasa_gpu_cell_widths.argtypes = [_dp, _dp]
         L.freesasa_gpu_cell_from_dcd.argtypes = [_dp, _dp, C.c_char_p, C.c_int]
+        L.freesasa_gpu_cell_from_lengths_angles.argtypes = [_dp, _dp, _dp, C.c_char_p, C.c_int]
         L.freesasa_gpu_test_points.argtypes = [C.c_int, _dp]
         L.freesasa_gpu_test_points.restype = None
         L.freesasa_gpu_calc_batch.argtypes = [_dp, _dp, _lp, C.c_int, C.c_int, C.c_double, C.c_int,
@@ -304,6 +305,19 @@ def cell_from_dcd(rec):
     why = C.create_string_buffer(256)
     if lib().freesasa_gpu_cell_from_dcd(rec.ctypes.data_as(_dp), out.ctypes.data_as(_dp), why, 256):
         raise ValueError("freesasa_gpu_cell_from_dcd: " + why.value.decode())
+    return out
+
+
+def cell_from_lengths_angles(lengths, angles):
+    """freesasa_gpu_cell_from_lengths_angles(): the edges (a, b, c) and the angles (alpha, beta, gamma) in degrees, as AMBER NetCDF
+    files hold them -> the cell (ax, bx, by, cx, cy, cz), bit for bit what cell_from_dcd gives for the same numbers in degrees;
+    ValueError with the library's reason for an angle outside (0, 180) or angles that span no cell."""
+    lengths, angles, out = _f64(lengths).reshape(-1), _f64(angles).reshape(-1), np.empty(6)
+    if lengths.size != 3 or angles.size != 3:
+        raise ValueError("a cell is three lengths and three angles")
+    why = C.create_string_buffer(256)
+    if lib().freesasa_gpu_cell_from_lengths_angles(lengths.ctypes.data_as(_dp), angles.ctypes.data_as(_dp), out.ctypes.data_as(_dp), why, 256):
+        raise ValueError("freesasa_gpu_cell_from_lengths_angles: " + why.value.decode())
     return out
 
 
@@ -702,7 +716,7 @@ def trajectory(xyz_frames, radii, alg=LEE_RICHARDS, probe=1.4, resolution=20, fr
     return totals, sasa
 
 
-FRAMES_F32, FRAMES_OUT_F32, FRAMES_DCD, FRAMES_PBC, FRAMES_TRICLINIC = 1, 2, 4, 8, 16   # the bits of frames_f32 (include/freesasa_gpu.h)
+FRAMES_F32, FRAMES_OUT_F32, FRAMES_DCD, FRAMES_PBC, FRAMES_TRICLINIC, FRAMES_NETCDF = 1, 2, 4, 8, 16, 32   # the bits of frames_f32 (include/freesasa_gpu.h)
 
 
 class DcdInfoC(C.Structure):
@@ -737,24 +751,61 @@ def dcd_info(path):
     return DcdInfo(c)
 
 
-def _frames_bits(f32, out_f32, dcd, header_bytes, pbc=False, triclinic=False):
+class NcInfoC(C.Structure):
+    _fields_ = [("n_atoms", C.c_int32), ("n_frames", C.c_int64), ("n_frames_header", C.c_int64), ("first_record", C.c_int64),
+                ("record_bytes", C.c_int64), ("coord_off", C.c_int64), ("lengths_off", C.c_int64), ("angles_off", C.c_int64),
+                ("version", C.c_int32), ("has_cell", C.c_int32), ("has_time", C.c_int32), ("has_velocities", C.c_int32)]
+
+
+class NcInfo:
+    """What nc_info() returns: the fields of freesasa_gpu_nc_info (include/freesasa_gpu.h) - n_atoms, n_frames (whole records
+    by file size), n_frames_header (numrecs as the header claims, -1: streaming), first_record, record_bytes, coord_off,
+    lengths_off, angles_off (bytes; -1 without a cell), version, and the flags has_cell, has_time, has_velocities as bools."""
+
+    def __init__(self, c):
+        for name, _ in NcInfoC._fields_:
+            v = int(getattr(c, name))
+            setattr(self, name, bool(v) if name.startswith("has_") else v)
+
+    def __repr__(self):
+        return "NcInfo(" + ", ".join(f"{name}={getattr(self, name)}" for name, _ in NcInfoC._fields_) + ")"
+
+
+def nc_info(path):
+    """freesasa_gpu_nc_info_read(): the header of an AMBER NetCDF trajectory -> NcInfo; ValueError with the library's message
+    for a file that is no NetCDF classic file, is damaged, or is one the drivers do not read (NetCDF-4 / HDF5, CDF-5, a restart
+    file, a scale_factor other than 1)."""
+    L = lib()
+    L.freesasa_gpu_nc_info_read.argtypes = [C.c_char_p, C.POINTER(NcInfoC), C.c_char_p, C.c_int]
+    c = NcInfoC()
+    err = C.create_string_buffer(512)
+    if L.freesasa_gpu_nc_info_read(str(path).encode(), C.byref(c), err, 512):
+        raise ValueError("freesasa_gpu_nc_info_read: " + err.value.decode())
+    return NcInfo(c)
+
+
+def _frames_bits(f32, out_f32, dcd, header_bytes, pbc=False, triclinic=False, netcdf=False):
     if dcd and (f32 or header_bytes):
         raise ValueError("dcd=True excludes f32=True and a non-zero header_bytes: a DCD file says for itself where its frames are")
+    if netcdf and (dcd or f32 or header_bytes):
+        raise ValueError("netcdf=True excludes dcd=True, f32=True and a non-zero header_bytes: an AMBER NetCDF file says for itself where its frames are")
     return (FRAMES_F32 if f32 else 0) | (FRAMES_OUT_F32 if out_f32 else 0) | (FRAMES_DCD if dcd else 0) | (FRAMES_PBC if pbc else 0) | \
-        (FRAMES_TRICLINIC if triclinic else 0)
+        (FRAMES_TRICLINIC if triclinic else 0) | (FRAMES_NETCDF if netcdf else 0)
 
 
 def trajectory_file(frames_path, radii, totals_path, sasa_path=None, done_path=None, f32=False, header_bytes=0,
                     n_frames=0, alg=LEE_RICHARDS, probe=1.4, resolution=20, frames_per_batch=0, max_new_shards=0, device=-1,
-                    devices=None, out_f32=False, dcd=False, pbc=False, triclinic=False):
+                    devices=None, out_f32=False, dcd=False, pbc=False, triclinic=False, netcdf=False):
     """freesasa_gpu_trajectory_file(): raw frame file -> totals file (+ per-atom file), resumable through the
     done-list at done_path.  Returns (complete, n_frames): complete is False when max_new_shards stopped the run.
     f32: the frames are floats (an input format); out_f32: the per-atom file holds floats (an output format);
     dcd: frames_path is a DCD trajectory whose NATOM is len(radii) (no f32, no header_bytes with it);
     pbc: (with dcd) every frame among the periodic images its unit-cell record implies, as calc_periodic defines them;
-    triclinic: (with dcd and pbc) the record decoded by cell_from_dcd, the frame as calc_periodic_triclinic defines it."""
+    triclinic: (with dcd and pbc) the record decoded by cell_from_dcd, the frame as calc_periodic_triclinic defines it;
+    netcdf: frames_path is an AMBER NetCDF trajectory whose atom count is len(radii) (no dcd, no f32, no header_bytes with
+    it); pbc and triclinic go with it as with dcd: the cell is the frame's cell_lengths and cell_angles (cell_from_lengths_angles)."""
     radii = _f64(radii)
-    f32 = _frames_bits(f32, out_f32, dcd, header_bytes, pbc, triclinic)
+    f32 = _frames_bits(f32, out_f32, dcd, header_bytes, pbc, triclinic, netcdf)
     err = C.create_string_buffer(512)
     total = C.c_longlong(0)
     enc = lambda p: None if p is None else str(p).encode()
@@ -898,7 +949,7 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
                              f32=False, header_bytes=0, n_frames=0, alg=LEE_RICHARDS, probe=1.4, resolution=20, frames_per_batch=0,
                              max_new_shards=0, device=-1, devices=None, out_f32=False, chain_groups=None, separate_chains=False,
                              long=False, group=None, n_groups=None, group_areas_path=None, isolated_path=None, dcd=False, pbc=False,
-                             triclinic=False):
+                             triclinic=False, netcdf=False):
     """freesasa_gpu_trajectory_file_topology(): trajectory_file() with a topology (see trajectory_topology; frame_atoms:
     atoms per frame of the file, None: the structure's) and one raw fp64 result file per output asked for: class sums
     [F, 3], residues [F, R, 6], selection areas [F, S].  Returns (complete, n_frames, selection_atoms [S] or None).
@@ -906,14 +957,17 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
     [F, G, 3] fp64, isolated_path [F, n] fp64 (fp32 with out_f32).
     dcd: frames_path is a DCD trajectory; frame_atoms None is then the file's NATOM.
     pbc: (with dcd) the atoms the index keeps among their periodic images, frame by frame (not offered with chain groups);
-    triclinic: (with dcd and pbc) the cell records decoded as triclinic cells, see trajectory_file."""
+    triclinic: (with dcd and pbc) the cell records decoded as triclinic cells, see trajectory_file;
+    netcdf: frames_path is an AMBER NetCDF trajectory; frame_atoms None is then the file's atom count; pbc and triclinic as with dcd."""
     L = _topology_proto(lib())
+    bits = _frames_bits(f32, out_f32, dcd, header_bytes, pbc, triclinic, netcdf)
     if dcd and frame_atoms is None:
         frame_atoms = dcd_info(frames_path).n_atoms
+    if netcdf and frame_atoms is None:
+        frame_atoms = nc_info(frames_path).n_atoms
     n, R, res_ref, idx, fa_ = _topology_args(batch, structure, atom_index, frame_atoms)
     S = len(selection) if selection is not None else 0
     sel_atoms = np.zeros(S, dtype=np.int64) if selection is not None else None
-    bits = _frames_bits(f32, out_f32, dcd, header_bytes, pbc, triclinic)
     err = C.create_string_buffer(512)
     total = C.c_longlong(0)
     enc = lambda p: None if p is None else str(p).encode()

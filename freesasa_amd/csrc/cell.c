@@ -1,6 +1,6 @@
 /*
  * cell.c — the host arithmetic of triclinic cells (include/freesasa_gpu.h: freesasa_gpu_cell_widths,
- * freesasa_gpu_cell_from_dcd).  A cell is six numbers ax, bx, by, cx, cy, cz: the lower-triangular box matrix with rows
+ * freesasa_gpu_cell_from_dcd, freesasa_gpu_cell_from_lengths_angles).  A cell is six numbers ax, bx, by, cx, cy, cz: the lower-triangular box matrix with rows
  * a = (ax, 0, 0), b = (bx, by, 0), c = (cx, cy, cz).  Plain C without allocation, compiled with -ffp-contract=off like all of
  * the engine: every operation below is rounded on its own, in the order written (pbc_tri_kernels.h and the tests pin it).
  */
@@ -35,6 +35,17 @@ int freesasa_gpu_cell_widths(const double cell6[6], double widths_out[3])
     return 0;
 }
 
+/* the cosine of an angle given in degrees; 0 / -1 with the reason, which ends in `expected` */
+static int degrees_cosine(double v, const char *name, const char *expected, double *cosine, char *why, int why_len)
+{
+    if (!(v > 0.0 && v < 180.0)) { /* (a NaN comes here) */
+        if (why && why_len > 0) snprintf(why, (size_t)why_len, "angle %s of its cell is %.9g: %s", name, v, expected);
+        return -1;
+    }
+    *cosine = fabs(v - 90.0) <= 1e-4 ? 0.0 : cos(v * 3.14159265358979323846 / 180.0);
+    return 0;
+}
+
 /* the cosine an angle field of a CHARMM cell record stands for; 0 / -1 with the reason */
 static int angle_cosine(double v, const char *name, double *cosine, char *why, int why_len)
 {
@@ -42,11 +53,33 @@ static int angle_cosine(double v, const char *name, double *cosine, char *why, i
         *cosine = fabs(v) <= 1e-6 ? 0.0 : v;
         return 0;
     }
-    if (!(v > 0.0 && v < 180.0)) { /* (a NaN comes here) */
-        if (why && why_len > 0) snprintf(why, (size_t)why_len, "angle %s of its cell is %.9g: neither a cosine nor degrees in (0, 180)", name, v);
+    return degrees_cosine(v, name, "neither a cosine nor degrees in (0, 180)", cosine, why, why_len);
+}
+
+static int edges_finite(double A, double B, double C, char *why, int why_len)
+{
+    const double edge[3] = {A, B, C};
+    for (int k = 0; k < 3; ++k)
+        if (!isfinite(edge[k])) {
+            if (why && why_len > 0) snprintf(why, (size_t)why_len, "edge %c of its cell is not finite", "ABC"[k]);
+            return -1;
+        }
+    return 0;
+}
+
+/* the six numbers from the edges and the cosines; g, b, a: the angles as they were given, for the reason */
+static int cell_from_cosines(double A, double B, double C, double cg, double cb, double ca, double g, double b, double a, double cell6_out[6],
+                             char *why, int why_len)
+{
+    const double sg = sqrt(1.0 - cg * cg);
+    const double ax = A, bx = B * cg, by = B * sg, cx = C * cb, cy = C * ((ca - cb * cg) / sg);
+    const double cz2 = (C * C - cx * cx) - cy * cy;
+    if (!(cz2 > 0.0) || !isfinite(cz2) || !isfinite(bx) || !isfinite(by) || !isfinite(cx) || !isfinite(cy)) {
+        if (why && why_len > 0)
+            snprintf(why, (size_t)why_len, "the angles of its cell span no cell (gamma, beta, alpha fields %.9g, %.9g, %.9g)", g, b, a);
         return -1;
     }
-    *cosine = fabs(v - 90.0) <= 1e-4 ? 0.0 : cos(v * 3.14159265358979323846 / 180.0);
+    cell6_out[0] = ax; cell6_out[1] = bx; cell6_out[2] = by; cell6_out[3] = cx; cell6_out[4] = cy; cell6_out[5] = sqrt(cz2);
     return 0;
 }
 
@@ -57,25 +90,25 @@ int freesasa_gpu_cell_from_dcd(const double rec[6], double cell6_out[6], char *w
         if (why && why_len > 0) snprintf(why, (size_t)why_len, "null argument");
         return -1;
     }
-    const double A = rec[0], B = rec[2], C = rec[5];
-    const double edge[3] = {A, B, C};
-    for (int k = 0; k < 3; ++k)
-        if (!isfinite(edge[k])) {
-            if (why && why_len > 0) snprintf(why, (size_t)why_len, "edge %c of its cell is not finite", "ABC"[k]);
-            return -1;
-        }
+    if (edges_finite(rec[0], rec[2], rec[5], why, why_len)) return -1;
     double cg, cb, ca;
     if (angle_cosine(rec[1], "gamma", &cg, why, why_len) || angle_cosine(rec[3], "beta", &cb, why, why_len) ||
         angle_cosine(rec[4], "alpha", &ca, why, why_len))
         return -1;
-    const double sg = sqrt(1.0 - cg * cg);
-    const double ax = A, bx = B * cg, by = B * sg, cx = C * cb, cy = C * ((ca - cb * cg) / sg);
-    const double cz2 = (C * C - cx * cx) - cy * cy;
-    if (!(cz2 > 0.0) || !isfinite(cz2) || !isfinite(bx) || !isfinite(by) || !isfinite(cx) || !isfinite(cy)) {
-        if (why && why_len > 0)
-            snprintf(why, (size_t)why_len, "the angles of its cell span no cell (gamma, beta, alpha fields %.9g, %.9g, %.9g)", rec[1], rec[3], rec[4]);
+    return cell_from_cosines(rec[0], rec[2], rec[5], cg, cb, ca, rec[1], rec[3], rec[4], cell6_out, why, why_len);
+}
+
+int freesasa_gpu_cell_from_lengths_angles(const double len[3], const double deg[3], double cell6_out[6], char *why, int why_len)
+{
+    if (why && why_len > 0) why[0] = 0;
+    if (!len || !deg || !cell6_out) {
+        if (why && why_len > 0) snprintf(why, (size_t)why_len, "null argument");
         return -1;
     }
-    cell6_out[0] = ax; cell6_out[1] = bx; cell6_out[2] = by; cell6_out[3] = cx; cell6_out[4] = cy; cell6_out[5] = sqrt(cz2);
-    return 0;
+    if (edges_finite(len[0], len[1], len[2], why, why_len)) return -1;
+    double cg, cb, ca; /* (gamma, beta, alpha: the order the DCD entry takes them in) */
+    if (degrees_cosine(deg[2], "gamma", "not degrees in (0, 180)", &cg, why, why_len) || degrees_cosine(deg[1], "beta", "not degrees in (0, 180)", &cb, why, why_len) ||
+        degrees_cosine(deg[0], "alpha", "not degrees in (0, 180)", &ca, why, why_len))
+        return -1;
+    return cell_from_cosines(len[0], len[1], len[2], cg, cb, ca, deg[2], deg[1], deg[0], cell6_out, why, why_len);
 }

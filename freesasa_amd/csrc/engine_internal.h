@@ -97,6 +97,8 @@ hipError_t kl_sel_sums(const sasa::SelArgs &a, hipStream_t st);
 hipError_t kl_traj_gather(const sasa::TrajArgs &a, const void *d_in, bool in_f32, double *d_out, hipStream_t st);
 /* ... the same from the bytes of DCD frames (planar fp32 records, byte-swapped when big_endian): the gather and the widening in one */
 hipError_t kl_traj_gather_dcd(const sasa::TrajDcdArgs &a, const void *d_in, bool big_endian, double *d_out, hipStream_t st);
+/* ... and from the bytes of AMBER NetCDF records (big-endian fp32, atom by atom, at a record stride) */
+hipError_t kl_traj_gather_nc(const sasa::TrajNcArgs &a, const void *d_in, double *d_out, hipStream_t st);
 hipError_t kl_traj_residues(const sasa::TrajArgs &a, hipStream_t st);
 hipError_t kl_traj_class(const sasa::TrajArgs &a, hipStream_t st);
 hipError_t kl_traj_sel(const sasa::TrajArgs &a, hipStream_t st);

@@ -123,7 +123,8 @@ namespace {
  * frames that goes through the engine as one batch.  A few host lanes PER DEVICE take shards from a shared counter; a
  * lane owns a pooled context (stream, workspace, page-locked staging) of its device and does, for its shard,
  *     read (memory or frame file) -> host-to-device -> [fp32 frames widened to fp64 on the device: an INPUT format,
- *     the arithmetic stays fp64; the planar fp32 records of a DCD file made into compact fp64 frames by one kernel]
+ *     the arithmetic stays fp64; the planar fp32 records of a DCD file, or the big-endian fp32 records of an AMBER NetCDF
+ *     file, made into compact fp64 frames by one kernel]
  *     -> cell sort + tile kernels -> device-to-host -> write (memory or files)
  * while the other lanes are in another stage.  The radii live once per device context (shared by every frame of
  * a batch).  With a done-list file every finished shard is recorded after its results are on disk; a later call
@@ -155,6 +156,8 @@ struct TrajIO {
     int in_f32 = 0;
     bool in_dcd = false;            /* the file is a DCD trajectory: its frames go up as they lie in the file ... */
     freesasa_gpu_dcd_info dcd = {}; /* ... and this says where their planes are (dcd.c) */
+    bool in_nc = false;             /* the file is an AMBER NetCDF trajectory: its records go up as they lie in the file ... */
+    freesasa_gpu_nc_info nc = {};   /* ... and this says where their coordinates and their cell are (netcdf.c) */
     bool pbc = false;               /* FREESASA_GPU_FRAMES_PBC: every frame among the images its cell record implies (gpu_periodic.hip) */
     bool tri = false;               /* ... FREESASA_GPU_FRAMES_TRICLINIC beside it: the record decoded as a triclinic cell */
     /* per frame: total [1], per-atom areas [n]; runs with a topology: class sums [3], residue areas [6 R], selection areas [S];
@@ -361,10 +364,10 @@ struct TrajRun {
     const bool gather = topo && topo->index;
     const size_t fa = topo ? (size_t)topo->frame_atoms : n, esz = io.in_f32 ? 12 : 24;
     const size_t widen_bytes = io.in_f32 && !gather ? 12 * n * FB : 0; /* (fp32 frames without an index: kl_widen_f32's input) */
-    /* bytes from one input frame to the next: raw frames, or a DCD file's stride (kl_traj_gather_dcd then does the gather's
-       and the widening's work, with or without an index) */
-    const bool dcd = io.in_dcd;
-    const size_t stride = dcd ? (size_t)io.dcd.frame_bytes : esz * fa;
+    /* bytes from one input frame to the next: raw frames, or a DCD / NetCDF file's stride (kl_traj_gather_dcd / _nc then does
+       the gather's and the widening's work, with or without an index) */
+    const bool dcd = io.in_dcd, netcdf = io.in_nc, container = dcd || netcdf;
+    const size_t stride = dcd ? (size_t)io.dcd.frame_bytes : netcdf ? (size_t)io.nc.record_bytes : esz * fa;
     /* periodic images: a shard's [nf][3] cell edges ride behind its bytes (at the next multiple of 8); every edge must reach
        the system's c = 2 (max radius + probe) */
     const bool pbc = io.pbc;
@@ -439,7 +442,7 @@ int shard_size(TrajRun &T, TrajLane &L)
     if (ensure(c, c->h_xyz, 24 * nc * FB) || ensure(c, c->h_radii, T.groups ? 8 * nc * FB : 8 * n) || ensure(c, c->h_sasa, 8 * nc * FB) ||
         ensure(c, c->h_totals, 8 * (1 + T.G) * FB) ||
         (T.widen_bytes + narrow_bytes && ensure(c, c->h_counts, T.widen_bytes + narrow_bytes)) ||
-        ((T.gather || T.dcd) && ensure(c, c->g_xyz, T.pbc ? TrajRun::cells_at(T.stride * FB) + T.cell_bytes * FB : T.stride * FB)) || (T.xw && ensure(c, c->h_gtot, 8 * T.xw * FB)) ||
+        ((T.gather || T.container) && ensure(c, c->g_xyz, T.pbc ? TrajRun::cells_at(T.stride * FB) + T.cell_bytes * FB : T.stride * FB)) || (T.xw && ensure(c, c->h_gtot, 8 * T.xw * FB)) ||
         (T.groups && (ensure(c, c->g_gath, 8 * nc * FB) || ensure(c, c->g_tot2, 8 * (1 + T.G) * FB))) || (iso && ensure(c, c->h_iso, 8 * n * FB)))
         return -1;
     if (!T.groups && !L.radii_up && hipMemcpyAsync(c->h_radii.p, T.s.radii, 8 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "radii upload failed");
@@ -509,6 +512,21 @@ long long dcd_cells(const freesasa_gpu_dcd_info &d, const char *bytes, long long
     return -1;
 }
 
+/* A decoded cell h[6] of a frame: its shape, and its three widths - made here, into h[6 .. 8] - against cut.  edge: A, B, C as the
+   file holds them, for the reason.  false, or true with the reason in why. */
+static bool tri_cell_bad(double *h, const double edge[3], double cut, char *why, size_t why_len)
+{
+    const int shape = periodic_cell6_bad(h);
+    if (shape) { /* (an edge that is not positive: everything else the decoder has refused) */
+        snprintf(why, why_len, "edge %c of its cell is %.9g: not positive", shape == 1 ? 'A' : shape == 3 ? 'B' : 'C', edge[shape == 1 ? 0 : shape == 3 ? 1 : 2]);
+        return true;
+    }
+    (void)freesasa_gpu_cell_widths(h, h + 6);
+    const int bad = periodic_widths_bad(h + 6, cut);
+    if (bad) snprintf(why, why_len, "width %c of its cell is %.9g, smaller than c = 2 (max radius + probe) = %.9g", "abc"[bad - 1], h[6 + bad - 1], cut);
+    return bad != 0;
+}
+
 /* The same records decoded as triclinic cells (freesasa_gpu_cell_from_dcd): cell9[nf][9] receives the six numbers of every
    frame's cell and, behind them, its three widths; returns -1, or the first frame whose record spans no cell or whose cell has
    a width below cut, the reason in why. */
@@ -517,25 +535,46 @@ long long dcd_cells_tri(const freesasa_gpu_dcd_info &d, const char *bytes, long 
     for (long long f = 0; f < nf; ++f) {
         double v[6], *h = cell9 + PBC_TRI_CELL * f;
         dcd_cell_record(d, bytes, f, v);
-        if (freesasa_gpu_cell_from_dcd(v, h, why, (int)why_len)) return f;
-        const int shape = periodic_cell6_bad(h);
-        if (shape) { /* (an edge that is not positive: everything else the decoder has refused) */
-            snprintf(why, why_len, "edge %c of its cell is %.9g: not positive", shape == 1 ? 'A' : shape == 3 ? 'B' : 'C', v[shape == 1 ? 0 : shape == 3 ? 2 : 5]);
-            return f;
+        const double edge[3] = {v[0], v[2], v[5]};
+        if (freesasa_gpu_cell_from_dcd(v, h, why, (int)why_len) || tri_cell_bad(h, edge, cut, why, why_len)) return f;
+    }
+    return -1;
+}
+
+/* The cells of the AMBER NetCDF frames [0, nf) at `bytes`: three edge lengths and alpha, beta, gamma, big-endian doubles, the
+   angles ALWAYS degrees (a 0 is not a right angle here).  Orthorhombic runs: the edges into cells[nf][3]; triclinic runs:
+   cells[nf][9] as dcd_cells_tri fills it, through freesasa_gpu_cell_from_lengths_angles and tri_cell_bad.  Returns -1, or the first frame whose
+   cell periodic images are not offered for, the reason in why. */
+long long nc_cells(const freesasa_gpu_nc_info &d, const char *bytes, long long nf, bool tri, double cut, double *cells, char *why, size_t why_len)
+{
+    for (long long f = 0; f < nf; ++f) {
+        double len[3], deg[3];
+        freesasa_gpu_nc_cell_record(&d, bytes, f, len, deg);
+        if (!tri) {
+            for (int k = 0; k < 3; ++k)
+                if (!(fabs(deg[k] - 90.0) <= 1e-4)) {
+                    snprintf(why, why_len, "its cell is not orthorhombic (angle %s is %.9g degrees): triclinic cells need bit 4", k == 0 ? "alpha" : k == 1 ? "beta" : "gamma", deg[k]);
+                    return f;
+                }
+            for (int k = 0; k < 3; ++k) {
+                if (!isfinite(len[k])) { snprintf(why, why_len, "edge %c of its cell is not finite", "xyz"[k]); return f; }
+                if (!(len[k] >= cut)) {
+                    snprintf(why, why_len, "edge %c of its cell is %.9g, shorter than c = 2 (max radius + probe) = %.9g", "xyz"[k], len[k], cut);
+                    return f;
+                }
+                cells[3 * f + k] = len[k];
+            }
+            continue;
         }
-        (void)freesasa_gpu_cell_widths(h, h + 6);
-        const int bad = periodic_widths_bad(h + 6, cut);
-        if (bad) {
-            snprintf(why, why_len, "width %c of its cell is %.9g, smaller than c = 2 (max radius + probe) = %.9g", "abc"[bad - 1], h[6 + bad - 1], cut);
-            return f;
-        }
+        double *h = cells + PBC_TRI_CELL * f;
+        if (freesasa_gpu_cell_from_lengths_angles(len, deg, h, why, (int)why_len) || tri_cell_bad(h, len, cut, why, why_len)) return f;
     }
     return -1;
 }
 
 /* the shard's frames in page-locked memory: the caller's own, or the lane's staging filled from memory or from the file
    (a DCD file: the bytes as they lie there, every record marker checked; with periodic images every cell record decoded and
-   checked, the edges behind the bytes) */
+   checked, the edges behind the bytes; an AMBER NetCDF file: the records as they lie there, with periodic images likewise) */
 int shard_read(TrajRun &T, freesasa_gpu_ctx *c, TrajShard &h)
 {
     h.src = T.io.mem_in ? T.io.mem_in + 3 * T.fa * (size_t)h.f0 : nullptr;
@@ -555,17 +594,22 @@ int shard_read(TrajRun &T, freesasa_gpu_ctx *c, TrajShard &h)
             if (odd >= 0) return ctx_fail(c, "frame %lld of the DCD file: %s", h.f0 + odd, why);
         }
     }
+    if (T.netcdf && T.pbc) {
+        char why[160];
+        const long long odd = nc_cells(T.io.nc, (const char *)c->stage_in, h.nf, T.io.tri, T.pbc_cut, (double *)((char *)c->stage_in + TrajRun::cells_at(h.in_bytes)), why, sizeof why);
+        if (odd >= 0) return ctx_fail(c, "frame %lld of the NetCDF file: %s", h.f0 + odd, why);
+    }
     h.src = c->stage_in;
     return 0;
 }
 
 /* ... to the device, into the compact fp64 frames the engine reads (c->h_xyz): as they are, widened, or gathered; a DCD file's
-   bytes as they are, de-planarized (and gathered, widened, byte-swapped) by one kernel */
+   bytes as they are, de-planarized (and gathered, widened, byte-swapped) by one kernel; a NetCDF file's likewise */
 int shard_upload(TrajRun &T, TrajLane &L, const TrajShard &h)
 {
     freesasa_gpu_ctx *c = L.c;
     const bool f32 = T.io.in_f32 != 0;
-    void *d_in = T.gather || T.dcd ? c->g_xyz.p : (f32 ? c->h_counts.p : c->h_xyz.p);
+    void *d_in = T.gather || T.container ? c->g_xyz.p : (f32 ? c->h_counts.p : c->h_xyz.p);
     /* (periodic images: the shard's cell edges behind its bytes, in the same copy) */
     const size_t up_bytes = T.pbc ? TrajRun::cells_at(h.in_bytes) + T.cell_bytes * (size_t)h.nf : h.in_bytes;
     if (hipMemcpyAsync(d_in, h.src, up_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "host-to-device copy failed");
@@ -575,8 +619,12 @@ int shard_upload(TrajRun &T, TrajLane &L, const TrajShard &h)
         const sasa::TrajDcdArgs da = {(int)T.n, h.nf, T.gather ? L.ta.index : nullptr, d.frame_bytes, d.x_off, d.plane_bytes};
         if (kl_traj_gather_dcd(da, d_in, d.big_endian != 0, (double *)c->h_xyz.p, c->stream) != hipSuccess) return ctx_fail(c, "DCD gather launch failed");
     }
+    if (T.netcdf) {
+        const sasa::TrajNcArgs na = {(int)T.n, h.nf, T.gather ? L.ta.index : nullptr, T.io.nc.record_bytes, T.io.nc.coord_off};
+        if (kl_traj_gather_nc(na, d_in, (double *)c->h_xyz.p, c->stream) != hipSuccess) return ctx_fail(c, "NetCDF gather launch failed");
+    }
     /* full frames up as they were read: one kernel drops the solvent and widens fp32 */
-    if (T.gather && !T.dcd && kl_traj_gather(L.ta, d_in, f32, (double *)c->h_xyz.p, c->stream) != hipSuccess) return ctx_fail(c, "gather launch failed");
+    if (T.gather && !T.container && kl_traj_gather(L.ta, d_in, f32, (double *)c->h_xyz.p, c->stream) != hipSuccess) return ctx_fail(c, "gather launch failed");
     if (!T.gather && f32 && kl_widen_f32((const float *)d_in, (double *)c->h_xyz.p, (long long)(3 * h.na), c->stream) != hipSuccess) return ctx_fail(c, "widening launch failed");
     if (!T.groups) return 0;
     /* chain groups: behind the compact frames, whoever made them, every group's atoms of every frame; the radii of the
@@ -828,12 +876,12 @@ extern "C" int freesasa_gpu_trajectory_topology(const double *xyz_frames, int n_
    files byte for byte.  With a topology, in front of the line's end, what its outputs depend on: digests of the index, of
    residue boundaries + classes + backbone flags, of the selection set's program, and which result files the run writes; with
    chain groups, behind that, a digest of the group count and the ids.  A DCD run: bit 2 in the f32= word and the byte of
-   frame 0 as header_bytes=; a raw run's line is what it was.  Periodic images: bit 3 in the f32= word, triclinic cells: bit 4. */
+   frame 0 as header_bytes=; an AMBER NetCDF run: bit 5 and the byte of record 0; a raw run's line is what it was.  Periodic images: bit 3 in the f32= word, triclinic cells: bit 4. */
 static int traj_done_head(char *head, size_t cap, const TrajSpec &s, const TrajIO &io, const struct stat &st)
 {
     int len = snprintf(head, cap, "freesasa_amd trajectory done-list v2 n_atoms=%d n_frames=%lld frames_per_batch=%d alg=%d resolution=%d probe=%.17g f32=%d "
                        "header_bytes=%lld frames_size=%lld frames_mtime=%lld.%09ld radii=%016llx\n",
-                       s.n_atoms, s.n_frames, s.frames_per_batch, s.alg, s.resolution, s.probe, io.in_f32 | (io.out_f32() << 1) | (io.in_dcd ? FREESASA_GPU_FRAMES_DCD : 0) | (io.pbc ? FREESASA_GPU_FRAMES_PBC : 0) | (io.tri ? FREESASA_GPU_FRAMES_TRICLINIC : 0), io.in_header, (long long)st.st_size,
+                       s.n_atoms, s.n_frames, s.frames_per_batch, s.alg, s.resolution, s.probe, io.in_f32 | (io.out_f32() << 1) | (io.in_dcd ? FREESASA_GPU_FRAMES_DCD : 0) | (io.in_nc ? FREESASA_GPU_FRAMES_NETCDF : 0) | (io.pbc ? FREESASA_GPU_FRAMES_PBC : 0) | (io.tri ? FREESASA_GPU_FRAMES_TRICLINIC : 0), io.in_header, (long long)st.st_size,
                        (long long)st.st_mtim.tv_sec, (long)st.st_mtim.tv_nsec, fnv1a(s.radii, 8 * (size_t)s.n_atoms));
     const TrajTopo *tp = s.topo;
     if (tp && len > 0 && len < (int)cap) {
@@ -857,7 +905,7 @@ static int traj_done_head(char *head, size_t cap, const TrajSpec &s, const TrajI
     return len > 0 && len < (int)cap ? 0 : -1;
 }
 
-/* Frame file (raw frames, or with FREESASA_GPU_FRAMES_DCD a DCD trajectory) -> result files, resumable (include/freesasa_gpu.h has the formats).  The caller has put the result files'
+/* Frame file (raw frames, with FREESASA_GPU_FRAMES_DCD a DCD trajectory, with FREESASA_GPU_FRAMES_NETCDF an AMBER NetCDF one) -> result files, resumable (include/freesasa_gpu.h has the formats).  The caller has put the result files'
    paths into io.out[]; s.topo: a run with a topology - frames of its frame_atoms atoms, a longer first line of the done-list. */
 static int trajectory_file_run(const char *frames_path, int frames_f32, long long header_bytes, TrajSpec s, TrajIO &io,
                                const char *done_path, long long *frames_total_out, char *err_out, int err_len)
@@ -865,11 +913,28 @@ static int trajectory_file_run(const char *frames_path, int frames_f32, long lon
     if (!frames_path || !s.radii || !io.out[OUT_TOTALS].path) return set_err(err_out, err_len, "null argument");
     if (s.n_atoms <= 0 || header_bytes < 0) return set_err(err_out, err_len, "bad argument");
     const long long frame_atoms = s.topo ? s.topo->frame_atoms : s.n_atoms;
-    if ((frames_f32 & FREESASA_GPU_FRAMES_PBC) && !(frames_f32 & FREESASA_GPU_FRAMES_DCD))
-        return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) needs bit 2 (a DCD file): raw frame files carry no cell");
+    if ((frames_f32 & FREESASA_GPU_FRAMES_PBC) && !(frames_f32 & (FREESASA_GPU_FRAMES_DCD | FREESASA_GPU_FRAMES_NETCDF)))
+        return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) needs bit 2 (a DCD file) or bit 5 (an AMBER NetCDF file): raw frame files carry no cell");
     if ((frames_f32 & FREESASA_GPU_FRAMES_TRICLINIC) && !(frames_f32 & FREESASA_GPU_FRAMES_PBC))
-        return set_err(err_out, err_len, "bit 4 of frames_f32 (triclinic cells) needs bit 3 (periodic images) and bit 2 (a DCD file)");
-    if (frames_f32 & FREESASA_GPU_FRAMES_DCD) {
+        return set_err(err_out, err_len, "bit 4 of frames_f32 (triclinic cells) needs bit 3 (periodic images) and bit 2 (a DCD file) or bit 5 (an AMBER NetCDF file)");
+    if (frames_f32 & FREESASA_GPU_FRAMES_NETCDF) {
+        /* an AMBER NetCDF file says for itself where its frames are and what they are: before a device is touched or an output file opened */
+        if (frames_f32 & FREESASA_GPU_FRAMES_F32) return set_err(err_out, err_len, "bit 0 of frames_f32 (raw fp32 frames) and bit 5 (an AMBER NetCDF file) exclude each other");
+        if (frames_f32 & FREESASA_GPU_FRAMES_DCD) return set_err(err_out, err_len, "bit 2 of frames_f32 (a DCD file) and bit 5 (an AMBER NetCDF file) exclude each other");
+        if (header_bytes != 0) return set_err(err_out, err_len, "header_bytes must be 0 with an AMBER NetCDF file: the byte of its first record comes from its header");
+        if (freesasa_gpu_nc_info_read(frames_path, &io.nc, err_out, err_len)) return -1;
+        if (io.nc.n_atoms != frame_atoms) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "the NetCDF file holds %d atoms per frame, the run expects %lld", (int)io.nc.n_atoms, frame_atoms);
+            return set_err(err_out, err_len, msg);
+        }
+        io.in_nc = true;
+        if (frames_f32 & FREESASA_GPU_FRAMES_PBC) {
+            if (!io.nc.has_cell) return set_err(err_out, err_len, "periodic images need a NetCDF file with the variables cell_lengths and cell_angles: this one has no cell");
+            io.pbc = true;
+            io.tri = (frames_f32 & FREESASA_GPU_FRAMES_TRICLINIC) != 0;
+        }
+    } else if (frames_f32 & FREESASA_GPU_FRAMES_DCD) {
         /* a DCD file says for itself where its frames are and what they are: before a device is touched or an output file opened */
         if (header_bytes != 0) return set_err(err_out, err_len, "header_bytes must be 0 with a DCD file: the byte of its first frame comes from its header");
         if (frames_f32 & FREESASA_GPU_FRAMES_F32) return set_err(err_out, err_len, "bit 0 of frames_f32 (raw fp32 frames) and bit 2 (a DCD file) exclude each other");
@@ -892,9 +957,10 @@ static int trajectory_file_run(const char *frames_path, int frames_f32, long lon
     if (io.in.fd < 0) return set_err(err_out, err_len, "cannot open the frame file");
     struct stat st;
     if (fstat(io.in.fd, &st) != 0) return set_err(err_out, err_len, "cannot stat the frame file");
-    io.in_header = io.in_dcd ? io.dcd.first_frame : header_bytes;
+    io.in_header = io.in_dcd ? io.dcd.first_frame : io.in_nc ? io.nc.first_record : header_bytes;
     io.in_f32 = (frames_f32 & 1) ? 1 : 0; io.out[OUT_SASA].esz = io.out[OUT_ISO].esz = (frames_f32 & 2) ? 4 : 8;
     const long long in_file = io.in_dcd ? ((long long)st.st_size - io.dcd.first_frame) / io.dcd.frame_bytes
+                            : io.in_nc ? ((long long)st.st_size - io.nc.first_record) / io.nc.record_bytes
                                         : ((long long)st.st_size - header_bytes) / ((io.in_f32 ? 12LL : 24LL) * frame_atoms);
     if (s.n_frames <= 0) s.n_frames = in_file;
     if (s.n_frames <= 0 || s.n_frames > in_file) return set_err(err_out, err_len, "the frame file holds fewer frames than asked for");

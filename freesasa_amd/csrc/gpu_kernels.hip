@@ -879,6 +879,10 @@ __global__ __launch_bounds__(TRAJ_B) void k_traj_gather_dcd(TrajDcdArgs a, const
 {
     traj_gather_dcd<SWAP>(a, in, out, (int64_t)blockIdx.x * TRAJ_B + threadIdx.x);
 }
+__global__ __launch_bounds__(TRAJ_B) void k_traj_gather_nc(TrajNcArgs a, const uint32_t *in, double *out)
+{
+    traj_gather_nc(a, in, out, (int64_t)blockIdx.x * TRAJ_B + threadIdx.x);
+}
 __global__ __launch_bounds__(TRAJ_B) void k_traj_residues(TrajArgs a)
 {
     traj_residue(a, (int64_t)blockIdx.x * TRAJ_B + threadIdx.x);
@@ -910,6 +914,12 @@ hipError_t kl_traj_gather_dcd(const TrajDcdArgs &a, const void *d_in, bool big_e
     const unsigned grid = (unsigned)((3 * (int64_t)a.n_frames * a.n + TRAJ_B - 1) / TRAJ_B);
     if (big_endian) hipLaunchKernelGGL(k_traj_gather_dcd<true>, dim3(grid), dim3(TRAJ_B), 0, st, a, (const uint32_t *)d_in, d_out);
     else hipLaunchKernelGGL(k_traj_gather_dcd<false>, dim3(grid), dim3(TRAJ_B), 0, st, a, (const uint32_t *)d_in, d_out);
+    return hipGetLastError();
+}
+hipError_t kl_traj_gather_nc(const TrajNcArgs &a, const void *d_in, double *d_out, hipStream_t st)
+{
+    const unsigned grid = (unsigned)((3 * (int64_t)a.n_frames * a.n + TRAJ_B - 1) / TRAJ_B);
+    hipLaunchKernelGGL(k_traj_gather_nc, dim3(grid), dim3(TRAJ_B), 0, st, a, (const uint32_t *)d_in, d_out);
     return hipGetLastError();
 }
 hipError_t kl_traj_residues(const TrajArgs &a, hipStream_t st)

@@ -6,6 +6,7 @@
  *
  *   traj_gather        out[f][i] = in[f][index[i]], fp32 input widened on the way (before the engine sees the frames)
  *   traj_gather_dcd    the same from the bytes of DCD frames: planar x[] | y[] | z[] records of fp32, either byte order
+ *   traj_gather_nc     the same from the bytes of AMBER NetCDF records: big-endian fp32, atom by atom, at a record stride
  *   traj_residue       the six per-residue areas of every (frame, residue), as residue_areas (sasa_kernels.h)
  *   traj_class_phase0  the three class sums of every frame, as class_phase0 / class_phase1
  *   traj_sel_phase0/1  the selection areas of every frame, as sel_sums_phase0 / sel_sums_phase1 (select_kernels.h)
@@ -88,6 +89,36 @@ SASA_D void traj_gather_dcd(const TrajDcdArgs &a, const uint32_t *in, double *ou
     const int64_t byte = f * a.frame_bytes + a.x_off + (int64_t)comp * a.plane_bytes + 4 * (int64_t)(a.index ? a.index[i] : i);
     uint32_t w = in[byte >> 2];
     if (SWAP) w = (w >> 24) | ((w >> 8) & 0xff00u) | ((w << 8) & 0xff0000u) | (w << 24);
+    float v;
+    memcpy(&v, &w, 4);
+    out[t] = (double)v;
+}
+
+/* traj_gather_nc: the frames of a shard as they lie in an AMBER NetCDF file (netcdf.c has the layout) -> the compact fp64
+   frames.  Each frame is one record of record_bytes; from byte coord_off on it holds x, y, z of ALL its atoms as big-endian fp32,
+   atom by atom; what else the record holds (time, cell, velocities, forces) no thread reads.  One thread per output coordinate,
+   t -> (f, i, comp) as in traj_gather: with the identity index (index NULL) consecutive lanes read consecutive words and write
+   consecutive doubles.  Every offset is a multiple of 4 and in general not of 8 (37 atoms without a time variable: records of
+   444 bytes): 4-byte loads only, `in` is the shard's bytes as 32-bit words.  The file is always big-endian: the swap is not a
+   template flag.  This is traj_gather AND the widening for NetCDF input. */
+struct TrajNcArgs {
+    int n;                /* atoms of a frame as the engine sees it */
+    int n_frames;         /* frames of this shard */
+    const int32_t *index; /* [n] output atom i is the file's atom index[i]; NULL: i */
+    int64_t record_bytes; /* the file's stride from frame to frame */
+    int64_t coord_off;    /* byte of atom 0's x within a record */
+};
+SASA_D void traj_gather_nc(const TrajNcArgs &a, const uint32_t *in, double *out, int64_t t)
+{
+    const int64_t total = 3 * (int64_t)a.n_frames * a.n;
+    if (t >= total) return;
+    const int64_t atom = t / 3;
+    const int comp = (int)(t - 3 * atom);
+    const int64_t f = atom / a.n;
+    const int i = (int)(atom - f * a.n);
+    const int64_t byte = f * a.record_bytes + a.coord_off + 12 * (int64_t)(a.index ? a.index[i] : i) + 4 * comp;
+    uint32_t w = in[byte >> 2];
+    w = (w >> 24) | ((w >> 8) & 0xff00u) | ((w << 8) & 0xff0000u) | (w << 24);
     float v;
     memcpy(&v, &w, 4);
     out[t] = (double)v;

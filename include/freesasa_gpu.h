@@ -475,6 +475,11 @@ int freesasa_gpu_cell_widths(const double cell6[6], double widths_out[3]);
    exactly.  Returns 0, or -1 with the reason in why (may be NULL): an edge that is not finite, an angle field that is neither,
    angles that span no cell (cz^2 <= 0 or not a number).  Touches no device. */
 int freesasa_gpu_cell_from_dcd(const double rec[6], double cell6_out[6], char *why, int why_len);
+/* The same from three edge lengths (a, b, c) and three angles (alpha, beta, gamma) as AMBER NetCDF files hold them.  The
+   angles are ALWAYS degrees, each in (0, 180): there is no cosine reading.  The operations and their order are those of the
+   degree branch of freesasa_gpu_cell_from_dcd, so a DCD record (len[0], deg[2], len[1], deg[1], deg[0], len[2]) in degrees gives
+   the same six doubles bit for bit.  Returns 0, or -1 with the reason in why (may be NULL).  Touches no device. */
+int freesasa_gpu_cell_from_lengths_angles(const double len[3], const double deg[3], double cell6_out[6], char *why, int why_len);
 
 /* Trajectory drivers (BASELINE configs[4]): frames of the SAME n_atoms atoms, radii constant.
    Frames are independent structures; a SHARD = frames_per_batch frames (<= 0: about 1.25e6 atoms) goes through the
@@ -513,11 +518,30 @@ int freesasa_gpu_cell_from_dcd(const double rec[6], double cell6_out[6], char *w
    failed read ("frame K of the DCD file is damaged"; the shard is not listed).  The done-list's f32= word carries bit 2
    and its header_bytes= the byte of frame 0: a raw run's list is refused by a DCD run and the other way round; a raw run's
    line is what it was.  Without bit 3 SASA is computed WITHOUT periodic images: a solute that the writer wrapped across the
-   box must be made whole beforehand.  Not offered: DCD files with fixed atoms or 64-bit record markers, other container
-   formats (XTC, TRR, NetCDF), a memory form.
+   box must be made whole beforehand.  Not offered: DCD files with fixed atoms or 64-bit record markers, XTC / TRR, a memory
+   form.
+
+   AMBER NetCDF input (all four file entries): with bit 5 of frames_f32 set (FREESASA_GPU_FRAMES_NETCDF) frames_path is an
+   AMBER NetCDF trajectory (convention 1.0, `.nc` as sander, pmemd, cpptraj, OpenMM and MDAnalysis write it): NetCDF classic,
+   version 1 or 2, big-endian, every frame one record at the same byte stride (freesasa_gpu_nc_info_read below has the
+   layout).  header_bytes must be 0, bits 0 and 2 clear; bit 1 keeps its meaning.  The frame count comes from the file's SIZE
+   (never from the header's numrecs), the byte of record 0 and the stride from its header; the file's atom count must equal
+   n_atoms (with a topology: frame_atoms) - a mismatch, a non-zero header_bytes, bit 0 or bit 2 is -1 with a message before a
+   device is touched or an output file opened.  A shard is one read and one host-to-device copy of whole records exactly as
+   they lie in the file - the time, the cell, velocities and forces of a record go up with it and are never read on the
+   device; ONE kernel (traj_kernels.h, traj_gather_nc) makes of the big-endian fp32 coordinates the compact fp64 frames the
+   engine reads, through the atom index when there is a topology.  There are no record markers to check.  The done-list's
+   f32= word carries bit 5 and its header_bytes= the byte of record 0: raw, DCD and NetCDF runs refuse each other's lists.
+   Periodic images: bits 3 and 4 may stand beside bit 5 as they stand beside bit 2, for a file with the variables
+   cell_lengths and cell_angles (fp64, in the same record).  Every frame's cell is decoded on the host from the staged bytes:
+   without bit 4 every angle v must satisfy |v - 90| <= 1e-4 (the angles are degrees: a 0 is not a right angle here) and every
+   edge must be finite and >= c; with bit 4 the cell goes through freesasa_gpu_cell_from_lengths_angles and the checks of a
+   DCD record.  A frame that fails ends the run ("frame K of the NetCDF file: ..." with the reason; the shard is not listed).
+   Refused up front: bit 3 on a file without the cell variables, freesasa_gpu_trajectory_file_groups with bit 3.
+   Not offered: XTC / TRR, NetCDF-4 (HDF5) and CDF-5 files, AMBER restart files, a scale_factor other than 1, a memory form.
 
    Periodic images (freesasa_gpu_trajectory_file, _file_devices, _file_topology): with bit 3 (FREESASA_GPU_FRAMES_PBC) beside
-   bit 2 every frame is computed among the periodic images its own unit-cell record implies, as freesasa_gpu_calc_periodic
+   bit 2 (beside bit 5: above) every frame is computed among the periodic images its own unit-cell record implies, as freesasa_gpu_calc_periodic
    below defines them - the atoms the engine sees (with a topology: the atoms the index keeps) wrapped into the cell, the
    first-shell images that can touch them added on the device in front of the engine, the areas and the total of the real
    atoms collected behind it; residues, class sums, selections, fp32 output and the files are what they are without the bit.
@@ -542,8 +566,9 @@ int freesasa_gpu_cell_from_dcd(const double rec[6], double cell6_out[6], char *w
 #define FREESASA_GPU_FRAMES_F32 1     /* frames_f32 bit 0: raw fp32 frames (input format) */
 #define FREESASA_GPU_FRAMES_OUT_F32 2 /* bit 1: per-atom (and isolated) areas written as fp32 (output format) */
 #define FREESASA_GPU_FRAMES_DCD 4     /* bit 2: frames_path is a DCD trajectory */
-#define FREESASA_GPU_FRAMES_PBC 8     /* bit 3: with bit 2, every frame among the periodic images of its cell record */
-#define FREESASA_GPU_FRAMES_TRICLINIC 16 /* bit 4: with bits 2 and 3, the cell record decoded as a triclinic cell */
+#define FREESASA_GPU_FRAMES_PBC 8     /* bit 3: with bit 2 or bit 5, every frame among the periodic images of its cell */
+#define FREESASA_GPU_FRAMES_TRICLINIC 16 /* bit 4: with bit 3, the cell decoded as a triclinic cell */
+#define FREESASA_GPU_FRAMES_NETCDF 32 /* bit 5: frames_path is an AMBER NetCDF trajectory */
 
 /* The header of a DCD file.  Every integer of the file is an int32 in the file's byte order; records lie between two equal
    byte counts:  [84 | "CORD" | 20 control words | 84]  [m | NTITLE | 80 NTITLE bytes | m]  [4 | NATOM | 4], then per frame
@@ -564,6 +589,40 @@ typedef struct freesasa_gpu_dcd_info {
     int32_t big_endian, has_cell, has_4d, charmm_version;
 } freesasa_gpu_dcd_info;
 int freesasa_gpu_dcd_info_read(const char *path, freesasa_gpu_dcd_info *out, char *err, int err_len); /* 0 / -1 */
+
+/* The header of an AMBER NetCDF trajectory.  The file is NetCDF classic, every integer big-endian and 32 bits wide unless said
+   otherwise:  'C' 'D' 'F' version (1, or 2: a variable's begin is 8 bytes) | numrecs (0xFFFFFFFF: streaming) | dim_list |
+   gatt_list | var_list, each list ABSENT (two zero words) or [tag | nelems | elements] with the tags 0x0A dimensions, 0x0C
+   attributes, 0x0B variables.  name = length, bytes, padded to 4; dim = name, length (0: the record dimension); attr = name,
+   nc_type, nelems, values padded to 4; var = name, ndims, dimid[ndims], its attribute list, nc_type, vsize, begin; nc_type and
+   bytes: BYTE 1/1, CHAR 2/1, SHORT 3/2, INT 4/4, FLOAT 5/4, DOUBLE 6/8.  A record variable is one whose first dimension is the
+   record dimension; the record size is the sum of the record variables' vsize (each padded to 4; with exactly one record
+   variable its unpadded size); record 0 begins at the smallest begin among them, and variable v of frame f lies at
+   begin_v + f * record size.
+   What must hold: the global CHAR attribute Conventions has AMBER among its tokens (split on ',' and ' '; AMBERRESTART is
+   a restart file, not a trajectory); `coordinates` is NC_FLOAT over (record dimension, `atom`, a dimension of length 3) and
+   has no scale_factor other than 1; 0 < atoms, 12 atoms < 2^31; cell_lengths and cell_angles, where present, are NC_DOUBLE
+   record variables over (record dimension, a dimension of length 3): has_cell when both are.
+   Returns 0, or -1 with a message in err that says which check failed: those above, a NetCDF-4 (HDF5) or CDF-5 file, a file
+   that is not CDF, a header that ends before its grammar or is longer than 64 KiB, a count, name length, dimid or begin that
+   points outside the header or the file, a record layout that is not made of 32-bit words or does not hold its variables, a
+   file that holds no whole record.  A tail that is not a whole record is ignored.  Reads the first 64 KiB of the file into a
+   buffer of its own and nothing outside it; allocates nothing. */
+typedef struct freesasa_gpu_nc_info {
+    int32_t n_atoms;          /* the dimension `atom` */
+    int64_t n_frames;         /* whole records by FILE SIZE */
+    int64_t n_frames_header;  /* numrecs as the header claims, -1: streaming (reported, never trusted) */
+    int64_t first_record;     /* byte of record 0 */
+    int64_t record_bytes;     /* constant stride */
+    int64_t coord_off;        /* byte of `coordinates` within a record */
+    int64_t lengths_off, angles_off; /* of cell_lengths and cell_angles; -1 without a cell */
+    int32_t version;          /* 1 or 2 */
+    int32_t has_cell, has_time, has_velocities;
+} freesasa_gpu_nc_info;
+int freesasa_gpu_nc_info_read(const char *path, freesasa_gpu_nc_info *out, char *err, int err_len); /* 0 / -1 */
+/* The cell of frame f of the records at `records` (frame 0's first byte; info->has_cell): three edge lengths and alpha, beta,
+   gamma in degrees, in the host's byte order.  The offsets are multiples of 4, not of 8: copied byte by byte. */
+void freesasa_gpu_nc_cell_record(const freesasa_gpu_nc_info *info, const void *records, long long f, double lengths_out[3], double angles_out[3]);
 
 int freesasa_gpu_trajectory(const double *xyz_frames, const double *radii, int n_atoms, int n_frames,
                             int alg, double probe_radius, int resolution, int frames_per_batch,
@@ -606,7 +665,7 @@ int freesasa_gpu_trajectory(const double *xyz_frames, const double *radii, int n
    Argument errors - NULL batch, structure out of range, a structure that failed to load or has no atoms, a bad index,
    frame_atoms < n - return -1 with a message before a device is touched or a file opened.
    Returns as the plain drivers: 0 / -1, the file form 1 when max_new_shards stopped it.
-   Not offered: relative areas in files, trajectory container formats other than DCD.  (Chain groups: freesasa_gpu_trajectory_groups below.) */
+   Not offered: relative areas in files, trajectory container formats other than DCD and AMBER NetCDF.  (Chain groups: freesasa_gpu_trajectory_groups below.) */
 int freesasa_gpu_trajectory_topology(const double *xyz_frames, int n_frames, const struct freesasa_ingest_batch *batch, int structure,
                                      int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
                                      int alg, double probe_radius, int resolution, int frames_per_batch,
@@ -648,7 +707,7 @@ int freesasa_gpu_trajectory_file_topology(const char *frames_path, int frames_f3
    Argument errors, -1 with a message before a device is touched or a file opened: an id < -1 or >= n_groups (the message
    names the atom and the id), n_groups out of range, group given without group areas or either output without group.
    Not offered: a buried area per residue, group ids made on the device for a trajectory (make them once with
-   freesasa_gpu_chain_group_ids), trajectory container formats other than DCD. */
+   freesasa_gpu_chain_group_ids), trajectory container formats other than DCD and AMBER NetCDF. */
 int freesasa_gpu_trajectory_groups(const double *xyz_frames, int n_frames, const struct freesasa_ingest_batch *batch, int structure,
                                    int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
                                    const int32_t *group, int n_groups,

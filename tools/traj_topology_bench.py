@@ -17,6 +17,9 @@ With --dcd the arms are instead
     dcd       the same call on a little-endian DCD file with a unit-cell record that holds the same fp32 values (12 N + 80 bytes
               per frame against 12 N; de-planarized, gathered and widened by one kernel on the device)
 timed in one process, interleaved; the totals files must be identical.
+With --netcdf (alone or beside --dcd) one arm more, interleaved with the others:
+    netcdf    the same call on an AMBER NetCDF file (64-bit offset, written here) whose records hold the time, the same fp32 values
+              big-endian and the cell: 12 N + 52 bytes per frame; byte-swapped, gathered and widened by one kernel on the device
 
 With --pbc the arms are the periodic images of the DCD drivers (FREESASA_GPU_FRAMES_PBC) against the same call without the bit,
 on two DCD files with a unit-cell record:
@@ -36,9 +39,12 @@ With --triclinic beside --pbc (FREESASA_GPU_FRAMES_TRICLINIC) three arms more, i
                   from calc_periodic_triclinic on frame 0.  The globule was not built for that cell: where its corners wrap onto
                   its faces atoms overlap, which a cost measurement can live with.
 
+With --netcdf beside --pbc two arms more: `solvated` and `solvated-pbc` on an AMBER NetCDF file of the same frames and cell
+(solvated-nc, solvated-nc-pbc); their totals files must be those of the DCD arms, byte for byte.
+
 One JSON line per arm: atom-frames/s counted in SOLUTE atoms and in frame atoms, the median and the spread of --reps runs.
 
-    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd] [--pbc [--pbc-arms all|off] [--triclinic]]
+    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd] [--netcdf] [--pbc [--pbc-arms all|off] [--triclinic]]
 
 For the kernel times: `rocprofv3 --kernel-trace --stats -- python tools/traj_topology_bench.py --reps 1 --arms all`
 (k_traj_gather / k_traj_residues / k_traj_class / k_traj_sel are the topology's kernels, k_traj_group_* the groups')."""
@@ -87,14 +93,40 @@ def dcd_header(n_atoms, n_frames):
     return rec(b"CORD" + struct.pack("<20i", *icntrl)) + rec(struct.pack("<i", 1) + b"REMARKS traj_topology_bench".ljust(80)) + rec(struct.pack("<i", n_atoms))
 
 
-def make_frames(scratch, xyz, n_frames, dcd=False):
+def nc_header(n_atoms, n_frames):
+    """a NetCDF classic header (64-bit offset) in the AMBER trajectory convention: a record holds time (fp32), coordinates (fp32),
+    cell_lengths and cell_angles (fp64), all big-endian"""
+    name = lambda t: struct.pack(">i", len(t)) + t.encode() + b"\0" * (-len(t) % 4)
+    text = lambda k, v: name(k) + struct.pack(">ii", 2, len(v)) + v.encode() + b"\0" * (-len(v) % 4)
+    dims = [("frame", 0), ("spatial", 3), ("atom", n_atoms), ("cell_spatial", 3), ("cell_angular", 3)]
+    gatts = [("Conventions", "AMBER"), ("ConventionVersion", "1.0"), ("program", "traj_topology_bench")]
+    variables = [("time", (0,), 5, 4), ("coordinates", (0, 2, 1), 5, 12 * n_atoms), ("cell_lengths", (0, 3), 6, 24), ("cell_angles", (0, 4), 6, 24)]
+    head = b"CDF\x02" + struct.pack(">iii", n_frames, 0x0A, len(dims)) + b"".join(name(d) + struct.pack(">i", n) for d, n in dims)
+    head += struct.pack(">ii", 0x0C, len(gatts)) + b"".join(text(k, v) for k, v in gatts) + struct.pack(">ii", 0x0B, len(variables))
+    metas = [name(v) + struct.pack(">i", len(d)) + b"".join(struct.pack(">i", k) for k in d) + b"\0" * 8 + struct.pack(">ii", t, size)
+             for v, d, t, size in variables]
+    begin = len(head) + sum(len(m) + 8 for m in metas)
+    for m, v in zip(metas, variables):
+        head += m + struct.pack(">q", begin)
+        begin += v[3]
+    return head
+
+
+def nc_record(f, frame, cell):
+    return struct.pack(">f", f) + frame.astype(">f4").tobytes() + np.array(list(cell) + [90.0] * 3).astype(">f8").tobytes()
+
+
+def make_frames(scratch, xyz, n_frames, dcd=False, nc=False):
     full, bare, as_dcd = os.path.join(scratch, "solvated.f32"), os.path.join(scratch, "solute.f32"), os.path.join(scratch, "solvated.dcd")
+    as_nc = os.path.join(scratch, "solvated.nc")
     rng = np.random.default_rng(5)
     half = 1.3 * np.abs(xyz).max()
     plane = struct.pack("<i", 4 * N_FRAME)
     cell = struct.pack("<i", 48) + np.array([2 * half, 0, 2 * half, 0, 0, 2 * half]).astype("<f8").tobytes() + struct.pack("<i", 48)
-    with open(full, "wb") as f_full, open(bare, "wb") as f_bare, open(as_dcd if dcd else os.devnull, "wb") as f_dcd:
+    with open(full, "wb") as f_full, open(bare, "wb") as f_bare, open(as_dcd if dcd else os.devnull, "wb") as f_dcd, \
+            open(as_nc if nc else os.devnull, "wb") as f_nc:
         f_dcd.write(dcd_header(N_FRAME, n_frames))
+        f_nc.write(nc_header(N_FRAME, n_frames))
         for f in range(n_frames):
             s = (xyz + rng.uniform(-0.25, 0.25, xyz.shape)).astype(np.float32)
             w = rng.uniform(-half, half, (N_FRAME - N_SOLUTE, 3)).astype(np.float32)
@@ -103,13 +135,16 @@ def make_frames(scratch, xyz, n_frames, dcd=False):
             frame.tofile(f_full)
             if dcd:
                 f_dcd.write(cell + b"".join(plane + np.ascontiguousarray(frame[:, k]).tobytes() + plane for k in range(3)))
-    return full, bare, as_dcd
+            if nc:
+                f_nc.write(nc_record(f, frame, [2 * half] * 3))
+    return full, bare, as_dcd, as_nc
 
 
-def make_pbc_frames(scratch, xyz, n_frames, octa=False):
+def make_pbc_frames(scratch, xyz, n_frames, octa=False, nc=False):
     """the two DCD files of --pbc -> (solvated path, its cell, filled path, its cell); coordinates as make_frames draws them,
     moved so that the cell begins at 0.  octa: behind them the path of a third file - filled's frames with the record of a
-    truncated octahedron of filled's volume - and that record"""
+    truncated octahedron of filled's volume - and that record.  nc: beside the solvated file an AMBER NetCDF file of the same frames
+    and cell, solvated_pbc.nc"""
     rng = np.random.default_rng(5)
     half = 1.3 * np.abs(xyz).max()
     lo = xyz.min(0) - 0.5 * 2.6 - 0.25
@@ -119,13 +154,16 @@ def make_pbc_frames(scratch, xyz, n_frames, octa=False):
         path = os.path.join(scratch, name)
         plane = struct.pack("<i", 4 * n)
         rec = struct.pack("<i", 48) + np.array([cell[0], 0, cell[1], 0, 0, cell[2]]).astype("<f8").tobytes() + struct.pack("<i", 48)
-        with open(path, "wb") as fh:
+        with open(path, "wb") as fh, open(os.path.join(scratch, "solvated_pbc.nc") if nc and n > N_SOLUTE else os.devnull, "wb") as f_nc:
             fh.write(dcd_header(n, n_frames))
+            f_nc.write(nc_header(n, n_frames))
             for f in range(n_frames):
                 frame = (xyz + rng.uniform(-0.25, 0.25, xyz.shape) + shift).astype(np.float32)
                 if n > N_SOLUTE:
                     frame = np.concatenate([frame, rng.uniform(0, 2 * half, (n - N_SOLUTE, 3)).astype(np.float32)])
                 fh.write(rec + b"".join(plane + np.ascontiguousarray(frame[:, k]).tobytes() + plane for k in range(3)))
+                if nc and n > N_SOLUTE:
+                    f_nc.write(nc_record(f, frame, cell))
         out += [path, cell]
     if octa:
         d = float(np.prod(out[3]) / (4.0 * np.sqrt(3.0) / 9.0)) ** (1.0 / 3.0)     # the volume of GROMACS's cell of vector length d is 4 sqrt(3) / 9 d^3
@@ -171,6 +209,8 @@ def main():
     ap.add_argument("--scratch", default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--dcd", action="store_true", help="time the raw fp32 file against a DCD file of the same frames")
+    ap.add_argument("--netcdf", action="store_true", help="time the raw fp32 file (and with --dcd the DCD file) against an AMBER NetCDF file of the same "
+                                                          "frames; with --pbc: the solvated arms on a NetCDF file as well")
     ap.add_argument("--pbc", action="store_true", help="time the DCD drivers with and without periodic images")
     ap.add_argument("--pbc-arms", default="all", choices=["all", "off"])
     ap.add_argument("--triclinic", action="store_true", help="with --pbc: the arms of the triclinic bit beside the others")
@@ -178,7 +218,7 @@ def main():
     scratch = args.scratch or tempfile.mkdtemp(prefix="traj_topology_bench_")
     try:
         b, xyz = solute()
-        full, bare, as_dcd = make_frames(scratch, xyz, args.frames, args.dcd) if not args.pbc else (None, None, None)
+        full, bare, as_dcd, as_nc = make_frames(scratch, xyz, args.frames, args.dcd, args.netcdf) if not args.pbc else (None, None, None, None)
         sel = ingest.Selection(EIGHT)
         index = np.arange(N_SOLUTE, dtype=np.int32)
         ids = (np.arange(N_SOLUTE) >= N_SOLUTE // 2).astype(np.int32)
@@ -196,10 +236,16 @@ def main():
             arms = {"raw": arms["totals"],
                     "dcd": lambda: fa.trajectory_file_topology(as_dcd, b, p("t5"), atom_index=index, dcd=True)}
             assert fa.dcd_info(as_dcd).n_frames == args.frames and os.path.getsize(as_dcd) - os.path.getsize(full) == 80 * args.frames + 196
+        if args.netcdf and not args.pbc:
+            arms = {"raw": arms["raw" if args.dcd else "totals"], **({"dcd": arms["dcd"]} if args.dcd else {}),
+                    "netcdf": lambda: fa.trajectory_file_topology(as_nc, b, p("t13"), atom_index=index, netcdf=True)}
+            info = fa.nc_info(as_nc)
+            assert info.n_frames == args.frames and info.record_bytes == 12 * N_FRAME + 52 and info.has_cell
         images = {}
         if args.pbc:
             tri = args.triclinic and args.pbc_arms == "all"
-            solv, solv_cell, fill, fill_cell, *octa = make_pbc_frames(scratch, xyz, args.frames, tri)
+            solv, solv_cell, fill, fill_cell, *octa = make_pbc_frames(scratch, xyz, args.frames, tri, args.netcdf)
+            solv_nc = os.path.join(scratch, "solvated_pbc.nc")
             arms = {"solvated": lambda: fa.trajectory_file_topology(solv, b, p("t6"), atom_index=index, dcd=True),
                     "filled": lambda: fa.trajectory_file(fill, b.radii, p("t8"), dcd=True)}
             if args.pbc_arms == "all":
@@ -211,7 +257,11 @@ def main():
                 arms.update({"solvated-tri": lambda: fa.trajectory_file_topology(solv, b, p("t10"), atom_index=index, dcd=True, pbc=True, triclinic=True),
                              "filled-tri": lambda: fa.trajectory_file(fill, b.radii, p("t11"), dcd=True, pbc=True, triclinic=True),
                              "octa-tri": lambda: fa.trajectory_file(octa[0], b.radii, p("t12"), dcd=True, pbc=True, triclinic=True)})
-        names = list(arms) if args.dcd or args.pbc else [a for a in args.arms.split(",") if a in arms]
+            if args.netcdf:
+                arms["solvated-nc"] = lambda: fa.trajectory_file_topology(solv_nc, b, p("t14"), atom_index=index, netcdf=True)
+                if args.pbc_arms == "all":
+                    arms["solvated-nc-pbc"] = lambda: fa.trajectory_file_topology(solv_nc, b, p("t15"), atom_index=index, netcdf=True, pbc=True)
+        names = list(arms) if args.dcd or args.netcdf or args.pbc else [a for a in args.arms.split(",") if a in arms]
         runs = {a: [] for a in names}
         for a in names:
             arms[a]()                                                    # warm-up: contexts, staging, page cache
@@ -224,15 +274,18 @@ def main():
         if args.pbc and hasattr(fa, "calc_periodic"):    # (behind the timed runs: a batch of another shape leaves its launch history in a pooled context)
             for a, path, cell in (("solvated", solv, solv_cell), ("filled", fill, fill_cell)):
                 k = fa.calc_periodic(first_frame(path, N_SOLUTE), b.radii, [0, N_SOLUTE], [cell])[2]
-                images[a] = images[a + "-pbc"] = images[a + "-tri"] = float(k[0]) / N_SOLUTE
+                images[a] = images[a + "-pbc"] = images[a + "-tri"] = images[a + "-nc"] = images[a + "-nc-pbc"] = float(k[0]) / N_SOLUTE
             if tri:
                 k = fa.calc_periodic_triclinic(first_frame(octa[0], N_SOLUTE), b.radii, [0, N_SOLUTE], [fa.cell_from_dcd(octa[1])])[2]
                 images["octa-tri"] = float(k[0]) / N_SOLUTE
-        totals = [np.fromfile(p(k)) for a, k in (("plain", "t0"), ("totals", "t1"), ("all", "t2"), ("groups", "t3"), ("raw", "t1"), ("dcd", "t5")) if a in names]
+        totals = [np.fromfile(p(k)) for a, k in (("plain", "t0"), ("totals", "t1"), ("all", "t2"), ("groups", "t3"), ("raw", "t1"), ("dcd", "t5"), ("netcdf", "t13")) if a in names]
         assert all(np.array_equal(t, totals[0]) for t in totals)
         if "solvated-pbc" in names:      # no atom of the solute within c of a face: the bit changes nothing; a filled box: it must
             assert images["solvated"] > 0 or np.array_equal(np.fromfile(p("t6")), np.fromfile(p("t7")))
             assert np.all(np.fromfile(p("t9")) < np.fromfile(p("t8")))
+        if "solvated-nc" in names:       # the NetCDF arms: the files of the DCD arms
+            assert np.array_equal(np.fromfile(p("t14")), np.fromfile(p("t6")))
+            assert "solvated-nc-pbc" not in names or np.array_equal(np.fromfile(p("t15")), np.fromfile(p("t7")))
         if "filled-tri" in names:        # right-angled records through the general geometry: the files of the arms without bit 4
             assert np.array_equal(np.fromfile(p("t10")), np.fromfile(p("t7"))) and np.array_equal(np.fromfile(p("t11")), np.fromfile(p("t9")))
         assert not ("groups" in names and "longway" in names) or np.array_equal(np.fromfile(p("g3")), np.fromfile(p("g4")))
