@@ -716,7 +716,7 @@ def trajectory(xyz_frames, radii, alg=LEE_RICHARDS, probe=1.4, resolution=20, fr
     return totals, sasa
 
 
-FRAMES_F32, FRAMES_OUT_F32, FRAMES_DCD, FRAMES_PBC, FRAMES_TRICLINIC, FRAMES_NETCDF = 1, 2, 4, 8, 16, 32   # the bits of frames_f32 (include/freesasa_gpu.h)
+FRAMES_F32, FRAMES_OUT_F32, FRAMES_DCD, FRAMES_PBC, FRAMES_TRICLINIC, FRAMES_NETCDF, FRAMES_XTC = 1, 2, 4, 8, 16, 32, 64   # the bits of frames_f32 (include/freesasa_gpu.h)
 
 
 class DcdInfoC(C.Structure):
@@ -784,18 +784,50 @@ def nc_info(path):
     return NcInfo(c)
 
 
-def _frames_bits(f32, out_f32, dcd, header_bytes, pbc=False, triclinic=False, netcdf=False):
+class XtcInfoC(C.Structure):
+    _fields_ = [("n_atoms", C.c_int32), ("n_frames", C.c_int64), ("max_frame_bytes", C.c_int64), ("precision", C.c_float), ("has_box", C.c_int32)]
+
+
+class XtcInfo:
+    """What xtc_info() returns: the fields of freesasa_gpu_xtc_info (include/freesasa_gpu.h) - n_atoms, n_frames (by one pass
+    over the frames' headers), max_frame_bytes (the longest frame, header and padding included), precision (frame 0's) and
+    has_box (frame 0's box has a non-zero element) as a bool."""
+
+    def __init__(self, c):
+        self.n_atoms, self.n_frames, self.max_frame_bytes = int(c.n_atoms), int(c.n_frames), int(c.max_frame_bytes)
+        self.precision, self.has_box = float(c.precision), bool(c.has_box)
+
+    def __repr__(self):
+        return "XtcInfo(" + ", ".join(f"{name}={getattr(self, name)}" for name, _ in XtcInfoC._fields_) + ")"
+
+
+def xtc_info(path):
+    """freesasa_gpu_xtc_info_read(): one pass over the headers of a GROMACS XTC trajectory -> XtcInfo; ValueError with the
+    library's message, which names the frame, for a file that is no XTC file, is damaged, or is one the drivers do not read
+    (magic 2023, frames of 9 atoms or fewer)."""
+    L = lib()
+    L.freesasa_gpu_xtc_info_read.argtypes = [C.c_char_p, C.POINTER(XtcInfoC), C.c_char_p, C.c_int]
+    c = XtcInfoC()
+    err = C.create_string_buffer(512)
+    if L.freesasa_gpu_xtc_info_read(str(path).encode(), C.byref(c), err, 512):
+        raise ValueError("freesasa_gpu_xtc_info_read: " + err.value.decode())
+    return XtcInfo(c)
+
+
+def _frames_bits(f32, out_f32, dcd, header_bytes, pbc=False, triclinic=False, netcdf=False, xtc=False):
     if dcd and (f32 or header_bytes):
         raise ValueError("dcd=True excludes f32=True and a non-zero header_bytes: a DCD file says for itself where its frames are")
     if netcdf and (dcd or f32 or header_bytes):
         raise ValueError("netcdf=True excludes dcd=True, f32=True and a non-zero header_bytes: an AMBER NetCDF file says for itself where its frames are")
+    if xtc and (dcd or netcdf or f32 or header_bytes):
+        raise ValueError("xtc=True excludes dcd=True, netcdf=True, f32=True and a non-zero header_bytes: an XTC file's frames are found by their headers")
     return (FRAMES_F32 if f32 else 0) | (FRAMES_OUT_F32 if out_f32 else 0) | (FRAMES_DCD if dcd else 0) | (FRAMES_PBC if pbc else 0) | \
-        (FRAMES_TRICLINIC if triclinic else 0) | (FRAMES_NETCDF if netcdf else 0)
+        (FRAMES_TRICLINIC if triclinic else 0) | (FRAMES_NETCDF if netcdf else 0) | (FRAMES_XTC if xtc else 0)
 
 
 def trajectory_file(frames_path, radii, totals_path, sasa_path=None, done_path=None, f32=False, header_bytes=0,
                     n_frames=0, alg=LEE_RICHARDS, probe=1.4, resolution=20, frames_per_batch=0, max_new_shards=0, device=-1,
-                    devices=None, out_f32=False, dcd=False, pbc=False, triclinic=False, netcdf=False):
+                    devices=None, out_f32=False, dcd=False, pbc=False, triclinic=False, netcdf=False, xtc=False):
     """freesasa_gpu_trajectory_file(): raw frame file -> totals file (+ per-atom file), resumable through the
     done-list at done_path.  Returns (complete, n_frames): complete is False when max_new_shards stopped the run.
     f32: the frames are floats (an input format); out_f32: the per-atom file holds floats (an output format);
@@ -803,9 +835,11 @@ def trajectory_file(frames_path, radii, totals_path, sasa_path=None, done_path=N
     pbc: (with dcd) every frame among the periodic images its unit-cell record implies, as calc_periodic defines them;
     triclinic: (with dcd and pbc) the record decoded by cell_from_dcd, the frame as calc_periodic_triclinic defines it;
     netcdf: frames_path is an AMBER NetCDF trajectory whose atom count is len(radii) (no dcd, no f32, no header_bytes with
-    it); pbc and triclinic go with it as with dcd: the cell is the frame's cell_lengths and cell_angles (cell_from_lengths_angles)."""
+    it); pbc and triclinic go with it as with dcd: the cell is the frame's cell_lengths and cell_angles (cell_from_lengths_angles);
+    xtc: frames_path is a GROMACS XTC trajectory whose atom count is len(radii) (no dcd, no netcdf, no f32, no header_bytes with
+    it), decoded on the device; pbc and triclinic go with it as with dcd: the cell is the frame's box, nm * 10."""
     radii = _f64(radii)
-    f32 = _frames_bits(f32, out_f32, dcd, header_bytes, pbc, triclinic, netcdf)
+    f32 = _frames_bits(f32, out_f32, dcd, header_bytes, pbc, triclinic, netcdf, xtc)
     err = C.create_string_buffer(512)
     total = C.c_longlong(0)
     enc = lambda p: None if p is None else str(p).encode()
@@ -949,7 +983,7 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
                              f32=False, header_bytes=0, n_frames=0, alg=LEE_RICHARDS, probe=1.4, resolution=20, frames_per_batch=0,
                              max_new_shards=0, device=-1, devices=None, out_f32=False, chain_groups=None, separate_chains=False,
                              long=False, group=None, n_groups=None, group_areas_path=None, isolated_path=None, dcd=False, pbc=False,
-                             triclinic=False, netcdf=False):
+                             triclinic=False, netcdf=False, xtc=False):
     """freesasa_gpu_trajectory_file_topology(): trajectory_file() with a topology (see trajectory_topology; frame_atoms:
     atoms per frame of the file, None: the structure's) and one raw fp64 result file per output asked for: class sums
     [F, 3], residues [F, R, 6], selection areas [F, S].  Returns (complete, n_frames, selection_atoms [S] or None).
@@ -958,13 +992,16 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
     dcd: frames_path is a DCD trajectory; frame_atoms None is then the file's NATOM.
     pbc: (with dcd) the atoms the index keeps among their periodic images, frame by frame (not offered with chain groups);
     triclinic: (with dcd and pbc) the cell records decoded as triclinic cells, see trajectory_file;
-    netcdf: frames_path is an AMBER NetCDF trajectory; frame_atoms None is then the file's atom count; pbc and triclinic as with dcd."""
+    netcdf: frames_path is an AMBER NetCDF trajectory; frame_atoms None is then the file's atom count; pbc and triclinic as with dcd;
+    xtc: frames_path is a GROMACS XTC trajectory; frame_atoms None is then the file's atom count; pbc and triclinic as with dcd."""
     L = _topology_proto(lib())
-    bits = _frames_bits(f32, out_f32, dcd, header_bytes, pbc, triclinic, netcdf)
+    bits = _frames_bits(f32, out_f32, dcd, header_bytes, pbc, triclinic, netcdf, xtc)
     if dcd and frame_atoms is None:
         frame_atoms = dcd_info(frames_path).n_atoms
     if netcdf and frame_atoms is None:
         frame_atoms = nc_info(frames_path).n_atoms
+    if xtc and frame_atoms is None:
+        frame_atoms = xtc_info(frames_path).n_atoms
     n, R, res_ref, idx, fa_ = _topology_args(batch, structure, atom_index, frame_atoms)
     S = len(selection) if selection is not None else 0
     sel_atoms = np.zeros(S, dtype=np.int64) if selection is not None else None

@@ -158,6 +158,9 @@ struct TrajIO {
     freesasa_gpu_dcd_info dcd = {}; /* ... and this says where their planes are (dcd.c) */
     bool in_nc = false;             /* the file is an AMBER NetCDF trajectory: its records go up as they lie in the file ... */
     freesasa_gpu_nc_info nc = {};   /* ... and this says where their coordinates and their cell are (netcdf.c) */
+    bool in_xtc = false;            /* the file is a GROMACS XTC trajectory: compressed frames of unequal length, decoded on the device ... */
+    freesasa_gpu_xtc_info xtc = {}; /* ... what the pass over its headers found (xtc.c) ... */
+    std::vector<int64_t> xtc_off;   /* ... and its index: the byte of every frame [n_frames + 1], by which the shards are cut */
     bool pbc = false;               /* FREESASA_GPU_FRAMES_PBC: every frame among the images its cell record implies (gpu_periodic.hip) */
     bool tri = false;               /* ... FREESASA_GPU_FRAMES_TRICLINIC beside it: the record decoded as a triclinic cell */
     /* per frame: total [1], per-atom areas [n]; runs with a topology: class sums [3], residue areas [6 R], selection areas [S];
@@ -362,8 +365,10 @@ struct TrajRun {
     const long long n_shards = (s.n_frames + s.frames_per_batch - 1) / s.frames_per_batch;
     /* a topology: frames of fa atoms come in (with an index the gather makes the engine's n of them); esz bytes per atom */
     const bool gather = topo && topo->index;
-    const size_t fa = topo ? (size_t)topo->frame_atoms : n, esz = io.in_f32 ? 12 : 24;
-    const size_t widen_bytes = io.in_f32 && !gather ? 12 * n * FB : 0; /* (fp32 frames without an index: kl_widen_f32's input) */
+    /* (an XTC file's frames are raw fp32 frames once xtc_unpack has written them: from there on the run is a raw fp32 run) */
+    const bool xtc = io.in_xtc, f32 = io.in_f32 || xtc;
+    const size_t fa = topo ? (size_t)topo->frame_atoms : n, esz = f32 ? 12 : 24;
+    const size_t widen_bytes = f32 && !gather ? 12 * n * FB : 0; /* (fp32 frames without an index: kl_widen_f32's input) */
     /* bytes from one input frame to the next: raw frames, or a DCD / NetCDF file's stride (kl_traj_gather_dcd / _nc then does
        the gather's and the widening's work, with or without an index) */
     const bool dcd = io.in_dcd, netcdf = io.in_nc, container = dcd || netcdf;
@@ -375,6 +380,17 @@ struct TrajRun {
     static size_t cells_at(size_t in_bytes) { return (in_bytes + 7) & ~(size_t)7; }
     /* (a triclinic run: per frame the six numbers of the cell and its three widths) */
     const size_t cell_bytes = io.tri ? 8 * PBC_TRI_CELL : 24;
+    /* An XTC shard on the device (c->g_xyz), every part at a multiple of 8: its bytes | its cells (periodic runs) | one descriptor
+       per frame - up to here the one copy from the host - | group count and status per frame | the group records (at a multiple
+       of 16) | with an index the fp32 frames xtc_unpack writes (without: kl_widen_f32's input, c->h_counts) */
+    size_t xtc_desc_at(size_t in_bytes, size_t nf) const { return cells_at(in_bytes) + (pbc ? cell_bytes * nf : 0); }
+    size_t xtc_count_at(size_t in_bytes, size_t nf) const { return xtc_desc_at(in_bytes, nf) + sizeof(freesasa_gpu_xtc_frame) * nf; }
+    size_t xtc_rec_at(size_t in_bytes, size_t nf) const { return (xtc_count_at(in_bytes, nf) + 8 * nf + 15) & ~(size_t)15; }
+    size_t xtc_f32_at(size_t in_bytes, size_t nf) const { return xtc_rec_at(in_bytes, nf) + sizeof(sasa::XtcRec) * fa * nf; }
+    size_t xtc_max_bytes = 0; /* the bytes of the index's largest shard */
+    size_t shard_bytes(long long f0, long long nf) const { return xtc ? (size_t)(io.xtc_off[(size_t)(f0 + nf)] - io.xtc_off[(size_t)f0]) : stride * (size_t)nf; }
+    /* what goes up in a shard's one copy */
+    size_t up_bytes(size_t in_bytes, size_t nf) const { return xtc ? xtc_count_at(in_bytes, nf) : pbc ? cells_at(in_bytes) + cell_bytes * nf : in_bytes; }
     /* the caller's arrays are page-locked: no staging */
     const bool in_pinned = io.mem_in && host_pinned(io.mem_in);
     const bool direct_out = io.out[OUT_TOTALS].mem && host_pinned(io.out[OUT_TOTALS].mem) && (!io.out[OUT_SASA].mem || host_pinned(io.out[OUT_SASA].mem)) &&
@@ -411,6 +427,10 @@ struct TrajRun {
             if (k >= OUT_CLS) x0[k + 1] = x0[k] + io.out[k].per_frame;
         }
         xw = x0[N_OUT] + S;
+        for (long long k = 0; xtc && k < n_shards; ++k) {
+            const long long f0 = k * s.frames_per_batch, nf = s.n_frames - f0 < s.frames_per_batch ? s.n_frames - f0 : s.frames_per_batch;
+            if (shard_bytes(f0, nf) > xtc_max_bytes) xtc_max_bytes = shard_bytes(f0, nf);
+        }
     }
 };
 /* a lane: its pooled context and what it has put there once */
@@ -442,7 +462,8 @@ int shard_size(TrajRun &T, TrajLane &L)
     if (ensure(c, c->h_xyz, 24 * nc * FB) || ensure(c, c->h_radii, T.groups ? 8 * nc * FB : 8 * n) || ensure(c, c->h_sasa, 8 * nc * FB) ||
         ensure(c, c->h_totals, 8 * (1 + T.G) * FB) ||
         (T.widen_bytes + narrow_bytes && ensure(c, c->h_counts, T.widen_bytes + narrow_bytes)) ||
-        ((T.gather || T.container) && ensure(c, c->g_xyz, T.pbc ? TrajRun::cells_at(T.stride * FB) + T.cell_bytes * FB : T.stride * FB)) || (T.xw && ensure(c, c->h_gtot, 8 * T.xw * FB)) ||
+        ((T.gather || T.container || T.xtc) && ensure(c, c->g_xyz, T.xtc ? T.xtc_f32_at(T.xtc_max_bytes, FB) + (T.gather ? 12 * T.fa * FB : 0)
+                                                                        : T.pbc ? TrajRun::cells_at(T.stride * FB) + T.cell_bytes * FB : T.stride * FB)) || (T.xw && ensure(c, c->h_gtot, 8 * T.xw * FB)) ||
         (T.groups && (ensure(c, c->g_gath, 8 * nc * FB) || ensure(c, c->g_tot2, 8 * (1 + T.G) * FB))) || (iso && ensure(c, c->h_iso, 8 * n * FB)))
         return -1;
     if (!T.groups && !L.radii_up && hipMemcpyAsync(c->h_radii.p, T.s.radii, 8 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "radii upload failed");
@@ -572,6 +593,68 @@ long long nc_cells(const freesasa_gpu_nc_info &d, const char *bytes, long long n
     return -1;
 }
 
+/* The descriptors of the XTC frames [f0, f0 + nf) at `bytes` (xtc.c: every header checked again as it lies in the staging - the
+   device trusts the descriptors for its bounds - and against the index: a frame must be as long as the index pass found it).
+   Returns -1, or the first frame that fails, the reason in why. */
+long long xtc_descriptors(const TrajIO &io, const char *bytes, long long f0, long long nf, int frame_atoms, freesasa_gpu_xtc_frame *desc, char *why, size_t why_len)
+{
+    const int64_t *off = io.xtc_off.data() + f0;
+    for (long long f = 0; f < nf; ++f) {
+        long long frame_bytes = 0;
+        const long long at = off[f] - off[0], len = off[f + 1] - off[f];
+        if (freesasa_gpu_xtc_frame_desc(bytes + at, len, frame_atoms, at + FREESASA_GPU_XTC_HEADER, &desc[f], &frame_bytes, why, (int)why_len)) return f;
+        if (frame_bytes != len) { snprintf(why, why_len, "its header is not the one the index was made from"); return f; }
+    }
+    return -1;
+}
+
+/* The cells of the same frames: a frame's box is nine floats in nm, GROMACS' lower triangle - rows a = (ax, 0, 0), b = (bx, by, 0),
+   c = (cx, cy, cz) -, each element (double) float * 10.0.  Orthorhombic runs: the edges into cells[nf][3]; triclinic runs:
+   cells[nf][9] as dcd_cells_tri fills it, through tri_cell_bad.  Returns -1, or the first frame whose box periodic images are not
+   offered for, the reason in why. */
+long long xtc_cells(const TrajIO &io, const char *bytes, long long f0, long long nf, bool tri, double cut, double *cells, char *why, size_t why_len)
+{
+    const int64_t *off = io.xtc_off.data() + f0;
+    for (long long f = 0; f < nf; ++f) {
+        float b[9];
+        freesasa_gpu_xtc_frame_box(bytes + (off[f] - off[0]), b);
+        bool zero = true;
+        for (int k = 0; k < 9; ++k) zero = zero && b[k] == 0.0f;
+        if (zero) { snprintf(why, why_len, "its box is all zero: the frame carries no cell"); return f; }
+        const int upper[3] = {1, 2, 5}, lower[3] = {3, 6, 7};
+        for (int k = 0; k < 3; ++k)
+            if (b[upper[k]] != 0.0f) {
+                snprintf(why, why_len, "element [%d][%d] of its box is %.9g: a box must be lower-triangular", upper[k] / 3, upper[k] % 3, (double)b[upper[k]]);
+                return f;
+            }
+        const double len[3] = {(double)b[0] * 10.0, (double)b[4] * 10.0, (double)b[8] * 10.0};
+        if (!tri) {
+            for (int k = 0; k < 3; ++k)
+                if (b[lower[k]] != 0.0f) {
+                    snprintf(why, why_len, "its cell is not orthorhombic (element [%d][%d] of its box is %.9g): triclinic cells need bit 4", lower[k] / 3, lower[k] % 3, (double)b[lower[k]]);
+                    return f;
+                }
+            for (int k = 0; k < 3; ++k) {
+                if (!isfinite(len[k])) { snprintf(why, why_len, "edge %c of its cell is not finite", "xyz"[k]); return f; }
+                if (!(len[k] >= cut)) {
+                    snprintf(why, why_len, "edge %c of its cell is %.9g, shorter than c = 2 (max radius + probe) = %.9g", "xyz"[k], len[k], cut);
+                    return f;
+                }
+                cells[3 * f + k] = len[k];
+            }
+            continue;
+        }
+        double *h = cells + PBC_TRI_CELL * f;
+        const int at[6] = {0, 3, 4, 6, 7, 8};
+        for (int k = 0; k < 6; ++k) {
+            h[k] = (double)b[at[k]] * 10.0;
+            if (!isfinite(h[k])) { snprintf(why, why_len, "element [%d][%d] of its box is not finite", at[k] / 3, at[k] % 3); return f; }
+        }
+        if (tri_cell_bad(h, len, cut, why, why_len)) return f;
+    }
+    return -1;
+}
+
 /* the shard's frames in page-locked memory: the caller's own, or the lane's staging filled from memory or from the file
    (a DCD file: the bytes as they lie there, every record marker checked; with periodic images every cell record decoded and
    checked, the edges behind the bytes; an AMBER NetCDF file: the records as they lie there, with periodic images likewise) */
@@ -579,10 +662,21 @@ int shard_read(TrajRun &T, freesasa_gpu_ctx *c, TrajShard &h)
 {
     h.src = T.io.mem_in ? T.io.mem_in + 3 * T.fa * (size_t)h.f0 : nullptr;
     if (h.src && T.in_pinned) return 0;
-    if (ensure_pinned(c, &c->stage_in, &c->stage_in_cap, T.pbc ? TrajRun::cells_at(h.in_bytes) + T.cell_bytes * (size_t)h.nf : h.in_bytes)) return -1;
+    /* (an XTC shard: behind what goes up, the place its frames' status comes down to) */
+    if (ensure_pinned(c, &c->stage_in, &c->stage_in_cap, T.up_bytes(h.in_bytes, (size_t)h.nf) + (T.xtc ? 8 * (size_t)h.nf : 0))) return -1;
     if (h.src) memcpy(c->stage_in, h.src, h.in_bytes);
-    else if (!pread_all(T.io.in.fd, c->stage_in, h.in_bytes, T.io.in_header + (long long)T.stride * h.f0))
+    else if (!pread_all(T.io.in.fd, c->stage_in, h.in_bytes, T.xtc ? (long long)T.io.xtc_off[(size_t)h.f0] : T.io.in_header + (long long)T.stride * h.f0))
         return ctx_fail(c, "could not read frames %lld..%lld of the frame file", h.f0, h.f0 + h.nf - 1);
+    if (T.xtc) {
+        char why[200];
+        const char *bytes = (const char *)c->stage_in;
+        const long long bad = xtc_descriptors(T.io, bytes, h.f0, h.nf, (int)T.fa, (freesasa_gpu_xtc_frame *)((char *)c->stage_in + T.xtc_desc_at(h.in_bytes, (size_t)h.nf)), why, sizeof why);
+        if (bad >= 0) return ctx_fail(c, "frame %lld of the XTC file is damaged: %s", h.f0 + bad, why);
+        if (T.pbc) {
+            const long long odd = xtc_cells(T.io, bytes, h.f0, h.nf, T.io.tri, T.pbc_cut, (double *)((char *)c->stage_in + TrajRun::cells_at(h.in_bytes)), why, sizeof why);
+            if (odd >= 0) return ctx_fail(c, "frame %lld of the XTC file: %s", h.f0 + odd, why);
+        }
+    }
     if (T.dcd) {
         const long long bad = dcd_damaged_frame(T.io.dcd, (const char *)c->stage_in, h.nf);
         if (bad >= 0) return ctx_fail(c, "frame %lld of the DCD file is damaged: a record marker is not what the header implies", h.f0 + bad);
@@ -608,12 +702,31 @@ int shard_read(TrajRun &T, freesasa_gpu_ctx *c, TrajShard &h)
 int shard_upload(TrajRun &T, TrajLane &L, const TrajShard &h)
 {
     freesasa_gpu_ctx *c = L.c;
-    const bool f32 = T.io.in_f32 != 0;
-    void *d_in = T.gather || T.container ? c->g_xyz.p : (f32 ? c->h_counts.p : c->h_xyz.p);
-    /* (periodic images: the shard's cell edges behind its bytes, in the same copy) */
-    const size_t up_bytes = T.pbc ? TrajRun::cells_at(h.in_bytes) + T.cell_bytes * (size_t)h.nf : h.in_bytes;
+    const bool f32 = T.f32;
+    void *d_in = T.gather || T.container || T.xtc ? c->g_xyz.p : (f32 ? c->h_counts.p : c->h_xyz.p);
+    /* (periodic images: the shard's cell edges behind its bytes, in the same copy; an XTC shard: its descriptors too) */
+    const size_t up_bytes = T.up_bytes(h.in_bytes, (size_t)h.nf);
     if (hipMemcpyAsync(d_in, h.src, up_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "host-to-device copy failed");
     L.ta.n_frames = h.nf;
+    if (T.xtc) {
+        /* scan, then unpack: raw fp32 frames where the raw fp32 path has them - and the frames' status down BEFORE the engine sees
+           them: what a damaged stream leaves of a frame is not a frame (one more synchronisation per shard; the other lanes' shards
+           fill the device meanwhile) */
+        const size_t nf = (size_t)h.nf;
+        char *g = (char *)c->g_xyz.p;
+        int32_t *status = (int32_t *)((char *)c->stage_in + up_bytes);
+        d_in = T.gather ? (void *)(g + T.xtc_f32_at(h.in_bytes, nf)) : c->h_counts.p;
+        const sasa::XtcArgs xa = {(int)T.fa, h.nf, (const uint32_t *)g, (const freesasa_gpu_xtc_frame *)(g + T.xtc_desc_at(h.in_bytes, nf)),
+                                  (sasa::XtcRec *)(g + T.xtc_rec_at(h.in_bytes, nf)), (int32_t *)(g + T.xtc_count_at(h.in_bytes, nf)), (float *)d_in};
+        if (kl_xtc_scan(xa, c->stream) != hipSuccess || kl_xtc_unpack(xa, c->stream) != hipSuccess) return ctx_fail(c, "XTC decode launch failed");
+        if (hipMemcpyAsync(status, xa.count, 8 * nf, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
+            return ctx_fail(c, "could not read the status of the XTC frames");
+        for (size_t f = 0; f < nf; ++f)
+            if (const int st = status[2 * f + 1])
+                return ctx_fail(c, "frame %lld of the XTC file is damaged: %s", h.f0 + (long long)f,
+                                st & sasa::XTC_ST_BITS ? "its stream ends before its atoms do" : st & sasa::XTC_ST_ATOMS ? "a group of its stream runs past its atoms"
+                                : st & sasa::XTC_ST_SMALLIDX ? "smallidx leaves 9 .. 72 in its stream" : "its stream unpacks to a value outside its range");
+    }
     if (T.dcd) {
         const freesasa_gpu_dcd_info &d = T.io.dcd;
         const sasa::TrajDcdArgs da = {(int)T.n, h.nf, T.gather ? L.ta.index : nullptr, d.frame_bytes, d.x_off, d.plane_bytes};
@@ -774,7 +887,7 @@ void traj_lane(TrajRun &T, int id) noexcept
         if (s.max_new > 0 && T.fresh.fetch_add(1) >= s.max_new) { T.stopped = 1; break; }
         h.f0 = h.k * s.frames_per_batch;
         h.nf = (int)(s.n_frames - h.f0 < s.frames_per_batch ? s.n_frames - h.f0 : s.frames_per_batch);
-        h.na = T.n * (size_t)h.nf; h.in_bytes = T.stride * (size_t)h.nf;
+        h.na = T.n * (size_t)h.nf; h.in_bytes = T.shard_bytes(h.f0, h.nf);
         if (shard_run(T, L, h)) {
             (void)hipStreamSynchronize(L.c->stream); /* nothing of the shard may still run when the lane lets go */
             T.fe.set(L.c->err[0] ? L.c->err : "trajectory shard failed");
@@ -876,12 +989,12 @@ extern "C" int freesasa_gpu_trajectory_topology(const double *xyz_frames, int n_
    files byte for byte.  With a topology, in front of the line's end, what its outputs depend on: digests of the index, of
    residue boundaries + classes + backbone flags, of the selection set's program, and which result files the run writes; with
    chain groups, behind that, a digest of the group count and the ids.  A DCD run: bit 2 in the f32= word and the byte of
-   frame 0 as header_bytes=; an AMBER NetCDF run: bit 5 and the byte of record 0; a raw run's line is what it was.  Periodic images: bit 3 in the f32= word, triclinic cells: bit 4. */
+   frame 0 as header_bytes=; an AMBER NetCDF run: bit 5 and the byte of record 0; an XTC run: bit 6 (its frames are found by the index: header_bytes=0); a raw run's line is what it was.  Periodic images: bit 3 in the f32= word, triclinic cells: bit 4. */
 static int traj_done_head(char *head, size_t cap, const TrajSpec &s, const TrajIO &io, const struct stat &st)
 {
     int len = snprintf(head, cap, "freesasa_amd trajectory done-list v2 n_atoms=%d n_frames=%lld frames_per_batch=%d alg=%d resolution=%d probe=%.17g f32=%d "
                        "header_bytes=%lld frames_size=%lld frames_mtime=%lld.%09ld radii=%016llx\n",
-                       s.n_atoms, s.n_frames, s.frames_per_batch, s.alg, s.resolution, s.probe, io.in_f32 | (io.out_f32() << 1) | (io.in_dcd ? FREESASA_GPU_FRAMES_DCD : 0) | (io.in_nc ? FREESASA_GPU_FRAMES_NETCDF : 0) | (io.pbc ? FREESASA_GPU_FRAMES_PBC : 0) | (io.tri ? FREESASA_GPU_FRAMES_TRICLINIC : 0), io.in_header, (long long)st.st_size,
+                       s.n_atoms, s.n_frames, s.frames_per_batch, s.alg, s.resolution, s.probe, io.in_f32 | (io.out_f32() << 1) | (io.in_dcd ? FREESASA_GPU_FRAMES_DCD : 0) | (io.in_nc ? FREESASA_GPU_FRAMES_NETCDF : 0) | (io.in_xtc ? FREESASA_GPU_FRAMES_XTC : 0) | (io.pbc ? FREESASA_GPU_FRAMES_PBC : 0) | (io.tri ? FREESASA_GPU_FRAMES_TRICLINIC : 0), io.in_header, (long long)st.st_size,
                        (long long)st.st_mtim.tv_sec, (long)st.st_mtim.tv_nsec, fnv1a(s.radii, 8 * (size_t)s.n_atoms));
     const TrajTopo *tp = s.topo;
     if (tp && len > 0 && len < (int)cap) {
@@ -913,11 +1026,33 @@ static int trajectory_file_run(const char *frames_path, int frames_f32, long lon
     if (!frames_path || !s.radii || !io.out[OUT_TOTALS].path) return set_err(err_out, err_len, "null argument");
     if (s.n_atoms <= 0 || header_bytes < 0) return set_err(err_out, err_len, "bad argument");
     const long long frame_atoms = s.topo ? s.topo->frame_atoms : s.n_atoms;
-    if ((frames_f32 & FREESASA_GPU_FRAMES_PBC) && !(frames_f32 & (FREESASA_GPU_FRAMES_DCD | FREESASA_GPU_FRAMES_NETCDF)))
-        return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) needs bit 2 (a DCD file) or bit 5 (an AMBER NetCDF file): raw frame files carry no cell");
+    if ((frames_f32 & FREESASA_GPU_FRAMES_PBC) && !(frames_f32 & (FREESASA_GPU_FRAMES_DCD | FREESASA_GPU_FRAMES_NETCDF | FREESASA_GPU_FRAMES_XTC)))
+        return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) needs bit 2 (a DCD file), bit 5 (an AMBER NetCDF file) or bit 6 (an XTC file): raw frame files carry no cell");
     if ((frames_f32 & FREESASA_GPU_FRAMES_TRICLINIC) && !(frames_f32 & FREESASA_GPU_FRAMES_PBC))
-        return set_err(err_out, err_len, "bit 4 of frames_f32 (triclinic cells) needs bit 3 (periodic images) and bit 2 (a DCD file) or bit 5 (an AMBER NetCDF file)");
-    if (frames_f32 & FREESASA_GPU_FRAMES_NETCDF) {
+        return set_err(err_out, err_len, "bit 4 of frames_f32 (triclinic cells) needs bit 3 (periodic images) and bit 2 (a DCD file), bit 5 (an AMBER NetCDF file) or bit 6 (an XTC file)");
+    if (frames_f32 & FREESASA_GPU_FRAMES_XTC) {
+        /* an XTC file's frames are found by one pass over their headers: before a device is touched or an output file opened */
+        if (frames_f32 & FREESASA_GPU_FRAMES_F32) return set_err(err_out, err_len, "bit 0 of frames_f32 (raw fp32 frames) and bit 6 (an XTC file) exclude each other");
+        if (frames_f32 & FREESASA_GPU_FRAMES_DCD) return set_err(err_out, err_len, "bit 2 of frames_f32 (a DCD file) and bit 6 (an XTC file) exclude each other");
+        if (frames_f32 & FREESASA_GPU_FRAMES_NETCDF) return set_err(err_out, err_len, "bit 5 of frames_f32 (an AMBER NetCDF file) and bit 6 (an XTC file) exclude each other");
+        if (header_bytes != 0) return set_err(err_out, err_len, "header_bytes must be 0 with an XTC file: its frames are found by their headers");
+        int64_t *offsets = nullptr;
+        if (freesasa_gpu_xtc_index_read(frames_path, &io.xtc, &offsets, err_out, err_len)) return -1;
+        const int rc = guarded(err_out, err_len, [&]() -> int { io.xtc_off.assign(offsets, offsets + io.xtc.n_frames + 1); return 0; });
+        freesasa_gpu_xtc_index_free(offsets);
+        if (rc) return -1;
+        if (io.xtc.n_atoms != frame_atoms) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "the XTC file holds %d atoms per frame, the run expects %lld", (int)io.xtc.n_atoms, frame_atoms);
+            return set_err(err_out, err_len, msg);
+        }
+        io.in_xtc = true;
+        if (frames_f32 & FREESASA_GPU_FRAMES_PBC) {
+            if (!io.xtc.has_box) return set_err(err_out, err_len, "periodic images need an XTC file with a box: the box of this one's first frame is all zero");
+            io.pbc = true;
+            io.tri = (frames_f32 & FREESASA_GPU_FRAMES_TRICLINIC) != 0;
+        }
+    } else if (frames_f32 & FREESASA_GPU_FRAMES_NETCDF) {
         /* an AMBER NetCDF file says for itself where its frames are and what they are: before a device is touched or an output file opened */
         if (frames_f32 & FREESASA_GPU_FRAMES_F32) return set_err(err_out, err_len, "bit 0 of frames_f32 (raw fp32 frames) and bit 5 (an AMBER NetCDF file) exclude each other");
         if (frames_f32 & FREESASA_GPU_FRAMES_DCD) return set_err(err_out, err_len, "bit 2 of frames_f32 (a DCD file) and bit 5 (an AMBER NetCDF file) exclude each other");
@@ -961,6 +1096,7 @@ static int trajectory_file_run(const char *frames_path, int frames_f32, long lon
     io.in_f32 = (frames_f32 & 1) ? 1 : 0; io.out[OUT_SASA].esz = io.out[OUT_ISO].esz = (frames_f32 & 2) ? 4 : 8;
     const long long in_file = io.in_dcd ? ((long long)st.st_size - io.dcd.first_frame) / io.dcd.frame_bytes
                             : io.in_nc ? ((long long)st.st_size - io.nc.first_record) / io.nc.record_bytes
+                            : io.in_xtc ? (long long)io.xtc.n_frames
                                         : ((long long)st.st_size - header_bytes) / ((io.in_f32 ? 12LL : 24LL) * frame_atoms);
     if (s.n_frames <= 0) s.n_frames = in_file;
     if (s.n_frames <= 0 || s.n_frames > in_file) return set_err(err_out, err_len, "the frame file holds fewer frames than asked for");

@@ -883,6 +883,27 @@ __global__ __launch_bounds__(TRAJ_B) void k_traj_gather_nc(TrajNcArgs a, const u
 {
     traj_gather_nc(a, in, out, (int64_t)blockIdx.x * TRAJ_B + threadIdx.x);
 }
+/* XTC input: a workgroup of one wavefront per frame - the lanes stage a window of the stream, lane 0 walks it - and one thread
+   per group record */
+__global__ __launch_bounds__(XTC_SCAN_B) void k_xtc_scan(XtcArgs a)
+{
+    __shared__ uint32_t win[XTC_WIN + 1];
+    __shared__ XtcScanState st;
+    const int f = blockIdx.x, lane = threadIdx.x;
+    if (lane == 0) { xtc_scan_init(a, f, st); win[XTC_WIN] = 0; }
+    __syncthreads();
+    for (;;) { /* (every round moves the window on by XTC_WIN - 1 words at least, or ends the walk) */
+        xtc_scan_stage(a, f, st, win, lane);
+        __syncthreads();
+        if (lane == 0) xtc_scan_walk(a, f, st, win);
+        __syncthreads();
+        if (st.done) break;
+    }
+}
+__global__ __launch_bounds__(XTC_UNPACK_B) void k_xtc_unpack(XtcArgs a)
+{
+    xtc_unpack(a, (int64_t)blockIdx.x * XTC_UNPACK_B + threadIdx.x);
+}
 __global__ __launch_bounds__(TRAJ_B) void k_traj_residues(TrajArgs a)
 {
     traj_residue(a, (int64_t)blockIdx.x * TRAJ_B + threadIdx.x);
@@ -920,6 +941,16 @@ hipError_t kl_traj_gather_nc(const TrajNcArgs &a, const void *d_in, double *d_ou
 {
     const unsigned grid = (unsigned)((3 * (int64_t)a.n_frames * a.n + TRAJ_B - 1) / TRAJ_B);
     hipLaunchKernelGGL(k_traj_gather_nc, dim3(grid), dim3(TRAJ_B), 0, st, a, (const uint32_t *)d_in, d_out);
+    return hipGetLastError();
+}
+hipError_t kl_xtc_scan(const XtcArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_xtc_scan, dim3((unsigned)a.n_frames), dim3(XTC_SCAN_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_xtc_unpack(const XtcArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_xtc_unpack, dim3((unsigned)(((int64_t)a.n_frames * a.n_atoms + XTC_UNPACK_B - 1) / XTC_UNPACK_B)), dim3(XTC_UNPACK_B), 0, st, a);
     return hipGetLastError();
 }
 hipError_t kl_traj_residues(const TrajArgs &a, hipStream_t st)

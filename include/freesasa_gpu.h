@@ -518,7 +518,7 @@ int freesasa_gpu_cell_from_lengths_angles(const double len[3], const double deg[
    failed read ("frame K of the DCD file is damaged"; the shard is not listed).  The done-list's f32= word carries bit 2
    and its header_bytes= the byte of frame 0: a raw run's list is refused by a DCD run and the other way round; a raw run's
    line is what it was.  Without bit 3 SASA is computed WITHOUT periodic images: a solute that the writer wrapped across the
-   box must be made whole beforehand.  Not offered: DCD files with fixed atoms or 64-bit record markers, XTC / TRR, a memory
+   box must be made whole beforehand.  Not offered: DCD files with fixed atoms or 64-bit record markers, TRR, a memory
    form.
 
    AMBER NetCDF input (all four file entries): with bit 5 of frames_f32 set (FREESASA_GPU_FRAMES_NETCDF) frames_path is an
@@ -538,7 +538,31 @@ int freesasa_gpu_cell_from_lengths_angles(const double len[3], const double deg[
    edge must be finite and >= c; with bit 4 the cell goes through freesasa_gpu_cell_from_lengths_angles and the checks of a
    DCD record.  A frame that fails ends the run ("frame K of the NetCDF file: ..." with the reason; the shard is not listed).
    Refused up front: bit 3 on a file without the cell variables, freesasa_gpu_trajectory_file_groups with bit 3.
-   Not offered: XTC / TRR, NetCDF-4 (HDF5) and CDF-5 files, AMBER restart files, a scale_factor other than 1, a memory form.
+   Not offered: TRR, NetCDF-4 (HDF5) and CDF-5 files, AMBER restart files, a scale_factor other than 1, a memory form.
+
+   GROMACS XTC input (all four file entries): with bit 6 of frames_f32 set (FREESASA_GPU_FRAMES_XTC) frames_path is an XTC
+   trajectory (magic 1995, more than 9 atoms: compressed coordinates; freesasa_gpu_xtc_info_read below has the layout).
+   header_bytes must be 0, bits 0, 2 and 5 clear; bit 1 keeps its meaning.  Frames are compressed and of unequal length: one
+   pass over the file's headers before a device is touched or an output file opened builds the INDEX, the byte offset of every
+   frame, checks every header and counts the frames; the file's atom count must equal n_atoms (with a topology: frame_atoms).
+   A shard is the bytes offset[f0] .. offset[f0 + nf], still one read and one host-to-device copy; behind the bytes ride (the
+   cells of a periodic run and) one descriptor of 64 bytes per frame, made on the host from the frame's header
+   (freesasa_gpu_xtc_frame).  Two kernels decode on the device (xtc_kernels.h): xtc_scan, one wavefront per frame, walks the
+   stream's groups and notes where each begins; xtc_unpack, one thread per group, unpacks the integers and writes fp32
+   Angstrom coordinates, (float) integer * (float)(1 / (double) precision) * 10.0f in two fp32 products, as raw interleaved
+   frames - from where the raw fp32 path goes on unchanged (the gather through a topology's index, or the widening): an XTC
+   run's results are those of a raw fp32 file of the decoded values, byte for byte.  A stream that runs out of bits, runs past
+   its atoms, leaves smallidx's range 9 .. 72 or unpacks a value outside its range gives its frame a non-zero status, which
+   the host reads before the engine runs: the run ends ("frame K of the XTC file is damaged: ..."), nothing of the shard is
+   written and it is not listed.  The done-list's f32= word carries bit 6: raw, DCD, NetCDF and XTC runs refuse each other's
+   lists.  Periodic images: bits 3 and 4 may stand beside bit 6 as beside bit 2; the cell is every frame's box, each element
+   (double) float * 10.0, GROMACS' lower triangle (ax, bx, by, cx, cy, cz) = box[0][0], box[1][0], box[1][1], box[2][0],
+   box[2][1], box[2][2].  A non-zero upper element, an off-diagonal element without bit 4 or an all-zero box ends the run
+   ("frame K of the XTC file: ..."); the rest are the checks of a DCD cell.  Refused up front: bit 3 on a file whose first
+   frame has an all-zero box, freesasa_gpu_trajectory_file_groups with bit 3.
+   Not offered: TRR, magic 2023 (64-bit byte counts), frames of 9 atoms or fewer (uncompressed), streams of 2^28 bytes and
+   more, a memory form, chain groups with periodic images, double-precision XTC.  No GROMACS-written file was at hand when
+   this was written: conformance rests on the format's description; compare one frame against `gmx dump` first.
 
    Periodic images (freesasa_gpu_trajectory_file, _file_devices, _file_topology): with bit 3 (FREESASA_GPU_FRAMES_PBC) beside
    bit 2 (beside bit 5: above) every frame is computed among the periodic images its own unit-cell record implies, as freesasa_gpu_calc_periodic
@@ -569,6 +593,7 @@ int freesasa_gpu_cell_from_lengths_angles(const double len[3], const double deg[
 #define FREESASA_GPU_FRAMES_PBC 8     /* bit 3: with bit 2 or bit 5, every frame among the periodic images of its cell */
 #define FREESASA_GPU_FRAMES_TRICLINIC 16 /* bit 4: with bit 3, the cell decoded as a triclinic cell */
 #define FREESASA_GPU_FRAMES_NETCDF 32 /* bit 5: frames_path is an AMBER NetCDF trajectory */
+#define FREESASA_GPU_FRAMES_XTC 64    /* bit 6: frames_path is a GROMACS XTC trajectory */
 
 /* The header of a DCD file.  Every integer of the file is an int32 in the file's byte order; records lie between two equal
    byte counts:  [84 | "CORD" | 20 control words | 84]  [m | NTITLE | 80 NTITLE bytes | m]  [4 | NATOM | 4], then per frame
@@ -623,6 +648,51 @@ int freesasa_gpu_nc_info_read(const char *path, freesasa_gpu_nc_info *out, char 
 /* The cell of frame f of the records at `records` (frame 0's first byte; info->has_cell): three edge lengths and alpha, beta,
    gamma in degrees, in the host's byte order.  The offsets are multiples of 4, not of 8: copied byte by byte. */
 void freesasa_gpu_nc_cell_record(const freesasa_gpu_nc_info *info, const void *records, long long f, double lengths_out[3], double angles_out[3]);
+
+/* A GROMACS XTC trajectory.  Every value of the file is XDR: big-endian, 4 bytes.  A frame:
+       int magic = 1995 | int natoms | int step | float time | float box[3][3] (nm, row-major) | int natoms | float precision |
+       int minint[3] | int maxint[3] | int smallidx | int bytecount | bytecount bytes, padded to a multiple of 4
+   The bit stream starts FREESASA_GPU_XTC_HEADER = 92 bytes into the frame, the next frame follows the padding; every offset is
+   a multiple of 4.  freesasa_gpu_xtc_index_read makes ONE pass over the file, one read of 92 bytes per frame: it checks every
+   header, counts the frames (the count comes from this pass, not from the file's size) and, with offsets_out, returns the
+   byte offset of every frame, [n_frames + 1] with the end of the last one behind them, in an array the caller frees with
+   freesasa_gpu_xtc_index_free; without offsets_out (freesasa_gpu_xtc_info_read) it allocates nothing.  Returns 0, or -1 with
+   "frame K of the XTC file: <reason>" in err - each its own reason: magic 2023 (the variant with 64-bit byte counts), any
+   other magic, 9 atoms or fewer (such frames hold uncompressed floats), two atom counts that differ from each other or from
+   frame 0's, a precision that is not finite or <= 0, minint > maxint in a dimension (or a dimension that spans all 2^32
+   integers), smallidx outside 9 .. 72, a byte count that is negative, 2^28 or more, or runs past the end of the file, a file
+   that ends inside a header. */
+#define FREESASA_GPU_XTC_HEADER 92
+typedef struct freesasa_gpu_xtc_info {
+    int32_t n_atoms;          /* of frame 0, and so of every frame */
+    int64_t n_frames;         /* by the pass over the headers */
+    int64_t max_frame_bytes;  /* the longest frame, header and padding included */
+    float precision;          /* of frame 0 (every frame carries its own) */
+    int32_t has_box;          /* frame 0's box has a non-zero element */
+} freesasa_gpu_xtc_info;
+int freesasa_gpu_xtc_info_read(const char *path, freesasa_gpu_xtc_info *out, char *err, int err_len); /* 0 / -1 */
+int freesasa_gpu_xtc_index_read(const char *path, freesasa_gpu_xtc_info *out, int64_t **offsets_out, char *err, int err_len);
+void freesasa_gpu_xtc_index_free(int64_t *offsets);
+/* What the device needs to decode one frame, made from its header; 64 bytes, one per frame of a shard behind the shard's bytes.
+   sizeint = maxint - minint + 1.  bitsize: 0 when (sizeint[0] | sizeint[1] | sizeint[2]) > 0xffffff - a "big" triple is then
+   three fields of bitsizeint[k] = the smallest b <= 32 with 2^b > sizeint[k] bits - else the bit length of the product of the
+   three sizes: a big triple is one field of that many bits. */
+typedef struct freesasa_gpu_xtc_frame {
+    int64_t stream_off;       /* byte of the stream's first byte within the shard (a multiple of 4) */
+    int32_t bytecount;        /* bytes of the stream, < 2^28 */
+    int32_t minint[3];
+    uint32_t sizeint[3];
+    int32_t bitsize, bitsizeint[3];
+    int32_t smallidx;         /* of the frame's first group, 9 .. 72 */
+    float inv_precision;      /* (float)(1.0 / (double) precision) */
+    int32_t pad_;
+} freesasa_gpu_xtc_frame;
+/* The checks of one header (`avail` bytes of the file lie from its first byte on; n_atoms > 0: the count it must hold) and its
+   descriptor, the stream at byte stream_off; *frame_bytes_out: header + stream + padding.  0, or -1 with the reason in why. */
+int freesasa_gpu_xtc_frame_desc(const void *header, long long avail, int n_atoms, long long stream_off, freesasa_gpu_xtc_frame *out,
+                                long long *frame_bytes_out, char *why, int why_len);
+/* the nine floats of a header's box, in the host's byte order (nm) */
+void freesasa_gpu_xtc_frame_box(const void *header, float box_out[9]);
 
 int freesasa_gpu_trajectory(const double *xyz_frames, const double *radii, int n_atoms, int n_frames,
                             int alg, double probe_radius, int resolution, int frames_per_batch,

@@ -42,9 +42,18 @@ With --triclinic beside --pbc (FREESASA_GPU_FRAMES_TRICLINIC) three arms more, i
 With --netcdf beside --pbc two arms more: `solvated` and `solvated-pbc` on an AMBER NetCDF file of the same frames and cell
 (solvated-nc, solvated-nc-pbc); their totals files must be those of the DCD arms, byte for byte.
 
+With --xtc the system is instead 10 000 atoms of water-like runs (3333 groups of an oxygen and two hydrogens within 0.1 nm of it,
+and one atom more), no topology, and the arms are three files of the same decoded frames, interleaved:
+    raw       trajectory_file on the raw fp32 file
+    netcdf    ... on an AMBER NetCDF file of them
+    xtc       ... on a GROMACS XTC file: --xtc-distinct frames encoded by tests/xtc_codec.py (precision 1000) and repeated up to
+              --frames, since frames are independent; scanned and unpacked on the device
+each line with the host CPU time of the process per atom-frame; the totals files must be identical.  --xtc-fpb sets
+frames_per_batch for all three arms (0: the driver's default).
+
 One JSON line per arm: atom-frames/s counted in SOLUTE atoms and in frame atoms, the median and the spread of --reps runs.
 
-    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd] [--netcdf] [--pbc [--pbc-arms all|off] [--triclinic]]
+    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd] [--netcdf] [--pbc [--pbc-arms all|off] [--triclinic]] [--xtc [--xtc-distinct 24] [--xtc-fpb 0]]
 
 For the kernel times: `rocprofv3 --kernel-trace --stats -- python tools/traj_topology_bench.py --reps 1 --arms all`
 (k_traj_gather / k_traj_residues / k_traj_class / k_traj_sel are the topology's kernels, k_traj_group_* the groups')."""
@@ -201,6 +210,60 @@ def long_way(full, b, ids, n_frames, out_path):
     return True, n_frames
 
 
+def xtc_mode(args, scratch):
+    """the three arms of --xtc -> the JSON lines"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import xtc_codec as xc
+    n, mol = N_SOLUTE, N_SOLUTE // 3
+    rng = np.random.default_rng(9)
+    plan = [(2, 0)] * mol + [(0, 0)] * (n - 3 * mol)
+    box = np.diag([4.64, 4.64, 4.64])
+    coded, decoded = [], []
+    for f in range(args.xtc_distinct):
+        big = rng.integers(0, 4640, (mol + n - 3 * mol, 3))
+        h1 = big[:mol] + rng.integers(-100, 101, (mol, 3))
+        h2 = h1 + rng.integers(-160, 161, (mol, 3))
+        ints = np.concatenate([np.stack([h1, big[:mol], h2], axis=1).reshape(-1, 3), big[mol:]])        # (output order: small, big, small)
+        coded.append(xc.encode(ints, 1000.0, box=box, plan=plan, smallidx=33, step=f, time=float(f)))      # (magicints[33] / 2 = 1024 > 160)
+        decoded.append(xc.to_angstrom(ints, 1000.0))
+    p = lambda k: os.path.join(scratch, k)
+    half = 23.2
+    with open(p("water.xtc"), "wb") as f_xtc, open(p("water.f32"), "wb") as f_raw, open(p("water.nc"), "wb") as f_nc:
+        f_nc.write(nc_header(n, args.frames))
+        for f in range(args.frames):
+            f_xtc.write(coded[f % len(coded)])
+            decoded[f % len(decoded)].tofile(f_raw)
+            f_nc.write(nc_record(f, decoded[f % len(decoded)], [2 * half] * 3))
+    info = fa.xtc_info(p("water.xtc"))
+    assert info.n_frames == args.frames and info.n_atoms == n
+    radii = np.tile([1.1, 1.52, 1.1], mol + 1)[:n].astype(np.float64)
+    kw = dict(frames_per_batch=args.xtc_fpb)
+    arms = {"raw": lambda: fa.trajectory_file(p("water.f32"), radii, p("x0"), f32=True, **kw),
+            "netcdf": lambda: fa.trajectory_file(p("water.nc"), radii, p("x1"), netcdf=True, **kw),
+            "xtc": lambda: fa.trajectory_file(p("water.xtc"), radii, p("x2"), xtc=True, **kw)}
+    runs, cpu = {a: [] for a in arms}, {a: [] for a in arms}
+    for a in arms:
+        arms[a]()                                                        # warm-up: contexts, staging, page cache
+    for _ in range(args.reps):
+        for a in arms:
+            t0, c0 = time.perf_counter(), time.process_time()
+            res = arms[a]()
+            runs[a].append(time.perf_counter() - t0)
+            cpu[a].append(time.process_time() - c0)
+            assert res[0] and res[1] == args.frames
+    totals = [np.fromfile(p(k)) for k in ("x0", "x1", "x2")]
+    assert all(np.array_equal(t, totals[0]) for t in totals) and np.all(totals[0] > 0)
+    lines = []
+    for a in arms:
+        v, c = sorted(runs[a]), sorted(cpu[a])
+        med = v[len(v) // 2]
+        lines.append(json.dumps({"arm": a, "frames": args.frames, "frame_atoms": n, "frames_per_batch": args.xtc_fpb, "file_bytes_per_frame":
+                                 os.path.getsize(p({"raw": "water.f32", "netcdf": "water.nc", "xtc": "water.xtc"}[a])) / args.frames,
+                                 "median_seconds": med, "min_seconds": v[0], "max_seconds": v[-1], "atom_frames_per_s": n * args.frames / med,
+                                 "host_cpu_ns_per_atom_frame": 1e9 * c[len(c) // 2] / (n * args.frames), "runs": len(v)}))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=240)
@@ -214,9 +277,19 @@ def main():
     ap.add_argument("--pbc", action="store_true", help="time the DCD drivers with and without periodic images")
     ap.add_argument("--pbc-arms", default="all", choices=["all", "off"])
     ap.add_argument("--triclinic", action="store_true", help="with --pbc: the arms of the triclinic bit beside the others")
+    ap.add_argument("--xtc", action="store_true", help="time a GROMACS XTC file against the raw fp32 file and an AMBER NetCDF file of the same decoded frames")
+    ap.add_argument("--xtc-distinct", type=int, default=24, help="with --xtc: distinct frames that are encoded and then repeated")
+    ap.add_argument("--xtc-fpb", type=int, default=0, help="with --xtc: frames_per_batch of all three arms (0: the driver's default)")
     args = ap.parse_args()
     scratch = args.scratch or tempfile.mkdtemp(prefix="traj_topology_bench_")
     try:
+        if args.xtc:
+            lines = xtc_mode(args, scratch)
+            print("\n".join(lines))
+            if args.out:
+                with open(args.out, "w") as fh:
+                    fh.write("\n".join(lines) + "\n")
+            return
         b, xyz = solute()
         full, bare, as_dcd, as_nc = make_frames(scratch, xyz, args.frames, args.dcd, args.netcdf) if not args.pbc else (None, None, None, None)
         sel = ingest.Selection(EIGHT)
