@@ -689,10 +689,113 @@ def sweep_cache(cache_path, alg=LEE_RICHARDS, probe=1.4, resolution=20, batch_at
     return totals, cls, atoms, status
 
 
+# run statistics (include/freesasa_gpu.h, FREESASA_GPU_STATS_*): the outputs in the order of a partial's columns
+STATS_BITS = {"totals": 1, "atoms": 2, "isolated": 4, "classes": 8, "residues": 16, "selections": 32, "groups": 64}
+
+
+def _stats_proto(L):
+    _i32p, _llp = C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
+    L.freesasa_gpu_traj_stats_width.argtypes = [C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _llp]
+    L.freesasa_gpu_traj_stats_width.restype = C.c_longlong
+    L.freesasa_gpu_traj_stats_merge.argtypes = [_dp, _llp, C.c_longlong, C.c_longlong, _dp, _llp]
+    L.freesasa_gpu_trajectory_stats.argtypes = [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int,
+                                                C.c_int, _dp, _dp, C.c_char_p, C.c_int]
+    L.freesasa_gpu_trajectory_file_stats.argtypes = [C.c_char_p, C.c_int, C.c_longlong, _dp, C.c_int, C.c_longlong, C.c_int, C.c_double,
+                                                     C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_longlong, _ip, C.c_int,
+                                                     _llp, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
+    L.freesasa_gpu_trajectory_groups_stats.argtypes = [_dp, C.c_int, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_void_p, _i32p, C.c_int,
+                                                       C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _llp, _dp, _dp,
+                                                       _ip, C.c_int, C.c_int, _dp, _dp, C.c_char_p, C.c_int]
+    L.freesasa_gpu_trajectory_file_groups_stats.argtypes = [C.c_char_p, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, C.c_int, _i32p,
+                                                            C.c_void_p, _i32p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_char_p,
+                                                            C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, _llp, C.c_char_p, C.c_char_p,
+                                                            C.c_char_p, C.c_longlong, _ip, C.c_int, _llp, C.c_int, C.c_char_p, C.c_char_p,
+                                                            C.c_char_p, C.c_int]
+    return L
+
+
+def stats_word(stats):
+    """the FREESASA_GPU_STATS_* word of stats=("atoms", "residues", ...); None or () is 0"""
+    word = 0
+    for name in ([stats] if isinstance(stats, str) else stats or ()):
+        if name not in STATS_BITS:
+            raise ValueError(f"unknown statistics output {name!r}: one of {', '.join(STATS_BITS)}")
+        word |= STATS_BITS[name]
+    return word
+
+
+def traj_stats_width(stats, n_atoms, n_res=0, n_sel=0, n_groups=0):
+    """(W, first column of every output [7], -1: not asked for) of a statistics word or tuple of names"""
+    word = stats if isinstance(stats, int) else stats_word(stats)
+    first = np.zeros(7, dtype=np.int64)
+    W = _stats_proto(lib()).freesasa_gpu_traj_stats_width(word, n_atoms, n_res, n_sel, n_groups, first.ctypes.data_as(C.POINTER(C.c_longlong)))
+    if W < 0:
+        raise ValueError("bad statistics word or counts")
+    return int(W), first
+
+
+class RunStats(dict):
+    """Run statistics of a trajectory: a dict of the outputs asked for, each [4, ...] - mean, std (population), min, max over
+    the frames: totals [4], atoms [4, n], isolated [4, n], classes [4, 3], residues [4, R, 6], selections [4, S], groups
+    [4, G, 3].  raw: the same as the library delivers it, [4, W]; partials [n_shards, 4, W] (rows mean, M2, min, max of every
+    shard) and frames [n_shards] where they were asked for, else None: traj_stats_merge(partials, frames, a, b) gives the
+    statistics of shards [a, b) - block averages."""
+
+    def __init__(self, raw, stats, n_atoms, n_res=0, n_sel=0, n_groups=0, partials=None, frames=None):
+        W, first = traj_stats_width(stats, n_atoms, n_res, n_sel, n_groups)
+        raw = np.asarray(raw, dtype=np.float64).reshape(4, W)
+        shapes = [(), (n_atoms,), (n_atoms,), (3,), (n_res, 6), (n_sel,), (n_groups, 3)]
+        for name, at, shape in zip(STATS_BITS, first, shapes):
+            if at >= 0:
+                self[name] = raw[:, at:at + int(np.prod(shape, dtype=np.int64))].reshape((4,) + shape)
+        self.raw, self.partials, self.frames = raw, partials, frames
+
+
+def traj_stats_merge(parts, frames, first=0, last=None):
+    """freesasa_gpu_traj_stats_merge(): the statistics [4, W] (mean, std, min, max) of the consecutive shards [first, last) of
+    parts [n_shards, 4, W] (a partials file or RunStats.partials) with frames [n_shards] frames each."""
+    parts = np.ascontiguousarray(parts, dtype=np.float64)
+    frames = np.ascontiguousarray(frames, dtype=np.int64)
+    if parts.ndim != 3 or parts.shape[1] != 4 or frames.shape != (parts.shape[0],):
+        raise ValueError("parts must be [n_shards, 4, W] and frames [n_shards]")
+    last = parts.shape[0] if last is None else last
+    if not 0 <= first < last <= parts.shape[0]:
+        raise ValueError("bad range of shards")
+    cut, nf = np.ascontiguousarray(parts[first:last]), np.ascontiguousarray(frames[first:last])
+    out = np.empty((4, parts.shape[2]))
+    if _stats_proto(lib()).freesasa_gpu_traj_stats_merge(cut.ctypes.data_as(_dp), nf.ctypes.data_as(C.POINTER(C.c_longlong)), cut.shape[0],
+                                                         cut.shape[2], out.ctypes.data_as(_dp), None):
+        raise ValueError("freesasa_gpu_traj_stats_merge: zero parts, a part without frames or a width below 1")
+    return out
+
+
+def traj_stats_read(path, stats, n_atoms, n_res=0, n_sel=0, n_groups=0, partials_path=None, frames=None):
+    """The statistics file of a file run (raw fp64 [4, W]) as a RunStats; with partials_path and frames [n_shards] (the frames
+    of every shard: frames_per_batch each, the last one the rest) its partials too."""
+    W, _ = traj_stats_width(stats, n_atoms, n_res, n_sel, n_groups)
+    raw = np.fromfile(path, dtype=np.float64)
+    if raw.size != 4 * W:
+        raise ValueError("the statistics file does not have 4 x W values")
+    parts = None if partials_path is None else np.fromfile(partials_path, dtype=np.float64).reshape(-1, 4, W)
+    return RunStats(raw, stats, n_atoms, n_res, n_sel, n_groups, parts, None if frames is None else np.asarray(frames, dtype=np.int64))
+
+
+def _shard_frames(n_frames, frames_per_batch):
+    """frames of every shard of a run whose frames_per_batch was given; None when the library chooses it"""
+    if frames_per_batch <= 0:
+        return None
+    fpb = min(int(frames_per_batch), n_frames)
+    return np.array([min(fpb, n_frames - f0) for f0 in range(0, n_frames, fpb)], dtype=np.int64)
+
+
 def trajectory(xyz_frames, radii, alg=LEE_RICHARDS, probe=1.4, resolution=20, frames_per_batch=0,
-               per_atom=True, device=-1, devices=None):
+               per_atom=True, device=-1, devices=None, stats=None):
     """freesasa_gpu_trajectory() on host arrays: xyz_frames [n_frames, n_atoms, 3] -> (totals
-    [n_frames], per-atom [n_frames, n_atoms] or None)."""
+    [n_frames], per-atom [n_frames, n_atoms] or None).
+    stats=("totals", "atoms"): freesasa_gpu_trajectory_stats() - a third element, the RunStats of those outputs over the run,
+    reduced on the device (with per_atom=False the per-atom areas never leave it); its partials come with a frames_per_batch > 0."""
+    if stats:
+        return _trajectory_stats(xyz_frames, radii, alg, probe, resolution, frames_per_batch, per_atom, device, devices, stats)
     xyz_frames = np.ascontiguousarray(xyz_frames, dtype=np.float64)
     radii = _f64(radii)
     n_frames, n_atoms = xyz_frames.shape[0], radii.size
@@ -714,6 +817,29 @@ def trajectory(xyz_frames, radii, alg=LEE_RICHARDS, probe=1.4, resolution=20, fr
     if ret:
         raise RuntimeError("freesasa_gpu_trajectory: " + err.value.decode())
     return totals, sasa
+
+
+def _trajectory_stats(xyz_frames, radii, alg, probe, resolution, frames_per_batch, per_atom, device, devices, stats):
+    L = _stats_proto(lib())
+    xyz_frames = np.ascontiguousarray(xyz_frames, dtype=np.float64)
+    radii = _f64(radii)
+    n_frames, n_atoms = xyz_frames.shape[0], radii.size
+    assert xyz_frames.size == n_frames * n_atoms * 3
+    word = stats_word(stats)
+    W, _ = traj_stats_width(word, n_atoms)
+    totals = np.empty(n_frames)
+    sasa = np.empty((n_frames, n_atoms)) if per_atom else None
+    raw = np.empty((4, W))
+    nf = _shard_frames(n_frames, frames_per_batch)
+    parts = None if nf is None else np.empty((nf.size, 4, W))
+    err = C.create_string_buffer(512)
+    keep, dp_, nd = _devs(devices, device)
+    ret = L.freesasa_gpu_trajectory_stats(xyz_frames.ctypes.data_as(_dp), radii.ctypes.data_as(_dp), n_atoms, n_frames, alg, probe, resolution,
+                                          frames_per_batch, totals.ctypes.data_as(_dp), sasa.ctypes.data_as(_dp) if sasa is not None else None,
+                                          dp_, nd, word, raw.ctypes.data_as(_dp), parts.ctypes.data_as(_dp) if parts is not None else None, err, 512)
+    if ret:
+        raise RuntimeError("freesasa_gpu_trajectory_stats: " + err.value.decode())
+    return totals, sasa, RunStats(raw, word, n_atoms, partials=parts, frames=nf)
 
 
 FRAMES_F32, FRAMES_OUT_F32, FRAMES_DCD, FRAMES_PBC, FRAMES_TRICLINIC, FRAMES_NETCDF, FRAMES_XTC = 1, 2, 4, 8, 16, 32, 64   # the bits of frames_f32 (include/freesasa_gpu.h)
@@ -827,7 +953,8 @@ def _frames_bits(f32, out_f32, dcd, header_bytes, pbc=False, triclinic=False, ne
 
 def trajectory_file(frames_path, radii, totals_path, sasa_path=None, done_path=None, f32=False, header_bytes=0,
                     n_frames=0, alg=LEE_RICHARDS, probe=1.4, resolution=20, frames_per_batch=0, max_new_shards=0, device=-1,
-                    devices=None, out_f32=False, dcd=False, pbc=False, triclinic=False, netcdf=False, xtc=False):
+                    devices=None, out_f32=False, dcd=False, pbc=False, triclinic=False, netcdf=False, xtc=False,
+                    stats=None, stats_path=None, partials_path=None):
     """freesasa_gpu_trajectory_file(): raw frame file -> totals file (+ per-atom file), resumable through the
     done-list at done_path.  Returns (complete, n_frames): complete is False when max_new_shards stopped the run.
     f32: the frames are floats (an input format); out_f32: the per-atom file holds floats (an output format);
@@ -837,12 +964,24 @@ def trajectory_file(frames_path, radii, totals_path, sasa_path=None, done_path=N
     netcdf: frames_path is an AMBER NetCDF trajectory whose atom count is len(radii) (no dcd, no f32, no header_bytes with
     it); pbc and triclinic go with it as with dcd: the cell is the frame's cell_lengths and cell_angles (cell_from_lengths_angles);
     xtc: frames_path is a GROMACS XTC trajectory whose atom count is len(radii) (no dcd, no netcdf, no f32, no header_bytes with
-    it), decoded on the device; pbc and triclinic go with it as with dcd: the cell is the frame's box, nm * 10."""
+    it), decoded on the device; pbc and triclinic go with it as with dcd: the cell is the frame's box, nm * 10.
+    stats=("totals", "atoms") with stats_path and partials_path: freesasa_gpu_trajectory_file_stats() - the run statistics of those
+    outputs; the shards' partials go to partials_path as they finish, the call that finds the run complete writes stats_path
+    (traj_stats_read reads it).  With out_f32 the statistics are still those of the fp64 areas."""
     radii = _f64(radii)
     f32 = _frames_bits(f32, out_f32, dcd, header_bytes, pbc, triclinic, netcdf, xtc)
     err = C.create_string_buffer(512)
     total = C.c_longlong(0)
     enc = lambda p: None if p is None else str(p).encode()
+    if stats:
+        keep, dp_, nd = _devs(devices, device)
+        ret = _stats_proto(lib()).freesasa_gpu_trajectory_file_stats(
+            enc(frames_path), f32, header_bytes, radii.ctypes.data_as(_dp), radii.size, n_frames, alg, probe, resolution, frames_per_batch,
+            enc(totals_path), enc(sasa_path), enc(done_path), max_new_shards, dp_, nd, C.byref(total), stats_word(stats), enc(stats_path),
+            enc(partials_path), err, 512)
+        if ret < 0:
+            raise RuntimeError("freesasa_gpu_trajectory_file_stats: " + err.value.decode())
+        return ret == 0, int(total.value)
     if devices is None:
         ret = lib().freesasa_gpu_trajectory_file(enc(frames_path), f32, header_bytes, radii.ctypes.data_as(_dp), radii.size,
                                                  n_frames, alg, probe, resolution, frames_per_batch, enc(totals_path), enc(sasa_path),
@@ -883,10 +1022,13 @@ class TopologyResult:
     selection set), sasa [F, n] or None, and res_ref [R]: rows of ingest.residue_reference_table() - the relative areas are
     100 * residues[..., :5] / table[res_ref] where res_ref >= 0.  With chain groups (None without): group_areas [F, G, 3]
     (isolated, complex, buried per frame and group), group_atoms [G], and with per_atom isolated [F, n], every atom's area in
-    its group taken on its own (isolated - sasa: what the atom buries in the complex)."""
+    its group taken on its own (isolated - sasa: what the atom buries in the complex).  stats: the RunStats of the outputs
+    named in stats=, None without.  With per_frame=False only totals (and selection_atoms) are delivered per frame: the others
+    are None."""
 
     def __init__(self, totals, class_sums, residues, selection_areas, selection_atoms, sasa, res_ref, group_areas=None,
-                 group_atoms=None, isolated=None):
+                 group_atoms=None, isolated=None, stats=None):
+        self.stats = stats
         self.totals, self.class_sums, self.residues = totals, class_sums, residues
         self.selection_areas, self.selection_atoms, self.sasa, self.res_ref = selection_areas, selection_atoms, sasa, res_ref
         self.group_areas, self.group_atoms, self.isolated = group_areas, group_atoms, isolated
@@ -932,14 +1074,21 @@ def _topology_groups(batch, structure, n, chain_groups, separate_chains, long, g
 
 def trajectory_topology(frames, batch, structure=0, atom_index=None, selection=None, per_atom=False, alg=LEE_RICHARDS, probe=1.4,
                         resolution=20, frames_per_batch=0, device=-1, devices=None, chain_groups=None, separate_chains=False,
-                        long=False, group=None, n_groups=None):
+                        long=False, group=None, n_groups=None, stats=None, per_frame=True):
     """freesasa_gpu_trajectory_topology(): frames [F, frame_atoms, 3] of a (solvated) system whose solute is structure
     `structure` of the ingest.Batch - topology atom i is frame atom atom_index[i] (None: the frames hold exactly the
     structure's atoms) - -> a TopologyResult.  The gather, the per-residue, per-class and per-selection sums run on the
     device; the per-atom areas come back only with per_atom=True.
     Chain groups (freesasa_gpu_trajectory_groups): chain_groups="AB+C" (long=True: the long syntax) or separate_chains=True
     as Batch.chain_groups takes them, or group=ids [n] (-1: in no group) with n_groups=G - the result then has group_areas,
-    group_atoms and, with per_atom, isolated."""
+    group_atoms and, with per_atom, isolated.
+    stats=("atoms", "residues", ...) (the names of STATS_BITS; freesasa_gpu_trajectory_groups_stats): the result's stats holds the
+    RunStats of those outputs over the run, reduced on the device shard by shard.  An output named there is computed whether or not
+    it is delivered: with per_atom=False the per-atom areas never leave the device, and with per_frame=False neither do the class
+    sums, residues, selection and group areas."""
+    if stats or not per_frame:
+        return _trajectory_topology_stats(frames, batch, structure, atom_index, selection, per_atom, alg, probe, resolution, frames_per_batch,
+                                          device, devices, chain_groups, separate_chains, long, group, n_groups, stats, per_frame)
     L = _topology_proto(lib())
     frames = np.ascontiguousarray(frames, dtype=np.float64)
     if frames.ndim != 3 or frames.shape[2] != 3:
@@ -978,12 +1127,49 @@ def trajectory_topology(frames, batch, structure=0, atom_index=None, selection=N
     return TopologyResult(totals, cls, res, sel_area, sel_atoms, sasa, res_ref, g_areas, g_atoms, iso)
 
 
+def _trajectory_topology_stats(frames, batch, structure, atom_index, selection, per_atom, alg, probe, resolution, frames_per_batch,
+                               device, devices, chain_groups, separate_chains, long, group, n_groups, stats, per_frame):
+    L = _stats_proto(_topology_proto(lib()))
+    frames = np.ascontiguousarray(frames, dtype=np.float64)
+    if frames.ndim != 3 or frames.shape[2] != 3:
+        raise ValueError("frames must be [n_frames, frame_atoms, 3]")
+    F = frames.shape[0]
+    n, R, res_ref, idx, fa_ = _topology_args(batch, structure, atom_index, frames.shape[1])
+    S = len(selection) if selection is not None else 0
+    ids, G, g_atoms = _topology_groups(batch, structure, n, chain_groups, separate_chains, long, group, n_groups)
+    word = stats_word(stats)
+    totals = np.zeros(F)
+    cls, res = (np.zeros((F, 3)), np.zeros((F, R, 6))) if per_frame else (None, None)
+    sel_area = np.zeros((F, S)) if selection is not None and per_frame else None
+    sel_atoms = np.zeros(S, dtype=np.int64) if selection is not None else None
+    sasa = np.zeros((F, n)) if per_atom else None
+    g_areas = np.zeros((F, max(G, 0), 3)) if ids is not None and per_frame else None
+    iso = np.zeros((F, n)) if ids is not None and per_atom else None
+    W = _stats_proto(lib()).freesasa_gpu_traj_stats_width(word, n, R, S, max(G, 0), None)
+    raw = np.empty((4, max(W, 0)))
+    nf = _shard_frames(F, frames_per_batch)
+    parts = None if nf is None or not word else np.empty((nf.size, 4, max(W, 0)))
+    err = C.create_string_buffer(512)
+    keep, dp_, nd = _devs(devices, device)
+    cb = batch._as_c()
+    opt = lambda a, t=_dp: None if a is None else a.ctypes.data_as(t)
+    ret = L.freesasa_gpu_trajectory_groups_stats(frames.ctypes.data_as(_dp), F, C.byref(cb), structure, fa_, opt(idx, C.POINTER(C.c_int32)),
+                                                 selection.handle if selection is not None else None, opt(ids, C.POINTER(C.c_int32)), G,
+                                                 alg, probe, resolution, frames_per_batch, totals.ctypes.data_as(_dp), opt(sasa),
+                                                 opt(cls), opt(res), opt(sel_area), opt(sel_atoms, C.POINTER(C.c_longlong)), opt(g_areas),
+                                                 opt(iso), dp_, nd, word, raw.ctypes.data_as(_dp) if word else None, opt(parts), err, 512)
+    if ret:
+        raise RuntimeError("freesasa_gpu_trajectory_groups_stats: " + err.value.decode())
+    run = RunStats(raw, word, n, R, S, max(G, 0), parts, nf) if word else None
+    return TopologyResult(totals, cls, res, sel_area, sel_atoms, sasa, res_ref, g_areas, g_atoms if ids is not None else None, iso, run)
+
+
 def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_index=None, frame_atoms=None, selection=None,
                              sasa_path=None, class_sums_path=None, residues_path=None, selections_path=None, done_path=None,
                              f32=False, header_bytes=0, n_frames=0, alg=LEE_RICHARDS, probe=1.4, resolution=20, frames_per_batch=0,
                              max_new_shards=0, device=-1, devices=None, out_f32=False, chain_groups=None, separate_chains=False,
                              long=False, group=None, n_groups=None, group_areas_path=None, isolated_path=None, dcd=False, pbc=False,
-                             triclinic=False, netcdf=False, xtc=False):
+                             triclinic=False, netcdf=False, xtc=False, stats=None, stats_path=None, partials_path=None):
     """freesasa_gpu_trajectory_file_topology(): trajectory_file() with a topology (see trajectory_topology; frame_atoms:
     atoms per frame of the file, None: the structure's) and one raw fp64 result file per output asked for: class sums
     [F, 3], residues [F, R, 6], selection areas [F, S].  Returns (complete, n_frames, selection_atoms [S] or None).
@@ -993,8 +1179,10 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
     pbc: (with dcd) the atoms the index keeps among their periodic images, frame by frame (not offered with chain groups);
     triclinic: (with dcd and pbc) the cell records decoded as triclinic cells, see trajectory_file;
     netcdf: frames_path is an AMBER NetCDF trajectory; frame_atoms None is then the file's atom count; pbc and triclinic as with dcd;
-    xtc: frames_path is a GROMACS XTC trajectory; frame_atoms None is then the file's atom count; pbc and triclinic as with dcd."""
-    L = _topology_proto(lib())
+    xtc: frames_path is a GROMACS XTC trajectory; frame_atoms None is then the file's atom count; pbc and triclinic as with dcd.
+    stats=("atoms", "residues", ...) with stats_path and partials_path (freesasa_gpu_trajectory_file_groups_stats): the run statistics of
+    those outputs, as trajectory_file describes them; an output named there needs no result file of its own."""
+    L = _stats_proto(_topology_proto(lib()))
     bits = _frames_bits(f32, out_f32, dcd, header_bytes, pbc, triclinic, netcdf, xtc)
     if dcd and frame_atoms is None:
         frame_atoms = dcd_info(frames_path).n_atoms
@@ -1011,6 +1199,20 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
     keep, dp_, nd = _devs(devices, device)
     cb = batch._as_c()
     ids, G, _ = _topology_groups(batch, structure, n, chain_groups, separate_chains, long, group, n_groups)
+    if stats:
+        ret = L.freesasa_gpu_trajectory_file_groups_stats(enc(frames_path), bits, header_bytes, n_frames, C.byref(cb), structure, fa_,
+                                                          None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                          selection.handle if selection is not None else None,
+                                                          None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), G,
+                                                          alg, probe, resolution, frames_per_batch, enc(totals_path), enc(sasa_path),
+                                                          enc(class_sums_path), enc(residues_path), enc(selections_path),
+                                                          None if sel_atoms is None else sel_atoms.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                                          enc(group_areas_path), enc(isolated_path),
+                                                          enc(done_path), max_new_shards, dp_, nd, C.byref(total), stats_word(stats),
+                                                          enc(stats_path), enc(partials_path), err, 512)
+        if ret < 0:
+            raise RuntimeError("freesasa_gpu_trajectory_file_groups_stats: " + err.value.decode())
+        return ret == 0, int(total.value), sel_atoms
     if ids is not None or group_areas_path is not None or isolated_path is not None:
         ret = L.freesasa_gpu_trajectory_file_groups(enc(frames_path), bits, header_bytes, n_frames, C.byref(cb), structure, fa_,
                                                     None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),

@@ -112,6 +112,8 @@ hipError_t kl_traj_group_radii(const sasa::TrajGroupArgs &a, hipStream_t st);
 hipError_t kl_traj_group_gather(const sasa::TrajGroupArgs &a, hipStream_t st);
 hipError_t kl_traj_group_finish(const sasa::TrajGroupArgs &a, hipStream_t st);
 hipError_t kl_traj_group_totals(const sasa::TrajGroupArgs &a, hipStream_t st);
+/* ... run statistics: a shard's partial [4][W] of the outputs in the table of segments (one thread per column) */
+hipError_t kl_traj_stats(const sasa::TrajStatsArgs &a, hipStream_t st);
 
 /* periodic images (pbc_kernels.h): image counts and bases (one workgroup per structure); the expanded batch, the real atoms'
    areas out of its areas (both one thread per atom of the caller's batch) */

@@ -23,6 +23,7 @@
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/mman.h>
 #include <sys/stat.h>
 #include <time.h>
 
@@ -143,11 +144,15 @@ enum { OUT_TOTALS, OUT_SASA, OUT_ISO, OUT_CLS, OUT_RES, OUT_SEL, OUT_GRP, N_OUT 
 struct TrajOut {
     const char *name;           /* in messages: "cannot open the %s file", "could not write the %s file" */
     int bit;                    /* in the outputs= word of a done-list's first line */
+    int sbit;                   /* in the statistics word (FREESASA_GPU_STATS_*) */
     void *mem = nullptr;        /* the caller's array [n_frames * per_frame] ... */
     const char *path = nullptr; /* ... or a result file, */
     Fd f;                       /* open for the length of the run */
     size_t esz = 8, per_frame = 0; /* bytes per value (4: per-atom areas asked for as fp32); (TrajRun) values per frame, 0: not computed */
+    bool stat = false;          /* (TrajRun) its run statistics are asked for: computed, whether or not it is delivered ... */
+    size_t s0 = 0;              /* ... and its first column of a shard's partial */
     bool wanted() const { return mem || path; }
+    size_t deliver() const { return wanted() ? per_frame : 0; } /* values per frame that go down and out (0: computed at most) */
 };
 struct TrajIO {
     const double *mem_in = nullptr; /* frames in host memory (fp64) ... */
@@ -165,7 +170,15 @@ struct TrajIO {
     bool tri = false;               /* ... FREESASA_GPU_FRAMES_TRICLINIC beside it: the record decoded as a triclinic cell */
     /* per frame: total [1], per-atom areas [n]; runs with a topology: class sums [3], residue areas [6 R], selection areas [S];
        with chain groups: every atom's area in its isolated group [n], and isolated, complex, buried per group [3 G] */
-    TrajOut out[N_OUT] = {{"totals", 0}, {"per-atom", 1}, {"isolated", 32}, {"class-sums", 2}, {"residues", 4}, {"selections", 8}, {"groups", 16}};
+    TrajOut out[N_OUT] = {{"totals", 0, FREESASA_GPU_STATS_TOTALS}, {"per-atom", 1, FREESASA_GPU_STATS_ATOMS}, {"isolated", 32, FREESASA_GPU_STATS_ISOLATED},
+                          {"class-sums", 2, FREESASA_GPU_STATS_CLASSES}, {"residues", 4, FREESASA_GPU_STATS_RESIDUES},
+                          {"selections", 8, FREESASA_GPU_STATS_SELECTIONS}, {"groups", 16, FREESASA_GPU_STATS_GROUPS}};
+    /* run statistics (include/freesasa_gpu.h): the word; every shard's partial [4][W] at k * 4 W doubles of a host array or of
+       the partials file; the merged result to the caller's array (memory form: the entry merges) or the statistics file */
+    int stats = 0;
+    double *parts_mem = nullptr;
+    const char *stats_path = nullptr, *parts_path = nullptr;
+    Fd parts_f;
     long long *sel_atoms = nullptr; /* the selections' atoms [S]: frame-independent, delivered once */
     bool out_f32() const { return out[OUT_SASA].esz == 4; } /* per-atom and isolated areas written as fp32 (narrowed on the device; an output format) */
     DoneList list;                  /* (active: a file run with a done-list) */
@@ -260,6 +273,33 @@ int group_make(const int32_t *group, int n_groups, bool areas, bool iso, TrajTop
     }
     tp->group = group; tp->n_groups = n_groups; tp->n_iso = (int)n_iso;
     return 0;
+}
+
+/* The argument checks of a statistics word, on the host: 0, or -1 with a message that names the output.  tp NULL: a run without
+   a topology; has_sel, has_group: was a selection set, were group ids given? */
+int stats_check(int stats, const TrajTopo *tp, bool has_sel, bool has_group, char *err_out, int err_len)
+{
+    if (stats & ~127) return set_err(err_out, err_len, "unknown bit in the statistics word");
+    /* (the table's names and bits, without a TrajIO: nothing here allocates) */
+    static const char *const name[N_OUT] = {"totals", "per-atom", "isolated", "class-sums", "residues", "selections", "groups"};
+    static const int sbit[N_OUT] = {FREESASA_GPU_STATS_TOTALS, FREESASA_GPU_STATS_ATOMS, FREESASA_GPU_STATS_ISOLATED, FREESASA_GPU_STATS_CLASSES,
+                                    FREESASA_GPU_STATS_RESIDUES, FREESASA_GPU_STATS_SELECTIONS, FREESASA_GPU_STATS_GROUPS};
+    char msg[160];
+    for (int k = 0; k < N_OUT; ++k) {
+        if (!(stats & sbit[k])) continue;
+        const char *needs = (k == OUT_ISO || k == OUT_GRP) && !has_group ? "chain groups" : k >= OUT_CLS && !tp ? "a topology"
+                          : k == OUT_SEL && !has_sel ? "a selection set" : nullptr;
+        if (!needs) continue;
+        snprintf(msg, sizeof msg, "statistics of the %s output need %s", name[k], needs);
+        return set_err(err_out, err_len, msg);
+    }
+    return 0;
+}
+/* W of a run's statistics word, every output's first column into first[N_OUT] (trajstats.c: the one place that knows the layout) */
+size_t stats_width(int stats, int n_atoms, const TrajTopo *tp, long long *first)
+{
+    const long long W = freesasa_gpu_traj_stats_width(stats, n_atoms, tp ? tp->n_res : 0, tp ? tp->n_sel : 0, tp ? tp->n_groups : 0, first);
+    return W > 0 ? (size_t)W : 0;
 }
 
 /* Once per lane: the topology onto the lane's context - c->seg: residue boundaries | the one structure's offsets | index |
@@ -395,10 +435,13 @@ struct TrajRun {
     const bool in_pinned = io.mem_in && host_pinned(io.mem_in);
     const bool direct_out = io.out[OUT_TOTALS].mem && host_pinned(io.out[OUT_TOTALS].mem) && (!io.out[OUT_SASA].mem || host_pinned(io.out[OUT_SASA].mem)) &&
                             (!io.out[OUT_ISO].mem || host_pinned(io.out[OUT_ISO].mem));
-    const size_t S = topo && topo->sel && (io.out[OUT_SEL].wanted() || io.sel_atoms) ? (size_t)topo->n_sel : 0; /* selections computed */
+    const size_t S = topo && topo->sel && (io.out[OUT_SEL].wanted() || io.sel_atoms || (io.stats & FREESASA_GPU_STATS_SELECTIONS)) ? (size_t)topo->n_sel : 0; /* selections computed */
     /* A shard's sums lie one behind the other in ONE block, cut to its nf frames: classes | residues | selection areas |
        groups | selected atoms.  Output k's begin at x0[k] * nf doubles (k = N_OUT: the atom counts); xw doubles per frame hold it all. */
     size_t x0[N_OUT + 1] = {0, 0, 0}, xw;
+    /* does the block of sums go to the host?  (not when its outputs are computed for their statistics alone) */
+    const bool sums_down = io.out[OUT_CLS].wanted() || io.out[OUT_RES].wanted() || io.out[OUT_SEL].wanted() || io.out[OUT_GRP].wanted() || io.sel_atoms;
+    size_t sW = 0; /* run statistics: columns of a shard's partial; it lies behind a FULL shard's block of sums, at xw * FB doubles of c->h_gtot */
     const std::vector<double> tp = call_test_points(s.alg, s.resolution);
     /* a full shard as a batch: k n; with chain groups behind them FB n + f n_iso + gfirst[g] - and the same for the run's short
        last shard, whose isolated structures begin earlier (without groups a short shard is a prefix of the full one) */
@@ -422,8 +465,13 @@ struct TrajRun {
         batch_offsets(FB, offs);
         if (groups && (size_t)(s.n_frames % s.frames_per_batch)) batch_offsets((size_t)(s.n_frames % s.frames_per_batch), offs_last);
         const size_t per[N_OUT] = {1, n, groups ? n : 0, topo ? (size_t)3 : 0, topo ? 6 * (size_t)topo->n_res : 0, S, 3 * G};
+        long long first[N_OUT];
+        sW = stats_width(io.stats, s.n_atoms, topo, first);
         for (int k = 0; k < N_OUT; ++k) {
-            io.out[k].per_frame = io.out[k].wanted() || k == OUT_SEL ? per[k] : 0;
+            /* computed: delivered, or its statistics asked for (the selections' and the groups' kernels write theirs whenever they run) */
+            io.out[k].stat = (io.stats & io.out[k].sbit) != 0;
+            io.out[k].s0 = io.out[k].stat ? (size_t)first[k] : 0;
+            io.out[k].per_frame = io.out[k].wanted() || io.out[k].stat || k == OUT_SEL || k == OUT_GRP ? per[k] : 0;
             if (k >= OUT_CLS) x0[k + 1] = x0[k] + io.out[k].per_frame;
         }
         xw = x0[N_OUT] + S;
@@ -448,6 +496,7 @@ struct TrajShard {
     const void *src;     /* its frames on the host (page-locked) */
     const void *d_areas, *d_iso; /* its per-atom (and isolated) areas on the device, as they go out */
     char *host[N_OUT];   /* where every output's values are after the download (page-locked) */
+    char *stat_host;     /* ... and the shard's partial statistics [4][W] */
 };
 long long now_ns() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (long long)ts.tv_sec * 1000000000LL + ts.tv_nsec; }
 
@@ -463,7 +512,7 @@ int shard_size(TrajRun &T, TrajLane &L)
         ensure(c, c->h_totals, 8 * (1 + T.G) * FB) ||
         (T.widen_bytes + narrow_bytes && ensure(c, c->h_counts, T.widen_bytes + narrow_bytes)) ||
         ((T.gather || T.container || T.xtc) && ensure(c, c->g_xyz, T.xtc ? T.xtc_f32_at(T.xtc_max_bytes, FB) + (T.gather ? 12 * T.fa * FB : 0)
-                                                                        : T.pbc ? TrajRun::cells_at(T.stride * FB) + T.cell_bytes * FB : T.stride * FB)) || (T.xw && ensure(c, c->h_gtot, 8 * T.xw * FB)) ||
+                                                                        : T.pbc ? TrajRun::cells_at(T.stride * FB) + T.cell_bytes * FB : T.stride * FB)) || (T.xw + T.sW && ensure(c, c->h_gtot, 8 * (T.xw * FB + 4 * T.sW))) ||
         (T.groups && (ensure(c, c->g_gath, 8 * nc * FB) || ensure(c, c->g_tot2, 8 * (1 + T.G) * FB))) || (iso && ensure(c, c->h_iso, 8 * n * FB)))
         return -1;
     if (!T.groups && !L.radii_up && hipMemcpyAsync(c->h_radii.p, T.s.radii, 8 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "radii upload failed");
@@ -790,21 +839,35 @@ int shard_compute(TrajRun &T, TrajLane &L, TrajShard &h)
         h.d_iso = ga.iso;
     }
     /* (file output only) per-atom areas narrowed on the device: half the bytes over PCIe and into the file */
-    const bool narrow = out[OUT_SASA].per_frame && T.io.out_f32();
+    const bool narrow = out[OUT_SASA].deliver() && T.io.out_f32();
     h.d_areas = narrow ? (char *)c->h_counts.p + T.widen_bytes : c->h_sasa.p;
     if (narrow && kl_narrow_f64((const double *)c->h_sasa.p, (float *)h.d_areas, (long long)h.na, c->stream) != hipSuccess) return ctx_fail(c, "narrowing launch failed");
-    if (h.d_iso && T.io.out_f32()) {
+    if (h.d_iso && out[OUT_ISO].deliver() && T.io.out_f32()) {
         h.d_iso = (char *)c->h_counts.p + T.widen_bytes + 4 * T.n * T.FB;
         if (kl_narrow_f64((const double *)c->h_iso.p, (float *)h.d_iso, (long long)h.na, c->stream) != hipSuccess) return ctx_fail(c, "narrowing launch failed");
     }
-    if (!T.xw) return 0;
-    sasa::TrajArgs &ta = L.ta; /* (n_frames: shard_upload's) */
     double *const d_x = (double *)c->h_gtot.p;
-    ta.sasa = (const double *)c->h_sasa.p;
-    ta.cls_out = d_x; ta.res_out = d_x + T.x0[OUT_RES] * nf; ta.sel_out = d_x + T.x0[OUT_SEL] * nf; ta.sel_count = (long long *)(d_x + T.x0[N_OUT] * nf);
-    if ((out[OUT_RES].per_frame && kl_traj_residues(ta, c->stream) != hipSuccess) || (out[OUT_CLS].per_frame && kl_traj_class(ta, c->stream) != hipSuccess) ||
-        (T.S && kl_traj_sel(ta, c->stream) != hipSuccess))
-        return ctx_fail(c, "launch of the per-frame sums failed");
+    if (T.xw) {
+        sasa::TrajArgs &ta = L.ta; /* (n_frames: shard_upload's) */
+        ta.sasa = (const double *)c->h_sasa.p;
+        ta.cls_out = d_x; ta.res_out = d_x + T.x0[OUT_RES] * nf; ta.sel_out = d_x + T.x0[OUT_SEL] * nf; ta.sel_count = (long long *)(d_x + T.x0[N_OUT] * nf);
+        if ((out[OUT_RES].per_frame && kl_traj_residues(ta, c->stream) != hipSuccess) || (out[OUT_CLS].per_frame && kl_traj_class(ta, c->stream) != hipSuccess) ||
+            (T.S && kl_traj_sel(ta, c->stream) != hipSuccess))
+            return ctx_fail(c, "launch of the per-frame sums failed");
+    }
+    if (!T.sW) return 0;
+    /* run statistics: the shard's partial of every output asked for, in ONE launch behind the kernels that wrote the blocks -
+       the fp64 areas and sums where they lie, never the narrowed copies */
+    sasa::TrajStatsArgs sa;
+    memset(&sa, 0, sizeof sa);
+    sa.n_frames = h.nf; sa.W = (int64_t)T.sW; sa.out = d_x + T.xw * T.FB;
+    for (int k = 0; k < N_OUT; ++k) {
+        if (!out[k].stat) continue;
+        const double *src = k == OUT_TOTALS ? (const double *)c->h_totals.p : k == OUT_SASA ? (const double *)c->h_sasa.p
+                          : k == OUT_ISO ? (const double *)c->h_iso.p : d_x + T.x0[k] * nf;
+        sa.seg[sa.n_seg++] = {src, (int64_t)out[k].per_frame, (int64_t)out[k].s0};
+    }
+    if (kl_traj_stats(sa, c->stream) != hipSuccess) return ctx_fail(c, "launch of the statistics failed");
     return 0;
 }
 
@@ -813,17 +876,19 @@ int shard_compute(TrajRun &T, TrajLane &L, TrajShard &h)
 int shard_download(TrajRun &T, freesasa_gpu_ctx *c, TrajShard &h)
 {
     const TrajOut *out = T.io.out;
-    const size_t nf = (size_t)h.nf, sasa_bytes = out[OUT_SASA].esz * out[OUT_SASA].per_frame * nf, iso_bytes = out[OUT_ISO].esz * out[OUT_ISO].per_frame * nf;
-    if (!T.direct_out && ensure_pinned(c, &c->stage_out, &c->stage_out_cap, 8 * nf + 8 * (out[OUT_SASA].per_frame + out[OUT_ISO].per_frame) * nf)) return -1;
-    if (T.xw && ensure_pinned(c, &c->res_stage, &c->res_stage_cap, 8 * T.xw * nf)) return -1;
+    const size_t nf = (size_t)h.nf, sasa_bytes = out[OUT_SASA].esz * out[OUT_SASA].deliver() * nf, iso_bytes = out[OUT_ISO].esz * out[OUT_ISO].deliver() * nf;
+    if (!T.direct_out && ensure_pinned(c, &c->stage_out, &c->stage_out_cap, 8 * nf + 8 * (out[OUT_SASA].deliver() + out[OUT_ISO].deliver()) * nf)) return -1;
+    if (T.xw + T.sW && ensure_pinned(c, &c->res_stage, &c->res_stage_cap, 8 * (T.xw * nf + 4 * T.sW))) return -1;
     for (int k = 0; k < N_OUT; ++k)
         h.host[k] = k >= OUT_CLS ? (char *)c->res_stage + 8 * T.x0[k] * nf
-                  : T.direct_out ? (char *)out[k].mem + 8 * out[k].per_frame * (size_t)h.f0
-                  : (char *)c->stage_out + (k == OUT_SASA ? 8 * nf : k == OUT_ISO ? 8 * nf + 8 * out[OUT_SASA].per_frame * nf : 0);
+                  : T.direct_out ? (char *)out[k].mem + 8 * out[k].deliver() * (size_t)h.f0
+                  : (char *)c->stage_out + (k == OUT_SASA ? 8 * nf : k == OUT_ISO ? 8 * nf + 8 * out[OUT_SASA].deliver() * nf : 0);
+    h.stat_host = (char *)c->res_stage + 8 * T.xw * nf; /* (behind the shard's block of sums) */
     if (hipMemcpyAsync(h.host[OUT_TOTALS], c->h_totals.p, 8 * nf, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         (sasa_bytes && hipMemcpyAsync(h.host[OUT_SASA], h.d_areas, sasa_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
         (iso_bytes && hipMemcpyAsync(h.host[OUT_ISO], h.d_iso, iso_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-        (T.xw && hipMemcpyAsync(c->res_stage, c->h_gtot.p, 8 * (T.x0[N_OUT] * nf + T.S), hipMemcpyDeviceToHost, c->stream) != hipSuccess))
+        (T.xw && T.sums_down && hipMemcpyAsync(c->res_stage, c->h_gtot.p, 8 * (T.x0[N_OUT] * nf + T.S), hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+        (T.sW && hipMemcpyAsync(h.stat_host, (const double *)c->h_gtot.p + T.xw * T.FB, 32 * T.sW, hipMemcpyDeviceToHost, c->stream) != hipSuccess))
         return ctx_fail(c, "device-to-host copy failed");
     if (hipStreamSynchronize(c->stream) != hipSuccess) return ctx_fail(c, "stream synchronize failed");
     return 0;
@@ -834,10 +899,14 @@ int shard_write(TrajRun &T, freesasa_gpu_ctx *c, const TrajShard &h)
 {
     for (int k = 0; k < N_OUT; ++k) {
         const TrajOut &o = T.io.out[k];
-        const size_t bytes = o.esz * o.per_frame * (size_t)h.nf;
-        const long long at = (long long)(o.esz * o.per_frame) * h.f0;
+        const size_t bytes = o.esz * o.deliver() * (size_t)h.nf;
+        const long long at = (long long)(o.esz * o.deliver()) * h.f0;
         if (o.mem && bytes && (char *)o.mem + at != h.host[k]) memcpy((char *)o.mem + at, h.host[k], bytes);
         if (o.f.fd >= 0 && bytes && !pwrite_all(o.f.fd, h.host[k], bytes, at)) return ctx_fail(c, "could not write the %s file", o.name);
+    }
+    if (T.sW) { /* the shard's partial statistics at its place of the partials */
+        if (T.io.parts_mem) memcpy(T.io.parts_mem + 4 * T.sW * (size_t)h.k, h.stat_host, 32 * T.sW);
+        if (T.io.parts_f.fd >= 0 && !pwrite_all(T.io.parts_f.fd, h.stat_host, 32 * T.sW, (long long)(32 * T.sW) * h.k)) return ctx_fail(c, "could not write the partials file");
     }
     if (T.io.sel_atoms && T.S && !T.counts_out.exchange(1)) memcpy(T.io.sel_atoms, (char *)c->res_stage + 8 * T.x0[N_OUT] * (size_t)h.nf, 8 * T.S); /* (frame-independent: once) */
     return 0;
@@ -849,6 +918,7 @@ int shard_record(TrajRun &T, freesasa_gpu_ctx *c, const TrajShard &h)
     if (!T.io.list.active()) return 0;
     for (const TrajOut &o : T.io.out)
         if (o.f.fd >= 0 && fdatasync(o.f.fd) != 0) return ctx_fail(c, "could not flush the result files: the shard is not listed as done");
+    if (T.io.parts_f.fd >= 0 && fdatasync(T.io.parts_f.fd) != 0) return ctx_fail(c, "could not flush the partials file: the shard is not listed as done");
     return T.io.list.append(h.k, h.f0, h.nf) ? ctx_fail(c, "could not append to the done-list") : 0;
 }
 
@@ -921,23 +991,58 @@ int traj_run(TrajIO &io, const TrajSpec &s, char *err_out, int err_len)
     });
 }
 
+/* run statistics: the frames of every shard of a run, for the merge (trajstats.c) */
+std::vector<long long> shard_frames(const TrajSpec &s)
+{
+    const long long n_shards = (s.n_frames + s.frames_per_batch - 1) / s.frames_per_batch;
+    std::vector<long long> nf((size_t)n_shards, s.frames_per_batch);
+    nf.back() = s.n_frames - (n_shards - 1) * s.frames_per_batch;
+    return nf;
+}
+
+/* a memory-form run with its statistics: the partials into the caller's array or one of the call's own, merged when the run is through */
+int traj_run_mem(TrajIO &io, const TrajSpec &s, double *stats_out, double *partials_out, char *err_out, int err_len)
+{
+    if (!io.stats) return traj_run(io, s, err_out, err_len) < 0 ? -1 : 0;
+    std::vector<double> own;
+    const size_t W = stats_width(io.stats, s.n_atoms, s.topo, nullptr);
+    const std::vector<long long> nf = shard_frames(s);
+    if (W && !partials_out) own.resize(4 * W * nf.size());
+    io.parts_mem = W ? (partials_out ? partials_out : own.data()) : nullptr;
+    if (traj_run(io, s, err_out, err_len) < 0) return -1;
+    if (W && freesasa_gpu_traj_stats_merge(io.parts_mem, nf.data(), (long long)nf.size(), (long long)W, stats_out, nullptr))
+        return set_err(err_out, err_len, "could not merge the partial statistics");
+    return 0;
+}
+
 } /* namespace */
 
 /* ------------------------------------------------------------------ entry points: trajectories */
+
+extern "C" int freesasa_gpu_trajectory_stats(const double *xyz_frames, const double *radii, int n_atoms, int n_frames,
+                                             int alg, double probe, int resolution, int frames_per_batch,
+                                             double *totals_out, double *sasa_out, const int *devices, int n_devices,
+                                             int stats, double *stats_out, double *partials_out, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (!xyz_frames || !radii || !totals_out) return set_err(err_out, err_len, "null argument");
+    if (stats_check(stats, nullptr, false, false, err_out, err_len)) return -1;
+    if (stats && !stats_out) return set_err(err_out, err_len, "statistics are asked for but have nowhere to go (stats_out is NULL)");
+    TrajSpec s = {radii, n_atoms, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices};
+    if (traj_check_args(s, "n_atoms and n_frames must be > 0", err_out, err_len) || traj_shard_size(s, n_atoms, err_out, err_len)) return -1;
+    return guarded(err_out, err_len, [&]() -> int {
+        TrajIO io;
+        io.mem_in = xyz_frames; io.out[OUT_TOTALS].mem = totals_out; io.out[OUT_SASA].mem = sasa_out; io.stats = stats;
+        return traj_run_mem(io, s, stats_out, partials_out, err_out, err_len);
+    });
+}
 
 extern "C" int freesasa_gpu_trajectory_devices(const double *xyz_frames, const double *radii, int n_atoms, int n_frames,
                                                int alg, double probe, int resolution, int frames_per_batch,
                                                double *totals_out, double *sasa_out, const int *devices, int n_devices, char *err_out, int err_len)
 {
-    if (err_out && err_len > 0) err_out[0] = 0;
-    if (!xyz_frames || !radii || !totals_out) return set_err(err_out, err_len, "null argument");
-    TrajSpec s = {radii, n_atoms, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices};
-    if (traj_check_args(s, "n_atoms and n_frames must be > 0", err_out, err_len) || traj_shard_size(s, n_atoms, err_out, err_len)) return -1;
-    return guarded(err_out, err_len, [&]() -> int {
-        TrajIO io;
-        io.mem_in = xyz_frames; io.out[OUT_TOTALS].mem = totals_out; io.out[OUT_SASA].mem = sasa_out;
-        return traj_run(io, s, err_out, err_len) < 0 ? -1 : 0;
-    });
+    return freesasa_gpu_trajectory_stats(xyz_frames, radii, n_atoms, n_frames, alg, probe, resolution, frames_per_batch, totals_out, sasa_out, devices, n_devices,
+                                         0, nullptr, nullptr, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_trajectory(const double *xyz_frames, const double *radii, int n_atoms, int n_frames,
@@ -945,6 +1050,37 @@ extern "C" int freesasa_gpu_trajectory(const double *xyz_frames, const double *r
                                        double *totals_out, double *sasa_out, int device, char *err_out, int err_len)
 {
     return freesasa_gpu_trajectory_devices(xyz_frames, radii, n_atoms, n_frames, alg, probe, resolution, frames_per_batch, totals_out, sasa_out, &device, 1, err_out, err_len);
+}
+
+extern "C" int freesasa_gpu_trajectory_groups_stats(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
+                                                    int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
+                                                    const int32_t *group, int n_groups,
+                                                    int alg, double probe, int resolution, int frames_per_batch,
+                                                    double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
+                                                    double *sel_area_out, long long *sel_atoms_out, double *group_areas_out, double *iso_out,
+                                                    const int *devices, int n_devices,
+                                                    int stats, double *stats_out, double *partials_out, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    return guarded(err_out, err_len, [&]() -> int {
+        TrajTopo tp;
+        if (topo_make(batch, structure, frame_atoms, atom_index, sel, &tp, err_out, err_len)) return -1;
+        if (stats_check(stats, &tp, sel != nullptr, group != nullptr, err_out, err_len)) return -1;
+        if (stats && !stats_out) return set_err(err_out, err_len, "statistics are asked for but have nowhere to go (stats_out is NULL)");
+        /* (statistics of either group output make the groups' areas wanted: their kernels run) */
+        if (group_make(group, n_groups, group_areas_out || (stats & (FREESASA_GPU_STATS_GROUPS | FREESASA_GPU_STATS_ISOLATED)),
+                       iso_out || (stats & FREESASA_GPU_STATS_ISOLATED), &tp, err_out, err_len)) return -1;
+        if (!xyz_frames || !totals_out) return set_err(err_out, err_len, "null argument");
+        if ((sel_area_out || sel_atoms_out) && !sel) return set_err(err_out, err_len, "selection outputs need a selection set");
+        TrajSpec s = {tp.radii, tp.n, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, &tp};
+        if (traj_check_args(s, "n_frames must be > 0", err_out, err_len) || traj_shard_size(s, frame_atoms, err_out, err_len)) return -1;
+        TrajIO io;
+        io.mem_in = xyz_frames; io.sel_atoms = sel_atoms_out;
+        double *const mem[N_OUT] = {totals_out, sasa_out, iso_out, class_sums_out, residues_out, sel_area_out, group_areas_out};
+        for (int k = 0; k < N_OUT; ++k) io.out[k].mem = mem[k];
+        io.stats = stats;
+        return traj_run_mem(io, s, stats_out, partials_out, err_out, err_len);
+    });
 }
 
 extern "C" int freesasa_gpu_trajectory_groups(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
@@ -955,21 +1091,9 @@ extern "C" int freesasa_gpu_trajectory_groups(const double *xyz_frames, int n_fr
                                               double *sel_area_out, long long *sel_atoms_out, double *group_areas_out, double *iso_out,
                                               const int *devices, int n_devices, char *err_out, int err_len)
 {
-    if (err_out && err_len > 0) err_out[0] = 0;
-    return guarded(err_out, err_len, [&]() -> int {
-        TrajTopo tp;
-        if (topo_make(batch, structure, frame_atoms, atom_index, sel, &tp, err_out, err_len)) return -1;
-        if (group_make(group, n_groups, group_areas_out != nullptr, iso_out != nullptr, &tp, err_out, err_len)) return -1;
-        if (!xyz_frames || !totals_out) return set_err(err_out, err_len, "null argument");
-        if ((sel_area_out || sel_atoms_out) && !sel) return set_err(err_out, err_len, "selection outputs need a selection set");
-        TrajSpec s = {tp.radii, tp.n, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, &tp};
-        if (traj_check_args(s, "n_frames must be > 0", err_out, err_len) || traj_shard_size(s, frame_atoms, err_out, err_len)) return -1;
-        TrajIO io;
-        io.mem_in = xyz_frames; io.sel_atoms = sel_atoms_out;
-        double *const mem[N_OUT] = {totals_out, sasa_out, iso_out, class_sums_out, residues_out, sel_area_out, group_areas_out};
-        for (int k = 0; k < N_OUT; ++k) io.out[k].mem = mem[k];
-        return traj_run(io, s, err_out, err_len) < 0 ? -1 : 0;
-    });
+    return freesasa_gpu_trajectory_groups_stats(xyz_frames, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups, alg, probe, resolution,
+                                                frames_per_batch, totals_out, sasa_out, class_sums_out, residues_out, sel_area_out, sel_atoms_out,
+                                                group_areas_out, iso_out, devices, n_devices, 0, nullptr, nullptr, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_trajectory_topology(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
@@ -988,7 +1112,7 @@ extern "C" int freesasa_gpu_trajectory_topology(const double *xyz_frames, int n_
    time and a checksum of the radii - NOT the devices: a run interrupted on eight GPUs may be finished on one, with the same
    files byte for byte.  With a topology, in front of the line's end, what its outputs depend on: digests of the index, of
    residue boundaries + classes + backbone flags, of the selection set's program, and which result files the run writes; with
-   chain groups, behind that, a digest of the group count and the ids.  A DCD run: bit 2 in the f32= word and the byte of
+   chain groups, behind that, a digest of the group count and the ids; with run statistics, last, the word as stats=.  A DCD run: bit 2 in the f32= word and the byte of
    frame 0 as header_bytes=; an AMBER NetCDF run: bit 5 and the byte of record 0; an XTC run: bit 6 (its frames are found by the index: header_bytes=0); a raw run's line is what it was.  Periodic images: bit 3 in the f32= word, triclinic cells: bit 4. */
 static int traj_done_head(char *head, size_t cap, const TrajSpec &s, const TrajIO &io, const struct stat &st)
 {
@@ -1015,6 +1139,8 @@ static int traj_done_head(char *head, size_t cap, const TrajSpec &s, const TrajI
         if (tp->group && len > 0 && len < (int)cap)
             len += snprintf(head + len - 1, cap - (size_t)len + 1, " groups=%016llx\n", fnv1a(tp->group, 4 * (size_t)tp->n, fnv1a(&tp->n_groups, sizeof tp->n_groups))) - 1;
     }
+    /* ... and with run statistics the word (a run without statistics keeps the line it had) */
+    if (io.stats && len > 0 && len < (int)cap) len += snprintf(head + len - 1, cap - (size_t)len + 1, " stats=%d\n", io.stats) - 1;
     return len > 0 && len < (int)cap ? 0 : -1;
 }
 
@@ -1025,6 +1151,7 @@ static int trajectory_file_run(const char *frames_path, int frames_f32, long lon
 {
     if (!frames_path || !s.radii || !io.out[OUT_TOTALS].path) return set_err(err_out, err_len, "null argument");
     if (s.n_atoms <= 0 || header_bytes < 0) return set_err(err_out, err_len, "bad argument");
+    if (io.stats && (!io.stats_path || !io.parts_path)) return set_err(err_out, err_len, "statistics need a statistics path and a partials path");
     const long long frame_atoms = s.topo ? s.topo->frame_atoms : s.n_atoms;
     if ((frames_f32 & FREESASA_GPU_FRAMES_PBC) && !(frames_f32 & (FREESASA_GPU_FRAMES_DCD | FREESASA_GPU_FRAMES_NETCDF | FREESASA_GPU_FRAMES_XTC)))
         return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) needs bit 2 (a DCD file), bit 5 (an AMBER NetCDF file) or bit 6 (an XTC file): raw frame files carry no cell");
@@ -1107,7 +1234,8 @@ static int trajectory_file_run(const char *frames_path, int frames_f32, long lon
         if (traj_done_head(head, sizeof head, s, io, st)) return set_err(err_out, err_len, "cannot write the done-list");
         const int fpb = s.frames_per_batch;
         if (io.list.read(done_path, head, (s.n_frames + fpb - 1) / fpb, [fpb](long long k, long long f0, long long) { return f0 == k * fpb; }) == DoneList::REFUSED)
-            return set_err(err_out, err_len, s.topo && s.topo->group ? "the done-list belongs to a run with other parameters, radii, topology, selections, chain groups, outputs or frame file"
+            return set_err(err_out, err_len, io.stats ? "the done-list belongs to a run with other parameters, radii, topology, outputs, statistics or frame file"
+                                           : s.topo && s.topo->group ? "the done-list belongs to a run with other parameters, radii, topology, selections, chain groups, outputs or frame file"
                                            : s.topo ? "the done-list belongs to a run with other parameters, radii, topology, selections, outputs or frame file"
                                                     : "the done-list belongs to a run with other parameters, radii or frame file");
     }
@@ -1116,11 +1244,54 @@ static int trajectory_file_run(const char *frames_path, int frames_f32, long lon
         o.f.fd = open(o.path, io.list.resumed() ? O_WRONLY | O_CREAT : O_WRONLY | O_CREAT | O_TRUNC, 0644);
         if (o.f.fd < 0) return set_err(err_out, err_len, ("cannot open the " + std::string(o.name) + " file").c_str());
     }
+    if (io.stats) { /* the partials like a result file; a statistics file of an earlier run does not outlive the start of a fresh one */
+        if (!io.list.resumed()) (void)unlink(io.stats_path);
+        io.parts_f.fd = open(io.parts_path, io.list.resumed() ? O_RDWR | O_CREAT : O_RDWR | O_CREAT | O_TRUNC, 0644);
+        if (io.parts_f.fd < 0) return set_err(err_out, err_len, "cannot open the partials file");
+    }
     if (done_path) {
         const int orc = io.list.open();
         if (orc) return set_err(err_out, err_len, orc == -1 ? "cannot open the done-list" : "cannot write the done-list");
     }
-    return traj_run(io, s, err_out, err_len);
+    const int rc = traj_run(io, s, err_out, err_len);
+    if (rc != 0 || !io.stats) return rc;
+    /* every shard is done - by this call or by earlier ones: the partials back from their file, merged, the statistics file */
+    const size_t W = stats_width(io.stats, s.n_atoms, s.topo, nullptr);
+    const std::vector<long long> nf = shard_frames(s);
+    /* (mapped, not read: the partials of a long run are tens of megabytes that the merge walks once) */
+    const size_t part_bytes = 32 * W * nf.size();
+    struct stat pst;
+    if (fstat(io.parts_f.fd, &pst) != 0 || (size_t)pst.st_size < part_bytes) return set_err(err_out, err_len, "the partials file is shorter than its shards: it is not this run's");
+    std::vector<double> merged(4 * W);
+    void *parts = mmap(nullptr, part_bytes, PROT_READ, MAP_SHARED | MAP_POPULATE, io.parts_f.fd, 0);
+    if (parts == MAP_FAILED) return set_err(err_out, err_len, "could not read the partials file");
+    const int mrc = freesasa_gpu_traj_stats_merge((const double *)parts, nf.data(), (long long)nf.size(), (long long)W, merged.data(), nullptr);
+    (void)munmap(parts, part_bytes);
+    if (mrc) return set_err(err_out, err_len, "could not merge the partial statistics");
+    Fd out;
+    out.fd = open(io.stats_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (out.fd < 0) return set_err(err_out, err_len, "cannot open the statistics file");
+    /* (flushed like the result files: in a run with a done-list) */
+    if (!pwrite_all(out.fd, merged.data(), 8 * merged.size(), 0) || (io.list.active() && fdatasync(out.fd) != 0)) return set_err(err_out, err_len, "could not write the statistics file");
+    return 0;
+    });
+}
+
+extern "C" int freesasa_gpu_trajectory_file_stats(const char *frames_path, int frames_f32, long long header_bytes, const double *radii,
+                                                  int n_atoms, long long n_frames, int alg, double probe, int resolution,
+                                                  int frames_per_batch, const char *totals_path, const char *sasa_path,
+                                                  const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                                  long long *frames_total_out,
+                                                  int stats, const char *stats_path, const char *partials_path, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (stats_check(stats, nullptr, false, false, err_out, err_len)) return -1;
+    TrajSpec s = {radii, n_atoms, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, nullptr, max_new_shards};
+    return guarded(err_out, err_len, [&]() -> int {
+        TrajIO io;
+        io.out[OUT_TOTALS].path = totals_path; io.out[OUT_SASA].path = sasa_path;
+        io.stats = stats; io.stats_path = stats_path; io.parts_path = partials_path;
+        return trajectory_file_run(frames_path, frames_f32, header_bytes, s, io, done_path, frames_total_out, err_out, err_len);
     });
 }
 
@@ -1130,11 +1301,9 @@ extern "C" int freesasa_gpu_trajectory_file_devices(const char *frames_path, int
                                                     const char *done_path, long long max_new_shards, const int *devices, int n_devices,
                                                     long long *frames_total_out, char *err_out, int err_len)
 {
-    if (err_out && err_len > 0) err_out[0] = 0;
-    TrajSpec s = {radii, n_atoms, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, nullptr, max_new_shards};
-    TrajIO io;
-    io.out[OUT_TOTALS].path = totals_path; io.out[OUT_SASA].path = sasa_path;
-    return trajectory_file_run(frames_path, frames_f32, header_bytes, s, io, done_path, frames_total_out, err_out, err_len);
+    return freesasa_gpu_trajectory_file_stats(frames_path, frames_f32, header_bytes, radii, n_atoms, n_frames, alg, probe, resolution, frames_per_batch,
+                                              totals_path, sasa_path, done_path, max_new_shards, devices, n_devices, frames_total_out,
+                                              0, nullptr, nullptr, err_out, err_len);
 }
 
 /* the file form with a topology, with or without chain groups: both entries below */
@@ -1147,21 +1316,49 @@ static int trajectory_file_topo(const char *frames_path, int frames_f32, long lo
                                 const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
                                 const char *group_areas_path, const char *iso_path,
                                 const char *done_path, long long max_new_shards, const int *devices, int n_devices,
-                                long long *frames_total_out, char *err_out, int err_len)
+                                long long *frames_total_out, int stats, const char *stats_path, const char *partials_path, char *err_out, int err_len)
 {
     if (err_out && err_len > 0) err_out[0] = 0;
     return guarded(err_out, err_len, [&]() -> int {
         TrajTopo tp; /* (outlives the run: the lanes upload from it) */
         if (topo_make(batch, structure, frame_atoms, atom_index, sel, &tp, err_out, err_len)) return -1;
-        if (group_make(group, n_groups, group_areas_path != nullptr, iso_path != nullptr, &tp, err_out, err_len)) return -1;
+        if (stats_check(stats, &tp, sel != nullptr, group != nullptr, err_out, err_len)) return -1;
+        if (group_make(group, n_groups, group_areas_path || (stats & (FREESASA_GPU_STATS_GROUPS | FREESASA_GPU_STATS_ISOLATED)),
+                       iso_path || (stats & FREESASA_GPU_STATS_ISOLATED), &tp, err_out, err_len)) return -1;
         if ((sel_area_path || sel_atoms_out) && !sel) return set_err(err_out, err_len, "selection outputs need a selection set");
         TrajSpec s = {tp.radii, tp.n, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, &tp, max_new_shards};
         TrajIO io;
         io.sel_atoms = sel_atoms_out;
         const char *const path[N_OUT] = {totals_path, sasa_path, iso_path, class_sums_path, residues_path, sel_area_path, group_areas_path};
         for (int k = 0; k < N_OUT; ++k) io.out[k].path = path[k];
+        io.stats = stats; io.stats_path = stats_path; io.parts_path = partials_path;
         return trajectory_file_run(frames_path, frames_f32, header_bytes, s, io, done_path, frames_total_out, err_out, err_len);
     });
+}
+
+extern "C" int freesasa_gpu_trajectory_file_groups_stats(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
+                                                         const freesasa_ingest_batch *batch, int structure,
+                                                         int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
+                                                         const int32_t *group, int n_groups,
+                                                         int alg, double probe, int resolution, int frames_per_batch,
+                                                         const char *totals_path, const char *sasa_path, const char *class_sums_path,
+                                                         const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
+                                                         const char *group_areas_path, const char *iso_path,
+                                                         const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                                         long long *frames_total_out,
+                                                         int stats, const char *stats_path, const char *partials_path, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    /* (group NULL and neither group output: the run is freesasa_gpu_trajectory_file_topology's, periodic images included) */
+    const bool with_groups = group || group_areas_path || iso_path || (stats & (FREESASA_GPU_STATS_GROUPS | FREESASA_GPU_STATS_ISOLATED));
+    if (with_groups && (frames_f32 & FREESASA_GPU_FRAMES_TRICLINIC))
+        return set_err(err_out, err_len, "bit 4 of frames_f32 (triclinic cells) is not offered with chain groups: an isolated group among periodic images is not defined");
+    if (with_groups && (frames_f32 & FREESASA_GPU_FRAMES_PBC))
+        return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) is not offered with chain groups: an isolated group among periodic images is not defined");
+    return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,
+                                alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
+                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, done_path, max_new_shards, devices, n_devices,
+                                frames_total_out, stats, stats_path, partials_path, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_trajectory_file_groups(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
@@ -1183,7 +1380,7 @@ extern "C" int freesasa_gpu_trajectory_file_groups(const char *frames_path, int 
     return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,
                                 alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
                                 sel_area_path, sel_atoms_out, group_areas_path, iso_path, done_path, max_new_shards, devices, n_devices,
-                                frames_total_out, err_out, err_len);
+                                frames_total_out, 0, nullptr, nullptr, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_trajectory_file_topology(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
@@ -1198,7 +1395,7 @@ extern "C" int freesasa_gpu_trajectory_file_topology(const char *frames_path, in
     return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, nullptr, 0,
                                 alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
                                 sel_area_path, sel_atoms_out, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
-                                frames_total_out, err_out, err_len);
+                                frames_total_out, 0, nullptr, nullptr, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_trajectory_file(const char *frames_path, int frames_f32, long long header_bytes, const double *radii,

@@ -1010,6 +1010,20 @@ hipError_t kl_traj_group_totals(const TrajGroupArgs &a, hipStream_t st)
     return hipGetLastError();
 }
 
+/* ... run statistics (traj_kernels.h): a shard's partial, one thread per column, one launch for every output asked for.  Workgroups
+   of one wave: a shard of 10^4 columns still spreads over 157 compute units, and a thread's frame loop is serial by definition */
+#define TRAJ_STAT_B 64
+__global__ __launch_bounds__(TRAJ_STAT_B) void k_traj_stats(TrajStatsArgs a)
+{
+    traj_stats(a, (int64_t)blockIdx.x * TRAJ_STAT_B + threadIdx.x);
+}
+hipError_t kl_traj_stats(const TrajStatsArgs &a, hipStream_t st)
+{
+    if (a.W <= 0 || a.n_frames <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_traj_stats, dim3((unsigned)((a.W + TRAJ_STAT_B - 1) / TRAJ_STAT_B)), dim3(TRAJ_STAT_B), 0, st, a);
+    return hipGetLastError();
+}
+
 /* periodic images (pbc_kernels.h): the image counts and their bases (one workgroup per structure), the expanded batch in
    front of the engine and the real atoms' areas behind it (one thread per atom of the caller's batch) */
 __global__ __launch_bounds__(PBC_B) void k_pbc_count(PbcArgs a)

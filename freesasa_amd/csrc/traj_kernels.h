@@ -10,7 +10,8 @@
  *   traj_residue       the six per-residue areas of every (frame, residue), as residue_areas (sasa_kernels.h)
  *   traj_class_phase0  the three class sums of every frame, as class_phase0 / class_phase1
  *   traj_sel_phase0/1  the selection areas of every frame, as sel_sums_phase0 / sel_sums_phase1 (select_kernels.h)
- *   traj_group_*       chain groups per frame: the isolated structures behind the frames, as group_kernels.h (at the end)
+ *   traj_group_*       chain groups per frame: the isolated structures behind the frames, as group_kernels.h
+ *   traj_stats         run statistics: a shard's partial (mean, M2, min, max) of every column of the outputs asked for (at the end)
  *
  * Atom i of frame f is element f * n + i of the shard's per-atom areas and reads the per-topology arrays at i.  Every sum
  * takes its atoms in the order of the function it is named after - the same chunks of SASA_TOT_B, left to right, the
@@ -281,6 +282,79 @@ SASA_D void traj_group_totals(const TrajGroupArgs &a, int64_t t)
     a.out[3 * t] = t0;
     a.out[3 * t + 1] = t1;
     a.out[3 * t + 2] = t0 - t1;
+}
+
+/* ------------------------------------------------------------------ run statistics
+ * (freesasa_gpu_trajectory_stats and its kin, include/freesasa_gpu.h): a shard's PARTIAL of every output statistics are asked
+ * for - per column of the output's block a[n_frames][width] of fp64 the mean, M2 = sum (a - mean)^2, the smallest and the
+ * largest value.  The blocks are where the kernels before this one wrote them; a small table of segments says which block a
+ * column of the partial belongs to.  One thread per column, ONE launch per shard: consecutive lanes take consecutive columns,
+ * so every frame's row is read coalesced; the frame loop is serial in the thread, because its order is the definition - the
+ * frames of a column are never split over lanes, and the second pass re-reads the block (a shard's areas were just written).
+ * Every operation is rounded on its own: the square is a multiplication of its own, never fused into the add (contraction is
+ * switched off in the function itself). */
+
+#define TRAJ_STAT_SEGS 7 /* the drivers' table of outputs has seven rows */
+#define TRAJ_STAT_U 8    /* rows a thread loads ahead of its additions */
+struct TrajStatSeg {
+    const double *src;    /* the output's block [n_frames][width] */
+    int64_t width, first; /* ... and its first column of the partial */
+};
+struct TrajStatsArgs {
+    int n_frames;   /* frames of this shard */
+    int n_seg;
+    int64_t W;      /* columns of the partial: the sum of the segments' widths */
+    TrajStatSeg seg[TRAJ_STAT_SEGS];
+    double *out;    /* [4][W]: mean, M2, min, max */
+};
+
+SASA_D void traj_stats(const TrajStatsArgs &a, int64_t t)
+{
+#ifndef SASA_EMU
+#pragma clang fp contract(off) /* (the emulation is built with -ffp-contract=off; so is the library - this holds whatever the flags) */
+#endif
+    if (t >= a.W) return;
+    int k = 0;
+    while (k + 1 < a.n_seg && t >= a.seg[k + 1].first) ++k;
+    const int64_t w = a.seg[k].width;
+    const double *col = a.seg[k].src + (t - a.seg[k].first);
+    /* TRAJ_STAT_U rows are loaded before the first of them is added: the loads of a thread are in flight together (a load per
+       add would wait out the memory's latency n_frames times), the additions stay in frame order */
+    const int nf = a.n_frames;
+    double s = 0, lo = col[0], hi = col[0];
+    int f = 0;
+    for (; f + TRAJ_STAT_U <= nf; f += TRAJ_STAT_U) {
+        double v[TRAJ_STAT_U];
+        for (int q = 0; q < TRAJ_STAT_U; ++q) v[q] = col[(int64_t)(f + q) * w];
+        for (int q = 0; q < TRAJ_STAT_U; ++q) {
+            s += v[q];
+            lo = v[q] < lo ? v[q] : lo;
+            hi = v[q] > hi ? v[q] : hi;
+        }
+    }
+    for (; f < nf; ++f) {
+        const double v = col[(int64_t)f * w];
+        s += v;
+        lo = v < lo ? v : lo;
+        hi = v > hi ? v : hi;
+    }
+    const double mean = s / (double)nf;
+    double m2 = 0;
+    for (f = 0; f + TRAJ_STAT_U <= nf; f += TRAJ_STAT_U) {
+        double v[TRAJ_STAT_U];
+        for (int q = 0; q < TRAJ_STAT_U; ++q) v[q] = col[(int64_t)(f + q) * w];
+        for (int q = 0; q < TRAJ_STAT_U; ++q) {
+            const double d = v[q] - mean;
+            const double sq = d * d;
+            m2 += sq;
+        }
+    }
+    for (; f < nf; ++f) {
+        const double d = col[(int64_t)f * w] - mean;
+        const double sq = d * d;
+        m2 += sq;
+    }
+    a.out[t] = mean; a.out[a.W + t] = m2; a.out[2 * a.W + t] = lo; a.out[3 * a.W + t] = hi;
 }
 
 } /* namespace sasa */

@@ -797,6 +797,81 @@ int freesasa_gpu_trajectory_file_groups(const char *frames_path, int frames_f32,
                                         const char *done_path, long long max_new_shards, const int *devices, int n_devices,
                                         long long *frames_total_out, char *err, int err_len);
 
+/* RUN STATISTICS of the trajectory drivers: mean, standard deviation, minimum and maximum over the frames of a run, of any
+   per-frame output, reduced on the device - the per-frame values need not leave it (what `gmx sasa -or / -oa` prints; the
+   per-atom stream-out is n_frames x n_atoms values, the statistics are 4 x n_atoms).
+   stats: a word of FREESASA_GPU_STATS_* bits, one per output.  An output with its bit set is COMPUTED for every frame whether
+   or not its array / its path is given; without array or path it is neither downloaded nor written.  W = the sum of the widths
+   of the outputs asked for, in the order totals [1] | per-atom [n] | isolated [n] | class sums [3] | residues [6 R] |
+   selections [S] | groups [3 G] (freesasa_gpu_traj_stats_width gives W and every output's first column).
+   The definition (the tests hold the device to it bit for bit; fp64, every operation rounded on its own, no fma).  Per shard -
+   frames [f0, f0 + nf) - and per column j of its block a[nf][w] of fp64 values (never the fp32 copies of an out-f32 run):
+       s = 0; for f = 0 .. nf-1: s += a[f][j];     mean = s / nf;     lo, hi = the smallest and largest a[f][j];
+       M2 = 0; for f = 0 .. nf-1: d = a[f][j] - mean; M2 += d * d
+   the shard's PARTIAL is [4][W]: mean, M2, lo, hi.  The partials of a run are merged in shard order, left to right, starting
+   from shard 0's; with n frames so far and nb of the next shard:
+       t = n + nb;  d = mean_b - mean;  mean += d * (nb / t);  M2 = (M2 + M2_b) + (d * d) * (n * (nb / t));  lo = min, hi = max;  n = t
+   and the result is [4][W]: mean, std = sqrt(M2 / n) (the population's, numpy's default), min, max.
+   A run's statistics depend on the frames and on frames_per_batch - not on the device list, the lanes or on how often the run
+   was interrupted and resumed.  Runs with different frames_per_batch agree to rounding, NOT to the bit.
+   Memory forms: stats_out [4][W]; partials_out [n_shards][4][W] or NULL.  File forms: partials_path receives the partials as
+   the shards finish (raw fp64, shard k at byte k * 4 W * 8; flushed with the result files before the shard is listed);
+   a call that finds every shard done merges them and writes stats_path, raw fp64 [4][W]; a call stopped by max_new_shards writes
+   none, a run that is not resumed removes a stale one at its start, a repeated call on a complete run writes the same bytes.
+   With statistics the done-list's first line ends in stats=<word>; a list written with another word is refused; without
+   statistics the line is what it was.  With stats == 0 every entry below is its parent.
+   Argument errors, -1 with a message that names the output, before a device is touched or a file opened: class sums, residues
+   or selections without a topology (the two plain entries), selections without a selection set, groups or isolated areas
+   without chain groups, an unknown bit, statistics without stats_out / without stats_path and partials_path.
+   Not offered: medians and quantiles, time correlation, statistics independent of frames_per_batch to the bit, weights per frame. */
+#define FREESASA_GPU_STATS_TOTALS 1
+#define FREESASA_GPU_STATS_ATOMS 2
+#define FREESASA_GPU_STATS_ISOLATED 4
+#define FREESASA_GPU_STATS_CLASSES 8
+#define FREESASA_GPU_STATS_RESIDUES 16
+#define FREESASA_GPU_STATS_SELECTIONS 32
+#define FREESASA_GPU_STATS_GROUPS 64
+int freesasa_gpu_trajectory_stats(const double *xyz_frames, const double *radii, int n_atoms, int n_frames,
+                                  int alg, double probe_radius, int resolution, int frames_per_batch,
+                                  double *totals_out, double *sasa_out, const int *devices, int n_devices,
+                                  int stats, double *stats_out, double *partials_out, char *err_out, int err_len);
+int freesasa_gpu_trajectory_groups_stats(const double *xyz_frames, int n_frames, const struct freesasa_ingest_batch *batch, int structure,
+                                         int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
+                                         const int32_t *group, int n_groups,
+                                         int alg, double probe_radius, int resolution, int frames_per_batch,
+                                         double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
+                                         double *sel_area_out, long long *sel_atoms_out, double *group_areas_out, double *iso_out,
+                                         const int *devices, int n_devices,
+                                         int stats, double *stats_out, double *partials_out, char *err, int err_len);
+int freesasa_gpu_trajectory_file_stats(const char *frames_path, int frames_f32, long long header_bytes, const double *radii,
+                                       int n_atoms, long long n_frames, int alg, double probe_radius, int resolution,
+                                       int frames_per_batch, const char *totals_path, const char *sasa_path,
+                                       const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                       long long *frames_total_out,
+                                       int stats, const char *stats_path, const char *partials_path, char *err_out, int err_len);
+int freesasa_gpu_trajectory_file_groups_stats(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
+                                              const struct freesasa_ingest_batch *batch, int structure,
+                                              int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
+                                              const int32_t *group, int n_groups,
+                                              int alg, double probe_radius, int resolution, int frames_per_batch,
+                                              const char *totals_path, const char *sasa_path, const char *class_sums_path,
+                                              const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
+                                              const char *group_areas_path, const char *iso_path,
+                                              const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                              long long *frames_total_out,
+                                              int stats, const char *stats_path, const char *partials_path, char *err, int err_len);
+/* W of a statistics word for a system of n_atoms atoms, n_res residues, n_sel selections and n_groups groups; first_out (may be
+   NULL) [7] receives the first column of every output in the order above, -1 for one whose bit is not set.  -1: an unknown bit
+   or a negative count.  (csrc/trajstats.c: plain C, no allocation, no GPU call.) */
+long long freesasa_gpu_traj_stats_width(int stats, long long n_atoms, long long n_res, long long n_sel, long long n_groups,
+                                        long long *first_out);
+/* The merge above over n_parts consecutive partials parts [n_parts][4][width] of frames_per_part [n_parts] frames each:
+   out [4][width] = mean, std, min, max; frames_total_out (may be NULL) their frames.  Exported so that a caller can merge ANY
+   run of consecutive shards of a partials file: block averages, the error estimate of an MD average.  No allocation, no GPU
+   call.  -1 (out untouched): a NULL argument, n_parts < 1, a part with fewer than 1 frame, width < 1. */
+int freesasa_gpu_traj_stats_merge(const double *parts, const long long *frames_per_part, long long n_parts, long long width,
+                                  double *out, long long *frames_total_out);
+
 /* Chain groups: the area of every atom in its complex AND in its group taken on its own (the reference's
    --chain-groups / --separate-chains: freesasa_structure_get_chains_lcl, src/structure.c:1026-1080, minus the
    re-classification), so that iso - sasa is the area an atom buries in the complex.

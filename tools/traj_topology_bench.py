@@ -51,9 +51,17 @@ and one atom more), no topology, and the arms are three files of the same decode
 each line with the host CPU time of the process per atom-frame; the totals files must be identical.  --xtc-fpb sets
 frames_per_batch for all three arms (0: the driver's default).
 
+With --stats the frames are those of the 10 000 solute atoms alone (fp32, no solvent, the topology the whole frame) and the arms are
+what a caller who wants the averages over the run can do, interleaved:
+    totals    trajectory_file_topology, totals only (the floor: nothing per atom leaves the device)
+    stream    ... with the per-atom file (fp64 [F, n]): the stream-out a host-side reduction needs (the reduction itself is not timed)
+    stats     ... with stats=("atoms", "residues") and no per-atom file: mean, std, min, max per atom and per residue column, reduced on
+              the device shard by shard (k_traj_stats), 4 W doubles per shard down
+each line with the bytes of results per frame; the stats arm's per-atom means must be those of the stream arm's file to rounding.
+
 One JSON line per arm: atom-frames/s counted in SOLUTE atoms and in frame atoms, the median and the spread of --reps runs.
 
-    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd] [--netcdf] [--pbc [--pbc-arms all|off] [--triclinic]] [--xtc [--xtc-distinct 24] [--xtc-fpb 0]]
+    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd] [--netcdf] [--pbc [--pbc-arms all|off] [--triclinic]] [--xtc [--xtc-distinct 24] [--xtc-fpb 0]] [--stats]
 
 For the kernel times: `rocprofv3 --kernel-trace --stats -- python tools/traj_topology_bench.py --reps 1 --arms all`
 (k_traj_gather / k_traj_residues / k_traj_class / k_traj_sel are the topology's kernels, k_traj_group_* the groups')."""
@@ -264,6 +272,44 @@ def xtc_mode(args, scratch):
     return lines
 
 
+def stats_mode(args, scratch):
+    """the three arms of --stats -> the JSON lines"""
+    b, xyz = solute()
+    p = lambda k: os.path.join(scratch, k)
+    rng = np.random.default_rng(5)
+    with open(p("solute.f32"), "wb") as fh:
+        for f in range(args.frames):
+            (xyz + rng.uniform(-0.25, 0.25, xyz.shape)).astype(np.float32).tofile(fh)
+    R = b.n_residues
+    arms = {"totals": lambda: fa.trajectory_file_topology(p("solute.f32"), b, p("t0"), f32=True),
+            "stream": lambda: fa.trajectory_file_topology(p("solute.f32"), b, p("t1"), f32=True, sasa_path=p("a1")),
+            "stats": lambda: fa.trajectory_file_topology(p("solute.f32"), b, p("t2"), f32=True, stats=("atoms", "residues"),
+                                                         stats_path=p("s2"), partials_path=p("p2"))}
+    runs = {a: [] for a in arms}
+    for a in arms:
+        arms[a]()                                                        # warm-up: contexts, staging, page cache
+    for _ in range(args.reps):
+        for a in arms:
+            t0 = time.perf_counter()
+            res = arms[a]()
+            runs[a].append(time.perf_counter() - t0)
+            assert res[0] and res[1] == args.frames
+    totals = [np.fromfile(p(k)) for k in ("t0", "t1", "t2")]
+    assert all(np.array_equal(t, totals[0]) for t in totals) and np.all(totals[0] > 0)
+    got = fa.traj_stats_read(p("s2"), ("atoms", "residues"), N_SOLUTE, R)
+    areas = np.memmap(p("a1"), dtype=np.float64, mode="r", shape=(args.frames, N_SOLUTE))
+    assert np.allclose(got["atoms"][0], areas.mean(0), rtol=1e-12, atol=1e-12) and np.array_equal(got["atoms"][3], areas.max(0))
+    out_bytes = {"totals": 8, "stream": 8 + 8 * N_SOLUTE, "stats": 8 + os.path.getsize(p("p2")) / args.frames}
+    lines = []
+    for a in arms:
+        v = sorted(runs[a])
+        med = v[len(v) // 2]
+        lines.append(json.dumps({"arm": a, "frames": args.frames, "frame_atoms": N_SOLUTE, "result_bytes_per_frame": out_bytes[a],
+                                 "median_seconds": med, "min_seconds": v[0], "max_seconds": v[-1],
+                                 "atom_frames_per_s": N_SOLUTE * args.frames / med, "runs": len(v)}))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=240)
@@ -280,11 +326,12 @@ def main():
     ap.add_argument("--xtc", action="store_true", help="time a GROMACS XTC file against the raw fp32 file and an AMBER NetCDF file of the same decoded frames")
     ap.add_argument("--xtc-distinct", type=int, default=24, help="with --xtc: distinct frames that are encoded and then repeated")
     ap.add_argument("--xtc-fpb", type=int, default=0, help="with --xtc: frames_per_batch of all three arms (0: the driver's default)")
+    ap.add_argument("--stats", action="store_true", help="time the run statistics against the per-atom stream-out and against totals only")
     args = ap.parse_args()
     scratch = args.scratch or tempfile.mkdtemp(prefix="traj_topology_bench_")
     try:
-        if args.xtc:
-            lines = xtc_mode(args, scratch)
+        if args.xtc or args.stats:
+            lines = stats_mode(args, scratch) if args.stats else xtc_mode(args, scratch)
             print("\n".join(lines))
             if args.out:
                 with open(args.out, "w") as fh:
