@@ -2,8 +2,8 @@
 #   make            -> freesasa_amd/lib/libfreesasa_amd.so (stand-alone drop-in library)
 #                      freesasa_amd/lib/libfreesasa_amd_seam.a (seam objects for a drop-in
 #                      build of the reference)
-#   make emu        -> tests/emu/libsasa_emu.so, libselect_emu.so, libgroups_emu.so, libtraj_emu.so, libtraj_groups_emu.so, libdcd_emu.so, libnc_emu.so, libxtc_emu.so, libpbc_emu.so, libpbc_tri_emu.so, libstats_emu.so  (TESTS ONLY: the kernel phase
-#                      functions driven on the CPU; never linked into the product) and tests/emu/dcd_check, tests/emu/cell_check, tests/emu/nc_check, tests/emu/xtc_check, tests/emu/xtc_emu_check, tests/emu/stats_check (the DCD, NetCDF and XTC header parsers, the cell arithmetic, the emulated XTC decode and the merge of the run statistics under sanitizers)
+#   make emu        -> tests/emu/libsasa_emu.so, libselect_emu.so, libgroups_emu.so, libtraj_emu.so, libtraj_groups_emu.so, libdcd_emu.so, libnc_emu.so, libxtc_emu.so, libtrr_emu.so, libpbc_emu.so, libpbc_tri_emu.so, libstats_emu.so  (TESTS ONLY: the kernel phase
+#                      functions driven on the CPU; never linked into the product) and tests/emu/dcd_check, tests/emu/cell_check, tests/emu/nc_check, tests/emu/xtc_check, tests/emu/xtc_emu_check, tests/emu/trr_check, tests/emu/stats_check (the DCD, NetCDF, XTC and TRR header parsers, the cell arithmetic, the emulated XTC decode and the merge of the run statistics under sanitizers)
 #   make oracle     -> oracle/ (TESTS ONLY) ; make tools -> tools/libsasa_synth.so
 HIPCC   ?= /opt/rocm/bin/hipcc
 CC      ?= gcc
@@ -49,6 +49,10 @@ $(LIBDIR)/xtc.o: $(CSRC)/xtc.c include/freesasa_gpu.h
 	@mkdir -p $(LIBDIR)
 	$(CC) $(CFLAGS) -c $< -o $@
 
+$(LIBDIR)/trr.o: $(CSRC)/trr.c include/freesasa_gpu.h
+	@mkdir -p $(LIBDIR)
+	$(CC) $(CFLAGS) -c $< -o $@
+
 $(LIBDIR)/cell.o: $(CSRC)/cell.c include/freesasa_gpu.h
 	@mkdir -p $(LIBDIR)
 	$(CC) $(CFLAGS) -c $< -o $@
@@ -87,13 +91,13 @@ $(LIBDIR)/ingest_cache.o: $(CSRC)/ingest_cache.c include/freesasa_ingest.h $(CSR
 	@mkdir -p $(LIBDIR)
 	$(CC) $(CFLAGS) -Iinclude -pthread -c $< -o $@
 
-$(LIBDIR)/libfreesasa_amd.so: $(GPU_OBJS) $(LIBDIR)/seam.o $(LIBDIR)/testpoints.o $(LIBDIR)/dcd.o $(LIBDIR)/netcdf.o $(LIBDIR)/xtc.o $(LIBDIR)/cell.o $(LIBDIR)/trajstats.o $(LIBDIR)/api.o $(LIBDIR)/ingest.o $(LIBDIR)/classifier.o $(LIBDIR)/select.o $(LIBDIR)/ingest_cache.o $(LIBDIR)/hostfault.o $(LIBDIR)/hostfault_new.o $(CSRC)/exports.map
+$(LIBDIR)/libfreesasa_amd.so: $(GPU_OBJS) $(LIBDIR)/seam.o $(LIBDIR)/testpoints.o $(LIBDIR)/dcd.o $(LIBDIR)/netcdf.o $(LIBDIR)/xtc.o $(LIBDIR)/trr.o $(LIBDIR)/cell.o $(LIBDIR)/trajstats.o $(LIBDIR)/api.o $(LIBDIR)/ingest.o $(LIBDIR)/classifier.o $(LIBDIR)/select.o $(LIBDIR)/ingest_cache.o $(LIBDIR)/hostfault.o $(LIBDIR)/hostfault_new.o $(CSRC)/exports.map
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--version-script=$(CSRC)/exports.map -o $@ $(filter %.o,$^)
 
-$(LIBDIR)/libfreesasa_amd_seam.a: $(GPU_OBJS) $(LIBDIR)/seam.o $(LIBDIR)/testpoints.o $(LIBDIR)/dcd.o $(LIBDIR)/netcdf.o $(LIBDIR)/xtc.o $(LIBDIR)/cell.o $(LIBDIR)/trajstats.o $(LIBDIR)/ingest.o $(LIBDIR)/classifier.o $(LIBDIR)/select.o $(LIBDIR)/ingest_cache.o $(LIBDIR)/hostfault.o
+$(LIBDIR)/libfreesasa_amd_seam.a: $(GPU_OBJS) $(LIBDIR)/seam.o $(LIBDIR)/testpoints.o $(LIBDIR)/dcd.o $(LIBDIR)/netcdf.o $(LIBDIR)/xtc.o $(LIBDIR)/trr.o $(LIBDIR)/cell.o $(LIBDIR)/trajstats.o $(LIBDIR)/ingest.o $(LIBDIR)/classifier.o $(LIBDIR)/select.o $(LIBDIR)/ingest_cache.o $(LIBDIR)/hostfault.o
 	rm -f $@; ar rcs $@ $^
 
-emu: tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so tests/emu/libtraj_groups_emu.so tests/emu/libdcd_emu.so tests/emu/libpbc_emu.so tests/emu/libpbc_tri_emu.so tests/emu/libnc_emu.so tests/emu/libxtc_emu.so tests/emu/libstats_emu.so tests/emu/dcd_check tests/emu/cell_check tests/emu/nc_check tests/emu/xtc_check tests/emu/xtc_emu_check tests/emu/stats_check
+emu: tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so tests/emu/libtraj_groups_emu.so tests/emu/libdcd_emu.so tests/emu/libpbc_emu.so tests/emu/libpbc_tri_emu.so tests/emu/libnc_emu.so tests/emu/libxtc_emu.so tests/emu/libtrr_emu.so tests/emu/libstats_emu.so tests/emu/dcd_check tests/emu/cell_check tests/emu/nc_check tests/emu/xtc_check tests/emu/xtc_emu_check tests/emu/trr_check tests/emu/stats_check
 # the loader with its byte-at-a-time mmCIF tokenizer only: the differential twin of the SSE2 row scanner
 tests/emu/libingest_scalar.so: $(CSRC)/ingest.c $(CSRC)/classifier.c $(CSRC)/classifier.h $(CSRC)/hostfault.c $(CSRC)/hostfault.h $(CSRC)/protor_table.h include/freesasa_ingest.h
 	$(CC) $(CFLAGS) -DFREESASA_INGEST_NO_SIMD -Iinclude -pthread -shared -o $@ $(CSRC)/ingest.c $(CSRC)/classifier.c $(CSRC)/hostfault.c -lm
@@ -119,6 +123,11 @@ tests/emu/libnc_emu.so: tests/emu/emu_nc.cpp $(CSRC)/traj_kernels.h $(CSRC)/sele
 tests/emu/libxtc_emu.so: tests/emu/emu_xtc.cpp $(CSRC)/xtc.c $(CSRC)/xtc_kernels.h $(CSRC)/sasa_kernels.h include/freesasa_gpu.h
 	$(CC) $(CFLAGS) -c $(CSRC)/xtc.c -o tests/emu/xtc_emu.o
 	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -DSASA_EMU -shared -o $@ tests/emu/emu_xtc.cpp tests/emu/xtc_emu.o -lm
+# TRR input (traj_kernels.h, traj_gather_trr): the bytes of a file's records -> compact fp64 frames; x_off through trr.c, as the
+# driver makes it
+tests/emu/libtrr_emu.so: tests/emu/emu_trr.cpp $(CSRC)/trr.c $(CSRC)/traj_kernels.h $(CSRC)/select_kernels.h $(CSRC)/select_program.h $(CSRC)/sasa_kernels.h include/freesasa_gpu.h include/freesasa_ingest.h
+	$(CC) $(CFLAGS) -c $(CSRC)/trr.c -o tests/emu/trr_emu.o
+	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -DSASA_EMU -Iinclude -shared -o $@ tests/emu/emu_trr.cpp tests/emu/trr_emu.o -lm
 # periodic images (pbc_kernels.h): count, emit and collect, the 256 threads of a workgroup as fibers in lock step
 tests/emu/libpbc_emu.so: tests/emu/emu_pbc.cpp $(CSRC)/pbc_kernels.h $(CSRC)/lr2_kernels.h $(CSRC)/sasa_kernels.h $(CSRC)/sr_caps.h
 	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -DSASA_EMU -shared -o $@ tests/emu/emu_pbc.cpp -lm
@@ -143,6 +152,9 @@ tests/emu/nc_check: tests/emu/nc_check.c $(CSRC)/netcdf.c $(CSRC)/cell.c include
 # the XTC header walker (xtc.c) likewise: one line per file of argv
 tests/emu/xtc_check: tests/emu/xtc_check.c $(CSRC)/xtc.c include/freesasa_gpu.h
 	$(CC) -O1 -g -std=gnu99 -Wall -ffp-contract=off -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -o $@ tests/emu/xtc_check.c $(CSRC)/xtc.c -lm
+# the TRR header walker (trr.c) likewise: one line per file of argv
+tests/emu/trr_check: tests/emu/trr_check.c $(CSRC)/trr.c include/freesasa_gpu.h
+	$(CC) -O1 -g -std=gnu99 -Wall -ffp-contract=off -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -o $@ tests/emu/trr_check.c $(CSRC)/trr.c -lm
 # ... and the emulated XTC decode kernels behind it (emu_xtc.cpp with its main): one line per frame of the files of argv
 tests/emu/xtc_emu_check: tests/emu/emu_xtc.cpp $(CSRC)/xtc.c $(CSRC)/xtc_kernels.h $(CSRC)/sasa_kernels.h include/freesasa_gpu.h
 	$(CC) -O1 -g -std=gnu99 -Wall -ffp-contract=off -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -c $(CSRC)/xtc.c -o tests/emu/xtc_san.o
@@ -164,9 +176,9 @@ tests/emu/libgroups_emu.so: tests/emu/emu_groups.cpp $(CSRC)/group_kernels.h $(C
 ASAN_SO = tests/emu/libfreesasa_amd_asan.so
 SANFLAGS = -O1 -g -std=gnu99 -fPIC -ffp-contract=off -Wall -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined
 asan: $(ASAN_SO)
-$(ASAN_SO): $(CSRC)/api.c $(CSRC)/seam.c $(CSRC)/testpoints.c $(CSRC)/dcd.c $(CSRC)/netcdf.c $(CSRC)/xtc.c $(CSRC)/cell.c $(CSRC)/trajstats.c $(CSRC)/ingest.c $(CSRC)/classifier.c $(CSRC)/classifier.h $(CSRC)/select.c $(CSRC)/ingest_cache.c $(CSRC)/hostfault.c $(CSRC)/hostfault.h $(CSRC)/protor_table.h $(GPU_OBJS) include/freesasa_amd.h include/freesasa_gpu.h include/freesasa_ingest.h
-	for f in api seam testpoints dcd netcdf xtc cell trajstats ingest classifier select ingest_cache hostfault; do $(CC) $(SANFLAGS) -Iinclude -pthread -c $(CSRC)/$$f.c -o tests/emu/asan_$$f.o || exit 1; done
-	$(CXX) -shared -fPIC -o $@ $(foreach f,api seam testpoints dcd netcdf xtc cell trajstats ingest classifier select ingest_cache hostfault,tests/emu/asan_$(f).o) $(GPU_OBJS) \
+$(ASAN_SO): $(CSRC)/api.c $(CSRC)/seam.c $(CSRC)/testpoints.c $(CSRC)/dcd.c $(CSRC)/netcdf.c $(CSRC)/xtc.c $(CSRC)/trr.c $(CSRC)/cell.c $(CSRC)/trajstats.c $(CSRC)/ingest.c $(CSRC)/classifier.c $(CSRC)/classifier.h $(CSRC)/select.c $(CSRC)/ingest_cache.c $(CSRC)/hostfault.c $(CSRC)/hostfault.h $(CSRC)/protor_table.h $(GPU_OBJS) include/freesasa_amd.h include/freesasa_gpu.h include/freesasa_ingest.h
+	for f in api seam testpoints dcd netcdf xtc trr cell trajstats ingest classifier select ingest_cache hostfault; do $(CC) $(SANFLAGS) -Iinclude -pthread -c $(CSRC)/$$f.c -o tests/emu/asan_$$f.o || exit 1; done
+	$(CXX) -shared -fPIC -o $@ $(foreach f,api seam testpoints dcd netcdf xtc trr cell trajstats ingest classifier select ingest_cache hostfault,tests/emu/asan_$(f).o) $(GPU_OBJS) \
 	    -fsanitize=address,undefined -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib -lamdhip64 -lpthread -lm
 asan-test: $(ASAN_SO)
 	LD_PRELOAD="$$($(CC) -print-file-name=libasan.so) $$($(CC) -print-file-name=libubsan.so)" ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 \
@@ -180,7 +192,7 @@ tools:
 	$(MAKE) -C tools
 
 clean:
-	rm -rf $(LIBDIR) tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so tests/emu/libtraj_groups_emu.so tests/emu/libdcd_emu.so tests/emu/libpbc_emu.so tests/emu/libpbc_tri_emu.so tests/emu/libnc_emu.so tests/emu/libxtc_emu.so tests/emu/dcd_check tests/emu/cell_check tests/emu/nc_check tests/emu/xtc_check tests/emu/xtc_emu_check tests/emu/xtc_*.o tests/emu/libstats_emu.so tests/emu/stats_check
+	rm -rf $(LIBDIR) tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so tests/emu/libtraj_groups_emu.so tests/emu/libdcd_emu.so tests/emu/libpbc_emu.so tests/emu/libpbc_tri_emu.so tests/emu/libnc_emu.so tests/emu/libxtc_emu.so tests/emu/dcd_check tests/emu/cell_check tests/emu/nc_check tests/emu/xtc_check tests/emu/xtc_emu_check tests/emu/xtc_*.o tests/emu/libtrr_emu.so tests/emu/trr_check tests/emu/trr_*.o tests/emu/libstats_emu.so tests/emu/stats_check
 	$(MAKE) -C oracle clean
 	$(MAKE) -C tools clean
 .PHONY: all emu oracle tools clean asan asan-test

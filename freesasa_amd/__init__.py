@@ -842,7 +842,7 @@ def _trajectory_stats(xyz_frames, radii, alg, probe, resolution, frames_per_batc
     return totals, sasa, RunStats(raw, word, n_atoms, partials=parts, frames=nf)
 
 
-FRAMES_F32, FRAMES_OUT_F32, FRAMES_DCD, FRAMES_PBC, FRAMES_TRICLINIC, FRAMES_NETCDF, FRAMES_XTC = 1, 2, 4, 8, 16, 32, 64   # the bits of frames_f32 (include/freesasa_gpu.h)
+FRAMES_F32, FRAMES_OUT_F32, FRAMES_DCD, FRAMES_PBC, FRAMES_TRICLINIC, FRAMES_NETCDF, FRAMES_XTC, FRAMES_TRR = 1, 2, 4, 8, 16, 32, 64, 128   # the bits of frames_f32 (include/freesasa_gpu.h)
 
 
 class DcdInfoC(C.Structure):
@@ -940,21 +940,57 @@ def xtc_info(path):
     return XtcInfo(c)
 
 
-def _frames_bits(f32, out_f32, dcd, header_bytes, pbc=False, triclinic=False, netcdf=False, xtc=False):
+class TrrInfoC(C.Structure):
+    _fields_ = [("n_atoms", C.c_int32), ("n_frames", C.c_int64), ("n_records", C.c_int64), ("max_frame_bytes", C.c_int64),
+                ("real_bytes", C.c_int32), ("has_box", C.c_int32), ("has_velocities", C.c_int32), ("has_forces", C.c_int32)]
+
+
+class TrrInfo:
+    """What trr_info() returns: the fields of freesasa_gpu_trr_info (include/freesasa_gpu.h) - n_atoms, n_frames (the records
+    WITH coordinates, by one pass over the records' headers), n_records (all records), max_frame_bytes (the longest stretch from
+    one frame's first byte to the next frame's), real_bytes (4: single, 8: double precision) and the flags has_box (the first
+    frame has a box with a non-zero element), has_velocities, has_forces (some record has them) as bools."""
+
+    def __init__(self, c):
+        for name, _ in TrrInfoC._fields_:
+            v = int(getattr(c, name))
+            setattr(self, name, bool(v) if name.startswith("has_") else v)
+
+    def __repr__(self):
+        return "TrrInfo(" + ", ".join(f"{name}={getattr(self, name)}" for name, _ in TrrInfoC._fields_) + ")"
+
+
+def trr_info(path):
+    """freesasa_gpu_trr_info_read(): one pass over the headers of a GROMACS TRR trajectory -> TrrInfo; ValueError with the
+    library's message, which names the record, for a file that is no TRR file, is damaged, or is one the drivers do not read
+    (records that change atom count or precision, no record with coordinates)."""
+    L = lib()
+    L.freesasa_gpu_trr_info_read.argtypes = [C.c_char_p, C.POINTER(TrrInfoC), C.c_char_p, C.c_int]
+    c = TrrInfoC()
+    err = C.create_string_buffer(512)
+    if L.freesasa_gpu_trr_info_read(str(path).encode(), C.byref(c), err, 512):
+        raise ValueError("freesasa_gpu_trr_info_read: " + err.value.decode())
+    return TrrInfo(c)
+
+
+def _frames_bits(f32, out_f32, dcd, header_bytes, pbc=False, triclinic=False, netcdf=False, xtc=False, trr=False):
     if dcd and (f32 or header_bytes):
         raise ValueError("dcd=True excludes f32=True and a non-zero header_bytes: a DCD file says for itself where its frames are")
     if netcdf and (dcd or f32 or header_bytes):
         raise ValueError("netcdf=True excludes dcd=True, f32=True and a non-zero header_bytes: an AMBER NetCDF file says for itself where its frames are")
     if xtc and (dcd or netcdf or f32 or header_bytes):
         raise ValueError("xtc=True excludes dcd=True, netcdf=True, f32=True and a non-zero header_bytes: an XTC file's frames are found by their headers")
+    if trr and (dcd or netcdf or xtc or f32 or header_bytes):
+        raise ValueError("trr=True excludes dcd=True, netcdf=True, xtc=True, f32=True and a non-zero header_bytes: a TRR file's frames are found by "
+                         "their headers, which say their precision")
     return (FRAMES_F32 if f32 else 0) | (FRAMES_OUT_F32 if out_f32 else 0) | (FRAMES_DCD if dcd else 0) | (FRAMES_PBC if pbc else 0) | \
-        (FRAMES_TRICLINIC if triclinic else 0) | (FRAMES_NETCDF if netcdf else 0) | (FRAMES_XTC if xtc else 0)
+        (FRAMES_TRICLINIC if triclinic else 0) | (FRAMES_NETCDF if netcdf else 0) | (FRAMES_XTC if xtc else 0) | (FRAMES_TRR if trr else 0)
 
 
 def trajectory_file(frames_path, radii, totals_path, sasa_path=None, done_path=None, f32=False, header_bytes=0,
                     n_frames=0, alg=LEE_RICHARDS, probe=1.4, resolution=20, frames_per_batch=0, max_new_shards=0, device=-1,
                     devices=None, out_f32=False, dcd=False, pbc=False, triclinic=False, netcdf=False, xtc=False,
-                    stats=None, stats_path=None, partials_path=None):
+                    stats=None, stats_path=None, partials_path=None, trr=False):
     """freesasa_gpu_trajectory_file(): raw frame file -> totals file (+ per-atom file), resumable through the
     done-list at done_path.  Returns (complete, n_frames): complete is False when max_new_shards stopped the run.
     f32: the frames are floats (an input format); out_f32: the per-atom file holds floats (an output format);
@@ -965,11 +1001,14 @@ def trajectory_file(frames_path, radii, totals_path, sasa_path=None, done_path=N
     it); pbc and triclinic go with it as with dcd: the cell is the frame's cell_lengths and cell_angles (cell_from_lengths_angles);
     xtc: frames_path is a GROMACS XTC trajectory whose atom count is len(radii) (no dcd, no netcdf, no f32, no header_bytes with
     it), decoded on the device; pbc and triclinic go with it as with dcd: the cell is the frame's box, nm * 10.
+    trr: frames_path is a GROMACS TRR trajectory, single or double precision, whose atom count is len(radii) (no dcd, no netcdf,
+    no xtc, no f32, no header_bytes with it); records without coordinates are no frames of the run; results are those of a raw
+    fp64 file of float64(x_nm) * 10; pbc and triclinic go with it as with xtc.
     stats=("totals", "atoms") with stats_path and partials_path: freesasa_gpu_trajectory_file_stats() - the run statistics of those
     outputs; the shards' partials go to partials_path as they finish, the call that finds the run complete writes stats_path
     (traj_stats_read reads it).  With out_f32 the statistics are still those of the fp64 areas."""
     radii = _f64(radii)
-    f32 = _frames_bits(f32, out_f32, dcd, header_bytes, pbc, triclinic, netcdf, xtc)
+    f32 = _frames_bits(f32, out_f32, dcd, header_bytes, pbc, triclinic, netcdf, xtc, trr)
     err = C.create_string_buffer(512)
     total = C.c_longlong(0)
     enc = lambda p: None if p is None else str(p).encode()
@@ -1169,7 +1208,7 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
                              f32=False, header_bytes=0, n_frames=0, alg=LEE_RICHARDS, probe=1.4, resolution=20, frames_per_batch=0,
                              max_new_shards=0, device=-1, devices=None, out_f32=False, chain_groups=None, separate_chains=False,
                              long=False, group=None, n_groups=None, group_areas_path=None, isolated_path=None, dcd=False, pbc=False,
-                             triclinic=False, netcdf=False, xtc=False, stats=None, stats_path=None, partials_path=None):
+                             triclinic=False, netcdf=False, xtc=False, stats=None, stats_path=None, partials_path=None, trr=False):
     """freesasa_gpu_trajectory_file_topology(): trajectory_file() with a topology (see trajectory_topology; frame_atoms:
     atoms per frame of the file, None: the structure's) and one raw fp64 result file per output asked for: class sums
     [F, 3], residues [F, R, 6], selection areas [F, S].  Returns (complete, n_frames, selection_atoms [S] or None).
@@ -1180,16 +1219,19 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
     triclinic: (with dcd and pbc) the cell records decoded as triclinic cells, see trajectory_file;
     netcdf: frames_path is an AMBER NetCDF trajectory; frame_atoms None is then the file's atom count; pbc and triclinic as with dcd;
     xtc: frames_path is a GROMACS XTC trajectory; frame_atoms None is then the file's atom count; pbc and triclinic as with dcd.
+    trr: frames_path is a GROMACS TRR trajectory; frame_atoms None is then the file's atom count; pbc and triclinic as with dcd.
     stats=("atoms", "residues", ...) with stats_path and partials_path (freesasa_gpu_trajectory_file_groups_stats): the run statistics of
     those outputs, as trajectory_file describes them; an output named there needs no result file of its own."""
     L = _stats_proto(_topology_proto(lib()))
-    bits = _frames_bits(f32, out_f32, dcd, header_bytes, pbc, triclinic, netcdf, xtc)
+    bits = _frames_bits(f32, out_f32, dcd, header_bytes, pbc, triclinic, netcdf, xtc, trr)
     if dcd and frame_atoms is None:
         frame_atoms = dcd_info(frames_path).n_atoms
     if netcdf and frame_atoms is None:
         frame_atoms = nc_info(frames_path).n_atoms
     if xtc and frame_atoms is None:
         frame_atoms = xtc_info(frames_path).n_atoms
+    if trr and frame_atoms is None:
+        frame_atoms = trr_info(frames_path).n_atoms
     n, R, res_ref, idx, fa_ = _topology_args(batch, structure, atom_index, frame_atoms)
     S = len(selection) if selection is not None else 0
     sel_atoms = np.zeros(S, dtype=np.int64) if selection is not None else None

@@ -100,6 +100,7 @@ hipError_t kl_traj_gather(const sasa::TrajArgs &a, const void *d_in, bool in_f32
 hipError_t kl_traj_gather_dcd(const sasa::TrajDcdArgs &a, const void *d_in, bool big_endian, double *d_out, hipStream_t st);
 /* ... and from the bytes of AMBER NetCDF records (big-endian fp32, atom by atom, at a record stride) */
 hipError_t kl_traj_gather_nc(const sasa::TrajNcArgs &a, const void *d_in, double *d_out, hipStream_t st);
+hipError_t kl_traj_gather_trr(const sasa::TrajTrrArgs &a, const void *d_in, bool is_double, double *d_out, hipStream_t st);
 /* XTC input (xtc_kernels.h): one wavefront per frame walks the stream's groups; one thread per group unpacks them into raw fp32 frames */
 hipError_t kl_xtc_scan(const sasa::XtcArgs &a, hipStream_t st);
 hipError_t kl_xtc_unpack(const sasa::XtcArgs &a, hipStream_t st);

@@ -166,6 +166,9 @@ struct TrajIO {
     bool in_xtc = false;            /* the file is a GROMACS XTC trajectory: compressed frames of unequal length, decoded on the device ... */
     freesasa_gpu_xtc_info xtc = {}; /* ... what the pass over its headers found (xtc.c) ... */
     std::vector<int64_t> xtc_off;   /* ... and its index: the byte of every frame [n_frames + 1], by which the shards are cut */
+    bool in_trr = false;            /* the file is a GROMACS TRR trajectory: uncompressed records of unequal length, fp32 or fp64 ... */
+    freesasa_gpu_trr_info trr = {}; /* ... what the pass over its headers found (trr.c) ... */
+    std::vector<int64_t> trr_off;   /* ... and its index: the byte of every record WITH coordinates [n_frames + 1] */
     bool pbc = false;               /* FREESASA_GPU_FRAMES_PBC: every frame among the images its cell record implies (gpu_periodic.hip) */
     bool tri = false;               /* ... FREESASA_GPU_FRAMES_TRICLINIC beside it: the record decoded as a triclinic cell */
     /* per frame: total [1], per-atom areas [n]; runs with a topology: class sums [3], residue areas [6 R], selection areas [S];
@@ -411,8 +414,11 @@ struct TrajRun {
     const size_t widen_bytes = f32 && !gather ? 12 * n * FB : 0; /* (fp32 frames without an index: kl_widen_f32's input) */
     /* bytes from one input frame to the next: raw frames, or a DCD / NetCDF file's stride (kl_traj_gather_dcd / _nc then does
        the gather's and the widening's work, with or without an index) */
-    const bool dcd = io.in_dcd, netcdf = io.in_nc, container = dcd || netcdf;
+    const bool dcd = io.in_dcd, netcdf = io.in_nc, trr = io.in_trr, container = dcd || netcdf || trr;
     const size_t stride = dcd ? (size_t)io.dcd.frame_bytes : netcdf ? (size_t)io.nc.record_bytes : esz * fa;
+    /* (an XTC and a TRR file have no stride: their shards are cut by the index of the file) */
+    const bool indexed = xtc || trr;
+    const std::vector<int64_t> &idx = trr ? io.trr_off : io.xtc_off;
     /* periodic images: a shard's [nf][3] cell edges ride behind its bytes (at the next multiple of 8); every edge must reach
        the system's c = 2 (max radius + probe) */
     const bool pbc = io.pbc;
@@ -427,10 +433,16 @@ struct TrajRun {
     size_t xtc_count_at(size_t in_bytes, size_t nf) const { return xtc_desc_at(in_bytes, nf) + sizeof(freesasa_gpu_xtc_frame) * nf; }
     size_t xtc_rec_at(size_t in_bytes, size_t nf) const { return (xtc_count_at(in_bytes, nf) + 8 * nf + 15) & ~(size_t)15; }
     size_t xtc_f32_at(size_t in_bytes, size_t nf) const { return xtc_rec_at(in_bytes, nf) + sizeof(sasa::XtcRec) * fa * nf; }
-    size_t xtc_max_bytes = 0; /* the bytes of the index's largest shard */
-    size_t shard_bytes(long long f0, long long nf) const { return xtc ? (size_t)(io.xtc_off[(size_t)(f0 + nf)] - io.xtc_off[(size_t)f0]) : stride * (size_t)nf; }
+    /* A TRR shard on the device (c->g_xyz): its bytes | its cells (periodic runs) | the byte of every frame's x[0] within the shard,
+       one int64 per frame - all of it the one copy from the host */
+    size_t trr_xoff_at(size_t in_bytes, size_t nf) const { return xtc_desc_at(in_bytes, nf); }
+    size_t idx_max_bytes = 0; /* the bytes of the index's largest shard */
+    size_t shard_bytes(long long f0, long long nf) const { return indexed ? (size_t)(idx[(size_t)(f0 + nf)] - idx[(size_t)f0]) : stride * (size_t)nf; }
     /* what goes up in a shard's one copy */
-    size_t up_bytes(size_t in_bytes, size_t nf) const { return xtc ? xtc_count_at(in_bytes, nf) : pbc ? cells_at(in_bytes) + cell_bytes * nf : in_bytes; }
+    size_t up_bytes(size_t in_bytes, size_t nf) const
+    {
+        return xtc ? xtc_count_at(in_bytes, nf) : trr ? trr_xoff_at(in_bytes, nf) + 8 * nf : pbc ? cells_at(in_bytes) + cell_bytes * nf : in_bytes;
+    }
     /* the caller's arrays are page-locked: no staging */
     const bool in_pinned = io.mem_in && host_pinned(io.mem_in);
     const bool direct_out = io.out[OUT_TOTALS].mem && host_pinned(io.out[OUT_TOTALS].mem) && (!io.out[OUT_SASA].mem || host_pinned(io.out[OUT_SASA].mem)) &&
@@ -475,9 +487,9 @@ struct TrajRun {
             if (k >= OUT_CLS) x0[k + 1] = x0[k] + io.out[k].per_frame;
         }
         xw = x0[N_OUT] + S;
-        for (long long k = 0; xtc && k < n_shards; ++k) {
+        for (long long k = 0; indexed && k < n_shards; ++k) {
             const long long f0 = k * s.frames_per_batch, nf = s.n_frames - f0 < s.frames_per_batch ? s.n_frames - f0 : s.frames_per_batch;
-            if (shard_bytes(f0, nf) > xtc_max_bytes) xtc_max_bytes = shard_bytes(f0, nf);
+            if (shard_bytes(f0, nf) > idx_max_bytes) idx_max_bytes = shard_bytes(f0, nf);
         }
     }
 };
@@ -511,7 +523,8 @@ int shard_size(TrajRun &T, TrajLane &L)
     if (ensure(c, c->h_xyz, 24 * nc * FB) || ensure(c, c->h_radii, T.groups ? 8 * nc * FB : 8 * n) || ensure(c, c->h_sasa, 8 * nc * FB) ||
         ensure(c, c->h_totals, 8 * (1 + T.G) * FB) ||
         (T.widen_bytes + narrow_bytes && ensure(c, c->h_counts, T.widen_bytes + narrow_bytes)) ||
-        ((T.gather || T.container || T.xtc) && ensure(c, c->g_xyz, T.xtc ? T.xtc_f32_at(T.xtc_max_bytes, FB) + (T.gather ? 12 * T.fa * FB : 0)
+        ((T.gather || T.container || T.xtc) && ensure(c, c->g_xyz, T.xtc ? T.xtc_f32_at(T.idx_max_bytes, FB) + (T.gather ? 12 * T.fa * FB : 0)
+                                                                        : T.trr ? T.up_bytes(T.idx_max_bytes, FB)
                                                                         : T.pbc ? TrajRun::cells_at(T.stride * FB) + T.cell_bytes * FB : T.stride * FB)) || (T.xw + T.sW && ensure(c, c->h_gtot, 8 * (T.xw * FB + 4 * T.sW))) ||
         (T.groups && (ensure(c, c->g_gath, 8 * nc * FB) || ensure(c, c->g_tot2, 8 * (1 + T.G) * FB))) || (iso && ensure(c, c->h_iso, 8 * n * FB)))
         return -1;
@@ -657,49 +670,95 @@ long long xtc_descriptors(const TrajIO &io, const char *bytes, long long f0, lon
     return -1;
 }
 
-/* The cells of the same frames: a frame's box is nine floats in nm, GROMACS' lower triangle - rows a = (ax, 0, 0), b = (bx, by, 0),
-   c = (cx, cy, cz) -, each element (double) float * 10.0.  Orthorhombic runs: the edges into cells[nf][3]; triclinic runs:
-   cells[nf][9] as dcd_cells_tri fills it, through tri_cell_bad.  Returns -1, or the first frame whose box periodic images are not
-   offered for, the reason in why. */
+/* The cell of ONE frame from its box, for XTC and TRR frames alike: nine numbers in nm as doubles - each what the file holds,
+   widened -, GROMACS' lower triangle - rows a = (ax, 0, 0), b = (bx, by, 0), c = (cx, cy, cz) -, each element b * 10.0.
+   Orthorhombic runs: the edges into cell[3]; triclinic runs: cell[9] as dcd_cells_tri fills it, through tri_cell_bad.  false, or
+   true with the reason periodic images are not offered for this box in why. */
+static bool box_cell_bad(const double b[9], bool tri, double cut, double *cell, char *why, size_t why_len)
+{
+    bool zero = true;
+    for (int k = 0; k < 9; ++k) zero = zero && b[k] == 0.0;
+    if (zero) { snprintf(why, why_len, "its box is all zero: the frame carries no cell"); return true; }
+    const int upper[3] = {1, 2, 5}, lower[3] = {3, 6, 7};
+    for (int k = 0; k < 3; ++k)
+        if (b[upper[k]] != 0.0) {
+            snprintf(why, why_len, "element [%d][%d] of its box is %.9g: a box must be lower-triangular", upper[k] / 3, upper[k] % 3, b[upper[k]]);
+            return true;
+        }
+    const double len[3] = {b[0] * 10.0, b[4] * 10.0, b[8] * 10.0};
+    if (!tri) {
+        for (int k = 0; k < 3; ++k)
+            if (b[lower[k]] != 0.0) {
+                snprintf(why, why_len, "its cell is not orthorhombic (element [%d][%d] of its box is %.9g): triclinic cells need bit 4", lower[k] / 3, lower[k] % 3, b[lower[k]]);
+                return true;
+            }
+        for (int k = 0; k < 3; ++k) {
+            if (!isfinite(len[k])) { snprintf(why, why_len, "edge %c of its cell is not finite", "xyz"[k]); return true; }
+            if (!(len[k] >= cut)) {
+                snprintf(why, why_len, "edge %c of its cell is %.9g, shorter than c = 2 (max radius + probe) = %.9g", "xyz"[k], len[k], cut);
+                return true;
+            }
+            cell[k] = len[k];
+        }
+        return false;
+    }
+    const int at[6] = {0, 3, 4, 6, 7, 8};
+    for (int k = 0; k < 6; ++k) {
+        cell[k] = b[at[k]] * 10.0;
+        if (!isfinite(cell[k])) { snprintf(why, why_len, "element [%d][%d] of its box is not finite", at[k] / 3, at[k] % 3); return true; }
+    }
+    return tri_cell_bad(cell, len, cut, why, why_len);
+}
+
+/* The cells of the same frames: a frame's box is nine floats in nm (box_cell_bad).  cells[nf][3], or [nf][9] in a triclinic run.
+   Returns -1, or the first frame whose box periodic images are not offered for, the reason in why. */
 long long xtc_cells(const TrajIO &io, const char *bytes, long long f0, long long nf, bool tri, double cut, double *cells, char *why, size_t why_len)
 {
     const int64_t *off = io.xtc_off.data() + f0;
     for (long long f = 0; f < nf; ++f) {
         float b[9];
+        double bd[9];
         freesasa_gpu_xtc_frame_box(bytes + (off[f] - off[0]), b);
-        bool zero = true;
-        for (int k = 0; k < 9; ++k) zero = zero && b[k] == 0.0f;
-        if (zero) { snprintf(why, why_len, "its box is all zero: the frame carries no cell"); return f; }
-        const int upper[3] = {1, 2, 5}, lower[3] = {3, 6, 7};
-        for (int k = 0; k < 3; ++k)
-            if (b[upper[k]] != 0.0f) {
-                snprintf(why, why_len, "element [%d][%d] of its box is %.9g: a box must be lower-triangular", upper[k] / 3, upper[k] % 3, (double)b[upper[k]]);
-                return f;
-            }
-        const double len[3] = {(double)b[0] * 10.0, (double)b[4] * 10.0, (double)b[8] * 10.0};
-        if (!tri) {
-            for (int k = 0; k < 3; ++k)
-                if (b[lower[k]] != 0.0f) {
-                    snprintf(why, why_len, "its cell is not orthorhombic (element [%d][%d] of its box is %.9g): triclinic cells need bit 4", lower[k] / 3, lower[k] % 3, (double)b[lower[k]]);
-                    return f;
-                }
-            for (int k = 0; k < 3; ++k) {
-                if (!isfinite(len[k])) { snprintf(why, why_len, "edge %c of its cell is not finite", "xyz"[k]); return f; }
-                if (!(len[k] >= cut)) {
-                    snprintf(why, why_len, "edge %c of its cell is %.9g, shorter than c = 2 (max radius + probe) = %.9g", "xyz"[k], len[k], cut);
-                    return f;
-                }
-                cells[3 * f + k] = len[k];
-            }
-            continue;
+        for (int k = 0; k < 9; ++k) bd[k] = (double)b[k];
+        if (box_cell_bad(bd, tri, cut, cells + (tri ? PBC_TRI_CELL : 3) * f, why, why_len)) return f;
+    }
+    return -1;
+}
+
+/* The frames [f0, f0 + nf) of a TRR file at `bytes` (trr.c): EVERY header of the shard checked again as it lies in the staging -
+   the device trusts x_off for its bounds - and against the index: a frame's stretch begins with a record that holds coordinates,
+   the records behind it hold none, and they end where the index says the next frame begins.  x_off[nf]: the byte of every
+   frame's x[0] within the shard.  Returns -1, or the first frame that fails, the reason in why. */
+long long trr_descriptors(const TrajIO &io, const char *bytes, long long f0, long long nf, int frame_atoms, int64_t *x_off, char *why, size_t why_len)
+{
+    const int64_t *off = io.trr_off.data() + f0;
+    for (long long f = 0; f < nf; ++f) {
+        long long at = off[f] - off[0];
+        const long long end = off[f + 1] - off[0];
+        for (bool first = true; at < end; first = false) {
+            freesasa_gpu_trr_record r;
+            if (freesasa_gpu_trr_frame_desc(bytes + at, end - at, frame_atoms, io.trr.real_bytes, at, &r, why, (int)why_len)) return f;
+            if (first != (r.has_x != 0)) { snprintf(why, why_len, "its headers are not the ones the index was made from"); return f; }
+            if (first) x_off[f] = r.x_off;
+            at += r.record_bytes; /* (<= end: the record lies within what is left) */
         }
-        double *h = cells + PBC_TRI_CELL * f;
-        const int at[6] = {0, 3, 4, 6, 7, 8};
-        for (int k = 0; k < 6; ++k) {
-            h[k] = (double)b[at[k]] * 10.0;
-            if (!isfinite(h[k])) { snprintf(why, why_len, "element [%d][%d] of its box is not finite", at[k] / 3, at[k] % 3); return f; }
-        }
-        if (tri_cell_bad(h, len, cut, why, why_len)) return f;
+    }
+    return -1;
+}
+
+/* The cells of the same frames, their headers checked: a frame's box is nine reals in nm (box_cell_bad); a frame without a box
+   carries no cell.  cells[nf][3], or [nf][9] in a triclinic run.  Returns -1, or the first frame that fails, the reason in why. */
+long long trr_cells(const TrajIO &io, const char *bytes, long long f0, long long nf, bool tri, double cut, double *cells, char *why, size_t why_len)
+{
+    const int64_t *off = io.trr_off.data() + f0;
+    for (long long f = 0; f < nf; ++f) {
+        const long long at = off[f] - off[0];
+        freesasa_gpu_trr_record r;
+        double b[9];
+        if (freesasa_gpu_trr_frame_desc(bytes + at, off[f + 1] - off[f], 0, 0, at, &r, why, (int)why_len)) return f;
+        if (r.box_off < 0) { snprintf(why, why_len, "it has no box: the frame carries no cell"); return f; }
+        freesasa_gpu_trr_box(bytes + r.box_off, r.real_bytes, b);
+        if (box_cell_bad(b, tri, cut, cells + (tri ? PBC_TRI_CELL : 3) * f, why, why_len)) return f;
     }
     return -1;
 }
@@ -714,7 +773,7 @@ int shard_read(TrajRun &T, freesasa_gpu_ctx *c, TrajShard &h)
     /* (an XTC shard: behind what goes up, the place its frames' status comes down to) */
     if (ensure_pinned(c, &c->stage_in, &c->stage_in_cap, T.up_bytes(h.in_bytes, (size_t)h.nf) + (T.xtc ? 8 * (size_t)h.nf : 0))) return -1;
     if (h.src) memcpy(c->stage_in, h.src, h.in_bytes);
-    else if (!pread_all(T.io.in.fd, c->stage_in, h.in_bytes, T.xtc ? (long long)T.io.xtc_off[(size_t)h.f0] : T.io.in_header + (long long)T.stride * h.f0))
+    else if (!pread_all(T.io.in.fd, c->stage_in, h.in_bytes, T.indexed ? (long long)T.idx[(size_t)h.f0] : T.io.in_header + (long long)T.stride * h.f0))
         return ctx_fail(c, "could not read frames %lld..%lld of the frame file", h.f0, h.f0 + h.nf - 1);
     if (T.xtc) {
         char why[200];
@@ -724,6 +783,16 @@ int shard_read(TrajRun &T, freesasa_gpu_ctx *c, TrajShard &h)
         if (T.pbc) {
             const long long odd = xtc_cells(T.io, bytes, h.f0, h.nf, T.io.tri, T.pbc_cut, (double *)((char *)c->stage_in + TrajRun::cells_at(h.in_bytes)), why, sizeof why);
             if (odd >= 0) return ctx_fail(c, "frame %lld of the XTC file: %s", h.f0 + odd, why);
+        }
+    }
+    if (T.trr) {
+        char why[200];
+        const char *bytes = (const char *)c->stage_in;
+        const long long bad = trr_descriptors(T.io, bytes, h.f0, h.nf, (int)T.fa, (int64_t *)((char *)c->stage_in + T.trr_xoff_at(h.in_bytes, (size_t)h.nf)), why, sizeof why);
+        if (bad >= 0) return ctx_fail(c, "frame %lld of the TRR file is damaged: %s", h.f0 + bad, why);
+        if (T.pbc) {
+            const long long odd = trr_cells(T.io, bytes, h.f0, h.nf, T.io.tri, T.pbc_cut, (double *)((char *)c->stage_in + TrajRun::cells_at(h.in_bytes)), why, sizeof why);
+            if (odd >= 0) return ctx_fail(c, "frame %lld of the TRR file: %s", h.f0 + odd, why);
         }
     }
     if (T.dcd) {
@@ -784,6 +853,10 @@ int shard_upload(TrajRun &T, TrajLane &L, const TrajShard &h)
     if (T.netcdf) {
         const sasa::TrajNcArgs na = {(int)T.n, h.nf, T.gather ? L.ta.index : nullptr, T.io.nc.record_bytes, T.io.nc.coord_off};
         if (kl_traj_gather_nc(na, d_in, (double *)c->h_xyz.p, c->stream) != hipSuccess) return ctx_fail(c, "NetCDF gather launch failed");
+    }
+    if (T.trr) {
+        const sasa::TrajTrrArgs ra = {(int)T.n, h.nf, T.gather ? L.ta.index : nullptr, (const int64_t *)((const char *)d_in + T.trr_xoff_at(h.in_bytes, (size_t)h.nf))};
+        if (kl_traj_gather_trr(ra, d_in, T.io.trr.real_bytes == 8, (double *)c->h_xyz.p, c->stream) != hipSuccess) return ctx_fail(c, "TRR gather launch failed");
     }
     /* full frames up as they were read: one kernel drops the solvent and widens fp32 */
     if (T.gather && !T.container && kl_traj_gather(L.ta, d_in, f32, (double *)c->h_xyz.p, c->stream) != hipSuccess) return ctx_fail(c, "gather launch failed");
@@ -1113,12 +1186,12 @@ extern "C" int freesasa_gpu_trajectory_topology(const double *xyz_frames, int n_
    files byte for byte.  With a topology, in front of the line's end, what its outputs depend on: digests of the index, of
    residue boundaries + classes + backbone flags, of the selection set's program, and which result files the run writes; with
    chain groups, behind that, a digest of the group count and the ids; with run statistics, last, the word as stats=.  A DCD run: bit 2 in the f32= word and the byte of
-   frame 0 as header_bytes=; an AMBER NetCDF run: bit 5 and the byte of record 0; an XTC run: bit 6 (its frames are found by the index: header_bytes=0); a raw run's line is what it was.  Periodic images: bit 3 in the f32= word, triclinic cells: bit 4. */
+   frame 0 as header_bytes=; an AMBER NetCDF run: bit 5 and the byte of record 0; an XTC run: bit 6 (its frames are found by the index: header_bytes=0); a TRR run: bit 7 likewise; a raw run's line is what it was.  Periodic images: bit 3 in the f32= word, triclinic cells: bit 4. */
 static int traj_done_head(char *head, size_t cap, const TrajSpec &s, const TrajIO &io, const struct stat &st)
 {
     int len = snprintf(head, cap, "freesasa_amd trajectory done-list v2 n_atoms=%d n_frames=%lld frames_per_batch=%d alg=%d resolution=%d probe=%.17g f32=%d "
                        "header_bytes=%lld frames_size=%lld frames_mtime=%lld.%09ld radii=%016llx\n",
-                       s.n_atoms, s.n_frames, s.frames_per_batch, s.alg, s.resolution, s.probe, io.in_f32 | (io.out_f32() << 1) | (io.in_dcd ? FREESASA_GPU_FRAMES_DCD : 0) | (io.in_nc ? FREESASA_GPU_FRAMES_NETCDF : 0) | (io.in_xtc ? FREESASA_GPU_FRAMES_XTC : 0) | (io.pbc ? FREESASA_GPU_FRAMES_PBC : 0) | (io.tri ? FREESASA_GPU_FRAMES_TRICLINIC : 0), io.in_header, (long long)st.st_size,
+                       s.n_atoms, s.n_frames, s.frames_per_batch, s.alg, s.resolution, s.probe, io.in_f32 | (io.out_f32() << 1) | (io.in_dcd ? FREESASA_GPU_FRAMES_DCD : 0) | (io.in_nc ? FREESASA_GPU_FRAMES_NETCDF : 0) | (io.in_xtc ? FREESASA_GPU_FRAMES_XTC : 0) | (io.in_trr ? FREESASA_GPU_FRAMES_TRR : 0) | (io.pbc ? FREESASA_GPU_FRAMES_PBC : 0) | (io.tri ? FREESASA_GPU_FRAMES_TRICLINIC : 0), io.in_header, (long long)st.st_size,
                        (long long)st.st_mtim.tv_sec, (long)st.st_mtim.tv_nsec, fnv1a(s.radii, 8 * (size_t)s.n_atoms));
     const TrajTopo *tp = s.topo;
     if (tp && len > 0 && len < (int)cap) {
@@ -1144,7 +1217,7 @@ static int traj_done_head(char *head, size_t cap, const TrajSpec &s, const TrajI
     return len > 0 && len < (int)cap ? 0 : -1;
 }
 
-/* Frame file (raw frames, with FREESASA_GPU_FRAMES_DCD a DCD trajectory, with FREESASA_GPU_FRAMES_NETCDF an AMBER NetCDF one) -> result files, resumable (include/freesasa_gpu.h has the formats).  The caller has put the result files'
+/* Frame file (raw frames, with FREESASA_GPU_FRAMES_DCD a DCD trajectory, with FREESASA_GPU_FRAMES_NETCDF an AMBER NetCDF one, with FREESASA_GPU_FRAMES_XTC / _TRR a GROMACS one) -> result files, resumable (include/freesasa_gpu.h has the formats).  The caller has put the result files'
    paths into io.out[]; s.topo: a run with a topology - frames of its frame_atoms atoms, a longer first line of the done-list. */
 static int trajectory_file_run(const char *frames_path, int frames_f32, long long header_bytes, TrajSpec s, TrajIO &io,
                                const char *done_path, long long *frames_total_out, char *err_out, int err_len)
@@ -1153,11 +1226,34 @@ static int trajectory_file_run(const char *frames_path, int frames_f32, long lon
     if (s.n_atoms <= 0 || header_bytes < 0) return set_err(err_out, err_len, "bad argument");
     if (io.stats && (!io.stats_path || !io.parts_path)) return set_err(err_out, err_len, "statistics need a statistics path and a partials path");
     const long long frame_atoms = s.topo ? s.topo->frame_atoms : s.n_atoms;
-    if ((frames_f32 & FREESASA_GPU_FRAMES_PBC) && !(frames_f32 & (FREESASA_GPU_FRAMES_DCD | FREESASA_GPU_FRAMES_NETCDF | FREESASA_GPU_FRAMES_XTC)))
-        return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) needs bit 2 (a DCD file), bit 5 (an AMBER NetCDF file) or bit 6 (an XTC file): raw frame files carry no cell");
+    if ((frames_f32 & FREESASA_GPU_FRAMES_PBC) && !(frames_f32 & (FREESASA_GPU_FRAMES_DCD | FREESASA_GPU_FRAMES_NETCDF | FREESASA_GPU_FRAMES_XTC | FREESASA_GPU_FRAMES_TRR)))
+        return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) needs bit 2 (a DCD file), bit 5 (an AMBER NetCDF file), bit 6 (an XTC file) or bit 7 (a TRR file): raw frame files carry no cell");
     if ((frames_f32 & FREESASA_GPU_FRAMES_TRICLINIC) && !(frames_f32 & FREESASA_GPU_FRAMES_PBC))
-        return set_err(err_out, err_len, "bit 4 of frames_f32 (triclinic cells) needs bit 3 (periodic images) and bit 2 (a DCD file), bit 5 (an AMBER NetCDF file) or bit 6 (an XTC file)");
-    if (frames_f32 & FREESASA_GPU_FRAMES_XTC) {
+        return set_err(err_out, err_len, "bit 4 of frames_f32 (triclinic cells) needs bit 3 (periodic images) and bit 2 (a DCD file), bit 5 (an AMBER NetCDF file), bit 6 (an XTC file) or bit 7 (a TRR file)");
+    if (frames_f32 & FREESASA_GPU_FRAMES_TRR) {
+        /* a TRR file's frames are found by one pass over its records' headers: before a device is touched or an output file opened */
+        if (frames_f32 & FREESASA_GPU_FRAMES_F32) return set_err(err_out, err_len, "bit 0 of frames_f32 (raw fp32 frames) and bit 7 (a TRR file) exclude each other: the file says its own precision");
+        if (frames_f32 & FREESASA_GPU_FRAMES_DCD) return set_err(err_out, err_len, "bit 2 of frames_f32 (a DCD file) and bit 7 (a TRR file) exclude each other");
+        if (frames_f32 & FREESASA_GPU_FRAMES_NETCDF) return set_err(err_out, err_len, "bit 5 of frames_f32 (an AMBER NetCDF file) and bit 7 (a TRR file) exclude each other");
+        if (frames_f32 & FREESASA_GPU_FRAMES_XTC) return set_err(err_out, err_len, "bit 6 of frames_f32 (an XTC file) and bit 7 (a TRR file) exclude each other");
+        if (header_bytes != 0) return set_err(err_out, err_len, "header_bytes must be 0 with a TRR file: its frames are found by their headers");
+        int64_t *offsets = nullptr;
+        if (freesasa_gpu_trr_index_read(frames_path, &io.trr, &offsets, err_out, err_len)) return -1;
+        const int rc = guarded(err_out, err_len, [&]() -> int { io.trr_off.assign(offsets, offsets + io.trr.n_frames + 1); return 0; });
+        freesasa_gpu_trr_index_free(offsets);
+        if (rc) return -1;
+        if (io.trr.n_atoms != frame_atoms) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "the TRR file holds %d atoms per frame, the run expects %lld", (int)io.trr.n_atoms, frame_atoms);
+            return set_err(err_out, err_len, msg);
+        }
+        io.in_trr = true;
+        if (frames_f32 & FREESASA_GPU_FRAMES_PBC) {
+            if (!io.trr.has_box) return set_err(err_out, err_len, "periodic images need a TRR file with a box: this one's first coordinate frame has none, or one that is all zero");
+            io.pbc = true;
+            io.tri = (frames_f32 & FREESASA_GPU_FRAMES_TRICLINIC) != 0;
+        }
+    } else if (frames_f32 & FREESASA_GPU_FRAMES_XTC) {
         /* an XTC file's frames are found by one pass over their headers: before a device is touched or an output file opened */
         if (frames_f32 & FREESASA_GPU_FRAMES_F32) return set_err(err_out, err_len, "bit 0 of frames_f32 (raw fp32 frames) and bit 6 (an XTC file) exclude each other");
         if (frames_f32 & FREESASA_GPU_FRAMES_DCD) return set_err(err_out, err_len, "bit 2 of frames_f32 (a DCD file) and bit 6 (an XTC file) exclude each other");
@@ -1224,6 +1320,7 @@ static int trajectory_file_run(const char *frames_path, int frames_f32, long lon
     const long long in_file = io.in_dcd ? ((long long)st.st_size - io.dcd.first_frame) / io.dcd.frame_bytes
                             : io.in_nc ? ((long long)st.st_size - io.nc.first_record) / io.nc.record_bytes
                             : io.in_xtc ? (long long)io.xtc.n_frames
+                            : io.in_trr ? (long long)io.trr.n_frames
                                         : ((long long)st.st_size - header_bytes) / ((io.in_f32 ? 12LL : 24LL) * frame_atoms);
     if (s.n_frames <= 0) s.n_frames = in_file;
     if (s.n_frames <= 0 || s.n_frames > in_file) return set_err(err_out, err_len, "the frame file holds fewer frames than asked for");

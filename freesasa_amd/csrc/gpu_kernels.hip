@@ -883,6 +883,11 @@ __global__ __launch_bounds__(TRAJ_B) void k_traj_gather_nc(TrajNcArgs a, const u
 {
     traj_gather_nc(a, in, out, (int64_t)blockIdx.x * TRAJ_B + threadIdx.x);
 }
+template <bool DOUBLE>
+__global__ __launch_bounds__(TRAJ_B) void k_traj_gather_trr(TrajTrrArgs a, const uint32_t *in, double *out)
+{
+    traj_gather_trr<DOUBLE>(a, in, out, (int64_t)blockIdx.x * TRAJ_B + threadIdx.x);
+}
 /* XTC input: a workgroup of one wavefront per frame - the lanes stage a window of the stream, lane 0 walks it - and one thread
    per group record */
 __global__ __launch_bounds__(XTC_SCAN_B) void k_xtc_scan(XtcArgs a)
@@ -941,6 +946,13 @@ hipError_t kl_traj_gather_nc(const TrajNcArgs &a, const void *d_in, double *d_ou
 {
     const unsigned grid = (unsigned)((3 * (int64_t)a.n_frames * a.n + TRAJ_B - 1) / TRAJ_B);
     hipLaunchKernelGGL(k_traj_gather_nc, dim3(grid), dim3(TRAJ_B), 0, st, a, (const uint32_t *)d_in, d_out);
+    return hipGetLastError();
+}
+hipError_t kl_traj_gather_trr(const TrajTrrArgs &a, const void *d_in, bool is_double, double *d_out, hipStream_t st)
+{
+    const unsigned grid = (unsigned)((3 * (int64_t)a.n_frames * a.n + TRAJ_B - 1) / TRAJ_B);
+    if (is_double) hipLaunchKernelGGL(k_traj_gather_trr<true>, dim3(grid), dim3(TRAJ_B), 0, st, a, (const uint32_t *)d_in, d_out);
+    else hipLaunchKernelGGL(k_traj_gather_trr<false>, dim3(grid), dim3(TRAJ_B), 0, st, a, (const uint32_t *)d_in, d_out);
     return hipGetLastError();
 }
 hipError_t kl_xtc_scan(const XtcArgs &a, hipStream_t st)

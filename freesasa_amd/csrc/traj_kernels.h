@@ -7,6 +7,7 @@
  *   traj_gather        out[f][i] = in[f][index[i]], fp32 input widened on the way (before the engine sees the frames)
  *   traj_gather_dcd    the same from the bytes of DCD frames: planar x[] | y[] | z[] records of fp32, either byte order
  *   traj_gather_nc     the same from the bytes of AMBER NetCDF records: big-endian fp32, atom by atom, at a record stride
+ *   traj_gather_trr    the same from the bytes of GROMACS TRR records: big-endian fp32 or fp64 in nm, each frame at its own byte
  *   traj_residue       the six per-residue areas of every (frame, residue), as residue_areas (sasa_kernels.h)
  *   traj_class_phase0  the three class sums of every frame, as class_phase0 / class_phase1
  *   traj_sel_phase0/1  the selection areas of every frame, as sel_sums_phase0 / sel_sums_phase1 (select_kernels.h)
@@ -123,6 +124,46 @@ SASA_D void traj_gather_nc(const TrajNcArgs &a, const uint32_t *in, double *out,
     float v;
     memcpy(&v, &w, 4);
     out[t] = (double)v;
+}
+
+/* traj_gather_trr: the frames of a shard as they lie in a GROMACS TRR file (trr.c has the layout) -> the compact fp64 frames.
+   Records have no common stride and some hold no coordinates: x_off[f] is the byte of frame f's x[0] within the shard, made
+   on the host from the checked headers; from there x, y, z of ALL the frame's atoms lie atom by atom as big-endian reals in
+   nm.  One thread per output coordinate, t -> (f, i, comp) as in traj_gather: with the identity index (index NULL)
+   consecutive lanes read consecutive reals and write consecutive doubles.  Every offset is a multiple of 4 and in general
+   not of 8 (x[0] of a double record with a box: byte 164): 4-byte loads only, `in` is the shard's bytes as 32-bit words - a
+   double is two of them, the high word first.  DOUBLE: the file's precision - a build of its own, not a branch per lane.
+   out = (double) real * 10.0 (nm to Angstrom): exact for a float, one rounding for a double, so both precisions give the
+   frames of a raw fp64 file that holds (double) x_nm * 10.0.  This is traj_gather AND the widening for TRR input. */
+struct TrajTrrArgs {
+    int n;                /* atoms of a frame as the engine sees it */
+    int n_frames;         /* frames of this shard */
+    const int32_t *index; /* [n] output atom i is the file's atom index[i]; NULL: i */
+    const int64_t *x_off; /* [n_frames] byte of x[0] of every frame within the shard (a multiple of 4) */
+};
+SASA_D uint32_t traj_bswap32(uint32_t w) { return (w >> 24) | ((w >> 8) & 0xff00u) | ((w << 8) & 0xff0000u) | (w << 24); }
+template <bool DOUBLE>
+SASA_D void traj_gather_trr(const TrajTrrArgs &a, const uint32_t *in, double *out, int64_t t)
+{
+    const int64_t total = 3 * (int64_t)a.n_frames * a.n;
+    if (t >= total) return;
+    const int64_t atom = t / 3;
+    const int comp = (int)(t - 3 * atom);
+    const int64_t f = atom / a.n;
+    const int i = (int)(atom - f * a.n);
+    const int64_t real = 3 * (int64_t)(a.index ? a.index[i] : i) + comp; /* of the frame's x[] */
+    const int64_t word = (a.x_off[f] >> 2) + (DOUBLE ? 2 * real : real);
+    const uint32_t hi = traj_bswap32(in[word]);
+    double v;
+    if (DOUBLE) {
+        const uint64_t u = ((uint64_t)hi << 32) | traj_bswap32(in[word + 1]);
+        memcpy(&v, &u, 8);
+    } else {
+        float s;
+        memcpy(&s, &hi, 4);
+        v = (double)s;
+    }
+    out[t] = v * 10.0;
 }
 
 /* traj_residue, one thread per (frame, residue): residue_areas' loop with the areas of frame f and the flags of the topology */

@@ -518,8 +518,7 @@ int freesasa_gpu_cell_from_lengths_angles(const double len[3], const double deg[
    failed read ("frame K of the DCD file is damaged"; the shard is not listed).  The done-list's f32= word carries bit 2
    and its header_bytes= the byte of frame 0: a raw run's list is refused by a DCD run and the other way round; a raw run's
    line is what it was.  Without bit 3 SASA is computed WITHOUT periodic images: a solute that the writer wrapped across the
-   box must be made whole beforehand.  Not offered: DCD files with fixed atoms or 64-bit record markers, TRR, a memory
-   form.
+   box must be made whole beforehand.  Not offered: DCD files with fixed atoms or 64-bit record markers, a memory form.
 
    AMBER NetCDF input (all four file entries): with bit 5 of frames_f32 set (FREESASA_GPU_FRAMES_NETCDF) frames_path is an
    AMBER NetCDF trajectory (convention 1.0, `.nc` as sander, pmemd, cpptraj, OpenMM and MDAnalysis write it): NetCDF classic,
@@ -538,7 +537,7 @@ int freesasa_gpu_cell_from_lengths_angles(const double len[3], const double deg[
    edge must be finite and >= c; with bit 4 the cell goes through freesasa_gpu_cell_from_lengths_angles and the checks of a
    DCD record.  A frame that fails ends the run ("frame K of the NetCDF file: ..." with the reason; the shard is not listed).
    Refused up front: bit 3 on a file without the cell variables, freesasa_gpu_trajectory_file_groups with bit 3.
-   Not offered: TRR, NetCDF-4 (HDF5) and CDF-5 files, AMBER restart files, a scale_factor other than 1, a memory form.
+   Not offered: NetCDF-4 (HDF5) and CDF-5 files, AMBER restart files, a scale_factor other than 1, a memory form.
 
    GROMACS XTC input (all four file entries): with bit 6 of frames_f32 set (FREESASA_GPU_FRAMES_XTC) frames_path is an XTC
    trajectory (magic 1995, more than 9 atoms: compressed coordinates; freesasa_gpu_xtc_info_read below has the layout).
@@ -560,9 +559,33 @@ int freesasa_gpu_cell_from_lengths_angles(const double len[3], const double deg[
    box[2][1], box[2][2].  A non-zero upper element, an off-diagonal element without bit 4 or an all-zero box ends the run
    ("frame K of the XTC file: ..."); the rest are the checks of a DCD cell.  Refused up front: bit 3 on a file whose first
    frame has an all-zero box, freesasa_gpu_trajectory_file_groups with bit 3.
-   Not offered: TRR, magic 2023 (64-bit byte counts), frames of 9 atoms or fewer (uncompressed), streams of 2^28 bytes and
+   Not offered: magic 2023 (64-bit byte counts), frames of 9 atoms or fewer (uncompressed), streams of 2^28 bytes and
    more, a memory form, chain groups with periodic images, double-precision XTC.  No GROMACS-written file was at hand when
    this was written: conformance rests on the format's description; compare one frame against `gmx dump` first.
+
+   GROMACS TRR input (all four file entries): with bit 7 of frames_f32 set (FREESASA_GPU_FRAMES_TRR) frames_path is a TRR
+   trajectory, the full-precision file GROMACS writes with nstxout, in single or double precision
+   (freesasa_gpu_trr_info_read below has the layout).  header_bytes must be 0, bits 0, 2, 5 and 6 clear; bit 1 keeps its
+   meaning.  Records are uncompressed but of unequal length - nstvout and nstfout differ from nstxout - and need not hold
+   coordinates: one pass over the file's headers before a device is touched or an output file opened builds the INDEX, the
+   byte offset of every record WITH coordinates, checks every header and counts the frames; the records without coordinates
+   are no frames of the run: they lie between the frames and go up unread.  The file's atom count must equal n_atoms (with a
+   topology: frame_atoms).  A shard is the bytes offset[f0] .. offset[f0 + nf], still one read and one host-to-device copy;
+   behind the bytes ride (the cells of a periodic run and) one int64 per frame, the byte of its x[0] within the shard.  Every
+   header of the shard is checked again as it lies in the staging before anything goes up: a failure ends the run ("frame K
+   of the TRR file is damaged: ..."), nothing of the shard is written and it is not listed.  ONE kernel (traj_kernels.h,
+   traj_gather_trr) makes of the big-endian reals the compact fp64 frames the engine reads, through the atom index when
+   there is a topology: 4-byte loads only (a double is two words, high word first: x[0] of a double record with a box lies at
+   byte 164), (double) real * 10.0 (nm to Angstrom) - exact for a float, one rounding for a double.  BOTH precisions land in
+   the fp64 frames directly: a TRR run's results are those of a raw fp64 frame file that holds (double) x_nm * 10.0, byte for
+   byte.  The done-list's f32= word carries bit 7: raw, DCD, NetCDF, XTC and TRR runs refuse each other's lists.  Periodic
+   images: bits 3 and 4 may stand beside bit 7 as beside bit 6; the cell is every frame's box, each element
+   (double) real * 10.0, GROMACS' lower triangle as in an XTC frame, and the checks are those of an XTC box, a frame without
+   a box failing like one whose box is all zero ("frame K of the TRR file: ...").  Refused up front: bit 3 on a file whose
+   first coordinate frame has no box or an all-zero one, freesasa_gpu_trajectory_file_groups with bit 3.
+   Not offered: a memory form, chain groups with periodic images, a TRR whose records change atom count or precision, a read
+   of velocities or forces, records with an ir, e, top or sym part.  No GROMACS-written file was at hand when this was
+   written: conformance rests on the format's description; compare one frame against `gmx dump` first.
 
    Periodic images (freesasa_gpu_trajectory_file, _file_devices, _file_topology): with bit 3 (FREESASA_GPU_FRAMES_PBC) beside
    bit 2 (beside bit 5: above) every frame is computed among the periodic images its own unit-cell record implies, as freesasa_gpu_calc_periodic
@@ -590,10 +613,11 @@ int freesasa_gpu_cell_from_lengths_angles(const double len[3], const double deg[
 #define FREESASA_GPU_FRAMES_F32 1     /* frames_f32 bit 0: raw fp32 frames (input format) */
 #define FREESASA_GPU_FRAMES_OUT_F32 2 /* bit 1: per-atom (and isolated) areas written as fp32 (output format) */
 #define FREESASA_GPU_FRAMES_DCD 4     /* bit 2: frames_path is a DCD trajectory */
-#define FREESASA_GPU_FRAMES_PBC 8     /* bit 3: with bit 2 or bit 5, every frame among the periodic images of its cell */
+#define FREESASA_GPU_FRAMES_PBC 8     /* bit 3: with bit 2, 5, 6 or 7, every frame among the periodic images of its cell */
 #define FREESASA_GPU_FRAMES_TRICLINIC 16 /* bit 4: with bit 3, the cell decoded as a triclinic cell */
 #define FREESASA_GPU_FRAMES_NETCDF 32 /* bit 5: frames_path is an AMBER NetCDF trajectory */
 #define FREESASA_GPU_FRAMES_XTC 64    /* bit 6: frames_path is a GROMACS XTC trajectory */
+#define FREESASA_GPU_FRAMES_TRR 128   /* bit 7: frames_path is a GROMACS TRR trajectory, single or double precision */
 
 /* The header of a DCD file.  Every integer of the file is an int32 in the file's byte order; records lie between two equal
    byte counts:  [84 | "CORD" | 20 control words | 84]  [m | NTITLE | 80 NTITLE bytes | m]  [4 | NATOM | 4], then per frame
@@ -693,6 +717,49 @@ int freesasa_gpu_xtc_frame_desc(const void *header, long long avail, int n_atoms
                                 long long *frame_bytes_out, char *why, int why_len);
 /* the nine floats of a header's box, in the host's byte order (nm) */
 void freesasa_gpu_xtc_frame_box(const void *header, float box_out[9]);
+
+/* A GROMACS TRR trajectory.  Every value of the file is XDR: big-endian, 4-byte units.  A record:
+       int magic = 1993 | int 13 | int 12 | 12 bytes "GMX_trn_file" |
+       int ir_size, e_size, box_size, vir_size, pres_size, top_size, sym_size, x_size, v_size, f_size, natoms, step, nre |
+       real t | real lambda | box[9] | vir[9] | pres[9] | x[3 natoms] | v[3 natoms] | f[3 natoms]
+   each part of the body present only when its size is not 0; real is 4 or 8 bytes for the whole record: box_size / 9 when
+   box_size != 0, else the first non-zero of x_size, v_size, f_size divided by 3 natoms.  The header is
+   FREESASA_GPU_TRR_HEADER_MIN + 2 reals = 84 or 92 bytes; units are nm; the box rows are a, b, c, the lower triangle of an
+   XTC box.  freesasa_gpu_trr_index_read makes ONE pass over the file, one read of at most 92 bytes per record: it checks every
+   header, counts the records and those WITH coordinates (the frames) and, with offsets_out, returns the byte at which every
+   frame begins, [n_frames + 1] with the end of the file behind them, in an array the caller frees with
+   freesasa_gpu_trr_index_free; without offsets_out (freesasa_gpu_trr_info_read) it allocates nothing.  Returns 0, or -1 with
+   "record K of the TRR file: <reason>" in err - each its own reason: a magic number other than 1993, a version string other
+   than 13, 12, "GMX_trn_file", a non-zero ir_size, e_size, top_size or sym_size, natoms <= 0, a real width that is neither 4
+   nor 8, a size that disagrees with natoms and that width, an atom count or a precision other than record 0's, a file that
+   ends inside a header or inside a body - or "the TRR file holds no coordinate frame".  A file cut exactly between two
+   records is a shorter file. */
+#define FREESASA_GPU_TRR_HEADER_MIN 76
+typedef struct freesasa_gpu_trr_info {
+    int32_t n_atoms;          /* of record 0, and so of every record */
+    int64_t n_frames;         /* records WITH coordinates, by the pass over the headers */
+    int64_t n_records;        /* all records */
+    int64_t max_frame_bytes;  /* the longest stretch from a frame's first byte to the next frame's (the file's end) */
+    int32_t real_bytes;       /* 4 or 8: of record 0, and so of every record */
+    int32_t has_box;          /* the first frame has a box with a non-zero element */
+    int32_t has_velocities, has_forces; /* some record has them (never read) */
+} freesasa_gpu_trr_info;
+int freesasa_gpu_trr_info_read(const char *path, freesasa_gpu_trr_info *out, char *err, int err_len); /* 0 / -1 */
+int freesasa_gpu_trr_index_read(const char *path, freesasa_gpu_trr_info *out, int64_t **offsets_out, char *err, int err_len);
+void freesasa_gpu_trr_index_free(int64_t *offsets);
+/* What one record's header says, and where its parts lie when the record begins at byte `base` (of a shard, of the file) */
+typedef struct freesasa_gpu_trr_record {
+    int32_t n_atoms, real_bytes;
+    int32_t has_box, has_x, has_v, has_f;
+    int64_t record_bytes;     /* header and body */
+    int64_t box_off, x_off;   /* byte of box[0] and of x[0]; -1: the record has none (multiples of 4, not of 8 in general) */
+} freesasa_gpu_trr_record;
+/* The checks of one header (`avail` bytes of the file lie from its first byte on, of which at most 92 are read; n_atoms > 0 and
+   real_bytes > 0: what it must hold) and what it says.  0, or -1 with the reason in why. */
+int freesasa_gpu_trr_frame_desc(const void *header, long long avail, int n_atoms, int real_bytes, long long base,
+                                freesasa_gpu_trr_record *out, char *why, int why_len);
+/* the nine reals of a box, as doubles in the host's byte order (nm) */
+void freesasa_gpu_trr_box(const void *box, int real_bytes, double box_out[9]);
 
 int freesasa_gpu_trajectory(const double *xyz_frames, const double *radii, int n_atoms, int n_frames,
                             int alg, double probe_radius, int resolution, int frames_per_batch,

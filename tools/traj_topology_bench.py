@@ -51,6 +51,14 @@ and one atom more), no topology, and the arms are three files of the same decode
 each line with the host CPU time of the process per atom-frame; the totals files must be identical.  --xtc-fpb sets
 frames_per_batch for all three arms (0: the driver's default).
 
+With --trr the system is the same water-like 10 000 atoms and the arms are two files of the same frames, interleaved:
+    raw       trajectory_file on the raw frame file a TRR file of that precision stands in for: fp32 (Angstrom, rounded once more)
+              for a single-precision TRR, fp64 (float64(x_nm) * 10.0, the very numbers) with --double
+    trr       ... on a GROMACS TRR file written by tests/trr_codec.py (box and coordinates per record), single precision or, with
+              --double, double: --xtc-distinct frames repeated up to --frames; gathered, byte-swapped and scaled on the device
+each line with the host CPU time of the process per atom-frame; with --double the totals files must be identical, in single
+precision equal to fp32 rounding.  --trr-arms raw times the raw arm alone (a library without TRR input); --xtc-fpb as above.
+
 With --stats the frames are those of the 10 000 solute atoms alone (fp32, no solvent, the topology the whole frame) and the arms are
 what a caller who wants the averages over the run can do, interleaved:
     totals    trajectory_file_topology, totals only (the floor: nothing per atom leaves the device)
@@ -61,7 +69,7 @@ each line with the bytes of results per frame; the stats arm's per-atom means mu
 
 One JSON line per arm: atom-frames/s counted in SOLUTE atoms and in frame atoms, the median and the spread of --reps runs.
 
-    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd] [--netcdf] [--pbc [--pbc-arms all|off] [--triclinic]] [--xtc [--xtc-distinct 24] [--xtc-fpb 0]] [--stats]
+    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd] [--netcdf] [--pbc [--pbc-arms all|off] [--triclinic]] [--xtc [--xtc-distinct 24] [--xtc-fpb 0]] [--trr [--double] [--trr-arms raw,trr]] [--stats]
 
 For the kernel times: `rocprofv3 --kernel-trace --stats -- python tools/traj_topology_bench.py --reps 1 --arms all`
 (k_traj_gather / k_traj_residues / k_traj_class / k_traj_sel are the topology's kernels, k_traj_group_* the groups')."""
@@ -272,6 +280,59 @@ def xtc_mode(args, scratch):
     return lines
 
 
+def trr_mode(args, scratch):
+    """the arms of --trr -> the JSON lines"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import trr_codec as tc
+    n, mol = N_SOLUTE, N_SOLUTE // 3
+    rng = np.random.default_rng(9)
+    box = np.diag([4.64, 4.64, 4.64])
+    real = np.float64 if args.double else np.float32
+    coded, raw = [], []
+    for f in range(args.xtc_distinct):
+        big = rng.integers(0, 4640, (mol + n - 3 * mol, 3))
+        h1 = big[:mol] + rng.integers(-100, 101, (mol, 3))
+        h2 = h1 + rng.integers(-160, 161, (mol, 3))
+        x_nm = np.concatenate([np.stack([h1, big[:mol], h2], axis=1).reshape(-1, 3), big[mol:]]) / 1000.0
+        coded.append(tc.record_bytes(n, double=args.double, x=x_nm, box=box, step=f, t=float(f)))
+        raw.append((x_nm.astype(real).astype(np.float64) * 10.0).astype(real))                           # (--double: what the TRR run computes on)
+    p = lambda k: os.path.join(scratch, k)
+    with open(p("water.trr"), "wb") as f_trr, open(p("water.raw"), "wb") as f_raw:
+        for f in range(args.frames):
+            f_trr.write(coded[f % len(coded)])
+            raw[f % len(raw)].tofile(f_raw)
+    radii = np.tile([1.1, 1.52, 1.1], mol + 1)[:n].astype(np.float64)
+    kw = dict(frames_per_batch=args.xtc_fpb)
+    arms = {"raw": lambda: fa.trajectory_file(p("water.raw"), radii, p("x0"), f32=not args.double, **kw),
+            "trr": lambda: fa.trajectory_file(p("water.trr"), radii, p("x1"), trr=True, **kw)}
+    arms = {a: arms[a] for a in args.trr_arms.split(",")}
+    if "trr" in arms:
+        info = fa.trr_info(p("water.trr"))
+        assert info.n_frames == args.frames and info.n_atoms == n and info.real_bytes == (8 if args.double else 4)
+    runs, cpu = {a: [] for a in arms}, {a: [] for a in arms}
+    for a in arms:
+        arms[a]()                                                        # warm-up: contexts, staging, page cache
+    for _ in range(args.reps):
+        for a in arms:
+            t0, c0 = time.perf_counter(), time.process_time()
+            res = arms[a]()
+            runs[a].append(time.perf_counter() - t0)
+            cpu[a].append(time.process_time() - c0)
+            assert res[0] and res[1] == args.frames
+    if len(arms) == 2:
+        t_raw, t_trr = np.fromfile(p("x0")), np.fromfile(p("x1"))
+        assert np.all(t_raw > 0) and (np.array_equal(t_raw, t_trr) if args.double else np.allclose(t_raw, t_trr, rtol=1e-5, atol=0))
+    lines = []
+    for a in arms:
+        v, c = sorted(runs[a]), sorted(cpu[a])
+        med = v[len(v) // 2]
+        lines.append(json.dumps({"arm": a + ("-f64" if args.double else "-f32"), "frames": args.frames, "frame_atoms": n, "frames_per_batch": args.xtc_fpb,
+                                 "file_bytes_per_frame": os.path.getsize(p({"raw": "water.raw", "trr": "water.trr"}[a])) / args.frames,
+                                 "median_seconds": med, "min_seconds": v[0], "max_seconds": v[-1], "atom_frames_per_s": n * args.frames / med,
+                                 "host_cpu_ns_per_atom_frame": 1e9 * c[len(c) // 2] / (n * args.frames), "runs": len(v)}))
+    return lines
+
+
 def stats_mode(args, scratch):
     """the three arms of --stats -> the JSON lines"""
     b, xyz = solute()
@@ -326,12 +387,15 @@ def main():
     ap.add_argument("--xtc", action="store_true", help="time a GROMACS XTC file against the raw fp32 file and an AMBER NetCDF file of the same decoded frames")
     ap.add_argument("--xtc-distinct", type=int, default=24, help="with --xtc: distinct frames that are encoded and then repeated")
     ap.add_argument("--xtc-fpb", type=int, default=0, help="with --xtc: frames_per_batch of all three arms (0: the driver's default)")
+    ap.add_argument("--trr", action="store_true", help="time a GROMACS TRR file against the raw frame file of the same frames")
+    ap.add_argument("--double", action="store_true", help="with --trr: a double-precision TRR file against the raw fp64 file (default: single against raw fp32)")
+    ap.add_argument("--trr-arms", default="raw,trr", help="with --trr: the arms that run")
     ap.add_argument("--stats", action="store_true", help="time the run statistics against the per-atom stream-out and against totals only")
     args = ap.parse_args()
     scratch = args.scratch or tempfile.mkdtemp(prefix="traj_topology_bench_")
     try:
-        if args.xtc or args.stats:
-            lines = stats_mode(args, scratch) if args.stats else xtc_mode(args, scratch)
+        if args.xtc or args.stats or args.trr:
+            lines = stats_mode(args, scratch) if args.stats else trr_mode(args, scratch) if args.trr else xtc_mode(args, scratch)
             print("\n".join(lines))
             if args.out:
                 with open(args.out, "w") as fh:
