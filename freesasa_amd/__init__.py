@@ -122,6 +122,10 @@ def lib():
                                               C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.freesasa_gpu_calc_groups.argtypes = [_dp, _dp, _lp, C.c_int, _i32p, _i32p, C.c_int, C.c_double, C.c_int,
                                                _dp, _dp, _dp, _dp, C.c_int, C.c_char_p, C.c_int]
+        L.freesasa_gpu_sr_volume_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _lp, C.c_int, C.c_double, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.freesasa_gpu_calc_volume.argtypes = [_dp, _dp, _lp, C.c_int, C.c_double, C.c_int, _dp, _ip, _dp, _dp, _dp, _dp,
+                                               C.c_int, C.c_char_p, C.c_int]
         L.freesasa_gpu_periodic_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _lp, C.c_int, _dp, C.c_double, C.c_int,
                                                 C.c_void_p, C.c_void_p, _lp]
         L.freesasa_gpu_calc_periodic.argtypes = [_dp, _dp, _lp, C.c_int, _dp, C.c_int, C.c_double, C.c_int, _dp, _dp, _lp,
@@ -242,6 +246,27 @@ def calc_groups(xyz, radii, offsets, group, n_groups, alg=LEE_RICHARDS, probe=1.
     if ret:
         raise RuntimeError("freesasa_gpu_calc_groups: " + err.value.decode())
     return sasa, iso, totals, gt
+
+
+def calc_volume(xyz, radii, offsets, probe=1.4, n_points=100, device=-1, per_atom=False):
+    """freesasa_gpu_calc_volume() on host arrays: (sasa, counts, totals, volumes) - the Shrake-Rupley areas, exposed-point
+    counts and totals of calc_batch, bit for bit, and the volume the solvent-accessible surface of every structure encloses
+    (what `gmx sasa -tv` gives; include/freesasa_gpu.h has the definition) - and with per_atom=True behind them evec [n, 3],
+    every atom's sum of its exposed unit points, and vol [n], its term of the volume.  Up to 128 test points."""
+    xyz, radii = _f64(xyz).reshape(-1), _f64(radii)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n, ns = radii.size, offsets.size - 1
+    sasa, totals, volumes = np.empty(n), np.empty(ns), np.empty(ns)
+    counts = np.empty(n, dtype=np.int32)
+    evec, vol = (np.empty((n, 3)), np.empty(n)) if per_atom else (None, None)
+    err = C.create_string_buffer(512)
+    opt = lambda a: None if a is None else a.ctypes.data_as(_dp)
+    ret = lib().freesasa_gpu_calc_volume(xyz.ctypes.data_as(_dp), radii.ctypes.data_as(_dp), offsets.ctypes.data_as(_lp), ns,
+                                         probe, n_points, sasa.ctypes.data_as(_dp), counts.ctypes.data_as(_ip), opt(evec), opt(vol),
+                                         totals.ctypes.data_as(_dp), volumes.ctypes.data_as(_dp), device, err, 512)
+    if ret:
+        raise RuntimeError("freesasa_gpu_calc_volume: " + err.value.decode())
+    return (sasa, counts, totals, volumes, evec, vol) if per_atom else (sasa, counts, totals, volumes)
 
 
 def calc_periodic(xyz, radii, offsets, cells, alg=LEE_RICHARDS, probe=1.4, resolution=20, device=-1):
@@ -1044,6 +1069,14 @@ def _topology_proto(L):
                                                         C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
                                                         C.c_char_p, C.c_char_p, C.c_char_p, _llp, C.c_char_p, C.c_longlong, _ip, C.c_int,
                                                         _llp, C.c_char_p, C.c_int]
+    # ... with the frames' volumes behind sel_atoms_out (an array / a path)
+    L.freesasa_gpu_trajectory_volume.argtypes = [_dp, C.c_int, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_void_p,
+                                                 C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _llp, _dp,
+                                                 _ip, C.c_int, C.c_char_p, C.c_int]
+    L.freesasa_gpu_trajectory_file_volume.argtypes = [C.c_char_p, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, C.c_int, _i32p,
+                                                      C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
+                                                      C.c_char_p, C.c_char_p, C.c_char_p, _llp, C.c_char_p, C.c_char_p, C.c_longlong, _ip, C.c_int,
+                                                      _llp, C.c_char_p, C.c_int]
     # the same with chain groups: (group, n_groups) behind the selection set, the two group outputs behind sel_atoms_out
     L.freesasa_gpu_trajectory_groups.argtypes = [_dp, C.c_int, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_void_p, _i32p, C.c_int,
                                                  C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _llp, _dp, _dp,
@@ -1063,11 +1096,11 @@ class TopologyResult:
     (isolated, complex, buried per frame and group), group_atoms [G], and with per_atom isolated [F, n], every atom's area in
     its group taken on its own (isolated - sasa: what the atom buries in the complex).  stats: the RunStats of the outputs
     named in stats=, None without.  With per_frame=False only totals (and selection_atoms) are delivered per frame: the others
-    are None."""
+    are None.  volumes [F]: with volumes=True, the volume every frame's solvent-accessible surface encloses; None without."""
 
     def __init__(self, totals, class_sums, residues, selection_areas, selection_atoms, sasa, res_ref, group_areas=None,
-                 group_atoms=None, isolated=None, stats=None):
-        self.stats = stats
+                 group_atoms=None, isolated=None, stats=None, volumes=None):
+        self.stats, self.volumes = stats, volumes
         self.totals, self.class_sums, self.residues = totals, class_sums, residues
         self.selection_areas, self.selection_atoms, self.sasa, self.res_ref = selection_areas, selection_atoms, sasa, res_ref
         self.group_areas, self.group_atoms, self.isolated = group_areas, group_atoms, isolated
@@ -1113,7 +1146,7 @@ def _topology_groups(batch, structure, n, chain_groups, separate_chains, long, g
 
 def trajectory_topology(frames, batch, structure=0, atom_index=None, selection=None, per_atom=False, alg=LEE_RICHARDS, probe=1.4,
                         resolution=20, frames_per_batch=0, device=-1, devices=None, chain_groups=None, separate_chains=False,
-                        long=False, group=None, n_groups=None, stats=None, per_frame=True):
+                        long=False, group=None, n_groups=None, stats=None, per_frame=True, volumes=False):
     """freesasa_gpu_trajectory_topology(): frames [F, frame_atoms, 3] of a (solvated) system whose solute is structure
     `structure` of the ingest.Batch - topology atom i is frame atom atom_index[i] (None: the frames hold exactly the
     structure's atoms) - -> a TopologyResult.  The gather, the per-residue, per-class and per-selection sums run on the
@@ -1124,7 +1157,11 @@ def trajectory_topology(frames, batch, structure=0, atom_index=None, selection=N
     stats=("atoms", "residues", ...) (the names of STATS_BITS; freesasa_gpu_trajectory_groups_stats): the result's stats holds the
     RunStats of those outputs over the run, reduced on the device shard by shard.  An output named there is computed whether or not
     it is delivered: with per_atom=False the per-atom areas never leave the device, and with per_frame=False neither do the class
-    sums, residues, selection and group areas."""
+    sums, residues, selection and group areas.
+    volumes=True (freesasa_gpu_trajectory_volume; Shrake-Rupley, up to 128 points, no chain groups, no statistics): the
+    result's volumes [F] holds the volume every frame's surface encloses, as calc_volume gives it for the frame."""
+    if volumes and (stats or not per_frame or chain_groups is not None or separate_chains or group is not None):
+        raise ValueError("volumes=True is not offered with chain groups, stats= or per_frame=False")
     if stats or not per_frame:
         return _trajectory_topology_stats(frames, batch, structure, atom_index, selection, per_atom, alg, probe, resolution, frames_per_batch,
                                           device, devices, chain_groups, separate_chains, long, group, n_groups, stats, per_frame)
@@ -1144,6 +1181,16 @@ def trajectory_topology(frames, batch, structure=0, atom_index=None, selection=N
     cb = batch._as_c()
     opt = lambda a, t=_dp: None if a is None else a.ctypes.data_as(t)
     ids, G, g_atoms = _topology_groups(batch, structure, n, chain_groups, separate_chains, long, group, n_groups)
+    if volumes:
+        vols = np.zeros(F)
+        ret = L.freesasa_gpu_trajectory_volume(frames.ctypes.data_as(_dp), F, C.byref(cb), structure, fa_, opt(idx, C.POINTER(C.c_int32)),
+                                               selection.handle if selection is not None else None, alg, probe, resolution,
+                                               frames_per_batch, totals.ctypes.data_as(_dp), opt(sasa), cls.ctypes.data_as(_dp),
+                                               res.ctypes.data_as(_dp), opt(sel_area), opt(sel_atoms, C.POINTER(C.c_longlong)),
+                                               vols.ctypes.data_as(_dp), dp_, nd, err, 512)
+        if ret:
+            raise RuntimeError("freesasa_gpu_trajectory_volume: " + err.value.decode())
+        return TopologyResult(totals, cls, res, sel_area, sel_atoms, sasa, res_ref, volumes=vols)
     if ids is None:
         ret = L.freesasa_gpu_trajectory_topology(frames.ctypes.data_as(_dp), F, C.byref(cb), structure, fa_, opt(idx, C.POINTER(C.c_int32)),
                                                  selection.handle if selection is not None else None, alg, probe, resolution,
@@ -1208,7 +1255,8 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
                              f32=False, header_bytes=0, n_frames=0, alg=LEE_RICHARDS, probe=1.4, resolution=20, frames_per_batch=0,
                              max_new_shards=0, device=-1, devices=None, out_f32=False, chain_groups=None, separate_chains=False,
                              long=False, group=None, n_groups=None, group_areas_path=None, isolated_path=None, dcd=False, pbc=False,
-                             triclinic=False, netcdf=False, xtc=False, stats=None, stats_path=None, partials_path=None, trr=False):
+                             triclinic=False, netcdf=False, xtc=False, stats=None, stats_path=None, partials_path=None, trr=False,
+                             volumes_path=None):
     """freesasa_gpu_trajectory_file_topology(): trajectory_file() with a topology (see trajectory_topology; frame_atoms:
     atoms per frame of the file, None: the structure's) and one raw fp64 result file per output asked for: class sums
     [F, 3], residues [F, R, 6], selection areas [F, S].  Returns (complete, n_frames, selection_atoms [S] or None).
@@ -1221,8 +1269,13 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
     xtc: frames_path is a GROMACS XTC trajectory; frame_atoms None is then the file's atom count; pbc and triclinic as with dcd.
     trr: frames_path is a GROMACS TRR trajectory; frame_atoms None is then the file's atom count; pbc and triclinic as with dcd.
     stats=("atoms", "residues", ...) with stats_path and partials_path (freesasa_gpu_trajectory_file_groups_stats): the run statistics of
-    those outputs, as trajectory_file describes them; an output named there needs no result file of its own."""
+    those outputs, as trajectory_file describes them; an output named there needs no result file of its own.
+    volumes_path (freesasa_gpu_trajectory_file_volume; Shrake-Rupley, up to 128 points, no chain groups, no statistics, no pbc):
+    receives the frames' volumes [F] fp64, as trajectory_topology(volumes=True) gives them."""
     L = _stats_proto(_topology_proto(lib()))
+    if volumes_path is not None and (stats or chain_groups is not None or separate_chains or group is not None or
+                                     group_areas_path is not None or isolated_path is not None):
+        raise ValueError("volumes_path is not offered with chain groups or stats=")
     bits = _frames_bits(f32, out_f32, dcd, header_bytes, pbc, triclinic, netcdf, xtc, trr)
     if dcd and frame_atoms is None:
         frame_atoms = dcd_info(frames_path).n_atoms
@@ -1241,6 +1294,17 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
     keep, dp_, nd = _devs(devices, device)
     cb = batch._as_c()
     ids, G, _ = _topology_groups(batch, structure, n, chain_groups, separate_chains, long, group, n_groups)
+    if volumes_path is not None:
+        ret = L.freesasa_gpu_trajectory_file_volume(enc(frames_path), bits, header_bytes, n_frames, C.byref(cb), structure, fa_,
+                                                    None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    selection.handle if selection is not None else None, alg, probe, resolution,
+                                                    frames_per_batch, enc(totals_path), enc(sasa_path), enc(class_sums_path),
+                                                    enc(residues_path), enc(selections_path),
+                                                    None if sel_atoms is None else sel_atoms.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                                    enc(volumes_path), enc(done_path), max_new_shards, dp_, nd, C.byref(total), err, 512)
+        if ret < 0:
+            raise RuntimeError("freesasa_gpu_trajectory_file_volume: " + err.value.decode())
+        return ret == 0, int(total.value), sel_atoms
     if stats:
         ret = L.freesasa_gpu_trajectory_file_groups_stats(enc(frames_path), bits, header_bytes, n_frames, C.byref(cb), structure, fa_,
                                                           None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
@@ -1471,6 +1535,15 @@ class GpuContext:
         if ret:
             raise RuntimeError("freesasa_gpu_periodic_triclinic_dev: " + self.error())
         return images
+
+    def volume(self, d_xyz, d_radii, offsets, d_sasa, d_volumes, d_counts=0, d_evec=0, d_vol=0, d_totals=0, probe=1.4, n_points=100):
+        """freesasa_gpu_sr_volume_dev(): shrake_rupley() and, into d_volumes [n_structs], the volume every structure's
+        solvent-accessible surface encloses (device pointers; d_counts [n], d_evec [3 n], d_vol [n], d_totals optional)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        ret = lib().freesasa_gpu_sr_volume_dev(self._h, d_xyz, d_radii, offsets.ctypes.data_as(_lp), offsets.size - 1, probe, n_points,
+                                               d_sasa, d_counts or None, d_evec or None, d_vol or None, d_totals or None, d_volumes or None)
+        if ret:
+            raise RuntimeError("freesasa_gpu_sr_volume_dev: " + self.error())
 
     def shrake_rupley(self, d_xyz, d_radii, offsets, d_sasa, d_counts=0, d_totals=0, probe=1.4,
                       n_points=100):

@@ -15,6 +15,8 @@
  *   gpu_parse.hip      the device-side PDB / mmCIF parser: its kernels and their host driver (gpu_parse.h)
  *   gpu_groups.hip     chain groups: a batch and every group of it cut out as a structure of its own, in one batch; the
  *                      group ids made on the device
+ *   gpu_volume.hip     molecular volume: the batch through the engine with the exposed-point vectors kept, the atoms' terms
+ *                      and the structures' volumes behind it; its device-pointer and host-pointer entries
  *   gpu_periodic.hip   periodic images: a batch and its cells (orthorhombic or triclinic) expanded into a batch with the
  *                      images that matter, the areas of the real atoms collected; the stage the trajectory file drivers share
  */
@@ -44,6 +46,7 @@
 #include "xtc_kernels.h"
 #include "pbc_kernels.h"
 #include "pbc_tri_kernels.h"
+#include "vol_kernels.h"
 #include "gpu_parse.h"
 
 /* ------------------------------------------------------------------ kernel launchers (gpu_kernels.hip) */
@@ -66,7 +69,9 @@ hipError_t kl_lr2_main(int rmax, int grid, size_t lds, hipStream_t st, const sas
 hipError_t kl_lr2_mid(int grid, size_t lds, hipStream_t st, const sasa::Lr2Args &la);
 /* first-generation tile kernels: tier 0 main launch, 1 second launch, 2 last launch (lists in a global slab) */
 hipError_t kl_lr_tile(int tier, const sasa::TileCfg &c, const sasa::TileArgs &t, int grid, size_t lds, hipStream_t st, bool bucket);
-hipError_t kl_sr_tile(int tier, const sasa::TileCfg &c, const sasa::TileArgs &t, int grid, size_t lds, hipStream_t st);
+/* (evec: the volume's exposed-point vectors [3 n_atoms], kept by the launches that run the third arrangement - sr_caps_shape;
+   null: the builds without them) */
+hipError_t kl_sr_tile(int tier, const sasa::TileCfg &c, const sasa::TileArgs &t, int grid, size_t lds, hipStream_t st, double *evec = nullptr);
 /* per-structure totals in two levels (chunk partials in `bpart`) */
 hipError_t kl_totals(const sasa::PipeArgs &pa, int n_chunks, int n_structs, const double *d_sasa, double *bpart, double *d_totals, hipStream_t st);
 hipError_t kl_segment_sums(const double *d_sasa, const int64_t *d_seg, int n_segs, bool short_segments, double *d_out, hipStream_t st);
@@ -124,6 +129,10 @@ hipError_t kl_pbc_collect(const sasa::PbcArgs &a, hipStream_t st);
 /* ... in a triclinic cell (pbc_tri_kernels.h): the same two phases with the general geometry; the collect is kl_pbc_collect */
 hipError_t kl_pbc_tri_count(const sasa::PbcTriArgs &a, hipStream_t st);
 hipError_t kl_pbc_tri_emit(const sasa::PbcTriArgs &a, hipStream_t st);
+
+/* molecular volume (vol_kernels.h): the origins (one workgroup per structure), the atoms' terms (one thread per atom) */
+hipError_t kl_vol_origin(const sasa::VolArgs &a, hipStream_t st);
+hipError_t kl_vol_atom(const sasa::VolArgs &a, hipStream_t st);
 
 /* ------------------------------------------------------------------ context (gpu_engine.hip) */
 
@@ -185,6 +194,11 @@ struct freesasa_gpu_ctx {
     DevBuf p_meta, p_ibase, p_xyz, p_radii, p_sasa, p_chunks, p_part;
     std::vector<int64_t> p_offsets_host; /* the offsets p_chunks was made for */
     int p_n_chunks = 0;
+    /* molecular volume (gpu_volume.hip): counts, exposed-point vectors, the atoms' terms, the structures' origins and volumes
+       where the caller gives no array of its own; vol_evec: set for the length of ONE run_batch, which then keeps the vectors
+       there - or refuses the batch (run_batch_once) */
+    DevBuf v_counts, v_evec, v_vol, v_origin, v_volumes;
+    double *vol_evec = nullptr;
     void *stage_in = nullptr, *stage_out = nullptr; /* page-locked host staging of freesasa_gpu_calc_batch_pipelined */
     size_t stage_in_cap = 0, stage_out_cap = 0;
     void *res_stage = nullptr; /* page-locked: a batch's per-residue areas and arrays on their way to the host (gpu_sweep.hip) */
@@ -298,6 +312,20 @@ int periodic_widths_bad(const double *widths, double c);
 int periodic_resident_tri(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
                           int n_fixed, const double *cells9, const double *d_cells9, double probe, int resolution, const double *unit_points,
                           double *d_sasa, double *d_totals, int64_t *images_out);
+
+/* ------------------------------------------------------------------ molecular volume (gpu_volume.hip) */
+
+/* freesasa_gpu_sr_volume_dev's pipeline on arrays that are on the context's stream already: run_batch (Shrake-Rupley, with
+   c->shared_radii as the caller has set it) with the exposed-point vectors kept, then origins, the atoms' terms and the
+   structures' volumes (kl_totals over the terms, with the chunk tables run_batch left on the device) enqueued on the stream;
+   nothing is waited for at its end.  d_counts / d_evec / d_vol / d_totals may be null (the context's own scratch then);
+   d_volumes [n_structs] is required.  0, or -1 with the context's message: a bad argument, or a batch whose volume the
+   engine does not make (more than 128 points, no table of cap masks, a launch in the second arrangement). */
+int volume_resident(freesasa_gpu_ctx *c, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
+                    double probe, int n_points, const double *unit_points, double *d_sasa, int *d_counts, double *d_evec,
+                    double *d_vol, double *d_totals, double *d_volumes);
+/* the arguments both volume entries check before a device is touched: 0, or the message */
+const char *volume_bad_args(const void *xyz, const void *radii, const int64_t *offsets, int n_structs, int n_points, const void *sasa, const void *volumes);
 
 /* ------------------------------------------------------------------ host-side helpers (gpu_hostbatch.hip) */
 

@@ -140,7 +140,7 @@ namespace {
 /* One per-frame OUTPUT of a run: a row of TrajIO's table.  An entry point says where it goes - the caller's array or a
    result file - and everything else that is per output (opening the files, is it wanted, its place in a shard's blocks, the
    copy or the pwrite at the frame's offset, the flush, the done-list's outputs= word) is a loop over the table. */
-enum { OUT_TOTALS, OUT_SASA, OUT_ISO, OUT_CLS, OUT_RES, OUT_SEL, OUT_GRP, N_OUT }; /* (per atom | from OUT_CLS on: the block of sums) */
+enum { OUT_TOTALS, OUT_SASA, OUT_ISO, OUT_CLS, OUT_RES, OUT_SEL, OUT_GRP, OUT_VOL, N_OUT }; /* (per atom | from OUT_CLS on: the block of sums) */
 struct TrajOut {
     const char *name;           /* in messages: "cannot open the %s file", "could not write the %s file" */
     int bit;                    /* in the outputs= word of a done-list's first line */
@@ -172,10 +172,11 @@ struct TrajIO {
     bool pbc = false;               /* FREESASA_GPU_FRAMES_PBC: every frame among the images its cell record implies (gpu_periodic.hip) */
     bool tri = false;               /* ... FREESASA_GPU_FRAMES_TRICLINIC beside it: the record decoded as a triclinic cell */
     /* per frame: total [1], per-atom areas [n]; runs with a topology: class sums [3], residue areas [6 R], selection areas [S];
-       with chain groups: every atom's area in its isolated group [n], and isolated, complex, buried per group [3 G] */
+       with chain groups: every atom's area in its isolated group [n], and isolated, complex, buried per group [3 G]; the volume
+       entries: the frame's volume [1] (gpu_volume.hip; it has no run statistics: no bit of the statistics word) */
     TrajOut out[N_OUT] = {{"totals", 0, FREESASA_GPU_STATS_TOTALS}, {"per-atom", 1, FREESASA_GPU_STATS_ATOMS}, {"isolated", 32, FREESASA_GPU_STATS_ISOLATED},
                           {"class-sums", 2, FREESASA_GPU_STATS_CLASSES}, {"residues", 4, FREESASA_GPU_STATS_RESIDUES},
-                          {"selections", 8, FREESASA_GPU_STATS_SELECTIONS}, {"groups", 16, FREESASA_GPU_STATS_GROUPS}};
+                          {"selections", 8, FREESASA_GPU_STATS_SELECTIONS}, {"groups", 16, FREESASA_GPU_STATS_GROUPS}, {"volumes", 64, 0}};
     /* run statistics (include/freesasa_gpu.h): the word; every shard's partial [4][W] at k * 4 W doubles of a host array or of
        the partials file; the merged result to the caller's array (memory form: the entry merges) or the statistics file */
     int stats = 0;
@@ -284,9 +285,9 @@ int stats_check(int stats, const TrajTopo *tp, bool has_sel, bool has_group, cha
 {
     if (stats & ~127) return set_err(err_out, err_len, "unknown bit in the statistics word");
     /* (the table's names and bits, without a TrajIO: nothing here allocates) */
-    static const char *const name[N_OUT] = {"totals", "per-atom", "isolated", "class-sums", "residues", "selections", "groups"};
+    static const char *const name[N_OUT] = {"totals", "per-atom", "isolated", "class-sums", "residues", "selections", "groups", "volumes"};
     static const int sbit[N_OUT] = {FREESASA_GPU_STATS_TOTALS, FREESASA_GPU_STATS_ATOMS, FREESASA_GPU_STATS_ISOLATED, FREESASA_GPU_STATS_CLASSES,
-                                    FREESASA_GPU_STATS_RESIDUES, FREESASA_GPU_STATS_SELECTIONS, FREESASA_GPU_STATS_GROUPS};
+                                    FREESASA_GPU_STATS_RESIDUES, FREESASA_GPU_STATS_SELECTIONS, FREESASA_GPU_STATS_GROUPS, 0};
     char msg[160];
     for (int k = 0; k < N_OUT; ++k) {
         if (!(stats & sbit[k])) continue;
@@ -449,10 +450,10 @@ struct TrajRun {
                             (!io.out[OUT_ISO].mem || host_pinned(io.out[OUT_ISO].mem));
     const size_t S = topo && topo->sel && (io.out[OUT_SEL].wanted() || io.sel_atoms || (io.stats & FREESASA_GPU_STATS_SELECTIONS)) ? (size_t)topo->n_sel : 0; /* selections computed */
     /* A shard's sums lie one behind the other in ONE block, cut to its nf frames: classes | residues | selection areas |
-       groups | selected atoms.  Output k's begin at x0[k] * nf doubles (k = N_OUT: the atom counts); xw doubles per frame hold it all. */
+       groups | volumes | selected atoms.  Output k's begin at x0[k] * nf doubles (k = N_OUT: the atom counts); xw doubles per frame hold it all. */
     size_t x0[N_OUT + 1] = {0, 0, 0}, xw;
     /* does the block of sums go to the host?  (not when its outputs are computed for their statistics alone) */
-    const bool sums_down = io.out[OUT_CLS].wanted() || io.out[OUT_RES].wanted() || io.out[OUT_SEL].wanted() || io.out[OUT_GRP].wanted() || io.sel_atoms;
+    const bool sums_down = io.out[OUT_CLS].wanted() || io.out[OUT_RES].wanted() || io.out[OUT_SEL].wanted() || io.out[OUT_GRP].wanted() || io.out[OUT_VOL].wanted() || io.sel_atoms;
     size_t sW = 0; /* run statistics: columns of a shard's partial; it lies behind a FULL shard's block of sums, at xw * FB doubles of c->h_gtot */
     const std::vector<double> tp = call_test_points(s.alg, s.resolution);
     /* a full shard as a batch: k n; with chain groups behind them FB n + f n_iso + gfirst[g] - and the same for the run's short
@@ -476,8 +477,8 @@ struct TrajRun {
     {
         batch_offsets(FB, offs);
         if (groups && (size_t)(s.n_frames % s.frames_per_batch)) batch_offsets((size_t)(s.n_frames % s.frames_per_batch), offs_last);
-        const size_t per[N_OUT] = {1, n, groups ? n : 0, topo ? (size_t)3 : 0, topo ? 6 * (size_t)topo->n_res : 0, S, 3 * G};
-        long long first[N_OUT];
+        const size_t per[N_OUT] = {1, n, groups ? n : 0, topo ? (size_t)3 : 0, topo ? 6 * (size_t)topo->n_res : 0, S, 3 * G, 1};
+        long long first[N_OUT] = {0};
         sW = stats_width(io.stats, s.n_atoms, topo, first);
         for (int k = 0; k < N_OUT; ++k) {
             /* computed: delivered, or its statistics asked for (the selections' and the groups' kernels write theirs whenever they run) */
@@ -888,6 +889,9 @@ int shard_compute(TrajRun &T, TrajLane &L, TrajShard &h)
                                              (const double *)((const char *)h.src + at), (const double *)((const char *)c->g_xyz.p + at),
                                              T.s.probe, T.s.resolution, T.s.alg == 1 ? T.tp.data() : nullptr, (double *)c->h_sasa.p,
                                              (double *)c->h_totals.p, nullptr)
+                 : out[OUT_VOL].per_frame /* (the volume entries: the batch with its exposed-point vectors kept, the frames' volumes into the block of sums) */
+                     ? volume_resident(c, (double *)c->h_xyz.p, (double *)c->h_radii.p, T.offs.data(), h.nf, T.s.probe, T.s.resolution, T.tp.data(),
+                                       (double *)c->h_sasa.p, nullptr, nullptr, nullptr, (double *)c->h_totals.p, (double *)c->h_gtot.p + T.x0[OUT_VOL] * nf)
                  : run_batch(c, T.s.alg == 0, (double *)c->h_xyz.p, (double *)c->h_radii.p, (T.groups && nf != T.FB ? T.offs_last : T.offs).data(),
                              (int)(nf * (1 + T.G)), T.s.probe, T.s.resolution, T.s.alg == 1 ? T.tp.data() : nullptr, (double *)c->h_sasa.p, nullptr,
                              (double *)c->h_totals.p);
@@ -1125,14 +1129,15 @@ extern "C" int freesasa_gpu_trajectory(const double *xyz_frames, const double *r
     return freesasa_gpu_trajectory_devices(xyz_frames, radii, n_atoms, n_frames, alg, probe, resolution, frames_per_batch, totals_out, sasa_out, &device, 1, err_out, err_len);
 }
 
-extern "C" int freesasa_gpu_trajectory_groups_stats(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
-                                                    int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
-                                                    const int32_t *group, int n_groups,
-                                                    int alg, double probe, int resolution, int frames_per_batch,
-                                                    double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
-                                                    double *sel_area_out, long long *sel_atoms_out, double *group_areas_out, double *iso_out,
-                                                    const int *devices, int n_devices,
-                                                    int stats, double *stats_out, double *partials_out, char *err_out, int err_len)
+/* the memory form with a topology: with or without chain groups, statistics, the frames' volumes (the entries below) */
+static int trajectory_mem_topo(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
+                               int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
+                               const int32_t *group, int n_groups,
+                               int alg, double probe, int resolution, int frames_per_batch,
+                               double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
+                               double *sel_area_out, long long *sel_atoms_out, double *group_areas_out, double *iso_out, double *volumes_out,
+                               const int *devices, int n_devices,
+                               int stats, double *stats_out, double *partials_out, char *err_out, int err_len)
 {
     if (err_out && err_len > 0) err_out[0] = 0;
     return guarded(err_out, err_len, [&]() -> int {
@@ -1149,11 +1154,54 @@ extern "C" int freesasa_gpu_trajectory_groups_stats(const double *xyz_frames, in
         if (traj_check_args(s, "n_frames must be > 0", err_out, err_len) || traj_shard_size(s, frame_atoms, err_out, err_len)) return -1;
         TrajIO io;
         io.mem_in = xyz_frames; io.sel_atoms = sel_atoms_out;
-        double *const mem[N_OUT] = {totals_out, sasa_out, iso_out, class_sums_out, residues_out, sel_area_out, group_areas_out};
+        double *const mem[N_OUT] = {totals_out, sasa_out, iso_out, class_sums_out, residues_out, sel_area_out, group_areas_out, volumes_out};
         for (int k = 0; k < N_OUT; ++k) io.out[k].mem = mem[k];
         io.stats = stats;
         return traj_run_mem(io, s, stats_out, partials_out, err_out, err_len);
     });
+}
+
+extern "C" int freesasa_gpu_trajectory_groups_stats(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
+                                                    int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
+                                                    const int32_t *group, int n_groups,
+                                                    int alg, double probe, int resolution, int frames_per_batch,
+                                                    double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
+                                                    double *sel_area_out, long long *sel_atoms_out, double *group_areas_out, double *iso_out,
+                                                    const int *devices, int n_devices,
+                                                    int stats, double *stats_out, double *partials_out, char *err_out, int err_len)
+{
+    return trajectory_mem_topo(xyz_frames, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups, alg, probe, resolution,
+                               frames_per_batch, totals_out, sasa_out, class_sums_out, residues_out, sel_area_out, sel_atoms_out, group_areas_out, iso_out,
+                               nullptr, devices, n_devices, stats, stats_out, partials_out, err_out, err_len);
+}
+
+/* what both volume entries refuse before a device is touched or a file opened: 0, or -1 with the message */
+static int volume_traj_check(int alg, int resolution, int frames_f32, const void *volumes, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (!volumes) return set_err(err_out, err_len, "null argument: the volumes have nowhere to go");
+    if (alg != 1) return set_err(err_out, err_len, "the volume is made of the Shrake-Rupley test points: Lee-Richards is not offered");
+    if (frames_f32 & (FREESASA_GPU_FRAMES_PBC | FREESASA_GPU_FRAMES_TRICLINIC))
+        return set_err(err_out, err_len, "bit 3 and bit 4 of frames_f32 (periodic images) are not offered with the volume: among periodic images the surface is not closed within the cell");
+    if (resolution > SR_CAP_POINTS_MAX) {
+        char msg[120];
+        snprintf(msg, sizeof msg, "the volume is offered up to %d test points (%d asked for)", SR_CAP_POINTS_MAX, resolution);
+        return set_err(err_out, err_len, msg);
+    }
+    return 0;
+}
+
+extern "C" int freesasa_gpu_trajectory_volume(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
+                                              int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
+                                              int alg, double probe, int resolution, int frames_per_batch,
+                                              double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
+                                              double *sel_area_out, long long *sel_atoms_out, double *volumes_out,
+                                              const int *devices, int n_devices, char *err_out, int err_len)
+{
+    if (volume_traj_check(alg, resolution, 0, volumes_out, err_out, err_len)) return -1;
+    return trajectory_mem_topo(xyz_frames, n_frames, batch, structure, frame_atoms, atom_index, sel, nullptr, 0, alg, probe, resolution,
+                               frames_per_batch, totals_out, sasa_out, class_sums_out, residues_out, sel_area_out, sel_atoms_out, nullptr, nullptr,
+                               volumes_out, devices, n_devices, 0, nullptr, nullptr, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_trajectory_groups(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
@@ -1411,7 +1459,7 @@ static int trajectory_file_topo(const char *frames_path, int frames_f32, long lo
                                 int alg, double probe, int resolution, int frames_per_batch,
                                 const char *totals_path, const char *sasa_path, const char *class_sums_path,
                                 const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
-                                const char *group_areas_path, const char *iso_path,
+                                const char *group_areas_path, const char *iso_path, const char *volumes_path,
                                 const char *done_path, long long max_new_shards, const int *devices, int n_devices,
                                 long long *frames_total_out, int stats, const char *stats_path, const char *partials_path, char *err_out, int err_len)
 {
@@ -1426,7 +1474,7 @@ static int trajectory_file_topo(const char *frames_path, int frames_f32, long lo
         TrajSpec s = {tp.radii, tp.n, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, &tp, max_new_shards};
         TrajIO io;
         io.sel_atoms = sel_atoms_out;
-        const char *const path[N_OUT] = {totals_path, sasa_path, iso_path, class_sums_path, residues_path, sel_area_path, group_areas_path};
+        const char *const path[N_OUT] = {totals_path, sasa_path, iso_path, class_sums_path, residues_path, sel_area_path, group_areas_path, volumes_path};
         for (int k = 0; k < N_OUT; ++k) io.out[k].path = path[k];
         io.stats = stats; io.stats_path = stats_path; io.parts_path = partials_path;
         return trajectory_file_run(frames_path, frames_f32, header_bytes, s, io, done_path, frames_total_out, err_out, err_len);
@@ -1454,7 +1502,7 @@ extern "C" int freesasa_gpu_trajectory_file_groups_stats(const char *frames_path
         return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) is not offered with chain groups: an isolated group among periodic images is not defined");
     return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,
                                 alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
-                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, done_path, max_new_shards, devices, n_devices,
+                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, done_path, max_new_shards, devices, n_devices,
                                 frames_total_out, stats, stats_path, partials_path, err_out, err_len);
 }
 
@@ -1476,7 +1524,7 @@ extern "C" int freesasa_gpu_trajectory_file_groups(const char *frames_path, int 
         return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) is not offered with chain groups: an isolated group among periodic images is not defined");
     return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,
                                 alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
-                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, done_path, max_new_shards, devices, n_devices,
+                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, done_path, max_new_shards, devices, n_devices,
                                 frames_total_out, 0, nullptr, nullptr, err_out, err_len);
 }
 
@@ -1491,7 +1539,24 @@ extern "C" int freesasa_gpu_trajectory_file_topology(const char *frames_path, in
 {
     return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, nullptr, 0,
                                 alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
-                                sel_area_path, sel_atoms_out, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
+                                sel_area_path, sel_atoms_out, nullptr, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
+                                frames_total_out, 0, nullptr, nullptr, err_out, err_len);
+}
+
+extern "C" int freesasa_gpu_trajectory_file_volume(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
+                                                   const freesasa_ingest_batch *batch, int structure,
+                                                   int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
+                                                   int alg, double probe, int resolution, int frames_per_batch,
+                                                   const char *totals_path, const char *sasa_path, const char *class_sums_path,
+                                                   const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
+                                                   const char *volumes_path,
+                                                   const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                                   long long *frames_total_out, char *err_out, int err_len)
+{
+    if (volume_traj_check(alg, resolution, frames_f32, volumes_path, err_out, err_len)) return -1;
+    return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, nullptr, 0,
+                                alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
+                                sel_area_path, sel_atoms_out, nullptr, nullptr, volumes_path, done_path, max_new_shards, devices, n_devices,
                                 frames_total_out, 0, nullptr, nullptr, err_out, err_len);
 }
 

@@ -130,7 +130,8 @@ extern "C" void freesasa_gpu_ctx_destroy(freesasa_gpu_ctx *c)
                      &c->h_xyz, &c->h_radii, &c->h_sasa, &c->h_counts, &c->h_totals, &c->h_group, &c->h_iso, &c->h_gtot,
                      &c->g_meta, &c->g_key, &c->g_count, &c->g_cursor, &c->g_xyz, &c->g_radii, &c->g_src, &c->g_sasa,
                      &c->g_gath, &c->g_tot, &c->g_tot2, &c->gi_tab, &c->gi_words, &c->gi_label,
-                     &c->p_meta, &c->p_ibase, &c->p_xyz, &c->p_radii, &c->p_sasa, &c->p_chunks, &c->p_part};
+                     &c->p_meta, &c->p_ibase, &c->p_xyz, &c->p_radii, &c->p_sasa, &c->p_chunks, &c->p_part,
+                     &c->v_counts, &c->v_evec, &c->v_vol, &c->v_origin, &c->v_volumes};
     for (DevBuf *b : all)
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : c->parse)
@@ -599,6 +600,15 @@ static int run_batch_once(freesasa_gpu_ctx *c, bool lr, const double *d_xyz, con
     }
 
     const bool sr_caps = !lr && c->captab_n > 0;
+    /* a volume (gpu_volume.hip: c->vol_evec) is made by the third arrangement's store phase alone: without its table - and,
+       below, for a launch sr_caps_shape sends to the second arrangement - the batch is refused, with the reason */
+    double *const evec = lr ? nullptr : c->vol_evec;
+    if (evec && !sr_caps) {
+        if (resolution > SR_CAP_POINTS_MAX) return ctx_fail(c, "the volume is offered up to %d test points (%d asked for)", SR_CAP_POINTS_MAX, resolution);
+        const char *e = getenv("FREESASA_AMD_SR_CAPS");
+        if (e && atoi(e) == 0 && !strchr(e, ',')) return ctx_fail(c, "the volume needs the cap-mask kernel, which FREESASA_AMD_SR_CAPS=0 switches off");
+        return ctx_fail(c, "the volume needs unit test points: these are not unit vectors");
+    }
     TileCfg cfg = choose_cfg(resolution, lr, c->hint_res[hi] == resolution ? c->hint_pool[hi] : 0, sr_caps, c->hint_res[hi] == resolution ? c->hint_ta[hi] : 0);
     if (const char *e = getenv("FREESASA_AMD_CFG")) { /* tuning aid: "B,TA,pool,ds" */
         int b = 0, t = 0, pl = 0, d = 0;
@@ -643,6 +653,9 @@ static int run_batch_once(freesasa_gpu_ctx *c, bool lr, const double *d_xyz, con
     if (!lr) {
         ta.unit_pts = (const double *)c->unit_pts.p;
         if (sr_caps) { ta.captab = c->captab.p; ta.cap_n = c->captab_n; ta.cap_l = c->captab_l; }
+        if (evec && !sr_caps_shape(cfg, ta, false))
+            return ctx_fail(c, "the volume needs the cap-mask kernel, and this tile shape runs the second arrangement (%d records per atom, at most 128; %s survivor table)",
+                            cfg.cap_idx, cfg.tab ? "with a" : "without a");
     }
 
     /* workgroups loop over tiles (w, w + grid, ...): ~150k workgroups measured ~2% better than
@@ -655,7 +668,7 @@ static int run_batch_once(freesasa_gpu_ctx *c, bool lr, const double *d_xyz, con
     }
     hipError_t le;
     const bool bucket = lr && c->hint_bucket && c->hint_res[0] == resolution;
-    le = lr ? kl_lr_tile(0, cfg, ta, grid_main, cfg.lds, st, bucket) : kl_sr_tile(0, cfg, ta, grid_main, cfg.lds, st);
+    le = lr ? kl_lr_tile(0, cfg, ta, grid_main, cfg.lds, st, bucket) : kl_sr_tile(0, cfg, ta, grid_main, cfg.lds, st, evec);
     if (le != hipSuccess) return ctx_fail(c, "tile kernel launch failed: %s", hipGetErrorString(le));
     if (c->timing) HIP_TRY(c, hipEventRecord(ctx_ev(c)[2], st));
 
@@ -670,7 +683,7 @@ static int run_batch_once(freesasa_gpu_ctx *c, bool lr, const double *d_xyz, con
         tm.ovf_tiles = (int *)c->ovf_tiles2.p;
         tm.ovf_count = (int *)c->status.p + ST_OVF2_TILES;
         const int grid_mid = n_tiles < SASA_MID_BLOCKS ? n_tiles : SASA_MID_BLOCKS;
-        le = lr ? kl_lr_tile(1, mc, tm, grid_mid, mc.lds, st, bucket) : kl_sr_tile(1, mc, tm, grid_mid, mc.lds, st);
+        le = lr ? kl_lr_tile(1, mc, tm, grid_mid, mc.lds, st, bucket) : kl_sr_tile(1, mc, tm, grid_mid, mc.lds, st, evec);
         if (le != hipSuccess) return ctx_fail(c, "second tile launch failed: %s", hipGetErrorString(le));
     }
     /* third launch: whatever is left (pathological densities), lists in a global slab */
@@ -717,6 +730,16 @@ static int run_batch_once(freesasa_gpu_ctx *c, bool lr, const double *d_xyz, con
         if (hipEventElapsedTime(&ms, ctx_ev(c)[0], ctx_ev(c)[3]) == hipSuccess) S.ms_total = ms;
     }
     if (rcs) return rcs;
+    /* a volume: the tiles the main launch handed on were redone by the second launch - the third arrangement too, if
+       sr_caps_shape says so - and what that handed on by the last launch, which never is: their atoms have no vectors */
+    if (evec) {
+        const TileCfg mc = mid_cfg(cfg, lr);
+        TileArgs tm = ta;
+        tm.cap_idx = mc.cap_idx;
+        if (status_h[ST_OVF2_TILES] > 0 || (status_h[ST_OVF_TILES] > 0 && !sr_caps_shape(mc, tm, false)))
+            return ctx_fail(c, "the volume needs the cap-mask kernel, and %d tiles of this batch have neighbour lists beyond its limits (more than 128 records per atom): they ran the second arrangement",
+                            status_h[ST_OVF2_TILES] > 0 ? status_h[ST_OVF2_TILES] : status_h[ST_OVF_TILES]);
+    }
     if (total_cells + total_cells / 32 > c->cells_hint) c->cells_hint = total_cells + total_cells / 32;
     kl_dump_phase_clocks();
     /* learn the pool size for the next batch of this kind (trajectory frames, sweeps) */

@@ -623,6 +623,45 @@ __global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(CAPS ? SR_CAP
     tile_report_flush(a, tid, wg_max_nn);
 }
 
+/* ... and the third arrangement with the volume's vectors (gpu_volume.hip): k_sr_tile<B, false, TIER, true>'s phases, the store
+   phase the one that also sums every atom's exposed unit points into evec [3 n_atoms] (sr_caps_store<true>).  A kernel of its
+   own with the vectors' place as an argument of its own: TileArgs, and with it every build of k_sr_tile, is what it was (a
+   member more moved the kernel argument behind the struct and with it the prologue and the scalar registers of every build
+   that takes one - measured on the MI355X, +0.02 ms on the 2.93 ms of the PDB entries at 100 points - and the body as a
+   function shared by both kernels was compiled to other code than the kernel it came from). */
+template <int B, int TIER>
+__global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(SR_CAPS_WPE, SR_CAPS_WPE))) void k_sr_tile_vol(TileArgs a, int items, double *evec)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x;
+    PIPE_GATE(a.status);
+    TileMem m = tile_carve<false>(a, smem, items, B, blockIdx.x);
+    const int n_work = a.work_tiles ? *a.work_count : ((a.n_tiles + 7) >> 3) << 3;
+    int wg_max_nn = 0;
+    for (int w = blockIdx.x; w < n_work; w += gridDim.x) {
+        const int tile = a.work_tiles ? a.work_tiles[w] : xcd_tile(w, a.n_tiles);
+        if (tile >= a.n_tiles) continue;
+        sr_phase_load(a, m, tile, tid, B);
+        sr_caps_clear(a, m, tile, tid, B);
+        __syncthreads();
+        sr_phase_neighbors(a, m, tile, tid, B);
+        __syncthreads();
+        sr_caps_lists(a, m, tid);
+        __syncthreads();
+        sr_report<false>(a, m, tile, tid, wg_max_nn);
+        SrCapRegs regs;
+        sr_caps_lookup_pass(a, m, tid, B, regs);
+        __syncthreads();
+        sr_caps_todo_pass(a, m, tid, B, items, regs);
+        __syncthreads();
+        sr_caps_exact(a, m, tid, B, items);
+        __syncthreads();
+        sr_caps_store<true>(a, m, tile, tid, evec);
+        __syncthreads();
+    }
+    tile_report_flush(a, tid, wg_max_nn);
+}
+
 /* ------------------------------------------------------------------ launchers (engine_internal.h) */
 
 hipError_t kl_lr2_mid(int grid, size_t lds, hipStream_t st, const Lr2Args &la)
@@ -654,11 +693,22 @@ static hipError_t launch_lr(const TileCfg &c, const TileArgs &t, int grid, size_
     return hipGetLastError();
 }
 template <bool GLOBAL, int TIER>
-static hipError_t launch_sr(const TileCfg &c, const TileArgs &t, int grid, size_t lds, hipStream_t s)
+static hipError_t launch_sr(const TileCfg &c, const TileArgs &t, int grid, size_t lds, hipStream_t s, double *evec)
 {
     if constexpr (!GLOBAL) {
-        /* the third arrangement (sr_caps.h) where its table exists and a wave's lanes hold an atom's list (C <= 128) */
-        if (t.captab && t.tab && t.n_res <= SR_CAP_POINTS_MAX && sr_order_in_wave(c.cap_idx) && c.B >= 64) {
+        /* the third arrangement (sr_caps.h) where its table exists and a wave's lanes hold an atom's list (C <= 128):
+           sr_caps_shape; with evec the builds whose store phase makes the volume's vectors */
+        if (sr_caps_shape(c, t, false)) {
+            if (evec) {
+                if (c.B == 256)
+                    hipLaunchKernelGGL((k_sr_tile_vol<256, TIER>), dim3(grid), dim3(256), lds, s, t, c.items, evec);
+                else if (c.B == 128)
+                    hipLaunchKernelGGL((k_sr_tile_vol<128, TIER>), dim3(grid), dim3(128), lds, s, t, c.items, evec);
+                else if (c.B == 64)
+                    hipLaunchKernelGGL((k_sr_tile_vol<64, TIER>), dim3(grid), dim3(64), lds, s, t, c.items, evec);
+                else return hipErrorInvalidValue;
+                return hipGetLastError();
+            }
             if (c.B == 256)
                 hipLaunchKernelGGL((k_sr_tile<256, false, TIER, true>), dim3(grid), dim3(256), lds, s, t, c.items);
             else if (c.B == 128)
@@ -689,7 +739,9 @@ static void allow_large_lds()
                              (const void *)k_sr_tile<256, false, 0>, (const void *)k_sr_tile<128, false, 0>, (const void *)k_sr_tile<64, false, 0>,
                              (const void *)k_sr_tile<256, false, 1>, (const void *)k_sr_tile<128, false, 1>, (const void *)k_sr_tile<64, false, 1>,
                              (const void *)k_sr_tile<256, false, 0, true>, (const void *)k_sr_tile<128, false, 0, true>, (const void *)k_sr_tile<64, false, 0, true>,
-                             (const void *)k_sr_tile<256, false, 1, true>, (const void *)k_sr_tile<128, false, 1, true>, (const void *)k_sr_tile<64, false, 1, true>};
+                             (const void *)k_sr_tile<256, false, 1, true>, (const void *)k_sr_tile<128, false, 1, true>, (const void *)k_sr_tile<64, false, 1, true>,
+                             (const void *)k_sr_tile_vol<256, 0>, (const void *)k_sr_tile_vol<128, 0>, (const void *)k_sr_tile_vol<64, 0>,
+                             (const void *)k_sr_tile_vol<256, 1>, (const void *)k_sr_tile_vol<128, 1>, (const void *)k_sr_tile_vol<64, 1>};
         for (const void *fn : fns) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
 }
@@ -701,12 +753,12 @@ hipError_t kl_lr_tile(int tier, const TileCfg &c, const TileArgs &t, int grid, s
     if (tier == 1) return launch_lr<false, 1>(c, t, grid, lds, st, bucket);
     return launch_lr<true, 2>(c, t, grid, lds, st, false);
 }
-hipError_t kl_sr_tile(int tier, const TileCfg &c, const TileArgs &t, int grid, size_t lds, hipStream_t st)
+hipError_t kl_sr_tile(int tier, const TileCfg &c, const TileArgs &t, int grid, size_t lds, hipStream_t st, double *evec)
 {
     allow_large_lds();
-    if (tier == 0) return launch_sr<false, 0>(c, t, grid, lds, st);
-    if (tier == 1) return launch_sr<false, 1>(c, t, grid, lds, st);
-    return launch_sr<true, 2>(c, t, grid, lds, st);
+    if (tier == 0) return launch_sr<false, 0>(c, t, grid, lds, st, evec);
+    if (tier == 1) return launch_sr<false, 1>(c, t, grid, lds, st, evec);
+    return launch_sr<true, 2>(c, t, grid, lds, st, nullptr); /* (the slab launch: the second arrangement, no vectors) */
 }
 
 hipError_t kl_prep_fused(const PipeArgs &pa, hipStream_t st)
@@ -733,6 +785,29 @@ hipError_t kl_totals(const PipeArgs &pa, int n_chunks, int n_structs, const doub
 {
     hipLaunchKernelGGL(k_totals_chunks, dim3(n_chunks), dim3(SASA_TOT_B), 0, st, pa, d_sasa, bpart);
     hipLaunchKernelGGL(k_totals_structs, dim3((n_structs + 255) / 256), dim3(256), 0, st, pa, (const double *)bpart, d_totals);
+    return hipGetLastError();
+}
+
+/* molecular volume (vol_kernels.h): the structures' origins (one workgroup per structure), the atoms' terms (one thread per atom) */
+__global__ __launch_bounds__(SASA_TOT_B) void k_vol_origin(VolArgs a)
+{
+    __shared__ double part[6 * SASA_TOT_B];
+    vol_origin_phase0(a, part, blockIdx.x, threadIdx.x);
+    __syncthreads();
+    vol_origin_phase1(a, part, blockIdx.x, threadIdx.x);
+}
+__global__ __launch_bounds__(VOL_B) void k_vol_atom(VolArgs a)
+{
+    vol_atom(a, (int64_t)blockIdx.x * VOL_B + threadIdx.x);
+}
+hipError_t kl_vol_origin(const VolArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_vol_origin, dim3((unsigned)a.n_structs), dim3(SASA_TOT_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_vol_atom(const VolArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_vol_atom, dim3((unsigned)((a.n_atoms + VOL_B - 1) / VOL_B)), dim3(VOL_B), 0, st, a);
     return hipGetLastError();
 }
 hipError_t kl_segment_sums(const double *d_sasa, const int64_t *d_seg, int n_segs, bool short_segments, double *d_out, hipStream_t st)

@@ -2022,6 +2022,18 @@ struct TileCfg {
     size_t lds;
 };
 
+/* Does an S&R launch of this shape run the third arrangement (sr_caps.h)?  The one place that says so: launch_sr
+   (gpu_kernels.hip) dispatches on it, and the engine refuses a volume - which only that arrangement's store phase makes -
+   for a launch it sends to the second.  slab: the last launch, its lists in global memory.
+   (The volume's vectors are NOT a member of TileArgs: the struct is passed by value, one pointer more moves the kernel
+   argument behind it and with that changed the prologue and the scalar register allocation of every build that takes it -
+   measured on the MI355X: +0.02 ms on the 2.93 ms of the PDB entries at 100 points, outside the parent's run-to-run spread.
+   The builds that make them take the pointer as an argument of their own: k_sr_tile_vol, gpu_kernels.hip.) */
+SASA_HD bool sr_caps_shape(const TileCfg &c, const TileArgs &t, bool slab)
+{
+    return !slab && t.captab && t.tab && t.n_res <= SR_CAP_POINTS_MAX && sr_order_in_wave(c.cap_idx) && c.B >= 64;
+}
+
 #define SR_CAP_DEFAULT 64 /* S&R: records per atom's segment (main launch) without history */
 #define SR_CAP_MIN 32
 #define SR_CAP_MAX 112

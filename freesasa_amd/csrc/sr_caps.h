@@ -275,23 +275,45 @@ SASA_D void sr_caps_exact(const TileArgs &a, TileMem &m, int tid, int B, int ite
     }
 }
 
-SASA_D void sr_caps_store(const TileArgs &a, TileMem &m, int tile, int tid)
+/* VOL (the volume's builds, k_sr_tile_vol; evec [3 n_atoms], original order): beside the area, E_i = the sum of the atom's exposed unit points, taken in ascending
+   point order from (0, 0, 0), component by component - the mask never leaves the LDS, so this is the only place that can
+   make it (vol_kernels.h has the definition of the volume built on it).  A tile that overflowed (flags[0]) stores nothing
+   here and is redone by a later launch: every atom's vector is written exactly once.  The builds without VOL are the
+   builds they were. */
+template <bool VOL = false>
+SASA_D void sr_caps_store(const TileArgs &a, TileMem &m, int tile, int tid, double *evec = nullptr)
 {
     if (m.flags[0]) return;
     const int na = tile_atoms(a, tile);
     if (tid < na) {
         const unsigned *V = sr_caps_cov(a, m, tid);
         int covered = 0;
+        unsigned dw[SR_CAP_WORDS];
         for (int w = 0; w < SR_CAP_WORDS; ++w) {
             unsigned d = V[w];
             for (int c = 0; c < SR_CAP_COPIES; ++c) d |= sr_caps_def(m, tid, c)[w];
             covered += __builtin_popcount(d);
+            dw[w] = d;
         }
         const double ri = m.aR[tid];
         const int n_surface = a.n_res - covered;
         const int i = m.aexp[tid]; /* (sr_caps_clear) */
         a.sasa[i] = (4.0 * SASA_PI * ri * ri * n_surface) / a.n_res; /* ref: src/sasa_sr.c:337 */
         if (a.counts) a.counts[i] = n_surface;
+        if constexpr (VOL) {
+            /* (a point per trip.  Four points per trip - their twelve loads issued together, the adds still in point order -
+               was measured on the MI355X and gained nothing: 10.14 against 9.98 ms per step of the coil batch,
+               profiles/volume_bench.md) */
+            const double *upts = a.unit_pts;
+            double ex = 0, ey = 0, ez = 0;
+#pragma unroll 1
+            for (int w = 0; w < SR_CAP_WORDS; ++w) /* (a wave runs as many trips as its most exposed atom has points: <= n_res) */
+                for (unsigned e = ~dw[w] & sr_cap_full_word(a.n_res, w); e; e &= e - 1) {
+                    const int k = 32 * w + __builtin_ctz(e);
+                    ex += upts[3 * k]; ey += upts[3 * k + 1]; ez += upts[3 * k + 2];
+                }
+            evec[3 * (size_t)i] = ex; evec[3 * (size_t)i + 1] = ey; evec[3 * (size_t)i + 2] = ez;
+        } else (void)dw;
     }
 }
 

@@ -968,6 +968,71 @@ int freesasa_gpu_calc_groups(const double *xyz, const double *radii, const int64
                              int resolution, double *sasa_out, double *iso_out, double *totals_out,
                              double *group_totals_out, int device, char *err_out, int err_len);
 
+/* MOLECULAR VOLUME: the volume enclosed by the solvent-accessible surface of every structure, made of the Shrake-Rupley test
+   points by the divergence theorem - what `gmx sasa -tv` prints per frame, in the same formulation:
+       V = (1/3) sum_i a_i ( (x_i - o) . E_i + R_i n_i ),   E_i = sum over atom i's exposed points of u_k,  a_i = 4 pi R_i^2 / N
+   The definition (csrc/vol_kernels.h; tests/volume_ref.py restates it in numpy).  fp64, every operation rounded on its own.
+   Structure s, atoms b .. e-1, probe p, the N points u_k of freesasa_gpu_test_points(N):
+     radius     R_i = r_i + p
+     exposure   what the engine decides for the areas: t = u_k * R_i; t += x_i; covered iff for some other atom j
+                dx^2 + dy^2 + dz^2 <= R_j * R_j.  n_i is the `counts` output.
+     E_i        from (0, 0, 0); for k = 0 .. N-1 ascending, if point k is exposed, += u_k component by component: evec[3i .. 3i+2]
+     origin     per axis o_s = (min_i x_i + max_i x_i) * 0.5 over the structure's atoms (one atom: o = x exactly)
+     per atom   a = (4.0 * PI * R_i * R_i) / N;  d = x_i - o_s;  t = d_x * E_x + d_y * E_y + d_z * E_z, left to right;
+                v_i = (a * (t + R_i * (double) n_i)) / 3.0
+     volume     V_s = the engine's totals kernels over v (the sum that makes d_totals of the areas): deterministic, independent
+                of launch shape, tile shape, device list, shard cut and restarts.  A structure without atoms: 0.
+   A lone sphere gives 4/3 pi R^3 to the last bits at any N; two overlapping spheres of 3 A whose centres are 3 A apart along x:
+   -0.9 % at 100 points, -0.2 % at 1000, +0.01 % at 5000 against the analytic union (tests/test_volume.py).
+   The batch goes through the engine ONCE: d_sasa, d_counts and d_totals are bit for bit freesasa_gpu_sr_batch_dev's with the
+   points of freesasa_gpu_test_points(n_points); E_i is one more output of the tile kernel's store phase (the mask of covered
+   points never leaves the LDS), the rest two small kernels and the totals behind it.
+   freesasa_gpu_sr_volume_dev: arrays on the device, offsets on the host; synchronous; batches in flight on the context are
+   collected first.  d_counts [n], d_evec [3 n], d_vol [n] and d_totals [n_structs] may be NULL (the context keeps scratch of
+   its own for the ones it needs); d_volumes [n_structs] is required.
+   REFUSED, -1 with a message that names the reason, nothing returned: more than 128 test points; test points that are not
+   unit vectors; FREESASA_AMD_SR_CAPS=0; a launch, or tiles of a batch, whose neighbour lists are beyond the cap-mask
+   kernel's limits (more than 128 records per atom) and run the engine's second arrangement.  A volume made any other way
+   is never returned.  The context stays usable.  Argument errors (NULL, n_points <= 0, bad offsets, an empty batch): -1
+   with a message before a device is touched.
+   Not offered: density (mass over V: the loader does no arithmetic and the batch holds no masses); Lee-Richards volume;
+   more than 128 points; volume among periodic images; volume in the plain (radii, n_atoms) trajectory entries, the group
+   entries and the file and cache sweeps; run statistics of the volume column (per-frame volumes are 8 bytes a frame, and
+   freesasa_gpu_traj_stats_merge is exported for block averages); Connolly dot output (`gmx sasa -q`). */
+int freesasa_gpu_sr_volume_dev(freesasa_gpu_ctx *ctx, const double *d_xyz, const double *d_radii, const int64_t *offsets,
+                               int n_structs, double probe_radius, int n_points, double *d_sasa, int *d_counts, double *d_evec,
+                               double *d_vol, double *d_totals, double *d_volumes);
+/* The same on host arrays, on a pooled per-thread context like freesasa_gpu_calc_batch.  counts_out, evec_out, vol_out and
+   totals_out may be NULL; sasa_out [n] and volumes_out [n_structs] are required.  Returns 0 / -1 with err_out. */
+int freesasa_gpu_calc_volume(const double *xyz, const double *radii, const int64_t *offsets, int n_structs, double probe_radius,
+                             int n_points, double *sasa_out, int *counts_out, double *evec_out, double *vol_out,
+                             double *totals_out, double *volumes_out, int device, char *err_out, int err_len);
+/* ... and per frame of a trajectory: freesasa_gpu_trajectory_topology / freesasa_gpu_trajectory_file_topology with one more
+   output behind sel_atoms_out
+     volumes     1 per frame          (8 f)            V of the frame's topology atoms: bit for bit volumes_out of
+                                                       freesasa_gpu_calc_volume on the frame taken as a structure of its own
+   (memory form: volumes_out [n_frames]; file form: volumes_path, raw fp64, frame f at byte 8 f; required).  The solute index,
+   residues, class sums and selections are what they are there, every other output byte for byte that entry's; all file formats,
+   fp32 input, fp32 per-atom output and any device list work unchanged.  alg must be Shrake-Rupley (1).  The done-list's first
+   line names the volume output (64 in outputs=): a list of a run without it and a list of a run with it refuse each other.
+   -1 with a message before a device is touched or a file opened: volumes NULL, Lee-Richards, more than 128 points, bit 3 or 4
+   of frames_f32 (among periodic images the surface is not closed within the cell). */
+int freesasa_gpu_trajectory_volume(const double *xyz_frames, int n_frames, const struct freesasa_ingest_batch *batch, int structure,
+                                   int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
+                                   int alg, double probe_radius, int resolution, int frames_per_batch,
+                                   double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
+                                   double *sel_area_out, long long *sel_atoms_out, double *volumes_out,
+                                   const int *devices, int n_devices, char *err, int err_len);
+int freesasa_gpu_trajectory_file_volume(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
+                                        const struct freesasa_ingest_batch *batch, int structure,
+                                        int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
+                                        int alg, double probe_radius, int resolution, int frames_per_batch,
+                                        const char *totals_path, const char *sasa_path, const char *class_sums_path,
+                                        const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
+                                        const char *volumes_path,
+                                        const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                        long long *frames_total_out, char *err, int err_len);
+
 #ifdef __cplusplus
 }
 #endif
