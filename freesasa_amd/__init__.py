@@ -145,6 +145,8 @@ def lib():
                                                         C.c_int, C.c_int, C.c_longlong, C.c_char_p, C.c_int]
         L.freesasa_gpu_lr_neighbors_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _lp, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int]
         L.freesasa_gpu_arc_union_dev.argtypes = [C.c_void_p, _dp, _ip, C.c_int, _dp]
+        L.freesasa_gpu_xtc_decode_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.freesasa_gpu_xtc_decode_check.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
         L.freesasa_gpu_release_pool.argtypes = []
         L.freesasa_gpu_release_pool.restype = None
         L.freesasa_gpu_test_fail_after.argtypes = [C.c_int]
@@ -1468,6 +1470,21 @@ class GpuContext:
                                             out.ctypes.data_as(_dp)):
             raise RuntimeError("freesasa_gpu_arc_union_dev: " + self.error())
         return out
+
+    def xtc_decode(self, file_bytes, n_frames, n_atoms):
+        """Test hook: the XTC decode kernels over n_frames whole frames at the beginning of file_bytes -> (records: per frame the
+        [groups, 4] int32 array of (bit, atom, run, smallidx), status [n_frames], xyz [n_frames, n_atoms, 3] float32 in Angstrom,
+        NaN where no thread wrote).  ValueError for an argument or a header that is refused."""
+        n_frames, n_atoms = int(n_frames), int(n_atoms)
+        slots = max(n_frames, 0) * max(n_atoms, 0)
+        rec = np.zeros((slots, 4), dtype=np.int32)
+        count = np.full((max(n_frames, 0), 2), -1, dtype=np.int32)
+        out = np.full((slots, 3), np.nan, dtype=np.float32)
+        data = bytes(file_bytes)
+        if lib().freesasa_gpu_xtc_decode_dev(self._h, data, len(data), n_frames, n_atoms, rec.ctypes.data, count.ctypes.data, out.ctypes.data):
+            raise ValueError("freesasa_gpu_xtc_decode_dev: " + self.error())
+        rec = rec.reshape(n_frames, n_atoms, 4)
+        return [rec[f, :max(int(count[f, 0]), 0)] for f in range(n_frames)], count[:, 1].copy(), out.reshape(n_frames, n_atoms, 3)
 
     def segment_sums(self, d_sasa, seg_offsets, d_out):
         seg = np.ascontiguousarray(seg_offsets, dtype=np.int64)

@@ -816,6 +816,17 @@ int shard_read(TrajRun &T, freesasa_gpu_ctx *c, TrajShard &h)
     return 0;
 }
 
+/* The decode of the XTC frames that lie on the device with their descriptors, for the driver's shards and for the test hook
+   freesasa_gpu_xtc_decode_dev alike: scan, then unpack, on the context's stream, then the frames' (groups, status) pairs down
+   to `status` (page-locked, 2 n_frames words); returns when they are there. */
+int xtc_decode(freesasa_gpu_ctx *c, const sasa::XtcArgs &xa, int32_t *status)
+{
+    if (kl_xtc_scan(xa, c->stream) != hipSuccess || kl_xtc_unpack(xa, c->stream) != hipSuccess) return ctx_fail(c, "XTC decode launch failed");
+    if (hipMemcpyAsync(status, xa.count, 8 * (size_t)xa.n_frames, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
+        return ctx_fail(c, "could not read the status of the XTC frames");
+    return 0;
+}
+
 /* ... to the device, into the compact fp64 frames the engine reads (c->h_xyz): as they are, widened, or gathered; a DCD file's
    bytes as they are, de-planarized (and gathered, widened, byte-swapped) by one kernel; a NetCDF file's likewise */
 int shard_upload(TrajRun &T, TrajLane &L, const TrajShard &h)
@@ -837,9 +848,7 @@ int shard_upload(TrajRun &T, TrajLane &L, const TrajShard &h)
         d_in = T.gather ? (void *)(g + T.xtc_f32_at(h.in_bytes, nf)) : c->h_counts.p;
         const sasa::XtcArgs xa = {(int)T.fa, h.nf, (const uint32_t *)g, (const freesasa_gpu_xtc_frame *)(g + T.xtc_desc_at(h.in_bytes, nf)),
                                   (sasa::XtcRec *)(g + T.xtc_rec_at(h.in_bytes, nf)), (int32_t *)(g + T.xtc_count_at(h.in_bytes, nf)), (float *)d_in};
-        if (kl_xtc_scan(xa, c->stream) != hipSuccess || kl_xtc_unpack(xa, c->stream) != hipSuccess) return ctx_fail(c, "XTC decode launch failed");
-        if (hipMemcpyAsync(status, xa.count, 8 * nf, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
-            return ctx_fail(c, "could not read the status of the XTC frames");
+        if (xtc_decode(c, xa, status)) return -1;
         for (size_t f = 0; f < nf; ++f)
             if (const int st = status[2 * f + 1])
                 return ctx_fail(c, "frame %lld of the XTC file is damaged: %s", h.f0 + (long long)f,
@@ -1093,6 +1102,69 @@ int traj_run_mem(TrajIO &io, const TrajSpec &s, double *stats_out, double *parti
 }
 
 } /* namespace */
+
+/* ------------------------------------------------------------------ test hook: the XTC decode on its own (include/freesasa_gpu.h) */
+
+/* what freesasa_gpu_xtc_decode_dev refuses before it touches a device: host only */
+extern "C" int freesasa_gpu_xtc_decode_check(const void *bytes, long long len, int n_frames, int n_atoms, const int32_t *rec, const int32_t *count,
+                                             const float *out, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (!bytes || !rec || !count || !out) return set_err(err_out, err_len, "xtc_decode: null argument");
+    if (n_frames < 1) return set_err(err_out, err_len, "xtc_decode: n_frames must be at least 1");
+    if (n_atoms < 1) return set_err(err_out, err_len, "xtc_decode: n_atoms must be at least 1");
+    if (len < 1) return set_err(err_out, err_len, "xtc_decode: len must be at least 1");
+    if ((long long)n_frames * n_atoms > 0x7fffffffLL) return set_err(err_out, err_len, "xtc_decode: n_frames * n_atoms does not fit an int");
+    return 0;
+}
+
+extern "C" int freesasa_gpu_xtc_decode_dev(freesasa_gpu_ctx *c, const void *bytes, long long len, int n_frames, int n_atoms, int32_t *rec,
+                                           int32_t *count, float *out)
+{
+    if (!c) return -1;
+    return guarded_ctx(c, [&]() -> int {
+    c->err[0] = 0;
+    if (freesasa_gpu_xtc_decode_check(bytes, len, n_frames, n_atoms, rec, count, out, c->err, (int)sizeof c->err)) return -1;
+    if (freesasa_gpu_wait(c)) return -1; /* (batches submitted asynchronously come first, as for every synchronous entry) */
+    /* on the device, every part at a multiple of 8: the bytes | one descriptor per frame | (groups, status) per frame | the
+       group records (at a multiple of 16) | the fp32 frames; in the staging: the bytes | the descriptors | where the status comes down to */
+    const size_t nf = (size_t)n_frames, slots = nf * (size_t)n_atoms, in_bytes = ((size_t)len + 7) & ~(size_t)7;
+    const size_t desc_at = in_bytes, count_at = desc_at + sizeof(freesasa_gpu_xtc_frame) * nf, rec_at = (count_at + 8 * nf + 15) & ~(size_t)15;
+    const size_t out_at = rec_at + sizeof(sasa::XtcRec) * slots;
+    if (ensure_pinned(c, &c->stage_in, &c->stage_in_cap, count_at + 8 * nf)) return -1;
+    char *stage = (char *)c->stage_in;
+    memcpy(stage, bytes, (size_t)len);
+    memset(stage + len, 0, in_bytes - (size_t)len);
+    freesasa_gpu_xtc_frame *desc = (freesasa_gpu_xtc_frame *)(stage + desc_at);
+    long long at = 0;
+    for (int f = 0; f < n_frames; ++f) {
+        char why[200];
+        long long frame_bytes = 0;
+        if (freesasa_gpu_xtc_frame_desc(stage + at, len - at, n_atoms, at + FREESASA_GPU_XTC_HEADER, &desc[f], &frame_bytes, why, (int)sizeof why))
+            return ctx_fail(c, "frame %d of the XTC bytes: %s", f, why);
+        at += frame_bytes;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (ensure(c, c->g_xyz, out_at + 12 * slots)) return -1;
+    char *g = (char *)c->g_xyz.p;
+    const sasa::XtcArgs xa = {n_atoms, n_frames, (const uint32_t *)g, (const freesasa_gpu_xtc_frame *)(g + desc_at), (sasa::XtcRec *)(g + rec_at),
+                              (int32_t *)(g + count_at), (float *)(g + out_at)};
+    HIP_TRY(c, hipMemcpyAsync(g, stage, count_at, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(xa.count, 0xff, 8 * nf, c->stream));
+    HIP_TRY(c, hipMemsetAsync(xa.rec, 0, sizeof(sasa::XtcRec) * slots, c->stream));
+    HIP_TRY(c, hipMemsetAsync(xa.out, 0xff, 12 * slots, c->stream));
+    int32_t *status = (int32_t *)(stage + count_at);
+    int rc = xtc_decode(c, xa, status);
+    if (!rc && (hipMemcpyAsync(rec, xa.rec, sizeof(sasa::XtcRec) * slots, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                hipMemcpyAsync(out, xa.out, 12 * slots, hipMemcpyDeviceToHost, c->stream) != hipSuccess))
+        rc = ctx_fail(c, "could not read the XTC records and frames back");
+    /* (nothing is left running on the stream, whatever failed) */
+    if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = ctx_fail(c, "could not read the XTC records and frames back");
+    if (rc) return -1;
+    memcpy(count, status, 8 * nf);
+    return 0;
+    });
+}
 
 /* ------------------------------------------------------------------ entry points: trajectories */
 

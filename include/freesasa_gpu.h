@@ -195,6 +195,25 @@ int freesasa_gpu_test_node_cpus(const char *sysfs_root, const char *pci_address,
 int freesasa_gpu_lr_neighbors_dev(freesasa_gpu_ctx *ctx, const double *d_xyz, const double *d_radii, const int64_t *offsets,
                                   int n_structs, double probe_radius, int *d_nn, int *d_nb, int nb_cap);
 int freesasa_gpu_arc_union_dev(freesasa_gpu_ctx *ctx, const double *arcs, const int *first, int n_sets, double *out);
+/* Test hook: the two XTC decode kernels (xtc_scan, xtc_unpack: "GROMACS XTC input" below) run on the device on their own, by the
+   launches the file drivers make for a shard.  Host arrays: `bytes` is n_frames whole frames of n_atoms atoms, one behind the
+   other, as a file holds them (len bytes); their descriptors are made as the drivers make them (freesasa_gpu_xtc_frame_desc, the
+   stream at the frame's byte + FREESASA_GPU_XTC_HEADER).  rec [n_frames * n_atoms * 4]: per frame and group (bit offset, first
+   atom, run, smallidx), zero where the scan wrote none; count [n_frames * 2]: per frame (groups, status; 0 is good, the bits are
+   xtc_kernels.h's XTC_ST_*); out [n_frames * n_atoms * 3]: fp32 Angstrom, all-ones bytes (NaN) where no thread wrote.  Returns 0,
+   or -1 with the context's error text: "frame K of the XTC bytes: <the host's reason>" for a header the host refuses, and - before
+   any device call; freesasa_gpu_xtc_decode_check is that part alone, host only, the message in err - "xtc_decode: ..." for a null
+   pointer, n_frames, n_atoms or len below 1, or n_frames * n_atoms beyond an int.  Device and page-locked memory are the
+   context's workspace (freesasa_gpu_test_fail_after reaches them).  Through it tests/test_xtc_decode_gpu.py pins the device
+   decode group by group to the pure-Python codec: every path of the format (runs 0 to 8, forced flags, inherited runs, smallidx
+   held at 9 and at 72, bitsize 0 with runs) alone and as the frames of one shard, every padding, the scan's window as it moves
+   (a group that ends on the window's last bit, a hop by every excess of 1 to 6 bits, flags at bit 0 and bit 31 of a word), 600
+   frames in one launch, integers beyond 2^24 at four precisions and the widest dimensions a header may hold, and the status
+   word of damaged streams. */
+int freesasa_gpu_xtc_decode_dev(freesasa_gpu_ctx *ctx, const void *bytes, long long len, int n_frames, int n_atoms, int32_t *rec,
+                                int32_t *count, float *out);
+int freesasa_gpu_xtc_decode_check(const void *bytes, long long len, int n_frames, int n_atoms, const int32_t *rec, const int32_t *count,
+                                  const float *out, char *err, int err_len);
 /* cuts[0..n_parts]: first structure of every run for the partition above (host-only helper) */
 void freesasa_gpu_shard_cuts(const int64_t *offsets, int n_structs, int n_parts, int *cuts);
 

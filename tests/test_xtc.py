@@ -449,3 +449,36 @@ def test_driver_argument_errors_come_before_any_device_or_file(tmp_path):
         with pytest.raises(ValueError, match="xtc=True"):
             fa.trajectory_file_topology(boxed, batch, outs[0], atom_index=index, xtc=True, **kw)
     assert not any(p.exists() for p in outs)
+
+
+def test_decode_hook_argument_errors_come_with_their_messages_and_without_a_device():
+    """freesasa_gpu_xtc_decode_check is what freesasa_gpu_xtc_decode_dev (the test hook of tests/test_xtc_decode_gpu.py) refuses
+    before its first device call: host only; the hook copies the message into its context's error text.  Without a context the
+    hook has nowhere to put one."""
+    L = fa.lib()
+    _, _, ints, data = case_frame("ten atoms")
+    n = len(ints)
+    rec, count, out = np.zeros((n, 4), dtype=np.int32), np.zeros(2, dtype=np.int32), np.full((n, 3), np.nan, dtype=np.float32)
+    good = dict(bytes=data, len=len(data), n_frames=1, n_atoms=n, rec=rec.ctypes.data, count=count.ctypes.data, out=out.ctypes.data)
+
+    def check(**kw):
+        a = dict(good, **kw)
+        err = C.create_string_buffer(b"untouched", 200)
+        rc = L.freesasa_gpu_xtc_decode_check(a["bytes"], a["len"], a["n_frames"], a["n_atoms"], a["rec"], a["count"], a["out"], err, 200)
+        return rc, err.value.decode()
+
+    assert check() == (0, "")
+    for kw, text in ((dict(bytes=None), "null argument"), (dict(rec=None), "null argument"), (dict(count=None), "null argument"),
+                     (dict(out=None), "null argument"), (dict(n_frames=0), "n_frames must be at least 1"), (dict(n_frames=-3), "n_frames must be at least 1"),
+                     (dict(n_atoms=0), "n_atoms must be at least 1"), (dict(n_atoms=-1), "n_atoms must be at least 1"),
+                     (dict(len=0), "len must be at least 1"), (dict(len=-92), "len must be at least 1"),
+                     (dict(n_frames=1 << 16, n_atoms=1 << 15), "n_frames * n_atoms does not fit an int"),
+                     (dict(n_frames=2 ** 31 - 1, n_atoms=2 ** 31 - 1), "n_frames * n_atoms does not fit an int")):
+        assert check(**kw) == (-1, "xtc_decode: " + text), kw
+    assert check(n_frames=(1 << 16) - 1, n_atoms=1 << 15) == (0, "")               # (2^31 - 2^15 slots: the most an int holds, nearly)
+    # a short message buffer, and none
+    err = C.create_string_buffer(8)
+    assert L.freesasa_gpu_xtc_decode_check(None, 1, 1, 10, None, None, None, err, 8) == -1 and err.value == b"xtc_dec"
+    assert L.freesasa_gpu_xtc_decode_check(None, 1, 1, 10, None, None, None, None, 0) == -1
+    assert L.freesasa_gpu_xtc_decode_dev(None, data, len(data), 1, n, rec.ctypes.data, count.ctypes.data, out.ctypes.data) == -1
+    assert not rec.any() and not count.any() and np.isnan(out).all()
