@@ -20,6 +20,7 @@ SUCCESS, FAIL, WARN = 0, -1, -2
 V_NORMAL, V_NOWARNINGS, V_SILENT, V_DEBUG = 0, 1, 2, 3
 
 _dp, _ip, _lp = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int64)
+_u32p = C.POINTER(C.c_uint32)
 
 
 class Parameters(C.Structure):
@@ -126,6 +127,15 @@ def lib():
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.freesasa_gpu_calc_volume.argtypes = [_dp, _dp, _lp, C.c_int, C.c_double, C.c_int, _dp, _ip, _dp, _dp, _dp, _dp,
                                                C.c_int, C.c_char_p, C.c_int]
+        L.freesasa_gpu_sr_masks_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _lp, C.c_int, C.c_double, C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.freesasa_gpu_dots_count_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.POINTER(C.c_longlong)]
+        L.freesasa_gpu_dots_expand_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_double, C.c_int, C.c_void_p,
+                                                   C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.freesasa_gpu_calc_masks.argtypes = [_dp, _dp, _lp, C.c_int, C.c_double, C.c_int, _dp, _ip, _dp, _u32p, C.c_int, C.c_char_p, C.c_int]
+        L.freesasa_gpu_masks_count.argtypes = [_u32p, C.c_longlong, C.c_int, C.POINTER(C.c_longlong), C.c_char_p, C.c_int]
+        L.freesasa_gpu_dots_from_masks.argtypes = [_dp, _dp, C.c_longlong, C.c_double, C.c_int, _u32p, C.c_longlong, _lp, _dp, _ip, _ip,
+                                                   C.c_int, C.c_char_p, C.c_int]
         L.freesasa_gpu_periodic_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _lp, C.c_int, _dp, C.c_double, C.c_int,
                                                 C.c_void_p, C.c_void_p, _lp]
         L.freesasa_gpu_calc_periodic.argtypes = [_dp, _dp, _lp, C.c_int, _dp, C.c_int, C.c_double, C.c_int, _dp, _dp, _lp,
@@ -269,6 +279,66 @@ def calc_volume(xyz, radii, offsets, probe=1.4, n_points=100, device=-1, per_ato
     if ret:
         raise RuntimeError("freesasa_gpu_calc_volume: " + err.value.decode())
     return (sasa, counts, totals, volumes, evec, vol) if per_atom else (sasa, counts, totals, volumes)
+
+
+def calc_masks(xyz, radii, offsets, probe=1.4, n_points=100, device=-1):
+    """freesasa_gpu_calc_masks() on host arrays: (sasa, counts, totals, masks) - the Shrake-Rupley areas, exposed-point counts and
+    totals of calc_batch, bit for bit, and masks [n, 4] uint32: bit k & 31 of word k >> 5 of atom i is set iff test point k of
+    atom i is exposed (include/freesasa_gpu.h has the definitions).  Up to 128 test points."""
+    xyz, radii = _f64(xyz).reshape(-1), _f64(radii)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n, ns = radii.size, offsets.size - 1
+    sasa, totals = np.empty(n), np.empty(ns)
+    counts, masks = np.empty(n, dtype=np.int32), np.empty((n, 4), dtype=np.uint32)
+    err = C.create_string_buffer(512)
+    ret = lib().freesasa_gpu_calc_masks(xyz.ctypes.data_as(_dp), radii.ctypes.data_as(_dp), offsets.ctypes.data_as(_lp), ns, probe, n_points,
+                                        sasa.ctypes.data_as(_dp), counts.ctypes.data_as(_ip), totals.ctypes.data_as(_dp),
+                                        masks.ctypes.data_as(_u32p), device, err, 512)
+    if ret:
+        raise RuntimeError("freesasa_gpu_calc_masks: " + err.value.decode())
+    return sasa, counts, totals, masks
+
+
+def masks_count(masks, n_points=100):
+    """freesasa_gpu_masks_count(): the number of dots the masks [n, 4] hold (on the host; refused if a bit at or above n_points is set)"""
+    masks = np.ascontiguousarray(masks, dtype=np.uint32).reshape(-1)
+    D, err = C.c_longlong(0), C.create_string_buffer(512)
+    if lib().freesasa_gpu_masks_count(masks.ctypes.data_as(_u32p), masks.size // 4, n_points, C.byref(D), err, 512):
+        raise RuntimeError("freesasa_gpu_masks_count: " + err.value.decode())
+    return int(D.value)
+
+
+def dots_from_masks(xyz, radii, masks, n_dots, probe=1.4, n_points=100, device=-1, with_index=False):
+    """freesasa_gpu_dots_from_masks() on host arrays: the surface dots of stored masks [n, 4] -> (dots [n_dots, 3], dot_first
+    [n + 1] int64), with with_index=True behind them dot_atom [n_dots] and dot_point [n_dots] (int32).  n_dots: what the masks
+    are held to have (the sum of `counts`); refused if their popcount is another number or a bit at or above n_points is set."""
+    xyz, radii = _f64(xyz).reshape(-1), _f64(radii)
+    masks = np.ascontiguousarray(masks, dtype=np.uint32).reshape(-1)
+    n, D = radii.size, int(n_dots)
+    if xyz.size != 3 * n or masks.size != 4 * n:
+        raise ValueError("xyz [n, 3], radii [n] and masks [n, 4] must agree")
+    dots, first = np.empty((max(D, 0), 3)), np.empty(n + 1, dtype=np.int64)
+    atom, point = (np.empty(max(D, 0), dtype=np.int32), np.empty(max(D, 0), dtype=np.int32)) if with_index else (None, None)
+    err = C.create_string_buffer(512)
+    opt = lambda a: None if a is None else a.ctypes.data_as(_ip)
+    ret = lib().freesasa_gpu_dots_from_masks(xyz.ctypes.data_as(_dp), radii.ctypes.data_as(_dp), n, probe, n_points, masks.ctypes.data_as(_u32p),
+                                             D, first.ctypes.data_as(_lp), dots.ctypes.data_as(_dp), opt(atom), opt(point), device, err, 512)
+    if ret:
+        raise RuntimeError("freesasa_gpu_dots_from_masks: " + err.value.decode())
+    return (dots, first, atom, point) if with_index else (dots, first)
+
+
+def calc_dots(xyz, radii, offsets, probe=1.4, n_points=100, device=-1, with_index=False):
+    """calc_masks() and dots_from_masks() behind it: (sasa, counts, totals, dots [D, 3], dot_offsets [n_structs + 1]) - the dots of
+    structure s are dots[dot_offsets[s]:dot_offsets[s + 1]], atom by atom, within an atom by ascending test point: what
+    `gmx sasa -q` writes - and with with_index=True behind them dot_atom [D] and dot_point [D].  A dot's outward normal is
+    test_points(n_points)[dot_point], the area it stands for 4 pi (r + probe)^2 / n_points.  (The arrays are sized by
+    masks_count(): the loader does no arithmetic of its own.)"""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    sasa, counts, totals, masks = calc_masks(xyz, radii, offsets, probe, n_points, device)
+    got = dots_from_masks(xyz, radii, masks, masks_count(masks, n_points), probe, n_points, device, with_index)
+    dot_offsets = got[1][offsets]
+    return (sasa, counts, totals, got[0], dot_offsets) + tuple(got[2:])
 
 
 def calc_periodic(xyz, radii, offsets, cells, alg=LEE_RICHARDS, probe=1.4, resolution=20, device=-1):
@@ -1079,6 +1149,14 @@ def _topology_proto(L):
                                                       C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
                                                       C.c_char_p, C.c_char_p, C.c_char_p, _llp, C.c_char_p, C.c_char_p, C.c_longlong, _ip, C.c_int,
                                                       _llp, C.c_char_p, C.c_int]
+    # ... with the frames' exposure masks behind sel_atoms_out (an array / a path)
+    L.freesasa_gpu_trajectory_masks.argtypes = [_dp, C.c_int, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_void_p,
+                                                C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _llp, _u32p,
+                                                _ip, C.c_int, C.c_char_p, C.c_int]
+    L.freesasa_gpu_trajectory_file_masks.argtypes = [C.c_char_p, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, C.c_int, _i32p,
+                                                     C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
+                                                     C.c_char_p, C.c_char_p, C.c_char_p, _llp, C.c_char_p, C.c_char_p, C.c_longlong, _ip, C.c_int,
+                                                     _llp, C.c_char_p, C.c_int]
     # the same with chain groups: (group, n_groups) behind the selection set, the two group outputs behind sel_atoms_out
     L.freesasa_gpu_trajectory_groups.argtypes = [_dp, C.c_int, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_void_p, _i32p, C.c_int,
                                                  C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _llp, _dp, _dp,
@@ -1098,11 +1176,12 @@ class TopologyResult:
     (isolated, complex, buried per frame and group), group_atoms [G], and with per_atom isolated [F, n], every atom's area in
     its group taken on its own (isolated - sasa: what the atom buries in the complex).  stats: the RunStats of the outputs
     named in stats=, None without.  With per_frame=False only totals (and selection_atoms) are delivered per frame: the others
-    are None.  volumes [F]: with volumes=True, the volume every frame's solvent-accessible surface encloses; None without."""
+    are None.  volumes [F]: with volumes=True, the volume every frame's solvent-accessible surface encloses; None without.
+    masks [F, n, 4] uint32: with masks=True, every atom's exposure mask in every frame (calc_masks); None without."""
 
     def __init__(self, totals, class_sums, residues, selection_areas, selection_atoms, sasa, res_ref, group_areas=None,
-                 group_atoms=None, isolated=None, stats=None, volumes=None):
-        self.stats, self.volumes = stats, volumes
+                 group_atoms=None, isolated=None, stats=None, volumes=None, masks=None):
+        self.stats, self.volumes, self.masks = stats, volumes, masks
         self.totals, self.class_sums, self.residues = totals, class_sums, residues
         self.selection_areas, self.selection_atoms, self.sasa, self.res_ref = selection_areas, selection_atoms, sasa, res_ref
         self.group_areas, self.group_atoms, self.isolated = group_areas, group_atoms, isolated
@@ -1148,7 +1227,7 @@ def _topology_groups(batch, structure, n, chain_groups, separate_chains, long, g
 
 def trajectory_topology(frames, batch, structure=0, atom_index=None, selection=None, per_atom=False, alg=LEE_RICHARDS, probe=1.4,
                         resolution=20, frames_per_batch=0, device=-1, devices=None, chain_groups=None, separate_chains=False,
-                        long=False, group=None, n_groups=None, stats=None, per_frame=True, volumes=False):
+                        long=False, group=None, n_groups=None, stats=None, per_frame=True, volumes=False, masks=False):
     """freesasa_gpu_trajectory_topology(): frames [F, frame_atoms, 3] of a (solvated) system whose solute is structure
     `structure` of the ingest.Batch - topology atom i is frame atom atom_index[i] (None: the frames hold exactly the
     structure's atoms) - -> a TopologyResult.  The gather, the per-residue, per-class and per-selection sums run on the
@@ -1161,9 +1240,14 @@ def trajectory_topology(frames, batch, structure=0, atom_index=None, selection=N
     it is delivered: with per_atom=False the per-atom areas never leave the device, and with per_frame=False neither do the class
     sums, residues, selection and group areas.
     volumes=True (freesasa_gpu_trajectory_volume; Shrake-Rupley, up to 128 points, no chain groups, no statistics): the
-    result's volumes [F] holds the volume every frame's surface encloses, as calc_volume gives it for the frame."""
+    result's volumes [F] holds the volume every frame's surface encloses, as calc_volume gives it for the frame.
+    masks=True (freesasa_gpu_trajectory_masks; Shrake-Rupley, up to 128 points, no chain groups, no statistics, no volumes): the
+    result's masks [F, n, 4] holds every atom's exposure mask in every frame, as calc_masks gives it for the frame; the dots of any
+    frame follow from it with dots_from_masks."""
     if volumes and (stats or not per_frame or chain_groups is not None or separate_chains or group is not None):
         raise ValueError("volumes=True is not offered with chain groups, stats= or per_frame=False")
+    if masks and (volumes or stats or not per_frame or chain_groups is not None or separate_chains or group is not None):
+        raise ValueError("masks=True is not offered with chain groups, stats=, per_frame=False or volumes=True")
     if stats or not per_frame:
         return _trajectory_topology_stats(frames, batch, structure, atom_index, selection, per_atom, alg, probe, resolution, frames_per_batch,
                                           device, devices, chain_groups, separate_chains, long, group, n_groups, stats, per_frame)
@@ -1193,6 +1277,16 @@ def trajectory_topology(frames, batch, structure=0, atom_index=None, selection=N
         if ret:
             raise RuntimeError("freesasa_gpu_trajectory_volume: " + err.value.decode())
         return TopologyResult(totals, cls, res, sel_area, sel_atoms, sasa, res_ref, volumes=vols)
+    if masks:
+        mk = np.zeros((F, n, 4), dtype=np.uint32)
+        ret = L.freesasa_gpu_trajectory_masks(frames.ctypes.data_as(_dp), F, C.byref(cb), structure, fa_, opt(idx, C.POINTER(C.c_int32)),
+                                              selection.handle if selection is not None else None, alg, probe, resolution,
+                                              frames_per_batch, totals.ctypes.data_as(_dp), opt(sasa), cls.ctypes.data_as(_dp),
+                                              res.ctypes.data_as(_dp), opt(sel_area), opt(sel_atoms, C.POINTER(C.c_longlong)),
+                                              mk.ctypes.data_as(_u32p), dp_, nd, err, 512)
+        if ret:
+            raise RuntimeError("freesasa_gpu_trajectory_masks: " + err.value.decode())
+        return TopologyResult(totals, cls, res, sel_area, sel_atoms, sasa, res_ref, masks=mk)
     if ids is None:
         ret = L.freesasa_gpu_trajectory_topology(frames.ctypes.data_as(_dp), F, C.byref(cb), structure, fa_, opt(idx, C.POINTER(C.c_int32)),
                                                  selection.handle if selection is not None else None, alg, probe, resolution,
@@ -1258,7 +1352,7 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
                              max_new_shards=0, device=-1, devices=None, out_f32=False, chain_groups=None, separate_chains=False,
                              long=False, group=None, n_groups=None, group_areas_path=None, isolated_path=None, dcd=False, pbc=False,
                              triclinic=False, netcdf=False, xtc=False, stats=None, stats_path=None, partials_path=None, trr=False,
-                             volumes_path=None):
+                             volumes_path=None, masks_path=None):
     """freesasa_gpu_trajectory_file_topology(): trajectory_file() with a topology (see trajectory_topology; frame_atoms:
     atoms per frame of the file, None: the structure's) and one raw fp64 result file per output asked for: class sums
     [F, 3], residues [F, R, 6], selection areas [F, S].  Returns (complete, n_frames, selection_atoms [S] or None).
@@ -1273,11 +1367,16 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
     stats=("atoms", "residues", ...) with stats_path and partials_path (freesasa_gpu_trajectory_file_groups_stats): the run statistics of
     those outputs, as trajectory_file describes them; an output named there needs no result file of its own.
     volumes_path (freesasa_gpu_trajectory_file_volume; Shrake-Rupley, up to 128 points, no chain groups, no statistics, no pbc):
-    receives the frames' volumes [F] fp64, as trajectory_topology(volumes=True) gives them."""
+    receives the frames' volumes [F] fp64, as trajectory_topology(volumes=True) gives them.
+    masks_path (freesasa_gpu_trajectory_file_masks; Shrake-Rupley, up to 128 points, no chain groups, no statistics, no pbc, no
+    volumes): receives the frames' exposure masks [F, n, 4] uint32, as trajectory_topology(masks=True) gives them."""
     L = _stats_proto(_topology_proto(lib()))
     if volumes_path is not None and (stats or chain_groups is not None or separate_chains or group is not None or
                                      group_areas_path is not None or isolated_path is not None):
         raise ValueError("volumes_path is not offered with chain groups or stats=")
+    if masks_path is not None and (volumes_path is not None or stats or chain_groups is not None or separate_chains or group is not None or
+                                   group_areas_path is not None or isolated_path is not None):
+        raise ValueError("masks_path is not offered with chain groups, stats= or volumes_path")
     bits = _frames_bits(f32, out_f32, dcd, header_bytes, pbc, triclinic, netcdf, xtc, trr)
     if dcd and frame_atoms is None:
         frame_atoms = dcd_info(frames_path).n_atoms
@@ -1306,6 +1405,17 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
                                                     enc(volumes_path), enc(done_path), max_new_shards, dp_, nd, C.byref(total), err, 512)
         if ret < 0:
             raise RuntimeError("freesasa_gpu_trajectory_file_volume: " + err.value.decode())
+        return ret == 0, int(total.value), sel_atoms
+    if masks_path is not None:
+        ret = L.freesasa_gpu_trajectory_file_masks(enc(frames_path), bits, header_bytes, n_frames, C.byref(cb), structure, fa_,
+                                                   None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                   selection.handle if selection is not None else None, alg, probe, resolution,
+                                                   frames_per_batch, enc(totals_path), enc(sasa_path), enc(class_sums_path),
+                                                   enc(residues_path), enc(selections_path),
+                                                   None if sel_atoms is None else sel_atoms.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                                   enc(masks_path), enc(done_path), max_new_shards, dp_, nd, C.byref(total), err, 512)
+        if ret < 0:
+            raise RuntimeError("freesasa_gpu_trajectory_file_masks: " + err.value.decode())
         return ret == 0, int(total.value), sel_atoms
     if stats:
         ret = L.freesasa_gpu_trajectory_file_groups_stats(enc(frames_path), bits, header_bytes, n_frames, C.byref(cb), structure, fa_,
@@ -1561,6 +1671,30 @@ class GpuContext:
                                                d_sasa, d_counts or None, d_evec or None, d_vol or None, d_totals or None, d_volumes or None)
         if ret:
             raise RuntimeError("freesasa_gpu_sr_volume_dev: " + self.error())
+
+    def masks(self, d_xyz, d_radii, offsets, d_sasa, d_masks, d_counts=0, d_totals=0, probe=1.4, n_points=100):
+        """freesasa_gpu_sr_masks_dev(): shrake_rupley() and, into d_masks [n, 4] uint32, every atom's exposure mask (device
+        pointers; d_counts [n] and d_totals [n_structs] optional)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        ret = lib().freesasa_gpu_sr_masks_dev(self._h, d_xyz, d_radii, offsets.ctypes.data_as(_lp), offsets.size - 1, probe, n_points,
+                                              d_sasa, d_counts or None, d_totals or None, d_masks or None)
+        if ret:
+            raise RuntimeError("freesasa_gpu_sr_masks_dev: " + self.error())
+
+    def dots_count(self, d_masks, n_atoms, d_dot_first, n_points=100):
+        """freesasa_gpu_dots_count_dev(): d_dot_first [n_atoms + 1] int64, the exclusive prefix sum of the masks' popcounts -> D"""
+        D = C.c_longlong(0)
+        if lib().freesasa_gpu_dots_count_dev(self._h, d_masks or None, n_atoms, n_points, d_dot_first or None, C.byref(D)):
+            raise RuntimeError("freesasa_gpu_dots_count_dev: " + self.error())
+        return int(D.value)
+
+    def dots_expand(self, d_xyz, d_radii, n_atoms, d_masks, d_dot_first, capacity, d_dot_xyz, d_dot_atom=0, d_dot_point=0, probe=1.4,
+                    n_points=100):
+        """freesasa_gpu_dots_expand_dev(): the dots of the masks into d_dot_xyz [capacity, 3] (d_dot_atom, d_dot_point [capacity]
+        int32 optional); nothing is written at or beyond slot `capacity`"""
+        if lib().freesasa_gpu_dots_expand_dev(self._h, d_xyz or None, d_radii or None, n_atoms, probe, n_points, d_masks or None,
+                                              d_dot_first or None, capacity, d_dot_xyz or None, d_dot_atom or None, d_dot_point or None):
+            raise RuntimeError("freesasa_gpu_dots_expand_dev: " + self.error())
 
     def shrake_rupley(self, d_xyz, d_radii, offsets, d_sasa, d_counts=0, d_totals=0, probe=1.4,
                       n_points=100):

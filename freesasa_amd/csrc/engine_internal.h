@@ -17,6 +17,8 @@
  *                      group ids made on the device
  *   gpu_volume.hip     molecular volume: the batch through the engine with the exposed-point vectors kept, the atoms' terms
  *                      and the structures' volumes behind it; its device-pointer and host-pointer entries
+ *   gpu_dots.hip       exposure masks and surface dots: the batch through the engine with the store phase's masks kept; the scan
+ *                      of their popcounts and the expansion into dots; their device-pointer and host-pointer entries
  *   gpu_periodic.hip   periodic images: a batch and its cells (orthorhombic or triclinic) expanded into a batch with the
  *                      images that matter, the areas of the real atoms collected; the stage the trajectory file drivers share
  */
@@ -47,6 +49,7 @@
 #include "pbc_kernels.h"
 #include "pbc_tri_kernels.h"
 #include "vol_kernels.h"
+#include "dots_kernels.h"
 #include "gpu_parse.h"
 
 /* ------------------------------------------------------------------ kernel launchers (gpu_kernels.hip) */
@@ -70,8 +73,8 @@ hipError_t kl_lr2_mid(int grid, size_t lds, hipStream_t st, const sasa::Lr2Args 
 /* first-generation tile kernels: tier 0 main launch, 1 second launch, 2 last launch (lists in a global slab) */
 hipError_t kl_lr_tile(int tier, const sasa::TileCfg &c, const sasa::TileArgs &t, int grid, size_t lds, hipStream_t st, bool bucket);
 /* (evec: the volume's exposed-point vectors [3 n_atoms], kept by the launches that run the third arrangement - sr_caps_shape;
-   null: the builds without them) */
-hipError_t kl_sr_tile(int tier, const sasa::TileCfg &c, const sasa::TileArgs &t, int grid, size_t lds, hipStream_t st, double *evec = nullptr);
+   null: the builds without them; masks: the dots' exposure masks [n_atoms][SR_CAP_WORDS], kept the same way - one of the two at most) */
+hipError_t kl_sr_tile(int tier, const sasa::TileCfg &c, const sasa::TileArgs &t, int grid, size_t lds, hipStream_t st, double *evec = nullptr, unsigned *masks = nullptr);
 /* per-structure totals in two levels (chunk partials in `bpart`) */
 hipError_t kl_totals(const sasa::PipeArgs &pa, int n_chunks, int n_structs, const double *d_sasa, double *bpart, double *d_totals, hipStream_t st);
 hipError_t kl_segment_sums(const double *d_sasa, const int64_t *d_seg, int n_segs, bool short_segments, double *d_out, hipStream_t st);
@@ -133,6 +136,10 @@ hipError_t kl_pbc_tri_emit(const sasa::PbcTriArgs &a, hipStream_t st);
 /* molecular volume (vol_kernels.h): the origins (one workgroup per structure), the atoms' terms (one thread per atom) */
 hipError_t kl_vol_origin(const sasa::VolArgs &a, hipStream_t st);
 hipError_t kl_vol_atom(const sasa::VolArgs &a, hipStream_t st);
+
+/* surface dots (dots_kernels.h): the scan in its three launches (dot_first and, at its end, D); the expansion */
+hipError_t kl_dots_count(const sasa::DotsArgs &a, hipStream_t st);
+hipError_t kl_dots_expand(const sasa::DotsArgs &a, hipStream_t st);
 
 /* ------------------------------------------------------------------ context (gpu_engine.hip) */
 
@@ -199,6 +206,11 @@ struct freesasa_gpu_ctx {
        there - or refuses the batch (run_batch_once) */
     DevBuf v_counts, v_evec, v_vol, v_origin, v_volumes;
     double *vol_evec = nullptr;
+    /* exposure masks and surface dots (gpu_dots.hip): sr_masks: set for the length of ONE run_batch, which then keeps the masks
+       there - or refuses the batch (run_batch_once); the host-pointer entries' masks, prefix sums, block sums and dots */
+    unsigned *sr_masks = nullptr;
+    DevBuf dt_masks, dt_first, dt_bsum, dt_xyz, dt_atom, dt_point, dt_unit;
+    int dt_unit_n = 0; /* the point count whose unit points dt_unit holds (the expansion's; 0: none) */
     void *stage_in = nullptr, *stage_out = nullptr; /* page-locked host staging of freesasa_gpu_calc_batch_pipelined */
     size_t stage_in_cap = 0, stage_out_cap = 0;
     void *res_stage = nullptr; /* page-locked: a batch's per-residue areas and arrays on their way to the host (gpu_sweep.hip) */
@@ -326,6 +338,19 @@ int volume_resident(freesasa_gpu_ctx *c, const double *d_xyz, const double *d_ra
                     double *d_vol, double *d_totals, double *d_volumes);
 /* the arguments both volume entries check before a device is touched: 0, or the message */
 const char *volume_bad_args(const void *xyz, const void *radii, const int64_t *offsets, int n_structs, int n_points, const void *sasa, const void *volumes);
+
+/* ------------------------------------------------------------------ exposure masks and surface dots (gpu_dots.hip) */
+
+/* freesasa_gpu_sr_masks_dev's pipeline on arrays that are on the context's stream already: run_batch (Shrake-Rupley, with
+   c->shared_radii as the caller has set it) with the exposure masks kept in d_masks [n_atoms][SR_CAP_WORDS]; nothing is
+   waited for beyond what run_batch waits for.  d_counts / d_totals may be null.  0, or -1 with the context's message: a bad
+   argument, or a batch whose masks the engine does not make (more than 128 points, no table of cap masks, a launch in the
+   second arrangement, the volume's vectors asked for in the same batch). */
+int masks_resident(freesasa_gpu_ctx *c, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
+                   double probe, int n_points, const double *unit_points, double *d_sasa, int *d_counts, double *d_totals,
+                   unsigned *d_masks);
+/* the arguments the mask entries check before a device is touched: 0, or the message */
+const char *masks_bad_args(const void *xyz, const void *radii, const int64_t *offsets, int n_structs, int n_points, const void *sasa, const void *masks);
 
 /* ------------------------------------------------------------------ host-side helpers (gpu_hostbatch.hip) */
 

@@ -140,7 +140,7 @@ namespace {
 /* One per-frame OUTPUT of a run: a row of TrajIO's table.  An entry point says where it goes - the caller's array or a
    result file - and everything else that is per output (opening the files, is it wanted, its place in a shard's blocks, the
    copy or the pwrite at the frame's offset, the flush, the done-list's outputs= word) is a loop over the table. */
-enum { OUT_TOTALS, OUT_SASA, OUT_ISO, OUT_CLS, OUT_RES, OUT_SEL, OUT_GRP, OUT_VOL, N_OUT }; /* (per atom | from OUT_CLS on: the block of sums) */
+enum { OUT_TOTALS, OUT_SASA, OUT_ISO, OUT_MASK, OUT_CLS, OUT_RES, OUT_SEL, OUT_GRP, OUT_VOL, N_OUT }; /* (per atom | from OUT_CLS on: the block of sums) */
 struct TrajOut {
     const char *name;           /* in messages: "cannot open the %s file", "could not write the %s file" */
     int bit;                    /* in the outputs= word of a done-list's first line */
@@ -173,8 +173,10 @@ struct TrajIO {
     bool tri = false;               /* ... FREESASA_GPU_FRAMES_TRICLINIC beside it: the record decoded as a triclinic cell */
     /* per frame: total [1], per-atom areas [n]; runs with a topology: class sums [3], residue areas [6 R], selection areas [S];
        with chain groups: every atom's area in its isolated group [n], and isolated, complex, buried per group [3 G]; the volume
-       entries: the frame's volume [1] (gpu_volume.hip; it has no run statistics: no bit of the statistics word) */
+       entries: the frame's volume [1] (gpu_volume.hip; it has no run statistics: no bit of the statistics word); the mask entries:
+       every atom's exposure mask, four uint32 words [4 n] (gpu_dots.hip; per atom, 4 bytes a value, copied as it lies; no statistics) */
     TrajOut out[N_OUT] = {{"totals", 0, FREESASA_GPU_STATS_TOTALS}, {"per-atom", 1, FREESASA_GPU_STATS_ATOMS}, {"isolated", 32, FREESASA_GPU_STATS_ISOLATED},
+                          {"masks", 128, 0, nullptr, nullptr, Fd(), 4},
                           {"class-sums", 2, FREESASA_GPU_STATS_CLASSES}, {"residues", 4, FREESASA_GPU_STATS_RESIDUES},
                           {"selections", 8, FREESASA_GPU_STATS_SELECTIONS}, {"groups", 16, FREESASA_GPU_STATS_GROUPS}, {"volumes", 64, 0}};
     /* run statistics (include/freesasa_gpu.h): the word; every shard's partial [4][W] at k * 4 W doubles of a host array or of
@@ -285,8 +287,8 @@ int stats_check(int stats, const TrajTopo *tp, bool has_sel, bool has_group, cha
 {
     if (stats & ~127) return set_err(err_out, err_len, "unknown bit in the statistics word");
     /* (the table's names and bits, without a TrajIO: nothing here allocates) */
-    static const char *const name[N_OUT] = {"totals", "per-atom", "isolated", "class-sums", "residues", "selections", "groups", "volumes"};
-    static const int sbit[N_OUT] = {FREESASA_GPU_STATS_TOTALS, FREESASA_GPU_STATS_ATOMS, FREESASA_GPU_STATS_ISOLATED, FREESASA_GPU_STATS_CLASSES,
+    static const char *const name[N_OUT] = {"totals", "per-atom", "isolated", "masks", "class-sums", "residues", "selections", "groups", "volumes"};
+    static const int sbit[N_OUT] = {FREESASA_GPU_STATS_TOTALS, FREESASA_GPU_STATS_ATOMS, FREESASA_GPU_STATS_ISOLATED, 0, FREESASA_GPU_STATS_CLASSES,
                                     FREESASA_GPU_STATS_RESIDUES, FREESASA_GPU_STATS_SELECTIONS, FREESASA_GPU_STATS_GROUPS, 0};
     char msg[160];
     for (int k = 0; k < N_OUT; ++k) {
@@ -299,7 +301,7 @@ int stats_check(int stats, const TrajTopo *tp, bool has_sel, bool has_group, cha
     }
     return 0;
 }
-/* W of a run's statistics word, every output's first column into first[N_OUT] (trajstats.c: the one place that knows the layout) */
+/* W of a run's statistics word, every output's first column into first[7], in the order of the word's bits (trajstats.c: the one place that knows the layout) */
 size_t stats_width(int stats, int n_atoms, const TrajTopo *tp, long long *first)
 {
     const long long W = freesasa_gpu_traj_stats_width(stats, n_atoms, tp ? tp->n_res : 0, tp ? tp->n_sel : 0, tp ? tp->n_groups : 0, first);
@@ -447,7 +449,7 @@ struct TrajRun {
     /* the caller's arrays are page-locked: no staging */
     const bool in_pinned = io.mem_in && host_pinned(io.mem_in);
     const bool direct_out = io.out[OUT_TOTALS].mem && host_pinned(io.out[OUT_TOTALS].mem) && (!io.out[OUT_SASA].mem || host_pinned(io.out[OUT_SASA].mem)) &&
-                            (!io.out[OUT_ISO].mem || host_pinned(io.out[OUT_ISO].mem));
+                            (!io.out[OUT_ISO].mem || host_pinned(io.out[OUT_ISO].mem)) && (!io.out[OUT_MASK].mem || host_pinned(io.out[OUT_MASK].mem));
     const size_t S = topo && topo->sel && (io.out[OUT_SEL].wanted() || io.sel_atoms || (io.stats & FREESASA_GPU_STATS_SELECTIONS)) ? (size_t)topo->n_sel : 0; /* selections computed */
     /* A shard's sums lie one behind the other in ONE block, cut to its nf frames: classes | residues | selection areas |
        groups | volumes | selected atoms.  Output k's begin at x0[k] * nf doubles (k = N_OUT: the atom counts); xw doubles per frame hold it all. */
@@ -462,6 +464,21 @@ struct TrajRun {
     std::atomic<long long> next{0}, fresh{0};
     std::atomic<int> stopped{0}, counts_out{0};
     FirstError fe;
+    /* A run reports the failure of its LOWEST failed shard, whichever lane got there first: shards are handed out in ascending
+       order, a shard in a lane's hands is run to its end, and a lane that holds a shard BELOW the lowest failed one runs it even
+       after the failure (traj_lane), so every shard below a failed one has reported by the time the lanes are joined - the message of a run does not depend on how its lanes happen to be scheduled (a file whose every frame is
+       refused is refused "at frame 0"). */
+    std::mutex shard_err_mu;
+    std::atomic<long long> shard_err_k{-1};
+    char shard_err[256] = {0};
+    void shard_failed(long long k, const char *msg)
+    {
+        {
+            std::lock_guard<std::mutex> lk(shard_err_mu);
+            if (shard_err_k.load() < 0 || k < shard_err_k.load()) { snprintf(shard_err, sizeof shard_err, "%s", msg); shard_err_k = k; }
+        }
+        fe.set(msg);
+    }
     /* dev aid (FREESASA_AMD_TRAJ_PROFILE): where the lanes' host time goes - read, waiting for the device, write, flush */
     const bool prof = getenv("FREESASA_AMD_TRAJ_PROFILE") != nullptr;
     std::atomic<long long> t_read{0}, t_dev{0}, t_write{0}, t_flush{0};
@@ -477,13 +494,16 @@ struct TrajRun {
     {
         batch_offsets(FB, offs);
         if (groups && (size_t)(s.n_frames % s.frames_per_batch)) batch_offsets((size_t)(s.n_frames % s.frames_per_batch), offs_last);
-        const size_t per[N_OUT] = {1, n, groups ? n : 0, topo ? (size_t)3 : 0, topo ? 6 * (size_t)topo->n_res : 0, S, 3 * G, 1};
+        const size_t per[N_OUT] = {1, n, groups ? n : 0, SR_CAP_WORDS * n, topo ? (size_t)3 : 0, topo ? 6 * (size_t)topo->n_res : 0, S, 3 * G, 1};
+        /* (an output's place in the order of the statistics word's outputs, which is trajstats.c's and not the table's: the
+           masks and the volumes have no statistics) */
+        static const int scol[N_OUT] = {0, 1, 2, -1, 3, 4, 5, 6, -1};
         long long first[N_OUT] = {0};
         sW = stats_width(io.stats, s.n_atoms, topo, first);
         for (int k = 0; k < N_OUT; ++k) {
             /* computed: delivered, or its statistics asked for (the selections' and the groups' kernels write theirs whenever they run) */
             io.out[k].stat = (io.stats & io.out[k].sbit) != 0;
-            io.out[k].s0 = io.out[k].stat ? (size_t)first[k] : 0;
+            io.out[k].s0 = io.out[k].stat && scol[k] >= 0 ? (size_t)first[scol[k]] : 0;
             io.out[k].per_frame = io.out[k].wanted() || io.out[k].stat || k == OUT_SEL || k == OUT_GRP ? per[k] : 0;
             if (k >= OUT_CLS) x0[k + 1] = x0[k] + io.out[k].per_frame;
         }
@@ -527,7 +547,8 @@ int shard_size(TrajRun &T, TrajLane &L)
         ((T.gather || T.container || T.xtc) && ensure(c, c->g_xyz, T.xtc ? T.xtc_f32_at(T.idx_max_bytes, FB) + (T.gather ? 12 * T.fa * FB : 0)
                                                                         : T.trr ? T.up_bytes(T.idx_max_bytes, FB)
                                                                         : T.pbc ? TrajRun::cells_at(T.stride * FB) + T.cell_bytes * FB : T.stride * FB)) || (T.xw + T.sW && ensure(c, c->h_gtot, 8 * (T.xw * FB + 4 * T.sW))) ||
-        (T.groups && (ensure(c, c->g_gath, 8 * nc * FB) || ensure(c, c->g_tot2, 8 * (1 + T.G) * FB))) || (iso && ensure(c, c->h_iso, 8 * n * FB)))
+        (T.groups && (ensure(c, c->g_gath, 8 * nc * FB) || ensure(c, c->g_tot2, 8 * (1 + T.G) * FB))) || (iso && ensure(c, c->h_iso, 8 * n * FB)) ||
+        (T.io.out[OUT_MASK].per_frame && ensure(c, c->dt_masks, 4 * SR_CAP_WORDS * n * FB)))
         return -1;
     if (!T.groups && !L.radii_up && hipMemcpyAsync(c->h_radii.p, T.s.radii, 8 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "radii upload failed");
     if (T.topo && !L.topo_up && topo_upload(c, *T.topo, L.ta, L.ga)) return -1;
@@ -901,6 +922,9 @@ int shard_compute(TrajRun &T, TrajLane &L, TrajShard &h)
                  : out[OUT_VOL].per_frame /* (the volume entries: the batch with its exposed-point vectors kept, the frames' volumes into the block of sums) */
                      ? volume_resident(c, (double *)c->h_xyz.p, (double *)c->h_radii.p, T.offs.data(), h.nf, T.s.probe, T.s.resolution, T.tp.data(),
                                        (double *)c->h_sasa.p, nullptr, nullptr, nullptr, (double *)c->h_totals.p, (double *)c->h_gtot.p + T.x0[OUT_VOL] * nf)
+                 : out[OUT_MASK].per_frame /* (the mask entries: the batch with its exposure masks kept, where they go down from) */
+                     ? masks_resident(c, (double *)c->h_xyz.p, (double *)c->h_radii.p, T.offs.data(), h.nf, T.s.probe, T.s.resolution, T.tp.data(),
+                                      (double *)c->h_sasa.p, nullptr, (double *)c->h_totals.p, (unsigned *)c->dt_masks.p)
                  : run_batch(c, T.s.alg == 0, (double *)c->h_xyz.p, (double *)c->h_radii.p, (T.groups && nf != T.FB ? T.offs_last : T.offs).data(),
                              (int)(nf * (1 + T.G)), T.s.probe, T.s.resolution, T.s.alg == 1 ? T.tp.data() : nullptr, (double *)c->h_sasa.p, nullptr,
                              (double *)c->h_totals.p);
@@ -962,17 +986,20 @@ int shard_compute(TrajRun &T, TrajLane &L, TrajShard &h)
 int shard_download(TrajRun &T, freesasa_gpu_ctx *c, TrajShard &h)
 {
     const TrajOut *out = T.io.out;
-    const size_t nf = (size_t)h.nf, sasa_bytes = out[OUT_SASA].esz * out[OUT_SASA].deliver() * nf, iso_bytes = out[OUT_ISO].esz * out[OUT_ISO].deliver() * nf;
-    if (!T.direct_out && ensure_pinned(c, &c->stage_out, &c->stage_out_cap, 8 * nf + 8 * (out[OUT_SASA].deliver() + out[OUT_ISO].deliver()) * nf)) return -1;
+    const size_t nf = (size_t)h.nf, sasa_bytes = out[OUT_SASA].esz * out[OUT_SASA].deliver() * nf, iso_bytes = out[OUT_ISO].esz * out[OUT_ISO].deliver() * nf,
+                 mask_bytes = out[OUT_MASK].esz * out[OUT_MASK].deliver() * nf;
+    if (!T.direct_out && ensure_pinned(c, &c->stage_out, &c->stage_out_cap, 8 * nf + 8 * (out[OUT_SASA].deliver() + out[OUT_ISO].deliver()) * nf + mask_bytes)) return -1;
     if (T.xw + T.sW && ensure_pinned(c, &c->res_stage, &c->res_stage_cap, 8 * (T.xw * nf + 4 * T.sW))) return -1;
     for (int k = 0; k < N_OUT; ++k)
         h.host[k] = k >= OUT_CLS ? (char *)c->res_stage + 8 * T.x0[k] * nf
-                  : T.direct_out ? (char *)out[k].mem + 8 * out[k].deliver() * (size_t)h.f0
-                  : (char *)c->stage_out + (k == OUT_SASA ? 8 * nf : k == OUT_ISO ? 8 * nf + 8 * out[OUT_SASA].deliver() * nf : 0);
+                  : T.direct_out ? (char *)out[k].mem + out[k].esz * out[k].deliver() * (size_t)h.f0 /* (memory forms: 8 bytes a value but the masks' 4) */
+                  : (char *)c->stage_out + (k == OUT_SASA ? 8 * nf : k == OUT_ISO ? 8 * nf + 8 * out[OUT_SASA].deliver() * nf
+                                            : k == OUT_MASK ? 8 * nf + 8 * (out[OUT_SASA].deliver() + out[OUT_ISO].deliver()) * nf : 0);
     h.stat_host = (char *)c->res_stage + 8 * T.xw * nf; /* (behind the shard's block of sums) */
     if (hipMemcpyAsync(h.host[OUT_TOTALS], c->h_totals.p, 8 * nf, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         (sasa_bytes && hipMemcpyAsync(h.host[OUT_SASA], h.d_areas, sasa_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
         (iso_bytes && hipMemcpyAsync(h.host[OUT_ISO], h.d_iso, iso_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+        (mask_bytes && hipMemcpyAsync(h.host[OUT_MASK], c->dt_masks.p, mask_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
         (T.xw && T.sums_down && hipMemcpyAsync(c->res_stage, c->h_gtot.p, 8 * (T.x0[N_OUT] * nf + T.S), hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
         (T.sW && hipMemcpyAsync(h.stat_host, (const double *)c->h_gtot.p + T.xw * T.FB, 32 * T.sW, hipMemcpyDeviceToHost, c->stream) != hipSuccess))
         return ctx_fail(c, "device-to-host copy failed");
@@ -1038,7 +1065,7 @@ void traj_lane(TrajRun &T, int id) noexcept
     for (;;) {
         TrajShard h;
         h.k = T.next.fetch_add(1);
-        if (h.k >= T.n_shards || T.fe.failed.load()) break;
+        if (h.k >= T.n_shards || (T.fe.failed.load() && h.k >= T.shard_err_k.load())) break; /* (shard_err_k -1: a failure that is no shard's ends every lane) */
         if (T.io.list.done(h.k)) continue;
         if (s.max_new > 0 && T.fresh.fetch_add(1) >= s.max_new) { T.stopped = 1; break; }
         h.f0 = h.k * s.frames_per_batch;
@@ -1046,7 +1073,7 @@ void traj_lane(TrajRun &T, int id) noexcept
         h.na = T.n * (size_t)h.nf; h.in_bytes = T.shard_bytes(h.f0, h.nf);
         if (shard_run(T, L, h)) {
             (void)hipStreamSynchronize(L.c->stream); /* nothing of the shard may still run when the lane lets go */
-            T.fe.set(L.c->err[0] ? L.c->err : "trajectory shard failed");
+            T.shard_failed(h.k, L.c->err[0] ? L.c->err : "trajectory shard failed");
             break;
         }
     }
@@ -1072,7 +1099,7 @@ int traj_run(TrajIO &io, const TrajSpec &s, char *err_out, int err_len)
     run_lanes(n_lanes, T.fe, [&T](int id) noexcept { traj_lane(T, id); });
     if (T.prof) fprintf(stderr, "trajectory lanes %d: per lane, ms: read %.1f  device (copies + kernels) %.1f  write %.1f  flush + done-list %.1f\n", n_lanes,
                         1e-6 * T.t_read.load() / n_lanes, 1e-6 * T.t_dev.load() / n_lanes, 1e-6 * T.t_write.load() / n_lanes, 1e-6 * T.t_flush.load() / n_lanes);
-    if (T.fe.failed.load()) return set_err(err_out, err_len, T.fe.text);
+    if (T.fe.failed.load()) return set_err(err_out, err_len, T.shard_err_k.load() >= 0 ? T.shard_err : T.fe.text);
     return T.stopped.load() ? 1 : 0;
     });
 }
@@ -1208,7 +1235,7 @@ static int trajectory_mem_topo(const double *xyz_frames, int n_frames, const fre
                                int alg, double probe, int resolution, int frames_per_batch,
                                double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
                                double *sel_area_out, long long *sel_atoms_out, double *group_areas_out, double *iso_out, double *volumes_out,
-                               const int *devices, int n_devices,
+                               uint32_t *masks_out, const int *devices, int n_devices,
                                int stats, double *stats_out, double *partials_out, char *err_out, int err_len)
 {
     if (err_out && err_len > 0) err_out[0] = 0;
@@ -1226,7 +1253,7 @@ static int trajectory_mem_topo(const double *xyz_frames, int n_frames, const fre
         if (traj_check_args(s, "n_frames must be > 0", err_out, err_len) || traj_shard_size(s, frame_atoms, err_out, err_len)) return -1;
         TrajIO io;
         io.mem_in = xyz_frames; io.sel_atoms = sel_atoms_out;
-        double *const mem[N_OUT] = {totals_out, sasa_out, iso_out, class_sums_out, residues_out, sel_area_out, group_areas_out, volumes_out};
+        void *const mem[N_OUT] = {totals_out, sasa_out, iso_out, masks_out, class_sums_out, residues_out, sel_area_out, group_areas_out, volumes_out};
         for (int k = 0; k < N_OUT; ++k) io.out[k].mem = mem[k];
         io.stats = stats;
         return traj_run_mem(io, s, stats_out, partials_out, err_out, err_len);
@@ -1244,7 +1271,7 @@ extern "C" int freesasa_gpu_trajectory_groups_stats(const double *xyz_frames, in
 {
     return trajectory_mem_topo(xyz_frames, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups, alg, probe, resolution,
                                frames_per_batch, totals_out, sasa_out, class_sums_out, residues_out, sel_area_out, sel_atoms_out, group_areas_out, iso_out,
-                               nullptr, devices, n_devices, stats, stats_out, partials_out, err_out, err_len);
+                               nullptr, nullptr, devices, n_devices, stats, stats_out, partials_out, err_out, err_len);
 }
 
 /* what both volume entries refuse before a device is touched or a file opened: 0, or -1 with the message */
@@ -1273,7 +1300,36 @@ extern "C" int freesasa_gpu_trajectory_volume(const double *xyz_frames, int n_fr
     if (volume_traj_check(alg, resolution, 0, volumes_out, err_out, err_len)) return -1;
     return trajectory_mem_topo(xyz_frames, n_frames, batch, structure, frame_atoms, atom_index, sel, nullptr, 0, alg, probe, resolution,
                                frames_per_batch, totals_out, sasa_out, class_sums_out, residues_out, sel_area_out, sel_atoms_out, nullptr, nullptr,
-                               volumes_out, devices, n_devices, 0, nullptr, nullptr, err_out, err_len);
+                               volumes_out, nullptr, devices, n_devices, 0, nullptr, nullptr, err_out, err_len);
+}
+
+/* what both mask entries refuse before a device is touched or a file opened: 0, or -1 with the message */
+static int masks_traj_check(int alg, int resolution, int frames_f32, const void *masks, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (!masks) return set_err(err_out, err_len, "null argument: the exposure masks have nowhere to go");
+    if (alg != 1) return set_err(err_out, err_len, "the exposure masks are those of the Shrake-Rupley test points: Lee-Richards is not offered");
+    if (frames_f32 & (FREESASA_GPU_FRAMES_PBC | FREESASA_GPU_FRAMES_TRICLINIC))
+        return set_err(err_out, err_len, "bit 3 and bit 4 of frames_f32 (periodic images) are not offered with the exposure masks");
+    if (resolution > SR_CAP_POINTS_MAX) {
+        char msg[120];
+        snprintf(msg, sizeof msg, "the exposure masks are offered up to %d test points (%d asked for)", SR_CAP_POINTS_MAX, resolution);
+        return set_err(err_out, err_len, msg);
+    }
+    return 0;
+}
+
+extern "C" int freesasa_gpu_trajectory_masks(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
+                                             int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
+                                             int alg, double probe, int resolution, int frames_per_batch,
+                                             double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
+                                             double *sel_area_out, long long *sel_atoms_out, uint32_t *masks_out,
+                                             const int *devices, int n_devices, char *err_out, int err_len)
+{
+    if (masks_traj_check(alg, resolution, 0, masks_out, err_out, err_len)) return -1;
+    return trajectory_mem_topo(xyz_frames, n_frames, batch, structure, frame_atoms, atom_index, sel, nullptr, 0, alg, probe, resolution,
+                               frames_per_batch, totals_out, sasa_out, class_sums_out, residues_out, sel_area_out, sel_atoms_out, nullptr, nullptr,
+                               nullptr, masks_out, devices, n_devices, 0, nullptr, nullptr, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_trajectory_groups(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
@@ -1531,7 +1587,7 @@ static int trajectory_file_topo(const char *frames_path, int frames_f32, long lo
                                 int alg, double probe, int resolution, int frames_per_batch,
                                 const char *totals_path, const char *sasa_path, const char *class_sums_path,
                                 const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
-                                const char *group_areas_path, const char *iso_path, const char *volumes_path,
+                                const char *group_areas_path, const char *iso_path, const char *volumes_path, const char *masks_path,
                                 const char *done_path, long long max_new_shards, const int *devices, int n_devices,
                                 long long *frames_total_out, int stats, const char *stats_path, const char *partials_path, char *err_out, int err_len)
 {
@@ -1546,7 +1602,7 @@ static int trajectory_file_topo(const char *frames_path, int frames_f32, long lo
         TrajSpec s = {tp.radii, tp.n, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, &tp, max_new_shards};
         TrajIO io;
         io.sel_atoms = sel_atoms_out;
-        const char *const path[N_OUT] = {totals_path, sasa_path, iso_path, class_sums_path, residues_path, sel_area_path, group_areas_path, volumes_path};
+        const char *const path[N_OUT] = {totals_path, sasa_path, iso_path, masks_path, class_sums_path, residues_path, sel_area_path, group_areas_path, volumes_path};
         for (int k = 0; k < N_OUT; ++k) io.out[k].path = path[k];
         io.stats = stats; io.stats_path = stats_path; io.parts_path = partials_path;
         return trajectory_file_run(frames_path, frames_f32, header_bytes, s, io, done_path, frames_total_out, err_out, err_len);
@@ -1574,7 +1630,7 @@ extern "C" int freesasa_gpu_trajectory_file_groups_stats(const char *frames_path
         return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) is not offered with chain groups: an isolated group among periodic images is not defined");
     return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,
                                 alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
-                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, done_path, max_new_shards, devices, n_devices,
+                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
                                 frames_total_out, stats, stats_path, partials_path, err_out, err_len);
 }
 
@@ -1596,7 +1652,7 @@ extern "C" int freesasa_gpu_trajectory_file_groups(const char *frames_path, int 
         return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) is not offered with chain groups: an isolated group among periodic images is not defined");
     return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,
                                 alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
-                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, done_path, max_new_shards, devices, n_devices,
+                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
                                 frames_total_out, 0, nullptr, nullptr, err_out, err_len);
 }
 
@@ -1611,7 +1667,7 @@ extern "C" int freesasa_gpu_trajectory_file_topology(const char *frames_path, in
 {
     return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, nullptr, 0,
                                 alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
-                                sel_area_path, sel_atoms_out, nullptr, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
+                                sel_area_path, sel_atoms_out, nullptr, nullptr, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
                                 frames_total_out, 0, nullptr, nullptr, err_out, err_len);
 }
 
@@ -1628,7 +1684,24 @@ extern "C" int freesasa_gpu_trajectory_file_volume(const char *frames_path, int 
     if (volume_traj_check(alg, resolution, frames_f32, volumes_path, err_out, err_len)) return -1;
     return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, nullptr, 0,
                                 alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
-                                sel_area_path, sel_atoms_out, nullptr, nullptr, volumes_path, done_path, max_new_shards, devices, n_devices,
+                                sel_area_path, sel_atoms_out, nullptr, nullptr, volumes_path, nullptr, done_path, max_new_shards, devices, n_devices,
+                                frames_total_out, 0, nullptr, nullptr, err_out, err_len);
+}
+
+extern "C" int freesasa_gpu_trajectory_file_masks(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
+                                                  const freesasa_ingest_batch *batch, int structure,
+                                                  int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
+                                                  int alg, double probe, int resolution, int frames_per_batch,
+                                                  const char *totals_path, const char *sasa_path, const char *class_sums_path,
+                                                  const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
+                                                  const char *masks_path,
+                                                  const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                                  long long *frames_total_out, char *err_out, int err_len)
+{
+    if (masks_traj_check(alg, resolution, frames_f32, masks_path, err_out, err_len)) return -1;
+    return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, nullptr, 0,
+                                alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
+                                sel_area_path, sel_atoms_out, nullptr, nullptr, nullptr, masks_path, done_path, max_new_shards, devices, n_devices,
                                 frames_total_out, 0, nullptr, nullptr, err_out, err_len);
 }
 

@@ -131,7 +131,8 @@ extern "C" void freesasa_gpu_ctx_destroy(freesasa_gpu_ctx *c)
                      &c->g_meta, &c->g_key, &c->g_count, &c->g_cursor, &c->g_xyz, &c->g_radii, &c->g_src, &c->g_sasa,
                      &c->g_gath, &c->g_tot, &c->g_tot2, &c->gi_tab, &c->gi_words, &c->gi_label,
                      &c->p_meta, &c->p_ibase, &c->p_xyz, &c->p_radii, &c->p_sasa, &c->p_chunks, &c->p_part,
-                     &c->v_counts, &c->v_evec, &c->v_vol, &c->v_origin, &c->v_volumes};
+                     &c->v_counts, &c->v_evec, &c->v_vol, &c->v_origin, &c->v_volumes,
+                     &c->dt_masks, &c->dt_first, &c->dt_bsum, &c->dt_xyz, &c->dt_atom, &c->dt_point, &c->dt_unit};
     for (DevBuf *b : all)
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : c->parse)
@@ -587,7 +588,13 @@ static int run_batch_once(freesasa_gpu_ctx *c, bool lr, const double *d_xyz, con
                 else if (atoi(e) == 0) tn = 0;
             }
             c->captab_n = c->captab_l = 0;
-            if (tn > 0 && sr_captab_build(c->unit_host.data(), resolution, tn, tl, c->captab_host)) {
+            /* (the table's host copy is a std::vector: if it cannot be had, the points count as not seen - else the next batch
+               with these points would find them uploaded, build no table and run the second arrangement for good; found by the
+               masks' walk of failing allocations at alternating point counts, tests/test_dots_hostfault.py) */
+            bool built = false;
+            try { built = tn > 0 && sr_captab_build(c->unit_host.data(), resolution, tn, tl, c->captab_host); }
+            catch (...) { c->unit_host.clear(); throw; }
+            if (built) {
                 const size_t bytes = sizeof(SrCapEntry) * c->captab_host.size();
                 if (ensure(c, c->captab, bytes)) { c->unit_host.clear(); return -1; }
                 if (hipMemcpyAsync(c->captab.p, c->captab_host.data(), bytes, hipMemcpyHostToDevice, st) != hipSuccess) {
@@ -603,11 +610,16 @@ static int run_batch_once(freesasa_gpu_ctx *c, bool lr, const double *d_xyz, con
     /* a volume (gpu_volume.hip: c->vol_evec) is made by the third arrangement's store phase alone: without its table - and,
        below, for a launch sr_caps_shape sends to the second arrangement - the batch is refused, with the reason */
     double *const evec = lr ? nullptr : c->vol_evec;
-    if (evec && !sr_caps) {
-        if (resolution > SR_CAP_POINTS_MAX) return ctx_fail(c, "the volume is offered up to %d test points (%d asked for)", SR_CAP_POINTS_MAX, resolution);
+    /* the exposure masks (gpu_dots.hip: c->sr_masks) are that store phase's too, refused where the volume is; and one store
+       phase makes one of the two */
+    unsigned *const masks = lr ? nullptr : c->sr_masks;
+    if (evec && masks) return ctx_fail(c, "the exposure masks and the volume's vectors cannot be asked for in one batch: one store phase makes one of them");
+    const char *const what = masks ? "the exposure masks" : "the volume", *const is = masks ? "are" : "is", *const needs = masks ? "need" : "needs";
+    if ((evec || masks) && !sr_caps) {
+        if (resolution > SR_CAP_POINTS_MAX) return ctx_fail(c, "%s %s offered up to %d test points (%d asked for)", what, is, SR_CAP_POINTS_MAX, resolution);
         const char *e = getenv("FREESASA_AMD_SR_CAPS");
-        if (e && atoi(e) == 0 && !strchr(e, ',')) return ctx_fail(c, "the volume needs the cap-mask kernel, which FREESASA_AMD_SR_CAPS=0 switches off");
-        return ctx_fail(c, "the volume needs unit test points: these are not unit vectors");
+        if (e && atoi(e) == 0 && !strchr(e, ',')) return ctx_fail(c, "%s %s the cap-mask kernel, which FREESASA_AMD_SR_CAPS=0 switches off", what, needs);
+        return ctx_fail(c, "%s %s unit test points: these are not unit vectors", what, needs);
     }
     TileCfg cfg = choose_cfg(resolution, lr, c->hint_res[hi] == resolution ? c->hint_pool[hi] : 0, sr_caps, c->hint_res[hi] == resolution ? c->hint_ta[hi] : 0);
     if (const char *e = getenv("FREESASA_AMD_CFG")) { /* tuning aid: "B,TA,pool,ds" */
@@ -653,9 +665,9 @@ static int run_batch_once(freesasa_gpu_ctx *c, bool lr, const double *d_xyz, con
     if (!lr) {
         ta.unit_pts = (const double *)c->unit_pts.p;
         if (sr_caps) { ta.captab = c->captab.p; ta.cap_n = c->captab_n; ta.cap_l = c->captab_l; }
-        if (evec && !sr_caps_shape(cfg, ta, false))
-            return ctx_fail(c, "the volume needs the cap-mask kernel, and this tile shape runs the second arrangement (%d records per atom, at most 128; %s survivor table)",
-                            cfg.cap_idx, cfg.tab ? "with a" : "without a");
+        if ((evec || masks) && !sr_caps_shape(cfg, ta, false))
+            return ctx_fail(c, "%s %s the cap-mask kernel, and this tile shape runs the second arrangement (%d records per atom, at most 128; %s survivor table)",
+                            what, needs, cfg.cap_idx, cfg.tab ? "with a" : "without a");
     }
 
     /* workgroups loop over tiles (w, w + grid, ...): ~150k workgroups measured ~2% better than
@@ -668,7 +680,7 @@ static int run_batch_once(freesasa_gpu_ctx *c, bool lr, const double *d_xyz, con
     }
     hipError_t le;
     const bool bucket = lr && c->hint_bucket && c->hint_res[0] == resolution;
-    le = lr ? kl_lr_tile(0, cfg, ta, grid_main, cfg.lds, st, bucket) : kl_sr_tile(0, cfg, ta, grid_main, cfg.lds, st, evec);
+    le = lr ? kl_lr_tile(0, cfg, ta, grid_main, cfg.lds, st, bucket) : kl_sr_tile(0, cfg, ta, grid_main, cfg.lds, st, evec, masks);
     if (le != hipSuccess) return ctx_fail(c, "tile kernel launch failed: %s", hipGetErrorString(le));
     if (c->timing) HIP_TRY(c, hipEventRecord(ctx_ev(c)[2], st));
 
@@ -683,7 +695,7 @@ static int run_batch_once(freesasa_gpu_ctx *c, bool lr, const double *d_xyz, con
         tm.ovf_tiles = (int *)c->ovf_tiles2.p;
         tm.ovf_count = (int *)c->status.p + ST_OVF2_TILES;
         const int grid_mid = n_tiles < SASA_MID_BLOCKS ? n_tiles : SASA_MID_BLOCKS;
-        le = lr ? kl_lr_tile(1, mc, tm, grid_mid, mc.lds, st, bucket) : kl_sr_tile(1, mc, tm, grid_mid, mc.lds, st, evec);
+        le = lr ? kl_lr_tile(1, mc, tm, grid_mid, mc.lds, st, bucket) : kl_sr_tile(1, mc, tm, grid_mid, mc.lds, st, evec, masks);
         if (le != hipSuccess) return ctx_fail(c, "second tile launch failed: %s", hipGetErrorString(le));
     }
     /* third launch: whatever is left (pathological densities), lists in a global slab */
@@ -732,13 +744,13 @@ static int run_batch_once(freesasa_gpu_ctx *c, bool lr, const double *d_xyz, con
     if (rcs) return rcs;
     /* a volume: the tiles the main launch handed on were redone by the second launch - the third arrangement too, if
        sr_caps_shape says so - and what that handed on by the last launch, which never is: their atoms have no vectors */
-    if (evec) {
+    if (evec || masks) {
         const TileCfg mc = mid_cfg(cfg, lr);
         TileArgs tm = ta;
         tm.cap_idx = mc.cap_idx;
         if (status_h[ST_OVF2_TILES] > 0 || (status_h[ST_OVF_TILES] > 0 && !sr_caps_shape(mc, tm, false)))
-            return ctx_fail(c, "the volume needs the cap-mask kernel, and %d tiles of this batch have neighbour lists beyond its limits (more than 128 records per atom): they ran the second arrangement",
-                            status_h[ST_OVF2_TILES] > 0 ? status_h[ST_OVF2_TILES] : status_h[ST_OVF_TILES]);
+            return ctx_fail(c, "%s %s the cap-mask kernel, and %d tiles of this batch have neighbour lists beyond its limits (more than 128 records per atom): they ran the second arrangement",
+                            what, needs, status_h[ST_OVF2_TILES] > 0 ? status_h[ST_OVF2_TILES] : status_h[ST_OVF_TILES]);
     }
     if (total_cells + total_cells / 32 > c->cells_hint) c->cells_hint = total_cells + total_cells / 32;
     kl_dump_phase_clocks();

@@ -656,7 +656,43 @@ __global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(SR_CAPS_WPE, 
         __syncthreads();
         sr_caps_exact(a, m, tid, B, items);
         __syncthreads();
-        sr_caps_store<true>(a, m, tile, tid, evec);
+        sr_caps_store<SR_STORE_EVEC>(a, m, tile, tid, evec);
+        __syncthreads();
+    }
+    tile_report_flush(a, tid, wg_max_nn);
+}
+
+/* ... and with the exposure masks kept (gpu_dots.hip): the same phases, the store phase the one that also writes every atom's
+   four mask words into masks [n_atoms][SR_CAP_WORDS] (sr_caps_store<SR_STORE_MASK>).  A kernel of its own with the masks' place
+   as an argument of its own, for the reason written above k_sr_tile_vol: TileArgs must not grow. */
+template <int B, int TIER>
+__global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(SR_CAPS_WPE, SR_CAPS_WPE))) void k_sr_tile_mask(TileArgs a, int items, unsigned *masks)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x;
+    PIPE_GATE(a.status);
+    TileMem m = tile_carve<false>(a, smem, items, B, blockIdx.x);
+    const int n_work = a.work_tiles ? *a.work_count : ((a.n_tiles + 7) >> 3) << 3;
+    int wg_max_nn = 0;
+    for (int w = blockIdx.x; w < n_work; w += gridDim.x) {
+        const int tile = a.work_tiles ? a.work_tiles[w] : xcd_tile(w, a.n_tiles);
+        if (tile >= a.n_tiles) continue;
+        sr_phase_load(a, m, tile, tid, B);
+        sr_caps_clear(a, m, tile, tid, B);
+        __syncthreads();
+        sr_phase_neighbors(a, m, tile, tid, B);
+        __syncthreads();
+        sr_caps_lists(a, m, tid);
+        __syncthreads();
+        sr_report<false>(a, m, tile, tid, wg_max_nn);
+        SrCapRegs regs;
+        sr_caps_lookup_pass(a, m, tid, B, regs);
+        __syncthreads();
+        sr_caps_todo_pass(a, m, tid, B, items, regs);
+        __syncthreads();
+        sr_caps_exact(a, m, tid, B, items);
+        __syncthreads();
+        sr_caps_store<SR_STORE_MASK>(a, m, tile, tid, nullptr, masks);
         __syncthreads();
     }
     tile_report_flush(a, tid, wg_max_nn);
@@ -693,11 +729,12 @@ static hipError_t launch_lr(const TileCfg &c, const TileArgs &t, int grid, size_
     return hipGetLastError();
 }
 template <bool GLOBAL, int TIER>
-static hipError_t launch_sr(const TileCfg &c, const TileArgs &t, int grid, size_t lds, hipStream_t s, double *evec)
+static hipError_t launch_sr(const TileCfg &c, const TileArgs &t, int grid, size_t lds, hipStream_t s, double *evec, unsigned *masks)
 {
     if constexpr (!GLOBAL) {
         /* the third arrangement (sr_caps.h) where its table exists and a wave's lanes hold an atom's list (C <= 128):
-           sr_caps_shape; with evec the builds whose store phase makes the volume's vectors */
+           sr_caps_shape; with evec the builds whose store phase makes the volume's vectors, with masks the builds whose
+           store phase keeps the exposure masks (the engine refuses a batch that asks for both) */
         if (sr_caps_shape(c, t, false)) {
             if (evec) {
                 if (c.B == 256)
@@ -706,6 +743,16 @@ static hipError_t launch_sr(const TileCfg &c, const TileArgs &t, int grid, size_
                     hipLaunchKernelGGL((k_sr_tile_vol<128, TIER>), dim3(grid), dim3(128), lds, s, t, c.items, evec);
                 else if (c.B == 64)
                     hipLaunchKernelGGL((k_sr_tile_vol<64, TIER>), dim3(grid), dim3(64), lds, s, t, c.items, evec);
+                else return hipErrorInvalidValue;
+                return hipGetLastError();
+            }
+            if (masks) {
+                if (c.B == 256)
+                    hipLaunchKernelGGL((k_sr_tile_mask<256, TIER>), dim3(grid), dim3(256), lds, s, t, c.items, masks);
+                else if (c.B == 128)
+                    hipLaunchKernelGGL((k_sr_tile_mask<128, TIER>), dim3(grid), dim3(128), lds, s, t, c.items, masks);
+                else if (c.B == 64)
+                    hipLaunchKernelGGL((k_sr_tile_mask<64, TIER>), dim3(grid), dim3(64), lds, s, t, c.items, masks);
                 else return hipErrorInvalidValue;
                 return hipGetLastError();
             }
@@ -741,7 +788,9 @@ static void allow_large_lds()
                              (const void *)k_sr_tile<256, false, 0, true>, (const void *)k_sr_tile<128, false, 0, true>, (const void *)k_sr_tile<64, false, 0, true>,
                              (const void *)k_sr_tile<256, false, 1, true>, (const void *)k_sr_tile<128, false, 1, true>, (const void *)k_sr_tile<64, false, 1, true>,
                              (const void *)k_sr_tile_vol<256, 0>, (const void *)k_sr_tile_vol<128, 0>, (const void *)k_sr_tile_vol<64, 0>,
-                             (const void *)k_sr_tile_vol<256, 1>, (const void *)k_sr_tile_vol<128, 1>, (const void *)k_sr_tile_vol<64, 1>};
+                             (const void *)k_sr_tile_vol<256, 1>, (const void *)k_sr_tile_vol<128, 1>, (const void *)k_sr_tile_vol<64, 1>,
+                             (const void *)k_sr_tile_mask<256, 0>, (const void *)k_sr_tile_mask<128, 0>, (const void *)k_sr_tile_mask<64, 0>,
+                             (const void *)k_sr_tile_mask<256, 1>, (const void *)k_sr_tile_mask<128, 1>, (const void *)k_sr_tile_mask<64, 1>};
         for (const void *fn : fns) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
 }
@@ -753,12 +802,12 @@ hipError_t kl_lr_tile(int tier, const TileCfg &c, const TileArgs &t, int grid, s
     if (tier == 1) return launch_lr<false, 1>(c, t, grid, lds, st, bucket);
     return launch_lr<true, 2>(c, t, grid, lds, st, false);
 }
-hipError_t kl_sr_tile(int tier, const TileCfg &c, const TileArgs &t, int grid, size_t lds, hipStream_t st, double *evec)
+hipError_t kl_sr_tile(int tier, const TileCfg &c, const TileArgs &t, int grid, size_t lds, hipStream_t st, double *evec, unsigned *masks)
 {
     allow_large_lds();
-    if (tier == 0) return launch_sr<false, 0>(c, t, grid, lds, st, evec);
-    if (tier == 1) return launch_sr<false, 1>(c, t, grid, lds, st, evec);
-    return launch_sr<true, 2>(c, t, grid, lds, st, nullptr); /* (the slab launch: the second arrangement, no vectors) */
+    if (tier == 0) return launch_sr<false, 0>(c, t, grid, lds, st, evec, masks);
+    if (tier == 1) return launch_sr<false, 1>(c, t, grid, lds, st, evec, masks);
+    return launch_sr<true, 2>(c, t, grid, lds, st, nullptr, nullptr); /* (the slab launch: the second arrangement, no vectors, no masks) */
 }
 
 hipError_t kl_prep_fused(const PipeArgs &pa, hipStream_t st)
@@ -808,6 +857,52 @@ hipError_t kl_vol_origin(const VolArgs &a, hipStream_t st)
 hipError_t kl_vol_atom(const VolArgs &a, hipStream_t st)
 {
     hipLaunchKernelGGL(k_vol_atom, dim3((unsigned)((a.n_atoms + VOL_B - 1) / VOL_B)), dim3(VOL_B), 0, st, a);
+    return hipGetLastError();
+}
+
+/* surface dots (dots_kernels.h): the scan of the masks' popcounts in three plain launches - the blocks' sums, ONE workgroup over
+   them, dot_first - and the expansion, one lane per (atom, point) pair */
+__global__ __launch_bounds__(DOTS_SCAN_T) void k_dots_block_sums(DotsArgs a)
+{
+    __shared__ int part[DOTS_SCAN_T];
+    dots_count_phase0(a, part, blockIdx.x, threadIdx.x);
+    __syncthreads();
+    dots_count_phase1(a, part, blockIdx.x, threadIdx.x);
+}
+__global__ __launch_bounds__(DOTS_SCAN_T) void k_dots_scan_blocks(DotsArgs a)
+{
+    __shared__ int64_t part[DOTS_SCAN_T];
+    dots_scan_phase0(a, part, threadIdx.x);
+    __syncthreads();
+    dots_scan_phase1(a, part, threadIdx.x);
+    __syncthreads();
+    dots_scan_phase2(a, part, threadIdx.x);
+}
+__global__ __launch_bounds__(DOTS_SCAN_T) void k_dots_first(DotsArgs a)
+{
+    __shared__ int part[DOTS_SCAN_T];
+    dots_first_phase0(a, part, blockIdx.x, threadIdx.x);
+    __syncthreads();
+    dots_first_phase1(a, part, blockIdx.x, threadIdx.x);
+    __syncthreads();
+    dots_first_phase2(a, part, blockIdx.x, threadIdx.x);
+}
+__global__ __launch_bounds__(DOTS_EXPAND_B) void k_dots_expand(DotsArgs a)
+{
+    dots_expand(a, (int64_t)blockIdx.x, threadIdx.x);
+}
+hipError_t kl_dots_count(const DotsArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_dots_block_sums, dim3((unsigned)a.n_blocks), dim3(DOTS_SCAN_T), 0, st, a);
+    hipLaunchKernelGGL(k_dots_scan_blocks, dim3(1), dim3(DOTS_SCAN_T), 0, st, a);
+    hipLaunchKernelGGL(k_dots_first, dim3((unsigned)a.n_blocks), dim3(DOTS_SCAN_T), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_dots_expand(const DotsArgs &a, hipStream_t st)
+{
+    const int64_t pairs = a.n_atoms * a.n_points;
+    const int64_t per_wg = (int64_t)DOTS_EXPAND_B * DOTS_EXPAND_U;
+    hipLaunchKernelGGL(k_dots_expand, dim3((unsigned)((pairs + per_wg - 1) / per_wg)), dim3(DOTS_EXPAND_B), 0, st, a);
     return hipGetLastError();
 }
 hipError_t kl_segment_sums(const double *d_sasa, const int64_t *d_seg, int n_segs, bool short_segments, double *d_out, hipStream_t st)

@@ -275,13 +275,19 @@ SASA_D void sr_caps_exact(const TileArgs &a, TileMem &m, int tid, int B, int ite
     }
 }
 
-/* VOL (the volume's builds, k_sr_tile_vol; evec [3 n_atoms], original order): beside the area, E_i = the sum of the atom's exposed unit points, taken in ascending
+/* MODE: what the store phase writes beside the area and the count.
+   SR_STORE_EVEC (the volume's builds, k_sr_tile_vol; evec [3 n_atoms], original order): E_i = the sum of the atom's exposed unit points, taken in ascending
    point order from (0, 0, 0), component by component - the mask never leaves the LDS, so this is the only place that can
-   make it (vol_kernels.h has the definition of the volume built on it).  A tile that overflowed (flags[0]) stores nothing
-   here and is redone by a later launch: every atom's vector is written exactly once.  The builds without VOL are the
-   builds they were. */
-template <bool VOL = false>
-SASA_D void sr_caps_store(const TileArgs &a, TileMem &m, int tile, int tid, double *evec = nullptr)
+   make it (vol_kernels.h has the definition of the volume built on it).
+   SR_STORE_MASK (the dots' builds, k_sr_tile_mask; masks [n_atoms][SR_CAP_WORDS], original order): the exposure mask itself, bit
+   k & 31 of word k >> 5 set iff point k is exposed, bits >= n_res 0, the four words in one 16-byte store (dots_kernels.h
+   makes the dots of it).
+   A tile that overflowed (flags[0]) stores nothing here and is redone by a later launch: every atom's vector or mask is
+   written exactly once.  The builds of SR_STORE_NONE are the builds they were. */
+enum { SR_STORE_NONE = 0, SR_STORE_EVEC = 1, SR_STORE_MASK = 2 };
+struct alignas(16) SrMaskWords { unsigned w[SR_CAP_WORDS]; };
+template <int MODE = SR_STORE_NONE>
+SASA_D void sr_caps_store(const TileArgs &a, TileMem &m, int tile, int tid, double *evec = nullptr, unsigned *masks = nullptr)
 {
     if (m.flags[0]) return;
     const int na = tile_atoms(a, tile);
@@ -300,7 +306,7 @@ SASA_D void sr_caps_store(const TileArgs &a, TileMem &m, int tile, int tid, doub
         const int i = m.aexp[tid]; /* (sr_caps_clear) */
         a.sasa[i] = (4.0 * SASA_PI * ri * ri * n_surface) / a.n_res; /* ref: src/sasa_sr.c:337 */
         if (a.counts) a.counts[i] = n_surface;
-        if constexpr (VOL) {
+        if constexpr (MODE == SR_STORE_EVEC) {
             /* (a point per trip.  Four points per trip - their twelve loads issued together, the adds still in point order -
                was measured on the MI355X and gained nothing: 10.14 against 9.98 ms per step of the coil batch,
                profiles/volume_bench.md) */
@@ -313,6 +319,10 @@ SASA_D void sr_caps_store(const TileArgs &a, TileMem &m, int tile, int tid, doub
                     ex += upts[3 * k]; ey += upts[3 * k + 1]; ez += upts[3 * k + 2];
                 }
             evec[3 * (size_t)i] = ex; evec[3 * (size_t)i + 1] = ey; evec[3 * (size_t)i + 2] = ez;
+        } else if constexpr (MODE == SR_STORE_MASK) {
+            SrMaskWords e;
+            for (int w = 0; w < SR_CAP_WORDS; ++w) e.w[w] = ~dw[w] & sr_cap_full_word(a.n_res, w);
+            *(SrMaskWords *)(masks + SR_CAP_WORDS * (size_t)i) = e;
         } else (void)dw;
     }
 }

@@ -1052,6 +1052,88 @@ int freesasa_gpu_trajectory_file_volume(const char *frames_path, int frames_f32,
                                         const char *done_path, long long max_new_shards, const int *devices, int n_devices,
                                         long long *frames_total_out, char *err, int err_len);
 
+/* EXPOSURE MASKS AND SURFACE DOTS: which Shrake-Rupley test points of every atom are exposed, and those points in space - the
+   Connolly dots of `gmx sasa -q`.  The mask is the compact, lossless form of the dots (16 bytes per atom, where the dots of a
+   protein atom take about 600): counts, dots and anything else made of the exposed points follow from it later without the engine.
+   The definitions (csrc/dots_kernels.h; tests/dots_ref.py restates them in numpy).  Probe p, the N = n_points unit points u_k
+   of freesasa_gpu_test_points(N), R_i = r_i + p:
+     mask        uint32 [n_atoms][4], atoms in the caller's order: bit k & 31 of word k >> 5 of atom i is SET iff point k of atom
+                 i is EXPOSED (by the engine's own test: what makes `counts`); bits k >= N are 0; popcount(mask_i) == counts[i]
+     dot_first   int64 [n_atoms + 1]: the exclusive prefix sum of popcount(mask_i & the N bits that exist), taken from the masks
+                 themselves.  D = dot_first[n_atoms]; the dots of structure s are dot_first[offsets[s]] .. dot_first[offsets[s + 1]]
+     dots        for atom i ascending, within it for exposed k ascending, one dot at slot dot_first[i] + rank:
+                 dot_xyz[3 slot ..] fp64, per component t = u_k * R_i; t += x_i - the engine's own test point, every operation
+                 rounded on its own; optional dot_atom[slot] = i and dot_point[slot] = k (int32)
+   The outward normal of a dot is u_k (freesasa_gpu_test_points(N)[dot_point]) and the area it stands for 4 pi R_i^2 / N: no array
+   is delivered for either.
+   freesasa_gpu_sr_masks_dev: freesasa_gpu_sr_batch_dev with the masks kept: arrays on the device, offsets on the host,
+   synchronous.  d_sasa, d_counts and d_totals are that entry's bit for bit (d_counts, d_totals may be NULL); d_masks
+   [n_atoms][4] is required, here and in the two entries below aligned to 16 bytes (-1 with a message otherwise).  The batch goes through the engine ONCE: the mask is one more output of the tile kernel's store
+   phase, written in one 16-byte store per atom.
+   REFUSED, -1 with a message that names the reason, nothing returned: more than 128 test points; test points that are not unit
+   vectors; FREESASA_AMD_SR_CAPS=0; a launch, or tiles of a batch, whose neighbour lists are beyond the cap-mask kernel's limits
+   (more than 128 records per atom) and run the engine's second arrangement.  A mask made any other way is never returned.  The
+   context stays usable.  Argument errors (NULL, n_points <= 0, bad offsets, an empty batch): -1 before a device is touched.
+   freesasa_gpu_dots_count_dev: dot_first of masks that are on the device (three plain launches; everything int64: 2^24 atoms
+   with 128 exposed points have more than 2^31 dots) and D into *n_dots_out; synchronous.
+   freesasa_gpu_dots_expand_dev: the dots of masks and their dot_first, into arrays that hold `capacity` dots: nothing is ever
+   written at or beyond slot `capacity`, or outside an atom's own run of slots, whatever the masks and dot_first say; bits at or
+   above n_points are ignored.  d_dot_atom and d_dot_point may be NULL.  D == 0 or capacity == 0: nothing is launched.
+   Not offered: more than 128 points; Lee-Richards; masks among periodic images; masks in the plain (radii, n_atoms) trajectory
+   entries, the group entries and the file and cache sweeps; fp32 dots; the volume's E_i made from stored masks instead of in
+   the store phase (masks and the volume in one batch are refused: one store phase makes one of them). */
+int freesasa_gpu_sr_masks_dev(freesasa_gpu_ctx *ctx, const double *d_xyz, const double *d_radii, const int64_t *offsets,
+                              int n_structs, double probe_radius, int n_points, double *d_sasa, int *d_counts, double *d_totals,
+                              uint32_t *d_masks);
+int freesasa_gpu_dots_count_dev(freesasa_gpu_ctx *ctx, const uint32_t *d_masks, long long n_atoms, int n_points,
+                                int64_t *d_dot_first, long long *n_dots_out);
+int freesasa_gpu_dots_expand_dev(freesasa_gpu_ctx *ctx, const double *d_xyz, const double *d_radii, long long n_atoms,
+                                 double probe_radius, int n_points, const uint32_t *d_masks, const int64_t *d_dot_first,
+                                 long long capacity, double *d_dot_xyz, int *d_dot_atom, int *d_dot_point);
+/* The same on host arrays, on a pooled per-thread context like freesasa_gpu_calc_batch.  counts_out and totals_out may be
+   NULL; sasa_out [n] and masks_out [n][4] are required.  Returns 0 / -1 with err_out. */
+int freesasa_gpu_calc_masks(const double *xyz, const double *radii, const int64_t *offsets, int n_structs, double probe_radius,
+                            int n_points, double *sasa_out, int *counts_out, double *totals_out, uint32_t *masks_out,
+                            int device, char *err_out, int err_len);
+/* The number of dots stored masks hold (host array, no device): the sum of their popcounts into *n_dots_out - what sizes the
+   arrays of freesasa_gpu_dots_from_masks.  -1 with a message: NULL, n_atoms or n_points out of range, a bit at or above
+   n_points set. */
+int freesasa_gpu_masks_count(const uint32_t *masks, long long n_atoms, int n_points, long long *n_dots_out, char *err_out, int err_len);
+/* The dots of stored masks, host arrays: upload, scan and expansion on the device.  n_dots is what the caller holds the masks
+   to have (the sum of `counts`): -1 with a message before a device is touched if their popcount is another number or a bit at
+   or above n_points is set.  dot_xyz_out [3 n_dots] is required; dot_first_out [n_atoms + 1], dot_atom_out [n_dots] and
+   dot_point_out [n_dots] may be NULL. */
+int freesasa_gpu_dots_from_masks(const double *xyz, const double *radii, long long n_atoms, double probe_radius, int n_points,
+                                 const uint32_t *masks, long long n_dots, int64_t *dot_first_out, double *dot_xyz_out,
+                                 int *dot_atom_out, int *dot_point_out, int device, char *err_out, int err_len);
+/* ... and per frame of a trajectory: freesasa_gpu_trajectory_topology / freesasa_gpu_trajectory_file_topology with one more
+   output behind sel_atoms_out
+     masks       4 n uint32 per frame     (16 n f)       the masks of the frame's topology atoms: bit for bit masks_out of
+                                                         freesasa_gpu_calc_masks on the frame taken as a structure of its own
+   (memory form: masks_out [n_frames][n][4]; file form: masks_path, raw, frame f at byte 16 n f; required).  Every other output is
+   byte for byte that entry's; all file formats, fp32 input, a gather index, fp32 per-atom output and any device list work
+   unchanged.  alg must be Shrake-Rupley (1).  The done-list's first line names the mask output (128 in outputs=): a list of a
+   run without it and a list of a run with it refuse each other.  The dots of any frame follow from its masks and coordinates
+   with freesasa_gpu_dots_from_masks.
+   -1 with a message before a device is touched or a file opened: masks NULL, Lee-Richards, more than 128 points, bit 3 or 4 of
+   frames_f32 (periodic images).  Chain groups, a statistics word and the frames' volumes have entries of their own, which
+   take no masks. */
+int freesasa_gpu_trajectory_masks(const double *xyz_frames, int n_frames, const struct freesasa_ingest_batch *batch, int structure,
+                                  int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
+                                  int alg, double probe_radius, int resolution, int frames_per_batch,
+                                  double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
+                                  double *sel_area_out, long long *sel_atoms_out, uint32_t *masks_out,
+                                  const int *devices, int n_devices, char *err, int err_len);
+int freesasa_gpu_trajectory_file_masks(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
+                                       const struct freesasa_ingest_batch *batch, int structure,
+                                       int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
+                                       int alg, double probe_radius, int resolution, int frames_per_batch,
+                                       const char *totals_path, const char *sasa_path, const char *class_sums_path,
+                                       const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
+                                       const char *masks_path,
+                                       const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                       long long *frames_total_out, char *err, int err_len);
+
 #ifdef __cplusplus
 }
 #endif
