@@ -123,6 +123,19 @@ def lib():
                                               C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.freesasa_gpu_calc_groups.argtypes = [_dp, _dp, _lp, C.c_int, _i32p, _i32p, C.c_int, C.c_double, C.c_int,
                                                _dp, _dp, _dp, _dp, C.c_int, C.c_char_p, C.c_int]
+        _llp = C.POINTER(C.c_longlong)
+        L.freesasa_gpu_interface_pairs_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _lp, C.c_int, C.c_void_p, _i32p,
+                                                       C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_longlong, _llp, _llp, _i32p, _i32p, _llp]
+        L.freesasa_gpu_interfaces_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _lp, C.c_int, C.c_void_p, _i32p,
+                                                  C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_longlong, C.c_longlong, _llp, _llp, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]
+        L.freesasa_gpu_calc_interface_pairs.argtypes = [_dp, _dp, _lp, C.c_int, _i32p, _i32p, C.c_int, C.c_double, C.c_int,
+                                                        C.c_longlong, _llp, _llp, _i32p, _i32p, _llp, C.c_int, C.c_char_p, C.c_int]
+        L.freesasa_gpu_calc_interfaces.argtypes = [_dp, _dp, _lp, C.c_int, _i32p, _i32p, C.c_int, C.c_double, C.c_int,
+                                                   _dp, _dp, _dp, _dp, C.c_longlong, C.c_longlong, _llp, _llp, _i32p, _i32p, _dp,
+                                                   _lp, _i32p, _dp, C.c_int, C.c_char_p, C.c_int]
         L.freesasa_gpu_sr_volume_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _lp, C.c_int, C.c_double, C.c_int,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.freesasa_gpu_calc_volume.argtypes = [_dp, _dp, _lp, C.c_int, C.c_double, C.c_int, _dp, _ip, _dp, _dp, _dp, _dp,
@@ -258,6 +271,88 @@ def calc_groups(xyz, radii, offsets, group, n_groups, alg=LEE_RICHARDS, probe=1.
     if ret:
         raise RuntimeError("freesasa_gpu_calc_groups: " + err.value.decode())
     return sasa, iso, totals, gt
+
+
+def _group_batch(xyz, radii, offsets, group, n_groups):
+    xyz, radii = _f64(xyz).reshape(-1), _f64(radii)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    group = np.ascontiguousarray(group, dtype=np.int32)
+    n_groups = np.ascontiguousarray(n_groups, dtype=np.int32)
+    if group.size != radii.size or n_groups.size != offsets.size - 1:
+        raise ValueError("group needs one id per atom and n_groups one count per structure")
+    return xyz, radii, offsets, group, n_groups
+
+
+class InterfacePairs:
+    """The groups of a batch that touch: n_pairs, n_pair_atoms (the atoms of all pair structures), pair_struct [P] and
+    pair_groups [P, 2] (int32; structure-major, then g, then h ascending), n_tests and n_candidates (the pairs the screen
+    tested and those whose boxes came close)."""
+
+    def __init__(self, n_pairs, n_pair_atoms, pair_struct, pair_groups, n_tests, n_candidates):
+        self.n_pairs, self.n_pair_atoms = n_pairs, n_pair_atoms
+        self.pair_struct, self.pair_groups = pair_struct, pair_groups
+        self.n_tests, self.n_candidates = n_tests, n_candidates
+
+
+class Interfaces:
+    """calc_interfaces()'s result: sasa, iso [n], totals [n_structs], group_totals [G, 3] as calc_groups gives them; pair_struct
+    [P], pair_groups [P, 2], pair_areas [P, 6] = (iso_g, iso_h, in_pair_g, in_pair_h, buried_g, buried_h); with per_atom
+    side_offsets [2P + 1], pair_atom [M], pair_buried [M] (else None)."""
+
+    def __init__(self, sasa, iso, totals, group_totals, pair_struct, pair_groups, pair_areas, side_offsets, pair_atom, pair_buried):
+        self.sasa, self.iso, self.totals, self.group_totals = sasa, iso, totals, group_totals
+        self.pair_struct, self.pair_groups, self.pair_areas = pair_struct, pair_groups, pair_areas
+        self.side_offsets, self.pair_atom, self.pair_buried = side_offsets, pair_atom, pair_buried
+        self.n_pairs = int(pair_struct.size)
+
+
+def interface_pairs(xyz, radii, offsets, group, n_groups, alg=LEE_RICHARDS, probe=1.4, resolution=20, device=-1):
+    """freesasa_gpu_calc_interface_pairs() on host arrays: which groups of every structure are in contact (the reference's
+    neighbour test between their atoms; include/freesasa_gpu.h) -> InterfacePairs.  Two calls: the counts, then the list."""
+    xyz, radii, offsets, group, n_groups = _group_batch(xyz, radii, offsets, group, n_groups)
+    i32 = C.POINTER(C.c_int32)
+    P, M, err = C.c_longlong(0), C.c_longlong(0), C.create_string_buffer(512)
+    stats = (C.c_longlong * 2)()
+
+    def call(cap, ps, pg):
+        if lib().freesasa_gpu_calc_interface_pairs(xyz.ctypes.data_as(_dp), radii.ctypes.data_as(_dp), offsets.ctypes.data_as(_lp),
+                                                   offsets.size - 1, group.ctypes.data_as(i32), n_groups.ctypes.data_as(i32), alg,
+                                                   probe, resolution, cap, C.byref(P), C.byref(M),
+                                                   None if ps is None else ps.ctypes.data_as(i32),
+                                                   None if pg is None else pg.ctypes.data_as(i32), stats, device, err, 512):
+            raise RuntimeError("freesasa_gpu_calc_interface_pairs: " + err.value.decode())
+
+    call(0, None, None)
+    ps, pg = np.empty(P.value, dtype=np.int32), np.empty((P.value, 2), dtype=np.int32)
+    if P.value:
+        call(P.value, ps, pg)
+    return InterfacePairs(int(P.value), int(M.value), ps, pg, int(stats[0]), int(stats[1]))
+
+
+def calc_interfaces(xyz, radii, offsets, group, n_groups, alg=LEE_RICHARDS, probe=1.4, resolution=20, device=-1, per_atom=False):
+    """freesasa_gpu_calc_interfaces() on host arrays -> Interfaces: calc_groups()'s results and a row for every pair of groups of
+    a structure that are in contact, with each side's isolated area, its area in the pair taken on its own, and the
+    difference: the interface area.  The arrays are sized by a first interface_pairs() call."""
+    xyz, radii, offsets, group, n_groups = _group_batch(xyz, radii, offsets, group, n_groups)
+    n, ns = radii.size, offsets.size - 1
+    pairs = interface_pairs(xyz, radii, offsets, group, n_groups, alg, probe, resolution, device)
+    P, M = pairs.n_pairs, pairs.n_pair_atoms
+    G = int(n_groups.astype(np.int64).sum())
+    sasa, iso, totals, gt = np.empty(n), np.empty(n), np.empty(ns), np.empty((max(G, 0), 3))
+    ps, pg, areas = np.empty(P, dtype=np.int32), np.empty((P, 2), dtype=np.int32), np.empty((P, 6))
+    so, pa, pb = (np.empty(2 * P + 1, dtype=np.int64), np.empty(M, dtype=np.int32), np.empty(M)) if per_atom else (None, None, None)
+    i32 = C.POINTER(C.c_int32)
+    opt = lambda a, t: None if a is None else a.ctypes.data_as(t)
+    Pc, Mc, err = C.c_longlong(0), C.c_longlong(0), C.create_string_buffer(512)
+    ret = lib().freesasa_gpu_calc_interfaces(xyz.ctypes.data_as(_dp), radii.ctypes.data_as(_dp), offsets.ctypes.data_as(_lp), ns,
+                                             group.ctypes.data_as(i32), n_groups.ctypes.data_as(i32), alg, probe, resolution,
+                                             sasa.ctypes.data_as(_dp), iso.ctypes.data_as(_dp), totals.ctypes.data_as(_dp),
+                                             gt.ctypes.data_as(_dp), P, M, C.byref(Pc), C.byref(Mc), ps.ctypes.data_as(i32),
+                                             pg.ctypes.data_as(i32), areas.ctypes.data_as(_dp), opt(so, _lp), opt(pa, i32), opt(pb, _dp),
+                                             device, err, 512)
+    if ret:
+        raise RuntimeError("freesasa_gpu_calc_interfaces: " + err.value.decode())
+    return Interfaces(sasa, iso, totals, gt, ps, pg, areas, so, pa, pb)
 
 
 def calc_volume(xyz, radii, offsets, probe=1.4, n_points=100, device=-1, per_atom=False):
@@ -1631,6 +1726,39 @@ class GpuContext:
                                             d_iso, d_totals or None, d_group_totals or None)
         if ret:
             raise RuntimeError("freesasa_gpu_groups_dev: " + self.error())
+
+    def interface_pairs(self, d_xyz, d_radii, offsets, d_group, n_groups, pair_capacity=0, pair_struct=None, pair_groups=None,
+                        d_sasa=0, d_iso=0, d_totals=0, d_group_totals=0, alg=LEE_RICHARDS, probe=1.4, resolution=20):
+        """freesasa_gpu_interface_pairs_dev(): the contact screen behind groups() -> (n_pairs, n_pair_atoms, n_tests,
+        n_candidates); pair_struct [pair_capacity] and pair_groups [pair_capacity, 2]: host int32 arrays (None: the counts only)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        ng = np.ascontiguousarray(n_groups, dtype=np.int32)
+        i32 = C.POINTER(C.c_int32)
+        P, M, stats = C.c_longlong(0), C.c_longlong(0), (C.c_longlong * 2)()
+        if lib().freesasa_gpu_interface_pairs_dev(self._h, alg, d_xyz, d_radii, offsets.ctypes.data_as(_lp), offsets.size - 1, d_group,
+                                                  ng.ctypes.data_as(i32), probe, resolution, d_sasa or None, d_iso or None,
+                                                  d_totals or None, d_group_totals or None, pair_capacity, C.byref(P), C.byref(M),
+                                                  None if pair_struct is None else pair_struct.ctypes.data_as(i32),
+                                                  None if pair_groups is None else pair_groups.ctypes.data_as(i32), stats):
+            raise RuntimeError("freesasa_gpu_interface_pairs_dev: " + self.error())
+        return int(P.value), int(M.value), int(stats[0]), int(stats[1])
+
+    def interfaces(self, d_xyz, d_radii, offsets, d_group, n_groups, d_sasa, d_iso, pair_capacity, d_pair_areas, d_pair_struct=0,
+                   d_pair_groups=0, atom_capacity=0, d_side_offsets=0, d_pair_atom=0, d_pair_buried=0, d_totals=0, d_group_totals=0,
+                   alg=LEE_RICHARDS, probe=1.4, resolution=20):
+        """freesasa_gpu_interfaces_dev(): groups() and the pair table into device arrays that hold pair_capacity rows
+        (d_pair_areas [6 P], d_pair_struct [P], d_pair_groups [2 P], d_side_offsets [2 P + 1]) and atom_capacity atoms
+        (d_pair_atom, d_pair_buried [M]) -> (n_pairs, n_pair_atoms); a capacity that is too small: RuntimeError naming the number."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        ng = np.ascontiguousarray(n_groups, dtype=np.int32)
+        P, M = C.c_longlong(0), C.c_longlong(0)
+        if lib().freesasa_gpu_interfaces_dev(self._h, alg, d_xyz, d_radii, offsets.ctypes.data_as(_lp), offsets.size - 1, d_group,
+                                             ng.ctypes.data_as(C.POINTER(C.c_int32)), probe, resolution, d_sasa or None, d_iso or None,
+                                             d_totals or None, d_group_totals or None, pair_capacity, atom_capacity, C.byref(P),
+                                             C.byref(M), d_pair_struct or None, d_pair_groups or None, d_pair_areas or None,
+                                             d_side_offsets or None, d_pair_atom or None, d_pair_buried or None):
+            raise RuntimeError("freesasa_gpu_interfaces_dev: " + self.error())
+        return int(P.value), int(M.value)
 
     def periodic(self, d_xyz, d_radii, offsets, cells, d_sasa, d_totals=0, alg=LEE_RICHARDS, probe=1.4, resolution=20):
         """freesasa_gpu_periodic_dev(): every atom's area among the periodic images of its structure's cell (cells: a host

@@ -19,6 +19,8 @@
  *                      and the structures' volumes behind it; its device-pointer and host-pointer entries
  *   gpu_dots.hip       exposure masks and surface dots: the batch through the engine with the store phase's masks kept; the scan
  *                      of their popcounts and the expansion into dots; their device-pointer and host-pointer entries
+ *   gpu_interfaces.hip pairwise interface areas between chain groups: the contact screen behind the chain-group pipeline, the batch of
+ *                      the pair structures through the engine, the pair table; their device-pointer and host-pointer entries
  *   gpu_periodic.hip   periodic images: a batch and its cells (orthorhombic or triclinic) expanded into a batch with the
  *                      images that matter, the areas of the real atoms collected; the stage the trajectory file drivers share
  */
@@ -50,6 +52,7 @@
 #include "pbc_tri_kernels.h"
 #include "vol_kernels.h"
 #include "dots_kernels.h"
+#include "iface_kernels.h"
 #include "gpu_parse.h"
 
 /* ------------------------------------------------------------------ kernel launchers (gpu_kernels.hip) */
@@ -141,6 +144,15 @@ hipError_t kl_vol_atom(const sasa::VolArgs &a, hipStream_t st);
 hipError_t kl_dots_count(const sasa::DotsArgs &a, hipStream_t st);
 hipError_t kl_dots_expand(const sasa::DotsArgs &a, hipStream_t st);
 
+/* interfaces between chain groups (iface_kernels.h): the groups' boxes (one wave per group), the candidate pairs (one thread per
+   test), the exact contact (one workgroup per candidate at a time), the pair batch (one thread per atom), the finish (per atom,
+   then - behind kl_segment_sums over the sides - per row) */
+hipError_t kl_iface_box(const sasa::IfaceArgs &a, hipStream_t st);
+hipError_t kl_iface_candidates(const sasa::IfaceArgs &a, hipStream_t st);
+hipError_t kl_iface_contact(const sasa::IfaceArgs &a, hipStream_t st);
+hipError_t kl_iface_gather(const sasa::IfaceArgs &a, hipStream_t st);
+hipError_t kl_iface_finish(const sasa::IfaceArgs &a, hipStream_t st);
+
 /* ------------------------------------------------------------------ context (gpu_engine.hip) */
 
 struct DevBuf {
@@ -210,6 +222,9 @@ struct freesasa_gpu_ctx {
        there - or refuses the batch (run_batch_once); the host-pointer entries' masks, prefix sums, block sums and dots */
     unsigned *sr_masks = nullptr;
     DevBuf dt_masks, dt_first, dt_bsum, dt_xyz, dt_atom, dt_point, dt_unit;
+    /* interfaces between chain groups (gpu_interfaces.hip): group starts and test bases; boxes; the candidates' list, its length
+       and the flags; the sides' tables; the pair batch, its areas and what is made of them; the host-pointer entry's rows */
+    DevBuf if_meta, if_box, if_cand, if_flag, if_sides, if_xyz, if_radii, if_comb, if_sasa, if_inpair, if_areas, if_patom, if_pburied, if_rows;
     int dt_unit_n = 0; /* the point count whose unit points dt_unit holds (the expansion's; 0: none) */
     void *stage_in = nullptr, *stage_out = nullptr; /* page-locked host staging of freesasa_gpu_calc_batch_pipelined */
     size_t stage_in_cap = 0, stage_out_cap = 0;

@@ -132,7 +132,9 @@ extern "C" void freesasa_gpu_ctx_destroy(freesasa_gpu_ctx *c)
                      &c->g_gath, &c->g_tot, &c->g_tot2, &c->gi_tab, &c->gi_words, &c->gi_label,
                      &c->p_meta, &c->p_ibase, &c->p_xyz, &c->p_radii, &c->p_sasa, &c->p_chunks, &c->p_part,
                      &c->v_counts, &c->v_evec, &c->v_vol, &c->v_origin, &c->v_volumes,
-                     &c->dt_masks, &c->dt_first, &c->dt_bsum, &c->dt_xyz, &c->dt_atom, &c->dt_point, &c->dt_unit};
+                     &c->dt_masks, &c->dt_first, &c->dt_bsum, &c->dt_xyz, &c->dt_atom, &c->dt_point, &c->dt_unit,
+                     &c->if_meta, &c->if_box, &c->if_cand, &c->if_flag, &c->if_sides, &c->if_xyz, &c->if_radii, &c->if_comb, &c->if_sasa,
+                     &c->if_inpair, &c->if_areas, &c->if_patom, &c->if_pburied, &c->if_rows};
     for (DevBuf *b : all)
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : c->parse)

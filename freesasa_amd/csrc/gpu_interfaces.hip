@@ -1,0 +1,410 @@
+/*
+ * gpu_interfaces.hip — pairwise interface areas between chain groups (include/freesasa_gpu.h: freesasa_gpu_interface_pairs_dev,
+ * freesasa_gpu_interfaces_dev, freesasa_gpu_calc_interface_pairs, freesasa_gpu_calc_interfaces).  Host code; the kernels are in
+ * gpu_kernels.hip (phase functions: iface_kernels.h).
+ *
+ *   1. groups_resident   the chain-group pipeline as it is: the combined batch stays in c->g_xyz / g_radii / g_src, its areas in
+ *                        c->g_sasa, its totals in c->g_tot; the groups' atom counts are on the host
+ *   2. boxes             k_iface_box: one wave per isolated group
+ *   3. candidates        k_iface_candidates: one thread per pair (g < h) of a structure, the candidates appended to a list
+ *   4. exact contact     k_iface_contact: a workgroup per candidate at a time, one flag per pair
+ *   5. order and sizes   the flags come back (one stream synchronization, like the counts of step 1); the host walks them in
+ *                        the table's order: rows, side_offsets, P, M
+ *   6. pair batch        k_iface_gather: one thread per pair-structure atom
+ *   7. one run_batch     over the P pair structures: same algorithm, probe, resolution and unit points
+ *   8. finish            k_iface_finish_atom, kl_segment_sums over the 2 P sides, k_iface_finish_row
+ *
+ * iface_screen is steps 1 to 5, iface_pipeline all of them; the pipeline's results stay in the context's own buffers and the
+ * entries deliver them - to device arrays or to host arrays - once the capacities have been held against P and M, so that a
+ * call that fails for its capacities has written none of the caller's pair arrays.
+ */
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+#include <vector>
+
+#include "engine_internal.h"
+
+using namespace sasa;
+
+namespace {
+
+struct IfacePlan {
+    int64_t P = 0, M = 0, T = 0, n_cand = 0;
+    int64_t n = 0, n_iso = 0;
+    int G = 0;
+    std::vector<int32_t> pair_struct, pair_groups; /* [P], [2 P] */
+    std::vector<int64_t> side_off;                 /* [2 P + 1] */
+    std::vector<int64_t> sides;                    /* the upload: side_off [2 P + 1] | side_start [2 P] | side_group [2 P] as int32 */
+    std::vector<int64_t> pair_off;                 /* [P + 1] the pair batch's offsets */
+    std::vector<int64_t> meta;                     /* the upload: gstart [G + 1] | tbase [n_structs + 1] */
+    std::vector<double> tp;                        /* S&R test points */
+};
+
+/* what every entry checks before a device is touched: 0, or the message in msg */
+int iface_bad_args(const void *xyz, const void *radii, const int64_t *offsets, int n_structs, const void *group, const int32_t *n_groups,
+                   int alg, int resolution, char *msg, size_t len)
+{
+    const char *bad = nullptr;
+    if (!xyz || !radii || !offsets || !group || !n_groups) bad = "null argument";
+    else if (alg != 0 && alg != 1) { snprintf(msg, len, "unknown algorithm %d", alg); return -1; }
+    else if (n_structs <= 0) bad = "n_structs must be > 0";
+    else if (resolution <= 0) bad = "resolution must be > 0";
+    else if (offsets[0] != 0) bad = "offsets[0] must be 0";
+    if (bad) { snprintf(msg, len, "%s", bad); return -1; }
+    for (int s = 0; s < n_structs; ++s)
+        if (offsets[s + 1] < offsets[s]) { snprintf(msg, len, "offsets must be non-decreasing"); return -1; }
+    if (offsets[n_structs] <= 0) { snprintf(msg, len, "empty batch"); return -1; }
+    int64_t T = 0;
+    for (int s = 0; s < n_structs; ++s) {
+        const int64_t ng = n_groups[s];
+        if (ng > IF_MAX_GROUPS && ng <= 65535) { /* (a count the chain-group entry refuses is left to it, with its message) */
+            snprintf(msg, len, "structure %d has %lld groups: interfaces are made for up to %d groups of a structure", s, (long long)ng, IF_MAX_GROUPS);
+            return -1;
+        }
+        if (ng >= 2 && ng <= IF_MAX_GROUPS) T += ng * (ng - 1) / 2;
+        if (T > IF_MAX_TESTS) {
+            snprintf(msg, len, "structures 0 .. %d have %lld pairs of groups to test: a call takes up to %d", s, (long long)T, IF_MAX_TESTS);
+            return -1;
+        }
+    }
+    return 0;
+}
+int iface_bad_caps(long long pair_capacity, long long atom_capacity, char *msg, size_t len)
+{
+    if (pair_capacity < 0) { snprintf(msg, len, "pair_capacity must be >= 0 (it is %lld)", pair_capacity); return -1; }
+    if (atom_capacity < 0) { snprintf(msg, len, "atom_capacity must be >= 0 (it is %lld)", atom_capacity); return -1; }
+    return 0;
+}
+
+/* steps 1 to 5 on arrays that are on the context's stream; at its end the stream is idle (the flags are on the host) */
+int iface_screen(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
+                 const int32_t *d_group, const int32_t *n_groups, double probe, int resolution, double *d_sasa, double *d_iso,
+                 double *d_totals, double *d_group_totals, IfacePlan &pl, IfaceArgs &ia)
+{
+    if (alg == 1) pl.tp = call_test_points(alg, resolution);
+    std::vector<int> cnt;
+    if (groups_resident(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe, resolution, alg == 1 ? pl.tp.data() : nullptr,
+                        d_sasa, d_iso, d_totals, d_group_totals, &cnt))
+        return -1;
+    const int G = (int)cnt.size();
+    const int64_t n = offsets[n_structs];
+    pl.G = G; pl.n = n;
+    pl.meta.assign((size_t)G + 1 + (size_t)n_structs + 1, 0);
+    int64_t *gstart = pl.meta.data(), *tbase = gstart + G + 1;
+    gstart[0] = n;
+    for (int k = 0; k < G; ++k) gstart[k + 1] = gstart[k] + cnt[(size_t)k];
+    pl.n_iso = gstart[G] - n;
+    int64_t T = 0;
+    for (int s = 0; s < n_structs; ++s) {
+        tbase[s] = T;
+        const int64_t ng = n_groups[s];
+        T += ng * (ng - 1) / 2;
+    }
+    tbase[n_structs] = T;
+    pl.T = T;
+
+    memset(&ia, 0, sizeof ia);
+    ia.cxyz = (const double *)c->g_xyz.p; ia.cradii = (const double *)c->g_radii.p; ia.src = (const int *)c->g_src.p;
+    ia.csasa = (const double *)c->g_sasa.p; ia.ctot = (const double *)c->g_tot.p;
+    ia.n_atoms = (int)n; ia.n_structs = n_structs; ia.n_groups = G; ia.probe = probe;
+    ia.gbase = (const int64_t *)c->g_meta.p + n_structs + 1;
+    ia.n_tests = (int)T;
+    pl.side_off.assign(1, 0);
+    if (T == 0) return 0;
+
+    hipStream_t st = c->stream;
+    if (ensure(c, c->if_meta, 8 * pl.meta.size()) || ensure(c, c->if_box, 64 * (size_t)G) || ensure(c, c->if_cand, 4 * (size_t)T + 8) ||
+        ensure(c, c->if_flag, (size_t)T))
+        return -1;
+    ia.gstart = (const int64_t *)c->if_meta.p; ia.tbase = ia.gstart + G + 1;
+    ia.box = (double *)c->if_box.p;
+    ia.n_cand = (int *)c->if_cand.p; ia.cand = ia.n_cand + 2;
+    ia.flag = (unsigned char *)c->if_flag.p;
+    HIP_TRY(c, hipMemcpyAsync(c->if_meta.p, pl.meta.data(), 8 * pl.meta.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(c->if_cand.p, 0, 8, st));
+    HIP_TRY(c, hipMemsetAsync(c->if_flag.p, 0, (size_t)T, st));
+    HIP_TRY(c, kl_iface_box(ia, st));
+    HIP_TRY(c, kl_iface_candidates(ia, st));
+    HIP_TRY(c, kl_iface_contact(ia, st));
+    std::vector<unsigned char> flag((size_t)T);
+    int nc = 0;
+    HIP_TRY(c, hipMemcpyAsync(flag.data(), c->if_flag.p, (size_t)T, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&nc, c->if_cand.p, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    pl.n_cand = nc;
+
+    /* 5. the table's order is the tests' order */
+    int64_t P = 0;
+    for (int64_t t = 0; t < T; ++t) P += flag[(size_t)t];
+    pl.P = P;
+    pl.pair_struct.reserve((size_t)P); pl.pair_groups.reserve(2 * (size_t)P); pl.side_off.reserve(2 * (size_t)P + 1);
+    std::vector<int64_t> start; std::vector<int32_t> grp;
+    start.reserve(2 * (size_t)P); grp.reserve(2 * (size_t)P);
+    int64_t t = 0, k0 = 0, M = 0;
+    for (int s = 0; s < n_structs; ++s) {
+        const int ng = n_groups[s];
+        for (int g = 0; g + 1 < ng; ++g)
+            for (int h = g + 1; h < ng; ++h, ++t) {
+                if (!flag[(size_t)t]) continue;
+                pl.pair_struct.push_back(s);
+                pl.pair_groups.push_back(g); pl.pair_groups.push_back(h);
+                for (int side = 0; side < 2; ++side) {
+                    const int64_t k = k0 + (side ? h : g);
+                    start.push_back(gstart[k]); grp.push_back((int32_t)k);
+                    M += cnt[(size_t)k];
+                    pl.side_off.push_back(M);
+                }
+            }
+        k0 += ng;
+    }
+    pl.M = M;
+    pl.pair_off.resize((size_t)P + 1);
+    for (int64_t p = 0; p <= P; ++p) pl.pair_off[(size_t)p] = pl.side_off[2 * (size_t)p];
+    /* side_off | side_start | side_group (two int32 to a word) */
+    pl.sides.assign(2 * (size_t)P + 1 + 2 * (size_t)P + (size_t)P, 0);
+    if (P > 0) {
+        memcpy(pl.sides.data(), pl.side_off.data(), 8 * (2 * (size_t)P + 1));
+        memcpy(pl.sides.data() + 2 * P + 1, start.data(), 8 * 2 * (size_t)P);
+        memcpy(pl.sides.data() + 4 * P + 1, grp.data(), 4 * 2 * (size_t)P);
+    }
+    return 0;
+}
+
+/* what an entry wants delivered: held against P and M before anything of steps 6 to 8 runs */
+struct IfaceWant {
+    long long pair_capacity = 0, atom_capacity = 0;
+    bool rows = false;  /* one of pair_struct, pair_groups, pair_areas, side_offsets */
+    bool atoms = false; /* one of pair_atom, pair_buried */
+};
+int iface_check_caps(freesasa_gpu_ctx *c, const IfacePlan &pl, const IfaceWant &w)
+{
+    if (w.rows && pl.P > w.pair_capacity)
+        return ctx_fail(c, "pair_capacity %lld is too small: the batch has %lld pairs of groups in contact", w.pair_capacity, (long long)pl.P);
+    if (w.atoms && pl.M > w.atom_capacity)
+        return ctx_fail(c, "atom_capacity %lld is too small: the pair structures hold %lld atoms", w.atom_capacity, (long long)pl.M);
+    return 0;
+}
+
+/* the whole pipeline: the rows in c->if_areas [6 P], the per-atom arrays in c->if_patom / c->if_pburied [M]; nothing is waited
+   for at its end beyond what run_batch waits for */
+int iface_pipeline(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
+                   const int32_t *d_group, const int32_t *n_groups, double probe, int resolution, double *d_sasa, double *d_iso,
+                   double *d_totals, double *d_group_totals, const IfaceWant &w, IfacePlan &pl, long long *n_pairs_out,
+                   long long *n_pair_atoms_out)
+{
+    IfaceArgs ia;
+    if (iface_screen(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe, resolution, d_sasa, d_iso, d_totals,
+                     d_group_totals, pl, ia))
+        return -1;
+    if (n_pairs_out) *n_pairs_out = pl.P;
+    if (n_pair_atoms_out) *n_pair_atoms_out = pl.M;
+    if (iface_check_caps(c, pl, w)) return -1;
+    if (pl.n + pl.n_iso + pl.M > (int64_t)1 << 30)
+        return ctx_fail(c, "the batch (%lld atoms), its groups (%lld) and the pair structures (%lld) hold more than 2^30 atoms together",
+                        (long long)pl.n, (long long)pl.n_iso, (long long)pl.M);
+    if (pl.P == 0) return 0;
+    const size_t P = (size_t)pl.P, M = (size_t)pl.M;
+    hipStream_t st = c->stream;
+    if (ensure(c, c->if_sides, 8 * pl.sides.size()) || ensure(c, c->if_xyz, 24 * M) || ensure(c, c->if_radii, 8 * M) ||
+        ensure(c, c->if_comb, 4 * M) || ensure(c, c->if_sasa, 8 * M) || ensure(c, c->if_inpair, 16 * P) || ensure(c, c->if_areas, 48 * P) ||
+        ensure(c, c->if_patom, 4 * M) || ensure(c, c->if_pburied, 8 * M))
+        return -1;
+    ia.n_sides = 2 * pl.P; ia.n_pair_atoms = pl.M;
+    ia.side_off = (const int64_t *)c->if_sides.p; ia.side_start = ia.side_off + 2 * P + 1; ia.side_group = (const int *)(ia.side_start + 2 * P);
+    ia.pxyz = (double *)c->if_xyz.p; ia.pradii = (double *)c->if_radii.p; ia.pcomb = (int *)c->if_comb.p; ia.pair_atom = (int *)c->if_patom.p;
+    ia.psasa = (const double *)c->if_sasa.p; ia.inpair = (const double *)c->if_inpair.p;
+    ia.pair_buried = (double *)c->if_pburied.p; ia.pair_areas = (double *)c->if_areas.p;
+    HIP_TRY(c, hipMemcpyAsync(c->if_sides.p, pl.sides.data(), 8 * pl.sides.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, kl_iface_gather(ia, st));
+    if (run_batch(c, alg == 0, ia.pxyz, ia.pradii, pl.pair_off.data(), (int)P, probe, resolution, alg == 1 ? pl.tp.data() : nullptr,
+                  (double *)c->if_sasa.p, nullptr, nullptr))
+        return -1;
+    HIP_TRY(c, kl_segment_sums(ia.psasa, ia.side_off, (int)(2 * P), pl.M < (int64_t)64 * 2 * (int64_t)P, (double *)c->if_inpair.p, st));
+    HIP_TRY(c, kl_iface_finish(ia, st));
+    return 0;
+}
+
+int iface_dev_checks(freesasa_gpu_ctx *c, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
+                     const int32_t *d_group, const int32_t *n_groups, int alg, int resolution, long long pair_capacity, long long atom_capacity)
+{
+    char msg[200];
+    c->err[0] = 0;
+    if (iface_bad_args(d_xyz, d_radii, offsets, n_structs, d_group, n_groups, alg, resolution, msg, sizeof msg) ||
+        iface_bad_caps(pair_capacity, atom_capacity, msg, sizeof msg))
+        return ctx_fail(c, "%s", msg);
+    if (offsets[n_structs] > (int64_t)1 << 30) return ctx_fail(c, "batch too large (max 2^30 atoms per call)");
+    if (hipSetDevice(c->device) != hipSuccess) return ctx_fail(c, "hipSetDevice failed");
+    return 0;
+}
+
+/* the screen's rows into host arrays */
+void iface_rows_to_host(const IfacePlan &pl, int32_t *pair_struct_out, int32_t *pair_groups_out, long long *stats_out)
+{
+    if (pair_struct_out && pl.P > 0) memcpy(pair_struct_out, pl.pair_struct.data(), 4 * (size_t)pl.P);
+    if (pair_groups_out && pl.P > 0) memcpy(pair_groups_out, pl.pair_groups.data(), 8 * (size_t)pl.P);
+    if (stats_out) { stats_out[0] = pl.T; stats_out[1] = pl.n_cand; }
+}
+
+} /* namespace */
+
+extern "C" int freesasa_gpu_interface_pairs_dev(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii,
+                                                const int64_t *offsets, int n_structs, const int32_t *d_group, const int32_t *n_groups,
+                                                double probe_radius, int resolution, double *d_sasa, double *d_iso, double *d_totals,
+                                                double *d_group_totals, long long pair_capacity, long long *n_pairs_out,
+                                                long long *n_pair_atoms_out, int32_t *pair_struct_out, int32_t *pair_groups_out,
+                                                long long *stats_out)
+{
+    if (!c) return -1;
+    if (freesasa_gpu_wait(c)) return -1; /* (batches submitted asynchronously come first) */
+    return guarded_ctx(c, [&]() -> int {
+        if (iface_dev_checks(c, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, alg, resolution, pair_capacity, 0)) return -1;
+        if (!n_pairs_out || !n_pair_atoms_out) return ctx_fail(c, "null argument");
+        IfacePlan pl;
+        IfaceArgs ia;
+        int rc = iface_screen(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe_radius, resolution, d_sasa, d_iso,
+                              d_totals, d_group_totals, pl, ia);
+        if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = ctx_fail(c, "stream synchronize failed");
+        if (rc) return rc;
+        *n_pairs_out = pl.P; *n_pair_atoms_out = pl.M;
+        IfaceWant w;
+        w.pair_capacity = pair_capacity; w.rows = pair_struct_out || pair_groups_out;
+        if (iface_check_caps(c, pl, w)) return -1;
+        iface_rows_to_host(pl, pair_struct_out, pair_groups_out, stats_out);
+        return 0;
+    });
+}
+
+extern "C" int freesasa_gpu_interfaces_dev(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii,
+                                           const int64_t *offsets, int n_structs, const int32_t *d_group, const int32_t *n_groups,
+                                           double probe_radius, int resolution, double *d_sasa, double *d_iso, double *d_totals,
+                                           double *d_group_totals, long long pair_capacity, long long atom_capacity,
+                                           long long *n_pairs_out, long long *n_pair_atoms_out, int32_t *d_pair_struct,
+                                           int32_t *d_pair_groups, double *d_pair_areas, int64_t *d_side_offsets, int32_t *d_pair_atom,
+                                           double *d_pair_buried)
+{
+    if (!c) return -1;
+    if (freesasa_gpu_wait(c)) return -1;
+    return guarded_ctx(c, [&]() -> int {
+        if (iface_dev_checks(c, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, alg, resolution, pair_capacity, atom_capacity)) return -1;
+        if (!d_sasa || !d_iso || !n_pairs_out || !n_pair_atoms_out || !d_pair_areas) return ctx_fail(c, "null argument");
+        IfacePlan pl; /* (its arrays are the sources of copies enqueued below: it lives until the stream is idle) */
+        IfaceWant w;
+        w.pair_capacity = pair_capacity; w.atom_capacity = atom_capacity; w.rows = true; w.atoms = d_pair_atom || d_pair_buried;
+        int rc = [&]() -> int {
+            if (iface_pipeline(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe_radius, resolution, d_sasa, d_iso,
+                               d_totals, d_group_totals, w, pl, n_pairs_out, n_pair_atoms_out))
+                return -1;
+            const size_t P = (size_t)pl.P, M = (size_t)pl.M;
+            hipStream_t st = c->stream;
+            if (d_side_offsets) HIP_TRY(c, hipMemcpyAsync(d_side_offsets, pl.side_off.data(), 8 * (2 * P + 1), hipMemcpyHostToDevice, st));
+            if (P == 0) return 0;
+            if (d_pair_struct) HIP_TRY(c, hipMemcpyAsync(d_pair_struct, pl.pair_struct.data(), 4 * P, hipMemcpyHostToDevice, st));
+            if (d_pair_groups) HIP_TRY(c, hipMemcpyAsync(d_pair_groups, pl.pair_groups.data(), 8 * P, hipMemcpyHostToDevice, st));
+            HIP_TRY(c, hipMemcpyAsync(d_pair_areas, c->if_areas.p, 48 * P, hipMemcpyDeviceToDevice, st));
+            if (d_pair_atom) HIP_TRY(c, hipMemcpyAsync(d_pair_atom, c->if_patom.p, 4 * M, hipMemcpyDeviceToDevice, st));
+            if (d_pair_buried) HIP_TRY(c, hipMemcpyAsync(d_pair_buried, c->if_pburied.p, 8 * M, hipMemcpyDeviceToDevice, st));
+            return 0;
+        }();
+        if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = ctx_fail(c, "stream synchronize failed"); /* (the call is synchronous) */
+        return rc;
+    });
+}
+
+/* the host-pointer entries: the batch as one chunk of the host-batch path, in place, as freesasa_gpu_calc_groups has it */
+static int iface_host(const double *xyz, const double *radii, const int64_t *offsets, int n_structs, const int32_t *group,
+                      const int32_t *n_groups, int alg, double probe, int resolution, double *sasa_out, double *iso_out, double *totals_out,
+                      double *group_totals_out, bool whole, long long pair_capacity, long long atom_capacity, long long *n_pairs_out,
+                      long long *n_pair_atoms_out, int32_t *pair_struct_out, int32_t *pair_groups_out, double *pair_areas_out,
+                      int64_t *side_offsets_out, int32_t *pair_atom_out, double *pair_buried_out, long long *stats_out, int device,
+                      char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    char msg[200];
+    if (iface_bad_args(xyz, radii, offsets, n_structs, group, n_groups, alg, resolution, msg, sizeof msg) ||
+        iface_bad_caps(pair_capacity, atom_capacity, msg, sizeof msg))
+        return set_err(err_out, err_len, msg);
+    if (!n_pairs_out || !n_pair_atoms_out || (whole && !pair_areas_out)) return set_err(err_out, err_len, "null argument");
+    if (freesasa_gpu_device_count() <= 0)
+        return set_err(err_out, err_len, "no HIP device available: libfreesasa_amd has no CPU path");
+    return guarded(err_out, err_len, [&]() -> int {
+    IfacePlan pl; /* (declared before the lease: freed after its stream is idle) */
+    PoolLease lease(device);
+    freesasa_gpu_ctx *c = lease.c;
+    if (!c) return set_err(err_out, err_len, "could not create a GPU context");
+    const size_t n = (size_t)offsets[n_structs];
+    int64_t G = 0; /* (bad counts are refused by the chain-group pipeline, with its message: staged for none here) */
+    for (int s = 0; s < n_structs; ++s) G += n_groups[s] > 0 && n_groups[s] <= 65535 ? n_groups[s] : 0;
+    BatchCall b;
+    b.fallback = "GPU interface batch failed";
+    Chunk h;
+    h.ns = n_structs; h.n = n; h.off = offsets; h.xyz = xyz; h.radii = radii;
+    const int rc = [&]() -> int {
+        c->err[0] = 0;
+        if (chunk_size(b, c, h) || ensure(c, c->h_group, 4 * n) || ensure(c, c->h_iso, 8 * n) || ensure(c, c->h_gtot, 24 * (size_t)G + 8)) return -1;
+        if (chunk_upload(c, h)) return -1;
+        hipStream_t st = c->stream;
+        if (hipMemcpyAsync(c->h_group.p, group, 4 * n, hipMemcpyHostToDevice, st) != hipSuccess) return ctx_fail(c, "host-to-device copy failed");
+        const double *d_xyz = (const double *)c->h_xyz.p, *d_radii = (const double *)c->h_radii.p;
+        const int32_t *d_group = (const int32_t *)c->h_group.p;
+        double *d_sasa = (double *)c->h_sasa.p, *d_iso = (double *)c->h_iso.p;
+        double *d_tot = totals_out ? (double *)c->h_totals.p : nullptr, *d_gtot = group_totals_out ? (double *)c->h_gtot.p : nullptr;
+        if (offsets[n_structs] > (int64_t)1 << 30) return ctx_fail(c, "batch too large (max 2^30 atoms per call)");
+        IfaceWant w;
+        w.pair_capacity = pair_capacity; w.atom_capacity = atom_capacity;
+        if (whole) {
+            w.rows = true; w.atoms = pair_atom_out || pair_buried_out;
+            if (iface_pipeline(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe, resolution, d_sasa, d_iso, d_tot, d_gtot,
+                               w, pl, n_pairs_out, n_pair_atoms_out))
+                return -1;
+        } else {
+            IfaceArgs ia;
+            w.rows = pair_struct_out || pair_groups_out;
+            if (iface_screen(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe, resolution, d_sasa, d_iso, d_tot, d_gtot, pl, ia))
+                return -1;
+            *n_pairs_out = pl.P; *n_pair_atoms_out = pl.M;
+            if (iface_check_caps(c, pl, w)) return -1;
+        }
+        const size_t P = (size_t)pl.P, M = (size_t)pl.M;
+        if ((sasa_out && hipMemcpyAsync(sasa_out, d_sasa, 8 * n, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+            (iso_out && hipMemcpyAsync(iso_out, d_iso, 8 * n, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+            (totals_out && hipMemcpyAsync(totals_out, d_tot, 8 * (size_t)n_structs, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+            (group_totals_out && G > 0 && hipMemcpyAsync(group_totals_out, d_gtot, 24 * (size_t)G, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+            (whole && P > 0 && hipMemcpyAsync(pair_areas_out, c->if_areas.p, 48 * P, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+            (whole && P > 0 && pair_atom_out && hipMemcpyAsync(pair_atom_out, c->if_patom.p, 4 * M, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+            (whole && P > 0 && pair_buried_out && hipMemcpyAsync(pair_buried_out, c->if_pburied.p, 8 * M, hipMemcpyDeviceToHost, st) != hipSuccess))
+            return ctx_fail(c, "device-to-host copy failed");
+        if (hipStreamSynchronize(st) != hipSuccess) return ctx_fail(c, "stream synchronize failed");
+        iface_rows_to_host(pl, pair_struct_out, pair_groups_out, stats_out);
+        if (side_offsets_out) memcpy(side_offsets_out, pl.side_off.data(), 8 * (2 * P + 1));
+        return 0;
+    }();
+    return rc ? set_err(err_out, err_len, chunk_failed(b, c)) : 0;
+    });
+}
+
+extern "C" int freesasa_gpu_calc_interface_pairs(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
+                                                 const int32_t *group, const int32_t *n_groups, int alg, double probe_radius,
+                                                 int resolution, long long pair_capacity, long long *n_pairs_out,
+                                                 long long *n_pair_atoms_out, int32_t *pair_struct_out, int32_t *pair_groups_out,
+                                                 long long *stats_out, int device, char *err_out, int err_len)
+{
+    return iface_host(xyz, radii, offsets, n_structs, group, n_groups, alg, probe_radius, resolution, nullptr, nullptr, nullptr, nullptr,
+                      false, pair_capacity, 0, n_pairs_out, n_pair_atoms_out, pair_struct_out, pair_groups_out, nullptr, nullptr, nullptr,
+                      nullptr, stats_out, device, err_out, err_len);
+}
+
+extern "C" int freesasa_gpu_calc_interfaces(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
+                                            const int32_t *group, const int32_t *n_groups, int alg, double probe_radius, int resolution,
+                                            double *sasa_out, double *iso_out, double *totals_out, double *group_totals_out,
+                                            long long pair_capacity, long long atom_capacity, long long *n_pairs_out,
+                                            long long *n_pair_atoms_out, int32_t *pair_struct_out, int32_t *pair_groups_out,
+                                            double *pair_areas_out, int64_t *side_offsets_out, int32_t *pair_atom_out,
+                                            double *pair_buried_out, int device, char *err_out, int err_len)
+{
+    return iface_host(xyz, radii, offsets, n_structs, group, n_groups, alg, probe_radius, resolution, sasa_out, iso_out, totals_out,
+                      group_totals_out, true, pair_capacity, atom_capacity, n_pairs_out, n_pair_atoms_out, pair_struct_out, pair_groups_out,
+                      pair_areas_out, side_offsets_out, pair_atom_out, pair_buried_out, nullptr, device, err_out, err_len);
+}

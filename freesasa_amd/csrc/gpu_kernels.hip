@@ -1262,6 +1262,69 @@ hipError_t kl_pbc_collect(const PbcArgs &a, hipStream_t st)
     return hipGetLastError();
 }
 
+/* interfaces between chain groups (iface_kernels.h, gpu_interfaces.hip): the groups' boxes (one wave per group), the candidate
+   pairs (one thread per test), the exact contact (workgroups that stride over the candidates' list: its length stays on the
+   device), the pair batch's gather, the finish */
+__global__ __launch_bounds__(IF_B) void k_iface_box(IfaceArgs a)
+{
+    const int k = blockIdx.x * (IF_B / 64) + (threadIdx.x >> 6);
+    if (k < a.n_groups) iface_box(a, k, threadIdx.x & 63); /* (a whole wave leaves or stays) */
+}
+__global__ __launch_bounds__(IF_B) void k_iface_candidates(IfaceArgs a)
+{
+    iface_candidates(a, blockIdx.x * IF_B + threadIdx.x);
+}
+__global__ __launch_bounds__(IF_B) void k_iface_contact(IfaceArgs a)
+{
+    __shared__ IfaceLds m;
+    const int nc = *a.n_cand;
+    for (int c = blockIdx.x; c < nc; c += gridDim.x) iface_contact(a, m, c, threadIdx.x);
+}
+__global__ __launch_bounds__(IF_B) void k_iface_gather(IfaceArgs a)
+{
+    iface_gather(a, (int64_t)blockIdx.x * IF_B + threadIdx.x);
+}
+__global__ __launch_bounds__(IF_B) void k_iface_finish_atom(IfaceArgs a)
+{
+    iface_finish_atom(a, (int64_t)blockIdx.x * IF_B + threadIdx.x);
+}
+__global__ __launch_bounds__(IF_B) void k_iface_finish_row(IfaceArgs a)
+{
+    iface_finish_row(a, (int64_t)blockIdx.x * IF_B + threadIdx.x);
+}
+hipError_t kl_iface_box(const IfaceArgs &a, hipStream_t st)
+{
+    if (a.n_groups == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_iface_box, dim3((unsigned)((a.n_groups + IF_B / 64 - 1) / (IF_B / 64))), dim3(IF_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_iface_candidates(const IfaceArgs &a, hipStream_t st)
+{
+    if (a.n_tests == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_iface_candidates, dim3((unsigned)((a.n_tests + IF_B - 1) / IF_B)), dim3(IF_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_iface_contact(const IfaceArgs &a, hipStream_t st)
+{
+    if (a.n_tests == 0) return hipSuccess;
+    const int grid = a.n_tests < IF_CONTACT_GRID ? a.n_tests : IF_CONTACT_GRID;
+    hipLaunchKernelGGL(k_iface_contact, dim3((unsigned)grid), dim3(IF_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_iface_gather(const IfaceArgs &a, hipStream_t st)
+{
+    if (a.n_pair_atoms == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_iface_gather, dim3((unsigned)((a.n_pair_atoms + IF_B - 1) / IF_B)), dim3(IF_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_iface_finish(const IfaceArgs &a, hipStream_t st)
+{
+    if (a.n_sides == 0) return hipSuccess;
+    if (a.pair_buried) hipLaunchKernelGGL(k_iface_finish_atom, dim3((unsigned)((a.n_pair_atoms + IF_B - 1) / IF_B)), dim3(IF_B), 0, st, a);
+    hipLaunchKernelGGL(k_iface_finish_row, dim3((unsigned)((a.n_sides / 2 + IF_B - 1) / IF_B)), dim3(IF_B), 0, st, a);
+    return hipGetLastError();
+}
+
 void kl_dump_phase_clocks(void)
 {
 #ifdef SASA_PHASE_TIMING

@@ -987,6 +987,73 @@ int freesasa_gpu_calc_groups(const double *xyz, const double *radii, const int64
                              int resolution, double *sasa_out, double *iso_out, double *totals_out,
                              double *group_totals_out, int device, char *err_out, int err_len);
 
+/* INTERFACES BETWEEN CHAIN GROUPS: which groups of a structure bury each other, and by how much - the interface areas of an
+   oligomer, a capsid, an antibody-antigen pair - from ONE call: the chain-group pipeline above, a contact screen between the
+   groups on the device, and one more batch that holds only the pairs that touch (csrc/iface_kernels.h, gpu_interfaces.hip;
+   tests/interfaces_ref.py restates the definitions in numpy).  Input: that of freesasa_gpu_groups_dev.
+   Contact.  Groups g < h of one structure are in contact iff some atom i of g and some atom j of h pass the reference's
+     neighbour test (ref: src/nb.c:487-491; nb_test, csrc/sasa_kernels.h), in fp64, every operation rounded on its own:
+         ri = radii[i] + probe,  rj = radii[j] + probe,  cut2 = (ri + rj) * (ri + rj),  dx = xj - xi ...
+         dx * dx + dy * dy + dz * dz < cut2                                                     (strict)
+     The engine admits exactly these pairs as neighbours: groups that are not in contact bury nothing of each other, by
+     construction, and get no row.
+   Pair table.  P rows, structure-major, then g ascending, then h ascending.  Row p: pair_struct[p] = s, pair_groups[2p], [2p + 1]
+     = g, h (local ids), and six doubles pair_areas[6p ..] = iso_g, iso_h, in_pair_g, in_pair_h, buried_g, buried_h:
+       iso_*      the group's isolated total: bit for bit column 0 of d_group_totals
+       in_pair_*  the total of the group's atoms in the PAIR STRUCTURE of (g, h): the atoms of g in input order, then the atoms
+                  of h in input order (two isolated groups of the combined batch, one behind the other), given to the engine
+                  as a structure of its own; summed over the side's atoms in order (freesasa_gpu_segment_sums_dev)
+       buried_*   = iso_* - in_pair_*
+   Per atom (optional).  side_offsets [2P + 1] (int64): the boundaries of every pair's two sides among the M pair-structure
+     atoms, side 2p that of g, side 2p + 1 that of h; pair_atom [M] (int32): the input atom of every pair-structure atom;
+     pair_buried [M]: that atom's isolated area (d_iso) minus its area in the pair structure.  M is the sum over the rows of
+     the atom counts of the row's two groups.
+   d_sasa, d_iso, d_totals, d_group_totals: as freesasa_gpu_groups_dev delivers them, bit for bit.
+   Capacities.  Every output array is given with its capacity, pair_capacity in rows (pair_struct: 1, pair_groups: 2, pair_areas:
+     6 entries a row; side_offsets: 2 a row and one more) and atom_capacity in atoms; nothing is written beyond them.  A call
+     whose P or M is larger fails with a message that names the number, after *n_pairs_out and *n_pair_atoms_out are set and
+     before any of these arrays is written.  A NULL array is not delivered and its capacity not looked at.
+   Refused, with a message that names the structure and the number: more than 4096 groups in one structure (8.4e6 pairs to
+     test), more than 2^27 pairs to test in a call, n_atoms + the groups' atoms + M > 2^30; a bad group id or n_groups as by
+     freesasa_gpu_groups_dev, with its message.
+   Not offered: file sweeps and trajectory drivers, periodic images, per-residue tables, pair batches cut into several engine
+     runs, interfaces of more than two groups.
+
+   freesasa_gpu_interface_pairs_dev: the screen alone - the chain-group pipeline, then boxes, candidates and contacts - one
+     stream synchronization more than freesasa_gpu_groups_dev (the flags come back to the host).  d_sasa, d_iso, d_totals,
+     d_group_totals may be NULL.  pair_struct_out [pair_capacity], pair_groups_out [2 pair_capacity]: HOST arrays, as offsets
+     and n_groups are (NULL: only the two counts).  stats_out (may be NULL) [2]: the pairs tested and the candidates among them.
+   freesasa_gpu_interfaces_dev: the whole pipeline; the arrays after the counts are DEVICE arrays; d_pair_areas is required,
+     the others may be NULL.
+   freesasa_gpu_calc_interfaces / _calc_interface_pairs: the same on host arrays, on a pooled context like
+     freesasa_gpu_calc_groups; sasa_out, iso_out, totals_out, group_totals_out may be NULL.
+   All: 0, or -1 with the context's error text / err_out; the context stays usable. */
+int freesasa_gpu_interface_pairs_dev(freesasa_gpu_ctx *ctx, int alg, const double *d_xyz, const double *d_radii,
+                                     const int64_t *offsets, int n_structs, const int32_t *d_group, const int32_t *n_groups,
+                                     double probe_radius, int resolution,
+                                     double *d_sasa, double *d_iso, double *d_totals, double *d_group_totals,
+                                     long long pair_capacity, long long *n_pairs_out, long long *n_pair_atoms_out,
+                                     int32_t *pair_struct_out, int32_t *pair_groups_out, long long *stats_out);
+int freesasa_gpu_interfaces_dev(freesasa_gpu_ctx *ctx, int alg, const double *d_xyz, const double *d_radii,
+                                const int64_t *offsets, int n_structs, const int32_t *d_group, const int32_t *n_groups,
+                                double probe_radius, int resolution,
+                                double *d_sasa, double *d_iso, double *d_totals, double *d_group_totals,
+                                long long pair_capacity, long long atom_capacity, long long *n_pairs_out, long long *n_pair_atoms_out,
+                                int32_t *d_pair_struct, int32_t *d_pair_groups, double *d_pair_areas,
+                                int64_t *d_side_offsets, int32_t *d_pair_atom, double *d_pair_buried);
+int freesasa_gpu_calc_interface_pairs(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
+                                      const int32_t *group, const int32_t *n_groups, int alg, double probe_radius, int resolution,
+                                      long long pair_capacity, long long *n_pairs_out, long long *n_pair_atoms_out,
+                                      int32_t *pair_struct_out, int32_t *pair_groups_out, long long *stats_out,
+                                      int device, char *err_out, int err_len);
+int freesasa_gpu_calc_interfaces(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
+                                 const int32_t *group, const int32_t *n_groups, int alg, double probe_radius, int resolution,
+                                 double *sasa_out, double *iso_out, double *totals_out, double *group_totals_out,
+                                 long long pair_capacity, long long atom_capacity, long long *n_pairs_out, long long *n_pair_atoms_out,
+                                 int32_t *pair_struct_out, int32_t *pair_groups_out, double *pair_areas_out,
+                                 int64_t *side_offsets_out, int32_t *pair_atom_out, double *pair_buried_out,
+                                 int device, char *err_out, int err_len);
+
 /* MOLECULAR VOLUME: the volume enclosed by the solvent-accessible surface of every structure, made of the Shrake-Rupley test
    points by the divergence theorem - what `gmx sasa -tv` prints per frame, in the same formulation:
        V = (1/3) sum_i a_i ( (x_i - o) . E_i + R_i n_i ),   E_i = sum over atom i's exposed points of u_k,  a_i = 4 pi R_i^2 / N
