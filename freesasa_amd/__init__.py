@@ -155,6 +155,12 @@ def lib():
                                                  C.c_int, C.c_char_p, C.c_int]
         L.freesasa_gpu_periodic_triclinic_dev.argtypes = L.freesasa_gpu_periodic_dev.argtypes
         L.freesasa_gpu_calc_periodic_triclinic.argtypes = L.freesasa_gpu_calc_periodic.argtypes
+        L.freesasa_gpu_groups_periodic_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _lp, C.c_int, C.c_void_p, _i32p, _dp,
+                                                       C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _lp]
+        L.freesasa_gpu_groups_periodic_triclinic_dev.argtypes = L.freesasa_gpu_groups_periodic_dev.argtypes
+        L.freesasa_gpu_calc_groups_periodic.argtypes = [_dp, _dp, _lp, C.c_int, _i32p, _i32p, _dp, C.c_int, C.c_double, C.c_int,
+                                                        _dp, _dp, _dp, _dp, _lp, C.c_int, C.c_char_p, C.c_int]
+        L.freesasa_gpu_calc_groups_periodic_triclinic.argtypes = L.freesasa_gpu_calc_groups_periodic.argtypes
         L.freesasa_gpu_cell_widths.argtypes = [_dp, _dp]
         L.freesasa_gpu_cell_from_dcd.argtypes = [_dp, _dp, C.c_char_p, C.c_int]
         L.freesasa_gpu_cell_from_lengths_angles.argtypes = [_dp, _dp, _dp, C.c_char_p, C.c_int]
@@ -475,6 +481,41 @@ def calc_periodic_triclinic(xyz, radii, offsets, cells6, alg=LEE_RICHARDS, probe
     if ret:
         raise RuntimeError("freesasa_gpu_calc_periodic_triclinic: " + err.value.decode())
     return sasa, totals, images
+
+
+def _calc_groups_periodic(name, W, xyz, radii, offsets, group, n_groups, cells, alg, probe, resolution, device):
+    xyz, radii, offsets, group, n_groups = _group_batch(xyz, radii, offsets, group, n_groups)
+    cells = _f64(cells).reshape(-1)
+    n, ns = radii.size, offsets.size - 1
+    if cells.size != W * ns:
+        raise ValueError("cells needs three edges per structure" if W == 3 else "cells6 needs six numbers per structure")
+    G = int(n_groups.astype(np.int64).sum())
+    sasa, iso, totals, gt = np.empty(n), np.empty(n), np.empty(ns), np.empty((max(G, 0), 3))
+    images = np.zeros(ns, dtype=np.int64)
+    err = C.create_string_buffer(512)
+    i32 = C.POINTER(C.c_int32)
+    ret = getattr(lib(), name)(xyz.ctypes.data_as(_dp), radii.ctypes.data_as(_dp), offsets.ctypes.data_as(_lp), ns,
+                               group.ctypes.data_as(i32), n_groups.ctypes.data_as(i32), cells.ctypes.data_as(_dp), alg, probe,
+                               resolution, sasa.ctypes.data_as(_dp), iso.ctypes.data_as(_dp), totals.ctypes.data_as(_dp),
+                               gt.ctypes.data_as(_dp), images.ctypes.data_as(_lp), device, err, 512)
+    if ret:
+        raise RuntimeError(name + ": " + err.value.decode())
+    return sasa, iso, totals, gt, images
+
+
+def calc_groups_periodic(xyz, radii, offsets, group, n_groups, cells, alg=LEE_RICHARDS, probe=1.4, resolution=20, device=-1):
+    """freesasa_gpu_calc_groups_periodic() on host arrays: (sasa, iso, totals, group_totals[G, 3], images) - calc_groups with every
+    structure among the periodic images of its orthorhombic cell (cells [n_structs, 3], see calc_periodic) and every group,
+    taken on its own, among ITS images in the same cell: chains that lie in different images of the box bury what they bury."""
+    return _calc_groups_periodic("freesasa_gpu_calc_groups_periodic", 3, xyz, radii, offsets, group, n_groups, cells, alg, probe,
+                                 resolution, device)
+
+
+def calc_groups_periodic_triclinic(xyz, radii, offsets, group, n_groups, cells6, alg=LEE_RICHARDS, probe=1.4, resolution=20, device=-1):
+    """freesasa_gpu_calc_groups_periodic_triclinic(): calc_groups_periodic for triclinic cells (cells6 [n_structs, 6], see
+    calc_periodic_triclinic)."""
+    return _calc_groups_periodic("freesasa_gpu_calc_groups_periodic_triclinic", 6, xyz, radii, offsets, group, n_groups, cells6, alg,
+                                 probe, resolution, device)
 
 
 def cell_widths(cell6):
@@ -903,6 +944,7 @@ def _stats_proto(L):
                                                             C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, _llp, C.c_char_p, C.c_char_p,
                                                             C.c_char_p, C.c_longlong, _ip, C.c_int, _llp, C.c_int, C.c_char_p, C.c_char_p,
                                                             C.c_char_p, C.c_int]
+    L.freesasa_gpu_trajectory_file_groups_periodic.argtypes = L.freesasa_gpu_trajectory_file_groups_stats.argtypes
     return L
 
 
@@ -1454,7 +1496,8 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
     Chain groups (the keywords of trajectory_topology; freesasa_gpu_trajectory_file_groups): group_areas_path receives
     [F, G, 3] fp64, isolated_path [F, n] fp64 (fp32 with out_f32).
     dcd: frames_path is a DCD trajectory; frame_atoms None is then the file's NATOM.
-    pbc: (with dcd) the atoms the index keeps among their periodic images, frame by frame (not offered with chain groups);
+    pbc: (with dcd) the atoms the index keeps among their periodic images, frame by frame (with chain groups:
+    trajectory_file_groups_periodic);
     triclinic: (with dcd and pbc) the cell records decoded as triclinic cells, see trajectory_file;
     netcdf: frames_path is an AMBER NetCDF trajectory; frame_atoms None is then the file's atom count; pbc and triclinic as with dcd;
     xtc: frames_path is a GROMACS XTC trajectory; frame_atoms None is then the file's atom count; pbc and triclinic as with dcd.
@@ -1548,6 +1591,48 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
                                                   enc(done_path), max_new_shards, dp_, nd, C.byref(total), err, 512)
     if ret < 0:
         raise RuntimeError("freesasa_gpu_trajectory_file_topology: " + err.value.decode())
+    return ret == 0, int(total.value), sel_atoms
+
+
+def trajectory_file_groups_periodic(frames_path, batch, totals_path, structure=0, atom_index=None, frame_atoms=None, selection=None,
+                                    sasa_path=None, class_sums_path=None, residues_path=None, selections_path=None, done_path=None,
+                                    n_frames=0, alg=LEE_RICHARDS, probe=1.4, resolution=20, frames_per_batch=0,
+                                    max_new_shards=0, device=-1, devices=None, out_f32=False, chain_groups=None, separate_chains=False,
+                                    long=False, group=None, n_groups=None, group_areas_path=None, isolated_path=None, dcd=False,
+                                    triclinic=False, netcdf=False, xtc=False, stats=None, stats_path=None, partials_path=None, trr=False):
+    """freesasa_gpu_trajectory_file_groups_periodic(): trajectory_file_topology() with chain groups and every frame among the
+    periodic images of its own cell (pbc is implied; dcd, netcdf, xtc or trr names the container, triclinic how its cell is read):
+    per frame the totals, the per-atom areas, the per-atom isolated areas and the group table are those of calc_groups_periodic
+    (calc_groups_periodic_triclinic) on that frame - chains that lie in different images of the box bury what they bury.  The
+    keywords, outputs, statistics and the done-list are trajectory_file_topology's.  Returns (complete, n_frames,
+    selection_atoms [S] or None)."""
+    L = _stats_proto(_topology_proto(lib()))
+    bits = _frames_bits(False, out_f32, dcd, 0, True, triclinic, netcdf, xtc, trr)
+    if frame_atoms is None:
+        info = dcd_info if dcd else nc_info if netcdf else xtc_info if xtc else trr_info if trr else None
+        if info is not None:
+            frame_atoms = info(frames_path).n_atoms
+    n, R, res_ref, idx, fa_ = _topology_args(batch, structure, atom_index, frame_atoms)
+    S = len(selection) if selection is not None else 0
+    sel_atoms = np.zeros(S, dtype=np.int64) if selection is not None else None
+    err = C.create_string_buffer(512)
+    total = C.c_longlong(0)
+    enc = lambda p: None if p is None else str(p).encode()
+    keep, dp_, nd = _devs(devices, device)
+    cb = batch._as_c()
+    ids, G, _ = _topology_groups(batch, structure, n, chain_groups, separate_chains, long, group, n_groups)
+    ret = L.freesasa_gpu_trajectory_file_groups_periodic(enc(frames_path), bits, 0, n_frames, C.byref(cb), structure, fa_,
+                                                         None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                         selection.handle if selection is not None else None,
+                                                         None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), G,
+                                                         alg, probe, resolution, frames_per_batch, enc(totals_path), enc(sasa_path),
+                                                         enc(class_sums_path), enc(residues_path), enc(selections_path),
+                                                         None if sel_atoms is None else sel_atoms.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                                         enc(group_areas_path), enc(isolated_path),
+                                                         enc(done_path), max_new_shards, dp_, nd, C.byref(total), stats_word(stats) if stats else 0,
+                                                         enc(stats_path), enc(partials_path), err, 512)
+    if ret < 0:
+        raise RuntimeError("freesasa_gpu_trajectory_file_groups_periodic: " + err.value.decode())
     return ret == 0, int(total.value), sel_atoms
 
 
@@ -1790,6 +1875,36 @@ class GpuContext:
         if ret:
             raise RuntimeError("freesasa_gpu_periodic_triclinic_dev: " + self.error())
         return images
+
+    def _groups_periodic(self, name, W, d_xyz, d_radii, offsets, d_group, n_groups, cells, d_sasa, d_iso, d_totals, d_group_totals,
+                         alg, probe, resolution):
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        ng = np.ascontiguousarray(n_groups, dtype=np.int32)
+        cells = _f64(cells).reshape(-1)
+        if cells.size != W * (offsets.size - 1):
+            raise ValueError("cells needs three edges per structure" if W == 3 else "cells6 needs six numbers per structure")
+        images = np.zeros(offsets.size - 1, dtype=np.int64)
+        ret = getattr(lib(), name)(self._h, alg, d_xyz, d_radii, offsets.ctypes.data_as(_lp), offsets.size - 1, d_group,
+                                   ng.ctypes.data_as(C.POINTER(C.c_int32)), cells.ctypes.data_as(_dp), probe, resolution, d_sasa, d_iso,
+                                   d_totals or None, d_group_totals or None, images.ctypes.data_as(_lp))
+        if ret:
+            raise RuntimeError(name + ": " + self.error())
+        return images
+
+    def groups_periodic(self, d_xyz, d_radii, offsets, d_group, n_groups, cells, d_sasa, d_iso, d_totals=0, d_group_totals=0,
+                        alg=LEE_RICHARDS, probe=1.4, resolution=20):
+        """freesasa_gpu_groups_periodic_dev(): groups() with every structure, and every group taken on its own, among the
+        periodic images of the structure's cell (cells: a host array [n_structs, 3], see calc_periodic); returns the image count
+        of every complex (a host int64 array)."""
+        return self._groups_periodic("freesasa_gpu_groups_periodic_dev", 3, d_xyz, d_radii, offsets, d_group, n_groups, cells, d_sasa,
+                                     d_iso, d_totals, d_group_totals, alg, probe, resolution)
+
+    def groups_periodic_triclinic(self, d_xyz, d_radii, offsets, d_group, n_groups, cells6, d_sasa, d_iso, d_totals=0, d_group_totals=0,
+                                  alg=LEE_RICHARDS, probe=1.4, resolution=20):
+        """freesasa_gpu_groups_periodic_triclinic_dev(): groups_periodic() for triclinic cells (cells6: a host array
+        [n_structs, 6], see calc_periodic_triclinic)."""
+        return self._groups_periodic("freesasa_gpu_groups_periodic_triclinic_dev", 6, d_xyz, d_radii, offsets, d_group, n_groups, cells6,
+                                     d_sasa, d_iso, d_totals, d_group_totals, alg, probe, resolution)
 
     def volume(self, d_xyz, d_radii, offsets, d_sasa, d_volumes, d_counts=0, d_evec=0, d_vol=0, d_totals=0, probe=1.4, n_points=100):
         """freesasa_gpu_sr_volume_dev(): shrake_rupley() and, into d_volumes [n_structs], the volume every structure's

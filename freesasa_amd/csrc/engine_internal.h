@@ -22,7 +22,8 @@
  *   gpu_interfaces.hip pairwise interface areas between chain groups: the contact screen behind the chain-group pipeline, the batch of
  *                      the pair structures through the engine, the pair table; their device-pointer and host-pointer entries
  *   gpu_periodic.hip   periodic images: a batch and its cells (orthorhombic or triclinic) expanded into a batch with the
- *                      images that matter, the areas of the real atoms collected; the stage the trajectory file drivers share
+ *                      images that matter, the areas of the real atoms collected; the stage the trajectory file drivers share;
+ *                      chain groups among periodic images: the same stage over the chain-group entry's combined batch
  */
 #ifndef FREESASA_AMD_ENGINE_INTERNAL_H
 #define FREESASA_AMD_ENGINE_INTERNAL_H
@@ -135,6 +136,10 @@ hipError_t kl_pbc_collect(const sasa::PbcArgs &a, hipStream_t st);
 /* ... in a triclinic cell (pbc_tri_kernels.h): the same two phases with the general geometry; the collect is kl_pbc_collect */
 hipError_t kl_pbc_tri_count(const sasa::PbcTriArgs &a, hipStream_t st);
 hipError_t kl_pbc_tri_emit(const sasa::PbcTriArgs &a, hipStream_t st);
+/* ... chain groups among periodic images (pbc_kernels.h, GpbcArgs): the cell of every combined structure (one thread per
+   structure); collect and the groups' finish in one (one thread per combined atom) */
+hipError_t kl_gpbc_cells(const sasa::GpbcArgs &a, hipStream_t st);
+hipError_t kl_gpbc_finish(const sasa::GpbcArgs &a, hipStream_t st);
 
 /* molecular volume (vol_kernels.h): the origins (one workgroup per structure), the atoms' terms (one thread per atom) */
 hipError_t kl_vol_origin(const sasa::VolArgs &a, hipStream_t st);
@@ -213,6 +218,8 @@ struct freesasa_gpu_ctx {
     DevBuf p_meta, p_ibase, p_xyz, p_radii, p_sasa, p_chunks, p_part;
     std::vector<int64_t> p_offsets_host; /* the offsets p_chunks was made for */
     int p_n_chunks = 0;
+    /* chain groups among periodic images: the cell of every combined structure (the batch entries: the complexes' behind them) */
+    DevBuf gp_cells;
     /* molecular volume (gpu_volume.hip): counts, exposed-point vectors, the atoms' terms, the structures' origins and volumes
        where the caller gives no array of its own; vol_evec: set for the length of ONE run_batch, which then keeps the vectors
        there - or refuses the batch (run_batch_once) */
@@ -311,6 +318,13 @@ int group_ids_resident(freesasa_gpu_ctx *c, const GroupSpec &gs, sasa::GidArgs &
 int groups_resident(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
                     const int32_t *d_group, const int32_t *n_groups, double probe, int resolution, const double *unit_points,
                     double *d_sasa, double *d_iso, double *d_totals, double *d_group_totals, std::vector<int> *counts_out);
+/* Its first two stages alone - count and validate, the stable cut - for the callers that put another stage between the cut and
+   the finish (gpu_periodic.hip): the combined batch in c->g_xyz / c->g_radii, its offsets in `comb` [n_structs + G + 1], the
+   atoms of every group in `cnt` (its first G entries; it must outlive the stream's work), and in `ga` the batch, the keys, the group
+   bases and the source atoms; c->g_sasa, g_gath, g_tot and g_tot2 sized for it.  The refusals and their messages are
+   groups_resident's. */
+int groups_cut(freesasa_gpu_ctx *c, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
+               const int32_t *d_group, const int32_t *n_groups, sasa::GrpArgs &ga, std::vector<int64_t> &comb, std::vector<int> &cnt);
 
 /* ------------------------------------------------------------------ periodic images (gpu_periodic.hip) */
 
@@ -339,6 +353,25 @@ int periodic_widths_bad(const double *widths, double c);
 int periodic_resident_tri(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
                           int n_fixed, const double *cells9, const double *d_cells9, double probe, int resolution, const double *unit_points,
                           double *d_sasa, double *d_totals, int64_t *images_out);
+
+/* Chain groups among periodic images.  groups_periodic_stage: a COMBINED batch that is on the context's stream - n_cplx
+   complexes, then their groups as structures (comb: its host offsets, n_comb structures; radii per atom) - through
+   periodic_resident's pipeline, every group in the cell of its complex, in ONE engine run: the cells of the combined structures
+   made on the device (c->gp_cells) from d_cells [W n_cplx], the stage's collect replaced by pbc_kernels.h's fused finish, then
+   the totals kernels with the chunk table of `comb` over the compact combined areas (x.carea -> d_ctot [n_comb]) and, when
+   d_ctot2 is not null, over the gathered complex areas (x.cgath -> d_ctot2 [n_comb]).  The caller fills the layout and the
+   outputs of `x` (n_cplx, n_comb, gbase / g_fixed, n_atoms, n_all, src, n_fixed, n_iso_fixed, key, carea, cgath, sasa, iso);
+   cells (host, [W n_cplx], W = 3 or PBC_TRI_CELL) are the complexes' rows only: a cell is checked once, against its complex, and
+   the messages name the complex.  images_out (host, [n_cplx], may be null): the images of the complexes.  Nothing is waited for
+   at its end.  groups_periodic_resident: freesasa_gpu_groups_periodic_dev's pipeline - groups_cut, that stage, k_grp_totals -
+   on arrays that are on the context's stream; cells as above, uploaded here. */
+int groups_periodic_stage(freesasa_gpu_ctx *c, bool tri, int alg, const double *d_cxyz, const double *d_cradii, const int64_t *comb,
+                          const double *cells, const double *d_cells, sasa::GpbcArgs &x, double probe, int resolution,
+                          const double *unit_points, double *d_ctot, double *d_ctot2, int64_t *images_out);
+int groups_periodic_resident(freesasa_gpu_ctx *c, bool tri, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets,
+                             int n_structs, const int32_t *d_group, const int32_t *n_groups, const double *cells, double probe,
+                             int resolution, const double *unit_points, double *d_sasa, double *d_iso, double *d_totals,
+                             double *d_group_totals, int64_t *images_out);
 
 /* ------------------------------------------------------------------ molecular volume (gpu_volume.hip) */
 

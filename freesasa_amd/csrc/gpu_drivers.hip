@@ -915,7 +915,23 @@ int shard_compute(TrajRun &T, TrajLane &L, TrajShard &h)
     /* periodic images: the compact frames expanded by their cells, the engine on the expanded shard (radii per atom, offsets
        that vary), the real atoms' areas and totals collected where the plain path puts them (gpu_periodic.hip) */
     const size_t at = TrajRun::cells_at(h.in_bytes);
-    const int rb = T.pbc ? (T.io.tri ? periodic_resident_tri : periodic_resident)(c, T.s.alg, (double *)c->h_xyz.p, (double *)c->h_radii.p, T.offs.data(), h.nf, (int)T.n,
+    /* chain groups among periodic images: the combined batch - the frames, behind them every group of every frame - through the
+       same stage, every group in its frame's cell; behind the engine the fused finish has put areas, isolated areas, gathered
+       complex areas and both sets of totals where the groups' path below has them after its own finish (gpu_periodic.hip) */
+    const bool gpbc = T.pbc && T.groups;
+    sasa::GpbcArgs gx;
+    memset(&gx, 0, sizeof gx);
+    if (gpbc) {
+        gx.n_cplx = h.nf; gx.n_comb = (int)(nf * (1 + T.G)); gx.g_fixed = (int)T.G;
+        gx.n_atoms = (int64_t)(nf * T.n); gx.n_all = (int64_t)(nf * T.nc);
+        gx.src = L.ga.src; gx.n_fixed = (int)T.n; gx.n_iso_fixed = (int)T.n_iso; gx.key = L.ga.group;
+        gx.carea = (double *)c->h_sasa.p; gx.cgath = (double *)c->g_gath.p; gx.iso = out[OUT_ISO].per_frame ? (double *)c->h_iso.p : nullptr;
+    }
+    const int rb = gpbc ? groups_periodic_stage(c, T.io.tri, T.s.alg, (double *)c->h_xyz.p, (double *)c->h_radii.p, (nf != T.FB ? T.offs_last : T.offs).data(),
+                                                (const double *)((const char *)h.src + at), (const double *)((const char *)c->g_xyz.p + at), gx,
+                                                T.s.probe, T.s.resolution, T.s.alg == 1 ? T.tp.data() : nullptr, (double *)c->h_totals.p,
+                                                (double *)c->g_tot2.p, nullptr)
+                 : T.pbc ? (T.io.tri ? periodic_resident_tri : periodic_resident)(c, T.s.alg, (double *)c->h_xyz.p, (double *)c->h_radii.p, T.offs.data(), h.nf, (int)T.n,
                                              (const double *)((const char *)h.src + at), (const double *)((const char *)c->g_xyz.p + at),
                                              T.s.probe, T.s.resolution, T.s.alg == 1 ? T.tp.data() : nullptr, (double *)c->h_sasa.p,
                                              (double *)c->h_totals.p, nullptr)
@@ -942,8 +958,9 @@ int shard_compute(TrajRun &T, TrajLane &L, TrajShard &h)
         pa.n_structs = (int)(nf * (1 + T.G)); pa.n_atoms = (int)(nf * T.nc); pa.offsets = (const int64_t *)c->offsets.p;
         pa.n_chunks = c->n_chunks; pa.chunk_struct = (const int *)c->chunk_struct.p; pa.chunk_begin = (const int64_t *)c->chunk_begin.p;
         pa.chunk_len = (const int *)c->chunk_len.p; pa.struct_chunk0 = (const int *)c->struct_chunk0.p;
-        if (kl_traj_group_finish(ga, c->stream) != hipSuccess ||
-            kl_totals(pa, c->n_chunks, pa.n_structs, (const double *)c->g_gath.p, (double *)c->bpart.p, (double *)c->g_tot2.p, c->stream) != hipSuccess ||
+        /* (among periodic images the finish and both reductions are done: run_batch's chunk tables describe the expanded batch) */
+        if ((!gpbc && (kl_traj_group_finish(ga, c->stream) != hipSuccess ||
+                       kl_totals(pa, c->n_chunks, pa.n_structs, (const double *)c->g_gath.p, (double *)c->bpart.p, (double *)c->g_tot2.p, c->stream) != hipSuccess)) ||
             kl_traj_group_totals(ga, c->stream) != hipSuccess)
             return ctx_fail(c, "launch of the groups' sums failed");
         h.d_iso = ga.iso;
@@ -1625,9 +1642,9 @@ extern "C" int freesasa_gpu_trajectory_file_groups_stats(const char *frames_path
     /* (group NULL and neither group output: the run is freesasa_gpu_trajectory_file_topology's, periodic images included) */
     const bool with_groups = group || group_areas_path || iso_path || (stats & (FREESASA_GPU_STATS_GROUPS | FREESASA_GPU_STATS_ISOLATED));
     if (with_groups && (frames_f32 & FREESASA_GPU_FRAMES_TRICLINIC))
-        return set_err(err_out, err_len, "bit 4 of frames_f32 (triclinic cells) is not offered with chain groups: an isolated group among periodic images is not defined");
+        return set_err(err_out, err_len, "bit 4 of frames_f32 (triclinic cells) is not offered with chain groups by this entry: freesasa_gpu_trajectory_file_groups_periodic is the one");
     if (with_groups && (frames_f32 & FREESASA_GPU_FRAMES_PBC))
-        return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) is not offered with chain groups: an isolated group among periodic images is not defined");
+        return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) is not offered with chain groups by this entry: freesasa_gpu_trajectory_file_groups_periodic is the one");
     return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,
                                 alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
                                 sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
@@ -1647,13 +1664,37 @@ extern "C" int freesasa_gpu_trajectory_file_groups(const char *frames_path, int 
 {
     if (err_out && err_len > 0) err_out[0] = 0;
     if (frames_f32 & FREESASA_GPU_FRAMES_TRICLINIC)
-        return set_err(err_out, err_len, "bit 4 of frames_f32 (triclinic cells) is not offered with chain groups: an isolated group among periodic images is not defined");
+        return set_err(err_out, err_len, "bit 4 of frames_f32 (triclinic cells) is not offered with chain groups by this entry: freesasa_gpu_trajectory_file_groups_periodic is the one");
     if (frames_f32 & FREESASA_GPU_FRAMES_PBC)
-        return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) is not offered with chain groups: an isolated group among periodic images is not defined");
+        return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) is not offered with chain groups by this entry: freesasa_gpu_trajectory_file_groups_periodic is the one");
     return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,
                                 alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
                                 sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
                                 frames_total_out, 0, nullptr, nullptr, err_out, err_len);
+}
+
+/* chain groups among periodic images: the groups' run with every frame - and every group of it, taken on its own - among the
+   images of the frame's cell (shard_compute: groups_periodic_stage) */
+extern "C" int freesasa_gpu_trajectory_file_groups_periodic(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
+                                                            const freesasa_ingest_batch *batch, int structure,
+                                                            int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
+                                                            const int32_t *group, int n_groups,
+                                                            int alg, double probe, int resolution, int frames_per_batch,
+                                                            const char *totals_path, const char *sasa_path, const char *class_sums_path,
+                                                            const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
+                                                            const char *group_areas_path, const char *iso_path,
+                                                            const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                                            long long *frames_total_out,
+                                                            int stats, const char *stats_path, const char *partials_path, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (!(frames_f32 & FREESASA_GPU_FRAMES_PBC))
+        return set_err(err_out, err_len, "chain groups among periodic images need bit 3 of frames_f32 (periodic images): without it the run is freesasa_gpu_trajectory_file_groups_stats's");
+    if (!group) return set_err(err_out, err_len, "chain groups among periodic images need group ids (group is NULL): without them the run is freesasa_gpu_trajectory_file_topology's");
+    return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,
+                                alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
+                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
+                                frames_total_out, stats, stats_path, partials_path, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_trajectory_file_topology(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,

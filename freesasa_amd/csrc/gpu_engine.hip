@@ -130,7 +130,7 @@ extern "C" void freesasa_gpu_ctx_destroy(freesasa_gpu_ctx *c)
                      &c->h_xyz, &c->h_radii, &c->h_sasa, &c->h_counts, &c->h_totals, &c->h_group, &c->h_iso, &c->h_gtot,
                      &c->g_meta, &c->g_key, &c->g_count, &c->g_cursor, &c->g_xyz, &c->g_radii, &c->g_src, &c->g_sasa,
                      &c->g_gath, &c->g_tot, &c->g_tot2, &c->gi_tab, &c->gi_words, &c->gi_label,
-                     &c->p_meta, &c->p_ibase, &c->p_xyz, &c->p_radii, &c->p_sasa, &c->p_chunks, &c->p_part,
+                     &c->p_meta, &c->p_ibase, &c->p_xyz, &c->p_radii, &c->p_sasa, &c->p_chunks, &c->p_part, &c->gp_cells,
                      &c->v_counts, &c->v_evec, &c->v_vol, &c->v_origin, &c->v_volumes,
                      &c->dt_masks, &c->dt_first, &c->dt_bsum, &c->dt_xyz, &c->dt_atom, &c->dt_point, &c->dt_unit,
                      &c->if_meta, &c->if_box, &c->if_cand, &c->if_flag, &c->if_sides, &c->if_xyz, &c->if_radii, &c->if_comb, &c->if_sasa,

@@ -12,7 +12,8 @@
  *   4. finish               k_grp_finish (areas back to input order), the totals kernels over the groups' complex
  *                           areas, k_grp_totals
  *
- * groups_resident is that pipeline for callers whose arrays are on the context's stream (the file sweep, gpu_sweep.hip);
+ * groups_cut is stages 1 and 2 alone, for chain groups among periodic images (gpu_periodic.hip puts the periodic stage between
+ * the cut and the finish).  groups_resident is that pipeline for callers whose arrays are on the context's stream (the file sweep, gpu_sweep.hip);
  * freesasa_gpu_calc_groups brings host arrays to it with the host-batch path's sizing, upload and failure epilogue
  * (chunk_size, chunk_upload, chunk_failed: gpu_hostbatch.hip) and its own extras; below it, the group ids themselves made
  * on the device from residues and chain labels (k_gid_struct).
@@ -35,9 +36,8 @@ using namespace sasa;
 static_assert(GID_EGROUP == FREESASA_INGEST_EGROUP && GID_MAX_PER_STRUCT == GRP_MAX_PER_STRUCT && GID_MAX_LABELS == FREESASA_INGEST_MAX_GROUP_LABELS, "group_kernels.h");
 
 /* (engine_internal.h) */
-int groups_resident(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
-                    const int32_t *d_group, const int32_t *n_groups, double probe, int resolution, const double *unit_points,
-                    double *d_sasa, double *d_iso, double *d_totals, double *d_group_totals, std::vector<int> *counts_out)
+int groups_cut(freesasa_gpu_ctx *c, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
+               const int32_t *d_group, const int32_t *n_groups, GrpArgs &ga, std::vector<int64_t> &comb, std::vector<int> &cnt)
 {
     const int64_t n64 = offsets[n_structs];
     if (n64 <= 0) return ctx_fail(c, "empty batch");
@@ -63,7 +63,6 @@ int groups_resident(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const dou
     if (ensure(c, c->g_meta, meta.size() * sizeof(int64_t)) || ensure(c, c->g_key, 4 * (size_t)n) ||
         ensure(c, c->g_count, 4 * ((size_t)G + 2)))
         return -1;
-    GrpArgs ga;
     memset(&ga, 0, sizeof ga);
     ga.xyz = d_xyz; ga.radii = d_radii; ga.group = d_group;
     ga.offsets = (const int64_t *)c->g_meta.p; ga.gbase = ga.offsets + n_structs + 1;
@@ -74,7 +73,7 @@ int groups_resident(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const dou
     HIP_TRY(c, hipMemcpyAsync(c->g_meta.p, meta.data(), meta.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemsetAsync(c->g_count.p, 0, 4 * ((size_t)G + 2), st));
     HIP_TRY(c, kl_grp_count(ga, st));
-    std::vector<int> cnt((size_t)G + 2);
+    cnt.assign((size_t)G + 2, 0);
     HIP_TRY(c, hipMemcpyAsync(cnt.data(), c->g_count.p, 4 * ((size_t)G + 2), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     if (cnt[G]) {
@@ -88,8 +87,9 @@ int groups_resident(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const dou
     }
 
     /* the combined batch: the complex structures, then every group as a structure */
-    std::vector<int64_t> comb((size_t)n_structs + G + 1);
-    std::vector<int> cursor((size_t)G + 1);
+    comb.assign((size_t)n_structs + G + 1, 0);
+    cnt.resize(2 * (size_t)G + 3); /* (the cursors behind the counts: the caller's vector outlives the stream's read of them) */
+    int *const cursor = cnt.data() + G + 2;
     for (int s = 0; s <= n_structs; ++s) comb[s] = offsets[s];
     int64_t pos = n;
     for (int k = 0; k < G; ++k) {
@@ -111,9 +111,24 @@ int groups_resident(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const dou
     HIP_TRY(c, hipMemcpyAsync(c->g_xyz.p, d_xyz, 24 * (size_t)n, hipMemcpyDeviceToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(c->g_radii.p, d_radii, 8 * (size_t)n, hipMemcpyDeviceToDevice, st));
     if (G > 0) {
-        HIP_TRY(c, hipMemcpyAsync(c->g_cursor.p, cursor.data(), 4 * (size_t)G, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(c->g_cursor.p, cursor, 4 * (size_t)G, hipMemcpyHostToDevice, st));
         HIP_TRY(c, kl_grp_rank(ga, st));
     }
+    return 0;
+}
+
+/* (engine_internal.h) */
+int groups_resident(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
+                    const int32_t *d_group, const int32_t *n_groups, double probe, int resolution, const double *unit_points,
+                    double *d_sasa, double *d_iso, double *d_totals, double *d_group_totals, std::vector<int> *counts_out)
+{
+    GrpArgs ga;
+    std::vector<int64_t> comb;
+    std::vector<int> cnt;
+    if (groups_cut(c, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, ga, comb, cnt)) return -1;
+    const int G = ga.n_groups;
+    const size_t N = (size_t)comb.back(), NS = (size_t)n_structs + G;
+    hipStream_t st = c->stream;
 
     /* 3. one batch over the complex and its groups */
     std::vector<double> tp;

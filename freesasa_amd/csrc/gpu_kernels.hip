@@ -1261,6 +1261,28 @@ hipError_t kl_pbc_collect(const PbcArgs &a, hipStream_t st)
     hipLaunchKernelGGL(k_pbc_collect, dim3((unsigned)((a.n_atoms + PBC_B - 1) / PBC_B)), dim3(PBC_B), 0, st, a);
     return hipGetLastError();
 }
+/* ... chain groups among periodic images: the cell of every combined structure (one thread per structure); collect and the
+   groups' finish in one (one thread per combined atom) */
+__global__ __launch_bounds__(PBC_B) void k_gpbc_cells(GpbcArgs a)
+{
+    gpbc_cell_struct(a, blockIdx.x * PBC_B + threadIdx.x);
+}
+__global__ __launch_bounds__(PBC_B) void k_gpbc_finish(GpbcArgs a)
+{
+    gpbc_finish_atom(a, (int64_t)blockIdx.x * PBC_B + threadIdx.x);
+}
+hipError_t kl_gpbc_cells(const GpbcArgs &a, hipStream_t st)
+{
+    if (a.n_comb == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_gpbc_cells, dim3((unsigned)((a.n_comb + PBC_B - 1) / PBC_B)), dim3(PBC_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_gpbc_finish(const GpbcArgs &a, hipStream_t st)
+{
+    if (a.n_all == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_gpbc_finish, dim3((unsigned)((a.n_all + PBC_B - 1) / PBC_B)), dim3(PBC_B), 0, st, a);
+    return hipGetLastError();
+}
 
 /* interfaces between chain groups (iface_kernels.h, gpu_interfaces.hip): the groups' boxes (one wave per group), the candidate
    pairs (one thread per test), the exact contact (workgroups that stride over the candidates' list: its length stays on the

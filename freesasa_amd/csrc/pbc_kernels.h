@@ -33,9 +33,10 @@
  * One workgroup per structure suits trajectory shards of hundreds of frames and batches of many structures; for ONE
  * structure of 1e6 atoms it is slow (a single CU walks it).  That is accepted: there is no multi-workgroup scan here.
  *
- * Triclinic cells: pbc_tri_kernels.h, beside this file (nothing here changes for them).
+ * Triclinic cells: pbc_tri_kernels.h, beside this file (nothing here changes for them).  Chain groups among periodic images
+ * (freesasa_gpu_groups_periodic_dev, freesasa_gpu_trajectory_file_groups_periodic): the two phases at the end of this file.
  * Not offered: cells smaller than c; a cell for raw fp32 / fp64 frame files or the memory trajectory
- * entries (callers pass frames as a batch to freesasa_gpu_calc_periodic); chain groups with periodic images; skipping the
+ * entries (callers pass frames as a batch to freesasa_gpu_calc_periodic); skipping the
  * area computation of the image atoms (their areas are computed and dropped); file or cache sweeps (a PDB CRYST1 record is a
  * crystallographic cell with symmetry: another feature).
  *
@@ -196,6 +197,96 @@ SASA_D void pbc_collect_atom(const PbcArgs &a, int64_t t)
     if (t >= a.n_atoms) return;
     const int s = pbc_struct_of(a, t);
     a.sasa[t] = a.esasa[a.eoff[s] + (t - pbc_begin(a, s))];
+}
+
+/* ------------------------------------------------------------------ chain groups among periodic images
+ * (freesasa_gpu_groups_periodic_dev and its kin, freesasa_gpu_trajectory_file_groups_periodic; host side: gpu_periodic.hip).
+ * The COMBINED batch of the chain-group entries - the n_cplx complexes first, then every group as a structure of its own
+ * (group_kernels.h; per frame: traj_kernels.h) - goes through the stage above as any batch, every group structure in the cell
+ * of its complex.  Two phases are the groups' own:
+ *
+ *   gpbc_cell_struct    one thread per combined structure: the W doubles of its complex's cell (3, or PBC_TRI_CELL) to its own
+ *                       row.  A trajectory's cells are on the device per frame, so this is a kernel and no host loop.
+ *   gpbc_finish_atom    one thread per combined atom: collect and the groups' finish in one - the atom's area out of the
+ *                       EXPANDED batch into the compact combined areas (what the totals of complexes and isolated groups are
+ *                       summed from), a complex atom's to the caller (and as its isolated area when it is in no group), an
+ *                       isolated atom's to its source atom's isolated area, and beside it the source atom's COMPLEX area, read
+ *                       out of the complex's expanded structure (cgath: what a group's complex total is summed from).  No
+ *                       thread reads what another writes.
+ *
+ * Which complex a group structure k >= n_cplx belongs to: the last s with gbase[s] <= k - n_cplx (the batch entries; a complex
+ * without groups is never the last), or (k - n_cplx) / g_fixed (a shard's frames, each with the same groups).  Which atom an
+ * isolated atom t >= n_atoms comes from: src[t - n_atoms] (the batch entries), or atom src[j] of frame f with
+ * t - n_atoms = f n_iso_fixed + j (a shard's frames). */
+struct GpbcArgs {
+    int n_cplx, n_comb;     /* complexes; combined structures: the complexes and all their groups */
+    const int64_t *coff;    /* [n_comb + 1] the combined batch's offsets */
+    const int64_t *eoff;    /* [n_comb + 1] the expanded batch's */
+    const int64_t *gbase;   /* [n_cplx + 1] first group of every complex; NULL: g_fixed groups per complex */
+    int g_fixed;
+    /* gpbc_cell_struct */
+    int W;                  /* doubles per cell */
+    const double *cells;    /* [W n_cplx] */
+    double *ccells;         /* [W n_comb] */
+    /* gpbc_finish_atom */
+    int64_t n_atoms, n_all; /* atoms of the complexes, atoms of the combined batch */
+    const int *src;         /* [n_all - n_atoms]; a shard's frames: [n_iso_fixed], the topology's */
+    int n_fixed, n_iso_fixed; /* a shard's frames: atoms of a frame, those of them with an id >= 0; else 0 */
+    const int *key;         /* [n_atoms] < 0: in no group; a shard's frames: [n_fixed], the topology's ids */
+    const double *esasa;    /* [eoff[n_comb]] */
+    double *carea;          /* [n_all] the compact combined areas */
+    double *cgath;          /* [n_all] the complex area of every combined atom */
+    double *sasa, *iso;     /* [n_atoms]; either may be null */
+};
+
+/* the last s in [0, n) with first[s] <= v */
+SASA_D int gpbc_last_le(const int64_t *first, int n, int64_t v)
+{
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (first[mid] <= v) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+SASA_D int gpbc_complex_of(const GpbcArgs &a, int k)
+{
+    if (k < a.n_cplx) return k;
+    return a.gbase ? gpbc_last_le(a.gbase, a.n_cplx, (int64_t)(k - a.n_cplx)) : (k - a.n_cplx) / a.g_fixed;
+}
+
+/* one thread per combined structure k */
+SASA_D void gpbc_cell_struct(const GpbcArgs &a, int k)
+{
+    if (k >= a.n_comb) return;
+    const int s = gpbc_complex_of(a, k);
+    for (int w = 0; w < a.W; ++w) a.ccells[(int64_t)a.W * k + w] = a.cells[(int64_t)a.W * s + w];
+}
+
+/* one thread per combined atom t */
+SASA_D void gpbc_finish_atom(const GpbcArgs &a, int64_t t)
+{
+    if (t >= a.n_all) return;
+    const int k = gpbc_last_le(a.coff, a.n_comb, t); /* (atoms of empty structures do not exist) */
+    const double v = a.esasa[a.eoff[k] + (t - a.coff[k])];
+    a.carea[t] = v;
+    if (t < a.n_atoms) {
+        if (a.sasa) a.sasa[t] = v;
+        a.cgath[t] = v;
+        if (a.iso && a.key[a.n_fixed ? t % a.n_fixed : t] < 0) a.iso[t] = v;
+        return;
+    }
+    const int s = gpbc_complex_of(a, k);
+    int64_t i;
+    if (a.n_fixed) {
+        const int64_t q = t - a.n_atoms, f = q / a.n_iso_fixed;
+        i = f * a.n_fixed + a.src[q - f * a.n_iso_fixed];
+    } else {
+        i = a.src[t - a.n_atoms];
+    }
+    if (a.iso) a.iso[i] = v;
+    a.cgath[t] = a.esasa[a.eoff[s] + (i - a.coff[s])];
 }
 
 } /* namespace sasa */

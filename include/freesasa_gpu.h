@@ -437,7 +437,8 @@ int freesasa_gpu_calc_batch(const double *xyz, const double *radii, const int64_
    current one); the cells are checked against the radii before a device is touched.  Returns 0 / -1.
    Not offered: cells smaller than c, skipping the area computation of the image atoms (their areas are
    computed and dropped), periodic images in the file or cache sweeps (a PDB CRYST1 record is a crystallographic cell with
-   symmetry).  Triclinic cells: the two entries below these.  Trajectories: FREESASA_GPU_FRAMES_PBC below. */
+   symmetry).  Triclinic cells: the two entries below these.  Trajectories: FREESASA_GPU_FRAMES_PBC below.  Chain groups among the
+   images (isolated, complex and buried areas of chains that lie in different images): freesasa_gpu_groups_periodic_dev, below. */
 int freesasa_gpu_periodic_dev(freesasa_gpu_ctx *ctx, int alg, const double *d_xyz, const double *d_radii,
                               const int64_t *offsets, int n_structs, const double *cells /* host, [3 n_structs] */,
                               double probe_radius, int resolution, double *d_sasa, double *d_totals,
@@ -473,8 +474,8 @@ int freesasa_gpu_calc_periodic(const double *xyz, const double *radii, const int
    On cells (Lx, 0, Ly, 0, 0, Lz) this is the definition above (the tests hold both entries to the same bytes).  Arguments,
    limits, images_out and return values are those of freesasa_gpu_periodic_dev / freesasa_gpu_calc_periodic, whose behaviour,
    messages and refusals do not change; the expansion is made on the device (pbc_tri_kernels.h).
-   Not offered: cells with a width below c, skipping the area computation of the image atoms, chain groups with images, a
-   PDB CRYST1 record. */
+   Not offered: cells with a width below c, skipping the area computation of the image atoms, a
+   PDB CRYST1 record.  Chain groups among the images: freesasa_gpu_groups_periodic_triclinic_dev, below. */
 int freesasa_gpu_periodic_triclinic_dev(freesasa_gpu_ctx *ctx, int alg, const double *d_xyz, const double *d_radii,
                                         const int64_t *offsets, int n_structs, const double *cells6 /* host, [6 n_structs] */,
                                         double probe_radius, int resolution, double *d_sasa, double *d_totals,
@@ -579,7 +580,7 @@ int freesasa_gpu_cell_from_lengths_angles(const double len[3], const double deg[
    ("frame K of the XTC file: ..."); the rest are the checks of a DCD cell.  Refused up front: bit 3 on a file whose first
    frame has an all-zero box, freesasa_gpu_trajectory_file_groups with bit 3.
    Not offered: magic 2023 (64-bit byte counts), frames of 9 atoms or fewer (uncompressed), streams of 2^28 bytes and
-   more, a memory form, chain groups with periodic images, double-precision XTC.  No GROMACS-written file was at hand when
+   more, a memory form, double-precision XTC (chain groups with periodic images: freesasa_gpu_trajectory_file_groups_periodic).  No GROMACS-written file was at hand when
    this was written: conformance rests on the format's description; compare one frame against `gmx dump` first.
 
    GROMACS TRR input (all four file entries): with bit 7 of frames_f32 set (FREESASA_GPU_FRAMES_TRR) frames_path is a TRR
@@ -602,7 +603,8 @@ int freesasa_gpu_cell_from_lengths_angles(const double len[3], const double deg[
    (double) real * 10.0, GROMACS' lower triangle as in an XTC frame, and the checks are those of an XTC box, a frame without
    a box failing like one whose box is all zero ("frame K of the TRR file: ...").  Refused up front: bit 3 on a file whose
    first coordinate frame has no box or an all-zero one, freesasa_gpu_trajectory_file_groups with bit 3.
-   Not offered: a memory form, chain groups with periodic images, a TRR whose records change atom count or precision, a read
+   Chain groups with periodic images: freesasa_gpu_trajectory_file_groups_periodic.
+   Not offered: a memory form, a TRR whose records change atom count or precision, a read
    of velocities or forces, records with an ir, e, top or sym part.  No GROMACS-written file was at hand when this was
    written: conformance rests on the format's description; compare one frame against `gmx dump` first.
 
@@ -628,7 +630,8 @@ int freesasa_gpu_cell_from_lengths_angles(const double len[3], const double deg[
    per frame instead of 24, still one copy.  Bit 4 without bits 2 and 3, and freesasa_gpu_trajectory_file_groups with it,
    are refused before a device is touched or an output file opened.  The done-list's f32= word carries bit 4: runs with and
    without it refuse each other's lists.  A right-angled file gives the files of the run without bit 4, byte for byte.
-   Not offered: cells smaller than c, a cell for raw frame files or the memory entries, chain groups with periodic images. */
+   Chain groups with periodic images: freesasa_gpu_trajectory_file_groups_periodic (the other entries refuse them and name it).
+   Not offered: cells smaller than c, a cell for raw frame files or the memory entries. */
 #define FREESASA_GPU_FRAMES_F32 1     /* frames_f32 bit 0: raw fp32 frames (input format) */
 #define FREESASA_GPU_FRAMES_OUT_F32 2 /* bit 1: per-atom (and isolated) areas written as fp32 (output format) */
 #define FREESASA_GPU_FRAMES_DCD 4     /* bit 2: frames_path is a DCD trajectory */
@@ -946,6 +949,29 @@ int freesasa_gpu_trajectory_file_groups_stats(const char *frames_path, int frame
                                               const char *done_path, long long max_new_shards, const int *devices, int n_devices,
                                               long long *frames_total_out,
                                               int stats, const char *stats_path, const char *partials_path, char *err, int err_len);
+/* CHAIN GROUPS AMONG PERIODIC IMAGES over a trajectory: freesasa_gpu_trajectory_file_groups_stats with every frame - and every
+   group of it, taken on its own - among the periodic images of the frame's own cell: the buried area of a complex over a wrapped
+   trajectory, whichever images of the box its chains lie in.  The signature is that entry's.  Bit 3 of frames_f32
+   (FREESASA_GPU_FRAMES_PBC) and group are REQUIRED (-1 with a message before a file is opened: without either the run is
+   another entry's), bit 4 (triclinic cells) is optional; the containers are those that carry a cell: DCD, AMBER NetCDF, XTC,
+   TRR.  Per frame f the totals, the per-atom areas, the isolated areas and the group table are bit for bit
+   freesasa_gpu_groups_periodic_dev (with bit 4: _triclinic_dev; below) on frame f taken as a structure with its cell: ONE engine
+   run per shard holds the frames, their groups and the images of both.  Class sums, residues, selections, fp32 output, the
+   statistics word and the done-list work as in the non-periodic groups run; the done-list's first line carries bit 3 (and 4)
+   in its f32= word and the groups' digest, so the lists of this run, of the plain periodic run and of the non-periodic groups
+   run refuse each other.  The other entries keep refusing chain groups with bit 3 or bit 4, and name this one.
+   Not offered: the memory form (it has no cells), exposure masks, volume or interfaces among periodic images. */
+int freesasa_gpu_trajectory_file_groups_periodic(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
+                                                 const struct freesasa_ingest_batch *batch, int structure,
+                                                 int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
+                                                 const int32_t *group, int n_groups,
+                                                 int alg, double probe_radius, int resolution, int frames_per_batch,
+                                                 const char *totals_path, const char *sasa_path, const char *class_sums_path,
+                                                 const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
+                                                 const char *group_areas_path, const char *iso_path,
+                                                 const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                                 long long *frames_total_out,
+                                                 int stats, const char *stats_path, const char *partials_path, char *err, int err_len);
 /* W of a statistics word for a system of n_atoms atoms, n_res residues, n_sel selections and n_groups groups; first_out (may be
    NULL) [7] receives the first column of every output in the order above, -1 for one whose bit is not set.  -1: an unknown bit
    or a negative count.  (csrc/trajstats.c: plain C, no allocation, no GPU call.) */
@@ -986,6 +1012,55 @@ int freesasa_gpu_calc_groups(const double *xyz, const double *radii, const int64
                              const int32_t *group, const int32_t *n_groups, int alg, double probe_radius,
                              int resolution, double *sasa_out, double *iso_out, double *totals_out,
                              double *group_totals_out, int device, char *err_out, int err_len);
+
+/* CHAIN GROUPS AMONG PERIODIC IMAGES: the two features above composed - the complex, its groups and the buried area of a
+   system whose chains lie in different images of the box (a wrapped MD frame of a complex), with no clustering and no making
+   whole by the caller.  The arguments are those of freesasa_gpu_groups_dev / freesasa_gpu_calc_groups with, behind n_groups,
+   cells (HOST, [3 n_structs], or cells6 [6 n_structs] for the triclinic entries: the cell of every structure as
+   freesasa_gpu_periodic_dev / freesasa_gpu_periodic_triclinic_dev take it) and, last of the outputs, images_out (host,
+   [n_structs], may be NULL: the images of every complex).  Group ids, their validation and its message are those of
+   freesasa_gpu_groups_dev.  For structure s with cell C_s:
+     complex     d_sasa[i] is the periodic entry's area of atom i of s in C_s, d_totals[s] its total: bit for bit
+                 freesasa_gpu_periodic_dev (_triclinic_dev) on the same batch and cells
+     isolated    d_iso[i] is the periodic entry's area of atom i in the structure made of the atoms of i's group alone - in input
+                 order, radii unchanged, in the SAME cell C_s, among that group's own images; the cutoff c = 2 (max radius +
+                 probe) of an isolated group is that of ITS OWN atoms, exactly as the periodic entry takes it when handed the
+                 group as a structure: bit for bit that entry on the group cut out.  A molecule split over a face is whole in
+                 its isolated form too.  An atom with id -1: its complex area, as in freesasa_gpu_groups_dev.
+     groups      d_group_totals [3 G]: per group the isolated total (the periodic entry's total of the group as a structure),
+                 the complex areas of its atoms reduced by the totals kernels over the gathered array - layout, order and
+                 kernels are freesasa_gpu_groups_dev's -, and their difference, the buried area
+     cells       a group's max radius never exceeds its complex's, so a cell its complex passes is valid for every group: cells
+                 are checked once per complex, and a refusal names the complex with the periodic entries' messages, unchanged
+     limit       the atoms of the complexes, the atoms of their groups and the images of both, together at most 2^30 per call
+                 (-1 with the three numbers in the message)
+   ONE engine run holds complexes, groups and all their images (gpu_periodic.hip); the expansion is the periodic entries', the
+   cut the group entry's.  A cell so large and so placed that no atom of s comes within c of a face gives every output of
+   freesasa_gpu_groups_dev bit for bit; a right-angled triclinic cell gives the orthorhombic entry's.
+   Not offered: exposure masks, volume or pairwise interfaces among periodic images (their entries take no cell).
+   Trajectories: freesasa_gpu_trajectory_file_groups_periodic. */
+int freesasa_gpu_groups_periodic_dev(freesasa_gpu_ctx *ctx, int alg, const double *d_xyz, const double *d_radii,
+                                     const int64_t *offsets, int n_structs, const int32_t *d_group, const int32_t *n_groups,
+                                     const double *cells /* host, [3 n_structs] */, double probe_radius, int resolution,
+                                     double *d_sasa, double *d_iso, double *d_totals, double *d_group_totals,
+                                     int64_t *images_out /* host, [n_structs], may be NULL */);
+int freesasa_gpu_groups_periodic_triclinic_dev(freesasa_gpu_ctx *ctx, int alg, const double *d_xyz, const double *d_radii,
+                                               const int64_t *offsets, int n_structs, const int32_t *d_group, const int32_t *n_groups,
+                                               const double *cells6 /* host, [6 n_structs] */, double probe_radius, int resolution,
+                                               double *d_sasa, double *d_iso, double *d_totals, double *d_group_totals,
+                                               int64_t *images_out /* host, [n_structs], may be NULL */);
+/* The same on host arrays, on a pooled per-thread context, with the host-batch path's sizing, upload and failure epilogue as
+   freesasa_gpu_calc_groups; the cells are checked against the complexes' radii before a device is touched.  totals_out,
+   group_totals_out and images_out may be NULL.  Returns 0 / -1 with err_out. */
+int freesasa_gpu_calc_groups_periodic(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
+                                      const int32_t *group, const int32_t *n_groups, const double *cells, int alg,
+                                      double probe_radius, int resolution, double *sasa_out, double *iso_out, double *totals_out,
+                                      double *group_totals_out, int64_t *images_out, int device, char *err_out, int err_len);
+int freesasa_gpu_calc_groups_periodic_triclinic(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
+                                                const int32_t *group, const int32_t *n_groups, const double *cells6, int alg,
+                                                double probe_radius, int resolution, double *sasa_out, double *iso_out,
+                                                double *totals_out, double *group_totals_out, int64_t *images_out, int device,
+                                                char *err_out, int err_len);
 
 /* INTERFACES BETWEEN CHAIN GROUPS: which groups of a structure bury each other, and by how much - the interface areas of an
    oligomer, a capsid, an antibody-antigen pair - from ONE call: the chain-group pipeline above, a contact screen between the

@@ -39,6 +39,14 @@ With --triclinic beside --pbc (FREESASA_GPU_FRAMES_TRICLINIC) three arms more, i
                   from calc_periodic_triclinic on frame 0.  The globule was not built for that cell: where its corners wrap onto
                   its faces atoms overlap, which a cost measurement can live with.
 
+With --groups beside --pbc three arms more, all on the filled box's frames and cells through the topology entries, the solute cut
+into two groups of 5 000 atoms, totals and group areas only:
+    filled-topo-pbc    freesasa_gpu_trajectory_file_topology with pbc=True: the plain periodic run
+    filled-groups      the chain groups' run without the bit: isolated, complex, buried of a system that is not periodic
+    filled-groups-pbc  freesasa_gpu_trajectory_file_groups_periodic: chain groups among periodic images - its totals file must be
+                       filled-topo-pbc's, byte for byte
+each line with real_atoms, group_atoms and image_atoms (the images of the complex and of its groups in frame 0): the atoms per
+frame the engine sees are their sum.
 With --netcdf beside --pbc two arms more: `solvated` and `solvated-pbc` on an AMBER NetCDF file of the same frames and cell
 (solvated-nc, solvated-nc-pbc); their totals files must be those of the DCD arms, byte for byte.
 
@@ -69,7 +77,7 @@ each line with the bytes of results per frame; the stats arm's per-atom means mu
 
 One JSON line per arm: atom-frames/s counted in SOLUTE atoms and in frame atoms, the median and the spread of --reps runs.
 
-    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd] [--netcdf] [--pbc [--pbc-arms all|off] [--triclinic]] [--xtc [--xtc-distinct 24] [--xtc-fpb 0]] [--trr [--double] [--trr-arms raw,trr]] [--stats]
+    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd] [--netcdf] [--pbc [--pbc-arms all|off] [--triclinic] [--groups]] [--xtc [--xtc-distinct 24] [--xtc-fpb 0]] [--trr [--double] [--trr-arms raw,trr]] [--stats]
 
 For the kernel times: `rocprofv3 --kernel-trace --stats -- python tools/traj_topology_bench.py --reps 1 --arms all`
 (k_traj_gather / k_traj_residues / k_traj_class / k_traj_sel are the topology's kernels, k_traj_group_* the groups')."""
@@ -384,6 +392,7 @@ def main():
     ap.add_argument("--pbc", action="store_true", help="time the DCD drivers with and without periodic images")
     ap.add_argument("--pbc-arms", default="all", choices=["all", "off"])
     ap.add_argument("--triclinic", action="store_true", help="with --pbc: the arms of the triclinic bit beside the others")
+    ap.add_argument("--groups", action="store_true", help="with --pbc: chain groups among periodic images against the plain periodic run and the non-periodic groups' run")
     ap.add_argument("--xtc", action="store_true", help="time a GROMACS XTC file against the raw fp32 file and an AMBER NetCDF file of the same decoded frames")
     ap.add_argument("--xtc-distinct", type=int, default=24, help="with --xtc: distinct frames that are encoded and then repeated")
     ap.add_argument("--xtc-fpb", type=int, default=0, help="with --xtc: frames_per_batch of all three arms (0: the driver's default)")
@@ -441,6 +450,12 @@ def main():
                 arms.update({"solvated-tri": lambda: fa.trajectory_file_topology(solv, b, p("t10"), atom_index=index, dcd=True, pbc=True, triclinic=True),
                              "filled-tri": lambda: fa.trajectory_file(fill, b.radii, p("t11"), dcd=True, pbc=True, triclinic=True),
                              "octa-tri": lambda: fa.trajectory_file(octa[0], b.radii, p("t12"), dcd=True, pbc=True, triclinic=True)})
+            if args.groups and args.pbc_arms == "all":
+                arms.update({"filled-topo-pbc": lambda: fa.trajectory_file_topology(fill, b, p("t16"), dcd=True, pbc=True),
+                             "filled-groups": lambda: fa.trajectory_file_topology(fill, b, p("t17"), dcd=True, group=ids, n_groups=2,
+                                                                                  group_areas_path=p("g17")),
+                             "filled-groups-pbc": lambda: fa.trajectory_file_groups_periodic(fill, b, p("t18"), dcd=True, group=ids, n_groups=2,
+                                                                                             group_areas_path=p("g18"))})
             if args.netcdf:
                 arms["solvated-nc"] = lambda: fa.trajectory_file_topology(solv_nc, b, p("t14"), atom_index=index, netcdf=True)
                 if args.pbc_arms == "all":
@@ -462,6 +477,16 @@ def main():
             if tri:
                 k = fa.calc_periodic_triclinic(first_frame(octa[0], N_SOLUTE), b.radii, [0, N_SOLUTE], [fa.cell_from_dcd(octa[1])])[2]
                 images["octa-tri"] = float(k[0]) / N_SOLUTE
+        atoms = {}
+        if "filled-groups-pbc" in names:  # the atoms per frame the engine sees in each of the three arms (frame 0)
+            x0 = first_frame(fill, N_SOLUTE)
+            k_c = int(fa.calc_periodic(x0, b.radii, [0, N_SOLUTE], [fill_cell])[2][0])
+            k_g = int(fa.calc_periodic(np.concatenate([x0[ids == 0], x0[ids == 1]]), np.concatenate([b.radii[ids == 0], b.radii[ids == 1]]),
+                                       [0, N_SOLUTE // 2, N_SOLUTE], [fill_cell, fill_cell])[2].sum())
+            atoms = {"filled-topo-pbc": (N_SOLUTE, 0, k_c), "filled-groups": (N_SOLUTE, N_SOLUTE, 0), "filled-groups-pbc": (N_SOLUTE, N_SOLUTE, k_c + k_g)}
+            assert np.array_equal(np.fromfile(p("t18")), np.fromfile(p("t16"))) and np.array_equal(np.fromfile(p("t18")), np.fromfile(p("t9")))
+            assert not np.array_equal(np.fromfile(p("g18")), np.fromfile(p("g17")))
+            images["filled-topo-pbc"] = images["filled-groups-pbc"] = images["filled-pbc"]
         totals = [np.fromfile(p(k)) for a, k in (("plain", "t0"), ("totals", "t1"), ("all", "t2"), ("groups", "t3"), ("raw", "t1"), ("dcd", "t5"), ("netcdf", "t13")) if a in names]
         assert all(np.array_equal(t, totals[0]) for t in totals)
         if "solvated-pbc" in names:      # no atom of the solute within c of a face: the bit changes nothing; a filled box: it must
@@ -484,6 +509,8 @@ def main():
                     "frame_atom_frames_per_s": frame_atoms * args.frames / med, "runs": len(v)}
             if args.pbc:
                 line["images_per_atom"] = images.get(a)
+            if a in atoms:
+                line["real_atoms"], line["group_atoms"], line["image_atoms"] = atoms[a]
             lines.append(json.dumps(line))
         print("\n".join(lines))
         if args.out:
