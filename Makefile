@@ -2,8 +2,8 @@
 #   make            -> freesasa_amd/lib/libfreesasa_amd.so (stand-alone drop-in library)
 #                      freesasa_amd/lib/libfreesasa_amd_seam.a (seam objects for a drop-in
 #                      build of the reference)
-#   make emu        -> tests/emu/libsasa_emu.so, libselect_emu.so, libgroups_emu.so, libtraj_emu.so, libtraj_groups_emu.so, libdcd_emu.so, libnc_emu.so, libxtc_emu.so, libtrr_emu.so, libpbc_emu.so, libpbc_tri_emu.so, libgroups_pbc_emu.so, libstats_emu.so, libvolume_emu.so, libdots_emu.so, libiface_emu.so  (TESTS ONLY: the kernel phase
-#                      functions driven on the CPU; never linked into the product) and tests/emu/dcd_check, tests/emu/cell_check, tests/emu/nc_check, tests/emu/xtc_check, tests/emu/xtc_emu_check, tests/emu/trr_check, tests/emu/stats_check, tests/emu/dots_check, tests/emu/iface_check, tests/emu/groups_pbc_check (the DCD, NetCDF, XTC and TRR header parsers, the cell arithmetic, the emulated XTC decode, the merge of the run statistics and the emulated scan and expansion of the surface dots and the emulated phases of the interfaces between chain groups under sanitizers)
+#   make emu        -> tests/emu/libsasa_emu.so, libselect_emu.so, libgroups_emu.so, libtraj_emu.so, libtraj_groups_emu.so, libdcd_emu.so, libnc_emu.so, libxtc_emu.so, libtrr_emu.so, libpbc_emu.so, libpbc_tri_emu.so, libgroups_pbc_emu.so, libstats_emu.so, libvolume_emu.so, libdots_emu.so, libiface_emu.so, libiface_res_emu.so  (TESTS ONLY: the kernel phase
+#                      functions driven on the CPU; never linked into the product) and tests/emu/dcd_check, tests/emu/cell_check, tests/emu/nc_check, tests/emu/xtc_check, tests/emu/xtc_emu_check, tests/emu/trr_check, tests/emu/stats_check, tests/emu/dots_check, tests/emu/iface_check, tests/emu/iface_res_check, tests/emu/groups_pbc_check (the DCD, NetCDF, XTC and TRR header parsers, the cell arithmetic, the emulated XTC decode, the merge of the run statistics and the emulated scan and expansion of the surface dots and the emulated phases of the interfaces between chain groups and of their per-residue tables under sanitizers)
 #   make oracle     -> oracle/ (TESTS ONLY) ; make tools -> tools/libsasa_synth.so
 HIPCC   ?= /opt/rocm/bin/hipcc
 CC      ?= gcc
@@ -97,7 +97,7 @@ $(LIBDIR)/libfreesasa_amd.so: $(GPU_OBJS) $(LIBDIR)/seam.o $(LIBDIR)/testpoints.
 $(LIBDIR)/libfreesasa_amd_seam.a: $(GPU_OBJS) $(LIBDIR)/seam.o $(LIBDIR)/testpoints.o $(LIBDIR)/dcd.o $(LIBDIR)/netcdf.o $(LIBDIR)/xtc.o $(LIBDIR)/trr.o $(LIBDIR)/cell.o $(LIBDIR)/trajstats.o $(LIBDIR)/ingest.o $(LIBDIR)/classifier.o $(LIBDIR)/select.o $(LIBDIR)/ingest_cache.o $(LIBDIR)/hostfault.o
 	rm -f $@; ar rcs $@ $^
 
-emu: tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so tests/emu/libtraj_groups_emu.so tests/emu/libdcd_emu.so tests/emu/libpbc_emu.so tests/emu/libpbc_tri_emu.so tests/emu/libgroups_pbc_emu.so tests/emu/libnc_emu.so tests/emu/libxtc_emu.so tests/emu/libtrr_emu.so tests/emu/libstats_emu.so tests/emu/libvolume_emu.so tests/emu/libdots_emu.so tests/emu/dcd_check tests/emu/cell_check tests/emu/nc_check tests/emu/xtc_check tests/emu/xtc_emu_check tests/emu/trr_check tests/emu/stats_check tests/emu/dots_check tests/emu/libiface_emu.so tests/emu/iface_check tests/emu/groups_pbc_check
+emu: tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so tests/emu/libtraj_groups_emu.so tests/emu/libdcd_emu.so tests/emu/libpbc_emu.so tests/emu/libpbc_tri_emu.so tests/emu/libgroups_pbc_emu.so tests/emu/libnc_emu.so tests/emu/libxtc_emu.so tests/emu/libtrr_emu.so tests/emu/libstats_emu.so tests/emu/libvolume_emu.so tests/emu/libdots_emu.so tests/emu/dcd_check tests/emu/cell_check tests/emu/nc_check tests/emu/xtc_check tests/emu/xtc_emu_check tests/emu/trr_check tests/emu/stats_check tests/emu/dots_check tests/emu/libiface_emu.so tests/emu/iface_check tests/emu/libiface_res_emu.so tests/emu/iface_res_check tests/emu/groups_pbc_check
 # the loader with its byte-at-a-time mmCIF tokenizer only: the differential twin of the SSE2 row scanner
 tests/emu/libingest_scalar.so: $(CSRC)/ingest.c $(CSRC)/classifier.c $(CSRC)/classifier.h $(CSRC)/hostfault.c $(CSRC)/hostfault.h $(CSRC)/protor_table.h include/freesasa_ingest.h
 	$(CC) $(CFLAGS) -DFREESASA_INGEST_NO_SIMD -Iinclude -pthread -shared -o $@ $(CSRC)/ingest.c $(CSRC)/classifier.c $(CSRC)/hostfault.c -lm
@@ -156,6 +156,12 @@ tests/emu/libiface_emu.so: tests/emu/emu_iface.cpp $(CSRC)/iface_kernels.h $(CSR
 # ... and the same phases (emu_iface.cpp with its main) under AddressSanitizer + UBSan in a stand-alone program: one line per case
 tests/emu/iface_check: tests/emu/emu_iface.cpp $(CSRC)/iface_kernels.h $(CSRC)/lr2_kernels.h $(CSRC)/sasa_kernels.h $(CSRC)/sr_caps.h
 	$(CXX) -O1 -g -std=c++17 -Wall -Wno-unused-function -Wno-unknown-pragmas -ffp-contract=off -DSASA_EMU -DIFACE_CHECK_MAIN -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -o $@ tests/emu/emu_iface.cpp -lm
+# ... their per-residue tables (iface_kernels.h, IfaceResArgs): heads, the block scan, segments and rows
+tests/emu/libiface_res_emu.so: tests/emu/emu_iface_res.cpp $(CSRC)/iface_kernels.h $(CSRC)/lr2_kernels.h $(CSRC)/sasa_kernels.h $(CSRC)/sr_caps.h
+	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -DSASA_EMU -shared -o $@ tests/emu/emu_iface_res.cpp -lm
+# ... and the same phases (emu_iface_res.cpp with its main) under AddressSanitizer + UBSan in a stand-alone program: one line per case
+tests/emu/iface_res_check: tests/emu/emu_iface_res.cpp $(CSRC)/iface_kernels.h $(CSRC)/lr2_kernels.h $(CSRC)/sasa_kernels.h $(CSRC)/sr_caps.h
+	$(CXX) -O1 -g -std=c++17 -Wall -Wno-unused-function -Wno-unknown-pragmas -ffp-contract=off -DSASA_EMU -DIFACE_RES_CHECK_MAIN -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -o $@ tests/emu/emu_iface_res.cpp -lm
 
 tests/emu/libstats_emu.so: tests/emu/emu_stats.cpp $(CSRC)/traj_kernels.h $(CSRC)/select_kernels.h $(CSRC)/select_program.h $(CSRC)/sasa_kernels.h include/freesasa_ingest.h
 	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -DSASA_EMU -Iinclude -shared -o $@ tests/emu/emu_stats.cpp -lm
@@ -202,7 +208,8 @@ $(ASAN_SO): $(CSRC)/api.c $(CSRC)/seam.c $(CSRC)/testpoints.c $(CSRC)/dcd.c $(CS
 	for f in api seam testpoints dcd netcdf xtc trr cell trajstats ingest classifier select ingest_cache hostfault; do $(CC) $(SANFLAGS) -Iinclude -pthread -c $(CSRC)/$$f.c -o tests/emu/asan_$$f.o || exit 1; done
 	$(CXX) -shared -fPIC -o $@ $(foreach f,api seam testpoints dcd netcdf xtc trr cell trajstats ingest classifier select ingest_cache hostfault,tests/emu/asan_$(f).o) $(GPU_OBJS) \
 	    -fsanitize=address,undefined -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib -lamdhip64 -lpthread -lm
-asan-test: $(ASAN_SO)
+asan-test: $(ASAN_SO) tests/emu/iface_res_check
+	tests/emu/iface_res_check
 	LD_PRELOAD="$$($(CC) -print-file-name=libasan.so) $$($(CC) -print-file-name=libubsan.so)" ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 \
 	    FREESASA_AMD_LIB=$(CURDIR)/$(ASAN_SO) python -m pytest tests/test_ingest.py tests/test_select.py tests/test_capi.py tests/test_hostfault.py tests/test_classifier.py tests/test_classifier_hostfault.py -q -m "not gpu" -p no:cacheprovider
 
@@ -214,7 +221,7 @@ tools:
 	$(MAKE) -C tools
 
 clean:
-	rm -rf $(LIBDIR) tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so tests/emu/libtraj_groups_emu.so tests/emu/libdcd_emu.so tests/emu/libpbc_emu.so tests/emu/libpbc_tri_emu.so tests/emu/libgroups_pbc_emu.so tests/emu/libnc_emu.so tests/emu/libxtc_emu.so tests/emu/dcd_check tests/emu/cell_check tests/emu/nc_check tests/emu/xtc_check tests/emu/xtc_emu_check tests/emu/xtc_*.o tests/emu/libtrr_emu.so tests/emu/trr_check tests/emu/trr_*.o tests/emu/libstats_emu.so tests/emu/stats_check tests/emu/libvolume_emu.so tests/emu/libdots_emu.so tests/emu/dots_check tests/emu/libiface_emu.so tests/emu/iface_check tests/emu/groups_pbc_check
+	rm -rf $(LIBDIR) tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so tests/emu/libtraj_groups_emu.so tests/emu/libdcd_emu.so tests/emu/libpbc_emu.so tests/emu/libpbc_tri_emu.so tests/emu/libgroups_pbc_emu.so tests/emu/libnc_emu.so tests/emu/libxtc_emu.so tests/emu/dcd_check tests/emu/cell_check tests/emu/nc_check tests/emu/xtc_check tests/emu/xtc_emu_check tests/emu/xtc_*.o tests/emu/libtrr_emu.so tests/emu/trr_check tests/emu/trr_*.o tests/emu/libstats_emu.so tests/emu/stats_check tests/emu/libvolume_emu.so tests/emu/libdots_emu.so tests/emu/dots_check tests/emu/libiface_emu.so tests/emu/iface_check tests/emu/libiface_res_emu.so tests/emu/iface_res_check tests/emu/groups_pbc_check
 	$(MAKE) -C oracle clean
 	$(MAKE) -C tools clean
 .PHONY: all emu oracle tools clean asan asan-test

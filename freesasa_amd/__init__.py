@@ -136,6 +136,15 @@ def lib():
         L.freesasa_gpu_calc_interfaces.argtypes = [_dp, _dp, _lp, C.c_int, _i32p, _i32p, C.c_int, C.c_double, C.c_int,
                                                    _dp, _dp, _dp, _dp, C.c_longlong, C.c_longlong, _llp, _llp, _i32p, _i32p, _dp,
                                                    _lp, _i32p, _dp, C.c_int, C.c_char_p, C.c_int]
+        L.freesasa_gpu_interface_residues_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _lp, C.c_int, C.c_void_p, _i32p,
+                                                          _lp, C.c_int, C.c_double, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_longlong, _llp, _llp,
+                                                          _llp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.freesasa_gpu_calc_interface_residues.argtypes = [_dp, _dp, _lp, C.c_int, _i32p, _i32p, _lp, C.c_int, C.c_int, C.c_double,
+                                                           C.c_int, C.c_double, _dp, _dp, _dp, _dp, C.c_longlong, C.c_longlong,
+                                                           C.c_longlong, _llp, _llp, _llp, _i32p, _i32p, _dp, _lp, _i32p, _dp, _lp,
+                                                           _i32p, _i32p, _dp, C.c_int, C.c_char_p, C.c_int]
         L.freesasa_gpu_sr_volume_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _lp, C.c_int, C.c_double, C.c_int,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.freesasa_gpu_calc_volume.argtypes = [_dp, _dp, _lp, C.c_int, C.c_double, C.c_int, _dp, _ip, _dp, _dp, _dp, _dp,
@@ -303,13 +312,24 @@ class InterfacePairs:
 class Interfaces:
     """calc_interfaces()'s result: sasa, iso [n], totals [n_structs], group_totals [G, 3] as calc_groups gives them; pair_struct
     [P], pair_groups [P, 2], pair_areas [P, 6] = (iso_g, iso_h, in_pair_g, in_pair_h, buried_g, buried_h); with per_atom
-    side_offsets [2P + 1], pair_atom [M], pair_buried [M] (else None)."""
+    side_offsets [2P + 1], pair_atom [M], pair_buried [M] (else None); with res_first the per-residue table: res_offsets [2P + 1]
+    (the row range of every side), res_index [R] (the batch-wide residue), res_atoms [R], res_areas [R, 3] = (iso_res,
+    in_pair_res, buried_res) and n_res_rows = R (else None)."""
 
-    def __init__(self, sasa, iso, totals, group_totals, pair_struct, pair_groups, pair_areas, side_offsets, pair_atom, pair_buried):
+    def __init__(self, sasa, iso, totals, group_totals, pair_struct, pair_groups, pair_areas, side_offsets, pair_atom, pair_buried,
+                 res_offsets=None, res_index=None, res_atoms=None, res_areas=None):
         self.sasa, self.iso, self.totals, self.group_totals = sasa, iso, totals, group_totals
         self.pair_struct, self.pair_groups, self.pair_areas = pair_struct, pair_groups, pair_areas
         self.side_offsets, self.pair_atom, self.pair_buried = side_offsets, pair_atom, pair_buried
         self.n_pairs = int(pair_struct.size)
+        self.res_offsets, self.res_index, self.res_atoms, self.res_areas = res_offsets, res_index, res_atoms, res_areas
+        self.n_res_rows = None if res_areas is None else int(res_areas.shape[0])
+
+    def side_rows(self, p, side):
+        """the rows of side 0 (group g) or 1 (group h) of pair p, as a slice into res_index, res_atoms and res_areas"""
+        if self.res_offsets is None:
+            raise ValueError("no per-residue table: calc_interfaces() was called without res_first")
+        return slice(int(self.res_offsets[2 * p + side]), int(self.res_offsets[2 * p + side + 1]))
 
 
 def interface_pairs(xyz, radii, offsets, group, n_groups, alg=LEE_RICHARDS, probe=1.4, resolution=20, device=-1):
@@ -335,10 +355,14 @@ def interface_pairs(xyz, radii, offsets, group, n_groups, alg=LEE_RICHARDS, prob
     return InterfacePairs(int(P.value), int(M.value), ps, pg, int(stats[0]), int(stats[1]))
 
 
-def calc_interfaces(xyz, radii, offsets, group, n_groups, alg=LEE_RICHARDS, probe=1.4, resolution=20, device=-1, per_atom=False):
+def calc_interfaces(xyz, radii, offsets, group, n_groups, alg=LEE_RICHARDS, probe=1.4, resolution=20, device=-1, per_atom=False,
+                    res_first=None, min_buried=0.0):
     """freesasa_gpu_calc_interfaces() on host arrays -> Interfaces: calc_groups()'s results and a row for every pair of groups of
     a structure that are in contact, with each side's isolated area, its area in the pair taken on its own, and the
-    difference: the interface area.  The arrays are sized by a first interface_pairs() call."""
+    difference: the interface area.  The arrays are sized by a first interface_pairs() call.
+    res_first (the batch's residue boundaries [n_res + 1], as ingest.Batch.res_first): freesasa_gpu_calc_interface_residues()
+    instead, which adds the per-residue table - a row for every residue of a side that loses more than min_buried; it has at
+    most as many rows as the pair structures have atoms, so its arrays are sized by the same first call and trimmed."""
     xyz, radii, offsets, group, n_groups = _group_batch(xyz, radii, offsets, group, n_groups)
     n, ns = radii.size, offsets.size - 1
     pairs = interface_pairs(xyz, radii, offsets, group, n_groups, alg, probe, resolution, device)
@@ -350,6 +374,25 @@ def calc_interfaces(xyz, radii, offsets, group, n_groups, alg=LEE_RICHARDS, prob
     i32 = C.POINTER(C.c_int32)
     opt = lambda a, t: None if a is None else a.ctypes.data_as(t)
     Pc, Mc, err = C.c_longlong(0), C.c_longlong(0), C.create_string_buffer(512)
+    if res_first is not None:
+        res_first = np.ascontiguousarray(res_first, dtype=np.int64)
+        if res_first.ndim != 1 or res_first.size < 2:
+            raise ValueError("res_first must be a one-dimensional array of n_res + 1 >= 2 boundaries")
+        ro, ri, ra, rar = np.empty(2 * P + 1, dtype=np.int64), np.empty(M, dtype=np.int32), np.empty(M, dtype=np.int32), np.empty((M, 3))
+        Rc = C.c_longlong(0)
+        ret = lib().freesasa_gpu_calc_interface_residues(xyz.ctypes.data_as(_dp), radii.ctypes.data_as(_dp), offsets.ctypes.data_as(_lp), ns,
+                                                         group.ctypes.data_as(i32), n_groups.ctypes.data_as(i32),
+                                                         res_first.ctypes.data_as(_lp), res_first.size - 1, alg, probe, resolution,
+                                                         min_buried, sasa.ctypes.data_as(_dp), iso.ctypes.data_as(_dp),
+                                                         totals.ctypes.data_as(_dp), gt.ctypes.data_as(_dp), P, M, M, C.byref(Pc),
+                                                         C.byref(Mc), C.byref(Rc), ps.ctypes.data_as(i32), pg.ctypes.data_as(i32),
+                                                         areas.ctypes.data_as(_dp), opt(so, _lp), opt(pa, i32), opt(pb, _dp),
+                                                         ro.ctypes.data_as(_lp), ri.ctypes.data_as(i32), ra.ctypes.data_as(i32),
+                                                         rar.ctypes.data_as(_dp), device, err, 512)
+        if ret:
+            raise RuntimeError("freesasa_gpu_calc_interface_residues: " + err.value.decode())
+        R = int(Rc.value)
+        return Interfaces(sasa, iso, totals, gt, ps, pg, areas, so, pa, pb, ro, ri[:R].copy(), ra[:R].copy(), rar[:R].copy())
     ret = lib().freesasa_gpu_calc_interfaces(xyz.ctypes.data_as(_dp), radii.ctypes.data_as(_dp), offsets.ctypes.data_as(_lp), ns,
                                              group.ctypes.data_as(i32), n_groups.ctypes.data_as(i32), alg, probe, resolution,
                                              sasa.ctypes.data_as(_dp), iso.ctypes.data_as(_dp), totals.ctypes.data_as(_dp),
@@ -1844,6 +1887,30 @@ class GpuContext:
                                              d_side_offsets or None, d_pair_atom or None, d_pair_buried or None):
             raise RuntimeError("freesasa_gpu_interfaces_dev: " + self.error())
         return int(P.value), int(M.value)
+
+    def interface_residues(self, d_xyz, d_radii, offsets, d_group, n_groups, res_first, d_sasa, d_iso, pair_capacity, d_pair_areas,
+                           res_capacity, d_res_areas, d_res_offsets=0, d_res_index=0, d_res_atoms=0, d_pair_struct=0, d_pair_groups=0,
+                           atom_capacity=0, d_side_offsets=0, d_pair_atom=0, d_pair_buried=0, d_totals=0, d_group_totals=0,
+                           alg=LEE_RICHARDS, probe=1.4, resolution=20, min_buried=0.0):
+        """freesasa_gpu_interface_residues_dev(): interfaces() and the per-residue table of every side - res_first: a host
+        array of the batch's residue boundaries [n_res + 1]; d_res_areas [3 R], d_res_index [R], d_res_atoms [R]: device arrays
+        that hold res_capacity rows, d_res_offsets [2 P + 1] one that holds pair_capacity rows - a row for every residue of a
+        side that loses more than min_buried -> (n_pairs, n_pair_atoms, n_res_rows); a capacity that is too small: RuntimeError
+        naming the number."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        ng = np.ascontiguousarray(n_groups, dtype=np.int32)
+        res_first = np.ascontiguousarray(res_first, dtype=np.int64)
+        P, M, R = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        if lib().freesasa_gpu_interface_residues_dev(self._h, alg, d_xyz, d_radii, offsets.ctypes.data_as(_lp), offsets.size - 1, d_group,
+                                                     ng.ctypes.data_as(C.POINTER(C.c_int32)), res_first.ctypes.data_as(_lp),
+                                                     res_first.size - 1, probe, resolution, min_buried, d_sasa or None, d_iso or None,
+                                                     d_totals or None, d_group_totals or None, pair_capacity, atom_capacity,
+                                                     res_capacity, C.byref(P), C.byref(M), C.byref(R), d_pair_struct or None,
+                                                     d_pair_groups or None, d_pair_areas or None, d_side_offsets or None,
+                                                     d_pair_atom or None, d_pair_buried or None, d_res_offsets or None,
+                                                     d_res_index or None, d_res_atoms or None, d_res_areas or None):
+            raise RuntimeError("freesasa_gpu_interface_residues_dev: " + self.error())
+        return int(P.value), int(M.value), int(R.value)
 
     def periodic(self, d_xyz, d_radii, offsets, cells, d_sasa, d_totals=0, alg=LEE_RICHARDS, probe=1.4, resolution=20):
         """freesasa_gpu_periodic_dev(): every atom's area among the periodic images of its structure's cell (cells: a host

@@ -157,6 +157,11 @@ hipError_t kl_iface_candidates(const sasa::IfaceArgs &a, hipStream_t st);
 hipError_t kl_iface_contact(const sasa::IfaceArgs &a, hipStream_t st);
 hipError_t kl_iface_gather(const sasa::IfaceArgs &a, hipStream_t st);
 hipError_t kl_iface_finish(const sasa::IfaceArgs &a, hipStream_t st);
+/* ... their per-residue tables (IfaceResArgs): heads, the scan of the heads, the segments' first atoms and sums; the scan of the
+   keep flags and the rows.  kl_iface_res_scan: the in-place exclusive block scan both use (scratch: ifr_scan_scratch(n) ints) */
+hipError_t kl_iface_res_scan(int *a, int64_t n, int *scratch, hipStream_t st);
+hipError_t kl_iface_res_segments(const sasa::IfaceResArgs &a, int *scratch, hipStream_t st);
+hipError_t kl_iface_res_rows(const sasa::IfaceResArgs &a, int *scratch, hipStream_t st);
 
 /* ------------------------------------------------------------------ context (gpu_engine.hip) */
 
@@ -232,6 +237,8 @@ struct freesasa_gpu_ctx {
     /* interfaces between chain groups (gpu_interfaces.hip): group starts and test bases; boxes; the candidates' list, its length
        and the flags; the sides' tables; the pair batch, its areas and what is made of them; the host-pointer entry's rows */
     DevBuf if_meta, if_box, if_cand, if_flag, if_sides, if_xyz, if_radii, if_comb, if_sasa, if_inpair, if_areas, if_patom, if_pburied, if_rows;
+    /* ... their per-residue tables: the residue boundaries; the int32 work arrays; the segments' areas; the table itself */
+    DevBuf if_rfirst, if_rwork, if_rsegs, if_rtable;
     int dt_unit_n = 0; /* the point count whose unit points dt_unit holds (the expansion's; 0: none) */
     void *stage_in = nullptr, *stage_out = nullptr; /* page-locked host staging of freesasa_gpu_calc_batch_pipelined */
     size_t stage_in_cap = 0, stage_out_cap = 0;

@@ -1,7 +1,8 @@
 /*
  * gpu_interfaces.hip — pairwise interface areas between chain groups (include/freesasa_gpu.h: freesasa_gpu_interface_pairs_dev,
- * freesasa_gpu_interfaces_dev, freesasa_gpu_calc_interface_pairs, freesasa_gpu_calc_interfaces).  Host code; the kernels are in
- * gpu_kernels.hip (phase functions: iface_kernels.h).
+ * freesasa_gpu_interfaces_dev, freesasa_gpu_calc_interface_pairs, freesasa_gpu_calc_interfaces) and their per-residue tables
+ * (freesasa_gpu_interface_residues_dev, freesasa_gpu_calc_interface_residues).  Host code; the kernels are in gpu_kernels.hip
+ * (phase functions: iface_kernels.h).
  *
  *   1. groups_resident   the chain-group pipeline as it is: the combined batch stays in c->g_xyz / g_radii / g_src, its areas in
  *                        c->g_sasa, its totals in c->g_tot; the groups' atom counts are on the host
@@ -17,6 +18,11 @@
  * iface_screen is steps 1 to 5, iface_pipeline all of them; the pipeline's results stay in the context's own buffers and the
  * entries deliver them - to device arrays or to host arrays - once the capacities have been held against P and M, so that a
  * call that fails for its capacities has written none of the caller's pair arrays.
+ *
+ * The residue entries run iface_pipeline as it is and one more stage behind it:
+ *   9. residues          iface_residues: k_iface_res_head, the block scan, k_iface_res_first, k_iface_res_segment, the scan again,
+ *                        k_iface_res_rows; R comes back (one more stream synchronization); the table stays in c->if_rtable
+ * and hold the three capacities against P, M and R together, once R is known (iface_res_check_caps), before anything is delivered.
  */
 #include <hip/hip_runtime.h>
 
@@ -227,6 +233,91 @@ int iface_pipeline(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const doub
     return 0;
 }
 
+/* the per-residue tables: what an entry gives on top of the interface entries' arguments, and what it wants back */
+struct IfaceResWant {
+    const int64_t *res_first = nullptr;
+    int n_res = 0;
+    double min_buried = 0;
+    long long res_capacity = 0;
+    long long *n_res_rows_out = nullptr;
+};
+/* ... checked before a device is touched, behind iface_bad_args and iface_bad_caps: 0, or the message in msg */
+int iface_res_bad_args(const IfaceResWant &rw, const int64_t *offsets, int n_structs, char *msg, size_t len)
+{
+    if (!rw.res_first || !rw.n_res_rows_out) { snprintf(msg, len, "null argument"); return -1; }
+    if (rw.n_res <= 0) { snprintf(msg, len, "n_res must be > 0"); return -1; }
+    if (!(rw.min_buried >= 0.0) || rw.min_buried > 1.7976931348623157e308) { snprintf(msg, len, "min_buried must be finite and >= 0"); return -1; }
+    if (rw.res_capacity < 0) { snprintf(msg, len, "res_capacity must be >= 0 (it is %lld)", rw.res_capacity); return -1; }
+    if (rw.res_first[0] != 0) { snprintf(msg, len, "res_first[0] must be 0"); return -1; }
+    for (int r = 0; r < rw.n_res; ++r)
+        if (rw.res_first[r + 1] < rw.res_first[r]) { snprintf(msg, len, "res_first must be non-decreasing"); return -1; }
+    if (rw.res_first[rw.n_res] != offsets[n_structs]) {
+        snprintf(msg, len, "res_first[n_res] is %lld: the batch has %lld atoms", (long long)rw.res_first[rw.n_res], (long long)offsets[n_structs]);
+        return -1;
+    }
+    int s = 0;
+    for (int r = 0; r < rw.n_res; ++r) {
+        const int64_t b = rw.res_first[r], e = rw.res_first[r + 1];
+        if (b == e) continue;
+        while (offsets[s + 1] <= b) ++s; /* (b < offsets[n_structs]: the structure that holds the residue's first atom) */
+        if (e > offsets[s + 1]) { snprintf(msg, len, "residue %d spans the boundary between structures %d and %d", r, s, s + 1); return -1; }
+    }
+    return 0;
+}
+
+/* the stage behind iface_pipeline (k_iface_finish is the last thing on the stream): the table in c->if_rtable - res_offsets
+   [2 P + 1] | res_areas [3 M] | res_index [M] | res_atoms [M], R rows of them used; R comes back to the host (one stream
+   synchronization), so at the stage's end the stream is idle */
+struct IfaceResTable {
+    int64_t R = 0;
+    const int64_t *off = nullptr;
+    const double *areas = nullptr;
+    const int32_t *index = nullptr, *atoms = nullptr;
+    std::vector<int64_t> first; /* the upload of res_first (like the plan, the table lives until the stream is idle) */
+};
+int iface_residues(freesasa_gpu_ctx *c, const IfacePlan &pl, const IfaceResWant &rw, const double *d_iso, IfaceResTable &t)
+{
+    t.R = 0;
+    if (pl.P == 0) return 0;
+    const size_t P = (size_t)pl.P, M = (size_t)pl.M;
+    const size_t S = (size_t)ifr_scan_scratch(pl.M);
+    hipStream_t st = c->stream;
+    if (ensure(c, c->if_rfirst, 8 * ((size_t)rw.n_res + 1)) || ensure(c, c->if_rwork, 4 * (6 * M + 3 + S) + 8) ||
+        ensure(c, c->if_rsegs, 24 * M) || ensure(c, c->if_rtable, 8 * (2 * P + 1) + 24 * M + 8 * M))
+        return -1;
+    IfaceResArgs a;
+    memset(&a, 0, sizeof a);
+    a.n_pair_atoms = pl.M; a.n_sides = 2 * pl.P; a.n_res = rw.n_res;
+    a.side_off = (const int64_t *)c->if_sides.p; a.pair_atom = (const int *)c->if_patom.p;
+    a.res_first = (const int64_t *)c->if_rfirst.p; a.iso = d_iso; a.psasa = (const double *)c->if_sasa.p;
+    a.min_buried = rw.min_buried;
+    int *w = (int *)c->if_rwork.p;
+    a.atom_res = w; a.hs = w + M; a.seg_first = a.hs + M + 1; a.seg_res = a.seg_first + M + 1; a.seg_atoms = a.seg_res + M; a.ks = a.seg_atoms + M;
+    int *scratch = a.ks + M + 1;
+    a.seg_areas = (double *)c->if_rsegs.p;
+    a.res_off = (int64_t *)c->if_rtable.p; a.res_areas = (double *)(a.res_off + 2 * P + 1);
+    a.res_index = (int *)(a.res_areas + 3 * M); a.res_atoms = a.res_index + M;
+    /* (the upload's source is the stage's own copy, as the plan's arrays are: what the device searches is what was copied here,
+       whatever becomes of the caller's array while the stream runs) */
+    t.first.assign(rw.res_first, rw.res_first + rw.n_res + 1);
+    HIP_TRY(c, hipMemcpyAsync(c->if_rfirst.p, t.first.data(), 8 * t.first.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, kl_iface_res_segments(a, scratch, st));
+    HIP_TRY(c, kl_iface_res_rows(a, scratch, st));
+    int R = 0;
+    HIP_TRY(c, hipMemcpyAsync(&R, a.ks + M, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    t.R = R; t.off = a.res_off; t.areas = a.res_areas; t.index = a.res_index; t.atoms = a.res_atoms;
+    return 0;
+}
+/* the three capacities against P, M and R, in this order, with the interface entries' messages for the first two */
+int iface_res_check_caps(freesasa_gpu_ctx *c, const IfacePlan &pl, const IfaceWant &w, const IfaceResWant &rw, int64_t R)
+{
+    if (iface_check_caps(c, pl, w)) return -1;
+    if (R > rw.res_capacity)
+        return ctx_fail(c, "res_capacity %lld is too small: the interfaces have %lld residue rows", rw.res_capacity, (long long)R);
+    return 0;
+}
+
 int iface_dev_checks(freesasa_gpu_ctx *c, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
                      const int32_t *d_group, const int32_t *n_groups, int alg, int resolution, long long pair_capacity, long long atom_capacity)
 {
@@ -313,24 +404,84 @@ extern "C" int freesasa_gpu_interfaces_dev(freesasa_gpu_ctx *c, int alg, const d
     });
 }
 
+extern "C" int freesasa_gpu_interface_residues_dev(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii,
+                                                   const int64_t *offsets, int n_structs, const int32_t *d_group, const int32_t *n_groups,
+                                                   const int64_t *res_first, int n_res, double probe_radius, int resolution,
+                                                   double min_buried, double *d_sasa, double *d_iso, double *d_totals,
+                                                   double *d_group_totals, long long pair_capacity, long long atom_capacity,
+                                                   long long res_capacity, long long *n_pairs_out, long long *n_pair_atoms_out,
+                                                   long long *n_res_rows_out, int32_t *d_pair_struct, int32_t *d_pair_groups,
+                                                   double *d_pair_areas, int64_t *d_side_offsets, int32_t *d_pair_atom,
+                                                   double *d_pair_buried, int64_t *d_res_offsets, int32_t *d_res_index,
+                                                   int32_t *d_res_atoms, double *d_res_areas)
+{
+    if (!c) return -1;
+    if (freesasa_gpu_wait(c)) return -1;
+    return guarded_ctx(c, [&]() -> int {
+        char msg[200];
+        c->err[0] = 0;
+        IfaceResWant rw;
+        rw.res_first = res_first; rw.n_res = n_res; rw.min_buried = min_buried; rw.res_capacity = res_capacity; rw.n_res_rows_out = n_res_rows_out;
+        if (iface_bad_args(d_xyz, d_radii, offsets, n_structs, d_group, n_groups, alg, resolution, msg, sizeof msg) ||
+            iface_bad_caps(pair_capacity, atom_capacity, msg, sizeof msg) || iface_res_bad_args(rw, offsets, n_structs, msg, sizeof msg))
+            return ctx_fail(c, "%s", msg);
+        if (iface_dev_checks(c, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, alg, resolution, pair_capacity, atom_capacity)) return -1;
+        if (!d_sasa || !d_iso || !n_pairs_out || !n_pair_atoms_out || !d_pair_areas || !d_res_areas) return ctx_fail(c, "null argument");
+        IfacePlan pl; /* (plan and table hold the sources of copies enqueued below: they live until the stream is idle) */
+        IfaceResTable t;
+        IfaceWant w, none; /* (the pipeline holds no capacity against its counts here: the three are held together, once R is known) */
+        w.pair_capacity = pair_capacity; w.atom_capacity = atom_capacity; w.rows = true; w.atoms = d_pair_atom || d_pair_buried;
+        int rc = [&]() -> int {
+            if (iface_pipeline(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe_radius, resolution, d_sasa, d_iso,
+                               d_totals, d_group_totals, none, pl, n_pairs_out, n_pair_atoms_out) ||
+                iface_residues(c, pl, rw, d_iso, t))
+                return -1;
+            *n_res_rows_out = t.R;
+            if (iface_res_check_caps(c, pl, w, rw, t.R)) return -1;
+            const size_t P = (size_t)pl.P, M = (size_t)pl.M, R = (size_t)t.R;
+            hipStream_t st = c->stream;
+            if (d_side_offsets) HIP_TRY(c, hipMemcpyAsync(d_side_offsets, pl.side_off.data(), 8 * (2 * P + 1), hipMemcpyHostToDevice, st));
+            if (P == 0) {
+                if (d_res_offsets) HIP_TRY(c, hipMemsetAsync(d_res_offsets, 0, 8, st));
+                return 0;
+            }
+            if (d_pair_struct) HIP_TRY(c, hipMemcpyAsync(d_pair_struct, pl.pair_struct.data(), 4 * P, hipMemcpyHostToDevice, st));
+            if (d_pair_groups) HIP_TRY(c, hipMemcpyAsync(d_pair_groups, pl.pair_groups.data(), 8 * P, hipMemcpyHostToDevice, st));
+            HIP_TRY(c, hipMemcpyAsync(d_pair_areas, c->if_areas.p, 48 * P, hipMemcpyDeviceToDevice, st));
+            if (d_pair_atom) HIP_TRY(c, hipMemcpyAsync(d_pair_atom, c->if_patom.p, 4 * M, hipMemcpyDeviceToDevice, st));
+            if (d_pair_buried) HIP_TRY(c, hipMemcpyAsync(d_pair_buried, c->if_pburied.p, 8 * M, hipMemcpyDeviceToDevice, st));
+            if (d_res_offsets) HIP_TRY(c, hipMemcpyAsync(d_res_offsets, t.off, 8 * (2 * P + 1), hipMemcpyDeviceToDevice, st));
+            if (R == 0) return 0;
+            if (d_res_index) HIP_TRY(c, hipMemcpyAsync(d_res_index, t.index, 4 * R, hipMemcpyDeviceToDevice, st));
+            if (d_res_atoms) HIP_TRY(c, hipMemcpyAsync(d_res_atoms, t.atoms, 4 * R, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(c, hipMemcpyAsync(d_res_areas, t.areas, 24 * R, hipMemcpyDeviceToDevice, st));
+            return 0;
+        }();
+        if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = ctx_fail(c, "stream synchronize failed"); /* (the call is synchronous) */
+        return rc;
+    });
+}
+
 /* the host-pointer entries: the batch as one chunk of the host-batch path, in place, as freesasa_gpu_calc_groups has it */
 static int iface_host(const double *xyz, const double *radii, const int64_t *offsets, int n_structs, const int32_t *group,
                       const int32_t *n_groups, int alg, double probe, int resolution, double *sasa_out, double *iso_out, double *totals_out,
                       double *group_totals_out, bool whole, long long pair_capacity, long long atom_capacity, long long *n_pairs_out,
                       long long *n_pair_atoms_out, int32_t *pair_struct_out, int32_t *pair_groups_out, double *pair_areas_out,
                       int64_t *side_offsets_out, int32_t *pair_atom_out, double *pair_buried_out, long long *stats_out, int device,
-                      char *err_out, int err_len)
+                      char *err_out, int err_len, const IfaceResWant *rw = nullptr, int64_t *res_offsets_out = nullptr,
+                      int32_t *res_index_out = nullptr, int32_t *res_atoms_out = nullptr, double *res_areas_out = nullptr)
 {
     if (err_out && err_len > 0) err_out[0] = 0;
     char msg[200];
     if (iface_bad_args(xyz, radii, offsets, n_structs, group, n_groups, alg, resolution, msg, sizeof msg) ||
-        iface_bad_caps(pair_capacity, atom_capacity, msg, sizeof msg))
+        iface_bad_caps(pair_capacity, atom_capacity, msg, sizeof msg) || (rw && iface_res_bad_args(*rw, offsets, n_structs, msg, sizeof msg)))
         return set_err(err_out, err_len, msg);
-    if (!n_pairs_out || !n_pair_atoms_out || (whole && !pair_areas_out)) return set_err(err_out, err_len, "null argument");
+    if (!n_pairs_out || !n_pair_atoms_out || (whole && !pair_areas_out) || (rw && !res_areas_out)) return set_err(err_out, err_len, "null argument");
     if (freesasa_gpu_device_count() <= 0)
         return set_err(err_out, err_len, "no HIP device available: libfreesasa_amd has no CPU path");
     return guarded(err_out, err_len, [&]() -> int {
     IfacePlan pl; /* (declared before the lease: freed after its stream is idle) */
+    IfaceResTable t;
     PoolLease lease(device);
     freesasa_gpu_ctx *c = lease.c;
     if (!c) return set_err(err_out, err_len, "could not create a GPU context");
@@ -356,9 +507,15 @@ static int iface_host(const double *xyz, const double *radii, const int64_t *off
         w.pair_capacity = pair_capacity; w.atom_capacity = atom_capacity;
         if (whole) {
             w.rows = true; w.atoms = pair_atom_out || pair_buried_out;
+            /* (with residues the pipeline holds no capacity itself: the three are held together, once R is known) */
             if (iface_pipeline(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe, resolution, d_sasa, d_iso, d_tot, d_gtot,
-                               w, pl, n_pairs_out, n_pair_atoms_out))
+                               rw ? IfaceWant() : w, pl, n_pairs_out, n_pair_atoms_out))
                 return -1;
+            if (rw) {
+                if (iface_residues(c, pl, *rw, d_iso, t)) return -1;
+                *rw->n_res_rows_out = t.R;
+                if (iface_res_check_caps(c, pl, w, *rw, t.R)) return -1;
+            }
         } else {
             IfaceArgs ia;
             w.rows = pair_struct_out || pair_groups_out;
@@ -367,7 +524,14 @@ static int iface_host(const double *xyz, const double *radii, const int64_t *off
             *n_pairs_out = pl.P; *n_pair_atoms_out = pl.M;
             if (iface_check_caps(c, pl, w)) return -1;
         }
-        const size_t P = (size_t)pl.P, M = (size_t)pl.M;
+        const size_t P = (size_t)pl.P, M = (size_t)pl.M, R = (size_t)t.R;
+        if (rw && res_offsets_out && P == 0) res_offsets_out[0] = 0;
+        if (rw && P > 0 &&
+            ((res_offsets_out && hipMemcpyAsync(res_offsets_out, t.off, 8 * (2 * P + 1), hipMemcpyDeviceToHost, st) != hipSuccess) ||
+             (R > 0 && res_index_out && hipMemcpyAsync(res_index_out, t.index, 4 * R, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+             (R > 0 && res_atoms_out && hipMemcpyAsync(res_atoms_out, t.atoms, 4 * R, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+             (R > 0 && hipMemcpyAsync(res_areas_out, t.areas, 24 * R, hipMemcpyDeviceToHost, st) != hipSuccess)))
+            return ctx_fail(c, "device-to-host copy failed");
         if ((sasa_out && hipMemcpyAsync(sasa_out, d_sasa, 8 * n, hipMemcpyDeviceToHost, st) != hipSuccess) ||
             (iso_out && hipMemcpyAsync(iso_out, d_iso, 8 * n, hipMemcpyDeviceToHost, st) != hipSuccess) ||
             (totals_out && hipMemcpyAsync(totals_out, d_tot, 8 * (size_t)n_structs, hipMemcpyDeviceToHost, st) != hipSuccess) ||
@@ -407,4 +571,23 @@ extern "C" int freesasa_gpu_calc_interfaces(const double *xyz, const double *rad
     return iface_host(xyz, radii, offsets, n_structs, group, n_groups, alg, probe_radius, resolution, sasa_out, iso_out, totals_out,
                       group_totals_out, true, pair_capacity, atom_capacity, n_pairs_out, n_pair_atoms_out, pair_struct_out, pair_groups_out,
                       pair_areas_out, side_offsets_out, pair_atom_out, pair_buried_out, nullptr, device, err_out, err_len);
+}
+
+extern "C" int freesasa_gpu_calc_interface_residues(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
+                                                    const int32_t *group, const int32_t *n_groups, const int64_t *res_first, int n_res,
+                                                    int alg, double probe_radius, int resolution, double min_buried, double *sasa_out,
+                                                    double *iso_out, double *totals_out, double *group_totals_out,
+                                                    long long pair_capacity, long long atom_capacity, long long res_capacity,
+                                                    long long *n_pairs_out, long long *n_pair_atoms_out, long long *n_res_rows_out,
+                                                    int32_t *pair_struct_out, int32_t *pair_groups_out, double *pair_areas_out,
+                                                    int64_t *side_offsets_out, int32_t *pair_atom_out, double *pair_buried_out,
+                                                    int64_t *res_offsets_out, int32_t *res_index_out, int32_t *res_atoms_out,
+                                                    double *res_areas_out, int device, char *err_out, int err_len)
+{
+    IfaceResWant rw;
+    rw.res_first = res_first; rw.n_res = n_res; rw.min_buried = min_buried; rw.res_capacity = res_capacity; rw.n_res_rows_out = n_res_rows_out;
+    return iface_host(xyz, radii, offsets, n_structs, group, n_groups, alg, probe_radius, resolution, sasa_out, iso_out, totals_out,
+                      group_totals_out, true, pair_capacity, atom_capacity, n_pairs_out, n_pair_atoms_out, pair_struct_out, pair_groups_out,
+                      pair_areas_out, side_offsets_out, pair_atom_out, pair_buried_out, nullptr, device, err_out, err_len, &rw,
+                      res_offsets_out, res_index_out, res_atoms_out, res_areas_out);
 }

@@ -1347,6 +1347,76 @@ hipError_t kl_iface_finish(const IfaceArgs &a, hipStream_t st)
     return hipGetLastError();
 }
 
+/* ... their per-residue tables (iface_kernels.h, IfaceResArgs): heads, segments and rows, one thread per pair-structure atom /
+   segment, and between them the block scan of int32 counts in place: the levels' sums bottom up, one workgroup over the top
+   level, the levels applied top down - plain launches, each ordered behind the one before by the stream */
+__global__ __launch_bounds__(IF_B) void k_iface_res_head(IfaceResArgs a)
+{
+    iface_res_head(a, (int64_t)blockIdx.x * IF_B + threadIdx.x);
+}
+__global__ __launch_bounds__(IF_B) void k_iface_res_first(IfaceResArgs a)
+{
+    iface_res_first(a, (int64_t)blockIdx.x * IF_B + threadIdx.x);
+}
+__global__ __launch_bounds__(IF_B) void k_iface_res_segment(IfaceResArgs a)
+{
+    iface_res_segment(a, (int64_t)blockIdx.x * IF_B + threadIdx.x);
+}
+__global__ __launch_bounds__(IF_B) void k_iface_res_rows(IfaceResArgs a)
+{
+    iface_res_rows(a, (int64_t)blockIdx.x * IF_B + threadIdx.x);
+}
+__global__ __launch_bounds__(IF_B) void k_iface_res_scan_sums(const int *in, int64_t n, int *sums)
+{
+    __shared__ int part[IF_B];
+    ifr_scan_sums_phase0(in, n, part, blockIdx.x, threadIdx.x);
+    __syncthreads();
+    ifr_scan_sums_phase1(part, sums, blockIdx.x, threadIdx.x);
+}
+__global__ __launch_bounds__(IF_B) void k_iface_res_scan_apply(int *a, int64_t n, const int *base, int *total)
+{
+    __shared__ int part[IF_B];
+    ifr_scan_apply_phase0(a, n, part, blockIdx.x, threadIdx.x);
+    __syncthreads();
+    ifr_scan_apply_phase1(part, total, threadIdx.x);
+    __syncthreads();
+    ifr_scan_apply_phase2(a, n, part, base, blockIdx.x, threadIdx.x);
+}
+/* a [n + 1] in place: a[i] = the sum of what a[0 .. i - 1] held, a[n] = the sum of all; scratch: ifr_scan_scratch(n) ints */
+hipError_t kl_iface_res_scan(int *a, int64_t n, int *scratch, hipStream_t st)
+{
+    int64_t cnt[IFR_MAX_LEVELS];
+    int *lvl[IFR_MAX_LEVELS];
+    const int top = ifr_scan_levels(n, cnt);
+    lvl[0] = a;
+    for (int l = 1; l <= top; ++l) lvl[l] = l == 1 ? scratch : lvl[l - 1] + cnt[l - 1];
+    for (int l = 0; l < top; ++l)
+        hipLaunchKernelGGL(k_iface_res_scan_sums, dim3((unsigned)cnt[l + 1]), dim3(IF_B), 0, st, (const int *)lvl[l], cnt[l], lvl[l + 1]);
+    hipLaunchKernelGGL(k_iface_res_scan_apply, dim3(1), dim3(IF_B), 0, st, lvl[top], cnt[top], (const int *)nullptr, a + n);
+    for (int l = top - 1; l >= 0; --l)
+        hipLaunchKernelGGL(k_iface_res_scan_apply, dim3((unsigned)cnt[l + 1]), dim3(IF_B), 0, st, lvl[l], cnt[l], (const int *)lvl[l + 1], (int *)nullptr);
+    return hipGetLastError();
+}
+hipError_t kl_iface_res_segments(const IfaceResArgs &a, int *scratch, hipStream_t st)
+{
+    if (a.n_pair_atoms == 0) return hipSuccess;
+    const dim3 grid((unsigned)((a.n_pair_atoms + IF_B - 1) / IF_B));
+    hipLaunchKernelGGL(k_iface_res_head, grid, dim3(IF_B), 0, st, a);
+    hipError_t e = kl_iface_res_scan(a.hs, a.n_pair_atoms, scratch, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_iface_res_first, grid, dim3(IF_B), 0, st, a);
+    hipLaunchKernelGGL(k_iface_res_segment, grid, dim3(IF_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_iface_res_rows(const IfaceResArgs &a, int *scratch, hipStream_t st)
+{
+    if (a.n_pair_atoms == 0) return hipSuccess;
+    hipError_t e = kl_iface_res_scan(a.ks, a.n_pair_atoms, scratch, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_iface_res_rows, dim3((unsigned)((a.n_pair_atoms + 1 + IF_B - 1) / IF_B)), dim3(IF_B), 0, st, a);
+    return hipGetLastError();
+}
+
 void kl_dump_phase_clocks(void)
 {
 #ifdef SASA_PHASE_TIMING

@@ -274,6 +274,156 @@ SASA_D void iface_finish_row(const IfaceArgs &a, int64_t p)
     o[0] = ig; o[1] = ih; o[2] = pg; o[3] = ph; o[4] = ig - pg; o[5] = ih - ph;
 }
 
+/*
+ * PER-RESIDUE TABLES (freesasa_gpu_interface_residues_dev; include/freesasa_gpu.h has the definitions, tests/interface_residues_ref.py
+ * restates them in numpy): behind step 8, the residues of every side that lose area, as a compact table whose size only the
+ * device knows.  A SEGMENT is a maximal run of consecutive pair-structure atoms of one side whose input atoms lie in one
+ * residue; a segment whose buried area exceeds min_buried gets a ROW.
+ *
+ *   iface_res_head       one thread per pair-structure atom m: its residue (the last r with res_first[r] <= pair_atom[m]: empty
+ *                        residues are never found) and its head flag - m starts a side, or the atom before it lies in another
+ *                        residue - into hs[m]
+ *   scan                 hs[0 .. M] becomes the exclusive prefix sum of the flags in place, hs[M] = K segments (below)
+ *   iface_res_first      one thread per m: a head writes seg_first[hs[m]] = m; the last atom also seg_first[K] = M
+ *   iface_res_segment    one thread per k < M: segment k < K sums iso (d_iso[pair_atom[m]]) and in_pair (the pair batch's area)
+ *                        over its atoms in strict atom order, one addition at a time, as segsum_small does; buried = iso - in_pair;
+ *                        ks[k] = buried > min_buried (strict, fp64); k >= K: ks[k] = 0
+ *   scan                 ks[0 .. M] likewise, ks[M] = R rows
+ *   iface_res_rows       one thread per t <= M: a kept segment t writes its row at ks[t]; side t <= 2 P writes
+ *                        res_off[t] = ks[hs[side_off[t]]], the rows before the side's first segment
+ *
+ * The scan is a plain multi-level block scan of int32 counts in place, IF_B elements to a workgroup (ifr_scan_sums: a block's
+ * sum; ifr_scan_apply: a block's exclusive scan plus what precedes the block): the blocks' sums are scanned by the same two
+ * phases a level up until one workgroup holds a level, then the levels are applied top down.  Every launch is ordered behind
+ * the one before by the stream; no workgroup waits for another inside a launch.  M <= 2^30: four levels at most.  Integer sums:
+ * no result depends on launch shape or scheduling.
+ */
+#define IFR_MAX_LEVELS 5
+
+struct IfaceResArgs {
+    int64_t n_pair_atoms, n_sides; /* M, 2 P */
+    int n_res;
+    const int64_t *side_off;       /* [2 P + 1] */
+    const int *pair_atom;          /* [M] */
+    const int64_t *res_first;      /* [n_res + 1] */
+    const double *iso;             /* [n] the isolated areas of the input atoms (d_iso) */
+    const double *psasa;           /* [M] the pair batch's areas */
+    double min_buried;
+    int *atom_res;                 /* [M] */
+    int *hs;                       /* [M + 1] head flags, then their exclusive scan; hs[M] = K */
+    int *seg_first;                /* [M + 1] first pair-structure atom of every segment; seg_first[K] = M */
+    int *seg_res, *seg_atoms;      /* [M] */
+    double *seg_areas;             /* [3 M] iso, in_pair, buried */
+    int *ks;                       /* [M + 1] keep flags, then their exclusive scan; ks[M] = R */
+    int64_t *res_off;              /* [2 P + 1] */
+    int *res_index, *res_atoms;    /* [M] (R used) */
+    double *res_areas;             /* [3 M] (3 R used) */
+};
+
+/* the sizes of the scan's levels over n elements: cnt[0] = n, cnt[l + 1] = the blocks of level l; returns the top level, the
+   first that one workgroup holds (host and device agree on it: the launcher and the emulation both ask here) */
+inline int ifr_scan_levels(int64_t n, int64_t *cnt)
+{
+    int top = 0;
+    cnt[0] = n;
+    while (cnt[top] > IF_B) { cnt[top + 1] = (cnt[top] + IF_B - 1) / IF_B; ++top; }
+    return top;
+}
+/* the ints the levels above the first need: a level begins where the one below it ends */
+inline int64_t ifr_scan_scratch(int64_t n)
+{
+    int64_t cnt[IFR_MAX_LEVELS], s = 0;
+    const int top = ifr_scan_levels(n, cnt);
+    for (int l = 1; l <= top; ++l) s += cnt[l];
+    return s;
+}
+
+/* thread tid of block `block` over the n ints of `in`: the block's sum -> sums[block] (part: [IF_B] ints of LDS; a barrier
+   between the two phases) */
+SASA_D void ifr_scan_sums_phase0(const int *in, int64_t n, int *part, int64_t block, int tid)
+{
+    const int64_t i = block * IF_B + tid;
+    part[tid] = i < n ? in[i] : 0;
+}
+SASA_D void ifr_scan_sums_phase1(const int *part, int *sums, int64_t block, int tid)
+{
+    if (tid != 0) return;
+    int s = 0;
+    for (int t = 0; t < IF_B; ++t) s += part[t];
+    sums[block] = s;
+}
+/* ... the block's exclusive scan in place, plus base[block] (null: 0 - the top level, whose sum goes to *total); three phases */
+SASA_D void ifr_scan_apply_phase0(const int *a, int64_t n, int *part, int64_t block, int tid) { ifr_scan_sums_phase0(a, n, part, block, tid); }
+SASA_D void ifr_scan_apply_phase1(int *part, int *total, int tid)
+{
+    if (tid != 0) return;
+    int s = 0;
+    for (int t = 0; t < IF_B; ++t) { const int v = part[t]; part[t] = s; s += v; }
+    if (total) *total = s;
+}
+SASA_D void ifr_scan_apply_phase2(int *a, int64_t n, const int *part, const int *base, int64_t block, int tid)
+{
+    const int64_t i = block * IF_B + tid;
+    if (i < n) a[i] = (base ? base[block] : 0) + part[tid];
+}
+
+/* the residue of input atom i: the last r with res_first[r] <= i (res_first[0] = 0 <= i < res_first[n_res]) */
+SASA_D int ifr_residue(const IfaceResArgs &a, int64_t i)
+{
+    int lo = 0, hi = a.n_res - 1;
+    while (lo < hi) {
+        const int mid = (int)(((int64_t)lo + hi + 1) >> 1);
+        if (a.res_first[mid] <= i) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+SASA_D void iface_res_head(const IfaceResArgs &a, int64_t m)
+{
+    if (m >= a.n_pair_atoms) return;
+    const int r = ifr_residue(a, a.pair_atom[m]);
+    a.atom_res[m] = r;
+    int64_t lo = 0, hi = a.n_sides - 1;
+    while (lo < hi) { /* the last side that begins at or before m (iface_gather) */
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (a.side_off[mid] <= m) lo = mid;
+        else hi = mid - 1;
+    }
+    a.hs[m] = a.side_off[lo] == m || ifr_residue(a, a.pair_atom[m - 1]) != r ? 1 : 0;
+}
+SASA_D void iface_res_first(const IfaceResArgs &a, int64_t m)
+{
+    if (m >= a.n_pair_atoms) return;
+    const int k = a.hs[m], next = a.hs[m + 1];
+    if (next != k) a.seg_first[k] = (int)m;
+    if (m == a.n_pair_atoms - 1) a.seg_first[next] = (int)a.n_pair_atoms;
+}
+SASA_D void iface_res_segment(const IfaceResArgs &a, int64_t k)
+{
+    if (k >= a.n_pair_atoms) return;
+    if (k >= a.hs[a.n_pair_atoms]) { a.ks[k] = 0; return; }
+    const int b = a.seg_first[k], e = a.seg_first[k + 1];
+    double iso = 0, inp = 0;
+    for (int m = b; m < e; ++m) { iso += a.iso[a.pair_atom[m]]; inp += a.psasa[m]; }
+    const double buried = iso - inp;
+    a.seg_res[k] = a.atom_res[b];
+    a.seg_atoms[k] = e - b;
+    a.seg_areas[3 * k] = iso; a.seg_areas[3 * k + 1] = inp; a.seg_areas[3 * k + 2] = buried;
+    a.ks[k] = buried > a.min_buried ? 1 : 0;
+}
+SASA_D void iface_res_rows(const IfaceResArgs &a, int64_t t)
+{
+    if (t > a.n_pair_atoms) return;
+    if (t <= a.n_sides) a.res_off[t] = a.ks[a.hs[a.side_off[t]]];
+    if (t >= a.hs[a.n_pair_atoms]) return;
+    const int j = a.ks[t];
+    if (a.ks[t + 1] == j) return;
+    a.res_index[j] = a.seg_res[t];
+    a.res_atoms[j] = a.seg_atoms[t];
+    a.res_areas[3 * (int64_t)j] = a.seg_areas[3 * t]; a.res_areas[3 * (int64_t)j + 1] = a.seg_areas[3 * t + 1];
+    a.res_areas[3 * (int64_t)j + 2] = a.seg_areas[3 * t + 2];
+}
+
 } /* namespace sasa */
 
 #endif

@@ -1091,8 +1091,8 @@ int freesasa_gpu_calc_groups_periodic_triclinic(const double *xyz, const double 
    Refused, with a message that names the structure and the number: more than 4096 groups in one structure (8.4e6 pairs to
      test), more than 2^27 pairs to test in a call, n_atoms + the groups' atoms + M > 2^30; a bad group id or n_groups as by
      freesasa_gpu_groups_dev, with its message.
-   Not offered: file sweeps and trajectory drivers, periodic images, per-residue tables, pair batches cut into several engine
-     runs, interfaces of more than two groups.
+   Not offered: file sweeps and trajectory drivers, periodic images, pair batches cut into several engine runs, interfaces of
+     more than two groups.  (Per-residue tables: freesasa_gpu_interface_residues_dev below.)
 
    freesasa_gpu_interface_pairs_dev: the screen alone - the chain-group pipeline, then boxes, candidates and contacts - one
      stream synchronization more than freesasa_gpu_groups_dev (the flags come back to the host).  d_sasa, d_iso, d_totals,
@@ -1128,6 +1128,71 @@ int freesasa_gpu_calc_interfaces(const double *xyz, const double *radii, const i
                                  int32_t *pair_struct_out, int32_t *pair_groups_out, double *pair_areas_out,
                                  int64_t *side_offsets_out, int32_t *pair_atom_out, double *pair_buried_out,
                                  int device, char *err_out, int err_len);
+
+/* PER-RESIDUE INTERFACE TABLES: which residues make up every interface above, and how much each loses - the interface-residue
+   table of an assembly analysis - made on the device behind the interface pipeline and delivered compact: only the residues
+   that lose area get a row, so the table's size is decided by areas and known to the device alone (csrc/iface_kernels.h,
+   IfaceResArgs; tests/interface_residues_ref.py restates the definitions in numpy).
+   Input: that of freesasa_gpu_interfaces_dev, and
+     res_first [n_res + 1]  a HOST int64 array: the residue boundaries over the input batch, as freesasa_ingest_batch.res_first
+                            has them; residue r owns the input atoms res_first[r] .. res_first[r + 1] - 1
+     min_buried             a double, see Rows
+   Everything of the interface definition stays: the pair table, the sides' order, side_offsets, pair_atom, pair_buried, and
+   their bytes.
+   Segments.  Within side q of the pair table (q = 2p: group g, q = 2p + 1: group h) the pair-structure atoms are in input
+     order.  A SEGMENT is a maximal run of consecutive atoms of one side whose input atoms lie in the same residue.  The atoms of
+     a residue are contiguous in the input, so a segment is all atoms of that residue that belong to the side's group.  Group
+     ids are arbitrary: a residue split over several groups gives one segment in every side it occurs in.  Atoms in no group
+     occur in no segment; empty residues (res_first[r] == res_first[r + 1]) occur in none.
+   Sums per segment, each in strict atom order, one addition at a time from 0 (as freesasa_gpu_segment_sums_dev and
+     freesasa_gpu_residue_areas_dev sum), fp64, every operation rounded on its own:
+       iso_res      the sum of d_iso[pair_atom[m]] over the segment's atoms m
+       in_pair_res  the sum of those atoms' areas in the pair structure (what in_pair_* sums over the whole side)
+       buried_res   = iso_res - in_pair_res, the convention of the pair row's buried_* = iso_* - in_pair_*
+   Rows.  A segment gets a row iff buried_res > min_buried (strict, fp64).  The R rows are in segment order: pair-major, side g
+     before side h, residues ascending.  Row k: res_index[k] (int32) the batch-wide residue r, res_atoms[k] (int32) the atoms
+     of the segment, res_areas[3k ..] = iso_res, in_pair_res, buried_res.  res_offsets [2P + 1] (int64): the row range of
+     every side, in the order of side_offsets; a side with no rows has an empty range; res_offsets[2P] = R.
+   min_buried.  With Shrake-Rupley a residue none of whose atoms loses a test point has buried_res == 0 exactly (its atoms'
+     areas in the pair structure are those of the isolated group bit for bit), so min_buried = 0 gives exactly the residues that
+     lose a test point.  With Lee-Richards nobody has measured whether an atom without a neighbour across the interface has the
+     same area to the last bit in the pair structure as in its isolated group: min_buried is the caller's instrument against
+     rows made of such last bits.  No tolerance is built in.
+   Capacities.  As above, with res_capacity in rows (res_index, res_atoms: 1, res_areas: 3 entries a row; res_offsets goes by
+     pair_capacity: 2 a row and one more).  *n_pairs_out, *n_pair_atoms_out and *n_res_rows_out are set first, then the three
+     capacities are held against them in this order; a res_capacity below R fails with
+     "res_capacity %lld is too small: the interfaces have %lld residue rows" before any of the caller's pair, atom or residue
+     arrays is written.  R <= M: arrays of M rows always suffice.
+   Refused with a message before a device is touched: everything the interface entries refuse, with their messages; res_first
+     NULL or n_res <= 0; res_first[0] != 0, a decreasing entry, res_first[n_res] != offsets[n_structs]; a residue that spans
+     a structure boundary (the message names residue and structures); min_buried negative, NaN or infinite; res_capacity < 0.
+   One stream synchronization more than freesasa_gpu_interfaces_dev (R comes back to the host before delivery).
+   Not offered: class splits (polar / apolar / main chain) of the buried area per residue, relative buried areas, interfaces
+     in the file sweep and the trajectory drivers, interfaces among periodic images, a per-atom contact criterion by distance.
+
+   freesasa_gpu_interface_residues_dev: d_res_areas is required, d_res_offsets, d_res_index, d_res_atoms may be NULL; the rest
+     as freesasa_gpu_interfaces_dev.
+   freesasa_gpu_calc_interface_residues: the same on host arrays, as freesasa_gpu_calc_interfaces.
+   Both: 0, or -1 with the context's error text / err_out; the context stays usable. */
+int freesasa_gpu_interface_residues_dev(freesasa_gpu_ctx *ctx, int alg, const double *d_xyz, const double *d_radii,
+                                        const int64_t *offsets, int n_structs, const int32_t *d_group, const int32_t *n_groups,
+                                        const int64_t *res_first, int n_res, double probe_radius, int resolution, double min_buried,
+                                        double *d_sasa, double *d_iso, double *d_totals, double *d_group_totals,
+                                        long long pair_capacity, long long atom_capacity, long long res_capacity,
+                                        long long *n_pairs_out, long long *n_pair_atoms_out, long long *n_res_rows_out,
+                                        int32_t *d_pair_struct, int32_t *d_pair_groups, double *d_pair_areas,
+                                        int64_t *d_side_offsets, int32_t *d_pair_atom, double *d_pair_buried,
+                                        int64_t *d_res_offsets, int32_t *d_res_index, int32_t *d_res_atoms, double *d_res_areas);
+int freesasa_gpu_calc_interface_residues(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
+                                         const int32_t *group, const int32_t *n_groups, const int64_t *res_first, int n_res,
+                                         int alg, double probe_radius, int resolution, double min_buried,
+                                         double *sasa_out, double *iso_out, double *totals_out, double *group_totals_out,
+                                         long long pair_capacity, long long atom_capacity, long long res_capacity,
+                                         long long *n_pairs_out, long long *n_pair_atoms_out, long long *n_res_rows_out,
+                                         int32_t *pair_struct_out, int32_t *pair_groups_out, double *pair_areas_out,
+                                         int64_t *side_offsets_out, int32_t *pair_atom_out, double *pair_buried_out,
+                                         int64_t *res_offsets_out, int32_t *res_index_out, int32_t *res_atoms_out,
+                                         double *res_areas_out, int device, char *err_out, int err_len);
 
 /* MOLECULAR VOLUME: the volume enclosed by the solvent-accessible surface of every structure, made of the Shrake-Rupley test
    points by the divergence theorem - what `gmx sasa -tv` prints per frame, in the same formulation:
