@@ -27,7 +27,7 @@ $(LIBDIR)/gpu_kernels.o: $(CSRC)/gpu_kernels.hip $(ENGINE_HDRS)
 $(LIBDIR)/gpu_%.o: $(CSRC)/gpu_%.hip $(ENGINE_HDRS)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-GPU_OBJS = $(LIBDIR)/gpu_kernels.o $(LIBDIR)/gpu_engine.o $(LIBDIR)/gpu_ops.o $(LIBDIR)/gpu_hostbatch.o $(LIBDIR)/gpu_drivers.o $(LIBDIR)/gpu_sweep.o $(LIBDIR)/gpu_parse.o $(LIBDIR)/gpu_groups.o $(LIBDIR)/gpu_periodic.o $(LIBDIR)/gpu_volume.o $(LIBDIR)/gpu_dots.o $(LIBDIR)/gpu_interfaces.o
+GPU_OBJS = $(LIBDIR)/gpu_kernels.o $(LIBDIR)/gpu_engine.o $(LIBDIR)/gpu_ops.o $(LIBDIR)/gpu_hostbatch.o $(LIBDIR)/gpu_drivers.o $(LIBDIR)/gpu_frames.o $(LIBDIR)/gpu_sweep.o $(LIBDIR)/gpu_parse.o $(LIBDIR)/gpu_groups.o $(LIBDIR)/gpu_periodic.o $(LIBDIR)/gpu_volume.o $(LIBDIR)/gpu_dots.o $(LIBDIR)/gpu_interfaces.o
 
 $(LIBDIR)/seam.o: $(CSRC)/seam.c include/freesasa_amd.h include/freesasa_gpu.h
 	@mkdir -p $(LIBDIR)

@@ -1,6 +1,6 @@
 /*
  * dcd.c — the header of a DCD trajectory (CHARMM, NAMD, OpenMM, LAMMPS), read on the host for the trajectory file drivers
- * (include/freesasa_gpu.h, freesasa_gpu_dcd_info_read; gpu_drivers.hip).  A DCD is uncompressed fp32 and every frame has
+ * (include/freesasa_gpu.h, freesasa_gpu_dcd_info_read; gpu_frames.hip).  A DCD is uncompressed fp32 and every frame has
  * the same byte stride, so all the drivers need from it is WHERE a frame's x, y and z planes lie: the planes themselves go to
  * the device as they are in the file (traj_kernels.h, traj_gather_dcd).
  *

@@ -11,6 +11,9 @@
  *                      the pipelined form, the cache sweep
  *   gpu_drivers.hip    trajectory drivers (one device or a list of devices); what the drivers share (device lists, the
  *                      host budget, DoneList)
+ *   gpu_frames.hip     the trajectory drivers' frame source: raw, DCD, AMBER NetCDF, GROMACS XTC and TRR input - open and its
+ *                      refusals, the layout of a shard, read + check on the host, the kernels that make compact fp64 frames;
+ *                      the XTC decode's test hook
  *   gpu_sweep.hip      the file sweep (host or device parser, done-list, per-residue table, selections) and the device parser's entries
  *   gpu_parse.hip      the device-side PDB / mmCIF parser: its kernels and their host driver (gpu_parse.h)
  *   gpu_groups.hip     chain groups: a batch and every group of it cut out as a structure of its own, in one batch; the
@@ -575,6 +578,59 @@ private:
 
 bool host_pinned(const void *p); /* page-locked already (hipHostMalloc / hipHostRegister, e.g. a pinned tensor)? */
 int ensure_pinned(freesasa_gpu_ctx *c, void **p, size_t *cap, size_t bytes); /* grow a context's page-locked staging buffer */
+
+/* The FRAME SOURCE of a trajectory run (gpu_frames.hip): where its frames come from, and everything that depends on it.  The
+   driver opens it (a file: open, every refusal of the frames_f32 word and of the file's header; memory: open_memory), asks for
+   the frames of the file and the two words of the done-list's first line, plans the run's shards, and per shard calls read and
+   to_frames.  Nothing outside gpu_frames.hip looks at `kind` or at what lies below it. */
+struct FrameContainer;
+struct FrameSource {
+    enum Kind { RAW_F64, RAW_F32, DCD, NETCDF, XTC, TRR };
+    Kind kind = RAW_F64;
+    const double *mem = nullptr; /* raw fp64 frames in host memory ... */
+    Fd file;                     /* ... or the frame file: the driver opens it once open() has let the run through */
+    bool pbc = false, tri = false; /* every frame among the images of its cell (gpu_periodic.hip); the cell decoded as a triclinic one */
+
+    /* 0, or -1 with the message: before a device is touched or an output file opened */
+    int open(const char *path, int frames_f32, long long header_bytes, long long frame_atoms, char *err_out, int err_len);
+    void open_memory(const double *frames, size_t frame_atoms);
+    long long frames_in_file(long long file_bytes) const;
+    /* the done-list's first line: the bits of its f32= word that say what comes IN, and its header_bytes= word (the byte of frame 0) */
+    int head_f32() const;
+    long long head_bytes() const { return first; }
+
+    /* once the run's shards are known (n_atoms: of a frame as the engine sees it; with_index: a topology's gather picks them
+       from the fa atoms that come in) */
+    void plan(size_t n_atoms, bool with_index, long long n_frames, int frames_per_batch, const double *radii, double probe);
+    size_t shard_bytes(long long f0, long long nf) const; /* of the frames [f0, f0 + nf) as they come in */
+    size_t up_bytes(size_t in_bytes, size_t nf) const;    /* what goes up in the shard's one copy */
+    size_t xyz_bytes() const;                             /* what c->g_xyz holds of a full shard (0: nothing) ... */
+    size_t widen_bytes() const { return (kind == RAW_F32 || kind == XTC) && !gather ? 12 * n * FB : 0; } /* ... and the head of c->h_counts: kl_widen_f32's input */
+    size_t cell_doubles() const { return tri ? PBC_TRI_CELL : 3; } /* per frame of a periodic run: edges, or the cell's six numbers and three widths */
+    const double *host_cells(const freesasa_gpu_ctx *c, size_t in_bytes) const; /* a periodic shard's cells [nf][cell_doubles] after read ... */
+    const double *dev_cells(const freesasa_gpu_ctx *c, size_t in_bytes) const;  /* ... and after to_frames */
+
+    /* host: the shard's bytes in page-locked memory at *src - the caller's own, or the lane's staging filled from memory or
+       from the file -, a container's records checked against its header or index, a periodic run's cells decoded and checked */
+    int read(freesasa_gpu_ctx *c, long long f0, int nf, size_t in_bytes, const void **src) const;
+    /* device: the one copy up, then compact fp64 frames in c->h_xyz, on the context's stream (ta: the topology's gather).  An
+       XTC shard waits for the status of its decode; nothing else is waited for. */
+    int to_frames(freesasa_gpu_ctx *c, const sasa::TrajArgs &ta, long long f0, int nf, size_t in_bytes, const void *src) const;
+
+    /* (gpu_frames.hip's own) */
+    const FrameContainer *con = nullptr; /* the container's row of open's table; NULL: raw frames */
+    size_t fa = 0, stride = 0;           /* atoms of a frame as it comes in; bytes from one frame to the next (raw, DCD, NetCDF) */
+    long long first = 0;                 /* ... and the byte of frame 0 */
+    freesasa_gpu_dcd_info dcd = {};      /* where a DCD frame's planes are (dcd.c) */
+    freesasa_gpu_nc_info nc = {};        /* where a NetCDF record's coordinates and cell are (netcdf.c) */
+    int real_bytes = 0;                  /* of a TRR file: 4 or 8 (trr.c) */
+    std::vector<int64_t> off;            /* XTC, TRR: the byte of every frame [n_frames + 1], by which the shards are cut */
+    bool indexed() const { return kind == XTC || kind == TRR; }
+    size_t n = 0, FB = 0, max_bytes = 0; /* (plan) atoms the engine sees, frames of a full shard, the bytes of the largest shard */
+    bool gather = false, mem_pinned = false;
+    double cut = 0;                      /* every edge (width) of a periodic frame's cell must reach c = 2 (max radius + probe) */
+    int read_header(const char *path, int *file_atoms, bool *has_cell, char *err_out, int err_len);
+};
 
 /* ------------------------------------------------------------------ host batches: the chunk path (gpu_hostbatch.hip)
  * freesasa_gpu_calc_batch, _calc_batch_devices, _calc_batch_pipelined and the cache sweep are ONE path: a BatchCall is what

@@ -1,8 +1,8 @@
 /*
  * gpu_drivers.hip — the drivers for BASELINE configs[3] and configs[4] (include/freesasa_gpu.h): the structure sweep
  * over PDB / mmCIF files (gpu_sweep.hip), the same sweep from a binary cache (gpu_hostbatch.hip: chunks of the host-batch
- * path whose source is the file) and the trajectory drivers (here, with what all three share: engine_internal.h) — each
- * over ONE device or a LIST of devices of the node.  Host code; kernels in gpu_kernels.hip.
+ * path whose source is the file) and the trajectory drivers (here, with what all three share: engine_internal.h; where
+ * their frames come from: gpu_frames.hip) — each over ONE device or a LIST of devices of the node.  Host code; kernels in gpu_kernels.hip.
  *
  * What replaces what: the reference reads one file per run of its CLI (src/main.cc:763-779) and spreads ONE structure
  * over <= 16 pthreads (src/sasa_lr.c:219-253).  Here the unit of parallel work is a batch of whole structures (a
@@ -123,9 +123,8 @@ namespace {
 /* Frames of ONE system (same atoms, same radii) are independent structures: a SHARD is a run of frames_per_batch
  * frames that goes through the engine as one batch.  A few host lanes PER DEVICE take shards from a shared counter; a
  * lane owns a pooled context (stream, workspace, page-locked staging) of its device and does, for its shard,
- *     read (memory or frame file) -> host-to-device -> [fp32 frames widened to fp64 on the device: an INPUT format,
- *     the arithmetic stays fp64; the planar fp32 records of a DCD file, or the big-endian fp32 records of an AMBER NetCDF
- *     file, made into compact fp64 frames by one kernel]
+ *     read (memory or frame file) -> host-to-device -> [whatever came in made into compact fp64 frames on the device: the
+ *     FRAME SOURCE's two steps (gpu_frames.hip), the only code that knows the format of the input; the arithmetic is fp64]
  *     -> cell sort + tile kernels -> device-to-host -> write (memory or files)
  * while the other lanes are in another stage.  The radii live once per device context (shared by every frame of
  * a batch).  With a done-list file every finished shard is recorded after its results are on disk; a later call
@@ -155,22 +154,7 @@ struct TrajOut {
     size_t deliver() const { return wanted() ? per_frame : 0; } /* values per frame that go down and out (0: computed at most) */
 };
 struct TrajIO {
-    const double *mem_in = nullptr; /* frames in host memory (fp64) ... */
-    Fd in;                          /* ... or in a file of raw frames */
-    long long in_header = 0;        /* (a DCD file: the byte of frame 0) */
-    int in_f32 = 0;
-    bool in_dcd = false;            /* the file is a DCD trajectory: its frames go up as they lie in the file ... */
-    freesasa_gpu_dcd_info dcd = {}; /* ... and this says where their planes are (dcd.c) */
-    bool in_nc = false;             /* the file is an AMBER NetCDF trajectory: its records go up as they lie in the file ... */
-    freesasa_gpu_nc_info nc = {};   /* ... and this says where their coordinates and their cell are (netcdf.c) */
-    bool in_xtc = false;            /* the file is a GROMACS XTC trajectory: compressed frames of unequal length, decoded on the device ... */
-    freesasa_gpu_xtc_info xtc = {}; /* ... what the pass over its headers found (xtc.c) ... */
-    std::vector<int64_t> xtc_off;   /* ... and its index: the byte of every frame [n_frames + 1], by which the shards are cut */
-    bool in_trr = false;            /* the file is a GROMACS TRR trajectory: uncompressed records of unequal length, fp32 or fp64 ... */
-    freesasa_gpu_trr_info trr = {}; /* ... what the pass over its headers found (trr.c) ... */
-    std::vector<int64_t> trr_off;   /* ... and its index: the byte of every record WITH coordinates [n_frames + 1] */
-    bool pbc = false;               /* FREESASA_GPU_FRAMES_PBC: every frame among the images its cell record implies (gpu_periodic.hip) */
-    bool tri = false;               /* ... FREESASA_GPU_FRAMES_TRICLINIC beside it: the record decoded as a triclinic cell */
+    FrameSource src; /* the frames: host memory or a frame file of any format (engine_internal.h, gpu_frames.hip) */
     /* per frame: total [1], per-atom areas [n]; runs with a topology: class sums [3], residue areas [6 R], selection areas [S];
        with chain groups: every atom's area in its isolated group [n], and isolated, complex, buried per group [3 G]; the volume
        entries: the frame's volume [1] (gpu_volume.hip; it has no run statistics: no bit of the statistics word); the mask entries:
@@ -409,45 +393,8 @@ struct TrajRun {
     const bool groups = topo && topo->group;
     const size_t G = groups ? (size_t)topo->n_groups : 0, n_iso = groups ? (size_t)topo->n_iso : 0, nc = n + n_iso; /* nc: combined atoms per frame */
     const long long n_shards = (s.n_frames + s.frames_per_batch - 1) / s.frames_per_batch;
-    /* a topology: frames of fa atoms come in (with an index the gather makes the engine's n of them); esz bytes per atom */
-    const bool gather = topo && topo->index;
-    /* (an XTC file's frames are raw fp32 frames once xtc_unpack has written them: from there on the run is a raw fp32 run) */
-    const bool xtc = io.in_xtc, f32 = io.in_f32 || xtc;
-    const size_t fa = topo ? (size_t)topo->frame_atoms : n, esz = f32 ? 12 : 24;
-    const size_t widen_bytes = f32 && !gather ? 12 * n * FB : 0; /* (fp32 frames without an index: kl_widen_f32's input) */
-    /* bytes from one input frame to the next: raw frames, or a DCD / NetCDF file's stride (kl_traj_gather_dcd / _nc then does
-       the gather's and the widening's work, with or without an index) */
-    const bool dcd = io.in_dcd, netcdf = io.in_nc, trr = io.in_trr, container = dcd || netcdf || trr;
-    const size_t stride = dcd ? (size_t)io.dcd.frame_bytes : netcdf ? (size_t)io.nc.record_bytes : esz * fa;
-    /* (an XTC and a TRR file have no stride: their shards are cut by the index of the file) */
-    const bool indexed = xtc || trr;
-    const std::vector<int64_t> &idx = trr ? io.trr_off : io.xtc_off;
-    /* periodic images: a shard's [nf][3] cell edges ride behind its bytes (at the next multiple of 8); every edge must reach
-       the system's c = 2 (max radius + probe) */
-    const bool pbc = io.pbc;
-    const double pbc_cut = pbc ? periodic_cutoff(s.radii, s.n_atoms, s.probe) : 0;
-    static size_t cells_at(size_t in_bytes) { return (in_bytes + 7) & ~(size_t)7; }
-    /* (a triclinic run: per frame the six numbers of the cell and its three widths) */
-    const size_t cell_bytes = io.tri ? 8 * PBC_TRI_CELL : 24;
-    /* An XTC shard on the device (c->g_xyz), every part at a multiple of 8: its bytes | its cells (periodic runs) | one descriptor
-       per frame - up to here the one copy from the host - | group count and status per frame | the group records (at a multiple
-       of 16) | with an index the fp32 frames xtc_unpack writes (without: kl_widen_f32's input, c->h_counts) */
-    size_t xtc_desc_at(size_t in_bytes, size_t nf) const { return cells_at(in_bytes) + (pbc ? cell_bytes * nf : 0); }
-    size_t xtc_count_at(size_t in_bytes, size_t nf) const { return xtc_desc_at(in_bytes, nf) + sizeof(freesasa_gpu_xtc_frame) * nf; }
-    size_t xtc_rec_at(size_t in_bytes, size_t nf) const { return (xtc_count_at(in_bytes, nf) + 8 * nf + 15) & ~(size_t)15; }
-    size_t xtc_f32_at(size_t in_bytes, size_t nf) const { return xtc_rec_at(in_bytes, nf) + sizeof(sasa::XtcRec) * fa * nf; }
-    /* A TRR shard on the device (c->g_xyz): its bytes | its cells (periodic runs) | the byte of every frame's x[0] within the shard,
-       one int64 per frame - all of it the one copy from the host */
-    size_t trr_xoff_at(size_t in_bytes, size_t nf) const { return xtc_desc_at(in_bytes, nf); }
-    size_t idx_max_bytes = 0; /* the bytes of the index's largest shard */
-    size_t shard_bytes(long long f0, long long nf) const { return indexed ? (size_t)(idx[(size_t)(f0 + nf)] - idx[(size_t)f0]) : stride * (size_t)nf; }
-    /* what goes up in a shard's one copy */
-    size_t up_bytes(size_t in_bytes, size_t nf) const
-    {
-        return xtc ? xtc_count_at(in_bytes, nf) : trr ? trr_xoff_at(in_bytes, nf) + 8 * nf : pbc ? cells_at(in_bytes) + cell_bytes * nf : in_bytes;
-    }
+    FrameSource &src = io.src; /* (planned below: what its shards are, a topology's index, the cutoff of periodic images) */
     /* the caller's arrays are page-locked: no staging */
-    const bool in_pinned = io.mem_in && host_pinned(io.mem_in);
     const bool direct_out = io.out[OUT_TOTALS].mem && host_pinned(io.out[OUT_TOTALS].mem) && (!io.out[OUT_SASA].mem || host_pinned(io.out[OUT_SASA].mem)) &&
                             (!io.out[OUT_ISO].mem || host_pinned(io.out[OUT_ISO].mem)) && (!io.out[OUT_MASK].mem || host_pinned(io.out[OUT_MASK].mem));
     const size_t S = topo && topo->sel && (io.out[OUT_SEL].wanted() || io.sel_atoms || (io.stats & FREESASA_GPU_STATS_SELECTIONS)) ? (size_t)topo->n_sel : 0; /* selections computed */
@@ -508,10 +455,7 @@ struct TrajRun {
             if (k >= OUT_CLS) x0[k + 1] = x0[k] + io.out[k].per_frame;
         }
         xw = x0[N_OUT] + S;
-        for (long long k = 0; indexed && k < n_shards; ++k) {
-            const long long f0 = k * s.frames_per_batch, nf = s.n_frames - f0 < s.frames_per_batch ? s.n_frames - f0 : s.frames_per_batch;
-            if (shard_bytes(f0, nf) > idx_max_bytes) idx_max_bytes = shard_bytes(f0, nf);
-        }
+        src.plan(n, topo && topo->index, s.n_frames, s.frames_per_batch, s.radii, s.probe);
     }
 };
 /* a lane: its pooled context and what it has put there once */
@@ -543,10 +487,8 @@ int shard_size(TrajRun &T, TrajLane &L)
     /* (with chain groups nc = n + n_iso atoms and 1 + G structures per frame, and radii per atom: the isolated structures are not n atoms long) */
     if (ensure(c, c->h_xyz, 24 * nc * FB) || ensure(c, c->h_radii, T.groups ? 8 * nc * FB : 8 * n) || ensure(c, c->h_sasa, 8 * nc * FB) ||
         ensure(c, c->h_totals, 8 * (1 + T.G) * FB) ||
-        (T.widen_bytes + narrow_bytes && ensure(c, c->h_counts, T.widen_bytes + narrow_bytes)) ||
-        ((T.gather || T.container || T.xtc) && ensure(c, c->g_xyz, T.xtc ? T.xtc_f32_at(T.idx_max_bytes, FB) + (T.gather ? 12 * T.fa * FB : 0)
-                                                                        : T.trr ? T.up_bytes(T.idx_max_bytes, FB)
-                                                                        : T.pbc ? TrajRun::cells_at(T.stride * FB) + T.cell_bytes * FB : T.stride * FB)) || (T.xw + T.sW && ensure(c, c->h_gtot, 8 * (T.xw * FB + 4 * T.sW))) ||
+        (T.src.widen_bytes() + narrow_bytes && ensure(c, c->h_counts, T.src.widen_bytes() + narrow_bytes)) ||
+        (T.src.xyz_bytes() && ensure(c, c->g_xyz, T.src.xyz_bytes())) || (T.xw + T.sW && ensure(c, c->h_gtot, 8 * (T.xw * FB + 4 * T.sW))) ||
         (T.groups && (ensure(c, c->g_gath, 8 * nc * FB) || ensure(c, c->g_tot2, 8 * (1 + T.G) * FB))) || (iso && ensure(c, c->h_iso, 8 * n * FB)) ||
         (T.io.out[OUT_MASK].per_frame && ensure(c, c->dt_masks, 4 * SR_CAP_WORDS * n * FB)))
         return -1;
@@ -556,342 +498,19 @@ int shard_size(TrajRun &T, TrajLane &L)
     return 0;
 }
 
-/* every record marker of the DCD frames [0, nf) at `bytes`: 6 per frame, 2 more with a cell record, 2 more with a 4th dimension.
-   Returns the first frame with a wrong one, or -1. */
-long long dcd_damaged_frame(const freesasa_gpu_dcd_info &d, const char *bytes, long long nf)
-{
-    auto word = [&](uint32_t v) { return d.big_endian ? __builtin_bswap32(v) : v; };
-    const uint32_t cell = word(48), plane = word(4u * (uint32_t)d.n_atoms);
-    for (long long f = 0; f < nf; ++f) {
-        const char *p = bytes + f * d.frame_bytes;
-        uint32_t w[2];
-        if (d.has_cell) {
-            memcpy(&w[0], p, 4); memcpy(&w[1], p + 52, 4);
-            if (w[0] != cell || w[1] != cell) return f;
-            p += 56;
-        }
-        for (int k = 0; k < 3 + d.has_4d; ++k, p += d.plane_bytes) {
-            memcpy(&w[0], p, 4); memcpy(&w[1], p + d.plane_bytes - 4, 4);
-            if (w[0] != plane || w[1] != plane) return f;
-        }
-    }
-    return -1;
-}
-
-/* the six doubles of frame f's cell record, in the host's byte order */
-static void dcd_cell_record(const freesasa_gpu_dcd_info &d, const char *bytes, long long f, double *v)
-{
-    for (int k = 0; k < 6; ++k) {
-        uint64_t w;
-        memcpy(&w, bytes + f * d.frame_bytes + 4 + 8 * k, 8);
-        if (d.big_endian) w = __builtin_bswap64(w);
-        memcpy(&v[k], &w, 8);
-    }
-}
-
-/* The cell records of the DCD frames [0, nf) at `bytes` (their markers are checked): 6 doubles in the file's byte order, CHARMM's
-   A, gamma, B, beta, alpha, C - the angles as cosines or as degrees.  The edges into edges[nf][3]; returns -1, or the first frame
-   whose cell periodic images are not offered for, the reason in why: an angle that is not a right one, an edge that is not
-   finite or shorter than cut. */
-long long dcd_cells(const freesasa_gpu_dcd_info &d, const char *bytes, long long nf, double cut, double *edges, char *why, size_t why_len)
-{
-    for (long long f = 0; f < nf; ++f) {
-        double v[6];
-        dcd_cell_record(d, bytes, f, v);
-        const int ang[3] = {1, 3, 4}, edge[3] = {0, 2, 5};
-        for (int k = 0; k < 3; ++k)
-            if (!(fabs(v[ang[k]]) <= 1e-6 || fabs(v[ang[k]] - 90.0) <= 1e-4)) {
-                snprintf(why, why_len, "its cell is not orthorhombic (angle field %.9g): triclinic cells are not offered", v[ang[k]]);
-                return f;
-            }
-        for (int k = 0; k < 3; ++k) {
-            const double L = v[edge[k]];
-            if (!isfinite(L)) { snprintf(why, why_len, "edge %c of its cell is not finite", "xyz"[k]); return f; }
-            if (!(L >= cut)) {
-                snprintf(why, why_len, "edge %c of its cell is %.9g, shorter than c = 2 (max radius + probe) = %.9g", "xyz"[k], L, cut);
-                return f;
-            }
-            edges[3 * f + k] = L;
-        }
-    }
-    return -1;
-}
-
-/* A decoded cell h[6] of a frame: its shape, and its three widths - made here, into h[6 .. 8] - against cut.  edge: A, B, C as the
-   file holds them, for the reason.  false, or true with the reason in why. */
-static bool tri_cell_bad(double *h, const double edge[3], double cut, char *why, size_t why_len)
-{
-    const int shape = periodic_cell6_bad(h);
-    if (shape) { /* (an edge that is not positive: everything else the decoder has refused) */
-        snprintf(why, why_len, "edge %c of its cell is %.9g: not positive", shape == 1 ? 'A' : shape == 3 ? 'B' : 'C', edge[shape == 1 ? 0 : shape == 3 ? 1 : 2]);
-        return true;
-    }
-    (void)freesasa_gpu_cell_widths(h, h + 6);
-    const int bad = periodic_widths_bad(h + 6, cut);
-    if (bad) snprintf(why, why_len, "width %c of its cell is %.9g, smaller than c = 2 (max radius + probe) = %.9g", "abc"[bad - 1], h[6 + bad - 1], cut);
-    return bad != 0;
-}
-
-/* The same records decoded as triclinic cells (freesasa_gpu_cell_from_dcd): cell9[nf][9] receives the six numbers of every
-   frame's cell and, behind them, its three widths; returns -1, or the first frame whose record spans no cell or whose cell has
-   a width below cut, the reason in why. */
-long long dcd_cells_tri(const freesasa_gpu_dcd_info &d, const char *bytes, long long nf, double cut, double *cell9, char *why, size_t why_len)
-{
-    for (long long f = 0; f < nf; ++f) {
-        double v[6], *h = cell9 + PBC_TRI_CELL * f;
-        dcd_cell_record(d, bytes, f, v);
-        const double edge[3] = {v[0], v[2], v[5]};
-        if (freesasa_gpu_cell_from_dcd(v, h, why, (int)why_len) || tri_cell_bad(h, edge, cut, why, why_len)) return f;
-    }
-    return -1;
-}
-
-/* The cells of the AMBER NetCDF frames [0, nf) at `bytes`: three edge lengths and alpha, beta, gamma, big-endian doubles, the
-   angles ALWAYS degrees (a 0 is not a right angle here).  Orthorhombic runs: the edges into cells[nf][3]; triclinic runs:
-   cells[nf][9] as dcd_cells_tri fills it, through freesasa_gpu_cell_from_lengths_angles and tri_cell_bad.  Returns -1, or the first frame whose
-   cell periodic images are not offered for, the reason in why. */
-long long nc_cells(const freesasa_gpu_nc_info &d, const char *bytes, long long nf, bool tri, double cut, double *cells, char *why, size_t why_len)
-{
-    for (long long f = 0; f < nf; ++f) {
-        double len[3], deg[3];
-        freesasa_gpu_nc_cell_record(&d, bytes, f, len, deg);
-        if (!tri) {
-            for (int k = 0; k < 3; ++k)
-                if (!(fabs(deg[k] - 90.0) <= 1e-4)) {
-                    snprintf(why, why_len, "its cell is not orthorhombic (angle %s is %.9g degrees): triclinic cells need bit 4", k == 0 ? "alpha" : k == 1 ? "beta" : "gamma", deg[k]);
-                    return f;
-                }
-            for (int k = 0; k < 3; ++k) {
-                if (!isfinite(len[k])) { snprintf(why, why_len, "edge %c of its cell is not finite", "xyz"[k]); return f; }
-                if (!(len[k] >= cut)) {
-                    snprintf(why, why_len, "edge %c of its cell is %.9g, shorter than c = 2 (max radius + probe) = %.9g", "xyz"[k], len[k], cut);
-                    return f;
-                }
-                cells[3 * f + k] = len[k];
-            }
-            continue;
-        }
-        double *h = cells + PBC_TRI_CELL * f;
-        if (freesasa_gpu_cell_from_lengths_angles(len, deg, h, why, (int)why_len) || tri_cell_bad(h, len, cut, why, why_len)) return f;
-    }
-    return -1;
-}
-
-/* The descriptors of the XTC frames [f0, f0 + nf) at `bytes` (xtc.c: every header checked again as it lies in the staging - the
-   device trusts the descriptors for its bounds - and against the index: a frame must be as long as the index pass found it).
-   Returns -1, or the first frame that fails, the reason in why. */
-long long xtc_descriptors(const TrajIO &io, const char *bytes, long long f0, long long nf, int frame_atoms, freesasa_gpu_xtc_frame *desc, char *why, size_t why_len)
-{
-    const int64_t *off = io.xtc_off.data() + f0;
-    for (long long f = 0; f < nf; ++f) {
-        long long frame_bytes = 0;
-        const long long at = off[f] - off[0], len = off[f + 1] - off[f];
-        if (freesasa_gpu_xtc_frame_desc(bytes + at, len, frame_atoms, at + FREESASA_GPU_XTC_HEADER, &desc[f], &frame_bytes, why, (int)why_len)) return f;
-        if (frame_bytes != len) { snprintf(why, why_len, "its header is not the one the index was made from"); return f; }
-    }
-    return -1;
-}
-
-/* The cell of ONE frame from its box, for XTC and TRR frames alike: nine numbers in nm as doubles - each what the file holds,
-   widened -, GROMACS' lower triangle - rows a = (ax, 0, 0), b = (bx, by, 0), c = (cx, cy, cz) -, each element b * 10.0.
-   Orthorhombic runs: the edges into cell[3]; triclinic runs: cell[9] as dcd_cells_tri fills it, through tri_cell_bad.  false, or
-   true with the reason periodic images are not offered for this box in why. */
-static bool box_cell_bad(const double b[9], bool tri, double cut, double *cell, char *why, size_t why_len)
-{
-    bool zero = true;
-    for (int k = 0; k < 9; ++k) zero = zero && b[k] == 0.0;
-    if (zero) { snprintf(why, why_len, "its box is all zero: the frame carries no cell"); return true; }
-    const int upper[3] = {1, 2, 5}, lower[3] = {3, 6, 7};
-    for (int k = 0; k < 3; ++k)
-        if (b[upper[k]] != 0.0) {
-            snprintf(why, why_len, "element [%d][%d] of its box is %.9g: a box must be lower-triangular", upper[k] / 3, upper[k] % 3, b[upper[k]]);
-            return true;
-        }
-    const double len[3] = {b[0] * 10.0, b[4] * 10.0, b[8] * 10.0};
-    if (!tri) {
-        for (int k = 0; k < 3; ++k)
-            if (b[lower[k]] != 0.0) {
-                snprintf(why, why_len, "its cell is not orthorhombic (element [%d][%d] of its box is %.9g): triclinic cells need bit 4", lower[k] / 3, lower[k] % 3, b[lower[k]]);
-                return true;
-            }
-        for (int k = 0; k < 3; ++k) {
-            if (!isfinite(len[k])) { snprintf(why, why_len, "edge %c of its cell is not finite", "xyz"[k]); return true; }
-            if (!(len[k] >= cut)) {
-                snprintf(why, why_len, "edge %c of its cell is %.9g, shorter than c = 2 (max radius + probe) = %.9g", "xyz"[k], len[k], cut);
-                return true;
-            }
-            cell[k] = len[k];
-        }
-        return false;
-    }
-    const int at[6] = {0, 3, 4, 6, 7, 8};
-    for (int k = 0; k < 6; ++k) {
-        cell[k] = b[at[k]] * 10.0;
-        if (!isfinite(cell[k])) { snprintf(why, why_len, "element [%d][%d] of its box is not finite", at[k] / 3, at[k] % 3); return true; }
-    }
-    return tri_cell_bad(cell, len, cut, why, why_len);
-}
-
-/* The cells of the same frames: a frame's box is nine floats in nm (box_cell_bad).  cells[nf][3], or [nf][9] in a triclinic run.
-   Returns -1, or the first frame whose box periodic images are not offered for, the reason in why. */
-long long xtc_cells(const TrajIO &io, const char *bytes, long long f0, long long nf, bool tri, double cut, double *cells, char *why, size_t why_len)
-{
-    const int64_t *off = io.xtc_off.data() + f0;
-    for (long long f = 0; f < nf; ++f) {
-        float b[9];
-        double bd[9];
-        freesasa_gpu_xtc_frame_box(bytes + (off[f] - off[0]), b);
-        for (int k = 0; k < 9; ++k) bd[k] = (double)b[k];
-        if (box_cell_bad(bd, tri, cut, cells + (tri ? PBC_TRI_CELL : 3) * f, why, why_len)) return f;
-    }
-    return -1;
-}
-
-/* The frames [f0, f0 + nf) of a TRR file at `bytes` (trr.c): EVERY header of the shard checked again as it lies in the staging -
-   the device trusts x_off for its bounds - and against the index: a frame's stretch begins with a record that holds coordinates,
-   the records behind it hold none, and they end where the index says the next frame begins.  x_off[nf]: the byte of every
-   frame's x[0] within the shard.  Returns -1, or the first frame that fails, the reason in why. */
-long long trr_descriptors(const TrajIO &io, const char *bytes, long long f0, long long nf, int frame_atoms, int64_t *x_off, char *why, size_t why_len)
-{
-    const int64_t *off = io.trr_off.data() + f0;
-    for (long long f = 0; f < nf; ++f) {
-        long long at = off[f] - off[0];
-        const long long end = off[f + 1] - off[0];
-        for (bool first = true; at < end; first = false) {
-            freesasa_gpu_trr_record r;
-            if (freesasa_gpu_trr_frame_desc(bytes + at, end - at, frame_atoms, io.trr.real_bytes, at, &r, why, (int)why_len)) return f;
-            if (first != (r.has_x != 0)) { snprintf(why, why_len, "its headers are not the ones the index was made from"); return f; }
-            if (first) x_off[f] = r.x_off;
-            at += r.record_bytes; /* (<= end: the record lies within what is left) */
-        }
-    }
-    return -1;
-}
-
-/* The cells of the same frames, their headers checked: a frame's box is nine reals in nm (box_cell_bad); a frame without a box
-   carries no cell.  cells[nf][3], or [nf][9] in a triclinic run.  Returns -1, or the first frame that fails, the reason in why. */
-long long trr_cells(const TrajIO &io, const char *bytes, long long f0, long long nf, bool tri, double cut, double *cells, char *why, size_t why_len)
-{
-    const int64_t *off = io.trr_off.data() + f0;
-    for (long long f = 0; f < nf; ++f) {
-        const long long at = off[f] - off[0];
-        freesasa_gpu_trr_record r;
-        double b[9];
-        if (freesasa_gpu_trr_frame_desc(bytes + at, off[f + 1] - off[f], 0, 0, at, &r, why, (int)why_len)) return f;
-        if (r.box_off < 0) { snprintf(why, why_len, "it has no box: the frame carries no cell"); return f; }
-        freesasa_gpu_trr_box(bytes + r.box_off, r.real_bytes, b);
-        if (box_cell_bad(b, tri, cut, cells + (tri ? PBC_TRI_CELL : 3) * f, why, why_len)) return f;
-    }
-    return -1;
-}
-
-/* the shard's frames in page-locked memory: the caller's own, or the lane's staging filled from memory or from the file
-   (a DCD file: the bytes as they lie there, every record marker checked; with periodic images every cell record decoded and
-   checked, the edges behind the bytes; an AMBER NetCDF file: the records as they lie there, with periodic images likewise) */
+/* the shard's frames in page-locked memory, checked: the frame source's (gpu_frames.hip) */
 int shard_read(TrajRun &T, freesasa_gpu_ctx *c, TrajShard &h)
 {
-    h.src = T.io.mem_in ? T.io.mem_in + 3 * T.fa * (size_t)h.f0 : nullptr;
-    if (h.src && T.in_pinned) return 0;
-    /* (an XTC shard: behind what goes up, the place its frames' status comes down to) */
-    if (ensure_pinned(c, &c->stage_in, &c->stage_in_cap, T.up_bytes(h.in_bytes, (size_t)h.nf) + (T.xtc ? 8 * (size_t)h.nf : 0))) return -1;
-    if (h.src) memcpy(c->stage_in, h.src, h.in_bytes);
-    else if (!pread_all(T.io.in.fd, c->stage_in, h.in_bytes, T.indexed ? (long long)T.idx[(size_t)h.f0] : T.io.in_header + (long long)T.stride * h.f0))
-        return ctx_fail(c, "could not read frames %lld..%lld of the frame file", h.f0, h.f0 + h.nf - 1);
-    if (T.xtc) {
-        char why[200];
-        const char *bytes = (const char *)c->stage_in;
-        const long long bad = xtc_descriptors(T.io, bytes, h.f0, h.nf, (int)T.fa, (freesasa_gpu_xtc_frame *)((char *)c->stage_in + T.xtc_desc_at(h.in_bytes, (size_t)h.nf)), why, sizeof why);
-        if (bad >= 0) return ctx_fail(c, "frame %lld of the XTC file is damaged: %s", h.f0 + bad, why);
-        if (T.pbc) {
-            const long long odd = xtc_cells(T.io, bytes, h.f0, h.nf, T.io.tri, T.pbc_cut, (double *)((char *)c->stage_in + TrajRun::cells_at(h.in_bytes)), why, sizeof why);
-            if (odd >= 0) return ctx_fail(c, "frame %lld of the XTC file: %s", h.f0 + odd, why);
-        }
-    }
-    if (T.trr) {
-        char why[200];
-        const char *bytes = (const char *)c->stage_in;
-        const long long bad = trr_descriptors(T.io, bytes, h.f0, h.nf, (int)T.fa, (int64_t *)((char *)c->stage_in + T.trr_xoff_at(h.in_bytes, (size_t)h.nf)), why, sizeof why);
-        if (bad >= 0) return ctx_fail(c, "frame %lld of the TRR file is damaged: %s", h.f0 + bad, why);
-        if (T.pbc) {
-            const long long odd = trr_cells(T.io, bytes, h.f0, h.nf, T.io.tri, T.pbc_cut, (double *)((char *)c->stage_in + TrajRun::cells_at(h.in_bytes)), why, sizeof why);
-            if (odd >= 0) return ctx_fail(c, "frame %lld of the TRR file: %s", h.f0 + odd, why);
-        }
-    }
-    if (T.dcd) {
-        const long long bad = dcd_damaged_frame(T.io.dcd, (const char *)c->stage_in, h.nf);
-        if (bad >= 0) return ctx_fail(c, "frame %lld of the DCD file is damaged: a record marker is not what the header implies", h.f0 + bad);
-        if (T.pbc) {
-            char why[160];
-            double *cells = (double *)((char *)c->stage_in + TrajRun::cells_at(h.in_bytes));
-            const long long odd = T.io.tri ? dcd_cells_tri(T.io.dcd, (const char *)c->stage_in, h.nf, T.pbc_cut, cells, why, sizeof why)
-                                           : dcd_cells(T.io.dcd, (const char *)c->stage_in, h.nf, T.pbc_cut, cells, why, sizeof why);
-            if (odd >= 0) return ctx_fail(c, "frame %lld of the DCD file: %s", h.f0 + odd, why);
-        }
-    }
-    if (T.netcdf && T.pbc) {
-        char why[160];
-        const long long odd = nc_cells(T.io.nc, (const char *)c->stage_in, h.nf, T.io.tri, T.pbc_cut, (double *)((char *)c->stage_in + TrajRun::cells_at(h.in_bytes)), why, sizeof why);
-        if (odd >= 0) return ctx_fail(c, "frame %lld of the NetCDF file: %s", h.f0 + odd, why);
-    }
-    h.src = c->stage_in;
-    return 0;
+    return T.src.read(c, h.f0, h.nf, h.in_bytes, &h.src);
 }
 
-/* The decode of the XTC frames that lie on the device with their descriptors, for the driver's shards and for the test hook
-   freesasa_gpu_xtc_decode_dev alike: scan, then unpack, on the context's stream, then the frames' (groups, status) pairs down
-   to `status` (page-locked, 2 n_frames words); returns when they are there. */
-int xtc_decode(freesasa_gpu_ctx *c, const sasa::XtcArgs &xa, int32_t *status)
-{
-    if (kl_xtc_scan(xa, c->stream) != hipSuccess || kl_xtc_unpack(xa, c->stream) != hipSuccess) return ctx_fail(c, "XTC decode launch failed");
-    if (hipMemcpyAsync(status, xa.count, 8 * (size_t)xa.n_frames, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
-        return ctx_fail(c, "could not read the status of the XTC frames");
-    return 0;
-}
-
-/* ... to the device, into the compact fp64 frames the engine reads (c->h_xyz): as they are, widened, or gathered; a DCD file's
-   bytes as they are, de-planarized (and gathered, widened, byte-swapped) by one kernel; a NetCDF file's likewise */
+/* ... to the device, into the compact fp64 frames the engine reads (c->h_xyz): the frame source's copy and kernels; with chain
+   groups, behind them, every group's atoms of every frame */
 int shard_upload(TrajRun &T, TrajLane &L, const TrajShard &h)
 {
     freesasa_gpu_ctx *c = L.c;
-    const bool f32 = T.f32;
-    void *d_in = T.gather || T.container || T.xtc ? c->g_xyz.p : (f32 ? c->h_counts.p : c->h_xyz.p);
-    /* (periodic images: the shard's cell edges behind its bytes, in the same copy; an XTC shard: its descriptors too) */
-    const size_t up_bytes = T.up_bytes(h.in_bytes, (size_t)h.nf);
-    if (hipMemcpyAsync(d_in, h.src, up_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "host-to-device copy failed");
     L.ta.n_frames = h.nf;
-    if (T.xtc) {
-        /* scan, then unpack: raw fp32 frames where the raw fp32 path has them - and the frames' status down BEFORE the engine sees
-           them: what a damaged stream leaves of a frame is not a frame (one more synchronisation per shard; the other lanes' shards
-           fill the device meanwhile) */
-        const size_t nf = (size_t)h.nf;
-        char *g = (char *)c->g_xyz.p;
-        int32_t *status = (int32_t *)((char *)c->stage_in + up_bytes);
-        d_in = T.gather ? (void *)(g + T.xtc_f32_at(h.in_bytes, nf)) : c->h_counts.p;
-        const sasa::XtcArgs xa = {(int)T.fa, h.nf, (const uint32_t *)g, (const freesasa_gpu_xtc_frame *)(g + T.xtc_desc_at(h.in_bytes, nf)),
-                                  (sasa::XtcRec *)(g + T.xtc_rec_at(h.in_bytes, nf)), (int32_t *)(g + T.xtc_count_at(h.in_bytes, nf)), (float *)d_in};
-        if (xtc_decode(c, xa, status)) return -1;
-        for (size_t f = 0; f < nf; ++f)
-            if (const int st = status[2 * f + 1])
-                return ctx_fail(c, "frame %lld of the XTC file is damaged: %s", h.f0 + (long long)f,
-                                st & sasa::XTC_ST_BITS ? "its stream ends before its atoms do" : st & sasa::XTC_ST_ATOMS ? "a group of its stream runs past its atoms"
-                                : st & sasa::XTC_ST_SMALLIDX ? "smallidx leaves 9 .. 72 in its stream" : "its stream unpacks to a value outside its range");
-    }
-    if (T.dcd) {
-        const freesasa_gpu_dcd_info &d = T.io.dcd;
-        const sasa::TrajDcdArgs da = {(int)T.n, h.nf, T.gather ? L.ta.index : nullptr, d.frame_bytes, d.x_off, d.plane_bytes};
-        if (kl_traj_gather_dcd(da, d_in, d.big_endian != 0, (double *)c->h_xyz.p, c->stream) != hipSuccess) return ctx_fail(c, "DCD gather launch failed");
-    }
-    if (T.netcdf) {
-        const sasa::TrajNcArgs na = {(int)T.n, h.nf, T.gather ? L.ta.index : nullptr, T.io.nc.record_bytes, T.io.nc.coord_off};
-        if (kl_traj_gather_nc(na, d_in, (double *)c->h_xyz.p, c->stream) != hipSuccess) return ctx_fail(c, "NetCDF gather launch failed");
-    }
-    if (T.trr) {
-        const sasa::TrajTrrArgs ra = {(int)T.n, h.nf, T.gather ? L.ta.index : nullptr, (const int64_t *)((const char *)d_in + T.trr_xoff_at(h.in_bytes, (size_t)h.nf))};
-        if (kl_traj_gather_trr(ra, d_in, T.io.trr.real_bytes == 8, (double *)c->h_xyz.p, c->stream) != hipSuccess) return ctx_fail(c, "TRR gather launch failed");
-    }
-    /* full frames up as they were read: one kernel drops the solvent and widens fp32 */
-    if (T.gather && !T.container && kl_traj_gather(L.ta, d_in, f32, (double *)c->h_xyz.p, c->stream) != hipSuccess) return ctx_fail(c, "gather launch failed");
-    if (!T.gather && f32 && kl_widen_f32((const float *)d_in, (double *)c->h_xyz.p, (long long)(3 * h.na), c->stream) != hipSuccess) return ctx_fail(c, "widening launch failed");
+    if (T.src.to_frames(c, L.ta, h.f0, h.nf, h.in_bytes, h.src)) return -1;
     if (!T.groups) return 0;
     /* chain groups: behind the compact frames, whoever made them, every group's atoms of every frame; the radii of the
        combined batch once per shard length (the isolated structures begin at nf n) */
@@ -914,11 +533,12 @@ int shard_compute(TrajRun &T, TrajLane &L, TrajShard &h)
     c->shared_radii = !T.groups;
     /* periodic images: the compact frames expanded by their cells, the engine on the expanded shard (radii per atom, offsets
        that vary), the real atoms' areas and totals collected where the plain path puts them (gpu_periodic.hip) */
-    const size_t at = TrajRun::cells_at(h.in_bytes);
+    const bool pbc = T.src.pbc;
+    const double *cells = pbc ? T.src.host_cells(c, h.in_bytes) : nullptr, *d_cells = pbc ? T.src.dev_cells(c, h.in_bytes) : nullptr;
     /* chain groups among periodic images: the combined batch - the frames, behind them every group of every frame - through the
        same stage, every group in its frame's cell; behind the engine the fused finish has put areas, isolated areas, gathered
        complex areas and both sets of totals where the groups' path below has them after its own finish (gpu_periodic.hip) */
-    const bool gpbc = T.pbc && T.groups;
+    const bool gpbc = pbc && T.groups;
     sasa::GpbcArgs gx;
     memset(&gx, 0, sizeof gx);
     if (gpbc) {
@@ -927,12 +547,12 @@ int shard_compute(TrajRun &T, TrajLane &L, TrajShard &h)
         gx.src = L.ga.src; gx.n_fixed = (int)T.n; gx.n_iso_fixed = (int)T.n_iso; gx.key = L.ga.group;
         gx.carea = (double *)c->h_sasa.p; gx.cgath = (double *)c->g_gath.p; gx.iso = out[OUT_ISO].per_frame ? (double *)c->h_iso.p : nullptr;
     }
-    const int rb = gpbc ? groups_periodic_stage(c, T.io.tri, T.s.alg, (double *)c->h_xyz.p, (double *)c->h_radii.p, (nf != T.FB ? T.offs_last : T.offs).data(),
-                                                (const double *)((const char *)h.src + at), (const double *)((const char *)c->g_xyz.p + at), gx,
+    const int rb = gpbc ? groups_periodic_stage(c, T.src.tri, T.s.alg, (double *)c->h_xyz.p, (double *)c->h_radii.p, (nf != T.FB ? T.offs_last : T.offs).data(),
+                                                cells, d_cells, gx,
                                                 T.s.probe, T.s.resolution, T.s.alg == 1 ? T.tp.data() : nullptr, (double *)c->h_totals.p,
                                                 (double *)c->g_tot2.p, nullptr)
-                 : T.pbc ? (T.io.tri ? periodic_resident_tri : periodic_resident)(c, T.s.alg, (double *)c->h_xyz.p, (double *)c->h_radii.p, T.offs.data(), h.nf, (int)T.n,
-                                             (const double *)((const char *)h.src + at), (const double *)((const char *)c->g_xyz.p + at),
+                 : pbc ? (T.src.tri ? periodic_resident_tri : periodic_resident)(c, T.s.alg, (double *)c->h_xyz.p, (double *)c->h_radii.p, T.offs.data(), h.nf, (int)T.n,
+                                             cells, d_cells,
                                              T.s.probe, T.s.resolution, T.s.alg == 1 ? T.tp.data() : nullptr, (double *)c->h_sasa.p,
                                              (double *)c->h_totals.p, nullptr)
                  : out[OUT_VOL].per_frame /* (the volume entries: the batch with its exposed-point vectors kept, the frames' volumes into the block of sums) */
@@ -967,10 +587,10 @@ int shard_compute(TrajRun &T, TrajLane &L, TrajShard &h)
     }
     /* (file output only) per-atom areas narrowed on the device: half the bytes over PCIe and into the file */
     const bool narrow = out[OUT_SASA].deliver() && T.io.out_f32();
-    h.d_areas = narrow ? (char *)c->h_counts.p + T.widen_bytes : c->h_sasa.p;
+    h.d_areas = narrow ? (char *)c->h_counts.p + T.src.widen_bytes() : c->h_sasa.p;
     if (narrow && kl_narrow_f64((const double *)c->h_sasa.p, (float *)h.d_areas, (long long)h.na, c->stream) != hipSuccess) return ctx_fail(c, "narrowing launch failed");
     if (h.d_iso && out[OUT_ISO].deliver() && T.io.out_f32()) {
-        h.d_iso = (char *)c->h_counts.p + T.widen_bytes + 4 * T.n * T.FB;
+        h.d_iso = (char *)c->h_counts.p + T.src.widen_bytes() + 4 * T.n * T.FB;
         if (kl_narrow_f64((const double *)c->h_iso.p, (float *)h.d_iso, (long long)h.na, c->stream) != hipSuccess) return ctx_fail(c, "narrowing launch failed");
     }
     double *const d_x = (double *)c->h_gtot.p;
@@ -1087,7 +707,7 @@ void traj_lane(TrajRun &T, int id) noexcept
         if (s.max_new > 0 && T.fresh.fetch_add(1) >= s.max_new) { T.stopped = 1; break; }
         h.f0 = h.k * s.frames_per_batch;
         h.nf = (int)(s.n_frames - h.f0 < s.frames_per_batch ? s.n_frames - h.f0 : s.frames_per_batch);
-        h.na = T.n * (size_t)h.nf; h.in_bytes = T.shard_bytes(h.f0, h.nf);
+        h.na = T.n * (size_t)h.nf; h.in_bytes = T.src.shard_bytes(h.f0, h.nf);
         if (shard_run(T, L, h)) {
             (void)hipStreamSynchronize(L.c->stream); /* nothing of the shard may still run when the lane lets go */
             T.shard_failed(h.k, L.c->err[0] ? L.c->err : "trajectory shard failed");
@@ -1147,69 +767,6 @@ int traj_run_mem(TrajIO &io, const TrajSpec &s, double *stats_out, double *parti
 
 } /* namespace */
 
-/* ------------------------------------------------------------------ test hook: the XTC decode on its own (include/freesasa_gpu.h) */
-
-/* what freesasa_gpu_xtc_decode_dev refuses before it touches a device: host only */
-extern "C" int freesasa_gpu_xtc_decode_check(const void *bytes, long long len, int n_frames, int n_atoms, const int32_t *rec, const int32_t *count,
-                                             const float *out, char *err_out, int err_len)
-{
-    if (err_out && err_len > 0) err_out[0] = 0;
-    if (!bytes || !rec || !count || !out) return set_err(err_out, err_len, "xtc_decode: null argument");
-    if (n_frames < 1) return set_err(err_out, err_len, "xtc_decode: n_frames must be at least 1");
-    if (n_atoms < 1) return set_err(err_out, err_len, "xtc_decode: n_atoms must be at least 1");
-    if (len < 1) return set_err(err_out, err_len, "xtc_decode: len must be at least 1");
-    if ((long long)n_frames * n_atoms > 0x7fffffffLL) return set_err(err_out, err_len, "xtc_decode: n_frames * n_atoms does not fit an int");
-    return 0;
-}
-
-extern "C" int freesasa_gpu_xtc_decode_dev(freesasa_gpu_ctx *c, const void *bytes, long long len, int n_frames, int n_atoms, int32_t *rec,
-                                           int32_t *count, float *out)
-{
-    if (!c) return -1;
-    return guarded_ctx(c, [&]() -> int {
-    c->err[0] = 0;
-    if (freesasa_gpu_xtc_decode_check(bytes, len, n_frames, n_atoms, rec, count, out, c->err, (int)sizeof c->err)) return -1;
-    if (freesasa_gpu_wait(c)) return -1; /* (batches submitted asynchronously come first, as for every synchronous entry) */
-    /* on the device, every part at a multiple of 8: the bytes | one descriptor per frame | (groups, status) per frame | the
-       group records (at a multiple of 16) | the fp32 frames; in the staging: the bytes | the descriptors | where the status comes down to */
-    const size_t nf = (size_t)n_frames, slots = nf * (size_t)n_atoms, in_bytes = ((size_t)len + 7) & ~(size_t)7;
-    const size_t desc_at = in_bytes, count_at = desc_at + sizeof(freesasa_gpu_xtc_frame) * nf, rec_at = (count_at + 8 * nf + 15) & ~(size_t)15;
-    const size_t out_at = rec_at + sizeof(sasa::XtcRec) * slots;
-    if (ensure_pinned(c, &c->stage_in, &c->stage_in_cap, count_at + 8 * nf)) return -1;
-    char *stage = (char *)c->stage_in;
-    memcpy(stage, bytes, (size_t)len);
-    memset(stage + len, 0, in_bytes - (size_t)len);
-    freesasa_gpu_xtc_frame *desc = (freesasa_gpu_xtc_frame *)(stage + desc_at);
-    long long at = 0;
-    for (int f = 0; f < n_frames; ++f) {
-        char why[200];
-        long long frame_bytes = 0;
-        if (freesasa_gpu_xtc_frame_desc(stage + at, len - at, n_atoms, at + FREESASA_GPU_XTC_HEADER, &desc[f], &frame_bytes, why, (int)sizeof why))
-            return ctx_fail(c, "frame %d of the XTC bytes: %s", f, why);
-        at += frame_bytes;
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (ensure(c, c->g_xyz, out_at + 12 * slots)) return -1;
-    char *g = (char *)c->g_xyz.p;
-    const sasa::XtcArgs xa = {n_atoms, n_frames, (const uint32_t *)g, (const freesasa_gpu_xtc_frame *)(g + desc_at), (sasa::XtcRec *)(g + rec_at),
-                              (int32_t *)(g + count_at), (float *)(g + out_at)};
-    HIP_TRY(c, hipMemcpyAsync(g, stage, count_at, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemsetAsync(xa.count, 0xff, 8 * nf, c->stream));
-    HIP_TRY(c, hipMemsetAsync(xa.rec, 0, sizeof(sasa::XtcRec) * slots, c->stream));
-    HIP_TRY(c, hipMemsetAsync(xa.out, 0xff, 12 * slots, c->stream));
-    int32_t *status = (int32_t *)(stage + count_at);
-    int rc = xtc_decode(c, xa, status);
-    if (!rc && (hipMemcpyAsync(rec, xa.rec, sizeof(sasa::XtcRec) * slots, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                hipMemcpyAsync(out, xa.out, 12 * slots, hipMemcpyDeviceToHost, c->stream) != hipSuccess))
-        rc = ctx_fail(c, "could not read the XTC records and frames back");
-    /* (nothing is left running on the stream, whatever failed) */
-    if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = ctx_fail(c, "could not read the XTC records and frames back");
-    if (rc) return -1;
-    memcpy(count, status, 8 * nf);
-    return 0;
-    });
-}
-
 /* ------------------------------------------------------------------ entry points: trajectories */
 
 extern "C" int freesasa_gpu_trajectory_stats(const double *xyz_frames, const double *radii, int n_atoms, int n_frames,
@@ -1225,7 +782,7 @@ extern "C" int freesasa_gpu_trajectory_stats(const double *xyz_frames, const dou
     if (traj_check_args(s, "n_atoms and n_frames must be > 0", err_out, err_len) || traj_shard_size(s, n_atoms, err_out, err_len)) return -1;
     return guarded(err_out, err_len, [&]() -> int {
         TrajIO io;
-        io.mem_in = xyz_frames; io.out[OUT_TOTALS].mem = totals_out; io.out[OUT_SASA].mem = sasa_out; io.stats = stats;
+        io.src.open_memory(xyz_frames, (size_t)n_atoms); io.out[OUT_TOTALS].mem = totals_out; io.out[OUT_SASA].mem = sasa_out; io.stats = stats;
         return traj_run_mem(io, s, stats_out, partials_out, err_out, err_len);
     });
 }
@@ -1269,7 +826,7 @@ static int trajectory_mem_topo(const double *xyz_frames, int n_frames, const fre
         TrajSpec s = {tp.radii, tp.n, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, &tp};
         if (traj_check_args(s, "n_frames must be > 0", err_out, err_len) || traj_shard_size(s, frame_atoms, err_out, err_len)) return -1;
         TrajIO io;
-        io.mem_in = xyz_frames; io.sel_atoms = sel_atoms_out;
+        io.src.open_memory(xyz_frames, (size_t)frame_atoms); io.sel_atoms = sel_atoms_out;
         void *const mem[N_OUT] = {totals_out, sasa_out, iso_out, masks_out, class_sums_out, residues_out, sel_area_out, group_areas_out, volumes_out};
         for (int k = 0; k < N_OUT; ++k) io.out[k].mem = mem[k];
         io.stats = stats;
@@ -1378,13 +935,13 @@ extern "C" int freesasa_gpu_trajectory_topology(const double *xyz_frames, int n_
    time and a checksum of the radii - NOT the devices: a run interrupted on eight GPUs may be finished on one, with the same
    files byte for byte.  With a topology, in front of the line's end, what its outputs depend on: digests of the index, of
    residue boundaries + classes + backbone flags, of the selection set's program, and which result files the run writes; with
-   chain groups, behind that, a digest of the group count and the ids; with run statistics, last, the word as stats=.  A DCD run: bit 2 in the f32= word and the byte of
-   frame 0 as header_bytes=; an AMBER NetCDF run: bit 5 and the byte of record 0; an XTC run: bit 6 (its frames are found by the index: header_bytes=0); a TRR run: bit 7 likewise; a raw run's line is what it was.  Periodic images: bit 3 in the f32= word, triclinic cells: bit 4. */
+   chain groups, behind that, a digest of the group count and the ids; with run statistics, last, the word as stats=.  The f32= word:
+   the frame source's bits (the input's format, periodic images) and bit 1, fp32 per-atom output; header_bytes=: the byte of frame 0. */
 static int traj_done_head(char *head, size_t cap, const TrajSpec &s, const TrajIO &io, const struct stat &st)
 {
     int len = snprintf(head, cap, "freesasa_amd trajectory done-list v2 n_atoms=%d n_frames=%lld frames_per_batch=%d alg=%d resolution=%d probe=%.17g f32=%d "
                        "header_bytes=%lld frames_size=%lld frames_mtime=%lld.%09ld radii=%016llx\n",
-                       s.n_atoms, s.n_frames, s.frames_per_batch, s.alg, s.resolution, s.probe, io.in_f32 | (io.out_f32() << 1) | (io.in_dcd ? FREESASA_GPU_FRAMES_DCD : 0) | (io.in_nc ? FREESASA_GPU_FRAMES_NETCDF : 0) | (io.in_xtc ? FREESASA_GPU_FRAMES_XTC : 0) | (io.in_trr ? FREESASA_GPU_FRAMES_TRR : 0) | (io.pbc ? FREESASA_GPU_FRAMES_PBC : 0) | (io.tri ? FREESASA_GPU_FRAMES_TRICLINIC : 0), io.in_header, (long long)st.st_size,
+                       s.n_atoms, s.n_frames, s.frames_per_batch, s.alg, s.resolution, s.probe, io.src.head_f32() | (io.out_f32() << 1), io.src.head_bytes(), (long long)st.st_size,
                        (long long)st.st_mtim.tv_sec, (long)st.st_mtim.tv_nsec, fnv1a(s.radii, 8 * (size_t)s.n_atoms));
     const TrajTopo *tp = s.topo;
     if (tp && len > 0 && len < (int)cap) {
@@ -1410,8 +967,8 @@ static int traj_done_head(char *head, size_t cap, const TrajSpec &s, const TrajI
     return len > 0 && len < (int)cap ? 0 : -1;
 }
 
-/* Frame file (raw frames, with FREESASA_GPU_FRAMES_DCD a DCD trajectory, with FREESASA_GPU_FRAMES_NETCDF an AMBER NetCDF one, with FREESASA_GPU_FRAMES_XTC / _TRR a GROMACS one) -> result files, resumable (include/freesasa_gpu.h has the formats).  The caller has put the result files'
-   paths into io.out[]; s.topo: a run with a topology - frames of its frame_atoms atoms, a longer first line of the done-list. */
+/* Frame file (of any format the frame source opens: include/freesasa_gpu.h has them) -> result files, resumable.  The caller has
+   put the result files' paths into io.out[]; s.topo: a run with a topology - frames of its frame_atoms atoms, a longer first line of the done-list. */
 static int trajectory_file_run(const char *frames_path, int frames_f32, long long header_bytes, TrajSpec s, TrajIO &io,
                                const char *done_path, long long *frames_total_out, char *err_out, int err_len)
 {
@@ -1419,102 +976,15 @@ static int trajectory_file_run(const char *frames_path, int frames_f32, long lon
     if (s.n_atoms <= 0 || header_bytes < 0) return set_err(err_out, err_len, "bad argument");
     if (io.stats && (!io.stats_path || !io.parts_path)) return set_err(err_out, err_len, "statistics need a statistics path and a partials path");
     const long long frame_atoms = s.topo ? s.topo->frame_atoms : s.n_atoms;
-    if ((frames_f32 & FREESASA_GPU_FRAMES_PBC) && !(frames_f32 & (FREESASA_GPU_FRAMES_DCD | FREESASA_GPU_FRAMES_NETCDF | FREESASA_GPU_FRAMES_XTC | FREESASA_GPU_FRAMES_TRR)))
-        return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) needs bit 2 (a DCD file), bit 5 (an AMBER NetCDF file), bit 6 (an XTC file) or bit 7 (a TRR file): raw frame files carry no cell");
-    if ((frames_f32 & FREESASA_GPU_FRAMES_TRICLINIC) && !(frames_f32 & FREESASA_GPU_FRAMES_PBC))
-        return set_err(err_out, err_len, "bit 4 of frames_f32 (triclinic cells) needs bit 3 (periodic images) and bit 2 (a DCD file), bit 5 (an AMBER NetCDF file), bit 6 (an XTC file) or bit 7 (a TRR file)");
-    if (frames_f32 & FREESASA_GPU_FRAMES_TRR) {
-        /* a TRR file's frames are found by one pass over its records' headers: before a device is touched or an output file opened */
-        if (frames_f32 & FREESASA_GPU_FRAMES_F32) return set_err(err_out, err_len, "bit 0 of frames_f32 (raw fp32 frames) and bit 7 (a TRR file) exclude each other: the file says its own precision");
-        if (frames_f32 & FREESASA_GPU_FRAMES_DCD) return set_err(err_out, err_len, "bit 2 of frames_f32 (a DCD file) and bit 7 (a TRR file) exclude each other");
-        if (frames_f32 & FREESASA_GPU_FRAMES_NETCDF) return set_err(err_out, err_len, "bit 5 of frames_f32 (an AMBER NetCDF file) and bit 7 (a TRR file) exclude each other");
-        if (frames_f32 & FREESASA_GPU_FRAMES_XTC) return set_err(err_out, err_len, "bit 6 of frames_f32 (an XTC file) and bit 7 (a TRR file) exclude each other");
-        if (header_bytes != 0) return set_err(err_out, err_len, "header_bytes must be 0 with a TRR file: its frames are found by their headers");
-        int64_t *offsets = nullptr;
-        if (freesasa_gpu_trr_index_read(frames_path, &io.trr, &offsets, err_out, err_len)) return -1;
-        const int rc = guarded(err_out, err_len, [&]() -> int { io.trr_off.assign(offsets, offsets + io.trr.n_frames + 1); return 0; });
-        freesasa_gpu_trr_index_free(offsets);
-        if (rc) return -1;
-        if (io.trr.n_atoms != frame_atoms) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "the TRR file holds %d atoms per frame, the run expects %lld", (int)io.trr.n_atoms, frame_atoms);
-            return set_err(err_out, err_len, msg);
-        }
-        io.in_trr = true;
-        if (frames_f32 & FREESASA_GPU_FRAMES_PBC) {
-            if (!io.trr.has_box) return set_err(err_out, err_len, "periodic images need a TRR file with a box: this one's first coordinate frame has none, or one that is all zero");
-            io.pbc = true;
-            io.tri = (frames_f32 & FREESASA_GPU_FRAMES_TRICLINIC) != 0;
-        }
-    } else if (frames_f32 & FREESASA_GPU_FRAMES_XTC) {
-        /* an XTC file's frames are found by one pass over their headers: before a device is touched or an output file opened */
-        if (frames_f32 & FREESASA_GPU_FRAMES_F32) return set_err(err_out, err_len, "bit 0 of frames_f32 (raw fp32 frames) and bit 6 (an XTC file) exclude each other");
-        if (frames_f32 & FREESASA_GPU_FRAMES_DCD) return set_err(err_out, err_len, "bit 2 of frames_f32 (a DCD file) and bit 6 (an XTC file) exclude each other");
-        if (frames_f32 & FREESASA_GPU_FRAMES_NETCDF) return set_err(err_out, err_len, "bit 5 of frames_f32 (an AMBER NetCDF file) and bit 6 (an XTC file) exclude each other");
-        if (header_bytes != 0) return set_err(err_out, err_len, "header_bytes must be 0 with an XTC file: its frames are found by their headers");
-        int64_t *offsets = nullptr;
-        if (freesasa_gpu_xtc_index_read(frames_path, &io.xtc, &offsets, err_out, err_len)) return -1;
-        const int rc = guarded(err_out, err_len, [&]() -> int { io.xtc_off.assign(offsets, offsets + io.xtc.n_frames + 1); return 0; });
-        freesasa_gpu_xtc_index_free(offsets);
-        if (rc) return -1;
-        if (io.xtc.n_atoms != frame_atoms) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "the XTC file holds %d atoms per frame, the run expects %lld", (int)io.xtc.n_atoms, frame_atoms);
-            return set_err(err_out, err_len, msg);
-        }
-        io.in_xtc = true;
-        if (frames_f32 & FREESASA_GPU_FRAMES_PBC) {
-            if (!io.xtc.has_box) return set_err(err_out, err_len, "periodic images need an XTC file with a box: the box of this one's first frame is all zero");
-            io.pbc = true;
-            io.tri = (frames_f32 & FREESASA_GPU_FRAMES_TRICLINIC) != 0;
-        }
-    } else if (frames_f32 & FREESASA_GPU_FRAMES_NETCDF) {
-        /* an AMBER NetCDF file says for itself where its frames are and what they are: before a device is touched or an output file opened */
-        if (frames_f32 & FREESASA_GPU_FRAMES_F32) return set_err(err_out, err_len, "bit 0 of frames_f32 (raw fp32 frames) and bit 5 (an AMBER NetCDF file) exclude each other");
-        if (frames_f32 & FREESASA_GPU_FRAMES_DCD) return set_err(err_out, err_len, "bit 2 of frames_f32 (a DCD file) and bit 5 (an AMBER NetCDF file) exclude each other");
-        if (header_bytes != 0) return set_err(err_out, err_len, "header_bytes must be 0 with an AMBER NetCDF file: the byte of its first record comes from its header");
-        if (freesasa_gpu_nc_info_read(frames_path, &io.nc, err_out, err_len)) return -1;
-        if (io.nc.n_atoms != frame_atoms) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "the NetCDF file holds %d atoms per frame, the run expects %lld", (int)io.nc.n_atoms, frame_atoms);
-            return set_err(err_out, err_len, msg);
-        }
-        io.in_nc = true;
-        if (frames_f32 & FREESASA_GPU_FRAMES_PBC) {
-            if (!io.nc.has_cell) return set_err(err_out, err_len, "periodic images need a NetCDF file with the variables cell_lengths and cell_angles: this one has no cell");
-            io.pbc = true;
-            io.tri = (frames_f32 & FREESASA_GPU_FRAMES_TRICLINIC) != 0;
-        }
-    } else if (frames_f32 & FREESASA_GPU_FRAMES_DCD) {
-        /* a DCD file says for itself where its frames are and what they are: before a device is touched or an output file opened */
-        if (header_bytes != 0) return set_err(err_out, err_len, "header_bytes must be 0 with a DCD file: the byte of its first frame comes from its header");
-        if (frames_f32 & FREESASA_GPU_FRAMES_F32) return set_err(err_out, err_len, "bit 0 of frames_f32 (raw fp32 frames) and bit 2 (a DCD file) exclude each other");
-        if (freesasa_gpu_dcd_info_read(frames_path, &io.dcd, err_out, err_len)) return -1;
-        if (io.dcd.n_atoms != frame_atoms) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "the DCD file holds %d atoms per frame, the run expects %lld", (int)io.dcd.n_atoms, frame_atoms);
-            return set_err(err_out, err_len, msg);
-        }
-        io.in_dcd = true;
-        if (frames_f32 & FREESASA_GPU_FRAMES_PBC) {
-            if (!io.dcd.has_cell) return set_err(err_out, err_len, "periodic images need a DCD file with a unit-cell record per frame: this one has none");
-            io.pbc = true;
-            io.tri = (frames_f32 & FREESASA_GPU_FRAMES_TRICLINIC) != 0;
-        }
-    }
+    if (io.src.open(frames_path, frames_f32, header_bytes, frame_atoms, err_out, err_len)) return -1;
     if (traj_check_args(s, nullptr, err_out, err_len)) return -1;
     return guarded(err_out, err_len, [&]() -> int {
-    io.in.fd = open(frames_path, O_RDONLY);
-    if (io.in.fd < 0) return set_err(err_out, err_len, "cannot open the frame file");
+    io.src.file.fd = open(frames_path, O_RDONLY);
+    if (io.src.file.fd < 0) return set_err(err_out, err_len, "cannot open the frame file");
     struct stat st;
-    if (fstat(io.in.fd, &st) != 0) return set_err(err_out, err_len, "cannot stat the frame file");
-    io.in_header = io.in_dcd ? io.dcd.first_frame : io.in_nc ? io.nc.first_record : header_bytes;
-    io.in_f32 = (frames_f32 & 1) ? 1 : 0; io.out[OUT_SASA].esz = io.out[OUT_ISO].esz = (frames_f32 & 2) ? 4 : 8;
-    const long long in_file = io.in_dcd ? ((long long)st.st_size - io.dcd.first_frame) / io.dcd.frame_bytes
-                            : io.in_nc ? ((long long)st.st_size - io.nc.first_record) / io.nc.record_bytes
-                            : io.in_xtc ? (long long)io.xtc.n_frames
-                            : io.in_trr ? (long long)io.trr.n_frames
-                                        : ((long long)st.st_size - header_bytes) / ((io.in_f32 ? 12LL : 24LL) * frame_atoms);
+    if (fstat(io.src.file.fd, &st) != 0) return set_err(err_out, err_len, "cannot stat the frame file");
+    io.out[OUT_SASA].esz = io.out[OUT_ISO].esz = (frames_f32 & 2) ? 4 : 8;
+    const long long in_file = io.src.frames_in_file((long long)st.st_size);
     if (s.n_frames <= 0) s.n_frames = in_file;
     if (s.n_frames <= 0 || s.n_frames > in_file) return set_err(err_out, err_len, "the frame file holds fewer frames than asked for");
     if (frames_total_out) *frames_total_out = s.n_frames;

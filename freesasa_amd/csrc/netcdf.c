@@ -1,7 +1,7 @@
 /*
  * netcdf.c — the header of an AMBER NetCDF trajectory (convention 1.0, `.nc` as sander / pmemd / cpptraj / OpenMM / MDAnalysis
  * write it), read on the host for the trajectory file drivers (include/freesasa_gpu.h, freesasa_gpu_nc_info_read;
- * gpu_drivers.hip).  The file is NetCDF classic: uncompressed, big-endian, and every frame is one RECORD at a constant byte
+ * gpu_frames.hip).  The file is NetCDF classic: uncompressed, big-endian, and every frame is one RECORD at a constant byte
  * stride, so all the drivers need from it is where a record's coordinates (and its cell) lie: the records themselves go to the
  * device as they are in the file (traj_kernels.h, traj_gather_nc).
  *

@@ -1,7 +1,7 @@
 /*
  * trr.c — the records of a GROMACS TRR trajectory, found and checked on the host for the trajectory file drivers
  * (include/freesasa_gpu.h, freesasa_gpu_trr_info_read, freesasa_gpu_trr_index_read, freesasa_gpu_trr_frame_desc;
- * gpu_drivers.hip).  A TRR record is UNCOMPRESSED, in single or double precision, and holds whichever of box, virial,
+ * gpu_frames.hip).  A TRR record is UNCOMPRESSED, in single or double precision, and holds whichever of box, virial,
  * pressure, coordinates, velocities and forces its writer chose for that step (nstxout, nstvout, nstfout): records have no
  * common stride and need not hold coordinates at all.  The host does what the header says: ONE pass over the headers gives the
  * byte offset of every record WITH coordinates (the index, by which shards are cut - the records without lie between them and

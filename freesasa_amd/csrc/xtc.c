@@ -1,7 +1,7 @@
 /*
  * xtc.c — the frames of a GROMACS XTC trajectory, found and checked on the host for the trajectory file drivers
  * (include/freesasa_gpu.h, freesasa_gpu_xtc_info_read, freesasa_gpu_xtc_index_read, freesasa_gpu_xtc_frame_desc;
- * gpu_drivers.hip).  An XTC frame is COMPRESSED: a 92-byte header and one bit stream of packed integers whose length the
+ * gpu_frames.hip).  An XTC frame is COMPRESSED: a 92-byte header and one bit stream of packed integers whose length the
  * header names, so frames have no common stride.  The host does what needs no bit of the stream: ONE pass over the headers
  * gives the byte offset of every frame (the index, by which shards are cut) and checks every header; per frame of a shard a
  * descriptor of 64 bytes says where the stream lies and how its integers are packed.  The streams go to the device as they

@@ -1,7 +1,7 @@
 /* TESTS ONLY: traj_gather_trr (freesasa_amd/csrc/traj_kernels.h) driven thread by thread on the CPU, in the launch shape of
  * kl_traj_gather_trr (gpu_kernels.hip): workgroups of TRAJ_B threads over 3 * n_frames * n output coordinates.  `shard`: the
  * bytes of a run of whole records; the table of x_off is made from their headers by trr.c, as the driver makes it
- * (gpu_drivers.hip, trr_descriptors).  Never linked into the product. */
+ * (gpu_frames.hip, trr_descriptors).  Never linked into the product. */
 #include <stdint.h>
 #include <string.h>
 

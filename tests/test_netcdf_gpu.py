@@ -170,7 +170,7 @@ def test_periodic_run_with_a_topology_equals_the_dcd_run(solvated, tmp_path):
     sel = ingest.Selection(COMMANDS)
     try:
         out = {}
-        for tag, path, kw in (("dcd", dcd, dict(dcd=True)), ("nc", nc, dict(netcdf=True))):
+        for tag, path, kw in (("dcd", dcd, dict(dcd=True)), ("nc", nc, dict(netcdf=True)), ("nc-tri", nc, dict(netcdf=True, triclinic=True))):
             p = {k: str(tmp_path / f"{tag}.{k}") for k in OUTS[:5] + ("done",)}
             done, n_frames, atoms = fa.trajectory_file_topology(path, b, p["totals"], atom_index=index, selection=sel, sasa_path=p["sasa"],
                                                                 class_sums_path=p["cls"], residues_path=p["res"], selections_path=p["sel"],
@@ -180,6 +180,7 @@ def test_periodic_run_with_a_topology_equals_the_dcd_run(solvated, tmp_path):
     finally:
         sel.close()
     assert out["nc"] == out["dcd"] and np.all(np.frombuffer(out["nc"]["totals"]) > 0)
+    assert out["nc-tri"] == out["nc"]          # (an atom index and triclinic cells: the right-angled cells through the general geometry)
 
 
 def test_a_bad_frame_ends_the_run_and_a_repaired_file_completes_it(coil, tmp_path):

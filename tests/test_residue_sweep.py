@@ -130,7 +130,7 @@ def test_null_arguments_are_refused_and_the_table_is_zeroed():
 
 def test_new_code_does_not_reference_the_oracle():
     """(tests/test_capi.py::test_product_never_references_the_oracle keeps passing: the same scan over the files this adds to)"""
-    for rel in ("freesasa_amd/csrc/gpu_parse.hip", "freesasa_amd/csrc/gpu_drivers.hip", "freesasa_amd/csrc/gpu_sweep.hip", "freesasa_amd/csrc/gpu_ops.hip", "freesasa_amd/__init__.py"):
+    for rel in ("freesasa_amd/csrc/gpu_parse.hip", "freesasa_amd/csrc/gpu_drivers.hip", "freesasa_amd/csrc/gpu_frames.hip", "freesasa_amd/csrc/gpu_sweep.hip", "freesasa_amd/csrc/gpu_ops.hip", "freesasa_amd/__init__.py"):
         txt = open(os.path.join(ROOT, rel)).read()
         assert not re.search(r"#include\s+\"[^\"]*oracle|import\s+oracle|from\s+oracle|sasa_oracle|libsasa_emu", txt), rel
 

@@ -19,7 +19,7 @@ from test_dcd import write_dcd
 from test_dcd_gpu import ALGS, COMMANDS, F, FPB, OUTS, jittered, plain_run, solvated, topo_run  # noqa: F401  (solvated: a fixture)
 from test_pbc_gpu import patch_cells
 from test_pbc_tri_gpu import patch_records
-from test_xtc_gpu import boxes_nm, exact_triclinic
+from test_xtc_gpu import boxes_nm, exact_triclinic, indexed_periodic_runs_equal_the_dcd_run, solute_cells
 
 pytestmark = pytest.mark.gpu
 
@@ -138,9 +138,16 @@ def ortho_cells():
     return [(14.0 + 0.3 * f, 13.0, 12.5 - 0.1 * f) for f in range(F)]
 
 
-@pytest.mark.parametrize("alg, out_f32", [("lr20", False), ("sr100", True)])
+@pytest.mark.parametrize("alg, out_f32, indexed", [("lr20", False, False), ("sr100", True, False), ("lr20", False, True)],
+                         ids=["lr20-False", "sr100-True", "atom-index"])
 @PRECISIONS
-def test_periodic_orthorhombic_run_equals_the_dcd_run(tmp_path, double, alg, out_f32):
+def test_periodic_orthorhombic_run_equals_the_dcd_run(request, tmp_path, double, alg, out_f32, indexed):
+    if indexed:
+        b, full, index = request.getfixturevalue("solvated")
+        boxes, cells = boxes_nm(solute_cells(full, index))
+        trr, dcd = periodic_files(tmp_path, full, double, boxes)
+        patch_cells(dcd, cells)
+        return indexed_periodic_runs_equal_the_dcd_run(tmp_path, (b, full, index), dcd, trr, trr=True)
     frames, radii = coil()
     boxes, cells = boxes_nm(ortho_cells())
     trr, dcd = periodic_files(tmp_path, frames, double, boxes)

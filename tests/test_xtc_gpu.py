@@ -128,8 +128,42 @@ def ortho_cells():
     return [(14.0 + 0.3 * f, 13.0, 12.5 - 0.1 * f) for f in range(F)]
 
 
-@pytest.mark.parametrize("alg, out_f32", [("lr20", False), ("sr100", True)])
-def test_periodic_orthorhombic_run_equals_the_dcd_run(tmp_path, alg, out_f32):
+def solute_cells(full, index):
+    """right-angled cells for the solvated system's frames, another in every frame: 2 A short of the solute's extent (about 30 A, far
+    above c), so that the images of its outermost atoms lie among the atoms of the opposite face - with 4 A more than the extent
+    no image of 2jo4 reaches an atom (the solvent, which the index drops, may lie anywhere)"""
+    s = full[:, index].astype(np.float64).reshape(-1, 3)
+    ext = s.max(0) - s.min(0) - 2.0
+    return [(float(ext[0]) + 0.25 * f, float(ext[1]), float(ext[2]) + 0.125 * f) for f in range(len(full))]
+
+
+def indexed_periodic_runs_equal_the_dcd_run(tmp, system, dcd, path, **how):
+    """A periodic run WITH an atom index (the solvated system: a short last shard, two lanes) on a container file against the
+    DCD run of the same frames and cells: totals, areas, class sums, residues and selections byte for byte; the container's
+    run once more with its right-angled cells read as triclinic ones: the same files; and not the non-periodic run's"""
+    sel = ingest.Selection(COMMANDS)
+    try:
+        want, want_atoms = topo_run(tmp, "dcd-index", dcd, system, sel, False, dcd=True, pbc=True)
+        got, atoms = topo_run(tmp, "index", path, system, sel, False, pbc=True, **how)
+        tri, _ = topo_run(tmp, "index-tri", path, system, sel, False, pbc=True, triclinic=True, **how)
+        plain, _ = topo_run(tmp, "index-plain", path, system, sel, False, **how)
+    finally:
+        sel.close()
+    assert sorted(got) == sorted(OUTS[:5]) and got == want and tri == got and np.array_equal(atoms, want_atoms)
+    # images bury area and never add any; in cells this tight they bury some in every frame
+    assert np.all(np.frombuffer(plain["totals"]) > np.frombuffer(got["totals"])) and np.all(np.frombuffer(got["totals"]) > 0)
+
+
+@pytest.mark.parametrize("alg, out_f32, indexed", [("lr20", False, False), ("sr100", True, False), ("lr20", False, True)],
+                         ids=["lr20-False", "sr100-True", "atom-index"])
+def test_periodic_orthorhombic_run_equals_the_dcd_run(request, tmp_path, alg, out_f32, indexed):
+    if indexed:             # the only kind whose decoded fp32 frames lie inside c->g_xyz, behind the cells and the group records
+        b, full, index = request.getfixturevalue("solvated")
+        boxes, cells = boxes_nm(solute_cells(full, index))
+        decoded, _ = xtc_of(tmp_path / "frames.xtc", full, boxes=boxes)
+        write_dcd(tmp_path / "frames.dcd", decoded, cell=True)
+        patch_cells(tmp_path / "frames.dcd", cells)
+        return indexed_periodic_runs_equal_the_dcd_run(tmp_path, (b, decoded, index), tmp_path / "frames.dcd", tmp_path / "frames.xtc", xtc=True)
     frames, radii = coil(37)
     boxes, cells = boxes_nm(ortho_cells())
     decoded, _ = xtc_of(tmp_path / "frames.xtc", frames, boxes=boxes)
