@@ -145,6 +145,15 @@ def lib():
                                                            C.c_int, C.c_double, _dp, _dp, _dp, _dp, C.c_longlong, C.c_longlong,
                                                            C.c_longlong, _llp, _llp, _llp, _i32p, _i32p, _dp, _lp, _i32p, _dp, _lp,
                                                            _i32p, _i32p, _dp, C.c_int, C.c_char_p, C.c_int]
+        L.freesasa_gpu_interface_contacts_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _lp, C.c_int, C.c_void_p, _i32p,
+                                                          C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                          C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _llp, _llp, _llp, _llp,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.freesasa_gpu_calc_interface_contacts.argtypes = [_dp, _dp, _lp, C.c_int, _i32p, _i32p, C.c_int, C.c_double, C.c_int,
+                                                           _dp, _dp, _dp, _dp, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong,
+                                                           _llp, _llp, _llp, _llp, _i32p, _i32p, _dp, _lp, _i32p, _dp, _lp, _i32p, _i32p,
+                                                           _dp, C.POINTER(C.c_uint32), _i32p, C.c_int, C.c_char_p, C.c_int]
         L.freesasa_gpu_sr_volume_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _lp, C.c_int, C.c_double, C.c_int,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.freesasa_gpu_calc_volume.argtypes = [_dp, _dp, _lp, C.c_int, C.c_double, C.c_int, _dp, _ip, _dp, _dp, _dp, _dp,
@@ -402,6 +411,65 @@ def calc_interfaces(xyz, radii, offsets, group, n_groups, alg=LEE_RICHARDS, prob
     if ret:
         raise RuntimeError("freesasa_gpu_calc_interfaces: " + err.value.decode())
     return Interfaces(sasa, iso, totals, gt, ps, pg, areas, so, pa, pb)
+
+
+class InterfaceContacts(Interfaces):
+    """calc_interface_contacts()'s result: everything calc_interfaces(per_atom=True) gives, and the directed atom-atom contact
+    table over the M pair-structure atoms: contact_first [M + 1] (int64, the row range of every atom), contact_partner [C]
+    (int32, a pair-structure atom: pair_atom[j] is the input atom), contact_points [C] (int32), contact_area [C], buried_masks
+    [M, 4] (uint32: the test points the partner buries), n_contacts = C, n_buried_dots = D_b."""
+
+    def __init__(self, base, contact_first, contact_partner, contact_points, contact_area, buried_masks, n_buried_dots):
+        Interfaces.__init__(self, *base)
+        self.contact_first, self.contact_partner, self.contact_points = contact_first, contact_partner, contact_points
+        self.contact_area, self.buried_masks = contact_area, buried_masks
+        self.n_contacts, self.n_buried_dots = int(contact_partner.size), int(n_buried_dots)
+
+    def atom_rows(self, i):
+        """the rows of pair-structure atom i, as a slice into contact_partner, contact_points and contact_area"""
+        return slice(int(self.contact_first[i]), int(self.contact_first[i + 1]))
+
+    def side_rows(self, p, side):
+        """the rows of all atoms of side 0 (group g) or 1 (group h) of pair p, as a slice into the same arrays"""
+        q = 2 * p + side
+        return slice(int(self.contact_first[self.side_offsets[q]]), int(self.contact_first[self.side_offsets[q + 1]]))
+
+
+def calc_interface_contacts(xyz, radii, offsets, group, n_groups, probe=1.4, n_points=100, device=-1):
+    """freesasa_gpu_calc_interface_contacts() on host arrays -> InterfaceContacts: calc_interfaces() with Shrake-Rupley and, for
+    every pair-structure atom, which atoms of the partner bury its test points, how many, and the area they stand for
+    (include/freesasa_gpu.h).  Two calls: the counts, then the arrays."""
+    xyz, radii, offsets, group, n_groups = _group_batch(xyz, radii, offsets, group, n_groups)
+    n, ns = radii.size, offsets.size - 1
+    G = int(n_groups.astype(np.int64).sum())
+    i32, u32 = C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
+    Pc, Mc, Cc, Dc, err = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0), C.c_longlong(0), C.create_string_buffer(512)
+    sasa, iso, totals, gt = np.empty(n), np.empty(n), np.empty(ns), np.empty((max(G, 0), 3))
+
+    def call(P, M, Cn, arrays):
+        ps, pg, areas, so, pa, pb, cf, cp, cn, ca, bm = arrays
+        opt = lambda a, t: None if a is None else a.ctypes.data_as(t)
+        return lib().freesasa_gpu_calc_interface_contacts(xyz.ctypes.data_as(_dp), radii.ctypes.data_as(_dp), offsets.ctypes.data_as(_lp), ns,
+                                                          group.ctypes.data_as(i32), n_groups.ctypes.data_as(i32), SHRAKE_RUPLEY, probe,
+                                                          n_points, sasa.ctypes.data_as(_dp), iso.ctypes.data_as(_dp),
+                                                          totals.ctypes.data_as(_dp), gt.ctypes.data_as(_dp), P, M, Cn, 0, C.byref(Pc),
+                                                          C.byref(Mc), C.byref(Cc), C.byref(Dc), opt(ps, i32), opt(pg, i32),
+                                                          areas.ctypes.data_as(_dp), opt(so, _lp), opt(pa, i32), opt(pb, _dp), opt(cf, _lp),
+                                                          opt(cp, i32), opt(cn, i32), opt(ca, _dp), opt(bm, u32), None, device, err, 512)
+
+    pairs = interface_pairs(xyz, radii, offsets, group, n_groups, SHRAKE_RUPLEY, probe, n_points, device)
+    P, M = pairs.n_pairs, pairs.n_pair_atoms
+    areas = np.empty((P, 6))
+    if call(P, M, 0, (None, None, areas, None, None, None, None, None, None, None, None)):      # the counts: no contact array is asked for
+        raise RuntimeError("freesasa_gpu_calc_interface_contacts: " + err.value.decode())
+    Cn = int(Cc.value)
+    arrays = (np.empty(P, dtype=np.int32), np.empty((P, 2), dtype=np.int32), areas, np.empty(2 * P + 1, dtype=np.int64),
+              np.empty(M, dtype=np.int32), np.empty(M), np.empty(M + 1, dtype=np.int64), np.empty(Cn, dtype=np.int32),
+              np.empty(Cn, dtype=np.int32), np.empty(Cn), np.empty((M, 4), dtype=np.uint32))
+    if call(P, M, Cn, arrays):
+        raise RuntimeError("freesasa_gpu_calc_interface_contacts: " + err.value.decode())
+    ps, pg, areas, so, pa, pb, cf, cp, cn, ca, bm = arrays
+    return InterfaceContacts((sasa, iso, totals, gt, ps, pg, areas, so, pa, pb), cf, cp, cn, ca, bm, Dc.value)
 
 
 def calc_volume(xyz, radii, offsets, probe=1.4, n_points=100, device=-1, per_atom=False):
@@ -1911,6 +1979,29 @@ class GpuContext:
                                                      d_res_index or None, d_res_atoms or None, d_res_areas or None):
             raise RuntimeError("freesasa_gpu_interface_residues_dev: " + self.error())
         return int(P.value), int(M.value), int(R.value)
+
+    def interface_contacts(self, d_xyz, d_radii, offsets, d_group, n_groups, d_sasa, d_iso, pair_capacity, d_pair_areas,
+                           contact_capacity=0, d_contact_first=0, d_contact_partner=0, d_contact_points=0, d_contact_area=0,
+                           d_buried_masks=0, dot_capacity=0, d_dot_partner=0, d_pair_struct=0, d_pair_groups=0, atom_capacity=0,
+                           d_side_offsets=0, d_pair_atom=0, d_pair_buried=0, d_totals=0, d_group_totals=0, alg=SHRAKE_RUPLEY, probe=1.4,
+                           n_points=100):
+        """freesasa_gpu_interface_contacts_dev(): interfaces() with Shrake-Rupley and the atom-atom contact table -
+        d_contact_first [M + 1] and d_buried_masks [4 M] (device arrays that hold atom_capacity atoms), d_contact_partner,
+        d_contact_points, d_contact_area [C] (contact_capacity rows), d_dot_partner [D_b] (dot_capacity dots) ->
+        (n_pairs, n_pair_atoms, n_contacts, n_buried_dots); a capacity that is too small: RuntimeError naming the number."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        ng = np.ascontiguousarray(n_groups, dtype=np.int32)
+        P, M, Cn, D = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        if lib().freesasa_gpu_interface_contacts_dev(self._h, alg, d_xyz, d_radii, offsets.ctypes.data_as(_lp), offsets.size - 1, d_group,
+                                                     ng.ctypes.data_as(C.POINTER(C.c_int32)), probe, n_points, d_sasa or None, d_iso or None,
+                                                     d_totals or None, d_group_totals or None, pair_capacity, atom_capacity,
+                                                     contact_capacity, dot_capacity, C.byref(P), C.byref(M), C.byref(Cn), C.byref(D),
+                                                     d_pair_struct or None, d_pair_groups or None, d_pair_areas or None,
+                                                     d_side_offsets or None, d_pair_atom or None, d_pair_buried or None,
+                                                     d_contact_first or None, d_contact_partner or None, d_contact_points or None,
+                                                     d_contact_area or None, d_buried_masks or None, d_dot_partner or None):
+            raise RuntimeError("freesasa_gpu_interface_contacts_dev: " + self.error())
+        return int(P.value), int(M.value), int(Cn.value), int(D.value)
 
     def periodic(self, d_xyz, d_radii, offsets, cells, d_sasa, d_totals=0, alg=LEE_RICHARDS, probe=1.4, resolution=20):
         """freesasa_gpu_periodic_dev(): every atom's area among the periodic images of its structure's cell (cells: a host

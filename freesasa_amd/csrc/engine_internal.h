@@ -57,6 +57,7 @@
 #include "vol_kernels.h"
 #include "dots_kernels.h"
 #include "iface_kernels.h"
+#include "contact_kernels.h"
 #include "gpu_parse.h"
 
 /* ------------------------------------------------------------------ kernel launchers (gpu_kernels.hip) */
@@ -165,6 +166,11 @@ hipError_t kl_iface_finish(const sasa::IfaceArgs &a, hipStream_t st);
 hipError_t kl_iface_res_scan(int *a, int64_t n, int *scratch, hipStream_t st);
 hipError_t kl_iface_res_segments(const sasa::IfaceResArgs &a, int *scratch, hipStream_t st);
 hipError_t kl_iface_res_rows(const sasa::IfaceResArgs &a, int *scratch, hipStream_t st);
+/* ... their atom-atom contact tables (contact_kernels.h): the buried masks; the partner of every buried dot; the rows (count, rank,
+   the scan of the atoms' distinct partners - a.nd [M + 1], zeroed by the caller; scratch: ifr_scan_scratch(M) ints - and the write) */
+hipError_t kl_contact_masks(const sasa::ContactArgs &a, hipStream_t st);
+hipError_t kl_contact_attribute(const sasa::ContactArgs &a, hipStream_t st);
+hipError_t kl_contact_rows(const sasa::ContactArgs &a, int *scratch, hipStream_t st);
 
 /* ------------------------------------------------------------------ context (gpu_engine.hip) */
 
@@ -242,6 +248,9 @@ struct freesasa_gpu_ctx {
     DevBuf if_meta, if_box, if_cand, if_flag, if_sides, if_xyz, if_radii, if_comb, if_sasa, if_inpair, if_areas, if_patom, if_pburied, if_rows;
     /* ... their per-residue tables: the residue boundaries; the int32 work arrays; the segments' areas; the table itself */
     DevBuf if_rfirst, if_rwork, if_rsegs, if_rtable;
+    /* ... their atom-atom contact tables: the side, pair and buried masks with the two runs' areas; the atoms' int32 work arrays
+       and the flag; the buried dots (dot_first, points, atoms, point numbers, partners, counts, ranks); the table itself */
+    DevBuf if_cmasks, if_cwork, if_cdots, if_ctable;
     int dt_unit_n = 0; /* the point count whose unit points dt_unit holds (the expansion's; 0: none) */
     void *stage_in = nullptr, *stage_out = nullptr; /* page-locked host staging of freesasa_gpu_calc_batch_pipelined */
     size_t stage_in_cap = 0, stage_out_cap = 0;
@@ -407,6 +416,15 @@ const char *volume_bad_args(const void *xyz, const void *radii, const int64_t *o
 int masks_resident(freesasa_gpu_ctx *c, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
                    double probe, int n_points, const double *unit_points, double *d_sasa, int *d_counts, double *d_totals,
                    unsigned *d_masks);
+/* the scan of the masks' popcounts on the context's stream: dot_first [n_atoms + 1]; nothing is waited for */
+int dots_count_resident(freesasa_gpu_ctx *c, const unsigned *d_masks, int64_t n_atoms, int n_points, int64_t *d_dot_first);
+/* the unit points of n_points on the context's device (c->dt_unit): the expansion's one host allocation - callers run it BEFORE
+   they enqueue anything, so that a failure leaves nothing in flight */
+int dots_unit_ready(freesasa_gpu_ctx *c, int n_points);
+/* the expansion on the context's stream (dots_unit_ready first); nothing is waited for */
+int dots_expand_resident(freesasa_gpu_ctx *c, const double *d_xyz, const double *d_radii, int64_t n_atoms, double probe, int n_points,
+                         const unsigned *d_masks, const int64_t *d_dot_first, int64_t capacity, double *d_dot_xyz, int *d_dot_atom,
+                         int *d_dot_point);
 /* the arguments the mask entries check before a device is touched: 0, or the message */
 const char *masks_bad_args(const void *xyz, const void *radii, const int64_t *offsets, int n_structs, int n_points, const void *sasa, const void *masks);
 

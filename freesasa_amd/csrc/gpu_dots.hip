@@ -69,8 +69,9 @@ int masks_resident(freesasa_gpu_ctx *c, const double *d_xyz, const double *d_rad
     return run_batch(c, false, d_xyz, d_radii, offsets, n_structs, probe, n_points, unit_points, d_sasa, d_counts, d_totals);
 }
 
-/* the scan on the context's stream: dot_first [n_atoms + 1] from the masks; nothing is waited for */
-static int dots_count_resident(freesasa_gpu_ctx *c, const unsigned *d_masks, int64_t n_atoms, int n_points, int64_t *d_dot_first)
+/* the scan on the context's stream: dot_first [n_atoms + 1] from the masks; nothing is waited for (engine_internal.h: the
+   interfaces' contact tables run scan and expansion too) */
+int dots_count_resident(freesasa_gpu_ctx *c, const unsigned *d_masks, int64_t n_atoms, int n_points, int64_t *d_dot_first)
 {
     DotsArgs a;
     memset(&a, 0, sizeof a);
@@ -83,7 +84,7 @@ static int dots_count_resident(freesasa_gpu_ctx *c, const unsigned *d_masks, int
 
 /* the unit points of n_points on the context's device (c->dt_unit), made and copied where it does not hold them yet.  It is
    the expansion's one host allocation: callers run it BEFORE they enqueue anything, so that a failure leaves nothing in flight. */
-static int dots_unit_ready(freesasa_gpu_ctx *c, int n_points)
+int dots_unit_ready(freesasa_gpu_ctx *c, int n_points)
 {
     if (c->dt_unit_n == n_points) return 0;
     std::vector<double> u(3 * (size_t)n_points);
@@ -96,7 +97,7 @@ static int dots_unit_ready(freesasa_gpu_ctx *c, int n_points)
 }
 
 /* the expansion on the context's stream (dots_unit_ready first); nothing is waited for */
-static int dots_expand_resident(freesasa_gpu_ctx *c, const double *d_xyz, const double *d_radii, int64_t n_atoms, double probe, int n_points,
+int dots_expand_resident(freesasa_gpu_ctx *c, const double *d_xyz, const double *d_radii, int64_t n_atoms, double probe, int n_points,
                                 const unsigned *d_masks, const int64_t *d_dot_first, int64_t capacity, double *d_dot_xyz, int *d_dot_atom,
                                 int *d_dot_point)
 {

@@ -1,8 +1,9 @@
 /*
  * gpu_interfaces.hip — pairwise interface areas between chain groups (include/freesasa_gpu.h: freesasa_gpu_interface_pairs_dev,
  * freesasa_gpu_interfaces_dev, freesasa_gpu_calc_interface_pairs, freesasa_gpu_calc_interfaces) and their per-residue tables
- * (freesasa_gpu_interface_residues_dev, freesasa_gpu_calc_interface_residues).  Host code; the kernels are in gpu_kernels.hip
- * (phase functions: iface_kernels.h).
+ * (freesasa_gpu_interface_residues_dev, freesasa_gpu_calc_interface_residues) and atom-atom contact tables
+ * (freesasa_gpu_interface_contacts_dev, freesasa_gpu_calc_interface_contacts).  Host code; the kernels are in gpu_kernels.hip
+ * (phase functions: iface_kernels.h, contact_kernels.h).
  *
  *   1. groups_resident   the chain-group pipeline as it is: the combined batch stays in c->g_xyz / g_radii / g_src, its areas in
  *                        c->g_sasa, its totals in c->g_tot; the groups' atom counts are on the host
@@ -23,6 +24,15 @@
  *   9. residues          iface_residues: k_iface_res_head, the block scan, k_iface_res_first, k_iface_res_segment, the scan again,
  *                        k_iface_res_rows; R comes back (one more stream synchronization); the table stays in c->if_rtable
  * and hold the three capacities against P, M and R together, once R is known (iface_res_check_caps), before anything is delivered.
+ *
+ * The contact entries (freesasa_gpu_interface_contacts_dev, freesasa_gpu_calc_interface_contacts; Shrake-Rupley only; phase
+ * functions: contact_kernels.h) likewise run iface_pipeline as it is and one more stage behind it:
+ *  10. contacts          iface_contacts: two more engine runs over the M pair-structure atoms with the mask request (masks_resident:
+ *                        as the P pair structures, as the 2 P sides), k_contact_masks, the dots' scan - D_b comes back (one stream
+ *                        synchronization) and sizes what follows - the dots' expansion, k_contact_attribute, k_contact_rows_count /
+ *                        _rank, the block scan, k_contact_rows_write; C and the flag come back (one more); the table stays in
+ *                        c->if_ctable, the masks in c->if_cmasks, the dots in c->if_cdots
+ * and hold the four capacities against P, M, C and D_b together (iface_contact_check_caps) before anything is delivered.
  */
 #include <hip/hip_runtime.h>
 
@@ -318,6 +328,105 @@ int iface_res_check_caps(freesasa_gpu_ctx *c, const IfacePlan &pl, const IfaceWa
     return 0;
 }
 
+/* the atom-atom contact tables: what an entry gives on top of the interface entries' arguments, and what it wants back */
+struct IfaceContactWant {
+    long long contact_capacity = 0, dot_capacity = 0;
+    long long *n_contacts_out = nullptr, *n_buried_dots_out = nullptr;
+    bool rows = false; /* one of contact_partner, contact_points, contact_area */
+    bool dots = false; /* dot_partner */
+};
+/* ... checked before a device is touched, behind iface_bad_args and iface_bad_caps: 0, or the message in msg */
+int iface_contact_bad_args(const IfaceContactWant &cw, int alg, int resolution, const void *masks, char *msg, size_t len)
+{
+    if (!cw.n_contacts_out) { snprintf(msg, len, "null argument"); return -1; }
+    if (alg != 1) { snprintf(msg, len, "the contact tables are made of Shrake-Rupley test points: Lee-Richards has none"); return -1; }
+    if (resolution > SR_CAP_POINTS_MAX) {
+        snprintf(msg, len, "the contact tables are offered up to %d test points (%d asked for)", SR_CAP_POINTS_MAX, resolution);
+        return -1;
+    }
+    if (cw.contact_capacity < 0) { snprintf(msg, len, "contact_capacity must be >= 0 (it is %lld)", cw.contact_capacity); return -1; }
+    if (cw.dot_capacity < 0) { snprintf(msg, len, "dot_capacity must be >= 0 (it is %lld)", cw.dot_capacity); return -1; }
+    if ((uintptr_t)masks % 16) { snprintf(msg, len, "the buried mask array must be aligned to 16 bytes (an atom's four words are one store)"); return -1; }
+    return 0;
+}
+
+/* the stage behind iface_pipeline (Shrake-Rupley; k_iface_finish is the last thing on the stream): the table in c->if_ctable -
+   contact_first [M + 1] | contact_area [D_b] | contact_partner [D_b] | contact_points [D_b], C rows of them used -, the buried masks
+   in c->if_cmasks, the dots' partners in c->if_cdots.  D_b, then C and the flag come back to the host (two stream
+   synchronizations), so at the stage's end the stream is idle. */
+struct IfaceContactTable {
+    int64_t C = 0, D = 0;
+    const int64_t *first = nullptr;
+    const int32_t *partner = nullptr, *points = nullptr, *dot_partner = nullptr;
+    const double *area = nullptr;
+    const unsigned *buried = nullptr;
+};
+int iface_contacts(freesasa_gpu_ctx *c, const IfacePlan &pl, double probe, int n_points, IfaceContactTable &t)
+{
+    t = IfaceContactTable();
+    if (pl.P == 0) return 0;
+    const size_t P = (size_t)pl.P, M = (size_t)pl.M;
+    const size_t S = (size_t)ifr_scan_scratch(pl.M);
+    hipStream_t st = c->stream;
+    /* side masks | pair masks | buried masks (16 M bytes each) | the two runs' areas [M] (nobody reads them) */
+    if (ensure(c, c->if_cmasks, 48 * M + 8 * M) || ensure(c, c->if_cwork, 8 * (M + 1) + 4 * (M + 1 + S + 1)) || dots_unit_ready(c, n_points))
+        return -1;
+    unsigned *side_masks = (unsigned *)c->if_cmasks.p, *pair_masks = side_masks + SR_CAP_WORDS * M, *buried = pair_masks + SR_CAP_WORDS * M;
+    double *areas = (double *)(buried + SR_CAP_WORDS * M);
+    int64_t *dot_first = (int64_t *)c->if_cwork.p;
+    int *nd = (int *)(dot_first + M + 1), *scratch = nd + M + 1, *flag = scratch + S;
+    const double *pxyz = (const double *)c->if_xyz.p, *pradii = (const double *)c->if_radii.p;
+    /* the same atoms as P structures and as 2 P: what the pair run and the groups' run of the pipeline counted, as masks */
+    if (masks_resident(c, pxyz, pradii, pl.pair_off.data(), (int)P, probe, n_points, pl.tp.data(), areas, nullptr, nullptr, pair_masks) ||
+        masks_resident(c, pxyz, pradii, pl.side_off.data(), (int)(2 * P), probe, n_points, pl.tp.data(), areas, nullptr, nullptr, side_masks))
+        return -1;
+    ContactArgs a;
+    memset(&a, 0, sizeof a);
+    a.n_pair_atoms = pl.M; a.n_sides = 2 * pl.P; a.n_points = n_points; a.probe = probe;
+    a.side_off = (const int64_t *)c->if_sides.p; a.pxyz = pxyz; a.pradii = pradii;
+    a.side_masks = side_masks; a.pair_masks = pair_masks; a.buried = buried;
+    a.dot_first = dot_first; a.nd = nd; a.flag = flag;
+    HIP_TRY(c, kl_contact_masks(a, st));
+    if (dots_count_resident(c, buried, pl.M, n_points, dot_first)) return -1;
+    int64_t D = 0;
+    HIP_TRY(c, hipMemcpyAsync(&D, dot_first + M, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    t.D = D; t.buried = buried;
+    if (D > 0x7fffffffLL) return ctx_fail(c, "the interfaces bury %lld test points: a call takes up to 2^31 - 1", (long long)D);
+    if (D == 0) return 0; /* (no buried point: no row) */
+    const size_t Db = (size_t)D;
+    if (ensure(c, c->if_cdots, 24 * Db + 4 * 5 * Db) || ensure(c, c->if_ctable, 8 * (M + 1) + 8 * Db + 4 * 2 * Db)) return -1;
+    double *dot_xyz = (double *)c->if_cdots.p;
+    int *dot_atom = (int *)(dot_xyz + 3 * Db), *dot_point = dot_atom + Db;
+    a.n_dots = D; a.dot_xyz = dot_xyz; a.dot_atom = dot_atom; a.dot_partner = dot_point + Db; a.cnt = a.dot_partner + Db; a.rank = a.cnt + Db;
+    a.contact_first = (int64_t *)c->if_ctable.p; a.contact_area = (double *)(a.contact_first + M + 1);
+    a.contact_partner = (int *)(a.contact_area + Db); a.contact_points = a.contact_partner + Db;
+    HIP_TRY(c, hipMemsetAsync(nd, 0, 4 * (M + 1 + S + 1), st)); /* (the atoms' counts, the scan's levels, the flag) */
+    if (dots_expand_resident(c, pxyz, pradii, pl.M, probe, n_points, buried, dot_first, D, dot_xyz, dot_atom, dot_point)) return -1;
+    HIP_TRY(c, kl_contact_attribute(a, st));
+    HIP_TRY(c, kl_contact_rows(a, scratch, st));
+    int back[2] = {0, 0}; /* C, the flag */
+    HIP_TRY(c, hipMemcpyAsync(&back[0], nd + M, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&back[1], flag, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (back[1] != 0)
+        return ctx_fail(c, "pair-structure atom %d has a buried test point that no atom of the other side covers: the exposure masks and the cover test disagree",
+                        back[1] - 1);
+    t.C = back[0]; t.first = a.contact_first; t.partner = a.contact_partner; t.points = a.contact_points; t.area = a.contact_area;
+    t.dot_partner = a.dot_partner;
+    return 0;
+}
+/* the four capacities against P, M, C and D_b, in this order, with the interface entries' messages for the first two */
+int iface_contact_check_caps(freesasa_gpu_ctx *c, const IfacePlan &pl, const IfaceWant &w, const IfaceContactWant &cw, const IfaceContactTable &t)
+{
+    if (iface_check_caps(c, pl, w)) return -1;
+    if (cw.rows && t.C > cw.contact_capacity)
+        return ctx_fail(c, "contact_capacity %lld is too small: the interfaces have %lld contact rows", cw.contact_capacity, (long long)t.C);
+    if (cw.dots && t.D > cw.dot_capacity)
+        return ctx_fail(c, "dot_capacity %lld is too small: the interfaces bury %lld test points", cw.dot_capacity, (long long)t.D);
+    return 0;
+}
+
 int iface_dev_checks(freesasa_gpu_ctx *c, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
                      const int32_t *d_group, const int32_t *n_groups, int alg, int resolution, long long pair_capacity, long long atom_capacity)
 {
@@ -462,19 +571,93 @@ extern "C" int freesasa_gpu_interface_residues_dev(freesasa_gpu_ctx *c, int alg,
     });
 }
 
+extern "C" int freesasa_gpu_interface_contacts_dev(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii,
+                                                   const int64_t *offsets, int n_structs, const int32_t *d_group, const int32_t *n_groups,
+                                                   double probe_radius, int resolution, double *d_sasa, double *d_iso, double *d_totals,
+                                                   double *d_group_totals, long long pair_capacity, long long atom_capacity,
+                                                   long long contact_capacity, long long dot_capacity, long long *n_pairs_out,
+                                                   long long *n_pair_atoms_out, long long *n_contacts_out, long long *n_buried_dots_out,
+                                                   int32_t *d_pair_struct, int32_t *d_pair_groups, double *d_pair_areas,
+                                                   int64_t *d_side_offsets, int32_t *d_pair_atom, double *d_pair_buried,
+                                                   int64_t *d_contact_first, int32_t *d_contact_partner, int32_t *d_contact_points,
+                                                   double *d_contact_area, uint32_t *d_buried_masks, int32_t *d_dot_partner)
+{
+    if (!c) return -1;
+    if (freesasa_gpu_wait(c)) return -1;
+    return guarded_ctx(c, [&]() -> int {
+        char msg[200];
+        c->err[0] = 0;
+        IfaceContactWant cw;
+        cw.contact_capacity = contact_capacity; cw.dot_capacity = dot_capacity; cw.n_contacts_out = n_contacts_out; cw.n_buried_dots_out = n_buried_dots_out;
+        cw.rows = d_contact_partner || d_contact_points || d_contact_area; cw.dots = d_dot_partner != nullptr;
+        if (iface_bad_args(d_xyz, d_radii, offsets, n_structs, d_group, n_groups, alg, resolution, msg, sizeof msg) ||
+            iface_bad_caps(pair_capacity, atom_capacity, msg, sizeof msg) || iface_contact_bad_args(cw, alg, resolution, d_buried_masks, msg, sizeof msg))
+            return ctx_fail(c, "%s", msg);
+        if (iface_dev_checks(c, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, alg, resolution, pair_capacity, atom_capacity)) return -1;
+        if (!d_sasa || !d_iso || !n_pairs_out || !n_pair_atoms_out || !d_pair_areas) return ctx_fail(c, "null argument");
+        IfacePlan pl; /* (the plan holds the sources of copies enqueued below: it lives until the stream is idle) */
+        IfaceContactTable t;
+        IfaceWant w, none; /* (the pipeline holds no capacity against its counts here: the four are held together, once C and D_b are known) */
+        w.pair_capacity = pair_capacity; w.atom_capacity = atom_capacity; w.rows = true;
+        w.atoms = d_pair_atom || d_pair_buried || d_contact_first || d_buried_masks;
+        int rc = [&]() -> int {
+            if (iface_pipeline(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe_radius, resolution, d_sasa, d_iso,
+                               d_totals, d_group_totals, none, pl, n_pairs_out, n_pair_atoms_out) ||
+                iface_contacts(c, pl, probe_radius, resolution, t))
+                return -1;
+            *n_contacts_out = t.C;
+            if (n_buried_dots_out) *n_buried_dots_out = t.D;
+            if (iface_contact_check_caps(c, pl, w, cw, t)) return -1;
+            const size_t P = (size_t)pl.P, M = (size_t)pl.M, Cn = (size_t)t.C, D = (size_t)t.D;
+            hipStream_t st = c->stream;
+            if (d_side_offsets) HIP_TRY(c, hipMemcpyAsync(d_side_offsets, pl.side_off.data(), 8 * (2 * P + 1), hipMemcpyHostToDevice, st));
+            if (P == 0) {
+                if (d_contact_first) HIP_TRY(c, hipMemsetAsync(d_contact_first, 0, 8, st));
+                return 0;
+            }
+            if (d_pair_struct) HIP_TRY(c, hipMemcpyAsync(d_pair_struct, pl.pair_struct.data(), 4 * P, hipMemcpyHostToDevice, st));
+            if (d_pair_groups) HIP_TRY(c, hipMemcpyAsync(d_pair_groups, pl.pair_groups.data(), 8 * P, hipMemcpyHostToDevice, st));
+            HIP_TRY(c, hipMemcpyAsync(d_pair_areas, c->if_areas.p, 48 * P, hipMemcpyDeviceToDevice, st));
+            if (d_pair_atom) HIP_TRY(c, hipMemcpyAsync(d_pair_atom, c->if_patom.p, 4 * M, hipMemcpyDeviceToDevice, st));
+            if (d_pair_buried) HIP_TRY(c, hipMemcpyAsync(d_pair_buried, c->if_pburied.p, 8 * M, hipMemcpyDeviceToDevice, st));
+            if (d_buried_masks) HIP_TRY(c, hipMemcpyAsync(d_buried_masks, t.buried, 4 * SR_CAP_WORDS * M, hipMemcpyDeviceToDevice, st));
+            if (D == 0) {
+                if (d_contact_first) HIP_TRY(c, hipMemsetAsync(d_contact_first, 0, 8 * (M + 1), st));
+                return 0;
+            }
+            if (d_contact_first) HIP_TRY(c, hipMemcpyAsync(d_contact_first, t.first, 8 * (M + 1), hipMemcpyDeviceToDevice, st));
+            if (d_contact_partner) HIP_TRY(c, hipMemcpyAsync(d_contact_partner, t.partner, 4 * Cn, hipMemcpyDeviceToDevice, st));
+            if (d_contact_points) HIP_TRY(c, hipMemcpyAsync(d_contact_points, t.points, 4 * Cn, hipMemcpyDeviceToDevice, st));
+            if (d_contact_area) HIP_TRY(c, hipMemcpyAsync(d_contact_area, t.area, 8 * Cn, hipMemcpyDeviceToDevice, st));
+            if (d_dot_partner) HIP_TRY(c, hipMemcpyAsync(d_dot_partner, t.dot_partner, 4 * D, hipMemcpyDeviceToDevice, st));
+            return 0;
+        }();
+        if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = ctx_fail(c, "stream synchronize failed"); /* (the call is synchronous) */
+        return rc;
+    });
+}
+
 /* the host-pointer entries: the batch as one chunk of the host-batch path, in place, as freesasa_gpu_calc_groups has it */
+struct IfaceContactHost { /* the contact entry's host arrays: any may be null */
+    int64_t *first = nullptr;
+    int32_t *partner = nullptr, *points = nullptr, *dot_partner = nullptr;
+    double *area = nullptr;
+    uint32_t *buried = nullptr;
+};
 static int iface_host(const double *xyz, const double *radii, const int64_t *offsets, int n_structs, const int32_t *group,
                       const int32_t *n_groups, int alg, double probe, int resolution, double *sasa_out, double *iso_out, double *totals_out,
                       double *group_totals_out, bool whole, long long pair_capacity, long long atom_capacity, long long *n_pairs_out,
                       long long *n_pair_atoms_out, int32_t *pair_struct_out, int32_t *pair_groups_out, double *pair_areas_out,
                       int64_t *side_offsets_out, int32_t *pair_atom_out, double *pair_buried_out, long long *stats_out, int device,
                       char *err_out, int err_len, const IfaceResWant *rw = nullptr, int64_t *res_offsets_out = nullptr,
-                      int32_t *res_index_out = nullptr, int32_t *res_atoms_out = nullptr, double *res_areas_out = nullptr)
+                      int32_t *res_index_out = nullptr, int32_t *res_atoms_out = nullptr, double *res_areas_out = nullptr,
+                      const IfaceContactWant *cw = nullptr, const IfaceContactHost *co = nullptr)
 {
     if (err_out && err_len > 0) err_out[0] = 0;
     char msg[200];
     if (iface_bad_args(xyz, radii, offsets, n_structs, group, n_groups, alg, resolution, msg, sizeof msg) ||
-        iface_bad_caps(pair_capacity, atom_capacity, msg, sizeof msg) || (rw && iface_res_bad_args(*rw, offsets, n_structs, msg, sizeof msg)))
+        iface_bad_caps(pair_capacity, atom_capacity, msg, sizeof msg) || (rw && iface_res_bad_args(*rw, offsets, n_structs, msg, sizeof msg)) ||
+        (cw && iface_contact_bad_args(*cw, alg, resolution, nullptr, msg, sizeof msg)))
         return set_err(err_out, err_len, msg);
     if (!n_pairs_out || !n_pair_atoms_out || (whole && !pair_areas_out) || (rw && !res_areas_out)) return set_err(err_out, err_len, "null argument");
     if (freesasa_gpu_device_count() <= 0)
@@ -482,6 +665,7 @@ static int iface_host(const double *xyz, const double *radii, const int64_t *off
     return guarded(err_out, err_len, [&]() -> int {
     IfacePlan pl; /* (declared before the lease: freed after its stream is idle) */
     IfaceResTable t;
+    IfaceContactTable ct;
     PoolLease lease(device);
     freesasa_gpu_ctx *c = lease.c;
     if (!c) return set_err(err_out, err_len, "could not create a GPU context");
@@ -506,11 +690,17 @@ static int iface_host(const double *xyz, const double *radii, const int64_t *off
         IfaceWant w;
         w.pair_capacity = pair_capacity; w.atom_capacity = atom_capacity;
         if (whole) {
-            w.rows = true; w.atoms = pair_atom_out || pair_buried_out;
-            /* (with residues the pipeline holds no capacity itself: the three are held together, once R is known) */
+            w.rows = true; w.atoms = pair_atom_out || pair_buried_out || (co && (co->first || co->buried));
+            /* (with residues or contacts the pipeline holds no capacity itself: all are held together, once R or C and D_b are known) */
             if (iface_pipeline(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe, resolution, d_sasa, d_iso, d_tot, d_gtot,
-                               rw ? IfaceWant() : w, pl, n_pairs_out, n_pair_atoms_out))
+                               rw || cw ? IfaceWant() : w, pl, n_pairs_out, n_pair_atoms_out))
                 return -1;
+            if (cw) {
+                if (iface_contacts(c, pl, probe, resolution, ct)) return -1;
+                *cw->n_contacts_out = ct.C;
+                if (cw->n_buried_dots_out) *cw->n_buried_dots_out = ct.D;
+                if (iface_contact_check_caps(c, pl, w, *cw, ct)) return -1;
+            }
             if (rw) {
                 if (iface_residues(c, pl, *rw, d_iso, t)) return -1;
                 *rw->n_res_rows_out = t.R;
@@ -532,6 +722,18 @@ static int iface_host(const double *xyz, const double *radii, const int64_t *off
              (R > 0 && res_atoms_out && hipMemcpyAsync(res_atoms_out, t.atoms, 4 * R, hipMemcpyDeviceToHost, st) != hipSuccess) ||
              (R > 0 && hipMemcpyAsync(res_areas_out, t.areas, 24 * R, hipMemcpyDeviceToHost, st) != hipSuccess)))
             return ctx_fail(c, "device-to-host copy failed");
+        if (cw && co) {
+            const size_t Cn = (size_t)ct.C, D = (size_t)ct.D;
+            if (co->first && (P == 0 || D == 0)) memset(co->first, 0, 8 * (P == 0 ? 1 : M + 1));
+            if (P > 0 &&
+                ((co->buried && hipMemcpyAsync(co->buried, ct.buried, 4 * SR_CAP_WORDS * M, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+                 (D > 0 && co->first && hipMemcpyAsync(co->first, ct.first, 8 * (M + 1), hipMemcpyDeviceToHost, st) != hipSuccess) ||
+                 (Cn > 0 && co->partner && hipMemcpyAsync(co->partner, ct.partner, 4 * Cn, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+                 (Cn > 0 && co->points && hipMemcpyAsync(co->points, ct.points, 4 * Cn, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+                 (Cn > 0 && co->area && hipMemcpyAsync(co->area, ct.area, 8 * Cn, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+                 (D > 0 && co->dot_partner && hipMemcpyAsync(co->dot_partner, ct.dot_partner, 4 * D, hipMemcpyDeviceToHost, st) != hipSuccess)))
+                return ctx_fail(c, "device-to-host copy failed");
+        }
         if ((sasa_out && hipMemcpyAsync(sasa_out, d_sasa, 8 * n, hipMemcpyDeviceToHost, st) != hipSuccess) ||
             (iso_out && hipMemcpyAsync(iso_out, d_iso, 8 * n, hipMemcpyDeviceToHost, st) != hipSuccess) ||
             (totals_out && hipMemcpyAsync(totals_out, d_tot, 8 * (size_t)n_structs, hipMemcpyDeviceToHost, st) != hipSuccess) ||
@@ -590,4 +792,28 @@ extern "C" int freesasa_gpu_calc_interface_residues(const double *xyz, const dou
                       group_totals_out, true, pair_capacity, atom_capacity, n_pairs_out, n_pair_atoms_out, pair_struct_out, pair_groups_out,
                       pair_areas_out, side_offsets_out, pair_atom_out, pair_buried_out, nullptr, device, err_out, err_len, &rw,
                       res_offsets_out, res_index_out, res_atoms_out, res_areas_out);
+}
+
+extern "C" int freesasa_gpu_calc_interface_contacts(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
+                                                    const int32_t *group, const int32_t *n_groups, int alg, double probe_radius,
+                                                    int resolution, double *sasa_out, double *iso_out, double *totals_out,
+                                                    double *group_totals_out, long long pair_capacity, long long atom_capacity,
+                                                    long long contact_capacity, long long dot_capacity, long long *n_pairs_out,
+                                                    long long *n_pair_atoms_out, long long *n_contacts_out, long long *n_buried_dots_out,
+                                                    int32_t *pair_struct_out, int32_t *pair_groups_out, double *pair_areas_out,
+                                                    int64_t *side_offsets_out, int32_t *pair_atom_out, double *pair_buried_out,
+                                                    int64_t *contact_first_out, int32_t *contact_partner_out, int32_t *contact_points_out,
+                                                    double *contact_area_out, uint32_t *buried_masks_out, int32_t *dot_partner_out,
+                                                    int device, char *err_out, int err_len)
+{
+    IfaceContactWant cw;
+    cw.contact_capacity = contact_capacity; cw.dot_capacity = dot_capacity; cw.n_contacts_out = n_contacts_out; cw.n_buried_dots_out = n_buried_dots_out;
+    cw.rows = contact_partner_out || contact_points_out || contact_area_out; cw.dots = dot_partner_out != nullptr;
+    IfaceContactHost co;
+    co.first = contact_first_out; co.partner = contact_partner_out; co.points = contact_points_out; co.area = contact_area_out;
+    co.buried = buried_masks_out; co.dot_partner = dot_partner_out;
+    return iface_host(xyz, radii, offsets, n_structs, group, n_groups, alg, probe_radius, resolution, sasa_out, iso_out, totals_out,
+                      group_totals_out, true, pair_capacity, atom_capacity, n_pairs_out, n_pair_atoms_out, pair_struct_out, pair_groups_out,
+                      pair_areas_out, side_offsets_out, pair_atom_out, pair_buried_out, nullptr, device, err_out, err_len, nullptr, nullptr,
+                      nullptr, nullptr, nullptr, &cw, &co);
 }

@@ -1417,6 +1417,55 @@ hipError_t kl_iface_res_rows(const IfaceResArgs &a, int *scratch, hipStream_t st
     return hipGetLastError();
 }
 
+/* ... their atom-atom contact tables (contact_kernels.h): the buried masks (one thread per pair-structure atom); the partner of
+   every buried dot (a workgroup per CT_B dots); the rows (one thread per dot, and per atom for contact_first) */
+__global__ __launch_bounds__(CT_B) void k_contact_masks(ContactArgs a)
+{
+    contact_masks(a, (int64_t)blockIdx.x * CT_B + threadIdx.x);
+}
+__global__ __launch_bounds__(CT_B) void k_contact_attribute(ContactArgs a)
+{
+    __shared__ ContactLds m;
+    contact_attribute(a, m, (int64_t)blockIdx.x, threadIdx.x);
+}
+__global__ __launch_bounds__(CT_B) void k_contact_rows_count(ContactArgs a)
+{
+    contact_rows_count(a, (int64_t)blockIdx.x * CT_B + threadIdx.x);
+}
+__global__ __launch_bounds__(CT_B) void k_contact_rows_rank(ContactArgs a)
+{
+    contact_rows_rank(a, (int64_t)blockIdx.x * CT_B + threadIdx.x);
+}
+__global__ __launch_bounds__(CT_B) void k_contact_rows_write(ContactArgs a)
+{
+    contact_rows_write(a, (int64_t)blockIdx.x * CT_B + threadIdx.x);
+}
+hipError_t kl_contact_masks(const ContactArgs &a, hipStream_t st)
+{
+    if (a.n_pair_atoms == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_contact_masks, dim3((unsigned)((a.n_pair_atoms + CT_B - 1) / CT_B)), dim3(CT_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_contact_attribute(const ContactArgs &a, hipStream_t st)
+{
+    if (a.n_dots == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_contact_attribute, dim3((unsigned)((a.n_dots + CT_B - 1) / CT_B)), dim3(CT_B), 0, st, a);
+    return hipGetLastError();
+}
+/* a.nd [M + 1] zeroed by the caller; scratch: ifr_scan_scratch(M) ints */
+hipError_t kl_contact_rows(const ContactArgs &a, int *scratch, hipStream_t st)
+{
+    if (a.n_dots == 0) return hipSuccess;
+    const dim3 grid((unsigned)((a.n_dots + CT_B - 1) / CT_B));
+    const int64_t n = a.n_dots > a.n_pair_atoms + 1 ? a.n_dots : a.n_pair_atoms + 1;
+    hipLaunchKernelGGL(k_contact_rows_count, grid, dim3(CT_B), 0, st, a);
+    hipLaunchKernelGGL(k_contact_rows_rank, grid, dim3(CT_B), 0, st, a);
+    hipError_t e = kl_iface_res_scan(a.nd, a.n_pair_atoms, scratch, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_contact_rows_write, dim3((unsigned)((n + CT_B - 1) / CT_B)), dim3(CT_B), 0, st, a);
+    return hipGetLastError();
+}
+
 void kl_dump_phase_clocks(void)
 {
 #ifdef SASA_PHASE_TIMING

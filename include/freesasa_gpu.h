@@ -1194,6 +1194,73 @@ int freesasa_gpu_calc_interface_residues(const double *xyz, const double *radii,
                                          int64_t *res_offsets_out, int32_t *res_index_out, int32_t *res_atoms_out,
                                          double *res_areas_out, int device, char *err_out, int err_len);
 
+/* ATOM-ATOM CONTACT TABLES: what is in contact with what across every interface above - which atom of the partner buries which
+   atom, and how much area each such pair accounts for: the contact map of an interface analysis.  Made on the device behind
+   the interface pipeline from Shrake-Rupley exposure masks (csrc/contact_kernels.h; tests/interface_contacts_ref.py restates
+   the definitions in numpy).  Shrake-Rupley only; fp64, every operation rounded on its own.
+   Input: that of freesasa_gpu_interfaces_dev with alg = 1; N = resolution <= 128 test points u_k = freesasa_gpu_test_points(N);
+     R_i = r_i + probe.  Everything of the interface definition stays: the pair table, side_offsets, pair_atom, pair_buried and
+     their bytes.  Pair-structure atom i (0 <= i < M) lies on one side of one pair structure p = (g, h).
+   Masks (as freesasa_gpu_sr_masks_dev makes them).  side_mask_i: atom i's exposure mask with its side taken as a structure of
+     its own (the bits behind d_iso); pair_mask_i: its mask in the pair structure (the bits behind in_pair_*).
+     buried_mask_i = side_mask_i & ~pair_mask_i over the N bits that exist: the test points the partner buries; bits at or above
+     N are 0; its popcount is counts_side_i - counts_pair_i.
+   Test point of set bit k: per component t = u_k * R_i; t += x_i (the engine's own, as the surface dots have it).
+   Cover.  Atom j of the OTHER side of the same pair covers the point iff dx * dx + dy * dy + dz * dz <= R_j * R_j, dx = t_x - x_j
+     and so on (the reference's operand order, src/sasa_sr.c:321-324).
+   Partner.  The covering j with the smallest w = (dx * dx + dy * dy + dz * dz) - R_j * R_j: the deepest penetration; among equal
+     w the smallest pair-structure index.  By the definition of the two masks a cover exists; if the device finds none the call
+     fails with a message that names the pair-structure atom - it never invents a partner.
+   Rows.  One row per (i, j) with at least one point, ordered by i ascending over all M atoms, then j ascending:
+     contact_first [M + 1] (int64)  the exclusive prefix of the rows per atom; C = contact_first[M]
+     contact_partner [C] (int32)    j, a pair-structure atom index: pair_atom[j] is the input atom
+     contact_points [C] (int32)     n, the number of i's buried points whose partner is j
+     contact_area [C] (fp64)        (4.0 * PI * R_i * R_i * n) / N, the reference's expression (src/sasa_sr.c:337)
+     The table is directed: row (i -> j) lies in i's run, row (j -> i) in j's; they generally differ, nothing symmetrises them.
+   Optional: buried_masks [M][4] (uint32, 16-byte aligned; freesasa_gpu_dots_from_masks draws the interface patch from it with
+     the pair-structure atoms' coordinates) and dot_partner [D_b] (int32): the partner of every buried point in dot order (atom
+     ascending, point ascending); D_b = the buried points of all atoms.
+   Capacities.  As above: pair_capacity and atom_capacity (contact_first: atom_capacity + 1 entries; buried_masks: 4 words an
+     atom), contact_capacity in rows, dot_capacity in dots.  The four counts are set first, then the capacities are held against
+     P, M, C and D_b in this order; one that is too small fails with a message that names the number - "contact_capacity %lld is
+     too small: the interfaces have %lld contact rows" - before any of the caller's arrays is written.  A NULL array is not
+     delivered and its capacity not looked at.  C <= D_b <= M N.
+   P == 0 or no buried point: C = 0 and contact_first, where delivered, is all zeros ([1] without a pair, [M + 1] otherwise).
+   Refused with a message before a device is touched: everything the interface entries refuse; Lee-Richards; N > 128; a negative
+     capacity; d_buried_masks not aligned to 16 bytes.  Refused with the mask request's messages (freesasa_gpu_sr_masks_dev):
+     FREESASA_AMD_SR_CAPS=0, tiles beyond the cap-mask kernel's 128 records per atom.  More than 2^31 - 1 buried points.
+   Two engine runs over the M pair-structure atoms and two stream synchronizations more than freesasa_gpu_interfaces_dev (D_b
+     comes back before the arrays it sizes are made, then C and the flag of a dot without a cover).
+   Not offered: Lee-Richards; the file sweep and the trajectory drivers; periodic images; a symmetrised table; a fold of the
+     rows per residue pair on the device (tools/interfaces.py --residue-contacts folds on the host).
+
+   freesasa_gpu_interface_contacts_dev: the arrays after the counts are DEVICE arrays; d_pair_areas is required, every other
+     array and n_buried_dots_out may be NULL; the rest as freesasa_gpu_interfaces_dev.
+   freesasa_gpu_calc_interface_contacts: the same on host arrays, on a pooled context, as freesasa_gpu_calc_interface_residues.
+   Both: 0, or -1 with the context's error text / err_out; the context stays usable. */
+int freesasa_gpu_interface_contacts_dev(freesasa_gpu_ctx *ctx, int alg, const double *d_xyz, const double *d_radii,
+                                        const int64_t *offsets, int n_structs, const int32_t *d_group, const int32_t *n_groups,
+                                        double probe_radius, int resolution,
+                                        double *d_sasa, double *d_iso, double *d_totals, double *d_group_totals,
+                                        long long pair_capacity, long long atom_capacity, long long contact_capacity, long long dot_capacity,
+                                        long long *n_pairs_out, long long *n_pair_atoms_out, long long *n_contacts_out,
+                                        long long *n_buried_dots_out,
+                                        int32_t *d_pair_struct, int32_t *d_pair_groups, double *d_pair_areas,
+                                        int64_t *d_side_offsets, int32_t *d_pair_atom, double *d_pair_buried,
+                                        int64_t *d_contact_first, int32_t *d_contact_partner, int32_t *d_contact_points,
+                                        double *d_contact_area, uint32_t *d_buried_masks, int32_t *d_dot_partner);
+int freesasa_gpu_calc_interface_contacts(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
+                                         const int32_t *group, const int32_t *n_groups, int alg, double probe_radius, int resolution,
+                                         double *sasa_out, double *iso_out, double *totals_out, double *group_totals_out,
+                                         long long pair_capacity, long long atom_capacity, long long contact_capacity, long long dot_capacity,
+                                         long long *n_pairs_out, long long *n_pair_atoms_out, long long *n_contacts_out,
+                                         long long *n_buried_dots_out,
+                                         int32_t *pair_struct_out, int32_t *pair_groups_out, double *pair_areas_out,
+                                         int64_t *side_offsets_out, int32_t *pair_atom_out, double *pair_buried_out,
+                                         int64_t *contact_first_out, int32_t *contact_partner_out, int32_t *contact_points_out,
+                                         double *contact_area_out, uint32_t *buried_masks_out, int32_t *dot_partner_out,
+                                         int device, char *err_out, int err_len);
+
 /* MOLECULAR VOLUME: the volume enclosed by the solvent-accessible surface of every structure, made of the Shrake-Rupley test
    points by the divergence theorem - what `gmx sasa -tv` prints per frame, in the same formulation:
        V = (1/3) sum_i a_i ( (x_i - o) . E_i + R_i n_i ),   E_i = sum over atom i's exposed points of u_k,  a_i = 4 pi R_i^2 / N

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/interfaces.py STRUCTURE... [--chain-groups SPEC | --separate-chains] -o OUT.tsv [--alg lr|sr] [--resolution N] [--probe P]
-                       [--residues RES.tsv [--min-buried X]]
+                       [--residues RES.tsv [--min-buried X]] [--contacts ATOMS.tsv [--residue-contacts RES.tsv]]
 
 The interface areas between the chain groups of structure files (freesasa_amd.calc_interfaces): one line per pair of groups
 that are in contact - file, the two groups' chain labels, the atoms of each side, and six areas in A^2: each side's isolated
@@ -11,7 +11,12 @@ load, or lacks a requested chain, is reported on stderr and gets no lines.
 --residues RES.tsv adds the interface-residue table (the per-residue table of calc_interfaces, made on the device): one line per
 residue of a side that loses more than --min-buried (default 0) A^2 - file, the two groups' labels, the label of the side the
 residue is on, its chain, name and number (with insertion code), the atoms of the residue in that group, and its isolated
-area, its area in the pair and the difference.  OUT.tsv is the same with and without it."""
+area, its area in the pair and the difference.  OUT.tsv is the same with and without it.
+--contacts ATOMS.tsv (Shrake-Rupley only: with --alg lr it is refused) adds the atom-atom contact table (freesasa_amd.
+calc_interface_contacts, made on the device): one line per row - file, the two groups' labels, then chain, residue name, residue
+number and atom name of the buried atom and of the partner atom that buries it, the test points and the area in A^2.  The table is
+directed: a -> b and b -> a are rows of their own.  --residue-contacts RES.tsv folds these rows per (pair, residue of the buried
+atom, residue of the partner) here, with numpy: the points summed, the areas added in row order."""
 import argparse
 import os
 import sys
@@ -48,6 +53,60 @@ def format_residue_rows(files, labels, pair_struct, pair_groups, res_offsets, re
     return out
 
 
+CONTACT_HEADER = "file\tgroup_a\tgroup_b\tchain\tres_name\tres_number\tatom\tpartner_chain\tpartner_res_name\tpartner_res_number\tpartner_atom\tpoints\tarea"
+RESIDUE_CONTACT_HEADER = "file\tgroup_a\tgroup_b\tchain\tres_name\tres_number\tpartner_chain\tpartner_res_name\tpartner_res_number\tpoints\tarea"
+
+
+def contact_row_keys(side_offsets, pair_atom, contact_first, contact_partner):
+    """per row of the contact table: (its pair p, the input atom of i, the input atom of j) as three int64 arrays"""
+    import numpy as np
+    rows_of = np.diff(np.asarray(contact_first, dtype=np.int64))
+    i = np.repeat(np.arange(len(rows_of), dtype=np.int64), rows_of)
+    p = (np.searchsorted(np.asarray(side_offsets, dtype=np.int64), i, side="right") - 1) // 2
+    pair_atom = np.asarray(pair_atom, dtype=np.int64)
+    return p, pair_atom[i], pair_atom[np.asarray(contact_partner, dtype=np.int64)]
+
+
+def format_contact_rows(files, labels, pair_struct, pair_groups, row_pair, atom_i, atom_j, points, area, atom_res, atom_name, res_chain,
+                        res_name, res_number):
+    """the atom records, one string per row of the contact table (no line ends), in its order.  atom_res [n]: the residue of every
+    input atom; atom_name [n], res_chain, res_name, res_number: the loader's labels."""
+    out = []
+    tag = lambda r: [str(res_chain[r]).strip() or "_", str(res_name[r]).strip(), str(res_number[r]).strip()]
+    for p, i, j, n, a in zip(row_pair, atom_i, atom_j, points, area):
+        s, (g, h) = int(pair_struct[p]), pair_groups[p]
+        out.append("\t".join([files[s], labels[s][int(g)], labels[s][int(h)]] + tag(int(atom_res[i])) + [str(atom_name[i]).strip()] +
+                             tag(int(atom_res[j])) + [str(atom_name[j]).strip(), str(int(n)), "%.3f" % float(a)]))
+    return out
+
+
+def fold_contact_rows(row_pair, res_i, res_j, points, area):
+    """the rows folded per (pair, residue of i, residue of j), in order of first appearance: (pair, res_i, res_j, points, area) -
+    points summed, areas added in row order"""
+    import numpy as np
+    key = np.stack([np.asarray(row_pair, np.int64), np.asarray(res_i, np.int64), np.asarray(res_j, np.int64)], axis=1)
+    if len(key) == 0:
+        return key[:, 0], key[:, 1], key[:, 2], np.zeros(0, np.int64), np.zeros(0)
+    uniq, first, inverse = np.unique(key, axis=0, return_index=True, return_inverse=True)
+    order = np.argsort(first, kind="stable")              # the folded rows in order of first appearance
+    place = np.empty(len(uniq), np.int64); place[order] = np.arange(len(uniq))
+    slot = place[np.asarray(inverse).reshape(-1)]
+    pts, tot = np.zeros(len(uniq), np.int64), np.zeros(len(uniq))
+    np.add.at(pts, slot, np.asarray(points, np.int64))
+    np.add.at(tot, slot, np.asarray(area, np.float64))   # (unbuffered, element by element: row order)
+    u = uniq[order]
+    return u[:, 0], u[:, 1], u[:, 2], pts, tot
+
+
+def format_residue_contact_rows(files, labels, pair_struct, pair_groups, fold, res_chain, res_name, res_number):
+    out = []
+    tag = lambda r: [str(res_chain[r]).strip() or "_", str(res_name[r]).strip(), str(res_number[r]).strip()]
+    for p, ri, rj, n, a in zip(*fold):
+        s, (g, h) = int(pair_struct[p]), pair_groups[p]
+        out.append("\t".join([files[s], labels[s][int(g)], labels[s][int(h)]] + tag(int(ri)) + tag(int(rj)) + [str(int(n)), "%.3f" % float(a)]))
+    return out
+
+
 def group_labels(batch, group, n_groups):
     """per structure, per group: the chain labels of its atoms in order of appearance, joined"""
     import numpy as np
@@ -80,9 +139,15 @@ def main(argv=None):
     ap.add_argument("--probe", type=float, default=1.4)
     ap.add_argument("--residues", default=None, metavar="RES.tsv")
     ap.add_argument("--min-buried", type=float, default=0.0)
+    ap.add_argument("--contacts", default=None, metavar="ATOMS.tsv")
+    ap.add_argument("--residue-contacts", default=None, metavar="RES.tsv")
     args = ap.parse_args(argv)
     if args.chain_groups and args.separate_chains:
         sys.exit("--chain-groups and --separate-chains exclude each other")
+    if args.residue_contacts and not args.contacts:
+        sys.exit("--residue-contacts needs --contacts")
+    if args.contacts and args.alg != "sr":
+        sys.exit("--contacts is made of Shrake-Rupley test points: give --alg sr (Lee-Richards has no contact table)")
     import freesasa_amd as fa
     from freesasa_amd import ingest
     batch = ingest.load_files(args.structures)
@@ -113,6 +178,27 @@ def main(argv=None):
                                             batch.res_number):
                 f.write(line + "\n")
         print(f"{got.n_res_rows} interface residues -> {args.residues}")
+    if args.contacts:
+        import numpy as np
+        ct = fa.calc_interface_contacts(batch.xyz, batch.radii, batch.offsets, group, n_groups, probe=args.probe, n_points=res)
+        files = [os.path.basename(p) for p in args.structures]
+        atom_res = np.repeat(np.arange(batch.n_residues, dtype=np.int64), np.diff(batch.res_first))
+        atom_name = [v.decode() for v in batch.atom_name_raw.tolist()]
+        row_pair, atom_i, atom_j = contact_row_keys(ct.side_offsets, ct.pair_atom, ct.contact_first, ct.contact_partner)
+        with open(args.contacts, "w") as f:
+            f.write(CONTACT_HEADER + "\n")
+            for line in format_contact_rows(files, labels, ct.pair_struct, ct.pair_groups, row_pair, atom_i, atom_j, ct.contact_points,
+                                            ct.contact_area, atom_res, atom_name, batch.res_chain, batch.res_name, batch.res_number):
+                f.write(line + "\n")
+        print(f"{ct.n_contacts} atom contacts -> {args.contacts}")
+        if args.residue_contacts:
+            fold = fold_contact_rows(row_pair, atom_res[atom_i], atom_res[atom_j], ct.contact_points, ct.contact_area)
+            with open(args.residue_contacts, "w") as f:
+                f.write(RESIDUE_CONTACT_HEADER + "\n")
+                for line in format_residue_contact_rows(files, labels, ct.pair_struct, ct.pair_groups, fold, batch.res_chain, batch.res_name,
+                                                        batch.res_number):
+                    f.write(line + "\n")
+            print(f"{len(fold[0])} residue contacts -> {args.residue_contacts}")
 
 
 if __name__ == "__main__":
