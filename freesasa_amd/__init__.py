@@ -154,6 +154,10 @@ def lib():
                                                            _dp, _dp, _dp, _dp, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong,
                                                            _llp, _llp, _llp, _llp, _i32p, _i32p, _dp, _lp, _i32p, _dp, _lp, _i32p, _i32p,
                                                            _dp, C.POINTER(C.c_uint32), _i32p, C.c_int, C.c_char_p, C.c_int]
+        L.freesasa_gpu_interface_residue_contacts_dev.argtypes = L.freesasa_gpu_interface_contacts_dev.argtypes + [
+            _lp, C.c_int, C.c_longlong, _llp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.freesasa_gpu_calc_interface_residue_contacts.argtypes = L.freesasa_gpu_calc_interface_contacts.argtypes[:-3] + [
+            _lp, C.c_int, C.c_longlong, _llp, _lp, _i32p, _i32p, _dp, _i32p, C.c_int, C.c_char_p, C.c_int]
         L.freesasa_gpu_sr_volume_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _lp, C.c_int, C.c_double, C.c_int,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.freesasa_gpu_calc_volume.argtypes = [_dp, _dp, _lp, C.c_int, C.c_double, C.c_int, _dp, _ip, _dp, _dp, _dp, _dp,
@@ -417,13 +421,25 @@ class InterfaceContacts(Interfaces):
     """calc_interface_contacts()'s result: everything calc_interfaces(per_atom=True) gives, and the directed atom-atom contact
     table over the M pair-structure atoms: contact_first [M + 1] (int64, the row range of every atom), contact_partner [C]
     (int32, a pair-structure atom: pair_atom[j] is the input atom), contact_points [C] (int32), contact_area [C], buried_masks
-    [M, 4] (uint32: the test points the partner buries), n_contacts = C, n_buried_dots = D_b."""
+    [M, 4] (uint32: the test points the partner buries), n_contacts = C, n_buried_dots = D_b; with res_first the rows folded per
+    pair of residues: rescontact_offsets [2P + 1] (int64, the row range of every source side), rescontact_residues [Q, 2] (int32,
+    the batch-wide residue of source and partner), rescontact_counts [Q, 2] (int32: contact rows folded, points), rescontact_area
+    [Q], rescontact_reverse [Q] (int32: the row that runs the other way, or -1) and n_rescontacts = Q (else None)."""
 
-    def __init__(self, base, contact_first, contact_partner, contact_points, contact_area, buried_masks, n_buried_dots):
+    def __init__(self, base, contact_first, contact_partner, contact_points, contact_area, buried_masks, n_buried_dots, rescontacts=None):
         Interfaces.__init__(self, *base)
         self.contact_first, self.contact_partner, self.contact_points = contact_first, contact_partner, contact_points
         self.contact_area, self.buried_masks = contact_area, buried_masks
         self.n_contacts, self.n_buried_dots = int(contact_partner.size), int(n_buried_dots)
+        (self.rescontact_offsets, self.rescontact_residues, self.rescontact_counts, self.rescontact_area,
+         self.rescontact_reverse) = rescontacts if rescontacts is not None else (None,) * 5
+        self.n_rescontacts = None if rescontacts is None else int(self.rescontact_area.size)
+
+    def residue_side_rows(self, p, side):
+        """the folded rows whose source is side 0 (group g) or 1 (group h) of pair p, as a range over the rescontact arrays"""
+        if self.rescontact_offsets is None:
+            raise ValueError("no residue-residue contact table: calc_interface_contacts() was called without res_first")
+        return range(int(self.rescontact_offsets[2 * p + side]), int(self.rescontact_offsets[2 * p + side + 1]))
 
     def atom_rows(self, i):
         """the rows of pair-structure atom i, as a slice into contact_partner, contact_points and contact_area"""
@@ -435,10 +451,13 @@ class InterfaceContacts(Interfaces):
         return slice(int(self.contact_first[self.side_offsets[q]]), int(self.contact_first[self.side_offsets[q + 1]]))
 
 
-def calc_interface_contacts(xyz, radii, offsets, group, n_groups, probe=1.4, n_points=100, device=-1):
+def calc_interface_contacts(xyz, radii, offsets, group, n_groups, probe=1.4, n_points=100, device=-1, res_first=None):
     """freesasa_gpu_calc_interface_contacts() on host arrays -> InterfaceContacts: calc_interfaces() with Shrake-Rupley and, for
     every pair-structure atom, which atoms of the partner bury its test points, how many, and the area they stand for
-    (include/freesasa_gpu.h).  Two calls: the counts, then the arrays."""
+    (include/freesasa_gpu.h).  Two calls: the counts, then the arrays.
+    res_first (the batch's residue boundaries [n_res + 1], as ingest.Batch.res_first): the second call is
+    freesasa_gpu_calc_interface_residue_contacts(), which adds the rows folded per pair of residues and their reverse rows; the
+    folded table has at most as many rows as the contact table, so its arrays are sized by the same first call and trimmed."""
     xyz, radii, offsets, group, n_groups = _group_batch(xyz, radii, offsets, group, n_groups)
     n, ns = radii.size, offsets.size - 1
     G = int(n_groups.astype(np.int64).sum())
@@ -466,6 +485,25 @@ def calc_interface_contacts(xyz, radii, offsets, group, n_groups, probe=1.4, n_p
     arrays = (np.empty(P, dtype=np.int32), np.empty((P, 2), dtype=np.int32), areas, np.empty(2 * P + 1, dtype=np.int64),
               np.empty(M, dtype=np.int32), np.empty(M), np.empty(M + 1, dtype=np.int64), np.empty(Cn, dtype=np.int32),
               np.empty(Cn, dtype=np.int32), np.empty(Cn), np.empty((M, 4), dtype=np.uint32))
+    if res_first is not None:
+        res_first = np.ascontiguousarray(res_first, dtype=np.int64)
+        if res_first.ndim != 1 or res_first.size < 2:
+            raise ValueError("res_first must be a one-dimensional array of n_res + 1 >= 2 boundaries")
+        ps, pg, areas, so, pa, pb, cf, cp, cn, ca, bm = arrays
+        qo, qr, qc = np.empty(2 * P + 1, dtype=np.int64), np.empty((Cn, 2), dtype=np.int32), np.empty((Cn, 2), dtype=np.int32)
+        qa, qv, Qc = np.empty(Cn), np.empty(Cn, dtype=np.int32), C.c_longlong(0)
+        if lib().freesasa_gpu_calc_interface_residue_contacts(
+                xyz.ctypes.data_as(_dp), radii.ctypes.data_as(_dp), offsets.ctypes.data_as(_lp), ns, group.ctypes.data_as(i32),
+                n_groups.ctypes.data_as(i32), SHRAKE_RUPLEY, probe, n_points, sasa.ctypes.data_as(_dp), iso.ctypes.data_as(_dp),
+                totals.ctypes.data_as(_dp), gt.ctypes.data_as(_dp), P, M, Cn, 0, C.byref(Pc), C.byref(Mc), C.byref(Cc), C.byref(Dc),
+                ps.ctypes.data_as(i32), pg.ctypes.data_as(i32), areas.ctypes.data_as(_dp), so.ctypes.data_as(_lp), pa.ctypes.data_as(i32),
+                pb.ctypes.data_as(_dp), cf.ctypes.data_as(_lp), cp.ctypes.data_as(i32), cn.ctypes.data_as(i32), ca.ctypes.data_as(_dp),
+                bm.ctypes.data_as(u32), None, res_first.ctypes.data_as(_lp), res_first.size - 1, Cn, C.byref(Qc), qo.ctypes.data_as(_lp),
+                qr.ctypes.data_as(i32), qc.ctypes.data_as(i32), qa.ctypes.data_as(_dp), qv.ctypes.data_as(i32), device, err, 512):
+            raise RuntimeError("freesasa_gpu_calc_interface_residue_contacts: " + err.value.decode())
+        Q = int(Qc.value)
+        return InterfaceContacts((sasa, iso, totals, gt, ps, pg, areas, so, pa, pb), cf, cp, cn, ca, bm, Dc.value,
+                                 (qo, qr[:Q].copy(), qc[:Q].copy(), qa[:Q].copy(), qv[:Q].copy()))
     if call(P, M, Cn, arrays):
         raise RuntimeError("freesasa_gpu_calc_interface_contacts: " + err.value.decode())
     ps, pg, areas, so, pa, pb, cf, cp, cn, ca, bm = arrays
@@ -2002,6 +2040,32 @@ class GpuContext:
                                                      d_contact_area or None, d_buried_masks or None, d_dot_partner or None):
             raise RuntimeError("freesasa_gpu_interface_contacts_dev: " + self.error())
         return int(P.value), int(M.value), int(Cn.value), int(D.value)
+
+    def interface_residue_contacts(self, d_xyz, d_radii, offsets, d_group, n_groups, res_first, d_sasa, d_iso, pair_capacity, d_pair_areas,
+                                   rescontact_capacity, d_rescontact_area, d_rescontact_offsets=0, d_rescontact_residues=0,
+                                   d_rescontact_counts=0, d_rescontact_reverse=0, contact_capacity=0, d_contact_first=0,
+                                   d_contact_partner=0, d_contact_points=0, d_contact_area=0, d_buried_masks=0, dot_capacity=0,
+                                   d_dot_partner=0, d_pair_struct=0, d_pair_groups=0, atom_capacity=0, d_side_offsets=0, d_pair_atom=0,
+                                   d_pair_buried=0, d_totals=0, d_group_totals=0, alg=SHRAKE_RUPLEY, probe=1.4, n_points=100):
+        """freesasa_gpu_interface_residue_contacts_dev(): interface_contacts() and the contact rows folded per pair of residues
+        - res_first: a host array of the batch's residue boundaries [n_res + 1]; d_rescontact_area [Q], d_rescontact_residues
+        [2 Q], d_rescontact_counts [2 Q], d_rescontact_reverse [Q]: device arrays that hold rescontact_capacity rows,
+        d_rescontact_offsets [2 P + 1] one that holds pair_capacity rows -> (n_pairs, n_pair_atoms, n_contacts, n_buried_dots,
+        n_rescontacts); a capacity that is too small: RuntimeError naming the number."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        ng = np.ascontiguousarray(n_groups, dtype=np.int32)
+        res_first = np.ascontiguousarray(res_first, dtype=np.int64)
+        P, M, Cn, D, Q = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        if lib().freesasa_gpu_interface_residue_contacts_dev(
+                self._h, alg, d_xyz, d_radii, offsets.ctypes.data_as(_lp), offsets.size - 1, d_group, ng.ctypes.data_as(C.POINTER(C.c_int32)),
+                probe, n_points, d_sasa or None, d_iso or None, d_totals or None, d_group_totals or None, pair_capacity, atom_capacity,
+                contact_capacity, dot_capacity, C.byref(P), C.byref(M), C.byref(Cn), C.byref(D), d_pair_struct or None, d_pair_groups or None,
+                d_pair_areas or None, d_side_offsets or None, d_pair_atom or None, d_pair_buried or None, d_contact_first or None,
+                d_contact_partner or None, d_contact_points or None, d_contact_area or None, d_buried_masks or None, d_dot_partner or None,
+                res_first.ctypes.data_as(_lp), res_first.size - 1, rescontact_capacity, C.byref(Q), d_rescontact_offsets or None,
+                d_rescontact_residues or None, d_rescontact_counts or None, d_rescontact_area or None, d_rescontact_reverse or None):
+            raise RuntimeError("freesasa_gpu_interface_residue_contacts_dev: " + self.error())
+        return int(P.value), int(M.value), int(Cn.value), int(D.value), int(Q.value)
 
     def periodic(self, d_xyz, d_radii, offsets, cells, d_sasa, d_totals=0, alg=LEE_RICHARDS, probe=1.4, resolution=20):
         """freesasa_gpu_periodic_dev(): every atom's area among the periodic images of its structure's cell (cells: a host

@@ -58,6 +58,7 @@
 #include "dots_kernels.h"
 #include "iface_kernels.h"
 #include "contact_kernels.h"
+#include "rescontact_kernels.h"
 #include "gpu_parse.h"
 
 /* ------------------------------------------------------------------ kernel launchers (gpu_kernels.hip) */
@@ -171,6 +172,11 @@ hipError_t kl_iface_res_rows(const sasa::IfaceResArgs &a, int *scratch, hipStrea
 hipError_t kl_contact_masks(const sasa::ContactArgs &a, hipStream_t st);
 hipError_t kl_contact_attribute(const sasa::ContactArgs &a, hipStream_t st);
 hipError_t kl_contact_rows(const sasa::ContactArgs &a, int *scratch, hipStream_t st);
+/* ... their residue-residue contact tables (rescontact_kernels.h): the segments (the per-residue tables' heads, scan and first
+   atoms, nothing else of them); the fold of the contact rows - count, the scan of a.fc [M + 1], write - and the reverse rows with
+   the sides' offsets (scratch: ifr_scan_scratch(M) ints) */
+hipError_t kl_rc_segments(const sasa::IfaceResArgs &s, int *scratch, hipStream_t st);
+hipError_t kl_rc_fold(const sasa::ResContactArgs &a, int *scratch, hipStream_t st);
 
 /* ------------------------------------------------------------------ context (gpu_engine.hip) */
 
@@ -251,6 +257,8 @@ struct freesasa_gpu_ctx {
     /* ... their atom-atom contact tables: the side, pair and buried masks with the two runs' areas; the atoms' int32 work arrays
        and the flag; the buried dots (dot_first, points, atoms, point numbers, partners, counts, ranks); the table itself */
     DevBuf if_cmasks, if_cwork, if_cdots, if_ctable;
+    /* ... their residue-residue contact tables: the segments' and the fold's int32 work arrays; the table itself */
+    DevBuf if_rcwork, if_rctable;
     int dt_unit_n = 0; /* the point count whose unit points dt_unit holds (the expansion's; 0: none) */
     void *stage_in = nullptr, *stage_out = nullptr; /* page-locked host staging of freesasa_gpu_calc_batch_pipelined */
     size_t stage_in_cap = 0, stage_out_cap = 0;

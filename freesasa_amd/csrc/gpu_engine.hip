@@ -136,7 +136,8 @@ extern "C" void freesasa_gpu_ctx_destroy(freesasa_gpu_ctx *c)
                      &c->if_meta, &c->if_box, &c->if_cand, &c->if_flag, &c->if_sides, &c->if_xyz, &c->if_radii, &c->if_comb, &c->if_sasa,
                      &c->if_inpair, &c->if_areas, &c->if_patom, &c->if_pburied, &c->if_rows,
                      &c->if_rfirst, &c->if_rwork, &c->if_rsegs, &c->if_rtable,
-                     &c->if_cmasks, &c->if_cwork, &c->if_cdots, &c->if_ctable};
+                     &c->if_cmasks, &c->if_cwork, &c->if_cdots, &c->if_ctable,
+                     &c->if_rcwork, &c->if_rctable};
     for (DevBuf *b : all)
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : c->parse)

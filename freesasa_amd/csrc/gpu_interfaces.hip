@@ -33,6 +33,13 @@
  *                        _rank, the block scan, k_contact_rows_write; C and the flag come back (one more); the table stays in
  *                        c->if_ctable, the masks in c->if_cmasks, the dots in c->if_cdots
  * and hold the four capacities against P, M, C and D_b together (iface_contact_check_caps) before anything is delivered.
+ *
+ * The residue-residue contact entries (freesasa_gpu_interface_residue_contacts_dev, freesasa_gpu_calc_interface_residue_contacts;
+ * phase functions: rescontact_kernels.h) run the contact entries' path as it is and one more stage behind it:
+ *  11. residue contacts  iface_rescontacts: the per-residue tables' k_iface_res_head, block scan and k_iface_res_first (the segments),
+ *                        k_rc_fold_count, the block scan, k_rc_fold_write, k_rc_reverse; Q comes back (one more stream
+ *                        synchronization); the table stays in c->if_rctable
+ * and hold the five capacities against P, M, C, D_b and Q together (iface_rescontact_check_caps) before anything is delivered.
  */
 #include <hip/hip_runtime.h>
 
@@ -427,6 +434,82 @@ int iface_contact_check_caps(freesasa_gpu_ctx *c, const IfacePlan &pl, const Ifa
     return 0;
 }
 
+/* the residue-residue contact tables: what an entry gives on top of the contact entries' arguments, and what it wants back */
+struct IfaceResContactWant {
+    const int64_t *res_first = nullptr;
+    int n_res = 0;
+    long long rescontact_capacity = 0;
+    long long *n_rescontacts_out = nullptr;
+};
+/* ... checked before a device is touched, behind the contact entries' checks: res_first by the residue entries' own check */
+int iface_rescontact_bad_args(const IfaceResContactWant &qw, const int64_t *offsets, int n_structs, char *msg, size_t len)
+{
+    IfaceResWant rw;
+    rw.res_first = qw.res_first; rw.n_res = qw.n_res; rw.n_res_rows_out = qw.n_rescontacts_out;
+    if (iface_res_bad_args(rw, offsets, n_structs, msg, len)) return -1;
+    if (qw.rescontact_capacity < 0) { snprintf(msg, len, "rescontact_capacity must be >= 0 (it is %lld)", qw.rescontact_capacity); return -1; }
+    return 0;
+}
+
+/* the stage behind iface_contacts (the stream is idle, C is on the host): the segments of the per-residue tables by their own
+   kernels, the fold of the contact rows per partner segment, the reverse rows; the table in c->if_rctable - rescontact_offsets
+   [2 P + 1] | rescontact_area [C] | rescontact_residues [2 C] | rescontact_counts [2 C] | rescontact_reverse [C], Q rows of them
+   used.  Q comes back to the host (one stream synchronization), so at the stage's end the stream is idle.  Without a contact row
+   nothing is launched: Q = 0. */
+struct IfaceResContactTable {
+    int64_t Q = 0;
+    const int64_t *off = nullptr;
+    const double *area = nullptr;
+    const int32_t *res = nullptr, *cnt = nullptr, *rev = nullptr;
+    std::vector<int64_t> first; /* the upload of res_first (like the plan, the table lives until the stream is idle) */
+};
+int iface_rescontacts(freesasa_gpu_ctx *c, const IfacePlan &pl, const IfaceResContactWant &qw, const IfaceContactTable &ct, IfaceResContactTable &t)
+{
+    t.Q = 0;
+    if (pl.P == 0 || ct.C == 0) return 0;
+    const size_t P = (size_t)pl.P, M = (size_t)pl.M, Cn = (size_t)ct.C;
+    const size_t S = (size_t)ifr_scan_scratch(pl.M);
+    hipStream_t st = c->stream;
+    if (ensure(c, c->if_rfirst, 8 * ((size_t)qw.n_res + 1)) || ensure(c, c->if_rcwork, 4 * (4 * M + 3 + S + Cn)) ||
+        ensure(c, c->if_rctable, 8 * (2 * P + 1) + 8 * Cn + 4 * 5 * Cn))
+        return -1;
+    int *w = (int *)c->if_rcwork.p;
+    IfaceResArgs s;
+    memset(&s, 0, sizeof s);
+    s.n_pair_atoms = pl.M; s.n_sides = 2 * pl.P; s.n_res = qw.n_res;
+    s.side_off = (const int64_t *)c->if_sides.p; s.pair_atom = (const int *)c->if_patom.p; s.res_first = (const int64_t *)c->if_rfirst.p;
+    s.atom_res = w; s.hs = w + M; s.seg_first = s.hs + M + 1;
+    ResContactArgs a;
+    memset(&a, 0, sizeof a);
+    a.n_pair_atoms = pl.M; a.n_sides = 2 * pl.P; a.row_cap = ct.C;
+    a.side_off = s.side_off; a.atom_res = s.atom_res; a.hs = s.hs; a.seg_first = s.seg_first;
+    a.contact_first = ct.first; a.contact_partner = ct.partner; a.contact_points = ct.points; a.contact_area = ct.area;
+    a.fc = s.seg_first + M + 1;
+    int *scratch = a.fc + M + 1;
+    a.pseg = scratch + S;
+    a.rc_off = (int64_t *)c->if_rctable.p; a.rc_area = (double *)(a.rc_off + 2 * P + 1);
+    a.rc_res = (int *)(a.rc_area + Cn); a.rc_cnt = a.rc_res + 2 * Cn; a.rc_rev = a.rc_cnt + 2 * Cn;
+    t.first.assign(qw.res_first, qw.res_first + qw.n_res + 1); /* (the stage's own copy: iface_residues) */
+    HIP_TRY(c, hipMemcpyAsync(c->if_rfirst.p, t.first.data(), 8 * t.first.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(a.fc, 0, 4 * (M + 1), st)); /* (the segments' counts: a slot at or beyond K has none) */
+    HIP_TRY(c, kl_rc_segments(s, scratch, st));
+    HIP_TRY(c, kl_rc_fold(a, scratch, st));
+    int Q = 0;
+    HIP_TRY(c, hipMemcpyAsync(&Q, a.fc + M, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    t.Q = Q; t.off = a.rc_off; t.area = a.rc_area; t.res = a.rc_res; t.cnt = a.rc_cnt; t.rev = a.rc_rev;
+    return 0;
+}
+/* the five capacities against P, M, C, D_b and Q, in this order */
+int iface_rescontact_check_caps(freesasa_gpu_ctx *c, const IfacePlan &pl, const IfaceWant &w, const IfaceContactWant &cw, const IfaceContactTable &ct,
+                                const IfaceResContactWant &qw, int64_t Q)
+{
+    if (iface_contact_check_caps(c, pl, w, cw, ct)) return -1;
+    if (Q > qw.rescontact_capacity)
+        return ctx_fail(c, "rescontact_capacity %lld is too small: the interfaces have %lld residue contact rows", qw.rescontact_capacity, (long long)Q);
+    return 0;
+}
+
 int iface_dev_checks(freesasa_gpu_ctx *c, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
                      const int32_t *d_group, const int32_t *n_groups, int alg, int resolution, long long pair_capacity, long long atom_capacity)
 {
@@ -571,16 +654,20 @@ extern "C" int freesasa_gpu_interface_residues_dev(freesasa_gpu_ctx *c, int alg,
     });
 }
 
-extern "C" int freesasa_gpu_interface_contacts_dev(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii,
-                                                   const int64_t *offsets, int n_structs, const int32_t *d_group, const int32_t *n_groups,
-                                                   double probe_radius, int resolution, double *d_sasa, double *d_iso, double *d_totals,
-                                                   double *d_group_totals, long long pair_capacity, long long atom_capacity,
-                                                   long long contact_capacity, long long dot_capacity, long long *n_pairs_out,
-                                                   long long *n_pair_atoms_out, long long *n_contacts_out, long long *n_buried_dots_out,
-                                                   int32_t *d_pair_struct, int32_t *d_pair_groups, double *d_pair_areas,
-                                                   int64_t *d_side_offsets, int32_t *d_pair_atom, double *d_pair_buried,
-                                                   int64_t *d_contact_first, int32_t *d_contact_partner, int32_t *d_contact_points,
-                                                   double *d_contact_area, uint32_t *d_buried_masks, int32_t *d_dot_partner)
+/* the contact entry, and - with qw - the residue-residue contact entry: the same call with one more stage and five more arrays */
+struct IfaceResContactOut { /* the residue-residue contact entries' arrays, on the device or on the host: area is required */
+    int64_t *off = nullptr;
+    int32_t *res = nullptr, *cnt = nullptr, *rev = nullptr;
+    double *area = nullptr;
+};
+static int iface_contacts_dev(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
+                              const int32_t *d_group, const int32_t *n_groups, double probe_radius, int resolution, double *d_sasa,
+                              double *d_iso, double *d_totals, double *d_group_totals, long long pair_capacity, long long atom_capacity,
+                              long long contact_capacity, long long dot_capacity, long long *n_pairs_out, long long *n_pair_atoms_out,
+                              long long *n_contacts_out, long long *n_buried_dots_out, int32_t *d_pair_struct, int32_t *d_pair_groups,
+                              double *d_pair_areas, int64_t *d_side_offsets, int32_t *d_pair_atom, double *d_pair_buried,
+                              int64_t *d_contact_first, int32_t *d_contact_partner, int32_t *d_contact_points, double *d_contact_area,
+                              uint32_t *d_buried_masks, int32_t *d_dot_partner, const IfaceResContactWant *qw, const IfaceResContactOut &qd)
 {
     if (!c) return -1;
     if (freesasa_gpu_wait(c)) return -1;
@@ -591,12 +678,14 @@ extern "C" int freesasa_gpu_interface_contacts_dev(freesasa_gpu_ctx *c, int alg,
         cw.contact_capacity = contact_capacity; cw.dot_capacity = dot_capacity; cw.n_contacts_out = n_contacts_out; cw.n_buried_dots_out = n_buried_dots_out;
         cw.rows = d_contact_partner || d_contact_points || d_contact_area; cw.dots = d_dot_partner != nullptr;
         if (iface_bad_args(d_xyz, d_radii, offsets, n_structs, d_group, n_groups, alg, resolution, msg, sizeof msg) ||
-            iface_bad_caps(pair_capacity, atom_capacity, msg, sizeof msg) || iface_contact_bad_args(cw, alg, resolution, d_buried_masks, msg, sizeof msg))
+            iface_bad_caps(pair_capacity, atom_capacity, msg, sizeof msg) || iface_contact_bad_args(cw, alg, resolution, d_buried_masks, msg, sizeof msg) ||
+            (qw && iface_rescontact_bad_args(*qw, offsets, n_structs, msg, sizeof msg)))
             return ctx_fail(c, "%s", msg);
         if (iface_dev_checks(c, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, alg, resolution, pair_capacity, atom_capacity)) return -1;
-        if (!d_sasa || !d_iso || !n_pairs_out || !n_pair_atoms_out || !d_pair_areas) return ctx_fail(c, "null argument");
+        if (!d_sasa || !d_iso || !n_pairs_out || !n_pair_atoms_out || !d_pair_areas || (qw && !qd.area)) return ctx_fail(c, "null argument");
         IfacePlan pl; /* (the plan holds the sources of copies enqueued below: it lives until the stream is idle) */
         IfaceContactTable t;
+        IfaceResContactTable qt;
         IfaceWant w, none; /* (the pipeline holds no capacity against its counts here: the four are held together, once C and D_b are known) */
         w.pair_capacity = pair_capacity; w.atom_capacity = atom_capacity; w.rows = true;
         w.atoms = d_pair_atom || d_pair_buried || d_contact_first || d_buried_masks;
@@ -607,9 +696,22 @@ extern "C" int freesasa_gpu_interface_contacts_dev(freesasa_gpu_ctx *c, int alg,
                 return -1;
             *n_contacts_out = t.C;
             if (n_buried_dots_out) *n_buried_dots_out = t.D;
-            if (iface_contact_check_caps(c, pl, w, cw, t)) return -1;
-            const size_t P = (size_t)pl.P, M = (size_t)pl.M, Cn = (size_t)t.C, D = (size_t)t.D;
+            if (qw) {
+                if (iface_rescontacts(c, pl, *qw, t, qt)) return -1;
+                *qw->n_rescontacts_out = qt.Q;
+            }
+            if (qw ? iface_rescontact_check_caps(c, pl, w, cw, t, *qw, qt.Q) : iface_contact_check_caps(c, pl, w, cw, t)) return -1;
+            const size_t P = (size_t)pl.P, M = (size_t)pl.M, Cn = (size_t)t.C, D = (size_t)t.D, Q = (size_t)qt.Q;
             hipStream_t st = c->stream;
+            /* rescontact_offsets: zeros without a pair ([1]) or without a folded row ([2 P + 1]) */
+            if (qd.off && Q == 0) HIP_TRY(c, hipMemsetAsync(qd.off, 0, 8 * (P == 0 ? 1 : 2 * P + 1), st));
+            if (Q > 0) {
+                if (qd.off) HIP_TRY(c, hipMemcpyAsync(qd.off, qt.off, 8 * (2 * P + 1), hipMemcpyDeviceToDevice, st));
+                if (qd.res) HIP_TRY(c, hipMemcpyAsync(qd.res, qt.res, 8 * Q, hipMemcpyDeviceToDevice, st));
+                if (qd.cnt) HIP_TRY(c, hipMemcpyAsync(qd.cnt, qt.cnt, 8 * Q, hipMemcpyDeviceToDevice, st));
+                if (qd.rev) HIP_TRY(c, hipMemcpyAsync(qd.rev, qt.rev, 4 * Q, hipMemcpyDeviceToDevice, st));
+                HIP_TRY(c, hipMemcpyAsync(qd.area, qt.area, 8 * Q, hipMemcpyDeviceToDevice, st));
+            }
             if (d_side_offsets) HIP_TRY(c, hipMemcpyAsync(d_side_offsets, pl.side_off.data(), 8 * (2 * P + 1), hipMemcpyHostToDevice, st));
             if (P == 0) {
                 if (d_contact_first) HIP_TRY(c, hipMemsetAsync(d_contact_first, 0, 8, st));
@@ -637,6 +739,45 @@ extern "C" int freesasa_gpu_interface_contacts_dev(freesasa_gpu_ctx *c, int alg,
     });
 }
 
+extern "C" int freesasa_gpu_interface_contacts_dev(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii,
+                                                   const int64_t *offsets, int n_structs, const int32_t *d_group, const int32_t *n_groups,
+                                                   double probe_radius, int resolution, double *d_sasa, double *d_iso, double *d_totals,
+                                                   double *d_group_totals, long long pair_capacity, long long atom_capacity,
+                                                   long long contact_capacity, long long dot_capacity, long long *n_pairs_out,
+                                                   long long *n_pair_atoms_out, long long *n_contacts_out, long long *n_buried_dots_out,
+                                                   int32_t *d_pair_struct, int32_t *d_pair_groups, double *d_pair_areas,
+                                                   int64_t *d_side_offsets, int32_t *d_pair_atom, double *d_pair_buried,
+                                                   int64_t *d_contact_first, int32_t *d_contact_partner, int32_t *d_contact_points,
+                                                   double *d_contact_area, uint32_t *d_buried_masks, int32_t *d_dot_partner)
+{
+    return iface_contacts_dev(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe_radius, resolution, d_sasa, d_iso, d_totals,
+                              d_group_totals, pair_capacity, atom_capacity, contact_capacity, dot_capacity, n_pairs_out, n_pair_atoms_out,
+                              n_contacts_out, n_buried_dots_out, d_pair_struct, d_pair_groups, d_pair_areas, d_side_offsets, d_pair_atom,
+                              d_pair_buried, d_contact_first, d_contact_partner, d_contact_points, d_contact_area, d_buried_masks,
+                              d_dot_partner, nullptr, IfaceResContactOut());
+}
+
+extern "C" int freesasa_gpu_interface_residue_contacts_dev(
+    freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs, const int32_t *d_group,
+    const int32_t *n_groups, double probe_radius, int resolution, double *d_sasa, double *d_iso, double *d_totals, double *d_group_totals,
+    long long pair_capacity, long long atom_capacity, long long contact_capacity, long long dot_capacity, long long *n_pairs_out,
+    long long *n_pair_atoms_out, long long *n_contacts_out, long long *n_buried_dots_out, int32_t *d_pair_struct, int32_t *d_pair_groups,
+    double *d_pair_areas, int64_t *d_side_offsets, int32_t *d_pair_atom, double *d_pair_buried, int64_t *d_contact_first,
+    int32_t *d_contact_partner, int32_t *d_contact_points, double *d_contact_area, uint32_t *d_buried_masks, int32_t *d_dot_partner,
+    const int64_t *res_first, int n_res, long long rescontact_capacity, long long *n_rescontacts_out, int64_t *d_rescontact_offsets,
+    int32_t *d_rescontact_residues, int32_t *d_rescontact_counts, double *d_rescontact_area, int32_t *d_rescontact_reverse)
+{
+    IfaceResContactWant qw;
+    qw.res_first = res_first; qw.n_res = n_res; qw.rescontact_capacity = rescontact_capacity; qw.n_rescontacts_out = n_rescontacts_out;
+    IfaceResContactOut qd;
+    qd.off = d_rescontact_offsets; qd.res = d_rescontact_residues; qd.cnt = d_rescontact_counts; qd.area = d_rescontact_area; qd.rev = d_rescontact_reverse;
+    return iface_contacts_dev(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe_radius, resolution, d_sasa, d_iso, d_totals,
+                              d_group_totals, pair_capacity, atom_capacity, contact_capacity, dot_capacity, n_pairs_out, n_pair_atoms_out,
+                              n_contacts_out, n_buried_dots_out, d_pair_struct, d_pair_groups, d_pair_areas, d_side_offsets, d_pair_atom,
+                              d_pair_buried, d_contact_first, d_contact_partner, d_contact_points, d_contact_area, d_buried_masks,
+                              d_dot_partner, &qw, qd);
+}
+
 /* the host-pointer entries: the batch as one chunk of the host-batch path, in place, as freesasa_gpu_calc_groups has it */
 struct IfaceContactHost { /* the contact entry's host arrays: any may be null */
     int64_t *first = nullptr;
@@ -651,21 +792,25 @@ static int iface_host(const double *xyz, const double *radii, const int64_t *off
                       int64_t *side_offsets_out, int32_t *pair_atom_out, double *pair_buried_out, long long *stats_out, int device,
                       char *err_out, int err_len, const IfaceResWant *rw = nullptr, int64_t *res_offsets_out = nullptr,
                       int32_t *res_index_out = nullptr, int32_t *res_atoms_out = nullptr, double *res_areas_out = nullptr,
-                      const IfaceContactWant *cw = nullptr, const IfaceContactHost *co = nullptr)
+                      const IfaceContactWant *cw = nullptr, const IfaceContactHost *co = nullptr, const IfaceResContactWant *qw = nullptr,
+                      const IfaceResContactOut *qo = nullptr)
 {
     if (err_out && err_len > 0) err_out[0] = 0;
     char msg[200];
     if (iface_bad_args(xyz, radii, offsets, n_structs, group, n_groups, alg, resolution, msg, sizeof msg) ||
         iface_bad_caps(pair_capacity, atom_capacity, msg, sizeof msg) || (rw && iface_res_bad_args(*rw, offsets, n_structs, msg, sizeof msg)) ||
-        (cw && iface_contact_bad_args(*cw, alg, resolution, nullptr, msg, sizeof msg)))
+        (cw && iface_contact_bad_args(*cw, alg, resolution, nullptr, msg, sizeof msg)) ||
+        (qw && iface_rescontact_bad_args(*qw, offsets, n_structs, msg, sizeof msg)))
         return set_err(err_out, err_len, msg);
-    if (!n_pairs_out || !n_pair_atoms_out || (whole && !pair_areas_out) || (rw && !res_areas_out)) return set_err(err_out, err_len, "null argument");
+    if (!n_pairs_out || !n_pair_atoms_out || (whole && !pair_areas_out) || (rw && !res_areas_out) || (qw && !(qo && qo->area)))
+        return set_err(err_out, err_len, "null argument");
     if (freesasa_gpu_device_count() <= 0)
         return set_err(err_out, err_len, "no HIP device available: libfreesasa_amd has no CPU path");
     return guarded(err_out, err_len, [&]() -> int {
     IfacePlan pl; /* (declared before the lease: freed after its stream is idle) */
     IfaceResTable t;
     IfaceContactTable ct;
+    IfaceResContactTable qt;
     PoolLease lease(device);
     freesasa_gpu_ctx *c = lease.c;
     if (!c) return set_err(err_out, err_len, "could not create a GPU context");
@@ -699,7 +844,11 @@ static int iface_host(const double *xyz, const double *radii, const int64_t *off
                 if (iface_contacts(c, pl, probe, resolution, ct)) return -1;
                 *cw->n_contacts_out = ct.C;
                 if (cw->n_buried_dots_out) *cw->n_buried_dots_out = ct.D;
-                if (iface_contact_check_caps(c, pl, w, *cw, ct)) return -1;
+                if (qw) {
+                    if (iface_rescontacts(c, pl, *qw, ct, qt)) return -1;
+                    *qw->n_rescontacts_out = qt.Q;
+                }
+                if (qw ? iface_rescontact_check_caps(c, pl, w, *cw, ct, *qw, qt.Q) : iface_contact_check_caps(c, pl, w, *cw, ct)) return -1;
             }
             if (rw) {
                 if (iface_residues(c, pl, *rw, d_iso, t)) return -1;
@@ -732,6 +881,17 @@ static int iface_host(const double *xyz, const double *radii, const int64_t *off
                  (Cn > 0 && co->points && hipMemcpyAsync(co->points, ct.points, 4 * Cn, hipMemcpyDeviceToHost, st) != hipSuccess) ||
                  (Cn > 0 && co->area && hipMemcpyAsync(co->area, ct.area, 8 * Cn, hipMemcpyDeviceToHost, st) != hipSuccess) ||
                  (D > 0 && co->dot_partner && hipMemcpyAsync(co->dot_partner, ct.dot_partner, 4 * D, hipMemcpyDeviceToHost, st) != hipSuccess)))
+                return ctx_fail(c, "device-to-host copy failed");
+        }
+        if (qw) {
+            const size_t Q = (size_t)qt.Q;
+            if (qo->off && Q == 0) memset(qo->off, 0, 8 * (P == 0 ? 1 : 2 * P + 1));
+            if (Q > 0 &&
+                ((qo->off && hipMemcpyAsync(qo->off, qt.off, 8 * (2 * P + 1), hipMemcpyDeviceToHost, st) != hipSuccess) ||
+                 (qo->res && hipMemcpyAsync(qo->res, qt.res, 8 * Q, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+                 (qo->cnt && hipMemcpyAsync(qo->cnt, qt.cnt, 8 * Q, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+                 (qo->rev && hipMemcpyAsync(qo->rev, qt.rev, 4 * Q, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+                 hipMemcpyAsync(qo->area, qt.area, 8 * Q, hipMemcpyDeviceToHost, st) != hipSuccess))
                 return ctx_fail(c, "device-to-host copy failed");
         }
         if ((sasa_out && hipMemcpyAsync(sasa_out, d_sasa, 8 * n, hipMemcpyDeviceToHost, st) != hipSuccess) ||
@@ -816,4 +976,32 @@ extern "C" int freesasa_gpu_calc_interface_contacts(const double *xyz, const dou
                       group_totals_out, true, pair_capacity, atom_capacity, n_pairs_out, n_pair_atoms_out, pair_struct_out, pair_groups_out,
                       pair_areas_out, side_offsets_out, pair_atom_out, pair_buried_out, nullptr, device, err_out, err_len, nullptr, nullptr,
                       nullptr, nullptr, nullptr, &cw, &co);
+}
+
+extern "C" int freesasa_gpu_calc_interface_residue_contacts(
+    const double *xyz, const double *radii, const int64_t *offsets, int n_structs, const int32_t *group, const int32_t *n_groups, int alg,
+    double probe_radius, int resolution, double *sasa_out, double *iso_out, double *totals_out, double *group_totals_out,
+    long long pair_capacity, long long atom_capacity, long long contact_capacity, long long dot_capacity, long long *n_pairs_out,
+    long long *n_pair_atoms_out, long long *n_contacts_out, long long *n_buried_dots_out, int32_t *pair_struct_out, int32_t *pair_groups_out,
+    double *pair_areas_out, int64_t *side_offsets_out, int32_t *pair_atom_out, double *pair_buried_out, int64_t *contact_first_out,
+    int32_t *contact_partner_out, int32_t *contact_points_out, double *contact_area_out, uint32_t *buried_masks_out, int32_t *dot_partner_out,
+    const int64_t *res_first, int n_res, long long rescontact_capacity, long long *n_rescontacts_out, int64_t *rescontact_offsets_out,
+    int32_t *rescontact_residues_out, int32_t *rescontact_counts_out, double *rescontact_area_out, int32_t *rescontact_reverse_out, int device,
+    char *err_out, int err_len)
+{
+    IfaceContactWant cw;
+    cw.contact_capacity = contact_capacity; cw.dot_capacity = dot_capacity; cw.n_contacts_out = n_contacts_out; cw.n_buried_dots_out = n_buried_dots_out;
+    cw.rows = contact_partner_out || contact_points_out || contact_area_out; cw.dots = dot_partner_out != nullptr;
+    IfaceContactHost co;
+    co.first = contact_first_out; co.partner = contact_partner_out; co.points = contact_points_out; co.area = contact_area_out;
+    co.buried = buried_masks_out; co.dot_partner = dot_partner_out;
+    IfaceResContactWant qw;
+    qw.res_first = res_first; qw.n_res = n_res; qw.rescontact_capacity = rescontact_capacity; qw.n_rescontacts_out = n_rescontacts_out;
+    IfaceResContactOut qo;
+    qo.off = rescontact_offsets_out; qo.res = rescontact_residues_out; qo.cnt = rescontact_counts_out; qo.area = rescontact_area_out;
+    qo.rev = rescontact_reverse_out;
+    return iface_host(xyz, radii, offsets, n_structs, group, n_groups, alg, probe_radius, resolution, sasa_out, iso_out, totals_out,
+                      group_totals_out, true, pair_capacity, atom_capacity, n_pairs_out, n_pair_atoms_out, pair_struct_out, pair_groups_out,
+                      pair_areas_out, side_offsets_out, pair_atom_out, pair_buried_out, nullptr, device, err_out, err_len, nullptr, nullptr,
+                      nullptr, nullptr, nullptr, &cw, &co, &qw, &qo);
 }

@@ -1466,6 +1466,53 @@ hipError_t kl_contact_rows(const ContactArgs &a, int *scratch, hipStream_t st)
     return hipGetLastError();
 }
 
+/* ... their residue-residue contact tables (rescontact_kernels.h): the segments by the per-residue tables' kernels as they are
+   (heads, the scan, the segments' first atoms); the fold of the contact rows (one wave per segment at a time, RC_WAVES waves to a
+   workgroup, each striding over the K segments with LDS of its own: count, the scan, write); the reverse rows and the sides' offsets (one thread per folded row and per side boundary) */
+__global__ __launch_bounds__(RC_WAVE * RC_WAVES) void k_rc_fold_count(ResContactArgs a)
+{
+    __shared__ ResContactLds m[RC_WAVES];
+    const int wave = threadIdx.x / RC_WAVE, lane = threadIdx.x % RC_WAVE;
+    const int64_t K = a.hs[a.n_pair_atoms];
+    for (int64_t s = (int64_t)blockIdx.x * RC_WAVES + wave; s < K; s += (int64_t)gridDim.x * RC_WAVES) rc_fold_count(a, m[wave], s, lane);
+}
+__global__ __launch_bounds__(RC_WAVE * RC_WAVES) void k_rc_fold_write(ResContactArgs a)
+{
+    __shared__ ResContactLds m[RC_WAVES];
+    const int wave = threadIdx.x / RC_WAVE, lane = threadIdx.x % RC_WAVE;
+    const int64_t K = a.hs[a.n_pair_atoms];
+    for (int64_t s = (int64_t)blockIdx.x * RC_WAVES + wave; s < K; s += (int64_t)gridDim.x * RC_WAVES) rc_fold_write(a, m[wave], s, lane);
+}
+__global__ __launch_bounds__(IF_B) void k_rc_reverse(ResContactArgs a)
+{
+    rc_reverse(a, (int64_t)blockIdx.x * IF_B + threadIdx.x);
+}
+/* s: pair_atom, res_first, side_off in; atom_res, hs, seg_first out; scratch: ifr_scan_scratch(M) ints */
+hipError_t kl_rc_segments(const IfaceResArgs &s, int *scratch, hipStream_t st)
+{
+    if (s.n_pair_atoms == 0) return hipSuccess;
+    const dim3 grid((unsigned)((s.n_pair_atoms + IF_B - 1) / IF_B));
+    hipLaunchKernelGGL(k_iface_res_head, grid, dim3(IF_B), 0, st, s);
+    hipError_t e = kl_iface_res_scan(s.hs, s.n_pair_atoms, scratch, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_iface_res_first, grid, dim3(IF_B), 0, st, s);
+    return hipGetLastError();
+}
+/* a.fc [M + 1] zeroed by the caller; scratch: ifr_scan_scratch(M) ints */
+hipError_t kl_rc_fold(const ResContactArgs &a, int *scratch, hipStream_t st)
+{
+    if (a.n_pair_atoms == 0 || a.row_cap == 0) return hipSuccess;
+    const int64_t n = a.row_cap > a.n_sides + 1 ? a.row_cap : a.n_sides + 1;
+    const int64_t wgs = (a.n_pair_atoms + RC_WAVES - 1) / RC_WAVES; /* (K <= M segments: the grid is made for M, the waves ask for K) */
+    const dim3 grid((unsigned)(wgs < RC_GRID ? wgs : RC_GRID));
+    hipLaunchKernelGGL(k_rc_fold_count, grid, dim3(RC_WAVE * RC_WAVES), 0, st, a);
+    hipError_t e = kl_iface_res_scan(a.fc, a.n_pair_atoms, scratch, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_rc_fold_write, grid, dim3(RC_WAVE * RC_WAVES), 0, st, a);
+    hipLaunchKernelGGL(k_rc_reverse, dim3((unsigned)((n + IF_B - 1) / IF_B)), dim3(IF_B), 0, st, a);
+    return hipGetLastError();
+}
+
 void kl_dump_phase_clocks(void)
 {
 #ifdef SASA_PHASE_TIMING

@@ -1231,8 +1231,8 @@ int freesasa_gpu_calc_interface_residues(const double *xyz, const double *radii,
      FREESASA_AMD_SR_CAPS=0, tiles beyond the cap-mask kernel's 128 records per atom.  More than 2^31 - 1 buried points.
    Two engine runs over the M pair-structure atoms and two stream synchronizations more than freesasa_gpu_interfaces_dev (D_b
      comes back before the arrays it sizes are made, then C and the flag of a dot without a cover).
-   Not offered: Lee-Richards; the file sweep and the trajectory drivers; periodic images; a symmetrised table; a fold of the
-     rows per residue pair on the device (tools/interfaces.py --residue-contacts folds on the host).
+   Not offered: Lee-Richards; the file sweep and the trajectory drivers; periodic images; class splits; a table with both
+     directions added.  (The fold of the rows per residue pair: freesasa_gpu_interface_residue_contacts_dev below.)
 
    freesasa_gpu_interface_contacts_dev: the arrays after the counts are DEVICE arrays; d_pair_areas is required, every other
      array and n_buried_dots_out may be NULL; the rest as freesasa_gpu_interfaces_dev.
@@ -1260,6 +1260,85 @@ int freesasa_gpu_calc_interface_contacts(const double *xyz, const double *radii,
                                          int64_t *contact_first_out, int32_t *contact_partner_out, int32_t *contact_points_out,
                                          double *contact_area_out, uint32_t *buried_masks_out, int32_t *dot_partner_out,
                                          int device, char *err_out, int err_len);
+
+/* RESIDUE-RESIDUE CONTACT TABLES: which residue is in contact with which residue across every interface above, and over how
+   much area - the contact rows above folded per pair of residues on the device, each folded row linked to the row that runs the
+   other way (csrc/rescontact_kernels.h; tests/interface_residue_contacts_ref.py restates the definitions in numpy).  fp64, every
+   operation rounded on its own.
+   Input: that of freesasa_gpu_interface_contacts_dev, and res_first [n_res + 1], a HOST int64 array, exactly as
+     freesasa_gpu_interface_residues_dev takes it (the same checks, the same messages).  Every output of the contact entry is
+     delivered byte for byte.
+   Segments.  Those of the per-residue tables: a maximal run of one side's pair-structure atoms whose input atoms lie in one
+     residue; K of them, numbered pair-major, side g before side h.  Within one side a residue has at most one segment, so on the
+     other side of a given pair "partner residue" and "partner segment" are the same thing.  A residue split over two groups has
+     a segment on both sides of their pair and may be in contact with itself: a legal row whose two residues are equal and
+     whose segments differ.
+   Folded rows.  Segment a with atoms b .. e-1 has the contact rows contact_first[b] .. contact_first[e] - 1 (contiguous: i
+     ascending, then j ascending).  They are folded by the residue of pair_atom[contact_partner[t]]: one folded row per distinct
+     partner residue, the partner residues ascending, with
+       n_rows (int32)    the contact rows folded
+       n_points (int32)  the sum of their contact_points
+       area (fp64)       the sum of their contact_area in row order, one addition at a time from 0
+     The Q folded rows are in segment order: pair-major, side g before side h, source residue ascending, then partner residue
+     ascending.
+     rescontact_offsets [2P + 1] (int64)   the row range of every source side, in the order of side_offsets; [2P] = Q
+     rescontact_residues [Q][2] (int32)    the batch-wide residue of the source and of the partner
+     rescontact_counts [Q][2] (int32)      n_rows, n_points
+     rescontact_area [Q] (fp64)
+     rescontact_reverse [Q] (int32)        the folded row of the same pair that runs from the partner segment to the source
+                                           segment, or -1: the partner buries points of the source and loses none to it (the
+                                           small atom inside the large one does not bury the large one).  reverse[k] = r >= 0
+                                           gives reverse[r] = k and the two rows' residues swapped.
+     Nothing else symmetrises the table: the caller adds or averages the two directions as they see fit.
+   Capacities.  As above, with rescontact_capacity in rows (rescontact_offsets goes by pair_capacity).  The five counts are set
+     first, then the capacities are held against P, M, C, D_b and Q in this order - "rescontact_capacity %lld is too small: the
+     interfaces have %lld residue contact rows" - before any of the caller's arrays is written.  Q <= C: arrays of C rows always
+     suffice.
+   P == 0 or no buried point: Q = 0 and rescontact_offsets, where delivered, is all zeros ([1] without a pair).
+   Refused with a message before a device is touched: everything the contact entry refuses, everything the per-residue entry
+     refuses about res_first and n_res, rescontact_capacity < 0.
+   One stream synchronization more than freesasa_gpu_interface_contacts_dev (Q comes back to the host before delivery).
+   Not offered: Lee-Richards; the file sweep and the trajectory drivers; periodic images; class splits; a table with both
+     directions added.
+
+   freesasa_gpu_interface_residue_contacts_dev: the contact entry's arguments, then res_first, n_res, rescontact_capacity,
+     n_rescontacts_out and the five DEVICE arrays; d_rescontact_area is required, the other four may be NULL and are then not
+     delivered.
+   freesasa_gpu_calc_interface_residue_contacts: the same on host arrays, on a pooled context, as its siblings.
+   Both: 0, or -1 with the context's error text / err_out; the context stays usable. */
+int freesasa_gpu_interface_residue_contacts_dev(freesasa_gpu_ctx *ctx, int alg, const double *d_xyz, const double *d_radii,
+                                                const int64_t *offsets, int n_structs, const int32_t *d_group, const int32_t *n_groups,
+                                                double probe_radius, int resolution,
+                                                double *d_sasa, double *d_iso, double *d_totals, double *d_group_totals,
+                                                long long pair_capacity, long long atom_capacity, long long contact_capacity,
+                                                long long dot_capacity,
+                                                long long *n_pairs_out, long long *n_pair_atoms_out, long long *n_contacts_out,
+                                                long long *n_buried_dots_out,
+                                                int32_t *d_pair_struct, int32_t *d_pair_groups, double *d_pair_areas,
+                                                int64_t *d_side_offsets, int32_t *d_pair_atom, double *d_pair_buried,
+                                                int64_t *d_contact_first, int32_t *d_contact_partner, int32_t *d_contact_points,
+                                                double *d_contact_area, uint32_t *d_buried_masks, int32_t *d_dot_partner,
+                                                const int64_t *res_first, int n_res, long long rescontact_capacity,
+                                                long long *n_rescontacts_out, int64_t *d_rescontact_offsets,
+                                                int32_t *d_rescontact_residues, int32_t *d_rescontact_counts,
+                                                double *d_rescontact_area, int32_t *d_rescontact_reverse);
+int freesasa_gpu_calc_interface_residue_contacts(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
+                                                 const int32_t *group, const int32_t *n_groups, int alg, double probe_radius,
+                                                 int resolution,
+                                                 double *sasa_out, double *iso_out, double *totals_out, double *group_totals_out,
+                                                 long long pair_capacity, long long atom_capacity, long long contact_capacity,
+                                                 long long dot_capacity,
+                                                 long long *n_pairs_out, long long *n_pair_atoms_out, long long *n_contacts_out,
+                                                 long long *n_buried_dots_out,
+                                                 int32_t *pair_struct_out, int32_t *pair_groups_out, double *pair_areas_out,
+                                                 int64_t *side_offsets_out, int32_t *pair_atom_out, double *pair_buried_out,
+                                                 int64_t *contact_first_out, int32_t *contact_partner_out, int32_t *contact_points_out,
+                                                 double *contact_area_out, uint32_t *buried_masks_out, int32_t *dot_partner_out,
+                                                 const int64_t *res_first, int n_res, long long rescontact_capacity,
+                                                 long long *n_rescontacts_out, int64_t *rescontact_offsets_out,
+                                                 int32_t *rescontact_residues_out, int32_t *rescontact_counts_out,
+                                                 double *rescontact_area_out, int32_t *rescontact_reverse_out,
+                                                 int device, char *err_out, int err_len);
 
 /* MOLECULAR VOLUME: the volume enclosed by the solvent-accessible surface of every structure, made of the Shrake-Rupley test
    points by the divergence theorem - what `gmx sasa -tv` prints per frame, in the same formulation:

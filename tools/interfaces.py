@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/interfaces.py STRUCTURE... [--chain-groups SPEC | --separate-chains] -o OUT.tsv [--alg lr|sr] [--resolution N] [--probe P]
-                       [--residues RES.tsv [--min-buried X]] [--contacts ATOMS.tsv [--residue-contacts RES.tsv]]
+                       [--residues RES.tsv [--min-buried X]] [--contacts ATOMS.tsv [--residue-contacts RES.tsv]] [--contact-map MAP.tsv]
 
 The interface areas between the chain groups of structure files (freesasa_amd.calc_interfaces): one line per pair of groups
 that are in contact - file, the two groups' chain labels, the atoms of each side, and six areas in A^2: each side's isolated
@@ -16,7 +16,13 @@ area, its area in the pair and the difference.  OUT.tsv is the same with and wit
 calc_interface_contacts, made on the device): one line per row - file, the two groups' labels, then chain, residue name, residue
 number and atom name of the buried atom and of the partner atom that buries it, the test points and the area in A^2.  The table is
 directed: a -> b and b -> a are rows of their own.  --residue-contacts RES.tsv folds these rows per (pair, residue of the buried
-atom, residue of the partner) here, with numpy: the points summed, the areas added in row order."""
+atom, residue of the partner) here, with numpy: the points summed, the areas added in row order.
+--contact-map MAP.tsv (Shrake-Rupley only, with or without --contacts) writes the residue-residue contact map folded on the device
+(calc_interface_contacts with res_first): one line per unordered pair of residues of every interface - file, the two groups'
+labels, chain, name and number of group a's residue and of group b's residue, then the contact rows folded, the test points and
+the area in A^2 that b's residue buries of a's (a -> b), and the same three for b -> a, zeros where there is no such row.  Per
+interface the lines are side a's folded rows in the table's order, each joined to its reverse row, then side b's rows that have
+no reverse."""
 import argparse
 import os
 import sys
@@ -107,6 +113,27 @@ def format_residue_contact_rows(files, labels, pair_struct, pair_groups, fold, r
     return out
 
 
+CONTACT_MAP_HEADER = ("file\tgroup_a\tgroup_b\tchain_a\tres_name_a\tres_number_a\tchain_b\tres_name_b\tres_number_b\t"
+                      "rows_ab\tpoints_ab\tarea_ab\trows_ba\tpoints_ba\tarea_ba")
+
+
+def format_contact_map_rows(files, labels, pair_struct, pair_groups, offsets, residues, counts, area, reverse, res_chain, res_name, res_number):
+    """the contact map's records, one string per unordered residue pair (no line ends): per pair of groups side a's folded rows
+    in their order, each with its reverse row, then side b's rows whose reverse is -1.  The five rescontact arrays of
+    calc_interface_contacts(res_first=...) are taken as they are."""
+    out = []
+    tag = lambda r: [str(res_chain[r]).strip() or "_", str(res_name[r]).strip(), str(res_number[r]).strip()]
+    three = lambda k: ["0", "0", "%.3f" % 0.0] if k < 0 else [str(int(counts[k][0])), str(int(counts[k][1])), "%.3f" % float(area[k])]
+    for p, (s, (g, h)) in enumerate(zip(pair_struct, pair_groups)):
+        head = [files[int(s)], labels[int(s)][int(g)], labels[int(s)][int(h)]]
+        for k in range(int(offsets[2 * p]), int(offsets[2 * p + 1])):
+            out.append("\t".join(head + tag(int(residues[k][0])) + tag(int(residues[k][1])) + three(k) + three(int(reverse[k]))))
+        for k in range(int(offsets[2 * p + 1]), int(offsets[2 * p + 2])):
+            if int(reverse[k]) < 0:
+                out.append("\t".join(head + tag(int(residues[k][1])) + tag(int(residues[k][0])) + three(-1) + three(k)))
+    return out
+
+
 def group_labels(batch, group, n_groups):
     """per structure, per group: the chain labels of its atoms in order of appearance, joined"""
     import numpy as np
@@ -141,6 +168,7 @@ def main(argv=None):
     ap.add_argument("--min-buried", type=float, default=0.0)
     ap.add_argument("--contacts", default=None, metavar="ATOMS.tsv")
     ap.add_argument("--residue-contacts", default=None, metavar="RES.tsv")
+    ap.add_argument("--contact-map", default=None, metavar="MAP.tsv")
     args = ap.parse_args(argv)
     if args.chain_groups and args.separate_chains:
         sys.exit("--chain-groups and --separate-chains exclude each other")
@@ -148,6 +176,8 @@ def main(argv=None):
         sys.exit("--residue-contacts needs --contacts")
     if args.contacts and args.alg != "sr":
         sys.exit("--contacts is made of Shrake-Rupley test points: give --alg sr (Lee-Richards has no contact table)")
+    if args.contact_map and args.alg != "sr":
+        sys.exit("--contact-map is made of Shrake-Rupley test points: give --alg sr (Lee-Richards has no contact table)")
     import freesasa_amd as fa
     from freesasa_amd import ingest
     batch = ingest.load_files(args.structures)
@@ -178,10 +208,21 @@ def main(argv=None):
                                             batch.res_number):
                 f.write(line + "\n")
         print(f"{got.n_res_rows} interface residues -> {args.residues}")
+    if args.contacts or args.contact_map:
+        ct = fa.calc_interface_contacts(batch.xyz, batch.radii, batch.offsets, group, n_groups, probe=args.probe, n_points=res,
+                                        res_first=batch.res_first if args.contact_map else None)
+        files = [os.path.basename(p) for p in args.structures]
+    if args.contact_map:
+        with open(args.contact_map, "w") as f:
+            f.write(CONTACT_MAP_HEADER + "\n")
+            lines = format_contact_map_rows(files, labels, ct.pair_struct, ct.pair_groups, ct.rescontact_offsets, ct.rescontact_residues,
+                                            ct.rescontact_counts, ct.rescontact_area, ct.rescontact_reverse, batch.res_chain, batch.res_name,
+                                            batch.res_number)
+            for line in lines:
+                f.write(line + "\n")
+        print(f"{len(lines)} residue pairs in contact -> {args.contact_map}")
     if args.contacts:
         import numpy as np
-        ct = fa.calc_interface_contacts(batch.xyz, batch.radii, batch.offsets, group, n_groups, probe=args.probe, n_points=res)
-        files = [os.path.basename(p) for p in args.structures]
         atom_res = np.repeat(np.arange(batch.n_residues, dtype=np.int64), np.diff(batch.res_first))
         atom_name = [v.decode() for v in batch.atom_name_raw.tolist()]
         row_pair, atom_i, atom_j = contact_row_keys(ct.side_offsets, ct.pair_atom, ct.contact_first, ct.contact_partner)
