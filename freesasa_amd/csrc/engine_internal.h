@@ -250,8 +250,8 @@ struct freesasa_gpu_ctx {
     unsigned *sr_masks = nullptr;
     DevBuf dt_masks, dt_first, dt_bsum, dt_xyz, dt_atom, dt_point, dt_unit;
     /* interfaces between chain groups (gpu_interfaces.hip): group starts and test bases; boxes; the candidates' list, its length
-       and the flags; the sides' tables; the pair batch, its areas and what is made of them; the host-pointer entry's rows */
-    DevBuf if_meta, if_box, if_cand, if_flag, if_sides, if_xyz, if_radii, if_comb, if_sasa, if_inpair, if_areas, if_patom, if_pburied, if_rows;
+       and the flags; the sides' tables; the pair batch, its areas and what is made of them */
+    DevBuf if_meta, if_box, if_cand, if_flag, if_sides, if_xyz, if_radii, if_comb, if_sasa, if_inpair, if_areas, if_patom, if_pburied;
     /* ... their per-residue tables: the residue boundaries; the int32 work arrays; the segments' areas; the table itself */
     DevBuf if_rfirst, if_rwork, if_rsegs, if_rtable;
     /* ... their atom-atom contact tables: the side, pair and buried masks with the two runs' areas; the atoms' int32 work arrays
@@ -352,6 +352,24 @@ int groups_resident(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const dou
    groups_resident's. */
 int groups_cut(freesasa_gpu_ctx *c, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
                const int32_t *d_group, const int32_t *n_groups, sasa::GrpArgs &ga, std::vector<int64_t> &comb, std::vector<int> &cnt);
+#define GRP_MAX_PER_STRUCT 65535 /* groups of a structure */
+/* The grouped host batch - freesasa_gpu_calc_groups, its periodic forms (gpu_periodic.hip) and the interface entries' host form
+   (gpu_interfaces.hip): host arrays with group ids as ONE chunk of the host-batch path (below), in place.  The caller fills the
+   first two lines and runs its pipeline between the two calls, on the d_* pointers; -1: it owes chunk_failed.
+   upload: G, the groups of all structures (a bad count is refused by the pipeline, with its message: staged for none here);
+   the chunk's buffers and c->h_group, h_iso, h_gtot sized; xyz, radii and group enqueued; the d_* set (d_totals,
+   d_group_totals: null where the caller's array is).  download: sasa, iso, totals and group_totals enqueued to the caller's
+   arrays that are not null.  Nothing is waited for. */
+struct BatchCall;
+struct GroupBatch {
+    const double *xyz = nullptr, *radii = nullptr; const int64_t *offsets = nullptr; int n_structs = 0; const int32_t *group = nullptr, *n_groups = nullptr;
+    double *sasa_out = nullptr, *iso_out = nullptr, *totals_out = nullptr, *group_totals_out = nullptr;
+    int64_t G = 0;
+    const double *d_xyz = nullptr, *d_radii = nullptr; const int32_t *d_group = nullptr;
+    double *d_sasa = nullptr, *d_iso = nullptr, *d_totals = nullptr, *d_group_totals = nullptr;
+};
+int group_batch_upload(const BatchCall &b, freesasa_gpu_ctx *c, GroupBatch &g);
+int group_batch_download(freesasa_gpu_ctx *c, const GroupBatch &g);
 
 /* ------------------------------------------------------------------ periodic images (gpu_periodic.hip) */
 

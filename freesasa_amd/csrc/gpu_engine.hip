@@ -134,7 +134,7 @@ extern "C" void freesasa_gpu_ctx_destroy(freesasa_gpu_ctx *c)
                      &c->v_counts, &c->v_evec, &c->v_vol, &c->v_origin, &c->v_volumes,
                      &c->dt_masks, &c->dt_first, &c->dt_bsum, &c->dt_xyz, &c->dt_atom, &c->dt_point, &c->dt_unit,
                      &c->if_meta, &c->if_box, &c->if_cand, &c->if_flag, &c->if_sides, &c->if_xyz, &c->if_radii, &c->if_comb, &c->if_sasa,
-                     &c->if_inpair, &c->if_areas, &c->if_patom, &c->if_pburied, &c->if_rows,
+                     &c->if_inpair, &c->if_areas, &c->if_patom, &c->if_pburied,
                      &c->if_rfirst, &c->if_rwork, &c->if_rsegs, &c->if_rtable,
                      &c->if_cmasks, &c->if_cwork, &c->if_cdots, &c->if_ctable,
                      &c->if_rcwork, &c->if_rctable};

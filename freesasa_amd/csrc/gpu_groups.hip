@@ -14,9 +14,10 @@
  *
  * groups_cut is stages 1 and 2 alone, for chain groups among periodic images (gpu_periodic.hip puts the periodic stage between
  * the cut and the finish).  groups_resident is that pipeline for callers whose arrays are on the context's stream (the file sweep, gpu_sweep.hip);
- * freesasa_gpu_calc_groups brings host arrays to it with the host-batch path's sizing, upload and failure epilogue
- * (chunk_size, chunk_upload, chunk_failed: gpu_hostbatch.hip) and its own extras; below it, the group ids themselves made
- * on the device from residues and chain labels (k_gid_struct).
+ * freesasa_gpu_calc_groups brings host arrays to it as the grouped host batch (group_batch_upload / _download: the host-batch
+ * path's sizing, upload and failure epilogue - chunk_size, chunk_upload, chunk_failed: gpu_hostbatch.hip - and the groups'
+ * extras), which its periodic forms (gpu_periodic.hip) and the interface entries (gpu_interfaces.hip) share; below it, the
+ * group ids themselves made on the device from residues and chain labels (k_gid_struct).
  */
 #include <hip/hip_runtime.h>
 
@@ -30,8 +31,6 @@
 #include "engine_internal.h"
 
 using namespace sasa;
-
-#define GRP_MAX_PER_STRUCT 65535
 
 static_assert(GID_EGROUP == FREESASA_INGEST_EGROUP && GID_MAX_PER_STRUCT == GRP_MAX_PER_STRUCT && GID_MAX_LABELS == FREESASA_INGEST_MAX_GROUP_LABELS, "group_kernels.h");
 
@@ -189,6 +188,36 @@ extern "C" int freesasa_gpu_groups_dev(freesasa_gpu_ctx *c, int alg, const doubl
     });
 }
 
+/* (engine_internal.h) */
+int group_batch_upload(const BatchCall &b, freesasa_gpu_ctx *c, GroupBatch &g)
+{
+    const size_t n = (size_t)g.offsets[g.n_structs];
+    g.G = 0;
+    for (int s = 0; s < g.n_structs; ++s) g.G += g.n_groups[s] > 0 && g.n_groups[s] <= GRP_MAX_PER_STRUCT ? g.n_groups[s] : 0;
+    Chunk h;
+    h.ns = g.n_structs; h.n = n; h.off = g.offsets; h.xyz = g.xyz; h.radii = g.radii;
+    if (chunk_size(b, c, h) || ensure(c, c->h_group, 4 * n) || ensure(c, c->h_iso, 8 * n) || ensure(c, c->h_gtot, 24 * (size_t)g.G + 8)) return -1;
+    if (chunk_upload(c, h)) return -1;
+    if (hipMemcpyAsync(c->h_group.p, g.group, 4 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "host-to-device copy failed");
+    g.d_xyz = (const double *)c->h_xyz.p; g.d_radii = (const double *)c->h_radii.p; g.d_group = (const int32_t *)c->h_group.p;
+    g.d_sasa = (double *)c->h_sasa.p; g.d_iso = (double *)c->h_iso.p;
+    g.d_totals = g.totals_out ? (double *)c->h_totals.p : nullptr; g.d_group_totals = g.group_totals_out ? (double *)c->h_gtot.p : nullptr;
+    return 0;
+}
+
+/* (engine_internal.h) */
+int group_batch_download(freesasa_gpu_ctx *c, const GroupBatch &g)
+{
+    const size_t n = (size_t)g.offsets[g.n_structs];
+    hipStream_t st = c->stream;
+    if ((g.sasa_out && hipMemcpyAsync(g.sasa_out, g.d_sasa, 8 * n, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        (g.iso_out && hipMemcpyAsync(g.iso_out, g.d_iso, 8 * n, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        (g.totals_out && hipMemcpyAsync(g.totals_out, g.d_totals, 8 * (size_t)g.n_structs, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        (g.group_totals_out && g.G > 0 && hipMemcpyAsync(g.group_totals_out, g.d_group_totals, 24 * (size_t)g.G, hipMemcpyDeviceToHost, st) != hipSuccess))
+        return ctx_fail(c, "device-to-host copy failed");
+    return 0;
+}
+
 extern "C" int freesasa_gpu_calc_groups(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
                                         const int32_t *group, const int32_t *n_groups, int alg, double probe_radius,
                                         int resolution, double *sasa_out, double *iso_out, double *totals_out,
@@ -203,28 +232,16 @@ extern "C" int freesasa_gpu_calc_groups(const double *xyz, const double *radii, 
     PoolLease lease(device);
     freesasa_gpu_ctx *c = lease.c;
     if (!c) return set_err(err_out, err_len, "could not create a GPU context");
-    const size_t n = (size_t)offsets[n_structs];
-    int64_t G = 0; /* (bad counts are refused by freesasa_gpu_groups_dev, with its message: staged for none here) */
-    for (int s = 0; s < n_structs; ++s) G += n_groups[s] > 0 && n_groups[s] <= GRP_MAX_PER_STRUCT ? n_groups[s] : 0;
-    /* the batch as one chunk of the host-batch path, in place: its sizing, upload and failure epilogue; the groups' extras here */
     const BatchCall b; /* (nothing staged, no counts, the fallback text of the batches) */
-    Chunk h;
-    h.ns = n_structs; h.n = n; h.off = offsets; h.xyz = xyz; h.radii = radii;
+    GroupBatch g;
+    g.xyz = xyz; g.radii = radii; g.offsets = offsets; g.n_structs = n_structs; g.group = group; g.n_groups = n_groups;
+    g.sasa_out = sasa_out; g.iso_out = iso_out; g.totals_out = totals_out; g.group_totals_out = group_totals_out;
     const int rc = [&]() -> int {
-        if (chunk_size(b, c, h) || ensure(c, c->h_group, 4 * n) || ensure(c, c->h_iso, 8 * n) || ensure(c, c->h_gtot, 24 * (size_t)G + 8)) return -1;
-        if (chunk_upload(c, h)) return -1;
-        if (hipMemcpyAsync(c->h_group.p, group, 4 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "host-to-device copy failed");
-        if (freesasa_gpu_groups_dev(c, alg, (const double *)c->h_xyz.p, (const double *)c->h_radii.p, offsets, n_structs,
-                                    (const int32_t *)c->h_group.p, n_groups, probe_radius, resolution, (double *)c->h_sasa.p,
-                                    (double *)c->h_iso.p, totals_out ? (double *)c->h_totals.p : nullptr,
-                                    group_totals_out ? (double *)c->h_gtot.p : nullptr))
+        if (group_batch_upload(b, c, g)) return -1;
+        if (freesasa_gpu_groups_dev(c, alg, g.d_xyz, g.d_radii, offsets, n_structs, g.d_group, n_groups, probe_radius, resolution, g.d_sasa,
+                                    g.d_iso, g.d_totals, g.d_group_totals))
             return -1;
-        if (hipMemcpyAsync(sasa_out, c->h_sasa.p, 8 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-            hipMemcpyAsync(iso_out, c->h_iso.p, 8 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-            (totals_out && hipMemcpyAsync(totals_out, c->h_totals.p, 8 * (size_t)n_structs, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-            (group_totals_out && G > 0 &&
-             hipMemcpyAsync(group_totals_out, c->h_gtot.p, 24 * (size_t)G, hipMemcpyDeviceToHost, c->stream) != hipSuccess))
-            return ctx_fail(c, "device-to-host copy failed");
+        if (group_batch_download(c, g)) return -1;
         if (hipStreamSynchronize(c->stream) != hipSuccess) return ctx_fail(c, "stream synchronize failed");
         return 0;
     }();

@@ -1,10 +1,19 @@
 /*
  * gpu_interfaces.hip — pairwise interface areas between chain groups (include/freesasa_gpu.h: freesasa_gpu_interface_pairs_dev,
- * freesasa_gpu_interfaces_dev, freesasa_gpu_calc_interface_pairs, freesasa_gpu_calc_interfaces) and their per-residue tables
- * (freesasa_gpu_interface_residues_dev, freesasa_gpu_calc_interface_residues) and atom-atom contact tables
- * (freesasa_gpu_interface_contacts_dev, freesasa_gpu_calc_interface_contacts).  Host code; the kernels are in gpu_kernels.hip
- * (phase functions: iface_kernels.h, contact_kernels.h).
+ * freesasa_gpu_interfaces_dev, freesasa_gpu_calc_interface_pairs, freesasa_gpu_calc_interfaces), their per-residue tables
+ * (freesasa_gpu_interface_residues_dev, freesasa_gpu_calc_interface_residues), atom-atom contact tables
+ * (freesasa_gpu_interface_contacts_dev, freesasa_gpu_calc_interface_contacts) and residue-residue contact tables
+ * (freesasa_gpu_interface_residue_contacts_dev, freesasa_gpu_calc_interface_residue_contacts).  Host code; the kernels are in
+ * gpu_kernels.hip (phase functions: iface_kernels.h, contact_kernels.h, rescontact_kernels.h).
  *
+ * The ten entries are ONE path.  An IfaceCall is what an entry was called with, filled by field name; an IfaceRun what the call
+ * produced and what has to outlive the stream's work.  iface_dev (arrays on the context's stream) and iface_host (host arrays: the
+ * grouped host batch of gpu_groups.hip, in place) both go through
+ *   iface_bad_call    every refusal before a device is touched, in one order
+ *   iface_run         the stages below, each count output set as soon as the count is known, the capacities held once
+ *   iface_deliver     the one table of outputs (iface_outputs), walked for device and for host destinations
+ *
+ * The stages of iface_run:
  *   1. groups_resident   the chain-group pipeline as it is: the combined batch stays in c->g_xyz / g_radii / g_src, its areas in
  *                        c->g_sasa, its totals in c->g_tot; the groups' atom counts are on the host
  *   2. boxes             k_iface_box: one wave per isolated group
@@ -15,37 +24,29 @@
  *   6. pair batch        k_iface_gather: one thread per pair-structure atom
  *   7. one run_batch     over the P pair structures: same algorithm, probe, resolution and unit points
  *   8. finish            k_iface_finish_atom, kl_segment_sums over the 2 P sides, k_iface_finish_row
+ *   9. residues          (the residue entries) k_iface_res_head, the block scan, k_iface_res_first, k_iface_res_segment, the scan
+ *                        again, k_iface_res_rows; R comes back (one more stream synchronization); the table stays in c->if_rtable
+ *  10. contacts          (the contact entries; Shrake-Rupley only) two more engine runs over the M pair-structure atoms with the
+ *                        mask request (masks_resident: as the P pair structures, as the 2 P sides), k_contact_masks, the dots' scan -
+ *                        D_b comes back (one stream synchronization) and sizes what follows - the dots' expansion,
+ *                        k_contact_attribute, k_contact_rows_count / _rank, the block scan, k_contact_rows_write; C and the flag
+ *                        come back (one more); the table stays in c->if_ctable, the masks in c->if_cmasks, the dots in c->if_cdots
+ *  11. residue contacts  (the residue-residue contact entries, behind 10) the per-residue tables' k_iface_res_head, block scan and
+ *                        k_iface_res_first (the segments), k_rc_fold_count, the block scan, k_rc_fold_write, k_rc_reverse; Q comes
+ *                        back (one more stream synchronization); the table stays in c->if_rctable
  *
- * iface_screen is steps 1 to 5, iface_pipeline all of them; the pipeline's results stay in the context's own buffers and the
- * entries deliver them - to device arrays or to host arrays - once the capacities have been held against P and M, so that a
- * call that fails for its capacities has written none of the caller's pair arrays.
- *
- * The residue entries run iface_pipeline as it is and one more stage behind it:
- *   9. residues          iface_residues: k_iface_res_head, the block scan, k_iface_res_first, k_iface_res_segment, the scan again,
- *                        k_iface_res_rows; R comes back (one more stream synchronization); the table stays in c->if_rtable
- * and hold the three capacities against P, M and R together, once R is known (iface_res_check_caps), before anything is delivered.
- *
- * The contact entries (freesasa_gpu_interface_contacts_dev, freesasa_gpu_calc_interface_contacts; Shrake-Rupley only; phase
- * functions: contact_kernels.h) likewise run iface_pipeline as it is and one more stage behind it:
- *  10. contacts          iface_contacts: two more engine runs over the M pair-structure atoms with the mask request (masks_resident:
- *                        as the P pair structures, as the 2 P sides), k_contact_masks, the dots' scan - D_b comes back (one stream
- *                        synchronization) and sizes what follows - the dots' expansion, k_contact_attribute, k_contact_rows_count /
- *                        _rank, the block scan, k_contact_rows_write; C and the flag come back (one more); the table stays in
- *                        c->if_ctable, the masks in c->if_cmasks, the dots in c->if_cdots
- * and hold the four capacities against P, M, C and D_b together (iface_contact_check_caps) before anything is delivered.
- *
- * The residue-residue contact entries (freesasa_gpu_interface_residue_contacts_dev, freesasa_gpu_calc_interface_residue_contacts;
- * phase functions: rescontact_kernels.h) run the contact entries' path as it is and one more stage behind it:
- *  11. residue contacts  iface_rescontacts: the per-residue tables' k_iface_res_head, block scan and k_iface_res_first (the segments),
- *                        k_rc_fold_count, the block scan, k_rc_fold_write, k_rc_reverse; Q comes back (one more stream
- *                        synchronization); the table stays in c->if_rctable
- * and hold the five capacities against P, M, C, D_b and Q together (iface_rescontact_check_caps) before anything is delivered.
+ * iface_screen is steps 1 to 5, iface_pairs steps 6 to 8; every stage leaves its results in the context's own buffers.  The
+ * capacities are held against the counts in ONE place (iface_check_caps: P, M, R, C, D_b, Q in this order): behind the screen and
+ * before steps 6 to 8 for the entries that end there or at step 8, behind the last stage - once all counts are known and set - for
+ * the others; iface_deliver runs only behind it, so that a call that fails for a capacity has written none of the caller's pair,
+ * atom, residue, contact or dot arrays.
  */
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <array>
 #include <vector>
 
 #include "engine_internal.h"
@@ -53,6 +54,43 @@
 using namespace sasa;
 
 namespace {
+
+/* What an entry was called with.  The batch and the four group outputs are where the pipeline reads and writes them: the caller's
+   device arrays (iface_dev), or - behind the upload - the context's staging (iface_host).  A null output array is not delivered
+   and asks for no capacity; a stage's own fields are looked at only where the stage is wanted. */
+struct IfaceCall {
+    const double *xyz = nullptr, *radii = nullptr;
+    const int64_t *offsets = nullptr;
+    int n_structs = 0;
+    const int32_t *group = nullptr, *n_groups = nullptr;
+    int alg = 0, resolution = 0;
+    double probe = 0;
+    double *sasa = nullptr, *iso = nullptr, *totals = nullptr, *group_totals = nullptr;
+    /* the stages behind the screen: steps 6 to 8, 9, 10, 11 (11 needs 10; 9 and 10 need 6 to 8) */
+    bool whole = false, residues = false, contacts = false, rescontacts = false;
+    const int64_t *res_first = nullptr;
+    int n_res = 0;
+    double min_buried = 0;
+    long long pair_capacity = 0, atom_capacity = 0, res_capacity = 0, contact_capacity = 0, dot_capacity = 0, rescontact_capacity = 0;
+    long long *n_pairs = nullptr, *n_pair_atoms = nullptr, *n_res_rows = nullptr, *n_contacts = nullptr, *n_buried_dots = nullptr,
+              *n_rescontacts = nullptr;
+    long long *stats = nullptr; /* host: the tests and the candidates of the screen */
+    /* the tables' arrays, all on the device (out_dev) or all on the host */
+    bool out_dev = false;
+    int32_t *pair_struct = nullptr, *pair_groups = nullptr, *pair_atom = nullptr;
+    double *pair_areas = nullptr, *pair_buried = nullptr;
+    int64_t *side_offsets = nullptr;
+    int64_t *res_offsets = nullptr;
+    int32_t *res_index = nullptr, *res_atoms = nullptr;
+    double *res_areas = nullptr;
+    int64_t *contact_first = nullptr;
+    int32_t *contact_partner = nullptr, *contact_points = nullptr, *dot_partner = nullptr;
+    double *contact_area = nullptr;
+    uint32_t *buried_masks = nullptr;
+    int64_t *rescontact_offsets = nullptr;
+    int32_t *rescontact_residues = nullptr, *rescontact_counts = nullptr, *rescontact_reverse = nullptr;
+    double *rescontact_area = nullptr;
+};
 
 struct IfacePlan {
     int64_t P = 0, M = 0, T = 0, n_cand = 0;
@@ -65,25 +103,58 @@ struct IfacePlan {
     std::vector<int64_t> meta;                     /* the upload: gstart [G + 1] | tbase [n_structs + 1] */
     std::vector<double> tp;                        /* S&R test points */
 };
+/* the tables of steps 9 to 11 where the stages left them, on the device; a pointer is null where the stage made no such array
+   (no pair; no buried point; no folded row), and iface_outputs' rows say what the caller gets then */
+struct IfaceResTable { /* c->if_rtable: res_offsets [2 P + 1] | res_areas [3 M] | res_index [M] | res_atoms [M], R rows of them used */
+    int64_t R = 0;
+    const int64_t *off = nullptr;
+    const double *areas = nullptr;
+    const int32_t *index = nullptr, *atoms = nullptr;
+};
+struct IfaceContactTable { /* c->if_ctable: contact_first [M + 1] | contact_area [D_b] | contact_partner [D_b] | contact_points [D_b], C rows used */
+    int64_t C = 0, D = 0;
+    const int64_t *first = nullptr;
+    const int32_t *partner = nullptr, *points = nullptr, *dot_partner = nullptr; /* (dot_partner: in c->if_cdots) */
+    const double *area = nullptr;
+    const unsigned *buried = nullptr; /* in c->if_cmasks */
+};
+struct IfaceResContactTable { /* c->if_rctable: rescontact_offsets [2 P + 1] | _area [C] | _residues [2 C] | _counts [2 C] | _reverse [C], Q rows used */
+    int64_t Q = 0;
+    const int64_t *off = nullptr;
+    const double *area = nullptr;
+    const int32_t *res = nullptr, *cnt = nullptr, *rev = nullptr;
+};
+/* What a call produced: the plan with P and M, the three tables with R, C and D_b, Q.  Its host arrays are the sources of copies
+   enqueued on the stream - the plan's uploads and deliveries, res_first -, so it is ONE object that lives until the stream is
+   idle: declared before the final synchronize in iface_dev and before the PoolLease in iface_host. */
+struct IfaceRun {
+    IfacePlan pl;
+    IfaceArgs ia;
+    IfaceResTable rt;
+    IfaceContactTable ct;
+    IfaceResContactTable qt;
+    std::vector<int64_t> res_first; /* the upload of res_first: what the device searches is what was copied here, whatever
+                                       becomes of the caller's array while the stream runs */
+};
 
-/* what every entry checks before a device is touched: 0, or the message in msg */
-int iface_bad_args(const void *xyz, const void *radii, const int64_t *offsets, int n_structs, const void *group, const int32_t *n_groups,
-                   int alg, int resolution, char *msg, size_t len)
+/* ------------------------------------------------------------------ the refusals before a device is touched */
+
+int iface_bad_batch(const IfaceCall &k, char *msg, size_t len)
 {
     const char *bad = nullptr;
-    if (!xyz || !radii || !offsets || !group || !n_groups) bad = "null argument";
-    else if (alg != 0 && alg != 1) { snprintf(msg, len, "unknown algorithm %d", alg); return -1; }
-    else if (n_structs <= 0) bad = "n_structs must be > 0";
-    else if (resolution <= 0) bad = "resolution must be > 0";
-    else if (offsets[0] != 0) bad = "offsets[0] must be 0";
+    if (!k.xyz || !k.radii || !k.offsets || !k.group || !k.n_groups) bad = "null argument";
+    else if (k.alg != 0 && k.alg != 1) { snprintf(msg, len, "unknown algorithm %d", k.alg); return -1; }
+    else if (k.n_structs <= 0) bad = "n_structs must be > 0";
+    else if (k.resolution <= 0) bad = "resolution must be > 0";
+    else if (k.offsets[0] != 0) bad = "offsets[0] must be 0";
     if (bad) { snprintf(msg, len, "%s", bad); return -1; }
-    for (int s = 0; s < n_structs; ++s)
-        if (offsets[s + 1] < offsets[s]) { snprintf(msg, len, "offsets must be non-decreasing"); return -1; }
-    if (offsets[n_structs] <= 0) { snprintf(msg, len, "empty batch"); return -1; }
+    for (int s = 0; s < k.n_structs; ++s)
+        if (k.offsets[s + 1] < k.offsets[s]) { snprintf(msg, len, "offsets must be non-decreasing"); return -1; }
+    if (k.offsets[k.n_structs] <= 0) { snprintf(msg, len, "empty batch"); return -1; }
     int64_t T = 0;
-    for (int s = 0; s < n_structs; ++s) {
-        const int64_t ng = n_groups[s];
-        if (ng > IF_MAX_GROUPS && ng <= 65535) { /* (a count the chain-group entry refuses is left to it, with its message) */
+    for (int s = 0; s < k.n_structs; ++s) {
+        const int64_t ng = k.n_groups[s];
+        if (ng > IF_MAX_GROUPS && ng <= GRP_MAX_PER_STRUCT) { /* (a count the chain-group entry refuses is left to it, with its message) */
             snprintf(msg, len, "structure %d has %lld groups: interfaces are made for up to %d groups of a structure", s, (long long)ng, IF_MAX_GROUPS);
             return -1;
         }
@@ -93,37 +164,105 @@ int iface_bad_args(const void *xyz, const void *radii, const int64_t *offsets, i
             return -1;
         }
     }
+    if (k.pair_capacity < 0) { snprintf(msg, len, "pair_capacity must be >= 0 (it is %lld)", k.pair_capacity); return -1; }
+    if (k.atom_capacity < 0) { snprintf(msg, len, "atom_capacity must be >= 0 (it is %lld)", k.atom_capacity); return -1; }
     return 0;
 }
-int iface_bad_caps(long long pair_capacity, long long atom_capacity, char *msg, size_t len)
+/* res_first, for the residue entries (with min_buried and their capacity) and for the residue-residue contact entries; n_rows_out:
+   the entry's own count output */
+int iface_bad_residues(const IfaceCall &k, const long long *n_rows_out, char *msg, size_t len)
 {
-    if (pair_capacity < 0) { snprintf(msg, len, "pair_capacity must be >= 0 (it is %lld)", pair_capacity); return -1; }
-    if (atom_capacity < 0) { snprintf(msg, len, "atom_capacity must be >= 0 (it is %lld)", atom_capacity); return -1; }
+    const int64_t *first = k.res_first, *offsets = k.offsets;
+    if (!first || !n_rows_out) { snprintf(msg, len, "null argument"); return -1; }
+    if (k.n_res <= 0) { snprintf(msg, len, "n_res must be > 0"); return -1; }
+    if (k.residues) {
+        if (!(k.min_buried >= 0.0) || k.min_buried > 1.7976931348623157e308) { snprintf(msg, len, "min_buried must be finite and >= 0"); return -1; }
+        if (k.res_capacity < 0) { snprintf(msg, len, "res_capacity must be >= 0 (it is %lld)", k.res_capacity); return -1; }
+    }
+    if (first[0] != 0) { snprintf(msg, len, "res_first[0] must be 0"); return -1; }
+    for (int r = 0; r < k.n_res; ++r)
+        if (first[r + 1] < first[r]) { snprintf(msg, len, "res_first must be non-decreasing"); return -1; }
+    if (first[k.n_res] != offsets[k.n_structs]) {
+        snprintf(msg, len, "res_first[n_res] is %lld: the batch has %lld atoms", (long long)first[k.n_res], (long long)offsets[k.n_structs]);
+        return -1;
+    }
+    int s = 0;
+    for (int r = 0; r < k.n_res; ++r) {
+        const int64_t b = first[r], e = first[r + 1];
+        if (b == e) continue;
+        while (offsets[s + 1] <= b) ++s; /* (b < offsets[n_structs]: the structure that holds the residue's first atom) */
+        if (e > offsets[s + 1]) { snprintf(msg, len, "residue %d spans the boundary between structures %d and %d", r, s, s + 1); return -1; }
+    }
     return 0;
+}
+int iface_bad_contacts(const IfaceCall &k, char *msg, size_t len)
+{
+    if (!k.n_contacts) { snprintf(msg, len, "null argument"); return -1; }
+    if (k.alg != 1) { snprintf(msg, len, "the contact tables are made of Shrake-Rupley test points: Lee-Richards has none"); return -1; }
+    if (k.resolution > SR_CAP_POINTS_MAX) {
+        snprintf(msg, len, "the contact tables are offered up to %d test points (%d asked for)", SR_CAP_POINTS_MAX, k.resolution);
+        return -1;
+    }
+    if (k.contact_capacity < 0) { snprintf(msg, len, "contact_capacity must be >= 0 (it is %lld)", k.contact_capacity); return -1; }
+    if (k.dot_capacity < 0) { snprintf(msg, len, "dot_capacity must be >= 0 (it is %lld)", k.dot_capacity); return -1; }
+    if (k.out_dev && (uintptr_t)k.buried_masks % 16) {
+        snprintf(msg, len, "the buried mask array must be aligned to 16 bytes (an atom's four words are one store)");
+        return -1;
+    }
+    return 0;
+}
+/* The one argument check of all entries - the batch and its two capacities, residues, contacts, residue contacts, in this order,
+   each at most once - and the entry kind's own tail: ctx_device >= 0 is iface_dev's context (2^30 atoms, hipSetDevice, null
+   outputs), < 0 iface_host (null outputs, the device count).  0, or -1 with the message in msg. */
+int iface_bad_call(const IfaceCall &k, int ctx_device, char *msg, size_t len)
+{
+    if (iface_bad_batch(k, msg, len) || (k.residues && iface_bad_residues(k, k.n_res_rows, msg, len)) ||
+        (k.contacts && iface_bad_contacts(k, msg, len)))
+        return -1;
+    if (k.rescontacts) {
+        if (iface_bad_residues(k, k.n_rescontacts, msg, len)) return -1;
+        if (k.rescontact_capacity < 0) { snprintf(msg, len, "rescontact_capacity must be >= 0 (it is %lld)", k.rescontact_capacity); return -1; }
+    }
+    const char *bad = nullptr;
+    const bool null_out = !k.n_pairs || !k.n_pair_atoms || (k.whole && !k.pair_areas) || (k.residues && !k.res_areas) ||
+                          (k.rescontacts && !k.rescontact_area) || (ctx_device >= 0 && k.whole && (!k.sasa || !k.iso));
+    if (ctx_device >= 0) {
+        if (k.offsets[k.n_structs] > (int64_t)1 << 30) bad = "batch too large (max 2^30 atoms per call)";
+        else if (hipSetDevice(ctx_device) != hipSuccess) bad = "hipSetDevice failed";
+        else if (null_out) bad = "null argument";
+    } else {
+        if (null_out) bad = "null argument";
+        else if (freesasa_gpu_device_count() <= 0) bad = "no HIP device available: libfreesasa_amd has no CPU path";
+    }
+    if (bad) snprintf(msg, len, "%s", bad);
+    return bad ? -1 : 0;
 }
 
-/* steps 1 to 5 on arrays that are on the context's stream; at its end the stream is idle (the flags are on the host) */
-int iface_screen(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
-                 const int32_t *d_group, const int32_t *n_groups, double probe, int resolution, double *d_sasa, double *d_iso,
-                 double *d_totals, double *d_group_totals, IfacePlan &pl, IfaceArgs &ia)
+/* ------------------------------------------------------------------ the stages */
+
+/* steps 1 to 5; at its end the stream is idle (the flags are on the host) */
+int iface_screen(freesasa_gpu_ctx *c, const IfaceCall &k, IfaceRun &r)
 {
-    if (alg == 1) pl.tp = call_test_points(alg, resolution);
+    IfacePlan &pl = r.pl;
+    IfaceArgs &ia = r.ia;
+    const int n_structs = k.n_structs;
+    if (k.alg == 1) pl.tp = call_test_points(k.alg, k.resolution);
     std::vector<int> cnt;
-    if (groups_resident(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe, resolution, alg == 1 ? pl.tp.data() : nullptr,
-                        d_sasa, d_iso, d_totals, d_group_totals, &cnt))
+    if (groups_resident(c, k.alg, k.xyz, k.radii, k.offsets, n_structs, k.group, k.n_groups, k.probe, k.resolution,
+                        k.alg == 1 ? pl.tp.data() : nullptr, k.sasa, k.iso, k.totals, k.group_totals, &cnt))
         return -1;
     const int G = (int)cnt.size();
-    const int64_t n = offsets[n_structs];
+    const int64_t n = k.offsets[n_structs];
     pl.G = G; pl.n = n;
     pl.meta.assign((size_t)G + 1 + (size_t)n_structs + 1, 0);
     int64_t *gstart = pl.meta.data(), *tbase = gstart + G + 1;
     gstart[0] = n;
-    for (int k = 0; k < G; ++k) gstart[k + 1] = gstart[k] + cnt[(size_t)k];
+    for (int g = 0; g < G; ++g) gstart[g + 1] = gstart[g] + cnt[(size_t)g];
     pl.n_iso = gstart[G] - n;
     int64_t T = 0;
     for (int s = 0; s < n_structs; ++s) {
         tbase[s] = T;
-        const int64_t ng = n_groups[s];
+        const int64_t ng = k.n_groups[s];
         T += ng * (ng - 1) / 2;
     }
     tbase[n_structs] = T;
@@ -132,7 +271,7 @@ int iface_screen(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double
     memset(&ia, 0, sizeof ia);
     ia.cxyz = (const double *)c->g_xyz.p; ia.cradii = (const double *)c->g_radii.p; ia.src = (const int *)c->g_src.p;
     ia.csasa = (const double *)c->g_sasa.p; ia.ctot = (const double *)c->g_tot.p;
-    ia.n_atoms = (int)n; ia.n_structs = n_structs; ia.n_groups = G; ia.probe = probe;
+    ia.n_atoms = (int)n; ia.n_structs = n_structs; ia.n_groups = G; ia.probe = k.probe;
     ia.gbase = (const int64_t *)c->g_meta.p + n_structs + 1;
     ia.n_tests = (int)T;
     pl.side_off.assign(1, 0);
@@ -168,16 +307,16 @@ int iface_screen(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double
     start.reserve(2 * (size_t)P); grp.reserve(2 * (size_t)P);
     int64_t t = 0, k0 = 0, M = 0;
     for (int s = 0; s < n_structs; ++s) {
-        const int ng = n_groups[s];
+        const int ng = k.n_groups[s];
         for (int g = 0; g + 1 < ng; ++g)
             for (int h = g + 1; h < ng; ++h, ++t) {
                 if (!flag[(size_t)t]) continue;
                 pl.pair_struct.push_back(s);
                 pl.pair_groups.push_back(g); pl.pair_groups.push_back(h);
                 for (int side = 0; side < 2; ++side) {
-                    const int64_t k = k0 + (side ? h : g);
-                    start.push_back(gstart[k]); grp.push_back((int32_t)k);
-                    M += cnt[(size_t)k];
+                    const int64_t q = k0 + (side ? h : g);
+                    start.push_back(gstart[q]); grp.push_back((int32_t)q);
+                    M += cnt[(size_t)q];
                     pl.side_off.push_back(M);
                 }
             }
@@ -196,35 +335,12 @@ int iface_screen(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double
     return 0;
 }
 
-/* what an entry wants delivered: held against P and M before anything of steps 6 to 8 runs */
-struct IfaceWant {
-    long long pair_capacity = 0, atom_capacity = 0;
-    bool rows = false;  /* one of pair_struct, pair_groups, pair_areas, side_offsets */
-    bool atoms = false; /* one of pair_atom, pair_buried */
-};
-int iface_check_caps(freesasa_gpu_ctx *c, const IfacePlan &pl, const IfaceWant &w)
+/* steps 6 to 8 behind the screen: the rows in c->if_areas [6 P], the per-atom arrays in c->if_patom / c->if_pburied [M]; nothing
+   is waited for at its end beyond what run_batch waits for */
+int iface_pairs(freesasa_gpu_ctx *c, const IfaceCall &k, IfaceRun &r)
 {
-    if (w.rows && pl.P > w.pair_capacity)
-        return ctx_fail(c, "pair_capacity %lld is too small: the batch has %lld pairs of groups in contact", w.pair_capacity, (long long)pl.P);
-    if (w.atoms && pl.M > w.atom_capacity)
-        return ctx_fail(c, "atom_capacity %lld is too small: the pair structures hold %lld atoms", w.atom_capacity, (long long)pl.M);
-    return 0;
-}
-
-/* the whole pipeline: the rows in c->if_areas [6 P], the per-atom arrays in c->if_patom / c->if_pburied [M]; nothing is waited
-   for at its end beyond what run_batch waits for */
-int iface_pipeline(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
-                   const int32_t *d_group, const int32_t *n_groups, double probe, int resolution, double *d_sasa, double *d_iso,
-                   double *d_totals, double *d_group_totals, const IfaceWant &w, IfacePlan &pl, long long *n_pairs_out,
-                   long long *n_pair_atoms_out)
-{
-    IfaceArgs ia;
-    if (iface_screen(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe, resolution, d_sasa, d_iso, d_totals,
-                     d_group_totals, pl, ia))
-        return -1;
-    if (n_pairs_out) *n_pairs_out = pl.P;
-    if (n_pair_atoms_out) *n_pair_atoms_out = pl.M;
-    if (iface_check_caps(c, pl, w)) return -1;
+    const IfacePlan &pl = r.pl;
+    IfaceArgs &ia = r.ia;
     if (pl.n + pl.n_iso + pl.M > (int64_t)1 << 30)
         return ctx_fail(c, "the batch (%lld atoms), its groups (%lld) and the pair structures (%lld) hold more than 2^30 atoms together",
                         (long long)pl.n, (long long)pl.n_iso, (long long)pl.M);
@@ -242,7 +358,7 @@ int iface_pipeline(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const doub
     ia.pair_buried = (double *)c->if_pburied.p; ia.pair_areas = (double *)c->if_areas.p;
     HIP_TRY(c, hipMemcpyAsync(c->if_sides.p, pl.sides.data(), 8 * pl.sides.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(c, kl_iface_gather(ia, st));
-    if (run_batch(c, alg == 0, ia.pxyz, ia.pradii, pl.pair_off.data(), (int)P, probe, resolution, alg == 1 ? pl.tp.data() : nullptr,
+    if (run_batch(c, k.alg == 0, ia.pxyz, ia.pradii, pl.pair_off.data(), (int)P, k.probe, k.resolution, k.alg == 1 ? pl.tp.data() : nullptr,
                   (double *)c->if_sasa.p, nullptr, nullptr))
         return -1;
     HIP_TRY(c, kl_segment_sums(ia.psasa, ia.side_off, (int)(2 * P), pl.M < (int64_t)64 * 2 * (int64_t)P, (double *)c->if_inpair.p, st));
@@ -250,74 +366,40 @@ int iface_pipeline(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const doub
     return 0;
 }
 
-/* the per-residue tables: what an entry gives on top of the interface entries' arguments, and what it wants back */
-struct IfaceResWant {
-    const int64_t *res_first = nullptr;
-    int n_res = 0;
-    double min_buried = 0;
-    long long res_capacity = 0;
-    long long *n_res_rows_out = nullptr;
-};
-/* ... checked before a device is touched, behind iface_bad_args and iface_bad_caps: 0, or the message in msg */
-int iface_res_bad_args(const IfaceResWant &rw, const int64_t *offsets, int n_structs, char *msg, size_t len)
+/* res_first on the device (c->if_rfirst), from the run's own copy */
+int iface_upload_res_first(freesasa_gpu_ctx *c, const IfaceCall &k, IfaceRun &r)
 {
-    if (!rw.res_first || !rw.n_res_rows_out) { snprintf(msg, len, "null argument"); return -1; }
-    if (rw.n_res <= 0) { snprintf(msg, len, "n_res must be > 0"); return -1; }
-    if (!(rw.min_buried >= 0.0) || rw.min_buried > 1.7976931348623157e308) { snprintf(msg, len, "min_buried must be finite and >= 0"); return -1; }
-    if (rw.res_capacity < 0) { snprintf(msg, len, "res_capacity must be >= 0 (it is %lld)", rw.res_capacity); return -1; }
-    if (rw.res_first[0] != 0) { snprintf(msg, len, "res_first[0] must be 0"); return -1; }
-    for (int r = 0; r < rw.n_res; ++r)
-        if (rw.res_first[r + 1] < rw.res_first[r]) { snprintf(msg, len, "res_first must be non-decreasing"); return -1; }
-    if (rw.res_first[rw.n_res] != offsets[n_structs]) {
-        snprintf(msg, len, "res_first[n_res] is %lld: the batch has %lld atoms", (long long)rw.res_first[rw.n_res], (long long)offsets[n_structs]);
-        return -1;
-    }
-    int s = 0;
-    for (int r = 0; r < rw.n_res; ++r) {
-        const int64_t b = rw.res_first[r], e = rw.res_first[r + 1];
-        if (b == e) continue;
-        while (offsets[s + 1] <= b) ++s; /* (b < offsets[n_structs]: the structure that holds the residue's first atom) */
-        if (e > offsets[s + 1]) { snprintf(msg, len, "residue %d spans the boundary between structures %d and %d", r, s, s + 1); return -1; }
-    }
+    if (ensure(c, c->if_rfirst, 8 * ((size_t)k.n_res + 1))) return -1;
+    r.res_first.assign(k.res_first, k.res_first + k.n_res + 1);
+    HIP_TRY(c, hipMemcpyAsync(c->if_rfirst.p, r.res_first.data(), 8 * r.res_first.size(), hipMemcpyHostToDevice, c->stream));
     return 0;
 }
 
-/* the stage behind iface_pipeline (k_iface_finish is the last thing on the stream): the table in c->if_rtable - res_offsets
-   [2 P + 1] | res_areas [3 M] | res_index [M] | res_atoms [M], R rows of them used; R comes back to the host (one stream
-   synchronization), so at the stage's end the stream is idle */
-struct IfaceResTable {
-    int64_t R = 0;
-    const int64_t *off = nullptr;
-    const double *areas = nullptr;
-    const int32_t *index = nullptr, *atoms = nullptr;
-    std::vector<int64_t> first; /* the upload of res_first (like the plan, the table lives until the stream is idle) */
-};
-int iface_residues(freesasa_gpu_ctx *c, const IfacePlan &pl, const IfaceResWant &rw, const double *d_iso, IfaceResTable &t)
+/* step 9 behind iface_pairs (k_iface_finish is the last thing on the stream).  R comes back to the host (one stream
+   synchronization), so at the stage's end the stream is idle. */
+int iface_residues(freesasa_gpu_ctx *c, const IfaceCall &k, IfaceRun &r)
 {
-    t.R = 0;
+    const IfacePlan &pl = r.pl;
+    IfaceResTable &t = r.rt;
     if (pl.P == 0) return 0;
     const size_t P = (size_t)pl.P, M = (size_t)pl.M;
     const size_t S = (size_t)ifr_scan_scratch(pl.M);
     hipStream_t st = c->stream;
-    if (ensure(c, c->if_rfirst, 8 * ((size_t)rw.n_res + 1)) || ensure(c, c->if_rwork, 4 * (6 * M + 3 + S) + 8) ||
-        ensure(c, c->if_rsegs, 24 * M) || ensure(c, c->if_rtable, 8 * (2 * P + 1) + 24 * M + 8 * M))
+    if (iface_upload_res_first(c, k, r) || ensure(c, c->if_rwork, 4 * (6 * M + 3 + S) + 8) || ensure(c, c->if_rsegs, 24 * M) ||
+        ensure(c, c->if_rtable, 8 * (2 * P + 1) + 24 * M + 8 * M))
         return -1;
     IfaceResArgs a;
     memset(&a, 0, sizeof a);
-    a.n_pair_atoms = pl.M; a.n_sides = 2 * pl.P; a.n_res = rw.n_res;
+    a.n_pair_atoms = pl.M; a.n_sides = 2 * pl.P; a.n_res = k.n_res;
     a.side_off = (const int64_t *)c->if_sides.p; a.pair_atom = (const int *)c->if_patom.p;
-    a.res_first = (const int64_t *)c->if_rfirst.p; a.iso = d_iso; a.psasa = (const double *)c->if_sasa.p;
-    a.min_buried = rw.min_buried;
+    a.res_first = (const int64_t *)c->if_rfirst.p; a.iso = k.iso; a.psasa = (const double *)c->if_sasa.p;
+    a.min_buried = k.min_buried;
     int *w = (int *)c->if_rwork.p;
     a.atom_res = w; a.hs = w + M; a.seg_first = a.hs + M + 1; a.seg_res = a.seg_first + M + 1; a.seg_atoms = a.seg_res + M; a.ks = a.seg_atoms + M;
     int *scratch = a.ks + M + 1;
     a.seg_areas = (double *)c->if_rsegs.p;
     a.res_off = (int64_t *)c->if_rtable.p; a.res_areas = (double *)(a.res_off + 2 * P + 1);
     a.res_index = (int *)(a.res_areas + 3 * M); a.res_atoms = a.res_index + M;
-    /* (the upload's source is the stage's own copy, as the plan's arrays are: what the device searches is what was copied here,
-       whatever becomes of the caller's array while the stream runs) */
-    t.first.assign(rw.res_first, rw.res_first + rw.n_res + 1);
-    HIP_TRY(c, hipMemcpyAsync(c->if_rfirst.p, t.first.data(), 8 * t.first.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(c, kl_iface_res_segments(a, scratch, st));
     HIP_TRY(c, kl_iface_res_rows(a, scratch, st));
     int R = 0;
@@ -326,51 +408,15 @@ int iface_residues(freesasa_gpu_ctx *c, const IfacePlan &pl, const IfaceResWant 
     t.R = R; t.off = a.res_off; t.areas = a.res_areas; t.index = a.res_index; t.atoms = a.res_atoms;
     return 0;
 }
-/* the three capacities against P, M and R, in this order, with the interface entries' messages for the first two */
-int iface_res_check_caps(freesasa_gpu_ctx *c, const IfacePlan &pl, const IfaceWant &w, const IfaceResWant &rw, int64_t R)
-{
-    if (iface_check_caps(c, pl, w)) return -1;
-    if (R > rw.res_capacity)
-        return ctx_fail(c, "res_capacity %lld is too small: the interfaces have %lld residue rows", rw.res_capacity, (long long)R);
-    return 0;
-}
 
-/* the atom-atom contact tables: what an entry gives on top of the interface entries' arguments, and what it wants back */
-struct IfaceContactWant {
-    long long contact_capacity = 0, dot_capacity = 0;
-    long long *n_contacts_out = nullptr, *n_buried_dots_out = nullptr;
-    bool rows = false; /* one of contact_partner, contact_points, contact_area */
-    bool dots = false; /* dot_partner */
-};
-/* ... checked before a device is touched, behind iface_bad_args and iface_bad_caps: 0, or the message in msg */
-int iface_contact_bad_args(const IfaceContactWant &cw, int alg, int resolution, const void *masks, char *msg, size_t len)
+/* step 10 behind iface_pairs (Shrake-Rupley; k_iface_finish is the last thing on the stream).  D_b, then C and the flag come
+   back to the host (two stream synchronizations), so at the stage's end the stream is idle.  Without a buried point there are
+   the masks and nothing else. */
+int iface_contacts(freesasa_gpu_ctx *c, const IfaceCall &k, IfaceRun &r)
 {
-    if (!cw.n_contacts_out) { snprintf(msg, len, "null argument"); return -1; }
-    if (alg != 1) { snprintf(msg, len, "the contact tables are made of Shrake-Rupley test points: Lee-Richards has none"); return -1; }
-    if (resolution > SR_CAP_POINTS_MAX) {
-        snprintf(msg, len, "the contact tables are offered up to %d test points (%d asked for)", SR_CAP_POINTS_MAX, resolution);
-        return -1;
-    }
-    if (cw.contact_capacity < 0) { snprintf(msg, len, "contact_capacity must be >= 0 (it is %lld)", cw.contact_capacity); return -1; }
-    if (cw.dot_capacity < 0) { snprintf(msg, len, "dot_capacity must be >= 0 (it is %lld)", cw.dot_capacity); return -1; }
-    if ((uintptr_t)masks % 16) { snprintf(msg, len, "the buried mask array must be aligned to 16 bytes (an atom's four words are one store)"); return -1; }
-    return 0;
-}
-
-/* the stage behind iface_pipeline (Shrake-Rupley; k_iface_finish is the last thing on the stream): the table in c->if_ctable -
-   contact_first [M + 1] | contact_area [D_b] | contact_partner [D_b] | contact_points [D_b], C rows of them used -, the buried masks
-   in c->if_cmasks, the dots' partners in c->if_cdots.  D_b, then C and the flag come back to the host (two stream
-   synchronizations), so at the stage's end the stream is idle. */
-struct IfaceContactTable {
-    int64_t C = 0, D = 0;
-    const int64_t *first = nullptr;
-    const int32_t *partner = nullptr, *points = nullptr, *dot_partner = nullptr;
-    const double *area = nullptr;
-    const unsigned *buried = nullptr;
-};
-int iface_contacts(freesasa_gpu_ctx *c, const IfacePlan &pl, double probe, int n_points, IfaceContactTable &t)
-{
-    t = IfaceContactTable();
+    const IfacePlan &pl = r.pl;
+    IfaceContactTable &t = r.ct;
+    const int n_points = k.resolution;
     if (pl.P == 0) return 0;
     const size_t P = (size_t)pl.P, M = (size_t)pl.M;
     const size_t S = (size_t)ifr_scan_scratch(pl.M);
@@ -384,12 +430,12 @@ int iface_contacts(freesasa_gpu_ctx *c, const IfacePlan &pl, double probe, int n
     int *nd = (int *)(dot_first + M + 1), *scratch = nd + M + 1, *flag = scratch + S;
     const double *pxyz = (const double *)c->if_xyz.p, *pradii = (const double *)c->if_radii.p;
     /* the same atoms as P structures and as 2 P: what the pair run and the groups' run of the pipeline counted, as masks */
-    if (masks_resident(c, pxyz, pradii, pl.pair_off.data(), (int)P, probe, n_points, pl.tp.data(), areas, nullptr, nullptr, pair_masks) ||
-        masks_resident(c, pxyz, pradii, pl.side_off.data(), (int)(2 * P), probe, n_points, pl.tp.data(), areas, nullptr, nullptr, side_masks))
+    if (masks_resident(c, pxyz, pradii, pl.pair_off.data(), (int)P, k.probe, n_points, pl.tp.data(), areas, nullptr, nullptr, pair_masks) ||
+        masks_resident(c, pxyz, pradii, pl.side_off.data(), (int)(2 * P), k.probe, n_points, pl.tp.data(), areas, nullptr, nullptr, side_masks))
         return -1;
     ContactArgs a;
     memset(&a, 0, sizeof a);
-    a.n_pair_atoms = pl.M; a.n_sides = 2 * pl.P; a.n_points = n_points; a.probe = probe;
+    a.n_pair_atoms = pl.M; a.n_sides = 2 * pl.P; a.n_points = n_points; a.probe = k.probe;
     a.side_off = (const int64_t *)c->if_sides.p; a.pxyz = pxyz; a.pradii = pradii;
     a.side_masks = side_masks; a.pair_masks = pair_masks; a.buried = buried;
     a.dot_first = dot_first; a.nd = nd; a.flag = flag;
@@ -409,7 +455,7 @@ int iface_contacts(freesasa_gpu_ctx *c, const IfacePlan &pl, double probe, int n
     a.contact_first = (int64_t *)c->if_ctable.p; a.contact_area = (double *)(a.contact_first + M + 1);
     a.contact_partner = (int *)(a.contact_area + Db); a.contact_points = a.contact_partner + Db;
     HIP_TRY(c, hipMemsetAsync(nd, 0, 4 * (M + 1 + S + 1), st)); /* (the atoms' counts, the scan's levels, the flag) */
-    if (dots_expand_resident(c, pxyz, pradii, pl.M, probe, n_points, buried, dot_first, D, dot_xyz, dot_atom, dot_point)) return -1;
+    if (dots_expand_resident(c, pxyz, pradii, pl.M, k.probe, n_points, buried, dot_first, D, dot_xyz, dot_atom, dot_point)) return -1;
     HIP_TRY(c, kl_contact_attribute(a, st));
     HIP_TRY(c, kl_contact_rows(a, scratch, st));
     int back[2] = {0, 0}; /* C, the flag */
@@ -423,60 +469,27 @@ int iface_contacts(freesasa_gpu_ctx *c, const IfacePlan &pl, double probe, int n
     t.dot_partner = a.dot_partner;
     return 0;
 }
-/* the four capacities against P, M, C and D_b, in this order, with the interface entries' messages for the first two */
-int iface_contact_check_caps(freesasa_gpu_ctx *c, const IfacePlan &pl, const IfaceWant &w, const IfaceContactWant &cw, const IfaceContactTable &t)
-{
-    if (iface_check_caps(c, pl, w)) return -1;
-    if (cw.rows && t.C > cw.contact_capacity)
-        return ctx_fail(c, "contact_capacity %lld is too small: the interfaces have %lld contact rows", cw.contact_capacity, (long long)t.C);
-    if (cw.dots && t.D > cw.dot_capacity)
-        return ctx_fail(c, "dot_capacity %lld is too small: the interfaces bury %lld test points", cw.dot_capacity, (long long)t.D);
-    return 0;
-}
 
-/* the residue-residue contact tables: what an entry gives on top of the contact entries' arguments, and what it wants back */
-struct IfaceResContactWant {
-    const int64_t *res_first = nullptr;
-    int n_res = 0;
-    long long rescontact_capacity = 0;
-    long long *n_rescontacts_out = nullptr;
-};
-/* ... checked before a device is touched, behind the contact entries' checks: res_first by the residue entries' own check */
-int iface_rescontact_bad_args(const IfaceResContactWant &qw, const int64_t *offsets, int n_structs, char *msg, size_t len)
+/* step 11 behind iface_contacts (the stream is idle, C is on the host): the segments of the per-residue tables by their own
+   kernels, the fold of the contact rows per partner segment, the reverse rows.  Q comes back to the host (one stream
+   synchronization), so at the stage's end the stream is idle.  Without a contact row nothing is launched: Q = 0; without a
+   folded row there is no table. */
+int iface_rescontacts(freesasa_gpu_ctx *c, const IfaceCall &k, IfaceRun &r)
 {
-    IfaceResWant rw;
-    rw.res_first = qw.res_first; rw.n_res = qw.n_res; rw.n_res_rows_out = qw.n_rescontacts_out;
-    if (iface_res_bad_args(rw, offsets, n_structs, msg, len)) return -1;
-    if (qw.rescontact_capacity < 0) { snprintf(msg, len, "rescontact_capacity must be >= 0 (it is %lld)", qw.rescontact_capacity); return -1; }
-    return 0;
-}
-
-/* the stage behind iface_contacts (the stream is idle, C is on the host): the segments of the per-residue tables by their own
-   kernels, the fold of the contact rows per partner segment, the reverse rows; the table in c->if_rctable - rescontact_offsets
-   [2 P + 1] | rescontact_area [C] | rescontact_residues [2 C] | rescontact_counts [2 C] | rescontact_reverse [C], Q rows of them
-   used.  Q comes back to the host (one stream synchronization), so at the stage's end the stream is idle.  Without a contact row
-   nothing is launched: Q = 0. */
-struct IfaceResContactTable {
-    int64_t Q = 0;
-    const int64_t *off = nullptr;
-    const double *area = nullptr;
-    const int32_t *res = nullptr, *cnt = nullptr, *rev = nullptr;
-    std::vector<int64_t> first; /* the upload of res_first (like the plan, the table lives until the stream is idle) */
-};
-int iface_rescontacts(freesasa_gpu_ctx *c, const IfacePlan &pl, const IfaceResContactWant &qw, const IfaceContactTable &ct, IfaceResContactTable &t)
-{
-    t.Q = 0;
+    const IfacePlan &pl = r.pl;
+    const IfaceContactTable &ct = r.ct;
+    IfaceResContactTable &t = r.qt;
     if (pl.P == 0 || ct.C == 0) return 0;
     const size_t P = (size_t)pl.P, M = (size_t)pl.M, Cn = (size_t)ct.C;
     const size_t S = (size_t)ifr_scan_scratch(pl.M);
     hipStream_t st = c->stream;
-    if (ensure(c, c->if_rfirst, 8 * ((size_t)qw.n_res + 1)) || ensure(c, c->if_rcwork, 4 * (4 * M + 3 + S + Cn)) ||
+    if (iface_upload_res_first(c, k, r) || ensure(c, c->if_rcwork, 4 * (4 * M + 3 + S + Cn)) ||
         ensure(c, c->if_rctable, 8 * (2 * P + 1) + 8 * Cn + 4 * 5 * Cn))
         return -1;
     int *w = (int *)c->if_rcwork.p;
     IfaceResArgs s;
     memset(&s, 0, sizeof s);
-    s.n_pair_atoms = pl.M; s.n_sides = 2 * pl.P; s.n_res = qw.n_res;
+    s.n_pair_atoms = pl.M; s.n_sides = 2 * pl.P; s.n_res = k.n_res;
     s.side_off = (const int64_t *)c->if_sides.p; s.pair_atom = (const int *)c->if_patom.p; s.res_first = (const int64_t *)c->if_rfirst.p;
     s.atom_res = w; s.hs = w + M; s.seg_first = s.hs + M + 1;
     ResContactArgs a;
@@ -489,46 +502,175 @@ int iface_rescontacts(freesasa_gpu_ctx *c, const IfacePlan &pl, const IfaceResCo
     a.pseg = scratch + S;
     a.rc_off = (int64_t *)c->if_rctable.p; a.rc_area = (double *)(a.rc_off + 2 * P + 1);
     a.rc_res = (int *)(a.rc_area + Cn); a.rc_cnt = a.rc_res + 2 * Cn; a.rc_rev = a.rc_cnt + 2 * Cn;
-    t.first.assign(qw.res_first, qw.res_first + qw.n_res + 1); /* (the stage's own copy: iface_residues) */
-    HIP_TRY(c, hipMemcpyAsync(c->if_rfirst.p, t.first.data(), 8 * t.first.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemsetAsync(a.fc, 0, 4 * (M + 1), st)); /* (the segments' counts: a slot at or beyond K has none) */
     HIP_TRY(c, kl_rc_segments(s, scratch, st));
     HIP_TRY(c, kl_rc_fold(a, scratch, st));
     int Q = 0;
     HIP_TRY(c, hipMemcpyAsync(&Q, a.fc + M, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    t.Q = Q; t.off = a.rc_off; t.area = a.rc_area; t.res = a.rc_res; t.cnt = a.rc_cnt; t.rev = a.rc_rev;
-    return 0;
-}
-/* the five capacities against P, M, C, D_b and Q, in this order */
-int iface_rescontact_check_caps(freesasa_gpu_ctx *c, const IfacePlan &pl, const IfaceWant &w, const IfaceContactWant &cw, const IfaceContactTable &ct,
-                                const IfaceResContactWant &qw, int64_t Q)
-{
-    if (iface_contact_check_caps(c, pl, w, cw, ct)) return -1;
-    if (Q > qw.rescontact_capacity)
-        return ctx_fail(c, "rescontact_capacity %lld is too small: the interfaces have %lld residue contact rows", qw.rescontact_capacity, (long long)Q);
+    t.Q = Q;
+    if (Q == 0) return 0;
+    t.off = a.rc_off; t.area = a.rc_area; t.res = a.rc_res; t.cnt = a.rc_cnt; t.rev = a.rc_rev;
     return 0;
 }
 
-int iface_dev_checks(freesasa_gpu_ctx *c, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
-                     const int32_t *d_group, const int32_t *n_groups, int alg, int resolution, long long pair_capacity, long long atom_capacity)
+/* The one capacity check: every capacity an array that is delivered asks for, against its count, in the order P, M, R, C, D_b, Q.
+   (atom_capacity counts for contact_first and the masks too: they have M + 1 and M entries.) */
+int iface_check_caps(freesasa_gpu_ctx *c, const IfaceCall &k, const IfaceRun &r)
 {
+    const struct { bool wanted; long long count, capacity; const char *message; } caps[] = {
+        {k.whole || k.pair_struct || k.pair_groups, r.pl.P, k.pair_capacity,
+         "pair_capacity %lld is too small: the batch has %lld pairs of groups in contact"},
+        {k.pair_atom || k.pair_buried || k.contact_first || k.buried_masks, r.pl.M, k.atom_capacity,
+         "atom_capacity %lld is too small: the pair structures hold %lld atoms"},
+        {k.residues, r.rt.R, k.res_capacity, "res_capacity %lld is too small: the interfaces have %lld residue rows"},
+        {k.contact_partner || k.contact_points || k.contact_area, r.ct.C, k.contact_capacity,
+         "contact_capacity %lld is too small: the interfaces have %lld contact rows"},
+        {k.dot_partner != nullptr, r.ct.D, k.dot_capacity, "dot_capacity %lld is too small: the interfaces bury %lld test points"},
+        {k.rescontacts, r.qt.Q, k.rescontact_capacity, "rescontact_capacity %lld is too small: the interfaces have %lld residue contact rows"},
+    };
+    for (const auto &x : caps)
+        if (x.wanted && x.count > x.capacity) return ctx_fail(c, x.message, x.capacity, x.count);
+    return 0;
+}
+
+/* The one run: the screen or the whole pipeline, then the stages asked for.  Every count output is set as soon as its count is
+   known; the capacities are held behind the screen where no stage follows step 8, else behind the last stage. */
+int iface_run(freesasa_gpu_ctx *c, const IfaceCall &k, IfaceRun &r)
+{
+    const bool later = k.residues || k.contacts;
+    if (iface_screen(c, k, r)) return -1;
+    *k.n_pairs = r.pl.P; *k.n_pair_atoms = r.pl.M;
+    if (!later && iface_check_caps(c, k, r)) return -1;
+    if (k.whole && iface_pairs(c, k, r)) return -1;
+    if (k.contacts) {
+        if (iface_contacts(c, k, r)) return -1;
+        *k.n_contacts = r.ct.C;
+        if (k.n_buried_dots) *k.n_buried_dots = r.ct.D;
+    }
+    if (k.rescontacts) {
+        if (iface_rescontacts(c, k, r)) return -1;
+        *k.n_rescontacts = r.qt.Q;
+    }
+    if (k.residues) {
+        if (iface_residues(c, k, r)) return -1;
+        *k.n_res_rows = r.rt.R;
+    }
+    return later ? iface_check_caps(c, k, r) : 0;
+}
+
+/* ------------------------------------------------------------------ the one table of outputs and the one delivery */
+
+/* a deliverable array: `count` elements of `size` bytes from `src` - a device buffer of the context, or (plan) a host vector of
+   the plan - to the caller's `dst` (null: not delivered); where the call made no such array (src null), `zeros` elements of 0 */
+struct IfaceOut {
+    void *dst;
+    const void *src;
+    bool plan;
+    size_t size, count, zeros;
+};
+enum { IF_N_OUT = 21 };
+std::array<IfaceOut, IF_N_OUT> iface_outputs(freesasa_gpu_ctx *c, const IfaceCall &k, const IfaceRun &r)
+{
+    const IfacePlan &pl = r.pl;
+    const size_t P = (size_t)pl.P, M = (size_t)pl.M, R = (size_t)r.rt.R, C = (size_t)r.ct.C, D = (size_t)r.ct.D, Q = (size_t)r.qt.Q;
+    const size_t sides = 2 * P + 1; /* (1 without a pair: the offsets of no side) */
+    return {{
+        {k.pair_struct, pl.pair_struct.data(), true, 4, P, 0},
+        {k.pair_groups, pl.pair_groups.data(), true, 8, P, 0},
+        {k.pair_areas, c->if_areas.p, false, 48, P, 0},
+        {k.side_offsets, pl.side_off.data(), true, 8, sides, 0},
+        {k.pair_atom, c->if_patom.p, false, 4, M, 0},
+        {k.pair_buried, c->if_pburied.p, false, 8, M, 0},
+        /* the per-residue table: without a pair res_offsets [1] = 0 */
+        {k.res_offsets, r.rt.off, false, 8, sides, 1},
+        {k.res_index, r.rt.index, false, 4, R, 0},
+        {k.res_atoms, r.rt.atoms, false, 4, R, 0},
+        {k.res_areas, r.rt.areas, false, 24, R, 0},
+        /* the contact table: without a pair contact_first [1] = 0, without a buried point zeros [M + 1] behind the masks */
+        {k.contact_first, r.ct.first, false, 8, M + 1, M + 1},
+        {k.contact_partner, r.ct.partner, false, 4, C, 0},
+        {k.contact_points, r.ct.points, false, 4, C, 0},
+        {k.contact_area, r.ct.area, false, 8, C, 0},
+        {k.buried_masks, r.ct.buried, false, 4 * SR_CAP_WORDS, M, 0},
+        {k.dot_partner, r.ct.dot_partner, false, 4, D, 0},
+        /* the folded table: without a folded row rescontact_offsets is zeros, [1] without a pair, else [2 P + 1] */
+        {k.rescontact_offsets, r.qt.off, false, 8, sides, sides},
+        {k.rescontact_residues, r.qt.res, false, 8, Q, 0},
+        {k.rescontact_counts, r.qt.cnt, false, 8, Q, 0},
+        {k.rescontact_area, r.qt.area, false, 8, Q, 0},
+        {k.rescontact_reverse, r.qt.rev, false, 4, Q, 0},
+    }};
+}
+
+/* The delivery, in two calls around the caller's stream synchronization.  idle = false: everything that goes over the stream is
+   enqueued - to device arrays the context's buffers, the plan's arrays and the zeros; to host arrays the context's buffers (the
+   zeros are written at once).  idle = true, once the synchronize has succeeded: the plan's arrays into host arrays, and stats. */
+int iface_deliver(freesasa_gpu_ctx *c, const IfaceCall &k, const IfaceRun &r, bool idle)
+{
+    hipStream_t st = c->stream;
+    for (const IfaceOut &o : iface_outputs(c, k, r)) {
+        const size_t bytes = o.size * (o.src ? o.count : o.zeros);
+        if (!o.dst || !bytes || idle != (o.plan && !k.out_dev)) continue;
+        hipError_t e = hipSuccess;
+        if (idle) memcpy(o.dst, o.src, bytes);
+        else if (!o.src && !k.out_dev) memset(o.dst, 0, bytes);
+        else if (!o.src) e = hipMemsetAsync(o.dst, 0, bytes, st);
+        else e = hipMemcpyAsync(o.dst, o.src, bytes, !k.out_dev ? hipMemcpyDeviceToHost : o.plan ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess)
+            return k.out_dev ? ctx_fail(c, "delivery to the caller's device arrays failed: %s", hipGetErrorString(e)) : ctx_fail(c, "device-to-host copy failed");
+    }
+    if (idle && k.stats) { k.stats[0] = r.pl.T; k.stats[1] = r.pl.n_cand; }
+    return 0;
+}
+
+/* ------------------------------------------------------------------ the two entry kinds */
+
+/* the batch on the context's stream; the call is synchronous, and a failed one drains the stream too */
+int iface_dev(freesasa_gpu_ctx *c, const IfaceCall &k)
+{
+    if (!c) return -1;
+    if (freesasa_gpu_wait(c)) return -1; /* (batches submitted asynchronously come first) */
+    return guarded_ctx(c, [&]() -> int {
+        char msg[200];
+        c->err[0] = 0;
+        if (iface_bad_call(k, c->device, msg, sizeof msg)) return ctx_fail(c, "%s", msg);
+        IfaceRun r;
+        int rc = iface_run(c, k, r) || iface_deliver(c, k, r, false) ? -1 : 0;
+        if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = ctx_fail(c, "stream synchronize failed");
+        return rc ? rc : iface_deliver(c, k, r, true);
+    });
+}
+
+/* the batch in host arrays: the grouped host batch (gpu_groups.hip) on a pooled context, the pipeline on its staging */
+int iface_host(const IfaceCall &k, int device, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
     char msg[200];
-    c->err[0] = 0;
-    if (iface_bad_args(d_xyz, d_radii, offsets, n_structs, d_group, n_groups, alg, resolution, msg, sizeof msg) ||
-        iface_bad_caps(pair_capacity, atom_capacity, msg, sizeof msg))
-        return ctx_fail(c, "%s", msg);
-    if (offsets[n_structs] > (int64_t)1 << 30) return ctx_fail(c, "batch too large (max 2^30 atoms per call)");
-    if (hipSetDevice(c->device) != hipSuccess) return ctx_fail(c, "hipSetDevice failed");
-    return 0;
-}
-
-/* the screen's rows into host arrays */
-void iface_rows_to_host(const IfacePlan &pl, int32_t *pair_struct_out, int32_t *pair_groups_out, long long *stats_out)
-{
-    if (pair_struct_out && pl.P > 0) memcpy(pair_struct_out, pl.pair_struct.data(), 4 * (size_t)pl.P);
-    if (pair_groups_out && pl.P > 0) memcpy(pair_groups_out, pl.pair_groups.data(), 8 * (size_t)pl.P);
-    if (stats_out) { stats_out[0] = pl.T; stats_out[1] = pl.n_cand; }
+    if (iface_bad_call(k, -1, msg, sizeof msg)) return set_err(err_out, err_len, msg);
+    return guarded(err_out, err_len, [&]() -> int {
+    IfaceRun r;
+    PoolLease lease(device);
+    freesasa_gpu_ctx *c = lease.c;
+    if (!c) return set_err(err_out, err_len, "could not create a GPU context");
+    BatchCall b;
+    b.fallback = "GPU interface batch failed";
+    GroupBatch g;
+    g.xyz = k.xyz; g.radii = k.radii; g.offsets = k.offsets; g.n_structs = k.n_structs; g.group = k.group; g.n_groups = k.n_groups;
+    g.sasa_out = k.sasa; g.iso_out = k.iso; g.totals_out = k.totals; g.group_totals_out = k.group_totals;
+    const int rc = [&]() -> int {
+        c->err[0] = 0;
+        if (group_batch_upload(b, c, g)) return -1;
+        if (k.offsets[k.n_structs] > (int64_t)1 << 30) return ctx_fail(c, "batch too large (max 2^30 atoms per call)");
+        IfaceCall d = k; /* the same call on the staged batch */
+        d.xyz = g.d_xyz; d.radii = g.d_radii; d.group = g.d_group;
+        d.sasa = g.d_sasa; d.iso = g.d_iso; d.totals = g.d_totals; d.group_totals = g.d_group_totals;
+        if (iface_run(c, d, r) || iface_deliver(c, d, r, false) || group_batch_download(c, g)) return -1;
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return ctx_fail(c, "stream synchronize failed");
+        return iface_deliver(c, d, r, true);
+    }();
+    return rc ? set_err(err_out, err_len, chunk_failed(b, c)) : 0;
+    });
 }
 
 } /* namespace */
@@ -540,24 +682,13 @@ extern "C" int freesasa_gpu_interface_pairs_dev(freesasa_gpu_ctx *c, int alg, co
                                                 long long *n_pair_atoms_out, int32_t *pair_struct_out, int32_t *pair_groups_out,
                                                 long long *stats_out)
 {
-    if (!c) return -1;
-    if (freesasa_gpu_wait(c)) return -1; /* (batches submitted asynchronously come first) */
-    return guarded_ctx(c, [&]() -> int {
-        if (iface_dev_checks(c, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, alg, resolution, pair_capacity, 0)) return -1;
-        if (!n_pairs_out || !n_pair_atoms_out) return ctx_fail(c, "null argument");
-        IfacePlan pl;
-        IfaceArgs ia;
-        int rc = iface_screen(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe_radius, resolution, d_sasa, d_iso,
-                              d_totals, d_group_totals, pl, ia);
-        if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = ctx_fail(c, "stream synchronize failed");
-        if (rc) return rc;
-        *n_pairs_out = pl.P; *n_pair_atoms_out = pl.M;
-        IfaceWant w;
-        w.pair_capacity = pair_capacity; w.rows = pair_struct_out || pair_groups_out;
-        if (iface_check_caps(c, pl, w)) return -1;
-        iface_rows_to_host(pl, pair_struct_out, pair_groups_out, stats_out);
-        return 0;
-    });
+    IfaceCall k;
+    k.xyz = d_xyz; k.radii = d_radii; k.offsets = offsets; k.n_structs = n_structs; k.group = d_group; k.n_groups = n_groups;
+    k.alg = alg; k.probe = probe_radius; k.resolution = resolution;
+    k.sasa = d_sasa; k.iso = d_iso; k.totals = d_totals; k.group_totals = d_group_totals;
+    k.pair_capacity = pair_capacity; k.n_pairs = n_pairs_out; k.n_pair_atoms = n_pair_atoms_out;
+    k.pair_struct = pair_struct_out; k.pair_groups = pair_groups_out; k.stats = stats_out; /* (host arrays) */
+    return iface_dev(c, k);
 }
 
 extern "C" int freesasa_gpu_interfaces_dev(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii,
@@ -568,32 +699,15 @@ extern "C" int freesasa_gpu_interfaces_dev(freesasa_gpu_ctx *c, int alg, const d
                                            int32_t *d_pair_groups, double *d_pair_areas, int64_t *d_side_offsets, int32_t *d_pair_atom,
                                            double *d_pair_buried)
 {
-    if (!c) return -1;
-    if (freesasa_gpu_wait(c)) return -1;
-    return guarded_ctx(c, [&]() -> int {
-        if (iface_dev_checks(c, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, alg, resolution, pair_capacity, atom_capacity)) return -1;
-        if (!d_sasa || !d_iso || !n_pairs_out || !n_pair_atoms_out || !d_pair_areas) return ctx_fail(c, "null argument");
-        IfacePlan pl; /* (its arrays are the sources of copies enqueued below: it lives until the stream is idle) */
-        IfaceWant w;
-        w.pair_capacity = pair_capacity; w.atom_capacity = atom_capacity; w.rows = true; w.atoms = d_pair_atom || d_pair_buried;
-        int rc = [&]() -> int {
-            if (iface_pipeline(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe_radius, resolution, d_sasa, d_iso,
-                               d_totals, d_group_totals, w, pl, n_pairs_out, n_pair_atoms_out))
-                return -1;
-            const size_t P = (size_t)pl.P, M = (size_t)pl.M;
-            hipStream_t st = c->stream;
-            if (d_side_offsets) HIP_TRY(c, hipMemcpyAsync(d_side_offsets, pl.side_off.data(), 8 * (2 * P + 1), hipMemcpyHostToDevice, st));
-            if (P == 0) return 0;
-            if (d_pair_struct) HIP_TRY(c, hipMemcpyAsync(d_pair_struct, pl.pair_struct.data(), 4 * P, hipMemcpyHostToDevice, st));
-            if (d_pair_groups) HIP_TRY(c, hipMemcpyAsync(d_pair_groups, pl.pair_groups.data(), 8 * P, hipMemcpyHostToDevice, st));
-            HIP_TRY(c, hipMemcpyAsync(d_pair_areas, c->if_areas.p, 48 * P, hipMemcpyDeviceToDevice, st));
-            if (d_pair_atom) HIP_TRY(c, hipMemcpyAsync(d_pair_atom, c->if_patom.p, 4 * M, hipMemcpyDeviceToDevice, st));
-            if (d_pair_buried) HIP_TRY(c, hipMemcpyAsync(d_pair_buried, c->if_pburied.p, 8 * M, hipMemcpyDeviceToDevice, st));
-            return 0;
-        }();
-        if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = ctx_fail(c, "stream synchronize failed"); /* (the call is synchronous) */
-        return rc;
-    });
+    IfaceCall k;
+    k.xyz = d_xyz; k.radii = d_radii; k.offsets = offsets; k.n_structs = n_structs; k.group = d_group; k.n_groups = n_groups;
+    k.alg = alg; k.probe = probe_radius; k.resolution = resolution;
+    k.sasa = d_sasa; k.iso = d_iso; k.totals = d_totals; k.group_totals = d_group_totals;
+    k.whole = true; k.out_dev = true;
+    k.pair_capacity = pair_capacity; k.atom_capacity = atom_capacity; k.n_pairs = n_pairs_out; k.n_pair_atoms = n_pair_atoms_out;
+    k.pair_struct = d_pair_struct; k.pair_groups = d_pair_groups; k.pair_areas = d_pair_areas; k.side_offsets = d_side_offsets;
+    k.pair_atom = d_pair_atom; k.pair_buried = d_pair_buried;
+    return iface_dev(c, k);
 }
 
 extern "C" int freesasa_gpu_interface_residues_dev(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii,
@@ -607,136 +721,18 @@ extern "C" int freesasa_gpu_interface_residues_dev(freesasa_gpu_ctx *c, int alg,
                                                    double *d_pair_buried, int64_t *d_res_offsets, int32_t *d_res_index,
                                                    int32_t *d_res_atoms, double *d_res_areas)
 {
-    if (!c) return -1;
-    if (freesasa_gpu_wait(c)) return -1;
-    return guarded_ctx(c, [&]() -> int {
-        char msg[200];
-        c->err[0] = 0;
-        IfaceResWant rw;
-        rw.res_first = res_first; rw.n_res = n_res; rw.min_buried = min_buried; rw.res_capacity = res_capacity; rw.n_res_rows_out = n_res_rows_out;
-        if (iface_bad_args(d_xyz, d_radii, offsets, n_structs, d_group, n_groups, alg, resolution, msg, sizeof msg) ||
-            iface_bad_caps(pair_capacity, atom_capacity, msg, sizeof msg) || iface_res_bad_args(rw, offsets, n_structs, msg, sizeof msg))
-            return ctx_fail(c, "%s", msg);
-        if (iface_dev_checks(c, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, alg, resolution, pair_capacity, atom_capacity)) return -1;
-        if (!d_sasa || !d_iso || !n_pairs_out || !n_pair_atoms_out || !d_pair_areas || !d_res_areas) return ctx_fail(c, "null argument");
-        IfacePlan pl; /* (plan and table hold the sources of copies enqueued below: they live until the stream is idle) */
-        IfaceResTable t;
-        IfaceWant w, none; /* (the pipeline holds no capacity against its counts here: the three are held together, once R is known) */
-        w.pair_capacity = pair_capacity; w.atom_capacity = atom_capacity; w.rows = true; w.atoms = d_pair_atom || d_pair_buried;
-        int rc = [&]() -> int {
-            if (iface_pipeline(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe_radius, resolution, d_sasa, d_iso,
-                               d_totals, d_group_totals, none, pl, n_pairs_out, n_pair_atoms_out) ||
-                iface_residues(c, pl, rw, d_iso, t))
-                return -1;
-            *n_res_rows_out = t.R;
-            if (iface_res_check_caps(c, pl, w, rw, t.R)) return -1;
-            const size_t P = (size_t)pl.P, M = (size_t)pl.M, R = (size_t)t.R;
-            hipStream_t st = c->stream;
-            if (d_side_offsets) HIP_TRY(c, hipMemcpyAsync(d_side_offsets, pl.side_off.data(), 8 * (2 * P + 1), hipMemcpyHostToDevice, st));
-            if (P == 0) {
-                if (d_res_offsets) HIP_TRY(c, hipMemsetAsync(d_res_offsets, 0, 8, st));
-                return 0;
-            }
-            if (d_pair_struct) HIP_TRY(c, hipMemcpyAsync(d_pair_struct, pl.pair_struct.data(), 4 * P, hipMemcpyHostToDevice, st));
-            if (d_pair_groups) HIP_TRY(c, hipMemcpyAsync(d_pair_groups, pl.pair_groups.data(), 8 * P, hipMemcpyHostToDevice, st));
-            HIP_TRY(c, hipMemcpyAsync(d_pair_areas, c->if_areas.p, 48 * P, hipMemcpyDeviceToDevice, st));
-            if (d_pair_atom) HIP_TRY(c, hipMemcpyAsync(d_pair_atom, c->if_patom.p, 4 * M, hipMemcpyDeviceToDevice, st));
-            if (d_pair_buried) HIP_TRY(c, hipMemcpyAsync(d_pair_buried, c->if_pburied.p, 8 * M, hipMemcpyDeviceToDevice, st));
-            if (d_res_offsets) HIP_TRY(c, hipMemcpyAsync(d_res_offsets, t.off, 8 * (2 * P + 1), hipMemcpyDeviceToDevice, st));
-            if (R == 0) return 0;
-            if (d_res_index) HIP_TRY(c, hipMemcpyAsync(d_res_index, t.index, 4 * R, hipMemcpyDeviceToDevice, st));
-            if (d_res_atoms) HIP_TRY(c, hipMemcpyAsync(d_res_atoms, t.atoms, 4 * R, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(c, hipMemcpyAsync(d_res_areas, t.areas, 24 * R, hipMemcpyDeviceToDevice, st));
-            return 0;
-        }();
-        if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = ctx_fail(c, "stream synchronize failed"); /* (the call is synchronous) */
-        return rc;
-    });
-}
-
-/* the contact entry, and - with qw - the residue-residue contact entry: the same call with one more stage and five more arrays */
-struct IfaceResContactOut { /* the residue-residue contact entries' arrays, on the device or on the host: area is required */
-    int64_t *off = nullptr;
-    int32_t *res = nullptr, *cnt = nullptr, *rev = nullptr;
-    double *area = nullptr;
-};
-static int iface_contacts_dev(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
-                              const int32_t *d_group, const int32_t *n_groups, double probe_radius, int resolution, double *d_sasa,
-                              double *d_iso, double *d_totals, double *d_group_totals, long long pair_capacity, long long atom_capacity,
-                              long long contact_capacity, long long dot_capacity, long long *n_pairs_out, long long *n_pair_atoms_out,
-                              long long *n_contacts_out, long long *n_buried_dots_out, int32_t *d_pair_struct, int32_t *d_pair_groups,
-                              double *d_pair_areas, int64_t *d_side_offsets, int32_t *d_pair_atom, double *d_pair_buried,
-                              int64_t *d_contact_first, int32_t *d_contact_partner, int32_t *d_contact_points, double *d_contact_area,
-                              uint32_t *d_buried_masks, int32_t *d_dot_partner, const IfaceResContactWant *qw, const IfaceResContactOut &qd)
-{
-    if (!c) return -1;
-    if (freesasa_gpu_wait(c)) return -1;
-    return guarded_ctx(c, [&]() -> int {
-        char msg[200];
-        c->err[0] = 0;
-        IfaceContactWant cw;
-        cw.contact_capacity = contact_capacity; cw.dot_capacity = dot_capacity; cw.n_contacts_out = n_contacts_out; cw.n_buried_dots_out = n_buried_dots_out;
-        cw.rows = d_contact_partner || d_contact_points || d_contact_area; cw.dots = d_dot_partner != nullptr;
-        if (iface_bad_args(d_xyz, d_radii, offsets, n_structs, d_group, n_groups, alg, resolution, msg, sizeof msg) ||
-            iface_bad_caps(pair_capacity, atom_capacity, msg, sizeof msg) || iface_contact_bad_args(cw, alg, resolution, d_buried_masks, msg, sizeof msg) ||
-            (qw && iface_rescontact_bad_args(*qw, offsets, n_structs, msg, sizeof msg)))
-            return ctx_fail(c, "%s", msg);
-        if (iface_dev_checks(c, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, alg, resolution, pair_capacity, atom_capacity)) return -1;
-        if (!d_sasa || !d_iso || !n_pairs_out || !n_pair_atoms_out || !d_pair_areas || (qw && !qd.area)) return ctx_fail(c, "null argument");
-        IfacePlan pl; /* (the plan holds the sources of copies enqueued below: it lives until the stream is idle) */
-        IfaceContactTable t;
-        IfaceResContactTable qt;
-        IfaceWant w, none; /* (the pipeline holds no capacity against its counts here: the four are held together, once C and D_b are known) */
-        w.pair_capacity = pair_capacity; w.atom_capacity = atom_capacity; w.rows = true;
-        w.atoms = d_pair_atom || d_pair_buried || d_contact_first || d_buried_masks;
-        int rc = [&]() -> int {
-            if (iface_pipeline(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe_radius, resolution, d_sasa, d_iso,
-                               d_totals, d_group_totals, none, pl, n_pairs_out, n_pair_atoms_out) ||
-                iface_contacts(c, pl, probe_radius, resolution, t))
-                return -1;
-            *n_contacts_out = t.C;
-            if (n_buried_dots_out) *n_buried_dots_out = t.D;
-            if (qw) {
-                if (iface_rescontacts(c, pl, *qw, t, qt)) return -1;
-                *qw->n_rescontacts_out = qt.Q;
-            }
-            if (qw ? iface_rescontact_check_caps(c, pl, w, cw, t, *qw, qt.Q) : iface_contact_check_caps(c, pl, w, cw, t)) return -1;
-            const size_t P = (size_t)pl.P, M = (size_t)pl.M, Cn = (size_t)t.C, D = (size_t)t.D, Q = (size_t)qt.Q;
-            hipStream_t st = c->stream;
-            /* rescontact_offsets: zeros without a pair ([1]) or without a folded row ([2 P + 1]) */
-            if (qd.off && Q == 0) HIP_TRY(c, hipMemsetAsync(qd.off, 0, 8 * (P == 0 ? 1 : 2 * P + 1), st));
-            if (Q > 0) {
-                if (qd.off) HIP_TRY(c, hipMemcpyAsync(qd.off, qt.off, 8 * (2 * P + 1), hipMemcpyDeviceToDevice, st));
-                if (qd.res) HIP_TRY(c, hipMemcpyAsync(qd.res, qt.res, 8 * Q, hipMemcpyDeviceToDevice, st));
-                if (qd.cnt) HIP_TRY(c, hipMemcpyAsync(qd.cnt, qt.cnt, 8 * Q, hipMemcpyDeviceToDevice, st));
-                if (qd.rev) HIP_TRY(c, hipMemcpyAsync(qd.rev, qt.rev, 4 * Q, hipMemcpyDeviceToDevice, st));
-                HIP_TRY(c, hipMemcpyAsync(qd.area, qt.area, 8 * Q, hipMemcpyDeviceToDevice, st));
-            }
-            if (d_side_offsets) HIP_TRY(c, hipMemcpyAsync(d_side_offsets, pl.side_off.data(), 8 * (2 * P + 1), hipMemcpyHostToDevice, st));
-            if (P == 0) {
-                if (d_contact_first) HIP_TRY(c, hipMemsetAsync(d_contact_first, 0, 8, st));
-                return 0;
-            }
-            if (d_pair_struct) HIP_TRY(c, hipMemcpyAsync(d_pair_struct, pl.pair_struct.data(), 4 * P, hipMemcpyHostToDevice, st));
-            if (d_pair_groups) HIP_TRY(c, hipMemcpyAsync(d_pair_groups, pl.pair_groups.data(), 8 * P, hipMemcpyHostToDevice, st));
-            HIP_TRY(c, hipMemcpyAsync(d_pair_areas, c->if_areas.p, 48 * P, hipMemcpyDeviceToDevice, st));
-            if (d_pair_atom) HIP_TRY(c, hipMemcpyAsync(d_pair_atom, c->if_patom.p, 4 * M, hipMemcpyDeviceToDevice, st));
-            if (d_pair_buried) HIP_TRY(c, hipMemcpyAsync(d_pair_buried, c->if_pburied.p, 8 * M, hipMemcpyDeviceToDevice, st));
-            if (d_buried_masks) HIP_TRY(c, hipMemcpyAsync(d_buried_masks, t.buried, 4 * SR_CAP_WORDS * M, hipMemcpyDeviceToDevice, st));
-            if (D == 0) {
-                if (d_contact_first) HIP_TRY(c, hipMemsetAsync(d_contact_first, 0, 8 * (M + 1), st));
-                return 0;
-            }
-            if (d_contact_first) HIP_TRY(c, hipMemcpyAsync(d_contact_first, t.first, 8 * (M + 1), hipMemcpyDeviceToDevice, st));
-            if (d_contact_partner) HIP_TRY(c, hipMemcpyAsync(d_contact_partner, t.partner, 4 * Cn, hipMemcpyDeviceToDevice, st));
-            if (d_contact_points) HIP_TRY(c, hipMemcpyAsync(d_contact_points, t.points, 4 * Cn, hipMemcpyDeviceToDevice, st));
-            if (d_contact_area) HIP_TRY(c, hipMemcpyAsync(d_contact_area, t.area, 8 * Cn, hipMemcpyDeviceToDevice, st));
-            if (d_dot_partner) HIP_TRY(c, hipMemcpyAsync(d_dot_partner, t.dot_partner, 4 * D, hipMemcpyDeviceToDevice, st));
-            return 0;
-        }();
-        if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = ctx_fail(c, "stream synchronize failed"); /* (the call is synchronous) */
-        return rc;
-    });
+    IfaceCall k;
+    k.xyz = d_xyz; k.radii = d_radii; k.offsets = offsets; k.n_structs = n_structs; k.group = d_group; k.n_groups = n_groups;
+    k.alg = alg; k.probe = probe_radius; k.resolution = resolution;
+    k.sasa = d_sasa; k.iso = d_iso; k.totals = d_totals; k.group_totals = d_group_totals;
+    k.whole = k.residues = true; k.out_dev = true;
+    k.res_first = res_first; k.n_res = n_res; k.min_buried = min_buried;
+    k.pair_capacity = pair_capacity; k.atom_capacity = atom_capacity; k.res_capacity = res_capacity;
+    k.n_pairs = n_pairs_out; k.n_pair_atoms = n_pair_atoms_out; k.n_res_rows = n_res_rows_out;
+    k.pair_struct = d_pair_struct; k.pair_groups = d_pair_groups; k.pair_areas = d_pair_areas; k.side_offsets = d_side_offsets;
+    k.pair_atom = d_pair_atom; k.pair_buried = d_pair_buried;
+    k.res_offsets = d_res_offsets; k.res_index = d_res_index; k.res_atoms = d_res_atoms; k.res_areas = d_res_areas;
+    return iface_dev(c, k);
 }
 
 extern "C" int freesasa_gpu_interface_contacts_dev(freesasa_gpu_ctx *c, int alg, const double *d_xyz, const double *d_radii,
@@ -750,11 +746,18 @@ extern "C" int freesasa_gpu_interface_contacts_dev(freesasa_gpu_ctx *c, int alg,
                                                    int64_t *d_contact_first, int32_t *d_contact_partner, int32_t *d_contact_points,
                                                    double *d_contact_area, uint32_t *d_buried_masks, int32_t *d_dot_partner)
 {
-    return iface_contacts_dev(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe_radius, resolution, d_sasa, d_iso, d_totals,
-                              d_group_totals, pair_capacity, atom_capacity, contact_capacity, dot_capacity, n_pairs_out, n_pair_atoms_out,
-                              n_contacts_out, n_buried_dots_out, d_pair_struct, d_pair_groups, d_pair_areas, d_side_offsets, d_pair_atom,
-                              d_pair_buried, d_contact_first, d_contact_partner, d_contact_points, d_contact_area, d_buried_masks,
-                              d_dot_partner, nullptr, IfaceResContactOut());
+    IfaceCall k;
+    k.xyz = d_xyz; k.radii = d_radii; k.offsets = offsets; k.n_structs = n_structs; k.group = d_group; k.n_groups = n_groups;
+    k.alg = alg; k.probe = probe_radius; k.resolution = resolution;
+    k.sasa = d_sasa; k.iso = d_iso; k.totals = d_totals; k.group_totals = d_group_totals;
+    k.whole = k.contacts = true; k.out_dev = true;
+    k.pair_capacity = pair_capacity; k.atom_capacity = atom_capacity; k.contact_capacity = contact_capacity; k.dot_capacity = dot_capacity;
+    k.n_pairs = n_pairs_out; k.n_pair_atoms = n_pair_atoms_out; k.n_contacts = n_contacts_out; k.n_buried_dots = n_buried_dots_out;
+    k.pair_struct = d_pair_struct; k.pair_groups = d_pair_groups; k.pair_areas = d_pair_areas; k.side_offsets = d_side_offsets;
+    k.pair_atom = d_pair_atom; k.pair_buried = d_pair_buried;
+    k.contact_first = d_contact_first; k.contact_partner = d_contact_partner; k.contact_points = d_contact_points;
+    k.contact_area = d_contact_area; k.buried_masks = d_buried_masks; k.dot_partner = d_dot_partner;
+    return iface_dev(c, k);
 }
 
 extern "C" int freesasa_gpu_interface_residue_contacts_dev(
@@ -767,148 +770,23 @@ extern "C" int freesasa_gpu_interface_residue_contacts_dev(
     const int64_t *res_first, int n_res, long long rescontact_capacity, long long *n_rescontacts_out, int64_t *d_rescontact_offsets,
     int32_t *d_rescontact_residues, int32_t *d_rescontact_counts, double *d_rescontact_area, int32_t *d_rescontact_reverse)
 {
-    IfaceResContactWant qw;
-    qw.res_first = res_first; qw.n_res = n_res; qw.rescontact_capacity = rescontact_capacity; qw.n_rescontacts_out = n_rescontacts_out;
-    IfaceResContactOut qd;
-    qd.off = d_rescontact_offsets; qd.res = d_rescontact_residues; qd.cnt = d_rescontact_counts; qd.area = d_rescontact_area; qd.rev = d_rescontact_reverse;
-    return iface_contacts_dev(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe_radius, resolution, d_sasa, d_iso, d_totals,
-                              d_group_totals, pair_capacity, atom_capacity, contact_capacity, dot_capacity, n_pairs_out, n_pair_atoms_out,
-                              n_contacts_out, n_buried_dots_out, d_pair_struct, d_pair_groups, d_pair_areas, d_side_offsets, d_pair_atom,
-                              d_pair_buried, d_contact_first, d_contact_partner, d_contact_points, d_contact_area, d_buried_masks,
-                              d_dot_partner, &qw, qd);
-}
-
-/* the host-pointer entries: the batch as one chunk of the host-batch path, in place, as freesasa_gpu_calc_groups has it */
-struct IfaceContactHost { /* the contact entry's host arrays: any may be null */
-    int64_t *first = nullptr;
-    int32_t *partner = nullptr, *points = nullptr, *dot_partner = nullptr;
-    double *area = nullptr;
-    uint32_t *buried = nullptr;
-};
-static int iface_host(const double *xyz, const double *radii, const int64_t *offsets, int n_structs, const int32_t *group,
-                      const int32_t *n_groups, int alg, double probe, int resolution, double *sasa_out, double *iso_out, double *totals_out,
-                      double *group_totals_out, bool whole, long long pair_capacity, long long atom_capacity, long long *n_pairs_out,
-                      long long *n_pair_atoms_out, int32_t *pair_struct_out, int32_t *pair_groups_out, double *pair_areas_out,
-                      int64_t *side_offsets_out, int32_t *pair_atom_out, double *pair_buried_out, long long *stats_out, int device,
-                      char *err_out, int err_len, const IfaceResWant *rw = nullptr, int64_t *res_offsets_out = nullptr,
-                      int32_t *res_index_out = nullptr, int32_t *res_atoms_out = nullptr, double *res_areas_out = nullptr,
-                      const IfaceContactWant *cw = nullptr, const IfaceContactHost *co = nullptr, const IfaceResContactWant *qw = nullptr,
-                      const IfaceResContactOut *qo = nullptr)
-{
-    if (err_out && err_len > 0) err_out[0] = 0;
-    char msg[200];
-    if (iface_bad_args(xyz, radii, offsets, n_structs, group, n_groups, alg, resolution, msg, sizeof msg) ||
-        iface_bad_caps(pair_capacity, atom_capacity, msg, sizeof msg) || (rw && iface_res_bad_args(*rw, offsets, n_structs, msg, sizeof msg)) ||
-        (cw && iface_contact_bad_args(*cw, alg, resolution, nullptr, msg, sizeof msg)) ||
-        (qw && iface_rescontact_bad_args(*qw, offsets, n_structs, msg, sizeof msg)))
-        return set_err(err_out, err_len, msg);
-    if (!n_pairs_out || !n_pair_atoms_out || (whole && !pair_areas_out) || (rw && !res_areas_out) || (qw && !(qo && qo->area)))
-        return set_err(err_out, err_len, "null argument");
-    if (freesasa_gpu_device_count() <= 0)
-        return set_err(err_out, err_len, "no HIP device available: libfreesasa_amd has no CPU path");
-    return guarded(err_out, err_len, [&]() -> int {
-    IfacePlan pl; /* (declared before the lease: freed after its stream is idle) */
-    IfaceResTable t;
-    IfaceContactTable ct;
-    IfaceResContactTable qt;
-    PoolLease lease(device);
-    freesasa_gpu_ctx *c = lease.c;
-    if (!c) return set_err(err_out, err_len, "could not create a GPU context");
-    const size_t n = (size_t)offsets[n_structs];
-    int64_t G = 0; /* (bad counts are refused by the chain-group pipeline, with its message: staged for none here) */
-    for (int s = 0; s < n_structs; ++s) G += n_groups[s] > 0 && n_groups[s] <= 65535 ? n_groups[s] : 0;
-    BatchCall b;
-    b.fallback = "GPU interface batch failed";
-    Chunk h;
-    h.ns = n_structs; h.n = n; h.off = offsets; h.xyz = xyz; h.radii = radii;
-    const int rc = [&]() -> int {
-        c->err[0] = 0;
-        if (chunk_size(b, c, h) || ensure(c, c->h_group, 4 * n) || ensure(c, c->h_iso, 8 * n) || ensure(c, c->h_gtot, 24 * (size_t)G + 8)) return -1;
-        if (chunk_upload(c, h)) return -1;
-        hipStream_t st = c->stream;
-        if (hipMemcpyAsync(c->h_group.p, group, 4 * n, hipMemcpyHostToDevice, st) != hipSuccess) return ctx_fail(c, "host-to-device copy failed");
-        const double *d_xyz = (const double *)c->h_xyz.p, *d_radii = (const double *)c->h_radii.p;
-        const int32_t *d_group = (const int32_t *)c->h_group.p;
-        double *d_sasa = (double *)c->h_sasa.p, *d_iso = (double *)c->h_iso.p;
-        double *d_tot = totals_out ? (double *)c->h_totals.p : nullptr, *d_gtot = group_totals_out ? (double *)c->h_gtot.p : nullptr;
-        if (offsets[n_structs] > (int64_t)1 << 30) return ctx_fail(c, "batch too large (max 2^30 atoms per call)");
-        IfaceWant w;
-        w.pair_capacity = pair_capacity; w.atom_capacity = atom_capacity;
-        if (whole) {
-            w.rows = true; w.atoms = pair_atom_out || pair_buried_out || (co && (co->first || co->buried));
-            /* (with residues or contacts the pipeline holds no capacity itself: all are held together, once R or C and D_b are known) */
-            if (iface_pipeline(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe, resolution, d_sasa, d_iso, d_tot, d_gtot,
-                               rw || cw ? IfaceWant() : w, pl, n_pairs_out, n_pair_atoms_out))
-                return -1;
-            if (cw) {
-                if (iface_contacts(c, pl, probe, resolution, ct)) return -1;
-                *cw->n_contacts_out = ct.C;
-                if (cw->n_buried_dots_out) *cw->n_buried_dots_out = ct.D;
-                if (qw) {
-                    if (iface_rescontacts(c, pl, *qw, ct, qt)) return -1;
-                    *qw->n_rescontacts_out = qt.Q;
-                }
-                if (qw ? iface_rescontact_check_caps(c, pl, w, *cw, ct, *qw, qt.Q) : iface_contact_check_caps(c, pl, w, *cw, ct)) return -1;
-            }
-            if (rw) {
-                if (iface_residues(c, pl, *rw, d_iso, t)) return -1;
-                *rw->n_res_rows_out = t.R;
-                if (iface_res_check_caps(c, pl, w, *rw, t.R)) return -1;
-            }
-        } else {
-            IfaceArgs ia;
-            w.rows = pair_struct_out || pair_groups_out;
-            if (iface_screen(c, alg, d_xyz, d_radii, offsets, n_structs, d_group, n_groups, probe, resolution, d_sasa, d_iso, d_tot, d_gtot, pl, ia))
-                return -1;
-            *n_pairs_out = pl.P; *n_pair_atoms_out = pl.M;
-            if (iface_check_caps(c, pl, w)) return -1;
-        }
-        const size_t P = (size_t)pl.P, M = (size_t)pl.M, R = (size_t)t.R;
-        if (rw && res_offsets_out && P == 0) res_offsets_out[0] = 0;
-        if (rw && P > 0 &&
-            ((res_offsets_out && hipMemcpyAsync(res_offsets_out, t.off, 8 * (2 * P + 1), hipMemcpyDeviceToHost, st) != hipSuccess) ||
-             (R > 0 && res_index_out && hipMemcpyAsync(res_index_out, t.index, 4 * R, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-             (R > 0 && res_atoms_out && hipMemcpyAsync(res_atoms_out, t.atoms, 4 * R, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-             (R > 0 && hipMemcpyAsync(res_areas_out, t.areas, 24 * R, hipMemcpyDeviceToHost, st) != hipSuccess)))
-            return ctx_fail(c, "device-to-host copy failed");
-        if (cw && co) {
-            const size_t Cn = (size_t)ct.C, D = (size_t)ct.D;
-            if (co->first && (P == 0 || D == 0)) memset(co->first, 0, 8 * (P == 0 ? 1 : M + 1));
-            if (P > 0 &&
-                ((co->buried && hipMemcpyAsync(co->buried, ct.buried, 4 * SR_CAP_WORDS * M, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-                 (D > 0 && co->first && hipMemcpyAsync(co->first, ct.first, 8 * (M + 1), hipMemcpyDeviceToHost, st) != hipSuccess) ||
-                 (Cn > 0 && co->partner && hipMemcpyAsync(co->partner, ct.partner, 4 * Cn, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-                 (Cn > 0 && co->points && hipMemcpyAsync(co->points, ct.points, 4 * Cn, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-                 (Cn > 0 && co->area && hipMemcpyAsync(co->area, ct.area, 8 * Cn, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-                 (D > 0 && co->dot_partner && hipMemcpyAsync(co->dot_partner, ct.dot_partner, 4 * D, hipMemcpyDeviceToHost, st) != hipSuccess)))
-                return ctx_fail(c, "device-to-host copy failed");
-        }
-        if (qw) {
-            const size_t Q = (size_t)qt.Q;
-            if (qo->off && Q == 0) memset(qo->off, 0, 8 * (P == 0 ? 1 : 2 * P + 1));
-            if (Q > 0 &&
-                ((qo->off && hipMemcpyAsync(qo->off, qt.off, 8 * (2 * P + 1), hipMemcpyDeviceToHost, st) != hipSuccess) ||
-                 (qo->res && hipMemcpyAsync(qo->res, qt.res, 8 * Q, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-                 (qo->cnt && hipMemcpyAsync(qo->cnt, qt.cnt, 8 * Q, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-                 (qo->rev && hipMemcpyAsync(qo->rev, qt.rev, 4 * Q, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-                 hipMemcpyAsync(qo->area, qt.area, 8 * Q, hipMemcpyDeviceToHost, st) != hipSuccess))
-                return ctx_fail(c, "device-to-host copy failed");
-        }
-        if ((sasa_out && hipMemcpyAsync(sasa_out, d_sasa, 8 * n, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-            (iso_out && hipMemcpyAsync(iso_out, d_iso, 8 * n, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-            (totals_out && hipMemcpyAsync(totals_out, d_tot, 8 * (size_t)n_structs, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-            (group_totals_out && G > 0 && hipMemcpyAsync(group_totals_out, d_gtot, 24 * (size_t)G, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-            (whole && P > 0 && hipMemcpyAsync(pair_areas_out, c->if_areas.p, 48 * P, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-            (whole && P > 0 && pair_atom_out && hipMemcpyAsync(pair_atom_out, c->if_patom.p, 4 * M, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-            (whole && P > 0 && pair_buried_out && hipMemcpyAsync(pair_buried_out, c->if_pburied.p, 8 * M, hipMemcpyDeviceToHost, st) != hipSuccess))
-            return ctx_fail(c, "device-to-host copy failed");
-        if (hipStreamSynchronize(st) != hipSuccess) return ctx_fail(c, "stream synchronize failed");
-        iface_rows_to_host(pl, pair_struct_out, pair_groups_out, stats_out);
-        if (side_offsets_out) memcpy(side_offsets_out, pl.side_off.data(), 8 * (2 * P + 1));
-        return 0;
-    }();
-    return rc ? set_err(err_out, err_len, chunk_failed(b, c)) : 0;
-    });
+    IfaceCall k;
+    k.xyz = d_xyz; k.radii = d_radii; k.offsets = offsets; k.n_structs = n_structs; k.group = d_group; k.n_groups = n_groups;
+    k.alg = alg; k.probe = probe_radius; k.resolution = resolution;
+    k.sasa = d_sasa; k.iso = d_iso; k.totals = d_totals; k.group_totals = d_group_totals;
+    k.whole = k.contacts = k.rescontacts = true; k.out_dev = true;
+    k.res_first = res_first; k.n_res = n_res;
+    k.pair_capacity = pair_capacity; k.atom_capacity = atom_capacity; k.contact_capacity = contact_capacity; k.dot_capacity = dot_capacity;
+    k.rescontact_capacity = rescontact_capacity;
+    k.n_pairs = n_pairs_out; k.n_pair_atoms = n_pair_atoms_out; k.n_contacts = n_contacts_out; k.n_buried_dots = n_buried_dots_out;
+    k.n_rescontacts = n_rescontacts_out;
+    k.pair_struct = d_pair_struct; k.pair_groups = d_pair_groups; k.pair_areas = d_pair_areas; k.side_offsets = d_side_offsets;
+    k.pair_atom = d_pair_atom; k.pair_buried = d_pair_buried;
+    k.contact_first = d_contact_first; k.contact_partner = d_contact_partner; k.contact_points = d_contact_points;
+    k.contact_area = d_contact_area; k.buried_masks = d_buried_masks; k.dot_partner = d_dot_partner;
+    k.rescontact_offsets = d_rescontact_offsets; k.rescontact_residues = d_rescontact_residues; k.rescontact_counts = d_rescontact_counts;
+    k.rescontact_area = d_rescontact_area; k.rescontact_reverse = d_rescontact_reverse;
+    return iface_dev(c, k);
 }
 
 extern "C" int freesasa_gpu_calc_interface_pairs(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
@@ -917,9 +795,12 @@ extern "C" int freesasa_gpu_calc_interface_pairs(const double *xyz, const double
                                                  long long *n_pair_atoms_out, int32_t *pair_struct_out, int32_t *pair_groups_out,
                                                  long long *stats_out, int device, char *err_out, int err_len)
 {
-    return iface_host(xyz, radii, offsets, n_structs, group, n_groups, alg, probe_radius, resolution, nullptr, nullptr, nullptr, nullptr,
-                      false, pair_capacity, 0, n_pairs_out, n_pair_atoms_out, pair_struct_out, pair_groups_out, nullptr, nullptr, nullptr,
-                      nullptr, stats_out, device, err_out, err_len);
+    IfaceCall k;
+    k.xyz = xyz; k.radii = radii; k.offsets = offsets; k.n_structs = n_structs; k.group = group; k.n_groups = n_groups;
+    k.alg = alg; k.probe = probe_radius; k.resolution = resolution;
+    k.pair_capacity = pair_capacity; k.n_pairs = n_pairs_out; k.n_pair_atoms = n_pair_atoms_out;
+    k.pair_struct = pair_struct_out; k.pair_groups = pair_groups_out; k.stats = stats_out;
+    return iface_host(k, device, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_calc_interfaces(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
@@ -930,9 +811,15 @@ extern "C" int freesasa_gpu_calc_interfaces(const double *xyz, const double *rad
                                             double *pair_areas_out, int64_t *side_offsets_out, int32_t *pair_atom_out,
                                             double *pair_buried_out, int device, char *err_out, int err_len)
 {
-    return iface_host(xyz, radii, offsets, n_structs, group, n_groups, alg, probe_radius, resolution, sasa_out, iso_out, totals_out,
-                      group_totals_out, true, pair_capacity, atom_capacity, n_pairs_out, n_pair_atoms_out, pair_struct_out, pair_groups_out,
-                      pair_areas_out, side_offsets_out, pair_atom_out, pair_buried_out, nullptr, device, err_out, err_len);
+    IfaceCall k;
+    k.xyz = xyz; k.radii = radii; k.offsets = offsets; k.n_structs = n_structs; k.group = group; k.n_groups = n_groups;
+    k.alg = alg; k.probe = probe_radius; k.resolution = resolution;
+    k.sasa = sasa_out; k.iso = iso_out; k.totals = totals_out; k.group_totals = group_totals_out;
+    k.whole = true;
+    k.pair_capacity = pair_capacity; k.atom_capacity = atom_capacity; k.n_pairs = n_pairs_out; k.n_pair_atoms = n_pair_atoms_out;
+    k.pair_struct = pair_struct_out; k.pair_groups = pair_groups_out; k.pair_areas = pair_areas_out; k.side_offsets = side_offsets_out;
+    k.pair_atom = pair_atom_out; k.pair_buried = pair_buried_out;
+    return iface_host(k, device, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_calc_interface_residues(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
@@ -946,12 +833,18 @@ extern "C" int freesasa_gpu_calc_interface_residues(const double *xyz, const dou
                                                     int64_t *res_offsets_out, int32_t *res_index_out, int32_t *res_atoms_out,
                                                     double *res_areas_out, int device, char *err_out, int err_len)
 {
-    IfaceResWant rw;
-    rw.res_first = res_first; rw.n_res = n_res; rw.min_buried = min_buried; rw.res_capacity = res_capacity; rw.n_res_rows_out = n_res_rows_out;
-    return iface_host(xyz, radii, offsets, n_structs, group, n_groups, alg, probe_radius, resolution, sasa_out, iso_out, totals_out,
-                      group_totals_out, true, pair_capacity, atom_capacity, n_pairs_out, n_pair_atoms_out, pair_struct_out, pair_groups_out,
-                      pair_areas_out, side_offsets_out, pair_atom_out, pair_buried_out, nullptr, device, err_out, err_len, &rw,
-                      res_offsets_out, res_index_out, res_atoms_out, res_areas_out);
+    IfaceCall k;
+    k.xyz = xyz; k.radii = radii; k.offsets = offsets; k.n_structs = n_structs; k.group = group; k.n_groups = n_groups;
+    k.alg = alg; k.probe = probe_radius; k.resolution = resolution;
+    k.sasa = sasa_out; k.iso = iso_out; k.totals = totals_out; k.group_totals = group_totals_out;
+    k.whole = k.residues = true;
+    k.res_first = res_first; k.n_res = n_res; k.min_buried = min_buried;
+    k.pair_capacity = pair_capacity; k.atom_capacity = atom_capacity; k.res_capacity = res_capacity;
+    k.n_pairs = n_pairs_out; k.n_pair_atoms = n_pair_atoms_out; k.n_res_rows = n_res_rows_out;
+    k.pair_struct = pair_struct_out; k.pair_groups = pair_groups_out; k.pair_areas = pair_areas_out; k.side_offsets = side_offsets_out;
+    k.pair_atom = pair_atom_out; k.pair_buried = pair_buried_out;
+    k.res_offsets = res_offsets_out; k.res_index = res_index_out; k.res_atoms = res_atoms_out; k.res_areas = res_areas_out;
+    return iface_host(k, device, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_calc_interface_contacts(const double *xyz, const double *radii, const int64_t *offsets, int n_structs,
@@ -966,16 +859,18 @@ extern "C" int freesasa_gpu_calc_interface_contacts(const double *xyz, const dou
                                                     double *contact_area_out, uint32_t *buried_masks_out, int32_t *dot_partner_out,
                                                     int device, char *err_out, int err_len)
 {
-    IfaceContactWant cw;
-    cw.contact_capacity = contact_capacity; cw.dot_capacity = dot_capacity; cw.n_contacts_out = n_contacts_out; cw.n_buried_dots_out = n_buried_dots_out;
-    cw.rows = contact_partner_out || contact_points_out || contact_area_out; cw.dots = dot_partner_out != nullptr;
-    IfaceContactHost co;
-    co.first = contact_first_out; co.partner = contact_partner_out; co.points = contact_points_out; co.area = contact_area_out;
-    co.buried = buried_masks_out; co.dot_partner = dot_partner_out;
-    return iface_host(xyz, radii, offsets, n_structs, group, n_groups, alg, probe_radius, resolution, sasa_out, iso_out, totals_out,
-                      group_totals_out, true, pair_capacity, atom_capacity, n_pairs_out, n_pair_atoms_out, pair_struct_out, pair_groups_out,
-                      pair_areas_out, side_offsets_out, pair_atom_out, pair_buried_out, nullptr, device, err_out, err_len, nullptr, nullptr,
-                      nullptr, nullptr, nullptr, &cw, &co);
+    IfaceCall k;
+    k.xyz = xyz; k.radii = radii; k.offsets = offsets; k.n_structs = n_structs; k.group = group; k.n_groups = n_groups;
+    k.alg = alg; k.probe = probe_radius; k.resolution = resolution;
+    k.sasa = sasa_out; k.iso = iso_out; k.totals = totals_out; k.group_totals = group_totals_out;
+    k.whole = k.contacts = true;
+    k.pair_capacity = pair_capacity; k.atom_capacity = atom_capacity; k.contact_capacity = contact_capacity; k.dot_capacity = dot_capacity;
+    k.n_pairs = n_pairs_out; k.n_pair_atoms = n_pair_atoms_out; k.n_contacts = n_contacts_out; k.n_buried_dots = n_buried_dots_out;
+    k.pair_struct = pair_struct_out; k.pair_groups = pair_groups_out; k.pair_areas = pair_areas_out; k.side_offsets = side_offsets_out;
+    k.pair_atom = pair_atom_out; k.pair_buried = pair_buried_out;
+    k.contact_first = contact_first_out; k.contact_partner = contact_partner_out; k.contact_points = contact_points_out;
+    k.contact_area = contact_area_out; k.buried_masks = buried_masks_out; k.dot_partner = dot_partner_out;
+    return iface_host(k, device, err_out, err_len);
 }
 
 extern "C" int freesasa_gpu_calc_interface_residue_contacts(
@@ -989,19 +884,21 @@ extern "C" int freesasa_gpu_calc_interface_residue_contacts(
     int32_t *rescontact_residues_out, int32_t *rescontact_counts_out, double *rescontact_area_out, int32_t *rescontact_reverse_out, int device,
     char *err_out, int err_len)
 {
-    IfaceContactWant cw;
-    cw.contact_capacity = contact_capacity; cw.dot_capacity = dot_capacity; cw.n_contacts_out = n_contacts_out; cw.n_buried_dots_out = n_buried_dots_out;
-    cw.rows = contact_partner_out || contact_points_out || contact_area_out; cw.dots = dot_partner_out != nullptr;
-    IfaceContactHost co;
-    co.first = contact_first_out; co.partner = contact_partner_out; co.points = contact_points_out; co.area = contact_area_out;
-    co.buried = buried_masks_out; co.dot_partner = dot_partner_out;
-    IfaceResContactWant qw;
-    qw.res_first = res_first; qw.n_res = n_res; qw.rescontact_capacity = rescontact_capacity; qw.n_rescontacts_out = n_rescontacts_out;
-    IfaceResContactOut qo;
-    qo.off = rescontact_offsets_out; qo.res = rescontact_residues_out; qo.cnt = rescontact_counts_out; qo.area = rescontact_area_out;
-    qo.rev = rescontact_reverse_out;
-    return iface_host(xyz, radii, offsets, n_structs, group, n_groups, alg, probe_radius, resolution, sasa_out, iso_out, totals_out,
-                      group_totals_out, true, pair_capacity, atom_capacity, n_pairs_out, n_pair_atoms_out, pair_struct_out, pair_groups_out,
-                      pair_areas_out, side_offsets_out, pair_atom_out, pair_buried_out, nullptr, device, err_out, err_len, nullptr, nullptr,
-                      nullptr, nullptr, nullptr, &cw, &co, &qw, &qo);
+    IfaceCall k;
+    k.xyz = xyz; k.radii = radii; k.offsets = offsets; k.n_structs = n_structs; k.group = group; k.n_groups = n_groups;
+    k.alg = alg; k.probe = probe_radius; k.resolution = resolution;
+    k.sasa = sasa_out; k.iso = iso_out; k.totals = totals_out; k.group_totals = group_totals_out;
+    k.whole = k.contacts = k.rescontacts = true;
+    k.res_first = res_first; k.n_res = n_res;
+    k.pair_capacity = pair_capacity; k.atom_capacity = atom_capacity; k.contact_capacity = contact_capacity; k.dot_capacity = dot_capacity;
+    k.rescontact_capacity = rescontact_capacity;
+    k.n_pairs = n_pairs_out; k.n_pair_atoms = n_pair_atoms_out; k.n_contacts = n_contacts_out; k.n_buried_dots = n_buried_dots_out;
+    k.n_rescontacts = n_rescontacts_out;
+    k.pair_struct = pair_struct_out; k.pair_groups = pair_groups_out; k.pair_areas = pair_areas_out; k.side_offsets = side_offsets_out;
+    k.pair_atom = pair_atom_out; k.pair_buried = pair_buried_out;
+    k.contact_first = contact_first_out; k.contact_partner = contact_partner_out; k.contact_points = contact_points_out;
+    k.contact_area = contact_area_out; k.buried_masks = buried_masks_out; k.dot_partner = dot_partner_out;
+    k.rescontact_offsets = rescontact_offsets_out; k.rescontact_residues = rescontact_residues_out; k.rescontact_counts = rescontact_counts_out;
+    k.rescontact_area = rescontact_area_out; k.rescontact_reverse = rescontact_reverse_out;
+    return iface_host(k, device, err_out, err_len);
 }

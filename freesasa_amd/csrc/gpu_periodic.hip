@@ -528,28 +528,16 @@ static int calc_groups_periodic(bool tri, const double *xyz, const double *radii
     PoolLease lease(device);
     freesasa_gpu_ctx *c = lease.c;
     if (!c) return set_err(err_out, err_len, "could not create a GPU context");
-    const size_t n = (size_t)offsets[n_structs];
-    int64_t G = 0; /* (bad counts are refused by the device-pointer entry, with its message: staged for none here) */
-    for (int s = 0; s < n_structs; ++s) G += n_groups[s] > 0 && n_groups[s] <= 65535 ? n_groups[s] : 0;
-    /* the batch as one chunk of the host-batch path, in place: its sizing, upload and failure epilogue; the groups' extras here */
     const BatchCall b;
-    Chunk h;
-    h.ns = n_structs; h.n = n; h.off = offsets; h.xyz = xyz; h.radii = radii;
+    GroupBatch g; /* (the grouped host batch: gpu_groups.hip) */
+    g.xyz = xyz; g.radii = radii; g.offsets = offsets; g.n_structs = n_structs; g.group = group; g.n_groups = n_groups;
+    g.sasa_out = sasa_out; g.iso_out = iso_out; g.totals_out = totals_out; g.group_totals_out = group_totals_out;
     const int rc = [&]() -> int {
-        if (chunk_size(b, c, h) || ensure(c, c->h_group, 4 * n) || ensure(c, c->h_iso, 8 * n) || ensure(c, c->h_gtot, 24 * (size_t)G + 8)) return -1;
-        if (chunk_upload(c, h)) return -1;
-        if (hipMemcpyAsync(c->h_group.p, group, 4 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "host-to-device copy failed");
-        if (groups_periodic_dev(c, tri, alg, (const double *)c->h_xyz.p, (const double *)c->h_radii.p, offsets, n_structs,
-                                (const int32_t *)c->h_group.p, n_groups, cells, probe_radius, resolution, (double *)c->h_sasa.p,
-                                (double *)c->h_iso.p, totals_out ? (double *)c->h_totals.p : nullptr,
-                                group_totals_out ? (double *)c->h_gtot.p : nullptr, images_out))
+        if (group_batch_upload(b, c, g)) return -1;
+        if (groups_periodic_dev(c, tri, alg, g.d_xyz, g.d_radii, offsets, n_structs, g.d_group, n_groups, cells, probe_radius, resolution, g.d_sasa,
+                                g.d_iso, g.d_totals, g.d_group_totals, images_out))
             return -1;
-        if (hipMemcpyAsync(sasa_out, c->h_sasa.p, 8 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-            hipMemcpyAsync(iso_out, c->h_iso.p, 8 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-            (totals_out && hipMemcpyAsync(totals_out, c->h_totals.p, 8 * (size_t)n_structs, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-            (group_totals_out && G > 0 &&
-             hipMemcpyAsync(group_totals_out, c->h_gtot.p, 24 * (size_t)G, hipMemcpyDeviceToHost, c->stream) != hipSuccess))
-            return ctx_fail(c, "device-to-host copy failed");
+        if (group_batch_download(c, g)) return -1;
         if (hipStreamSynchronize(c->stream) != hipSuccess) return ctx_fail(c, "stream synchronize failed");
         return 0;
     }();
