@@ -1019,6 +1019,120 @@ def sweep_files_groups(paths, spec=None, separate_chains=False, long_syntax=Fals
     return totals, cls, atoms, status, gstatus, table
 
 
+EIFACE_GROUPS = 100    # FREESASA_GPU_EIFACE_GROUPS: a file with more than 4096 groups owns no interface rows
+
+
+class InterfaceTableC(C.Structure):
+    """freesasa_gpu_interface_table (include/freesasa_gpu.h)."""
+    _fields_ = [("n_files", C.c_int32), ("n_pairs", C.c_int64), ("n_res_rows", C.c_int64), ("pair_offsets", _lp),
+                ("pair_groups", C.POINTER(C.c_int32)), ("pair_atoms", C.POINTER(C.c_int32)), ("pair_chain", C.POINTER(C.c_char)),
+                ("pair_areas", _dp), ("pair_class_buried", _dp), ("res_offsets", _lp), ("res_index", C.POINTER(C.c_int32)),
+                ("res_atoms", C.POINTER(C.c_int32)), ("res_areas", _dp), ("res_name", C.POINTER(C.c_char)),
+                ("res_number", C.POINTER(C.c_char)), ("res_chain", C.POINTER(C.c_char))]
+
+
+class InterfaceTable:
+    """numpy copy of a freesasa_gpu_interface_table: file k owns pairs [pair_offsets[k], pair_offsets[k + 1]); per pair
+    pair_groups[p] (rows of the file's block of the GroupTable), pair_atoms[p] (per side), pair_areas[p] (calc_interfaces'
+    six columns), pair_class_buried[p, side] (apolar, polar, unknown) and the two groups' labels.  residues: the per-residue
+    rows of side q = 2 p + side are [res_offsets[q], res_offsets[q + 1]): res_index (the residue's place among the residues of
+    its file), res_atoms, res_areas (isolated, in the pair, buried) and the residue's labels, decoded like ResidueTable's."""
+
+    def __init__(self, ct, residues):
+        n, P, R = int(ct.n_files), int(ct.n_pairs), int(ct.n_res_rows)
+
+        def arr(ptr, count, dtype):
+            if count == 0:
+                return np.zeros(0, dtype=dtype)
+            nbytes = count * np.dtype(dtype).itemsize    # (one copy: a view of the C block, copied before the block is freed)
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_ubyte)), (nbytes,)).view(dtype).copy()
+        self.n_files, self.n_pairs, self.n_res_rows, self.residues = n, P, R, bool(residues)
+        self.pair_offsets = arr(ct.pair_offsets, n + 1, np.int64)
+        self.pair_groups = arr(ct.pair_groups, 2 * P, np.int32).reshape(P, 2)
+        self.pair_atoms = arr(ct.pair_atoms, 2 * P, np.int32).reshape(P, 2)
+        self.pair_chain_raw = arr(ct.pair_chain, 2 * P, "S4").reshape(P, 2)
+        self.pair_areas = arr(ct.pair_areas, 6 * P, np.float64).reshape(P, 6)
+        self.pair_class_buried = arr(ct.pair_class_buried, 6 * P, np.float64).reshape(P, 2, 3)
+        self.res_offsets = arr(ct.res_offsets, 2 * P + 1, np.int64) if residues else np.zeros(2 * P + 1, dtype=np.int64)
+        self.res_index = arr(ct.res_index, R, np.int32)
+        self.res_atoms = arr(ct.res_atoms, R, np.int32)
+        self.res_areas = arr(ct.res_areas, 3 * R, np.float64).reshape(R, 3)
+        self.res_name_raw = arr(ct.res_name, R, "S4")
+        self.res_number_raw = arr(ct.res_number, R, "S6")
+        self.res_chain_raw = arr(ct.res_chain, R, "S4")
+
+    @property
+    def pair_chain(self):
+        return [(g.decode(), h.decode()) for g, h in self.pair_chain_raw.tolist()]
+
+    @property
+    def res_name(self):
+        return [v.decode() for v in self.res_name_raw.tolist()]
+
+    @property
+    def res_number(self):
+        return [v.decode() for v in self.res_number_raw.tolist()]
+
+    @property
+    def res_chain(self):
+        return [v.decode() for v in self.res_chain_raw.tolist()]
+
+    def file(self, k):
+        """the slice of file k's pairs"""
+        return slice(int(self.pair_offsets[k]), int(self.pair_offsets[k + 1]))
+
+    def side_rows(self, p, side):
+        """the slice of the residue rows of side 0 / 1 of pair p"""
+        q = 2 * int(p) + int(side)
+        return slice(int(self.res_offsets[q]), int(self.res_offsets[q + 1]))
+
+
+def _ifsweep_proto(L):
+    L.freesasa_gpu_sweep_files_interfaces.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                                      C.c_longlong, _dp, _dp, _lp, _ip, _ip, C.c_int, C.c_void_p, C.c_char_p, C.c_int,
+                                                      _ip, C.POINTER(GroupTableC), C.c_int, C.c_double, _ip,
+                                                      C.POINTER(InterfaceTableC), C.c_char_p, C.c_int]
+    L.freesasa_gpu_interface_table_free.argtypes = [C.POINTER(InterfaceTableC)]
+    L.freesasa_gpu_interface_table_free.restype = None
+    L.freesasa_gpu_group_table_free.argtypes = [C.POINTER(GroupTableC)]
+    L.freesasa_gpu_group_table_free.restype = None
+    return L
+
+
+def sweep_files_interfaces(paths, spec=None, separate_chains=False, long_syntax=False, alg=LEE_RICHARDS, probe=1.4, resolution=20,
+                           ingest_options=0, n_threads=0, batch_atoms=0, device=-1, devices=None, classifier=None,
+                           residues=False, min_buried=0.0):
+    """freesasa_gpu_sweep_files_interfaces(): sweep_files_groups plus the interfaces between the chain groups of every file ->
+    (totals[n], class_sums[n,3], n_atoms[n], status[n], group_status[n], iface_status[n], groups: a GroupTable, interfaces:
+    an InterfaceTable).  The first five and the group table are sweep_files_groups'.  iface_status: the group status, or
+    EIFACE_GROUPS (more than 4096 groups), or 0; a file whose iface_status is not 0 owns no interface rows.  residues=True:
+    the per-residue rows of every side whose buried area is > min_buried.  Nothing per atom leaves the device."""
+    from . import ingest
+    L = _ifsweep_proto(lib())
+    n = len(paths)
+    arr = (C.c_char_p * n)(*[str(p).encode() for p in paths])
+    totals, atoms, status = np.zeros(n), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+    gstatus, istatus = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    cls = np.zeros((n, 3))
+    err = C.create_string_buffer(512)
+    keep, dp_, nd = _devs(devices, device)
+    gt, it = GroupTableC(), InterfaceTableC()
+    ret = L.freesasa_gpu_sweep_files_interfaces(arr, n, ingest_options, n_threads, alg, probe, resolution, batch_atoms,
+                                                totals.ctypes.data_as(_dp), cls.ctypes.data_as(_dp), atoms.ctypes.data_as(_lp),
+                                                status.ctypes.data_as(_ip), dp_, nd, ingest._handle(classifier),
+                                                spec.encode() if spec is not None else None, _group_flags(long_syntax, separate_chains),
+                                                gstatus.ctypes.data_as(_ip), C.byref(gt), 1 if residues else 0, float(min_buried),
+                                                istatus.ctypes.data_as(_ip), C.byref(it), err, 512)
+    if ret:
+        raise RuntimeError("freesasa_gpu_sweep_files_interfaces: " + err.value.decode())
+    try:
+        groups, table = GroupTable(gt), InterfaceTable(it, residues)
+    finally:
+        L.freesasa_gpu_group_table_free(C.byref(gt))
+        L.freesasa_gpu_interface_table_free(C.byref(it))
+    return totals, cls, atoms, status, gstatus, istatus, groups, table
+
+
 def sweep_files_resumable(paths, done_path, alg=LEE_RICHARDS, probe=1.4, resolution=20, ingest_options=0, n_threads=0,
                           batch_atoms=0, max_new_batches=0, device=-1, devices=None, classifier=None):
     """freesasa_gpu_sweep_files_resumable(): like sweep_files with a done-list at done_path (+ done_path.bin):

@@ -14,7 +14,8 @@
  *   gpu_frames.hip     the trajectory drivers' frame source: raw, DCD, AMBER NetCDF, GROMACS XTC and TRR input - open and its
  *                      refusals, the layout of a shard, read + check on the host, the kernels that make compact fp64 frames;
  *                      the XTC decode's test hook
- *   gpu_sweep.hip      the file sweep (host or device parser, done-list, per-residue table, selections) and the device parser's entries
+ *   gpu_sweep.hip      the file sweep (host or device parser, done-list, per-residue table, selections, chain groups, interfaces
+ *                      between them) and the device parser's entries
  *   gpu_parse.hip      the device-side PDB / mmCIF parser: its kernels and their host driver (gpu_parse.h)
  *   gpu_groups.hip     chain groups: a batch and every group of it cut out as a structure of its own, in one batch; the
  *                      group ids made on the device
@@ -59,6 +60,7 @@
 #include "iface_kernels.h"
 #include "contact_kernels.h"
 #include "rescontact_kernels.h"
+#include "ifsweep_kernels.h"
 #include "gpu_parse.h"
 
 /* ------------------------------------------------------------------ kernel launchers (gpu_kernels.hip) */
@@ -177,6 +179,10 @@ hipError_t kl_contact_rows(const sasa::ContactArgs &a, int *scratch, hipStream_t
    the sides' offsets (scratch: ifr_scan_scratch(M) ints) */
 hipError_t kl_rc_segments(const sasa::IfaceResArgs &s, int *scratch, hipStream_t st);
 hipError_t kl_rc_fold(const sasa::ResContactArgs &a, int *scratch, hipStream_t st);
+/* ... in the file sweep (ifsweep_kernels.h): the class of every pair-structure atom (one thread per atom; kl_class_sums over the
+   sides follows it); the rows' place in their file and their labels (one thread per residue row).  Neither is launched without rows. */
+hipError_t kl_ifs_side_class(const sasa::IfsClassArgs &a, hipStream_t st);
+hipError_t kl_ifs_res_rows(const sasa::IfsRowArgs &a, hipStream_t st);
 
 /* ------------------------------------------------------------------ context (gpu_engine.hip) */
 
@@ -259,6 +265,10 @@ struct freesasa_gpu_ctx {
     DevBuf if_cmasks, if_cwork, if_cdots, if_ctable;
     /* ... their residue-residue contact tables: the segments' and the fold's int32 work arrays; the table itself */
     DevBuf if_rcwork, if_rctable;
+    /* ... in the file sweep (gpu_sweep.hip): the structures' isolated areas are h_iso; the combined batch's offsets for the labels
+       (run_batch over the pair structures has taken c->offsets); the sides' class sums, pair_struct, the rows' place and labels,
+       the pair-structure atoms' classes */
+    DevBuf ifs_comb, ifs_work;
     int dt_unit_n = 0; /* the point count whose unit points dt_unit holds (the expansion's; 0: none) */
     void *stage_in = nullptr, *stage_out = nullptr; /* page-locked host staging of freesasa_gpu_calc_batch_pipelined */
     size_t stage_in_cap = 0, stage_out_cap = 0;
@@ -453,6 +463,104 @@ int dots_expand_resident(freesasa_gpu_ctx *c, const double *d_xyz, const double 
                          int *d_dot_point);
 /* the arguments the mask entries check before a device is touched: 0, or the message */
 const char *masks_bad_args(const void *xyz, const void *radii, const int64_t *offsets, int n_structs, int n_points, const void *sasa, const void *masks);
+
+/* ------------------------------------------------------------------ interfaces between chain groups (gpu_interfaces.hip) */
+
+/* What an entry was called with.  The batch and the four group outputs are where the pipeline reads and writes them: the caller's
+   device arrays (iface_dev), or - behind the upload - the context's staging (iface_host, the file sweep).  A null output array is
+   not delivered and asks for no capacity; a stage's own fields are looked at only where the stage is wanted. */
+struct IfaceCall {
+    const double *xyz = nullptr, *radii = nullptr;
+    const int64_t *offsets = nullptr;
+    int n_structs = 0;
+    const int32_t *group = nullptr, *n_groups = nullptr;
+    /* (the file sweep) the groups of every structure as the SCREEN counts them: n_groups[s], or 0 for a structure whose groups
+       are cut and summed (step 1) but whose pairs are not looked for; null: n_groups */
+    const int32_t *screen_groups = nullptr;
+    int alg = 0, resolution = 0;
+    double probe = 0;
+    double *sasa = nullptr, *iso = nullptr, *totals = nullptr, *group_totals = nullptr;
+    /* the stages behind the screen: steps 6 to 8, 9, 10, 11 (11 needs 10; 9 and 10 need 6 to 8) */
+    bool whole = false, residues = false, contacts = false, rescontacts = false;
+    const int64_t *res_first = nullptr;
+    /* (the file sweep) res_first [n_res + 1] is on the device already - the loader's own, trusted as k_gid_struct trusts it: it is
+       neither validated nor uploaded */
+    const int64_t *res_first_dev = nullptr;
+    int n_res = 0;
+    double min_buried = 0;
+    long long pair_capacity = 0, atom_capacity = 0, res_capacity = 0, contact_capacity = 0, dot_capacity = 0, rescontact_capacity = 0;
+    long long *n_pairs = nullptr, *n_pair_atoms = nullptr, *n_res_rows = nullptr, *n_contacts = nullptr, *n_buried_dots = nullptr,
+              *n_rescontacts = nullptr;
+    long long *stats = nullptr; /* host: the tests and the candidates of the screen */
+    /* the tables' arrays, all on the device (out_dev) or all on the host */
+    bool out_dev = false;
+    int32_t *pair_struct = nullptr, *pair_groups = nullptr, *pair_atom = nullptr;
+    double *pair_areas = nullptr, *pair_buried = nullptr;
+    int64_t *side_offsets = nullptr;
+    int64_t *res_offsets = nullptr;
+    int32_t *res_index = nullptr, *res_atoms = nullptr;
+    double *res_areas = nullptr;
+    int64_t *contact_first = nullptr;
+    int32_t *contact_partner = nullptr, *contact_points = nullptr, *dot_partner = nullptr;
+    double *contact_area = nullptr;
+    uint32_t *buried_masks = nullptr;
+    int64_t *rescontact_offsets = nullptr;
+    int32_t *rescontact_residues = nullptr, *rescontact_counts = nullptr, *rescontact_reverse = nullptr;
+    double *rescontact_area = nullptr;
+};
+
+struct IfacePlan {
+    int64_t P = 0, M = 0, T = 0, n_cand = 0;
+    int64_t n = 0, n_iso = 0;
+    int G = 0;
+    std::vector<int32_t> pair_struct, pair_groups; /* [P], [2 P] */
+    std::vector<int64_t> side_off;                 /* [2 P + 1] */
+    std::vector<int64_t> sides;                    /* the upload: side_off [2 P + 1] | side_start [2 P] | side_group [2 P] as int32 */
+    std::vector<int64_t> pair_off;                 /* [P + 1] the pair batch's offsets */
+    std::vector<int64_t> meta;                     /* the upload: gstart [G + 1] | tbase [n_structs + 1] */
+    std::vector<double> tp;                        /* S&R test points */
+};
+/* the tables of steps 9 to 11 where the stages left them, on the device; a pointer is null where the stage made no such array
+   (no pair; no buried point; no folded row), and iface_outputs' rows say what the caller gets then */
+struct IfaceResTable { /* c->if_rtable: res_offsets [2 P + 1] | res_areas [3 M] | res_index [M] | res_atoms [M], R rows of them used */
+    int64_t R = 0;
+    const int64_t *off = nullptr;
+    const double *areas = nullptr;
+    const int32_t *index = nullptr, *atoms = nullptr;
+};
+struct IfaceContactTable { /* c->if_ctable: contact_first [M + 1] | contact_area [D_b] | contact_partner [D_b] | contact_points [D_b], C rows used */
+    int64_t C = 0, D = 0;
+    const int64_t *first = nullptr;
+    const int32_t *partner = nullptr, *points = nullptr, *dot_partner = nullptr; /* (dot_partner: in c->if_cdots) */
+    const double *area = nullptr;
+    const unsigned *buried = nullptr; /* in c->if_cmasks */
+};
+struct IfaceResContactTable { /* c->if_rctable: rescontact_offsets [2 P + 1] | _area [C] | _residues [2 C] | _counts [2 C] | _reverse [C], Q rows used */
+    int64_t Q = 0;
+    const int64_t *off = nullptr;
+    const double *area = nullptr;
+    const int32_t *res = nullptr, *cnt = nullptr, *rev = nullptr;
+};
+/* What a call produced: the plan with P and M, the three tables with R, C and D_b, Q.  Its host arrays are the sources of copies
+   enqueued on the stream - the plan's uploads and deliveries, res_first -, so it is ONE object that lives until the stream is
+   idle: declared before the final synchronize in iface_dev and before the PoolLease in iface_host and in the sweep's worker. */
+struct IfaceRun {
+    IfacePlan pl;
+    sasa::IfaceArgs ia;
+    IfaceResTable rt;
+    IfaceContactTable ct;
+    IfaceResContactTable qt;
+    std::vector<int64_t> res_first; /* the upload of res_first: what the device searches is what was copied here, whatever
+                                       becomes of the caller's array while the stream runs */
+};
+/* The one run (gpu_interfaces.hip says what its stages are) on a call whose refusals the caller has made; every count output is
+   set as soon as its count is known.  The file sweep calls it with capacities that hold anything and no output arrays, sizes its
+   host arrays from r.pl.P, r.pl.M and r.rt.R, puts them into the call and delivers: */
+int iface_run(freesasa_gpu_ctx *c, const IfaceCall &k, IfaceRun &r);
+/* The delivery, in two calls around the caller's stream synchronization.  idle = false: everything that goes over the stream is
+   enqueued - to device arrays the context's buffers, the plan's arrays and the zeros; to host arrays the context's buffers (the
+   zeros are written at once).  idle = true, once the synchronize has succeeded: the plan's arrays into host arrays, and stats. */
+int iface_deliver(freesasa_gpu_ctx *c, const IfaceCall &k, const IfaceRun &r, bool idle);
 
 /* ------------------------------------------------------------------ host-side helpers (gpu_hostbatch.hip) */
 

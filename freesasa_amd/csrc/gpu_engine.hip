@@ -137,7 +137,7 @@ extern "C" void freesasa_gpu_ctx_destroy(freesasa_gpu_ctx *c)
                      &c->if_inpair, &c->if_areas, &c->if_patom, &c->if_pburied,
                      &c->if_rfirst, &c->if_rwork, &c->if_rsegs, &c->if_rtable,
                      &c->if_cmasks, &c->if_cwork, &c->if_cdots, &c->if_ctable,
-                     &c->if_rcwork, &c->if_rctable};
+                     &c->if_rcwork, &c->if_rctable, &c->ifs_comb, &c->ifs_work};
     for (DevBuf *b : all)
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : c->parse)

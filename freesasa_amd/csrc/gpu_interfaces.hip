@@ -6,7 +6,7 @@
  * (freesasa_gpu_interface_residue_contacts_dev, freesasa_gpu_calc_interface_residue_contacts).  Host code; the kernels are in
  * gpu_kernels.hip (phase functions: iface_kernels.h, contact_kernels.h, rescontact_kernels.h).
  *
- * The ten entries are ONE path.  An IfaceCall is what an entry was called with, filled by field name; an IfaceRun what the call
+ * The ten entries are ONE path (and the file sweep's interfaces, gpu_sweep.hip, go through its iface_run and iface_deliver).  An IfaceCall is what an entry was called with, filled by field name; an IfaceRun what the call
  * produced and what has to outlive the stream's work.  iface_dev (arrays on the context's stream) and iface_host (host arrays: the
  * grouped host batch of gpu_groups.hip, in place) both go through
  *   iface_bad_call    every refusal before a device is touched, in one order
@@ -55,87 +55,8 @@ using namespace sasa;
 
 namespace {
 
-/* What an entry was called with.  The batch and the four group outputs are where the pipeline reads and writes them: the caller's
-   device arrays (iface_dev), or - behind the upload - the context's staging (iface_host).  A null output array is not delivered
-   and asks for no capacity; a stage's own fields are looked at only where the stage is wanted. */
-struct IfaceCall {
-    const double *xyz = nullptr, *radii = nullptr;
-    const int64_t *offsets = nullptr;
-    int n_structs = 0;
-    const int32_t *group = nullptr, *n_groups = nullptr;
-    int alg = 0, resolution = 0;
-    double probe = 0;
-    double *sasa = nullptr, *iso = nullptr, *totals = nullptr, *group_totals = nullptr;
-    /* the stages behind the screen: steps 6 to 8, 9, 10, 11 (11 needs 10; 9 and 10 need 6 to 8) */
-    bool whole = false, residues = false, contacts = false, rescontacts = false;
-    const int64_t *res_first = nullptr;
-    int n_res = 0;
-    double min_buried = 0;
-    long long pair_capacity = 0, atom_capacity = 0, res_capacity = 0, contact_capacity = 0, dot_capacity = 0, rescontact_capacity = 0;
-    long long *n_pairs = nullptr, *n_pair_atoms = nullptr, *n_res_rows = nullptr, *n_contacts = nullptr, *n_buried_dots = nullptr,
-              *n_rescontacts = nullptr;
-    long long *stats = nullptr; /* host: the tests and the candidates of the screen */
-    /* the tables' arrays, all on the device (out_dev) or all on the host */
-    bool out_dev = false;
-    int32_t *pair_struct = nullptr, *pair_groups = nullptr, *pair_atom = nullptr;
-    double *pair_areas = nullptr, *pair_buried = nullptr;
-    int64_t *side_offsets = nullptr;
-    int64_t *res_offsets = nullptr;
-    int32_t *res_index = nullptr, *res_atoms = nullptr;
-    double *res_areas = nullptr;
-    int64_t *contact_first = nullptr;
-    int32_t *contact_partner = nullptr, *contact_points = nullptr, *dot_partner = nullptr;
-    double *contact_area = nullptr;
-    uint32_t *buried_masks = nullptr;
-    int64_t *rescontact_offsets = nullptr;
-    int32_t *rescontact_residues = nullptr, *rescontact_counts = nullptr, *rescontact_reverse = nullptr;
-    double *rescontact_area = nullptr;
-};
-
-struct IfacePlan {
-    int64_t P = 0, M = 0, T = 0, n_cand = 0;
-    int64_t n = 0, n_iso = 0;
-    int G = 0;
-    std::vector<int32_t> pair_struct, pair_groups; /* [P], [2 P] */
-    std::vector<int64_t> side_off;                 /* [2 P + 1] */
-    std::vector<int64_t> sides;                    /* the upload: side_off [2 P + 1] | side_start [2 P] | side_group [2 P] as int32 */
-    std::vector<int64_t> pair_off;                 /* [P + 1] the pair batch's offsets */
-    std::vector<int64_t> meta;                     /* the upload: gstart [G + 1] | tbase [n_structs + 1] */
-    std::vector<double> tp;                        /* S&R test points */
-};
-/* the tables of steps 9 to 11 where the stages left them, on the device; a pointer is null where the stage made no such array
-   (no pair; no buried point; no folded row), and iface_outputs' rows say what the caller gets then */
-struct IfaceResTable { /* c->if_rtable: res_offsets [2 P + 1] | res_areas [3 M] | res_index [M] | res_atoms [M], R rows of them used */
-    int64_t R = 0;
-    const int64_t *off = nullptr;
-    const double *areas = nullptr;
-    const int32_t *index = nullptr, *atoms = nullptr;
-};
-struct IfaceContactTable { /* c->if_ctable: contact_first [M + 1] | contact_area [D_b] | contact_partner [D_b] | contact_points [D_b], C rows used */
-    int64_t C = 0, D = 0;
-    const int64_t *first = nullptr;
-    const int32_t *partner = nullptr, *points = nullptr, *dot_partner = nullptr; /* (dot_partner: in c->if_cdots) */
-    const double *area = nullptr;
-    const unsigned *buried = nullptr; /* in c->if_cmasks */
-};
-struct IfaceResContactTable { /* c->if_rctable: rescontact_offsets [2 P + 1] | _area [C] | _residues [2 C] | _counts [2 C] | _reverse [C], Q rows used */
-    int64_t Q = 0;
-    const int64_t *off = nullptr;
-    const double *area = nullptr;
-    const int32_t *res = nullptr, *cnt = nullptr, *rev = nullptr;
-};
-/* What a call produced: the plan with P and M, the three tables with R, C and D_b, Q.  Its host arrays are the sources of copies
-   enqueued on the stream - the plan's uploads and deliveries, res_first -, so it is ONE object that lives until the stream is
-   idle: declared before the final synchronize in iface_dev and before the PoolLease in iface_host. */
-struct IfaceRun {
-    IfacePlan pl;
-    IfaceArgs ia;
-    IfaceResTable rt;
-    IfaceContactTable ct;
-    IfaceResContactTable qt;
-    std::vector<int64_t> res_first; /* the upload of res_first: what the device searches is what was copied here, whatever
-                                       becomes of the caller's array while the stream runs */
-};
+/* (IfaceCall - what an entry was called with - and IfaceRun - what the call produced - are in engine_internal.h: the file sweep
+   goes through iface_run and iface_deliver too) */
 
 /* ------------------------------------------------------------------ the refusals before a device is touched */
 
@@ -259,10 +180,11 @@ int iface_screen(freesasa_gpu_ctx *c, const IfaceCall &k, IfaceRun &r)
     gstart[0] = n;
     for (int g = 0; g < G; ++g) gstart[g + 1] = gstart[g] + cnt[(size_t)g];
     pl.n_iso = gstart[G] - n;
+    const int32_t *sg = k.screen_groups ? k.screen_groups : k.n_groups; /* (a structure the screen passes over has no test) */
     int64_t T = 0;
     for (int s = 0; s < n_structs; ++s) {
         tbase[s] = T;
-        const int64_t ng = k.n_groups[s];
+        const int64_t ng = sg[s];
         T += ng * (ng - 1) / 2;
     }
     tbase[n_structs] = T;
@@ -307,7 +229,7 @@ int iface_screen(freesasa_gpu_ctx *c, const IfaceCall &k, IfaceRun &r)
     start.reserve(2 * (size_t)P); grp.reserve(2 * (size_t)P);
     int64_t t = 0, k0 = 0, M = 0;
     for (int s = 0; s < n_structs; ++s) {
-        const int ng = k.n_groups[s];
+        const int ng = sg[s];
         for (int g = 0; g + 1 < ng; ++g)
             for (int h = g + 1; h < ng; ++h, ++t) {
                 if (!flag[(size_t)t]) continue;
@@ -320,7 +242,7 @@ int iface_screen(freesasa_gpu_ctx *c, const IfaceCall &k, IfaceRun &r)
                     pl.side_off.push_back(M);
                 }
             }
-        k0 += ng;
+        k0 += k.n_groups[s];
     }
     pl.M = M;
     pl.pair_off.resize((size_t)P + 1);
@@ -385,14 +307,14 @@ int iface_residues(freesasa_gpu_ctx *c, const IfaceCall &k, IfaceRun &r)
     const size_t P = (size_t)pl.P, M = (size_t)pl.M;
     const size_t S = (size_t)ifr_scan_scratch(pl.M);
     hipStream_t st = c->stream;
-    if (iface_upload_res_first(c, k, r) || ensure(c, c->if_rwork, 4 * (6 * M + 3 + S) + 8) || ensure(c, c->if_rsegs, 24 * M) ||
+    if ((!k.res_first_dev && iface_upload_res_first(c, k, r)) || ensure(c, c->if_rwork, 4 * (6 * M + 3 + S) + 8) || ensure(c, c->if_rsegs, 24 * M) ||
         ensure(c, c->if_rtable, 8 * (2 * P + 1) + 24 * M + 8 * M))
         return -1;
     IfaceResArgs a;
     memset(&a, 0, sizeof a);
     a.n_pair_atoms = pl.M; a.n_sides = 2 * pl.P; a.n_res = k.n_res;
     a.side_off = (const int64_t *)c->if_sides.p; a.pair_atom = (const int *)c->if_patom.p;
-    a.res_first = (const int64_t *)c->if_rfirst.p; a.iso = k.iso; a.psasa = (const double *)c->if_sasa.p;
+    a.res_first = k.res_first_dev ? k.res_first_dev : (const int64_t *)c->if_rfirst.p; a.iso = k.iso; a.psasa = (const double *)c->if_sasa.p;
     a.min_buried = k.min_buried;
     int *w = (int *)c->if_rwork.p;
     a.atom_res = w; a.hs = w + M; a.seg_first = a.hs + M + 1; a.seg_res = a.seg_first + M + 1; a.seg_atoms = a.seg_res + M; a.ks = a.seg_atoms + M;
@@ -534,8 +456,10 @@ int iface_check_caps(freesasa_gpu_ctx *c, const IfaceCall &k, const IfaceRun &r)
     return 0;
 }
 
+} /* namespace */
+
 /* The one run: the screen or the whole pipeline, then the stages asked for.  Every count output is set as soon as its count is
-   known; the capacities are held behind the screen where no stage follows step 8, else behind the last stage. */
+   known; the capacities are held behind the screen where no stage follows step 8, else behind the last stage.  (engine_internal.h) */
 int iface_run(freesasa_gpu_ctx *c, const IfaceCall &k, IfaceRun &r)
 {
     const bool later = k.residues || k.contacts;
@@ -560,6 +484,8 @@ int iface_run(freesasa_gpu_ctx *c, const IfaceCall &k, IfaceRun &r)
 }
 
 /* ------------------------------------------------------------------ the one table of outputs and the one delivery */
+
+namespace {
 
 /* a deliverable array: `count` elements of `size` bytes from `src` - a device buffer of the context, or (plan) a host vector of
    the plan - to the caller's `dst` (null: not delivered); where the call made no such array (src null), `zeros` elements of 0 */
@@ -603,9 +529,12 @@ std::array<IfaceOut, IF_N_OUT> iface_outputs(freesasa_gpu_ctx *c, const IfaceCal
     }};
 }
 
+} /* namespace */
+
 /* The delivery, in two calls around the caller's stream synchronization.  idle = false: everything that goes over the stream is
    enqueued - to device arrays the context's buffers, the plan's arrays and the zeros; to host arrays the context's buffers (the
-   zeros are written at once).  idle = true, once the synchronize has succeeded: the plan's arrays into host arrays, and stats. */
+   zeros are written at once).  idle = true, once the synchronize has succeeded: the plan's arrays into host arrays, and stats.
+   (engine_internal.h) */
 int iface_deliver(freesasa_gpu_ctx *c, const IfaceCall &k, const IfaceRun &r, bool idle)
 {
     hipStream_t st = c->stream;
@@ -625,6 +554,8 @@ int iface_deliver(freesasa_gpu_ctx *c, const IfaceCall &k, const IfaceRun &r, bo
 }
 
 /* ------------------------------------------------------------------ the two entry kinds */
+
+namespace {
 
 /* the batch on the context's stream; the call is synchronous, and a failed one drains the stream too */
 int iface_dev(freesasa_gpu_ctx *c, const IfaceCall &k)

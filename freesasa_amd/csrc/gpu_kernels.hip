@@ -1513,6 +1513,28 @@ hipError_t kl_rc_fold(const ResContactArgs &a, int *scratch, hipStream_t st)
     return hipGetLastError();
 }
 
+/* ... in the file sweep (ifsweep_kernels.h): one thread per pair-structure atom, one thread per residue row; no launch without rows */
+__global__ __launch_bounds__(IFS_B) void k_ifs_side_class(IfsClassArgs a)
+{
+    ifs_side_class(a, (int64_t)blockIdx.x * IFS_B + threadIdx.x);
+}
+__global__ __launch_bounds__(IFS_B) void k_ifs_res_rows(IfsRowArgs a)
+{
+    ifs_res_rows(a, (int64_t)blockIdx.x * IFS_B + threadIdx.x);
+}
+hipError_t kl_ifs_side_class(const IfsClassArgs &a, hipStream_t st)
+{
+    if (a.n_pair_atoms <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_ifs_side_class, dim3((unsigned)((a.n_pair_atoms + IFS_B - 1) / IFS_B)), dim3(IFS_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_ifs_res_rows(const IfsRowArgs &a, hipStream_t st)
+{
+    if (a.n_rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_ifs_res_rows, dim3((unsigned)((a.n_rows + IFS_B - 1) / IFS_B)), dim3(IFS_B), 0, st, a);
+    return hipGetLastError();
+}
+
 void kl_dump_phase_clocks(void)
 {
 #ifdef SASA_PHASE_TIMING

@@ -8,6 +8,8 @@
  * (gpu_parse.hip), the files the device refuses read by the host parser - or every file read by the host parser.  From
  * there on a batch is "the atoms the device parsed, and behind them what the host parser read": ONE tail computes,
  * aggregates, copies back and records it, and sees the second case as the first with nothing parsed on the device.
+ * With chain groups the tail runs the chain-group pipeline in place of the plain batch (groups_run), and with interfaces the
+ * interface entries' one path in its place (ifaces_run: iface_run, gpu_interfaces.hip, whose step 1 is that pipeline).
  */
 #include <hip/hip_runtime.h>
 
@@ -165,6 +167,40 @@ struct GrpCollector {
     void add(std::unique_ptr<GrpBatch> &gb) { std::lock_guard<std::mutex> lk(mu); done.push_back(std::move(gb)); }
 };
 
+/* The interface table of freesasa_gpu_sweep_files_interfaces, collected like the group table: a block per batch, its pairs in the
+   batch's structure order and within a structure in the tests' order (fstart says where a file's run begins; a file whose
+   interface status is not 0 owns none), the residue rows of the 2 P sides behind res_off. */
+struct IfcBatch {
+    int first = 0, ns = 0;
+    std::vector<long long> fstart, fcount;      /* [ns] pairs */
+    long long P = 0, R = 0;
+    std::vector<int32_t> groups, atoms;         /* [2 P] */
+    std::vector<uint32_t> chain;                /* [2 P] */
+    std::vector<double> areas, cls;             /* [6 P] each */
+    std::vector<int64_t> res_off;               /* [2 P + 1] */
+    std::vector<int32_t> res_index, res_atoms;  /* [R] (the index: among the residues of the row's file) */
+    std::vector<double> res_areas;              /* [3 R] */
+    std::vector<char> labels;                   /* names [4 R] | chains [4 R] | numbers [6 R] */
+    void size(long long P_, long long R_)
+    {
+        P = P_; R = R_;
+        groups.assign(2 * (size_t)P, 0); atoms.assign(2 * (size_t)P, 0); chain.assign(2 * (size_t)P, 0);
+        areas.resize(6 * (size_t)P); cls.resize(6 * (size_t)P);
+        res_off.assign(2 * (size_t)P + 1, 0);
+        res_index.resize((size_t)R); res_atoms.resize((size_t)R); res_areas.resize(3 * (size_t)R); labels.resize(14 * (size_t)R);
+    }
+};
+struct IfcCollector {
+    std::mutex mu;
+    std::vector<std::unique_ptr<IfcBatch>> done;
+    void add(std::unique_ptr<IfcBatch> &ib) { std::lock_guard<std::mutex> lk(mu); done.push_back(std::move(ib)); }
+};
+/* the interface request of a sweep with chain groups */
+struct IfaceSpec {
+    bool residues; double min_buried;
+    IfcCollector *col; int *status_out; /* [n_paths] */
+};
+
 /* what a sweep entry was called with (read-only) */
 struct SweepArgs {
     const char *const *paths; int n_paths, ingest_options, n_threads;
@@ -178,6 +214,7 @@ struct SweepArgs {
     double *sel_area_out; long long *sel_atoms_out;   /* [n_paths * selections] */
     const GroupSpec *grp;                             /* (may be NULL; never together with rcol or sel) */
     GrpCollector *gcol; int *group_status_out;        /* [n_paths] */
+    const IfaceSpec *ifc;                             /* (may be NULL; only with grp) */
 };
 /* what the workers of one sweep share */
 struct Sweep {
@@ -238,11 +275,18 @@ struct Work {
     std::vector<long long> sel_count;
     std::unique_ptr<GrpBatch> gb;         /* chain groups: the batch's block, the words of its structures (status in | n_groups | group status) */
     std::vector<int32_t> gwords;
+    std::unique_ptr<IfcBatch> ib;         /* interfaces: the batch's block, the groups of its structures as the screen counts them, P | M | R */
+    std::vector<int32_t> screen;
+    long long if_counts[3] = {0, 0, 0};
     Work(const Sweep &S, int b_) : b(b_), first(S.cut[b_]), ns(S.cut[b_ + 1] - S.cut[b_]), atoms((size_t)ns), status((size_t)ns), host((size_t)ns), atoms64((size_t)ns, 0)
     {
         if (S.a.gcol) {
             gb.reset(new GrpBatch);
             gb->first = first; gb->ns = ns; gb->fstart.assign((size_t)ns, 0); gb->fcount.assign((size_t)ns, 0);
+        }
+        if (S.a.ifc) {
+            ib.reset(new IfcBatch);
+            ib->first = first; ib->ns = ns; ib->fstart.assign((size_t)ns, 0); ib->fcount.assign((size_t)ns, 0); ib->size(0, 0);
         }
         if (!S.a.rcol) return;
         rb.reset(new ResBatch);
@@ -409,7 +453,102 @@ int select_enqueue(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, int 
    back (they size the combined batch); then the complex and its groups as ONE batch (groups_resident, gpu_groups.hip).  The
    groups' atoms, and on the stream their three areas and - separate chains - their labels on the way into w.gb.  Leaves the
    complex's areas in c->g_sasa and its totals in d_tot. */
-int groups_run(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, int nst, const std::vector<int64_t> &off, std::vector<int64_t> &hrf, double *d_tot)
+int sweep_batch_too_large(Sweep &S, freesasa_gpu_ctx *c, const Work &w, const char *what, long long count)
+{
+    const char *p0 = S.a.paths[w.first], *p1 = S.a.paths[w.first + w.ns - 1];
+    return ctx_fail(c, "the batch of files %d .. %d (%.90s .. %.90s) needs %lld %s: use a smaller batch_atoms", w.first, w.first + w.ns - 1,
+                    p0 ? p0 : "", p1 ? p1 : "", count, what);
+}
+
+/* interfaces, IN PLACE of groups_resident (which is iface_run's step 1: the group outputs come from the same buffers): the one
+   run with capacities that hold anything and no output arrays; the batch's block sized from P and R; the sides' class sums
+   (k_ifs_side_class, the class-sum kernel over the sides) and the rows' place and labels (k_ifs_res_rows); the delivery into the
+   block enqueued.  ng [nst]: the groups of every structure (0 where the group status is not 0); cnt: the atoms of every group.
+   `r` outlives the stream's work (the worker's). */
+int ifaces_run(Sweep &S, freesasa_gpu_ctx *c, Work &w, int nst, const std::vector<int64_t> &off, const int32_t *d_group, const int32_t *ng,
+               long long n_res, long long Rd, double *d_tot, IfaceRun &r, std::vector<int> *cnt)
+{
+    const SweepArgs &a = S.a;
+    const long long n_all = off[(size_t)nst], Rh = n_res - Rd;
+    w.screen.assign(ng, ng + nst);
+    long long T = 0;
+    for (int k = 0; k < nst; ++k) {
+        if (w.screen[(size_t)k] > IF_MAX_GROUPS) w.screen[(size_t)k] = 0; /* (FREESASA_GPU_EIFACE_GROUPS: its groups are summed, its pairs not looked for) */
+        T += (long long)w.screen[(size_t)k] * (w.screen[(size_t)k] - 1) / 2;
+    }
+    if (T > IF_MAX_TESTS) return sweep_batch_too_large(S, c, w, "pairs of groups to test (a batch takes up to 2^27)", T);
+    if (ensure(c, c->h_iso, 8 * (size_t)n_all)) return -1;
+    r = IfaceRun();
+    IfaceCall k;
+    k.xyz = (const double *)c->h_xyz.p; k.radii = (const double *)c->h_radii.p; k.offsets = off.data(); k.n_structs = nst;
+    k.group = d_group; k.n_groups = ng; k.screen_groups = w.screen.data();
+    k.alg = a.alg; k.probe = a.probe; k.resolution = a.resolution;
+    k.sasa = (double *)c->h_sasa.p; k.iso = (double *)c->h_iso.p; k.totals = d_tot; k.group_totals = (double *)c->h_gtot.p;
+    k.whole = true; k.residues = a.ifc->residues;
+    k.res_first_dev = (const int64_t *)c->parse[PBUF_RES_FIRST].p; k.n_res = (int)n_res; k.min_buried = a.ifc->min_buried;
+    k.pair_capacity = k.atom_capacity = k.res_capacity = 0x7fffffffffffffffLL;
+    k.n_pairs = &w.if_counts[0]; k.n_pair_atoms = &w.if_counts[1]; k.n_res_rows = &w.if_counts[2];
+    if (iface_run(c, k, r)) {
+        const long long atoms = (long long)(r.pl.n + r.pl.n_iso + r.pl.M);
+        return atoms > 1LL << 30 ? sweep_batch_too_large(S, c, w, "atoms in the batch, its groups and its pair structures together (a batch takes up to 2^30)", atoms) : -1;
+    }
+    const int64_t *gstart = r.pl.meta.data();
+    cnt->resize((size_t)r.pl.G);
+    for (int g = 0; g < r.pl.G; ++g) (*cnt)[(size_t)g] = (int)(gstart[g + 1] - gstart[g]);
+    const size_t P = (size_t)r.pl.P, M = (size_t)r.pl.M, R = (size_t)r.rt.R;
+    IfcBatch *ib = w.ib.get();
+    ib->size((long long)P, (long long)R);
+    if (P == 0) return 0; /* (nothing to launch, nothing to deliver) */
+    hipStream_t st = c->stream;
+    /* class sums [6 P] | pair_struct [P] | the rows' place [R] | names [4 R] | chains [4 R] | numbers [6 R] | the atoms' classes [M] */
+    const size_t o_ps = 48 * P, o_loc = o_ps + 4 * P, o_lab = o_loc + 4 * R, o_cls = o_lab + 14 * R + (R & 1) * 2;
+    if (ensure(c, c->ifs_work, o_cls + M + 8)) return -1;
+    char *wk = (char *)c->ifs_work.p;
+    sasa::IfsClassArgs ca;
+    memset(&ca, 0, sizeof ca);
+    ca.n_pair_atoms = (int64_t)M; ca.pair_atom = (const int *)c->if_patom.p; ca.cls = (const unsigned char *)c->h_counts.p;
+    ca.pcls = (unsigned char *)(wk + o_cls);
+    HIP_TRY(c, kl_ifs_side_class(ca, st));
+    HIP_TRY(c, kl_class_sums((const double *)c->if_pburied.p, ca.pcls, (const int64_t *)c->if_sides.p, (int)(2 * P), (double *)wk, st));
+    HIP_TRY(c, hipMemcpyAsync(ib->cls.data(), wk, 48 * P, hipMemcpyDeviceToHost, st));
+    IfaceCall d = k; /* the same call with the block's arrays */
+    d.pair_areas = ib->areas.data();
+    if (k.residues) { d.res_offsets = ib->res_off.data(); d.res_atoms = ib->res_atoms.data(); d.res_areas = ib->res_areas.data(); }
+    if (iface_deliver(c, d, r, false)) return -1;
+    if (R == 0) return 0;
+    sasa::IfsRowArgs ra;
+    memset(&ra, 0, sizeof ra);
+    ra.n_rows = (int64_t)R; ra.n_sides = (int64_t)(2 * P); ra.res_off = r.rt.off; ra.pair_struct = (const int *)(wk + o_ps);
+    ra.offsets = (const int64_t *)c->gi_words.p; ra.res_first = k.res_first_dev; ra.n_res = n_res; ra.n_res_dev = Rd; ra.res_index = r.rt.index;
+    ra.name_d = (const uint32_t *)c->parse[PBUF_RES_LABELS].p; ra.chain_d = ra.name_d + Rd; ra.number_d = (const uint16_t *)(ra.chain_d + Rd);
+    ra.name_h = (const uint32_t *)c->parse[PBUF_SEL_LABELS].p; ra.chain_h = ra.name_h + Rh; ra.number_h = (const uint16_t *)(ra.chain_h + Rh);
+    ra.res_local = (int *)(wk + o_loc); ra.name = (uint32_t *)(wk + o_lab); ra.chain = ra.name + R; ra.number = (uint16_t *)(ra.chain + R);
+    HIP_TRY(c, hipMemcpyAsync(wk + o_ps, r.pl.pair_struct.data(), 4 * P, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, kl_ifs_res_rows(ra, st));
+    HIP_TRY(c, hipMemcpyAsync(ib->res_index.data(), ra.res_local, 4 * R, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(ib->labels.data(), ra.name, 14 * R, hipMemcpyDeviceToHost, st));
+    return 0;
+}
+/* ... and, the stream waited for: what the plan holds of the table, the pairs' labels from the group block, a file's run of pairs */
+void ifaces_collect(Work &w, const IfaceRun &r)
+{
+    IfcBatch *ib = w.ib.get();
+    const GrpBatch *gb = w.gb.get();
+    for (long long p = 0; p < ib->P; ++p) {
+        const int k = r.pl.pair_struct[(size_t)p];
+        const size_t f = k < w.nd ? (size_t)k : (size_t)w.fb[(size_t)(k - w.nd)];
+        if (ib->fcount[f]++ == 0) ib->fstart[f] = p;
+        for (int side = 0; side < 2; ++side) {
+            const size_t q = 2 * (size_t)p + side;
+            ib->groups[q] = r.pl.pair_groups[q];
+            ib->atoms[q] = (int32_t)(r.pl.side_off[q + 1] - r.pl.side_off[q]);
+            ib->chain[q] = gb->chain[(size_t)(gb->fstart[f] + ib->groups[q])];
+        }
+    }
+}
+
+int groups_run(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, int nst, const std::vector<int64_t> &off, std::vector<int64_t> &hrf, double *d_tot,
+               IfaceRun &ir)
 {
     const SweepArgs &a = S.a;
     const GroupSpec &gs = *a.grp;
@@ -420,12 +559,18 @@ int groups_run(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, int nst,
     DevBuf *B = c->parse;
     if (parse_batch_dev_residues_build(c, (int)Rd, Rh, a.classifier != nullptr)) return -1;
     const size_t b_off = 8 * ((size_t)nst + 1);
-    if (ensure(c, B[PBUF_SEL_LABELS], 4 * (size_t)Rh + 4) || ensure(c, c->h_group, 4 * (size_t)n_all) || ensure(c, c->gi_words, b_off + 12 * (size_t)nst)) return -1;
+    /* (interfaces: the rows' labels are gathered on the device, so the host parser's names and numbers go up beside its chains -
+       the selection sweep's 14 bytes per residue, names | chains | numbers) */
+    const bool ifc = a.ifc != nullptr;
+    if (ensure(c, B[PBUF_SEL_LABELS], (ifc ? 14 : 4) * (size_t)Rh + 4) || ensure(c, c->h_group, 4 * (size_t)n_all) || ensure(c, c->gi_words, b_off + 12 * (size_t)nst)) return -1;
+    char *hlab = (char *)B[PBUF_SEL_LABELS].p + (ifc ? 4 * (size_t)Rh : 0); /* the host parser's chains */
     if (Rh > 0) {
         hrf.resize((size_t)Rh + 1);
         for (long long j = 0; j <= Rh; ++j) hrf[(size_t)j] = total + hb.b.res_first[j];
         if (hipMemcpyAsync((int64_t *)B[PBUF_RES_FIRST].p + Rd, hrf.data(), 8 * ((size_t)Rh + 1), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-            hipMemcpyAsync(B[PBUF_SEL_LABELS].p, hb.b.res_chain, 4 * (size_t)Rh, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+            hipMemcpyAsync(hlab, hb.b.res_chain, 4 * (size_t)Rh, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            (ifc && (hipMemcpyAsync(B[PBUF_SEL_LABELS].p, hb.b.res_name, 4 * (size_t)Rh, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+                     hipMemcpyAsync(hlab + 4 * (size_t)Rh, hb.b.res_number, 6 * (size_t)Rh, hipMemcpyHostToDevice, c->stream) != hipSuccess)))
             return ctx_fail(c, "host-to-device copy failed");
     }
     /* structure k < nd is file k (one the device refused: an empty structure that failed), structure nd + j the j-th file the host read */
@@ -440,7 +585,7 @@ int groups_run(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, int nst,
     memset(&ga, 0, sizeof ga);
     ga.offsets = (const int64_t *)words; ga.n_structs = nst;
     ga.res_first = (const int64_t *)B[PBUF_RES_FIRST].p; ga.n_res = R; ga.n_res_dev = Rd;
-    ga.chain_d = (const uint32_t *)B[PBUF_RES_LABELS].p + Rd; ga.chain_h = (const uint32_t *)B[PBUF_SEL_LABELS].p;
+    ga.chain_d = (const uint32_t *)B[PBUF_RES_LABELS].p + Rd; ga.chain_h = (const uint32_t *)hlab;
     ga.status = (const int32_t *)(words + b_off); ga.n_groups = (int32_t *)(words + b_off) + nst; ga.group_status = ga.n_groups + nst;
     ga.group = (int32_t *)c->h_group.p;
     if (group_ids_resident(c, gs, ga)) return -1;
@@ -453,8 +598,9 @@ int groups_run(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, int nst,
     for (int k = 0; k < nst; ++k) { if (gst[k] != 0) ng[k] = 0; G += ng[k]; }
     if (ensure(c, c->h_gtot, 24 * (size_t)G + 8)) return -1;
     std::vector<int> cnt;
-    if (groups_resident(c, a.alg, (const double *)c->h_xyz.p, (const double *)c->h_radii.p, off.data(), nst, ga.group, ng, a.probe, a.resolution,
-                        a.alg == 1 ? S.tp.data() : nullptr, nullptr, nullptr, d_tot, (double *)c->h_gtot.p, &cnt))
+    if (ifc ? ifaces_run(S, c, w, nst, off, ga.group, ng, R, Rd, d_tot, ir, &cnt)
+            : groups_resident(c, a.alg, (const double *)c->h_xyz.p, (const double *)c->h_radii.p, off.data(), nst, ga.group, ng, a.probe, a.resolution,
+                              a.alg == 1 ? S.tp.data() : nullptr, nullptr, nullptr, d_tot, (double *)c->h_gtot.p, &cnt))
         return -1;
     GrpBatch *gb = w.gb.get();
     gb->atoms.assign(cnt.begin(), cnt.end());
@@ -465,6 +611,7 @@ int groups_run(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, int nst,
         if (k < w.nd && w.host[(size_t)k]) continue;
         gb->fstart[f] = at; gb->fcount[f] = ng[k];
         a.group_status_out[w.first + (int)f] = gst[k];
+        if (ifc) a.ifc->status_out[w.first + (int)f] = gst[k] ? gst[k] : (ng[k] > IF_MAX_GROUPS ? FREESASA_GPU_EIFACE_GROUPS : 0);
         if (!gs.separate) for (int g = 0; g < ng[k]; ++g) gb->chain[(size_t)(at + g)] = gs.first_label[(size_t)g];
         at += ng[k];
     }
@@ -474,6 +621,14 @@ int groups_run(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, int nst,
         sasa::GidLabelArgs la;
         memset(&la, 0, sizeof la);
         la.coffsets = (const int64_t *)c->offsets.p; la.src = (const int *)c->g_src.p;
+        if (ifc && ir.pl.P > 0) { /* (run_batch over the pair structures has left ITS offsets in c->offsets: the combined batch's, from the counts) */
+            std::vector<int64_t> &comb = ir.res_first; /* (the run's spare host array: it outlives the stream's work) */
+            comb.assign(off.begin(), off.end());
+            for (long long g = 0; g < G; ++g) comb.push_back(comb.back() + cnt[(size_t)g]);
+            if (ensure(c, c->ifs_comb, 8 * comb.size())) return -1;
+            if (hipMemcpyAsync(c->ifs_comb.p, comb.data(), 8 * comb.size(), hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "host-to-device copy failed");
+            la.coffsets = (const int64_t *)c->ifs_comb.p;
+        }
         la.n_structs = nst; la.n_groups = (int)G; la.n_atoms = n_all;
         la.res_first = ga.res_first; la.n_res = R; la.n_res_dev = Rd; la.chain_d = ga.chain_d; la.chain_h = ga.chain_h;
         la.label = (uint32_t *)c->gi_label.p;
@@ -487,7 +642,7 @@ int groups_run(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, int nst,
 /* The rest of a batch, whoever parsed: w.nd structures of w.total atoms are on the device (c->h_xyz, h_radii, h_counts;
    backbone flags and residue keys in c->parse[]), hb holds the files w.fb as the host parser read them and goes up behind
    them.  Results into the caller's arrays, w.atoms64 / w.cls and w.rb; on success the stream has been waited for. */
-int tail(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, std::vector<int64_t> &hrf, std::vector<uint64_t> &hkeys)
+int tail(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, std::vector<int64_t> &hrf, std::vector<uint64_t> &hkeys, IfaceRun &ir)
 {
     const SweepArgs &a = S.a;
     const int ns = w.ns, first = w.first, nd = w.nd, nst = nd + (int)w.fb.size();
@@ -509,6 +664,7 @@ int tail(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, std::vector<in
     }
     for (size_t j = 0; j < w.fb.size(); ++j) { a.status_out[first + w.fb[j]] = hb.b.status[j]; w.atoms64[(size_t)w.fb[j]] = hb.b.offsets[j + 1] - hb.b.offsets[j]; }
     if (a.grp) for (int k = 0; k < ns; ++k) a.group_status_out[first + k] = a.status_out[first + k]; /* (a batch without atoms: nobody loaded) */
+    if (a.ifc) for (int k = 0; k < ns; ++k) a.ifc->status_out[first + k] = a.status_out[first + k];
     if (a.atoms_out) for (int k = 0; k < ns; ++k) a.atoms_out[first + k] = w.atoms64[(size_t)k];
     if (n_all == 0) return 0;
     if (extra > 0 &&
@@ -521,7 +677,7 @@ int tail(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, std::vector<in
     double *d_tot = (double *)c->h_totals.p, *d_cls = d_tot + nst;
     const double *d_areas = (const double *)c->h_sasa.p;
     if (a.grp) {
-        if (groups_run(S, c, w, hb, nst, off, hrf, d_tot)) return -1;
+        if (groups_run(S, c, w, hb, nst, off, hrf, d_tot, ir)) return -1;
         d_areas = (const double *)c->g_sasa.p;
     } else if (run_batch(c, a.alg == 0, (double *)c->h_xyz.p, (double *)c->h_radii.p, off.data(), nst, a.probe, a.resolution,
                          a.alg == 1 ? S.tp.data() : nullptr, (double *)c->h_sasa.p, nullptr, d_tot))
@@ -550,6 +706,7 @@ int tail(Sweep &S, freesasa_gpu_ctx *c, Work &w, const Batch &hb, std::vector<in
         memcpy(a.sel_area_out + f * n_sel, &w.sel_area[(size_t)k * n_sel], 8 * (size_t)n_sel);
         memcpy(a.sel_atoms_out + f * n_sel, &w.sel_count[(size_t)k * n_sel], 8 * (size_t)n_sel);
     }
+    if (a.ifc) ifaces_collect(w, ir);
     return w.R > 0 ? residues_collect(c, w, hb) : 0;
 }
 
@@ -582,6 +739,7 @@ void worker(Sweep &S, int wi) noexcept
     Batch hb;
     std::vector<int64_t> hrf;
     std::vector<uint64_t> hkeys; /* (the host parser's atom keys, packed: selections) */
+    IfaceRun ir;                 /* (interfaces: the run's plan - uploads read it) */
     DeviceNodeScope node(S.a.devices[wi]); /* this worker - its context's page-locked memory, its loader threads - on the device's NUMA node */
     PoolLease lease(S.a.devices[wi]);
     freesasa_gpu_ctx *c = lease.c;
@@ -599,12 +757,16 @@ void worker(Sweep &S, int wi) noexcept
         int ret = hipSetDevice(c->device) == hipSuccess ? 0 : ctx_fail(c, "hipSetDevice failed");
         if (!ret) ret = S.dev_parse ? front_device(S, c, cur, w, hb) : front_host(c, cur, w, hb);
         long long tr = S.sprof ? now_ns() : 0;
-        if (!ret) ret = tail(S, c, w, hb, hrf, hkeys);
+        if (!ret) {
+            /* (copies into the batch's blocks may be on the stream when a host allocation fails: they end before `w` does) */
+            try { ret = tail(S, c, w, hb, hrf, hkeys, ir); } catch (...) { (void)hipStreamSynchronize(c->stream); throw; }
+        }
         if (ret) (void)hipStreamSynchronize(c->stream); /* no copy may still read the batch when it is freed */
         if (S.sprof) { const long long t1 = now_ns(); S.tp_run += t1 - tr; tr = t1; }
         if (!ret && S.list.active()) ret = record(S, c, w);
         if (!ret && S.a.rcol) S.a.rcol->add(w.rb);
         if (!ret && S.a.gcol) S.a.gcol->add(w.gb);
+        if (!ret && S.a.ifc) S.a.ifc->col->add(w.ib);
         if (ret) S.fe.set(c->err[0] ? c->err : "GPU sweep failed");
         if (S.sprof) { const long long t1 = now_ns(); S.tp_rec += t1 - tr; tr = t1; }
         loader.join();
@@ -960,5 +1122,105 @@ extern "C" int freesasa_gpu_sweep_files_groups(const char *const *paths, int n_p
         return assemble_group_table(n_paths, col.done, table_out, err_out, err_len);
     });
     if (rc) freesasa_gpu_group_table_free(table_out);
+    return rc ? -1 : 0;
+}
+
+/* The sweep with the interfaces between chain groups (include/freesasa_gpu.h): the batches' blocks (IfcBatch) into ONE block
+   behind pair_offsets, files in the caller's order, each file's pairs in the tests' order, the residue rows of their sides behind
+   res_offsets. */
+static int assemble_interface_table(int n_paths, bool residues, std::vector<std::unique_ptr<IfcBatch>> &done, freesasa_gpu_interface_table *t,
+                                    char *err_out, int err_len)
+{
+    std::vector<long long> count((size_t)n_paths, 0), rows((size_t)n_paths, 0);
+    std::vector<char> seen((size_t)n_paths, 0);
+    for (auto &ib : done)
+        for (int k = 0; k < ib->ns; ++k) {
+            const size_t f = (size_t)(ib->first + k), p0 = (size_t)ib->fstart[(size_t)k], m = (size_t)ib->fcount[(size_t)k];
+            count[f] = (long long)m; seen[f] = 1;
+            if (residues && m) rows[f] = ib->res_off[2 * (p0 + m)] - ib->res_off[2 * p0];
+        }
+    long long P = 0, R = 0;
+    for (int f = 0; f < n_paths; ++f) {
+        if (!seen[(size_t)f]) return set_err(err_out, err_len, "a batch of the sweep left no interface block");
+        P += count[(size_t)f]; R += rows[(size_t)f];
+    }
+    const size_t n = (size_t)n_paths, p = (size_t)P, r = (size_t)R;
+    const size_t o_areas = 8 * (n + 1), o_cls = o_areas + 48 * p, o_roff = o_cls + 48 * p, o_rareas = o_roff + (residues ? 8 * (2 * p + 1) : 0),
+                 o_groups = o_rareas + 24 * r, o_atoms = o_groups + 8 * p, o_chain = o_atoms + 8 * p, o_rindex = o_chain + 8 * p,
+                 o_ratoms = o_rindex + 4 * r, o_rname = o_ratoms + 4 * r, o_rchain = o_rname + 4 * r, o_rnumber = o_rchain + 4 * r,
+                 bytes = o_rnumber + 6 * r;
+    char *blk = (char *)hf_malloc(bytes + 8);
+    if (!blk) return set_err(err_out, err_len, "out of host memory (interface table)");
+    t->n_files = n_paths; t->n_pairs = P; t->n_res_rows = R;
+    t->pair_offsets = (int64_t *)blk; t->pair_areas = (double *)(blk + o_areas); t->pair_class_buried = (double *)(blk + o_cls);
+    t->pair_groups = (int32_t *)(blk + o_groups); t->pair_atoms = (int32_t *)(blk + o_atoms); t->pair_chain = blk + o_chain;
+    if (residues) {
+        t->res_offsets = (int64_t *)(blk + o_roff); t->res_areas = (double *)(blk + o_rareas);
+        t->res_index = (int32_t *)(blk + o_rindex); t->res_atoms = (int32_t *)(blk + o_ratoms);
+        t->res_name = blk + o_rname; t->res_chain = blk + o_rchain; t->res_number = blk + o_rnumber;
+    }
+    t->pair_offsets[0] = 0;
+    for (int f = 0; f < n_paths; ++f) t->pair_offsets[f + 1] = t->pair_offsets[f] + count[(size_t)f];
+    std::vector<long long> row0((size_t)n_paths + 1, 0);
+    for (int f = 0; f < n_paths; ++f) row0[(size_t)f + 1] = row0[(size_t)f] + rows[(size_t)f];
+    if (residues) t->res_offsets[2 * p] = R;
+    for (auto &ib : done)
+        for (int k = 0; k < ib->ns; ++k) {
+            const size_t f = (size_t)(ib->first + k), m = (size_t)ib->fcount[(size_t)k], src = (size_t)ib->fstart[(size_t)k], dst = (size_t)t->pair_offsets[f];
+            if (!m) continue;
+            memcpy(t->pair_areas + 6 * dst, ib->areas.data() + 6 * src, 48 * m);
+            memcpy(t->pair_class_buried + 6 * dst, ib->cls.data() + 6 * src, 48 * m);
+            memcpy(t->pair_groups + 2 * dst, ib->groups.data() + 2 * src, 8 * m);
+            memcpy(t->pair_atoms + 2 * dst, ib->atoms.data() + 2 * src, 8 * m);
+            memcpy(t->pair_chain + 8 * dst, ib->chain.data() + 2 * src, 8 * m);
+            if (!residues) continue;
+            const long long b0 = ib->res_off[2 * src];
+            const size_t rs = (size_t)b0, rd = (size_t)row0[f], rm = (size_t)rows[f], RB = (size_t)ib->R;
+            for (size_t q = 0; q < 2 * m; ++q) t->res_offsets[2 * dst + q] = row0[f] + (ib->res_off[2 * src + q] - b0);
+            if (!rm) continue;
+            memcpy(t->res_index + rd, ib->res_index.data() + rs, 4 * rm);
+            memcpy(t->res_atoms + rd, ib->res_atoms.data() + rs, 4 * rm);
+            memcpy(t->res_areas + 3 * rd, ib->res_areas.data() + 3 * rs, 24 * rm);
+            memcpy(t->res_name + 4 * rd, ib->labels.data() + 4 * rs, 4 * rm);
+            memcpy(t->res_chain + 4 * rd, ib->labels.data() + 4 * RB + 4 * rs, 4 * rm);
+            memcpy(t->res_number + 6 * rd, ib->labels.data() + 8 * RB + 6 * rs, 6 * rm);
+        }
+    return 0;
+}
+
+extern "C" void freesasa_gpu_interface_table_free(freesasa_gpu_interface_table *table)
+{
+    if (!table) return;
+    free(table->pair_offsets); /* (the one block: assemble_interface_table) */
+    memset(table, 0, sizeof *table);
+}
+
+extern "C" int freesasa_gpu_sweep_files_interfaces(const char *const *paths, int n_paths, int ingest_options, int n_threads,
+                                                   int alg, double probe, int resolution, long long batch_atoms,
+                                                   double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out,
+                                                   const int *devices, int n_devices, const freesasa_ingest_classifier *classifier,
+                                                   const char *spec, int group_flags, int *group_status_out,
+                                                   freesasa_gpu_group_table *table_out, int residue_rows, double min_buried,
+                                                   int *iface_status_out, freesasa_gpu_interface_table *itable_out, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (table_out) memset(table_out, 0, sizeof *table_out);
+    if (itable_out) memset(itable_out, 0, sizeof *itable_out);
+    if (!group_status_out) return set_err(err_out, err_len, "null argument");
+    const int rc = guarded(err_out, err_len, [&]() -> int {
+        GroupSpec gs; /* (outlives the workers and their contexts' streams) */
+        if (group_spec_parse(spec, group_flags, &gs, err_out, err_len)) return -1;
+        if (!(min_buried >= 0.0) || min_buried > 1.7976931348623157e308) return set_err(err_out, err_len, "min_buried must be finite and >= 0");
+        if (!itable_out || !iface_status_out) return set_err(err_out, err_len, "null argument");
+        GrpCollector col;
+        IfcCollector icol;
+        const IfaceSpec is = {residue_rows != 0, min_buried, &icol, iface_status_out};
+        SweepArgs a = {paths, n_paths, ingest_options, n_threads, alg, probe, resolution, batch_atoms, totals_out, class_sums_out, atoms_out, status_out,
+                       nullptr, 0, devices, n_devices, classifier, nullptr, nullptr, nullptr, nullptr, &gs, &col, group_status_out, &is};
+        if (sweep_impl(a, err_out, err_len)) return -1;
+        if (table_out && assemble_group_table(n_paths, col.done, table_out, err_out, err_len)) return -1;
+        return assemble_interface_table(n_paths, is.residues, icol.done, itable_out, err_out, err_len);
+    });
+    if (rc) { freesasa_gpu_group_table_free(table_out); freesasa_gpu_interface_table_free(itable_out); }
     return rc ? -1 : 0;
 }

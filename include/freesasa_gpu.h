@@ -395,6 +395,67 @@ int freesasa_gpu_sweep_files_groups(const char *const *paths, int n_paths, int i
                                     const char *spec, int group_flags, int *group_status_out,
                                     freesasa_gpu_group_table *table_out, char *err, int err_len);
 void freesasa_gpu_group_table_free(freesasa_gpu_group_table *table);
+/* INTERFACES BETWEEN CHAIN GROUPS in the file sweep: every interface of every file of a sweep in one call - which groups of
+   chains bury each other, by how much, of which polar / apolar make-up, through which residues (the batch entries:
+   freesasa_gpu_interfaces_dev and freesasa_gpu_interface_residues_dev below).
+   _sweep_files_interfaces: the arguments of freesasa_gpu_sweep_files_groups up to group_status_out and table_out (the group
+   table may be NULL here), then residue_rows, min_buried, iface_status_out [n_paths] and itable_out.
+   Totals, class sums, atom counts, status, group status and the group table are byte for byte those of
+   freesasa_gpu_sweep_files_groups with the same arguments.
+   iface_status_out[k]: the group status of the file where that is not 0; else FREESASA_GPU_EIFACE_GROUPS for a file with more
+   than 4096 groups (the interface entries' limit: such a file keeps its totals and its rows of the group table, and the other
+   files of its batch are not affected); else 0.  A file whose interface status is not 0 owns no rows of the interface table.
+   itable_out: file k owns pairs [pair_offsets[k], pair_offsets[k + 1]), in file order and within a file in the pair order of
+   freesasa_gpu_interfaces_dev (g < h, the tests' order), whatever the devices, the workers or the batch cut.  Per pair p:
+   pair_groups[2 p ..] indices into the file's rows of the group table, pair_atoms[2 p ..] the atoms of the two sides,
+   pair_chain[8 p ..] both groups' 4-byte labels as the group table holds them, pair_areas[6 p ..] the six areas of
+   freesasa_gpu_interfaces_dev, pair_class_buried[6 p ..] per side the buried area split as apolar, polar, unknown (the class
+   order of freesasa_gpu_class_sums_dev).  With residue_rows != 0 also the per-residue table of
+   freesasa_gpu_interface_residues_dev (else those pointers are NULL and n_res_rows is 0): res_offsets [2 n_pairs + 1] rows per
+   side, and per row res_index, res_atoms, res_areas[3 r ..] and the residue's labels res_name / res_number / res_chain at
+   4 | 6 | 4 bytes; a row exists for a residue segment of a side whose buried area is > min_buried.  res_index is the residue's
+   place among the residues of ITS FILE: the row of the file's block in freesasa_gpu_sweep_files_residues' table.
+   Every area equals, bit for bit, what freesasa_gpu_calc_interface_residues gives on that file alone, loaded with
+   freesasa_ingest_pdb_files_ex and cut with freesasa_ingest_chain_groups (the engine's results do not depend on the batch, and
+   the residue sums are taken in strict atom order); pair_class_buried of side q is freesasa_gpu_class_sums_dev over pair_buried
+   with the class atom_class[pair_atom[m]] and side_offsets as the structures' offsets, bit for bit.
+   Refused before a device is touched or a file read: what freesasa_gpu_sweep_files_groups refuses, with its messages;
+   min_buried not finite or < 0 (the per-residue entry's message); a NULL itable_out or iface_status_out.  The call fails
+   when ONE BATCH needs more than 2^27 pair tests or more than 2^30 atoms (the batch, its groups and its pair structures
+   together): the message names the batch's first and last file and says to lower batch_atoms; when the call succeeds its
+   results never depend on the batch cut.
+   The pipeline is the batch entries' (csrc/gpu_interfaces.hip), run ONCE per batch with capacities that hold anything: P, M
+   and R size the batch's block afterwards.  Residue boundaries are the ones the sweep holds on the device; nothing per atom
+   leaves it.  Two kernels of its own (csrc/ifsweep_kernels.h): the classes of the pair structures' atoms, and the rows' place
+   in their file with their labels.
+   The table's arrays are ONE block, released by freesasa_gpu_interface_table_free only (which zeroes the struct; a zeroed struct
+   is a no-op); on any failure (-1, message in err) both tables are zeroed and nothing is kept.
+   Not offered: a done-list / resumable form, the cache sweep, contact tables in the sweep, interfaces in the trajectory drivers
+   and among periodic images. */
+#define FREESASA_GPU_EIFACE_GROUPS 100 /* (no FREESASA_INGEST_* status: those are 0 .. 8) */
+typedef struct freesasa_gpu_interface_table {
+    int32_t n_files;
+    int64_t n_pairs, n_res_rows;
+    int64_t *pair_offsets;     /* [n_files + 1] */
+    int32_t *pair_groups;      /* [2 * n_pairs] */
+    int32_t *pair_atoms;       /* [2 * n_pairs] */
+    char *pair_chain;          /* [8 * n_pairs] */
+    double *pair_areas;        /* [6 * n_pairs] */
+    double *pair_class_buried; /* [6 * n_pairs] */
+    int64_t *res_offsets;      /* [2 * n_pairs + 1] */
+    int32_t *res_index;        /* [n_res_rows] */
+    int32_t *res_atoms;        /* [n_res_rows] */
+    double *res_areas;         /* [3 * n_res_rows]: isolated, in the pair, buried */
+    char *res_name, *res_number, *res_chain; /* [4 | 6 | 4 per row] */
+} freesasa_gpu_interface_table;
+int freesasa_gpu_sweep_files_interfaces(const char *const *paths, int n_paths, int ingest_options, int n_threads,
+                                        int alg, double probe_radius, int resolution, long long batch_atoms,
+                                        double *totals_out, double *class_sums_out, long long *atoms_out, int *status_out,
+                                        const int *devices, int n_devices, const struct freesasa_ingest_classifier *classifier,
+                                        const char *spec, int group_flags, int *group_status_out,
+                                        freesasa_gpu_group_table *table_out, int residue_rows, double min_buried,
+                                        int *iface_status_out, freesasa_gpu_interface_table *itable_out, char *err, int err_len);
+void freesasa_gpu_interface_table_free(freesasa_gpu_interface_table *table);
 int freesasa_gpu_chain_group_ids(const struct freesasa_ingest_batch *batch, const char *spec, int flags, int32_t *group_out,
                                  int32_t *n_groups_out, int32_t *status_out, int device, char *err, int err_len);
 int freesasa_gpu_sweep_cache_devices(const char *cache_path, int alg, double probe_radius, int resolution, long long batch_atoms,
@@ -1091,8 +1152,9 @@ int freesasa_gpu_calc_groups_periodic_triclinic(const double *xyz, const double 
    Refused, with a message that names the structure and the number: more than 4096 groups in one structure (8.4e6 pairs to
      test), more than 2^27 pairs to test in a call, n_atoms + the groups' atoms + M > 2^30; a bad group id or n_groups as by
      freesasa_gpu_groups_dev, with its message.
-   Not offered: file sweeps and trajectory drivers, periodic images, pair batches cut into several engine runs, interfaces of
-     more than two groups.  (Per-residue tables: freesasa_gpu_interface_residues_dev below.)
+   Not offered: trajectory drivers, periodic images, pair batches cut into several engine runs, interfaces of more than two
+     groups.  (Per-residue tables: freesasa_gpu_interface_residues_dev below; in the file sweep:
+     freesasa_gpu_sweep_files_interfaces above.)
 
    freesasa_gpu_interface_pairs_dev: the screen alone - the chain-group pipeline, then boxes, candidates and contacts - one
      stream synchronization more than freesasa_gpu_groups_dev (the flags come back to the host).  d_sasa, d_iso, d_totals,
@@ -1168,7 +1230,8 @@ int freesasa_gpu_calc_interfaces(const double *xyz, const double *radii, const i
      a structure boundary (the message names residue and structures); min_buried negative, NaN or infinite; res_capacity < 0.
    One stream synchronization more than freesasa_gpu_interfaces_dev (R comes back to the host before delivery).
    Not offered: class splits (polar / apolar / main chain) of the buried area per residue, relative buried areas, interfaces
-     in the file sweep and the trajectory drivers, interfaces among periodic images, a per-atom contact criterion by distance.
+     in the trajectory drivers, interfaces among periodic images, a per-atom contact criterion by distance.  (In the file sweep,
+     with the buried area of every side split by class: freesasa_gpu_sweep_files_interfaces above.)
 
    freesasa_gpu_interface_residues_dev: d_res_areas is required, d_res_offsets, d_res_index, d_res_atoms may be NULL; the rest
      as freesasa_gpu_interfaces_dev.

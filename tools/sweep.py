@@ -4,7 +4,9 @@ per-structure totals (BASELINE configs[3] in miniature; SURVEY §8f N1 + the bat
 
     python tools/sweep.py [--replicate N] [--threads T] [--batch-atoms A] [--devices 0,1,...] [--done FILE] [--cache FILE]
                           [--residues OUT.tsv] [--select CMD ... --select-out OUT.tsv]
-                          [--chain-groups SPEC | --separate-chains, --groups-out OUT.tsv] [paths ...]
+                          [--chain-groups SPEC | --separate-chains, --groups-out OUT.tsv]
+                          [--chain-groups SPEC | --separate-chains, --interfaces-out OUT.tsv [--interface-residues RES.tsv] [--min-buried X]]
+                          [paths ...]
 
 Without paths it sweeps the PDB fixtures under tests/golden/pdb, replicated N times.  Loading of
 batch k+1 runs on host threads while the GPU computes batch k.  Prints one JSON line with the
@@ -17,7 +19,12 @@ five absolute areas (total, main chain, side chain, polar, apolar) and the five 
 --select CMD (repeatable, up to 64) with --select-out OUT.tsv: the reference's --select for all files
 (freesasa_gpu_sweep_files_select): file, then one area column per selection name;
 --chain-groups SPEC ("AB+C") or --separate-chains with --groups-out OUT.tsv: the reference's chain groups for all files
-(freesasa_gpu_sweep_files_groups): file, group index, label, atoms, isolated, complex and buried area per line."""
+(freesasa_gpu_sweep_files_groups): file, group index, label, atoms, isolated, complex and buried area per line;
+--interfaces-out OUT.tsv (with --chain-groups or --separate-chains; --groups-out may ride along): the interfaces between the
+groups of all files (freesasa_gpu_sweep_files_interfaces): the lines of tools/interfaces.py -o for the same files, column for
+column (a group's label is the group table's: with a spec, the first chain it names for the group), then per side the buried
+area split as apolar, polar, unknown; --interface-residues RES.tsv: the lines of tools/interfaces.py --residues, a row per
+residue of a side that loses more than --min-buried (default 0) A^2."""
 import argparse
 import glob
 import json
@@ -63,6 +70,28 @@ def write_groups(path, paths, table):
                 fh.write("\t".join([p, str(g - s.start), chain[g], str(int(table.group_atoms[g]))] + [f"{v:.2f}" for v in table.areas[g]]) + "\n")
 
 
+def write_interfaces(path, res_path, paths, gtable, table):
+    """tools/interfaces.py's lines from the sweep's tables: per pair the file, the two groups' labels and atoms and the six areas,
+    then buried apolar / polar / unknown of side a and of side b; per residue row that tool's --residues line"""
+    import interfaces as fmt
+    files = [os.path.basename(p) for p in paths]
+    chain = [c.strip() or "_" for c in gtable.chain]
+    labels = [chain[gtable.file(k)] for k in range(len(paths))]
+    atoms = [gtable.group_atoms[gtable.file(k)] for k in range(len(paths))]
+    pair_struct = np.repeat(np.arange(len(paths)), np.diff(table.pair_offsets))
+    with open(path, "w") as fh:
+        fh.write(fmt.HEADER + "\tburied_apolar_a\tburied_polar_a\tburied_unknown_a\tburied_apolar_b\tburied_polar_b\tburied_unknown_b\n")
+        for line, cls in zip(fmt.format_rows(files, labels, atoms, pair_struct, table.pair_groups, table.pair_areas), table.pair_class_buried):
+            fh.write(line + "\t" + "\t".join("%.3f" % float(v) for v in cls.reshape(-1)) + "\n")
+    if res_path:
+        rows = np.arange(table.n_res_rows)      # (the rows carry their own labels: the formatter's residue r is row r)
+        with open(res_path, "w") as fh:
+            fh.write(fmt.RESIDUE_HEADER + "\n")
+            for line in fmt.format_residue_rows(files, labels, pair_struct, table.pair_groups, table.res_offsets, rows, table.res_atoms, table.res_areas,
+                                                table.res_chain, table.res_name, table.res_number):
+                fh.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("paths", nargs="*")
@@ -81,6 +110,9 @@ def main():
     ap.add_argument("--chain-groups", default=None, metavar="SPEC", help='the reference\'s --chain-groups for every file ("AB+C": chains A and B as one group, C as another)')
     ap.add_argument("--separate-chains", action="store_true", help="the reference's --separate-chains for every file: one group per chain")
     ap.add_argument("--groups-out", default=None, metavar="OUT.tsv", help="write the groups' areas of all files (not with --select, --residues, --done, --cache or --no-gpu)")
+    ap.add_argument("--interfaces-out", default=None, metavar="OUT.tsv", help="write the interfaces between the groups of all files (with --chain-groups or --separate-chains)")
+    ap.add_argument("--interface-residues", default=None, metavar="RES.tsv", help="... and their per-residue rows (with --interfaces-out)")
+    ap.add_argument("--min-buried", type=float, default=0.0, help="a residue row for a buried area above this (A^2)")
     ap.add_argument("--engine", choices=["python", "c"], default="c",
                     help="c: freesasa_gpu_sweep_files (loader thread || GPU inside the library); "
                          "python: the same pipeline written with the two-step Python API")
@@ -94,8 +126,10 @@ def main():
     want_groups = args.chain_groups is not None or args.separate_chains
     if args.chain_groups is not None and args.separate_chains:
         ap.error("--chain-groups and --separate-chains can't be combined")
-    if want_groups != bool(args.groups_out):
-        ap.error("--chain-groups / --separate-chains and --groups-out go together")
+    if want_groups != bool(args.groups_out or args.interfaces_out):
+        ap.error("--chain-groups / --separate-chains and --groups-out / --interfaces-out go together")
+    if args.interface_residues and not args.interfaces_out:
+        ap.error("--interface-residues needs --interfaces-out")
     if want_groups and (args.select or args.done or args.cache or args.no_gpu or args.residues or args.engine != "c"):
         ap.error("chain groups go with the C engine's plain file sweep only (no --select, --residues, --done, --cache, --no-gpu, --engine python)")
     import freesasa_amd as fa
@@ -155,6 +189,18 @@ def main():
             write_selections(args.select_out, paths, selection.names, areas)
             out["selections"] = len(selection)
             out["selected_atoms"] = int(counts.sum())
+        elif args.interfaces_out:
+            sys.path.insert(0, os.path.join(ROOT, "tools"))
+            totals, _, atoms, status, gstatus, istatus, gtable, itable = fa.sweep_files_interfaces(
+                paths, args.chain_groups, separate_chains=args.separate_chains, alg=fa.LEE_RICHARDS, resolution=args.slices, n_threads=args.threads,
+                batch_atoms=args.batch_atoms, devices=devices, ingest_options=popt, residues=bool(args.interface_residues), min_buried=args.min_buried)
+            if args.groups_out:
+                write_groups(args.groups_out, paths, gtable)
+            write_interfaces(args.interfaces_out, args.interface_residues, paths, gtable, itable)
+            out["groups"] = int(gtable.n_groups)
+            out["interfaces"] = int(itable.n_pairs)
+            out["interface_residues"] = int(itable.n_res_rows)
+            out["files_without_interface_rows"] = int(((istatus != 0) & (status == 0)).sum())
         elif want_groups:
             totals, _, atoms, status, gstatus, gtable = fa.sweep_files_groups(paths, args.chain_groups, separate_chains=args.separate_chains, alg=fa.LEE_RICHARDS,
                                                                               resolution=args.slices, n_threads=args.threads, batch_atoms=args.batch_atoms,
