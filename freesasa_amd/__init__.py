@@ -197,6 +197,9 @@ def lib():
         L.freesasa_gpu_lr_neighbors_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _lp, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int]
         L.freesasa_gpu_arc_union_dev.argtypes = [C.c_void_p, _dp, _ip, C.c_int, _dp]
         L.freesasa_gpu_xtc_decode_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.freesasa_gpu_cell_sort_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _lp, C.c_int, C.c_double, C.c_int, C.c_longlong, C.c_longlong, C.c_int] + [C.c_void_p] * 9
+        L.freesasa_gpu_cell_sort_cap.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_longlong]
+        L.freesasa_gpu_cell_sort_cap.restype = C.c_longlong
         L.freesasa_gpu_xtc_decode_check.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
         L.freesasa_gpu_release_pool.argtypes = []
         L.freesasa_gpu_release_pool.restype = None
@@ -1952,6 +1955,12 @@ def test_points(n_points):
     return tp.reshape(n_points, 3)
 
 
+# the records of the test hook GpuContext.cell_sort (include/freesasa_gpu.h, freesasa_gpu_cell_sort_dev)
+CELL_SORT_STATUS_WORDS = 142
+CELL_SORT_GRID = np.dtype([("x0", "<f8"), ("y0", "<f8"), ("z0", "<f8"), ("d", "<f8"), ("nx", "<i4"), ("ny", "<i4"), ("nz", "<i4"), ("cell_base", "<i4")])
+CELL_SORT_IDX = np.dtype([("cell", "<i8"), ("orig", "<i4"), ("strct", "<i4")])
+
+
 class GpuContext:
     """Device-resident batches: pointers are raw device addresses (e.g. tensor.data_ptr())."""
 
@@ -2038,6 +2047,40 @@ class GpuContext:
             raise ValueError("freesasa_gpu_xtc_decode_dev: " + self.error())
         rec = rec.reshape(n_frames, n_atoms, 4)
         return [rec[f, :max(int(count[f, 0]), 0)] for f in range(n_frames)], count[:, 1].copy(), out.reshape(n_frames, n_atoms, 3)
+
+    def cell_sort(self, d_xyz, d_radii, offsets, probe=1.4, arrangement=0, cells_cap=0, shared_radii=False):
+        """Test hook: ONE pass of the cell sort on its own (freesasa_gpu_cell_sort_dev), forced into `arrangement` - 0 the general
+        pipeline, 1 k_sort_struct with the dense table, 2 k_sort_struct with the compact table - with a table of cells_cap cells
+        (0: the engine's sizing of a first batch).  Nothing is redone and the context learns nothing.  Returns a dict: status
+        (int32 [CELL_SORT_STATUS_WORDS]), error, retry, occ_sum, occ_n, cells (the named status words), occ_stride, cells_cap
+        (the capacity used), grid (records x0, y0, z0, d, nx, ny, nz, cell_base), ncells, sq [n, 4], s_idx (records cell, orig,
+        strct), and cell_start [cells_cap + 2] or cell_tbl [(cells_cap >> 5) + 2] with cell_first [n + n_structs + 2]; what no
+        kernel wrote is all-ones bytes.  ValueError for arguments that are refused."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        ns = offsets.size - 1
+        n = int(offsets[-1]) if ns >= 1 else 0
+        cap = lib().freesasa_gpu_cell_sort_cap(self._h, n, ns, int(cells_cap))
+        dense = arrangement != 2
+        status = np.full(CELL_SORT_STATUS_WORDS, -1, dtype=np.int32)
+        stride = np.full(1, -1, dtype=np.int32)
+        nn, nss, capn = max(n, 0), max(ns, 0), max(cap, 0)
+        grid = np.full(nss, -1, dtype=np.int64).repeat(6).view(CELL_SORT_GRID)
+        ncells = np.full(nss, -1, dtype=np.int64)
+        sq = np.full(4 * nn, -1, dtype=np.int64).view(np.float64)
+        s_idx = np.full(2 * nn, -1, dtype=np.int64).view(CELL_SORT_IDX)
+        cell_start = np.full(capn + 2, -1, dtype=np.int32) if dense else None
+        cell_tbl = None if dense else np.full((capn >> 5) + 2, -1, dtype=np.int64).view(np.uint64)
+        cell_first = None if dense else np.full(nn + nss + 2, -1, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        if lib().freesasa_gpu_cell_sort_dev(self._h, d_xyz, d_radii, offsets.ctypes.data_as(_lp), ns, probe, int(arrangement), int(cells_cap),
+                                            int(cap), 1 if shared_radii else 0, ptr(status), ptr(stride), ptr(grid), ptr(ncells), ptr(sq), ptr(s_idx),
+                                            ptr(cell_start), ptr(cell_tbl), ptr(cell_first)):
+            raise ValueError("freesasa_gpu_cell_sort_dev: " + self.error())
+        out = {"status": status, "error": int(status[0]), "occ_sum": int(status[4]), "occ_n": int(status[5]), "retry": int(status[7]),
+               "cells": int(status[140:142].view(np.int64)[0]), "occ_stride": int(stride[0]), "cells_cap": int(cap), "grid": grid,
+               "ncells": ncells, "sq": sq.reshape(-1, 4), "s_idx": s_idx}
+        out.update({"cell_start": cell_start} if dense else {"cell_tbl": cell_tbl, "cell_first": cell_first})
+        return out
 
     def segment_sums(self, d_sasa, seg_offsets, d_out):
         seg = np.ascontiguousarray(seg_offsets, dtype=np.int64)

@@ -320,6 +320,21 @@ int ensure(freesasa_gpu_ctx *c, DevBuf &b, size_t bytes);
 int run_batch(freesasa_gpu_ctx *c, bool lr, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
               double probe, int resolution, const double *unit_points, double *d_sasa, int *d_counts, double *d_totals);
 
+/* The cell sort of one batch, the first stage of run_batch_once and the whole of the test hook freesasa_gpu_cell_sort_dev
+   (gpu_ops.hip): the workspace sized, offsets and chunk table uploaded when they changed, the status words cleared, `pa` filled,
+   the cell table sized for cells_cap cells, and the launches enqueued on the context's stream - k_sort_struct (fused; with the
+   compact table or the dense one) or the general pipeline (not fused: the dense table).  Nothing is waited for and nothing the
+   context has learnt is touched, but for the launch-shape history: history 0 (Lee-Richards) / 1 (Shrake-Rupley) with the
+   batch's resolution is run_batch_once's - another probe radius than the history's starts it over, and a batch with history
+   takes no density samples (PipeArgs::occ_stride 0); history -1 (the hook) neither reads nor resets it and samples every
+   (n / 256)-th atom.  prefill: all-ones bytes in grid, ncells, sq, s_idx and the table before the first launch (the hook).
+   The caller has checked the arguments (n = offsets[n_structs] > 0). */
+int cell_sort_enqueue(freesasa_gpu_ctx *c, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs, int n,
+                      double probe, int history, int resolution, bool fused, bool compact, long long cells_cap, bool prefill, sasa::PipeArgs &pa);
+/* the cells a batch's table is sized for before its total is known: 10 per atom and 256 per structure, raised to what the
+   context has seen (cells_hint), capped at max_cells */
+long long batch_cells_cap(const freesasa_gpu_ctx *c, int n, int n_structs);
+
 /* Per-residue areas (freesasa_gpu_residue_areas_dev's kernel) on arrays that are ALL on the device already - residue
    offsets [n_res + 1], reference rows [n_res] (NULL: no relative areas wanted, d_rel ignored), backbone flags, classes -
    enqueued on the context's stream, no synchronisation; the reference-area table goes up with the context's first call.

@@ -403,24 +403,20 @@ static int run_lr2(freesasa_gpu_ctx *c, const PipeArgs &pa, int n, int n_structs
 
 /* ------------------------------------------------------------------ one batch */
 
-static int run_batch_once(freesasa_gpu_ctx *c, bool lr, const double *d_xyz, const double *d_radii,
-                     const int64_t *offsets, int n_structs, double probe, int resolution,
-                     const double *unit_points, double *d_sasa, int *d_counts, double *d_totals, bool defer = false, bool *deferred = nullptr)
+/* (engine_internal.h) the cell table of a batch is sized WITHOUT waiting for K2's total: see run_batch_once */
+long long batch_cells_cap(const freesasa_gpu_ctx *c, int n, int n_structs)
 {
-    c->err[0] = 0;
-    if (deferred) *deferred = false;
-    if (!d_xyz || !d_radii || !offsets || !d_sasa) return ctx_fail(c, "null argument");
-    if (n_structs <= 0) return ctx_fail(c, "n_structs must be > 0");
-    if (resolution <= 0) return ctx_fail(c, "resolution must be > 0");
-    if (offsets[0] != 0) return ctx_fail(c, "offsets[0] must be 0");
-    for (int s = 0; s < n_structs; ++s)
-        if (offsets[s + 1] < offsets[s]) return ctx_fail(c, "offsets must be non-decreasing");
-    const int64_t n64 = offsets[n_structs];
-    if (n64 <= 0) return ctx_fail(c, "empty batch");
-    if (n64 > (int64_t)1 << 30) return ctx_fail(c, "batch too large (max 2^30 atoms per call)");
-    const int n = (int)n64;
+    long long cells_cap = 10LL * n + 256LL * n_structs; /* (0.4 GB for 1e7 atoms; a sparser batch is redone once with K2's size) */
+    if (cells_cap < c->cells_hint) cells_cap = c->cells_hint;
+    if (cells_cap > c->max_cells) cells_cap = c->max_cells;
+    return cells_cap;
+}
 
-    HIP_TRY(c, hipSetDevice(c->device));
+/* The cell sort of one batch, enqueued on the context's stream (engine_internal.h): workspace, offsets and chunk table, the
+ * status clear, the kernels' arguments, the cell table, and the launches of the arrangement the caller names. */
+int cell_sort_enqueue(freesasa_gpu_ctx *c, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs, int n,
+                      double probe, int history, int resolution, bool fused, bool compact, long long cells_cap, bool prefill, PipeArgs &pa)
+{
     hipStream_t st = c->stream;
     const size_t nb = (size_t)n;
 
@@ -465,7 +461,6 @@ static int run_batch_once(freesasa_gpu_ctx *c, bool lr, const double *d_xyz, con
     HIP_TRY(c, hipMemsetAsync(c->status.p, 0, (sizeof(int) * ST_WORDS + 63) & ~(size_t)63, st));
     if (c->timing) HIP_TRY(c, hipEventRecord(ctx_ev(c)[0], st));
 
-    PipeArgs pa;
     memset(&pa, 0, sizeof pa);
     pa.xyz = d_xyz; pa.radii = d_radii; pa.offsets = (const int64_t *)c->offsets.p;
     pa.n_structs = n_structs; pa.n_atoms = n; pa.probe = probe; pa.max_cells = c->max_cells;
@@ -479,34 +474,14 @@ static int run_batch_once(freesasa_gpu_ctx *c, bool lr, const double *d_xyz, con
     pa.status = (int *)c->status.p;
     pa.cells_total = (long long *)((int *)c->status.p + ST_CELLS);
     pa.cells_total_at = pa.cells_total - pa.ncells; /* (both 8-byte aligned device addresses) */
-    if (probe != c->hint_probe) { /* launch-shape history is per (resolution, probe radius) */
+    if (history >= 0 && probe != c->hint_probe) { /* launch-shape history is per (resolution, probe radius) */
         c->hint_res[0] = c->hint_res[1] = 0;
         c->hint_pool2 = 0;
         c->hint_probe = probe;
     }
-    pa.occ_stride = c->hint_res[lr ? 0 : 1] == resolution ? 0 : (n / 256 > 0 ? n / 256 : 1);
+    pa.occ_stride = history >= 0 && c->hint_res[history] == resolution ? 0 : (n / 256 > 0 ? n / 256 : 1);
 
-    /* The cell table is sized WITHOUT waiting for K2's total: for what the context has seen so far, and for a
-       first batch 10 cells per atom (sparse random coils need 9, proteins 1-2) plus 256 per structure.  K2 checks
-       the real total against it on the device (ST_RETRY, see PIPE_GATE); the total itself reaches the host with
-       the status words at the end of the batch. */
-    int *status_h = ctx_status_h(c);
-    long long cells_cap = 10LL * n + 256LL * n_structs; /* (0.4 GB for 1e7 atoms; a sparser batch is redone once with K2's size) */
-    if (cells_cap < c->cells_hint) cells_cap = c->cells_hint;
-    if (cells_cap > c->max_cells) cells_cap = c->max_cells;
     const int nblk_scan = (int)((cells_cap + 1 + (long long)SASA_PIPE_B * SASA_SCAN_ITEMS - 1) / ((long long)SASA_PIPE_B * SASA_SCAN_ITEMS));
-    /* batches of small structures: bounds, grid and cell sort of a structure in one workgroup (k_sort_struct) */
-    long long biggest = 0;
-    for (int s_ = 0; s_ < n_structs; ++s_) biggest = offsets[s_ + 1] - offsets[s_] > biggest ? offsets[s_ + 1] - offsets[s_] : biggest;
-    /* (... and a call with a few SMALL structures - freesasa_calc_coord on one protein - where one launch instead of nine
-       is worth more than the general pipeline's parallelism: round 5, MI355X, median of freesasa_calc_coord on 1UBQ / 1A0Q /
-       a 4000-atom coil, L&R 142 -> 134 / 174 -> 165 / 185 -> 177 us, S&R 131 -> 116 / 124 -> 115 / 140 -> 130 us; from
-       8000 atoms on the general pipeline wins; FREESASA_AMD_SMALL_FUSED=n moves the limit) */
-    static const long long small_fused = getenv("FREESASA_AMD_SMALL_FUSED") ? atoll(getenv("FREESASA_AMD_SMALL_FUSED")) : 4096;
-    const bool fused = c->sort_fused && biggest <= SORT_ATOMS && (n_structs >= 8 || biggest <= small_fused) && !getenv("FREESASA_AMD_NO_FUSED_SORT");
-    /* ... which writes the cell table in its compact form for the Lee-Richards tile kernel (PipeArgs::cell_tbl) */
-    /* (... and, since round 5, for the Shrake-Rupley kernel too: tile_phase_load looks cells up through cell_first_atom) */
-    const bool compact = fused && (!lr || (lr2_supported(resolution) && !getenv("FREESASA_AMD_LR1"))) && !getenv("FREESASA_AMD_DENSE_CELLS");
     if (compact) {
         if (ensure(c, c->cell_tbl, sizeof(unsigned long long) * ((size_t)(cells_cap >> 5) + 2)) || ensure(c, c->cell_first, sizeof(int) * (nb + (size_t)n_structs + 2)))
             return -1;
@@ -532,11 +507,66 @@ static int run_batch_once(freesasa_gpu_ctx *c, bool lr, const double *d_xyz, con
     pa.zero_n = cells_cap + 2;
     pa.cells_cap = cells_cap;
 
+    if (prefill) { /* (the test hook: what no kernel of the sort writes stays all-ones bytes) */
+        HIP_TRY(c, hipMemsetAsync(c->grid.p, 0xff, sizeof(GridS) * (size_t)n_structs, st));
+        HIP_TRY(c, hipMemsetAsync(c->ncells.p, 0xff, sizeof(long long) * (size_t)n_structs, st));
+        HIP_TRY(c, hipMemsetAsync(c->sq.p, 0xff, 32 * nb, st));
+        HIP_TRY(c, hipMemsetAsync(c->s_idx.p, 0xff, 16 * nb, st));
+        if (compact) {
+            HIP_TRY(c, hipMemsetAsync(c->cell_tbl.p, 0xff, sizeof(unsigned long long) * ((size_t)(cells_cap >> 5) + 2), st));
+            HIP_TRY(c, hipMemsetAsync(c->cell_first.p, 0xff, sizeof(int) * (nb + (size_t)n_structs + 2), st));
+        } else {
+            HIP_TRY(c, hipMemsetAsync(c->cell_start.p, 0xff, sizeof(int) * ((size_t)cells_cap + 2), st));
+        }
+    }
     if (fused) {
         HIP_TRY(c, kl_prep_fused(pa, st));
     } else {
         HIP_TRY(c, kl_prep_general(pa, cells_cap, st));
     }
+    return 0;
+}
+
+static int run_batch_once(freesasa_gpu_ctx *c, bool lr, const double *d_xyz, const double *d_radii,
+                     const int64_t *offsets, int n_structs, double probe, int resolution,
+                     const double *unit_points, double *d_sasa, int *d_counts, double *d_totals, bool defer = false, bool *deferred = nullptr)
+{
+    c->err[0] = 0;
+    if (deferred) *deferred = false;
+    if (!d_xyz || !d_radii || !offsets || !d_sasa) return ctx_fail(c, "null argument");
+    if (n_structs <= 0) return ctx_fail(c, "n_structs must be > 0");
+    if (resolution <= 0) return ctx_fail(c, "resolution must be > 0");
+    if (offsets[0] != 0) return ctx_fail(c, "offsets[0] must be 0");
+    for (int s = 0; s < n_structs; ++s)
+        if (offsets[s + 1] < offsets[s]) return ctx_fail(c, "offsets must be non-decreasing");
+    const int64_t n64 = offsets[n_structs];
+    if (n64 <= 0) return ctx_fail(c, "empty batch");
+    if (n64 > (int64_t)1 << 30) return ctx_fail(c, "batch too large (max 2^30 atoms per call)");
+    const int n = (int)n64;
+
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+
+    /* The cell table is sized WITHOUT waiting for K2's total: for what the context has seen so far, and for a
+       first batch 10 cells per atom (sparse random coils need 9, proteins 1-2) plus 256 per structure.  K2 checks
+       the real total against it on the device (ST_RETRY, see PIPE_GATE); the total itself reaches the host with
+       the status words at the end of the batch. */
+    int *status_h = ctx_status_h(c);
+    const long long cells_cap = batch_cells_cap(c, n, n_structs);
+    /* batches of small structures: bounds, grid and cell sort of a structure in one workgroup (k_sort_struct) */
+    long long biggest = 0;
+    for (int s_ = 0; s_ < n_structs; ++s_) biggest = offsets[s_ + 1] - offsets[s_] > biggest ? offsets[s_ + 1] - offsets[s_] : biggest;
+    /* (... and a call with a few SMALL structures - freesasa_calc_coord on one protein - where one launch instead of nine
+       is worth more than the general pipeline's parallelism: round 5, MI355X, median of freesasa_calc_coord on 1UBQ / 1A0Q /
+       a 4000-atom coil, L&R 142 -> 134 / 174 -> 165 / 185 -> 177 us, S&R 131 -> 116 / 124 -> 115 / 140 -> 130 us; from
+       8000 atoms on the general pipeline wins; FREESASA_AMD_SMALL_FUSED=n moves the limit) */
+    static const long long small_fused = getenv("FREESASA_AMD_SMALL_FUSED") ? atoll(getenv("FREESASA_AMD_SMALL_FUSED")) : 4096;
+    const bool fused = c->sort_fused && biggest <= SORT_ATOMS && (n_structs >= 8 || biggest <= small_fused) && !getenv("FREESASA_AMD_NO_FUSED_SORT");
+    /* ... which writes the cell table in its compact form for the Lee-Richards tile kernel (PipeArgs::cell_tbl) */
+    /* (... and, since round 5, for the Shrake-Rupley kernel too: tile_phase_load looks cells up through cell_first_atom) */
+    const bool compact = fused && (!lr || (lr2_supported(resolution) && !getenv("FREESASA_AMD_LR1"))) && !getenv("FREESASA_AMD_DENSE_CELLS");
+    PipeArgs pa;
+    if (cell_sort_enqueue(c, d_xyz, d_radii, offsets, n_structs, n, probe, lr ? 0 : 1, resolution, fused, compact, cells_cap, false, pa)) return -1;
     if (c->timing) HIP_TRY(c, hipEventRecord(ctx_ev(c)[1], st));
 
     /* Lee & Richards at ordinary resolutions: the second-generation kernel (lr2_kernels.h) */

@@ -248,3 +248,78 @@ extern "C" int freesasa_gpu_arc_union_dev(freesasa_gpu_ctx *c, const double *arc
     });
 }
 
+/* ------------------------------------------------------------------ test hook: the cell sort on its own (include/freesasa_gpu.h) */
+
+static_assert(FREESASA_GPU_CELL_SORT_STATUS_WORDS == sasa::ST_WORDS, "the hook hands out every status word");
+static_assert(sizeof(sasa::GridS) == 48 && sizeof(sasa::SortIdx) == 16 && sizeof(sasa::Quad) == 32, "the records the hook's header describes");
+
+extern "C" long long freesasa_gpu_cell_sort_cap(freesasa_gpu_ctx *c, long long n_atoms, int n_structs, long long cells_cap)
+{
+    if (!c || n_atoms < 1 || n_atoms > 1LL << 30 || n_structs < 1 || cells_cap < 0) return -1;
+    if (cells_cap > 0) return cells_cap;
+    /* (a batch in flight raises what the context has seen when it is collected: collected here, as the hook collects it, the
+       two name the same number) */
+    if (freesasa_gpu_wait(c)) return -1;
+    return batch_cells_cap(c, (int)n_atoms, n_structs);
+}
+
+/* One pass of the cell sort in the arrangement the caller names, by the engine's own launches (cell_sort_enqueue), and
+ * everything it wrote down to the caller's arrays.  Whatever the status words say, nothing is redone and the context learns
+ * nothing: judge_status (gpu_engine.hip) is not asked. */
+extern "C" int freesasa_gpu_cell_sort_dev(freesasa_gpu_ctx *c, const double *d_xyz, const double *d_radii, const int64_t *offsets,
+                                          int n_structs, double probe, int arrangement, long long cells_cap, long long table_cells,
+                                          int shared_radii, int32_t *status, int32_t *occ_stride, void *grid, int64_t *ncells, double *sq, void *s_idx,
+                                          int32_t *cell_start, uint64_t *cell_tbl, int32_t *cell_first)
+{
+    if (!c) return -1;
+    return guarded_ctx(c, [&]() -> int {
+    c->err[0] = 0;
+    if (!d_xyz || !d_radii || !offsets || !status || !occ_stride || !grid || !ncells || !sq || !s_idx) return ctx_fail(c, "null argument");
+    if (n_structs <= 0) return ctx_fail(c, "n_structs must be > 0");
+    if (offsets[0] != 0) return ctx_fail(c, "offsets[0] must be 0");
+    for (int s = 0; s < n_structs; ++s)
+        if (offsets[s + 1] < offsets[s]) return ctx_fail(c, "offsets must be non-decreasing");
+    const int64_t n64 = offsets[n_structs];
+    if (n64 <= 0) return ctx_fail(c, "empty batch");
+    if (n64 > (int64_t)1 << 30) return ctx_fail(c, "batch too large (max 2^30 atoms per call)");
+    if (arrangement < 0 || arrangement > 2) return ctx_fail(c, "unknown arrangement %d (0: general pipeline, 1: k_sort_struct with the dense table, 2: with the compact table)", arrangement);
+    if (arrangement == 2 ? !cell_tbl || !cell_first : !cell_start) return ctx_fail(c, "null argument");
+    if (cells_cap < 0) return ctx_fail(c, "cells_cap must not be negative");
+    if (cells_cap > c->max_cells) return ctx_fail(c, "cells_cap is beyond the %lld cells a context holds", c->max_cells);
+    if (shared_radii != 0 && shared_radii != 1) return ctx_fail(c, "shared_radii must be 0 or 1");
+    const int n = (int)n64;
+    if (freesasa_gpu_wait(c)) return -1; /* (batches submitted asynchronously come first, as for every synchronous entry) */
+    HIP_TRY(c, hipSetDevice(c->device));
+    struct Radii { /* (put back on every way out) */
+        freesasa_gpu_ctx *c;
+        bool was;
+        ~Radii() { c->shared_radii = was; }
+    } radii{c, c->shared_radii};
+    c->shared_radii = shared_radii != 0;
+    const long long cap = cells_cap > 0 ? cells_cap : batch_cells_cap(c, n, n_structs);
+    /* (everything below is copied into the caller's arrays by this number) */
+    if (table_cells != cap) return ctx_fail(c, "the table arrays are sized for %lld cells, the pass takes %lld (freesasa_gpu_cell_sort_cap)", table_cells, cap);
+    const size_t nb = (size_t)n, ns = (size_t)n_structs;
+    hipStream_t st = c->stream;
+    sasa::PipeArgs pa;
+    int rc = cell_sort_enqueue(c, d_xyz, d_radii, offsets, n_structs, n, probe, -1, 0, arrangement != 0, arrangement == 2, cap, true, pa);
+    if (!rc) {
+        bool ok = hipMemcpyAsync(status, pa.status, sizeof(int) * (size_t)sasa::ST_WORDS, hipMemcpyDeviceToHost, st) == hipSuccess &&
+                  hipMemcpyAsync(grid, pa.grid, sizeof(sasa::GridS) * ns, hipMemcpyDeviceToHost, st) == hipSuccess &&
+                  hipMemcpyAsync(ncells, pa.ncells, 8 * ns, hipMemcpyDeviceToHost, st) == hipSuccess &&
+                  hipMemcpyAsync(sq, pa.sq, 32 * nb, hipMemcpyDeviceToHost, st) == hipSuccess &&
+                  hipMemcpyAsync(s_idx, pa.s_idx, 16 * nb, hipMemcpyDeviceToHost, st) == hipSuccess;
+        if (ok && arrangement == 2)
+            ok = hipMemcpyAsync(cell_tbl, pa.cell_tbl, 8 * ((size_t)(cap >> 5) + 2), hipMemcpyDeviceToHost, st) == hipSuccess &&
+                 hipMemcpyAsync(cell_first, pa.cell_first, 4 * (nb + ns + 2), hipMemcpyDeviceToHost, st) == hipSuccess;
+        else if (ok)
+            ok = hipMemcpyAsync(cell_start, pa.cell_start, 4 * ((size_t)cap + 2), hipMemcpyDeviceToHost, st) == hipSuccess;
+        if (!ok) rc = ctx_fail(c, "could not read the cell sort's arrays back");
+    }
+    /* (nothing is left running on the stream, whatever failed) */
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = ctx_fail(c, "could not read the cell sort's arrays back");
+    if (rc) return -1;
+    *occ_stride = pa.occ_stride; /* (as a context without history: the density samples are part of what is checked) */
+    return 0;
+    });
+}

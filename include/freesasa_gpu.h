@@ -214,6 +214,42 @@ int freesasa_gpu_xtc_decode_dev(freesasa_gpu_ctx *ctx, const void *bytes, long l
                                 int32_t *count, float *out);
 int freesasa_gpu_xtc_decode_check(const void *bytes, long long len, int n_frames, int n_atoms, const int32_t *rec, const int32_t *count,
                                   const float *out, char *err, int err_len);
+/* Test hook: the cell sort - the first stage of every batch - run on the device on its own, by the engine's own launches.
+   d_xyz, d_radii (device), offsets (host), n_structs and probe_radius as freesasa_gpu_lr_batch_dev takes them.
+   arrangement: 0 the general pipeline (k_prep_general, k_count, k_scan, k_scatter) with the dense table, 1 k_sort_struct (one
+   workgroup per structure) with the dense table, 2 k_sort_struct with the compact table.  It is forced: what the engine would
+   choose for the batch (structure sizes, n_structs, the environment switches, what the context has learnt) is not consulted,
+   so the kernels' own refusals can be seen.  cells_cap: the cells the table has room for; 0: the engine's sizing of a first
+   batch (10 n + 256 n_structs, raised to what the context has seen) - freesasa_gpu_cell_sort_cap says which number that is (it
+   returns cells_cap itself when that is positive, -1 for arguments the hook refuses; it collects batches in flight first, as
+   the hook does, since collecting one raises what the context has seen): the table arrays below are sized with it, and the
+   caller says so in table_cells - a pass that would take another number of cells is refused ("the table arrays are sized for
+   ...") and copies nothing.  shared_radii (0 / 1): d_radii holds ONE structure's radii, used by every structure (the trajectory path's addressing).
+   ONE pass: whatever the status words say - an error, "redo with a larger table" (ST_RETRY bit 0), "not a batch for
+   k_sort_struct" (bit 1) - nothing is redone, and the context's learnt state (the choice of the sort, the table sizing, the
+   launch-shape hints) stays as it was; what a pass with ST_ERROR or ST_RETRY set leaves in the arrays is not a result.
+   Before the first launch grid, ncells, sq, s_idx and the table are filled with all-ones bytes: an entry no kernel wrote reads
+   as -1 (NaN in sq).  Host arrays out:
+     status [FREESASA_GPU_CELL_SORT_STATUS_WORDS] the batch's status words (sasa_kernels.h ST_*: ST_ERROR 0, ST_OCC_SUM 4,
+                 ST_OCC_N 5, ST_RETRY 7, the 64-bit cell total ST_CELLS at words 140-141);
+     occ_stride  every occ_stride-th atom is a density sample (n / 256, at least 1);
+     grid [n_structs] records of 48 bytes: x0, y0, z0, d (doubles), nx, ny, nz, cell_base (int32);
+     ncells [n_structs] int64;
+     sq [4 n] x, y, z, radius + probe of the atoms in cell-sorted order;
+     s_idx [n] records of 16 bytes: cell (int64: batch-wide cell | (border flags | cell_pack_grid) << 32), orig, strct (int32);
+     arrangements 0 and 1: cell_start [cells_cap + 2] (cell_tbl, cell_first may be NULL);
+     arrangement 2: cell_tbl [(cells_cap >> 5) + 2] and cell_first [n + n_structs + 2] (cell_start may be NULL).
+   Returns 0, or -1 with the context's error text; refused before any device call, with run_batch's wording where the condition is
+   the same: "null argument", "n_structs must be > 0", "offsets[0] must be 0", "offsets must be non-decreasing", "empty batch",
+   "unknown arrangement ...", "cells_cap must not be negative".  Batches in flight are collected first; device memory is the
+   context's workspace (freesasa_gpu_test_fail_after reaches it).  tests/test_cell_sort_gpu.py holds all three arrangements to
+   a numpy reference through it (tests/cell_sort_ref.py). */
+#define FREESASA_GPU_CELL_SORT_STATUS_WORDS 142
+int freesasa_gpu_cell_sort_dev(freesasa_gpu_ctx *ctx, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
+                               double probe_radius, int arrangement, long long cells_cap, long long table_cells, int shared_radii, int32_t *status,
+                               int32_t *occ_stride, void *grid, int64_t *ncells, double *sq, void *s_idx, int32_t *cell_start,
+                               uint64_t *cell_tbl, int32_t *cell_first);
+long long freesasa_gpu_cell_sort_cap(freesasa_gpu_ctx *ctx, long long n_atoms, int n_structs, long long cells_cap);
 /* cuts[0..n_parts]: first structure of every run for the partition above (host-only helper) */
 void freesasa_gpu_shard_cuts(const int64_t *offsets, int n_structs, int n_parts, int *cuts);
 

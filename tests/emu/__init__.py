@@ -56,3 +56,28 @@ def run_batch(lr, xyz, radii, offsets=None, probe=1.4, resolution=20, unit_pts=N
     if check and ret:
         raise RuntimeError(f"emulated batch failed: {st}")
     return sasa, counts, totals, st
+
+
+def cell_sort(xyz, radii, offsets, probe=1.4, cells_cap=0, shared_radii=False):
+    """The emulated general cell sort on its own (emu_cell_sort), in the shape of GpuContext.cell_sort's result for
+    arrangement 0; cells_cap 0: the engine's sizing of a first batch; what nobody wrote is all-ones bytes."""
+    import cell_sort_ref as ref
+    xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1)
+    radii = np.ascontiguousarray(radii, dtype=np.float64)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    ns, n = offsets.size - 1, int(offsets[-1])
+    cap = int(cells_cap) or 10 * n + 256 * ns
+    stride = n // 256 if n >= 256 else 1
+    status = np.full(ref.STATUS_WORDS, -1, dtype=np.int32)
+    grid = np.full(6 * ns, -1, dtype=np.int64).view(ref.GRID)
+    ncells = np.full(ns, -1, dtype=np.int64)
+    sq = np.full(4 * n, -1, dtype=np.int64).view(np.float64)
+    s_idx = np.full(2 * n, -1, dtype=np.int64).view(ref.IDX)
+    cell_start = np.full(cap + 2, -1, dtype=np.int32)
+    L = _load()
+    L.emu_cell_sort.argtypes = [_dp, _dp, _lp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 6
+    L.emu_cell_sort(xyz.ctypes.data_as(_dp), radii.ctypes.data_as(_dp), offsets.ctypes.data_as(_lp), ns, probe, 1 if shared_radii else 0,
+                    stride, cap, status.ctypes.data, grid.ctypes.data, ncells.ctypes.data, sq.ctypes.data, s_idx.ctypes.data, cell_start.ctypes.data)
+    return {"status": status, "error": int(status[ref.ST_ERROR]), "retry": int(status[ref.ST_RETRY]), "occ_sum": int(status[ref.ST_OCC_SUM]),
+            "occ_n": int(status[ref.ST_OCC_N]), "cells": int(status[ref.ST_CELLS:ref.ST_CELLS + 2].view(np.int64)[0]), "occ_stride": stride,
+            "cells_cap": cap, "grid": grid, "ncells": ncells, "sq": sq.reshape(-1, 4), "s_idx": s_idx, "cell_start": cell_start}

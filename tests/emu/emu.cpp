@@ -214,6 +214,128 @@ static void emu_lr2_kernel(const Lr2Cfg &cfg, Lr2Args a, int grid, bool main_lau
     }
 }
 
+/* The general cell sort as kl_prep_general launches it - bounds, grids, cell bases, count, the chained scan, scatter - over
+ * arrays of its own: the first stage of emu_run_batch, and the whole of emu_cell_sort. */
+struct EmuSort {
+    std::vector<GridS> grid;
+    std::vector<long long> ncells, cell_of;
+    std::vector<int> sid, rank, status, cs, cl, sc0, cell_start;
+    std::vector<int64_t> cb;
+    std::vector<SortIdx> s_idx;
+    std::vector<Quad> sq;
+    std::vector<double> bpart;
+    std::vector<unsigned long long> scan_desc;
+    PipeArgs pa;
+    long long total_cells = 0;
+    /* 0, or -1 with status[ST_ERROR] or - cells_cap > 0 and the batch's total beyond it: cellbase_phase1b - status[ST_RETRY] set:
+       nothing behind the cell bases ran, as behind the device's PIPE_GATE */
+    int run(const double *xyz, const double *radii, const int64_t *offsets, int n_structs, double probe, int shared_radii, int occ_stride,
+            long long cells_cap = 0)
+    {
+        const int PB = SASA_PIPE_B;
+        const int n = (int)offsets[n_structs];
+        grid.assign(n_structs, GridS()); ncells.assign(n_structs + 1, 0);
+        sid.assign(n, 0); rank.assign(n, 0); status.assign(ST_WORDS, 0);
+        cell_of.assign(n, 0); s_idx.assign(n, SortIdx()); sq.assign(n, Quad());
+
+        memset(&pa, 0, sizeof pa);
+        pa.xyz = xyz; pa.radii = radii; pa.offsets = offsets; pa.n_structs = n_structs; pa.n_atoms = n;
+        pa.probe = probe; pa.max_cells = 1LL << 28;
+        pa.shared_radii = shared_radii; pa.occ_stride = occ_stride; pa.cells_cap = cells_cap;
+        pa.grid = grid.data(); pa.ncells = ncells.data(); pa.sid = sid.data(); pa.cell_of = cell_of.data();
+        pa.rank = rank.data(); pa.sq = sq.data();
+        pa.s_idx = s_idx.data(); pa.status = status.data(); pa.cells_total = (long long *)(status.data() + ST_CELLS);
+
+        /* chunk table, as gpu_engine.hip builds it */
+        cs.clear(); cl.clear(); cb.clear(); sc0.assign(n_structs + 1, 0);
+        for (int s = 0; s < n_structs; ++s) {
+            sc0[s] = (int)cs.size();
+            for (int64_t b = offsets[s]; b < offsets[s + 1]; b += SASA_BOUNDS_CHUNK) {
+                const int64_t e = b + SASA_BOUNDS_CHUNK < offsets[s + 1] ? b + SASA_BOUNDS_CHUNK : offsets[s + 1];
+                cs.push_back(s); cb.push_back(b); cl.push_back((int)(e - b));
+            }
+        }
+        sc0[n_structs] = (int)cs.size();
+        bpart.assign(7 * cs.size() + 7, 0.0);
+        pa.n_chunks = (int)cs.size(); pa.chunk_struct = cs.data(); pa.chunk_begin = cb.data(); pa.chunk_len = cl.data();
+        pa.struct_chunk0 = sc0.data(); pa.bpart = bpart.data();
+        { /* k_bounds + k_grid */
+            std::vector<double> red(7 * PB), red2(7 * 16);
+            for (int ch = 0; ch < pa.n_chunks; ++ch) {
+                for (int t = 0; t < PB; ++t) bounds_phase0(pa, red.data(), ch, t, PB);
+                for (int t = 0; t < PB; ++t) bounds_phase1(red.data(), red2.data(), t, PB);
+                for (int t = 0; t < PB; ++t) bounds_phase2(pa, red2.data(), ch, t);
+            }
+            std::vector<double> gpart(7 * PB);
+            for (int s0 = 0; s0 < n_structs; s0 += PB / SASA_GRID_GROUP) {
+                for (int t = 0; t < PB; ++t) grid_phase0(pa, gpart.data(), s0, t);
+                for (int t = 0; t < PB; ++t) grid_phase1(pa, gpart.data(), s0, t);
+            }
+        }
+        { /* k_cell_base */
+            std::vector<long long> part(PB), part2(16);
+            for (int t = 0; t < PB; ++t) cellbase_phase0(pa, part.data(), t, PB);
+            for (int t = 0; t < PB; ++t) cellbase_phase1(part.data(), part2.data(), t, PB);
+            for (int t = 0; t < PB; ++t) cellbase_phase1b(pa, part2.data(), t);
+            for (int t = 0; t < PB; ++t) cellbase_phase2(pa, part.data(), part2.data(), t, PB);
+        }
+        total_cells = *cell_total(pa);
+        if (status[ST_ERROR] | status[ST_RETRY]) return -1;
+        const int nblk_scan = (int)((total_cells + 1 + (long long)PB * SASA_SCAN_ITEMS - 1) / ((long long)PB * SASA_SCAN_ITEMS));
+        cell_start.assign(total_cells + 2, 0);
+        scan_desc.assign(nblk_scan + 1, 0ULL); /* (fresh descriptors are cleared once: gpu_engine.hip) */
+        pa.cell_start = cell_start.data(); pa.scan_desc = scan_desc.data(); pa.scan_epoch = 1;
+
+        const int nblk_atoms = (n + PB - 1) / PB;
+        for (int b = 0; b < nblk_atoms; ++b)
+        {
+            std::vector<int> cells(PB), base(PB);
+            for (int t = 0; t < PB; ++t) count_phase0(pa, cells.data(), b * PB + t, t);
+            for (int t = 0; t < PB; ++t) count_phase1(pa, cells.data(), base.data(), t, PB);
+            for (int t = 0; t < PB; ++t) count_phase2(pa, cells.data(), base.data(), b * PB + t, t);
+        }
+        { /* k_scan: the chained scan, its workgroups one after the other (every look-back finds its predecessors done) */
+            std::vector<int> part(PB), part2(SASA_SCAN_GROUP);
+            std::vector<ScanRegs> regs(PB);
+            for (int w = 0; w < nblk_scan; ++w) {
+                const int b = scan_take_block(pa);
+                int before = 0;
+                for (int t = 0; t < PB; ++t) scan_phase0(pa, total_cells, part.data(), b, t, PB, regs[t]);
+                for (int t = 0; t < PB; ++t) scan_phase1(part.data(), part2.data(), t);
+                for (int t = 0; t < PB; ++t) scan_phase2(pa, part2.data(), &before, b, t);
+                for (int t = 0; t < PB; ++t) scan_phase3(pa, total_cells, part.data(), part2.data(), &before, b, t, PB, regs[t]);
+            }
+        }
+        for (int b = 0; b < nblk_atoms; ++b)
+            for (int t = 0; t < PB; ++t) scatter_atom(pa, b * PB + t);
+        return 0;
+    }
+};
+
+/* emu_cell_sort: what the test hook freesasa_gpu_cell_sort_dev hands out for arrangement 0 (include/freesasa_gpu.h), from the
+ * emulated general pipeline: status [ST_WORDS], grid [n_structs] (48-byte records), ncells [n_structs], sq [4 n], s_idx [n]
+ * (16-byte records), cell_start [total cells + 2] - the caller sizes it for cells_cap cells; the phase functions see that
+ * capacity (PipeArgs::cells_cap): a total beyond it raises ST_RETRY in cellbase_phase1b as on the device, and nothing behind
+ * the cell bases is written.  What is NOT emulated: the histogram and the scan are sized by the batch's total here, and the
+ * clearing of the table's whole capacity with its 16-byte words and tail is k_prep_general's own text (gpu_kernels.hip), no
+ * phase function - both are the device test's alone.  Returns the status' error code. */
+extern "C" int emu_cell_sort(const double *xyz, const double *radii, const int64_t *offsets, int n_structs, double probe, int shared_radii,
+                             int occ_stride, long long cells_cap, int *status, void *grid, long long *ncells, double *sq, void *s_idx,
+                             int *cell_start)
+{
+    const size_t n = (size_t)offsets[n_structs];
+    EmuSort S;
+    S.run(xyz, radii, offsets, n_structs, probe, shared_radii, occ_stride, cells_cap);
+    memcpy(status, S.status.data(), sizeof(int) * ST_WORDS);
+    if (S.status[ST_ERROR] || S.status[ST_RETRY]) return S.status[ST_ERROR];
+    memcpy(grid, S.grid.data(), sizeof(GridS) * (size_t)n_structs);
+    memcpy(ncells, S.ncells.data(), sizeof(long long) * (size_t)n_structs);
+    memcpy(sq, S.sq.data(), sizeof(Quad) * n);
+    memcpy(s_idx, S.s_idx.data(), sizeof(SortIdx) * n);
+    memcpy(cell_start, S.cell_start.data(), sizeof(int) * (size_t)(S.total_cells + 2));
+    return 0;
+}
+
 /* force_*: <= 0 keeps the production launch configuration; positive values shrink the
  * capacities so that small inputs exercise the overflow -> fallback path.
  * stats_out[10]: error, fallback tiles, max nn, TA, B, lds, total cells, items, slices that
@@ -225,86 +347,14 @@ extern "C" int emu_run_batch(int lr, const double *xyz, const double *radii, con
                              int fb_pool, int fb_ds, int mid_cap_idx, int mid_pool, int mid_ds)
 {
     const int n = (int)offsets[n_structs];
-    const int PB = SASA_PIPE_B;
-    std::vector<GridS> grid(n_structs);
-    std::vector<long long> ncells(n_structs + 1);
-    std::vector<int> sid(n), rank(n), status(ST_WORDS, 0);
-    std::vector<long long> cell_of(n);
-    std::vector<SortIdx> s_idx(n);
-    std::vector<Quad> sq(n);
-
-    PipeArgs pa;
-    memset(&pa, 0, sizeof pa);
-    pa.xyz = xyz; pa.radii = radii; pa.offsets = offsets; pa.n_structs = n_structs; pa.n_atoms = n;
-    pa.probe = probe; pa.max_cells = 1LL << 28;
-    pa.grid = grid.data(); pa.ncells = ncells.data(); pa.sid = sid.data(); pa.cell_of = cell_of.data();
-    pa.rank = rank.data(); pa.sq = sq.data();
-    pa.s_idx = s_idx.data(); pa.status = status.data(); pa.cells_total = (long long *)(status.data() + ST_CELLS);
-
-    /* chunk table, as gpu_engine.hip builds it */
-    std::vector<int> cs, cl, sc0(n_structs + 1);
-    std::vector<int64_t> cb;
-    for (int s = 0; s < n_structs; ++s) {
-        sc0[s] = (int)cs.size();
-        for (int64_t b = offsets[s]; b < offsets[s + 1]; b += SASA_BOUNDS_CHUNK) {
-            const int64_t e = b + SASA_BOUNDS_CHUNK < offsets[s + 1] ? b + SASA_BOUNDS_CHUNK : offsets[s + 1];
-            cs.push_back(s); cb.push_back(b); cl.push_back((int)(e - b));
-        }
-    }
-    sc0[n_structs] = (int)cs.size();
-    std::vector<double> bpart(7 * cs.size() + 7);
-    pa.n_chunks = (int)cs.size(); pa.chunk_struct = cs.data(); pa.chunk_begin = cb.data(); pa.chunk_len = cl.data();
-    pa.struct_chunk0 = sc0.data(); pa.bpart = bpart.data();
-    { /* k_bounds + k_grid */
-        std::vector<double> red(7 * PB), red2(7 * 16);
-        for (int ch = 0; ch < pa.n_chunks; ++ch) {
-            for (int t = 0; t < PB; ++t) bounds_phase0(pa, red.data(), ch, t, PB);
-            for (int t = 0; t < PB; ++t) bounds_phase1(red.data(), red2.data(), t, PB);
-            for (int t = 0; t < PB; ++t) bounds_phase2(pa, red2.data(), ch, t);
-        }
-        std::vector<double> gpart(7 * PB);
-        for (int s0 = 0; s0 < n_structs; s0 += PB / SASA_GRID_GROUP) {
-            for (int t = 0; t < PB; ++t) grid_phase0(pa, gpart.data(), s0, t);
-            for (int t = 0; t < PB; ++t) grid_phase1(pa, gpart.data(), s0, t);
-        }
-    }
-    { /* k_cell_base */
-        std::vector<long long> part(PB), part2(16);
-        for (int t = 0; t < PB; ++t) cellbase_phase0(pa, part.data(), t, PB);
-        for (int t = 0; t < PB; ++t) cellbase_phase1(part.data(), part2.data(), t, PB);
-        for (int t = 0; t < PB; ++t) cellbase_phase1b(pa, part2.data(), t);
-        for (int t = 0; t < PB; ++t) cellbase_phase2(pa, part.data(), part2.data(), t, PB);
-    }
+    EmuSort S;
+    const int sort_rc = S.run(xyz, radii, offsets, n_structs, probe, 0, 0);
+    PipeArgs &pa = S.pa;
+    std::vector<int> &status = S.status, &cell_start = S.cell_start;
+    std::vector<long long> &ncells = S.ncells;
+    const long long total_cells = S.total_cells;
     stats_out[0] = status[ST_ERROR];
-    if (status[ST_ERROR]) return -1;
-    const long long total_cells = *cell_total(pa);
-    const int nblk_scan = (int)((total_cells + 1 + (long long)PB * SASA_SCAN_ITEMS - 1) / ((long long)PB * SASA_SCAN_ITEMS));
-    std::vector<int> cell_start(total_cells + 2, 0);
-    std::vector<unsigned long long> scan_desc(nblk_scan + 1, 0ULL); /* (fresh descriptors are cleared once: gpu_engine.hip) */
-    pa.cell_start = cell_start.data(); pa.scan_desc = scan_desc.data(); pa.scan_epoch = 1;
-
-    const int nblk_atoms = (n + PB - 1) / PB;
-    for (int b = 0; b < nblk_atoms; ++b)
-    {
-        std::vector<int> cells(PB), base(PB);
-        for (int t = 0; t < PB; ++t) count_phase0(pa, cells.data(), b * PB + t, t);
-        for (int t = 0; t < PB; ++t) count_phase1(pa, cells.data(), base.data(), t, PB);
-        for (int t = 0; t < PB; ++t) count_phase2(pa, cells.data(), base.data(), b * PB + t, t);
-    }
-    { /* k_scan: the chained scan, its workgroups one after the other (every look-back finds its predecessors done) */
-        std::vector<int> part(PB), part2(SASA_SCAN_GROUP);
-        std::vector<ScanRegs> regs(PB);
-        for (int w = 0; w < nblk_scan; ++w) {
-            const int b = scan_take_block(pa);
-            int before = 0;
-            for (int t = 0; t < PB; ++t) scan_phase0(pa, total_cells, part.data(), b, t, PB, regs[t]);
-            for (int t = 0; t < PB; ++t) scan_phase1(part.data(), part2.data(), t);
-            for (int t = 0; t < PB; ++t) scan_phase2(pa, part2.data(), &before, b, t);
-            for (int t = 0; t < PB; ++t) scan_phase3(pa, total_cells, part.data(), part2.data(), &before, b, t, PB, regs[t]);
-        }
-    }
-    for (int b = 0; b < nblk_atoms; ++b)
-        for (int t = 0; t < PB; ++t) scatter_atom(pa, b * PB + t);
+    if (sort_rc) return -1;
 
     if (lr && emu_lr2 && lr2_supported(resolution)) {
         /* main and second launch: lr2_kernels.h; third launch: the slab-backed first-generation kernel
@@ -328,7 +378,8 @@ extern "C" int emu_run_batch(int lr, const double *xyz, const double *radii, con
         la.sasa = sasa; la.status = status.data();
         /* main launch: a tile that does not fit is split in place; halves that still do not fit go to the list */
         la.ovf_items = ovf2x.data(); la.ovf_count = status.data() + ST_OVF2_TILES; la.split_count = status.data() + ST_SPLIT;
-        /* the compact cell table, built from the dense one the way k_sort_struct's stage F leaves it (single structure) */
+        /* the compact cell table, built from the dense one the way k_sort_struct's stage F leaves it (single structure); a rebuild:
+           what the device kernel writes there is checked in tests/test_cell_sort_gpu.py */
         std::vector<unsigned long long> ctbl;
         std::vector<int> cfirst;
         if ((emu_lr2_opts & 2) && n_structs == 1) {

@@ -510,7 +510,9 @@ def test_shape_builds_and_the_compact_cell_table_give_the_generic_bits(oracle_li
     of the occupied cells: cell_rank, lr2_pre_b / b2), built the way k_sort_struct's stage F leaves it, including a cell
     count that is a multiple of 32 (the sentinel word).  Every variant must reproduce the generic build's areas bit for
     bit (the device-side twins: test_shape_builds_give_the_generic_builds_bits,
-    test_cell_sort_in_one_kernel_equals_the_general_pipeline in tests/test_gpu_parity.py)."""
+    test_cell_sort_in_one_kernel_equals_the_general_pipeline in tests/test_gpu_parity.py).  The table here is the emulation's
+    own rebuild of stage F, not the device's: what k_sort_struct itself writes is held to a reference, entry by entry, in
+    tests/test_cell_sort_gpu.py."""
     L = emu._load()
     g = load_golden("1ubq")
     coil = tools.coil(1500, 77)

@@ -471,10 +471,17 @@ def test_asynchronous_batches_match_the_synchronous_ones(fa, oracle_lib):
 def test_cell_sort_in_one_kernel_equals_the_general_pipeline(fa, oracle_lib, monkeypatch):
     """k_sort_struct (batches of structures up to 16 384 atoms: one workgroup sorts a structure in LDS) against the
     general pipeline (zero, count, scan, scatter) and the oracle: ordinary structures, an empty one, a single atom, and
-    a sparse diagonal whose grid has more cells (~8e5) than the kernel holds bits for at a time (several passes)."""
+    a sparse diagonal whose grid has more cells (~8e5) than the kernel holds bits for at a time (several passes), and the
+    atoms of two lattice structures of tests/cell_sort_ref.py (65x64x64 and 4x4x2 cells there) with radii that give them
+    neighbors.  k_sort_struct runs with the compact cell table and with the dense one (FREESASA_AMD_DENSE_CELLS).  The areas see
+    a wrong table entry only at the shapes that hit it: tests/test_cell_sort_gpu.py holds the stage's own outputs to a reference."""
+    import cell_sort_ref
     parts = [tools.coil(1500, 40 + k) for k in range(5)] + [tools.globule(1200, 3)]
     diag = np.linspace(0.0, 600.0, 240)[:, None] * np.ones((1, 3)) + np.random.default_rng(1).uniform(-0.3, 0.3, (240, 3))
     parts += [(diag, np.full(240, 1.8)), (np.zeros((0, 3)), np.zeros(0)), (np.array([[1.0, 2.0, 3.0]]), np.array([1.7])), tools.coil(900, 77)]
+    for k, dims in enumerate(((65, 64, 64), (4, 4, 2))):
+        lat = cell_sort_ref.lattice(dims, cell_sort_ref.random_cells(dims, 300 if k == 0 else 40, 60 + k), 60 + k)[0]
+        parts.append((lat, np.random.default_rng(70 + k).uniform(1.5, 2.0, len(lat))))
     xyz = np.concatenate([p[0] for p in parts]); r = np.concatenate([p[1] for p in parts])
     offs = np.concatenate([[0], np.cumsum([len(p[1]) for p in parts])]).astype(np.int64)
     monkeypatch.delenv("FREESASA_AMD_NO_FUSED_SORT", raising=False)
@@ -484,6 +491,28 @@ def test_cell_sort_in_one_kernel_equals_the_general_pipeline(fa, oracle_lib, mon
     lr2, _, ltot2 = fa.calc_batch(xyz, r, offs, fa.LEE_RICHARDS, 1.4, 20)
     sr2, cnt2, _ = fa.calc_batch(xyz, r, offs, fa.SHRAKE_RUPLEY, 1.4, 100)
     assert np.array_equal(lr, lr2) and np.array_equal(cnt, cnt2) and np.array_equal(sr, sr2) and np.array_equal(ltot, ltot2)
+    # ... and k_sort_struct with the dense table, on a context of this test's own (the calls above take theirs from the library's
+    # pool, whose contexts the suite's later tests meet again with what they learnt here: their number stays what it was)
+    import torch
+    monkeypatch.delenv("FREESASA_AMD_NO_FUSED_SORT")
+    monkeypatch.setenv("FREESASA_AMD_DENSE_CELLS", "1")
+    dx, dr = torch.from_numpy(xyz.reshape(-1)).cuda(), torch.from_numpy(r).cuda()
+    out, tot = torch.zeros(len(r), dtype=torch.float64, device="cuda"), torch.zeros(len(parts), dtype=torch.float64, device="cuda")
+    dcnt = torch.zeros(len(r), dtype=torch.int32, device="cuda")
+    ctx = fa.GpuContext(0)
+    try:
+        # (k_sort_struct with the dense table numbers C + 1 cells per structure that holds atoms, the general pipeline C: the
+        # batch's cell total says which of them sorted it - a batch handed back to the general pipeline would pass unseen)
+        dense_total = cell_sort_ref.Reference(xyz, r, offs, 1.4).total(1)
+        ctx.lee_richards(dx.data_ptr(), dr.data_ptr(), offs, out.data_ptr(), tot.data_ptr(), probe=1.4, n_slices=20)
+        assert ctx.stats()["n_cells"] == dense_total
+        lr3, ltot3 = out.cpu().numpy().copy(), tot.cpu().numpy().copy()
+        ctx.shrake_rupley(dx.data_ptr(), dr.data_ptr(), offs, out.data_ptr(), dcnt.data_ptr(), 0, probe=1.4, n_points=100)
+        assert ctx.stats()["n_cells"] == dense_total
+        sr3, cnt3 = out.cpu().numpy().copy(), dcnt.cpu().numpy().copy()
+    finally:
+        ctx.close()
+    assert np.array_equal(lr, lr3) and np.array_equal(cnt, cnt3) and np.array_equal(sr, sr3) and np.array_equal(ltot, ltot3)
     for k in range(len(parts)):
         sl = slice(offs[k], offs[k + 1])
         if offs[k + 1] > offs[k]:
