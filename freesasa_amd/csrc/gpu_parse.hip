@@ -22,9 +22,12 @@
  *                    kept atom in atom order, as the host loader stores them
  *
  * What the device REFUSES goes to the host parser, file by file, and is counted: coordinates not of the "%8.3f" form
- * (PDB) or not plain decimals of <= 15 digits (mmCIF) - the host's strtod path -, lines longer than the reference's
- * 119-byte fgets chunk, RADIUS_FROM_OCCUPANCY, mmCIF that is not ONE data block with its _atom_site category in one
- * loop with one row per line (pair form, several blocks, text fields or names with blanks inside the rows).
+ * (PDB; a field whose eight columns are all taken, 1000.000 and above, counts as not of the form: nothing separates it
+ * from its neighbour) or not plain decimals of <= 15 digits (mmCIF) - the host's strtod path -, lines longer than the
+ * reference's 119-byte fgets chunk, RADIUS_FROM_OCCUPANCY, mmCIF that is not ONE data block with its _atom_site category
+ * in one loop of at most 64 columns with one row per line (pair form, several blocks, text fields or names with blanks
+ * inside the rows, a keyword behind values on a line).  The bar for all of it: the generated files of tests/parse_gen.py,
+ * each marked with what this paragraph promises for it (tests/test_parse_gen_gpu.py).
  * Output: coordinates, radii, classes, atoms per file, status per file - what a sweep's totals and class sums need - and,
  * for freesasa_gpu_sweep_files_residues, residue boundaries, labels, reference rows and backbone flags by the host loader's
  * rules (parse_batch_dev_residues_*; kernels of their own, so the plain sweep runs exactly the kernels it ran before).
@@ -304,7 +307,7 @@ __device__ void parse_pdb_line(const ParseArgs &a, const unsigned char *line, in
         else hyd = (line[12] == 'H' || line[13] == 'H' || line[12] == 'D' || line[13] == 'D') ? 1 : 0;
         if (hyd && !want_h) return;
         const bool has_name = n >= 16;
-        const unsigned alt = has_name ? line[16] : 0u;
+        const unsigned alt = n > 16 ? line[16] : 0u; /* (n == 16: the byte behind the line is the next line's - or the next file's - first) */
         flag = PL_CAND | (alt << PL_ALT_SHIFT);
         if (n < 54) { flag |= PL_ERR_FORMAT; return; }
         if (!coords_8_3(line + 30, v)) { flag |= PL_HOST; return; } /* (the host's scan_double / strtod path) */

@@ -388,12 +388,12 @@ static void parse_pdb(const char *text, size_t len, int options, const freesasa_
 
             /* the fields atom_new_from_line takes (ref: src/structure.c:199-235) */
             const int has_name = n >= 16;
-            const char alt = has_name ? line[16] : '\0';
+            const char alt = n > 16 ? line[16] : '\0'; /* (n == 16: the reference reads its buffer's terminator there, ref: src/pdb.c:219-224 - here that byte is the next line's first) */
             char aname[5] = "", rname[4] = "", rnumber[6] = "", symbol[3] = "";
             if (has_name) memcpy(aname, line + 12, 4);
             if (n >= 20) memcpy(rname, line + 17, 3);
             if (n >= 27) memcpy(rnumber, line + 22, 5);
-            const char chain = n >= 21 ? line[21] : '\0';
+            const char chain = n > 21 ? line[21] : '\0';
             if (has_sym) { symbol[0] = s0; symbol[1] = s1; }
             if (!has_sym || (s0 == ' ' && s1 == ' ')) {
                 /* (a line without a name column is either skipped by the alt-loc rule or fails at
