@@ -1211,6 +1211,10 @@ def _stats_proto(L):
                                                             C.c_char_p, C.c_longlong, _ip, C.c_int, _llp, C.c_int, C.c_char_p, C.c_char_p,
                                                             C.c_char_p, C.c_int]
     L.freesasa_gpu_trajectory_file_groups_periodic.argtypes = L.freesasa_gpu_trajectory_file_groups_stats.argtypes
+    # the same with interface pairs: (pairs, n_pairs, the pair areas: an array / a path) in front of err
+    L.freesasa_gpu_trajectory_interfaces.argtypes = L.freesasa_gpu_trajectory_groups_stats.argtypes[:-2] + [_i32p, C.c_int, _dp, C.c_char_p, C.c_int]
+    L.freesasa_gpu_trajectory_file_interfaces.argtypes = L.freesasa_gpu_trajectory_file_groups_stats.argtypes[:-2] + \
+        [_i32p, C.c_int, C.c_char_p, C.c_char_p, C.c_int]
     return L
 
 
@@ -1580,11 +1584,14 @@ class TopologyResult:
     its group taken on its own (isolated - sasa: what the atom buries in the complex).  stats: the RunStats of the outputs
     named in stats=, None without.  With per_frame=False only totals (and selection_atoms) are delivered per frame: the others
     are None.  volumes [F]: with volumes=True, the volume every frame's solvent-accessible surface encloses; None without.
-    masks [F, n, 4] uint32: with masks=True, every atom's exposure mask in every frame (calc_masks); None without."""
+    masks [F, n, 4] uint32: with masks=True, every atom's exposure mask in every frame (calc_masks); None without.
+    pair_areas [F, K, 6] and pair_groups [K, 2]: with interface_pairs=, per frame and pair (g, h) of groups (iso_g, iso_h,
+    in_pair_g, in_pair_h, buried_g, buried_h) as calc_interfaces orders them; None without."""
 
     def __init__(self, totals, class_sums, residues, selection_areas, selection_atoms, sasa, res_ref, group_areas=None,
-                 group_atoms=None, isolated=None, stats=None, volumes=None, masks=None):
+                 group_atoms=None, isolated=None, stats=None, volumes=None, masks=None, pair_areas=None, pair_groups=None):
         self.stats, self.volumes, self.masks = stats, volumes, masks
+        self.pair_areas, self.pair_groups = pair_areas, pair_groups
         self.totals, self.class_sums, self.residues = totals, class_sums, residues
         self.selection_areas, self.selection_atoms, self.sasa, self.res_ref = selection_areas, selection_atoms, sasa, res_ref
         self.group_areas, self.group_atoms, self.isolated = group_areas, group_atoms, isolated
@@ -1628,9 +1635,27 @@ def _topology_groups(batch, structure, n, chain_groups, separate_chains, long, g
     return group, G, np.bincount(group[(group >= 0) & (group < G)], minlength=max(G, 0)).astype(np.int64)
 
 
+def _interface_pairs(interface_pairs, ids, G):
+    """pairs [K, 2] int32 of interface_pairs= ("all": every g < h, g-major - the order of calc_interfaces' table), or None; the
+    library checks the pairs"""
+    if interface_pairs is None:
+        return None
+    if ids is None:
+        raise ValueError("interface_pairs needs chain groups: chain_groups=, separate_chains=True or group= with n_groups=")
+    if isinstance(interface_pairs, str):
+        if interface_pairs != "all":
+            raise ValueError('interface_pairs is None, "all" or a list of (g, h)')
+        return np.array([(g, h) for g in range(G) for h in range(g + 1, G)], dtype=np.int32).reshape(-1, 2)
+    pairs = np.ascontiguousarray(interface_pairs, dtype=np.int32)
+    if pairs.size and (pairs.ndim != 2 or pairs.shape[1] != 2):
+        raise ValueError("interface_pairs must be [K, 2]: one (g, h) per pair")
+    return pairs.reshape(-1, 2)
+
+
 def trajectory_topology(frames, batch, structure=0, atom_index=None, selection=None, per_atom=False, alg=LEE_RICHARDS, probe=1.4,
                         resolution=20, frames_per_batch=0, device=-1, devices=None, chain_groups=None, separate_chains=False,
-                        long=False, group=None, n_groups=None, stats=None, per_frame=True, volumes=False, masks=False):
+                        long=False, group=None, n_groups=None, stats=None, per_frame=True, volumes=False, masks=False,
+                        interface_pairs=None):
     """freesasa_gpu_trajectory_topology(): frames [F, frame_atoms, 3] of a (solvated) system whose solute is structure
     `structure` of the ingest.Batch - topology atom i is frame atom atom_index[i] (None: the frames hold exactly the
     structure's atoms) - -> a TopologyResult.  The gather, the per-residue, per-class and per-selection sums run on the
@@ -1646,14 +1671,20 @@ def trajectory_topology(frames, batch, structure=0, atom_index=None, selection=N
     result's volumes [F] holds the volume every frame's surface encloses, as calc_volume gives it for the frame.
     masks=True (freesasa_gpu_trajectory_masks; Shrake-Rupley, up to 128 points, no chain groups, no statistics, no volumes): the
     result's masks [F, n, 4] holds every atom's exposure mask in every frame, as calc_masks gives it for the frame; the dots of any
-    frame follow from it with dots_from_masks."""
+    frame follow from it with dots_from_masks.
+    interface_pairs="all" or [(g, h), ...] (freesasa_gpu_trajectory_interfaces; needs chain groups; no volumes, no masks): the
+    result's pair_areas [F, K, 6] holds, per frame and pair of groups g < h, (iso_g, iso_h, in_pair_g, in_pair_h, buried_g,
+    buried_h) - which partner buries how much; pair_groups [K, 2] the pairs ("all": every g < h, g-major).  There is no contact
+    screen: a pair that does not touch in a frame has buried areas of 0 or rounding noise."""
+    if interface_pairs is not None and (volumes or masks):
+        raise ValueError("interface_pairs is not offered with volumes=True or masks=True")
     if volumes and (stats or not per_frame or chain_groups is not None or separate_chains or group is not None):
         raise ValueError("volumes=True is not offered with chain groups, stats= or per_frame=False")
     if masks and (volumes or stats or not per_frame or chain_groups is not None or separate_chains or group is not None):
         raise ValueError("masks=True is not offered with chain groups, stats=, per_frame=False or volumes=True")
-    if stats or not per_frame:
+    if stats or not per_frame or interface_pairs is not None:
         return _trajectory_topology_stats(frames, batch, structure, atom_index, selection, per_atom, alg, probe, resolution, frames_per_batch,
-                                          device, devices, chain_groups, separate_chains, long, group, n_groups, stats, per_frame)
+                                          device, devices, chain_groups, separate_chains, long, group, n_groups, stats, per_frame, interface_pairs)
     L = _topology_proto(lib())
     frames = np.ascontiguousarray(frames, dtype=np.float64)
     if frames.ndim != 3 or frames.shape[2] != 3:
@@ -1713,7 +1744,7 @@ def trajectory_topology(frames, batch, structure=0, atom_index=None, selection=N
 
 
 def _trajectory_topology_stats(frames, batch, structure, atom_index, selection, per_atom, alg, probe, resolution, frames_per_batch,
-                               device, devices, chain_groups, separate_chains, long, group, n_groups, stats, per_frame):
+                               device, devices, chain_groups, separate_chains, long, group, n_groups, stats, per_frame, interface_pairs=None):
     L = _stats_proto(_topology_proto(lib()))
     frames = np.ascontiguousarray(frames, dtype=np.float64)
     if frames.ndim != 3 or frames.shape[2] != 3:
@@ -1722,6 +1753,7 @@ def _trajectory_topology_stats(frames, batch, structure, atom_index, selection, 
     n, R, res_ref, idx, fa_ = _topology_args(batch, structure, atom_index, frames.shape[1])
     S = len(selection) if selection is not None else 0
     ids, G, g_atoms = _topology_groups(batch, structure, n, chain_groups, separate_chains, long, group, n_groups)
+    pairs = _interface_pairs(interface_pairs, ids, G)
     word = stats_word(stats)
     totals = np.zeros(F)
     cls, res = (np.zeros((F, 3)), np.zeros((F, R, 6))) if per_frame else (None, None)
@@ -1738,6 +1770,18 @@ def _trajectory_topology_stats(frames, batch, structure, atom_index, selection, 
     keep, dp_, nd = _devs(devices, device)
     cb = batch._as_c()
     opt = lambda a, t=_dp: None if a is None else a.ctypes.data_as(t)
+    if pairs is not None:
+        p_areas = np.zeros((F, pairs.shape[0], 6))
+        ret = L.freesasa_gpu_trajectory_interfaces(frames.ctypes.data_as(_dp), F, C.byref(cb), structure, fa_, opt(idx, C.POINTER(C.c_int32)),
+                                                   selection.handle if selection is not None else None, opt(ids, C.POINTER(C.c_int32)), G,
+                                                   alg, probe, resolution, frames_per_batch, totals.ctypes.data_as(_dp), opt(sasa),
+                                                   opt(cls), opt(res), opt(sel_area), opt(sel_atoms, C.POINTER(C.c_longlong)), opt(g_areas),
+                                                   opt(iso), dp_, nd, word, raw.ctypes.data_as(_dp) if word else None, opt(parts),
+                                                   pairs.ctypes.data_as(C.POINTER(C.c_int32)), pairs.shape[0], p_areas.ctypes.data_as(_dp), err, 512)
+        if ret:
+            raise RuntimeError("freesasa_gpu_trajectory_interfaces: " + err.value.decode())
+        run = RunStats(raw, word, n, R, S, max(G, 0), parts, nf) if word else None
+        return TopologyResult(totals, cls, res, sel_area, sel_atoms, sasa, res_ref, g_areas, g_atoms, iso, run, pair_areas=p_areas, pair_groups=pairs)
     ret = L.freesasa_gpu_trajectory_groups_stats(frames.ctypes.data_as(_dp), F, C.byref(cb), structure, fa_, opt(idx, C.POINTER(C.c_int32)),
                                                  selection.handle if selection is not None else None, opt(ids, C.POINTER(C.c_int32)), G,
                                                  alg, probe, resolution, frames_per_batch, totals.ctypes.data_as(_dp), opt(sasa),
@@ -1755,7 +1799,7 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
                              max_new_shards=0, device=-1, devices=None, out_f32=False, chain_groups=None, separate_chains=False,
                              long=False, group=None, n_groups=None, group_areas_path=None, isolated_path=None, dcd=False, pbc=False,
                              triclinic=False, netcdf=False, xtc=False, stats=None, stats_path=None, partials_path=None, trr=False,
-                             volumes_path=None, masks_path=None):
+                             volumes_path=None, masks_path=None, interface_pairs=None, pair_areas_path=None):
     """freesasa_gpu_trajectory_file_topology(): trajectory_file() with a topology (see trajectory_topology; frame_atoms:
     atoms per frame of the file, None: the structure's) and one raw fp64 result file per output asked for: class sums
     [F, 3], residues [F, R, 6], selection areas [F, S].  Returns (complete, n_frames, selection_atoms [S] or None).
@@ -1773,8 +1817,14 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
     volumes_path (freesasa_gpu_trajectory_file_volume; Shrake-Rupley, up to 128 points, no chain groups, no statistics, no pbc):
     receives the frames' volumes [F] fp64, as trajectory_topology(volumes=True) gives them.
     masks_path (freesasa_gpu_trajectory_file_masks; Shrake-Rupley, up to 128 points, no chain groups, no statistics, no pbc, no
-    volumes): receives the frames' exposure masks [F, n, 4] uint32, as trajectory_topology(masks=True) gives them."""
+    volumes): receives the frames' exposure masks [F, n, 4] uint32, as trajectory_topology(masks=True) gives them.
+    interface_pairs="all" or [(g, h), ...] with pair_areas_path (freesasa_gpu_trajectory_file_interfaces; needs chain groups; no
+    pbc, no volumes, no masks): pair_areas_path receives [F, K, 6] fp64, as trajectory_topology(interface_pairs=...) gives them."""
     L = _stats_proto(_topology_proto(lib()))
+    if (interface_pairs is None) != (pair_areas_path is None):
+        raise ValueError("interface_pairs and pair_areas_path go together")
+    if interface_pairs is not None and (volumes_path is not None or masks_path is not None):
+        raise ValueError("interface_pairs is not offered with volumes_path or masks_path")
     if volumes_path is not None and (stats or chain_groups is not None or separate_chains or group is not None or
                                      group_areas_path is not None or isolated_path is not None):
         raise ValueError("volumes_path is not offered with chain groups or stats=")
@@ -1799,6 +1849,22 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
     keep, dp_, nd = _devs(devices, device)
     cb = batch._as_c()
     ids, G, _ = _topology_groups(batch, structure, n, chain_groups, separate_chains, long, group, n_groups)
+    pairs = _interface_pairs(interface_pairs, ids, G)
+    if pairs is not None:
+        ret = L.freesasa_gpu_trajectory_file_interfaces(enc(frames_path), bits, header_bytes, n_frames, C.byref(cb), structure, fa_,
+                                                        None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                        selection.handle if selection is not None else None,
+                                                        ids.ctypes.data_as(C.POINTER(C.c_int32)), G,
+                                                        alg, probe, resolution, frames_per_batch, enc(totals_path), enc(sasa_path),
+                                                        enc(class_sums_path), enc(residues_path), enc(selections_path),
+                                                        None if sel_atoms is None else sel_atoms.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                                        enc(group_areas_path), enc(isolated_path),
+                                                        enc(done_path), max_new_shards, dp_, nd, C.byref(total), stats_word(stats) if stats else 0,
+                                                        enc(stats_path), enc(partials_path),
+                                                        pairs.ctypes.data_as(C.POINTER(C.c_int32)), pairs.shape[0], enc(pair_areas_path), err, 512)
+        if ret < 0:
+            raise RuntimeError("freesasa_gpu_trajectory_file_interfaces: " + err.value.decode())
+        return ret == 0, int(total.value), sel_atoms
     if volumes_path is not None:
         ret = L.freesasa_gpu_trajectory_file_volume(enc(frames_path), bits, header_bytes, n_frames, C.byref(cb), structure, fa_,
                                                     None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),

@@ -132,6 +132,11 @@ hipError_t kl_traj_group_radii(const sasa::TrajGroupArgs &a, hipStream_t st);
 hipError_t kl_traj_group_gather(const sasa::TrajGroupArgs &a, hipStream_t st);
 hipError_t kl_traj_group_finish(const sasa::TrajGroupArgs &a, hipStream_t st);
 hipError_t kl_traj_group_totals(const sasa::TrajGroupArgs &a, hipStream_t st);
+/* ... interfaces between chain groups per frame: the pair structures' radii and the sides' boundaries (once per shard length),
+   their coordinates behind the isolated structures, six doubles per (frame, pair) behind kl_segment_sums over the sides */
+hipError_t kl_traj_pair_radii(const sasa::TrajPairArgs &a, hipStream_t st);
+hipError_t kl_traj_pair_gather(const sasa::TrajPairArgs &a, hipStream_t st);
+hipError_t kl_traj_pair_rows(const sasa::TrajPairArgs &a, hipStream_t st);
 /* ... run statistics: a shard's partial [4][W] of the outputs in the table of segments (one thread per column) */
 hipError_t kl_traj_stats(const sasa::TrajStatsArgs &a, hipStream_t st);
 

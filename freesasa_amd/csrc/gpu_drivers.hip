@@ -27,6 +27,9 @@
 #include <sys/stat.h>
 #include <time.h>
 
+#include <algorithm>
+#include <utility>
+
 #include "engine_internal.h"
 #include "select_program.h"
 
@@ -139,7 +142,7 @@ namespace {
 /* One per-frame OUTPUT of a run: a row of TrajIO's table.  An entry point says where it goes - the caller's array or a
    result file - and everything else that is per output (opening the files, is it wanted, its place in a shard's blocks, the
    copy or the pwrite at the frame's offset, the flush, the done-list's outputs= word) is a loop over the table. */
-enum { OUT_TOTALS, OUT_SASA, OUT_ISO, OUT_MASK, OUT_CLS, OUT_RES, OUT_SEL, OUT_GRP, OUT_VOL, N_OUT }; /* (per atom | from OUT_CLS on: the block of sums) */
+enum { OUT_TOTALS, OUT_SASA, OUT_ISO, OUT_MASK, OUT_CLS, OUT_RES, OUT_SEL, OUT_GRP, OUT_PAIR, OUT_VOL, N_OUT }; /* (per atom | from OUT_CLS on: the block of sums) */
 struct TrajOut {
     const char *name;           /* in messages: "cannot open the %s file", "could not write the %s file" */
     int bit;                    /* in the outputs= word of a done-list's first line */
@@ -156,13 +159,14 @@ struct TrajOut {
 struct TrajIO {
     FrameSource src; /* the frames: host memory or a frame file of any format (engine_internal.h, gpu_frames.hip) */
     /* per frame: total [1], per-atom areas [n]; runs with a topology: class sums [3], residue areas [6 R], selection areas [S];
-       with chain groups: every atom's area in its isolated group [n], and isolated, complex, buried per group [3 G]; the volume
+       with chain groups: every atom's area in its isolated group [n], and isolated, complex, buried per group [3 G]; with
+       interface pairs: six doubles per pair [6 K] (traj_kernels.h, traj_pair_rows; no statistics: no bit of the statistics word); the volume
        entries: the frame's volume [1] (gpu_volume.hip; it has no run statistics: no bit of the statistics word); the mask entries:
        every atom's exposure mask, four uint32 words [4 n] (gpu_dots.hip; per atom, 4 bytes a value, copied as it lies; no statistics) */
     TrajOut out[N_OUT] = {{"totals", 0, FREESASA_GPU_STATS_TOTALS}, {"per-atom", 1, FREESASA_GPU_STATS_ATOMS}, {"isolated", 32, FREESASA_GPU_STATS_ISOLATED},
                           {"masks", 128, 0, nullptr, nullptr, Fd(), 4},
                           {"class-sums", 2, FREESASA_GPU_STATS_CLASSES}, {"residues", 4, FREESASA_GPU_STATS_RESIDUES},
-                          {"selections", 8, FREESASA_GPU_STATS_SELECTIONS}, {"groups", 16, FREESASA_GPU_STATS_GROUPS}, {"volumes", 64, 0}};
+                          {"selections", 8, FREESASA_GPU_STATS_SELECTIONS}, {"groups", 16, FREESASA_GPU_STATS_GROUPS}, {"interfaces", 256, 0}, {"volumes", 64, 0}};
     /* run statistics (include/freesasa_gpu.h): the word; every shard's partial [4][W] at k * 4 W doubles of a host array or of
        the partials file; the merged result to the caller's array (memory form: the entry merges) or the statistics file */
     int stats = 0;
@@ -192,6 +196,11 @@ struct TrajTopo {
     int n_groups = 0, n_iso = 0;     /* G; atoms with an id >= 0 */
     std::vector<int64_t> gfirst;     /* [G + 1] */
     std::vector<int32_t> src;        /* [n_iso] */
+    /* interfaces between chain groups (pair_make): the pairs, and the cut of a frame's pair structures (traj_kernels.h, traj_pair_cut) */
+    const int32_t *pairs = nullptr;  /* [K, 2] g < h; NULL: a run without pairs */
+    int n_pairs = 0, n_pair = 0;     /* K; atoms of a frame's pair structures: the sum over the pairs of |g| + |h| */
+    std::vector<int64_t> pfirst, pside; /* [K + 1], [2 K + 1] */
+    std::vector<int32_t> psrc;       /* [n_pair] */
 };
 
 unsigned long long fnv1a(const void *p, size_t bytes, unsigned long long h = 1469598103934665603ULL)
@@ -265,15 +274,58 @@ int group_make(const int32_t *group, int n_groups, bool areas, bool iso, TrajTop
     return 0;
 }
 
+/* What the interface entries refuse before a device is touched or a file opened, each with its own message: 0, or -1 */
+int pair_check(const int32_t *group, int n_groups, const int32_t *pairs, int n_pairs, int frames_f32, const void *out, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (!group) return set_err(err_out, err_len, "interfaces need chain groups: group ids (group is NULL)");
+    if (n_pairs < 1) return set_err(err_out, err_len, "interfaces need at least one pair of groups (n_pairs < 1)");
+    if (!pairs) return set_err(err_out, err_len, "null argument: the pairs");
+    if (!out) return set_err(err_out, err_len, "null argument: the pair areas have nowhere to go");
+    if (frames_f32 & (FREESASA_GPU_FRAMES_PBC | FREESASA_GPU_FRAMES_TRICLINIC))
+        return set_err(err_out, err_len, "bit 3 and bit 4 of frames_f32: interfaces among periodic images are not offered");
+    char msg[200];
+    for (int k = 0; k < n_pairs; ++k) {
+        const int32_t g = pairs[2 * k], h = pairs[2 * k + 1];
+        if (g < 0 || h < 0 || g >= n_groups || h >= n_groups || g >= h) {
+            snprintf(msg, sizeof msg, "pair %d is (%d, %d): a pair is (g, h) with 0 <= g < h < n_groups = %d", k, g, h, n_groups);
+            return set_err(err_out, err_len, msg);
+        }
+    }
+    return guarded(err_out, err_len, [&]() -> int {
+        std::vector<std::pair<int64_t, int>> key((size_t)n_pairs);
+        for (int k = 0; k < n_pairs; ++k) key[(size_t)k] = {(int64_t)pairs[2 * k] * n_groups + pairs[2 * k + 1], k};
+        std::sort(key.begin(), key.end());
+        for (int k = 1; k < n_pairs; ++k)
+            if (key[(size_t)k].first == key[(size_t)k - 1].first) {
+                snprintf(msg, sizeof msg, "pairs %d and %d are the same pair (%d, %d): a pair is named at most once", key[(size_t)k - 1].second,
+                         key[(size_t)k].second, pairs[2 * key[(size_t)k].second], pairs[2 * key[(size_t)k].second + 1]);
+                return set_err(err_out, err_len, msg);
+            }
+        return 0;
+    });
+}
+/* ... and the cut of the pair structures, behind group_make and pair_check: nothing is left to refuse */
+void pair_make(const int32_t *pairs, int n_pairs, TrajTopo *tp)
+{
+    if (!pairs || n_pairs < 1) return;
+    tp->pfirst.resize((size_t)n_pairs + 1);
+    tp->pside.resize(2 * (size_t)n_pairs + 1);
+    const int64_t n_pair = sasa::traj_pair_cut(pairs, n_pairs, tp->gfirst.data(), tp->src.data(), tp->pfirst.data(), tp->pside.data(), nullptr);
+    tp->psrc.resize((size_t)n_pair);
+    sasa::traj_pair_cut(pairs, n_pairs, tp->gfirst.data(), tp->src.data(), tp->pfirst.data(), tp->pside.data(), tp->psrc.data());
+    tp->pairs = pairs; tp->n_pairs = n_pairs; tp->n_pair = (int)n_pair;
+}
+
 /* The argument checks of a statistics word, on the host: 0, or -1 with a message that names the output.  tp NULL: a run without
    a topology; has_sel, has_group: was a selection set, were group ids given? */
 int stats_check(int stats, const TrajTopo *tp, bool has_sel, bool has_group, char *err_out, int err_len)
 {
     if (stats & ~127) return set_err(err_out, err_len, "unknown bit in the statistics word");
     /* (the table's names and bits, without a TrajIO: nothing here allocates) */
-    static const char *const name[N_OUT] = {"totals", "per-atom", "isolated", "masks", "class-sums", "residues", "selections", "groups", "volumes"};
+    static const char *const name[N_OUT] = {"totals", "per-atom", "isolated", "masks", "class-sums", "residues", "selections", "groups", "interfaces", "volumes"};
     static const int sbit[N_OUT] = {FREESASA_GPU_STATS_TOTALS, FREESASA_GPU_STATS_ATOMS, FREESASA_GPU_STATS_ISOLATED, 0, FREESASA_GPU_STATS_CLASSES,
-                                    FREESASA_GPU_STATS_RESIDUES, FREESASA_GPU_STATS_SELECTIONS, FREESASA_GPU_STATS_GROUPS, 0};
+                                    FREESASA_GPU_STATS_RESIDUES, FREESASA_GPU_STATS_SELECTIONS, FREESASA_GPU_STATS_GROUPS, 0, 0};
     char msg[160];
     for (int k = 0; k < N_OUT; ++k) {
         if (!(stats & sbit[k])) continue;
@@ -293,19 +345,31 @@ size_t stats_width(int stats, int n_atoms, const TrajTopo *tp, long long *first)
 }
 
 /* Once per lane: the topology onto the lane's context - c->seg: residue boundaries | the one structure's offsets | index |
-   classes | backbone flags [| radii | group ids | src: the constant part of `ga`]; with selections the keys, labels and program where freesasa_gpu_select_batch puts them, and
+   classes | backbone flags [| radii | group ids | src: the constant part of `ga` [| pside | pairs | psrc: that of `xa`]]; with selections the keys, labels and program where freesasa_gpu_select_batch puts them, and
    sel_mask_atom over the topology: the mask words stay in c->parse[PBUF_SEL_BITS].  (run_batch touches none of these.)
    Fills the constant part of `ta`.  Enqueued on the context's stream, nothing waited for. */
-int topo_upload(freesasa_gpu_ctx *c, const TrajTopo &tp, sasa::TrajArgs &ta, sasa::TrajGroupArgs &ga)
+int topo_upload(freesasa_gpu_ctx *c, const TrajTopo &tp, sasa::TrajArgs &ta, sasa::TrajGroupArgs &ga, sasa::TrajPairArgs &xa)
 {
     const size_t n = (size_t)tp.n, R = (size_t)tp.n_res;
     const size_t b_seg = 8 * (R + 3), b_idx = tp.index ? (4 * n + 7) & ~(size_t)7 : 0;
     /* chain groups, behind the flags: the structure's radii (the combined batch's are made of them on the device) | ids | src */
     const size_t b_flags = (2 * n + 7) & ~(size_t)7, b_grp = tp.group ? 8 * n + 4 * n + 4 * (size_t)tp.n_iso : 0;
-    if (ensure(c, c->seg, b_seg + b_idx + (tp.group ? b_flags : 2 * n) + b_grp)) return -1;
+    /* interface pairs, behind the groups' part at the next multiple of 8: the sides' begins | the pairs | psrc */
+    const size_t K = (size_t)tp.n_pairs, b_grp8 = (b_grp + 7) & ~(size_t)7, b_pair = K ? b_grp8 - b_grp + 8 * (2 * K + 1) + 8 * K + 4 * (size_t)tp.n_pair : 0;
+    if (ensure(c, c->seg, b_seg + b_idx + (tp.group ? b_flags : 2 * n) + b_grp + b_pair)) return -1;
     char *base = (char *)c->seg.p;
     hipStream_t st = c->stream;
     memset(&ga, 0, sizeof ga);
+    memset(&xa, 0, sizeof xa);
+    if (K) {
+        char *x = base + b_seg + b_idx + b_flags + b_grp8;
+        HIP_TRY(c, hipMemcpyAsync(x, tp.pside.data(), 8 * (2 * K + 1), hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(x + 8 * (2 * K + 1), tp.pairs, 8 * K, hipMemcpyHostToDevice, st));
+        if (tp.n_pair) HIP_TRY(c, hipMemcpyAsync(x + 8 * (2 * K + 1) + 8 * K, tp.psrc.data(), 4 * (size_t)tp.n_pair, hipMemcpyHostToDevice, st));
+        xa.n = tp.n; xa.n_iso = tp.n_iso; xa.n_pair = tp.n_pair; xa.n_groups = tp.n_groups; xa.n_pairs = tp.n_pairs;
+        xa.pside = (const int64_t *)x; xa.pairs = (const int32_t *)(x + 8 * (2 * K + 1)); xa.psrc = xa.pairs + 2 * K;
+        xa.radii = (const double *)(base + b_seg + b_idx + b_flags);
+    }
     if (tp.group) {
         char *g = base + b_seg + b_idx + b_flags;
         HIP_TRY(c, hipMemcpyAsync(g, tp.radii, 8 * n, hipMemcpyHostToDevice, st));
@@ -372,7 +436,10 @@ int traj_check_args(const TrajSpec &s, const char *sizes_msg, char *err_out, int
    sizing by the kept atoms, i.e. longer shards for the engine, would be faster). */
 int traj_shard_size(TrajSpec &s, long long frame_atoms, char *err_out, int err_len)
 {
-    if (s.frames_per_batch <= 0) s.frames_per_batch = (int)(1250000 / frame_atoms) + 1;
+    /* (with interface pairs the engine's batch can be many times the frames - all pairs of G groups: G - 1 times the atoms in
+       groups more - and the default goes by the combined atoms of a frame where those are more than come in) */
+    const long long comb = s.topo && s.topo->n_pairs ? (long long)s.topo->n + s.topo->n_iso + s.topo->n_pair : 0;
+    if (s.frames_per_batch <= 0) s.frames_per_batch = (int)(1250000 / (comb > frame_atoms ? comb : frame_atoms)) + 1;
     if (s.frames_per_batch > s.n_frames) s.frames_per_batch = (int)s.n_frames;
     if ((long long)s.frames_per_batch * frame_atoms > (1LL << 30)) return set_err(err_out, err_len, "batch too large");
     /* chain groups: the engine sees a shard's frames AND their isolated groups as one batch - up to twice the atoms */
@@ -380,6 +447,9 @@ int traj_shard_size(TrajSpec &s, long long frame_atoms, char *err_out, int err_l
                                     (long long)s.frames_per_batch * (1 + s.topo->n_groups) > (1LL << 30)))
         return set_err(err_out, err_len, "batch too large with chain groups: frames_per_batch x (atoms + atoms in groups) and frames_per_batch x (1 + groups) "
                                          "must not exceed 2^30");
+    if (comb && ((long long)s.frames_per_batch * comb > (1LL << 30) || (long long)s.frames_per_batch * (1 + s.topo->n_groups + s.topo->n_pairs) > (1LL << 30)))
+        return set_err(err_out, err_len, "batch too large with interface pairs: frames_per_batch x (atoms + atoms in groups + atoms in pair structures) and "
+                                         "frames_per_batch x (1 + groups + pairs) must not exceed 2^30");
     return 0;
 }
 
@@ -391,7 +461,9 @@ struct TrajRun {
     const size_t n = (size_t)s.n_atoms, FB = (size_t)s.frames_per_batch; /* atoms of a frame as the engine sees it, frames of a full shard */
     /* chain groups: behind a shard's frames every group of every frame as a structure of its own (traj_kernels.h) */
     const bool groups = topo && topo->group;
-    const size_t G = groups ? (size_t)topo->n_groups : 0, n_iso = groups ? (size_t)topo->n_iso : 0, nc = n + n_iso; /* nc: combined atoms per frame */
+    /* ... and with interface pairs, behind those, every pair structure of every frame */
+    const size_t G = groups ? (size_t)topo->n_groups : 0, n_iso = groups ? (size_t)topo->n_iso : 0;
+    const size_t K = groups ? (size_t)topo->n_pairs : 0, n_pair = groups ? (size_t)topo->n_pair : 0, nc = n + n_iso + n_pair; /* nc: combined atoms per frame */
     const long long n_shards = (s.n_frames + s.frames_per_batch - 1) / s.frames_per_batch;
     FrameSource &src = io.src; /* (planned below: what its shards are, a topology's index, the cutoff of periodic images) */
     /* the caller's arrays are page-locked: no staging */
@@ -399,15 +471,17 @@ struct TrajRun {
                             (!io.out[OUT_ISO].mem || host_pinned(io.out[OUT_ISO].mem)) && (!io.out[OUT_MASK].mem || host_pinned(io.out[OUT_MASK].mem));
     const size_t S = topo && topo->sel && (io.out[OUT_SEL].wanted() || io.sel_atoms || (io.stats & FREESASA_GPU_STATS_SELECTIONS)) ? (size_t)topo->n_sel : 0; /* selections computed */
     /* A shard's sums lie one behind the other in ONE block, cut to its nf frames: classes | residues | selection areas |
-       groups | volumes | selected atoms.  Output k's begin at x0[k] * nf doubles (k = N_OUT: the atom counts); xw doubles per frame hold it all. */
+       groups | interfaces | volumes | selected atoms.  Output k's begin at x0[k] * nf doubles (k = N_OUT: the atom counts); xw doubles per frame hold it all. */
     size_t x0[N_OUT + 1] = {0, 0, 0}, xw;
     /* does the block of sums go to the host?  (not when its outputs are computed for their statistics alone) */
-    const bool sums_down = io.out[OUT_CLS].wanted() || io.out[OUT_RES].wanted() || io.out[OUT_SEL].wanted() || io.out[OUT_GRP].wanted() || io.out[OUT_VOL].wanted() || io.sel_atoms;
+    const bool sums_down = io.out[OUT_CLS].wanted() || io.out[OUT_RES].wanted() || io.out[OUT_SEL].wanted() || io.out[OUT_GRP].wanted() || io.out[OUT_PAIR].wanted() || io.out[OUT_VOL].wanted() || io.sel_atoms;
     size_t sW = 0; /* run statistics: columns of a shard's partial; it lies behind a FULL shard's block of sums, at xw * FB doubles of c->h_gtot */
     const std::vector<double> tp = call_test_points(s.alg, s.resolution);
-    /* a full shard as a batch: k n; with chain groups behind them FB n + f n_iso + gfirst[g] - and the same for the run's short
-       last shard, whose isolated structures begin earlier (without groups a short shard is a prefix of the full one) */
+    /* a full shard as a batch: k n; with chain groups behind them FB n + f n_iso + gfirst[g], with interface pairs behind those
+       FB (n + n_iso) + f n_pair + pfirst[k] - and the same for the run's short last shard, whose isolated structures begin earlier
+       (without groups a short shard is a prefix of the full one) */
     std::vector<int64_t> offs, offs_last;
+    int grp_chunks = 0, grp_chunks_last = 0; /* (interface pairs) chunks of the engine's chunk table that belong to the frames and the isolated structures */
     std::atomic<long long> next{0}, fresh{0};
     std::atomic<int> stopped{0}, counts_out{0};
     FirstError fe;
@@ -432,26 +506,37 @@ struct TrajRun {
 
     void batch_offsets(size_t nf, std::vector<int64_t> &o) const
     {
-        o.resize(nf * (1 + G) + 1);
+        o.resize(nf * (1 + G + K) + 1);
         for (size_t k = 0; k <= nf; ++k) o[k] = (int64_t)(k * n);
         for (size_t f = 0; f < nf && G; ++f)
             for (size_t g = 1; g <= G; ++g) o[nf + f * G + g] = (int64_t)(nf * n + f * n_iso) + topo->gfirst[g];
+        for (size_t f = 0; f < nf && K; ++f)
+            for (size_t k = 1; k <= K; ++k) o[nf * (1 + G) + f * K + k] = (int64_t)(nf * (n + n_iso) + f * n_pair) + topo->pfirst[k];
+    }
+    /* the chunks of the first nf (1 + G) structures, as cell_sort_enqueue (gpu_engine.hip) cuts a batch's structures */
+    int chunks_before_pairs(size_t nf, const std::vector<int64_t> &o) const
+    {
+        int64_t k = 0;
+        for (size_t s = 0; s < nf * (1 + G); ++s) k += (o[s + 1] - o[s] + SASA_BOUNDS_CHUNK - 1) / SASA_BOUNDS_CHUNK;
+        return (int)k;
     }
     TrajRun(const TrajSpec &s_, TrajIO &io_) : s(s_), io(io_)
     {
         batch_offsets(FB, offs);
         if (groups && (size_t)(s.n_frames % s.frames_per_batch)) batch_offsets((size_t)(s.n_frames % s.frames_per_batch), offs_last);
-        const size_t per[N_OUT] = {1, n, groups ? n : 0, SR_CAP_WORDS * n, topo ? (size_t)3 : 0, topo ? 6 * (size_t)topo->n_res : 0, S, 3 * G, 1};
+        if (K) grp_chunks = chunks_before_pairs(FB, offs);
+        if (K && !offs_last.empty()) grp_chunks_last = chunks_before_pairs((size_t)(s.n_frames % s.frames_per_batch), offs_last);
+        const size_t per[N_OUT] = {1, n, groups ? n : 0, SR_CAP_WORDS * n, topo ? (size_t)3 : 0, topo ? 6 * (size_t)topo->n_res : 0, S, 3 * G, 6 * K, 1};
         /* (an output's place in the order of the statistics word's outputs, which is trajstats.c's and not the table's: the
            masks and the volumes have no statistics) */
-        static const int scol[N_OUT] = {0, 1, 2, -1, 3, 4, 5, 6, -1};
+        static const int scol[N_OUT] = {0, 1, 2, -1, 3, 4, 5, 6, -1, -1};
         long long first[N_OUT] = {0};
         sW = stats_width(io.stats, s.n_atoms, topo, first);
         for (int k = 0; k < N_OUT; ++k) {
             /* computed: delivered, or its statistics asked for (the selections' and the groups' kernels write theirs whenever they run) */
             io.out[k].stat = (io.stats & io.out[k].sbit) != 0;
             io.out[k].s0 = io.out[k].stat && scol[k] >= 0 ? (size_t)first[scol[k]] : 0;
-            io.out[k].per_frame = io.out[k].wanted() || io.out[k].stat || k == OUT_SEL || k == OUT_GRP ? per[k] : 0;
+            io.out[k].per_frame = io.out[k].wanted() || io.out[k].stat || k == OUT_SEL || k == OUT_GRP || k == OUT_PAIR ? per[k] : 0;
             if (k >= OUT_CLS) x0[k + 1] = x0[k] + io.out[k].per_frame;
         }
         xw = x0[N_OUT] + S;
@@ -464,6 +549,7 @@ struct TrajLane {
     bool radii_up = false, topo_up = false;
     sasa::TrajArgs ta;
     sasa::TrajGroupArgs ga; /* (chain groups) */
+    sasa::TrajPairArgs xa;  /* (interface pairs) */
     int radii_nf = 0;       /* ... the shard length the combined batch's radii are laid out for */
 };
 /* a shard in its lane's hands: frames [f0, f0 + nf) */
@@ -484,16 +570,17 @@ int shard_size(TrajRun &T, TrajLane &L)
     const size_t n = T.n, FB = T.FB, nc = T.nc, iso = T.io.out[OUT_ISO].per_frame;
     const size_t narrow_bytes = T.io.out_f32() ? 4 * (n + iso) * FB : 0; /* (the isolated areas' behind the per-atom areas') */
     if (hipSetDevice(c->device) != hipSuccess) return ctx_fail(c, "hipSetDevice failed");
-    /* (with chain groups nc = n + n_iso atoms and 1 + G structures per frame, and radii per atom: the isolated structures are not n atoms long) */
+    /* (with chain groups nc = n + n_iso [+ n_pair] atoms and 1 + G [+ K] structures per frame, and radii per atom: the isolated structures are not n atoms long) */
     if (ensure(c, c->h_xyz, 24 * nc * FB) || ensure(c, c->h_radii, T.groups ? 8 * nc * FB : 8 * n) || ensure(c, c->h_sasa, 8 * nc * FB) ||
-        ensure(c, c->h_totals, 8 * (1 + T.G) * FB) ||
+        ensure(c, c->h_totals, 8 * (1 + T.G + T.K) * FB) ||
+        (T.K && (ensure(c, c->if_sides, 8 * (2 * T.K * FB + 1)) || ensure(c, c->if_inpair, 16 * T.K * FB))) ||
         (T.src.widen_bytes() + narrow_bytes && ensure(c, c->h_counts, T.src.widen_bytes() + narrow_bytes)) ||
         (T.src.xyz_bytes() && ensure(c, c->g_xyz, T.src.xyz_bytes())) || (T.xw + T.sW && ensure(c, c->h_gtot, 8 * (T.xw * FB + 4 * T.sW))) ||
         (T.groups && (ensure(c, c->g_gath, 8 * nc * FB) || ensure(c, c->g_tot2, 8 * (1 + T.G) * FB))) || (iso && ensure(c, c->h_iso, 8 * n * FB)) ||
         (T.io.out[OUT_MASK].per_frame && ensure(c, c->dt_masks, 4 * SR_CAP_WORDS * n * FB)))
         return -1;
     if (!T.groups && !L.radii_up && hipMemcpyAsync(c->h_radii.p, T.s.radii, 8 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "radii upload failed");
-    if (T.topo && !L.topo_up && topo_upload(c, *T.topo, L.ta, L.ga)) return -1;
+    if (T.topo && !L.topo_up && topo_upload(c, *T.topo, L.ta, L.ga, L.xa)) return -1;
     L.radii_up = L.topo_up = true;
     return 0;
 }
@@ -516,9 +603,17 @@ int shard_upload(TrajRun &T, TrajLane &L, const TrajShard &h)
        combined batch once per shard length (the isolated structures begin at nf n) */
     sasa::TrajGroupArgs &ga = L.ga;
     ga.n_frames = h.nf; ga.xyz = (double *)c->h_xyz.p; ga.cradii = (double *)c->h_radii.p;
-    if (L.radii_nf != h.nf && kl_traj_group_radii(ga, c->stream) != hipSuccess) return ctx_fail(c, "launch of the groups' radii failed");
+    const bool radii_due = L.radii_nf != h.nf;
+    if (radii_due && kl_traj_group_radii(ga, c->stream) != hipSuccess) return ctx_fail(c, "launch of the groups' radii failed");
     L.radii_nf = h.nf;
     if (kl_traj_group_gather(ga, c->stream) != hipSuccess) return ctx_fail(c, "launch of the groups' gather failed");
+    if (!T.K) return 0;
+    /* interface pairs: behind the isolated structures every pair structure of every frame; their radii and the sides'
+       boundaries once per shard length too */
+    sasa::TrajPairArgs &xa = L.xa;
+    xa.n_frames = h.nf; xa.xyz = ga.xyz; xa.cradii = ga.cradii; xa.side_off = (int64_t *)c->if_sides.p;
+    if (radii_due && kl_traj_pair_radii(xa, c->stream) != hipSuccess) return ctx_fail(c, "launch of the pairs' radii failed");
+    if (kl_traj_pair_gather(xa, c->stream) != hipSuccess) return ctx_fail(c, "launch of the pairs' gather failed");
     return 0;
 }
 
@@ -562,7 +657,7 @@ int shard_compute(TrajRun &T, TrajLane &L, TrajShard &h)
                      ? masks_resident(c, (double *)c->h_xyz.p, (double *)c->h_radii.p, T.offs.data(), h.nf, T.s.probe, T.s.resolution, T.tp.data(),
                                       (double *)c->h_sasa.p, nullptr, (double *)c->h_totals.p, (unsigned *)c->dt_masks.p)
                  : run_batch(c, T.s.alg == 0, (double *)c->h_xyz.p, (double *)c->h_radii.p, (T.groups && nf != T.FB ? T.offs_last : T.offs).data(),
-                             (int)(nf * (1 + T.G)), T.s.probe, T.s.resolution, T.s.alg == 1 ? T.tp.data() : nullptr, (double *)c->h_sasa.p, nullptr,
+                             (int)(nf * (1 + T.G + T.K)), T.s.probe, T.s.resolution, T.s.alg == 1 ? T.tp.data() : nullptr, (double *)c->h_sasa.p, nullptr,
                              (double *)c->h_totals.p);
     c->shared_radii = false;
     if (rb) return -1;
@@ -575,15 +670,26 @@ int shard_compute(TrajRun &T, TrajLane &L, TrajShard &h)
         ga.ctot = (const double *)c->h_totals.p; ga.ctot2 = (const double *)c->g_tot2.p; ga.out = (double *)c->h_gtot.p + T.x0[OUT_GRP] * nf;
         sasa::PipeArgs pa;
         memset(&pa, 0, sizeof pa);
-        pa.n_structs = (int)(nf * (1 + T.G)); pa.n_atoms = (int)(nf * T.nc); pa.offsets = (const int64_t *)c->offsets.p;
-        pa.n_chunks = c->n_chunks; pa.chunk_struct = (const int *)c->chunk_struct.p; pa.chunk_begin = (const int64_t *)c->chunk_begin.p;
+        /* (interface pairs: the pair structures' chunks lie behind the others in the tables and are kept out - cgath has no
+           values there, and the groups' sums are what they are without pairs) */
+        pa.n_structs = (int)(nf * (1 + T.G)); pa.n_atoms = (int)(nf * (T.n + T.n_iso)); pa.offsets = (const int64_t *)c->offsets.p;
+        pa.n_chunks = !T.K ? c->n_chunks : nf != T.FB ? T.grp_chunks_last : T.grp_chunks; pa.chunk_struct = (const int *)c->chunk_struct.p; pa.chunk_begin = (const int64_t *)c->chunk_begin.p;
         pa.chunk_len = (const int *)c->chunk_len.p; pa.struct_chunk0 = (const int *)c->struct_chunk0.p;
         /* (among periodic images the finish and both reductions are done: run_batch's chunk tables describe the expanded batch) */
         if ((!gpbc && (kl_traj_group_finish(ga, c->stream) != hipSuccess ||
-                       kl_totals(pa, c->n_chunks, pa.n_structs, (const double *)c->g_gath.p, (double *)c->bpart.p, (double *)c->g_tot2.p, c->stream) != hipSuccess)) ||
+                       kl_totals(pa, pa.n_chunks, pa.n_structs, (const double *)c->g_gath.p, (double *)c->bpart.p, (double *)c->g_tot2.p, c->stream) != hipSuccess)) ||
             kl_traj_group_totals(ga, c->stream) != hipSuccess)
             return ctx_fail(c, "launch of the groups' sums failed");
         h.d_iso = ga.iso;
+        if (T.K) {
+            /* every side's area in its pair structure, summed as k_totals sums a segment whatever its length (a row does not
+               depend on what else is in the shard), then the six columns per (frame, pair) */
+            sasa::TrajPairArgs &xa = L.xa; /* (n_frames, side_off: shard_upload's) */
+            xa.ctot = (const double *)c->h_totals.p; xa.inpair = (const double *)c->if_inpair.p; xa.out = (double *)c->h_gtot.p + T.x0[OUT_PAIR] * nf;
+            if (kl_segment_sums((const double *)c->h_sasa.p, xa.side_off, (int)(2 * T.K * nf), false, (double *)c->if_inpair.p, c->stream) != hipSuccess ||
+                kl_traj_pair_rows(xa, c->stream) != hipSuccess)
+                return ctx_fail(c, "launch of the pairs' sums failed");
+        }
     }
     /* (file output only) per-atom areas narrowed on the device: half the bytes over PCIe and into the file */
     const bool narrow = out[OUT_SASA].deliver() && T.io.out_f32();
@@ -810,7 +916,8 @@ static int trajectory_mem_topo(const double *xyz_frames, int n_frames, const fre
                                double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
                                double *sel_area_out, long long *sel_atoms_out, double *group_areas_out, double *iso_out, double *volumes_out,
                                uint32_t *masks_out, const int *devices, int n_devices,
-                               int stats, double *stats_out, double *partials_out, char *err_out, int err_len)
+                               int stats, double *stats_out, double *partials_out, char *err_out, int err_len,
+                               const int32_t *pairs = nullptr, int n_pairs = 0, double *pair_areas_out = nullptr)
 {
     if (err_out && err_len > 0) err_out[0] = 0;
     return guarded(err_out, err_len, [&]() -> int {
@@ -819,15 +926,17 @@ static int trajectory_mem_topo(const double *xyz_frames, int n_frames, const fre
         if (stats_check(stats, &tp, sel != nullptr, group != nullptr, err_out, err_len)) return -1;
         if (stats && !stats_out) return set_err(err_out, err_len, "statistics are asked for but have nowhere to go (stats_out is NULL)");
         /* (statistics of either group output make the groups' areas wanted: their kernels run) */
-        if (group_make(group, n_groups, group_areas_out || (stats & (FREESASA_GPU_STATS_GROUPS | FREESASA_GPU_STATS_ISOLATED)),
+        /* (... and so do interface pairs: a row's isolated areas are the groups') */
+        if (group_make(group, n_groups, group_areas_out || pairs || (stats & (FREESASA_GPU_STATS_GROUPS | FREESASA_GPU_STATS_ISOLATED)),
                        iso_out || (stats & FREESASA_GPU_STATS_ISOLATED), &tp, err_out, err_len)) return -1;
+        pair_make(pairs, n_pairs, &tp);
         if (!xyz_frames || !totals_out) return set_err(err_out, err_len, "null argument");
         if ((sel_area_out || sel_atoms_out) && !sel) return set_err(err_out, err_len, "selection outputs need a selection set");
         TrajSpec s = {tp.radii, tp.n, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, &tp};
         if (traj_check_args(s, "n_frames must be > 0", err_out, err_len) || traj_shard_size(s, frame_atoms, err_out, err_len)) return -1;
         TrajIO io;
         io.src.open_memory(xyz_frames, (size_t)frame_atoms); io.sel_atoms = sel_atoms_out;
-        void *const mem[N_OUT] = {totals_out, sasa_out, iso_out, masks_out, class_sums_out, residues_out, sel_area_out, group_areas_out, volumes_out};
+        void *const mem[N_OUT] = {totals_out, sasa_out, iso_out, masks_out, class_sums_out, residues_out, sel_area_out, group_areas_out, pair_areas_out, volumes_out};
         for (int k = 0; k < N_OUT; ++k) io.out[k].mem = mem[k];
         io.stats = stats;
         return traj_run_mem(io, s, stats_out, partials_out, err_out, err_len);
@@ -846,6 +955,23 @@ extern "C" int freesasa_gpu_trajectory_groups_stats(const double *xyz_frames, in
     return trajectory_mem_topo(xyz_frames, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups, alg, probe, resolution,
                                frames_per_batch, totals_out, sasa_out, class_sums_out, residues_out, sel_area_out, sel_atoms_out, group_areas_out, iso_out,
                                nullptr, nullptr, devices, n_devices, stats, stats_out, partials_out, err_out, err_len);
+}
+
+/* the groups' run with the interfaces between the pairs of groups the caller names: six doubles per frame and pair */
+extern "C" int freesasa_gpu_trajectory_interfaces(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
+                                                  int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
+                                                  const int32_t *group, int n_groups,
+                                                  int alg, double probe, int resolution, int frames_per_batch,
+                                                  double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
+                                                  double *sel_area_out, long long *sel_atoms_out, double *group_areas_out, double *iso_out,
+                                                  const int *devices, int n_devices,
+                                                  int stats, double *stats_out, double *partials_out,
+                                                  const int32_t *pairs, int n_pairs, double *pair_areas_out, char *err_out, int err_len)
+{
+    if (pair_check(group, n_groups, pairs, n_pairs, 0, pair_areas_out, err_out, err_len)) return -1;
+    return trajectory_mem_topo(xyz_frames, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups, alg, probe, resolution,
+                               frames_per_batch, totals_out, sasa_out, class_sums_out, residues_out, sel_area_out, sel_atoms_out, group_areas_out, iso_out,
+                               nullptr, nullptr, devices, n_devices, stats, stats_out, partials_out, err_out, err_len, pairs, n_pairs, pair_areas_out);
 }
 
 /* what both volume entries refuse before a device is touched or a file opened: 0, or -1 with the message */
@@ -935,7 +1061,8 @@ extern "C" int freesasa_gpu_trajectory_topology(const double *xyz_frames, int n_
    time and a checksum of the radii - NOT the devices: a run interrupted on eight GPUs may be finished on one, with the same
    files byte for byte.  With a topology, in front of the line's end, what its outputs depend on: digests of the index, of
    residue boundaries + classes + backbone flags, of the selection set's program, and which result files the run writes; with
-   chain groups, behind that, a digest of the group count and the ids; with run statistics, last, the word as stats=.  The f32= word:
+   chain groups, behind that, a digest of the group count and the ids; with interface pairs, behind that, a digest of the pair count
+   and the pairs; with run statistics, last, the word as stats=.  The f32= word:
    the frame source's bits (the input's format, periodic images) and bit 1, fp32 per-atom output; header_bytes=: the byte of frame 0. */
 static int traj_done_head(char *head, size_t cap, const TrajSpec &s, const TrajIO &io, const struct stat &st)
 {
@@ -961,6 +1088,9 @@ static int traj_done_head(char *head, size_t cap, const TrajSpec &s, const TrajI
         /* ... and with chain groups a digest of G and the ids (a run without groups keeps the line it had) */
         if (tp->group && len > 0 && len < (int)cap)
             len += snprintf(head + len - 1, cap - (size_t)len + 1, " groups=%016llx\n", fnv1a(tp->group, 4 * (size_t)tp->n, fnv1a(&tp->n_groups, sizeof tp->n_groups))) - 1;
+        /* ... and with interface pairs a digest of K and the pairs (a run without pairs keeps the line it had) */
+        if (tp->pairs && len > 0 && len < (int)cap)
+            len += snprintf(head + len - 1, cap - (size_t)len + 1, " pairs=%016llx\n", fnv1a(tp->pairs, 8 * (size_t)tp->n_pairs, fnv1a(&tp->n_pairs, sizeof tp->n_pairs))) - 1;
     }
     /* ... and with run statistics the word (a run without statistics keeps the line it had) */
     if (io.stats && len > 0 && len < (int)cap) len += snprintf(head + len - 1, cap - (size_t)len + 1, " stats=%d\n", io.stats) - 1;
@@ -995,6 +1125,7 @@ static int trajectory_file_run(const char *frames_path, int frames_f32, long lon
         const int fpb = s.frames_per_batch;
         if (io.list.read(done_path, head, (s.n_frames + fpb - 1) / fpb, [fpb](long long k, long long f0, long long) { return f0 == k * fpb; }) == DoneList::REFUSED)
             return set_err(err_out, err_len, io.stats ? "the done-list belongs to a run with other parameters, radii, topology, outputs, statistics or frame file"
+                                           : s.topo && s.topo->pairs ? "the done-list belongs to a run with other parameters, radii, topology, selections, chain groups, interface pairs, outputs or frame file"
                                            : s.topo && s.topo->group ? "the done-list belongs to a run with other parameters, radii, topology, selections, chain groups, outputs or frame file"
                                            : s.topo ? "the done-list belongs to a run with other parameters, radii, topology, selections, outputs or frame file"
                                                     : "the done-list belongs to a run with other parameters, radii or frame file");
@@ -1076,20 +1207,22 @@ static int trajectory_file_topo(const char *frames_path, int frames_f32, long lo
                                 const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
                                 const char *group_areas_path, const char *iso_path, const char *volumes_path, const char *masks_path,
                                 const char *done_path, long long max_new_shards, const int *devices, int n_devices,
-                                long long *frames_total_out, int stats, const char *stats_path, const char *partials_path, char *err_out, int err_len)
+                                long long *frames_total_out, int stats, const char *stats_path, const char *partials_path, char *err_out, int err_len,
+                                const int32_t *pairs = nullptr, int n_pairs = 0, const char *pair_areas_path = nullptr)
 {
     if (err_out && err_len > 0) err_out[0] = 0;
     return guarded(err_out, err_len, [&]() -> int {
         TrajTopo tp; /* (outlives the run: the lanes upload from it) */
         if (topo_make(batch, structure, frame_atoms, atom_index, sel, &tp, err_out, err_len)) return -1;
         if (stats_check(stats, &tp, sel != nullptr, group != nullptr, err_out, err_len)) return -1;
-        if (group_make(group, n_groups, group_areas_path || (stats & (FREESASA_GPU_STATS_GROUPS | FREESASA_GPU_STATS_ISOLATED)),
+        if (group_make(group, n_groups, group_areas_path || pairs || (stats & (FREESASA_GPU_STATS_GROUPS | FREESASA_GPU_STATS_ISOLATED)),
                        iso_path || (stats & FREESASA_GPU_STATS_ISOLATED), &tp, err_out, err_len)) return -1;
+        pair_make(pairs, n_pairs, &tp);
         if ((sel_area_path || sel_atoms_out) && !sel) return set_err(err_out, err_len, "selection outputs need a selection set");
         TrajSpec s = {tp.radii, tp.n, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, &tp, max_new_shards};
         TrajIO io;
         io.sel_atoms = sel_atoms_out;
-        const char *const path[N_OUT] = {totals_path, sasa_path, iso_path, masks_path, class_sums_path, residues_path, sel_area_path, group_areas_path, volumes_path};
+        const char *const path[N_OUT] = {totals_path, sasa_path, iso_path, masks_path, class_sums_path, residues_path, sel_area_path, group_areas_path, pair_areas_path, volumes_path};
         for (int k = 0; k < N_OUT; ++k) io.out[k].path = path[k];
         io.stats = stats; io.stats_path = stats_path; io.parts_path = partials_path;
         return trajectory_file_run(frames_path, frames_f32, header_bytes, s, io, done_path, frames_total_out, err_out, err_len);
@@ -1119,6 +1252,27 @@ extern "C" int freesasa_gpu_trajectory_file_groups_stats(const char *frames_path
                                 alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
                                 sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
                                 frames_total_out, stats, stats_path, partials_path, err_out, err_len);
+}
+
+/* ... with the interfaces between the pairs of groups the caller names, six doubles per frame and pair into their own file */
+extern "C" int freesasa_gpu_trajectory_file_interfaces(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
+                                                       const freesasa_ingest_batch *batch, int structure,
+                                                       int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
+                                                       const int32_t *group, int n_groups,
+                                                       int alg, double probe, int resolution, int frames_per_batch,
+                                                       const char *totals_path, const char *sasa_path, const char *class_sums_path,
+                                                       const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
+                                                       const char *group_areas_path, const char *iso_path,
+                                                       const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                                       long long *frames_total_out,
+                                                       int stats, const char *stats_path, const char *partials_path,
+                                                       const int32_t *pairs, int n_pairs, const char *pair_areas_path, char *err_out, int err_len)
+{
+    if (pair_check(group, n_groups, pairs, n_pairs, frames_f32, pair_areas_path, err_out, err_len)) return -1;
+    return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,
+                                alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
+                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
+                                frames_total_out, stats, stats_path, partials_path, err_out, err_len, pairs, n_pairs, pair_areas_path);
 }
 
 extern "C" int freesasa_gpu_trajectory_file_groups(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,

@@ -1192,6 +1192,43 @@ hipError_t kl_traj_group_totals(const TrajGroupArgs &a, hipStream_t st)
     return hipGetLastError();
 }
 
+/* ... interfaces between chain groups per frame (traj_kernels.h): the pair structures' radii and the sides' boundaries (once per
+   lane and shard length, one launch call), their coordinates in front of the engine; one row per (frame, pair) behind the side
+   sums.  Workgroups and grids as the groups' kernels above: a thread per element, TRAJ_B a workgroup. */
+__global__ __launch_bounds__(TRAJ_B) void k_traj_pair_radii(TrajPairArgs a)
+{
+    traj_pair_radii(a, (int64_t)blockIdx.x * TRAJ_B + threadIdx.x);
+}
+__global__ __launch_bounds__(TRAJ_B) void k_traj_pair_sides(TrajPairArgs a)
+{
+    traj_pair_sides(a, (int64_t)blockIdx.x * TRAJ_B + threadIdx.x);
+}
+__global__ __launch_bounds__(TRAJ_B) void k_traj_pair_gather(TrajPairArgs a)
+{
+    traj_pair_gather(a, (int64_t)blockIdx.x * TRAJ_B + threadIdx.x);
+}
+__global__ __launch_bounds__(TRAJ_B) void k_traj_pair_rows(TrajPairArgs a)
+{
+    traj_pair_rows(a, (int64_t)blockIdx.x * TRAJ_B + threadIdx.x);
+}
+hipError_t kl_traj_pair_radii(const TrajPairArgs &a, hipStream_t st)
+{
+    if (a.n_pair) hipLaunchKernelGGL(k_traj_pair_radii, dim3(traj_group_grid((int64_t)a.n_frames * a.n_pair)), dim3(TRAJ_B), 0, st, a);
+    hipLaunchKernelGGL(k_traj_pair_sides, dim3(traj_group_grid(2 * (int64_t)a.n_frames * a.n_pairs + 1)), dim3(TRAJ_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_traj_pair_gather(const TrajPairArgs &a, hipStream_t st)
+{
+    if (a.n_pair == 0) return hipSuccess; /* (every side empty: nothing behind the isolated structures) */
+    hipLaunchKernelGGL(k_traj_pair_gather, dim3(traj_group_grid(3 * (int64_t)a.n_frames * a.n_pair)), dim3(TRAJ_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_traj_pair_rows(const TrajPairArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_traj_pair_rows, dim3(traj_group_grid((int64_t)a.n_frames * a.n_pairs)), dim3(TRAJ_B), 0, st, a);
+    return hipGetLastError();
+}
+
 /* ... run statistics (traj_kernels.h): a shard's partial, one thread per column, one launch for every output asked for.  Workgroups
    of one wave: a shard of 10^4 columns still spreads over 157 compute units, and a thread's frame loop is serial by definition */
 #define TRAJ_STAT_B 64

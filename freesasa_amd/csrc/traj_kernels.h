@@ -12,6 +12,7 @@
  *   traj_class_phase0  the three class sums of every frame, as class_phase0 / class_phase1
  *   traj_sel_phase0/1  the selection areas of every frame, as sel_sums_phase0 / sel_sums_phase1 (select_kernels.h)
  *   traj_group_*       chain groups per frame: the isolated structures behind the frames, as group_kernels.h
+ *   traj_pair_*        interfaces between chain groups per frame: the pair structures behind the isolated ones, six doubles a pair
  *   traj_stats         run statistics: a shard's partial (mean, M2, min, max) of every column of the outputs asked for (at the end)
  *
  * Atom i of frame f is element f * n + i of the shard's per-atom areas and reads the per-topology arrays at i.  Every sum
@@ -323,6 +324,104 @@ SASA_D void traj_group_totals(const TrajGroupArgs &a, int64_t t)
     a.out[3 * t] = t0;
     a.out[3 * t + 1] = t1;
     a.out[3 * t + 2] = t0 - t1;
+}
+
+/* ------------------------------------------------------------------ interfaces between chain groups per frame
+ * (freesasa_gpu_trajectory_interfaces / _trajectory_file_interfaces): the groups' run with, behind the isolated structures, the
+ * PAIR STRUCTURE of every pair (g, h) the caller names, g < h - group g's atoms in input order, then group h's - of every frame.
+ * The pairs are the same for every frame: the host makes pfirst, pside and psrc once per run (traj_pair_cut), a lane uploads
+ * them once.  The combined batch of a shard of nf frames, with n_pair = the sum over the pairs of |g| + |h|:
+ *
+ *     atoms  [0, nf n)                                   the nf complex frames                            } as the groups'
+ *            nf n + f n_iso + gfirst[g] ...              the isolated structure of group g of frame f     } run has them
+ *            nf (n + n_iso) + f n_pair + pfirst[k] ...   the pair structure of pair k of frame f: side g, then side h
+ *     structures  f | nf + f G + g | nf (1 + G) + f K + k
+ *
+ * There is no contact screen: a pair that does not touch in a frame has its structure and its row all the same.  Behind the
+ * engine a side's area in the pair is the sum of its atoms' areas in the order of totals_phase0 / totals_phase1 (k_totals over
+ * the 2 K nf sides, which are consecutive in the batch: side_off), whatever the side's size; the row of (frame, pair) is the
+ * six doubles of iface_finish_row (iface_kernels.h).  No float atomics, no workgroup waits for another. */
+
+struct TrajPairArgs {
+    int n, n_iso, n_pair;     /* atoms of the topology, of a frame's isolated structures, of a frame's pair structures */
+    int n_groups, n_pairs;    /* G, K */
+    int n_frames;             /* frames of this shard */
+    const int32_t *pairs;     /* [2 K] g, h of every pair */
+    const int64_t *pside;     /* [2 K + 1] where every side begins within a frame's pair part: pside[2 k] = pfirst[k] */
+    const int32_t *psrc;      /* [n_pair] topology atom of every pair-structure atom */
+    const double *radii;      /* [n] the topology's radii */
+    double *xyz;              /* [3 n_frames (n + n_iso + n_pair)] the combined batch: the compact frames first (gather: in and out) */
+    double *cradii;           /* [n_frames (n + n_iso + n_pair)] its per-atom radii */
+    int64_t *side_off;        /* [2 K n_frames + 1] where every side of the shard begins in the combined batch */
+    const double *ctot;       /* [n_frames (1 + G + K)] the engine's totals per combined structure */
+    const double *inpair;     /* [2 K n_frames] every side's area in its pair structure */
+    double *out;              /* [n_frames K 6] iso_g, iso_h, in_pair_g, in_pair_h, buried_g, buried_h */
+};
+
+/* The pairs' cut, on the host, once per run, from the groups' (traj_group_cut): pfirst [K + 1] (prefix of the pair structures'
+   atom counts), pside [2 K + 1] (every side's begin, pside[2 K] = n_pair) and psrc [n_pair].  Returns n_pair.  The pairs are
+   checked by the caller (0 <= g < h < G). */
+inline int64_t traj_pair_cut(const int32_t *pairs, int n_pairs, const int64_t *gfirst, const int32_t *src, int64_t *pfirst, int64_t *pside,
+                             int32_t *psrc)
+{
+    int64_t m = 0;
+    for (int k = 0; k < n_pairs; ++k) {
+        pfirst[k] = m;
+        for (int q = 0; q < 2; ++q) {
+            const int g = pairs[2 * k + q];
+            pside[2 * k + q] = m;
+            for (int64_t j = gfirst[g]; j < gfirst[g + 1]; ++j) {
+                if (psrc) psrc[m] = src[j];
+                ++m;
+            }
+        }
+    }
+    pfirst[n_pairs] = pside[2 * n_pairs] = m;
+    return m;
+}
+
+/* traj_pair_radii, one thread per pair-structure atom of the shard: n_frames copies of the n_pair permuted radii behind the
+   groups' part.  Once per lane and shard length, like traj_group_radii. */
+SASA_D void traj_pair_radii(const TrajPairArgs &a, int64_t t)
+{
+    if (t >= (int64_t)a.n_frames * a.n_pair) return;
+    a.cradii[(int64_t)a.n_frames * ((int64_t)a.n + a.n_iso) + t] = a.radii[a.psrc[t % a.n_pair]];
+}
+
+/* traj_pair_sides, one thread per boundary (2 K n_frames + 1): side j of frame f begins at nf (n + n_iso) + f n_pair + pside[j];
+   the last boundary is f = n_frames, j = 0.  Once per lane and shard length, with the radii. */
+SASA_D void traj_pair_sides(const TrajPairArgs &a, int64_t t)
+{
+    const int64_t per = 2 * (int64_t)a.n_pairs;
+    if (t > per * a.n_frames) return;
+    const int64_t f = t / per;
+    a.side_off[t] = (int64_t)a.n_frames * ((int64_t)a.n + a.n_iso) + f * a.n_pair + a.pside[t - f * per];
+}
+
+/* traj_pair_gather, one thread per COORDINATE of the pair part (3 n_frames n_pair): consecutive lanes write consecutive doubles
+   behind the isolated structures and read the compact frames through psrc (three lanes share an atom): traj_group_gather's shape. */
+SASA_D void traj_pair_gather(const TrajPairArgs &a, int64_t t)
+{
+    if (t >= 3 * (int64_t)a.n_frames * a.n_pair) return;
+    const int64_t atom = t / 3;
+    const int comp = (int)(t - 3 * atom);
+    const int64_t f = atom / a.n_pair;
+    const int j = (int)(atom - f * a.n_pair);
+    a.xyz[3 * (int64_t)a.n_frames * ((int64_t)a.n + a.n_iso) + t] = a.xyz[3 * (f * a.n + a.psrc[j]) + comp];
+}
+
+/* traj_pair_rows, one thread per (frame, pair): iface_finish_row's six doubles - the isolated totals are the engine's totals of
+   the frame's isolated structures (column 0 of the groups' output), buried = isolated - in the pair, one subtraction */
+SASA_D void traj_pair_rows(const TrajPairArgs &a, int64_t t)
+{
+    if (t >= (int64_t)a.n_frames * a.n_pairs) return;
+    const int64_t f = t / a.n_pairs;
+    const int k = (int)(t - f * a.n_pairs);
+    const double *iso = a.ctot + a.n_frames + f * a.n_groups;
+    const double ig = iso[a.pairs[2 * k]], ih = iso[a.pairs[2 * k + 1]];
+    const double pg = a.inpair[2 * t], ph = a.inpair[2 * t + 1];
+    double *o = a.out + 6 * t;
+    o[0] = ig; o[1] = ih; o[2] = pg; o[3] = ph; o[4] = ig - pg; o[5] = ih - ph;
 }
 
 /* ------------------------------------------------------------------ run statistics

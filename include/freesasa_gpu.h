@@ -466,8 +466,8 @@ void freesasa_gpu_group_table_free(freesasa_gpu_group_table *table);
    in their file with their labels.
    The table's arrays are ONE block, released by freesasa_gpu_interface_table_free only (which zeroes the struct; a zeroed struct
    is a no-op); on any failure (-1, message in err) both tables are zeroed and nothing is kept.
-   Not offered: a done-list / resumable form, the cache sweep, contact tables in the sweep, interfaces in the trajectory drivers
-   and among periodic images. */
+   Not offered: a done-list / resumable form, the cache sweep, contact tables in the sweep, interfaces among periodic images
+   (interfaces per frame of a trajectory: freesasa_gpu_trajectory_interfaces below). */
 #define FREESASA_GPU_EIFACE_GROUPS 100 /* (no FREESASA_INGEST_* status: those are 0 .. 8) */
 typedef struct freesasa_gpu_interface_table {
     int32_t n_files;
@@ -1069,6 +1069,58 @@ int freesasa_gpu_trajectory_file_groups_periodic(const char *frames_path, int fr
                                                  const char *done_path, long long max_new_shards, const int *devices, int n_devices,
                                                  long long *frames_total_out,
                                                  int stats, const char *stats_path, const char *partials_path, char *err, int err_len);
+/* INTERFACES BETWEEN CHAIN GROUPS over a trajectory: with three or more groups a group's buried area in the groups' run is the
+   sum over all its partners; these entries say which partner buries how much, per frame.  They are
+   freesasa_gpu_trajectory_groups_stats / _file_groups_stats - the arguments, the outputs, the statistics word, the done-list -
+   with, in front of err,
+     pairs, n_pairs     pairs [K, 2] int32: the pairs (g, h) of group numbers, 0 <= g < h < n_groups, every pair at most once,
+                        K >= 1; constant over the run.  A pair may name an empty group.
+     pair areas         6 K per frame (8 * 6 K f): per pair (iso_g, iso_h, in_pair_g, in_pair_h, buried_g, buried_h), the six
+                        doubles and the order of freesasa_gpu_interfaces_dev's pair_areas (below).  Required.
+   group is required; the group areas may be NULL here.  Per frame f and pair k:
+     iso_*      column 0 of the frame's group areas of that group, bit for bit.
+     in_pair_*  the PAIR STRUCTURE of (g, h) is group g's atoms in input order, then group h's; every atom's area in it is the
+                plain entry's (freesasa_gpu_calc_batch) on that structure cut on the host, bit for bit; a side's in_pair is the
+                sum of its atoms' areas in the order of the per-structure totals kernel: 256 contiguous runs of
+                ceil(len / 256) atoms, each added in atom order from 0, then the runs added in order from 0 - whatever the
+                side's size, so a row does not depend on what else is in the shard.
+     buried_*   iso_* - in_pair_*, one subtraction.
+   There is NO CONTACT SCREEN: a pair that does not touch in a frame still has its row.  Its in_pair is then the same terms as
+   its iso added in possibly another order: buried is 0 or rounding noise, |buried| <= N * 2^-53 * iso with N the side's atom
+   count.  An empty side's three columns are 0.
+   Per shard ONE batch goes through the engine: behind the frames and their isolated groups every pair structure of every frame
+   (csrc/traj_kernels.h has the layout): n + n_iso + n_pair atoms and 1 + G + K structures per frame, n_pair the sum over the
+   pairs of |g| + |h|.  frames_per_batch <= 0 goes by that sum where it exceeds frame_atoms: 1250000 / max + 1; frames_per_batch
+   times that sum, and times 1 + G + K, must not exceed 2^30.  Every output these entries share with the groups' run is bit for
+   bit what that run gives; the run statistics of the other outputs work beside the pairs.
+   The done-list's first line carries bit 256 in outputs= and, behind groups=, pairs=<digest of K and the pairs>: a list written
+   for other pairs, or without them, is refused.
+   Argument errors, -1 with a message before a device is touched or a file opened: group NULL, n_pairs < 1, pairs or the pair
+   areas NULL, a pair with g >= h or an id out of [0, n_groups) (the message names the pair's index), a pair named twice (it names
+   both indices), bit 3 or bit 4 of frames_f32.
+   Not offered: a contact screen per frame, per-atom or per-residue buried areas per pair, contact tables, interfaces among
+   periodic images, run statistics of the pair columns, group ids made on the device, more than two groups per interface. */
+int freesasa_gpu_trajectory_interfaces(const double *xyz_frames, int n_frames, const struct freesasa_ingest_batch *batch, int structure,
+                                       int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
+                                       const int32_t *group, int n_groups,
+                                       int alg, double probe_radius, int resolution, int frames_per_batch,
+                                       double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
+                                       double *sel_area_out, long long *sel_atoms_out, double *group_areas_out, double *iso_out,
+                                       const int *devices, int n_devices,
+                                       int stats, double *stats_out, double *partials_out,
+                                       const int32_t *pairs, int n_pairs, double *pair_areas_out /* [F, K, 6] */, char *err, int err_len);
+int freesasa_gpu_trajectory_file_interfaces(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
+                                            const struct freesasa_ingest_batch *batch, int structure,
+                                            int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
+                                            const int32_t *group, int n_groups,
+                                            int alg, double probe_radius, int resolution, int frames_per_batch,
+                                            const char *totals_path, const char *sasa_path, const char *class_sums_path,
+                                            const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
+                                            const char *group_areas_path, const char *iso_path,
+                                            const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                            long long *frames_total_out,
+                                            int stats, const char *stats_path, const char *partials_path,
+                                            const int32_t *pairs, int n_pairs, const char *pair_areas_path, char *err, int err_len);
 /* W of a statistics word for a system of n_atoms atoms, n_res residues, n_sel selections and n_groups groups; first_out (may be
    NULL) [7] receives the first column of every output in the order above, -1 for one whose bit is not set.  -1: an unknown bit
    or a negative count.  (csrc/trajstats.c: plain C, no allocation, no GPU call.) */
@@ -1265,8 +1317,8 @@ int freesasa_gpu_calc_interfaces(const double *xyz, const double *radii, const i
      NULL or n_res <= 0; res_first[0] != 0, a decreasing entry, res_first[n_res] != offsets[n_structs]; a residue that spans
      a structure boundary (the message names residue and structures); min_buried negative, NaN or infinite; res_capacity < 0.
    One stream synchronization more than freesasa_gpu_interfaces_dev (R comes back to the host before delivery).
-   Not offered: class splits (polar / apolar / main chain) of the buried area per residue, relative buried areas, interfaces
-     in the trajectory drivers, interfaces among periodic images, a per-atom contact criterion by distance.  (In the file sweep,
+   Not offered: class splits (polar / apolar / main chain) of the buried area per residue, relative buried areas, per-residue
+     tables in the trajectory drivers, interfaces among periodic images, a per-atom contact criterion by distance.  (In the file sweep,
      with the buried area of every side split by class: freesasa_gpu_sweep_files_interfaces above.)
 
    freesasa_gpu_interface_residues_dev: d_res_areas is required, d_res_offsets, d_res_index, d_res_atoms may be NULL; the rest

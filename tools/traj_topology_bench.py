@@ -75,9 +75,18 @@ what a caller who wants the averages over the run can do, interleaved:
               the device shard by shard (k_traj_stats), 4 W doubles per shard down
 each line with the bytes of results per frame; the stats arm's per-atom means must be those of the stream arm's file to rounding.
 
+With --groups (without --pbc) the solute is the same globule labelled as four chains A, B, C, D of 500 residues (2 500 atoms), in the
+same solvated frames, and the arms are, interleaved, totals and the named outputs only:
+    groups      trajectory_file_topology with separate_chains=True: isolated, complex, buried of the four chains per frame
+    interfaces  (with --interfaces beside it) the same with interface_pairs="all": the six pairs' rows per frame as well
+each line with frames_per_batch, the shards of the run and the median time per shard, and engine_atoms_per_frame: the atoms of a
+frame, of its isolated groups and of its pair structures that go through the engine (n + n_iso + n_pair).  --kernel-stats FILE: a
+`rocprofv3 --kernel-trace --stats` kernel-stats CSV of a run of this mode; the share of the kernels the pairs add (k_traj_pair_*
+and k_totals, which sums the sides) in the kernel time of the whole trace goes into the interfaces line as new_kernels_share.
+
 One JSON line per arm: atom-frames/s counted in SOLUTE atoms and in frame atoms, the median and the spread of --reps runs.
 
-    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd] [--netcdf] [--pbc [--pbc-arms all|off] [--triclinic] [--groups]] [--xtc [--xtc-distinct 24] [--xtc-fpb 0]] [--trr [--double] [--trr-arms raw,trr]] [--stats]
+    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd] [--netcdf] [--pbc [--pbc-arms all|off] [--triclinic] [--groups]] [--xtc [--xtc-distinct 24] [--xtc-fpb 0]] [--trr [--double] [--trr-arms raw,trr]] [--stats] [--groups [--interfaces] [--kernel-stats FILE]]
 
 For the kernel times: `rocprofv3 --kernel-trace --stats -- python tools/traj_topology_bench.py --reps 1 --arms all`
 (k_traj_gather / k_traj_residues / k_traj_class / k_traj_sel are the topology's kernels, k_traj_group_* the groups')."""
@@ -104,15 +113,17 @@ EIGHT = ["bb, name n+ca+c+o", "cb, name cb", "r, resi 10-200 and not symbol c", 
          "o, symbol o", "n, symbol n and resi 500-1500", "none, resn gly"]
 
 
-def solute():
-    """a poly-alanine of 2000 residues on the positions of tools.globule: (batch of one structure, xyz [n, 3])"""
+def solute(n_chains=1):
+    """a poly-alanine of 2000 residues on the positions of tools.globule: (batch of one structure, xyz [n, 3]); n_chains: the
+    residues labelled as that many chains A, B, ... of equal length"""
     xyz, _ = tools.globule(N_SOLUTE, 11)
     xyz = xyz - xyz.mean(0)
     names = [(" N  ", "N"), (" CA ", "C"), (" C  ", "C"), (" O  ", "O"), (" CB ", "C")]
     lines = []
     for i, (x, y, z) in enumerate(xyz):
         nm, el = names[i % 5]
-        lines.append("ATOM  %5d %s ALA A%4d    %8.3f%8.3f%8.3f  1.00  0.00          %2s" % ((i + 1) % 100000, nm, i // 5 + 1, x, y, z, el))
+        lines.append("ATOM  %5d %s ALA %s%4d    %8.3f%8.3f%8.3f  1.00  0.00          %2s" % ((i + 1) % 100000, nm, "ABCDEFGH"[i * n_chains // N_SOLUTE], i // 5 + 1,
+                                                                                          x, y, z, el))
     b = ingest.load_pdb_texts(["\n".join(lines) + "\nEND\n"])
     assert b.status[0] == 0 and b.n_atoms == N_SOLUTE and b.n_residues == N_SOLUTE // 5
     return b, b.xyz.copy()
@@ -379,6 +390,65 @@ def stats_mode(args, scratch):
     return lines
 
 
+def new_kernels_share(path):
+    """the share of k_traj_pair_* and k_totals in the kernel time of a rocprofv3 kernel-stats CSV (columns Name, ..., TotalDurationNs)"""
+    import csv
+    new = total = 0.0
+    with open(path, newline="") as fh:
+        for row in csv.DictReader(fh):
+            ns = float(row["TotalDurationNs"])
+            total += ns
+            name = row["Name"].split("(")[0]
+            if name.startswith("k_traj_pair_") or name == "k_totals":
+                new += ns
+    return new / total if total else None
+
+
+def groups_mode(args, scratch):
+    """the arms of --groups [--interfaces] -> the JSON lines"""
+    b, xyz = solute(4)
+    full = make_frames(scratch, xyz, args.frames)[0]
+    index = np.arange(N_SOLUTE, dtype=np.int32)
+    p = lambda k: os.path.join(scratch, k)
+    kw = dict(atom_index=index, frame_atoms=N_FRAME, f32=True, separate_chains=True)
+    arms = {"groups": lambda: fa.trajectory_file_topology(full, b, p("t0"), group_areas_path=p("g0"), **kw)}
+    if args.interfaces:
+        arms["interfaces"] = lambda: fa.trajectory_file_topology(full, b, p("t1"), group_areas_path=p("g1"), interface_pairs="all",
+                                                                 pair_areas_path=p("p1"), **kw)
+    ids, ng, _ = b.chain_groups(separate_chains=True)
+    G = int(ng[0])
+    assert G == 4 and np.array_equal(np.bincount(ids), [N_SOLUTE // 4] * 4)
+    K, n_pair = G * (G - 1) // 2, (G - 1) * N_SOLUTE
+    runs = {a: [] for a in arms}
+    for a in arms:
+        arms[a]()                                                        # warm-up: contexts, staging, page cache
+    for _ in range(args.reps):
+        for a in arms:
+            t0 = time.perf_counter()
+            res = arms[a]()
+            runs[a].append(time.perf_counter() - t0)
+            assert res[0] and res[1] == args.frames
+    if args.interfaces:
+        assert np.array_equal(np.fromfile(p("t1")), np.fromfile(p("t0"))) and np.array_equal(np.fromfile(p("g1")), np.fromfile(p("g0")))
+        rows, areas = np.fromfile(p("p1")).reshape(args.frames, K, 6), np.fromfile(p("g0")).reshape(args.frames, G, 3)
+        assert np.array_equal(rows[:, 0, 0], areas[:, 0, 0]) and np.array_equal(rows[:, K - 1, 1], areas[:, G - 1, 0]) and np.all(rows[:, :, 4:] >= -1e-6)
+    lines = []
+    for a in arms:
+        v = sorted(runs[a])
+        med = v[len(v) // 2]
+        engine = 2 * N_SOLUTE + (n_pair if a == "interfaces" else 0)
+        fpb = 1250000 // max(N_FRAME, engine) + 1                        # (the driver's default: include/freesasa_gpu.h)
+        shards = -(-args.frames // fpb)
+        line = {"arm": a, "frames": args.frames, "frame_atoms": N_FRAME, "solute_atoms": N_SOLUTE, "groups": G, "pairs": K if a == "interfaces" else 0,
+                "frames_per_batch": fpb, "shards": shards, "engine_atoms_per_frame": engine, "median_seconds": med, "min_seconds": v[0],
+                "max_seconds": v[-1], "median_ms_per_shard": 1e3 * med / shards, "solute_atom_frames_per_s": N_SOLUTE * args.frames / med,
+                "engine_atom_frames_per_s": engine * args.frames / med, "runs": len(v)}
+        if a == "interfaces" and args.kernel_stats:
+            line["new_kernels_share"] = new_kernels_share(args.kernel_stats)
+        lines.append(json.dumps(line))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=240)
@@ -392,7 +462,10 @@ def main():
     ap.add_argument("--pbc", action="store_true", help="time the DCD drivers with and without periodic images")
     ap.add_argument("--pbc-arms", default="all", choices=["all", "off"])
     ap.add_argument("--triclinic", action="store_true", help="with --pbc: the arms of the triclinic bit beside the others")
-    ap.add_argument("--groups", action="store_true", help="with --pbc: chain groups among periodic images against the plain periodic run and the non-periodic groups' run")
+    ap.add_argument("--groups", action="store_true", help="with --pbc: chain groups among periodic images against the plain periodic run and the non-periodic groups' run; "
+                                                          "without: the solute as four chains, a group each")
+    ap.add_argument("--interfaces", action="store_true", help="with --groups (without --pbc): the interfaces between all pairs of the four chains beside the groups' run")
+    ap.add_argument("--kernel-stats", default=None, help="with --groups --interfaces: a rocprofv3 kernel-stats CSV; the share of the pairs' kernels in it is reported")
     ap.add_argument("--xtc", action="store_true", help="time a GROMACS XTC file against the raw fp32 file and an AMBER NetCDF file of the same decoded frames")
     ap.add_argument("--xtc-distinct", type=int, default=24, help="with --xtc: distinct frames that are encoded and then repeated")
     ap.add_argument("--xtc-fpb", type=int, default=0, help="with --xtc: frames_per_batch of all three arms (0: the driver's default)")
@@ -403,8 +476,11 @@ def main():
     args = ap.parse_args()
     scratch = args.scratch or tempfile.mkdtemp(prefix="traj_topology_bench_")
     try:
-        if args.xtc or args.stats or args.trr:
-            lines = stats_mode(args, scratch) if args.stats else trr_mode(args, scratch) if args.trr else xtc_mode(args, scratch)
+        if args.interfaces and (args.pbc or not args.groups):
+            ap.error("--interfaces goes with --groups and without --pbc")
+        if args.xtc or args.stats or args.trr or (args.groups and not args.pbc):
+            lines = stats_mode(args, scratch) if args.stats else trr_mode(args, scratch) if args.trr else xtc_mode(args, scratch) if args.xtc \
+                else groups_mode(args, scratch)
             print("\n".join(lines))
             if args.out:
                 with open(args.out, "w") as fh:
