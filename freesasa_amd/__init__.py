@@ -1190,6 +1190,8 @@ def sweep_cache(cache_path, alg=LEE_RICHARDS, probe=1.4, resolution=20, batch_at
 
 # run statistics (include/freesasa_gpu.h, FREESASA_GPU_STATS_*): the outputs in the order of a partial's columns
 STATS_BITS = {"totals": 1, "atoms": 2, "isolated": 4, "classes": 8, "residues": 16, "selections": 32, "groups": 64}
+# ... and the two more that the interface-residue entries alone accept (FREESASA_GPU_STATS_PAIRS, _PAIR_RESIDUES), behind the groups
+PAIR_STATS_BITS = {"pairs": 128, "pair_residues": 256}
 
 
 def _stats_proto(L):
@@ -1215,16 +1217,25 @@ def _stats_proto(L):
     L.freesasa_gpu_trajectory_interfaces.argtypes = L.freesasa_gpu_trajectory_groups_stats.argtypes[:-2] + [_i32p, C.c_int, _dp, C.c_char_p, C.c_int]
     L.freesasa_gpu_trajectory_file_interfaces.argtypes = L.freesasa_gpu_trajectory_file_groups_stats.argtypes[:-2] + \
         [_i32p, C.c_int, C.c_char_p, C.c_char_p, C.c_int]
+    # ... and with their per-residue table: (min_buried, the pair residues: an array / a path) in front of err
+    L.freesasa_gpu_trajectory_interface_residues.argtypes = L.freesasa_gpu_trajectory_interfaces.argtypes[:-2] + [C.c_double, _dp, C.c_char_p, C.c_int]
+    L.freesasa_gpu_trajectory_file_interface_residues.argtypes = L.freesasa_gpu_trajectory_file_interfaces.argtypes[:-2] + \
+        [C.c_double, C.c_char_p, C.c_char_p, C.c_int]
+    L.freesasa_gpu_trajectory_interface_segments.argtypes = [C.c_void_p, C.c_int, _i32p, C.c_int, _i32p, C.c_int, C.c_longlong, _llp, _llp, _i32p,
+                                                             _i32p, C.c_char_p, C.c_int]
+    L.freesasa_gpu_traj_stats_width_pairs.argtypes = [C.c_int] + 6 * [C.c_longlong] + [_llp]
+    L.freesasa_gpu_traj_stats_width_pairs.restype = C.c_longlong
     return L
 
 
-def stats_word(stats):
-    """the FREESASA_GPU_STATS_* word of stats=("atoms", "residues", ...); None or () is 0"""
-    word = 0
+def stats_word(stats, pairs=False):
+    """the FREESASA_GPU_STATS_* word of stats=("atoms", "residues", ...); None or () is 0.  pairs: the names of PAIR_STATS_BITS
+    are known too (the interface-residue runs)"""
+    word, known = 0, dict(STATS_BITS, **PAIR_STATS_BITS) if pairs else STATS_BITS
     for name in ([stats] if isinstance(stats, str) else stats or ()):
-        if name not in STATS_BITS:
-            raise ValueError(f"unknown statistics output {name!r}: one of {', '.join(STATS_BITS)}")
-        word |= STATS_BITS[name]
+        if name not in known:
+            raise ValueError(f"unknown statistics output {name!r}: one of {', '.join(known)}")
+        word |= known[name]
     return word
 
 
@@ -1238,6 +1249,18 @@ def traj_stats_width(stats, n_atoms, n_res=0, n_sel=0, n_groups=0):
     return int(W), first
 
 
+def traj_stats_width_pairs(stats, n_atoms, n_res=0, n_sel=0, n_groups=0, n_pairs=0, n_segments=0):
+    """(W, first column of every output [9], -1: not asked for) of a statistics word or tuple of names of an interface-residue
+    run: the seven of traj_stats_width, then the pairs [6 K] and the interface residues [4 S]"""
+    word = stats if isinstance(stats, int) else stats_word(stats, pairs=True)
+    first = np.zeros(9, dtype=np.int64)
+    W = _stats_proto(lib()).freesasa_gpu_traj_stats_width_pairs(word, n_atoms, n_res, n_sel, n_groups, n_pairs, n_segments,
+                                                                first.ctypes.data_as(C.POINTER(C.c_longlong)))
+    if W < 0:
+        raise ValueError("bad statistics word or counts")
+    return int(W), first
+
+
 class RunStats(dict):
     """Run statistics of a trajectory: a dict of the outputs asked for, each [4, ...] - mean, std (population), min, max over
     the frames: totals [4], atoms [4, n], isolated [4, n], classes [4, 3], residues [4, R, 6], selections [4, S], groups
@@ -1245,11 +1268,16 @@ class RunStats(dict):
     shard) and frames [n_shards] where they were asked for, else None: traj_stats_merge(partials, frames, a, b) gives the
     statistics of shards [a, b) - block averages."""
 
-    def __init__(self, raw, stats, n_atoms, n_res=0, n_sel=0, n_groups=0, partials=None, frames=None):
-        W, first = traj_stats_width(stats, n_atoms, n_res, n_sel, n_groups)
+    def __init__(self, raw, stats, n_atoms, n_res=0, n_sel=0, n_groups=0, partials=None, frames=None, n_pairs=None, n_segments=0):
+        """n_pairs not None: the statistics of an interface-residue run, which may hold pairs [4, K, 6] and pair_residues [4, S, 4]
+        (pair_residues[0, :, 3] is the occupancy of every segment)"""
+        if n_pairs is None:
+            W, first = traj_stats_width(stats, n_atoms, n_res, n_sel, n_groups)
+        else:
+            W, first = traj_stats_width_pairs(stats, n_atoms, n_res, n_sel, n_groups, n_pairs, n_segments)
         raw = np.asarray(raw, dtype=np.float64).reshape(4, W)
-        shapes = [(), (n_atoms,), (n_atoms,), (3,), (n_res, 6), (n_sel,), (n_groups, 3)]
-        for name, at, shape in zip(STATS_BITS, first, shapes):
+        shapes = [(), (n_atoms,), (n_atoms,), (3,), (n_res, 6), (n_sel,), (n_groups, 3), (n_pairs or 0, 6), (n_segments, 4)]
+        for name, at, shape in zip(list(STATS_BITS) + list(PAIR_STATS_BITS), first, shapes):
             if at >= 0:
                 self[name] = raw[:, at:at + int(np.prod(shape, dtype=np.int64))].reshape((4,) + shape)
         self.raw, self.partials, self.frames = raw, partials, frames
@@ -1273,15 +1301,20 @@ def traj_stats_merge(parts, frames, first=0, last=None):
     return out
 
 
-def traj_stats_read(path, stats, n_atoms, n_res=0, n_sel=0, n_groups=0, partials_path=None, frames=None):
+def traj_stats_read(path, stats, n_atoms, n_res=0, n_sel=0, n_groups=0, partials_path=None, frames=None, n_pairs=None, n_segments=0):
     """The statistics file of a file run (raw fp64 [4, W]) as a RunStats; with partials_path and frames [n_shards] (the frames
-    of every shard: frames_per_batch each, the last one the rest) its partials too."""
-    W, _ = traj_stats_width(stats, n_atoms, n_res, n_sel, n_groups)
+    of every shard: frames_per_batch each, the last one the rest) its partials too.  n_pairs, n_segments: of an interface-residue
+    run (RunStats)."""
+    if n_pairs is None:
+        W, _ = traj_stats_width(stats, n_atoms, n_res, n_sel, n_groups)
+    else:
+        W, _ = traj_stats_width_pairs(stats, n_atoms, n_res, n_sel, n_groups, n_pairs, n_segments)
     raw = np.fromfile(path, dtype=np.float64)
     if raw.size != 4 * W:
         raise ValueError("the statistics file does not have 4 x W values")
     parts = None if partials_path is None else np.fromfile(partials_path, dtype=np.float64).reshape(-1, 4, W)
-    return RunStats(raw, stats, n_atoms, n_res, n_sel, n_groups, parts, None if frames is None else np.asarray(frames, dtype=np.int64))
+    return RunStats(raw, stats, n_atoms, n_res, n_sel, n_groups, parts, None if frames is None else np.asarray(frames, dtype=np.int64),
+                    n_pairs=n_pairs, n_segments=n_segments)
 
 
 def _shard_frames(n_frames, frames_per_batch):
@@ -1586,15 +1619,26 @@ class TopologyResult:
     are None.  volumes [F]: with volumes=True, the volume every frame's solvent-accessible surface encloses; None without.
     masks [F, n, 4] uint32: with masks=True, every atom's exposure mask in every frame (calc_masks); None without.
     pair_areas [F, K, 6] and pair_groups [K, 2]: with interface_pairs=, per frame and pair (g, h) of groups (iso_g, iso_h,
-    in_pair_g, in_pair_h, buried_g, buried_h) as calc_interfaces orders them; None without."""
+    in_pair_g, in_pair_h, buried_g, buried_h) as calc_interfaces orders them; None without.
+    With interface_residues=True: pair_residues [F, S, 4] - per frame and segment (iso_res, in_pair_res, buried_res, in_interface) -
+    and the segments, which are the same for every frame: pair_res_offsets [2 K + 1] (side q of pair k owns the segments
+    side_segments(k, q)), pair_res_index [S] (the residue within the structure) and pair_res_atoms [S]; None without."""
 
     def __init__(self, totals, class_sums, residues, selection_areas, selection_atoms, sasa, res_ref, group_areas=None,
-                 group_atoms=None, isolated=None, stats=None, volumes=None, masks=None, pair_areas=None, pair_groups=None):
+                 group_atoms=None, isolated=None, stats=None, volumes=None, masks=None, pair_areas=None, pair_groups=None,
+                 pair_residues=None, pair_res_offsets=None, pair_res_index=None, pair_res_atoms=None):
         self.stats, self.volumes, self.masks = stats, volumes, masks
         self.pair_areas, self.pair_groups = pair_areas, pair_groups
+        self.pair_residues, self.pair_res_offsets = pair_residues, pair_res_offsets
+        self.pair_res_index, self.pair_res_atoms = pair_res_index, pair_res_atoms
         self.totals, self.class_sums, self.residues = totals, class_sums, residues
         self.selection_areas, self.selection_atoms, self.sasa, self.res_ref = selection_areas, selection_atoms, sasa, res_ref
         self.group_areas, self.group_atoms, self.isolated = group_areas, group_atoms, isolated
+
+    def side_segments(self, k, side):
+        """the segments of side `side` (0: g, 1: h) of pair k, as a slice of the second axis of pair_residues"""
+        j = 2 * int(k) + int(side)
+        return slice(int(self.pair_res_offsets[j]), int(self.pair_res_offsets[j + 1]))
 
 
 def _topology_args(batch, structure, atom_index, frame_atoms):
@@ -1652,10 +1696,31 @@ def _interface_pairs(interface_pairs, ids, G):
     return pairs.reshape(-1, 2)
 
 
+def traj_pair_segments(batch, group, n_groups, pairs, structure=0):
+    """freesasa_gpu_trajectory_interface_segments(): the segments of an interface-residue run over structure `structure` of the
+    batch with these group ids and pairs, without a device -> (offsets [2 K + 1], residue [S], atoms [S])"""
+    L = _stats_proto(lib())
+    group = None if group is None else np.ascontiguousarray(group, dtype=np.int32)
+    pairs = None if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    K = 0 if pairs is None else pairs.shape[0]
+    cb = batch._as_c()
+    i32 = C.POINTER(C.c_int32)
+    opt = lambda a, t: None if a is None else a.ctypes.data_as(t)
+    S, err = C.c_longlong(0), C.create_string_buffer(512)
+    args = (C.byref(cb), structure, opt(group, i32), n_groups, opt(pairs, i32), K)
+    if L.freesasa_gpu_trajectory_interface_segments(*args, 1 << 62, C.byref(S), None, None, None, err, 512):
+        raise RuntimeError("freesasa_gpu_trajectory_interface_segments: " + err.value.decode())
+    offs, res, atoms = np.zeros(2 * K + 1, dtype=np.int64), np.zeros(S.value, dtype=np.int32), np.zeros(S.value, dtype=np.int32)
+    if L.freesasa_gpu_trajectory_interface_segments(*args, S.value, C.byref(S), offs.ctypes.data_as(C.POINTER(C.c_longlong)), opt(res, i32),
+                                                    opt(atoms, i32), err, 512):
+        raise RuntimeError("freesasa_gpu_trajectory_interface_segments: " + err.value.decode())
+    return offs, res, atoms
+
+
 def trajectory_topology(frames, batch, structure=0, atom_index=None, selection=None, per_atom=False, alg=LEE_RICHARDS, probe=1.4,
                         resolution=20, frames_per_batch=0, device=-1, devices=None, chain_groups=None, separate_chains=False,
                         long=False, group=None, n_groups=None, stats=None, per_frame=True, volumes=False, masks=False,
-                        interface_pairs=None):
+                        interface_pairs=None, interface_residues=False, min_buried=0.0):
     """freesasa_gpu_trajectory_topology(): frames [F, frame_atoms, 3] of a (solvated) system whose solute is structure
     `structure` of the ingest.Batch - topology atom i is frame atom atom_index[i] (None: the frames hold exactly the
     structure's atoms) - -> a TopologyResult.  The gather, the per-residue, per-class and per-selection sums run on the
@@ -1675,16 +1740,24 @@ def trajectory_topology(frames, batch, structure=0, atom_index=None, selection=N
     interface_pairs="all" or [(g, h), ...] (freesasa_gpu_trajectory_interfaces; needs chain groups; no volumes, no masks): the
     result's pair_areas [F, K, 6] holds, per frame and pair of groups g < h, (iso_g, iso_h, in_pair_g, in_pair_h, buried_g,
     buried_h) - which partner buries how much; pair_groups [K, 2] the pairs ("all": every g < h, g-major).  There is no contact
-    screen: a pair that does not touch in a frame has buried areas of 0 or rounding noise."""
+    screen: a pair that does not touch in a frame has buried areas of 0 or rounding noise.
+    interface_residues=True with interface_pairs (freesasa_gpu_trajectory_interface_residues): the result's pair_residues [F, S, 4]
+    holds, per frame and segment - the atoms of one side of a pair that lie in one residue - (iso_res, in_pair_res, buried_res,
+    in_interface = buried_res > min_buried); pair_res_offsets, pair_res_index, pair_res_atoms and side_segments(k, side) say which
+    segment is which.  stats= then also takes "pairs" and "pair_residues" (PAIR_STATS_BITS): stats["pair_residues"][0, :, 3] is
+    every segment's occupancy over the run; with per_frame=False an output named there is not delivered."""
     if interface_pairs is not None and (volumes or masks):
         raise ValueError("interface_pairs is not offered with volumes=True or masks=True")
+    if interface_residues and interface_pairs is None:
+        raise ValueError("interface_residues=True needs interface_pairs")
     if volumes and (stats or not per_frame or chain_groups is not None or separate_chains or group is not None):
         raise ValueError("volumes=True is not offered with chain groups, stats= or per_frame=False")
     if masks and (volumes or stats or not per_frame or chain_groups is not None or separate_chains or group is not None):
         raise ValueError("masks=True is not offered with chain groups, stats=, per_frame=False or volumes=True")
     if stats or not per_frame or interface_pairs is not None:
         return _trajectory_topology_stats(frames, batch, structure, atom_index, selection, per_atom, alg, probe, resolution, frames_per_batch,
-                                          device, devices, chain_groups, separate_chains, long, group, n_groups, stats, per_frame, interface_pairs)
+                                          device, devices, chain_groups, separate_chains, long, group, n_groups, stats, per_frame, interface_pairs,
+                                          interface_residues, min_buried)
     L = _topology_proto(lib())
     frames = np.ascontiguousarray(frames, dtype=np.float64)
     if frames.ndim != 3 or frames.shape[2] != 3:
@@ -1744,7 +1817,8 @@ def trajectory_topology(frames, batch, structure=0, atom_index=None, selection=N
 
 
 def _trajectory_topology_stats(frames, batch, structure, atom_index, selection, per_atom, alg, probe, resolution, frames_per_batch,
-                               device, devices, chain_groups, separate_chains, long, group, n_groups, stats, per_frame, interface_pairs=None):
+                               device, devices, chain_groups, separate_chains, long, group, n_groups, stats, per_frame, interface_pairs=None,
+                               interface_residues=False, min_buried=0.0):
     L = _stats_proto(_topology_proto(lib()))
     frames = np.ascontiguousarray(frames, dtype=np.float64)
     if frames.ndim != 3 or frames.shape[2] != 3:
@@ -1754,7 +1828,7 @@ def _trajectory_topology_stats(frames, batch, structure, atom_index, selection, 
     S = len(selection) if selection is not None else 0
     ids, G, g_atoms = _topology_groups(batch, structure, n, chain_groups, separate_chains, long, group, n_groups)
     pairs = _interface_pairs(interface_pairs, ids, G)
-    word = stats_word(stats)
+    word = stats_word(stats, pairs=bool(interface_residues))
     totals = np.zeros(F)
     cls, res = (np.zeros((F, 3)), np.zeros((F, R, 6))) if per_frame else (None, None)
     sel_area = np.zeros((F, S)) if selection is not None and per_frame else None
@@ -1770,6 +1844,27 @@ def _trajectory_topology_stats(frames, batch, structure, atom_index, selection, 
     keep, dp_, nd = _devs(devices, device)
     cb = batch._as_c()
     opt = lambda a, t=_dp: None if a is None else a.ctypes.data_as(t)
+    if pairs is not None and interface_residues:
+        # (the library's refusals of the topology, the ids and the pairs come from the segments entry first, with its messages)
+        s_offs, s_res, s_atoms = traj_pair_segments(batch, ids, G, pairs, structure)
+        K, NS = pairs.shape[0], s_res.size
+        W = L.freesasa_gpu_traj_stats_width_pairs(word, n, R, S, max(G, 0), K, NS, None)
+        raw = np.empty((4, max(W, 0)))
+        parts = None if nf is None or not word else np.empty((nf.size, 4, max(W, 0)))
+        p_areas = np.zeros((F, K, 6)) if per_frame or not word & PAIR_STATS_BITS["pairs"] else None
+        p_res = np.zeros((F, NS, 4)) if per_frame or not word & PAIR_STATS_BITS["pair_residues"] else None
+        ret = L.freesasa_gpu_trajectory_interface_residues(frames.ctypes.data_as(_dp), F, C.byref(cb), structure, fa_, opt(idx, C.POINTER(C.c_int32)),
+                                                           selection.handle if selection is not None else None, opt(ids, C.POINTER(C.c_int32)), G,
+                                                           alg, probe, resolution, frames_per_batch, totals.ctypes.data_as(_dp), opt(sasa),
+                                                           opt(cls), opt(res), opt(sel_area), opt(sel_atoms, C.POINTER(C.c_longlong)), opt(g_areas),
+                                                           opt(iso), dp_, nd, word, raw.ctypes.data_as(_dp) if word else None, opt(parts),
+                                                           pairs.ctypes.data_as(C.POINTER(C.c_int32)), K, opt(p_areas), float(min_buried), opt(p_res),
+                                                           err, 512)
+        if ret:
+            raise RuntimeError("freesasa_gpu_trajectory_interface_residues: " + err.value.decode())
+        run = RunStats(raw, word, n, R, S, max(G, 0), parts, nf, n_pairs=K, n_segments=NS) if word else None
+        return TopologyResult(totals, cls, res, sel_area, sel_atoms, sasa, res_ref, g_areas, g_atoms, iso, run, pair_areas=p_areas, pair_groups=pairs,
+                              pair_residues=p_res, pair_res_offsets=s_offs, pair_res_index=s_res, pair_res_atoms=s_atoms)
     if pairs is not None:
         p_areas = np.zeros((F, pairs.shape[0], 6))
         ret = L.freesasa_gpu_trajectory_interfaces(frames.ctypes.data_as(_dp), F, C.byref(cb), structure, fa_, opt(idx, C.POINTER(C.c_int32)),
@@ -1799,7 +1894,8 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
                              max_new_shards=0, device=-1, devices=None, out_f32=False, chain_groups=None, separate_chains=False,
                              long=False, group=None, n_groups=None, group_areas_path=None, isolated_path=None, dcd=False, pbc=False,
                              triclinic=False, netcdf=False, xtc=False, stats=None, stats_path=None, partials_path=None, trr=False,
-                             volumes_path=None, masks_path=None, interface_pairs=None, pair_areas_path=None):
+                             volumes_path=None, masks_path=None, interface_pairs=None, pair_areas_path=None, pair_residues_path=None,
+                             min_buried=None):
     """freesasa_gpu_trajectory_file_topology(): trajectory_file() with a topology (see trajectory_topology; frame_atoms:
     atoms per frame of the file, None: the structure's) and one raw fp64 result file per output asked for: class sums
     [F, 3], residues [F, R, 6], selection areas [F, S].  Returns (complete, n_frames, selection_atoms [S] or None).
@@ -1819,9 +1915,15 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
     masks_path (freesasa_gpu_trajectory_file_masks; Shrake-Rupley, up to 128 points, no chain groups, no statistics, no pbc, no
     volumes): receives the frames' exposure masks [F, n, 4] uint32, as trajectory_topology(masks=True) gives them.
     interface_pairs="all" or [(g, h), ...] with pair_areas_path (freesasa_gpu_trajectory_file_interfaces; needs chain groups; no
-    pbc, no volumes, no masks): pair_areas_path receives [F, K, 6] fp64, as trajectory_topology(interface_pairs=...) gives them."""
+    pbc, no volumes, no masks): pair_areas_path receives [F, K, 6] fp64, as trajectory_topology(interface_pairs=...) gives them.
+    pair_residues_path and / or min_buried with interface_pairs (freesasa_gpu_trajectory_file_interface_residues): pair_residues_path
+    receives [F, S, 4] fp64, as trajectory_topology(interface_residues=True) gives them (traj_pair_segments says which segment is
+    which); stats= then also takes "pairs" and "pair_residues", and pair_areas_path may be None; min_buried None is 0.0."""
     L = _stats_proto(_topology_proto(lib()))
-    if (interface_pairs is None) != (pair_areas_path is None):
+    with_res = pair_residues_path is not None or min_buried is not None
+    if with_res and interface_pairs is None:
+        raise ValueError("pair_residues_path and min_buried need interface_pairs")
+    if not with_res and (interface_pairs is None) != (pair_areas_path is None):
         raise ValueError("interface_pairs and pair_areas_path go together")
     if interface_pairs is not None and (volumes_path is not None or masks_path is not None):
         raise ValueError("interface_pairs is not offered with volumes_path or masks_path")
@@ -1850,6 +1952,22 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
     cb = batch._as_c()
     ids, G, _ = _topology_groups(batch, structure, n, chain_groups, separate_chains, long, group, n_groups)
     pairs = _interface_pairs(interface_pairs, ids, G)
+    if pairs is not None and with_res:
+        ret = L.freesasa_gpu_trajectory_file_interface_residues(enc(frames_path), bits, header_bytes, n_frames, C.byref(cb), structure, fa_,
+                                                                None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                                selection.handle if selection is not None else None,
+                                                                ids.ctypes.data_as(C.POINTER(C.c_int32)), G,
+                                                                alg, probe, resolution, frames_per_batch, enc(totals_path), enc(sasa_path),
+                                                                enc(class_sums_path), enc(residues_path), enc(selections_path),
+                                                                None if sel_atoms is None else sel_atoms.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                                                enc(group_areas_path), enc(isolated_path),
+                                                                enc(done_path), max_new_shards, dp_, nd, C.byref(total),
+                                                                stats_word(stats, pairs=True) if stats else 0, enc(stats_path), enc(partials_path),
+                                                                pairs.ctypes.data_as(C.POINTER(C.c_int32)), pairs.shape[0], enc(pair_areas_path),
+                                                                0.0 if min_buried is None else float(min_buried), enc(pair_residues_path), err, 512)
+        if ret < 0:
+            raise RuntimeError("freesasa_gpu_trajectory_file_interface_residues: " + err.value.decode())
+        return ret == 0, int(total.value), sel_atoms
     if pairs is not None:
         ret = L.freesasa_gpu_trajectory_file_interfaces(enc(frames_path), bits, header_bytes, n_frames, C.byref(cb), structure, fa_,
                                                         None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),

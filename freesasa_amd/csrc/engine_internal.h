@@ -137,6 +137,8 @@ hipError_t kl_traj_group_totals(const sasa::TrajGroupArgs &a, hipStream_t st);
 hipError_t kl_traj_pair_radii(const sasa::TrajPairArgs &a, hipStream_t st);
 hipError_t kl_traj_pair_gather(const sasa::TrajPairArgs &a, hipStream_t st);
 hipError_t kl_traj_pair_rows(const sasa::TrajPairArgs &a, hipStream_t st);
+/* ... and their per-residue table: four doubles per (frame, segment), one thread each, behind the engine */
+hipError_t kl_traj_pair_res(const sasa::TrajPairResArgs &a, hipStream_t st);
 /* ... run statistics: a shard's partial [4][W] of the outputs in the table of segments (one thread per column) */
 hipError_t kl_traj_stats(const sasa::TrajStatsArgs &a, hipStream_t st);
 

@@ -142,7 +142,7 @@ namespace {
 /* One per-frame OUTPUT of a run: a row of TrajIO's table.  An entry point says where it goes - the caller's array or a
    result file - and everything else that is per output (opening the files, is it wanted, its place in a shard's blocks, the
    copy or the pwrite at the frame's offset, the flush, the done-list's outputs= word) is a loop over the table. */
-enum { OUT_TOTALS, OUT_SASA, OUT_ISO, OUT_MASK, OUT_CLS, OUT_RES, OUT_SEL, OUT_GRP, OUT_PAIR, OUT_VOL, N_OUT }; /* (per atom | from OUT_CLS on: the block of sums) */
+enum { OUT_TOTALS, OUT_SASA, OUT_ISO, OUT_MASK, OUT_CLS, OUT_RES, OUT_SEL, OUT_GRP, OUT_PAIR, OUT_PRES, OUT_VOL, N_OUT }; /* (per atom | from OUT_CLS on: the block of sums) */
 struct TrajOut {
     const char *name;           /* in messages: "cannot open the %s file", "could not write the %s file" */
     int bit;                    /* in the outputs= word of a done-list's first line */
@@ -160,13 +160,15 @@ struct TrajIO {
     FrameSource src; /* the frames: host memory or a frame file of any format (engine_internal.h, gpu_frames.hip) */
     /* per frame: total [1], per-atom areas [n]; runs with a topology: class sums [3], residue areas [6 R], selection areas [S];
        with chain groups: every atom's area in its isolated group [n], and isolated, complex, buried per group [3 G]; with
-       interface pairs: six doubles per pair [6 K] (traj_kernels.h, traj_pair_rows; no statistics: no bit of the statistics word); the volume
+       interface pairs: six doubles per pair [6 K] (traj_kernels.h, traj_pair_rows) and, where asked for, four doubles per segment of a side
+       that lies in one residue [4 S] (traj_pair_res) - their statistics bits are accepted by the interface-residue entries only; the volume
        entries: the frame's volume [1] (gpu_volume.hip; it has no run statistics: no bit of the statistics word); the mask entries:
        every atom's exposure mask, four uint32 words [4 n] (gpu_dots.hip; per atom, 4 bytes a value, copied as it lies; no statistics) */
     TrajOut out[N_OUT] = {{"totals", 0, FREESASA_GPU_STATS_TOTALS}, {"per-atom", 1, FREESASA_GPU_STATS_ATOMS}, {"isolated", 32, FREESASA_GPU_STATS_ISOLATED},
                           {"masks", 128, 0, nullptr, nullptr, Fd(), 4},
                           {"class-sums", 2, FREESASA_GPU_STATS_CLASSES}, {"residues", 4, FREESASA_GPU_STATS_RESIDUES},
-                          {"selections", 8, FREESASA_GPU_STATS_SELECTIONS}, {"groups", 16, FREESASA_GPU_STATS_GROUPS}, {"interfaces", 256, 0}, {"volumes", 64, 0}};
+                          {"selections", 8, FREESASA_GPU_STATS_SELECTIONS}, {"groups", 16, FREESASA_GPU_STATS_GROUPS}, {"interfaces", 256, FREESASA_GPU_STATS_PAIRS},
+                          {"interface-residues", 512, FREESASA_GPU_STATS_PAIR_RESIDUES}, {"volumes", 64, 0}};
     /* run statistics (include/freesasa_gpu.h): the word; every shard's partial [4][W] at k * 4 W doubles of a host array or of
        the partials file; the merged result to the caller's array (memory form: the entry merges) or the statistics file */
     int stats = 0;
@@ -201,6 +203,12 @@ struct TrajTopo {
     int n_pairs = 0, n_pair = 0;     /* K; atoms of a frame's pair structures: the sum over the pairs of |g| + |h| */
     std::vector<int64_t> pfirst, pside; /* [K + 1], [2 K + 1] */
     std::vector<int32_t> psrc;       /* [n_pair] */
+    /* their per-residue table (pair_res_make): the segments of the sides (traj_kernels.h, traj_pair_res_cut) */
+    bool pres = false;               /* the table is computed: delivered, or its statistics asked for */
+    double min_buried = 0;
+    int n_seg = 0;                   /* S */
+    std::vector<int64_t> seg_first, seg_iso; /* [S + 1], [S] */
+    std::vector<int32_t> seg_res, seg_side;  /* [S], [S] */
 };
 
 unsigned long long fnv1a(const void *p, size_t bytes, unsigned long long h = 1469598103934665603ULL)
@@ -317,15 +325,41 @@ void pair_make(const int32_t *pairs, int n_pairs, TrajTopo *tp)
     tp->pairs = pairs; tp->n_pairs = n_pairs; tp->n_pair = (int)n_pair;
 }
 
-/* The argument checks of a statistics word, on the host: 0, or -1 with a message that names the output.  tp NULL: a run without
-   a topology; has_sel, has_group: was a selection set, were group ids given? */
-int stats_check(int stats, const TrajTopo *tp, bool has_sel, bool has_group, char *err_out, int err_len)
+/* ... and, for the interface-residue entries, the segments of the sides: behind pair_make */
+void pair_res_make(double min_buried, TrajTopo *tp)
 {
-    if (stats & ~127) return set_err(err_out, err_len, "unknown bit in the statistics word");
+    if (!tp->pairs) return;
+    const int64_t *res_first = tp->seg.data();
+    const int64_t S = sasa::traj_pair_res_cut(tp->pairs, tp->n_pairs, tp->gfirst.data(), tp->pside.data(), tp->psrc.data(), res_first, tp->n_res,
+                                              nullptr, nullptr, nullptr, nullptr);
+    tp->seg_first.resize((size_t)S + 1); tp->seg_iso.resize((size_t)S); tp->seg_res.resize((size_t)S); tp->seg_side.resize((size_t)S);
+    sasa::traj_pair_res_cut(tp->pairs, tp->n_pairs, tp->gfirst.data(), tp->pside.data(), tp->psrc.data(), res_first, tp->n_res,
+                            tp->seg_first.data(), tp->seg_res.data(), tp->seg_side.data(), tp->seg_iso.data());
+    tp->pres = true; tp->min_buried = min_buried; tp->n_seg = (int)S;
+}
+/* What the interface-residue entries refuse on top of pair_check (which they pass a place for the pair areas whether or not they
+   have one: here those may be NULL): 0, or -1 */
+int pair_res_check(const int32_t *group, int n_groups, const int32_t *pairs, int n_pairs, int frames_f32, const void *pair_out, const void *res_out,
+                   int stats, double min_buried, char *err_out, int err_len)
+{
+    if (pair_check(group, n_groups, pairs, n_pairs, frames_f32, "", err_out, err_len)) return -1;
+    if (!pair_out && !res_out && !(stats & (FREESASA_GPU_STATS_PAIRS | FREESASA_GPU_STATS_PAIR_RESIDUES)))
+        return set_err(err_out, err_len, "neither the pair areas nor the pair residues are delivered or named in the statistics word: they have nowhere to go");
+    if (!std::isfinite(min_buried)) return set_err(err_out, err_len, "min_buried must be finite");
+    return 0;
+}
+
+/* The argument checks of a statistics word, on the host: 0, or -1 with a message that names the output.  tp NULL: a run without
+   a topology; has_sel, has_group: was a selection set, were group ids given?  more: the bits the entry knows beyond the
+   seven (the interface-residue entries: pairs, pair residues - those runs have their pairs, so nothing is left to need) */
+int stats_check(int stats, const TrajTopo *tp, bool has_sel, bool has_group, char *err_out, int err_len, int more = 0)
+{
+    if (stats & ~(127 | more)) return set_err(err_out, err_len, "unknown bit in the statistics word");
     /* (the table's names and bits, without a TrajIO: nothing here allocates) */
-    static const char *const name[N_OUT] = {"totals", "per-atom", "isolated", "masks", "class-sums", "residues", "selections", "groups", "interfaces", "volumes"};
+    static const char *const name[N_OUT] = {"totals", "per-atom", "isolated", "masks", "class-sums", "residues", "selections", "groups", "interfaces",
+                                            "interface-residues", "volumes"};
     static const int sbit[N_OUT] = {FREESASA_GPU_STATS_TOTALS, FREESASA_GPU_STATS_ATOMS, FREESASA_GPU_STATS_ISOLATED, 0, FREESASA_GPU_STATS_CLASSES,
-                                    FREESASA_GPU_STATS_RESIDUES, FREESASA_GPU_STATS_SELECTIONS, FREESASA_GPU_STATS_GROUPS, 0, 0};
+                                    FREESASA_GPU_STATS_RESIDUES, FREESASA_GPU_STATS_SELECTIONS, FREESASA_GPU_STATS_GROUPS, 0, 0, 0};
     char msg[160];
     for (int k = 0; k < N_OUT; ++k) {
         if (!(stats & sbit[k])) continue;
@@ -337,18 +371,19 @@ int stats_check(int stats, const TrajTopo *tp, bool has_sel, bool has_group, cha
     }
     return 0;
 }
-/* W of a run's statistics word, every output's first column into first[7], in the order of the word's bits (trajstats.c: the one place that knows the layout) */
+/* W of a run's statistics word, every output's first column into first[9], in the order of the word's bits (trajstats.c: the one place that knows the layout) */
 size_t stats_width(int stats, int n_atoms, const TrajTopo *tp, long long *first)
 {
-    const long long W = freesasa_gpu_traj_stats_width(stats, n_atoms, tp ? tp->n_res : 0, tp ? tp->n_sel : 0, tp ? tp->n_groups : 0, first);
+    const long long W = freesasa_gpu_traj_stats_width_pairs(stats, n_atoms, tp ? tp->n_res : 0, tp ? tp->n_sel : 0, tp ? tp->n_groups : 0,
+                                                            tp ? tp->n_pairs : 0, tp ? tp->n_seg : 0, first);
     return W > 0 ? (size_t)W : 0;
 }
 
 /* Once per lane: the topology onto the lane's context - c->seg: residue boundaries | the one structure's offsets | index |
-   classes | backbone flags [| radii | group ids | src: the constant part of `ga` [| pside | pairs | psrc: that of `xa`]]; with selections the keys, labels and program where freesasa_gpu_select_batch puts them, and
+   classes | backbone flags [| radii | group ids | src: the constant part of `ga` [| pside | pairs | psrc: that of `xa` [| seg_first | seg_iso: that of `ra`]]]; with selections the keys, labels and program where freesasa_gpu_select_batch puts them, and
    sel_mask_atom over the topology: the mask words stay in c->parse[PBUF_SEL_BITS].  (run_batch touches none of these.)
    Fills the constant part of `ta`.  Enqueued on the context's stream, nothing waited for. */
-int topo_upload(freesasa_gpu_ctx *c, const TrajTopo &tp, sasa::TrajArgs &ta, sasa::TrajGroupArgs &ga, sasa::TrajPairArgs &xa)
+int topo_upload(freesasa_gpu_ctx *c, const TrajTopo &tp, sasa::TrajArgs &ta, sasa::TrajGroupArgs &ga, sasa::TrajPairArgs &xa, sasa::TrajPairResArgs &ra)
 {
     const size_t n = (size_t)tp.n, R = (size_t)tp.n_res;
     const size_t b_seg = 8 * (R + 3), b_idx = tp.index ? (4 * n + 7) & ~(size_t)7 : 0;
@@ -356,11 +391,21 @@ int topo_upload(freesasa_gpu_ctx *c, const TrajTopo &tp, sasa::TrajArgs &ta, sas
     const size_t b_flags = (2 * n + 7) & ~(size_t)7, b_grp = tp.group ? 8 * n + 4 * n + 4 * (size_t)tp.n_iso : 0;
     /* interface pairs, behind the groups' part at the next multiple of 8: the sides' begins | the pairs | psrc */
     const size_t K = (size_t)tp.n_pairs, b_grp8 = (b_grp + 7) & ~(size_t)7, b_pair = K ? b_grp8 - b_grp + 8 * (2 * K + 1) + 8 * K + 4 * (size_t)tp.n_pair : 0;
-    if (ensure(c, c->seg, b_seg + b_idx + (tp.group ? b_flags : 2 * n) + b_grp + b_pair)) return -1;
+    /* the segments of the per-residue table, behind the pairs' part at the next multiple of 8: seg_first | seg_iso */
+    const size_t NS = tp.pres ? (size_t)tp.n_seg : 0, b_end = b_grp + b_pair, b_end8 = (b_end + 7) & ~(size_t)7, b_pres = tp.pres ? b_end8 - b_end + 8 * (2 * NS + 1) : 0;
+    if (ensure(c, c->seg, b_seg + b_idx + (tp.group ? b_flags : 2 * n) + b_grp + b_pair + b_pres)) return -1;
     char *base = (char *)c->seg.p;
     hipStream_t st = c->stream;
     memset(&ga, 0, sizeof ga);
     memset(&xa, 0, sizeof xa);
+    memset(&ra, 0, sizeof ra);
+    if (tp.pres) {
+        char *r = base + b_seg + b_idx + b_flags + b_end8;
+        HIP_TRY(c, hipMemcpyAsync(r, tp.seg_first.data(), 8 * (NS + 1), hipMemcpyHostToDevice, st));
+        if (NS) HIP_TRY(c, hipMemcpyAsync(r + 8 * (NS + 1), tp.seg_iso.data(), 8 * NS, hipMemcpyHostToDevice, st));
+        ra.n = tp.n; ra.n_iso = tp.n_iso; ra.n_pair = tp.n_pair; ra.n_seg = tp.n_seg; ra.min_buried = tp.min_buried;
+        ra.seg_first = (const int64_t *)r; ra.seg_iso = ra.seg_first + NS + 1;
+    }
     if (K) {
         char *x = base + b_seg + b_idx + b_flags + b_grp8;
         HIP_TRY(c, hipMemcpyAsync(x, tp.pside.data(), 8 * (2 * K + 1), hipMemcpyHostToDevice, st));
@@ -471,10 +516,11 @@ struct TrajRun {
                             (!io.out[OUT_ISO].mem || host_pinned(io.out[OUT_ISO].mem)) && (!io.out[OUT_MASK].mem || host_pinned(io.out[OUT_MASK].mem));
     const size_t S = topo && topo->sel && (io.out[OUT_SEL].wanted() || io.sel_atoms || (io.stats & FREESASA_GPU_STATS_SELECTIONS)) ? (size_t)topo->n_sel : 0; /* selections computed */
     /* A shard's sums lie one behind the other in ONE block, cut to its nf frames: classes | residues | selection areas |
-       groups | interfaces | volumes | selected atoms.  Output k's begin at x0[k] * nf doubles (k = N_OUT: the atom counts); xw doubles per frame hold it all. */
+       groups | interfaces | interface residues | volumes | selected atoms.  Output k's begin at x0[k] * nf doubles (k = N_OUT: the atom counts); xw doubles per frame hold it all. */
     size_t x0[N_OUT + 1] = {0, 0, 0}, xw;
     /* does the block of sums go to the host?  (not when its outputs are computed for their statistics alone) */
-    const bool sums_down = io.out[OUT_CLS].wanted() || io.out[OUT_RES].wanted() || io.out[OUT_SEL].wanted() || io.out[OUT_GRP].wanted() || io.out[OUT_PAIR].wanted() || io.out[OUT_VOL].wanted() || io.sel_atoms;
+    const bool sums_down = io.out[OUT_CLS].wanted() || io.out[OUT_RES].wanted() || io.out[OUT_SEL].wanted() || io.out[OUT_GRP].wanted() || io.out[OUT_PAIR].wanted() ||
+                           io.out[OUT_PRES].wanted() || io.out[OUT_VOL].wanted() || io.sel_atoms;
     size_t sW = 0; /* run statistics: columns of a shard's partial; it lies behind a FULL shard's block of sums, at xw * FB doubles of c->h_gtot */
     const std::vector<double> tp = call_test_points(s.alg, s.resolution);
     /* a full shard as a batch: k n; with chain groups behind them FB n + f n_iso + gfirst[g], with interface pairs behind those
@@ -526,10 +572,11 @@ struct TrajRun {
         if (groups && (size_t)(s.n_frames % s.frames_per_batch)) batch_offsets((size_t)(s.n_frames % s.frames_per_batch), offs_last);
         if (K) grp_chunks = chunks_before_pairs(FB, offs);
         if (K && !offs_last.empty()) grp_chunks_last = chunks_before_pairs((size_t)(s.n_frames % s.frames_per_batch), offs_last);
-        const size_t per[N_OUT] = {1, n, groups ? n : 0, SR_CAP_WORDS * n, topo ? (size_t)3 : 0, topo ? 6 * (size_t)topo->n_res : 0, S, 3 * G, 6 * K, 1};
+        const size_t per[N_OUT] = {1, n, groups ? n : 0, SR_CAP_WORDS * n, topo ? (size_t)3 : 0, topo ? 6 * (size_t)topo->n_res : 0, S, 3 * G, 6 * K,
+                                   K && topo->pres ? 4 * (size_t)topo->n_seg : 0, 1};
         /* (an output's place in the order of the statistics word's outputs, which is trajstats.c's and not the table's: the
            masks and the volumes have no statistics) */
-        static const int scol[N_OUT] = {0, 1, 2, -1, 3, 4, 5, 6, -1, -1};
+        static const int scol[N_OUT] = {0, 1, 2, -1, 3, 4, 5, 6, 7, 8, -1};
         long long first[N_OUT] = {0};
         sW = stats_width(io.stats, s.n_atoms, topo, first);
         for (int k = 0; k < N_OUT; ++k) {
@@ -550,6 +597,7 @@ struct TrajLane {
     sasa::TrajArgs ta;
     sasa::TrajGroupArgs ga; /* (chain groups) */
     sasa::TrajPairArgs xa;  /* (interface pairs) */
+    sasa::TrajPairResArgs ra; /* (... and their per-residue table) */
     int radii_nf = 0;       /* ... the shard length the combined batch's radii are laid out for */
 };
 /* a shard in its lane's hands: frames [f0, f0 + nf) */
@@ -580,7 +628,7 @@ int shard_size(TrajRun &T, TrajLane &L)
         (T.io.out[OUT_MASK].per_frame && ensure(c, c->dt_masks, 4 * SR_CAP_WORDS * n * FB)))
         return -1;
     if (!T.groups && !L.radii_up && hipMemcpyAsync(c->h_radii.p, T.s.radii, 8 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ctx_fail(c, "radii upload failed");
-    if (T.topo && !L.topo_up && topo_upload(c, *T.topo, L.ta, L.ga, L.xa)) return -1;
+    if (T.topo && !L.topo_up && topo_upload(c, *T.topo, L.ta, L.ga, L.xa, L.ra)) return -1;
     L.radii_up = L.topo_up = true;
     return 0;
 }
@@ -689,6 +737,13 @@ int shard_compute(TrajRun &T, TrajLane &L, TrajShard &h)
             if (kl_segment_sums((const double *)c->h_sasa.p, xa.side_off, (int)(2 * T.K * nf), false, (double *)c->if_inpair.p, c->stream) != hipSuccess ||
                 kl_traj_pair_rows(xa, c->stream) != hipSuccess)
                 return ctx_fail(c, "launch of the pairs' sums failed");
+            /* ... and, where the table is delivered or its statistics are asked for, the four columns per (frame, segment) from the
+               engine's areas of the isolated part and of the pair part */
+            if (out[OUT_PRES].per_frame) {
+                sasa::TrajPairResArgs &ra = L.ra;
+                ra.n_frames = h.nf; ra.csasa = (const double *)c->h_sasa.p; ra.out = (double *)c->h_gtot.p + T.x0[OUT_PRES] * nf;
+                if (kl_traj_pair_res(ra, c->stream) != hipSuccess) return ctx_fail(c, "launch of the pairs' per-residue sums failed");
+            }
         }
     }
     /* (file output only) per-atom areas narrowed on the device: half the bytes over PCIe and into the file */
@@ -917,26 +972,28 @@ static int trajectory_mem_topo(const double *xyz_frames, int n_frames, const fre
                                double *sel_area_out, long long *sel_atoms_out, double *group_areas_out, double *iso_out, double *volumes_out,
                                uint32_t *masks_out, const int *devices, int n_devices,
                                int stats, double *stats_out, double *partials_out, char *err_out, int err_len,
-                               const int32_t *pairs = nullptr, int n_pairs = 0, double *pair_areas_out = nullptr)
+                               const int32_t *pairs = nullptr, int n_pairs = 0, double *pair_areas_out = nullptr,
+                               int more_stats = 0, double min_buried = 0, double *pair_res_out = nullptr)
 {
     if (err_out && err_len > 0) err_out[0] = 0;
     return guarded(err_out, err_len, [&]() -> int {
         TrajTopo tp;
         if (topo_make(batch, structure, frame_atoms, atom_index, sel, &tp, err_out, err_len)) return -1;
-        if (stats_check(stats, &tp, sel != nullptr, group != nullptr, err_out, err_len)) return -1;
+        if (stats_check(stats, &tp, sel != nullptr, group != nullptr, err_out, err_len, more_stats)) return -1;
         if (stats && !stats_out) return set_err(err_out, err_len, "statistics are asked for but have nowhere to go (stats_out is NULL)");
         /* (statistics of either group output make the groups' areas wanted: their kernels run) */
         /* (... and so do interface pairs: a row's isolated areas are the groups') */
         if (group_make(group, n_groups, group_areas_out || pairs || (stats & (FREESASA_GPU_STATS_GROUPS | FREESASA_GPU_STATS_ISOLATED)),
                        iso_out || (stats & FREESASA_GPU_STATS_ISOLATED), &tp, err_out, err_len)) return -1;
         pair_make(pairs, n_pairs, &tp);
+        if (pair_res_out || (stats & FREESASA_GPU_STATS_PAIR_RESIDUES)) pair_res_make(min_buried, &tp);
         if (!xyz_frames || !totals_out) return set_err(err_out, err_len, "null argument");
         if ((sel_area_out || sel_atoms_out) && !sel) return set_err(err_out, err_len, "selection outputs need a selection set");
         TrajSpec s = {tp.radii, tp.n, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, &tp};
         if (traj_check_args(s, "n_frames must be > 0", err_out, err_len) || traj_shard_size(s, frame_atoms, err_out, err_len)) return -1;
         TrajIO io;
         io.src.open_memory(xyz_frames, (size_t)frame_atoms); io.sel_atoms = sel_atoms_out;
-        void *const mem[N_OUT] = {totals_out, sasa_out, iso_out, masks_out, class_sums_out, residues_out, sel_area_out, group_areas_out, pair_areas_out, volumes_out};
+        void *const mem[N_OUT] = {totals_out, sasa_out, iso_out, masks_out, class_sums_out, residues_out, sel_area_out, group_areas_out, pair_areas_out, pair_res_out, volumes_out};
         for (int k = 0; k < N_OUT; ++k) io.out[k].mem = mem[k];
         io.stats = stats;
         return traj_run_mem(io, s, stats_out, partials_out, err_out, err_len);
@@ -972,6 +1029,61 @@ extern "C" int freesasa_gpu_trajectory_interfaces(const double *xyz_frames, int 
     return trajectory_mem_topo(xyz_frames, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups, alg, probe, resolution,
                                frames_per_batch, totals_out, sasa_out, class_sums_out, residues_out, sel_area_out, sel_atoms_out, group_areas_out, iso_out,
                                nullptr, nullptr, devices, n_devices, stats, stats_out, partials_out, err_out, err_len, pairs, n_pairs, pair_areas_out);
+}
+
+/* ... and with the per-residue table of the interfaces, its occupancy column and the statistics of both pair outputs */
+extern "C" int freesasa_gpu_trajectory_interface_residues(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
+                                                          int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
+                                                          const int32_t *group, int n_groups,
+                                                          int alg, double probe, int resolution, int frames_per_batch,
+                                                          double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
+                                                          double *sel_area_out, long long *sel_atoms_out, double *group_areas_out, double *iso_out,
+                                                          const int *devices, int n_devices,
+                                                          int stats, double *stats_out, double *partials_out,
+                                                          const int32_t *pairs, int n_pairs, double *pair_areas_out,
+                                                          double min_buried, double *pair_res_out, char *err_out, int err_len)
+{
+    if (pair_res_check(group, n_groups, pairs, n_pairs, 0, pair_areas_out, pair_res_out, stats, min_buried, err_out, err_len)) return -1;
+    return trajectory_mem_topo(xyz_frames, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups, alg, probe, resolution,
+                               frames_per_batch, totals_out, sasa_out, class_sums_out, residues_out, sel_area_out, sel_atoms_out, group_areas_out, iso_out,
+                               nullptr, nullptr, devices, n_devices, stats, stats_out, partials_out, err_out, err_len, pairs, n_pairs, pair_areas_out,
+                               FREESASA_GPU_STATS_PAIRS | FREESASA_GPU_STATS_PAIR_RESIDUES, min_buried, pair_res_out);
+}
+
+/* the segments of such a run, on the host: the run's own checks and cuts, no device */
+extern "C" int freesasa_gpu_trajectory_interface_segments(const freesasa_ingest_batch *batch, int structure, const int32_t *group, int n_groups,
+                                                          const int32_t *pairs, int n_pairs, long long seg_capacity, long long *n_segments_out,
+                                                          long long *seg_offsets_out, int32_t *seg_res_out, int32_t *seg_atoms_out, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (pair_check(group, n_groups, pairs, n_pairs, 0, "", err_out, err_len)) return -1;
+    if (!n_segments_out) return set_err(err_out, err_len, "null argument: n_segments_out");
+    return guarded(err_out, err_len, [&]() -> int {
+        TrajTopo tp;
+        /* (the frames are the structure's atoms: topo_make has nothing to say about an index) */
+        const bool sized = batch && structure >= 0 && structure < batch->n_structs && batch->offsets;
+        const long long n = sized ? (long long)(batch->offsets[structure + 1] - batch->offsets[structure]) : 0;
+        if (topo_make(batch, structure, n > 0 && n <= (1LL << 30) ? (int)n : 0, nullptr, nullptr, &tp, err_out, err_len)) return -1;
+        if (group_make(group, n_groups, true, false, &tp, err_out, err_len)) return -1;
+        pair_make(pairs, n_pairs, &tp);
+        pair_res_make(0.0, &tp);
+        *n_segments_out = tp.n_seg;
+        if (seg_capacity < tp.n_seg) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "seg_capacity %lld is too small: the run has %d segments", seg_capacity, tp.n_seg);
+            return set_err(err_out, err_len, msg);
+        }
+        if (seg_offsets_out) {
+            for (int j = 0; j <= 2 * n_pairs; ++j) seg_offsets_out[j] = 0;
+            for (int s = 0; s < tp.n_seg; ++s) ++seg_offsets_out[tp.seg_side[(size_t)s] + 1];
+            for (int j = 0; j < 2 * n_pairs; ++j) seg_offsets_out[j + 1] += seg_offsets_out[j];
+        }
+        for (int s = 0; s < tp.n_seg; ++s) {
+            if (seg_res_out) seg_res_out[s] = tp.seg_res[(size_t)s];
+            if (seg_atoms_out) seg_atoms_out[s] = (int32_t)(tp.seg_first[(size_t)s + 1] - tp.seg_first[(size_t)s]);
+        }
+        return 0;
+    });
 }
 
 /* what both volume entries refuse before a device is touched or a file opened: 0, or -1 with the message */
@@ -1091,6 +1203,13 @@ static int traj_done_head(char *head, size_t cap, const TrajSpec &s, const TrajI
         /* ... and with interface pairs a digest of K and the pairs (a run without pairs keeps the line it had) */
         if (tp->pairs && len > 0 && len < (int)cap)
             len += snprintf(head + len - 1, cap - (size_t)len + 1, " pairs=%016llx\n", fnv1a(tp->pairs, 8 * (size_t)tp->n_pairs, fnv1a(&tp->n_pairs, sizeof tp->n_pairs))) - 1;
+        /* ... and where their per-residue table is computed the threshold of its fourth column, bit for bit (the plain interfaces
+           run keeps the line it had) */
+        if (tp->pres && len > 0 && len < (int)cap) {
+            unsigned long long u;
+            memcpy(&u, &tp->min_buried, 8);
+            len += snprintf(head + len - 1, cap - (size_t)len + 1, " minburied=%016llx\n", u) - 1;
+        }
     }
     /* ... and with run statistics the word (a run without statistics keeps the line it had) */
     if (io.stats && len > 0 && len < (int)cap) len += snprintf(head + len - 1, cap - (size_t)len + 1, " stats=%d\n", io.stats) - 1;
@@ -1124,7 +1243,9 @@ static int trajectory_file_run(const char *frames_path, int frames_f32, long lon
         if (traj_done_head(head, sizeof head, s, io, st)) return set_err(err_out, err_len, "cannot write the done-list");
         const int fpb = s.frames_per_batch;
         if (io.list.read(done_path, head, (s.n_frames + fpb - 1) / fpb, [fpb](long long k, long long f0, long long) { return f0 == k * fpb; }) == DoneList::REFUSED)
-            return set_err(err_out, err_len, io.stats ? "the done-list belongs to a run with other parameters, radii, topology, outputs, statistics or frame file"
+            return set_err(err_out, err_len, s.topo && s.topo->pres ? "the done-list belongs to a run with other parameters, radii, topology, selections, chain groups, interface pairs, "
+                                                                      "min_buried, outputs, statistics or frame file"
+                                           : io.stats ? "the done-list belongs to a run with other parameters, radii, topology, outputs, statistics or frame file"
                                            : s.topo && s.topo->pairs ? "the done-list belongs to a run with other parameters, radii, topology, selections, chain groups, interface pairs, outputs or frame file"
                                            : s.topo && s.topo->group ? "the done-list belongs to a run with other parameters, radii, topology, selections, chain groups, outputs or frame file"
                                            : s.topo ? "the done-list belongs to a run with other parameters, radii, topology, selections, outputs or frame file"
@@ -1208,21 +1329,23 @@ static int trajectory_file_topo(const char *frames_path, int frames_f32, long lo
                                 const char *group_areas_path, const char *iso_path, const char *volumes_path, const char *masks_path,
                                 const char *done_path, long long max_new_shards, const int *devices, int n_devices,
                                 long long *frames_total_out, int stats, const char *stats_path, const char *partials_path, char *err_out, int err_len,
-                                const int32_t *pairs = nullptr, int n_pairs = 0, const char *pair_areas_path = nullptr)
+                                const int32_t *pairs = nullptr, int n_pairs = 0, const char *pair_areas_path = nullptr,
+                                int more_stats = 0, double min_buried = 0, const char *pair_res_path = nullptr)
 {
     if (err_out && err_len > 0) err_out[0] = 0;
     return guarded(err_out, err_len, [&]() -> int {
         TrajTopo tp; /* (outlives the run: the lanes upload from it) */
         if (topo_make(batch, structure, frame_atoms, atom_index, sel, &tp, err_out, err_len)) return -1;
-        if (stats_check(stats, &tp, sel != nullptr, group != nullptr, err_out, err_len)) return -1;
+        if (stats_check(stats, &tp, sel != nullptr, group != nullptr, err_out, err_len, more_stats)) return -1;
         if (group_make(group, n_groups, group_areas_path || pairs || (stats & (FREESASA_GPU_STATS_GROUPS | FREESASA_GPU_STATS_ISOLATED)),
                        iso_path || (stats & FREESASA_GPU_STATS_ISOLATED), &tp, err_out, err_len)) return -1;
         pair_make(pairs, n_pairs, &tp);
+        if (pair_res_path || (stats & FREESASA_GPU_STATS_PAIR_RESIDUES)) pair_res_make(min_buried, &tp);
         if ((sel_area_path || sel_atoms_out) && !sel) return set_err(err_out, err_len, "selection outputs need a selection set");
         TrajSpec s = {tp.radii, tp.n, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, &tp, max_new_shards};
         TrajIO io;
         io.sel_atoms = sel_atoms_out;
-        const char *const path[N_OUT] = {totals_path, sasa_path, iso_path, masks_path, class_sums_path, residues_path, sel_area_path, group_areas_path, pair_areas_path, volumes_path};
+        const char *const path[N_OUT] = {totals_path, sasa_path, iso_path, masks_path, class_sums_path, residues_path, sel_area_path, group_areas_path, pair_areas_path, pair_res_path, volumes_path};
         for (int k = 0; k < N_OUT; ++k) io.out[k].path = path[k];
         io.stats = stats; io.stats_path = stats_path; io.parts_path = partials_path;
         return trajectory_file_run(frames_path, frames_f32, header_bytes, s, io, done_path, frames_total_out, err_out, err_len);
@@ -1273,6 +1396,29 @@ extern "C" int freesasa_gpu_trajectory_file_interfaces(const char *frames_path, 
                                 alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
                                 sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
                                 frames_total_out, stats, stats_path, partials_path, err_out, err_len, pairs, n_pairs, pair_areas_path);
+}
+
+/* ... with the per-residue table of the interfaces into its own file, and the statistics of both pair outputs */
+extern "C" int freesasa_gpu_trajectory_file_interface_residues(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
+                                                               const freesasa_ingest_batch *batch, int structure,
+                                                               int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
+                                                               const int32_t *group, int n_groups,
+                                                               int alg, double probe, int resolution, int frames_per_batch,
+                                                               const char *totals_path, const char *sasa_path, const char *class_sums_path,
+                                                               const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
+                                                               const char *group_areas_path, const char *iso_path,
+                                                               const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                                               long long *frames_total_out,
+                                                               int stats, const char *stats_path, const char *partials_path,
+                                                               const int32_t *pairs, int n_pairs, const char *pair_areas_path,
+                                                               double min_buried, const char *pair_res_path, char *err_out, int err_len)
+{
+    if (pair_res_check(group, n_groups, pairs, n_pairs, frames_f32, pair_areas_path, pair_res_path, stats, min_buried, err_out, err_len)) return -1;
+    return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,
+                                alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
+                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
+                                frames_total_out, stats, stats_path, partials_path, err_out, err_len, pairs, n_pairs, pair_areas_path,
+                                FREESASA_GPU_STATS_PAIRS | FREESASA_GPU_STATS_PAIR_RESIDUES, min_buried, pair_res_path);
 }
 
 extern "C" int freesasa_gpu_trajectory_file_groups(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,

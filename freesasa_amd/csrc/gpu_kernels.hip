@@ -1229,6 +1229,21 @@ hipError_t kl_traj_pair_rows(const TrajPairArgs &a, hipStream_t st)
     return hipGetLastError();
 }
 
+/* ... and their per-residue table (traj_kernels.h): one row per (frame, segment), a thread each.  Workgroups of one wave: a
+   thread's loop is as long as its segment, and a wave that holds a long one keeps no other waves' registers waiting for it */
+#define TRAJ_PRES_B 64
+__global__ __launch_bounds__(TRAJ_PRES_B) void k_traj_pair_res(TrajPairResArgs a)
+{
+    traj_pair_res(a, (int64_t)blockIdx.x * TRAJ_PRES_B + threadIdx.x);
+}
+hipError_t kl_traj_pair_res(const TrajPairResArgs &a, hipStream_t st)
+{
+    const int64_t threads = (int64_t)a.n_frames * a.n_seg;
+    if (threads <= 0) return hipSuccess; /* (every side empty: no segment, no row) */
+    hipLaunchKernelGGL(k_traj_pair_res, dim3((unsigned)((threads + TRAJ_PRES_B - 1) / TRAJ_PRES_B)), dim3(TRAJ_PRES_B), 0, st, a);
+    return hipGetLastError();
+}
+
 /* ... run statistics (traj_kernels.h): a shard's partial, one thread per column, one launch for every output asked for.  Workgroups
    of one wave: a shard of 10^4 columns still spreads over 157 compute units, and a thread's frame loop is serial by definition */
 #define TRAJ_STAT_B 64

@@ -13,6 +13,7 @@
  *   traj_sel_phase0/1  the selection areas of every frame, as sel_sums_phase0 / sel_sums_phase1 (select_kernels.h)
  *   traj_group_*       chain groups per frame: the isolated structures behind the frames, as group_kernels.h
  *   traj_pair_*        interfaces between chain groups per frame: the pair structures behind the isolated ones, six doubles a pair
+ *   traj_pair_res      ... and their per-residue table: four doubles per (frame, segment of a side that lies in one residue)
  *   traj_stats         run statistics: a shard's partial (mean, M2, min, max) of every column of the outputs asked for (at the end)
  *
  * Atom i of frame f is element f * n + i of the shard's per-atom areas and reads the per-topology arrays at i.  Every sum
@@ -424,6 +425,93 @@ SASA_D void traj_pair_rows(const TrajPairArgs &a, int64_t t)
     o[0] = ig; o[1] = ih; o[2] = pg; o[3] = ph; o[4] = ig - pg; o[5] = ih - ph;
 }
 
+/* ------------------------------------------------------------------ per-residue interface tables per frame
+ * (freesasa_gpu_trajectory_interface_residues / _trajectory_file_interface_residues): the interfaces' run with, per frame, a
+ * DENSE table [S, 4].  A SEGMENT is a maximal run of consecutive atoms of ONE side of a frame's pair part whose topology atoms
+ * lie in one residue: a head at every side's begin and wherever the residue changes.  Empty residues are never found, a residue
+ * split over two groups gives a segment on each side it occurs on, atoms in no group are in no side, an empty side has no
+ * segment, and a group named in several pairs has its residues once per pair.  The segments are the same for every frame: the
+ * host makes them once per run (traj_pair_res_cut), a lane uploads seg_first and seg_iso once.  Per frame f and segment s, over
+ * the pair-part positions m in [seg_first[s], seg_first[s + 1]):
+ *
+ *     iso_res       the sum of the engine's areas of those atoms in their ISOLATED group of frame f - a side of group g lies
+ *                   there in the same order, so the segment is contiguous from seg_iso[s] = gfirst[g] + (seg_first[s] - pside[side])
+ *     in_pair_res   the sum of the engine's areas of the pair-structure atoms m of frame f
+ *     buried_res    iso_res - in_pair_res, one subtraction
+ *     in_interface  1.0 if buried_res > min_buried (strict), else 0.0 - its mean over a run is the residue's OCCUPANCY
+ *
+ * Both sums are taken one addition at a time in atom order from 0.0; there is no fma (contraction is off in the function
+ * itself, as in traj_stats).  No float atomics, no workgroup waits for another, no LDS. */
+
+struct TrajPairResArgs {
+    int n, n_iso, n_pair;     /* atoms of the topology, of a frame's isolated structures, of a frame's pair structures */
+    int n_seg;                /* S */
+    int n_frames;             /* frames of this shard */
+    const int64_t *seg_first; /* [S + 1] every segment's begin within a frame's pair part; seg_first[S] = n_pair */
+    const int64_t *seg_iso;   /* [S] its first atom's place within a frame's isolated part */
+    const double *csasa;      /* [n_frames (n + n_iso + n_pair)] the combined batch's areas */
+    double min_buried;
+    double *out;              /* [n_frames S 4] iso_res, in_pair_res, buried_res, in_interface */
+};
+
+/* The segments, on the host, once per run, behind traj_pair_cut: seg_first [S + 1], seg_res [S] (the residue, counted within the
+   structure), seg_side [S] (0 .. 2 K - 1) and seg_iso [S]; any of them may be NULL (a first call counts).  res_first [n_res + 1]
+   is the structure's, rebased to it.  An atom's residue is the last r < n_res with res_first[r] <= atom: within a side the
+   topology atoms ascend (input order), so r only walks forward.  Returns S (<= n_pair). */
+inline int64_t traj_pair_res_cut(const int32_t *pairs, int n_pairs, const int64_t *gfirst, const int64_t *pside, const int32_t *psrc,
+                                 const int64_t *res_first, int64_t n_res, int64_t *seg_first, int32_t *seg_res, int32_t *seg_side, int64_t *seg_iso)
+{
+    int64_t S = 0;
+    for (int j = 0; j < 2 * n_pairs; ++j) {
+        int64_t r = 0, last = -1;
+        for (int64_t m = pside[j]; m < pside[j + 1]; ++m) {
+            while (r + 1 < n_res && res_first[r + 1] <= psrc[m]) ++r;
+            if (m == pside[j] || r != last) {
+                if (seg_first) seg_first[S] = m;
+                if (seg_res) seg_res[S] = (int32_t)r;
+                if (seg_side) seg_side[S] = j;
+                if (seg_iso) seg_iso[S] = gfirst[pairs[j]] + (m - pside[j]);
+                ++S;
+            }
+            last = r;
+        }
+    }
+    if (seg_first) seg_first[S] = pside[2 * n_pairs];
+    return S;
+}
+
+#define TRAJ_PRES_U 8 /* atoms a thread loads ahead of its additions */
+
+/* traj_pair_res, one thread per (frame, segment), as traj_residue has one per (frame, residue): consecutive lanes take consecutive
+   segments of one frame, whose atoms lie one behind the other in both parts, and write consecutive rows.  The order of the
+   additions is the definition, so a segment is never split over lanes; what keeps a LONG segment (a chain under one residue
+   label, a lipid) from costing its length in memory latencies is that TRAJ_PRES_U atoms of both parts are loaded before the first
+   of them is added - sixteen loads of a thread are in flight together, the additions stay in atom order (traj_stats does the same
+   with its frames). */
+SASA_D void traj_pair_res(const TrajPairResArgs &a, int64_t t)
+{
+#ifndef SASA_EMU
+#pragma clang fp contract(off) /* (the emulation is built with -ffp-contract=off; so is the library - this holds whatever the flags) */
+#endif
+    if (t >= (int64_t)a.n_frames * a.n_seg) return;
+    const int64_t f = t / a.n_seg;
+    const int64_t s = t - f * a.n_seg;
+    const int64_t b = a.seg_first[s], len = a.seg_first[s + 1] - b;
+    const double *iso = a.csasa + (int64_t)a.n_frames * a.n + f * a.n_iso + a.seg_iso[s];
+    const double *pr = a.csasa + (int64_t)a.n_frames * ((int64_t)a.n + a.n_iso) + f * a.n_pair + b;
+    double si = 0.0, sp = 0.0;
+    int64_t m = 0;
+    for (; m + TRAJ_PRES_U <= len; m += TRAJ_PRES_U) {
+        double vi[TRAJ_PRES_U], vp[TRAJ_PRES_U];
+        for (int q = 0; q < TRAJ_PRES_U; ++q) { vi[q] = iso[m + q]; vp[q] = pr[m + q]; }
+        for (int q = 0; q < TRAJ_PRES_U; ++q) { si += vi[q]; sp += vp[q]; }
+    }
+    for (; m < len; ++m) { si += iso[m]; sp += pr[m]; }
+    const double buried = si - sp;
+    double *o = a.out + 4 * t;
+    o[0] = si; o[1] = sp; o[2] = buried; o[3] = buried > a.min_buried ? 1.0 : 0.0;
+}
+
 /* ------------------------------------------------------------------ run statistics
  * (freesasa_gpu_trajectory_stats and its kin, include/freesasa_gpu.h): a shard's PARTIAL of every output statistics are asked
  * for - per column of the output's block a[n_frames][width] of fp64 the mean, M2 = sum (a - mean)^2, the smallest and the
@@ -434,7 +522,7 @@ SASA_D void traj_pair_rows(const TrajPairArgs &a, int64_t t)
  * Every operation is rounded on its own: the square is a multiplication of its own, never fused into the add (contraction is
  * switched off in the function itself). */
 
-#define TRAJ_STAT_SEGS 7 /* the drivers' table of outputs has seven rows */
+#define TRAJ_STAT_SEGS 9 /* the drivers' table of outputs has nine rows with statistics */
 #define TRAJ_STAT_U 8    /* rows a thread loads ahead of its additions */
 struct TrajStatSeg {
     const double *src;    /* the output's block [n_frames][width] */

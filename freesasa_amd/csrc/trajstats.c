@@ -25,6 +25,23 @@ long long freesasa_gpu_traj_stats_width(int stats, long long n_atoms, long long 
     return W;
 }
 
+/* ... with the two outputs of the interface entries behind the groups: pairs [6 K] | interface residues [4 S] */
+long long freesasa_gpu_traj_stats_width_pairs(int stats, long long n_atoms, long long n_res, long long n_sel, long long n_groups,
+                                              long long n_pairs, long long n_segments, long long *first_out)
+{
+    const int bit[9] = {FREESASA_GPU_STATS_TOTALS, FREESASA_GPU_STATS_ATOMS, FREESASA_GPU_STATS_ISOLATED, FREESASA_GPU_STATS_CLASSES,
+                        FREESASA_GPU_STATS_RESIDUES, FREESASA_GPU_STATS_SELECTIONS, FREESASA_GPU_STATS_GROUPS, FREESASA_GPU_STATS_PAIRS,
+                        FREESASA_GPU_STATS_PAIR_RESIDUES};
+    const long long width[9] = {1, n_atoms, n_atoms, 3, 6 * n_res, n_sel, 3 * n_groups, 6 * n_pairs, 4 * n_segments};
+    long long W = 0;
+    if (stats < 0 || stats > 511 || n_atoms < 0 || n_res < 0 || n_sel < 0 || n_groups < 0 || n_pairs < 0 || n_segments < 0) return -1;
+    for (int k = 0; k < 9; ++k) {
+        if (first_out) first_out[k] = stats & bit[k] ? W : -1;
+        if (stats & bit[k]) W += width[k];
+    }
+    return W;
+}
+
 int freesasa_gpu_traj_stats_merge(const double *parts, const long long *frames_per_part, long long n_parts, long long width,
                                   double *out, long long *frames_total_out)
 {

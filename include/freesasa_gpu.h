@@ -1017,6 +1017,8 @@ int freesasa_gpu_trajectory_file_groups(const char *frames_path, int frames_f32,
 #define FREESASA_GPU_STATS_RESIDUES 16
 #define FREESASA_GPU_STATS_SELECTIONS 32
 #define FREESASA_GPU_STATS_GROUPS 64
+#define FREESASA_GPU_STATS_PAIRS 128          /* (freesasa_gpu_trajectory_interface_residues and its file form only, below) */
+#define FREESASA_GPU_STATS_PAIR_RESIDUES 256  /* (the same two entries only) */
 int freesasa_gpu_trajectory_stats(const double *xyz_frames, const double *radii, int n_atoms, int n_frames,
                                   int alg, double probe_radius, int resolution, int frames_per_batch,
                                   double *totals_out, double *sasa_out, const int *devices, int n_devices,
@@ -1098,8 +1100,9 @@ int freesasa_gpu_trajectory_file_groups_periodic(const char *frames_path, int fr
    Argument errors, -1 with a message before a device is touched or a file opened: group NULL, n_pairs < 1, pairs or the pair
    areas NULL, a pair with g >= h or an id out of [0, n_groups) (the message names the pair's index), a pair named twice (it names
    both indices), bit 3 or bit 4 of frames_f32.
-   Not offered: a contact screen per frame, per-atom or per-residue buried areas per pair, contact tables, interfaces among
-   periodic images, run statistics of the pair columns, group ids made on the device, more than two groups per interface. */
+   Not offered: a contact screen per frame, per-atom buried areas per pair, contact tables, interfaces among periodic images,
+   group ids made on the device, more than two groups per interface.  Per-residue buried areas per pair and the run statistics
+   of the pair columns: freesasa_gpu_trajectory_interface_residues below. */
 int freesasa_gpu_trajectory_interfaces(const double *xyz_frames, int n_frames, const struct freesasa_ingest_batch *batch, int structure,
                                        int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
                                        const int32_t *group, int n_groups,
@@ -1121,11 +1124,80 @@ int freesasa_gpu_trajectory_file_interfaces(const char *frames_path, int frames_
                                             long long *frames_total_out,
                                             int stats, const char *stats_path, const char *partials_path,
                                             const int32_t *pairs, int n_pairs, const char *pair_areas_path, char *err, int err_len);
+/* PER-RESIDUE INTERFACE TABLES over a trajectory, with OCCUPANCY: where on each partner an interface lies, frame by frame, and in
+   what fraction of the frames a residue is part of it.  These entries are freesasa_gpu_trajectory_interfaces / _file_interfaces
+   with, in front of err,
+     min_buried            a finite double, in A^2
+     pair residues         4 S per frame (8 * 4 S f): the DENSE table below; an array [F, S, 4] / a path of raw fp64
+   The pair part of a frame is the n_pair atoms of its pair structures: for every pair, side g's atoms in input order, then side
+   h's.  A SEGMENT is a maximal run of consecutive atoms of ONE side whose topology atoms lie in one residue of the topology's
+   structure: a head at every side's begin and wherever the residue changes.  Empty residues are never found; a residue split
+   over two groups gives a segment on each side it occurs on; atoms in no group are in no side; an empty side has no segment; a
+   group named in several pairs has its residues once per pair.  The segments are the same for every frame: S of them, S <=
+   n_pair (freesasa_gpu_trajectory_interface_segments gives them without a device).  Per frame f and segment s, four doubles:
+     iso_res       the sum of its atoms' areas in their ISOLATED group of frame f (the run's isolated output for those atoms)
+     in_pair_res   the sum of its atoms' areas in the pair structure of frame f (the plain entry's on that structure)
+     buried_res    iso_res - in_pair_res, one subtraction
+     in_interface  1.0 if buried_res > min_buried (strict, fp64), else 0.0
+   Both sums are taken one addition at a time in atom order, from 0.0; there is no fma.  The table is DENSE, not compacted, and
+   there is no contact screen: the frames of a run line up column by column.  Taking the frames as a batch,
+   freesasa_gpu_interface_residues_dev with the same res_first and min_buried lists rows that equal, in all three areas and bit
+   for bit, the dense row of the same (frame, pair, side, residue); every dense row it does not list has in_interface == 0 or
+   belongs to a pair that entry screened out.
+   Statistics: two more bits of the word, accepted by THESE TWO entries only (every other entry refuses them as unknown):
+   FREESASA_GPU_STATS_PAIRS - the 6 K pair columns - and FREESASA_GPU_STATS_PAIR_RESIDUES - the 4 S columns; they lie behind
+   the groups: ... | groups [3 G] | pairs [6 K] | interface residues [4 S] (freesasa_gpu_traj_stats_width_pairs).  The mean of
+   an in_interface column is the residue's OCCUPANCY: the fraction of the frames in which it is in the interface.
+   Here the pair areas may be NULL, and an output whose statistics bit is set need not be delivered.  The engine's batch of a
+   shard is the interfaces run's, atom for atom: every output shared with that run is bit for bit what it gives.
+   The done-list's first line carries bit 512 in outputs= when the table is written and, behind pairs=,
+   minburied=<the double's 16 hex digits> when it is computed: a list written with another min_buried, for other pairs, or by
+   the plain interfaces run is refused.
+   Argument errors, -1 with a message before a device is touched or a file opened: everything the interface entries refuse
+   (bit 3 and bit 4 of frames_f32 included) but NULL pair areas; neither pair areas nor pair residues delivered nor named in the
+   statistics word (nowhere to go); a min_buried that is not finite.
+   Not offered: a compacted per-frame table, contact tables per frame, periodic images, class splits of the buried area, a
+   contact screen per frame, medians, statistics of the volume column. */
+int freesasa_gpu_trajectory_interface_residues(const double *xyz_frames, int n_frames, const struct freesasa_ingest_batch *batch, int structure,
+                                               int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
+                                               const int32_t *group, int n_groups,
+                                               int alg, double probe_radius, int resolution, int frames_per_batch,
+                                               double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
+                                               double *sel_area_out, long long *sel_atoms_out, double *group_areas_out, double *iso_out,
+                                               const int *devices, int n_devices,
+                                               int stats, double *stats_out, double *partials_out,
+                                               const int32_t *pairs, int n_pairs, double *pair_areas_out /* [F, K, 6] or NULL */,
+                                               double min_buried, double *pair_res_out /* [F, S, 4] or NULL */, char *err, int err_len);
+int freesasa_gpu_trajectory_file_interface_residues(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
+                                                    const struct freesasa_ingest_batch *batch, int structure,
+                                                    int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
+                                                    const int32_t *group, int n_groups,
+                                                    int alg, double probe_radius, int resolution, int frames_per_batch,
+                                                    const char *totals_path, const char *sasa_path, const char *class_sums_path,
+                                                    const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
+                                                    const char *group_areas_path, const char *iso_path,
+                                                    const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                                    long long *frames_total_out,
+                                                    int stats, const char *stats_path, const char *partials_path,
+                                                    const int32_t *pairs, int n_pairs, const char *pair_areas_path,
+                                                    double min_buried, const char *pair_res_path, char *err, int err_len);
+/* The segments of such a run, on the host: no device is needed.  *n_segments_out = S is set first; then, when seg_capacity >= S,
+   seg_offsets_out [2 K + 1] (the prefix of the segments per side: side j = 2 k + q of pair k owns segments
+   [seg_offsets[j], seg_offsets[j + 1])), seg_res_out [S] (the residue of every segment, counted within the structure) and
+   seg_atoms_out [S] (its atom count); each may be NULL.  seg_capacity < S: -1, nothing written, the message names S.  The
+   refusals of the topology, the group ids and the pairs are the run's, with their messages. */
+int freesasa_gpu_trajectory_interface_segments(const struct freesasa_ingest_batch *batch, int structure, const int32_t *group, int n_groups,
+                                               const int32_t *pairs, int n_pairs, long long seg_capacity, long long *n_segments_out,
+                                               long long *seg_offsets_out, int32_t *seg_res_out, int32_t *seg_atoms_out, char *err, int err_len);
 /* W of a statistics word for a system of n_atoms atoms, n_res residues, n_sel selections and n_groups groups; first_out (may be
    NULL) [7] receives the first column of every output in the order above, -1 for one whose bit is not set.  -1: an unknown bit
    or a negative count.  (csrc/trajstats.c: plain C, no allocation, no GPU call.) */
 long long freesasa_gpu_traj_stats_width(int stats, long long n_atoms, long long n_res, long long n_sel, long long n_groups,
                                         long long *first_out);
+/* ... of the two interface-residue entries: n_pairs pairs and n_segments segments more, first_out [9] (pairs, interface residues
+   behind the seven); bits above 256 or a negative count: -1.  With stats <= 127 it is the function above. */
+long long freesasa_gpu_traj_stats_width_pairs(int stats, long long n_atoms, long long n_res, long long n_sel, long long n_groups,
+                                              long long n_pairs, long long n_segments, long long *first_out);
 /* The merge above over n_parts consecutive partials parts [n_parts][4][width] of frames_per_part [n_parts] frames each:
    out [4][width] = mean, std, min, max; frames_total_out (may be NULL) their frames.  Exported so that a caller can merge ANY
    run of consecutive shards of a partials file: block averages, the error estimate of an MD average.  No allocation, no GPU

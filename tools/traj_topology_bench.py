@@ -83,10 +83,16 @@ each line with frames_per_batch, the shards of the run and the median time per s
 frame, of its isolated groups and of its pair structures that go through the engine (n + n_iso + n_pair).  --kernel-stats FILE: a
 `rocprofv3 --kernel-trace --stats` kernel-stats CSV of a run of this mode; the share of the kernels the pairs add (k_traj_pair_*
 and k_totals, which sums the sides) in the kernel time of the whole trace goes into the interfaces line as new_kernels_share.
+    interface-residues        (with --interface-residues beside --interfaces) the same with pair_residues_path and min_buried = 0: the dense
+                              per-residue table [F, S, 4] as well (one kernel more, k_traj_pair_res, and 4 S doubles per frame down)
+    interface-residues-stats  (with --stats beside those) stats=("pairs", "pair_residues") and neither pair file: mean, std, min, max of
+                              the 6 K + 4 S columns - the occupancy among them - from the statistics alone; its means must be those of
+                              the interface-residues arm's files to rounding
+the share of k_traj_pair_res alone goes into those two lines as pair_res_kernel_share.
 
 One JSON line per arm: atom-frames/s counted in SOLUTE atoms and in frame atoms, the median and the spread of --reps runs.
 
-    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd] [--netcdf] [--pbc [--pbc-arms all|off] [--triclinic] [--groups]] [--xtc [--xtc-distinct 24] [--xtc-fpb 0]] [--trr [--double] [--trr-arms raw,trr]] [--stats] [--groups [--interfaces] [--kernel-stats FILE]]
+    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd] [--netcdf] [--pbc [--pbc-arms all|off] [--triclinic] [--groups]] [--xtc [--xtc-distinct 24] [--xtc-fpb 0]] [--trr [--double] [--trr-arms raw,trr]] [--stats] [--groups [--interfaces [--interface-residues [--stats]]] [--kernel-stats FILE]]
 
 For the kernel times: `rocprofv3 --kernel-trace --stats -- python tools/traj_topology_bench.py --reps 1 --arms all`
 (k_traj_gather / k_traj_residues / k_traj_class / k_traj_sel are the topology's kernels, k_traj_group_* the groups')."""
@@ -390,8 +396,9 @@ def stats_mode(args, scratch):
     return lines
 
 
-def new_kernels_share(path):
-    """the share of k_traj_pair_* and k_totals in the kernel time of a rocprofv3 kernel-stats CSV (columns Name, ..., TotalDurationNs)"""
+def new_kernels_share(path, only=None):
+    """the share of k_traj_pair_* and k_totals (only: of that kernel alone) in the kernel time of a rocprofv3 kernel-stats CSV
+    (columns Name, ..., TotalDurationNs)"""
     import csv
     new = total = 0.0
     with open(path, newline="") as fh:
@@ -399,7 +406,7 @@ def new_kernels_share(path):
             ns = float(row["TotalDurationNs"])
             total += ns
             name = row["Name"].split("(")[0]
-            if name.startswith("k_traj_pair_") or name == "k_totals":
+            if name == only if only else name.startswith("k_traj_pair_") or name == "k_totals":
                 new += ns
     return new / total if total else None
 
@@ -419,6 +426,16 @@ def groups_mode(args, scratch):
     G = int(ng[0])
     assert G == 4 and np.array_equal(np.bincount(ids), [N_SOLUTE // 4] * 4)
     K, n_pair = G * (G - 1) // 2, (G - 1) * N_SOLUTE
+    S = 0
+    if args.interface_residues:
+        S = fa.traj_pair_segments(b, ids, G, [(g, h) for g in range(G) for h in range(g + 1, G)])[1].size
+        assert S == (G - 1) * b.n_residues
+        arms["interface-residues"] = lambda: fa.trajectory_file_topology(full, b, p("t2"), group_areas_path=p("g2"), interface_pairs="all",
+                                                                         pair_areas_path=p("p2"), pair_residues_path=p("r2"), min_buried=0.0, **kw)
+        if args.stats:
+            arms["interface-residues-stats"] = lambda: fa.trajectory_file_topology(full, b, p("t3"), group_areas_path=p("g3"), interface_pairs="all",
+                                                                                   min_buried=0.0, stats=("pairs", "pair_residues"),
+                                                                                   stats_path=p("s3"), partials_path=p("q3"), **kw)
     runs = {a: [] for a in arms}
     for a in arms:
         arms[a]()                                                        # warm-up: contexts, staging, page cache
@@ -432,19 +449,32 @@ def groups_mode(args, scratch):
         assert np.array_equal(np.fromfile(p("t1")), np.fromfile(p("t0"))) and np.array_equal(np.fromfile(p("g1")), np.fromfile(p("g0")))
         rows, areas = np.fromfile(p("p1")).reshape(args.frames, K, 6), np.fromfile(p("g0")).reshape(args.frames, G, 3)
         assert np.array_equal(rows[:, 0, 0], areas[:, 0, 0]) and np.array_equal(rows[:, K - 1, 1], areas[:, G - 1, 0]) and np.all(rows[:, :, 4:] >= -1e-6)
+    if args.interface_residues:
+        assert np.array_equal(np.fromfile(p("t2")), np.fromfile(p("t0"))) and np.array_equal(np.fromfile(p("p2")), np.fromfile(p("p1")))
+        table = np.fromfile(p("r2")).reshape(args.frames, S, 4)
+        assert np.all(table[:, :, 2] == table[:, :, 0] - table[:, :, 1]) and np.array_equal(table[:, :, 3], (table[:, :, 2] > 0.0).astype(np.float64))
+        if args.stats:
+            got = fa.traj_stats_read(p("s3"), ("pairs", "pair_residues"), N_SOLUTE, b.n_residues, 0, G, n_pairs=K, n_segments=S)
+            assert np.allclose(got["pair_residues"][0], table.mean(0), rtol=1e-12, atol=1e-12) and np.array_equal(got["pair_residues"][3], table.max(0))
+            assert np.allclose(got["pairs"][0], np.fromfile(p("p2")).reshape(args.frames, K, 6).mean(0), rtol=1e-12, atol=1e-12)
     lines = []
     for a in arms:
         v = sorted(runs[a])
         med = v[len(v) // 2]
-        engine = 2 * N_SOLUTE + (n_pair if a == "interfaces" else 0)
+        engine = 2 * N_SOLUTE + (n_pair if a != "groups" else 0)
         fpb = 1250000 // max(N_FRAME, engine) + 1                        # (the driver's default: include/freesasa_gpu.h)
         shards = -(-args.frames // fpb)
-        line = {"arm": a, "frames": args.frames, "frame_atoms": N_FRAME, "solute_atoms": N_SOLUTE, "groups": G, "pairs": K if a == "interfaces" else 0,
+        line = {"arm": a, "frames": args.frames, "frame_atoms": N_FRAME, "solute_atoms": N_SOLUTE, "groups": G, "pairs": K if a != "groups" else 0,
+                "segments": S if a.startswith("interface-residues") else 0,
+                "result_bytes_per_frame": 8 + 24 * G + (48 * K if a in ("interfaces", "interface-residues") else 0) + (32 * S if a == "interface-residues" else 0)
+                + (os.path.getsize(p("q3")) / args.frames if a == "interface-residues-stats" else 0),
                 "frames_per_batch": fpb, "shards": shards, "engine_atoms_per_frame": engine, "median_seconds": med, "min_seconds": v[0],
                 "max_seconds": v[-1], "median_ms_per_shard": 1e3 * med / shards, "solute_atom_frames_per_s": N_SOLUTE * args.frames / med,
                 "engine_atom_frames_per_s": engine * args.frames / med, "runs": len(v)}
         if a == "interfaces" and args.kernel_stats:
             line["new_kernels_share"] = new_kernels_share(args.kernel_stats)
+        if a.startswith("interface-residues") and args.kernel_stats:
+            line["pair_res_kernel_share"] = new_kernels_share(args.kernel_stats, "k_traj_pair_res")
         lines.append(json.dumps(line))
     return lines
 
@@ -465,6 +495,8 @@ def main():
     ap.add_argument("--groups", action="store_true", help="with --pbc: chain groups among periodic images against the plain periodic run and the non-periodic groups' run; "
                                                           "without: the solute as four chains, a group each")
     ap.add_argument("--interfaces", action="store_true", help="with --groups (without --pbc): the interfaces between all pairs of the four chains beside the groups' run")
+    ap.add_argument("--interface-residues", action="store_true", help="with --groups --interfaces: the per-residue interface tables beside them; with --stats as well: "
+                                                                      "the statistics of both pair outputs with neither delivered")
     ap.add_argument("--kernel-stats", default=None, help="with --groups --interfaces: a rocprofv3 kernel-stats CSV; the share of the pairs' kernels in it is reported")
     ap.add_argument("--xtc", action="store_true", help="time a GROMACS XTC file against the raw fp32 file and an AMBER NetCDF file of the same decoded frames")
     ap.add_argument("--xtc-distinct", type=int, default=24, help="with --xtc: distinct frames that are encoded and then repeated")
@@ -478,8 +510,10 @@ def main():
     try:
         if args.interfaces and (args.pbc or not args.groups):
             ap.error("--interfaces goes with --groups and without --pbc")
+        if args.interface_residues and not args.interfaces:
+            ap.error("--interface-residues goes with --groups --interfaces")
         if args.xtc or args.stats or args.trr or (args.groups and not args.pbc):
-            lines = stats_mode(args, scratch) if args.stats else trr_mode(args, scratch) if args.trr else xtc_mode(args, scratch) if args.xtc \
+            lines = groups_mode(args, scratch) if args.interface_residues else stats_mode(args, scratch) if args.stats else trr_mode(args, scratch) if args.trr else xtc_mode(args, scratch) if args.xtc \
                 else groups_mode(args, scratch)
             print("\n".join(lines))
             if args.out:
