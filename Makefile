@@ -19,7 +19,7 @@ all: $(LIBDIR)/libfreesasa_amd.so $(LIBDIR)/libfreesasa_amd_seam.a
 # Device code lives in ONE translation unit (gpu_kernels.hip); the compiler's per-kernel resource report (registers,
 # scratch, LDS) is kept next to its object: tests/test_capi.py checks that the hot kernels do not spill.  The other
 # .hip files are host code over the HIP runtime (engine_internal.h says who holds what).
-ENGINE_HDRS = $(CSRC)/classifier.h $(CSRC)/engine_internal.h $(CSRC)/sasa_kernels.h $(CSRC)/group_kernels.h $(CSRC)/select_kernels.h $(CSRC)/traj_kernels.h $(CSRC)/xtc_kernels.h $(CSRC)/pbc_kernels.h $(CSRC)/pbc_tri_kernels.h $(CSRC)/vol_kernels.h $(CSRC)/dots_kernels.h $(CSRC)/iface_kernels.h $(CSRC)/contact_kernels.h $(CSRC)/rescontact_kernels.h $(CSRC)/ifsweep_kernels.h $(CSRC)/select_program.h $(CSRC)/sr_caps.h $(CSRC)/lr2_kernels.h $(CSRC)/gpu_parse.h $(CSRC)/protor_table.h include/freesasa_gpu.h include/freesasa_ingest.h
+ENGINE_HDRS = $(CSRC)/classifier.h $(CSRC)/engine_internal.h $(CSRC)/sasa_kernels.h $(CSRC)/group_kernels.h $(CSRC)/select_kernels.h $(CSRC)/traj_kernels.h $(CSRC)/xtc_kernels.h $(CSRC)/pbc_kernels.h $(CSRC)/pbc_tri_kernels.h $(CSRC)/vol_kernels.h $(CSRC)/dots_kernels.h $(CSRC)/iface_kernels.h $(CSRC)/contact_kernels.h $(CSRC)/rescontact_kernels.h $(CSRC)/ifsweep_kernels.h $(CSRC)/select_program.h $(CSRC)/sr_caps.h $(CSRC)/lr2_kernels.h $(CSRC)/kat_kernels.h $(CSRC)/gpu_parse.h $(CSRC)/protor_table.h include/freesasa_gpu.h include/freesasa_ingest.h
 $(LIBDIR)/gpu_kernels.o: $(CSRC)/gpu_kernels.hip $(ENGINE_HDRS)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(LIBDIR)/kernel_resources.txt; rc=$$?; \
@@ -104,7 +104,7 @@ tests/emu/libingest_scalar.so: $(CSRC)/ingest.c $(CSRC)/classifier.c $(CSRC)/cla
 # ... and the loader's parsers under AddressSanitizer + UBSan in a stand-alone program: every text in a block of exactly its size, one line per file of argv
 tests/emu/ingest_check: tests/emu/ingest_check.c $(CSRC)/ingest.c $(CSRC)/classifier.c $(CSRC)/classifier.h $(CSRC)/hostfault.c $(CSRC)/hostfault.h $(CSRC)/protor_table.h include/freesasa_ingest.h
 	$(CC) -O1 -g -std=gnu99 -Wall -ffp-contract=off -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -Iinclude -pthread -o $@ tests/emu/ingest_check.c $(CSRC)/ingest.c $(CSRC)/classifier.c $(CSRC)/hostfault.c -lm
-tests/emu/libsasa_emu.so: tests/emu/emu.cpp $(CSRC)/sasa_kernels.h $(CSRC)/sr_caps.h $(CSRC)/lr2_kernels.h
+tests/emu/libsasa_emu.so: tests/emu/emu.cpp $(CSRC)/sasa_kernels.h $(CSRC)/sr_caps.h $(CSRC)/lr2_kernels.h $(CSRC)/kat_kernels.h
 	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -DSASA_EMU -shared -o $@ tests/emu/emu.cpp -lm
 
 # the selection kernels' phase functions (select_kernels.h) driven over a loaded batch
@@ -145,10 +145,10 @@ tests/emu/groups_pbc_check: tests/emu/emu_groups_pbc.cpp tests/emu/emu_pbc_tri.c
 	$(CXX) -O1 -g -std=c++17 -Wall -Wno-unused-function -Wno-unknown-pragmas -ffp-contract=off -DSASA_EMU -DGPBC_CHECK_MAIN -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -o $@ tests/emu/emu_groups_pbc.cpp -lm
 # run statistics (traj_kernels.h, traj_stats): a shard's partial of the blocks of its outputs
 # molecular volume (vol_kernels.h): the structures' origins, the atoms' terms, the totals over them; and emu.cpp once more, its store phase the volume's
-tests/emu/libvolume_emu.so: tests/emu/emu_volume.cpp tests/emu/emu.cpp $(CSRC)/vol_kernels.h $(CSRC)/sasa_kernels.h $(CSRC)/sr_caps.h $(CSRC)/lr2_kernels.h
+tests/emu/libvolume_emu.so: tests/emu/emu_volume.cpp tests/emu/emu.cpp $(CSRC)/vol_kernels.h $(CSRC)/sasa_kernels.h $(CSRC)/sr_caps.h $(CSRC)/lr2_kernels.h $(CSRC)/kat_kernels.h
 	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -DSASA_EMU -shared -o $@ tests/emu/emu_volume.cpp -lm
 # surface dots (dots_kernels.h): the scan of the masks' popcounts and the expansion; and emu.cpp once more, its store phase the one that keeps the masks
-tests/emu/libdots_emu.so: tests/emu/emu_dots.cpp tests/emu/emu.cpp $(CSRC)/dots_kernels.h $(CSRC)/sasa_kernels.h $(CSRC)/sr_caps.h $(CSRC)/lr2_kernels.h
+tests/emu/libdots_emu.so: tests/emu/emu_dots.cpp tests/emu/emu.cpp $(CSRC)/dots_kernels.h $(CSRC)/sasa_kernels.h $(CSRC)/sr_caps.h $(CSRC)/lr2_kernels.h $(CSRC)/kat_kernels.h
 	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -DSASA_EMU -shared -o $@ tests/emu/emu_dots.cpp -lm
 # ... and scan and expansion (emu_dots.cpp with its main) under AddressSanitizer + UBSan in a stand-alone program: one line per case
 tests/emu/dots_check: tests/emu/emu_dots.cpp $(CSRC)/dots_kernels.h $(CSRC)/sasa_kernels.h $(CSRC)/sr_caps.h

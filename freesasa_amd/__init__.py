@@ -196,6 +196,9 @@ def lib():
                                                         C.c_int, C.c_int, C.c_longlong, C.c_char_p, C.c_int]
         L.freesasa_gpu_lr_neighbors_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _lp, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int]
         L.freesasa_gpu_arc_union_dev.argtypes = [C.c_void_p, _dp, _ip, C.c_int, _dp]
+        L.freesasa_gpu_kat_elementwise_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_double,
+                                                       C.c_void_p, C.c_void_p]
+        L.freesasa_gpu_kat_wave_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.freesasa_gpu_xtc_decode_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.freesasa_gpu_cell_sort_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _lp, C.c_int, C.c_double, C.c_int, C.c_longlong, C.c_longlong, C.c_int] + [C.c_void_p] * 9
         L.freesasa_gpu_cell_sort_cap.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_longlong]
@@ -2215,6 +2218,37 @@ class GpuContext:
         if lib().freesasa_gpu_arc_union_dev(self._h, arcs.ctypes.data_as(_dp), first.ctypes.data_as(_ip), len(sets),
                                             out.ctypes.data_as(_dp)):
             raise RuntimeError("freesasa_gpu_arc_union_dev: " + self.error())
+        return out
+
+    def kat_elementwise(self, op, a=None, b=None, c=None, k=0.0, n=None, outputs=2):
+        """Test hook: the device-only arithmetic, one thread per operand (csrc/kat_kernels.h numbers the ops and says which of
+        the float64 arrays a, b, c and the scalar k each reads).  Returns (out0, out1), NaN where the op writes nothing;
+        `n` and `outputs` (how many output arrays are handed over) default to what the arrays say.  ValueError for
+        arguments that are refused."""
+        arrs = [None if x is None else np.ascontiguousarray(x, dtype=np.float64).reshape(-1) for x in (a, b, c)]
+        if n is None:
+            n = max([x.size for x in arrs if x is not None] or [0])
+        if any(x is not None and x.size < min(max(int(n), 0), 1 << 20) for x in arrs):
+            raise ValueError("kat_elementwise: an array is shorter than n")
+        outs = [np.full(max(int(n), 0), np.nan) if j < outputs else None for j in range(2)]
+        ptr = lambda x: x.ctypes.data if x is not None else None
+        if lib().freesasa_gpu_kat_elementwise_dev(self._h, int(op), ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), int(n), float(k),
+                                                  ptr(outs[0]), ptr(outs[1])):
+            raise ValueError("freesasa_gpu_kat_elementwise_dev: " + self.error())
+        return outs[0], outs[1]
+
+    def kat_wave(self, op, words, rows=None):
+        """Test hook: the lane primitives, `words` (uint64 [rows, 64]) through one full wave (csrc/kat_kernels.h numbers the ops).
+        Returns uint64 [rows, 64]; words=None hands over no arrays.  ValueError for arguments that are refused."""
+        w = None if words is None else np.ascontiguousarray(words, dtype=np.uint64).reshape(-1, 64)
+        if rows is None:
+            rows = 0 if w is None else w.shape[0]
+        if w is not None and w.shape[0] < min(max(int(rows), 0), 4096):
+            raise ValueError("kat_wave: fewer rows than said")
+        out = None if w is None else np.zeros_like(w)
+        if lib().freesasa_gpu_kat_wave_dev(self._h, int(op), None if w is None else w.ctypes.data, int(rows),
+                                           None if out is None else out.ctypes.data):
+            raise ValueError("freesasa_gpu_kat_wave_dev: " + self.error())
         return out
 
     def xtc_decode(self, file_bytes, n_frames, n_atoms):

@@ -49,6 +49,7 @@
 #include "../../include/freesasa_ingest.h"
 #include "sasa_kernels.h"
 #include "lr2_kernels.h"
+#include "kat_kernels.h"
 #include "group_kernels.h"
 #include "select_kernels.h"
 #include "traj_kernels.h"
@@ -93,6 +94,10 @@ hipError_t kl_class_sums(const double *d_sasa, const unsigned char *d_class, con
 hipError_t kl_residue_areas(const double *d_sasa, const unsigned char *d_class, const unsigned char *d_backbone, const int64_t *d_res_first,
                             const short *d_ref_row, const double *d_ref_table, double *d_abs, double *d_rel, int n_res, hipStream_t st);
 hipError_t kl_arc_kat(const double *d_arcs, const int *d_first, int n_sets, double *d_out, hipStream_t st);
+/* test hooks (kat_kernels.h): n operands in workgroups of 256; `rows` rows of 64 words through one wave */
+hipError_t kl_kat_elementwise(int op, const double *d_a, const double *d_b, const double *d_c, double k, double *d_o0, double *d_o1, int n,
+                              hipStream_t st);
+hipError_t kl_kat_wave(int op, const unsigned long long *d_in, unsigned long long *d_out, int rows, hipStream_t st);
 hipError_t kl_widen_f32(const float *d_in, double *d_out, long long n, hipStream_t st);
 hipError_t kl_narrow_f64(const double *d_in, float *d_out, long long n, hipStream_t st);
 void kl_dump_phase_clocks(void); /* (dev builds with -DSASA_PHASE_TIMING; else nothing) */

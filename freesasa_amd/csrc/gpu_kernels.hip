@@ -929,6 +929,29 @@ hipError_t kl_arc_kat(const double *d_arcs, const int *d_first, int n_sets, doub
     hipLaunchKernelGGL(k_lr2_arc_kat, dim3(1), dim3(64), 0, st, d_arcs, d_first, n_sets, d_out);
     return hipGetLastError();
 }
+/* test hooks (kat_kernels.h): the device-only arithmetic, a thread per operand, and the lane primitives, ONE full wave
+   (op and k are kernel arguments: the switch is scalar control flow, and k sits in scalar registers) */
+__global__ __launch_bounds__(256) void k_kat_elementwise(int op, const double *a, const double *b, const double *c, double k, double *o0,
+                                                         double *o1, int n)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) kat_elementwise(op, a, b, c, k, o0, o1, i);
+}
+__global__ __launch_bounds__(64) void k_kat_wave(int op, const unsigned long long *in, unsigned long long *out, int rows)
+{
+    kat_wave(op, in, out, rows, threadIdx.x);
+}
+hipError_t kl_kat_elementwise(int op, const double *d_a, const double *d_b, const double *d_c, double k, double *d_o0, double *d_o1, int n,
+                              hipStream_t st)
+{
+    hipLaunchKernelGGL(k_kat_elementwise, dim3((n + 255) / 256), dim3(256), 0, st, op, d_a, d_b, d_c, k, d_o0, d_o1, n);
+    return hipGetLastError();
+}
+hipError_t kl_kat_wave(int op, const unsigned long long *d_in, unsigned long long *d_out, int rows, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_kat_wave, dim3(1), dim3(64), 0, st, op, d_in, d_out, rows);
+    return hipGetLastError();
+}
 
 /* fp32 trajectory frames widened on the device: an INPUT format, the arithmetic stays fp64 */
 __global__ __launch_bounds__(256) void k_widen_f32(const float *in, double *out, long long n)

@@ -248,6 +248,61 @@ extern "C" int freesasa_gpu_arc_union_dev(freesasa_gpu_ctx *c, const double *arc
     });
 }
 
+/* ------------------------------------------------------------------ test hooks: device-only arithmetic and lane primitives (kat_kernels.h) */
+
+extern "C" int freesasa_gpu_kat_elementwise_dev(freesasa_gpu_ctx *c, int op, const double *a, const double *b, const double *in_c, long long n,
+                                                double k, double *out0, double *out1)
+{
+    if (!c) return -1;
+    return guarded_ctx(c, [&]() -> int {
+    c->err[0] = 0;
+    const int arrays = sasa::kat_ew_arrays(op);
+    if (!arrays) return ctx_fail(c, "unknown op %d", op);
+    if (n < 1 || n > KAT_EW_MAX) return ctx_fail(c, "n must be 1 .. %d", KAT_EW_MAX);
+    const double *in[3] = {a, b, in_c};
+    double *out[2] = {out0, out1};
+    for (int j = 0; j < 3; ++j)
+        if ((arrays >> j & 1) && !in[j]) return ctx_fail(c, "null argument");
+    for (int j = 0; j < 2; ++j)
+        if ((arrays >> (4 + j) & 1) && !out[j]) return ctx_fail(c, "null argument");
+    if (freesasa_gpu_wait(c)) return -1; /* (batches submitted asynchronously come first, as for every synchronous entry) */
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = sizeof(double) * (size_t)n;
+    if (ensure(c, c->seg, 5 * bytes)) return -1;
+    double *d[5];
+    for (int j = 0; j < 5; ++j) d[j] = (double *)c->seg.p + (size_t)j * (size_t)n;
+    for (int j = 0; j < 3; ++j)
+        if (arrays >> j & 1) HIP_TRY(c, hipMemcpyAsync(d[j], in[j], bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, kl_kat_elementwise(op, d[0], d[1], d[2], k, d[3], d[4], (int)n, c->stream));
+    for (int j = 0; j < 2; ++j)
+        if (arrays >> (4 + j) & 1) HIP_TRY(c, hipMemcpyAsync(out[j], d[3 + j], bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+    });
+}
+
+extern "C" int freesasa_gpu_kat_wave_dev(freesasa_gpu_ctx *c, int op, const uint64_t *in, int rows, uint64_t *out)
+{
+    if (!c) return -1;
+    return guarded_ctx(c, [&]() -> int {
+    c->err[0] = 0;
+    if (op < 0 || op >= sasa::KAT_WAVE_OPS) return ctx_fail(c, "unknown op %d", op);
+    if (rows < 1 || rows > KAT_WAVE_ROWS_MAX) return ctx_fail(c, "rows must be 1 .. %d", KAT_WAVE_ROWS_MAX);
+    if (!in || !out) return ctx_fail(c, "null argument");
+    if (const char *why = sasa::kat_wave_refusal(op, (const unsigned long long *)in, rows)) return ctx_fail(c, "%s", why);
+    if (freesasa_gpu_wait(c)) return -1;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = 8 * (size_t)rows * LR2_LANES;
+    if (ensure(c, c->seg, 2 * bytes)) return -1;
+    unsigned long long *d_in = (unsigned long long *)c->seg.p, *d_out = d_in + (size_t)rows * LR2_LANES;
+    HIP_TRY(c, hipMemcpyAsync(d_in, in, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, kl_kat_wave(op, d_in, d_out, rows, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+    });
+}
+
 /* ------------------------------------------------------------------ test hook: the cell sort on its own (include/freesasa_gpu.h) */
 
 static_assert(FREESASA_GPU_CELL_SORT_STATUS_WORDS == sasa::ST_WORDS, "the hook hands out every status word");

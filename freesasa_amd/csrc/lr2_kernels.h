@@ -54,7 +54,7 @@ long long wave_exchange(long long v, int src);
 #define LR2_SHIFT_IN_LT(w, v, lim) (((w) << 1) | ((v) < (lim) ? 1u : 0u))
 #define LR2_UNIFORM(v) (v)
 #define LR2_READLANE(v, src) LR2_SHFL((v), (src))
-#define LR2_MUL24(a, b) ((int)(a) * (int)(b))
+#define LR2_MUL24(a, b) ((int)((unsigned)(a) * (unsigned)(b))) /* (the low 32 bits, as the device's: a signed product beyond 2^31 is not defined here) */
 #define LR2_UMUL24(a, b) ((unsigned)(a) * (unsigned)(b))
 #define LR2_RCPF(x) (1.0f / (x))
 #define LR2_RSQF(x) (1.0f / sqrtf(x))
@@ -207,16 +207,20 @@ SASA_D int lr2_div3(int v) { return LR2_MUL24(v, 43) >> 7; }  /* v / 3 for 0 <= 
 #define LR2_H2(x, h) do { double g_; sqrt_rh((x), g_, (h)); } while (0)
 #endif
 /* The screening's limit for v = b' + a' t (lr2_record): a neighbor cuts an arc when |v| h < 1, h = 1/(2 Ri') as LR2_H2
-   made it.  Comparing v with T = (1 - 2^-49) / h spares the product per (neighbor, slice); T from 4 A h (= 1/h up to
-   h's own 4e-15) and one Newton step (T h = 1 to 2^-52), so |v| < T guarantees |v| h < 1 - 2^-50: the arc pass never
-   takes the root of a negative number (lr2_arc_alpha), and the two passes agree on what an arc is because both read
-   the mask.  Against the exact rule (|v| / (2 Ri') < 1) a decision can differ only where cos(alpha) is within 2e-15 of
-   +-1: an arc of half-width < 6e-8 rad, or one that leaves that much of its circle (tests/test_adversarial.py). */
+   made it.  Comparing v with T = (1 - 14 u) / h, u = 2^-53, spares the product per (neighbor, slice); T from 4 A h (= 1/h
+   up to h's own 4e-15) and one Newton step (T1 h = 1 up to T1's own rounding, u; the product below rounds once more), so
+   T h lies in (1 - 14 u)(1 -+ u)^2, inside (1 - 16 u, 1 - 12 u): RN(T h) is within 2^-49 = 16 u of 1, below it, and the
+   largest double below T, at most T (1 - u), has |v| h < (1 - 12 u)(1 - u) < 1 - 2^-50 = 1 - 8 u: |v| < T guarantees
+   |v| h < 1 - 2^-50, the arc pass never takes the root of a negative number (lr2_arc_alpha), and the two passes agree on
+   what an arc is because both read the mask.  (Until tests/test_device_arith.py measured it the factor was 1 - 2^-49, which
+   put T h up to 2^-52 further from 1 than the 2^-49 meant: 1 - RN(T h) reached 18 u.)  Against the exact rule
+   (|v| / (2 Ri') < 1) a decision can differ only where cos(alpha) is within 2e-15 of +-1: an arc of half-width < 6e-8 rad,
+   or one that leaves that much of its circle (tests/test_adversarial.py). */
 SASA_D double lr2_arc_limit(double A, double h)
 {
     const double T0 = (4.0 * A) * h;
     const double T1 = fma(T0, fma(-T0, h, 1.0), T0);
-    return T1 * (1.0 - 0x1p-49);
+    return T1 * (1.0 - 0x1.cp-50); /* 1 - 14 x 2^-53 */
 }
 #define LR2_LANES 64
 /* The tile shape of the library's default parameters on sparse input - 6 atoms x 20 slices, two mask words, two

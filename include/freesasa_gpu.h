@@ -195,6 +195,22 @@ int freesasa_gpu_test_node_cpus(const char *sysfs_root, const char *pci_address,
 int freesasa_gpu_lr_neighbors_dev(freesasa_gpu_ctx *ctx, const double *d_xyz, const double *d_radii, const int64_t *offsets,
                                   int n_structs, double probe_radius, int *d_nn, int *d_nb, int nb_cap);
 int freesasa_gpu_arc_union_dev(freesasa_gpu_ctx *ctx, const double *arcs, const int *first, int n_sets, double *out);
+/* Test hooks: the arithmetic and the lane primitives that are defined one way for the device and another for the CPU
+   emulation of the kernels (hardware seeds, inline assembly, data-parallel scans, mbcnt, ballot, readlane, 24-bit products)
+   and the functions built on the seeds, run on the device on their own: known-answer kernels that call the product's own
+   macros and functions (csrc/kat_kernels.h, which numbers the ops and says what each reads and writes).  Host arrays.
+   _kat_elementwise_dev: n operands (1 .. 2^20), a thread each in workgroups of 256: thread i reads a[i], b[i], c[i] - those the
+   op takes; the others may be NULL - and the scalar k (a kernel argument: it sits in scalar registers), writes out0[i] and
+   out1[i] - those the op gives.
+   _kat_wave_dev: `rows` (1 .. 4096) rows of 64 64-bit words through ONE full wave, every lane active in every cross-lane
+   operation; lane l of row r reads in[64 r + l] and writes out[64 r + l].
+   Return 0, or -1 with the context's error text; refused before any device call: "unknown op ...", "n must be ...", "rows
+   must be ...", "null argument", a shuffle's source lane beyond 63, an operand beyond the range of lr2_div9 / lr2_div3, an
+   odd number of rows for the 64-bit shuffle.  tests/test_device_arith_gpu.py holds every op to exact or extended-precision
+   references through them (tests/device_arith_ref.py), tests/test_device_arith.py the CPU definitions to the same. */
+int freesasa_gpu_kat_elementwise_dev(freesasa_gpu_ctx *ctx, int op, const double *a, const double *b, const double *c, long long n, double k,
+                                     double *out0, double *out1);
+int freesasa_gpu_kat_wave_dev(freesasa_gpu_ctx *ctx, int op, const uint64_t *in, int rows, uint64_t *out);
 /* Test hook: the two XTC decode kernels (xtc_scan, xtc_unpack: "GROMACS XTC input" below) run on the device on their own, by the
    launches the file drivers make for a shard.  Host arrays: `bytes` is n_frames whole frames of n_atoms atoms, one behind the
    other, as a file holds them (len bytes); their descriptors are made as the drivers make them (freesasa_gpu_xtc_frame_desc, the

@@ -81,3 +81,35 @@ def cell_sort(xyz, radii, offsets, probe=1.4, cells_cap=0, shared_radii=False):
     return {"status": status, "error": int(status[ref.ST_ERROR]), "retry": int(status[ref.ST_RETRY]), "occ_sum": int(status[ref.ST_OCC_SUM]),
             "occ_n": int(status[ref.ST_OCC_N]), "cells": int(status[ref.ST_CELLS:ref.ST_CELLS + 2].view(np.int64)[0]), "occ_stride": stride,
             "cells_cap": cap, "grid": grid, "ncells": ncells, "sq": sq.reshape(-1, 4), "s_idx": s_idx, "cell_start": cell_start}
+
+
+def kat_elementwise(op, a=None, b=None, c=None, k=0.0, n=None, outputs=2):
+    """The emulated elementwise known-answer kernel (emu_kat_elementwise), with GpuContext.kat_elementwise's arguments, result
+    and refusals."""
+    arrs = [None if x is None else np.ascontiguousarray(x, dtype=np.float64).reshape(-1) for x in (a, b, c)]
+    if n is None:
+        n = max([x.size for x in arrs if x is not None] or [0])
+    if any(x is not None and x.size < min(max(int(n), 0), 1 << 20) for x in arrs):
+        raise ValueError("kat_elementwise: an array is shorter than n")
+    outs = [np.full(max(int(n), 0), np.nan) if j < outputs else None for j in range(2)]
+    ptr = lambda x: x.ctypes.data if x is not None else None
+    L = _load()
+    L.emu_kat_elementwise.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_double, C.c_void_p, C.c_void_p]
+    if L.emu_kat_elementwise(int(op), ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), int(n), float(k), ptr(outs[0]), ptr(outs[1])):
+        raise ValueError("emu_kat_elementwise: refused")
+    return outs[0], outs[1]
+
+
+def kat_wave(op, words, rows=None):
+    """The emulated wave known-answer kernel (emu_kat_wave): uint64 [rows, 64] in and out, as GpuContext.kat_wave."""
+    w = None if words is None else np.ascontiguousarray(words, dtype=np.uint64).reshape(-1, 64)
+    if rows is None:
+        rows = 0 if w is None else w.shape[0]
+    if w is not None and w.shape[0] < min(max(int(rows), 0), 4096):
+        raise ValueError("kat_wave: fewer rows than said")
+    out = None if w is None else np.zeros_like(w)
+    L = _load()
+    L.emu_kat_wave.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    if L.emu_kat_wave(int(op), None if w is None else w.ctypes.data, int(rows), None if out is None else out.ctypes.data):
+        raise ValueError("emu_kat_wave: refused")
+    return out

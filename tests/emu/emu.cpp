@@ -15,6 +15,7 @@
 #include <ucontext.h>
 
 #include "../../freesasa_amd/csrc/lr2_kernels.h"
+#include "../../freesasa_amd/csrc/kat_kernels.h"
 
 using namespace sasa;
 
@@ -575,6 +576,31 @@ extern "C" void emu_sqrt_rh(const double *x, double *g, double *h, int n)
 extern "C" void emu_atan2_fast(const double *y, const double *x, double *out, int n)
 {
     for (int i = 0; i < n; ++i) out[i] = atan2_fast(y[i], x[i]);
+}
+
+/* the known-answer kernels of kat_kernels.h (what freesasa_gpu_kat_elementwise_dev / _kat_wave_dev run on the device), with
+   the hooks' refusals: 0, or -1 for an unknown op, a size out of range, a missing array or operands the op does not take.
+   The wave ops run their 64 lanes as fibers in lock step, like the tile kernel */
+extern "C" int emu_kat_elementwise(int op, const double *a, const double *b, const double *c, long long n, double k, double *o0, double *o1)
+{
+    const int arrays = kat_ew_arrays(op);
+    if (!arrays || n < 1 || n > KAT_EW_MAX) return -1;
+    if (((arrays & 1) && !a) || ((arrays & 2) && !b) || ((arrays & 4) && !c) || ((arrays & 16) && !o0) || ((arrays & 32) && !o1)) return -1;
+    for (int i = 0; i < (int)n; ++i) kat_elementwise(op, a, b, c, k, o0, o1, i);
+    return 0;
+}
+struct KatRun { int op; const unsigned long long *in; unsigned long long *out; int rows; };
+static void kat_lane_body(int lane, void *ctx)
+{
+    const KatRun *r = (const KatRun *)ctx;
+    kat_wave(r->op, r->in, r->out, r->rows, lane);
+}
+extern "C" int emu_kat_wave(int op, const unsigned long long *in, int rows, unsigned long long *out)
+{
+    if (op < 0 || op >= KAT_WAVE_OPS || rows < 1 || rows > KAT_WAVE_ROWS_MAX || !in || !out || kat_wave_refusal(op, in, rows)) return -1;
+    KatRun run = {op, in, out, rows};
+    sasa_emu::run_wave(kat_lane_body, &run);
+    return 0;
 }
 
 /* the arc union and sweep of the Lee-Richards kernel on sets of arcs given in the order of their mid-points

@@ -5,7 +5,8 @@ result bit for bit given equal arc end points, but computes cos(alpha) with reci
 acos with its own polynomial.  Since round 3 the arc pass spends two orders of magnitude of the 1e-4 A^2
 contract on speed (degree-12 acos, 6e-13 relative; 1/(2 Ri') to 4e-15; slice planes in closed form, where the
 reference's accumulated z drifts by ~ns ulp(z)): held to LR_TOL = 1e-9 A^2 per atom here (observed 4.5e-11 at worst
-on these inputs, 3e-12 rms; 4e-10 with coordinates near 1e4 A); on this box only the device's v_rsq_f64 seed remains untested."""
+on these inputs, 3e-12 rms; 4e-10 with coordinates near 1e4 A); the device's own definitions - the v_rsq_f64 seed, the inline
+assembly, the lane primitives - are held to the same references on the MI355X by tests/test_device_arith_gpu.py."""
 import numpy as np
 import pytest
 
