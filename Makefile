@@ -2,8 +2,8 @@
 #   make            -> freesasa_amd/lib/libfreesasa_amd.so (stand-alone drop-in library)
 #                      freesasa_amd/lib/libfreesasa_amd_seam.a (seam objects for a drop-in
 #                      build of the reference)
-#   make emu        -> tests/emu/libsasa_emu.so, libselect_emu.so, libgroups_emu.so, libtraj_emu.so, libtraj_groups_emu.so, libtraj_pairs_emu.so, libtraj_pair_res_emu.so, libdcd_emu.so, libnc_emu.so, libxtc_emu.so, libtrr_emu.so, libpbc_emu.so, libpbc_tri_emu.so, libgroups_pbc_emu.so, libstats_emu.so, libvolume_emu.so, libdots_emu.so, libiface_emu.so, libiface_res_emu.so, libcontacts_emu.so, librescontacts_emu.so, libifsweep_emu.so  (TESTS ONLY: the kernel phase
-#                      functions driven on the CPU; never linked into the product) and tests/emu/dcd_check, tests/emu/cell_check, tests/emu/nc_check, tests/emu/xtc_check, tests/emu/xtc_emu_check, tests/emu/trr_check, tests/emu/stats_check, tests/emu/dots_check, tests/emu/iface_check, tests/emu/iface_res_check, tests/emu/contacts_check, tests/emu/rescontacts_check, tests/emu/ifsweep_check, tests/emu/groups_pbc_check, tests/emu/pair_res_check (the DCD, NetCDF, XTC and TRR header parsers, the cell arithmetic, the emulated XTC decode, the merge of the run statistics and the emulated scan and expansion of the surface dots and the emulated phases of the interfaces between chain groups and of their per-residue, atom-atom contact and residue-residue contact tables and of the file sweep's interface kernels and the segments and rows of the per-residue interface tables per frame under sanitizers) and tests/emu/ingest_check (the host loader's PDB / mmCIF parsers under sanitizers)
+#   make emu        -> tests/emu/libsasa_emu.so, libselect_emu.so, libgroups_emu.so, libtraj_emu.so, libtraj_groups_emu.so, libtraj_pairs_emu.so, libtraj_pair_res_emu.so, libdcd_emu.so, libnc_emu.so, libxtc_emu.so, libtrr_emu.so, libpbc_emu.so, libpbc_tri_emu.so, libgroups_pbc_emu.so, libstats_emu.so, libvolume_emu.so, libdots_emu.so, libiface_emu.so, libiface_res_emu.so, libcontacts_emu.so, librescontacts_emu.so, libifsweep_emu.so, libocc_emu.so  (TESTS ONLY: the kernel phase
+#                      functions driven on the CPU; never linked into the product) and tests/emu/dcd_check, tests/emu/cell_check, tests/emu/nc_check, tests/emu/xtc_check, tests/emu/xtc_emu_check, tests/emu/trr_check, tests/emu/stats_check, tests/emu/dots_check, tests/emu/iface_check, tests/emu/iface_res_check, tests/emu/contacts_check, tests/emu/rescontacts_check, tests/emu/ifsweep_check, tests/emu/occ_check, tests/emu/groups_pbc_check, tests/emu/pair_res_check (the DCD, NetCDF, XTC and TRR header parsers, the cell arithmetic, the emulated XTC decode, the merge of the run statistics and the emulated scan and expansion of the surface dots and the emulated phases of the interfaces between chain groups and of their per-residue, atom-atom contact and residue-residue contact tables and of the file sweep's interface kernels and of the contact occupancy map and the segments and rows of the per-residue interface tables per frame under sanitizers) and tests/emu/ingest_check (the host loader's PDB / mmCIF parsers under sanitizers)
 #   make oracle     -> oracle/ (TESTS ONLY) ; make tools -> tools/libsasa_synth.so
 HIPCC   ?= /opt/rocm/bin/hipcc
 CC      ?= gcc
@@ -19,7 +19,7 @@ all: $(LIBDIR)/libfreesasa_amd.so $(LIBDIR)/libfreesasa_amd_seam.a
 # Device code lives in ONE translation unit (gpu_kernels.hip); the compiler's per-kernel resource report (registers,
 # scratch, LDS) is kept next to its object: tests/test_capi.py checks that the hot kernels do not spill.  The other
 # .hip files are host code over the HIP runtime (engine_internal.h says who holds what).
-ENGINE_HDRS = $(CSRC)/classifier.h $(CSRC)/engine_internal.h $(CSRC)/sasa_kernels.h $(CSRC)/group_kernels.h $(CSRC)/select_kernels.h $(CSRC)/traj_kernels.h $(CSRC)/xtc_kernels.h $(CSRC)/pbc_kernels.h $(CSRC)/pbc_tri_kernels.h $(CSRC)/vol_kernels.h $(CSRC)/dots_kernels.h $(CSRC)/iface_kernels.h $(CSRC)/contact_kernels.h $(CSRC)/rescontact_kernels.h $(CSRC)/ifsweep_kernels.h $(CSRC)/select_program.h $(CSRC)/sr_caps.h $(CSRC)/lr2_kernels.h $(CSRC)/kat_kernels.h $(CSRC)/gpu_parse.h $(CSRC)/protor_table.h include/freesasa_gpu.h include/freesasa_ingest.h
+ENGINE_HDRS = $(CSRC)/classifier.h $(CSRC)/engine_internal.h $(CSRC)/sasa_kernels.h $(CSRC)/group_kernels.h $(CSRC)/select_kernels.h $(CSRC)/traj_kernels.h $(CSRC)/xtc_kernels.h $(CSRC)/pbc_kernels.h $(CSRC)/pbc_tri_kernels.h $(CSRC)/vol_kernels.h $(CSRC)/dots_kernels.h $(CSRC)/iface_kernels.h $(CSRC)/contact_kernels.h $(CSRC)/rescontact_kernels.h $(CSRC)/ifsweep_kernels.h $(CSRC)/occupancy_kernels.h $(CSRC)/select_program.h $(CSRC)/sr_caps.h $(CSRC)/lr2_kernels.h $(CSRC)/kat_kernels.h $(CSRC)/gpu_parse.h $(CSRC)/protor_table.h include/freesasa_gpu.h include/freesasa_ingest.h
 $(LIBDIR)/gpu_kernels.o: $(CSRC)/gpu_kernels.hip $(ENGINE_HDRS)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(LIBDIR)/kernel_resources.txt; rc=$$?; \
@@ -27,7 +27,7 @@ $(LIBDIR)/gpu_kernels.o: $(CSRC)/gpu_kernels.hip $(ENGINE_HDRS)
 $(LIBDIR)/gpu_%.o: $(CSRC)/gpu_%.hip $(ENGINE_HDRS)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-GPU_OBJS = $(LIBDIR)/gpu_kernels.o $(LIBDIR)/gpu_engine.o $(LIBDIR)/gpu_ops.o $(LIBDIR)/gpu_hostbatch.o $(LIBDIR)/gpu_drivers.o $(LIBDIR)/gpu_frames.o $(LIBDIR)/gpu_sweep.o $(LIBDIR)/gpu_parse.o $(LIBDIR)/gpu_groups.o $(LIBDIR)/gpu_periodic.o $(LIBDIR)/gpu_volume.o $(LIBDIR)/gpu_dots.o $(LIBDIR)/gpu_interfaces.o
+GPU_OBJS = $(LIBDIR)/gpu_kernels.o $(LIBDIR)/gpu_engine.o $(LIBDIR)/gpu_ops.o $(LIBDIR)/gpu_hostbatch.o $(LIBDIR)/gpu_drivers.o $(LIBDIR)/gpu_frames.o $(LIBDIR)/gpu_sweep.o $(LIBDIR)/gpu_parse.o $(LIBDIR)/gpu_groups.o $(LIBDIR)/gpu_periodic.o $(LIBDIR)/gpu_volume.o $(LIBDIR)/gpu_dots.o $(LIBDIR)/gpu_interfaces.o $(LIBDIR)/gpu_occupancy.o
 
 $(LIBDIR)/seam.o: $(CSRC)/seam.c include/freesasa_amd.h include/freesasa_gpu.h
 	@mkdir -p $(LIBDIR)
@@ -97,7 +97,7 @@ $(LIBDIR)/libfreesasa_amd.so: $(GPU_OBJS) $(LIBDIR)/seam.o $(LIBDIR)/testpoints.
 $(LIBDIR)/libfreesasa_amd_seam.a: $(GPU_OBJS) $(LIBDIR)/seam.o $(LIBDIR)/testpoints.o $(LIBDIR)/dcd.o $(LIBDIR)/netcdf.o $(LIBDIR)/xtc.o $(LIBDIR)/trr.o $(LIBDIR)/cell.o $(LIBDIR)/trajstats.o $(LIBDIR)/ingest.o $(LIBDIR)/classifier.o $(LIBDIR)/select.o $(LIBDIR)/ingest_cache.o $(LIBDIR)/hostfault.o
 	rm -f $@; ar rcs $@ $^
 
-emu: tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so tests/emu/libtraj_groups_emu.so tests/emu/libtraj_pairs_emu.so tests/emu/libtraj_pair_res_emu.so tests/emu/pair_res_check tests/emu/libdcd_emu.so tests/emu/libpbc_emu.so tests/emu/libpbc_tri_emu.so tests/emu/libgroups_pbc_emu.so tests/emu/libnc_emu.so tests/emu/libxtc_emu.so tests/emu/libtrr_emu.so tests/emu/libstats_emu.so tests/emu/libvolume_emu.so tests/emu/libdots_emu.so tests/emu/dcd_check tests/emu/cell_check tests/emu/nc_check tests/emu/xtc_check tests/emu/xtc_emu_check tests/emu/trr_check tests/emu/stats_check tests/emu/dots_check tests/emu/libiface_emu.so tests/emu/iface_check tests/emu/libiface_res_emu.so tests/emu/iface_res_check tests/emu/libcontacts_emu.so tests/emu/contacts_check tests/emu/librescontacts_emu.so tests/emu/rescontacts_check tests/emu/libifsweep_emu.so tests/emu/ifsweep_check tests/emu/groups_pbc_check tests/emu/ingest_check
+emu: tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so tests/emu/libtraj_groups_emu.so tests/emu/libtraj_pairs_emu.so tests/emu/libtraj_pair_res_emu.so tests/emu/pair_res_check tests/emu/libdcd_emu.so tests/emu/libpbc_emu.so tests/emu/libpbc_tri_emu.so tests/emu/libgroups_pbc_emu.so tests/emu/libnc_emu.so tests/emu/libxtc_emu.so tests/emu/libtrr_emu.so tests/emu/libstats_emu.so tests/emu/libvolume_emu.so tests/emu/libdots_emu.so tests/emu/dcd_check tests/emu/cell_check tests/emu/nc_check tests/emu/xtc_check tests/emu/xtc_emu_check tests/emu/trr_check tests/emu/stats_check tests/emu/dots_check tests/emu/libiface_emu.so tests/emu/iface_check tests/emu/libiface_res_emu.so tests/emu/iface_res_check tests/emu/libcontacts_emu.so tests/emu/contacts_check tests/emu/librescontacts_emu.so tests/emu/rescontacts_check tests/emu/libifsweep_emu.so tests/emu/ifsweep_check tests/emu/libocc_emu.so tests/emu/occ_check tests/emu/groups_pbc_check tests/emu/ingest_check
 # the loader with its byte-at-a-time mmCIF tokenizer only: the differential twin of the SSE2 row scanner
 tests/emu/libingest_scalar.so: $(CSRC)/ingest.c $(CSRC)/classifier.c $(CSRC)/classifier.h $(CSRC)/hostfault.c $(CSRC)/hostfault.h $(CSRC)/protor_table.h include/freesasa_ingest.h
 	$(CC) $(CFLAGS) -DFREESASA_INGEST_NO_SIMD -Iinclude -pthread -shared -o $@ $(CSRC)/ingest.c $(CSRC)/classifier.c $(CSRC)/hostfault.c -lm
@@ -183,6 +183,12 @@ tests/emu/libifsweep_emu.so: tests/emu/emu_ifsweep.cpp $(CSRC)/ifsweep_kernels.h
 # ... and the same phases (emu_ifsweep.cpp with its main) under AddressSanitizer + UBSan in a stand-alone program: one line per case
 tests/emu/ifsweep_check: tests/emu/emu_ifsweep.cpp $(CSRC)/ifsweep_kernels.h $(CSRC)/sasa_kernels.h
 	$(CXX) -O1 -g -std=c++17 -Wall -Wno-unused-function -Wno-unknown-pragmas -ffp-contract=off -DSASA_EMU -DIFSWEEP_CHECK_MAIN -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -o $@ tests/emu/emu_ifsweep.cpp -lm
+# the residue contact occupancy map (occupancy_kernels.h): the keys of a chunk, the first occurrences with the block scan, the merge by ranks, the accumulation and the reverse rows
+tests/emu/libocc_emu.so: tests/emu/emu_occupancy.cpp $(CSRC)/occupancy_kernels.h $(CSRC)/iface_kernels.h $(CSRC)/lr2_kernels.h $(CSRC)/sasa_kernels.h $(CSRC)/sr_caps.h
+	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -DSASA_EMU -shared -o $@ tests/emu/emu_occupancy.cpp -lm
+# ... and the same phases (emu_occupancy.cpp with its main) under AddressSanitizer + UBSan in a stand-alone program: one line per case
+tests/emu/occ_check: tests/emu/emu_occupancy.cpp $(CSRC)/occupancy_kernels.h $(CSRC)/iface_kernels.h $(CSRC)/lr2_kernels.h $(CSRC)/sasa_kernels.h $(CSRC)/sr_caps.h
+	$(CXX) -O1 -g -std=c++17 -Wall -Wno-unused-function -Wno-unknown-pragmas -ffp-contract=off -DSASA_EMU -DOCC_CHECK_MAIN -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -o $@ tests/emu/emu_occupancy.cpp -lm
 
 tests/emu/libstats_emu.so: tests/emu/emu_stats.cpp $(CSRC)/traj_kernels.h $(CSRC)/select_kernels.h $(CSRC)/select_program.h $(CSRC)/sasa_kernels.h include/freesasa_ingest.h
 	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -DSASA_EMU -Iinclude -shared -o $@ tests/emu/emu_stats.cpp -lm
@@ -251,7 +257,7 @@ tools:
 	$(MAKE) -C tools
 
 clean:
-	rm -rf $(LIBDIR) tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so tests/emu/libtraj_groups_emu.so tests/emu/libtraj_pairs_emu.so tests/emu/libtraj_pair_res_emu.so tests/emu/pair_res_check tests/emu/libdcd_emu.so tests/emu/libpbc_emu.so tests/emu/libpbc_tri_emu.so tests/emu/libgroups_pbc_emu.so tests/emu/libnc_emu.so tests/emu/libxtc_emu.so tests/emu/dcd_check tests/emu/cell_check tests/emu/nc_check tests/emu/xtc_check tests/emu/xtc_emu_check tests/emu/xtc_*.o tests/emu/libtrr_emu.so tests/emu/trr_check tests/emu/trr_*.o tests/emu/libstats_emu.so tests/emu/stats_check tests/emu/libvolume_emu.so tests/emu/libdots_emu.so tests/emu/dots_check tests/emu/libiface_emu.so tests/emu/iface_check tests/emu/libiface_res_emu.so tests/emu/iface_res_check tests/emu/libcontacts_emu.so tests/emu/contacts_check tests/emu/librescontacts_emu.so tests/emu/rescontacts_check tests/emu/libifsweep_emu.so tests/emu/ifsweep_check tests/emu/groups_pbc_check tests/emu/ingest_check
+	rm -rf $(LIBDIR) tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so tests/emu/libtraj_groups_emu.so tests/emu/libtraj_pairs_emu.so tests/emu/libtraj_pair_res_emu.so tests/emu/pair_res_check tests/emu/libdcd_emu.so tests/emu/libpbc_emu.so tests/emu/libpbc_tri_emu.so tests/emu/libgroups_pbc_emu.so tests/emu/libnc_emu.so tests/emu/libxtc_emu.so tests/emu/dcd_check tests/emu/cell_check tests/emu/nc_check tests/emu/xtc_check tests/emu/xtc_emu_check tests/emu/xtc_*.o tests/emu/libtrr_emu.so tests/emu/trr_check tests/emu/trr_*.o tests/emu/libstats_emu.so tests/emu/stats_check tests/emu/libvolume_emu.so tests/emu/libdots_emu.so tests/emu/dots_check tests/emu/libiface_emu.so tests/emu/iface_check tests/emu/libiface_res_emu.so tests/emu/iface_res_check tests/emu/libcontacts_emu.so tests/emu/contacts_check tests/emu/librescontacts_emu.so tests/emu/rescontacts_check tests/emu/libifsweep_emu.so tests/emu/ifsweep_check tests/emu/libocc_emu.so tests/emu/occ_check tests/emu/groups_pbc_check tests/emu/ingest_check
 	$(MAKE) -C oracle clean
 	$(MAKE) -C tools clean
 .PHONY: all emu oracle tools clean asan asan-test

@@ -48,6 +48,12 @@ class Stats(C.Structure):
                 ("ms_kernel", C.c_double), ("ms_total", C.c_double)]
 
 
+class _OccupancyTable(C.Structure):
+    """freesasa_gpu_contact_occupancy_table_t (include/freesasa_gpu.h): the library's arrays of a run table's snapshot."""
+    _fields_ = [("n_frames", C.c_longlong), ("n_rows", C.c_longlong), ("keys", C.POINTER(C.c_int32)), ("frames", _lp), ("frames_either", _lp),
+                ("counts", _lp), ("area", _dp), ("span", _lp), ("reverse", C.POINTER(C.c_int32))]
+
+
 _lib = None
 
 
@@ -158,6 +164,21 @@ def lib():
             _lp, C.c_int, C.c_longlong, _llp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.freesasa_gpu_calc_interface_residue_contacts.argtypes = L.freesasa_gpu_calc_interface_contacts.argtypes[:-3] + [
             _lp, C.c_int, C.c_longlong, _llp, _lp, _i32p, _i32p, _dp, _i32p, C.c_int, C.c_char_p, C.c_int]
+        _otp = C.POINTER(_OccupancyTable)
+        L.freesasa_gpu_contact_occupancy_open.argtypes = [_dp, C.c_int, _i32p, C.c_int, _lp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
+                                                          C.c_char_p, C.c_int]
+        L.freesasa_gpu_contact_occupancy_open.restype = C.c_void_p
+        L.freesasa_gpu_contact_occupancy_add_frames.argtypes = [C.c_void_p, _dp, C.c_int, _lp]
+        L.freesasa_gpu_contact_occupancy_add_rows.argtypes = [C.c_void_p, C.c_int, _lp, _i32p, _i32p, _dp]
+        L.freesasa_gpu_contact_occupancy_table.argtypes = [C.c_void_p, _otp]
+        L.freesasa_gpu_contact_occupancy_table_free.argtypes = [_otp]
+        L.freesasa_gpu_contact_occupancy_table_free.restype = None
+        L.freesasa_gpu_contact_occupancy_close.argtypes = [C.c_void_p]
+        L.freesasa_gpu_contact_occupancy_close.restype = None
+        L.freesasa_gpu_contact_occupancy_error.argtypes = [C.c_void_p]
+        L.freesasa_gpu_contact_occupancy_error.restype = C.c_char_p
+        L.freesasa_gpu_calc_contact_occupancy.argtypes = [_dp, C.c_int, _dp, C.c_int, _i32p, C.c_int, _lp, C.c_int, C.c_double, C.c_int, C.c_int,
+                                                          _lp, _otp, C.c_int, C.c_char_p, C.c_int]
         L.freesasa_gpu_sr_volume_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _lp, C.c_int, C.c_double, C.c_int,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.freesasa_gpu_calc_volume.argtypes = [_dp, _dp, _lp, C.c_int, C.c_double, C.c_int, _dp, _ip, _dp, _dp, _dp, _dp,
@@ -514,6 +535,164 @@ def calc_interface_contacts(xyz, radii, offsets, group, n_groups, probe=1.4, n_p
         raise RuntimeError("freesasa_gpu_calc_interface_contacts: " + err.value.decode())
     ps, pg, areas, so, pa, pb, cf, cp, cn, ca, bm = arrays
     return InterfaceContacts((sasa, iso, totals, gt, ps, pg, areas, so, pa, pb), cf, cp, cn, ca, bm, Dc.value)
+
+
+class ContactOccupancyTable:
+    """A snapshot of the run table of a ContactOccupancy (include/freesasa_gpu.h has the definitions), copied out of the library's
+    arrays: one row per distinct key (g, h, side, res_a, res_b), ascending - keys [U, 5] (int32), frames [U] and frames_either [U]
+    (int64: the frames that hold the key / the key or its reversed key), counts [U, 2] (int64: the sums of n_rows and n_points),
+    area [U, 3] (sum, min, max over the frames that hold the key), span [U, 2] (int64: the first and the last such frame), reverse
+    [U] (int32: the row of the reversed key, or -1) - and n_frames, the frames the run had when it was taken."""
+
+    def __init__(self, n_frames, keys, frames, frames_either, counts, area, span, reverse):
+        self.n_frames = int(n_frames)
+        self.keys, self.frames, self.frames_either, self.counts = keys, frames, frames_either, counts
+        self.area, self.span, self.reverse = area, span, reverse
+        self.n_rows = int(frames.size)
+
+    def occupancy(self):
+        """frames / n_frames: the share of the run's frames in which the key has a row"""
+        return self.frames / float(self.n_frames) if self.n_frames else np.zeros(self.n_rows)
+
+    def occupancy_either(self):
+        """frames_either / n_frames: ... in which the key or its reversed key has one - what a contact map plots"""
+        return self.frames_either / float(self.n_frames) if self.n_frames else np.zeros(self.n_rows)
+
+    def mean_area(self):
+        """area[:, 0] / frames: the mean area over the frames in which the key is present"""
+        return self.area[:, 0] / self.frames
+
+    def pair_rows(self, g, h, side):
+        """the rows of pair (g, h) whose source is side 0 (group g) or 1 (group h), as a range over the arrays"""
+        k = self.keys
+        at = np.nonzero((k[:, 0] == g) & (k[:, 1] == h) & (k[:, 2] == side))[0]
+        return range(int(at[0]), int(at[-1]) + 1) if at.size else range(0, 0)
+
+
+def _occupancy_table(t):
+    """the arrays of a filled _OccupancyTable, copied; the library's blocks are given back"""
+    U = int(t.n_rows)
+    try:
+        take = lambda p, shape, dtype: np.ctypeslib.as_array(p, shape=shape).astype(dtype, copy=True) if U else np.zeros(shape, dtype)
+        return ContactOccupancyTable(t.n_frames, take(t.keys, (U, 5), np.int32), take(t.frames, (U,), np.int64), take(t.frames_either, (U,), np.int64),
+                                     take(t.counts, (U, 2), np.int64), take(t.area, (U, 3), np.float64), take(t.span, (U, 2), np.int64),
+                                     take(t.reverse, (U,), np.int32))
+    finally:
+        lib().freesasa_gpu_contact_occupancy_table_free(C.byref(t))
+
+
+def _occupancy_system(radii, group, res_first):
+    radii, group = _f64(radii).reshape(-1), np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
+    res_first = np.ascontiguousarray(res_first, dtype=np.int64).reshape(-1)
+    if group.size != radii.size:
+        raise ValueError("group must have one id per atom")
+    if res_first.size < 1:
+        raise ValueError("res_first must hold n_res + 1 boundaries")
+    return radii, group, res_first
+
+
+class ContactOccupancy:
+    """freesasa_gpu_contact_occupancy_open(): a streaming accumulator of the residue contact occupancy map of ONE system over the
+    frames of a run (include/freesasa_gpu.h has the definitions): radii [n], group [n] (int32, -1: in no group), n_groups and
+    res_first [n_res + 1] are constant over the run; Shrake-Rupley with n_points <= 128.  add(frames) takes the run's next frames
+    [f, n, 3] and returns frame_counts [f, 2] = (pairs, folded rows) per frame; add_rows() takes frames whose folded rows the
+    caller has already; table() is a snapshot (the accumulator goes on).  The table does not depend on how the frames were cut
+    over the calls or on frames_per_batch.  radii=None: an accumulator for add_rows() only.  A failed add poisons the accumulator:
+    every later call raises with the first failure's message.  Use as a context manager, or close()."""
+
+    def __init__(self, radii, group=None, n_groups=0, res_first=None, probe=1.4, n_points=100, frames_per_batch=0, device=-1):
+        err = C.create_string_buffer(512)
+        i32 = C.POINTER(C.c_int32)
+        self.n_atoms = 0
+        if radii is None:
+            self._h = lib().freesasa_gpu_contact_occupancy_open(None, 0, None, 0, None, 0, probe, n_points, frames_per_batch, device, err, 512)
+        else:
+            radii, group, res_first = _occupancy_system(radii, group, res_first)
+            self.n_atoms = int(radii.size)
+            self._h = lib().freesasa_gpu_contact_occupancy_open(radii.ctypes.data_as(_dp), radii.size, group.ctypes.data_as(i32), n_groups,
+                                                               res_first.ctypes.data_as(_lp), res_first.size - 1, probe, n_points,
+                                                               frames_per_batch, device, err, 512)
+        if not self._h:
+            raise RuntimeError("freesasa_gpu_contact_occupancy_open: " + err.value.decode())
+
+    def _error(self, what):
+        return RuntimeError(what + ": " + lib().freesasa_gpu_contact_occupancy_error(self._h).decode())
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError("the accumulator is closed")
+        return self._h
+
+    def add(self, frames):
+        """freesasa_gpu_contact_occupancy_add_frames(): frames [f, n, 3] (or [n, 3]: one frame) -> frame_counts [f, 2] int64"""
+        h = self._handle()
+        frames = _f64(frames)
+        if self.n_atoms and frames.size % (3 * self.n_atoms):
+            raise ValueError("frames must be [f, n_atoms, 3]")
+        f = frames.size // (3 * self.n_atoms) if self.n_atoms else 0
+        counts = np.zeros((f, 2), dtype=np.int64)
+        if lib().freesasa_gpu_contact_occupancy_add_frames(h, frames.reshape(-1).ctypes.data_as(_dp), f, counts.ctypes.data_as(_lp)):
+            raise self._error("freesasa_gpu_contact_occupancy_add_frames")
+        return counts
+
+    def add_rows(self, frame_first, keys, counts, area):
+        """freesasa_gpu_contact_occupancy_add_rows(): frame_first [f + 1], keys [q, 5], counts [q, 2], area [q]"""
+        h = self._handle()
+        i32 = C.POINTER(C.c_int32)
+        frame_first = np.ascontiguousarray(frame_first, dtype=np.int64).reshape(-1)
+        keys, counts = np.ascontiguousarray(keys, dtype=np.int32).reshape(-1), np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+        area = _f64(area).reshape(-1)
+        if frame_first.size < 1:
+            raise ValueError("frame_first must hold f + 1 boundaries")
+        q = int(frame_first[-1])
+        if q > 0 and (keys.size < 5 * q or counts.size < 2 * q or area.size < q):
+            raise ValueError("keys, counts and area must hold frame_first[-1] rows")
+        if lib().freesasa_gpu_contact_occupancy_add_rows(h, frame_first.size - 1, frame_first.ctypes.data_as(_lp), keys.ctypes.data_as(i32),
+                                                         counts.ctypes.data_as(i32), area.ctypes.data_as(_dp)):
+            raise self._error("freesasa_gpu_contact_occupancy_add_rows")
+
+    def table(self):
+        """freesasa_gpu_contact_occupancy_table() -> ContactOccupancyTable"""
+        t = _OccupancyTable()
+        if lib().freesasa_gpu_contact_occupancy_table(self._handle(), C.byref(t)):
+            raise self._error("freesasa_gpu_contact_occupancy_table")
+        return _occupancy_table(t)
+
+    def close(self):
+        if self._h:
+            lib().freesasa_gpu_contact_occupancy_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def contact_occupancy(frames, radii, group, n_groups, res_first, probe=1.4, n_points=100, frames_per_batch=0, device=-1, frame_counts=False):
+    """freesasa_gpu_calc_contact_occupancy() on host arrays -> ContactOccupancyTable: the one-shot form of ContactOccupancy over
+    frames [f, n, 3]; with frame_counts=True (table, frame_counts [f, 2])."""
+    radii, group, res_first = _occupancy_system(radii, group, res_first)
+    frames = _f64(frames)
+    if frames.size % (3 * max(radii.size, 1)):
+        raise ValueError("frames must be [f, n_atoms, 3]")
+    f = frames.size // (3 * max(radii.size, 1))
+    counts = np.zeros((f, 2), dtype=np.int64)
+    t, err = _OccupancyTable(), C.create_string_buffer(512)
+    if lib().freesasa_gpu_calc_contact_occupancy(frames.reshape(-1).ctypes.data_as(_dp), f, radii.ctypes.data_as(_dp), radii.size,
+                                                 group.ctypes.data_as(C.POINTER(C.c_int32)), n_groups, res_first.ctypes.data_as(_lp),
+                                                 res_first.size - 1, probe, n_points, frames_per_batch, counts.ctypes.data_as(_lp), C.byref(t),
+                                                 device, err, 512):
+        raise RuntimeError("freesasa_gpu_calc_contact_occupancy: " + err.value.decode())
+    table = _occupancy_table(t)
+    return (table, counts) if frame_counts else table
 
 
 def calc_volume(xyz, radii, offsets, probe=1.4, n_points=100, device=-1, per_atom=False):

@@ -62,6 +62,7 @@
 #include "contact_kernels.h"
 #include "rescontact_kernels.h"
 #include "ifsweep_kernels.h"
+#include "occupancy_kernels.h"
 #include "gpu_parse.h"
 
 /* ------------------------------------------------------------------ kernel launchers (gpu_kernels.hip) */
@@ -195,6 +196,14 @@ hipError_t kl_rc_fold(const sasa::ResContactArgs &a, int *scratch, hipStream_t s
    sides follows it); the rows' place in their file and their labels (one thread per residue row).  Neither is launched without rows. */
 hipError_t kl_ifs_side_class(const sasa::IfsClassArgs &a, hipStream_t st);
 hipError_t kl_ifs_res_rows(const sasa::IfsRowArgs &a, hipStream_t st);
+/* the residue contact occupancy map (occupancy_kernels.h): a chunk's keys and frame boundaries out of the folded table (one thread
+   per folded row and per frame boundary); the first occurrences and their scan (a.fl [Q + 1]; scratch: ifr_scan_scratch(Q) ints);
+   the merge by ranks and the accumulation (a.n_new = U + N known: one thread per old and per chunk row, then one per row of the
+   next table); the reverse rows of a snapshot.  None is launched without rows. */
+hipError_t kl_occ_keys(const sasa::OccKeyArgs &a, hipStream_t st);
+hipError_t kl_occ_first(const sasa::OccArgs &a, int *scratch, hipStream_t st);
+hipError_t kl_occ_merge(const sasa::OccArgs &a, hipStream_t st);
+hipError_t kl_occ_reverse(const sasa::OccArgs &a, hipStream_t st);
 
 /* ------------------------------------------------------------------ context (gpu_engine.hip) */
 
@@ -588,6 +597,10 @@ int iface_run(freesasa_gpu_ctx *c, const IfaceCall &k, IfaceRun &r);
    enqueued - to device arrays the context's buffers, the plan's arrays and the zeros; to host arrays the context's buffers (the
    zeros are written at once).  idle = true, once the synchronize has succeeded: the plan's arrays into host arrays, and stats. */
 int iface_deliver(freesasa_gpu_ctx *c, const IfaceCall &k, const IfaceRun &r, bool idle);
+/* The refusals of the residue-residue contact entries about a call's batch, groups, res_first and resolution, before a device is
+   touched, with their messages (the capacities and the output arrays are not looked at): 0, or -1 with the message in msg.  For the
+   callers that make a call of their own and run it through iface_run (gpu_occupancy.hip). */
+int iface_bad_rescontact_call(const IfaceCall &k, char *msg, size_t len);
 
 /* ------------------------------------------------------------------ host-side helpers (gpu_hostbatch.hip) */
 

@@ -159,6 +159,20 @@ int iface_bad_call(const IfaceCall &k, int ctx_device, char *msg, size_t len)
     return bad ? -1 : 0;
 }
 
+} /* namespace */
+
+/* (engine_internal.h) the batch, the contact entries' algorithm and resolution, res_first - in the entries' order */
+int iface_bad_rescontact_call(const IfaceCall &k, char *msg, size_t len)
+{
+    long long rows = 0, contacts = 0;
+    IfaceCall d = k;
+    d.n_contacts = &contacts; d.out_dev = false;
+    d.pair_capacity = d.atom_capacity = d.contact_capacity = d.dot_capacity = 0;
+    return iface_bad_batch(d, msg, len) || iface_bad_contacts(d, msg, len) || iface_bad_residues(d, &rows, msg, len) ? -1 : 0;
+}
+
+namespace {
+
 /* ------------------------------------------------------------------ the stages */
 
 /* steps 1 to 5; at its end the stream is idle (the flags are on the host) */

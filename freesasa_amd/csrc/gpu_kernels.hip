@@ -1610,6 +1610,57 @@ hipError_t kl_ifs_res_rows(const IfsRowArgs &a, hipStream_t st)
     return hipGetLastError();
 }
 
+/* the residue contact occupancy map (occupancy_kernels.h): one thread per row of whatever list the phase walks; the scan of the
+   first-occurrence flags is kl_iface_res_scan */
+__global__ __launch_bounds__(IF_B) void k_occ_keys(OccKeyArgs a)
+{
+    occ_keys(a, (int64_t)blockIdx.x * IF_B + threadIdx.x);
+}
+__global__ __launch_bounds__(IF_B) void k_occ_first(OccArgs a)
+{
+    occ_first(a, (int64_t)blockIdx.x * IF_B + threadIdx.x);
+}
+__global__ __launch_bounds__(IF_B) void k_occ_rank(OccArgs a)
+{
+    occ_rank(a, (int64_t)blockIdx.x * IF_B + threadIdx.x);
+}
+__global__ __launch_bounds__(IF_B) void k_occ_accumulate(OccArgs a)
+{
+    occ_accumulate(a, (int64_t)blockIdx.x * IF_B + threadIdx.x);
+}
+__global__ __launch_bounds__(IF_B) void k_occ_reverse(OccArgs a)
+{
+    occ_reverse(a, (int64_t)blockIdx.x * IF_B + threadIdx.x);
+}
+hipError_t kl_occ_keys(const OccKeyArgs &a, hipStream_t st)
+{
+    if (a.n_rows <= 0) return hipSuccess;
+    const int64_t n = a.n_rows > a.n_frames + 1 ? a.n_rows : a.n_frames + 1;
+    hipLaunchKernelGGL(k_occ_keys, dim3((unsigned)((n + IF_B - 1) / IF_B)), dim3(IF_B), 0, st, a);
+    return hipGetLastError();
+}
+/* a.fl [Q + 1]; scratch: ifr_scan_scratch(Q) ints */
+hipError_t kl_occ_first(const OccArgs &a, int *scratch, hipStream_t st)
+{
+    if (a.n_rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_occ_first, dim3((unsigned)((a.n_rows + IF_B - 1) / IF_B)), dim3(IF_B), 0, st, a);
+    return kl_iface_res_scan(a.fl, a.n_rows, scratch, st);
+}
+hipError_t kl_occ_merge(const OccArgs &a, hipStream_t st)
+{
+    if (a.n_rows <= 0 || a.n_new <= 0) return hipSuccess;
+    const int64_t n = a.n_old + a.n_rows;
+    hipLaunchKernelGGL(k_occ_rank, dim3((unsigned)((n + IF_B - 1) / IF_B)), dim3(IF_B), 0, st, a);
+    hipLaunchKernelGGL(k_occ_accumulate, dim3((unsigned)((a.n_new + IF_B - 1) / IF_B)), dim3(IF_B), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t kl_occ_reverse(const OccArgs &a, hipStream_t st)
+{
+    if (a.n_new <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_occ_reverse, dim3((unsigned)((a.n_new + IF_B - 1) / IF_B)), dim3(IF_B), 0, st, a);
+    return hipGetLastError();
+}
+
 void kl_dump_phase_clocks(void)
 {
 #ifdef SASA_PHASE_TIMING

@@ -1172,8 +1172,9 @@ int freesasa_gpu_trajectory_file_interfaces(const char *frames_path, int frames_
    Argument errors, -1 with a message before a device is touched or a file opened: everything the interface entries refuse
    (bit 3 and bit 4 of frames_f32 included) but NULL pair areas; neither pair areas nor pair residues delivered nor named in the
    statistics word (nowhere to go); a min_buried that is not finite.
-   Not offered: a compacted per-frame table, contact tables per frame, periodic images, class splits of the buried area, a
-   contact screen per frame, medians, statistics of the volume column. */
+   Not offered: a compacted per-frame table, contact tables per frame (the run's residue-residue contacts as one table with
+   occupancies: freesasa_gpu_contact_occupancy_open), periodic images, class splits of the buried area, a contact screen per
+   frame, medians, statistics of the volume column. */
 int freesasa_gpu_trajectory_interface_residues(const double *xyz_frames, int n_frames, const struct freesasa_ingest_batch *batch, int structure,
                                                int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
                                                const int32_t *group, int n_groups,
@@ -1471,7 +1472,8 @@ int freesasa_gpu_calc_interface_residues(const double *xyz, const double *radii,
    Two engine runs over the M pair-structure atoms and two stream synchronizations more than freesasa_gpu_interfaces_dev (D_b
      comes back before the arrays it sizes are made, then C and the flag of a dot without a cover).
    Not offered: Lee-Richards; the file sweep and the trajectory drivers; periodic images; class splits; a table with both
-     directions added.  (The fold of the rows per residue pair: freesasa_gpu_interface_residue_contacts_dev below.)
+     directions added.  (The fold of the rows per residue pair: freesasa_gpu_interface_residue_contacts_dev below; over the
+     frames of a run: freesasa_gpu_contact_occupancy_open.)
 
    freesasa_gpu_interface_contacts_dev: the arrays after the counts are DEVICE arrays; d_pair_areas is required, every other
      array and n_buried_dots_out may be NULL; the rest as freesasa_gpu_interfaces_dev.
@@ -1537,8 +1539,9 @@ int freesasa_gpu_calc_interface_contacts(const double *xyz, const double *radii,
    Refused with a message before a device is touched: everything the contact entry refuses, everything the per-residue entry
      refuses about res_first and n_res, rescontact_capacity < 0.
    One stream synchronization more than freesasa_gpu_interface_contacts_dev (Q comes back to the host before delivery).
-   Not offered: Lee-Richards; the file sweep and the trajectory drivers; periodic images; class splits; a table with both
-     directions added.
+   Not offered: Lee-Richards; the file sweep and the trajectory drivers (the frames of a run reduced to one table of residue
+     pairs: freesasa_gpu_contact_occupancy_open below); periodic images; class splits; a table with both directions added (the
+     occupancy table's frames_either counts both).
 
    freesasa_gpu_interface_residue_contacts_dev: the contact entry's arguments, then res_first, n_res, rescontact_capacity,
      n_rescontacts_out and the five DEVICE arrays; d_rescontact_area is required, the other four may be NULL and are then not
@@ -1578,6 +1581,89 @@ int freesasa_gpu_calc_interface_residue_contacts(const double *xyz, const double
                                                  int32_t *rescontact_residues_out, int32_t *rescontact_counts_out,
                                                  double *rescontact_area_out, int32_t *rescontact_reverse_out,
                                                  int device, char *err_out, int err_len);
+
+/* RESIDUE CONTACT OCCUPANCY MAP: over the frames of a run, in how many frames residue a of one chain group touches residue b of
+   another, and over how much area when it does - the folded rows above, made per frame and reduced on the device into ONE table
+   by a streaming accumulator (csrc/occupancy_kernels.h; tests/contact_occupancy_ref.py restates the definitions in plain
+   Python).  Frames go in, in any cut; the per-frame tables never leave the device; the table that comes out is byte for byte
+   the same however the frames were cut.
+   The system: n_atoms atoms with radii [n], group [n] (int32; -1: in no group, 0 <= id < n_groups) and res_first [n_res + 1], a
+     HOST int64 array exactly as freesasa_gpu_interface_residues_dev takes it - all constant over the run.  Shrake-Rupley with
+     resolution <= 128 points.
+   A frame's rows: frame f as a batch of one structure - its coordinates, radii, group, n_groups, res_first - has the folded rows of
+     freesasa_gpu_interface_residue_contacts_dev: P_f pairs, Q_f rows.  Nothing of that definition changes; the contact screen per
+     frame stays.
+   Key.  The key of a folded row is (g, h, side, res_a, res_b): (g, h) its pair, side 0 if the source segment is in g and 1 if in
+     h, res_a / res_b the source and the partner residue, counted within the system.  A frame's keys ascend strictly as
+     5-tuples.  The REVERSED key of (g, h, s, a, b) is (g, h, 1 - s, b, a).
+   The run table after F frames: one row per distinct key seen so far, the U rows ascending by key, with
+     keys [U][5] (int32)
+     frames [U] (int64)          the frames in which the key has a folded row
+     frames_either [U] (int64)   the frames in which the key OR its reversed key has one: the symmetric occupancy a map plots
+     counts [U][2] (int64)       the sums over those frames of n_rows and of n_points
+     area [U][3] (fp64)          sum, min, max over the frames in which the key is present; the sum in frame order, one addition
+                                 at a time from 0.0, no fma
+     span [U][2] (int64)         the first and the last frame (0-based in the run) in which the key is present
+     reverse [U] (int32)         the row of the reversed key, or -1; reverse[k] = r >= 0 gives reverse[r] = k and
+                                 frames_either[k] == frames_either[r]; with reverse[k] == -1, frames_either[k] == frames[k]
+     Occupancy is frames / F, the mean area in contact area[0] / frames: the caller divides.
+   Cut independence.  The table after F frames is a function of the F frames in order and of nothing else: not of how they were
+     split over add calls, of frames_per_batch, of when snapshots were taken, of the launch shape.
+   Failure.  What is refused before the device is touched leaves the handle usable.  An add that fails behind that poisons the
+     handle: every later call but _close and _error returns -1 with the first failure's message - no partially merged table is
+     ever delivered.  No call throws.
+   Limits, refused with a message that names the number: U, or the folded rows of a chunk, beyond 2^31 - 1; everything the
+     interface pipeline refuses, with its text behind the run's frame number(s).
+   Not offered: Lee-Richards; periodic images; caller-named pairs (all pairs in contact are tabulated); atom-level occupancy;
+     standard deviations and medians of the area; the file drivers, done-lists and multi-device runs (partial tables of two
+     devices can be combined through _add_rows only per frame, not per table); a solvent gather (atom_index: pass the solute's
+     coordinates); trajectory containers (the device decoders have no memory form: the caller's own reader feeds _add_frames).
+
+   freesasa_gpu_contact_occupancy_open: the accumulator, or NULL with err.  radii == NULL and n_atoms == 0: an accumulator for
+     rows only (_add_frames refuses it; group, res_first and the resolution are not looked at).  Refused before a device is touched:
+     everything the residue-residue contact entry refuses about group, n_groups, res_first, n_res and the resolution, with its
+     messages; a group id outside -1 .. n_groups - 1.  frames_per_batch: the frames of a chunk, one run of the interface pipeline;
+     <= 0: the trajectory drivers' rule, 1250000 / atoms + 1, on THREE times the system's atoms - the frame, its isolated groups
+     and a pair structure's worth.  Either is lowered to what the pipeline takes: 2^30 atoms (three to an atom) and 2^27 pairs of
+     groups to a call, chunk-wide residue numbers below 2^31.  The handle keeps a pooled context until it is closed.
+   freesasa_gpu_contact_occupancy_add_frames: xyz_frames [f][n][3] (host) are the run's next f frames; frame_counts_out [f][2]
+     (int64, may be NULL) receives (P_f, Q_f).  Per chunk the coordinates go up and the pipeline runs with capacities that hold
+     anything; nothing per row comes back - one stream synchronization more than the pipeline's own, for the number of new keys.
+   freesasa_gpu_contact_occupancy_add_rows: the run's next f frames as rows the caller has already - from the batch entry, a file
+     sweep, another run: frame_first [f + 1] (int64), keys [q][5], counts [q][2] (int32: n_rows, n_points), area [q], host arrays,
+     through the same reduction.  Checked on the host before anything goes up, the frame and the row named in the message:
+     frame_first begins at 0 and does not descend; 0 <= g < h; side 0 or 1; residues >= 0; a frame's keys strictly ascending; both
+     counts >= 1; a finite area.
+   freesasa_gpu_contact_occupancy_table: a snapshot of the run table in host arrays of the library's (of one element where the
+     table has no row), to be given back with _table_free; the accumulator goes on.  n_frames: the frames added so far.
+   freesasa_gpu_contact_occupancy_close: NULL is allowed.  _error: the text of the last failure of the handle.
+   freesasa_gpu_calc_contact_occupancy: open, _add_frames over all frames, _table, close, on host arrays; the message in err_out.
+   All: 0, or -1 with the message. */
+typedef struct freesasa_gpu_contact_occupancy freesasa_gpu_contact_occupancy;
+typedef struct {
+    long long n_frames, n_rows;
+    int32_t *keys;
+    int64_t *frames, *frames_either, *counts;
+    double *area;
+    int64_t *span;
+    int32_t *reverse;
+} freesasa_gpu_contact_occupancy_table_t; /* (a type and a function cannot share a name in C) */
+freesasa_gpu_contact_occupancy *freesasa_gpu_contact_occupancy_open(const double *radii, int n_atoms, const int32_t *group, int n_groups,
+                                                                    const int64_t *res_first, int n_res, double probe_radius,
+                                                                    int resolution, int frames_per_batch, int device, char *err_out,
+                                                                    int err_len);
+int freesasa_gpu_contact_occupancy_add_frames(freesasa_gpu_contact_occupancy *o, const double *xyz_frames, int n_frames,
+                                              int64_t *frame_counts_out);
+int freesasa_gpu_contact_occupancy_add_rows(freesasa_gpu_contact_occupancy *o, int n_frames, const int64_t *frame_first,
+                                            const int32_t *keys, const int32_t *counts, const double *area);
+int freesasa_gpu_contact_occupancy_table(freesasa_gpu_contact_occupancy *o, freesasa_gpu_contact_occupancy_table_t *out);
+void freesasa_gpu_contact_occupancy_table_free(freesasa_gpu_contact_occupancy_table_t *t);
+void freesasa_gpu_contact_occupancy_close(freesasa_gpu_contact_occupancy *o);
+const char *freesasa_gpu_contact_occupancy_error(const freesasa_gpu_contact_occupancy *o);
+int freesasa_gpu_calc_contact_occupancy(const double *xyz_frames, int n_frames, const double *radii, int n_atoms, const int32_t *group,
+                                        int n_groups, const int64_t *res_first, int n_res, double probe_radius, int resolution,
+                                        int frames_per_batch, int64_t *frame_counts_out, freesasa_gpu_contact_occupancy_table_t *out,
+                                        int device, char *err_out, int err_len);
 
 /* MOLECULAR VOLUME: the volume enclosed by the solvent-accessible surface of every structure, made of the Shrake-Rupley test
    points by the divergence theorem - what `gmx sasa -tv` prints per frame, in the same formulation:
