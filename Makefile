@@ -2,7 +2,7 @@
 #   make            -> freesasa_amd/lib/libfreesasa_amd.so (stand-alone drop-in library)
 #                      freesasa_amd/lib/libfreesasa_amd_seam.a (seam objects for a drop-in
 #                      build of the reference)
-#   make emu        -> tests/emu/libsasa_emu.so, libselect_emu.so, libgroups_emu.so, libtraj_emu.so, libtraj_groups_emu.so, libtraj_pairs_emu.so, libtraj_pair_res_emu.so, libdcd_emu.so, libnc_emu.so, libxtc_emu.so, libtrr_emu.so, libpbc_emu.so, libpbc_tri_emu.so, libgroups_pbc_emu.so, libstats_emu.so, libvolume_emu.so, libdots_emu.so, libiface_emu.so, libiface_res_emu.so, libcontacts_emu.so, librescontacts_emu.so, libifsweep_emu.so, libocc_emu.so  (TESTS ONLY: the kernel phase
+#   make emu        -> tests/emu/libsasa_emu.so, libselect_emu.so, libgroups_emu.so, libtraj_emu.so, libtraj_groups_emu.so, libtraj_pairs_emu.so, libtraj_pair_res_emu.so, libdcd_emu.so, libnc_emu.so, libxtc_emu.so, libtrr_emu.so, libpbc_emu.so, libpbc_tri_emu.so, libgroups_pbc_emu.so, libtraj_pairs_pbc_emu.so, libstats_emu.so, libvolume_emu.so, libdots_emu.so, libiface_emu.so, libiface_res_emu.so, libcontacts_emu.so, librescontacts_emu.so, libifsweep_emu.so, libocc_emu.so  (TESTS ONLY: the kernel phase
 #                      functions driven on the CPU; never linked into the product) and tests/emu/dcd_check, tests/emu/cell_check, tests/emu/nc_check, tests/emu/xtc_check, tests/emu/xtc_emu_check, tests/emu/trr_check, tests/emu/stats_check, tests/emu/dots_check, tests/emu/iface_check, tests/emu/iface_res_check, tests/emu/contacts_check, tests/emu/rescontacts_check, tests/emu/ifsweep_check, tests/emu/occ_check, tests/emu/groups_pbc_check, tests/emu/pair_res_check (the DCD, NetCDF, XTC and TRR header parsers, the cell arithmetic, the emulated XTC decode, the merge of the run statistics and the emulated scan and expansion of the surface dots and the emulated phases of the interfaces between chain groups and of their per-residue, atom-atom contact and residue-residue contact tables and of the file sweep's interface kernels and of the contact occupancy map and the segments and rows of the per-residue interface tables per frame under sanitizers) and tests/emu/ingest_check (the host loader's PDB / mmCIF parsers under sanitizers)
 #   make oracle     -> oracle/ (TESTS ONLY) ; make tools -> tools/libsasa_synth.so
 HIPCC   ?= /opt/rocm/bin/hipcc
@@ -97,7 +97,7 @@ $(LIBDIR)/libfreesasa_amd.so: $(GPU_OBJS) $(LIBDIR)/seam.o $(LIBDIR)/testpoints.
 $(LIBDIR)/libfreesasa_amd_seam.a: $(GPU_OBJS) $(LIBDIR)/seam.o $(LIBDIR)/testpoints.o $(LIBDIR)/dcd.o $(LIBDIR)/netcdf.o $(LIBDIR)/xtc.o $(LIBDIR)/trr.o $(LIBDIR)/cell.o $(LIBDIR)/trajstats.o $(LIBDIR)/ingest.o $(LIBDIR)/classifier.o $(LIBDIR)/select.o $(LIBDIR)/ingest_cache.o $(LIBDIR)/hostfault.o
 	rm -f $@; ar rcs $@ $^
 
-emu: tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so tests/emu/libtraj_groups_emu.so tests/emu/libtraj_pairs_emu.so tests/emu/libtraj_pair_res_emu.so tests/emu/pair_res_check tests/emu/libdcd_emu.so tests/emu/libpbc_emu.so tests/emu/libpbc_tri_emu.so tests/emu/libgroups_pbc_emu.so tests/emu/libnc_emu.so tests/emu/libxtc_emu.so tests/emu/libtrr_emu.so tests/emu/libstats_emu.so tests/emu/libvolume_emu.so tests/emu/libdots_emu.so tests/emu/dcd_check tests/emu/cell_check tests/emu/nc_check tests/emu/xtc_check tests/emu/xtc_emu_check tests/emu/trr_check tests/emu/stats_check tests/emu/dots_check tests/emu/libiface_emu.so tests/emu/iface_check tests/emu/libiface_res_emu.so tests/emu/iface_res_check tests/emu/libcontacts_emu.so tests/emu/contacts_check tests/emu/librescontacts_emu.so tests/emu/rescontacts_check tests/emu/libifsweep_emu.so tests/emu/ifsweep_check tests/emu/libocc_emu.so tests/emu/occ_check tests/emu/groups_pbc_check tests/emu/ingest_check
+emu: tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so tests/emu/libtraj_groups_emu.so tests/emu/libtraj_pairs_emu.so tests/emu/libtraj_pair_res_emu.so tests/emu/pair_res_check tests/emu/libdcd_emu.so tests/emu/libpbc_emu.so tests/emu/libpbc_tri_emu.so tests/emu/libgroups_pbc_emu.so tests/emu/libtraj_pairs_pbc_emu.so tests/emu/libnc_emu.so tests/emu/libxtc_emu.so tests/emu/libtrr_emu.so tests/emu/libstats_emu.so tests/emu/libvolume_emu.so tests/emu/libdots_emu.so tests/emu/dcd_check tests/emu/cell_check tests/emu/nc_check tests/emu/xtc_check tests/emu/xtc_emu_check tests/emu/trr_check tests/emu/stats_check tests/emu/dots_check tests/emu/libiface_emu.so tests/emu/iface_check tests/emu/libiface_res_emu.so tests/emu/iface_res_check tests/emu/libcontacts_emu.so tests/emu/contacts_check tests/emu/librescontacts_emu.so tests/emu/rescontacts_check tests/emu/libifsweep_emu.so tests/emu/ifsweep_check tests/emu/libocc_emu.so tests/emu/occ_check tests/emu/groups_pbc_check tests/emu/ingest_check
 # the loader with its byte-at-a-time mmCIF tokenizer only: the differential twin of the SSE2 row scanner
 tests/emu/libingest_scalar.so: $(CSRC)/ingest.c $(CSRC)/classifier.c $(CSRC)/classifier.h $(CSRC)/hostfault.c $(CSRC)/hostfault.h $(CSRC)/protor_table.h include/freesasa_ingest.h
 	$(CC) $(CFLAGS) -DFREESASA_INGEST_NO_SIMD -Iinclude -pthread -shared -o $@ $(CSRC)/ingest.c $(CSRC)/classifier.c $(CSRC)/hostfault.c -lm
@@ -140,6 +140,9 @@ tests/emu/libpbc_tri_emu.so: tests/emu/emu_pbc_tri.cpp tests/emu/emu_pbc.cpp $(C
 # ... chain groups among periodic images (pbc_kernels.h, GpbcArgs): the combined structures' cells and the fused collect-and-finish
 tests/emu/libgroups_pbc_emu.so: tests/emu/emu_groups_pbc.cpp tests/emu/emu_pbc_tri.cpp tests/emu/emu_pbc.cpp $(CSRC)/pbc_tri_kernels.h $(CSRC)/pbc_kernels.h $(CSRC)/lr2_kernels.h $(CSRC)/sasa_kernels.h $(CSRC)/sr_caps.h
 	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -DSASA_EMU -shared -o $@ tests/emu/emu_groups_pbc.cpp -lm
+# ... with the pair part of a trajectory shard's combined batch (interfaces among periodic images: GpbcArgs' k_fixed)
+tests/emu/libtraj_pairs_pbc_emu.so: tests/emu/emu_traj_pairs_pbc.cpp tests/emu/emu_groups_pbc.cpp tests/emu/emu_pbc_tri.cpp tests/emu/emu_pbc.cpp $(CSRC)/pbc_tri_kernels.h $(CSRC)/pbc_kernels.h $(CSRC)/lr2_kernels.h $(CSRC)/sasa_kernels.h $(CSRC)/sr_caps.h
+	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -DSASA_EMU -shared -o $@ tests/emu/emu_traj_pairs_pbc.cpp -lm
 # ... and the same phases (emu_groups_pbc.cpp with its main) under AddressSanitizer + UBSan in a stand-alone program: one line per stage
 tests/emu/groups_pbc_check: tests/emu/emu_groups_pbc.cpp tests/emu/emu_pbc_tri.cpp tests/emu/emu_pbc.cpp $(CSRC)/pbc_tri_kernels.h $(CSRC)/pbc_kernels.h $(CSRC)/lr2_kernels.h $(CSRC)/sasa_kernels.h $(CSRC)/sr_caps.h
 	$(CXX) -O1 -g -std=c++17 -Wall -Wno-unused-function -Wno-unknown-pragmas -ffp-contract=off -DSASA_EMU -DGPBC_CHECK_MAIN -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -o $@ tests/emu/emu_groups_pbc.cpp -lm
@@ -257,7 +260,7 @@ tools:
 	$(MAKE) -C tools
 
 clean:
-	rm -rf $(LIBDIR) tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so tests/emu/libtraj_groups_emu.so tests/emu/libtraj_pairs_emu.so tests/emu/libtraj_pair_res_emu.so tests/emu/pair_res_check tests/emu/libdcd_emu.so tests/emu/libpbc_emu.so tests/emu/libpbc_tri_emu.so tests/emu/libgroups_pbc_emu.so tests/emu/libnc_emu.so tests/emu/libxtc_emu.so tests/emu/dcd_check tests/emu/cell_check tests/emu/nc_check tests/emu/xtc_check tests/emu/xtc_emu_check tests/emu/xtc_*.o tests/emu/libtrr_emu.so tests/emu/trr_check tests/emu/trr_*.o tests/emu/libstats_emu.so tests/emu/stats_check tests/emu/libvolume_emu.so tests/emu/libdots_emu.so tests/emu/dots_check tests/emu/libiface_emu.so tests/emu/iface_check tests/emu/libiface_res_emu.so tests/emu/iface_res_check tests/emu/libcontacts_emu.so tests/emu/contacts_check tests/emu/librescontacts_emu.so tests/emu/rescontacts_check tests/emu/libifsweep_emu.so tests/emu/ifsweep_check tests/emu/libocc_emu.so tests/emu/occ_check tests/emu/groups_pbc_check tests/emu/ingest_check
+	rm -rf $(LIBDIR) tests/emu/libsasa_emu.so tests/emu/libingest_scalar.so tests/emu/libselect_emu.so tests/emu/libgroups_emu.so tests/emu/libtraj_emu.so tests/emu/libtraj_groups_emu.so tests/emu/libtraj_pairs_emu.so tests/emu/libtraj_pair_res_emu.so tests/emu/pair_res_check tests/emu/libdcd_emu.so tests/emu/libpbc_emu.so tests/emu/libpbc_tri_emu.so tests/emu/libgroups_pbc_emu.so tests/emu/libtraj_pairs_pbc_emu.so tests/emu/libnc_emu.so tests/emu/libxtc_emu.so tests/emu/dcd_check tests/emu/cell_check tests/emu/nc_check tests/emu/xtc_check tests/emu/xtc_emu_check tests/emu/xtc_*.o tests/emu/libtrr_emu.so tests/emu/trr_check tests/emu/trr_*.o tests/emu/libstats_emu.so tests/emu/stats_check tests/emu/libvolume_emu.so tests/emu/libdots_emu.so tests/emu/dots_check tests/emu/libiface_emu.so tests/emu/iface_check tests/emu/libiface_res_emu.so tests/emu/iface_res_check tests/emu/libcontacts_emu.so tests/emu/contacts_check tests/emu/librescontacts_emu.so tests/emu/rescontacts_check tests/emu/libifsweep_emu.so tests/emu/ifsweep_check tests/emu/libocc_emu.so tests/emu/occ_check tests/emu/groups_pbc_check tests/emu/ingest_check
 	$(MAKE) -C oracle clean
 	$(MAKE) -C tools clean
 .PHONY: all emu oracle tools clean asan asan-test

@@ -1403,6 +1403,9 @@ def _stats_proto(L):
     L.freesasa_gpu_trajectory_interface_residues.argtypes = L.freesasa_gpu_trajectory_interfaces.argtypes[:-2] + [C.c_double, _dp, C.c_char_p, C.c_int]
     L.freesasa_gpu_trajectory_file_interface_residues.argtypes = L.freesasa_gpu_trajectory_file_interfaces.argtypes[:-2] + \
         [C.c_double, C.c_char_p, C.c_char_p, C.c_int]
+    # ... and both among periodic images: their siblings' signatures
+    L.freesasa_gpu_trajectory_file_interfaces_periodic.argtypes = L.freesasa_gpu_trajectory_file_interfaces.argtypes
+    L.freesasa_gpu_trajectory_file_interface_residues_periodic.argtypes = L.freesasa_gpu_trajectory_file_interface_residues.argtypes
     L.freesasa_gpu_trajectory_interface_segments.argtypes = [C.c_void_p, C.c_int, _i32p, C.c_int, _i32p, C.c_int, C.c_longlong, _llp, _llp, _i32p,
                                                              _i32p, C.c_char_p, C.c_int]
     L.freesasa_gpu_traj_stats_width_pairs.argtypes = [C.c_int] + 6 * [C.c_longlong] + [_llp]
@@ -2231,14 +2234,26 @@ def trajectory_file_groups_periodic(frames_path, batch, totals_path, structure=0
                                     n_frames=0, alg=LEE_RICHARDS, probe=1.4, resolution=20, frames_per_batch=0,
                                     max_new_shards=0, device=-1, devices=None, out_f32=False, chain_groups=None, separate_chains=False,
                                     long=False, group=None, n_groups=None, group_areas_path=None, isolated_path=None, dcd=False,
-                                    triclinic=False, netcdf=False, xtc=False, stats=None, stats_path=None, partials_path=None, trr=False):
+                                    triclinic=False, netcdf=False, xtc=False, stats=None, stats_path=None, partials_path=None, trr=False,
+                                    interface_pairs=None, pair_areas_path=None, pair_residues_path=None, min_buried=None):
     """freesasa_gpu_trajectory_file_groups_periodic(): trajectory_file_topology() with chain groups and every frame among the
     periodic images of its own cell (pbc is implied; dcd, netcdf, xtc or trr names the container, triclinic how its cell is read):
     per frame the totals, the per-atom areas, the per-atom isolated areas and the group table are those of calc_groups_periodic
     (calc_groups_periodic_triclinic) on that frame - chains that lie in different images of the box bury what they bury.  The
     keywords, outputs, statistics and the done-list are trajectory_file_topology's.  Returns (complete, n_frames,
-    selection_atoms [S] or None)."""
+    selection_atoms [S] or None).
+    interface_pairs="all" or [(g, h), ...] with pair_areas_path (freesasa_gpu_trajectory_file_interfaces_periodic): the interfaces
+    between the groups among periodic images - every pair structure in the frame's cell among its own images; pair_areas_path
+    receives [F, K, 6] fp64, the columns of trajectory_file_topology(interface_pairs=...).  pair_residues_path and / or min_buried
+    with interface_pairs (freesasa_gpu_trajectory_file_interface_residues_periodic): pair_residues_path receives [F, S, 4] fp64
+    (traj_pair_segments says which segment is which); stats= then also takes "pairs" and "pair_residues", and pair_areas_path
+    may be None; min_buried None is 0.0.  The argument checks are trajectory_file_topology's."""
     L = _stats_proto(_topology_proto(lib()))
+    with_res = pair_residues_path is not None or min_buried is not None
+    if with_res and interface_pairs is None:
+        raise ValueError("pair_residues_path and min_buried need interface_pairs")
+    if not with_res and (interface_pairs is None) != (pair_areas_path is None):
+        raise ValueError("interface_pairs and pair_areas_path go together")
     bits = _frames_bits(False, out_f32, dcd, 0, True, triclinic, netcdf, xtc, trr)
     if frame_atoms is None:
         info = dcd_info if dcd else nc_info if netcdf else xtc_info if xtc else trr_info if trr else None
@@ -2253,6 +2268,29 @@ def trajectory_file_groups_periodic(frames_path, batch, totals_path, structure=0
     keep, dp_, nd = _devs(devices, device)
     cb = batch._as_c()
     ids, G, _ = _topology_groups(batch, structure, n, chain_groups, separate_chains, long, group, n_groups)
+    pairs = _interface_pairs(interface_pairs, ids, G)
+    if pairs is not None:
+        i32 = C.POINTER(C.c_int32)
+        head = (enc(frames_path), bits, 0, n_frames, C.byref(cb), structure, fa_, None if idx is None else idx.ctypes.data_as(i32),
+                selection.handle if selection is not None else None, ids.ctypes.data_as(i32), G,
+                alg, probe, resolution, frames_per_batch, enc(totals_path), enc(sasa_path),
+                enc(class_sums_path), enc(residues_path), enc(selections_path),
+                None if sel_atoms is None else sel_atoms.ctypes.data_as(C.POINTER(C.c_longlong)),
+                enc(group_areas_path), enc(isolated_path), enc(done_path), max_new_shards, dp_, nd, C.byref(total))
+        if with_res:
+            name = "freesasa_gpu_trajectory_file_interface_residues_periodic"
+            ret = L.freesasa_gpu_trajectory_file_interface_residues_periodic(
+                *head, stats_word(stats, pairs=True) if stats else 0, enc(stats_path), enc(partials_path),
+                pairs.ctypes.data_as(i32), pairs.shape[0], enc(pair_areas_path),
+                0.0 if min_buried is None else float(min_buried), enc(pair_residues_path), err, 512)
+        else:
+            name = "freesasa_gpu_trajectory_file_interfaces_periodic"
+            ret = L.freesasa_gpu_trajectory_file_interfaces_periodic(
+                *head, stats_word(stats) if stats else 0, enc(stats_path), enc(partials_path),
+                pairs.ctypes.data_as(i32), pairs.shape[0], enc(pair_areas_path), err, 512)
+        if ret < 0:
+            raise RuntimeError(name + ": " + err.value.decode())
+        return ret == 0, int(total.value), sel_atoms
     ret = L.freesasa_gpu_trajectory_file_groups_periodic(enc(frames_path), bits, 0, n_frames, C.byref(cb), structure, fa_,
                                                          None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
                                                          selection.handle if selection is not None else None,

@@ -450,8 +450,11 @@ int periodic_resident_tri(freesasa_gpu_ctx *c, int alg, const double *d_xyz, con
    periodic_resident's pipeline, every group in the cell of its complex, in ONE engine run: the cells of the combined structures
    made on the device (c->gp_cells) from d_cells [W n_cplx], the stage's collect replaced by pbc_kernels.h's fused finish, then
    the totals kernels with the chunk table of `comb` over the compact combined areas (x.carea -> d_ctot [n_comb]) and, when
-   d_ctot2 is not null, over the gathered complex areas (x.cgath -> d_ctot2 [n_comb]).  The caller fills the layout and the
-   outputs of `x` (n_cplx, n_comb, gbase / g_fixed, n_atoms, n_all, src, n_fixed, n_iso_fixed, key, carea, cgath, sasa, iso);
+   d_ctot2 is not null, over the gathered complex areas (x.cgath -> d_ctot2 [n_comb]).  With x.k_fixed > 0 (a trajectory shard's
+   interface pairs: behind the groups k_fixed pair structures per complex, x.pair_first their first atom) the pair structures are
+   expanded and finished with the rest, d_ctot holds their totals too, and the reduction of x.cgath stops in front of them
+   (d_ctot2 [n_cplx (1 + g_fixed)]): a pair atom has no gathered area.  The caller fills the layout and the
+   outputs of `x` (n_cplx, n_comb, gbase / g_fixed, k_fixed, pair_first, n_atoms, n_all, src, n_fixed, n_iso_fixed, key, carea, cgath, sasa, iso);
    cells (host, [W n_cplx], W = 3 or PBC_TRI_CELL) are the complexes' rows only: a cell is checked once, against its complex, and
    the messages name the complex.  images_out (host, [n_cplx], may be null): the images of the complexes.  Nothing is waited for
    at its end.  groups_periodic_resident: freesasa_gpu_groups_periodic_dev's pipeline - groups_cut, that stage, k_grp_totals -

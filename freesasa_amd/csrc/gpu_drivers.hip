@@ -282,16 +282,19 @@ int group_make(const int32_t *group, int n_groups, bool areas, bool iso, TrajTop
     return 0;
 }
 
-/* What the interface entries refuse before a device is touched or a file opened, each with its own message: 0, or -1 */
-int pair_check(const int32_t *group, int n_groups, const int32_t *pairs, int n_pairs, int frames_f32, const void *out, char *err_out, int err_len)
+/* What the interface entries refuse before a device is touched or a file opened, each with its own message: 0, or -1.
+   periodic: the entry is one of the two among periodic images (the only ones bits 3 / 4 of frames_f32 get through for) */
+int pair_check(const int32_t *group, int n_groups, const int32_t *pairs, int n_pairs, int frames_f32, const void *out, char *err_out, int err_len,
+               bool periodic = false)
 {
     if (err_out && err_len > 0) err_out[0] = 0;
     if (!group) return set_err(err_out, err_len, "interfaces need chain groups: group ids (group is NULL)");
     if (n_pairs < 1) return set_err(err_out, err_len, "interfaces need at least one pair of groups (n_pairs < 1)");
     if (!pairs) return set_err(err_out, err_len, "null argument: the pairs");
     if (!out) return set_err(err_out, err_len, "null argument: the pair areas have nowhere to go");
-    if (frames_f32 & (FREESASA_GPU_FRAMES_PBC | FREESASA_GPU_FRAMES_TRICLINIC))
-        return set_err(err_out, err_len, "bit 3 and bit 4 of frames_f32: interfaces among periodic images are not offered");
+    if (!periodic && (frames_f32 & (FREESASA_GPU_FRAMES_PBC | FREESASA_GPU_FRAMES_TRICLINIC)))
+        return set_err(err_out, err_len, "bit 3 and bit 4 of frames_f32: interfaces among periodic images are not offered by this entry: "
+                                         "freesasa_gpu_trajectory_file_interfaces_periodic and _interface_residues_periodic are the ones");
     char msg[200];
     for (int k = 0; k < n_pairs; ++k) {
         const int32_t g = pairs[2 * k], h = pairs[2 * k + 1];
@@ -340,9 +343,9 @@ void pair_res_make(double min_buried, TrajTopo *tp)
 /* What the interface-residue entries refuse on top of pair_check (which they pass a place for the pair areas whether or not they
    have one: here those may be NULL): 0, or -1 */
 int pair_res_check(const int32_t *group, int n_groups, const int32_t *pairs, int n_pairs, int frames_f32, const void *pair_out, const void *res_out,
-                   int stats, double min_buried, char *err_out, int err_len)
+                   int stats, double min_buried, char *err_out, int err_len, bool periodic = false)
 {
-    if (pair_check(group, n_groups, pairs, n_pairs, frames_f32, "", err_out, err_len)) return -1;
+    if (pair_check(group, n_groups, pairs, n_pairs, frames_f32, "", err_out, err_len, periodic)) return -1;
     if (!pair_out && !res_out && !(stats & (FREESASA_GPU_STATS_PAIRS | FREESASA_GPU_STATS_PAIR_RESIDUES)))
         return set_err(err_out, err_len, "neither the pair areas nor the pair residues are delivered or named in the statistics word: they have nowhere to go");
     if (!std::isfinite(min_buried)) return set_err(err_out, err_len, "min_buried must be finite");
@@ -685,7 +688,10 @@ int shard_compute(TrajRun &T, TrajLane &L, TrajShard &h)
     sasa::GpbcArgs gx;
     memset(&gx, 0, sizeof gx);
     if (gpbc) {
-        gx.n_cplx = h.nf; gx.n_comb = (int)(nf * (1 + T.G)); gx.g_fixed = (int)T.G;
+        /* (interface pairs among periodic images: behind the groups the K pair structures of every frame, each in its frame's cell
+           among its own images; the finish gives their atoms' areas to the compact combined areas alone, pbc_kernels.h) */
+        gx.n_cplx = h.nf; gx.n_comb = (int)(nf * (1 + T.G + T.K)); gx.g_fixed = (int)T.G;
+        gx.k_fixed = (int)T.K; gx.pair_first = (int64_t)(nf * (T.n + T.n_iso));
         gx.n_atoms = (int64_t)(nf * T.n); gx.n_all = (int64_t)(nf * T.nc);
         gx.src = L.ga.src; gx.n_fixed = (int)T.n; gx.n_iso_fixed = (int)T.n_iso; gx.key = L.ga.group;
         gx.carea = (double *)c->h_sasa.p; gx.cgath = (double *)c->g_gath.p; gx.iso = out[OUT_ISO].per_frame ? (double *)c->h_iso.p : nullptr;
@@ -1465,6 +1471,58 @@ extern "C" int freesasa_gpu_trajectory_file_groups_periodic(const char *frames_p
                                 alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
                                 sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
                                 frames_total_out, stats, stats_path, partials_path, err_out, err_len);
+}
+
+/* interfaces between chain groups among periodic images: that run with, behind every frame's groups, its pair structures - each
+   in the frame's cell among its own images (shard_compute: the pair part of groups_periodic_stage's combined batch); behind the
+   stage the pairs' sums are the ones of the run without cells */
+extern "C" int freesasa_gpu_trajectory_file_interfaces_periodic(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
+                                                                const freesasa_ingest_batch *batch, int structure,
+                                                                int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
+                                                                const int32_t *group, int n_groups,
+                                                                int alg, double probe, int resolution, int frames_per_batch,
+                                                                const char *totals_path, const char *sasa_path, const char *class_sums_path,
+                                                                const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
+                                                                const char *group_areas_path, const char *iso_path,
+                                                                const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                                                long long *frames_total_out,
+                                                                int stats, const char *stats_path, const char *partials_path,
+                                                                const int32_t *pairs, int n_pairs, const char *pair_areas_path, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (!(frames_f32 & FREESASA_GPU_FRAMES_PBC))
+        return set_err(err_out, err_len, "interfaces among periodic images need bit 3 of frames_f32 (periodic images): without it the run is freesasa_gpu_trajectory_file_interfaces's");
+    if (pair_check(group, n_groups, pairs, n_pairs, frames_f32, pair_areas_path, err_out, err_len, true)) return -1;
+    return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,
+                                alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
+                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
+                                frames_total_out, stats, stats_path, partials_path, err_out, err_len, pairs, n_pairs, pair_areas_path);
+}
+
+/* ... with the per-residue table of the interfaces, read from the periodic isolated and pair areas, and the statistics of both pair outputs */
+extern "C" int freesasa_gpu_trajectory_file_interface_residues_periodic(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
+                                                                        const freesasa_ingest_batch *batch, int structure,
+                                                                        int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
+                                                                        const int32_t *group, int n_groups,
+                                                                        int alg, double probe, int resolution, int frames_per_batch,
+                                                                        const char *totals_path, const char *sasa_path, const char *class_sums_path,
+                                                                        const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
+                                                                        const char *group_areas_path, const char *iso_path,
+                                                                        const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                                                        long long *frames_total_out,
+                                                                        int stats, const char *stats_path, const char *partials_path,
+                                                                        const int32_t *pairs, int n_pairs, const char *pair_areas_path,
+                                                                        double min_buried, const char *pair_res_path, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (!(frames_f32 & FREESASA_GPU_FRAMES_PBC))
+        return set_err(err_out, err_len, "interfaces among periodic images need bit 3 of frames_f32 (periodic images): without it the run is freesasa_gpu_trajectory_file_interface_residues's");
+    if (pair_res_check(group, n_groups, pairs, n_pairs, frames_f32, pair_areas_path, pair_res_path, stats, min_buried, err_out, err_len, true)) return -1;
+    return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,
+                                alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
+                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
+                                frames_total_out, stats, stats_path, partials_path, err_out, err_len, pairs, n_pairs, pair_areas_path,
+                                FREESASA_GPU_STATS_PAIRS | FREESASA_GPU_STATS_PAIR_RESIDUES, min_buried, pair_res_path);
 }
 
 extern "C" int freesasa_gpu_trajectory_file_topology(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,

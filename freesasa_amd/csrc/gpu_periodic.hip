@@ -124,8 +124,10 @@ static int compact_chunks(freesasa_gpu_ctx *c, const int64_t *offsets, int n_str
 }
 
 /* periodic_resident (tri false: cells [3 n_structs]) and periodic_resident_tri (tri: cells [9 n_structs]).  gx (chain groups
-   among periodic images, groups_periodic_stage): the batch is a combined one - gx->n_cplx complexes, then their groups; the host
-   cells are the complexes' rows and are checked for them alone (a group's max radius never exceeds its complex's), images_out
+   among periodic images, groups_periodic_stage): the batch is a combined one - gx->n_cplx complexes, then their groups (and, for a
+   trajectory shard with interface pairs, behind those the pair structures of every frame: gx->k_fixed); the host
+   cells are the complexes' rows and are checked for them alone (a group's or a pair structure's max radius never exceeds its
+   complex's), images_out
    is the complexes', and behind the engine runs the groups' fused finish in the collect's place (d_sasa and d_totals: null). */
 static int resident(freesasa_gpu_ctx *c, bool tri, int alg, const double *d_xyz, const double *d_radii, const int64_t *offsets, int n_structs,
                     int n_fixed, const double *cells, const double *d_cells, double probe, int resolution, const double *unit_points,
@@ -428,7 +430,19 @@ int groups_periodic_stage(freesasa_gpu_ctx *c, bool tri, int alg, const double *
     PipeArgs ta;
     if (compact_chunks(c, comb, x.n_comb, ta)) return -1;
     HIP_TRY(c, kl_totals(ta, ta.n_chunks, x.n_comb, x.carea, (double *)c->p_part.p, d_ctot, c->stream));
-    if (d_ctot2) HIP_TRY(c, kl_totals(ta, ta.n_chunks, x.n_comb, x.cgath, (double *)c->p_part.p, d_ctot2, c->stream));
+    if (!d_ctot2) return 0;
+    /* (interface pairs: the pair structures lie behind the others, and so do their chunks in the table; the finish writes no
+       gathered area for a pair atom, so those chunks are KEPT OUT of this reduction - d_ctot2 is [n_cplx (1 + g_fixed)] - as
+       shard_compute keeps them out for the run without cells) */
+    int n_structs2 = x.n_comb, n_chunks2 = ta.n_chunks;
+    if (x.k_fixed) {
+        n_structs2 = x.n_cplx * (1 + x.g_fixed);
+        int64_t k = 0;
+        for (int s = 0; s < n_structs2; ++s) k += (comb[s + 1] - comb[s] + SASA_BOUNDS_CHUNK - 1) / SASA_BOUNDS_CHUNK;
+        n_chunks2 = (int)k;
+        ta.n_structs = n_structs2;
+    }
+    HIP_TRY(c, kl_totals(ta, n_chunks2, n_structs2, x.cgath, (double *)c->p_part.p, d_ctot2, c->stream));
     return 0;
 }
 

@@ -217,13 +217,24 @@ SASA_D void pbc_collect_atom(const PbcArgs &a, int64_t t)
  * Which complex a group structure k >= n_cplx belongs to: the last s with gbase[s] <= k - n_cplx (the batch entries; a complex
  * without groups is never the last), or (k - n_cplx) / g_fixed (a shard's frames, each with the same groups).  Which atom an
  * isolated atom t >= n_atoms comes from: src[t - n_atoms] (the batch entries), or atom src[j] of frame f with
- * t - n_atoms = f n_iso_fixed + j (a shard's frames). */
+ * t - n_atoms = f n_iso_fixed + j (a shard's frames).
+ *
+ * INTERFACE PAIRS among periodic images (freesasa_gpu_trajectory_file_interfaces_periodic and its kin): a shard's combined batch
+ * is frames | isolated groups | PAIR STRUCTURES (traj_kernels.h, traj_pair_cut), k_fixed of them per frame behind the n_cplx g_fixed
+ * groups: n_comb = n_cplx (1 + g_fixed + k_fixed) structures, n_all = n_cplx (n_fixed + n_iso_fixed + n_pair) atoms.  Pair
+ * structure k belongs to frame (k - n_cplx (1 + g_fixed)) / k_fixed and gets that frame's cell row; a pair atom t >= pair_first
+ * has its area read out of the expanded batch into the compact combined areas AND NOTHING ELSE: it has no source atom to write
+ * an isolated area to and no complex area to gather.  The pair part of cgath is therefore NEVER WRITTEN, and the host keeps the
+ * pair structures' chunks out of the reduction of cgath (gpu_periodic.hip, groups_periodic_stage - as the non-periodic run does
+ * with grp_chunks).  k_fixed = 0: no pairs, every byte what it was.  Only a shard's frames (gbase NULL) have pairs. */
 struct GpbcArgs {
     int n_cplx, n_comb;     /* complexes; combined structures: the complexes and all their groups */
     const int64_t *coff;    /* [n_comb + 1] the combined batch's offsets */
     const int64_t *eoff;    /* [n_comb + 1] the expanded batch's */
     const int64_t *gbase;   /* [n_cplx + 1] first group of every complex; NULL: g_fixed groups per complex */
     int g_fixed;
+    int k_fixed;            /* (gbase NULL) pair structures per complex, behind all the groups; 0: none */
+    int64_t pair_first;     /* (k_fixed > 0) the first pair atom of the combined batch: n_atoms + n_cplx n_iso_fixed */
     /* gpbc_cell_struct */
     int W;                  /* doubles per cell */
     const double *cells;    /* [W n_cplx] */
@@ -235,7 +246,7 @@ struct GpbcArgs {
     const int *key;         /* [n_atoms] < 0: in no group; a shard's frames: [n_fixed], the topology's ids */
     const double *esasa;    /* [eoff[n_comb]] */
     double *carea;          /* [n_all] the compact combined areas */
-    double *cgath;          /* [n_all] the complex area of every combined atom */
+    double *cgath;          /* [n_all] the complex area of every combined atom (the pair part: never written, never read) */
     double *sasa, *iso;     /* [n_atoms]; either may be null */
 };
 
@@ -253,6 +264,7 @@ SASA_D int gpbc_last_le(const int64_t *first, int n, int64_t v)
 SASA_D int gpbc_complex_of(const GpbcArgs &a, int k)
 {
     if (k < a.n_cplx) return k;
+    if (a.k_fixed && k >= a.n_cplx * (1 + a.g_fixed)) return (k - a.n_cplx * (1 + a.g_fixed)) / a.k_fixed; /* (a pair structure) */
     return a.gbase ? gpbc_last_le(a.gbase, a.n_cplx, (int64_t)(k - a.n_cplx)) : (k - a.n_cplx) / a.g_fixed;
 }
 
@@ -264,7 +276,10 @@ SASA_D void gpbc_cell_struct(const GpbcArgs &a, int k)
     for (int w = 0; w < a.W; ++w) a.ccells[(int64_t)a.W * k + w] = a.cells[(int64_t)a.W * s + w];
 }
 
-/* one thread per combined atom t */
+/* one thread per combined atom t.  No thread reads what another writes: every thread reads esasa, the offsets and the
+   topology's tables, which no thread writes, and writes carea[t] and cgath[t] of its own t, sasa[t] (a complex atom) or
+   iso[i] of its one source atom i (an isolated atom: an atom is in one group at most; an atom in no group is written by its
+   complex atom's thread); a pair atom's thread writes carea[t] alone. */
 SASA_D void gpbc_finish_atom(const GpbcArgs &a, int64_t t)
 {
     if (t >= a.n_all) return;
@@ -277,6 +292,7 @@ SASA_D void gpbc_finish_atom(const GpbcArgs &a, int64_t t)
         if (a.iso && a.key[a.n_fixed ? t % a.n_fixed : t] < 0) a.iso[t] = v;
         return;
     }
+    if (a.k_fixed && t >= a.pair_first) return; /* (a pair atom: no isolated area, no gathered complex area) */
     const int s = gpbc_complex_of(a, k);
     int64_t i;
     if (a.n_fixed) {

@@ -1075,7 +1075,8 @@ int freesasa_gpu_trajectory_file_groups_stats(const char *frames_path, int frame
    statistics word and the done-list work as in the non-periodic groups run; the done-list's first line carries bit 3 (and 4)
    in its f32= word and the groups' digest, so the lists of this run, of the plain periodic run and of the non-periodic groups
    run refuse each other.  The other entries keep refusing chain groups with bit 3 or bit 4, and name this one.
-   Not offered: the memory form (it has no cells), exposure masks, volume or interfaces among periodic images. */
+   Interfaces between the groups among periodic images: freesasa_gpu_trajectory_file_interfaces_periodic (below).
+   Not offered: the memory form (it has no cells), exposure masks or volume among periodic images. */
 int freesasa_gpu_trajectory_file_groups_periodic(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
                                                  const struct freesasa_ingest_batch *batch, int structure,
                                                  int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
@@ -1115,8 +1116,9 @@ int freesasa_gpu_trajectory_file_groups_periodic(const char *frames_path, int fr
    for other pairs, or without them, is refused.
    Argument errors, -1 with a message before a device is touched or a file opened: group NULL, n_pairs < 1, pairs or the pair
    areas NULL, a pair with g >= h or an id out of [0, n_groups) (the message names the pair's index), a pair named twice (it names
-   both indices), bit 3 or bit 4 of frames_f32.
-   Not offered: a contact screen per frame, per-atom buried areas per pair, contact tables, interfaces among periodic images,
+   both indices), bit 3 or bit 4 of frames_f32 (interfaces among periodic images are another entry's:
+   freesasa_gpu_trajectory_file_interfaces_periodic, below; the message names it).
+   Not offered: a contact screen per frame, per-atom buried areas per pair, contact tables,
    group ids made on the device, more than two groups per interface.  Per-residue buried areas per pair and the run statistics
    of the pair columns: freesasa_gpu_trajectory_interface_residues below. */
 int freesasa_gpu_trajectory_interfaces(const double *xyz_frames, int n_frames, const struct freesasa_ingest_batch *batch, int structure,
@@ -1173,8 +1175,9 @@ int freesasa_gpu_trajectory_file_interfaces(const char *frames_path, int frames_
    (bit 3 and bit 4 of frames_f32 included) but NULL pair areas; neither pair areas nor pair residues delivered nor named in the
    statistics word (nowhere to go); a min_buried that is not finite.
    Not offered: a compacted per-frame table, contact tables per frame (the run's residue-residue contacts as one table with
-   occupancies: freesasa_gpu_contact_occupancy_open), periodic images, class splits of the buried area, a contact screen per
-   frame, medians, statistics of the volume column. */
+   occupancies: freesasa_gpu_contact_occupancy_open), class splits of the buried area, a contact screen per
+   frame, medians, statistics of the volume column.  (Among periodic images: freesasa_gpu_trajectory_file_interface_residues_periodic
+   below.) */
 int freesasa_gpu_trajectory_interface_residues(const double *xyz_frames, int n_frames, const struct freesasa_ingest_batch *batch, int structure,
                                                int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
                                                const int32_t *group, int n_groups,
@@ -1198,6 +1201,64 @@ int freesasa_gpu_trajectory_file_interface_residues(const char *frames_path, int
                                                     int stats, const char *stats_path, const char *partials_path,
                                                     const int32_t *pairs, int n_pairs, const char *pair_areas_path,
                                                     double min_buried, const char *pair_res_path, char *err, int err_len);
+/* INTERFACES BETWEEN CHAIN GROUPS AMONG PERIODIC IMAGES over a trajectory: the two file entries above for the frames an MD engine
+   writes - wrapped into the box, the partners of a complex regularly in different images of it, where the run without cells
+   reports a buried area of 0 for the pair.  freesasa_gpu_trajectory_file_interfaces_periodic has the signature of
+   freesasa_gpu_trajectory_file_interfaces, freesasa_gpu_trajectory_file_interface_residues_periodic that of
+   freesasa_gpu_trajectory_file_interface_residues.  Bit 3 of frames_f32 (FREESASA_GPU_FRAMES_PBC) is REQUIRED (-1 with a message
+   that names the non-periodic entry), bit 4 (triclinic cells) is optional; the containers are those that carry a cell: DCD,
+   AMBER NetCDF, XTC, TRR.  The run composes freesasa_gpu_trajectory_file_groups_periodic and the interfaces run.  Per frame f, in
+   frame f's cell:
+     complex          the periodic entry's structure (freesasa_gpu_periodic_dev; with bit 4: _triclinic_dev) of frame f
+     isolated group   the periodic entry's structure of the group's atoms alone, among its own images
+     pair structure   for pair (g, h): g's atoms in input order, then h's, as the run without cells cuts it - taken as the periodic
+                      entry's structure in the same cell, among its OWN images, with the cutoff c of its OWN atoms
+   and per frame and pair the six doubles (iso_g, iso_h, in_pair_g, in_pair_h, buried_g, buried_h):
+     iso_*      column 0 of the frame's periodic group areas (freesasa_gpu_trajectory_file_groups_periodic), bit for bit
+     in_pair_*  the side's areas in the periodic pair structure, summed in the order of the per-structure totals kernel, as above
+     buried_*   iso_* - in_pair_*, one subtraction
+   The dense per-residue table [F, S, 4], its segments, min_buried, the strict > of in_interface and the statistics bits
+   FREESASA_GPU_STATS_PAIRS / _PAIR_RESIDUES are those of the entries above; the table reads the periodic isolated and pair areas.
+   Every output shared with freesasa_gpu_trajectory_file_groups_periodic is bit for bit what that run gives, and in cells that give
+   no structure an image the pair outputs are bit for bit those of the run without cells.
+   Per shard ONE batch goes through the periodic stage and the engine: frames | isolated groups | pair structures, 1 + G + K
+   structures and n + n_iso + n_pair atoms per frame, and the images of all of them (csrc/pbc_kernels.h has the layout); the
+   expanded batch must not exceed 2^30 atoms and images.  The cell is checked for the COMPLEXES alone: a pair structure's largest
+   radius never exceeds its complex's, so its c is no larger and a cell that suffices for the frame suffices for its pairs.
+   Class sums, residues, selections, fp32 per-atom output, the statistics word (bits 128 / 256 of it in the _residues_ entry), the
+   done-list and device lists work as in the groups' periodic run.  The done-list's first line carries bit 3 (and 4) in its f32=
+   word beside pairs= (and minburied=): the lists of this run and of the interfaces run without cells refuse each other, as do
+   those of an orthorhombic and a triclinic reading, of other pairs and of another min_buried.
+   Argument errors, -1 with a message before a device is touched or a file opened: bit 3 missing; then everything the entries
+   above refuse but bit 3 and bit 4.
+   Not offered: a memory form (it has no cells); the batch interface entries among periodic images (freesasa_gpu_interfaces_dev:
+   its contact screen would have to look among images); contact tables per frame, contact occupancy, exposure masks and volume
+   among periodic images. */
+int freesasa_gpu_trajectory_file_interfaces_periodic(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
+                                                     const struct freesasa_ingest_batch *batch, int structure,
+                                                     int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
+                                                     const int32_t *group, int n_groups,
+                                                     int alg, double probe_radius, int resolution, int frames_per_batch,
+                                                     const char *totals_path, const char *sasa_path, const char *class_sums_path,
+                                                     const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
+                                                     const char *group_areas_path, const char *iso_path,
+                                                     const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                                     long long *frames_total_out,
+                                                     int stats, const char *stats_path, const char *partials_path,
+                                                     const int32_t *pairs, int n_pairs, const char *pair_areas_path, char *err, int err_len);
+int freesasa_gpu_trajectory_file_interface_residues_periodic(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
+                                                             const struct freesasa_ingest_batch *batch, int structure,
+                                                             int frame_atoms, const int32_t *atom_index, const struct freesasa_ingest_selection *sel,
+                                                             const int32_t *group, int n_groups,
+                                                             int alg, double probe_radius, int resolution, int frames_per_batch,
+                                                             const char *totals_path, const char *sasa_path, const char *class_sums_path,
+                                                             const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
+                                                             const char *group_areas_path, const char *iso_path,
+                                                             const char *done_path, long long max_new_shards, const int *devices, int n_devices,
+                                                             long long *frames_total_out,
+                                                             int stats, const char *stats_path, const char *partials_path,
+                                                             const int32_t *pairs, int n_pairs, const char *pair_areas_path,
+                                                             double min_buried, const char *pair_res_path, char *err, int err_len);
 /* The segments of such a run, on the host: no device is needed.  *n_segments_out = S is set first; then, when seg_capacity >= S,
    seg_offsets_out [2 K + 1] (the prefix of the segments per side: side j = 2 k + q of pair k owns segments
    [seg_offsets[j], seg_offsets[j + 1])), seg_res_out [S] (the residue of every segment, counted within the structure) and
@@ -1276,7 +1337,8 @@ int freesasa_gpu_calc_groups(const double *xyz, const double *radii, const int64
    cut the group entry's.  A cell so large and so placed that no atom of s comes within c of a face gives every output of
    freesasa_gpu_groups_dev bit for bit; a right-angled triclinic cell gives the orthorhombic entry's.
    Not offered: exposure masks, volume or pairwise interfaces among periodic images (their entries take no cell).
-   Trajectories: freesasa_gpu_trajectory_file_groups_periodic. */
+   Trajectories: freesasa_gpu_trajectory_file_groups_periodic, and with the interfaces between the groups
+   freesasa_gpu_trajectory_file_interfaces_periodic. */
 int freesasa_gpu_groups_periodic_dev(freesasa_gpu_ctx *ctx, int alg, const double *d_xyz, const double *d_radii,
                                      const int64_t *offsets, int n_structs, const int32_t *d_group, const int32_t *n_groups,
                                      const double *cells /* host, [3 n_structs] */, double probe_radius, int resolution,
@@ -1407,7 +1469,8 @@ int freesasa_gpu_calc_interfaces(const double *xyz, const double *radii, const i
      a structure boundary (the message names residue and structures); min_buried negative, NaN or infinite; res_capacity < 0.
    One stream synchronization more than freesasa_gpu_interfaces_dev (R comes back to the host before delivery).
    Not offered: class splits (polar / apolar / main chain) of the buried area per residue, relative buried areas, per-residue
-     tables in the trajectory drivers, interfaces among periodic images, a per-atom contact criterion by distance.  (In the file sweep,
+     tables in the trajectory drivers, interfaces among periodic images in the batch entries (over a trajectory:
+     freesasa_gpu_trajectory_file_interfaces_periodic), a per-atom contact criterion by distance.  (In the file sweep,
      with the buried area of every side split by class: freesasa_gpu_sweep_files_interfaces above.)
 
    freesasa_gpu_interface_residues_dev: d_res_areas is required, d_res_offsets, d_res_index, d_res_atoms may be NULL; the rest

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """tools/interface_occupancy.py TOPOLOGY FRAMES... -o OUT.tsv [--chain-groups SPEC | --separate-chains] [--pairs all|A:B,...]
                                 [--min-buried X] [--alg lr|sr] [--resolution N] [--probe P] [--frames-per-batch N] [--devices 0,1]
+                                [--pbc [--triclinic]]
 
 Which residues make up the interfaces between the chain groups of a system over a trajectory, how much each buries on average
 and in what fraction of the frames it is in the interface at all (freesasa_amd.trajectory_file_topology with interface_pairs and
@@ -14,7 +15,12 @@ OUT.tsv has one line per SEGMENT - the atoms of one side of a pair that lie in o
 the label of the side the residue is on; its chain, name and number; its atoms in that group; mean, standard deviation, minimum
 and maximum over the frames of the area it buries in the pair (A^2); its mean isolated area; and its occupancy, the fraction of
 the frames in which it buries more than --min-buried (default 0; with Lee-Richards give a threshold above rounding noise, e.g.
-1).  It is made from the run statistics alone: the per-frame tables never leave the device."""
+1).  It is made from the run statistics alone: the per-frame tables never leave the device.
+
+--pbc: every frame, every group and every pair structure among the periodic images of the frame's own cell
+(freesasa_amd.trajectory_file_groups_periodic with interface_pairs): for a wrapped trajectory, whose partners may lie in different
+images of the box.  FRAMES must then be containers that carry a cell (.dcd with unit-cell records, .nc, .xtc, .trr); --triclinic
+reads the cell as a triclinic one."""
 import argparse
 import os
 import sys
@@ -64,12 +70,18 @@ def main(argv=None):
     ap.add_argument("--probe", type=float, default=1.4)
     ap.add_argument("--frames-per-batch", type=int, default=0)
     ap.add_argument("--devices", default="0")
+    ap.add_argument("--pbc", action="store_true", help="among the periodic images of every frame's own cell (containers that carry a cell)")
+    ap.add_argument("--triclinic", action="store_true", help="with --pbc: the cells read as triclinic cells")
     args = ap.parse_args(argv)
     if args.chain_groups and args.separate_chains:
         sys.exit("--chain-groups and --separate-chains exclude each other")
+    if args.triclinic and not args.pbc:
+        sys.exit("--triclinic goes with --pbc")
     for path in args.frames:
         if os.path.splitext(path)[1].lower() not in FORMATS:
             sys.exit(f"{path}: unknown trajectory format (one of {', '.join(sorted(FORMATS))})")
+        if args.pbc and FORMATS[os.path.splitext(path)[1].lower()] in ("f32", "f64"):
+            sys.exit(f"{path}: raw frame files carry no cell: --pbc needs .dcd, .nc, .xtc or .trr")
     import numpy as np
     import freesasa_amd as fa
     from freesasa_amd import ingest
@@ -100,11 +112,14 @@ def main(argv=None):
             # (the shard length is given, so that the frames of every partial are known: the driver's own default)
             fpb = args.frames_per_batch or 1250000 // max(frame_atoms, n + n_iso + n_pair) + 1
             p = lambda name: os.path.join(tmp, "%d.%s" % (k, name))
-            done, n_frames, _ = fa.trajectory_file_topology(path, batch, p("totals"), frame_atoms=frame_atoms,
-                                                            atom_index=None if frame_atoms == n else np.arange(n, dtype=np.int32),
-                                                            alg=alg, probe=args.probe, resolution=res, frames_per_batch=fpb, devices=devices,
-                                                            group=ids, n_groups=G, interface_pairs=pairs, min_buried=args.min_buried,
-                                                            stats=("pair_residues",), stats_path=p("stats"), partials_path=p("parts"), **kw)
+            if args.pbc:
+                kw["triclinic"] = args.triclinic
+            run = fa.trajectory_file_groups_periodic if args.pbc else fa.trajectory_file_topology
+            done, n_frames, _ = run(path, batch, p("totals"), frame_atoms=frame_atoms,
+                                    atom_index=None if frame_atoms == n else np.arange(n, dtype=np.int32),
+                                    alg=alg, probe=args.probe, resolution=res, frames_per_batch=fpb, devices=devices,
+                                    group=ids, n_groups=G, interface_pairs=pairs, min_buried=args.min_buried,
+                                    stats=("pair_residues",), stats_path=p("stats"), partials_path=p("parts"), **kw)
             assert done
             fpb = min(fpb, n_frames)
             parts.append(np.fromfile(p("parts"), dtype=np.float64).reshape(-1, 4, 4 * S))

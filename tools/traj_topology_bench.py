@@ -46,7 +46,12 @@ into two groups of 5 000 atoms, totals and group areas only:
     filled-groups-pbc  freesasa_gpu_trajectory_file_groups_periodic: chain groups among periodic images - its totals file must be
                        filled-topo-pbc's, byte for byte
 each line with real_atoms, group_atoms and image_atoms (the images of the complex and of its groups in frame 0): the atoms per
-frame the engine sees are their sum.
+frame in the engine.  With --interfaces beside --pbc --groups two arms more (and with --interface-residues a third), the one pair of the two groups:
+    filled-interfaces              freesasa_gpu_trajectory_file_interfaces without the bit
+    filled-interfaces-pbc          freesasa_gpu_trajectory_file_interfaces_periodic: its totals and group areas must be filled-groups-pbc's
+    filled-interface-residues-pbc  freesasa_gpu_trajectory_file_interface_residues_periodic, min_buried = 0
+each line with pair_atoms and, in image_atoms, the pair structure's images as well.  engine_atoms_per_frame is the sum of the four: the
+atoms per frame the engine sees.
 With --netcdf beside --pbc two arms more: `solvated` and `solvated-pbc` on an AMBER NetCDF file of the same frames and cell
 (solvated-nc, solvated-nc-pbc); their totals files must be those of the DCD arms, byte for byte.
 
@@ -92,7 +97,7 @@ the share of k_traj_pair_res alone goes into those two lines as pair_res_kernel_
 
 One JSON line per arm: atom-frames/s counted in SOLUTE atoms and in frame atoms, the median and the spread of --reps runs.
 
-    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd] [--netcdf] [--pbc [--pbc-arms all|off] [--triclinic] [--groups]] [--xtc [--xtc-distinct 24] [--xtc-fpb 0]] [--trr [--double] [--trr-arms raw,trr]] [--stats] [--groups [--interfaces [--interface-residues [--stats]]] [--kernel-stats FILE]]
+    python tools/traj_topology_bench.py [--frames 240] [--reps 5] [--arms plain,totals,all,groups,longway] [--scratch DIR] [--out FILE] [--dcd] [--netcdf] [--pbc [--pbc-arms all|off] [--triclinic] [--groups [--interfaces [--interface-residues]]]] [--xtc [--xtc-distinct 24] [--xtc-fpb 0]] [--trr [--double] [--trr-arms raw,trr]] [--stats] [--groups [--interfaces [--interface-residues [--stats]]] [--kernel-stats FILE]]
 
 For the kernel times: `rocprofv3 --kernel-trace --stats -- python tools/traj_topology_bench.py --reps 1 --arms all`
 (k_traj_gather / k_traj_residues / k_traj_class / k_traj_sel are the topology's kernels, k_traj_group_* the groups')."""
@@ -397,7 +402,7 @@ def stats_mode(args, scratch):
 
 
 def new_kernels_share(path, only=None):
-    """the share of k_traj_pair_* and k_totals (only: of that kernel alone) in the kernel time of a rocprofv3 kernel-stats CSV
+    """the share of k_traj_pair_* and k_totals (only: of that kernel alone, or of a tuple of kernels) in the kernel time of a rocprofv3 kernel-stats CSV
     (columns Name, ..., TotalDurationNs)"""
     import csv
     new = total = 0.0
@@ -406,7 +411,7 @@ def new_kernels_share(path, only=None):
             ns = float(row["TotalDurationNs"])
             total += ns
             name = row["Name"].split("(")[0]
-            if name == only if only else name.startswith("k_traj_pair_") or name == "k_totals":
+            if (name in only if isinstance(only, tuple) else name == only) if only else name.startswith("k_traj_pair_") or name == "k_totals":
                 new += ns
     return new / total if total else None
 
@@ -494,10 +499,12 @@ def main():
     ap.add_argument("--triclinic", action="store_true", help="with --pbc: the arms of the triclinic bit beside the others")
     ap.add_argument("--groups", action="store_true", help="with --pbc: chain groups among periodic images against the plain periodic run and the non-periodic groups' run; "
                                                           "without: the solute as four chains, a group each")
-    ap.add_argument("--interfaces", action="store_true", help="with --groups (without --pbc): the interfaces between all pairs of the four chains beside the groups' run")
+    ap.add_argument("--interfaces", action="store_true", help="with --groups: the interfaces between all pairs of the four chains beside the groups' run; "
+                                                             "with --pbc --groups: the interfaces between the two groups without and among periodic images")
     ap.add_argument("--interface-residues", action="store_true", help="with --groups --interfaces: the per-residue interface tables beside them; with --stats as well: "
                                                                       "the statistics of both pair outputs with neither delivered")
-    ap.add_argument("--kernel-stats", default=None, help="with --groups --interfaces: a rocprofv3 kernel-stats CSV; the share of the pairs' kernels in it is reported")
+    ap.add_argument("--kernel-stats", default=None, help="with --groups --interfaces: a rocprofv3 kernel-stats CSV; the share of the pairs' kernels in it is reported "
+                                                           "(with --pbc: of k_gpbc_cells and k_gpbc_finish, the phases that carry the pair part)")
     ap.add_argument("--xtc", action="store_true", help="time a GROMACS XTC file against the raw fp32 file and an AMBER NetCDF file of the same decoded frames")
     ap.add_argument("--xtc-distinct", type=int, default=24, help="with --xtc: distinct frames that are encoded and then repeated")
     ap.add_argument("--xtc-fpb", type=int, default=0, help="with --xtc: frames_per_batch of all three arms (0: the driver's default)")
@@ -508,12 +515,12 @@ def main():
     args = ap.parse_args()
     scratch = args.scratch or tempfile.mkdtemp(prefix="traj_topology_bench_")
     try:
-        if args.interfaces and (args.pbc or not args.groups):
-            ap.error("--interfaces goes with --groups and without --pbc")
+        if args.interfaces and not args.groups:
+            ap.error("--interfaces goes with --groups")
         if args.interface_residues and not args.interfaces:
             ap.error("--interface-residues goes with --groups --interfaces")
         if args.xtc or args.stats or args.trr or (args.groups and not args.pbc):
-            lines = groups_mode(args, scratch) if args.interface_residues else stats_mode(args, scratch) if args.stats else trr_mode(args, scratch) if args.trr else xtc_mode(args, scratch) if args.xtc \
+            lines = groups_mode(args, scratch) if args.interface_residues and not args.pbc else stats_mode(args, scratch) if args.stats else trr_mode(args, scratch) if args.trr else xtc_mode(args, scratch) if args.xtc \
                 else groups_mode(args, scratch)
             print("\n".join(lines))
             if args.out:
@@ -566,6 +573,16 @@ def main():
                                                                                   group_areas_path=p("g17")),
                              "filled-groups-pbc": lambda: fa.trajectory_file_groups_periodic(fill, b, p("t18"), dcd=True, group=ids, n_groups=2,
                                                                                              group_areas_path=p("g18"))})
+            if args.groups and args.interfaces and args.pbc_arms == "all":
+                arms.update({"filled-interfaces": lambda: fa.trajectory_file_topology(fill, b, p("t19"), dcd=True, group=ids, n_groups=2, group_areas_path=p("g19"),
+                                                                                      interface_pairs="all", pair_areas_path=p("p19")),
+                             "filled-interfaces-pbc": lambda: fa.trajectory_file_groups_periodic(fill, b, p("t20"), dcd=True, group=ids, n_groups=2,
+                                                                                                 group_areas_path=p("g20"), interface_pairs="all",
+                                                                                                 pair_areas_path=p("p20"))})
+                if args.interface_residues:
+                    arms["filled-interface-residues-pbc"] = lambda: fa.trajectory_file_groups_periodic(
+                        fill, b, p("t21"), dcd=True, group=ids, n_groups=2, group_areas_path=p("g21"), interface_pairs="all", pair_areas_path=p("p21"),
+                        pair_residues_path=p("r21"), min_buried=0.0)
             if args.netcdf:
                 arms["solvated-nc"] = lambda: fa.trajectory_file_topology(solv_nc, b, p("t14"), atom_index=index, netcdf=True)
                 if args.pbc_arms == "all":
@@ -597,6 +614,24 @@ def main():
             assert np.array_equal(np.fromfile(p("t18")), np.fromfile(p("t16"))) and np.array_equal(np.fromfile(p("t18")), np.fromfile(p("t9")))
             assert not np.array_equal(np.fromfile(p("g18")), np.fromfile(p("g17")))
             images["filled-topo-pbc"] = images["filled-groups-pbc"] = images["filled-pbc"]
+        if "filled-interfaces-pbc" in names:  # ... and with the one pair of the two groups: its pair structure holds the complex's atoms, group by group
+            r, gi, ti = atoms["filled-groups-pbc"]
+            atoms = {a: v + (0,) for a, v in atoms.items()}
+            atoms["filled-interfaces"] = (r, gi, 0, N_SOLUTE)
+            x0 = first_frame(fill, N_SOLUTE)
+            order = np.concatenate([np.flatnonzero(ids == 0), np.flatnonzero(ids == 1)])
+            k_p = int(fa.calc_periodic(x0[order], b.radii[order], [0, N_SOLUTE], [fill_cell])[2][0])
+            atoms["filled-interfaces-pbc"] = atoms["filled-interface-residues-pbc"] = (r, gi, ti + k_p, N_SOLUTE)
+            images["filled-interfaces-pbc"] = images["filled-interface-residues-pbc"] = images["filled-pbc"]
+            # the outputs shared with the groups' periodic run are its bytes; the pairs' rows are those of the definition's columns
+            assert np.array_equal(np.fromfile(p("t20")), np.fromfile(p("t18"))) and np.array_equal(np.fromfile(p("g20")), np.fromfile(p("g18")))
+            rows, areas = np.fromfile(p("p20")).reshape(args.frames, 1, 6), np.fromfile(p("g20")).reshape(args.frames, 2, 3)
+            assert np.array_equal(rows[:, 0, :2], areas[:, :, 0]) and np.array_equal(rows[:, 0, 4:], rows[:, 0, :2] - rows[:, 0, 2:4])
+            assert not np.array_equal(rows, np.fromfile(p("p19")).reshape(args.frames, 1, 6))
+            if "filled-interface-residues-pbc" in names:
+                assert np.array_equal(np.fromfile(p("p21")), np.fromfile(p("p20")))
+                table = np.fromfile(p("r21")).reshape(args.frames, -1, 4)
+                assert np.all(table[:, :, 2] == table[:, :, 0] - table[:, :, 1]) and np.array_equal(table[:, :, 3], (table[:, :, 2] > 0.0).astype(np.float64))
         totals = [np.fromfile(p(k)) for a, k in (("plain", "t0"), ("totals", "t1"), ("all", "t2"), ("groups", "t3"), ("raw", "t1"), ("dcd", "t5"), ("netcdf", "t13")) if a in names]
         assert all(np.array_equal(t, totals[0]) for t in totals)
         if "solvated-pbc" in names:      # no atom of the solute within c of a face: the bit changes nothing; a filled box: it must
@@ -620,7 +655,12 @@ def main():
             if args.pbc:
                 line["images_per_atom"] = images.get(a)
             if a in atoms:
-                line["real_atoms"], line["group_atoms"], line["image_atoms"] = atoms[a]
+                line["real_atoms"], line["group_atoms"], line["image_atoms"] = atoms[a][:3]
+                if len(atoms[a]) > 3:
+                    line["pair_atoms"] = atoms[a][3]
+                line["engine_atoms_per_frame"] = int(sum(atoms[a]))
+            if a.startswith("filled-interface") and a.endswith("-pbc") and args.kernel_stats:
+                line["new_kernels_share"] = new_kernels_share(args.kernel_stats, ("k_gpbc_cells", "k_gpbc_finish"))
             lines.append(json.dumps(line))
         print("\n".join(lines))
         if args.out:
