@@ -1376,8 +1376,80 @@ STATS_BITS = {"totals": 1, "atoms": 2, "isolated": 4, "classes": 8, "residues": 
 PAIR_STATS_BITS = {"pairs": 128, "pair_residues": 256}
 
 
+# The trajectory entries with a topology (include/freesasa_gpu.h): their argument lists from named pieces.  A piece is a list of
+# (argument, ctype); _OUT is an output - the caller's array of doubles in the memory form, a result file's path in the file form -
+# and "head" and "tail" are (the memory form's, the file form's).
+_i32p, _llp = C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
+_OUT = (_dp, C.c_char_p)
+_TRAJ_PIECES = {
+    "head": ([("frames", _dp), ("n_frames", C.c_int)],
+             [("frames_path", C.c_char_p), ("frames_f32", C.c_int), ("header_bytes", C.c_longlong), ("n_frames", C.c_longlong)]),
+    "topology": [("batch", C.c_void_p), ("structure", C.c_int), ("frame_atoms", C.c_int), ("atom_index", _i32p), ("selection", C.c_void_p)],
+    "groups": [("group", _i32p), ("n_groups", C.c_int)],
+    "parameters": [("alg", C.c_int), ("probe", C.c_double), ("resolution", C.c_int), ("frames_per_batch", C.c_int)],
+    "outputs": [("totals", _OUT), ("sasa", _OUT), ("class_sums", _OUT), ("residues", _OUT), ("sel_area", _OUT), ("sel_atoms", _llp)],
+    "group_outputs": [("group_areas", _OUT), ("isolated", _OUT)],
+    "volumes": [("volumes", _OUT)],
+    "masks": [("masks", (_u32p, C.c_char_p))],
+    "tail": ([("devices", _ip), ("n_devices", C.c_int)],
+             [("done_path", C.c_char_p), ("max_new_shards", C.c_longlong), ("devices", _ip), ("n_devices", C.c_int), ("frames_total", _llp)]),
+    "statistics": [("stats", C.c_int), ("stats_to", _OUT), ("partials_to", _OUT)],
+    "pairs": [("pairs", _i32p), ("n_pairs", C.c_int), ("pair_areas", _OUT)],
+    "pair_residues": [("min_buried", C.c_double), ("pair_residues", _OUT)],
+    "err": [("err", C.c_char_p), ("err_len", C.c_int)],
+}
+# entry -> its pieces: freesasa_gpu_trajectory_<entry> has them in the memory form, freesasa_gpu_trajectory_file_<entry> in the file form
+_GROUPS = "head topology groups parameters outputs group_outputs tail"
+_TRAJ_ENTRIES = {
+    "topology": "head topology parameters outputs tail err",
+    "volume": "head topology parameters outputs volumes tail err",
+    "masks": "head topology parameters outputs masks tail err",
+    "groups": _GROUPS + " err",
+    "groups_stats": _GROUPS + " statistics err",
+    "interfaces": _GROUPS + " statistics pairs err",
+    "interface_residues": _GROUPS + " statistics pairs pair_residues err",
+}
+# ... and the file entries among periodic images, which have their siblings' arguments
+_TRAJ_PERIODIC = {"file_groups_periodic": "groups_stats", "file_interfaces_periodic": "interfaces", "file_interface_residues_periodic": "interface_residues"}
+
+
+def _traj_entry_args(name):
+    """[(argument, ctype)] of freesasa_gpu_trajectory_<name>, err and err_len included"""
+    form = int(name.startswith("file_"))
+    pieces = _TRAJ_ENTRIES[_TRAJ_PERIODIC.get(name) or name[5 * form:]].split()
+    args = [a for p in pieces for a in (_TRAJ_PIECES[p][form] if p in ("head", "tail") else _TRAJ_PIECES[p])]
+    return [(arg, t[form] if isinstance(t, tuple) else t) for arg, t in args]
+
+
+def _traj_protos(L):
+    for name in list(_TRAJ_ENTRIES) + ["file_" + k for k in _TRAJ_ENTRIES] + list(_TRAJ_PERIODIC):
+        getattr(L, "freesasa_gpu_trajectory_" + name).argtypes = [t for _, t in _traj_entry_args(name)]
+    return L
+
+
+def _traj_call(name, batch, selection, devices, device, **values):
+    """Calls freesasa_gpu_trajectory_<name> with the arguments its pieces name, taken from `values` - which may hold more: the
+    arguments of the entry's siblings; arrays go as they are, paths as str() of what they are - and returns its code; a refusal
+    is a RuntimeError that begins with the entry's name."""
+    cb = batch._as_c()
+    keep, dp_, nd = _devs(devices, device)
+    values.update(batch=C.byref(cb), selection=selection.handle if selection is not None else None, devices=dp_, n_devices=nd)
+    args = []
+    for arg, ctype in _traj_entry_args(name)[:-2]:
+        v = values[arg]
+        if isinstance(v, np.ndarray):
+            v = v.ctypes.data_as(ctype)
+        elif ctype is C.c_char_p and v is not None:
+            v = str(v).encode()
+        args.append(v)
+    err = C.create_string_buffer(512)
+    ret = getattr(_traj_protos(lib()), "freesasa_gpu_trajectory_" + name)(*args, err, 512)
+    if ret < 0:
+        raise RuntimeError("freesasa_gpu_trajectory_" + name + ": " + err.value.decode())
+    return ret
+
+
 def _stats_proto(L):
-    _i32p, _llp = C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
     L.freesasa_gpu_traj_stats_width.argtypes = [C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _llp]
     L.freesasa_gpu_traj_stats_width.restype = C.c_longlong
     L.freesasa_gpu_traj_stats_merge.argtypes = [_dp, _llp, C.c_longlong, C.c_longlong, _dp, _llp]
@@ -1386,31 +1458,11 @@ def _stats_proto(L):
     L.freesasa_gpu_trajectory_file_stats.argtypes = [C.c_char_p, C.c_int, C.c_longlong, _dp, C.c_int, C.c_longlong, C.c_int, C.c_double,
                                                      C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_longlong, _ip, C.c_int,
                                                      _llp, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
-    L.freesasa_gpu_trajectory_groups_stats.argtypes = [_dp, C.c_int, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_void_p, _i32p, C.c_int,
-                                                       C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _llp, _dp, _dp,
-                                                       _ip, C.c_int, C.c_int, _dp, _dp, C.c_char_p, C.c_int]
-    L.freesasa_gpu_trajectory_file_groups_stats.argtypes = [C.c_char_p, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, C.c_int, _i32p,
-                                                            C.c_void_p, _i32p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_char_p,
-                                                            C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, _llp, C.c_char_p, C.c_char_p,
-                                                            C.c_char_p, C.c_longlong, _ip, C.c_int, _llp, C.c_int, C.c_char_p, C.c_char_p,
-                                                            C.c_char_p, C.c_int]
-    L.freesasa_gpu_trajectory_file_groups_periodic.argtypes = L.freesasa_gpu_trajectory_file_groups_stats.argtypes
-    # the same with interface pairs: (pairs, n_pairs, the pair areas: an array / a path) in front of err
-    L.freesasa_gpu_trajectory_interfaces.argtypes = L.freesasa_gpu_trajectory_groups_stats.argtypes[:-2] + [_i32p, C.c_int, _dp, C.c_char_p, C.c_int]
-    L.freesasa_gpu_trajectory_file_interfaces.argtypes = L.freesasa_gpu_trajectory_file_groups_stats.argtypes[:-2] + \
-        [_i32p, C.c_int, C.c_char_p, C.c_char_p, C.c_int]
-    # ... and with their per-residue table: (min_buried, the pair residues: an array / a path) in front of err
-    L.freesasa_gpu_trajectory_interface_residues.argtypes = L.freesasa_gpu_trajectory_interfaces.argtypes[:-2] + [C.c_double, _dp, C.c_char_p, C.c_int]
-    L.freesasa_gpu_trajectory_file_interface_residues.argtypes = L.freesasa_gpu_trajectory_file_interfaces.argtypes[:-2] + \
-        [C.c_double, C.c_char_p, C.c_char_p, C.c_int]
-    # ... and both among periodic images: their siblings' signatures
-    L.freesasa_gpu_trajectory_file_interfaces_periodic.argtypes = L.freesasa_gpu_trajectory_file_interfaces.argtypes
-    L.freesasa_gpu_trajectory_file_interface_residues_periodic.argtypes = L.freesasa_gpu_trajectory_file_interface_residues.argtypes
     L.freesasa_gpu_trajectory_interface_segments.argtypes = [C.c_void_p, C.c_int, _i32p, C.c_int, _i32p, C.c_int, C.c_longlong, _llp, _llp, _i32p,
                                                              _i32p, C.c_char_p, C.c_int]
     L.freesasa_gpu_traj_stats_width_pairs.argtypes = [C.c_int] + 6 * [C.c_longlong] + [_llp]
     L.freesasa_gpu_traj_stats_width_pairs.restype = C.c_longlong
-    return L
+    return _traj_protos(L)
 
 
 def stats_word(stats, pairs=False):
@@ -1758,39 +1810,7 @@ def trajectory_file(frames_path, radii, totals_path, sasa_path=None, done_path=N
 
 
 def _topology_proto(L):
-    _i32p, _llp = C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
-    L.freesasa_gpu_trajectory_topology.argtypes = [_dp, C.c_int, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_void_p,
-                                                   C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _llp,
-                                                   _ip, C.c_int, C.c_char_p, C.c_int]
-    L.freesasa_gpu_trajectory_file_topology.argtypes = [C.c_char_p, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, C.c_int, _i32p,
-                                                        C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
-                                                        C.c_char_p, C.c_char_p, C.c_char_p, _llp, C.c_char_p, C.c_longlong, _ip, C.c_int,
-                                                        _llp, C.c_char_p, C.c_int]
-    # ... with the frames' volumes behind sel_atoms_out (an array / a path)
-    L.freesasa_gpu_trajectory_volume.argtypes = [_dp, C.c_int, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_void_p,
-                                                 C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _llp, _dp,
-                                                 _ip, C.c_int, C.c_char_p, C.c_int]
-    L.freesasa_gpu_trajectory_file_volume.argtypes = [C.c_char_p, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, C.c_int, _i32p,
-                                                      C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
-                                                      C.c_char_p, C.c_char_p, C.c_char_p, _llp, C.c_char_p, C.c_char_p, C.c_longlong, _ip, C.c_int,
-                                                      _llp, C.c_char_p, C.c_int]
-    # ... with the frames' exposure masks behind sel_atoms_out (an array / a path)
-    L.freesasa_gpu_trajectory_masks.argtypes = [_dp, C.c_int, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_void_p,
-                                                C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _llp, _u32p,
-                                                _ip, C.c_int, C.c_char_p, C.c_int]
-    L.freesasa_gpu_trajectory_file_masks.argtypes = [C.c_char_p, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, C.c_int, _i32p,
-                                                     C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
-                                                     C.c_char_p, C.c_char_p, C.c_char_p, _llp, C.c_char_p, C.c_char_p, C.c_longlong, _ip, C.c_int,
-                                                     _llp, C.c_char_p, C.c_int]
-    # the same with chain groups: (group, n_groups) behind the selection set, the two group outputs behind sel_atoms_out
-    L.freesasa_gpu_trajectory_groups.argtypes = [_dp, C.c_int, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_void_p, _i32p, C.c_int,
-                                                 C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _llp, _dp, _dp,
-                                                 _ip, C.c_int, C.c_char_p, C.c_int]
-    L.freesasa_gpu_trajectory_file_groups.argtypes = [C.c_char_p, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, C.c_int, _i32p,
-                                                      C.c_void_p, _i32p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_char_p,
-                                                      C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, _llp, C.c_char_p, C.c_char_p,
-                                                      C.c_char_p, C.c_longlong, _ip, C.c_int, _llp, C.c_char_p, C.c_int]
-    return L
+    return _traj_protos(L)
 
 
 class TopologyResult:
@@ -1939,72 +1959,16 @@ def trajectory_topology(frames, batch, structure=0, atom_index=None, selection=N
         raise ValueError("volumes=True is not offered with chain groups, stats= or per_frame=False")
     if masks and (volumes or stats or not per_frame or chain_groups is not None or separate_chains or group is not None):
         raise ValueError("masks=True is not offered with chain groups, stats=, per_frame=False or volumes=True")
-    if stats or not per_frame or interface_pairs is not None:
-        return _trajectory_topology_stats(frames, batch, structure, atom_index, selection, per_atom, alg, probe, resolution, frames_per_batch,
-                                          device, devices, chain_groups, separate_chains, long, group, n_groups, stats, per_frame, interface_pairs,
-                                          interface_residues, min_buried)
-    L = _topology_proto(lib())
-    frames = np.ascontiguousarray(frames, dtype=np.float64)
-    if frames.ndim != 3 or frames.shape[2] != 3:
-        raise ValueError("frames must be [n_frames, frame_atoms, 3]")
-    F = frames.shape[0]
-    n, R, res_ref, idx, fa_ = _topology_args(batch, structure, atom_index, frames.shape[1])
-    S = len(selection) if selection is not None else 0
-    totals, cls, res = np.zeros(F), np.zeros((F, 3)), np.zeros((F, R, 6))
-    sel_area = np.zeros((F, S)) if selection is not None else None
-    sel_atoms = np.zeros(S, dtype=np.int64) if selection is not None else None
-    sasa = np.zeros((F, n)) if per_atom else None
-    err = C.create_string_buffer(512)
-    keep, dp_, nd = _devs(devices, device)
-    cb = batch._as_c()
-    opt = lambda a, t=_dp: None if a is None else a.ctypes.data_as(t)
-    ids, G, g_atoms = _topology_groups(batch, structure, n, chain_groups, separate_chains, long, group, n_groups)
-    if volumes:
-        vols = np.zeros(F)
-        ret = L.freesasa_gpu_trajectory_volume(frames.ctypes.data_as(_dp), F, C.byref(cb), structure, fa_, opt(idx, C.POINTER(C.c_int32)),
-                                               selection.handle if selection is not None else None, alg, probe, resolution,
-                                               frames_per_batch, totals.ctypes.data_as(_dp), opt(sasa), cls.ctypes.data_as(_dp),
-                                               res.ctypes.data_as(_dp), opt(sel_area), opt(sel_atoms, C.POINTER(C.c_longlong)),
-                                               vols.ctypes.data_as(_dp), dp_, nd, err, 512)
-        if ret:
-            raise RuntimeError("freesasa_gpu_trajectory_volume: " + err.value.decode())
-        return TopologyResult(totals, cls, res, sel_area, sel_atoms, sasa, res_ref, volumes=vols)
-    if masks:
-        mk = np.zeros((F, n, 4), dtype=np.uint32)
-        ret = L.freesasa_gpu_trajectory_masks(frames.ctypes.data_as(_dp), F, C.byref(cb), structure, fa_, opt(idx, C.POINTER(C.c_int32)),
-                                              selection.handle if selection is not None else None, alg, probe, resolution,
-                                              frames_per_batch, totals.ctypes.data_as(_dp), opt(sasa), cls.ctypes.data_as(_dp),
-                                              res.ctypes.data_as(_dp), opt(sel_area), opt(sel_atoms, C.POINTER(C.c_longlong)),
-                                              mk.ctypes.data_as(_u32p), dp_, nd, err, 512)
-        if ret:
-            raise RuntimeError("freesasa_gpu_trajectory_masks: " + err.value.decode())
-        return TopologyResult(totals, cls, res, sel_area, sel_atoms, sasa, res_ref, masks=mk)
-    if ids is None:
-        ret = L.freesasa_gpu_trajectory_topology(frames.ctypes.data_as(_dp), F, C.byref(cb), structure, fa_, opt(idx, C.POINTER(C.c_int32)),
-                                                 selection.handle if selection is not None else None, alg, probe, resolution,
-                                                 frames_per_batch, totals.ctypes.data_as(_dp), opt(sasa), cls.ctypes.data_as(_dp),
-                                                 res.ctypes.data_as(_dp), opt(sel_area), opt(sel_atoms, C.POINTER(C.c_longlong)),
-                                                 dp_, nd, err, 512)
-        if ret:
-            raise RuntimeError("freesasa_gpu_trajectory_topology: " + err.value.decode())
-        return TopologyResult(totals, cls, res, sel_area, sel_atoms, sasa, res_ref)
-    g_areas = np.zeros((F, max(G, 0), 3))
-    iso = np.zeros((F, n)) if per_atom else None
-    ret = L.freesasa_gpu_trajectory_groups(frames.ctypes.data_as(_dp), F, C.byref(cb), structure, fa_, opt(idx, C.POINTER(C.c_int32)),
-                                           selection.handle if selection is not None else None, opt(ids, C.POINTER(C.c_int32)), G,
-                                           alg, probe, resolution, frames_per_batch, totals.ctypes.data_as(_dp), opt(sasa),
-                                           cls.ctypes.data_as(_dp), res.ctypes.data_as(_dp), opt(sel_area),
-                                           opt(sel_atoms, C.POINTER(C.c_longlong)), g_areas.ctypes.data_as(_dp), opt(iso),
-                                           dp_, nd, err, 512)
-    if ret:
-        raise RuntimeError("freesasa_gpu_trajectory_groups: " + err.value.decode())
-    return TopologyResult(totals, cls, res, sel_area, sel_atoms, sasa, res_ref, g_areas, g_atoms, iso)
+    return _trajectory_topology_stats(frames, batch, structure, atom_index, selection, per_atom, alg, probe, resolution, frames_per_batch,
+                                      device, devices, chain_groups, separate_chains, long, group, n_groups, stats, per_frame, interface_pairs,
+                                      interface_residues, min_buried, volumes, masks)
 
 
 def _trajectory_topology_stats(frames, batch, structure, atom_index, selection, per_atom, alg, probe, resolution, frames_per_batch,
                                device, devices, chain_groups, separate_chains, long, group, n_groups, stats, per_frame, interface_pairs=None,
-                               interface_residues=False, min_buried=0.0):
-    L = _stats_proto(_topology_proto(lib()))
+                               interface_residues=False, min_buried=0.0, volumes=False, masks=False):
+    """the memory form of every entry with a topology: the arrays once, and the entry by what is asked for"""
+    L = _stats_proto(lib())
     frames = np.ascontiguousarray(frames, dtype=np.float64)
     if frames.ndim != 3 or frames.shape[2] != 3:
         raise ValueError("frames must be [n_frames, frame_atoms, 3]")
@@ -2013,64 +1977,38 @@ def _trajectory_topology_stats(frames, batch, structure, atom_index, selection, 
     S = len(selection) if selection is not None else 0
     ids, G, g_atoms = _topology_groups(batch, structure, n, chain_groups, separate_chains, long, group, n_groups)
     pairs = _interface_pairs(interface_pairs, ids, G)
+    with_res = pairs is not None and bool(interface_residues)
     word = stats_word(stats, pairs=bool(interface_residues))
-    totals = np.zeros(F)
-    cls, res = (np.zeros((F, 3)), np.zeros((F, R, 6))) if per_frame else (None, None)
-    sel_area = np.zeros((F, S)) if selection is not None and per_frame else None
-    sel_atoms = np.zeros(S, dtype=np.int64) if selection is not None else None
-    sasa = np.zeros((F, n)) if per_atom else None
-    g_areas = np.zeros((F, max(G, 0), 3)) if ids is not None and per_frame else None
-    iso = np.zeros((F, n)) if ids is not None and per_atom else None
-    W = _stats_proto(lib()).freesasa_gpu_traj_stats_width(word, n, R, S, max(G, 0), None)
+    K, NS, segments = 0 if pairs is None else pairs.shape[0], 0, (None, None, None)
+    if with_res:
+        # (the library's refusals of the topology, the ids and the pairs come from the segments entry first, with its messages)
+        segments = traj_pair_segments(batch, ids, G, pairs, structure)
+        NS = segments[1].size
+    name = "interface_residues" if with_res else "interfaces" if pairs is not None else "volume" if volumes else "masks" if masks else \
+        "groups_stats" if stats or not per_frame else "topology" if ids is None else "groups"
+    out = dict(totals=np.zeros(F), sasa=np.zeros((F, n)) if per_atom else None,
+               class_sums=np.zeros((F, 3)) if per_frame else None, residues=np.zeros((F, R, 6)) if per_frame else None,
+               sel_area=np.zeros((F, S)) if selection is not None and per_frame else None,
+               sel_atoms=np.zeros(S, dtype=np.int64) if selection is not None else None,
+               group_areas=np.zeros((F, max(G, 0), 3)) if ids is not None and per_frame else None,
+               isolated=np.zeros((F, n)) if ids is not None and per_atom else None,
+               volumes=np.zeros(F) if volumes else None, masks=np.zeros((F, n, 4), dtype=np.uint32) if masks else None,
+               pair_areas=np.zeros((F, K, 6)) if pairs is not None and (per_frame or not with_res or not word & PAIR_STATS_BITS["pairs"]) else None,
+               pair_residues=np.zeros((F, NS, 4)) if with_res and (per_frame or not word & PAIR_STATS_BITS["pair_residues"]) else None)
+    W = L.freesasa_gpu_traj_stats_width_pairs(word, n, R, S, max(G, 0), K, NS, None) if with_res else \
+        L.freesasa_gpu_traj_stats_width(word, n, R, S, max(G, 0), None)
     raw = np.empty((4, max(W, 0)))
     nf = _shard_frames(F, frames_per_batch)
     parts = None if nf is None or not word else np.empty((nf.size, 4, max(W, 0)))
-    err = C.create_string_buffer(512)
-    keep, dp_, nd = _devs(devices, device)
-    cb = batch._as_c()
-    opt = lambda a, t=_dp: None if a is None else a.ctypes.data_as(t)
-    if pairs is not None and interface_residues:
-        # (the library's refusals of the topology, the ids and the pairs come from the segments entry first, with its messages)
-        s_offs, s_res, s_atoms = traj_pair_segments(batch, ids, G, pairs, structure)
-        K, NS = pairs.shape[0], s_res.size
-        W = L.freesasa_gpu_traj_stats_width_pairs(word, n, R, S, max(G, 0), K, NS, None)
-        raw = np.empty((4, max(W, 0)))
-        parts = None if nf is None or not word else np.empty((nf.size, 4, max(W, 0)))
-        p_areas = np.zeros((F, K, 6)) if per_frame or not word & PAIR_STATS_BITS["pairs"] else None
-        p_res = np.zeros((F, NS, 4)) if per_frame or not word & PAIR_STATS_BITS["pair_residues"] else None
-        ret = L.freesasa_gpu_trajectory_interface_residues(frames.ctypes.data_as(_dp), F, C.byref(cb), structure, fa_, opt(idx, C.POINTER(C.c_int32)),
-                                                           selection.handle if selection is not None else None, opt(ids, C.POINTER(C.c_int32)), G,
-                                                           alg, probe, resolution, frames_per_batch, totals.ctypes.data_as(_dp), opt(sasa),
-                                                           opt(cls), opt(res), opt(sel_area), opt(sel_atoms, C.POINTER(C.c_longlong)), opt(g_areas),
-                                                           opt(iso), dp_, nd, word, raw.ctypes.data_as(_dp) if word else None, opt(parts),
-                                                           pairs.ctypes.data_as(C.POINTER(C.c_int32)), K, opt(p_areas), float(min_buried), opt(p_res),
-                                                           err, 512)
-        if ret:
-            raise RuntimeError("freesasa_gpu_trajectory_interface_residues: " + err.value.decode())
-        run = RunStats(raw, word, n, R, S, max(G, 0), parts, nf, n_pairs=K, n_segments=NS) if word else None
-        return TopologyResult(totals, cls, res, sel_area, sel_atoms, sasa, res_ref, g_areas, g_atoms, iso, run, pair_areas=p_areas, pair_groups=pairs,
-                              pair_residues=p_res, pair_res_offsets=s_offs, pair_res_index=s_res, pair_res_atoms=s_atoms)
-    if pairs is not None:
-        p_areas = np.zeros((F, pairs.shape[0], 6))
-        ret = L.freesasa_gpu_trajectory_interfaces(frames.ctypes.data_as(_dp), F, C.byref(cb), structure, fa_, opt(idx, C.POINTER(C.c_int32)),
-                                                   selection.handle if selection is not None else None, opt(ids, C.POINTER(C.c_int32)), G,
-                                                   alg, probe, resolution, frames_per_batch, totals.ctypes.data_as(_dp), opt(sasa),
-                                                   opt(cls), opt(res), opt(sel_area), opt(sel_atoms, C.POINTER(C.c_longlong)), opt(g_areas),
-                                                   opt(iso), dp_, nd, word, raw.ctypes.data_as(_dp) if word else None, opt(parts),
-                                                   pairs.ctypes.data_as(C.POINTER(C.c_int32)), pairs.shape[0], p_areas.ctypes.data_as(_dp), err, 512)
-        if ret:
-            raise RuntimeError("freesasa_gpu_trajectory_interfaces: " + err.value.decode())
-        run = RunStats(raw, word, n, R, S, max(G, 0), parts, nf) if word else None
-        return TopologyResult(totals, cls, res, sel_area, sel_atoms, sasa, res_ref, g_areas, g_atoms, iso, run, pair_areas=p_areas, pair_groups=pairs)
-    ret = L.freesasa_gpu_trajectory_groups_stats(frames.ctypes.data_as(_dp), F, C.byref(cb), structure, fa_, opt(idx, C.POINTER(C.c_int32)),
-                                                 selection.handle if selection is not None else None, opt(ids, C.POINTER(C.c_int32)), G,
-                                                 alg, probe, resolution, frames_per_batch, totals.ctypes.data_as(_dp), opt(sasa),
-                                                 opt(cls), opt(res), opt(sel_area), opt(sel_atoms, C.POINTER(C.c_longlong)), opt(g_areas),
-                                                 opt(iso), dp_, nd, word, raw.ctypes.data_as(_dp) if word else None, opt(parts), err, 512)
-    if ret:
-        raise RuntimeError("freesasa_gpu_trajectory_groups_stats: " + err.value.decode())
-    run = RunStats(raw, word, n, R, S, max(G, 0), parts, nf) if word else None
-    return TopologyResult(totals, cls, res, sel_area, sel_atoms, sasa, res_ref, g_areas, g_atoms if ids is not None else None, iso, run)
+    _traj_call(name, batch, selection, devices, device, frames=frames, n_frames=F, structure=structure, frame_atoms=fa_, atom_index=idx,
+               group=ids, n_groups=G, alg=alg, probe=probe, resolution=resolution, frames_per_batch=frames_per_batch, stats=word,
+               stats_to=raw if word else None, partials_to=parts, pairs=pairs, n_pairs=K, min_buried=float(min_buried) if with_res else 0.0, **out)
+    run = None
+    if word:
+        run = RunStats(raw, word, n, R, S, max(G, 0), parts, nf, **(dict(n_pairs=K, n_segments=NS) if with_res else {}))
+    return TopologyResult(out["totals"], out["class_sums"], out["residues"], out["sel_area"], out["sel_atoms"], out["sasa"], res_ref,
+                          out["group_areas"], g_atoms, out["isolated"], run, out["volumes"], out["masks"], out["pair_areas"], pairs,
+                          out["pair_residues"], *segments)
 
 
 def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_index=None, frame_atoms=None, selection=None,
@@ -2104,7 +2042,16 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
     pair_residues_path and / or min_buried with interface_pairs (freesasa_gpu_trajectory_file_interface_residues): pair_residues_path
     receives [F, S, 4] fp64, as trajectory_topology(interface_residues=True) gives them (traj_pair_segments says which segment is
     which); stats= then also takes "pairs" and "pair_residues", and pair_areas_path may be None; min_buried None is 0.0."""
-    L = _stats_proto(_topology_proto(lib()))
+    return _trajectory_file_topology(periodic=False, **locals())
+
+
+def _trajectory_file_topology(periodic, frames_path, batch, totals_path, structure, atom_index, frame_atoms, selection, sasa_path, class_sums_path,
+                              residues_path, selections_path, done_path, f32, header_bytes, n_frames, alg, probe, resolution, frames_per_batch,
+                              max_new_shards, device, devices, out_f32, chain_groups, separate_chains, long, group, n_groups, group_areas_path,
+                              isolated_path, dcd, pbc, triclinic, netcdf, xtc, stats, stats_path, partials_path, trr, volumes_path, masks_path,
+                              interface_pairs, pair_areas_path, pair_residues_path, min_buried):
+    """the file form of every entry with a topology, under the keywords of trajectory_file_topology: the entry by what is asked for;
+    periodic: the entries among periodic images (trajectory_file_groups_periodic)"""
     with_res = pair_residues_path is not None or min_buried is not None
     if with_res and interface_pairs is None:
         raise ValueError("pair_residues_path and min_buried need interface_pairs")
@@ -2119,113 +2066,32 @@ def trajectory_file_topology(frames_path, batch, totals_path, structure=0, atom_
                                    group_areas_path is not None or isolated_path is not None):
         raise ValueError("masks_path is not offered with chain groups, stats= or volumes_path")
     bits = _frames_bits(f32, out_f32, dcd, header_bytes, pbc, triclinic, netcdf, xtc, trr)
-    if dcd and frame_atoms is None:
-        frame_atoms = dcd_info(frames_path).n_atoms
-    if netcdf and frame_atoms is None:
-        frame_atoms = nc_info(frames_path).n_atoms
-    if xtc and frame_atoms is None:
-        frame_atoms = xtc_info(frames_path).n_atoms
-    if trr and frame_atoms is None:
-        frame_atoms = trr_info(frames_path).n_atoms
+    if frame_atoms is None:   # (a container says for itself how many atoms a frame has)
+        info = dcd_info if dcd else nc_info if netcdf else xtc_info if xtc else trr_info if trr else None
+        if info is not None:
+            frame_atoms = info(frames_path).n_atoms
     n, R, res_ref, idx, fa_ = _topology_args(batch, structure, atom_index, frame_atoms)
     S = len(selection) if selection is not None else 0
     sel_atoms = np.zeros(S, dtype=np.int64) if selection is not None else None
-    err = C.create_string_buffer(512)
     total = C.c_longlong(0)
-    enc = lambda p: None if p is None else str(p).encode()
-    keep, dp_, nd = _devs(devices, device)
-    cb = batch._as_c()
     ids, G, _ = _topology_groups(batch, structure, n, chain_groups, separate_chains, long, group, n_groups)
     pairs = _interface_pairs(interface_pairs, ids, G)
-    if pairs is not None and with_res:
-        ret = L.freesasa_gpu_trajectory_file_interface_residues(enc(frames_path), bits, header_bytes, n_frames, C.byref(cb), structure, fa_,
-                                                                None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                                selection.handle if selection is not None else None,
-                                                                ids.ctypes.data_as(C.POINTER(C.c_int32)), G,
-                                                                alg, probe, resolution, frames_per_batch, enc(totals_path), enc(sasa_path),
-                                                                enc(class_sums_path), enc(residues_path), enc(selections_path),
-                                                                None if sel_atoms is None else sel_atoms.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                                                enc(group_areas_path), enc(isolated_path),
-                                                                enc(done_path), max_new_shards, dp_, nd, C.byref(total),
-                                                                stats_word(stats, pairs=True) if stats else 0, enc(stats_path), enc(partials_path),
-                                                                pairs.ctypes.data_as(C.POINTER(C.c_int32)), pairs.shape[0], enc(pair_areas_path),
-                                                                0.0 if min_buried is None else float(min_buried), enc(pair_residues_path), err, 512)
-        if ret < 0:
-            raise RuntimeError("freesasa_gpu_trajectory_file_interface_residues: " + err.value.decode())
-        return ret == 0, int(total.value), sel_atoms
     if pairs is not None:
-        ret = L.freesasa_gpu_trajectory_file_interfaces(enc(frames_path), bits, header_bytes, n_frames, C.byref(cb), structure, fa_,
-                                                        None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                        selection.handle if selection is not None else None,
-                                                        ids.ctypes.data_as(C.POINTER(C.c_int32)), G,
-                                                        alg, probe, resolution, frames_per_batch, enc(totals_path), enc(sasa_path),
-                                                        enc(class_sums_path), enc(residues_path), enc(selections_path),
-                                                        None if sel_atoms is None else sel_atoms.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                                        enc(group_areas_path), enc(isolated_path),
-                                                        enc(done_path), max_new_shards, dp_, nd, C.byref(total), stats_word(stats) if stats else 0,
-                                                        enc(stats_path), enc(partials_path),
-                                                        pairs.ctypes.data_as(C.POINTER(C.c_int32)), pairs.shape[0], enc(pair_areas_path), err, 512)
-        if ret < 0:
-            raise RuntimeError("freesasa_gpu_trajectory_file_interfaces: " + err.value.decode())
-        return ret == 0, int(total.value), sel_atoms
-    if volumes_path is not None:
-        ret = L.freesasa_gpu_trajectory_file_volume(enc(frames_path), bits, header_bytes, n_frames, C.byref(cb), structure, fa_,
-                                                    None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                    selection.handle if selection is not None else None, alg, probe, resolution,
-                                                    frames_per_batch, enc(totals_path), enc(sasa_path), enc(class_sums_path),
-                                                    enc(residues_path), enc(selections_path),
-                                                    None if sel_atoms is None else sel_atoms.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                                    enc(volumes_path), enc(done_path), max_new_shards, dp_, nd, C.byref(total), err, 512)
-        if ret < 0:
-            raise RuntimeError("freesasa_gpu_trajectory_file_volume: " + err.value.decode())
-        return ret == 0, int(total.value), sel_atoms
-    if masks_path is not None:
-        ret = L.freesasa_gpu_trajectory_file_masks(enc(frames_path), bits, header_bytes, n_frames, C.byref(cb), structure, fa_,
-                                                   None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                   selection.handle if selection is not None else None, alg, probe, resolution,
-                                                   frames_per_batch, enc(totals_path), enc(sasa_path), enc(class_sums_path),
-                                                   enc(residues_path), enc(selections_path),
-                                                   None if sel_atoms is None else sel_atoms.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                                   enc(masks_path), enc(done_path), max_new_shards, dp_, nd, C.byref(total), err, 512)
-        if ret < 0:
-            raise RuntimeError("freesasa_gpu_trajectory_file_masks: " + err.value.decode())
-        return ret == 0, int(total.value), sel_atoms
-    if stats:
-        ret = L.freesasa_gpu_trajectory_file_groups_stats(enc(frames_path), bits, header_bytes, n_frames, C.byref(cb), structure, fa_,
-                                                          None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                          selection.handle if selection is not None else None,
-                                                          None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), G,
-                                                          alg, probe, resolution, frames_per_batch, enc(totals_path), enc(sasa_path),
-                                                          enc(class_sums_path), enc(residues_path), enc(selections_path),
-                                                          None if sel_atoms is None else sel_atoms.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                                          enc(group_areas_path), enc(isolated_path),
-                                                          enc(done_path), max_new_shards, dp_, nd, C.byref(total), stats_word(stats),
-                                                          enc(stats_path), enc(partials_path), err, 512)
-        if ret < 0:
-            raise RuntimeError("freesasa_gpu_trajectory_file_groups_stats: " + err.value.decode())
-        return ret == 0, int(total.value), sel_atoms
-    if ids is not None or group_areas_path is not None or isolated_path is not None:
-        ret = L.freesasa_gpu_trajectory_file_groups(enc(frames_path), bits, header_bytes, n_frames, C.byref(cb), structure, fa_,
-                                                    None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                    selection.handle if selection is not None else None,
-                                                    None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), G,
-                                                    alg, probe, resolution, frames_per_batch, enc(totals_path), enc(sasa_path),
-                                                    enc(class_sums_path), enc(residues_path), enc(selections_path),
-                                                    None if sel_atoms is None else sel_atoms.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                                    enc(group_areas_path), enc(isolated_path),
-                                                    enc(done_path), max_new_shards, dp_, nd, C.byref(total), err, 512)
-        if ret < 0:
-            raise RuntimeError("freesasa_gpu_trajectory_file_groups: " + err.value.decode())
-        return ret == 0, int(total.value), sel_atoms
-    ret = L.freesasa_gpu_trajectory_file_topology(enc(frames_path), bits, header_bytes, n_frames, C.byref(cb), structure, fa_,
-                                                  None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                  selection.handle if selection is not None else None, alg, probe, resolution,
-                                                  frames_per_batch, enc(totals_path), enc(sasa_path), enc(class_sums_path),
-                                                  enc(residues_path), enc(selections_path),
-                                                  None if sel_atoms is None else sel_atoms.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                                  enc(done_path), max_new_shards, dp_, nd, C.byref(total), err, 512)
-    if ret < 0:
-        raise RuntimeError("freesasa_gpu_trajectory_file_topology: " + err.value.decode())
+        name = "file_interface_residues" if with_res else "file_interfaces"
+    elif periodic:
+        name = "file_groups"
+    else:
+        name = "file_volume" if volumes_path is not None else "file_masks" if masks_path is not None else "file_groups_stats" if stats else \
+            "file_groups" if ids is not None or group_areas_path is not None or isolated_path is not None else "file_topology"
+    ret = _traj_call(name + "_periodic" * periodic, batch, selection, devices, device, frames_path=frames_path, frames_f32=bits,
+                     header_bytes=header_bytes, n_frames=n_frames, structure=structure, frame_atoms=fa_, atom_index=idx, group=ids, n_groups=G,
+                     alg=alg, probe=probe, resolution=resolution, frames_per_batch=frames_per_batch, totals=totals_path, sasa=sasa_path,
+                     class_sums=class_sums_path, residues=residues_path, sel_area=selections_path, sel_atoms=sel_atoms,
+                     group_areas=group_areas_path, isolated=isolated_path, volumes=volumes_path, masks=masks_path, done_path=done_path,
+                     max_new_shards=max_new_shards, frames_total=C.byref(total),
+                     stats=stats_word(stats, pairs=pairs is not None and with_res) if stats else 0, stats_to=stats_path, partials_to=partials_path,
+                     pairs=pairs, n_pairs=0 if pairs is None else pairs.shape[0], pair_areas=pair_areas_path,
+                     min_buried=0.0 if min_buried is None else float(min_buried), pair_residues=pair_residues_path)
     return ret == 0, int(total.value), sel_atoms
 
 
@@ -2248,62 +2114,7 @@ def trajectory_file_groups_periodic(frames_path, batch, totals_path, structure=0
     with interface_pairs (freesasa_gpu_trajectory_file_interface_residues_periodic): pair_residues_path receives [F, S, 4] fp64
     (traj_pair_segments says which segment is which); stats= then also takes "pairs" and "pair_residues", and pair_areas_path
     may be None; min_buried None is 0.0.  The argument checks are trajectory_file_topology's."""
-    L = _stats_proto(_topology_proto(lib()))
-    with_res = pair_residues_path is not None or min_buried is not None
-    if with_res and interface_pairs is None:
-        raise ValueError("pair_residues_path and min_buried need interface_pairs")
-    if not with_res and (interface_pairs is None) != (pair_areas_path is None):
-        raise ValueError("interface_pairs and pair_areas_path go together")
-    bits = _frames_bits(False, out_f32, dcd, 0, True, triclinic, netcdf, xtc, trr)
-    if frame_atoms is None:
-        info = dcd_info if dcd else nc_info if netcdf else xtc_info if xtc else trr_info if trr else None
-        if info is not None:
-            frame_atoms = info(frames_path).n_atoms
-    n, R, res_ref, idx, fa_ = _topology_args(batch, structure, atom_index, frame_atoms)
-    S = len(selection) if selection is not None else 0
-    sel_atoms = np.zeros(S, dtype=np.int64) if selection is not None else None
-    err = C.create_string_buffer(512)
-    total = C.c_longlong(0)
-    enc = lambda p: None if p is None else str(p).encode()
-    keep, dp_, nd = _devs(devices, device)
-    cb = batch._as_c()
-    ids, G, _ = _topology_groups(batch, structure, n, chain_groups, separate_chains, long, group, n_groups)
-    pairs = _interface_pairs(interface_pairs, ids, G)
-    if pairs is not None:
-        i32 = C.POINTER(C.c_int32)
-        head = (enc(frames_path), bits, 0, n_frames, C.byref(cb), structure, fa_, None if idx is None else idx.ctypes.data_as(i32),
-                selection.handle if selection is not None else None, ids.ctypes.data_as(i32), G,
-                alg, probe, resolution, frames_per_batch, enc(totals_path), enc(sasa_path),
-                enc(class_sums_path), enc(residues_path), enc(selections_path),
-                None if sel_atoms is None else sel_atoms.ctypes.data_as(C.POINTER(C.c_longlong)),
-                enc(group_areas_path), enc(isolated_path), enc(done_path), max_new_shards, dp_, nd, C.byref(total))
-        if with_res:
-            name = "freesasa_gpu_trajectory_file_interface_residues_periodic"
-            ret = L.freesasa_gpu_trajectory_file_interface_residues_periodic(
-                *head, stats_word(stats, pairs=True) if stats else 0, enc(stats_path), enc(partials_path),
-                pairs.ctypes.data_as(i32), pairs.shape[0], enc(pair_areas_path),
-                0.0 if min_buried is None else float(min_buried), enc(pair_residues_path), err, 512)
-        else:
-            name = "freesasa_gpu_trajectory_file_interfaces_periodic"
-            ret = L.freesasa_gpu_trajectory_file_interfaces_periodic(
-                *head, stats_word(stats) if stats else 0, enc(stats_path), enc(partials_path),
-                pairs.ctypes.data_as(i32), pairs.shape[0], enc(pair_areas_path), err, 512)
-        if ret < 0:
-            raise RuntimeError(name + ": " + err.value.decode())
-        return ret == 0, int(total.value), sel_atoms
-    ret = L.freesasa_gpu_trajectory_file_groups_periodic(enc(frames_path), bits, 0, n_frames, C.byref(cb), structure, fa_,
-                                                         None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                         selection.handle if selection is not None else None,
-                                                         None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), G,
-                                                         alg, probe, resolution, frames_per_batch, enc(totals_path), enc(sasa_path),
-                                                         enc(class_sums_path), enc(residues_path), enc(selections_path),
-                                                         None if sel_atoms is None else sel_atoms.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                                         enc(group_areas_path), enc(isolated_path),
-                                                         enc(done_path), max_new_shards, dp_, nd, C.byref(total), stats_word(stats) if stats else 0,
-                                                         enc(stats_path), enc(partials_path), err, 512)
-    if ret < 0:
-        raise RuntimeError("freesasa_gpu_trajectory_file_groups_periodic: " + err.value.decode())
-    return ret == 0, int(total.value), sel_atoms
+    return _trajectory_file_topology(periodic=True, f32=False, header_bytes=0, pbc=True, volumes_path=None, masks_path=None, **locals())
 
 
 def parse_files_dev(paths, ingest_options=0, n_threads=0, device=0, classifier=None):

@@ -137,20 +137,40 @@ namespace {
  * from and ONE TABLE of the per-frame outputs (TrajOut), TrajRun what the lanes of a run share, TrajLane a lane's context,
  * TrajShard the shard in its hands.  A shard goes through shard_size -> _read -> _upload -> _compute -> _download -> _write
  * -> _record (shard_run), each 0 or -1 with the context's message; traj_lane takes shards until none is left and on a
- * failure drains its stream and sets the run's first error. */
+ * failure drains its stream and sets the run's first error.  Above them, with the entry points: TrajCall, the one description of a call
+ * that every entry with a topology fills, and trajectory_call, which makes TrajTopo, TrajSpec and TrajIO of it. */
 
 /* One per-frame OUTPUT of a run: a row of TrajIO's table.  An entry point says where it goes - the caller's array or a
    result file - and everything else that is per output (opening the files, is it wanted, its place in a shard's blocks, the
    copy or the pwrite at the frame's offset, the flush, the done-list's outputs= word) is a loop over the table. */
 enum { OUT_TOTALS, OUT_SASA, OUT_ISO, OUT_MASK, OUT_CLS, OUT_RES, OUT_SEL, OUT_GRP, OUT_PAIR, OUT_PRES, OUT_VOL, N_OUT }; /* (per atom | from OUT_CLS on: the block of sums) */
-struct TrajOut {
+/* what is constant of an output: ONE table for TrajIO, for the check of a statistics word and for the done-list's first line */
+struct TrajOutDef {
     const char *name;           /* in messages: "cannot open the %s file", "could not write the %s file" */
     int bit;                    /* in the outputs= word of a done-list's first line */
-    int sbit;                   /* in the statistics word (FREESASA_GPU_STATS_*) */
+    int sbit;                   /* in the statistics word (FREESASA_GPU_STATS_*); 0: the output has no run statistics */
+    size_t esz;                 /* bytes per value */
+    /* an output of the Shrake-Rupley test points alone (the volume, the masks): what its entries say when they have nowhere to
+       put it, to Lee-Richards, to periodic images and to more test points than a cap holds (%d: the cap, the points asked for) */
+    const char *nowhere, *not_lr, *not_periodic, *too_many;
+};
+static const TrajOutDef OUT_DEF[N_OUT] = {
+    {"totals", 0, FREESASA_GPU_STATS_TOTALS, 8}, {"per-atom", 1, FREESASA_GPU_STATS_ATOMS, 8}, {"isolated", 32, FREESASA_GPU_STATS_ISOLATED, 8},
+    {"masks", 128, 0, 4, "null argument: the exposure masks have nowhere to go",
+     "the exposure masks are those of the Shrake-Rupley test points: Lee-Richards is not offered",
+     "bit 3 and bit 4 of frames_f32 (periodic images) are not offered with the exposure masks",
+     "the exposure masks are offered up to %d test points (%d asked for)"},
+    {"class-sums", 2, FREESASA_GPU_STATS_CLASSES, 8}, {"residues", 4, FREESASA_GPU_STATS_RESIDUES, 8}, {"selections", 8, FREESASA_GPU_STATS_SELECTIONS, 8},
+    {"groups", 16, FREESASA_GPU_STATS_GROUPS, 8}, {"interfaces", 256, FREESASA_GPU_STATS_PAIRS, 8}, {"interface-residues", 512, FREESASA_GPU_STATS_PAIR_RESIDUES, 8},
+    {"volumes", 64, 0, 8, "null argument: the volumes have nowhere to go",
+     "the volume is made of the Shrake-Rupley test points: Lee-Richards is not offered",
+     "bit 3 and bit 4 of frames_f32 (periodic images) are not offered with the volume: among periodic images the surface is not closed within the cell",
+     "the volume is offered up to %d test points (%d asked for)"}};
+struct TrajOut : TrajOutDef {   /* (esz of a run: 4 where the per-atom areas are asked for as fp32) */
     void *mem = nullptr;        /* the caller's array [n_frames * per_frame] ... */
     const char *path = nullptr; /* ... or a result file, */
     Fd f;                       /* open for the length of the run */
-    size_t esz = 8, per_frame = 0; /* bytes per value (4: per-atom areas asked for as fp32); (TrajRun) values per frame, 0: not computed */
+    size_t per_frame = 0;       /* (TrajRun) values per frame, 0: not computed */
     bool stat = false;          /* (TrajRun) its run statistics are asked for: computed, whether or not it is delivered ... */
     size_t s0 = 0;              /* ... and its first column of a shard's partial */
     bool wanted() const { return mem || path; }
@@ -164,11 +184,8 @@ struct TrajIO {
        that lies in one residue [4 S] (traj_pair_res) - their statistics bits are accepted by the interface-residue entries only; the volume
        entries: the frame's volume [1] (gpu_volume.hip; it has no run statistics: no bit of the statistics word); the mask entries:
        every atom's exposure mask, four uint32 words [4 n] (gpu_dots.hip; per atom, 4 bytes a value, copied as it lies; no statistics) */
-    TrajOut out[N_OUT] = {{"totals", 0, FREESASA_GPU_STATS_TOTALS}, {"per-atom", 1, FREESASA_GPU_STATS_ATOMS}, {"isolated", 32, FREESASA_GPU_STATS_ISOLATED},
-                          {"masks", 128, 0, nullptr, nullptr, Fd(), 4},
-                          {"class-sums", 2, FREESASA_GPU_STATS_CLASSES}, {"residues", 4, FREESASA_GPU_STATS_RESIDUES},
-                          {"selections", 8, FREESASA_GPU_STATS_SELECTIONS}, {"groups", 16, FREESASA_GPU_STATS_GROUPS}, {"interfaces", 256, FREESASA_GPU_STATS_PAIRS},
-                          {"interface-residues", 512, FREESASA_GPU_STATS_PAIR_RESIDUES}, {"volumes", 64, 0}};
+    TrajOut out[N_OUT];
+    TrajIO() { for (int k = 0; k < N_OUT; ++k) static_cast<TrajOutDef &>(out[k]) = OUT_DEF[k]; }
     /* run statistics (include/freesasa_gpu.h): the word; every shard's partial [4][W] at k * 4 W doubles of a host array or of
        the partials file; the merged result to the caller's array (memory form: the entry merges) or the statistics file */
     int stats = 0;
@@ -340,36 +357,19 @@ void pair_res_make(double min_buried, TrajTopo *tp)
                             tp->seg_first.data(), tp->seg_res.data(), tp->seg_side.data(), tp->seg_iso.data());
     tp->pres = true; tp->min_buried = min_buried; tp->n_seg = (int)S;
 }
-/* What the interface-residue entries refuse on top of pair_check (which they pass a place for the pair areas whether or not they
-   have one: here those may be NULL): 0, or -1 */
-int pair_res_check(const int32_t *group, int n_groups, const int32_t *pairs, int n_pairs, int frames_f32, const void *pair_out, const void *res_out,
-                   int stats, double min_buried, char *err_out, int err_len, bool periodic = false)
-{
-    if (pair_check(group, n_groups, pairs, n_pairs, frames_f32, "", err_out, err_len, periodic)) return -1;
-    if (!pair_out && !res_out && !(stats & (FREESASA_GPU_STATS_PAIRS | FREESASA_GPU_STATS_PAIR_RESIDUES)))
-        return set_err(err_out, err_len, "neither the pair areas nor the pair residues are delivered or named in the statistics word: they have nowhere to go");
-    if (!std::isfinite(min_buried)) return set_err(err_out, err_len, "min_buried must be finite");
-    return 0;
-}
-
 /* The argument checks of a statistics word, on the host: 0, or -1 with a message that names the output.  tp NULL: a run without
    a topology; has_sel, has_group: was a selection set, were group ids given?  more: the bits the entry knows beyond the
    seven (the interface-residue entries: pairs, pair residues - those runs have their pairs, so nothing is left to need) */
 int stats_check(int stats, const TrajTopo *tp, bool has_sel, bool has_group, char *err_out, int err_len, int more = 0)
 {
     if (stats & ~(127 | more)) return set_err(err_out, err_len, "unknown bit in the statistics word");
-    /* (the table's names and bits, without a TrajIO: nothing here allocates) */
-    static const char *const name[N_OUT] = {"totals", "per-atom", "isolated", "masks", "class-sums", "residues", "selections", "groups", "interfaces",
-                                            "interface-residues", "volumes"};
-    static const int sbit[N_OUT] = {FREESASA_GPU_STATS_TOTALS, FREESASA_GPU_STATS_ATOMS, FREESASA_GPU_STATS_ISOLATED, 0, FREESASA_GPU_STATS_CLASSES,
-                                    FREESASA_GPU_STATS_RESIDUES, FREESASA_GPU_STATS_SELECTIONS, FREESASA_GPU_STATS_GROUPS, 0, 0, 0};
     char msg[160];
     for (int k = 0; k < N_OUT; ++k) {
-        if (!(stats & sbit[k])) continue;
+        if (!(stats & OUT_DEF[k].sbit)) continue;
         const char *needs = (k == OUT_ISO || k == OUT_GRP) && !has_group ? "chain groups" : k >= OUT_CLS && !tp ? "a topology"
                           : k == OUT_SEL && !has_sel ? "a selection set" : nullptr;
         if (!needs) continue;
-        snprintf(msg, sizeof msg, "statistics of the %s output need %s", name[k], needs);
+        snprintf(msg, sizeof msg, "statistics of the %s output need %s", OUT_DEF[k].name, needs);
         return set_err(err_out, err_len, msg);
     }
     return 0;
@@ -969,93 +969,6 @@ extern "C" int freesasa_gpu_trajectory(const double *xyz_frames, const double *r
     return freesasa_gpu_trajectory_devices(xyz_frames, radii, n_atoms, n_frames, alg, probe, resolution, frames_per_batch, totals_out, sasa_out, &device, 1, err_out, err_len);
 }
 
-/* the memory form with a topology: with or without chain groups, statistics, the frames' volumes (the entries below) */
-static int trajectory_mem_topo(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
-                               int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
-                               const int32_t *group, int n_groups,
-                               int alg, double probe, int resolution, int frames_per_batch,
-                               double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
-                               double *sel_area_out, long long *sel_atoms_out, double *group_areas_out, double *iso_out, double *volumes_out,
-                               uint32_t *masks_out, const int *devices, int n_devices,
-                               int stats, double *stats_out, double *partials_out, char *err_out, int err_len,
-                               const int32_t *pairs = nullptr, int n_pairs = 0, double *pair_areas_out = nullptr,
-                               int more_stats = 0, double min_buried = 0, double *pair_res_out = nullptr)
-{
-    if (err_out && err_len > 0) err_out[0] = 0;
-    return guarded(err_out, err_len, [&]() -> int {
-        TrajTopo tp;
-        if (topo_make(batch, structure, frame_atoms, atom_index, sel, &tp, err_out, err_len)) return -1;
-        if (stats_check(stats, &tp, sel != nullptr, group != nullptr, err_out, err_len, more_stats)) return -1;
-        if (stats && !stats_out) return set_err(err_out, err_len, "statistics are asked for but have nowhere to go (stats_out is NULL)");
-        /* (statistics of either group output make the groups' areas wanted: their kernels run) */
-        /* (... and so do interface pairs: a row's isolated areas are the groups') */
-        if (group_make(group, n_groups, group_areas_out || pairs || (stats & (FREESASA_GPU_STATS_GROUPS | FREESASA_GPU_STATS_ISOLATED)),
-                       iso_out || (stats & FREESASA_GPU_STATS_ISOLATED), &tp, err_out, err_len)) return -1;
-        pair_make(pairs, n_pairs, &tp);
-        if (pair_res_out || (stats & FREESASA_GPU_STATS_PAIR_RESIDUES)) pair_res_make(min_buried, &tp);
-        if (!xyz_frames || !totals_out) return set_err(err_out, err_len, "null argument");
-        if ((sel_area_out || sel_atoms_out) && !sel) return set_err(err_out, err_len, "selection outputs need a selection set");
-        TrajSpec s = {tp.radii, tp.n, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, &tp};
-        if (traj_check_args(s, "n_frames must be > 0", err_out, err_len) || traj_shard_size(s, frame_atoms, err_out, err_len)) return -1;
-        TrajIO io;
-        io.src.open_memory(xyz_frames, (size_t)frame_atoms); io.sel_atoms = sel_atoms_out;
-        void *const mem[N_OUT] = {totals_out, sasa_out, iso_out, masks_out, class_sums_out, residues_out, sel_area_out, group_areas_out, pair_areas_out, pair_res_out, volumes_out};
-        for (int k = 0; k < N_OUT; ++k) io.out[k].mem = mem[k];
-        io.stats = stats;
-        return traj_run_mem(io, s, stats_out, partials_out, err_out, err_len);
-    });
-}
-
-extern "C" int freesasa_gpu_trajectory_groups_stats(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
-                                                    int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
-                                                    const int32_t *group, int n_groups,
-                                                    int alg, double probe, int resolution, int frames_per_batch,
-                                                    double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
-                                                    double *sel_area_out, long long *sel_atoms_out, double *group_areas_out, double *iso_out,
-                                                    const int *devices, int n_devices,
-                                                    int stats, double *stats_out, double *partials_out, char *err_out, int err_len)
-{
-    return trajectory_mem_topo(xyz_frames, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups, alg, probe, resolution,
-                               frames_per_batch, totals_out, sasa_out, class_sums_out, residues_out, sel_area_out, sel_atoms_out, group_areas_out, iso_out,
-                               nullptr, nullptr, devices, n_devices, stats, stats_out, partials_out, err_out, err_len);
-}
-
-/* the groups' run with the interfaces between the pairs of groups the caller names: six doubles per frame and pair */
-extern "C" int freesasa_gpu_trajectory_interfaces(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
-                                                  int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
-                                                  const int32_t *group, int n_groups,
-                                                  int alg, double probe, int resolution, int frames_per_batch,
-                                                  double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
-                                                  double *sel_area_out, long long *sel_atoms_out, double *group_areas_out, double *iso_out,
-                                                  const int *devices, int n_devices,
-                                                  int stats, double *stats_out, double *partials_out,
-                                                  const int32_t *pairs, int n_pairs, double *pair_areas_out, char *err_out, int err_len)
-{
-    if (pair_check(group, n_groups, pairs, n_pairs, 0, pair_areas_out, err_out, err_len)) return -1;
-    return trajectory_mem_topo(xyz_frames, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups, alg, probe, resolution,
-                               frames_per_batch, totals_out, sasa_out, class_sums_out, residues_out, sel_area_out, sel_atoms_out, group_areas_out, iso_out,
-                               nullptr, nullptr, devices, n_devices, stats, stats_out, partials_out, err_out, err_len, pairs, n_pairs, pair_areas_out);
-}
-
-/* ... and with the per-residue table of the interfaces, its occupancy column and the statistics of both pair outputs */
-extern "C" int freesasa_gpu_trajectory_interface_residues(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
-                                                          int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
-                                                          const int32_t *group, int n_groups,
-                                                          int alg, double probe, int resolution, int frames_per_batch,
-                                                          double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
-                                                          double *sel_area_out, long long *sel_atoms_out, double *group_areas_out, double *iso_out,
-                                                          const int *devices, int n_devices,
-                                                          int stats, double *stats_out, double *partials_out,
-                                                          const int32_t *pairs, int n_pairs, double *pair_areas_out,
-                                                          double min_buried, double *pair_res_out, char *err_out, int err_len)
-{
-    if (pair_res_check(group, n_groups, pairs, n_pairs, 0, pair_areas_out, pair_res_out, stats, min_buried, err_out, err_len)) return -1;
-    return trajectory_mem_topo(xyz_frames, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups, alg, probe, resolution,
-                               frames_per_batch, totals_out, sasa_out, class_sums_out, residues_out, sel_area_out, sel_atoms_out, group_areas_out, iso_out,
-                               nullptr, nullptr, devices, n_devices, stats, stats_out, partials_out, err_out, err_len, pairs, n_pairs, pair_areas_out,
-                               FREESASA_GPU_STATS_PAIRS | FREESASA_GPU_STATS_PAIR_RESIDUES, min_buried, pair_res_out);
-}
-
 /* the segments of such a run, on the host: the run's own checks and cuts, no device */
 extern "C" int freesasa_gpu_trajectory_interface_segments(const freesasa_ingest_batch *batch, int structure, const int32_t *group, int n_groups,
                                                           const int32_t *pairs, int n_pairs, long long seg_capacity, long long *n_segments_out,
@@ -1092,89 +1005,6 @@ extern "C" int freesasa_gpu_trajectory_interface_segments(const freesasa_ingest_
     });
 }
 
-/* what both volume entries refuse before a device is touched or a file opened: 0, or -1 with the message */
-static int volume_traj_check(int alg, int resolution, int frames_f32, const void *volumes, char *err_out, int err_len)
-{
-    if (err_out && err_len > 0) err_out[0] = 0;
-    if (!volumes) return set_err(err_out, err_len, "null argument: the volumes have nowhere to go");
-    if (alg != 1) return set_err(err_out, err_len, "the volume is made of the Shrake-Rupley test points: Lee-Richards is not offered");
-    if (frames_f32 & (FREESASA_GPU_FRAMES_PBC | FREESASA_GPU_FRAMES_TRICLINIC))
-        return set_err(err_out, err_len, "bit 3 and bit 4 of frames_f32 (periodic images) are not offered with the volume: among periodic images the surface is not closed within the cell");
-    if (resolution > SR_CAP_POINTS_MAX) {
-        char msg[120];
-        snprintf(msg, sizeof msg, "the volume is offered up to %d test points (%d asked for)", SR_CAP_POINTS_MAX, resolution);
-        return set_err(err_out, err_len, msg);
-    }
-    return 0;
-}
-
-extern "C" int freesasa_gpu_trajectory_volume(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
-                                              int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
-                                              int alg, double probe, int resolution, int frames_per_batch,
-                                              double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
-                                              double *sel_area_out, long long *sel_atoms_out, double *volumes_out,
-                                              const int *devices, int n_devices, char *err_out, int err_len)
-{
-    if (volume_traj_check(alg, resolution, 0, volumes_out, err_out, err_len)) return -1;
-    return trajectory_mem_topo(xyz_frames, n_frames, batch, structure, frame_atoms, atom_index, sel, nullptr, 0, alg, probe, resolution,
-                               frames_per_batch, totals_out, sasa_out, class_sums_out, residues_out, sel_area_out, sel_atoms_out, nullptr, nullptr,
-                               volumes_out, nullptr, devices, n_devices, 0, nullptr, nullptr, err_out, err_len);
-}
-
-/* what both mask entries refuse before a device is touched or a file opened: 0, or -1 with the message */
-static int masks_traj_check(int alg, int resolution, int frames_f32, const void *masks, char *err_out, int err_len)
-{
-    if (err_out && err_len > 0) err_out[0] = 0;
-    if (!masks) return set_err(err_out, err_len, "null argument: the exposure masks have nowhere to go");
-    if (alg != 1) return set_err(err_out, err_len, "the exposure masks are those of the Shrake-Rupley test points: Lee-Richards is not offered");
-    if (frames_f32 & (FREESASA_GPU_FRAMES_PBC | FREESASA_GPU_FRAMES_TRICLINIC))
-        return set_err(err_out, err_len, "bit 3 and bit 4 of frames_f32 (periodic images) are not offered with the exposure masks");
-    if (resolution > SR_CAP_POINTS_MAX) {
-        char msg[120];
-        snprintf(msg, sizeof msg, "the exposure masks are offered up to %d test points (%d asked for)", SR_CAP_POINTS_MAX, resolution);
-        return set_err(err_out, err_len, msg);
-    }
-    return 0;
-}
-
-extern "C" int freesasa_gpu_trajectory_masks(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
-                                             int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
-                                             int alg, double probe, int resolution, int frames_per_batch,
-                                             double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
-                                             double *sel_area_out, long long *sel_atoms_out, uint32_t *masks_out,
-                                             const int *devices, int n_devices, char *err_out, int err_len)
-{
-    if (masks_traj_check(alg, resolution, 0, masks_out, err_out, err_len)) return -1;
-    return trajectory_mem_topo(xyz_frames, n_frames, batch, structure, frame_atoms, atom_index, sel, nullptr, 0, alg, probe, resolution,
-                               frames_per_batch, totals_out, sasa_out, class_sums_out, residues_out, sel_area_out, sel_atoms_out, nullptr, nullptr,
-                               nullptr, masks_out, devices, n_devices, 0, nullptr, nullptr, err_out, err_len);
-}
-
-extern "C" int freesasa_gpu_trajectory_groups(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
-                                              int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
-                                              const int32_t *group, int n_groups,
-                                              int alg, double probe, int resolution, int frames_per_batch,
-                                              double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
-                                              double *sel_area_out, long long *sel_atoms_out, double *group_areas_out, double *iso_out,
-                                              const int *devices, int n_devices, char *err_out, int err_len)
-{
-    return freesasa_gpu_trajectory_groups_stats(xyz_frames, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups, alg, probe, resolution,
-                                                frames_per_batch, totals_out, sasa_out, class_sums_out, residues_out, sel_area_out, sel_atoms_out,
-                                                group_areas_out, iso_out, devices, n_devices, 0, nullptr, nullptr, err_out, err_len);
-}
-
-extern "C" int freesasa_gpu_trajectory_topology(const double *xyz_frames, int n_frames, const freesasa_ingest_batch *batch, int structure,
-                                                int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
-                                                int alg, double probe, int resolution, int frames_per_batch,
-                                                double *totals_out, double *sasa_out, double *class_sums_out, double *residues_out,
-                                                double *sel_area_out, long long *sel_atoms_out,
-                                                const int *devices, int n_devices, char *err_out, int err_len)
-{
-    return freesasa_gpu_trajectory_groups(xyz_frames, n_frames, batch, structure, frame_atoms, atom_index, sel, nullptr, 0, alg, probe, resolution,
-                                          frames_per_batch, totals_out, sasa_out, class_sums_out, residues_out, sel_area_out, sel_atoms_out, nullptr, nullptr,
-                                          devices, n_devices, err_out, err_len);
-}
-
 /* The first line of a trajectory file run's done-list names the run: the parameters, the frame file's size and modification
    time and a checksum of the radii - NOT the devices: a run interrupted on eight GPUs may be finished on one, with the same
    files byte for byte.  With a topology, in front of the line's end, what its outputs depend on: digests of the index, of
@@ -1200,7 +1030,7 @@ static int traj_done_head(char *head, size_t cap, const TrajSpec &s, const TrajI
             h_sel = fnv1a(prog, sizeof(freesasa_sel_word) * (size_t)n_words, fnv1a(key, sizeof key));
         }
         int outputs = 0;
-        for (const TrajOut &o : io.out) outputs |= o.path ? o.bit : 0;
+        for (int k = 0; k < N_OUT; ++k) outputs |= io.out[k].path ? OUT_DEF[k].bit : 0;
         len += snprintf(head + len - 1, cap - (size_t)len + 1, " topology frame_atoms=%d index=%016llx residues=%016llx selection=%016llx outputs=%d\n",
                         tp->frame_atoms, tp->index ? fnv1a(tp->index, 4 * (size_t)tp->n) : 0ULL, h_res, h_sel, outputs) - 1;
         /* ... and with chain groups a digest of G and the ids (a run without groups keeps the line it had) */
@@ -1324,256 +1154,6 @@ extern "C" int freesasa_gpu_trajectory_file_devices(const char *frames_path, int
                                               0, nullptr, nullptr, err_out, err_len);
 }
 
-/* the file form with a topology, with or without chain groups: both entries below */
-static int trajectory_file_topo(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
-                                const freesasa_ingest_batch *batch, int structure,
-                                int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
-                                const int32_t *group, int n_groups,
-                                int alg, double probe, int resolution, int frames_per_batch,
-                                const char *totals_path, const char *sasa_path, const char *class_sums_path,
-                                const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
-                                const char *group_areas_path, const char *iso_path, const char *volumes_path, const char *masks_path,
-                                const char *done_path, long long max_new_shards, const int *devices, int n_devices,
-                                long long *frames_total_out, int stats, const char *stats_path, const char *partials_path, char *err_out, int err_len,
-                                const int32_t *pairs = nullptr, int n_pairs = 0, const char *pair_areas_path = nullptr,
-                                int more_stats = 0, double min_buried = 0, const char *pair_res_path = nullptr)
-{
-    if (err_out && err_len > 0) err_out[0] = 0;
-    return guarded(err_out, err_len, [&]() -> int {
-        TrajTopo tp; /* (outlives the run: the lanes upload from it) */
-        if (topo_make(batch, structure, frame_atoms, atom_index, sel, &tp, err_out, err_len)) return -1;
-        if (stats_check(stats, &tp, sel != nullptr, group != nullptr, err_out, err_len, more_stats)) return -1;
-        if (group_make(group, n_groups, group_areas_path || pairs || (stats & (FREESASA_GPU_STATS_GROUPS | FREESASA_GPU_STATS_ISOLATED)),
-                       iso_path || (stats & FREESASA_GPU_STATS_ISOLATED), &tp, err_out, err_len)) return -1;
-        pair_make(pairs, n_pairs, &tp);
-        if (pair_res_path || (stats & FREESASA_GPU_STATS_PAIR_RESIDUES)) pair_res_make(min_buried, &tp);
-        if ((sel_area_path || sel_atoms_out) && !sel) return set_err(err_out, err_len, "selection outputs need a selection set");
-        TrajSpec s = {tp.radii, tp.n, n_frames, alg, probe, resolution, frames_per_batch, devices, n_devices, &tp, max_new_shards};
-        TrajIO io;
-        io.sel_atoms = sel_atoms_out;
-        const char *const path[N_OUT] = {totals_path, sasa_path, iso_path, masks_path, class_sums_path, residues_path, sel_area_path, group_areas_path, pair_areas_path, pair_res_path, volumes_path};
-        for (int k = 0; k < N_OUT; ++k) io.out[k].path = path[k];
-        io.stats = stats; io.stats_path = stats_path; io.parts_path = partials_path;
-        return trajectory_file_run(frames_path, frames_f32, header_bytes, s, io, done_path, frames_total_out, err_out, err_len);
-    });
-}
-
-extern "C" int freesasa_gpu_trajectory_file_groups_stats(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
-                                                         const freesasa_ingest_batch *batch, int structure,
-                                                         int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
-                                                         const int32_t *group, int n_groups,
-                                                         int alg, double probe, int resolution, int frames_per_batch,
-                                                         const char *totals_path, const char *sasa_path, const char *class_sums_path,
-                                                         const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
-                                                         const char *group_areas_path, const char *iso_path,
-                                                         const char *done_path, long long max_new_shards, const int *devices, int n_devices,
-                                                         long long *frames_total_out,
-                                                         int stats, const char *stats_path, const char *partials_path, char *err_out, int err_len)
-{
-    if (err_out && err_len > 0) err_out[0] = 0;
-    /* (group NULL and neither group output: the run is freesasa_gpu_trajectory_file_topology's, periodic images included) */
-    const bool with_groups = group || group_areas_path || iso_path || (stats & (FREESASA_GPU_STATS_GROUPS | FREESASA_GPU_STATS_ISOLATED));
-    if (with_groups && (frames_f32 & FREESASA_GPU_FRAMES_TRICLINIC))
-        return set_err(err_out, err_len, "bit 4 of frames_f32 (triclinic cells) is not offered with chain groups by this entry: freesasa_gpu_trajectory_file_groups_periodic is the one");
-    if (with_groups && (frames_f32 & FREESASA_GPU_FRAMES_PBC))
-        return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) is not offered with chain groups by this entry: freesasa_gpu_trajectory_file_groups_periodic is the one");
-    return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,
-                                alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
-                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
-                                frames_total_out, stats, stats_path, partials_path, err_out, err_len);
-}
-
-/* ... with the interfaces between the pairs of groups the caller names, six doubles per frame and pair into their own file */
-extern "C" int freesasa_gpu_trajectory_file_interfaces(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
-                                                       const freesasa_ingest_batch *batch, int structure,
-                                                       int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
-                                                       const int32_t *group, int n_groups,
-                                                       int alg, double probe, int resolution, int frames_per_batch,
-                                                       const char *totals_path, const char *sasa_path, const char *class_sums_path,
-                                                       const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
-                                                       const char *group_areas_path, const char *iso_path,
-                                                       const char *done_path, long long max_new_shards, const int *devices, int n_devices,
-                                                       long long *frames_total_out,
-                                                       int stats, const char *stats_path, const char *partials_path,
-                                                       const int32_t *pairs, int n_pairs, const char *pair_areas_path, char *err_out, int err_len)
-{
-    if (pair_check(group, n_groups, pairs, n_pairs, frames_f32, pair_areas_path, err_out, err_len)) return -1;
-    return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,
-                                alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
-                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
-                                frames_total_out, stats, stats_path, partials_path, err_out, err_len, pairs, n_pairs, pair_areas_path);
-}
-
-/* ... with the per-residue table of the interfaces into its own file, and the statistics of both pair outputs */
-extern "C" int freesasa_gpu_trajectory_file_interface_residues(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
-                                                               const freesasa_ingest_batch *batch, int structure,
-                                                               int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
-                                                               const int32_t *group, int n_groups,
-                                                               int alg, double probe, int resolution, int frames_per_batch,
-                                                               const char *totals_path, const char *sasa_path, const char *class_sums_path,
-                                                               const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
-                                                               const char *group_areas_path, const char *iso_path,
-                                                               const char *done_path, long long max_new_shards, const int *devices, int n_devices,
-                                                               long long *frames_total_out,
-                                                               int stats, const char *stats_path, const char *partials_path,
-                                                               const int32_t *pairs, int n_pairs, const char *pair_areas_path,
-                                                               double min_buried, const char *pair_res_path, char *err_out, int err_len)
-{
-    if (pair_res_check(group, n_groups, pairs, n_pairs, frames_f32, pair_areas_path, pair_res_path, stats, min_buried, err_out, err_len)) return -1;
-    return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,
-                                alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
-                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
-                                frames_total_out, stats, stats_path, partials_path, err_out, err_len, pairs, n_pairs, pair_areas_path,
-                                FREESASA_GPU_STATS_PAIRS | FREESASA_GPU_STATS_PAIR_RESIDUES, min_buried, pair_res_path);
-}
-
-extern "C" int freesasa_gpu_trajectory_file_groups(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
-                                                   const freesasa_ingest_batch *batch, int structure,
-                                                   int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
-                                                   const int32_t *group, int n_groups,
-                                                   int alg, double probe, int resolution, int frames_per_batch,
-                                                   const char *totals_path, const char *sasa_path, const char *class_sums_path,
-                                                   const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
-                                                   const char *group_areas_path, const char *iso_path,
-                                                   const char *done_path, long long max_new_shards, const int *devices, int n_devices,
-                                                   long long *frames_total_out, char *err_out, int err_len)
-{
-    if (err_out && err_len > 0) err_out[0] = 0;
-    if (frames_f32 & FREESASA_GPU_FRAMES_TRICLINIC)
-        return set_err(err_out, err_len, "bit 4 of frames_f32 (triclinic cells) is not offered with chain groups by this entry: freesasa_gpu_trajectory_file_groups_periodic is the one");
-    if (frames_f32 & FREESASA_GPU_FRAMES_PBC)
-        return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) is not offered with chain groups by this entry: freesasa_gpu_trajectory_file_groups_periodic is the one");
-    return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,
-                                alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
-                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
-                                frames_total_out, 0, nullptr, nullptr, err_out, err_len);
-}
-
-/* chain groups among periodic images: the groups' run with every frame - and every group of it, taken on its own - among the
-   images of the frame's cell (shard_compute: groups_periodic_stage) */
-extern "C" int freesasa_gpu_trajectory_file_groups_periodic(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
-                                                            const freesasa_ingest_batch *batch, int structure,
-                                                            int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
-                                                            const int32_t *group, int n_groups,
-                                                            int alg, double probe, int resolution, int frames_per_batch,
-                                                            const char *totals_path, const char *sasa_path, const char *class_sums_path,
-                                                            const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
-                                                            const char *group_areas_path, const char *iso_path,
-                                                            const char *done_path, long long max_new_shards, const int *devices, int n_devices,
-                                                            long long *frames_total_out,
-                                                            int stats, const char *stats_path, const char *partials_path, char *err_out, int err_len)
-{
-    if (err_out && err_len > 0) err_out[0] = 0;
-    if (!(frames_f32 & FREESASA_GPU_FRAMES_PBC))
-        return set_err(err_out, err_len, "chain groups among periodic images need bit 3 of frames_f32 (periodic images): without it the run is freesasa_gpu_trajectory_file_groups_stats's");
-    if (!group) return set_err(err_out, err_len, "chain groups among periodic images need group ids (group is NULL): without them the run is freesasa_gpu_trajectory_file_topology's");
-    return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,
-                                alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
-                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
-                                frames_total_out, stats, stats_path, partials_path, err_out, err_len);
-}
-
-/* interfaces between chain groups among periodic images: that run with, behind every frame's groups, its pair structures - each
-   in the frame's cell among its own images (shard_compute: the pair part of groups_periodic_stage's combined batch); behind the
-   stage the pairs' sums are the ones of the run without cells */
-extern "C" int freesasa_gpu_trajectory_file_interfaces_periodic(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
-                                                                const freesasa_ingest_batch *batch, int structure,
-                                                                int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
-                                                                const int32_t *group, int n_groups,
-                                                                int alg, double probe, int resolution, int frames_per_batch,
-                                                                const char *totals_path, const char *sasa_path, const char *class_sums_path,
-                                                                const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
-                                                                const char *group_areas_path, const char *iso_path,
-                                                                const char *done_path, long long max_new_shards, const int *devices, int n_devices,
-                                                                long long *frames_total_out,
-                                                                int stats, const char *stats_path, const char *partials_path,
-                                                                const int32_t *pairs, int n_pairs, const char *pair_areas_path, char *err_out, int err_len)
-{
-    if (err_out && err_len > 0) err_out[0] = 0;
-    if (!(frames_f32 & FREESASA_GPU_FRAMES_PBC))
-        return set_err(err_out, err_len, "interfaces among periodic images need bit 3 of frames_f32 (periodic images): without it the run is freesasa_gpu_trajectory_file_interfaces's");
-    if (pair_check(group, n_groups, pairs, n_pairs, frames_f32, pair_areas_path, err_out, err_len, true)) return -1;
-    return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,
-                                alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
-                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
-                                frames_total_out, stats, stats_path, partials_path, err_out, err_len, pairs, n_pairs, pair_areas_path);
-}
-
-/* ... with the per-residue table of the interfaces, read from the periodic isolated and pair areas, and the statistics of both pair outputs */
-extern "C" int freesasa_gpu_trajectory_file_interface_residues_periodic(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
-                                                                        const freesasa_ingest_batch *batch, int structure,
-                                                                        int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
-                                                                        const int32_t *group, int n_groups,
-                                                                        int alg, double probe, int resolution, int frames_per_batch,
-                                                                        const char *totals_path, const char *sasa_path, const char *class_sums_path,
-                                                                        const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
-                                                                        const char *group_areas_path, const char *iso_path,
-                                                                        const char *done_path, long long max_new_shards, const int *devices, int n_devices,
-                                                                        long long *frames_total_out,
-                                                                        int stats, const char *stats_path, const char *partials_path,
-                                                                        const int32_t *pairs, int n_pairs, const char *pair_areas_path,
-                                                                        double min_buried, const char *pair_res_path, char *err_out, int err_len)
-{
-    if (err_out && err_len > 0) err_out[0] = 0;
-    if (!(frames_f32 & FREESASA_GPU_FRAMES_PBC))
-        return set_err(err_out, err_len, "interfaces among periodic images need bit 3 of frames_f32 (periodic images): without it the run is freesasa_gpu_trajectory_file_interface_residues's");
-    if (pair_res_check(group, n_groups, pairs, n_pairs, frames_f32, pair_areas_path, pair_res_path, stats, min_buried, err_out, err_len, true)) return -1;
-    return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, group, n_groups,
-                                alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
-                                sel_area_path, sel_atoms_out, group_areas_path, iso_path, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
-                                frames_total_out, stats, stats_path, partials_path, err_out, err_len, pairs, n_pairs, pair_areas_path,
-                                FREESASA_GPU_STATS_PAIRS | FREESASA_GPU_STATS_PAIR_RESIDUES, min_buried, pair_res_path);
-}
-
-extern "C" int freesasa_gpu_trajectory_file_topology(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
-                                                     const freesasa_ingest_batch *batch, int structure,
-                                                     int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
-                                                     int alg, double probe, int resolution, int frames_per_batch,
-                                                     const char *totals_path, const char *sasa_path, const char *class_sums_path,
-                                                     const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
-                                                     const char *done_path, long long max_new_shards, const int *devices, int n_devices,
-                                                     long long *frames_total_out, char *err_out, int err_len)
-{
-    return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, nullptr, 0,
-                                alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
-                                sel_area_path, sel_atoms_out, nullptr, nullptr, nullptr, nullptr, done_path, max_new_shards, devices, n_devices,
-                                frames_total_out, 0, nullptr, nullptr, err_out, err_len);
-}
-
-extern "C" int freesasa_gpu_trajectory_file_volume(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
-                                                   const freesasa_ingest_batch *batch, int structure,
-                                                   int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
-                                                   int alg, double probe, int resolution, int frames_per_batch,
-                                                   const char *totals_path, const char *sasa_path, const char *class_sums_path,
-                                                   const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
-                                                   const char *volumes_path,
-                                                   const char *done_path, long long max_new_shards, const int *devices, int n_devices,
-                                                   long long *frames_total_out, char *err_out, int err_len)
-{
-    if (volume_traj_check(alg, resolution, frames_f32, volumes_path, err_out, err_len)) return -1;
-    return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, nullptr, 0,
-                                alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
-                                sel_area_path, sel_atoms_out, nullptr, nullptr, volumes_path, nullptr, done_path, max_new_shards, devices, n_devices,
-                                frames_total_out, 0, nullptr, nullptr, err_out, err_len);
-}
-
-extern "C" int freesasa_gpu_trajectory_file_masks(const char *frames_path, int frames_f32, long long header_bytes, long long n_frames,
-                                                  const freesasa_ingest_batch *batch, int structure,
-                                                  int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel,
-                                                  int alg, double probe, int resolution, int frames_per_batch,
-                                                  const char *totals_path, const char *sasa_path, const char *class_sums_path,
-                                                  const char *residues_path, const char *sel_area_path, long long *sel_atoms_out,
-                                                  const char *masks_path,
-                                                  const char *done_path, long long max_new_shards, const int *devices, int n_devices,
-                                                  long long *frames_total_out, char *err_out, int err_len)
-{
-    if (masks_traj_check(alg, resolution, frames_f32, masks_path, err_out, err_len)) return -1;
-    return trajectory_file_topo(frames_path, frames_f32, header_bytes, n_frames, batch, structure, frame_atoms, atom_index, sel, nullptr, 0,
-                                alg, probe, resolution, frames_per_batch, totals_path, sasa_path, class_sums_path, residues_path,
-                                sel_area_path, sel_atoms_out, nullptr, nullptr, nullptr, masks_path, done_path, max_new_shards, devices, n_devices,
-                                frames_total_out, 0, nullptr, nullptr, err_out, err_len);
-}
-
 extern "C" int freesasa_gpu_trajectory_file(const char *frames_path, int frames_f32, long long header_bytes, const double *radii,
                                             int n_atoms, long long n_frames, int alg, double probe, int resolution,
                                             int frames_per_batch, const char *totals_path, const char *sasa_path,
@@ -1583,4 +1163,295 @@ extern "C" int freesasa_gpu_trajectory_file(const char *frames_path, int frames_
     return freesasa_gpu_trajectory_file_devices(frames_path, frames_f32, header_bytes, radii, n_atoms, n_frames, alg, probe, resolution,
                                                 frames_per_batch, totals_path, sasa_path, done_path, max_new_shards, &device, 1,
                                                 frames_total_out, err_out, err_len);
+}
+
+/* ------------------------------------------------------------------ the entries with a topology */
+
+namespace {
+
+/* ONE call of any entry with a topology: what it was called with, under the names of include/freesasa_gpu.h, and the entry's own
+   rules.  A plain aggregate - nothing in it allocates -, so an entry fills it before anything is guarded; trajectory_call does
+   the rest.  The memory form fills xyz and mem[], the file form the frame file's four and path[]. */
+struct TrajCall {
+    bool file = false;              /* the file form: frames from a frame file, results to files, resumable */
+    const double *xyz = nullptr;
+    const char *frames_path = nullptr; int frames_f32 = 0; long long header_bytes = 0;
+    long long n_frames = 0;
+    const freesasa_ingest_batch *batch = nullptr; int structure = 0, frame_atoms = 0; const int32_t *atom_index = nullptr;
+    const freesasa_ingest_selection *sel = nullptr;
+    const int32_t *group = nullptr; int n_groups = 0;
+    const int32_t *pairs = nullptr; int n_pairs = 0; double min_buried = 0;
+    int alg = 0; double probe = 0; int resolution = 0, frames_per_batch = 0;
+    void *mem[N_OUT] = {};          /* where every output goes, by the table's OUT_*: the caller's array ... */
+    const char *path[N_OUT] = {};   /* ... or a result file; NULL in both: not delivered */
+    long long *sel_atoms_out = nullptr;
+    const char *done_path = nullptr; long long max_new_shards = 0;
+    const int *devices = nullptr; int n_devices = 0; long long *frames_total_out = nullptr;
+    int stats = 0; double *stats_out = nullptr, *partials_out = nullptr; const char *stats_path = nullptr, *partials_path = nullptr;
+    /* the entry's own rules */
+    int more_stats = 0;             /* the statistics bits it knows beyond the seven */
+    /* bits 3 and 4 of frames_f32, periodic images, with chain groups: fine (an entry without groups; the interface entries and
+       the outputs of the test points refuse the bits in words of their own), refused where the call has to do with groups,
+       refused whatever the call, or bit 3 REQUIRED: the entry is one among periodic images, and without the bit the run is its
+       `sibling`'s - an entry's name, for the message */
+    enum { IMAGES_FINE, IMAGES_NOT_WITH_GROUPS, IMAGES_NEVER, IMAGES_REQUIRED } images = IMAGES_FINE;
+    const char *sibling = nullptr;
+    int sr_only = -1;               /* OUT_VOL, OUT_MASK: the entry of that output of the Shrake-Rupley test points */
+    enum { NO_PAIRS, PAIRS, PAIR_RESIDUES } kind = NO_PAIRS; /* an interface entry, an interface-residue entry */
+    const void *to(int k) const { return mem[k] ? mem[k] : path[k]; }
+};
+
+/* what an entry refuses by its own rules, before everything else: 0, or -1 with the message */
+int traj_call_rules(const TrajCall &a, char *err_out, int err_len)
+{
+    char msg[200];
+    const bool periodic = a.images == TrajCall::IMAGES_REQUIRED;
+    if (periodic && !(a.frames_f32 & FREESASA_GPU_FRAMES_PBC)) {
+        snprintf(msg, sizeof msg, "%s among periodic images need bit 3 of frames_f32 (periodic images): without it the run is %s's",
+                 a.kind ? "interfaces" : "chain groups", a.sibling);
+        return set_err(err_out, err_len, msg);
+    }
+    if (periodic && !a.kind && !a.group)
+        return set_err(err_out, err_len, "chain groups among periodic images need group ids (group is NULL): without them the run is freesasa_gpu_trajectory_file_topology's");
+    /* (group NULL and neither group output: the run is freesasa_gpu_trajectory_file_topology's, periodic images included) */
+    const bool with_groups = a.group || a.to(OUT_GRP) || a.to(OUT_ISO) || (a.stats & (FREESASA_GPU_STATS_GROUPS | FREESASA_GPU_STATS_ISOLATED));
+    if (a.images == TrajCall::IMAGES_NEVER || (a.images == TrajCall::IMAGES_NOT_WITH_GROUPS && with_groups)) {
+        if (a.frames_f32 & FREESASA_GPU_FRAMES_TRICLINIC)
+            return set_err(err_out, err_len, "bit 4 of frames_f32 (triclinic cells) is not offered with chain groups by this entry: freesasa_gpu_trajectory_file_groups_periodic is the one");
+        if (a.frames_f32 & FREESASA_GPU_FRAMES_PBC)
+            return set_err(err_out, err_len, "bit 3 of frames_f32 (periodic images) is not offered with chain groups by this entry: freesasa_gpu_trajectory_file_groups_periodic is the one");
+    }
+    if (a.kind) {
+        /* (the interface-residue entries may have no place for the pair areas: they ask below for either output) */
+        if (pair_check(a.group, a.n_groups, a.pairs, a.n_pairs, a.frames_f32, a.kind == TrajCall::PAIR_RESIDUES ? "" : a.to(OUT_PAIR), err_out, err_len, periodic)) return -1;
+        if (a.kind == TrajCall::PAIRS) return 0;
+        if (!a.to(OUT_PAIR) && !a.to(OUT_PRES) && !(a.stats & (FREESASA_GPU_STATS_PAIRS | FREESASA_GPU_STATS_PAIR_RESIDUES)))
+            return set_err(err_out, err_len, "neither the pair areas nor the pair residues are delivered or named in the statistics word: they have nowhere to go");
+        if (!std::isfinite(a.min_buried)) return set_err(err_out, err_len, "min_buried must be finite");
+    }
+    if (a.sr_only >= 0) { /* the volume, the masks: in the output's words */
+        const TrajOutDef &o = OUT_DEF[a.sr_only];
+        if (!a.to(a.sr_only)) return set_err(err_out, err_len, o.nowhere);
+        if (a.alg != 1) return set_err(err_out, err_len, o.not_lr);
+        if (a.frames_f32 & (FREESASA_GPU_FRAMES_PBC | FREESASA_GPU_FRAMES_TRICLINIC)) return set_err(err_out, err_len, o.not_periodic);
+        if (a.resolution > SR_CAP_POINTS_MAX) {
+            snprintf(msg, sizeof msg, o.too_many, SR_CAP_POINTS_MAX, a.resolution);
+            return set_err(err_out, err_len, msg);
+        }
+    }
+    return 0;
+}
+
+/* The run of a TrajCall, either form: the entry's rules, the topology with its groups and pairs (TrajTopo outlives the run: the
+   lanes upload from it), TrajSpec and TrajIO, and then the memory form's run or the file form's.  The order of the checks is
+   interface, and the two forms differ in it: the memory form asks for stats_out behind the statistics word and for the frames
+   and the totals behind the pairs; the file form leaves its paths, header_bytes and the format to trajectory_file_run. */
+int trajectory_call(const TrajCall &a, char *err_out, int err_len)
+{
+    if (err_out && err_len > 0) err_out[0] = 0;
+    if (traj_call_rules(a, err_out, err_len)) return -1;
+    return guarded(err_out, err_len, [&]() -> int {
+        TrajTopo tp;
+        if (topo_make(a.batch, a.structure, a.frame_atoms, a.atom_index, a.sel, &tp, err_out, err_len)) return -1;
+        if (stats_check(a.stats, &tp, a.sel != nullptr, a.group != nullptr, err_out, err_len, a.more_stats)) return -1;
+        if (!a.file && a.stats && !a.stats_out) return set_err(err_out, err_len, "statistics are asked for but have nowhere to go (stats_out is NULL)");
+        /* (statistics of either group output make the groups' areas wanted: their kernels run) */
+        /* (... and so do interface pairs: a row's isolated areas are the groups') */
+        if (group_make(a.group, a.n_groups, a.to(OUT_GRP) || a.pairs || (a.stats & (FREESASA_GPU_STATS_GROUPS | FREESASA_GPU_STATS_ISOLATED)),
+                       a.to(OUT_ISO) || (a.stats & FREESASA_GPU_STATS_ISOLATED), &tp, err_out, err_len)) return -1;
+        pair_make(a.pairs, a.n_pairs, &tp);
+        if (a.to(OUT_PRES) || (a.stats & FREESASA_GPU_STATS_PAIR_RESIDUES)) pair_res_make(a.min_buried, &tp);
+        if (!a.file && (!a.xyz || !a.mem[OUT_TOTALS])) return set_err(err_out, err_len, "null argument");
+        if ((a.to(OUT_SEL) || a.sel_atoms_out) && !a.sel) return set_err(err_out, err_len, "selection outputs need a selection set");
+        TrajSpec s = {tp.radii, tp.n, a.n_frames, a.alg, a.probe, a.resolution, a.frames_per_batch, a.devices, a.n_devices, &tp, a.max_new_shards};
+        TrajIO io;
+        for (int k = 0; k < N_OUT; ++k) { io.out[k].mem = a.mem[k]; io.out[k].path = a.path[k]; }
+        io.sel_atoms = a.sel_atoms_out; io.stats = a.stats; io.stats_path = a.stats_path; io.parts_path = a.partials_path;
+        if (a.file) return trajectory_file_run(a.frames_path, a.frames_f32, a.header_bytes, s, io, a.done_path, a.frames_total_out, err_out, err_len);
+        if (traj_check_args(s, "n_frames must be > 0", err_out, err_len) || traj_shard_size(s, a.frame_atoms, err_out, err_len)) return -1;
+        io.src.open_memory(a.xyz, (size_t)a.frame_atoms);
+        return traj_run_mem(io, s, a.stats_out, a.partials_out, err_out, err_len);
+    });
+}
+
+} /* namespace */
+
+/* The entries, from PIECES: a piece is a run of arguments that every entry which has it has under the same names
+   (include/freesasa_gpu.h spells the prototypes out, and a definition here that differs from its prototype does not compile), once
+   as the parameters, P_, and once as their way into the TrajCall, TC_ - by name, so an argument cannot end up in another one's
+   field.  An output is `x_out`, an array, in the memory form and `x_path` in the file form: sfx is `out` or `path`. */
+#define T_out double *
+#define T_path const char *
+#define TO_out mem
+#define TO_path path
+#define P_MEMORY const double *xyz_frames, int n_frames
+#define TC_MEMORY a.xyz = xyz_frames; a.n_frames = n_frames
+#define P_FILE const char *frames_path, int frames_f32, long long header_bytes, long long n_frames
+#define TC_FILE a.file = true; a.frames_path = frames_path; a.frames_f32 = frames_f32; a.header_bytes = header_bytes; a.n_frames = n_frames
+#define P_TOPOLOGY const freesasa_ingest_batch *batch, int structure, int frame_atoms, const int32_t *atom_index, const freesasa_ingest_selection *sel
+#define TC_TOPOLOGY a.batch = batch; a.structure = structure; a.frame_atoms = frame_atoms; a.atom_index = atom_index; a.sel = sel
+#define P_GROUPS const int32_t *group, int n_groups
+#define TC_GROUPS a.group = group; a.n_groups = n_groups
+#define P_PARAMETERS int alg, double probe, int resolution, int frames_per_batch
+#define TC_PARAMETERS a.alg = alg; a.probe = probe; a.resolution = resolution; a.frames_per_batch = frames_per_batch
+#define P_OUTPUTS(sfx) T_##sfx totals_##sfx, T_##sfx sasa_##sfx, T_##sfx class_sums_##sfx, T_##sfx residues_##sfx, T_##sfx sel_area_##sfx, long long *sel_atoms_out
+#define TC_OUTPUTS(sfx) \
+    a.TO_##sfx[OUT_TOTALS] = totals_##sfx; a.TO_##sfx[OUT_SASA] = sasa_##sfx; a.TO_##sfx[OUT_CLS] = class_sums_##sfx; a.TO_##sfx[OUT_RES] = residues_##sfx; \
+    a.TO_##sfx[OUT_SEL] = sel_area_##sfx; a.sel_atoms_out = sel_atoms_out
+#define P_GROUP_OUTPUTS(sfx) T_##sfx group_areas_##sfx, T_##sfx iso_##sfx
+#define TC_GROUP_OUTPUTS(sfx) a.TO_##sfx[OUT_GRP] = group_areas_##sfx; a.TO_##sfx[OUT_ISO] = iso_##sfx
+#define P_DEVICES const int *devices, int n_devices
+#define TC_DEVICES a.devices = devices; a.n_devices = n_devices
+#define P_FILE_TAIL const char *done_path, long long max_new_shards, P_DEVICES, long long *frames_total_out
+#define TC_FILE_TAIL a.done_path = done_path; a.max_new_shards = max_new_shards; TC_DEVICES; a.frames_total_out = frames_total_out
+#define P_STATISTICS(sfx) int stats, T_##sfx stats_##sfx, T_##sfx partials_##sfx
+#define TC_STATISTICS(sfx) a.stats = stats; a.stats_##sfx = stats_##sfx; a.partials_##sfx = partials_##sfx
+#define P_PAIRS(sfx) const int32_t *pairs, int n_pairs, T_##sfx pair_areas_##sfx
+#define TC_PAIRS(sfx) a.kind = TrajCall::PAIRS; a.pairs = pairs; a.n_pairs = n_pairs; a.TO_##sfx[OUT_PAIR] = pair_areas_##sfx
+#define P_PAIR_RESIDUES(sfx) double min_buried, T_##sfx pair_res_##sfx
+#define TC_PAIR_RESIDUES(sfx) \
+    a.kind = TrajCall::PAIR_RESIDUES; a.more_stats = FREESASA_GPU_STATS_PAIRS | FREESASA_GPU_STATS_PAIR_RESIDUES; a.min_buried = min_buried; \
+    a.TO_##sfx[OUT_PRES] = pair_res_##sfx
+#define P_ERR char *err_out, int err_len
+/* an entry without groups: the memory form (..., the output of its own, if any, ...) and the file form */
+#define P_MEMORY_PLAIN(...) P_MEMORY, P_TOPOLOGY, P_PARAMETERS, P_OUTPUTS(out), ##__VA_ARGS__, P_DEVICES, P_ERR
+#define TC_MEMORY_PLAIN TC_MEMORY; TC_TOPOLOGY; TC_PARAMETERS; TC_OUTPUTS(out); TC_DEVICES
+#define P_FILE_PLAIN(...) P_FILE, P_TOPOLOGY, P_PARAMETERS, P_OUTPUTS(path), ##__VA_ARGS__, P_FILE_TAIL, P_ERR
+#define TC_FILE_PLAIN TC_FILE; TC_TOPOLOGY; TC_PARAMETERS; TC_OUTPUTS(path); TC_FILE_TAIL
+/* an entry with groups: behind the tail its statistics, pairs and pair residues, if any */
+#define P_MEMORY_GROUPS P_MEMORY, P_TOPOLOGY, P_GROUPS, P_PARAMETERS, P_OUTPUTS(out), P_GROUP_OUTPUTS(out), P_DEVICES
+#define TC_MEMORY_GROUPS TC_MEMORY; TC_TOPOLOGY; TC_GROUPS; TC_PARAMETERS; TC_OUTPUTS(out); TC_GROUP_OUTPUTS(out); TC_DEVICES
+#define P_FILE_GROUPS P_FILE, P_TOPOLOGY, P_GROUPS, P_PARAMETERS, P_OUTPUTS(path), P_GROUP_OUTPUTS(path), P_FILE_TAIL
+#define TC_FILE_GROUPS TC_FILE; TC_TOPOLOGY; TC_GROUPS; TC_PARAMETERS; TC_OUTPUTS(path); TC_GROUP_OUTPUTS(path); TC_FILE_TAIL
+
+extern "C" int freesasa_gpu_trajectory_topology(P_MEMORY_PLAIN())
+{
+    TrajCall a;
+    TC_MEMORY_PLAIN;
+    return trajectory_call(a, err_out, err_len);
+}
+
+extern "C" int freesasa_gpu_trajectory_volume(P_MEMORY_PLAIN(double *volumes_out))
+{
+    TrajCall a;
+    TC_MEMORY_PLAIN; a.mem[OUT_VOL] = volumes_out; a.sr_only = OUT_VOL;
+    return trajectory_call(a, err_out, err_len);
+}
+
+extern "C" int freesasa_gpu_trajectory_masks(P_MEMORY_PLAIN(uint32_t *masks_out))
+{
+    TrajCall a;
+    TC_MEMORY_PLAIN; a.mem[OUT_MASK] = masks_out; a.sr_only = OUT_MASK;
+    return trajectory_call(a, err_out, err_len);
+}
+
+extern "C" int freesasa_gpu_trajectory_groups(P_MEMORY_GROUPS, P_ERR)
+{
+    TrajCall a;
+    TC_MEMORY_GROUPS;
+    return trajectory_call(a, err_out, err_len);
+}
+
+extern "C" int freesasa_gpu_trajectory_groups_stats(P_MEMORY_GROUPS, P_STATISTICS(out), P_ERR)
+{
+    TrajCall a;
+    TC_MEMORY_GROUPS; TC_STATISTICS(out);
+    return trajectory_call(a, err_out, err_len);
+}
+
+/* the groups' run with the interfaces between the pairs of groups the caller names: six doubles per frame and pair */
+extern "C" int freesasa_gpu_trajectory_interfaces(P_MEMORY_GROUPS, P_STATISTICS(out), P_PAIRS(out), P_ERR)
+{
+    TrajCall a;
+    TC_MEMORY_GROUPS; TC_STATISTICS(out); TC_PAIRS(out);
+    return trajectory_call(a, err_out, err_len);
+}
+
+/* ... and with the per-residue table of the interfaces, its occupancy column and the statistics of both pair outputs */
+extern "C" int freesasa_gpu_trajectory_interface_residues(P_MEMORY_GROUPS, P_STATISTICS(out), P_PAIRS(out), P_PAIR_RESIDUES(out), P_ERR)
+{
+    TrajCall a;
+    TC_MEMORY_GROUPS; TC_STATISTICS(out); TC_PAIRS(out); TC_PAIR_RESIDUES(out);
+    return trajectory_call(a, err_out, err_len);
+}
+
+extern "C" int freesasa_gpu_trajectory_file_topology(P_FILE_PLAIN())
+{
+    TrajCall a;
+    TC_FILE_PLAIN;
+    return trajectory_call(a, err_out, err_len);
+}
+
+extern "C" int freesasa_gpu_trajectory_file_volume(P_FILE_PLAIN(const char *volumes_path))
+{
+    TrajCall a;
+    TC_FILE_PLAIN; a.path[OUT_VOL] = volumes_path; a.sr_only = OUT_VOL;
+    return trajectory_call(a, err_out, err_len);
+}
+
+extern "C" int freesasa_gpu_trajectory_file_masks(P_FILE_PLAIN(const char *masks_path))
+{
+    TrajCall a;
+    TC_FILE_PLAIN; a.path[OUT_MASK] = masks_path; a.sr_only = OUT_MASK;
+    return trajectory_call(a, err_out, err_len);
+}
+
+extern "C" int freesasa_gpu_trajectory_file_groups(P_FILE_GROUPS, P_ERR)
+{
+    TrajCall a;
+    TC_FILE_GROUPS; a.images = TrajCall::IMAGES_NEVER;
+    return trajectory_call(a, err_out, err_len);
+}
+
+extern "C" int freesasa_gpu_trajectory_file_groups_stats(P_FILE_GROUPS, P_STATISTICS(path), P_ERR)
+{
+    TrajCall a;
+    TC_FILE_GROUPS; TC_STATISTICS(path); a.images = TrajCall::IMAGES_NOT_WITH_GROUPS;
+    return trajectory_call(a, err_out, err_len);
+}
+
+/* ... with the interfaces between the pairs of groups the caller names, six doubles per frame and pair into their own file */
+extern "C" int freesasa_gpu_trajectory_file_interfaces(P_FILE_GROUPS, P_STATISTICS(path), P_PAIRS(path), P_ERR)
+{
+    TrajCall a;
+    TC_FILE_GROUPS; TC_STATISTICS(path); TC_PAIRS(path);
+    return trajectory_call(a, err_out, err_len);
+}
+
+/* ... with the per-residue table of the interfaces into its own file, and the statistics of both pair outputs */
+extern "C" int freesasa_gpu_trajectory_file_interface_residues(P_FILE_GROUPS, P_STATISTICS(path), P_PAIRS(path), P_PAIR_RESIDUES(path), P_ERR)
+{
+    TrajCall a;
+    TC_FILE_GROUPS; TC_STATISTICS(path); TC_PAIRS(path); TC_PAIR_RESIDUES(path);
+    return trajectory_call(a, err_out, err_len);
+}
+
+/* chain groups among periodic images: the groups' run with every frame - and every group of it, taken on its own - among the
+   images of the frame's cell (shard_compute: groups_periodic_stage) */
+extern "C" int freesasa_gpu_trajectory_file_groups_periodic(P_FILE_GROUPS, P_STATISTICS(path), P_ERR)
+{
+    TrajCall a;
+    TC_FILE_GROUPS; TC_STATISTICS(path);
+    a.images = TrajCall::IMAGES_REQUIRED; a.sibling = "freesasa_gpu_trajectory_file_groups_stats";
+    return trajectory_call(a, err_out, err_len);
+}
+
+/* interfaces between chain groups among periodic images: that run with, behind every frame's groups, its pair structures - each
+   in the frame's cell among its own images (shard_compute: the pair part of groups_periodic_stage's combined batch); behind the
+   stage the pairs' sums are the ones of the run without cells */
+extern "C" int freesasa_gpu_trajectory_file_interfaces_periodic(P_FILE_GROUPS, P_STATISTICS(path), P_PAIRS(path), P_ERR)
+{
+    TrajCall a;
+    TC_FILE_GROUPS; TC_STATISTICS(path); TC_PAIRS(path);
+    a.images = TrajCall::IMAGES_REQUIRED; a.sibling = "freesasa_gpu_trajectory_file_interfaces";
+    return trajectory_call(a, err_out, err_len);
+}
+
+/* ... with the per-residue table of the interfaces, read from the periodic isolated and pair areas, and the statistics of both pair outputs */
+extern "C" int freesasa_gpu_trajectory_file_interface_residues_periodic(P_FILE_GROUPS, P_STATISTICS(path), P_PAIRS(path), P_PAIR_RESIDUES(path), P_ERR)
+{
+    TrajCall a;
+    TC_FILE_GROUPS; TC_STATISTICS(path); TC_PAIRS(path); TC_PAIR_RESIDUES(path);
+    a.images = TrajCall::IMAGES_REQUIRED; a.sibling = "freesasa_gpu_trajectory_file_interface_residues";
+    return trajectory_call(a, err_out, err_len);
 }
